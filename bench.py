@@ -14,10 +14,22 @@ chain.get_counts(ga)`` does in the reference.  Headline workload = BASELINE.json
 ``configs[1]`` (C2): 100 M single-end reads, FivePrimeMapFactory(offset=12),
 20 k yeast-scale transcripts, one MI355X.
 
-N = 1 (default): after the headline, the same process runs the other GPU configs
-of BASELINE.json -- C3 (center rule), whole C4 and whole C5 (they fit one GPU) --
-each parity-gated against the oracle on a seeded sample of chains; their numbers
-go to ``config.other_configs`` (``--other-configs none`` skips them).
+A plain run does only what the headline figure needs: it generates and stages the
+inputs, builds the plan, warms up, times the ``--steps`` steps and prints the
+result line (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step``).  ``--dump-outputs DIR`` then also writes the counts of the last
+timed step as float64 ``.npy`` files (see ``dump_outputs``); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
+
+``--full`` adds everything else, as described below: the oracle parity gates, the
+CPU baseline, per-kernel timing and roofline, the size-filter and two-file
+variants, the stream probe, the single-query and e2e scopes, the other configs
+and ``bench_detail.json``.
+
+N = 1 (default), ``--full``: after the headline, the same process runs the other
+GPU configs of BASELINE.json -- C3 (center rule), whole C4 and whole C5 (they fit
+one GPU) -- each parity-gated against the oracle on a seeded sample of chains;
+their numbers go to ``config.other_configs`` (``--other-configs none`` skips them).
 
 N > 1: ONE job over N GPUs (``--partition genome``, strong scaling): the genome
 is cut at quantiles of the expected record density (``synth.JobLayout.cuts``,
@@ -29,9 +41,9 @@ is followed by C4 and C5, partitioned the same way (``config.other_configs``).
 ``--partition replicas`` gives every rank an independent shard of the same
 shape instead (weak scaling).
 
-Before anything is timed the GPU output is compared bit-for-bit with the oracle
-(``oracle/``) on a seeded sample of chains, and again after the timed steps; a
-mismatch aborts the run.
+With ``--full``, before anything is timed the GPU output is compared bit-for-bit
+with the oracle (``oracle/``) on a seeded sample of chains, and again after the
+timed steps; a mismatch aborts the run.
 """
 import argparse
 import gc
@@ -264,6 +276,29 @@ def load_traffic(config, n_records):
     return None, None
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs: data bytes of all files together (the limit is 64 MB, .npy headers included)
+DUMP_SEED = 20261016      # the positions of a sampled dump
+
+
+def dump_outputs(out_dir, counts, tag="", budget=DUMP_BYTES):
+    """``--dump-outputs``: the count vector of the last timed step, as ``plan.read()`` hands it to a caller, written as
+    float64 ``.npy`` files under `out_dir` (int64 counts are exact in float64).  A vector that fits in `budget` is written
+    whole (``counts<tag>.npy``).  A larger one is written as its elements at a fixed, seeded sample of positions
+    (``counts_sample<tag>.npy``, positions in increasing order) and as the sums of consecutive equal blocks of the whole
+    vector (``counts_block_sums<tag>.npy``), so that every element enters the comparison."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(counts.size)
+    if n * 8 <= budget:
+        np.save(os.path.join(out_dir, "counts%s.npy" % tag), counts.astype(np.float64))
+        return
+    rng = np.random.default_rng(DUMP_SEED)
+    pos = np.unique(rng.integers(0, n, size=budget * 3 // 4 // 8))
+    np.save(os.path.join(out_dir, "counts_sample%s.npy" % tag), counts[pos].astype(np.float64))
+    block = -(-n // (budget // 4 // 8))
+    sums = np.add.reduceat(counts, np.arange(0, n, block, dtype=np.int64))
+    np.save(os.path.join(out_dir, "counts_block_sums%s.npy" % tag), sums.astype(np.float64))
+
+
 def peak_rss_mb():
     import resource
     return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
@@ -283,6 +318,23 @@ def engine_class():
     return Engine, False
 
 
+def headline_result(name, args, tx, mapping, out_dtype, plan, rows, n_local, n_records_all, positions_all, elapsed, steps,
+                    warmup, gen_s, stage_s, plan_s):
+    """The result of a plain run's config (no --full): the timed steps and what describes the workload."""
+    return {
+        "workload": WORKLOAD_TEXT[name] + ("" if args.scale == 1.0 else " [scaled x%g]" % args.scale),
+        "value": n_records_all * steps / elapsed, "ms_per_step": elapsed / steps * 1e3, "steps": steps, "warmup": warmup,
+        "dtype": "float64" if out_dtype == np.float64 else "int64",
+        "records_per_gpu": n_local, "records_total": int(n_records_all),
+        "chains": int(tx.n), "segments": int(tx.n_segments), "output_positions_per_gpu": int(plan.out_elems),
+        "island_positions": int(plan.positions), "tiles": int(plan.tiles), "rows": rows,
+        "mapping": [str(x) for x in mapping], "read_seed": synth.CONFIGS[name][5], "transcript_seed": synth.CONFIGS[name][3],
+        "positions_per_sec": positions_all * steps / elapsed,
+        "host_generate_s": round(gen_s, 2), "host_stage_s": round(stage_s, 3),
+        "plan_build_ms_once_per_annotation": round(plan_s * 1e3, 2),
+    }
+
+
 def run_workload(name, args, ctx, headline):
     """One BASELINE config through the hot path.  Returns the result dict of that config."""
     from oracle import oracle
@@ -295,6 +347,7 @@ def run_workload(name, args, ctx, headline):
     warmup = max(args.warmup, 1) if headline else 2
     scale = args.scale
     tx_scale = args.tx_scale
+    full = args.full
 
     # ---------------------------------------------------------------- inputs (host)
     t0 = time.perf_counter()
@@ -308,44 +361,47 @@ def run_workload(name, args, ctx, headline):
     p = tx.plan_arrays(rows=rows)
     n_job = int(reads.n)                      # records of the whole job this rank belongs to
 
-    # ---------------------------------------------------------------- oracle: CPU baseline and parity sample
+    # ---------------------------------------------------------------- oracle: CPU baseline and parity sample (--full)
     cpu = None
-    aln = concat_file_major([reads])
-    spec = oracle_spec(oracle, mapping)
-    rng = np.random.default_rng(7 + (rank if partition == "replicas" else 0))
-    t0 = time.perf_counter()
-    prep = oracle.Prepared(aln)          # per-record arrays of the oracle, derived once (its "open the BAM file")
-    t_prep = time.perf_counter() - t0
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        # (beside every config: the other configs get ~6 s per figure so that the default run stays within minutes)
-        budget = args.cpu_budget if headline else min(args.cpu_budget, 6.0)
-        cpu, check_sel, check_arrays, _ = cpu_baseline(oracle, prep, t_prep, spec, p, tx, reads.n, budget, rng)
-        cpu["cpu_model"] = cpu_model()
-        cpu["host_cores"] = os.cpu_count()
-        cpu["usable_cores"] = usable_cpus()
-    else:
-        chains = rng.permutation(tx.n)[:min(tx.n, args.parity_chains)]
-        check_sel = segments_of_chains(tx, chains)
-        check_arrays, _ = oracle.count_segments(prep, spec, p["tid"][check_sel], p["start"][check_sel],
-                                                p["end"][check_sel], p["strand"][check_sel], threads=usable_cpus())
-    # the SizeFilterFactory(25,100) variant is gated on a small sample of its own
-    sf_chains = np.random.default_rng(9).permutation(tx.n)[:min(tx.n, 200)]
-    sf_sel = segments_of_chains(tx, sf_chains)
-    sf_arrays, _ = oracle.count_segments(prep, oracle_spec(oracle, mapping, SIZE_FILTER), p["tid"][sf_sel], p["start"][sf_sel],
-                                         p["end"][sf_sel], p["strand"][sf_sel], threads=usable_cpus())
-    prep.close()
-    del aln, prep
-    exp = sparse_expected(check_arrays, p, check_sel, rows)        # (element indices, values) of the sampled chains
-    sf_exp = sparse_expected(sf_arrays, p, sf_sel, rows)
-    del check_arrays, sf_arrays
+    if full:
+        aln = concat_file_major([reads])
+        spec = oracle_spec(oracle, mapping)
+        rng = np.random.default_rng(7 + (rank if partition == "replicas" else 0))
+        t0 = time.perf_counter()
+        prep = oracle.Prepared(aln)          # per-record arrays of the oracle, derived once (its "open the BAM file")
+        t_prep = time.perf_counter() - t0
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            # (beside every config: the other configs get ~6 s per figure so that the default run stays within minutes)
+            budget = args.cpu_budget if headline else min(args.cpu_budget, 6.0)
+            cpu, check_sel, check_arrays, _ = cpu_baseline(oracle, prep, t_prep, spec, p, tx, reads.n, budget, rng)
+            cpu["cpu_model"] = cpu_model()
+            cpu["host_cores"] = os.cpu_count()
+            cpu["usable_cores"] = usable_cpus()
+        else:
+            chains = rng.permutation(tx.n)[:min(tx.n, args.parity_chains)]
+            check_sel = segments_of_chains(tx, chains)
+            check_arrays, _ = oracle.count_segments(prep, spec, p["tid"][check_sel], p["start"][check_sel],
+                                                    p["end"][check_sel], p["strand"][check_sel], threads=usable_cpus())
+        # the SizeFilterFactory(25,100) variant is gated on a small sample of its own
+        sf_chains = np.random.default_rng(9).permutation(tx.n)[:min(tx.n, 200)]
+        sf_sel = segments_of_chains(tx, sf_chains)
+        sf_arrays, _ = oracle.count_segments(prep, oracle_spec(oracle, mapping, SIZE_FILTER), p["tid"][sf_sel], p["start"][sf_sel],
+                                             p["end"][sf_sel], p["strand"][sf_sel], threads=usable_cpus())
+        prep.close()
+        del aln, prep
+        exp = sparse_expected(check_arrays, p, check_sel, rows)        # (element indices, values) of the sampled chains
+        sf_exp = sparse_expected(sf_arrays, p, sf_sel, rows)
+        del check_arrays, sf_arrays
 
     my_reads, lp = reads, p     # (N > 1 here means independent replicas; the one-job mode is run_partitioned)
 
     # ---------------------------------------------------------------- GPU
     import torch
-    warm_runtime(ctx)
+    if full:
+        warm_runtime(ctx)
     eng = Engine(ctx["dev_index"])
-    time.sleep(0.3)   # the all-cores CPU baseline just burnt the cgroup's CPU quota (CFS, 100 ms periods): staging is a host pass
+    if full:
+        time.sleep(0.3)   # the all-cores CPU baseline just burnt the cgroup's CPU quota (CFS, 100 ms periods): staging is a host pass
     t0 = time.perf_counter()
     eng.set_alignments([my_reads])
     stage_s = time.perf_counter() - t0
@@ -357,10 +413,12 @@ def run_workload(name, args, ctx, headline):
 
     # host side of the read-back: page-locked memory from the engine itself (pc_host_alloc: what a caller that reads
     # repeatedly hands over); above 16 GiB ordinary pageable memory, which goes down through the transfer ring
-    if int(lp["out_elems"]) * 8 <= (16 << 30) and hasattr(eng, "host_buffer"):
+    # (--full only: a plain run reads nothing back but what --dump-outputs writes)
+    out_buf = None
+    if full and int(lp["out_elems"]) * 8 <= (16 << 30) and hasattr(eng, "host_buffer"):
         out_buf = eng.host_buffer(int(lp["out_elems"]), out_dtype)
         out_buf[:] = 0
-    else:
+    elif full:
         out_buf = np.zeros(int(lp["out_elems"]), out_dtype)
 
     def gate(expected, what):
@@ -371,20 +429,22 @@ def run_workload(name, args, ctx, headline):
             raise SystemExit("PARITY FAILURE (%s, %s): HIP counts differ from the oracle on the sampled chains" % (name, what))
         return len(e_idx)
 
-    plan.close()
-    plan, first_count_ms = first_count_of_fresh_plans(eng, lambda: eng.plan(lp["tid"], lp["start"], lp["end"], lp["strand"], lp["out_off"], lp["out_step"],
-                                                                             lp["row_stride"], lp["out_elems"], rows), out_dtype)
+    if full:
+        plan.close()
+        plan, first_count_ms = first_count_of_fresh_plans(eng, lambda: eng.plan(lp["tid"], lp["start"], lp["end"], lp["strand"], lp["out_off"], lp["out_step"],
+                                                                                 lp["row_stride"], lp["out_elems"], rows), out_dtype)
     for _ in range(warmup):
         plan.launch(out_dtype)
     eng.sync()
-    t0 = time.perf_counter()
-    plan.read(out_buf)
-    read_first_s = time.perf_counter() - t0   # the first copy into this buffer (whatever the runtime does once per buffer is in it)
-    t0 = time.perf_counter()
-    plan.read(out_buf)
-    read_s = time.perf_counter() - t0   # D2H of every output position
-    n_checked = gate(exp, "before timing")
-    total_counts = plan.total()
+    if full:
+        t0 = time.perf_counter()
+        plan.read(out_buf)
+        read_first_s = time.perf_counter() - t0   # the first copy into this buffer (whatever the runtime does once per buffer is in it)
+        t0 = time.perf_counter()
+        plan.read(out_buf)
+        read_s = time.perf_counter() - t0   # D2H of every output position
+        n_checked = gate(exp, "before timing")
+        total_counts = plan.total()
 
     # ---------------------------------------------------------------- timed region
     multigpu.barrier()
@@ -396,6 +456,14 @@ def run_workload(name, args, ctx, headline):
     torch.cuda.synchronize()
     multigpu.barrier()
     elapsed = multigpu.max_over_ranks(time.perf_counter() - t0, device=ctx["tdev"])
+    if headline and args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan.read(out_buf), tag="_rank%d" % rank if world > 1 else "",
+                     budget=DUMP_BYTES // world)
+    if not full:
+        n_records_all, positions_all = multigpu.allreduce_int_totals([int(my_reads.n), int(lp["out_elems"])], device=ctx["tdev"])
+        ctx["last_engine_objects"] = (eng, plan, my_reads)
+        return headline_result(name, args, tx, mapping, out_dtype, plan, rows, int(my_reads.n), n_records_all, positions_all,
+                               elapsed, steps, warmup, gen_s, stage_s, plan_s)
     gate(exp, "output of the last timed step")
 
     # ---------------------------------------------------------------- per-kernel timing (HIP events on the engine's stream)
@@ -535,6 +603,19 @@ def run_workload(name, args, ctx, headline):
     return res
 
 
+def remove_job_bam(bam_path, rank):
+    """--from-bam: rank 0 removes the job's shared BAM file (and its index) once every rank has staged its range."""
+    from plastid_amd import multigpu
+    if bam_path:
+        multigpu.barrier()
+        if rank == 0:
+            for f in (bam_path, bam_path + ".bai"):
+                try:
+                    os.remove(f)
+                except OSError:
+                    pass
+
+
 def run_partitioned(name, args, ctx, headline):
     """One BASELINE config as ONE job over the ranks (N > 1, ``--partition genome``): every rank generates, stages
     and counts only its own genome range.  Parity: every rank compares the sampled segment pieces it
@@ -547,6 +628,7 @@ def run_partitioned(name, args, ctx, headline):
     rank, world = ctx["rank"], ctx["world"]
     steps = args.steps if headline else max(3, min(args.steps, 10))
     warmup = max(args.warmup, 1) if headline else 2
+    full = args.full
 
     # ---------------------------------------------------------------- this rank's share of the inputs (host)
     t0 = time.perf_counter()
@@ -565,36 +647,37 @@ def run_partitioned(name, args, ctx, headline):
     lp = gp.local_plan_arrays(rank, rows)
     piece_owner = gp.piece["owner"][lp["piece_index"]]          # global segment of every local piece
 
-    # ---------------------------------------------------------------- oracle on the rank's own records: parity sample
-    aln = concat_file_major([my_reads])
-    spec = oracle_spec(oracle, mapping)
-    chains = np.random.default_rng(7).permutation(tx.n)[:min(tx.n, args.parity_chains)]      # the same chains on every rank
-    sampled = np.zeros(len(p["tid"]), bool)
-    sampled[segments_of_chains(tx, chains)] = True
+    # ---------------------------------------------------------------- oracle on the rank's own records: parity sample (--full)
+    if full:
+        aln = concat_file_major([my_reads])
+        spec = oracle_spec(oracle, mapping)
+        chains = np.random.default_rng(7).permutation(tx.n)[:min(tx.n, args.parity_chains)]      # the same chains on every rank
+        sampled = np.zeros(len(p["tid"]), bool)
+        sampled[segments_of_chains(tx, chains)] = True
 
-    def local_expectation(sp, pieces):
-        arrays, _ = oracle.count_segments(aln, sp, lp["tid"][pieces], lp["start"][pieces], lp["end"][pieces], lp["strand"][pieces])
-        idxs, vals = [], []
-        for a, j in zip(arrays, pieces):
-            n = a.shape[-1]
-            idxs.append((lp["out_off"][j] + (np.arange(rows)[:, None] * n + np.arange(n)[None, :])).reshape(-1))   # rank-local layout: [rows, len]
-            vals.append(a.reshape(-1))
-        if not idxs:
-            return np.zeros(0, np.int64), np.zeros(0, out_dtype), arrays
-        return np.concatenate(idxs), np.concatenate(vals), arrays
-    pieces = np.nonzero(sampled[piece_owner])[0]
-    exp_idx, exp_val, piece_arrays = local_expectation(spec, pieces)
-    sf_chains = np.random.default_rng(9).permutation(tx.n)[:min(tx.n, 40)]
-    sf_sampled = np.zeros(len(p["tid"]), bool)
-    sf_sampled[segments_of_chains(tx, sf_chains)] = True
-    sf_idx, sf_val, _ = local_expectation(oracle_spec(oracle, mapping, SIZE_FILTER), np.nonzero(sf_sampled[piece_owner])[0])
-    # the oracle's share of the per-chain sums (completed across the ranks below)
-    seg_chain = np.repeat(np.arange(tx.n, dtype=np.int64), np.diff(tx.ex_off))
-    oracle_part = np.zeros(tx.n * rows, np.int64)
-    if not center:
-        for a, j in zip(piece_arrays, pieces):
-            oracle_part[seg_chain[piece_owner[j]] * rows:(seg_chain[piece_owner[j]] + 1) * rows] += a.reshape(rows, -1).sum(axis=1)
-    del aln, piece_arrays
+        def local_expectation(sp, pieces):
+            arrays, _ = oracle.count_segments(aln, sp, lp["tid"][pieces], lp["start"][pieces], lp["end"][pieces], lp["strand"][pieces])
+            idxs, vals = [], []
+            for a, j in zip(arrays, pieces):
+                n = a.shape[-1]
+                idxs.append((lp["out_off"][j] + (np.arange(rows)[:, None] * n + np.arange(n)[None, :])).reshape(-1))   # rank-local layout: [rows, len]
+                vals.append(a.reshape(-1))
+            if not idxs:
+                return np.zeros(0, np.int64), np.zeros(0, out_dtype), arrays
+            return np.concatenate(idxs), np.concatenate(vals), arrays
+        pieces = np.nonzero(sampled[piece_owner])[0]
+        exp_idx, exp_val, piece_arrays = local_expectation(spec, pieces)
+        sf_chains = np.random.default_rng(9).permutation(tx.n)[:min(tx.n, 40)]
+        sf_sampled = np.zeros(len(p["tid"]), bool)
+        sf_sampled[segments_of_chains(tx, sf_chains)] = True
+        sf_idx, sf_val, _ = local_expectation(oracle_spec(oracle, mapping, SIZE_FILTER), np.nonzero(sf_sampled[piece_owner])[0])
+        # the oracle's share of the per-chain sums (completed across the ranks below)
+        seg_chain = np.repeat(np.arange(tx.n, dtype=np.int64), np.diff(tx.ex_off))
+        oracle_part = np.zeros(tx.n * rows, np.int64)
+        if not center:
+            for a, j in zip(piece_arrays, pieces):
+                oracle_part[seg_chain[piece_owner[j]] * rows:(seg_chain[piece_owner[j]] + 1) * rows] += a.reshape(rows, -1).sum(axis=1)
+        del aln, piece_arrays
 
     # ---------------------------------------------------------------- --from-bam: ONE shared file, written once (untimed)
     # What a user of the reference has is a BAM file, and the reference reads each region from it
@@ -614,15 +697,18 @@ def run_partitioned(name, args, ctx, headline):
 
     # ---------------------------------------------------------------- GPU
     import torch
-    warm_runtime(ctx)
+    if full:
+        warm_runtime(ctx)
     eng = Engine(ctx["dev_index"])
-    time.sleep(0.3)   # the all-cores CPU baseline just burnt the cgroup's CPU quota (CFS, 100 ms periods): staging is a host pass
+    if full:
+        time.sleep(0.3)   # the all-cores CPU baseline just burnt the cgroup's CPU quota (CFS, 100 ms periods): staging is a host pass
     staged_n = int(my_reads.n)
     if bam_path:
         regions = gp.rank_regions(rank, list(my_reads.references))
         if hasattr(eng, "add_bam"):
-            eng.clear_alignments()
-            eng.add_bam(bam_path, regions=regions)             # page cache + library warm-up
+            if full:
+                eng.clear_alignments()
+                eng.add_bam(bam_path, regions=regions)             # page cache + library warm-up
             t0 = time.perf_counter()
             eng.clear_alignments()
             eng.add_bam(bam_path, regions=regions)
@@ -646,26 +732,31 @@ def run_partitioned(name, args, ctx, headline):
     plan = eng.plan(lp["tid"], lp["start"], lp["end"], lp["strand"], lp["out_off"], lp["out_step"], lp["row_stride"],
                     lp["out_elems"], rows)
     plan_s = time.perf_counter() - t0
-    out_buf = (eng.host_buffer(int(lp["out_elems"]), out_dtype) if (hasattr(eng, "host_buffer") and int(lp["out_elems"]) * 8 <= (16 << 30))
-               else np.zeros(int(lp["out_elems"]), out_dtype))   # page-locked, as at N = 1
-    out_buf[:] = 0
+    out_buf = None   # (--full only, as at N = 1)
+    if full:
+        out_buf = (eng.host_buffer(int(lp["out_elems"]), out_dtype) if (hasattr(eng, "host_buffer") and int(lp["out_elems"]) * 8 <= (16 << 30))
+                   else np.zeros(int(lp["out_elems"]), out_dtype))   # page-locked, as at N = 1
+        out_buf[:] = 0
 
     def gate(idx, val, what):
         got = plan.read(out_buf)
         if not np.array_equal(got[idx], val.astype(got.dtype)):
             raise SystemExit("PARITY FAILURE (%s, rank %d, %s): HIP counts differ from the oracle on the sampled pieces" % (name, rank, what))
         return len(idx)
-    plan.close()
-    plan, first_count_ms = first_count_of_fresh_plans(eng, lambda: eng.plan(lp["tid"], lp["start"], lp["end"], lp["strand"], lp["out_off"], lp["out_step"],
-                                                                             lp["row_stride"], lp["out_elems"], rows), out_dtype)
+    if full:
+        plan.close()
+        plan, first_count_ms = first_count_of_fresh_plans(eng, lambda: eng.plan(lp["tid"], lp["start"], lp["end"], lp["strand"], lp["out_off"], lp["out_step"],
+                                                                                 lp["row_stride"], lp["out_elems"], rows), out_dtype)
     for _ in range(warmup):
         plan.launch(out_dtype)
     eng.sync()
-    t0 = time.perf_counter()
-    plan.read(out_buf)
-    read_s = time.perf_counter() - t0
-    n_checked = gate(exp_idx, exp_val, "before timing")
-    total_counts = plan.total()
+    if full:
+        t0 = time.perf_counter()
+        plan.read(out_buf)
+        read_s = time.perf_counter() - t0
+        n_checked = gate(exp_idx, exp_val, "before timing")
+        total_counts = plan.total()
+    per_rank = lambda v: multigpu.allreduce_int_totals([int(v) if r == rank else 0 for r in range(world)], device=ctx["tdev"])
 
     # ---------------------------------------------------------------- timed region
     multigpu.barrier()
@@ -679,6 +770,25 @@ def run_partitioned(name, args, ctx, headline):
         torch.cuda.synchronize()
     multigpu.barrier()
     elapsed = multigpu.max_over_ranks(time.perf_counter() - t0, device=ctx["tdev"])
+    if headline and args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan.read(out_buf), tag="_rank%d" % rank if world > 1 else "",
+                     budget=DUMP_BYTES // world)
+    if not full:
+        n_records_all, positions_all = multigpu.allreduce_int_totals([owned, int(lp["out_elems"])], device=ctx["tdev"])
+        if n_records_all != lay.n:
+            raise SystemExit("partition (%s): the ranks own %d records, the job has %d" % (name, n_records_all, lay.n))
+        balance, stage_ms_all = per_rank(owned), per_rank(round(stage_s * 1e3))
+        remove_job_bam(bam_path, rank)
+        res = headline_result(name, args, tx, mapping, out_dtype, plan, rows, owned, n_records_all, positions_all,
+                              elapsed, steps, warmup, gen_s, stage_s, plan_s)
+        res["workload"] += " -- one job over %d ranks" % world
+        res["partition"] = {"records_per_rank": balance, "halo_positions": int(lay.halo), "stage_ms_per_rank": stage_ms_all,
+                            "allreduce": None}
+        if rehearsal:
+            res["value"] = None
+            res["rehearsal"] = "engine stand-in %s: control flow only, no measurement" % getattr(Engine, "__module__", "?")
+        ctx["last_engine_objects"] = (eng, plan, my_reads)
+        return res
     gate(exp_idx, exp_val, "output of the last timed step")
 
     phases = {"total": 0.0, "worklist": 0.0, "hist": 0.0, "long": 0.0, "gather": 0.0, "zero": 0.0}
@@ -706,17 +816,9 @@ def run_partitioned(name, args, ctx, headline):
         raise SystemExit("partition (%s): the ranks own %d records, the job has %d" % (name, n_records_all, lay.n))
     if center:
         counts_all = multigpu.reduce_float_totals_ordered([float(total_counts)], device=ctx["tdev"])[0]
-    per_rank = lambda v: multigpu.allreduce_int_totals([int(v) if r == rank else 0 for r in range(world)], device=ctx["tdev"])
     balance, staged, rss = per_rank(owned), per_rank(staged_n), per_rank(peak_rss_mb())
     stage_ms_all = per_rank(round(stage_s * 1e3))
-    if bam_path:
-        multigpu.barrier()
-        if rank == 0:
-            for f in (bam_path, bam_path + ".bai"):
-                try:
-                    os.remove(f)
-                except OSError:
-                    pass
+    remove_job_bam(bam_path, rank)
     gen_all = per_rank(round(gen_s * 1e3))
     allreduce = None
     if not center:
@@ -998,6 +1100,40 @@ def center_issue_bound(eng, plan, kernel_ms):
             "issue_basis": "replay steps x (3 x 2 + 4) cycles / (1024 SIMDs x 2.4 GHz): subrev, subrev_co, cndmask at 2 cycles, v_fmac_f64 at 4"}
 
 
+def print_headline_line(args, head, world, partition, one_job, wall_s):
+    """The stdout line of a plain run (no --full): the contract's keys and what describes the workload.  `metric`,
+    `value`, `unit`, `higher_is_better`, `dtype` and `ms_per_step` mean what they mean in a --full line."""
+    config = {"workload": head["workload"], "records": head["records_total"], "chains": head["chains"],
+              "segments": head["segments"], "output_positions": head["output_positions_per_gpu"], "tiles": head["tiles"],
+              "mapping": head["mapping"], "plan_build_ms": head["plan_build_ms_once_per_annotation"],
+              "host_stage_s": head["host_stage_s"], "kernel_source_sha16": kernel_source_hash(), "bench_wall_s": round(wall_s, 1)}
+    if "partition" in head:
+        pt = head["partition"]
+        config["partition"] = {"records_per_rank": pt["records_per_rank"], "halo": pt["halo_positions"],
+                               "stage_ms_per_rank": pt["stage_ms_per_rank"], "from_bam": bool(args.from_bam)}
+    if "rehearsal" in head:
+        config["rehearsal"] = head["rehearsal"]
+    if args.detail_out:
+        with open(args.detail_out, "w") as f:
+            json.dump({"headline": head, "argv": sys.argv[1:]}, f, indent=1, default=str)
+    result = {
+        "metric": "mapped_reads_per_sec",
+        "value": head["value"],
+        "unit": "reads/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": head["ms_per_step"],
+        "higher_is_better": True,
+        "scaling": "weak" if (world == 1 or partition == "replicas") else "strong",
+        "vs_baseline": None,
+        "dtype": head["dtype"],
+        "data": "synthetic" if not one_job else "synthetic (every rank generates its own genome range of the one job)",
+        "config": config,
+    }
+    print(json.dumps(result, separators=(",", ":")))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1027,7 +1163,16 @@ def main():
     ap.add_argument("--no-single-query", action="store_true", help="skip the single-query latency loop (profiling passes: it launches the tile kernel hundreds of times)")
     ap.add_argument("--e2e-realistic-records", type=float, default=1e8,
                     help="records of the second e2e sample, written as an aligner writes them (~120 bytes per record; 0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline's timed steps: oracle parity gates, CPU baseline, per-kernel "
+                         "timing and roofline, size-filter and two-file variants, stream probe, single-query and e2e scopes, the "
+                         "other configs and bench_detail.json (the options above that tune these act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the counts of the last timed step to DIR/*.npy (float64; whole, or a seeded sample plus block "
+                         "sums when larger than 60 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     t_start = time.perf_counter()
     # this process creates one engine per config, tens of GB each, one after the other: the idle device blocks of a closed
     # engine are kept for the next one (on some boxes a hipMalloc behind the hipFree of tens of GB takes seconds); the
@@ -1081,6 +1226,14 @@ def main():
 
     head = run_config(args.config, args, ctx, headline=True)
     eng, plan, _reads = ctx.pop("last_engine_objects")
+    if not args.full:
+        plan.close()
+        eng.close()
+        if rank == 0:
+            print_headline_line(args, head, world, partition, one_job, time.perf_counter() - t_start)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     if rank == 0 and not rehearsal and head["roofline"]["kernel"] == "k_center":
         head["roofline"].update(center_issue_bound(eng, plan, head["roofline"]["avg_launch_ms"]))
     stream_peak = None

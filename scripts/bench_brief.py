@@ -1,4 +1,4 @@
-"""Print the few figures of a bench.py JSON line that a kernel experiment looks at (headline + every other config)."""
+"""Print the few figures of a `bench.py --full` JSON line that a kernel experiment looks at (headline + every other config)."""
 import json
 import sys
 

@@ -266,7 +266,7 @@ def test_bench_spawns_its_ranks_and_runs_the_one_job_mode(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     detail = str(tmp_path / "detail.json")
-    cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--gpus", "2", "--scale", "0.002", "--tx-scale", "0.01",
+    cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--gpus", "2", "--full", "--scale", "0.002", "--tx-scale", "0.01",
            "--steps", "2", "--warmup", "1", "--other-configs", "C4,C5", "--parity-chains", "60", "--detail-out", detail]
     proc = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert proc.returncode == 0, proc.stderr.decode()[-3000:]
@@ -306,7 +306,7 @@ def test_bench_one_job_from_one_shared_bam_file(tmp_path):
         env.pop(k, None)
     for cfg, n in (("C2", 100000), ("C3", 100000), ("C4", 100000)):
         detail = str(tmp_path / ("detail_%s.json" % cfg))
-        cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--gpus", "2", "--from-bam", "--config", cfg,
+        cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_rehearsal.py"), "--gpus", "2", "--full", "--from-bam", "--config", cfg,
                "--scale", str(n / {"C2": 1e8, "C3": 1e8, "C4": 5e8}[cfg]), "--tx-scale", "0.01",
                "--steps", "2", "--warmup", "1", "--parity-chains", "60", "--detail-out", detail]
         proc = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)

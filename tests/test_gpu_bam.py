@@ -884,7 +884,7 @@ def test_bench_one_job_from_one_bam_file_on_the_gpu(tmp_path):
     for cfg, scale in (("C2", 0.004), ("C3", 0.004), ("C4", 0.0008)):
         for mode in ("--from-bam", "--one-job"):
             detail = str(tmp_path / ("d_%s_%d.json" % (cfg, mode == "--from-bam")))
-            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", mode, "--config", cfg, "--scale", str(scale), "--tx-scale", "0.02",
+            cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", mode, "--config", cfg, "--scale", str(scale), "--tx-scale", "0.02",
                    "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-two-files", "--no-single-query", "--other-configs", "none",
                    "--e2e-records", "0", "--e2e-realistic-records", "0", "--parity-chains", "100", "--detail-out", detail]
             proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
