@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 6
+#define PC_ABI_VERSION 7
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -353,6 +353,23 @@ int pc_bam_open_span(pc_engine *e, const char *path, uint64_t voff_begin, uint64
                      const int64_t *beg, const int64_t *end, pc_bam **out);
 int pc_add_alignment_bam_span(pc_engine *e, const char *path, uint64_t voff_begin, uint64_t voff_end, int nreg, const int32_t *tid,
                               const int64_t *beg, const int64_t *end, int64_t *mapped);
+/* (ABI 7) The same region reads from the CHUNK LIST of the index instead of its span (plastid_amd/csrc/bam_stager.cpp
+ * pb_resolve_chunks: the regions' chunks, clipped by the linear index, sorted and merged -- what htslib's iterator walks
+ * chunk by chunk, hts.c:1924-1960):
+ *   nchunk, voff_beg, voff_end   [voff_beg[k], voff_end[k]) ascending and disjoint; nchunk = 0: the header alone is read.
+ * Only the leading members that hold the header and the members the chunks touch are uploaded and inflated: two far-apart
+ * regions cost what they hold, not the file between them.  Chunks that share or touch a member form one RUN (one
+ * contiguous upload; one record chain from the run's first chunk start to its last chunk end -- the records between two
+ * chunks of a run are decoded and dropped by the overlap rule).  The columns are those pc_bam_open_span gives over the
+ * enclosing span, record for record.  Errors: as pc_bam_open_span (a chunk beyond the end of the file, one that does not
+ * start at a member, one that ends inside a record: PC_ERR_ARG, "the index does not belong to this BAM file"). */
+int pc_bam_open_chunks(pc_engine *e, const char *path, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg,
+                       const int32_t *tid, const int64_t *beg, const int64_t *end, pc_bam **out);
+int pc_add_alignment_bam_chunks(pc_engine *e, const char *path, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end,
+                                int nreg, const int32_t *tid, const int64_t *beg, const int64_t *end, int64_t *mapped);
+/* what an open read: [0] compressed bytes of the file uploaded to HBM, [1] runs they came in (1: a whole file), [2] BGZF
+ * members inflated, [3] inflated bytes */
+int pc_bam_stats(pc_bam *b, int64_t *out4);
 
 #ifdef __cplusplus
 }

@@ -97,13 +97,16 @@ SIGNATURES = {
     "pc_add_alignment_bam_path": (_int, [_vp, ctypes.c_char_p, ctypes.POINTER(_i64)]),
     "pc_bam_open_span": (_int, [_vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, _int, _vp, _vp, _vp, _pp]),
     "pc_add_alignment_bam_span": (_int, [_vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, _int, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
+    "pc_bam_open_chunks": (_int, [_vp, ctypes.c_char_p, _int, _vp, _vp, _int, _vp, _vp, _vp, _pp]),
+    "pc_add_alignment_bam_chunks": (_int, [_vp, ctypes.c_char_p, _int, _vp, _vp, _int, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
+    "pc_bam_stats": (_int, [_vp, _vp]),
 }
 
 _lib = None
 
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 def load():

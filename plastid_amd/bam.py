@@ -43,6 +43,7 @@ def _load():
         L.pb_fill_sam.argtypes = [vp] * 4
         L.pb_fill_nh.argtypes = [vp] * 2
         L.pb_resolve_regions.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p)] + [vp] * 9
+        L.pb_resolve_chunks.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), vp, vp, ctypes.c_int64] + [vp] * 8
         _lib = L
     return _lib
 
@@ -107,10 +108,11 @@ def _region_tuples(regions):
 
 def resolve_regions(path, regions):
     """Resolve `regions` (``(chrom, start, end)`` or |GenomicSegments|) through the BAI index of `path` for a decoder
-    that reads the file itself (:func:`read_bam_gpu`, :meth:`Engine.add_bam`): returns a dict with the span of virtual
-    offsets ``voff_begin``, ``voff_end`` that holds every chunk of every region (bins + 16 kb linear index, SAM
-    specification section 5 -- what ``AlignmentFile.fetch`` walks per region, genome_array.py:800-809), the merged regions
-    by reference id (``tid``, ``beg``, ``end`` arrays), the index's whole-file ``mapped`` count (-1: none) and the
+    that reads the file itself (:func:`read_bam_gpu`, :meth:`Engine.add_bam`): returns a dict with the merged index
+    chunks of the regions, ``chunks`` (``uint64 [k, 2]``: ``[voff_beg, voff_end)`` pairs of virtual offsets, ascending and
+    disjoint; bins + 16 kb linear index, SAM specification section 5 -- what ``AlignmentFile.fetch`` walks per region,
+    genome_array.py:800-809), the span ``voff_begin``, ``voff_end`` that holds them all (0, 0: no chunk), the merged
+    regions by reference id (``tid``, ``beg``, ``end`` arrays), the index's whole-file ``mapped`` count (-1: none) and the
     file's ``references`` / ``lengths``."""
     L = _load()
     h = L.pb_open(os.fsencode(path))
@@ -122,22 +124,28 @@ def resolve_regions(path, regions):
         names = (ctypes.c_char_p * max(n, 1))(*[os.fsencode(str(c)) for c, _, _ in regs])
         starts = np.array([int(s) for _, s, _ in regs], np.int64)
         ends = np.array([int(e) for _, _, e in regs], np.int64)
-        vb, ve = ctypes.c_uint64(0), ctypes.c_uint64(0)
-        mapped, nm = ctypes.c_int64(0), ctypes.c_int(0)
+        nch, mapped, nm = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
         tid, beg, end = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
         p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-        rc = L.pb_resolve_regions(h, n, names, p(starts), p(ends), ctypes.byref(vb), ctypes.byref(ve), ctypes.byref(mapped), ctypes.byref(nm),
-                                  p(tid), p(beg), p(end))
-        if rc != 0:
-            raise ValueError(L.pb_last_error().decode())
+        cap = 8 * n + 64
+        while True:
+            cb, ce = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+            rc = L.pb_resolve_chunks(h, n, names, p(starts), p(ends), cap, p(cb), p(ce), ctypes.byref(nch), ctypes.byref(mapped), ctypes.byref(nm),
+                                     p(tid), p(beg), p(end))
+            if rc != 0:
+                raise ValueError(L.pb_last_error().decode())
+            if nch.value <= cap:
+                break
+            cap = int(nch.value)
         nref = L.pb_nref(h)
         refs = [L.pb_ref_name(h, i).decode() for i in range(nref)]
         lens = [int(L.pb_ref_length(h, i)) for i in range(nref)]
     finally:
         L.pb_close(h)
-    k = int(nm.value)
-    return dict(voff_begin=int(vb.value), voff_end=int(ve.value), tid=tid[:k].copy(), beg=beg[:k].copy(), end=end[:k].copy(),
-                mapped=int(mapped.value), references=refs, lengths=lens)
+    k, c = int(nm.value), int(nch.value)
+    chunks = np.ascontiguousarray(np.stack([cb[:c], ce[:c]], axis=1))
+    return dict(voff_begin=int(chunks[0, 0]) if c else 0, voff_end=int(chunks[:, 1].max()) if c else 0, chunks=chunks,
+                tid=tid[:k].copy(), beg=beg[:k].copy(), end=end[:k].copy(), mapped=int(mapped.value), references=refs, lengths=lens)
 
 
 def read_bam_gpu(path, engine, timing=None, regions=None):
@@ -146,9 +154,12 @@ def read_bam_gpu(path, engine, timing=None, regions=None):
     (``pc_bam_open``, ``csrc/bam_kernels.hip.h``); only the packed columns -- 13 bytes per record instead of the ~120 of
     an aligner's record -- come back.  `engine`: a :class:`plastid_amd.engine.Engine` (its device and stream are used).
     `timing`: optional dict that receives the phase times in ms and the member / byte counts.
+    `timing` then also has ``uploaded_bytes`` (compressed bytes of the file that went to HBM) and ``runs`` (the contiguous
+    stretches they came in).
     `regions`: as for :func:`read_bam` -- only the alignments that overlap one of them, through the BAI index: only the
-    BGZF members of ONE span of the file -- from the first to the last index chunk of the regions, whatever lies between two far-apart regions included -- are uploaded and inflated (``pc_bam_open_span``; the overlap test then drops what no region wants: regions that sit together, like one rank's genome range, read little else); ``mapped`` is then the index's
-    whole-file count, as pysam's."""
+    BGZF members the index chunks of the regions point to (and the leading ones with the header) are uploaded and
+    inflated (``pc_bam_open_chunks``; the overlap test then drops the records of those members that no region wants);
+    ``mapped`` is then the index's whole-file count, as pysam's."""
     import time
     from . import _lib as clib
     L = clib.load()
@@ -160,8 +171,9 @@ def read_bam_gpu(path, engine, timing=None, regions=None):
     if regions is not None:
         span = resolve_regions(path, regions)
         pv = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
-        clib.check(L.pc_bam_open_span(engine._h, os.fsencode(path), span["voff_begin"], span["voff_end"], len(span["tid"]),
-                                      pv(span["tid"]), pv(span["beg"]), pv(span["end"]), ctypes.byref(h)))
+        cb, ce = np.ascontiguousarray(span["chunks"][:, 0]), np.ascontiguousarray(span["chunks"][:, 1])
+        clib.check(L.pc_bam_open_chunks(engine._h, os.fsencode(path), len(cb), pv(cb), pv(ce), len(span["tid"]),
+                                        pv(span["tid"]), pv(span["beg"]), pv(span["end"]), ctypes.byref(h)))
     else:
         # (the library maps the file itself: pages touched by all host threads at once, unmapped on a thread of its own)
         clib.check(L.pc_bam_open_path(engine._h, os.fsencode(path), ctypes.byref(h)))
@@ -188,9 +200,11 @@ def read_bam_gpu(path, engine, timing=None, regions=None):
             timing.update(open_wall_ms=(t_open - t_0) * 1e3, read_wall_ms=(time.perf_counter() - t_open) * 1e3)
             ms = np.zeros(4, np.float64)
             clib.check(L.pc_bam_timing(h, p(ms)))
+            st = np.zeros(4, np.int64)
+            clib.check(L.pc_bam_stats(h, p(st)))
             timing.update(upload_ms=float(ms[0]), inflate_ms=float(ms[1]), chain_ms=float(ms[2]), decode_ms=float(ms[3]),
                           members=int(counts[5]), inflated_bytes=int(counts[6]), compressed_bytes=size, chain_restarts=int(counts[7]),
-                          records=int(counts[3]))
+                          records=int(counts[3]), uploaded_bytes=int(st[0]), runs=int(st[1]))
     finally:
         t_c = time.perf_counter()
         L.pc_bam_close(h)

@@ -796,13 +796,23 @@ struct MemberChain {
 
 // One wave per member.  forced[m] != ~0: start there instead of guessing (the host found that the preceding member's
 // chain ends there).  rec_off[m * kMaxRecPerMember + k] = offset of record k relative to the member's begin.
+// kRuns (multi-chunk region reads): the uploaded members form runs, each a contiguous stretch of the file with a chain of
+// its own; member m belongs to run member_run[m], whose records start at run_bounds[2 r] and stop at run_bounds[2 r + 1]
+// (first_record / stop_at are then ignored).  Without runs the kernel is the one-chain kernel of whole-file and span reads.
+template <bool kRuns>
 __global__ __launch_bounds__(64) void k_bam_chain(const uint8_t *__restrict__ stream, uint64_t stream_len, const Member *__restrict__ members,
                                                   int nmembers, int member_lo, uint32_t n_ref, uint64_t first_record, const uint64_t *__restrict__ forced,
-                                                  MemberChain *chain, uint32_t *rec_off, uint64_t stop_at) {
+                                                  MemberChain *chain, uint32_t *rec_off, uint64_t stop_at, const uint32_t *__restrict__ member_run,
+                                                  const uint64_t *__restrict__ run_bounds) {
     const int m = member_lo + (int)blockIdx.x;
     if (m >= nmembers) return;
     const int lane = threadIdx.x & 63;
     const Member mb = members[m];
+    if (kRuns) {
+        const uint32_t r = member_run[m];
+        first_record = run_bounds[2 * (size_t)r];
+        stop_at = run_bounds[2 * (size_t)r + 1];
+    }
     // (region reads: no record is looked for at or behind `stop_at`, the end of the last chunk of the index)
     const uint64_t begin = mb.uoff, end = mb.uoff + mb.ulen < stop_at ? mb.uoff + mb.ulen : stop_at;
     MemberChain mc;

@@ -1279,6 +1279,36 @@ int pb_resolve_regions(void *h, int nreg, const char *const *names, const int64_
     return 0;
 }
 
+// pb_resolve_regions with the merged chunk list itself instead of its span (pc_bam_open_chunks: only the members the
+// chunks touch go to the GPU): *nchunk = the number of chunks, ascending and disjoint [voff_beg[k], voff_end[k]); at most
+// `cap` of them are written (call again with a larger `cap` when *nchunk > cap).  Merged regions and *mapped as there.
+int pb_resolve_chunks(void *h, int nreg, const char *const *names, const int64_t *start, const int64_t *end, int64_t cap, uint64_t *voff_beg,
+                      uint64_t *voff_end, int64_t *nchunk, int64_t *mapped, int *nmerged, int32_t *m_tid, int64_t *m_start, int64_t *m_end) {
+    Bam *b = static_cast<Bam *>(h);
+    if (!b || nreg < 0 || (nreg > 0 && (!names || !start || !end)) || cap < 0 || (cap > 0 && (!voff_beg || !voff_end)) || !nchunk || !mapped ||
+        !nmerged)
+        return fail("pb_resolve_chunks: bad arguments");
+    FILE *f = fopen(b->path.c_str(), "rb");
+    if (!f) return fail("cannot read " + b->path);
+    uint32_t n_ref = 0;
+    const int hrc = read_header_members(*b, f, n_ref);
+    fclose(f);
+    if (hrc != 0) return -1;
+    std::vector<BaiRef> refs;
+    std::vector<RegionSpan> merged;
+    std::vector<std::pair<uint64_t, uint64_t>> chunks;
+    if (resolve_regions(*b, n_ref, nreg, names, start, end, refs, merged, chunks) != 0) return -1;
+    *nchunk = (int64_t)chunks.size();
+    for (size_t k = 0; k < chunks.size() && (int64_t)k < cap; ++k) { voff_beg[k] = chunks[k].first; voff_end[k] = chunks[k].second; }
+    int64_t m = 0;
+    bool any_meta = false;
+    for (const BaiRef &br : refs) { m += (int64_t)br.n_mapped; any_meta |= br.has_meta; }
+    *mapped = any_meta ? m : -1;
+    *nmerged = (int)merged.size();
+    for (size_t k = 0; k < merged.size() && m_tid && m_start && m_end; ++k) { m_tid[k] = merged[k].tid; m_start[k] = merged[k].s; m_end[k] = merged[k].e; }
+    return 0;
+}
+
 int pb_nref(void *h) { return h ? (int)static_cast<Bam *>(h)->ref_names.size() : -1; }
 const char *pb_ref_name(void *h, int i) { return static_cast<Bam *>(h)->ref_names[(size_t)i].c_str(); }
 int32_t pb_ref_length(void *h, int i) { return static_cast<Bam *>(h)->ref_lengths[(size_t)i]; }

@@ -3754,6 +3754,7 @@ struct pc_bam {
     std::vector<int32_t> wide_alen, wide_nblk;
     double ms[4] = {0, 0, 0, 0};     // upload, inflate (+ CRC), record chain, fields + columns
     int64_t members = 0, inflated_bytes = 0, compressed_bytes = 0;
+    int64_t uploaded_bytes = 0, runs = 0;   // bytes of the file image that went to HBM, contiguous stretches they came from
     int chain_restarts = 0;
 };
 
@@ -3819,8 +3820,13 @@ struct BamClock {   // PC_BAM_TIMING=1: wall-clock laps of the host side of the 
 typedef std::function<void(hipStream_t)> UploadedHook;
 // A region read (pc_bam_open_span): only the BGZF members between two virtual offsets of the BAI index are uploaded and
 // inflated (plus the leading members that hold the header), and only the records that overlap one of the regions stay.
+// A multi-chunk region read (pc_bam_open_chunks, nchunk >= 0): only the members the chunks [cbeg[k], cend[k]) touch go to HBM;
+// chunks that share or touch a member form one run (one contiguous upload, one record chain from the run's first chunk start
+// to its last chunk end).
 struct BamSpan {
     uint64_t voff_begin = 0, voff_end = 0;   // (file offset of a member << 16 | offset in its payload): [begin, end); 0, 0: header only
+    int nchunk = -1;                         // >= 0: the chunk list below replaces [voff_begin, voff_end)
+    const uint64_t *cbeg = nullptr, *cend = nullptr;   // ascending, disjoint
     int nreg = 0;                            // merged regions, ascending by (reference id, start)
     const int32_t *tid = nullptr;
     const int64_t *beg = nullptr, *end = nullptr;
@@ -3886,7 +3892,64 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     struct Run { int64_t file_lo, file_hi, dev_lo; int m0, m1; };
     std::vector<Run> runs;
     int span_first_member = -1, span_last_member = -1;   // region read: indices (in `members`) of the members at voff_begin >> 16 and at voff_end >> 16
-    if (span) {
+    const bool chunked = span && span->nchunk >= 0;
+    // multi-chunk read: where each chunk starts and ends, by member (index in `members` of the member at the offset -- of
+    // the next non-empty one for an empty member, members.size() past the last) and offset in its payload
+    struct ChunkAt { int64_t cb; int s_idx, e_idx; uint32_t ub, ue; };
+    std::vector<ChunkAt> chunk_at;
+    if (chunked) {
+        // every member walked: its file offset, its index in `members` (see ChunkAt) and its payload length
+        struct Walked { int64_t off; int idx; uint32_t ulen; };
+        std::vector<Walked> walked;
+        auto belongs_not = [&](const char *why) { return fail(PC_ERR_ARG, "the index does not belong to this BAM file (%s): %s", why, path.c_str()); };
+        // members from `off` on while they start before `hi_excl` (or at `last`, with_last); a new run unless `off` continues the last
+        auto walk = [&](int64_t off, int64_t hi_excl, bool with_last, int64_t last) -> int {
+            if (runs.empty() || runs.back().file_hi != off) runs.push_back(Run{off, off, 0, (int)members.size(), (int)members.size()});
+            const int64_t first = off;
+            while (off < size && (off < hi_excl || (with_last && off <= last))) {
+                Member mb;
+                int64_t clen = 0;
+                const int code = parse_member(off, mb, clen);
+                if (code) return off == first && first > 0 ? belongs_not("a chunk does not start at a BGZF member") : walk_error(code);
+                walked.push_back(Walked{off, (int)members.size(), mb.ulen});
+                if (mb.ulen) members.push_back(mb);
+                off += clen;
+            }
+            runs.back().file_hi = off; runs.back().m1 = (int)members.size();
+            if (runs.back().file_hi == runs.back().file_lo) runs.pop_back();
+            return PC_OK;
+        };
+        auto find = [&](int64_t off) -> const Walked * {
+            auto it = std::lower_bound(walked.begin(), walked.end(), off, [](const Walked &w, int64_t o) { return w.off < o; });
+            return it != walked.end() && it->off == off ? &*it : nullptr;
+        };
+        const int64_t cb0 = span->nchunk > 0 ? (int64_t)(span->cbeg[0] >> 16) : size;
+        int rc0 = walk(0, std::min<int64_t>(span->header_bytes, cb0), false, 0);
+        if (rc0 != PC_OK) return rc0;
+        for (int k = 0; k < span->nchunk; ++k) {
+            const uint64_t vb = span->cbeg[k], ve = span->cend[k];
+            const int64_t cb = (int64_t)(vb >> 16), ce = (int64_t)(ve >> 16);
+            const uint32_t ub = (uint32_t)(vb & 0xffffu), ue = (uint32_t)(ve & 0xffffu);
+            if (cb >= size || ce > size || (ue && ce >= size)) return belongs_not("a chunk lies beyond its end");
+            const int64_t hi = runs.empty() ? 0 : runs.back().file_hi;
+            if (cb < hi && !find(cb)) return belongs_not("a chunk does not start at a BGZF member");
+            rc0 = walk(std::max(cb, hi), ce, ue != 0, ce);
+            if (rc0 != PC_OK) return rc0;
+            ChunkAt c{cb, 0, 0, ub, ue};
+            const Walked *ws = find(cb);
+            if (!ws || ub > ws->ulen) return belongs_not("a chunk does not start at a BGZF member");
+            c.s_idx = ws->idx;
+            if (ue) {
+                const Walked *we = find(ce);
+                if (!we || ue > we->ulen) return belongs_not("a chunk does not end at a BGZF member");
+                c.e_idx = we->idx;
+            } else {
+                if (runs.empty() || runs.back().file_hi != ce) return belongs_not("a chunk does not end at a BGZF member");
+                c.e_idx = (int)members.size();
+            }
+            chunk_at.push_back(c);
+        }
+    } else if (span) {
         const int64_t cb = (int64_t)(span->voff_begin >> 16), ce = (int64_t)(span->voff_end >> 16);
         const bool have = span->voff_end > span->voff_begin;
         if (have && (cb >= size || ce > size)) return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk lies beyond its end): %s", path.c_str());
@@ -3917,6 +3980,8 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
             rc0 = walk_run(cb, ce, (span->voff_end & 0xffffu) != 0, ce, &span_last_member);
             if (rc0 != PC_OK) return rc0;
         }
+    }
+    if (span) {
         // adjacent runs become one (a run is uploaded as one contiguous copy)
         for (size_t k = 1; k < runs.size();)
             if (runs[k].file_lo == runs[k - 1].file_hi) { runs[k - 1].file_hi = runs[k].file_hi; runs[k - 1].m1 = runs[k].m1; runs.erase(runs.begin() + (long)k); }
@@ -3994,6 +4059,7 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     pc_bam *b = new pc_bam();
     clk.lap("member walk");
     b->e = e; b->name = path; b->members = (int64_t)members.size(); b->inflated_bytes = (int64_t)total_u; b->compressed_bytes = size;
+    b->uploaded_bytes = image_bytes; b->runs = (int64_t)runs.size();
     struct Guard { pc_bam *b; ~Guard() { if (b) pc_bam_close(b); } } guard{b};
     const int nm = (int)members.size();
     hipEvent_t ev[5];
@@ -4002,6 +4068,9 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     DevBuf<uint8_t> d_image, d_stream;
     DevBuf<Member> d_members;
     DevBuf<uint32_t> d_status, d_crc;
+    // (pieces of the image gathered from several runs, for an upload straight from pageable memory: they live until every
+    // stream has drained, i.e. longer than `drain` below)
+    std::vector<std::vector<uint8_t>> gathered;
     int rc = d_image.reserve((size_t)std::max<int64_t>(image_bytes, 16) + 16);
     if (rc == PC_OK) rc = d_stream.reserve((size_t)total_u + 64);
     if (rc == PC_OK) rc = d_members.reserve((size_t)std::max(nm, 1));
@@ -4066,19 +4135,35 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
             }
             (void)hipGetLastError();
         }
+        // bytes [lo, hi) of the image on the device, from the file, to dst: run by run (the file's bytes of run r start at
+        // r.file_lo - r.dev_lo before its offsets in the image on the device)
+        auto copy_image = [&](uint8_t *dst, int64_t lo, int64_t hi) {
+            auto it = std::upper_bound(runs.begin(), runs.end(), lo, [](int64_t x, const Run &r) { return x < r.dev_lo; });
+            for (size_t r = (size_t)(it - runs.begin()) - 1; r < runs.size() && lo < hi; ++r) {
+                const int64_t rhi = std::min(hi, runs[r].dev_lo + (runs[r].file_hi - runs[r].file_lo));
+                if (rhi > lo) std::memcpy(dst, image + (runs[r].file_lo - runs[r].dev_lo) + lo, (size_t)(rhi - lo));
+                dst += std::max<int64_t>(rhi - lo, 0);
+                lo = std::max(lo, rhi);
+            }
+        };
+        // the run each member belongs to (pieces end where a run ends; one piece may hold several short runs)
+        std::vector<uint32_t> run_of((size_t)nm);
+        for (size_t r = 0; r < runs.size(); ++r)
+            for (int m = runs[r].m0; m < runs[r].m1; ++m) run_of[(size_t)m] = (uint32_t)r;
         int piece_no = 0;
-        for (const Run &run : runs) {
-        // (offsets in the image on the device; the file's bytes of the run start at run.file_lo - run.dev_lo before them)
-        const uint8_t *run_src = image + (run.file_lo - run.dev_lo);
-        int64_t byte0 = run.dev_lo;          // the run is uploaded from here on (gzip headers and trailers ride along)
-        for (int m0 = run.m0; m0 < run.m1; ++piece_no) {
+        int64_t byte0 = 0;                   // the image is uploaded from here on (gzip headers and trailers ride along)
+        for (int m0 = 0; m0 < nm; ++piece_no) {
             int m1 = m0;
             int64_t byte1 = byte0;
-            while (m1 < run.m1 && (byte1 - byte0 < piece_bytes || m1 == m0)) {
+            while (m1 < nm && (byte1 - byte0 < piece_bytes || m1 == m0)) {
                 byte1 = (int64_t)(members[(size_t)m1].coff + members[(size_t)m1].clen);
                 ++m1;
             }
-            if (m1 == run.m1) byte1 = run.dev_lo + (run.file_hi - run.file_lo);
+            if (m1 == nm) byte1 = image_bytes;
+            else if (run_of[(size_t)m1] != run_of[(size_t)m1 - 1]) byte1 = runs[run_of[(size_t)m1]].dev_lo;   // (the rest of the run before)
+            const uint32_t r0 = run_of[(size_t)m0];
+            const bool one_run = byte1 <= runs[r0].dev_lo + (runs[r0].file_hi - runs[r0].file_lo);
+            const uint8_t *run_src = image + (runs[r0].file_lo - runs[r0].dev_lo);   // (one_run: the piece's bytes in the file)
             if (ring) {
                 // through a page-locked half: the runtime's own staging of a pageable copy runs on one thread (12 - 20 GB/s);
                 // here every host thread copies its share, and the DMA of one half overlaps the filling of the other
@@ -4089,13 +4174,19 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
                 const int64_t len = byte1 - byte0, blk = (int64_t)1 << 20;
                 parallel_chunks((len + blk - 1) / blk, ring_threads, [&](int, int64_t b, int64_t en) {
                     const int64_t lo = b * blk, hi = std::min(len, en * blk);
-                    if (hi > lo) std::memcpy(dstp + lo, srcp + lo, (size_t)(hi - lo));
+                    if (hi > lo && one_run) std::memcpy(dstp + lo, srcp + lo, (size_t)(hi - lo));
+                    else if (hi > lo) copy_image(dstp + lo, byte0 + lo, byte0 + hi);
                 });
                 HIP_TRY(hipMemcpyAsync(d_image.p + byte0, dstp, (size_t)len, hipMemcpyHostToDevice, up));
                 HIP_TRY(hipEventRecord(e->ev_ring[slot], up));
                 ring_busy[slot] = true;
-            } else
+            } else if (one_run)
                 HIP_TRY(hipMemcpyAsync(d_image.p + byte0, run_src + byte0, (size_t)(byte1 - byte0), hipMemcpyHostToDevice, up));
+            else {   // several runs in one piece: gathered, one copy
+                gathered.emplace_back((size_t)(byte1 - byte0));
+                copy_image(gathered.back().data(), byte0, byte1);
+                HIP_TRY(hipMemcpyAsync(d_image.p + byte0, gathered.back().data(), (size_t)(byte1 - byte0), hipMemcpyHostToDevice, up));
+            }
             if (up != st) {
                 hipEvent_t x;
                 HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
@@ -4110,7 +4201,6 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
             hipLaunchKernelGGL(k_bgzf_crc, dim3((unsigned)(m1 - m0)), dim3(64), 0, ks, d_stream.p, d_members.p, m0, m1, d_crc.p, d_crc.p + 256, d_status.p);
             byte0 = byte1;
             m0 = m1;
-        }
         }
         clk.note("every piece copied into the page-locked ring and queued");
         for (int k = 0; k < naux; ++k) {   // the main stream goes on behind all of them
@@ -4141,8 +4231,10 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     uint32_t n_ref = 0;
     // (region read: the header is looked for in the leading members only -- what follows them is the span, from some
     // record in the middle of the file on; a header that does not fit them makes the caller come back with more)
+    // stream offset at which member index m starts (total_u past the last)
+    auto uoff_of = [&](int m) -> uint64_t { return m < nm ? members[(size_t)m].uoff : total_u; };
     const size_t header_limit = (span && span_first_member >= 0) ? (size_t)(members[(size_t)span_first_member].uoff + members[(size_t)span_first_member].ulen)
-                                                                 : (size_t)total_u;
+                                : chunked ? (size_t)(runs.empty() ? 0 : uoff_of(runs[0].m1)) : (size_t)total_u;
     {
         std::vector<uint8_t> head;
         size_t want = std::min<size_t>(header_limit, (size_t)1 << 16);
@@ -4188,7 +4280,32 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     // region read: the records start where the index says (a record start inside the span's first member) and end at its
     // last chunk's end; a header-only read (no chunk at all) has no records
     uint64_t stop_at = total_u;
-    if (span) {
+    // multi-chunk read: every run's record chain, {start, stop} by run, and the run of every member
+    std::vector<uint64_t> run_bounds;
+    std::vector<uint32_t> member_run;
+    DevBuf<uint64_t> d_run_bounds;
+    DevBuf<uint32_t> d_member_run;
+    if (chunked) {
+        run_bounds.assign(2 * std::max<size_t>(runs.size(), 1), ~0ull);
+        member_run.assign((size_t)std::max(nm, 1), 0u);
+        for (size_t r = 0; r < runs.size(); ++r)
+            for (int m = runs[r].m0; m < runs[r].m1; ++m) member_run[(size_t)m] = (uint32_t)r;
+        for (const ChunkAt &c : chunk_at) {
+            const uint64_t a = uoff_of(c.s_idx) + c.ub, z = uoff_of(c.e_idx) + c.ue;
+            if (a < first_record || z < a || z > total_u)
+                return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk starts inside the header or ends before it starts): %s", path.c_str());
+            // (the run that holds the chunk's first member; runs ascend by file offset)
+            auto it = std::upper_bound(runs.begin(), runs.end(), c.cb, [](int64_t x, const Run &r) { return x < r.file_lo; });
+            const size_t r = (size_t)(it - runs.begin()) - 1;
+            if (run_bounds[2 * r] == ~0ull) run_bounds[2 * r] = a;
+            run_bounds[2 * r + 1] = z;
+        }
+        for (size_t r = 0; r < runs.size(); ++r)   // a run without a chunk (the header's): no record
+            if (run_bounds[2 * r] == ~0ull) run_bounds[2 * r] = run_bounds[2 * r + 1] = uoff_of(runs[r].m1);
+        rc = d_run_bounds.upload(run_bounds, st);
+        if (rc == PC_OK) rc = d_member_run.upload(member_run, st);
+        if (rc != PC_OK) return rc;
+    } else if (span) {
         if (span_first_member < 0) { first_record = total_u; stop_at = total_u; }
         else {
             const uint64_t fr = members[(size_t)span_first_member].uoff + (span->voff_begin & 0xffffu);
@@ -4209,15 +4326,31 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
         HIP_TRY(hipMemsetAsync(d_forced.p, 0xff, (size_t)nm * 8, st));
         int from = 0;
         uint64_t expected = first_record;
+        uint32_t cur_run = chunked ? member_run[0] : 0u;   // (multi-chunk read: the run whose chain `expected` follows)
+        if (chunked) expected = run_bounds[2 * (size_t)cur_run];
         for (int round = 0;; ++round) {
-            hipLaunchKernelGGL(k_bam_chain, dim3((unsigned)(nm - from)), dim3(64), 0, st, d_stream.p, total_u, d_members.p, nm, from, n_ref, first_record,
-                               d_forced.p, d_chain.p, d_rec_off.p, stop_at);
+            if (chunked)
+                hipLaunchKernelGGL(k_bam_chain<true>, dim3((unsigned)(nm - from)), dim3(64), 0, st, d_stream.p, total_u, d_members.p, nm, from, n_ref, first_record,
+                                   d_forced.p, d_chain.p, d_rec_off.p, stop_at, d_member_run.p, d_run_bounds.p);
+            else
+                hipLaunchKernelGGL(k_bam_chain<false>, dim3((unsigned)(nm - from)), dim3(64), 0, st, d_stream.p, total_u, d_members.p, nm, from, n_ref, first_record,
+                                   d_forced.p, d_chain.p, d_rec_off.p, stop_at, (const uint32_t *)nullptr, (const uint64_t *)nullptr);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(chain.data() + from, d_chain.p + from, (size_t)(nm - from) * sizeof(MemberChain), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             int redo = -1;
             for (int m = from; m < nm; ++m) {
-                const uint64_t begin = members[(size_t)m].uoff, end = std::min<uint64_t>(begin + members[(size_t)m].ulen, stop_at);
+                uint64_t stop_m = stop_at;
+                if (chunked) {   // each run settles from its forced start and has to end exactly at its stop
+                    if (member_run[(size_t)m] != cur_run) {
+                        if (expected != run_bounds[2 * (size_t)cur_run + 1])
+                            return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk ends inside a record): %s", path.c_str());
+                        cur_run = member_run[(size_t)m];
+                        expected = run_bounds[2 * (size_t)cur_run];
+                    }
+                    stop_m = run_bounds[2 * (size_t)cur_run + 1];
+                }
+                const uint64_t begin = members[(size_t)m].uoff, end = std::min<uint64_t>(begin + members[(size_t)m].ulen, stop_m);
                 nrec_of[(size_t)m] = 0;
                 if (expected >= end) continue;                      // no record starts in this member (or it lies behind the span)
                 const MemberChain &mc = chain[(size_t)m];
@@ -4236,6 +4369,7 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
             from = redo;
             if (round > nm + 8) return fail(PC_ERR_STATE, "pc_bam_open: the record chain of %s did not settle", path.c_str());
         }
+        if (chunked) stop_at = run_bounds[2 * (size_t)cur_run + 1];
         if (expected != stop_at) {   // the last record runs past (or stops short of) the end of the stream
             if (span) return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk ends inside a record): %s", path.c_str());
             truncated = true;
@@ -4394,6 +4528,11 @@ int pc_bam_counts(pc_bam *b, int64_t *counts) {
     if (!b || !counts) return fail(PC_ERR_ARG, "pc_bam_counts: bad arguments");
     counts[0] = b->n; counts[1] = b->nrun; counts[2] = b->mapped; counts[3] = b->total; counts[4] = (int64_t)b->wide_idx.size();
     counts[5] = b->members; counts[6] = b->inflated_bytes; counts[7] = b->chain_restarts;
+    return PC_OK;
+}
+int pc_bam_stats(pc_bam *b, int64_t *out4) {
+    if (!b || !out4) return fail(PC_ERR_ARG, "pc_bam_stats: bad arguments");
+    out4[0] = b->uploaded_bytes; out4[1] = b->runs; out4[2] = b->members; out4[3] = b->inflated_bytes;
     return PC_OK;
 }
 int pc_bam_timing(pc_bam *b, double *ms4) {
@@ -4650,6 +4789,42 @@ int pc_add_alignment_bam_span(pc_engine *e, const char *path, uint64_t voff_begi
     if (!e || !path) return fail(PC_ERR_ARG, "pc_add_alignment_bam_span: bad arguments");
     BamSpan sp;
     int rc = span_args("pc_add_alignment_bam_span", voff_begin, voff_end, nreg, tid, beg, end, sp);
+    if (rc != PC_OK) return rc;
+    MappedFile mf;
+    rc = mf.open(path, 0);
+    if (rc != PC_OK) return rc;
+    return add_alignment_bam_impl(e, mf.p, (int64_t)mf.size, path, mapped, nullptr, &sp);
+}
+
+static int chunk_args(const char *what, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg, const int32_t *tid, const int64_t *beg,
+                      const int64_t *end, BamSpan &sp) {
+    if (nchunk < 0 || (nchunk > 0 && (!voff_beg || !voff_end))) return fail(PC_ERR_ARG, "%s: bad chunk list", what);
+    for (int k = 0; k < nchunk; ++k)
+        if (voff_end[k] <= voff_beg[k] || (k > 0 && voff_beg[k] < voff_end[k - 1]))
+            return fail(PC_ERR_ARG, "%s: chunks must be non-empty, ascending and disjoint", what);
+    int rc = span_args(what, nchunk ? voff_beg[0] : 0, nchunk ? voff_end[nchunk - 1] : 0, nreg, tid, beg, end, sp);
+    if (rc != PC_OK) return rc;
+    sp.nchunk = nchunk; sp.cbeg = voff_beg; sp.cend = voff_end;
+    return PC_OK;
+}
+
+int pc_bam_open_chunks(pc_engine *e, const char *path, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg, const int32_t *tid,
+                       const int64_t *beg, const int64_t *end, pc_bam **out) {
+    if (!e || !path || !out) return fail(PC_ERR_ARG, "pc_bam_open_chunks: bad arguments");
+    BamSpan sp;
+    int rc = chunk_args("pc_bam_open_chunks", nchunk, voff_beg, voff_end, nreg, tid, beg, end, sp);
+    if (rc != PC_OK) return rc;
+    MappedFile mf;
+    rc = mf.open(path, 0);
+    if (rc != PC_OK) return rc;
+    return bam_open_span_retry(e, mf.p, (int64_t)mf.size, path, out, nullptr, &sp);
+}
+
+int pc_add_alignment_bam_chunks(pc_engine *e, const char *path, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg,
+                                const int32_t *tid, const int64_t *beg, const int64_t *end, int64_t *mapped) {
+    if (!e || !path) return fail(PC_ERR_ARG, "pc_add_alignment_bam_chunks: bad arguments");
+    BamSpan sp;
+    int rc = chunk_args("pc_add_alignment_bam_chunks", nchunk, voff_beg, voff_end, nreg, tid, beg, end, sp);
     if (rc != PC_OK) return rc;
     MappedFile mf;
     rc = mf.open(path, 0);

@@ -143,8 +143,8 @@ class Engine(object):
         counts exactly as after ``add_alignment_file(read_bam(path))``; callers that also want the reads themselves
         (``reads_out`` as objects, host-side filters) use :func:`plastid_amd.bam.read_bam_gpu` instead.
         `regions`: stage only the alignments that overlap one of them (``(chrom, start, end)`` or |GenomicSegments|),
-        through the file's BAI index -- the BGZF members of ONE span of the file, from the first to the last index chunk of the regions (what lies between far-apart regions included; the overlap test drops it), are uploaded and inflated
-        (``pc_add_alignment_bam_span``; what one rank of a multi-GPU job does with its genome range of a shared file);
+        through the file's BAI index -- only the BGZF members the index chunks of the regions point to are uploaded and inflated
+        (``pc_add_alignment_bam_chunks``; what one rank of a multi-GPU job does with its genome range of a shared file);
         the return value is then the number of mapped reads among those staged."""
         import os
         if not os.path.isfile(path):
@@ -153,8 +153,9 @@ class Engine(object):
         if regions is not None:
             from .bam import resolve_regions
             sp = resolve_regions(path, regions)
-            rc = self._lib.pc_add_alignment_bam_span(self._h, os.fsencode(path), sp["voff_begin"], sp["voff_end"], len(sp["tid"]),
-                                                     _ptr(sp["tid"]), _ptr(sp["beg"]), _ptr(sp["end"]), ctypes.byref(mapped))
+            cb, ce = np.ascontiguousarray(sp["chunks"][:, 0]), np.ascontiguousarray(sp["chunks"][:, 1])
+            rc = self._lib.pc_add_alignment_bam_chunks(self._h, os.fsencode(path), len(cb), _ptr(cb), _ptr(ce), len(sp["tid"]),
+                                                       _ptr(sp["tid"]), _ptr(sp["beg"]), _ptr(sp["end"]), ctypes.byref(mapped))
         else:
             rc = self._lib.pc_add_alignment_bam_path(self._h, os.fsencode(path), ctypes.byref(mapped))
         check(rc)
