@@ -887,6 +887,7 @@ __global__ __launch_bounds__(kRangesWG) void k_tile_ranges(const Tile *__restric
                     return nk > R;
                 };
                 if (CG == 16) {
+                    static_assert(kMaxSub <= 32, "the CG == 16 path gives every lane of a group two sub-windows (S <= kMaxSub)");
                     bool mrg = false, hv[2] = {false, false};
 #pragma unroll
                     for (int j = 0; j < 2; ++j)

@@ -458,6 +458,15 @@ static int stage_threads(int64_t n) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(t, n / (1 << 20) + 1)); // a thread is not worth < 1 M records
 }
 
+// The FLAG / MAPQ / NH filter as the setters leave it (pc_set_flag_filter, pc_set_nh_filter); all zero: no filter.
+struct FilterState {
+    bool ff_on = false;
+    uint32_t require = 0, exclude = 0, min_mapq = 0, max_nh = 0;
+    bool operator==(const FilterState &o) const {
+        return ff_on == o.ff_on && require == o.require && exclude == o.exclude && min_mapq == o.min_mapq && max_nh == o.max_nh;
+    }
+};
+
 struct StagedFile {
     int64_t n = 0, nrun = 0, nlong = 0;
     int W = 1;               // max reference span of the records scanned by the window kernels
@@ -506,6 +515,10 @@ struct StagedFile {
     bool have_sam = false;
     DevBuf<uint16_t> sam_nh;           // the NH:i tag of every record (0: none): pc_set_alignment_nh, or straight from the device decoder
     bool have_nh = false;
+    // the filter whose verdicts the exclusion bits of the staged records hold right now (none: the caller's bits alone);
+    // `applied_valid` false: the columns those verdicts were read from have been replaced since
+    FilterState applied;
+    bool applied_valid = true;
     // center streams (built at the first center-rule count that needs them; dropped when the host-side filters change)
     DevBuf<uint2> cs_ent[3];
     DevBuf<uint32_t> cs_soff[3];
@@ -627,6 +640,11 @@ struct pc_engine {
     uint32_t ff_require = 0, ff_exclude = 0, ff_min_mapq = 0;
     uint32_t ff_max_nh = 0;      // pc_set_nh_filter: keep only reads with an NH:i tag of at most this many reported alignments (0: no such test)
     bool filter_on() const { return ff_on || ff_max_nh != 0u; }
+    FilterState filter_state() const {
+        FilterState s;
+        s.ff_on = ff_on; s.require = ff_require; s.exclude = ff_exclude; s.min_mapq = ff_min_mapq; s.max_nh = ff_max_nh;
+        return s;
+    }
     bool pinned_busy = false;
     PinnedBuf pinned;            // host side of the plan-table upload (reused: ev_pinned is waited for before it is rewritten)
     PinnedBuf bam_ring[2];       // page-locked halves the image of a large BAM file crosses PCIe through (filled by all host threads)
@@ -690,9 +708,8 @@ struct pc_plan {
     DevBuf<GatherSeg> d_gsegs_own;
     bool has_sums = false;       // some slices are summed (out_step 0): the output is an accumulator
     bool out_needs_zero = false; // some queried positions lie outside every tile (unknown contig, clipped)
-    bool hist_clean = false;     // compact histogram known to be all zero (point-rule invariant; `hist_lazy`: in the slices of the merged windows)
+    bool hist_clean = false;     // the WHOLE compact histogram is known to be zero (a lazy count does not need that: it clears the slices it merges)
     bool hist_lazy = false;      // the histogram is large: never cleared as a whole, k_clear_split runs behind every k_tile_ranges
-    int hist_kind = -1;          // 0: holds uint32 zeros / merged point-rule windows; -1: freshly allocated, not cleared yet
     std::vector<CenterChunk> cchunks;
     std::vector<GatherSeg> gsegs;
     std::vector<GatherChunk> gchunks;
@@ -1061,7 +1078,7 @@ int plan_build_gpu(pc_engine *e, pc_plan *p, int64_t nseg, const int32_t *tid, c
     p->d_wcounters.p = (uint32_t *)(d + at_wcounters);
     p->tile_items_zero = true;
     p->wcounters_zero = true;
-    if (hist_here) { p->d_hist.p = d + at_hist; p->hist_kind = 0; p->hist_clean = true; }
+    if (hist_here) { p->d_hist.p = d + at_hist; p->hist_clean = true; }
     p->lazy_center = true;
     p->gpu_built = true;
     p->host_inputs = false;
@@ -2009,6 +2026,26 @@ static int stage_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid,
 
 static int propagate_record_flags(pc_engine *e, StagedFile *sf);
 
+// The columns the engine's filter reads are there for this file: the ONE test of every setter, of pc_update_flags and
+// of the entry points that read the exclusion bits (check_filter_columns).
+static bool columns_present(const pc_engine *e, const StagedFile *sf) {
+    return (!e->ff_on || sf->have_sam) && (!e->ff_max_nh || sf->have_nh);
+}
+
+// Every entry point that reads the exclusion bit of staged records refuses while a filter is set and a file with
+// records lacks the columns the filter reads: that file's verdicts cannot have been applied.
+static int check_filter_columns(const pc_engine *e, const char *who) {
+    for (size_t f = 0; f < e->files.size(); ++f) {
+        const StagedFile *sf = e->files[f];
+        if (sf->n == 0) continue;
+        if (e->ff_max_nh && !sf->have_nh)
+            return fail(PC_ERR_STATE, "%s: an NH filter is set but alignment file %d has no NH column (pc_set_alignment_nh)", who, (int)f);
+        if (e->ff_on && !sf->have_sam)   // a file staged after pc_set_flag_filter gets its verdicts when its columns arrive: not counted without them
+            return fail(PC_ERR_STATE, "%s: a FLAG / MAPQ filter is set but alignment file %d has no FLAG / MAPQ columns (pc_set_alignment_sam)", who, (int)f);
+    }
+    return PC_OK;
+}
+
 int pc_update_flags(pc_engine *e, int file, int64_t n, const uint8_t *flags) {
     if (!e || file < 0 || file >= (int)e->files.size()) return fail(PC_ERR_ARG, "pc_update_flags: bad file index");
     StagedFile *sf = e->files[file];
@@ -2022,10 +2059,15 @@ int pc_update_flags(pc_engine *e, int file, int64_t n, const uint8_t *flags) {
     HIP_TRY(hipMemcpyAsync(e->d_flags.p, flags, (size_t)n, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_update_flags, dim3((unsigned)((n + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->rec.p, sf->stream.p,
                        e->d_flags.p, n);
-    if (e->filter_on() && (sf->have_sam || !e->ff_on) && (sf->have_nh || !e->ff_max_nh))   // the FLAG / MAPQ / NH filter's verdicts on top of the caller's
+    // (k_update_flags has left the caller's verdicts alone in the exclusion bits)
+    sf->applied = FilterState();
+    sf->applied_valid = true;
+    if (e->filter_on() && columns_present(e, sf)) {   // the FLAG / MAPQ / NH filter's verdicts on top of the caller's
         hipLaunchKernelGGL(k_flag_filter, dim3((unsigned)((n + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->rec.p, sf->stream.p, sf->have_sam ? sf->sam_flag.p : nullptr,
                            sf->have_sam ? sf->sam_mapq.p : nullptr, n, 1u, e->ff_on ? e->ff_require : 0u, e->ff_on ? e->ff_exclude : 0u, e->ff_on ? e->ff_min_mapq : 0u,
                            sf->have_nh ? sf->sam_nh.p : nullptr, e->ff_max_nh);
+        sf->applied = e->filter_state();
+    }
     const int prc = propagate_record_flags(e, sf);
     if (prc != PC_OK) return prc;
     HIP_TRY(hipStreamSynchronize(st)); // the caller's flag buffer may go away
@@ -2070,7 +2112,23 @@ static int apply_flag_filter(pc_engine *e, StagedFile *sf) {
                        sf->have_sam ? sf->sam_flag.p : nullptr, sf->have_sam ? sf->sam_mapq.p : nullptr, sf->n, e->filter_on() ? 1u : 0u,
                        e->ff_on ? e->ff_require : 0u, e->ff_on ? e->ff_exclude : 0u, e->ff_on ? e->ff_min_mapq : 0u,
                        sf->have_nh ? sf->sam_nh.p : nullptr, e->ff_max_nh);
+    sf->applied = e->filter_state();
+    sf->applied_valid = true;
     return propagate_record_flags(e, sf);
+}
+
+// After any change of the filter or of a file's columns: bring the verdicts of every file up to date whose columns
+// allow it (the others are refused by check_filter_columns until theirs arrive).  A file whose exclusion bits already
+// hold the verdicts of the current filter costs nothing.
+static int sync_flag_filter(pc_engine *e) {
+    const FilterState want = e->filter_state();
+    for (StagedFile *sf : e->files) {
+        if (sf->n == 0 || !columns_present(e, sf)) continue;
+        if (sf->applied_valid && sf->applied == want) continue;
+        const int rc = apply_flag_filter(e, sf);
+        if (rc != PC_OK) return rc;
+    }
+    return PC_OK;
 }
 
 int pc_set_alignment_sam(pc_engine *e, int file, int64_t n, const uint16_t *flag, const uint8_t *mapq) {
@@ -2087,8 +2145,8 @@ int pc_set_alignment_sam(pc_engine *e, int file, int64_t n, const uint16_t *flag
         HIP_TRY(hipMemcpyAsync(sf->sam_mapq.p, mapq, (size_t)n, hipMemcpyHostToDevice, e->stream));
     }
     sf->have_sam = true;
-    int rc = PC_OK;
-    if (e->ff_on && (sf->have_nh || !e->ff_max_nh)) rc = apply_flag_filter(e, sf);
+    if (e->ff_on || sf->applied.ff_on) sf->applied_valid = false;   // verdicts read from the columns just replaced, if any
+    const int rc = sync_flag_filter(e);
     HIP_TRY(hipStreamSynchronize(e->stream));   // the caller's arrays may go away
     return rc;
 }
@@ -2105,8 +2163,8 @@ int pc_set_alignment_nh(pc_engine *e, int file, int64_t n, const uint16_t *nh) {
         HIP_TRY(hipMemcpyAsync(sf->sam_nh.p, nh, (size_t)n * 2, hipMemcpyHostToDevice, e->stream));
     }
     sf->have_nh = true;
-    int rc = PC_OK;
-    if (e->ff_max_nh && (sf->have_sam || !e->ff_on)) rc = apply_flag_filter(e, sf);
+    if (e->ff_max_nh || sf->applied.max_nh) sf->applied_valid = false;
+    const int rc = sync_flag_filter(e);
     HIP_TRY(hipStreamSynchronize(e->stream));   // the caller's array may go away
     return rc;
 }
@@ -2121,13 +2179,7 @@ int pc_set_nh_filter(pc_engine *e, int max_nh) {
     HIP_TRY(hipSetDevice(e->device));
     if (e->ff_max_nh == (uint32_t)max_nh) return PC_OK;
     e->ff_max_nh = (uint32_t)max_nh;
-    for (StagedFile *sf : e->files) {
-        if (!sf->have_nh && !sf->have_sam) continue;
-        if ((e->ff_on && !sf->have_sam)) continue;   // (pc_count refuses such a file until its columns arrive)
-        const int rc = apply_flag_filter(e, sf);
-        if (rc != PC_OK) return rc;
-    }
-    return PC_OK;
+    return sync_flag_filter(e);
 }
 
 int pc_set_flag_filter(pc_engine *e, int enabled, uint32_t require, uint32_t exclude, int min_mapq) {
@@ -2144,13 +2196,7 @@ int pc_set_flag_filter(pc_engine *e, int enabled, uint32_t require, uint32_t exc
     if (same) return PC_OK;
     e->ff_on = enabled != 0;
     e->ff_require = enabled ? require : 0u; e->ff_exclude = enabled ? exclude : 0u; e->ff_min_mapq = enabled ? (uint32_t)min_mapq : 0u;
-    for (StagedFile *sf : e->files) {
-        if (!sf->have_sam) continue;
-        if (e->ff_max_nh && !sf->have_nh) continue;   // (pc_count refuses such a file until its NH column arrives)
-        const int rc = apply_flag_filter(e, sf);
-        if (rc != PC_OK) return rc;
-    }
-    return PC_OK;
+    return sync_flag_filter(e);
 }
 
 int pc_set_mapping(pc_engine *e, int kind, int param, const int32_t *fw, const int32_t *rc, int table_len,
@@ -2653,7 +2699,7 @@ int pc_plan_create(pc_engine *e, int64_t nseg, const int32_t *tid, const int64_t
         p->d_wcounters.p = (uint32_t *)(d + at_wcounters);
         p->tile_items_zero = true;
         p->wcounters_zero = true;
-        if (hist_here) { p->d_hist.p = d + at_hist; p->hist_kind = 0; p->hist_clean = true; }
+        if (hist_here) { p->d_hist.p = d + at_hist; p->hist_clean = true; }
         if (!through_pinned) {   // the copies read the plan's own vectors, which live as long as the plan
             if (copy_failed) rc = fail(PC_ERR_HIP, "pc_plan_create: upload failed");
         } else if (hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) rc = fail(PC_ERR_HIP, "pc_plan_create: upload failed");
@@ -2719,14 +2765,7 @@ int pc_count(pc_engine *e, pc_plan *p, int out_dtype) {
     if (e->files.empty()) return fail(PC_ERR_STATE, "pc_count: no alignments staged (pc_add_alignment_file)");
     if (out_dtype != PC_OUT_INT64 && out_dtype != PC_OUT_FLOAT64) return fail(PC_ERR_ARG, "pc_count: bad out_dtype");
     if (p->rows != e->rows) return fail(PC_ERR_ARG, "pc_count: plan built for %d rows, mapping rule has %d", p->rows, e->rows);
-    if (e->ff_max_nh)
-        for (size_t f = 0; f < e->files.size(); ++f)
-            if (e->files[f]->n > 0 && !e->files[f]->have_nh)
-                return fail(PC_ERR_STATE, "pc_count: an NH filter is set but alignment file %d has no NH column (pc_set_alignment_nh)", (int)f);
-    if (e->ff_on)   // a file staged after pc_set_flag_filter gets its verdicts when its columns arrive: not counted without them
-        for (size_t f = 0; f < e->files.size(); ++f)
-            if (e->files[f]->n > 0 && !e->files[f]->have_sam)
-                return fail(PC_ERR_STATE, "pc_count: a FLAG / MAPQ filter is set but alignment file %d has no FLAG / MAPQ columns (pc_set_alignment_sam)", (int)f);
+    { const int frc = check_filter_columns(e, "pc_count"); if (frc != PC_OK) return frc; }
     const bool center = e->kind == PC_MAP_CENTER;
     if ((center || e->norm_on) && out_dtype != PC_OUT_FLOAT64)
         return fail(PC_ERR_ARG, "pc_count: center mapping / normalisation produce float64 (map_factories.pyx:230, genome_array.py:826-827)");
@@ -2775,15 +2814,18 @@ int pc_count(pc_engine *e, pc_plan *p, int out_dtype) {
         HIP_TRY(hipMemsetAsync(p->d_out.p, 0, (size_t)p->out_elems * 8, st));
     // (a large histogram is not cleared as a whole: k_clear_split zeroes the slices of the merged windows behind every
     // k_tile_ranges, which is all that is ever read of it)
+    // `hist_clean` says that the WHOLE histogram is zero: true once it has been cleared as a whole, and kept by every
+    // count (k_clear_split only zeroes, k_gather_split zeroes what it merged).  Lazy counts never make it true, so the
+    // first count after the knobs turn lazy off (pc_reload_knobs) clears what the lazy ones left alone.
     p->hist_lazy = !center && (int64_t)hist_bytes >= e->knobs.hist_lazy_bytes && !e->knobs.hist_memset;
-    if (!center && hist_bytes && !(p->hist_clean && p->hist_kind == 0) && !p->hist_lazy) {
+    if (!center && hist_bytes && !p->hist_clean && !p->hist_lazy) {
         HIP_TRY(hipMemsetAsync(p->d_hist.p, 0, hist_bytes, st));
+        p->hist_clean = true;
     }
     if (e->prof_level >= 2) HIP_TRY(hipEventRecord(e->ev[1], st));
 
     if (!center) {
-        p->hist_kind = 0;
-        p->hist_clean = true; // k_gather_split clears what the split tiles merged
+        // (k_gather_split clears what the split tiles merged: a histogram that was all zero stays so)
         // ---- a plan of ONE window over one file (`ga[segment]`): the whole count is one launch -- the workgroup looks its
         // record ranges up itself; no work list, no second window class, no merge pass, no events
         // (not under the stratified rule: its 16-bit bins rely on the work lists, which cut or merge a window that scans
@@ -3416,8 +3458,7 @@ int pc_query_segment(pc_engine *e, int32_t tid, int64_t start, int64_t end, uint
     if (len <= 0 || len > kQueryMax || start < 0 || end > 0x7fffffffLL) return fail(PC_ERR_STATE, "pc_query_segment: the segment does not fit one window (1 .. %d positions)", kQueryMax);
     if (tid < 0 || tid >= e->ntid) return fail(PC_ERR_ARG, "pc_query_segment: reference id out of range");
     StagedFile *sf = e->files[0];
-    if (e->ff_on && sf->n > 0 && !sf->have_sam) return fail(PC_ERR_STATE, "pc_query_segment: a FLAG / MAPQ filter is set but the alignment file has no FLAG / MAPQ columns");
-    if (e->ff_max_nh && sf->n > 0 && !sf->have_nh) return fail(PC_ERR_STATE, "pc_query_segment: an NH filter is set but the alignment file has no NH column");
+    { const int frc = check_filter_columns(e, "pc_query_segment"); if (frc != PC_OK) return frc; }
     HIP_TRY(hipSetDevice(e->device));
     if (!e->q_host) {
         HIP_TRY(hipHostMalloc((void **)&e->q_host, (size_t)kQueryMax * 8 + 64, hipHostMallocMapped));
@@ -3644,6 +3685,7 @@ int pc_mapped_reads(pc_engine *e, int file, int64_t rec_lo, int64_t rec_hi, int3
                     uint8_t strand, uint8_t *mask) {
     if (!e || file < 0 || file >= (int)e->files.size()) return fail(PC_ERR_ARG, "pc_mapped_reads: bad file index");
     if (!e->have_map) return fail(PC_ERR_STATE, "pc_mapped_reads: no mapping rule set");
+    { const int frc = check_filter_columns(e, "pc_mapped_reads"); if (frc != PC_OK) return frc; }
     StagedFile *f = e->files[file];
     if (rec_lo < 0 || rec_hi > f->n || rec_hi < rec_lo || (rec_hi > rec_lo && !mask)) return fail(PC_ERR_ARG, "pc_mapped_reads: bad record range");
     (void)tid;
@@ -3664,6 +3706,7 @@ int pc_mapped_reads_batch(pc_engine *e, pc_plan *p, int64_t *offsets, int64_t *t
     if (!e || !p || p->e != e || !offsets || !total) return fail(PC_ERR_ARG, "pc_mapped_reads_batch: bad arguments");
     if (!e->have_map) return fail(PC_ERR_STATE, "pc_mapped_reads_batch: no mapping rule set");
     if (e->files.empty()) return fail(PC_ERR_STATE, "pc_mapped_reads_batch: no alignments staged");
+    { const int frc = check_filter_columns(e, "pc_mapped_reads_batch"); if (frc != PC_OK) return frc; }
     HIP_TRY(hipSetDevice(e->device));
     int rc = refresh_file_views(e);
     if (rc != PC_OK) return rc;
@@ -4655,7 +4698,7 @@ static int add_alignment_bam_impl(pc_engine *e, const void *image, int64_t size,
         sf->have_sam = true;
         sf->sam_nh.swap(b->nh);
         sf->have_nh = true;
-        return e->filter_on() ? apply_flag_filter(e, sf) : PC_OK;
+        return sync_flag_filter(e);
     }
     std::vector<int32_t> tid((size_t)n), pos((size_t)n), bs((size_t)m), bl((size_t)m), wa((size_t)nw), wn((size_t)nw);
     std::vector<uint16_t> alen((size_t)n);

@@ -103,8 +103,7 @@ class Engine(object):
             self.set_alignment_sam(self.nfiles - 1, packed.flag16, packed.mapq)
         if getattr(packed, "nh", None) is not None:
             # the NH:i tag of every record (2 bytes each): what FlagFilterFactory(max_nh=...) tests on the GPU
-            nh = _c(packed.nh, np.uint16)
-            check(self._lib.pc_set_alignment_nh(self._h, self.nfiles - 1, len(nh), _ptr(nh)))
+            self.set_alignment_nh(self.nfiles - 1, packed.nh)
 
     def set_alignment_sam(self, file_index, flag16, mapq):
         """Hand the engine the SAM FLAG words and MAPQ values of a staged file (``pc_set_alignment_sam``)."""
@@ -112,6 +111,11 @@ class Engine(object):
         if len(flag16) != len(mapq):
             raise ValueError("flag16 / mapq differ in length")
         check(self._lib.pc_set_alignment_sam(self._h, int(file_index), len(flag16), _ptr(flag16), _ptr(mapq)))
+
+    def set_alignment_nh(self, file_index, nh):
+        """Hand the engine the ``NH:i`` tags of a staged file, 0 where a record has none (``pc_set_alignment_nh``)."""
+        nh = _c(nh, np.uint16)
+        check(self._lib.pc_set_alignment_nh(self._h, int(file_index), len(nh), _ptr(nh)))
 
     def set_nh_filter(self, max_nh=0):
         """Keep a read iff it carries an ``NH:i`` tag of at most `max_nh` reported alignments (``pc_set_nh_filter``;
