@@ -347,8 +347,13 @@ int pc_add_alignment_bam_path(pc_engine *e, const char *path, int64_t *mapped);
  * Only the members of the span -- and the leading ones that hold the header -- are uploaded and inflated; the record
  * chain starts at the record the index points to; a placed record stays iff pos < end && endpos > beg for one of the
  * regions (htslib's rule, as the host reader applies it).  counts[2] / *mapped = mapped records among those kept (the
- * whole file's count lives in the index).  One rank of a multi-GPU job stages its genome range of ONE shared file this
- * way.  Errors: as pc_bam_open, plus PC_ERR_ARG when the span does not fit the file (a foreign index). */
+ * whole file's count lives in the index).
+ * A span is read as the chunk list of ONE chunk [voff_begin, voff_end) (none for 0, 0) by pc_bam_open_chunks below, with
+ * that call's checks and errors: every offset has to name a BGZF member of the file and a place inside its payload.  For
+ * a span that no valid index holds this is stricter than the span reader of ABI 6 was; among other things, one that does
+ * not start at a BGZF member is PC_ERR_ARG "the index does not belong to this BAM file (...)" (not the error of the
+ * member walk that ran into it), and one that ends at the file's size with a non-zero offset in the payload -- inside a
+ * member that does not exist -- is refused with the same message (it is not read up to the end of the file). */
 int pc_bam_open_span(pc_engine *e, const char *path, uint64_t voff_begin, uint64_t voff_end, int nreg, const int32_t *tid,
                      const int64_t *beg, const int64_t *end, pc_bam **out);
 int pc_add_alignment_bam_span(pc_engine *e, const char *path, uint64_t voff_begin, uint64_t voff_end, int nreg, const int32_t *tid,
@@ -361,8 +366,9 @@ int pc_add_alignment_bam_span(pc_engine *e, const char *path, uint64_t voff_begi
  * regions cost what they hold, not the file between them.  Chunks that share or touch a member form one RUN (one
  * contiguous upload; one record chain from the run's first chunk start to its last chunk end -- the records between two
  * chunks of a run are decoded and dropped by the overlap rule).  The columns are those pc_bam_open_span gives over the
- * enclosing span, record for record.  Errors: as pc_bam_open_span (a chunk beyond the end of the file, one that does not
- * start at a member, one that ends inside a record: PC_ERR_ARG, "the index does not belong to this BAM file"). */
+ * enclosing span, record for record.  One rank of a multi-GPU job stages its genome range of ONE shared file this way
+ * (SURVEY 8e).  Errors: as pc_bam_open, plus PC_ERR_ARG, "the index does not belong to this BAM file (...)", for a foreign
+ * index: a chunk beyond the end of the file, one that does not start at a member, one that ends inside a record. */
 int pc_bam_open_chunks(pc_engine *e, const char *path, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg,
                        const int32_t *tid, const int64_t *beg, const int64_t *end, pc_bam **out);
 int pc_add_alignment_bam_chunks(pc_engine *e, const char *path, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end,

@@ -796,9 +796,9 @@ struct MemberChain {
 
 // One wave per member.  forced[m] != ~0: start there instead of guessing (the host found that the preceding member's
 // chain ends there).  rec_off[m * kMaxRecPerMember + k] = offset of record k relative to the member's begin.
-// kRuns (multi-chunk region reads): the uploaded members form runs, each a contiguous stretch of the file with a chain of
+// kRuns (region reads): the uploaded members form runs, each a contiguous stretch of the file with a chain of
 // its own; member m belongs to run member_run[m], whose records start at run_bounds[2 r] and stop at run_bounds[2 r + 1]
-// (first_record / stop_at are then ignored).  Without runs the kernel is the one-chain kernel of whole-file and span reads.
+// (first_record / stop_at are then ignored).  Without runs the kernel is the one-chain kernel of whole-file reads.
 template <bool kRuns>
 __global__ __launch_bounds__(64) void k_bam_chain(const uint8_t *__restrict__ stream, uint64_t stream_len, const Member *__restrict__ members,
                                                   int nmembers, int member_lo, uint32_t n_ref, uint64_t first_record, const uint64_t *__restrict__ forced,

@@ -3777,1102 +3777,5 @@ int pc_read_mapped_reads(pc_engine *e, pc_plan *p, uint32_t *rec, int64_t total)
 
 } // extern "C"
 
-// ================================================================== compressed BAM on the GPU (bam_kernels.hip.h)
-#include "bam_kernels.hip.h"
-
-struct pc_bam {
-    pc_engine *e = nullptr;
-    std::string name;
-    int64_t n = 0, nrun = 0, mapped = 0, unplaced = 0, total = 0;
-    std::vector<std::string> ref_names;
-    std::vector<int32_t> ref_lengths;
-    DevBuf<int32_t> tid, pos, blk_start, blk_len;
-    DevBuf<uint16_t> alen;
-    DevBuf<uint8_t> flags, nblk;
-    DevBuf<uint16_t> flag16;           // the SAM FLAG word, MAPQ and l_seq of every staged record (pc_bam_read_sam; the
-    DevBuf<uint8_t> mapq;              // first two stay with the staged file for the FLAG / MAPQ filter)
-    DevBuf<int32_t> lseq;
-    DevBuf<uint16_t> nh;               // the NH:i tag of every staged record, 0 without one (pc_bam_read_nh; stays with the staged file for the NH filter)
-    std::vector<int64_t> wide_idx;
-    std::vector<int32_t> wide_alen, wide_nblk;
-    double ms[4] = {0, 0, 0, 0};     // upload, inflate (+ CRC), record chain, fields + columns
-    int64_t members = 0, inflated_bytes = 0, compressed_bytes = 0;
-    int64_t uploaded_bytes = 0, runs = 0;   // bytes of the file image that went to HBM, contiguous stretches they came from
-    int chain_restarts = 0;
-};
-
-namespace {
-
-uint16_t brd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-uint32_t brd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
-// CRC-32 tables (RFC 1952): the byte table, and the operator that advances the register over kCrcSlice zero bytes
-// split by register byte (k_bgzf_crc combines 64 slice remainders with it)
-struct CrcTables {
-    uint32_t tab[256];
-    uint32_t shift[4 * 256];
-    CrcTables() {
-        for (uint32_t i = 0; i < 256; ++i) {
-            uint32_t c = i;
-            for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xedb88320u ^ (c >> 1) : c >> 1;
-            tab[i] = c;
-        }
-        for (int b = 0; b < 4; ++b)
-            for (uint32_t v = 0; v < 256; ++v) {
-                uint32_t c = v << (8 * b);
-                for (int k = 0; k < pcbam::kCrcSlice; ++k) c = tab[c & 0xffu] ^ (c >> 8);
-                shift[b * 256 + v] = c;
-            }
-    }
-};
-const CrcTables &crc_tables() { static const CrcTables t; return t; }
-
-double ms_between(hipEvent_t a, hipEvent_t b) { float t = 0.f; return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
-
-} // namespace
-
-extern "C" {
-
-int pc_bam_close(pc_bam *b) {
-    if (!b) return PC_OK;
-    if (b->e) { (void)hipSetDevice(b->e->device); (void)hipStreamSynchronize(b->e->stream); }
-    delete b;
-    return PC_OK;
-}
-
-namespace {
-struct BamClock {   // PC_BAM_TIMING=1: wall-clock laps of the host side of the GPU decoder
-    bool on = getenv("PC_BAM_TIMING") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char *what) {
-        if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[bam] %-34s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
-    void note(const char *what) {   // time since the last lap, the lap goes on
-        if (!on) return;
-        fprintf(stderr, "[bam]   (%s: %.2f ms into the lap)\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count());
-    }
-};
-} // namespace
-
-// `uploaded` (optional): called once, with the stream the image is uploaded on, when the last piece has been queued -- once
-// that stream has drained the host copy of the file is not read again (pc_bam_open_path takes its mapping down while the
-// GPU is still inflating).
-typedef std::function<void(hipStream_t)> UploadedHook;
-// A region read (pc_bam_open_span): only the BGZF members between two virtual offsets of the BAI index are uploaded and
-// inflated (plus the leading members that hold the header), and only the records that overlap one of the regions stay.
-// A multi-chunk region read (pc_bam_open_chunks, nchunk >= 0): only the members the chunks [cbeg[k], cend[k]) touch go to HBM;
-// chunks that share or touch a member form one run (one contiguous upload, one record chain from the run's first chunk start
-// to its last chunk end).
-struct BamSpan {
-    uint64_t voff_begin = 0, voff_end = 0;   // (file offset of a member << 16 | offset in its payload): [begin, end); 0, 0: header only
-    int nchunk = -1;                         // >= 0: the chunk list below replaces [voff_begin, voff_end)
-    const uint64_t *cbeg = nullptr, *cend = nullptr;   // ascending, disjoint
-    int nreg = 0;                            // merged regions, ascending by (reference id, start)
-    const int32_t *tid = nullptr;
-    const int64_t *beg = nullptr, *end = nullptr;
-    int64_t header_bytes = (int64_t)256 << 10;   // compressed bytes from the start of the file searched for the header (grown on retry)
-};
-constexpr int PC_RETRY_HEADER = -1000;   // (internal) the header did not fit the leading members that were inflated
-static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const char *name, pc_bam **out, const UploadedHook *uploaded, const BamSpan *span = nullptr);
-
-int pc_bam_open(pc_engine *e, const void *image, int64_t size, const char *name, pc_bam **out) {
-    return bam_open_impl(e, image, size, name, out, nullptr);
-}
-
-static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const char *name, pc_bam **out, const UploadedHook *uploaded, const BamSpan *span) {
-    using namespace pcbam;
-    if (!e || !out || size < 0 || (size > 0 && !image_)) return fail(PC_ERR_ARG, "pc_bam_open: bad arguments");
-    *out = nullptr;
-    const uint8_t *image = (const uint8_t *)image_;
-    const std::string path = name ? name : "<memory>";
-    HIP_TRY(hipSetDevice(e->device));
-    PoolScope pool_scope(&e->pool);   // (the decoder's scratch -- image, inflated stream, record table -- is recycled through the engine's pool)
-    hipStream_t st = e->stream;
-    BamClock clk;
-    // ---- member boundaries (host: a walk over the gzip headers; 18 + bytes per 64 KiB of payload)
-    // one member at `off`: 0, or which defect (the messages below)
-    auto parse_member = [&](int64_t off, Member &mb, int64_t &clen_out) -> int {
-        if (off + 18 > size) return 1;
-        const uint8_t *h = image + off;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return 2;
-        const uint16_t xlen = brd16(h + 10);
-        if (off + 12 + xlen > size) return 3;
-        int bsize = -1;
-        for (size_t x = 0; x + 4 <= xlen;) {
-            const uint8_t *sf = h + 12 + x;
-            const uint16_t slen = brd16(sf + 2);
-            if (sf[0] == 'B' && sf[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = brd16(sf + 4);
-            x += 4 + slen;
-        }
-        if (bsize < 0) return 4;
-        const int64_t clen = (int64_t)bsize + 1;
-        if (off + clen > size) return 5;
-        const uint32_t isize = brd32(image + off + clen - 4);
-        if (isize > (1u << 16)) return 6;
-        const int64_t hdr = 12 + xlen;
-        if (clen < hdr + 8) return 7;
-        mb.coff = (uint64_t)(off + hdr); mb.clen = (uint32_t)(clen - hdr - 8); mb.ulen = isize; mb.uoff = 0;
-        mb.crc = brd32(image + off + clen - 8); mb.pad = 0;
-        clen_out = clen;
-        return 0;
-    };
-    auto walk_error = [&](int code) -> int {
-        switch (code) {
-        case 1: return fail(PC_ERR_ARG, "truncated BGZF header");
-        case 2: return fail(PC_ERR_ARG, "not a BGZF file (bad gzip member header)");
-        case 3: return fail(PC_ERR_ARG, "truncated BGZF extra field");
-        case 4: return fail(PC_ERR_ARG, "BGZF member without BC subfield");
-        case 5: return fail(PC_ERR_ARG, "truncated BGZF member");
-        case 6: return fail(PC_ERR_ARG, "corrupt BGZF member (more than 64 KiB of payload)");
-        default: return fail(PC_ERR_ARG, "BGZF inflate failed in %s", path.c_str());
-        }
-    };
-    std::vector<Member> members;
-    // the parts of the file that go to the GPU: [file_lo, file_hi) lands at image offset dev_lo (one run: the whole file)
-    struct Run { int64_t file_lo, file_hi, dev_lo; int m0, m1; };
-    std::vector<Run> runs;
-    int span_first_member = -1, span_last_member = -1;   // region read: indices (in `members`) of the members at voff_begin >> 16 and at voff_end >> 16
-    const bool chunked = span && span->nchunk >= 0;
-    // multi-chunk read: where each chunk starts and ends, by member (index in `members` of the member at the offset -- of
-    // the next non-empty one for an empty member, members.size() past the last) and offset in its payload
-    struct ChunkAt { int64_t cb; int s_idx, e_idx; uint32_t ub, ue; };
-    std::vector<ChunkAt> chunk_at;
-    if (chunked) {
-        // every member walked: its file offset, its index in `members` (see ChunkAt) and its payload length
-        struct Walked { int64_t off; int idx; uint32_t ulen; };
-        std::vector<Walked> walked;
-        auto belongs_not = [&](const char *why) { return fail(PC_ERR_ARG, "the index does not belong to this BAM file (%s): %s", why, path.c_str()); };
-        // members from `off` on while they start before `hi_excl` (or at `last`, with_last); a new run unless `off` continues the last
-        auto walk = [&](int64_t off, int64_t hi_excl, bool with_last, int64_t last) -> int {
-            if (runs.empty() || runs.back().file_hi != off) runs.push_back(Run{off, off, 0, (int)members.size(), (int)members.size()});
-            const int64_t first = off;
-            while (off < size && (off < hi_excl || (with_last && off <= last))) {
-                Member mb;
-                int64_t clen = 0;
-                const int code = parse_member(off, mb, clen);
-                if (code) return off == first && first > 0 ? belongs_not("a chunk does not start at a BGZF member") : walk_error(code);
-                walked.push_back(Walked{off, (int)members.size(), mb.ulen});
-                if (mb.ulen) members.push_back(mb);
-                off += clen;
-            }
-            runs.back().file_hi = off; runs.back().m1 = (int)members.size();
-            if (runs.back().file_hi == runs.back().file_lo) runs.pop_back();
-            return PC_OK;
-        };
-        auto find = [&](int64_t off) -> const Walked * {
-            auto it = std::lower_bound(walked.begin(), walked.end(), off, [](const Walked &w, int64_t o) { return w.off < o; });
-            return it != walked.end() && it->off == off ? &*it : nullptr;
-        };
-        const int64_t cb0 = span->nchunk > 0 ? (int64_t)(span->cbeg[0] >> 16) : size;
-        int rc0 = walk(0, std::min<int64_t>(span->header_bytes, cb0), false, 0);
-        if (rc0 != PC_OK) return rc0;
-        for (int k = 0; k < span->nchunk; ++k) {
-            const uint64_t vb = span->cbeg[k], ve = span->cend[k];
-            const int64_t cb = (int64_t)(vb >> 16), ce = (int64_t)(ve >> 16);
-            const uint32_t ub = (uint32_t)(vb & 0xffffu), ue = (uint32_t)(ve & 0xffffu);
-            if (cb >= size || ce > size || (ue && ce >= size)) return belongs_not("a chunk lies beyond its end");
-            const int64_t hi = runs.empty() ? 0 : runs.back().file_hi;
-            if (cb < hi && !find(cb)) return belongs_not("a chunk does not start at a BGZF member");
-            rc0 = walk(std::max(cb, hi), ce, ue != 0, ce);
-            if (rc0 != PC_OK) return rc0;
-            ChunkAt c{cb, 0, 0, ub, ue};
-            const Walked *ws = find(cb);
-            if (!ws || ub > ws->ulen) return belongs_not("a chunk does not start at a BGZF member");
-            c.s_idx = ws->idx;
-            if (ue) {
-                const Walked *we = find(ce);
-                if (!we || ue > we->ulen) return belongs_not("a chunk does not end at a BGZF member");
-                c.e_idx = we->idx;
-            } else {
-                if (runs.empty() || runs.back().file_hi != ce) return belongs_not("a chunk does not end at a BGZF member");
-                c.e_idx = (int)members.size();
-            }
-            chunk_at.push_back(c);
-        }
-    } else if (span) {
-        const int64_t cb = (int64_t)(span->voff_begin >> 16), ce = (int64_t)(span->voff_end >> 16);
-        const bool have = span->voff_end > span->voff_begin;
-        if (have && (cb >= size || ce > size)) return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk lies beyond its end): %s", path.c_str());
-        // serial walks: the header's members from the start of the file, the span's from its first member on
-        // (members that start in [lo, hi_excl), and the one at `last` too if asked for)
-        auto walk_run = [&](int64_t lo, int64_t hi_excl, bool with_last, int64_t last, int *idx_last) -> int {
-            Run r; r.file_lo = lo; r.m0 = (int)members.size(); r.dev_lo = 0;
-            int64_t off = lo;
-            while (off < size && (off < hi_excl || (with_last && off <= last))) {
-                Member mb;
-                int64_t clen = 0;
-                const int code = parse_member(off, mb, clen);
-                if (code) return walk_error(code);
-                if (idx_last && off == last) *idx_last = mb.ulen ? (int)members.size() : -1;
-                if (mb.ulen) members.push_back(mb);
-                off += clen;
-            }
-            r.file_hi = off; r.m1 = (int)members.size();
-            if (r.file_hi > r.file_lo) runs.push_back(r);
-            return PC_OK;
-        };
-        int rc0 = walk_run(0, have ? std::min<int64_t>(span->header_bytes, cb) : span->header_bytes, false, 0, nullptr);
-        if (rc0 != PC_OK) return rc0;
-        if (have) {
-            if (!runs.empty() && runs.back().file_hi > cb)   // (member starts are what the walk lands on: cb is none)
-                return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk does not start at a BGZF member): %s", path.c_str());
-            span_first_member = (int)members.size();
-            rc0 = walk_run(cb, ce, (span->voff_end & 0xffffu) != 0, ce, &span_last_member);
-            if (rc0 != PC_OK) return rc0;
-        }
-    }
-    if (span) {
-        // adjacent runs become one (a run is uploaded as one contiguous copy)
-        for (size_t k = 1; k < runs.size();)
-            if (runs[k].file_lo == runs[k - 1].file_hi) { runs[k - 1].file_hi = runs[k].file_hi; runs[k - 1].m1 = runs[k].m1; runs.erase(runs.begin() + (long)k); }
-            else ++k;
-        int64_t dev = 0;
-        for (Run &r : runs) {   // the members' streams by their place in the image on the device
-            r.dev_lo = dev;
-            for (int m = r.m0; m < r.m1; ++m) members[(size_t)m].coff = (uint64_t)((int64_t)members[(size_t)m].coff - r.file_lo + r.dev_lo);
-            dev += r.file_hi - r.file_lo;
-        }
-    }
-    int64_t walked_to = span ? size : 0;
-    // Large files: the walk is a chain of dependent cache misses (40 k members: 5.6 ms), so every host thread walks its
-    // own stretch of the file from the first offset in it where three members in a row parse; a stretch counts only if
-    // the walk of the stretch before it LANDS on its first member -- whatever does not chain is walked again, serially.
-    const int64_t walk_min = getenv("PC_BAM_WALK_MIN") ? atoll(getenv("PC_BAM_WALK_MIN")) : ((int64_t)32 << 20);   // (tests: the parallel walk on small files)
-    const int WT = !span && size >= walk_min && size >= 64 ? std::max(1, std::min(usable_cpus(), 16)) : 1;
-    if (WT > 1) {
-        struct Stretch { int64_t first = -1, landing = -1; std::vector<Member> mem; };
-        std::vector<Stretch> str((size_t)WT);
-        parallel_chunks((int64_t)WT, WT, [&](int, int64_t kb, int64_t ke) {
-            for (int64_t k = kb; k < ke; ++k) {
-                Stretch &sx = str[(size_t)k];
-                const int64_t lo = size * k / WT, hi = size * (k + 1) / WT;
-                int64_t off = lo;
-                if (k > 0) {   // the first offset from which three members parse
-                    off = -1;
-                    for (int64_t c = lo; c < hi && c + 18 <= size; ++c) {
-                        if (image[c] != 31 || image[c + 1] != 139) continue;
-                        int64_t q = c;
-                        bool ok = true;
-                        for (int r = 0; r < 3 && ok && q < size; ++r) {
-                            Member mb;
-                            int64_t cl = 0;
-                            ok = parse_member(q, mb, cl) == 0;
-                            q += cl;
-                        }
-                        if (ok) { off = c; break; }
-                    }
-                    if (off < 0) continue;
-                }
-                sx.first = off;
-                while (off < hi && off < size) {
-                    Member mb;
-                    int64_t cl = 0;
-                    if (parse_member(off, mb, cl) != 0) { sx.first = -1; break; }   // (a defect: the serial walk below reports it)
-                    if (mb.ulen) sx.mem.push_back(mb);
-                    off += cl;
-                }
-                sx.landing = off;
-            }
-        });
-        int64_t expected = 0;
-        for (int k = 0; k < WT; ++k) {
-            const Stretch &sx = str[(size_t)k];
-            if (sx.first < 0 || sx.first != expected) break;
-            members.insert(members.end(), sx.mem.begin(), sx.mem.end());
-            expected = sx.landing;
-        }
-        walked_to = expected;
-    }
-    for (int64_t off = walked_to; off < size;) {
-        Member mb;
-        int64_t clen = 0;
-        const int code = parse_member(off, mb, clen);
-        if (code) return walk_error(code);
-        if (mb.ulen) members.push_back(mb);      // (empty members -- the end-of-file marker -- hold nothing)
-        off += clen;
-    }
-    uint64_t total_u = 0;
-    for (Member &mb : members) { mb.uoff = total_u; total_u += mb.ulen; }
-    if (!span) runs.push_back(Run{0, size, 0, 0, (int)members.size()});
-    int64_t image_bytes = 0;
-    for (const Run &r : runs) image_bytes += r.file_hi - r.file_lo;
-    pc_bam *b = new pc_bam();
-    clk.lap("member walk");
-    b->e = e; b->name = path; b->members = (int64_t)members.size(); b->inflated_bytes = (int64_t)total_u; b->compressed_bytes = size;
-    b->uploaded_bytes = image_bytes; b->runs = (int64_t)runs.size();
-    struct Guard { pc_bam *b; ~Guard() { if (b) pc_bam_close(b); } } guard{b};
-    const int nm = (int)members.size();
-    hipEvent_t ev[5];
-    for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]); } } evg{ev};
-    DevBuf<uint8_t> d_image, d_stream;
-    DevBuf<Member> d_members;
-    DevBuf<uint32_t> d_status, d_crc;
-    // (pieces of the image gathered from several runs, for an upload straight from pageable memory: they live until every
-    // stream has drained, i.e. longer than `drain` below)
-    std::vector<std::vector<uint8_t>> gathered;
-    int rc = d_image.reserve((size_t)std::max<int64_t>(image_bytes, 16) + 16);
-    if (rc == PC_OK) rc = d_stream.reserve((size_t)total_u + 64);
-    if (rc == PC_OK) rc = d_members.reserve((size_t)std::max(nm, 1));
-    if (rc == PC_OK) rc = d_status.reserve((size_t)std::max(nm, 1));
-    if (rc == PC_OK) rc = d_crc.reserve(5 * 256);
-    if (rc != PC_OK) return rc;
-    // An early return between here and the synchronisation behind the inflate launches must not hand the image, the
-    // stream buffer or the page-locked ring back (nor let the caller unmap the file) while the side / auxiliary streams
-    // still use them: drain every stream the decoder queues on before the buffers above go out of scope.
-    struct Drain {
-        pc_engine *e; bool armed;
-        ~Drain() {
-            if (!armed) return;
-            if (e->side_stream) (void)hipStreamSynchronize(e->side_stream);
-            for (int k = 0; k < pc_engine::kAux; ++k) if (e->aux_stream[k]) (void)hipStreamSynchronize(e->aux_stream[k]);
-            (void)hipStreamSynchronize(e->stream);
-        }
-    } drain{e, true};
-    clk.lap("allocations (image, stream)");
-    HIP_TRY(hipEventRecord(ev[0], st));
-    if (nm) HIP_TRY(hipMemcpyAsync(d_members.p, members.data(), (size_t)nm * sizeof(Member), hipMemcpyHostToDevice, st));
-    const CrcTables &ct = crc_tables();
-    HIP_TRY(hipMemcpyAsync(d_crc.p, ct.tab, sizeof(ct.tab), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_crc.p + 256, ct.shift, sizeof(ct.shift), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d_stream.p + total_u, 0, 64, st));
-    HIP_TRY(hipEventRecord(ev[1], st));
-    // ---- upload + inflate, piece by piece: the file image crosses PCIe on the side stream in pieces of ~128 MiB of
-    // whole members while the members of the pieces before are inflated on the main one (one wave per member).  (Every
-    // launch ends in a tail of half-empty CUs -- a member takes ~4 ms and ~3 000 are in flight -- so the pieces are
-    // large: 20 M aligner-like records, 578 MB: one piece 87 ms, 48 MiB pieces 67 ms, 128 MiB 58 ms, 256 MiB 61 ms.)
-    std::vector<uint32_t> status((size_t)nm, 0u);
-    if (nm) {
-        const bool serial_symbols = getenv("PC_BGZF_SERIAL") != nullptr && atoi(getenv("PC_BGZF_SERIAL")) != 0;   // (round 4's first kernel, for comparison)
-        const int64_t piece_bytes = getenv("PC_BAM_PIECE") ? std::max<int64_t>(1, atoll(getenv("PC_BAM_PIECE"))) : ((int64_t)64 << 20);
-        hipStream_t up = e->side_stream ? e->side_stream : st;
-        std::vector<hipEvent_t> landed;
-        struct EvList { std::vector<hipEvent_t> &v; ~EvList() { for (auto x : v) (void)hipEventDestroy(x); } } landed_guard{landed};
-        if (up != st) {   // the side stream starts behind what the main one has queued so far (the buffers' previous users)
-            hipEvent_t x;
-            HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-            landed.push_back(x);
-            HIP_TRY(hipEventRecord(x, st));
-            HIP_TRY(hipStreamWaitEvent(up, x, 0));
-        }
-        // The inflate launches alternate between the main stream and an auxiliary one: a launch ends in a tail of
-        // half-empty CUs (a member takes ~4 ms, ~3 000 are in flight), which the launch of the next piece fills.
-        // (two streams in turn: measured on two boxes, 64 MiB pieces, 20 M aligner-like records: one stream 56 - 58 ms, two
-        // 46.6 - 53.5, four 48.6; PC_BAM_STREAMS = 1 .. 4 for experiments)
-        int naux = up != st ? 1 : 0;
-        if (const char *env = getenv("PC_BAM_STREAMS")) naux = up != st ? std::max(0, std::min(pc_engine::kAux, atoi(env) - 1)) : 0;
-        for (int k = 0; k < naux; ++k)   // (behind what the main stream has queued: the members table, the previous users of the buffers)
-            HIP_TRY(hipStreamWaitEvent(e->aux_stream[k], landed[0], 0));
-        // large files cross PCIe through two page-locked halves of one piece each (made once per engine)
-        bool ring = up != st && image_bytes >= 2 * piece_bytes && !getenv("PC_BAM_NO_RING");
-        bool ring_busy[2] = {false, false};
-        const int ring_threads = std::max(1, std::min(usable_cpus(), 16));
-        if (ring) {
-            // (a piece ends with a whole member: up to 64 KiB beyond piece_bytes)
-            for (int k = 0; k < 2 && ring; ++k) {
-                if (e->bam_ring[k].reserve((size_t)piece_bytes + ((size_t)1 << 17)) != PC_OK) ring = false;
-                if (ring && !e->ev_ring[k] && hipEventCreateWithFlags(&e->ev_ring[k], hipEventDisableTiming) != hipSuccess) ring = false;
-            }
-            (void)hipGetLastError();
-        }
-        // bytes [lo, hi) of the image on the device, from the file, to dst: run by run (the file's bytes of run r start at
-        // r.file_lo - r.dev_lo before its offsets in the image on the device)
-        auto copy_image = [&](uint8_t *dst, int64_t lo, int64_t hi) {
-            auto it = std::upper_bound(runs.begin(), runs.end(), lo, [](int64_t x, const Run &r) { return x < r.dev_lo; });
-            for (size_t r = (size_t)(it - runs.begin()) - 1; r < runs.size() && lo < hi; ++r) {
-                const int64_t rhi = std::min(hi, runs[r].dev_lo + (runs[r].file_hi - runs[r].file_lo));
-                if (rhi > lo) std::memcpy(dst, image + (runs[r].file_lo - runs[r].dev_lo) + lo, (size_t)(rhi - lo));
-                dst += std::max<int64_t>(rhi - lo, 0);
-                lo = std::max(lo, rhi);
-            }
-        };
-        // the run each member belongs to (pieces end where a run ends; one piece may hold several short runs)
-        std::vector<uint32_t> run_of((size_t)nm);
-        for (size_t r = 0; r < runs.size(); ++r)
-            for (int m = runs[r].m0; m < runs[r].m1; ++m) run_of[(size_t)m] = (uint32_t)r;
-        int piece_no = 0;
-        int64_t byte0 = 0;                   // the image is uploaded from here on (gzip headers and trailers ride along)
-        for (int m0 = 0; m0 < nm; ++piece_no) {
-            int m1 = m0;
-            int64_t byte1 = byte0;
-            while (m1 < nm && (byte1 - byte0 < piece_bytes || m1 == m0)) {
-                byte1 = (int64_t)(members[(size_t)m1].coff + members[(size_t)m1].clen);
-                ++m1;
-            }
-            if (m1 == nm) byte1 = image_bytes;
-            else if (run_of[(size_t)m1] != run_of[(size_t)m1 - 1]) byte1 = runs[run_of[(size_t)m1]].dev_lo;   // (the rest of the run before)
-            const uint32_t r0 = run_of[(size_t)m0];
-            const bool one_run = byte1 <= runs[r0].dev_lo + (runs[r0].file_hi - runs[r0].file_lo);
-            const uint8_t *run_src = image + (runs[r0].file_lo - runs[r0].dev_lo);   // (one_run: the piece's bytes in the file)
-            if (ring) {
-                // through a page-locked half: the runtime's own staging of a pageable copy runs on one thread (12 - 20 GB/s);
-                // here every host thread copies its share, and the DMA of one half overlaps the filling of the other
-                const int slot = piece_no & 1;
-                if (ring_busy[slot]) HIP_TRY(hipEventSynchronize(e->ev_ring[slot]));
-                uint8_t *dstp = e->bam_ring[slot].p;
-                const uint8_t *srcp = run_src + byte0;
-                const int64_t len = byte1 - byte0, blk = (int64_t)1 << 20;
-                parallel_chunks((len + blk - 1) / blk, ring_threads, [&](int, int64_t b, int64_t en) {
-                    const int64_t lo = b * blk, hi = std::min(len, en * blk);
-                    if (hi > lo && one_run) std::memcpy(dstp + lo, srcp + lo, (size_t)(hi - lo));
-                    else if (hi > lo) copy_image(dstp + lo, byte0 + lo, byte0 + hi);
-                });
-                HIP_TRY(hipMemcpyAsync(d_image.p + byte0, dstp, (size_t)len, hipMemcpyHostToDevice, up));
-                HIP_TRY(hipEventRecord(e->ev_ring[slot], up));
-                ring_busy[slot] = true;
-            } else if (one_run)
-                HIP_TRY(hipMemcpyAsync(d_image.p + byte0, run_src + byte0, (size_t)(byte1 - byte0), hipMemcpyHostToDevice, up));
-            else {   // several runs in one piece: gathered, one copy
-                gathered.emplace_back((size_t)(byte1 - byte0));
-                copy_image(gathered.back().data(), byte0, byte1);
-                HIP_TRY(hipMemcpyAsync(d_image.p + byte0, gathered.back().data(), (size_t)(byte1 - byte0), hipMemcpyHostToDevice, up));
-            }
-            if (up != st) {
-                hipEvent_t x;
-                HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-                landed.push_back(x);
-                HIP_TRY(hipEventRecord(x, up));
-            }
-            hipStream_t ks = (piece_no % (naux + 1)) ? e->aux_stream[piece_no % (naux + 1) - 1] : st;
-            if (up != st) HIP_TRY(hipStreamWaitEvent(ks, landed.back(), 0));
-            if (serial_symbols) hipLaunchKernelGGL(k_bgzf_inflate<false>, dim3((unsigned)(m1 - m0)), dim3(kInflWG), 0, ks, d_image.p, d_members.p, m0, m1, d_stream.p, d_status.p);
-            else hipLaunchKernelGGL(k_bgzf_inflate<true>, dim3((unsigned)(m1 - m0)), dim3(kInflWG), 0, ks, d_image.p, d_members.p, m0, m1, d_stream.p, d_status.p);
-            // (the piece's CRC check right behind it, on the same stream: it runs while other pieces are still inflated)
-            hipLaunchKernelGGL(k_bgzf_crc, dim3((unsigned)(m1 - m0)), dim3(64), 0, ks, d_stream.p, d_members.p, m0, m1, d_crc.p, d_crc.p + 256, d_status.p);
-            byte0 = byte1;
-            m0 = m1;
-        }
-        clk.note("every piece copied into the page-locked ring and queued");
-        for (int k = 0; k < naux; ++k) {   // the main stream goes on behind all of them
-            hipEvent_t x;
-            HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-            landed.push_back(x);
-            HIP_TRY(hipEventRecord(x, e->aux_stream[k]));
-            HIP_TRY(hipStreamWaitEvent(st, x, 0));
-        }
-        if (uploaded) (*uploaded)(up);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, (size_t)nm * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipEventRecord(ev[2], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    drain.armed = false;   // (the main stream went on behind the side and auxiliary ones: all of them have drained)
-    clk.lap("upload + inflate + crc (sync)");
-    for (int m = 0; m < nm; ++m)
-        if (status[(size_t)m]) {
-            if (getenv("PC_BAM_DEBUG")) fprintf(stderr, "[bam] member %d of %d (%u compressed -> %u bytes at %llu): inflate status %u\n", m, nm,
-                                                members[(size_t)m].clen, members[(size_t)m].ulen, (unsigned long long)members[(size_t)m].uoff, status[(size_t)m]);
-            return fail(PC_ERR_ARG, "%s%s", status[(size_t)m] == (uint32_t)kInfCrc ? "BGZF CRC mismatch in " : "BGZF inflate failed in ", path.c_str());
-        }
-    d_image.release();
-    clk.lap("status check + image release");
-    // ---- BAM header (host, from the head of the inflated stream)
-    uint64_t first_record = 0;
-    uint32_t n_ref = 0;
-    // (region read: the header is looked for in the leading members only -- what follows them is the span, from some
-    // record in the middle of the file on; a header that does not fit them makes the caller come back with more)
-    // stream offset at which member index m starts (total_u past the last)
-    auto uoff_of = [&](int m) -> uint64_t { return m < nm ? members[(size_t)m].uoff : total_u; };
-    const size_t header_limit = (span && span_first_member >= 0) ? (size_t)(members[(size_t)span_first_member].uoff + members[(size_t)span_first_member].ulen)
-                                : chunked ? (size_t)(runs.empty() ? 0 : uoff_of(runs[0].m1)) : (size_t)total_u;
-    {
-        std::vector<uint8_t> head;
-        size_t want = std::min<size_t>(header_limit, (size_t)1 << 16);
-        for (;;) {
-            head.resize(want);
-            if (want) HIP_TRY(hipMemcpy(head.data(), d_stream.p, want, hipMemcpyDeviceToHost));
-            const uint8_t *p = head.data(), *end = p + want;
-            bool more = false;
-            auto need = [&](size_t k) { if ((size_t)(end - p) < k) { more = true; return false; } return true; };
-            bool ok = true;
-            if (!need(12)) ok = false;
-            if (ok && std::memcmp(p, "BAM\1", 4) != 0) return fail(PC_ERR_ARG, "not a BAM file (bad magic)");
-            uint32_t l_text = 0;
-            if (ok) { l_text = brd32(p + 4); p += 8; if (!need((size_t)l_text + 4)) ok = false; }
-            if (ok) { p += l_text; n_ref = brd32(p); p += 4; }
-            b->ref_names.clear(); b->ref_lengths.clear();
-            for (uint32_t r = 0; ok && r < n_ref; ++r) {
-                if (!need(4)) { ok = false; break; }
-                const uint32_t l_name = brd32(p);
-                p += 4;
-                if (!need((size_t)l_name + 4)) { ok = false; break; }
-                b->ref_names.emplace_back((const char *)p, l_name ? l_name - 1 : 0);
-                p += l_name;
-                b->ref_lengths.push_back((int32_t)brd32(p));
-                p += 4;
-            }
-            if (ok) { first_record = (uint64_t)(p - head.data()); break; }
-            if (more && want >= header_limit && span && header_limit < (size_t)total_u + 1 && span->header_bytes < size) return PC_RETRY_HEADER;
-            if (!more || want >= header_limit)
-                return fail(PC_ERR_ARG, want < 12 ? "not a BAM file (bad magic)" : (b->ref_names.empty() && n_ref == 0 ? "truncated BAM header" : "truncated BAM reference list"));
-            want = std::min<size_t>(header_limit, want * 4);
-        }
-    }
-    // ---- record starts: every member guesses its first record start and walks the chain of length prefixes; the
-    // host confirms that the walks chain, and restarts the members whose guess did not
-    DevBuf<MemberChain> d_chain;
-    DevBuf<uint32_t> d_rec_off;
-    DevBuf<uint64_t> d_forced;
-    rc = d_chain.reserve((size_t)std::max(nm, 1));
-    if (rc == PC_OK) rc = d_rec_off.reserve((size_t)std::max(nm, 1) * kMaxRecPerMember);
-    if (rc == PC_OK) rc = d_forced.reserve((size_t)std::max(nm, 1));
-    if (rc != PC_OK) return rc;
-    // region read: the records start where the index says (a record start inside the span's first member) and end at its
-    // last chunk's end; a header-only read (no chunk at all) has no records
-    uint64_t stop_at = total_u;
-    // multi-chunk read: every run's record chain, {start, stop} by run, and the run of every member
-    std::vector<uint64_t> run_bounds;
-    std::vector<uint32_t> member_run;
-    DevBuf<uint64_t> d_run_bounds;
-    DevBuf<uint32_t> d_member_run;
-    if (chunked) {
-        run_bounds.assign(2 * std::max<size_t>(runs.size(), 1), ~0ull);
-        member_run.assign((size_t)std::max(nm, 1), 0u);
-        for (size_t r = 0; r < runs.size(); ++r)
-            for (int m = runs[r].m0; m < runs[r].m1; ++m) member_run[(size_t)m] = (uint32_t)r;
-        for (const ChunkAt &c : chunk_at) {
-            const uint64_t a = uoff_of(c.s_idx) + c.ub, z = uoff_of(c.e_idx) + c.ue;
-            if (a < first_record || z < a || z > total_u)
-                return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk starts inside the header or ends before it starts): %s", path.c_str());
-            // (the run that holds the chunk's first member; runs ascend by file offset)
-            auto it = std::upper_bound(runs.begin(), runs.end(), c.cb, [](int64_t x, const Run &r) { return x < r.file_lo; });
-            const size_t r = (size_t)(it - runs.begin()) - 1;
-            if (run_bounds[2 * r] == ~0ull) run_bounds[2 * r] = a;
-            run_bounds[2 * r + 1] = z;
-        }
-        for (size_t r = 0; r < runs.size(); ++r)   // a run without a chunk (the header's): no record
-            if (run_bounds[2 * r] == ~0ull) run_bounds[2 * r] = run_bounds[2 * r + 1] = uoff_of(runs[r].m1);
-        rc = d_run_bounds.upload(run_bounds, st);
-        if (rc == PC_OK) rc = d_member_run.upload(member_run, st);
-        if (rc != PC_OK) return rc;
-    } else if (span) {
-        if (span_first_member < 0) { first_record = total_u; stop_at = total_u; }
-        else {
-            const uint64_t fr = members[(size_t)span_first_member].uoff + (span->voff_begin & 0xffffu);
-            if (fr < first_record || fr > total_u)
-                return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk starts inside the header or beyond its member): %s", path.c_str());
-            first_record = fr;
-            if (span_last_member >= 0) stop_at = members[(size_t)span_last_member].uoff + (span->voff_end & 0xffffu);
-            if (stop_at > total_u || stop_at < first_record)
-                return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk ends beyond its member): %s", path.c_str());
-        }
-    }
-    std::vector<MemberChain> chain((size_t)nm);
-    std::vector<uint64_t> forced((size_t)nm, ~0ull), rec_base((size_t)nm + 1, 0);
-    std::vector<uint32_t> nrec_of((size_t)nm, 0u);
-    bool truncated = false;
-    int64_t nrec = 0;
-    if (nm) {
-        HIP_TRY(hipMemsetAsync(d_forced.p, 0xff, (size_t)nm * 8, st));
-        int from = 0;
-        uint64_t expected = first_record;
-        uint32_t cur_run = chunked ? member_run[0] : 0u;   // (multi-chunk read: the run whose chain `expected` follows)
-        if (chunked) expected = run_bounds[2 * (size_t)cur_run];
-        for (int round = 0;; ++round) {
-            if (chunked)
-                hipLaunchKernelGGL(k_bam_chain<true>, dim3((unsigned)(nm - from)), dim3(64), 0, st, d_stream.p, total_u, d_members.p, nm, from, n_ref, first_record,
-                                   d_forced.p, d_chain.p, d_rec_off.p, stop_at, d_member_run.p, d_run_bounds.p);
-            else
-                hipLaunchKernelGGL(k_bam_chain<false>, dim3((unsigned)(nm - from)), dim3(64), 0, st, d_stream.p, total_u, d_members.p, nm, from, n_ref, first_record,
-                                   d_forced.p, d_chain.p, d_rec_off.p, stop_at, (const uint32_t *)nullptr, (const uint64_t *)nullptr);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(chain.data() + from, d_chain.p + from, (size_t)(nm - from) * sizeof(MemberChain), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            int redo = -1;
-            for (int m = from; m < nm; ++m) {
-                uint64_t stop_m = stop_at;
-                if (chunked) {   // each run settles from its forced start and has to end exactly at its stop
-                    if (member_run[(size_t)m] != cur_run) {
-                        if (expected != run_bounds[2 * (size_t)cur_run + 1])
-                            return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk ends inside a record): %s", path.c_str());
-                        cur_run = member_run[(size_t)m];
-                        expected = run_bounds[2 * (size_t)cur_run];
-                    }
-                    stop_m = run_bounds[2 * (size_t)cur_run + 1];
-                }
-                const uint64_t begin = members[(size_t)m].uoff, end = std::min<uint64_t>(begin + members[(size_t)m].ulen, stop_m);
-                nrec_of[(size_t)m] = 0;
-                if (expected >= end) continue;                      // no record starts in this member (or it lies behind the span)
-                const MemberChain &mc = chain[(size_t)m];
-                if (mc.first != expected) {                         // the guess was off (or there was none): walk again from the right place
-                    forced[(size_t)m] = expected;
-                    redo = m;
-                    break;
-                }
-                nrec_of[(size_t)m] = mc.nrec;
-                if (mc.flags & 2u) { truncated = true; from = nm; break; }   // a length prefix that cannot be: the walk ends here
-                expected = mc.next;
-            }
-            if (redo < 0) break;
-            b->chain_restarts += 1;
-            HIP_TRY(hipMemcpyAsync(d_forced.p + redo, &forced[(size_t)redo], 8, hipMemcpyHostToDevice, st));
-            from = redo;
-            if (round > nm + 8) return fail(PC_ERR_STATE, "pc_bam_open: the record chain of %s did not settle", path.c_str());
-        }
-        if (chunked) stop_at = run_bounds[2 * (size_t)cur_run + 1];
-        if (expected != stop_at) {   // the last record runs past (or stops short of) the end of the stream
-            if (span) return fail(PC_ERR_ARG, "the index does not belong to this BAM file (a chunk ends inside a record): %s", path.c_str());
-            truncated = true;
-        }
-        for (int m = 0; m < nm; ++m) rec_base[(size_t)m + 1] = rec_base[(size_t)m] + nrec_of[(size_t)m];
-        nrec = (int64_t)rec_base[(size_t)nm];
-    } else if (total_u != first_record && !span) truncated = true;
-    HIP_TRY(hipEventRecord(ev[3], st));
-    clk.lap("header + record chain");
-    b->total = nrec;
-    if (nrec >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_bam_open: more than 2^31-2 records per file are not supported");
-    // ---- fields, order checks, columns
-    DevBuf<uint64_t> d_rec_base;
-    DevBuf<uint32_t> d_rec_member, d_placed, d_runs, d_staged_at, d_run_at, d_wide;
-    DevBuf<RecOut> d_recs;
-    DevBuf<unsigned long long> d_misc;   // [0] first error (index << 8 | code), [1] mapped, [2] unplaced
-    rc = d_misc.reserve(4);
-    if (rc != PC_OK) return rc;
-    const unsigned long long misc0[4] = {~0ull, 0ull, 0ull, 0ull};
-    HIP_TRY(hipMemcpyAsync(d_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, st));
-    int64_t n_staged = 0, n_runs = 0;
-    if (nrec > 0) {
-        std::vector<uint32_t> rec_member((size_t)((nrec + 255) >> 8));
-        {
-            int m = 0;
-            for (size_t g = 0; g < rec_member.size(); ++g) {
-                const uint64_t i = (uint64_t)g << 8;
-                while (m + 1 < nm && rec_base[(size_t)m + 1] <= i) ++m;
-                rec_member[g] = (uint32_t)m;
-            }
-        }
-        rc = d_rec_base.upload(rec_base, st);
-        if (rc == PC_OK) rc = d_rec_member.upload(rec_member, st);
-        if (rc == PC_OK) rc = d_recs.reserve((size_t)nrec);
-        if (rc == PC_OK) rc = d_placed.reserve((size_t)nrec + 1);
-        if (rc == PC_OK) rc = d_runs.reserve((size_t)nrec + 1);
-        if (rc == PC_OK) rc = d_staged_at.reserve((size_t)nrec + 1);
-        if (rc == PC_OK) rc = d_run_at.reserve((size_t)nrec + 1);
-        if (rc != PC_OK) return rc;
-        const unsigned g256 = (unsigned)((nrec + 255) / 256);
-        hipLaunchKernelGGL(k_bam_fields, dim3(g256), dim3(256), 0, st, d_stream.p, total_u, d_members.p, d_rec_base.p, d_chain.p, d_rec_off.p, nm, nrec,
-                           n_ref, d_rec_member.p, d_recs.p);
-        hipLaunchKernelGGL(k_bam_order, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, d_placed.p, d_misc.p);
-        DevBuf<int32_t> d_rtid;
-        DevBuf<int64_t> d_rbe;
-        if (span) {   // keep what overlaps a requested region (htslib's overlap rule); everything else is as if it were not in the file
-            const size_t nr = (size_t)std::max(span->nreg, 0);
-            rc = d_rtid.upload(span->tid, nr, st);
-            if (rc == PC_OK) rc = d_rbe.reserve(2 * std::max<size_t>(nr, 1));
-            if (rc != PC_OK) return rc;
-            if (nr) {
-                HIP_TRY(hipMemcpyAsync(d_rbe.p, span->beg, nr * 8, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(d_rbe.p + nr, span->end, nr * 8, hipMemcpyHostToDevice, st));
-            }
-            hipLaunchKernelGGL(k_bam_region_filter, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, (int)nr, d_rtid.p, d_rbe.p, d_rbe.p + nr);
-        }
-        HIP_TRY(hipMemsetAsync(d_placed.p + nrec, 0, 4, st));
-        HIP_TRY(hipMemsetAsync(d_runs.p + nrec, 0, 4, st));
-        hipLaunchKernelGGL(k_bam_scan_inputs, dim3((unsigned)((nrec + 256 * kScanInputsPerThread - 1) / (256 * kScanInputsPerThread))), dim3(256), 0, st, d_recs.p, nrec, d_placed.p, d_runs.p, d_misc.p + 1);
-        {
-            size_t tmp_bytes = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_placed.p, d_staged_at.p, (int)(nrec + 1), st));
-            DevBuf<uint8_t> d_tmp;
-            rc = d_tmp.reserve(std::max<size_t>(tmp_bytes, 16));
-            if (rc != PC_OK) return rc;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_placed.p, d_staged_at.p, (int)(nrec + 1), st));
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_runs.p, d_run_at.p, (int)(nrec + 1), st));
-            uint32_t tot[2] = {0, 0};
-            unsigned long long misc[3] = {0, 0, 0};
-            HIP_TRY(hipMemcpyAsync(&tot[0], d_staged_at.p + nrec, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(&tot[1], d_run_at.p + nrec, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(misc, d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));   // (d_tmp goes out of scope)
-            n_staged = tot[0]; n_runs = tot[1];
-            b->mapped = (int64_t)misc[1]; b->unplaced = (int64_t)misc[2];
-            if (misc[0] != ~0ull) {
-                switch ((int)(misc[0] & 0xffu)) {
-                case kRecTidRange: return fail(PC_ERR_ARG, "BAM record with reference id out of range");
-                case kRecNegPos: return fail(PC_ERR_ARG, "placed BAM record with a negative position");
-                case kRecUnsorted: return fail(PC_ERR_UNSORTED, "BAM file is not coordinate sorted: %s", path.c_str());
-                case kRecCigarOverrun: return fail(PC_ERR_ARG, "corrupt BAM record (cigar overruns block)");
-                case kRecUnknownOp: return fail(PC_ERR_ARG, "unknown CIGAR operation in %s", path.c_str());
-                case kRecEndBeyond: return fail(PC_ERR_ARG, "alignment ends beyond 2^31 - 1");
-                case kRecTooLong: return fail(PC_ERR_ARG, "alignment with more than 2^31 - 1 aligned positions");
-                case kRecDeletionOrder: return fail(PC_ERR_ARG, "alignment starting with a deletion breaks coordinate order; not supported");
-                default: truncated = true; break;   // kRecTruncated / kRecBadSize: reported below, after every other defect
-                }
-            }
-        }
-        if (truncated) return fail(PC_ERR_ARG, "truncated BAM record");
-        rc = b->tid.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->pos.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->alen.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->flags.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->nblk.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->flag16.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->mapq.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->lseq.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->nh.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc == PC_OK) rc = b->blk_start.reserve((size_t)std::max<int64_t>(n_runs, 1));
-        if (rc == PC_OK) rc = b->blk_len.reserve((size_t)std::max<int64_t>(n_runs, 1));
-        if (rc == PC_OK) rc = d_wide.reserve((size_t)std::max<int64_t>(n_staged, 1));
-        if (rc != PC_OK) return rc;
-        HIP_TRY(hipMemsetAsync(d_wide.p, 0, (size_t)std::max<int64_t>(n_staged, 1) * 4, st));
-        hipLaunchKernelGGL(k_bam_columns, dim3(g256), dim3(256), 0, st, d_stream.p, d_members.p, d_rec_base.p, d_rec_off.p, nm, d_rec_member.p, d_recs.p,
-                           nrec, d_staged_at.p, d_run_at.p, b->tid.p, b->pos.p, b->alen.p, b->flags.p, b->nblk.p, b->blk_start.p, b->blk_len.p, d_wide.p,
-                           b->flag16.p, b->mapq.p, b->lseq.p, b->nh.p);
-        HIP_TRY(hipGetLastError());
-        // wide records (beyond the 16-bit / 8-bit columns): rare -- their staged indices are found from the markers on
-        // the host side of pc_bam_read; the true values are read back here, record by record
-        {
-            // count the flagged records (a sum reduction through the scan buffers would do; a plain read-back of the
-            // flags is only paid when the file has any: probe with a device-side total first)
-            DevBuf<uint32_t> d_wsum;
-            rc = d_wsum.reserve((size_t)n_staged + 1);
-            if (rc != PC_OK) return rc;
-            size_t tmp_bytes = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_wide.p, d_wsum.p, (int)std::max<int64_t>(n_staged, 1), st));
-            DevBuf<uint8_t> d_tmp;
-            rc = d_tmp.reserve(std::max<size_t>(tmp_bytes, 16));
-            if (rc != PC_OK) return rc;
-            uint32_t last_sum = 0, last_flag = 0;
-            if (n_staged > 0) {
-                HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_wide.p, d_wsum.p, (int)n_staged, st));
-                HIP_TRY(hipMemcpyAsync(&last_sum, d_wsum.p + (n_staged - 1), 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(&last_flag, d_wide.p + (n_staged - 1), 4, hipMemcpyDeviceToHost, st));
-            }
-            HIP_TRY(hipStreamSynchronize(st));
-            const uint32_t nwide = last_sum + last_flag;
-            if (nwide) {
-                std::vector<uint32_t> wf((size_t)n_staged), sa((size_t)nrec);
-                std::vector<RecOut> recs((size_t)nrec);
-                HIP_TRY(hipMemcpy(wf.data(), d_wide.p, (size_t)n_staged * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(sa.data(), d_staged_at.p, (size_t)nrec * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(recs.data(), d_recs.p, (size_t)nrec * sizeof(RecOut), hipMemcpyDeviceToHost));
-                for (int64_t i = 0; i < nrec; ++i)
-                    if (recs[(size_t)i].placed == 1 && wf[sa[(size_t)i]]) {
-                        b->wide_idx.push_back((int64_t)sa[(size_t)i]);
-                        b->wide_alen.push_back((int32_t)recs[(size_t)i].L);
-                        b->wide_nblk.push_back((int32_t)recs[(size_t)i].nruns);
-                    }
-            }
-        }
-    } else if (truncated) return fail(PC_ERR_ARG, "truncated BAM record");
-    HIP_TRY(hipEventRecord(ev[4], st));
-    HIP_TRY(hipStreamSynchronize(st));
-    clk.lap("fields + scans + columns");
-    b->n = n_staged; b->nrun = n_runs;
-    for (int k = 0; k < 4; ++k) b->ms[k] = ms_between(ev[k], ev[k + 1]);
-    guard.b = nullptr;
-    *out = b;
-    return PC_OK;
-}
-
-int pc_bam_counts(pc_bam *b, int64_t *counts) {
-    if (!b || !counts) return fail(PC_ERR_ARG, "pc_bam_counts: bad arguments");
-    counts[0] = b->n; counts[1] = b->nrun; counts[2] = b->mapped; counts[3] = b->total; counts[4] = (int64_t)b->wide_idx.size();
-    counts[5] = b->members; counts[6] = b->inflated_bytes; counts[7] = b->chain_restarts;
-    return PC_OK;
-}
-int pc_bam_stats(pc_bam *b, int64_t *out4) {
-    if (!b || !out4) return fail(PC_ERR_ARG, "pc_bam_stats: bad arguments");
-    out4[0] = b->uploaded_bytes; out4[1] = b->runs; out4[2] = b->members; out4[3] = b->inflated_bytes;
-    return PC_OK;
-}
-int pc_bam_timing(pc_bam *b, double *ms4) {
-    if (!b || !ms4) return fail(PC_ERR_ARG, "pc_bam_timing: bad arguments");
-    for (int k = 0; k < 4; ++k) ms4[k] = b->ms[k];
-    return PC_OK;
-}
-int pc_bam_nref(pc_bam *b) { return b ? (int)b->ref_names.size() : -1; }
-const char *pc_bam_ref_name(pc_bam *b, int i) { return (b && i >= 0 && i < (int)b->ref_names.size()) ? b->ref_names[(size_t)i].c_str() : nullptr; }
-int32_t pc_bam_ref_length(pc_bam *b, int i) { return (b && i >= 0 && i < (int)b->ref_lengths.size()) ? b->ref_lengths[(size_t)i] : -1; }
-
-int pc_bam_read(pc_bam *b, int32_t *tid, int32_t *pos, uint16_t *alen, uint8_t *flags, uint8_t *nblk, int32_t *blk_start, int32_t *blk_len,
-                int64_t *wide_idx, int32_t *wide_alen, int32_t *wide_nblk) {
-    if (!b) return fail(PC_ERR_ARG, "pc_bam_read: NULL handle");
-    if (b->n > 0 && (!tid || !pos || !alen || !flags || !nblk)) return fail(PC_ERR_ARG, "pc_bam_read: NULL array");
-    if (b->nrun > 0 && (!blk_start || !blk_len)) return fail(PC_ERR_ARG, "pc_bam_read: NULL run array");
-    if (!b->wide_idx.empty() && (!wide_idx || !wide_alen || !wide_nblk)) return fail(PC_ERR_ARG, "pc_bam_read: NULL wide array");
-    HIP_TRY(hipSetDevice(b->e->device));
-    hipStream_t st = b->e->stream;
-    BamClock rclk;
-    const size_t n = (size_t)b->n, m = (size_t)b->nrun;
-    // (through the ring of page-locked pieces when the columns are large: the caller's arrays are pageable, see TransferRing)
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<TransferJob> jobs;
-    if (n) {
-        jobs.push_back({tid, b->tid.p, n * 4});
-        jobs.push_back({pos, b->pos.p, n * 4});
-        jobs.push_back({alen, b->alen.p, n * 2});
-        jobs.push_back({flags, b->flags.p, n});
-        jobs.push_back({nblk, b->nblk.p, n});
-    }
-    if (m) {
-        jobs.push_back({blk_start, b->blk_start.p, m * 4});
-        jobs.push_back({blk_len, b->blk_len.p, m * 4});
-    }
-    {
-        const int rc = TransferRing::of(b->e->device).run(b->e->device, jobs, TransferRing::kPiece, false, true);
-        if (rc != PC_OK) return rc;
-    }
-    rclk.lap("columns to the host");
-    for (size_t k = 0; k < b->wide_idx.size(); ++k) { wide_idx[k] = b->wide_idx[k]; wide_alen[k] = b->wide_alen[k]; wide_nblk[k] = b->wide_nblk[k]; }
-    return PC_OK;
-}
-
-int pc_bam_read_sam(pc_bam *b, uint16_t *flag, uint8_t *mapq, int32_t *lseq) {
-    if (!b) return fail(PC_ERR_ARG, "pc_bam_read_sam: NULL handle");
-    HIP_TRY(hipSetDevice(b->e->device));
-    hipStream_t st = b->e->stream;
-    const size_t n = (size_t)b->n;
-    HIP_TRY(hipStreamSynchronize(st));
-    std::vector<TransferJob> jobs;
-    if (n && flag) jobs.push_back({flag, b->flag16.p, n * 2});
-    if (n && mapq) jobs.push_back({mapq, b->mapq.p, n});
-    if (n && lseq) jobs.push_back({lseq, b->lseq.p, n * 4});
-    return TransferRing::of(b->e->device).run(b->e->device, jobs, TransferRing::kPiece, false, true);
-}
-
-int pc_bam_read_nh(pc_bam *b, uint16_t *nh) {
-    if (!b) return fail(PC_ERR_ARG, "pc_bam_read_nh: NULL handle");
-    HIP_TRY(hipSetDevice(b->e->device));
-    HIP_TRY(hipStreamSynchronize(b->e->stream));
-    std::vector<TransferJob> jobs;
-    if (b->n && nh) jobs.push_back({nh, b->nh.p, (size_t)b->n * 2});
-    return TransferRing::of(b->e->device).run(b->e->device, jobs, TransferRing::kPiece, false, true);
-}
-
-static int add_alignment_bam_impl(pc_engine *e, const void *image, int64_t size, const char *name, int64_t *mapped, const UploadedHook *uploaded,
-                                  const BamSpan *span = nullptr);
-
-int pc_add_alignment_bam(pc_engine *e, const void *image, int64_t size, const char *name, int64_t *mapped) {
-    return add_alignment_bam_impl(e, image, size, name, mapped, nullptr);
-}
-
-// a region read comes back for a larger slice of the file's head when the header did not fit the first one
-static int bam_open_span_retry(pc_engine *e, const void *image, int64_t size, const char *name, pc_bam **out, const UploadedHook *uploaded, const BamSpan *span) {
-    if (!span) return bam_open_impl(e, image, size, name, out, uploaded, nullptr);
-    BamSpan sp = *span;
-    for (;;) {
-        const int rc = bam_open_impl(e, image, size, name, out, uploaded, &sp);
-        if (rc != PC_RETRY_HEADER) return rc;
-        sp.header_bytes = std::min<int64_t>(size, sp.header_bytes * 16);
-    }
-}
-
-static int add_alignment_bam_impl(pc_engine *e, const void *image, int64_t size, const char *name, int64_t *mapped, const UploadedHook *uploaded,
-                                  const BamSpan *span) {
-    pc_bam *b = nullptr;
-    int rc = bam_open_span_retry(e, image, size, name, &b, uploaded, span);
-    if (rc != PC_OK) return rc;
-    struct Closer { pc_bam *b; ~Closer() { pc_bam_close(b); } } closer{b};
-    PoolScope pool_scope(&e->pool);
-    const int64_t n = b->n, m = b->nrun, nw = (int64_t)b->wide_idx.size();
-    const int ntid = std::max(1, (int)b->ref_names.size());
-    if (mapped) *mapped = b->mapped;
-    // the decoder's columns never leave HBM
-    // (PC_BAM_STAGE_HOST=1: read them back and hand them over as host arrays, as a caller of pc_bam_read + pc_add_alignment_file does)
-    if (!getenv("PC_BAM_STAGE_HOST")) {
-        DevBuf<uint32_t> d_wr;
-        DevBuf<uint2> d_wv;
-        if (nw) {
-            std::vector<uint32_t> wr((size_t)nw);
-            std::vector<uint2> wv((size_t)nw);
-            for (int64_t k = 0; k < nw; ++k) { wr[(size_t)k] = (uint32_t)b->wide_idx[(size_t)k]; wv[(size_t)k] = make_uint2((uint32_t)b->wide_alen[(size_t)k], (uint32_t)b->wide_nblk[(size_t)k]); }
-            rc = d_wr.upload(wr, e->stream);
-            if (rc == PC_OK) rc = d_wv.upload(wv, e->stream);
-            if (rc != PC_OK) return rc;
-            HIP_TRY(hipStreamSynchronize(e->stream));   // (the host vectors go out of scope)
-        }
-        pcstage::DevCols dc;
-        dc.tid = b->tid.p; dc.pos = b->pos.p; dc.alen = b->alen.p; dc.flags = b->flags.p; dc.nblk = b->nblk.p;
-        dc.blk_start = b->blk_start.p; dc.blk_len = b->blk_len.p;
-        dc.wide_rec = d_wr.p; dc.wide_val = d_wv.p; dc.n_wide = nw;
-        rc = stage_file(e, n, ntid, nullptr, nullptr, nullptr, nullptr, nullptr, m, nullptr, nullptr, nw, b->wide_idx.data(), b->wide_alen.data(),
-                        b->wide_nblk.data(), &dc);
-        if (rc != PC_OK) return rc;
-        // the FLAG / MAPQ columns stay with the staged file (no copy: the decoder's blocks change hands)
-        StagedFile *sf = e->files.back();
-        sf->sam_flag.swap(b->flag16);
-        sf->sam_mapq.swap(b->mapq);
-        sf->have_sam = true;
-        sf->sam_nh.swap(b->nh);
-        sf->have_nh = true;
-        return sync_flag_filter(e);
-    }
-    std::vector<int32_t> tid((size_t)n), pos((size_t)n), bs((size_t)m), bl((size_t)m), wa((size_t)nw), wn((size_t)nw);
-    std::vector<uint16_t> alen((size_t)n);
-    std::vector<uint8_t> flags((size_t)n), nblk((size_t)n);
-    std::vector<int64_t> wi((size_t)nw);
-    rc = pc_bam_read(b, tid.data(), pos.data(), alen.data(), flags.data(), nblk.data(), bs.data(), bl.data(), wi.data(), wa.data(), wn.data());
-    if (rc != PC_OK) return rc;
-    std::vector<uint16_t> f16((size_t)n);
-    std::vector<uint8_t> mq((size_t)n);
-    rc = pc_bam_read_sam(b, f16.data(), mq.data(), nullptr);
-    if (rc != PC_OK) return rc;
-    rc = pc_add_alignment_file_wide(e, n, ntid, tid.data(), pos.data(), alen.data(), flags.data(), nblk.data(), m, bs.data(), bl.data(),
-                                    nw, wi.data(), wa.data(), wn.data());
-    if (rc != PC_OK) return rc;
-    rc = pc_set_alignment_sam(e, (int)e->files.size() - 1, n, f16.data(), mq.data());
-    if (rc != PC_OK) return rc;
-    std::vector<uint16_t> nhv((size_t)n);
-    rc = pc_bam_read_nh(b, nhv.data());
-    if (rc != PC_OK) return rc;
-    return pc_set_alignment_nh(e, (int)e->files.size() - 1, n, nhv.data());
-}
-
-namespace {
-// A file mapped for one call: every host thread touches its share of the pages (soft faults in parallel: 578 MB in ~2 ms
-// instead of the 15 of MAP_POPULATE's one thread), and the mapping is taken down by a helper thread as soon as the
-// image has been uploaded -- while the caller's thread waits for the GPU.
-struct MappedFile {
-    void *p = nullptr;
-    size_t size = 0;
-    // (a region read maps only, and faults what it uploads)
-    // touch_mode 1: fault every page in up front (all host threads); 0: map only; -1 (whole-file reads): up front for a
-    // file that is uploaded straight from the mapping (below two upload pieces: the runtime's one staging thread would take
-    // the faults one by one), map only for a larger one -- its pieces are copied into the page-locked ring by all host
-    // threads, which take the faults as they go, beside the GPU's work (the 2.9 GB file of 10^8 aligner-like records:
-    // file -> staged 169 - 180 ms with the pages touched up front, 147 - 149 without; PC_BAM_TOUCH=0 / 1 forces either)
-    int open(const char *path, int touch_mode = -1) {
-        bool touch = touch_mode > 0;
-        const char *env = getenv("PC_BAM_TOUCH");
-        const int forced = (touch_mode < 0 && env) ? (atoi(env) != 0 ? 1 : 0) : -1;
-        const int fd = ::open(path, O_RDONLY);
-        if (fd < 0) return fail(PC_ERR_ARG, "cannot open %s: %s", path, strerror(errno));
-        struct stat sb;
-        if (fstat(fd, &sb) != 0) { ::close(fd); return fail(PC_ERR_ARG, "cannot stat %s: %s", path, strerror(errno)); }
-        size = (size_t)sb.st_size;
-        if (touch_mode < 0) touch = forced >= 0 ? forced != 0 : size < ((size_t)128 << 20);
-        if (size) {
-            p = mmap(nullptr, size, PROT_READ, MAP_SHARED, fd, 0);
-            if (p == MAP_FAILED) { p = nullptr; ::close(fd); return fail(PC_ERR_NOMEM, "cannot map %s: %s", path, strerror(errno)); }
-            if (touch) {
-                (void)madvise(p, size, MADV_WILLNEED);
-                const int64_t pages = (int64_t)((size + 4095) / 4096);
-                const volatile uint8_t *q = (const volatile uint8_t *)p;
-                parallel_chunks(pages, std::min(usable_cpus(), 32), [&](int, int64_t b, int64_t en) {
-                    uint8_t acc = 0;
-                    for (int64_t k = b; k < en; ++k) acc ^= q[(size_t)k * 4096];
-                    (void)acc;
-                });
-            }
-        }
-        ::close(fd);
-        return PC_OK;
-    }
-    // the mapping goes as soon as the image has crossed PCIe -- on a helper thread, while the caller's thread waits for
-    // the GPU (munmap holds the address-space lock of the process: done later, it would stall the caller's next page faults)
-    std::thread helper;
-    void release_behind(hipStream_t up, int device) {
-        if (!p || helper.joinable()) return;
-        void *q = p;
-        const size_t n = size;
-        p = nullptr;
-        try {
-            helper = std::thread([q, n, up, device]() {
-                if (hipSetDevice(device) == hipSuccess) (void)hipStreamSynchronize(up);
-                (void)munmap(q, n);
-            });
-        } catch (...) { p = q; }
-    }
-    ~MappedFile() {
-        if (helper.joinable()) helper.join();
-        if (p) (void)munmap(p, size);
-    }
-};
-} // namespace
-
-int pc_bam_open_path(pc_engine *e, const char *path, pc_bam **out) {
-    if (!e || !path || !out) return fail(PC_ERR_ARG, "pc_bam_open_path: bad arguments");
-    MappedFile mf;
-    const int rc = mf.open(path);
-    if (rc != PC_OK) return rc;
-    const int device = e->device;
-    const UploadedHook hook = [&mf, device](hipStream_t up) { mf.release_behind(up, device); };
-    return bam_open_impl(e, mf.p, (int64_t)mf.size, path, out, &hook);
-}
-
-int pc_add_alignment_bam_path(pc_engine *e, const char *path, int64_t *mapped) {
-    if (!e || !path) return fail(PC_ERR_ARG, "pc_add_alignment_bam_path: bad arguments");
-    MappedFile mf;
-    const int rc = mf.open(path);
-    if (rc != PC_OK) return rc;
-    const int device = e->device;
-    const UploadedHook hook = [&mf, device](hipStream_t up) { mf.release_behind(up, device); };
-    return add_alignment_bam_impl(e, mf.p, (int64_t)mf.size, path, mapped, &hook);
-}
-
-static int span_args(const char *what, uint64_t voff_begin, uint64_t voff_end, int nreg, const int32_t *tid, const int64_t *beg, const int64_t *end, BamSpan &sp) {
-    if (voff_end < voff_begin || nreg < 0 || (nreg > 0 && (!tid || !beg || !end))) return fail(PC_ERR_ARG, "%s: bad span / regions", what);
-    for (int k = 0; k < nreg; ++k) {
-        if (tid[k] < 0 || end[k] <= beg[k]) return fail(PC_ERR_ARG, "%s: region %d is empty or has no reference id", what, k);
-        if (k > 0 && (tid[k] < tid[k - 1] || (tid[k] == tid[k - 1] && beg[k] < end[k - 1])))
-            return fail(PC_ERR_ARG, "%s: regions must be ascending by (reference id, start) and must not overlap", what);
-    }
-    sp.voff_begin = voff_begin; sp.voff_end = voff_end; sp.nreg = nreg; sp.tid = tid; sp.beg = beg; sp.end = end;
-    if (const char *env = getenv("PC_BAM_HEADER_BYTES")) sp.header_bytes = std::max<int64_t>(1, atoll(env));   // (tests: a header longer than the first slice)
-    return PC_OK;
-}
-
-int pc_bam_open_span(pc_engine *e, const char *path, uint64_t voff_begin, uint64_t voff_end, int nreg, const int32_t *tid, const int64_t *beg,
-                     const int64_t *end, pc_bam **out) {
-    if (!e || !path || !out) return fail(PC_ERR_ARG, "pc_bam_open_span: bad arguments");
-    BamSpan sp;
-    int rc = span_args("pc_bam_open_span", voff_begin, voff_end, nreg, tid, beg, end, sp);
-    if (rc != PC_OK) return rc;
-    MappedFile mf;
-    rc = mf.open(path, 0);
-    if (rc != PC_OK) return rc;
-    return bam_open_span_retry(e, mf.p, (int64_t)mf.size, path, out, nullptr, &sp);
-}
-
-int pc_add_alignment_bam_span(pc_engine *e, const char *path, uint64_t voff_begin, uint64_t voff_end, int nreg, const int32_t *tid,
-                              const int64_t *beg, const int64_t *end, int64_t *mapped) {
-    if (!e || !path) return fail(PC_ERR_ARG, "pc_add_alignment_bam_span: bad arguments");
-    BamSpan sp;
-    int rc = span_args("pc_add_alignment_bam_span", voff_begin, voff_end, nreg, tid, beg, end, sp);
-    if (rc != PC_OK) return rc;
-    MappedFile mf;
-    rc = mf.open(path, 0);
-    if (rc != PC_OK) return rc;
-    return add_alignment_bam_impl(e, mf.p, (int64_t)mf.size, path, mapped, nullptr, &sp);
-}
-
-static int chunk_args(const char *what, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg, const int32_t *tid, const int64_t *beg,
-                      const int64_t *end, BamSpan &sp) {
-    if (nchunk < 0 || (nchunk > 0 && (!voff_beg || !voff_end))) return fail(PC_ERR_ARG, "%s: bad chunk list", what);
-    for (int k = 0; k < nchunk; ++k)
-        if (voff_end[k] <= voff_beg[k] || (k > 0 && voff_beg[k] < voff_end[k - 1]))
-            return fail(PC_ERR_ARG, "%s: chunks must be non-empty, ascending and disjoint", what);
-    int rc = span_args(what, nchunk ? voff_beg[0] : 0, nchunk ? voff_end[nchunk - 1] : 0, nreg, tid, beg, end, sp);
-    if (rc != PC_OK) return rc;
-    sp.nchunk = nchunk; sp.cbeg = voff_beg; sp.cend = voff_end;
-    return PC_OK;
-}
-
-int pc_bam_open_chunks(pc_engine *e, const char *path, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg, const int32_t *tid,
-                       const int64_t *beg, const int64_t *end, pc_bam **out) {
-    if (!e || !path || !out) return fail(PC_ERR_ARG, "pc_bam_open_chunks: bad arguments");
-    BamSpan sp;
-    int rc = chunk_args("pc_bam_open_chunks", nchunk, voff_beg, voff_end, nreg, tid, beg, end, sp);
-    if (rc != PC_OK) return rc;
-    MappedFile mf;
-    rc = mf.open(path, 0);
-    if (rc != PC_OK) return rc;
-    return bam_open_span_retry(e, mf.p, (int64_t)mf.size, path, out, nullptr, &sp);
-}
-
-int pc_add_alignment_bam_chunks(pc_engine *e, const char *path, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg,
-                                const int32_t *tid, const int64_t *beg, const int64_t *end, int64_t *mapped) {
-    if (!e || !path) return fail(PC_ERR_ARG, "pc_add_alignment_bam_chunks: bad arguments");
-    BamSpan sp;
-    int rc = chunk_args("pc_add_alignment_bam_chunks", nchunk, voff_beg, voff_end, nreg, tid, beg, end, sp);
-    if (rc != PC_OK) return rc;
-    MappedFile mf;
-    rc = mf.open(path, 0);
-    if (rc != PC_OK) return rc;
-    return add_alignment_bam_impl(e, mf.p, (int64_t)mf.size, path, mapped, nullptr, &sp);
-}
-
-} // extern "C"
+// ================================================================== compressed BAM on the GPU (bam_decoder.hip.h, bam_kernels.hip.h)
+#include "bam_decoder.hip.h"

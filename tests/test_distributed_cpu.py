@@ -297,7 +297,7 @@ def test_bench_spawns_its_ranks_and_runs_the_one_job_mode(tmp_path):
 def test_bench_one_job_from_one_shared_bam_file(tmp_path):
     """``bench.py --gpus 2 --from-bam``: rank 0 writes the job's records as ONE indexed BAM file, every rank stages its
     genome range of it (the BAI index; here the host reader feeds the stand-in engine, on a GPU box
-    pc_add_alignment_bam_span) and passes the same parity gates as with generated records -- C2 (point rule), C3 (center
+    pc_add_alignment_bam_chunks) and passes the same parity gates as with generated records -- C2 (point rule), C3 (center
     rule: float64 sums in file order) and the spliced C4.  The line carries the per-rank file -> staged times."""
     import json
     import subprocess

@@ -767,7 +767,7 @@ def test_flag_filter_needs_the_columns(eng):
 
 # ---------------------------------------------------------------- region reads (round 5)
 def test_region_reads_match_hts_itr_query_on_the_gpu(eng, tmp_path):
-    """``read_bam_gpu(path, regions=...)`` (pc_bam_open_span: only the BGZF members the BAI index points to are inflated,
+    """``read_bam_gpu(path, regions=...)`` (pc_bam_open_chunks: only the BGZF members the BAI index points to are inflated,
     the record chain starts where the index says, htslib's overlap rule on the GPU) returns what the host region reader
     returns -- itself pinned to htslib's ``sam_itr_queryi`` result sets (tests/test_hts_golden.py) -- for each of the
     fixture's 400 regions, and, record for record, htslib's own result sets."""
@@ -875,7 +875,7 @@ def test_a_foreign_index_is_refused(eng, tmp_path):
 @pytest.mark.gpu
 def test_bench_one_job_from_one_bam_file_on_the_gpu(tmp_path):
     """``bench.py --gpus 1 --from-bam``: the job's records are written once as ONE indexed BAM file, the rank stages its
-    genome range of it through the BAI index with the decode on the GPU (pc_add_alignment_bam_span) and passes the very
+    genome range of it through the BAI index with the decode on the GPU (pc_add_alignment_bam_chunks) and passes the very
     parity gates of the generated-records run -- point rule (C2), the spliced C4 and the center rule (C3: float64 sums in
     file order, bit for bit); the sum of all counts equals that of the same job counted from generated arrays (--one-job)."""
     import json

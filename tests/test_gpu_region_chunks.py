@@ -1,6 +1,7 @@
 """Region reads on the GPU decoder from the index's chunk list (``pc_bam_open_chunks`` / ``pc_add_alignment_bam_chunks``):
 only the members the regions' chunks touch are uploaded and inflated, and the columns are those of the host region
 reader (itself pinned to htslib's ``sam_itr_queryi``, tests/test_hts_golden.py), record for record."""
+import ctypes
 import os
 import sys
 
@@ -182,6 +183,61 @@ def test_foreign_index_and_empty_region_sets(eng, tmp_path):
                 outcomes.append("error")
                 assert any(k in str(e) for k in ("index", "BGZF", "BAM", "sorted")), str(e)
     assert outcomes.count("error") >= len(outcomes) // 2, outcomes
+
+
+def open_span(eng, path, voff_begin, voff_end, sp):
+    """The columns, references and lengths of one ``pc_bam_open_span`` read (straight through ctypes: no Python caller is left)."""
+    from plastid_amd import _lib as clib
+    L = clib.load()
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
+    h = ctypes.c_void_p()
+    clib.check(L.pc_bam_open_span(eng._h, os.fsencode(path), int(voff_begin), int(voff_end), len(sp["tid"]), p(sp["tid"]), p(sp["beg"]), p(sp["end"]),
+                                  ctypes.byref(h)))
+    try:
+        counts = np.zeros(8, np.int64)
+        clib.check(L.pc_bam_counts(h, p(counts)))
+        n, nrun, nw = int(counts[0]), int(counts[1]), int(counts[4])
+        refs = [L.pc_bam_ref_name(h, i).decode() for i in range(L.pc_bam_nref(h))]
+        lens = [int(L.pc_bam_ref_length(h, i)) for i in range(len(refs))]
+        c = dict(tid=np.empty(n, np.int32), pos=np.empty(n, np.int32), alen=np.empty(n, np.uint16), flags=np.empty(n, np.uint8),
+                 nblk=np.empty(n, np.uint8), blk_start=np.empty(nrun, np.int32), blk_len=np.empty(nrun, np.int32),
+                 wide_idx=np.empty(nw, np.int64), wide_alen=np.empty(nw, np.int32), wide_nblk=np.empty(nw, np.int32),
+                 flag16=np.empty(n, np.uint16), mapq=np.empty(n, np.uint8), qlen=np.empty(n, np.int32), nh=np.empty(n, np.uint16))
+        clib.check(L.pc_bam_read(h, *(p(c[k]) for k in COLS[:10])))
+        clib.check(L.pc_bam_read_sam(h, p(c["flag16"]), p(c["mapq"]), p(c["qlen"])))
+        clib.check(L.pc_bam_read_nh(h, p(c["nh"])))
+    finally:
+        L.pc_bam_close(h)
+    return c, refs, lens
+
+
+def test_span_reads_are_one_chunk_reads(eng, tmp_path):
+    """(g) ``pc_bam_open_span`` over the span that encloses the regions' chunks: the host region reader's columns, for the
+    htslib fixture's 40-region set and for a multi-region set on a file of many members; the span 0, 0 reads the header
+    alone (every reference, no record)."""
+    hts = np.load(FIX)
+    fix = str(tmp_path / "htslib.bam")
+    open(fix, "wb").write(hts["bam"].tobytes())
+    open(fix + ".bai", "wb").write(hts["bai"].tobytes())
+    refs = [str(x) for x in hts["references"]]
+    many = [(refs[int(t)], int(b), int(e)) for t, b, e in hts["regions"][:40]]
+    genome, tx, reads, _ = synth.make_config("C4", scale=0.00006, tx_scale=0.002)
+    syn = str(tmp_path / "span.bam")
+    indexed_bam(syn, reads, 3000)
+    assert len(bgzf_members(syn)[0]) > 20
+    chains = tx.chains(limit=60)
+    some = [(c.chrom, c.spanning_segment.start, c.spanning_segment.end) for c in chains[5:45:4]]
+    for path, regs in ((fix, many), (syn, some)):
+        sp = resolve_regions(path, regs)
+        want = read_bam(path, regions=regs)
+        assert want.n > 0 and len(sp["tid"]) > 1 and sp["voff_end"] > sp["voff_begin"]
+        got, grefs, glens = open_span(eng, path, sp["voff_begin"], sp["voff_end"], sp)
+        for k in COLS:
+            assert np.array_equal(got[k], getattr(want, k)), (path, k)
+        assert grefs == list(want.references) and glens == [int(x) for x in want.lengths]
+        none, nrefs, nlens = open_span(eng, path, 0, 0, sp)
+        assert all(len(none[k]) == 0 for k in COLS)
+        assert nrefs == list(want.references) and nlens == [int(x) for x in want.lengths]
 
 
 def test_two_identical_calls_give_identical_arrays(eng, tmp_path):
