@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 7
+#define PC_ABI_VERSION 8
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -376,6 +376,42 @@ int pc_add_alignment_bam_chunks(pc_engine *e, const char *path, int nchunk, cons
 /* what an open read: [0] compressed bytes of the file uploaded to HBM, [1] runs they came in (1: a whole file), [2] BGZF
  * members inflated, [3] inflated bytes */
 int pc_bam_stats(pc_bam *b, int64_t *out4);
+
+/* ---- (ABI 8) the BAI index of a coordinate-sorted BAM file, built on the GPU.  Replaces `samtools index` / pysam.index,
+ * i.e. htslib's sam_index_build for BAI (kent/src/htslib/sam.c:470-496: every record is pushed with POS, bam_endpos
+ * (sam.c:338-344) and the virtual offset bgzf_tell gives (bgzf.c:569-572); hts_idx_push / hts_idx_finish, hts.c:1293-1351
+ * and :1193-1291; the file layout of hts_idx_save, hts.c:1395-1457; SAM specification section 5): min_shift 14, 5 levels,
+ * the pseudo-bin 37450 with the file range and the mapped / unmapped counts of every reference, n_no_coor.  The index a
+ * region read needs (pc_bam_open_chunks) without an outside tool.  The bins are written in ascending order with 37450
+ * last (htslib writes them in the order of its hash table); parsed, the two indexes are equal.
+ * The build runs the whole-file open up to the record fields (upload, inflate + CRC, record chain, k_bam_fields and the
+ * order checks), writes no column, and walks the records once more for their bins, runs, linear windows and counts; the
+ * host finishes the index.  Errors: those of pc_bam_open with its messages (a file the decoder refuses has no index), and
+ * PC_ERR_ARG "a BAI index cannot hold ..." for a reference longer than 2^29 or an alignment that reaches beyond it. */
+typedef struct pc_bam_index pc_bam_index;
+int pc_bam_index_build(pc_engine *e, const char *path, pc_bam_index **out);
+/* The host half alone -- no engine, no GPU call; the build above ends in it (hts_idx_finish: update_loff's forward fill
+ * and compress_binning, hts.c:1193-1275).  Input:
+ *   n_runs, run_tid, run_bin, run_beg, run_end   the runs (maximal stretches of consecutive placed records with one
+ *       reference id and one bin): [virtual offset of the first record, of the first record behind the run); in file order
+ *       or already in (tid, bin) order with file order kept inside a bin;
+ *   lin_start (n_ref + 1), linear                the 16 kb windows of reference t are linear[lin_start[t] .. lin_start[t + 1]):
+ *       the offset of the first mapped record that covers the window, 0 where none does;
+ *   ref_beg, ref_end, ref_mapped, ref_unmapped   per reference: the file range of its records and their counts (all 0:
+ *       a reference without records);  n_no_coor: records without a reference. */
+int pc_bam_index_finish(int n_ref, int64_t n_runs, const int32_t *run_tid, const uint32_t *run_bin, const uint64_t *run_beg,
+                        const uint64_t *run_end, const int64_t *lin_start, const uint64_t *linear, const uint64_t *ref_beg,
+                        const uint64_t *ref_end, const int64_t *ref_mapped, const int64_t *ref_unmapped, int64_t n_no_coor,
+                        pc_bam_index **out);
+/* the serialised .bai file: *bytes = its size; copied to buf when cap holds it (call with cap 0 first) */
+int pc_bam_index_bytes(pc_bam_index *idx, void *buf, int64_t cap, int64_t *bytes);
+/* [0] records, [1] placed records, [2] runs before the finish, [3] chunks after it, [4] bins (37450 not counted),
+ * [5] linear entries, [6] n_no_coor, [7] mapped (what pysam's AlignmentFile.mapped sums from the index) */
+int pc_bam_index_stats(pc_bam_index *idx, int64_t *out8);
+/* milliseconds: [0] upload, [1] inflate + CRC, [2] record chain (the engine's stream, as pc_bam_timing), [3] fields + order
+ * checks, [4] index kernels, [5] read-back, [6] host finish, [7] the whole call (wall clock) */
+int pc_bam_index_timing(pc_bam_index *idx, double *ms8);
+int pc_bam_index_close(pc_bam_index *idx);
 
 #ifdef __cplusplus
 }

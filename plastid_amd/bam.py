@@ -27,6 +27,8 @@ def _load():
         L.pb_last_error.restype = ctypes.c_char_p
         L.pb_open.restype = vp
         L.pb_open.argtypes = [ctypes.c_char_p]
+        L.pb_open_indexed.restype = vp
+        L.pb_open_indexed.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
         L.pb_close.argtypes = [vp]
         L.pb_load.argtypes = [vp, ctypes.c_int]
         L.pb_load_regions.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), vp, vp]
@@ -106,18 +108,212 @@ def _region_tuples(regions):
     return [(r.chrom, r.start, r.end) if hasattr(r, "chrom") else tuple(r) for r in regions]
 
 
-def resolve_regions(path, regions):
+class BamIndex(object):
+    """A BAI index (SAM specification 5.2), parsed: what ``samtools index`` writes and :func:`build_index` builds.
+
+    ``bins``: per reference, a dict from bin number to a ``uint64 [k, 2]`` array of chunks ``[begin, end)`` (virtual
+    offsets); ``linear``: per reference, the ``uint64`` offsets of its 16 kb windows; ``meta``: per reference, ``None`` or
+    ``(file begin, file end, mapped, unmapped)`` from samtools' pseudo-bin 37450; ``n_no_coor``: the records without a
+    reference; ``mapped``: the sum of the per-reference mapped counts (pysam's ``AlignmentFile.mapped``), -1 when the
+    index carries none.  Two indexes are equal when their parsed content is: the order of the bins in the file is not part of it
+    (htslib writes them in the order of its hash table; :meth:`to_bytes` writes them ascending, 37450 last)."""
+
+    META_BIN = 37450
+
+    def __init__(self, bins, linear, meta, n_no_coor=0):
+        self.bins, self.linear, self.meta, self.n_no_coor = bins, linear, meta, int(n_no_coor)
+
+    @property
+    def n_ref(self):
+        return len(self.bins)
+
+    @property
+    def mapped(self):
+        have = [m for m in self.meta if m is not None]
+        return sum(int(m[2]) for m in have) if have else -1
+
+    @classmethod
+    def from_bytes(cls, data):
+        import struct
+        data = bytes(data)
+        if len(data) < 8 or data[:4] != b"BAI\x01":
+            raise ValueError("not a BAI index")
+        n_ref, = struct.unpack_from("<i", data, 4)
+        o = 8
+        bins, linear, meta = [], [], []
+        try:
+            for _ in range(n_ref):
+                n_bin, = struct.unpack_from("<i", data, o)
+                o += 4
+                rb, rm = {}, None
+                for _ in range(n_bin):
+                    b, nc = struct.unpack_from("<Ii", data, o)
+                    o += 8
+                    if nc < 0 or o + 16 * nc > len(data):
+                        raise struct.error("chunks")
+                    ch = np.frombuffer(data, "<u8", 2 * nc, o).reshape(nc, 2).copy()
+                    o += 16 * nc
+                    if b == cls.META_BIN and nc >= 2:
+                        rm = tuple(int(x) for x in ch[:2].ravel())
+                    elif b != cls.META_BIN:
+                        rb[int(b)] = ch
+                n_intv, = struct.unpack_from("<i", data, o)
+                o += 4
+                if n_intv < 0 or o + 8 * n_intv > len(data):
+                    raise struct.error("linear")
+                linear.append(np.frombuffer(data, "<u8", n_intv, o).copy())
+                o += 8 * n_intv
+                bins.append(rb)
+                meta.append(rm)
+            n_no_coor = struct.unpack_from("<Q", data, o)[0] if o + 8 <= len(data) else 0   # (optional in the format)
+        except struct.error:
+            raise ValueError("truncated BAI index")
+        return cls(bins, linear, meta, n_no_coor)
+
+    @classmethod
+    def from_file(cls, path):
+        with open(path, "rb") as fh:
+            return cls.from_bytes(fh.read())
+
+    def to_bytes(self):
+        import struct
+        out = [b"BAI\x01", struct.pack("<i", self.n_ref)]
+        for rb, lin, rm in zip(self.bins, self.linear, self.meta):
+            out.append(struct.pack("<i", len(rb) + (rm is not None)))
+            for b in sorted(rb):
+                ch = np.ascontiguousarray(rb[b], "<u8")
+                out.append(struct.pack("<Ii", b, len(ch)))
+                out.append(ch.tobytes())
+            if rm is not None:
+                out.append(struct.pack("<Ii4Q", self.META_BIN, 2, *rm))
+            out.append(struct.pack("<i", len(lin)))
+            out.append(np.ascontiguousarray(lin, "<u8").tobytes())
+        out.append(struct.pack("<Q", self.n_no_coor))
+        return b"".join(out)
+
+    def write(self, path):
+        with open(path, "wb") as fh:
+            fh.write(self.to_bytes())
+
+    def __eq__(self, other):
+        if not isinstance(other, BamIndex):
+            return NotImplemented
+        if self.n_ref != other.n_ref or self.n_no_coor != other.n_no_coor or list(self.meta) != list(other.meta):
+            return False
+        for a, b, la, lb in zip(self.bins, other.bins, self.linear, other.linear):
+            if sorted(a) != sorted(b) or not np.array_equal(la, lb) or any(not np.array_equal(a[k], b[k]) for k in a):
+                return False
+        return True
+
+    def __ne__(self, other):
+        r = self.__eq__(other)
+        return r if r is NotImplemented else not r
+
+    __hash__ = None
+
+    def __repr__(self):
+        return "BamIndex(%d references, %d bins, %d chunks, n_no_coor=%d, mapped=%d)" % (
+            self.n_ref, sum(len(b) for b in self.bins), sum(len(c) for b in self.bins for c in b.values()), self.n_no_coor, self.mapped)
+
+
+def find_index(path):
+    """The index file the region reads find beside `path` (``path + ".bai"``, then ``.bai`` in place of the extension), or ``None``."""
+    path = os.fspath(path)
+    for cand in (path + ".bai", path[:-4] + ".bai" if len(path) > 4 else None):
+        if cand and os.path.isfile(cand):
+            return cand
+    return None
+
+
+def build_index(path, engine=None, out=None, overwrite=False, timing=None):
+    """Build the BAI index of the coordinate-sorted BAM file `path` ON THE GPU (``pc_bam_index_build``) -- what
+    ``samtools index`` / ``pysam.index`` do -- write it to `out` (default ``path + ".bai"``) and return it as a
+    :class:`BamIndex`.  The file goes through the decoder of :func:`read_bam_gpu` up to the record fields (a file that
+    decoder refuses is refused here with the same message); the bins, runs, linear windows and counts are taken from the
+    records in HBM, and the host finishes the index.  `engine`: a :class:`plastid_amd.engine.Engine` (default: the shared
+    one of device 0).  The file is written under a temporary name and renamed; an existing `out` is only replaced with
+    ``overwrite=True``.  `timing`: optional dict that receives the laps in ms (``upload_ms``, ``inflate_ms``, ``chain_ms``,
+    ``fields_ms``, ``index_ms``, ``readback_ms``, ``finish_ms``, ``total_ms``) and the counts (``records``, ``placed``,
+    ``runs``, ``chunks``, ``bins``, ``linear``, ``n_no_coor``, ``mapped``, ``index_bytes``).
+    ``ValueError``: a reference longer than 2^29 or an alignment that reaches beyond it (BAI cannot hold them)."""
+    from . import _lib as clib
+    path = os.fspath(path)
+    if not os.path.isfile(path):
+        raise IOError("No such file: %r" % (path,))
+    dest = os.fspath(out) if out is not None else path + ".bai"
+    if os.path.exists(dest) and not overwrite:
+        raise FileExistsError("%s exists; pass overwrite=True to replace it" % dest)
+    if engine is None:
+        from .engine import default_engine
+        engine = default_engine()
+    L = clib.load()
+    h = ctypes.c_void_p()
+    clib.check(L.pc_bam_index_build(engine._h, os.fsencode(path), ctypes.byref(h)))
+    try:
+        data = _index_bytes(L, h)
+        if timing is not None:
+            ms, st = np.zeros(8, np.float64), np.zeros(8, np.int64)
+            clib.check(L.pc_bam_index_timing(h, ms.ctypes.data_as(ctypes.c_void_p)))
+            clib.check(L.pc_bam_index_stats(h, st.ctypes.data_as(ctypes.c_void_p)))
+            timing.update(zip(("upload_ms", "inflate_ms", "chain_ms", "fields_ms", "index_ms", "readback_ms", "finish_ms", "total_ms"), ms.tolist()))
+            timing.update(zip(("records", "placed", "runs", "chunks", "bins", "linear", "n_no_coor", "mapped"), st.tolist()))
+            timing["index_bytes"] = len(data)
+    finally:
+        L.pc_bam_index_close(h)
+    tmp = "%s.tmp%d" % (dest, os.getpid())
+    try:
+        with open(tmp, "wb") as fh:
+            fh.write(data)
+        if os.path.exists(dest) and not overwrite:   # (made by someone else in the meantime)
+            raise FileExistsError("%s exists; pass overwrite=True to replace it" % dest)
+        os.replace(tmp, dest)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return BamIndex.from_bytes(data)
+
+
+def _index_bytes(L, h):
+    from . import _lib as clib
+    n = ctypes.c_int64(0)
+    clib.check(L.pc_bam_index_bytes(h, None, 0, ctypes.byref(n)))
+    buf = ctypes.create_string_buffer(max(int(n.value), 1))
+    clib.check(L.pc_bam_index_bytes(h, buf, int(n.value), ctypes.byref(n)))
+    return buf.raw[:int(n.value)]
+
+
+def _index_path(path, index, engine=None):
+    """The `index` keyword of the region reads: ``None`` -> ``None`` (the lookup beside the file, and its error); a path ->
+    that file; ``"build"`` -> the index beside the file, built first (:func:`build_index`) when there is none."""
+    if index is None:
+        return None
+    if isinstance(index, str) and index == "build":
+        if find_index(path) is None:
+            build_index(path, engine=engine)
+        return None
+    return os.fspath(index)
+
+
+def _pb_open(L, path, index_path):
+    h = L.pb_open(os.fsencode(path)) if index_path is None else L.pb_open_indexed(os.fsencode(path), os.fsencode(index_path))
+    if not h:
+        raise IOError(L.pb_last_error().decode())
+    return h
+
+
+def resolve_regions(path, regions, index=None):
     """Resolve `regions` (``(chrom, start, end)`` or |GenomicSegments|) through the BAI index of `path` for a decoder
     that reads the file itself (:func:`read_bam_gpu`, :meth:`Engine.add_bam`): returns a dict with the merged index
     chunks of the regions, ``chunks`` (``uint64 [k, 2]``: ``[voff_beg, voff_end)`` pairs of virtual offsets, ascending and
     disjoint; bins + 16 kb linear index, SAM specification section 5 -- what ``AlignmentFile.fetch`` walks per region,
     genome_array.py:800-809), the span ``voff_begin``, ``voff_end`` that holds them all (0, 0: no chunk), the merged
     regions by reference id (``tid``, ``beg``, ``end`` arrays), the index's whole-file ``mapped`` count (-1: none) and the
-    file's ``references`` / ``lengths``."""
+    file's ``references`` / ``lengths``.
+    `index`: ``None`` -- the index beside the file (``path + ".bai"`` or ``.bai`` in place of ``.bam``); a path -- that index
+    file (a BAM file in a read-only directory); ``"build"`` -- the index beside the file, built on the GPU first when there
+    is none (:func:`build_index`)."""
     L = _load()
-    h = L.pb_open(os.fsencode(path))
-    if not h:
-        raise IOError(L.pb_last_error().decode())
+    h = _pb_open(L, path, _index_path(path, index))
     try:
         regs = _region_tuples(regions)
         n = len(regs)
@@ -148,7 +344,7 @@ def resolve_regions(path, regions):
                 tid=tid[:k].copy(), beg=beg[:k].copy(), end=end[:k].copy(), mapped=int(mapped.value), references=refs, lengths=lens)
 
 
-def read_bam_gpu(path, engine, timing=None, regions=None):
+def read_bam_gpu(path, engine, timing=None, regions=None, index=None):
     """The same :class:`PackedAlignments` as :func:`read_bam` gives for a whole file, decoded ON THE GPU: the file image
     goes to HBM as it is, the BGZF members are inflated there (one wave per member) and the BAM records decoded
     (``pc_bam_open``, ``csrc/bam_kernels.hip.h``); only the packed columns -- 13 bytes per record instead of the ~120 of
@@ -159,7 +355,8 @@ def read_bam_gpu(path, engine, timing=None, regions=None):
     `regions`: as for :func:`read_bam` -- only the alignments that overlap one of them, through the BAI index: only the
     BGZF members the index chunks of the regions point to (and the leading ones with the header) are uploaded and
     inflated (``pc_bam_open_chunks``; the overlap test then drops the records of those members that no region wants);
-    ``mapped`` is then the index's whole-file count, as pysam's."""
+    ``mapped`` is then the index's whole-file count, as pysam's.
+    `index` (with `regions`): as for :func:`resolve_regions` -- an index file elsewhere, or ``"build"``."""
     import time
     from . import _lib as clib
     L = clib.load()
@@ -169,7 +366,7 @@ def read_bam_gpu(path, engine, timing=None, regions=None):
     h = ctypes.c_void_p()
     span = None
     if regions is not None:
-        span = resolve_regions(path, regions)
+        span = resolve_regions(path, regions, index=_index_path(path, index, engine))
         pv = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
         cb, ce = np.ascontiguousarray(span["chunks"][:, 0]), np.ascontiguousarray(span["chunks"][:, 1])
         clib.check(L.pc_bam_open_chunks(engine._h, os.fsencode(path), len(cb), pv(cb), pv(ce), len(span["tid"]),
@@ -224,7 +421,7 @@ def read_bam_gpu(path, engine, timing=None, regions=None):
     return out
 
 
-def read_bam(path, threads=0, regions=None):
+def read_bam(path, threads=0, regions=None, index=None):
     """Read a coordinate-sorted BAM file into a :class:`PackedAlignments`.
 
     `regions`: iterable of ``(chrom, start, end)`` (0-based, half-open) or objects with those
@@ -232,14 +429,14 @@ def read_bam(path, threads=0, regions=None):
     the file's BAI index (``path + ".bai"`` or ``.bai`` in place of ``.bam``) -- what the reference
     does region by region with ``AlignmentFile.fetch`` (genome_array.py:800-809), here for a whole
     query set at once.  Counts over positions inside the regions equal those of the whole file.
+    `index` (with `regions`): ``None`` -- the index beside the file; a path -- that index file; ``"build"`` -- build the
+    index on the GPU first when there is none (:func:`build_index`).
 
     ``mapped`` is the number of records with flag 0x4 unset (what ``pysam
     AlignmentFile.mapped`` reports from the index); unplaced reads are not staged
     (``fetch`` never returns them).  Raises ``ValueError`` for unsorted input, as pysam does."""
     L = _load()
-    h = L.pb_open(os.fsencode(path))
-    if not h:
-        raise IOError(L.pb_last_error().decode())
+    h = _pb_open(L, path, _index_path(path, index) if regions is not None else None)
     try:
         if regions is None:
             rc = L.pb_load(h, int(threads))

@@ -1,7 +1,9 @@
 // Compressed BAM on the GPU, host side: the entry points of include/plastid_counts.h that decode a BAM file with the
 // kernels of bam_kernels.hip.h.  One open is five phases (bam_open_impl): plan_members, upload_and_inflate, read_header,
-// chain_records, decode_columns.  Part of the one translation unit of plastid_counts.hip.
+// chain_records, decode_columns.  The BAI index build (bam_index_impl) runs the first four and index_records in place of the fifth.  Part of the one translation unit of plastid_counts.hip.
 #include "bam_kernels.hip.h"
+#include "index_kernels.hip.h"
+#include "bam_index.h"
 
 struct pc_bam {
     pc_engine *e = nullptr;
@@ -144,7 +146,7 @@ int parse_member(const uint8_t *image, int64_t size, int64_t off, pcbam::Member 
     const int64_t hdr = 12 + xlen;
     if (clen < hdr + 8) return 7;
     mb.coff = (uint64_t)(off + hdr); mb.clen = (uint32_t)(clen - hdr - 8); mb.ulen = isize; mb.uoff = 0;
-    mb.crc = brd32(image + off + clen - 8); mb.pad = 0;
+    mb.crc = brd32(image + off + clen - 8); mb.hdr = (uint32_t)hdr;
     clen_out = clen;
     return 0;
 }
@@ -629,6 +631,35 @@ int chain_records(BamDecode &d, const BamPlan &pl, const BamSpan *span, const Ba
     return PC_OK;
 }
 
+// The first defect the record decode found (k_bam_order's lowest record index), as the error the host reader gives for it;
+// PC_OK for kRecTruncated / kRecBadSize, which the caller reports after every other defect.
+int record_defect(int code, const char *path) {
+    using namespace pcbam;
+    switch (code) {
+    case kRecTidRange: return fail(PC_ERR_ARG, "BAM record with reference id out of range");
+    case kRecNegPos: return fail(PC_ERR_ARG, "placed BAM record with a negative position");
+    case kRecUnsorted: return fail(PC_ERR_UNSORTED, "BAM file is not coordinate sorted: %s", path);
+    case kRecCigarOverrun: return fail(PC_ERR_ARG, "corrupt BAM record (cigar overruns block)");
+    case kRecUnknownOp: return fail(PC_ERR_ARG, "unknown CIGAR operation in %s", path);
+    case kRecEndBeyond: return fail(PC_ERR_ARG, "alignment ends beyond 2^31 - 1");
+    case kRecTooLong: return fail(PC_ERR_ARG, "alignment with more than 2^31 - 1 aligned positions");
+    case kRecDeletionOrder: return fail(PC_ERR_ARG, "alignment starting with a deletion breaks coordinate order; not supported");
+    default: return PC_OK;
+    }
+}
+
+// the member of every 256th record (k_bam_fields and its kin walk forward from there)
+std::vector<uint32_t> group_members(const std::vector<uint64_t> &rec_base, int64_t nrec, int nm) {
+    std::vector<uint32_t> rec_member((size_t)((nrec + 255) >> 8));
+    int m = 0;
+    for (size_t g = 0; g < rec_member.size(); ++g) {
+        const uint64_t i = (uint64_t)g << 8;
+        while (m + 1 < nm && rec_base[(size_t)m + 1] <= i) ++m;
+        rec_member[g] = (uint32_t)m;
+    }
+    return rec_member;
+}
+
 // Phase 5: fields, order checks, the region filter, the scans that place every kept record, and the columns of `b`.
 int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const BamHeader &h, const BamRecords &recs, pc_bam &b) {
     using namespace pcbam;
@@ -647,15 +678,7 @@ int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const B
     HIP_TRY(hipMemcpyAsync(d_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, st));
     int64_t n_staged = 0, n_runs = 0;
     if (nrec > 0) {
-        std::vector<uint32_t> rec_member((size_t)((nrec + 255) >> 8));
-        {
-            int m = 0;
-            for (size_t g = 0; g < rec_member.size(); ++g) {
-                const uint64_t i = (uint64_t)g << 8;
-                while (m + 1 < nm && recs.rec_base[(size_t)m + 1] <= i) ++m;
-                rec_member[g] = (uint32_t)m;
-            }
-        }
+        const std::vector<uint32_t> rec_member = group_members(recs.rec_base, nrec, nm);
         rc = d_rec_base.upload(recs.rec_base, st);
         if (rc == PC_OK) rc = d_rec_member.upload(rec_member, st);
         room(rc, d_recs, (size_t)nrec);
@@ -698,17 +721,9 @@ int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const B
             n_staged = tot[0]; n_runs = tot[1];
             b.mapped = (int64_t)misc[1]; b.unplaced = (int64_t)misc[2];
             if (misc[0] != ~0ull) {
-                switch ((int)(misc[0] & 0xffu)) {
-                case kRecTidRange: return fail(PC_ERR_ARG, "BAM record with reference id out of range");
-                case kRecNegPos: return fail(PC_ERR_ARG, "placed BAM record with a negative position");
-                case kRecUnsorted: return fail(PC_ERR_UNSORTED, "BAM file is not coordinate sorted: %s", d.path.c_str());
-                case kRecCigarOverrun: return fail(PC_ERR_ARG, "corrupt BAM record (cigar overruns block)");
-                case kRecUnknownOp: return fail(PC_ERR_ARG, "unknown CIGAR operation in %s", d.path.c_str());
-                case kRecEndBeyond: return fail(PC_ERR_ARG, "alignment ends beyond 2^31 - 1");
-                case kRecTooLong: return fail(PC_ERR_ARG, "alignment with more than 2^31 - 1 aligned positions");
-                case kRecDeletionOrder: return fail(PC_ERR_ARG, "alignment starting with a deletion breaks coordinate order; not supported");
-                default: truncated = true; break;   // kRecTruncated / kRecBadSize: reported below, after every other defect
-                }
+                rc = record_defect((int)(misc[0] & 0xffu), d.path.c_str());
+                if (rc != PC_OK) return rc;
+                truncated = true;   // kRecTruncated / kRecBadSize: reported below, after every other defect
             }
         }
         if (truncated) return fail(PC_ERR_ARG, "truncated BAM record");
@@ -766,6 +781,183 @@ int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const B
     return PC_OK;
 }
 
+// What index_records brings down for pc_bam_index_finish.
+struct IndexParts {
+    std::vector<int32_t> run_tid;
+    std::vector<uint32_t> run_bin;
+    std::vector<uint64_t> run_beg, run_end, linear, ref_beg, ref_end;
+    std::vector<int64_t> lin_start, ref_mapped, ref_unmapped;
+    int64_t n_no_coor = 0;
+    double ms_fields = 0, ms_kernels = 0, ms_readback = 0;   // wall clock between the phase's synchronisations
+};
+
+// The index build's phase 5 (whole-file reads only): k_bam_fields and the order checks as decode_columns runs them -- no
+// column is written or read back -- then the kernels of index_kernels.hip.h; the sorted runs, the linear arrays and the
+// per-reference counts come down.
+int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader &h, const BamRecords &recs, IndexParts &out) {
+    using namespace pcbam;
+    using namespace pcidx;
+    hipStream_t st = d.st;
+    const int nm = pl.nm();
+    const int64_t nrec = recs.nrec;
+    const int n_ref = (int)h.n_ref;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
+    out.lin_start.assign((size_t)n_ref + 1, 0);
+    out.ref_beg.assign((size_t)n_ref, 0); out.ref_end.assign((size_t)n_ref, 0);
+    out.ref_mapped.assign((size_t)n_ref, 0); out.ref_unmapped.assign((size_t)n_ref, 0);
+    if (nrec == 0) {
+        if (recs.truncated) return fail(PC_ERR_ARG, "truncated BAM record");
+        return PC_OK;
+    }
+    // where bgzf_tell places a stream position (bgzf.c:569-572): per member, the file offset of the first gzip header whose
+    // payload begins where the member's does -- an empty member in front of it, if there is one -- and of its own header; the
+    // end of the stream lies in the first member behind the last payload (the EOF block), or at the end of the file
+    std::vector<uint64_t> blk(2 * (size_t)nm + 2);
+    {
+        uint64_t prev_end = 0;
+        for (int m = 0; m < nm; ++m) {
+            const Member &mb = pl.members[(size_t)m];
+            const uint64_t own = mb.coff - mb.hdr;
+            blk[2 * (size_t)m] = std::min(prev_end, own); blk[2 * (size_t)m + 1] = own;
+            prev_end = mb.coff + mb.clen + 8;
+        }
+        blk[2 * (size_t)nm] = blk[2 * (size_t)nm + 1] = std::min<uint64_t>(prev_end, (uint64_t)size);
+    }
+    DevBuf<uint64_t> d_rec_base, d_blk, d_key, d_voff, d_cov, d_covered;
+    DevBuf<uint32_t> d_rec_member, d_placed, d_mapped, d_mapped_before, d_head, d_slot;
+    DevBuf<int32_t> d_win_a;
+    DevBuf<RecOut> d_recs;
+    DevBuf<unsigned long long> d_misc;   // [0] first error (index << 8 | code); [1] (as uint32) a record reaches beyond 2^29
+    DevBuf<int64_t> d_ref_fl;            // first record of every reference, then the last
+    const size_t n1 = (size_t)nrec + 1, nr = (size_t)std::max(n_ref, 1);
+    int rc = d_misc.reserve(2);
+    room(rc, d_recs, (size_t)nrec); room(rc, d_placed, 1);
+    room(rc, d_key, (size_t)nrec); room(rc, d_voff, n1); room(rc, d_cov, n1); room(rc, d_covered, n1); room(rc, d_win_a, (size_t)nrec);
+    room(rc, d_mapped, n1); room(rc, d_mapped_before, n1); room(rc, d_head, n1); room(rc, d_slot, n1); room(rc, d_ref_fl, 2 * nr);
+    if (rc == PC_OK) rc = d_rec_base.upload(recs.rec_base, st);
+    const std::vector<uint32_t> rec_member = group_members(recs.rec_base, nrec, nm);
+    if (rc == PC_OK) rc = d_rec_member.upload(rec_member, st);
+    if (rc == PC_OK) rc = d_blk.upload(blk, st);
+    if (rc != PC_OK) return rc;
+    const unsigned long long misc0[2] = {~0ull, 0ull};
+    HIP_TRY(hipMemcpyAsync(d_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, st));
+    const unsigned g256 = (unsigned)((nrec + 255) / 256), g256p = (unsigned)((nrec + 1 + 255) / 256);
+    hipLaunchKernelGGL(k_bam_fields, dim3(g256), dim3(256), 0, st, d.d_stream.p, pl.total_u, d.d_members.p, d_rec_base.p, d.d_chain.p, d.d_rec_off.p, nm, nrec,
+                       h.n_ref, d_rec_member.p, d_recs.p);
+    hipLaunchKernelGGL(k_bam_order, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, d_placed.p, d_misc.p);
+    HIP_TRY(hipGetLastError());
+    unsigned long long misc[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(misc, d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out.ms_fields = ms_since(t0);
+    if (misc[0] != ~0ull) {   // the decoder's own refusals, in its order
+        rc = record_defect((int)(misc[0] & 0xffu), d.path.c_str());
+        return rc != PC_OK ? rc : fail(PC_ERR_ARG, "truncated BAM record");
+    }
+    if (recs.truncated) return fail(PC_ERR_ARG, "truncated BAM record");
+    const auto t1 = std::chrono::steady_clock::now();
+    // ---- keys, runs, per-reference bounds, covered windows
+    hipLaunchKernelGGL(k_idx_keys, dim3(g256p), dim3(256), 0, st, d.d_stream.p, d.d_members.p, d_blk.p, d_rec_base.p, d.d_rec_off.p, nm, nrec, d_rec_member.p,
+                       d_recs.p, d_key.p, d_voff.p, d_win_a.p, d_cov.p, d_mapped.p, (uint32_t *)(d_misc.p + 1));
+    HIP_TRY(hipMemsetAsync(d_ref_fl.p, 0xff, 2 * nr * sizeof(int64_t), st));
+    hipLaunchKernelGGL(k_idx_heads, dim3(g256p), dim3(256), 0, st, d_key.p, nrec, d_head.p, d_ref_fl.p, d_ref_fl.p + nr);
+    HIP_TRY(hipGetLastError());
+    DevBuf<uint8_t> d_tmp;
+    {
+        size_t a = 0, b = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, a, d_head.p, d_slot.p, (int)n1, st));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, b, d_cov.p, d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st));
+        size_t tmp_bytes = std::max<size_t>(std::max(a, b), 16);
+        rc = d_tmp.reserve(tmp_bytes);
+        if (rc != PC_OK) return rc;
+        a = b = tmp_bytes;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, a, d_head.p, d_slot.p, (int)n1, st));
+        a = tmp_bytes;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, a, d_mapped.p, d_mapped_before.p, (int)n1, st));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(d_tmp.p, b, d_cov.p, d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st));
+    }
+    DevBuf<uint64_t> d_ref_be;     // per reference: offset of its first record, then of the first record behind its last
+    DevBuf<int64_t> d_ref_cnt;     // mapped, then unmapped
+    DevBuf<int32_t> d_n_intv;
+    room(rc, d_ref_be, 2 * nr); room(rc, d_ref_cnt, 2 * nr); room(rc, d_n_intv, nr);
+    if (rc != PC_OK) return rc;
+    std::vector<int32_t> n_intv((size_t)n_ref, 0);
+    uint32_t n_runs32 = 0;
+    if (n_ref) {
+        hipLaunchKernelGGL(k_idx_ref_stats, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), 0, st, n_ref, d_ref_fl.p, d_ref_fl.p + nr, d_voff.p, d_mapped_before.p,
+                           d_covered.p, d_ref_be.p, d_ref_be.p + nr, d_ref_cnt.p, d_ref_cnt.p + nr, d_n_intv.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(n_intv.data(), d_n_intv.p, (size_t)n_ref * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.ref_beg.data(), d_ref_be.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.ref_end.data(), d_ref_be.p + nr, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.ref_mapped.data(), d_ref_cnt.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.ref_unmapped.data(), d_ref_cnt.p + nr, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(&n_runs32, d_slot.p + nrec, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(misc, d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((uint32_t)misc[1]) return fail(PC_ERR_ARG, "a BAI index cannot hold %s: an alignment reaches beyond 2^29", d.path.c_str());
+    int64_t placed = 0;
+    for (int t = 0; t < n_ref; ++t) {
+        out.lin_start[(size_t)t + 1] = out.lin_start[(size_t)t] + n_intv[(size_t)t];
+        placed += out.ref_mapped[(size_t)t] + out.ref_unmapped[(size_t)t];
+    }
+    out.n_no_coor = nrec - placed;
+    const int64_t n_runs = (int64_t)n_runs32, n_lin = out.lin_start[(size_t)n_ref];
+    // ---- the runs in (tid, bin) order, the linear windows
+    DevBuf<uint64_t> d_run_key, d_run_key2, d_run_beg, d_run_end, d_sbeg, d_send, d_linear;
+    DevBuf<uint32_t> d_order, d_order2, d_sbin;
+    DevBuf<int32_t> d_stid;
+    DevBuf<int64_t> d_lin_base;
+    const size_t nrun = (size_t)std::max<int64_t>(n_runs, 1);
+    room(rc, d_run_key, nrun); room(rc, d_run_key2, nrun); room(rc, d_run_beg, nrun); room(rc, d_run_end, nrun); room(rc, d_sbeg, nrun); room(rc, d_send, nrun);
+    room(rc, d_order, nrun); room(rc, d_order2, nrun); room(rc, d_sbin, nrun); room(rc, d_stid, nrun);
+    room(rc, d_linear, (size_t)std::max<int64_t>(n_lin, 1));
+    if (rc == PC_OK) rc = d_lin_base.upload(out.lin_start, st);
+    if (rc != PC_OK) return rc;
+    out.run_tid.resize((size_t)n_runs); out.run_bin.resize((size_t)n_runs); out.run_beg.resize((size_t)n_runs); out.run_end.resize((size_t)n_runs);
+    out.linear.resize((size_t)n_lin);
+    if (n_runs) {
+        hipLaunchKernelGGL(k_idx_runs, dim3(g256p), dim3(256), 0, st, d_key.p, d_voff.p, d_head.p, d_slot.p, nrec, d_run_key.p, d_run_beg.p, d_run_end.p);
+        // (hipcub's iota: the slots 0 .. n_runs - 1 are the values of the sort)
+        std::vector<uint32_t> iota((size_t)n_runs);
+        std::iota(iota.begin(), iota.end(), 0u);
+        HIP_TRY(hipMemcpyAsync(d_order.p, iota.data(), (size_t)n_runs * 4, hipMemcpyHostToDevice, st));
+        int key_bits = 32;   // bin below, then as many bits as the reference ids take
+        while (key_bits < 64 && ((uint64_t)n_ref >> (key_bits - 32))) ++key_bits;
+        size_t sort_bytes = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st));
+        DevBuf<uint8_t> d_sort_tmp;
+        rc = d_sort_tmp.reserve(std::max<size_t>(sort_bytes, 16));
+        if (rc != PC_OK) { (void)hipStreamSynchronize(st); return rc; }
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, sort_bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st));
+        hipLaunchKernelGGL(k_idx_gather, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, d_run_key2.p, d_order2.p, d_run_beg.p, d_run_end.p, n_runs,
+                           d_stid.p, d_sbin.p, d_sbeg.p, d_send.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));   // (iota and the sort's scratch go out of scope)
+    }
+    if (n_lin) {
+        HIP_TRY(hipMemsetAsync(d_linear.p, 0, (size_t)n_lin * 8, st));
+        hipLaunchKernelGGL(k_idx_linear, dim3(g256), dim3(256), 0, st, d_cov.p, d_covered.p, d_win_a.p, d_voff.p, nrec, d_lin_base.p, d_linear.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    out.ms_kernels = ms_since(t1);
+    const auto t2 = std::chrono::steady_clock::now();
+    if (n_runs) {
+        HIP_TRY(hipMemcpyAsync(out.run_tid.data(), d_stid.p, (size_t)n_runs * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.run_bin.data(), d_sbin.p, (size_t)n_runs * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.run_beg.data(), d_sbeg.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.run_end.data(), d_send.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (n_lin) HIP_TRY(hipMemcpyAsync(out.linear.data(), d_linear.p, (size_t)n_lin * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out.ms_readback = ms_since(t2);
+    d.clk.lap("fields + index kernels + read-back");
+    return PC_OK;
+}
+
 } // namespace
 
 // One open: the five phases above, in order.  `span`: a region read (its chunk list and regions); nullptr: the whole file.
@@ -803,6 +995,51 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     for (int k = 0; k < 4; ++k) b->ms[k] = ms_between(d.ev[k], d.ev[k + 1]);
     guard.b = nullptr;
     *out = b;
+    return PC_OK;
+}
+
+// The index build: phases 1 - 4 of a whole-file open, index_records, pc_bam_index_finish.
+static int bam_index_impl(pc_engine *e, const void *image_, int64_t size, const char *name, pc_bam_index **out, const UploadedHook *uploaded, const BamKnobs &knobs) {
+    if (!e || !out || size < 0 || (size > 0 && !image_)) return fail(PC_ERR_ARG, "pc_bam_index_build: bad arguments");
+    *out = nullptr;
+    const auto t_0 = std::chrono::steady_clock::now();
+    const uint8_t *image = (const uint8_t *)image_;
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    BamDecode d{e, e->stream, name ? name : "<memory>", knobs};
+    BamPlan pl;
+    int rc = plan_members(image, size, nullptr, d.path.c_str(), knobs.walk_min, pl);
+    if (rc != PC_OK) return rc;
+    d.clk.lap("member walk");
+    for (auto &x : d.ev) HIP_TRY(hipEventCreate(&x));
+    struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]); } } evg{d.ev};
+    rc = upload_and_inflate(d, image, pl, uploaded);
+    if (rc != PC_OK) return rc;
+    BamHeader h;
+    rc = read_header(d, pl, size, nullptr, h);
+    if (rc != PC_OK) return rc;
+    BamRecords recs;
+    rc = chain_records(d, pl, nullptr, h, recs);
+    if (rc != PC_OK) return rc;
+    if (recs.nrec >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_bam_index_build: more than 2^31-2 records per file are not supported");
+    IndexParts parts;
+    rc = index_records(d, pl, size, h, recs, parts);
+    if (rc != PC_OK) return rc;
+    for (size_t t = 0; t < h.ref_lengths.size(); ++t)   // (behind the decoder's own refusals)
+        if ((int64_t)h.ref_lengths[t] > pcidx::kBaiReach || h.ref_lengths[t] < 0)
+            return fail(PC_ERR_ARG, "a BAI index cannot hold %s: reference %s is longer than 2^29", d.path.c_str(), h.ref_names[t].c_str());
+    const auto t_f = std::chrono::steady_clock::now();
+    pc_bam_index *idx = nullptr;
+    rc = pc_bam_index_finish((int)h.n_ref, (int64_t)parts.run_tid.size(), parts.run_tid.data(), parts.run_bin.data(), parts.run_beg.data(), parts.run_end.data(),
+                             parts.lin_start.data(), parts.linear.data(), parts.ref_beg.data(), parts.ref_end.data(), parts.ref_mapped.data(),
+                             parts.ref_unmapped.data(), parts.n_no_coor, &idx);
+    if (rc != PC_OK) return rc;
+    const auto t_e = std::chrono::steady_clock::now();
+    for (int k = 0; k < 3; ++k) idx->ms[k] = ms_between(d.ev[k], d.ev[k + 1]);
+    idx->ms[3] = parts.ms_fields; idx->ms[4] = parts.ms_kernels; idx->ms[5] = parts.ms_readback;
+    idx->ms[6] = std::chrono::duration<double, std::milli>(t_e - t_f).count();
+    idx->ms[7] = std::chrono::duration<double, std::milli>(t_e - t_0).count();
+    *out = idx;
     return PC_OK;
 }
 
@@ -1110,6 +1347,55 @@ int pc_bam_read_nh(pc_bam *b, uint16_t *nh) {
     std::vector<TransferJob> jobs;
     if (b->n && nh) jobs.push_back({nh, b->nh.p, (size_t)b->n * 2});
     return TransferRing::of(b->e->device).run(b->e->device, jobs, TransferRing::kPiece, false, true);
+}
+
+int pc_bam_index_build(pc_engine *e, const char *path, pc_bam_index **out) {
+    if (!e || !path || !out) return fail(PC_ERR_ARG, "pc_bam_index_build: bad arguments");
+    const BamKnobs knobs;
+    MappedFile mf;
+    const int rc = mf.open(path, -1, knobs.touch);
+    if (rc != PC_OK) return rc;
+    const int device = e->device;
+    const UploadedHook release = [&mf, device](hipStream_t up) { mf.release_behind(up, device); };
+    return bam_index_impl(e, mf.p, (int64_t)mf.size, path, out, &release, knobs);
+}
+
+int pc_bam_index_finish(int n_ref, int64_t n_runs, const int32_t *run_tid, const uint32_t *run_bin, const uint64_t *run_beg, const uint64_t *run_end,
+                        const int64_t *lin_start, const uint64_t *linear, const uint64_t *ref_beg, const uint64_t *ref_end, const int64_t *ref_mapped,
+                        const int64_t *ref_unmapped, int64_t n_no_coor, pc_bam_index **out) {
+    if (!out) return fail(PC_ERR_ARG, "pc_bam_index_finish: bad arguments");
+    *out = nullptr;
+    pc_bam_index *idx = new pc_bam_index();
+    const auto t0 = std::chrono::steady_clock::now();
+    const char *msg = pcidxhost::finish(n_ref, n_runs, run_tid, run_bin, run_beg, run_end, lin_start, linear, ref_beg, ref_end, ref_mapped, ref_unmapped, n_no_coor, *idx);
+    if (msg) { delete idx; return fail(PC_ERR_ARG, "%s", msg); }
+    idx->ms[6] = idx->ms[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = idx;
+    return PC_OK;
+}
+
+int pc_bam_index_bytes(pc_bam_index *idx, void *buf, int64_t cap, int64_t *bytes) {
+    if (!idx || !bytes || cap < 0 || (cap > 0 && !buf)) return fail(PC_ERR_ARG, "pc_bam_index_bytes: bad arguments");
+    *bytes = (int64_t)idx->bytes.size();
+    if (cap >= *bytes && *bytes) std::memcpy(buf, idx->bytes.data(), idx->bytes.size());   // (a smaller buffer: the caller comes back with *bytes)
+    return PC_OK;
+}
+
+int pc_bam_index_stats(pc_bam_index *idx, int64_t *out8) {
+    if (!idx || !out8) return fail(PC_ERR_ARG, "pc_bam_index_stats: bad arguments");
+    for (int k = 0; k < 8; ++k) out8[k] = idx->stats[k];
+    return PC_OK;
+}
+
+int pc_bam_index_timing(pc_bam_index *idx, double *ms8) {
+    if (!idx || !ms8) return fail(PC_ERR_ARG, "pc_bam_index_timing: bad arguments");
+    for (int k = 0; k < 8; ++k) ms8[k] = idx->ms[k];
+    return PC_OK;
+}
+
+int pc_bam_index_close(pc_bam_index *idx) {
+    delete idx;
+    return PC_OK;
 }
 
 } // extern "C"

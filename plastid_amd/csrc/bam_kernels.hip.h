@@ -55,7 +55,7 @@ struct Member {
     uint32_t ulen;     // ISIZE: bytes it inflates to
     uint64_t uoff;     // where they go in the inflated stream
     uint32_t crc;      // CRC-32 of the payload (gzip trailer)
-    uint32_t pad;
+    uint32_t hdr;      // bytes of its gzip header (host side: the member starts at coff - hdr in the file)
 };
 
 // error codes of k_bgzf_inflate (per member)

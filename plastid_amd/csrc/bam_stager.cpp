@@ -10,7 +10,7 @@
 // BGZF members are independent, so they are inflated (and the records in them decoded) by a pool of threads.
 //
 // C ABI (ctypes: plastid_amd/bam.py):
-//   pb_open / pb_close, pb_nref / pb_ref_name / pb_ref_length,
+//   pb_open / pb_open_indexed / pb_close, pb_nref / pb_ref_name / pb_ref_length,
 //   pb_load  (decode the whole file), pb_counts, pb_fill (copy into caller arrays)
 #include <dlfcn.h>
 #include <zlib.h>
@@ -172,6 +172,7 @@ struct Cols {
 
 struct Bam {
     std::string path;
+    std::string index_path;   // pb_open_indexed: the index file to use instead of path + ".bai" / stem + ".bai"
     Arena arena;
     std::vector<std::string> ref_names;
     std::vector<int32_t> ref_lengths;
@@ -912,10 +913,12 @@ struct BaiRef {
     bool has_meta = false;
 };
 
-int load_bai(const std::string &bam_path, std::vector<BaiRef> &refs) {
+int load_bai(const std::string &bam_path, const std::string &index_path, std::vector<BaiRef> &refs) {
     std::vector<uint8_t> buf;
-    std::string ipath = bam_path + ".bai";
-    if (!read_file(ipath, buf)) {
+    std::string ipath = index_path.empty() ? bam_path + ".bai" : index_path;
+    if (!index_path.empty()) {
+        if (!read_file(ipath, buf)) return fail("cannot read the index of " + bam_path + " (" + ipath + ")");
+    } else if (!read_file(ipath, buf)) {
         ipath = bam_path.size() > 4 ? bam_path.substr(0, bam_path.size() - 4) + ".bai" : ipath;
         if (!read_file(ipath, buf)) return fail("cannot read the index of " + bam_path + " (.bam.bai / .bai)");
     }
@@ -1025,7 +1028,7 @@ struct RegionSpan { int32_t tid; int64_t s, e; };
 // index, sorted and merged (SAM specification section 5; what hts_itr_query does per region, hts.c:1924-1960).
 int resolve_regions(const Bam &bam, uint32_t n_ref, int nreg, const char *const *rname, const int64_t *rstart, const int64_t *rend,
                     std::vector<BaiRef> &refs, std::vector<RegionSpan> &merged, std::vector<std::pair<uint64_t, uint64_t>> &chunks) {
-    if (load_bai(bam.path, refs) != 0) return -1;
+    if (load_bai(bam.path, bam.index_path, refs) != 0) return -1;
     if (refs.size() != (size_t)n_ref) return fail("the index does not belong to this BAM file (reference count differs): " + bam.path);
     std::vector<RegionSpan> regs;
     for (int i = 0; i < nreg; ++i) {
@@ -1223,6 +1226,14 @@ void *pb_open(const char *path) {
     Bam *b = new Bam();
     b->path = path;
     return b;
+}
+
+// pb_open with an explicit index file (a BAM file in a read-only directory, an index built elsewhere): the region calls
+// read `index_path` instead of looking beside the file
+void *pb_open_indexed(const char *path, const char *index_path) {
+    void *h = pb_open(path);
+    if (h && index_path) static_cast<Bam *>(h)->index_path = index_path;
+    return h;
 }
 
 void pb_close(void *h) { delete static_cast<Bam *>(h); }

@@ -140,7 +140,7 @@ class Engine(object):
         for f in files:
             self.add_alignment_file(f, ntid)
 
-    def add_bam(self, path, regions=None):
+    def add_bam(self, path, regions=None, index=None):
         """Stage a coordinate-sorted BAM file WITHOUT its records ever visiting the host (``pc_add_alignment_bam``): the
         file image goes to HBM, the BGZF members are inflated and the records decoded there, and the packed columns are
         staged by kernels.  Returns the number of mapped reads (pysam's ``AlignmentFile.mapped``).  The engine then
@@ -149,14 +149,16 @@ class Engine(object):
         `regions`: stage only the alignments that overlap one of them (``(chrom, start, end)`` or |GenomicSegments|),
         through the file's BAI index -- only the BGZF members the index chunks of the regions point to are uploaded and inflated
         (``pc_add_alignment_bam_chunks``; what one rank of a multi-GPU job does with its genome range of a shared file);
-        the return value is then the number of mapped reads among those staged."""
+        the return value is then the number of mapped reads among those staged.
+        `index` (with `regions`): an index file elsewhere, or ``"build"`` to build a missing one on this engine first
+        (:func:`plastid_amd.bam.build_index`)."""
         import os
         if not os.path.isfile(path):
             raise IOError("No such file: %r" % (path,))
         mapped = ctypes.c_int64(0)
         if regions is not None:
-            from .bam import resolve_regions
-            sp = resolve_regions(path, regions)
+            from .bam import resolve_regions, _index_path
+            sp = resolve_regions(path, regions, index=_index_path(path, index, self))
             cb, ce = np.ascontiguousarray(sp["chunks"][:, 0]), np.ascontiguousarray(sp["chunks"][:, 1])
             rc = self._lib.pc_add_alignment_bam_chunks(self._h, os.fsencode(path), len(cb), _ptr(cb), _ptr(ce), len(sp["tid"]),
                                                        _ptr(sp["tid"]), _ptr(sp["beg"]), _ptr(sp["end"]), ctypes.byref(mapped))

@@ -41,10 +41,10 @@ from .roitools import GenomicSegment, SegmentChain
 GPU_DECODE_MIN_BYTES = 32 << 20
 
 
-def _open_alignment_source(src, regions=None, engine=None, decode="auto"):
+def _open_alignment_source(src, regions=None, engine=None, decode="auto", index=None):
     """Filenames are read with the package's own BAM readers; objects are used as
     given (``multiopen`` passes non-str objects through, util/io/openers.py:90-94).
-    `regions`: stage only the alignments that overlap them (through the BAI index).
+    `regions`: stage only the alignments that overlap them (through the BAI index; `index`: as for ``bam.read_bam``).
     `decode`: ``"host"`` (threads + zlib / libdeflate), ``"gpu"`` (the file image goes to HBM, pc_bam_open) or
     ``"auto"`` (the GPU for whole files of GPU_DECODE_MIN_BYTES and more); both give the same arrays."""
     if isinstance(src, PackedAlignments):
@@ -53,10 +53,11 @@ def _open_alignment_source(src, regions=None, engine=None, decode="auto"):
         from .bam import read_bam, read_bam_gpu
         if decode not in ("auto", "host", "gpu"):
             raise ValueError("decode must be 'auto', 'host' or 'gpu', got %r" % (decode,))
+        named = {} if index is None else dict(index=index)   # (the readers' calls are unchanged without the keyword)
         on_gpu = decode == "gpu" or (decode == "auto" and regions is None and os.path.exists(src) and os.path.getsize(src) >= GPU_DECODE_MIN_BYTES)
         if on_gpu and engine is not None:
             if decode == "gpu":   # (also with `regions`: the members the index points to are inflated on the GPU)
-                aln = read_bam_gpu(src, engine, regions=regions)
+                aln = read_bam_gpu(src, engine, regions=regions, **named)
                 aln.decoder = "gpu"
                 return aln
             # "auto": a file the device decoder rejects gets a second opinion from the host decoder (whose verdict -- the
@@ -67,7 +68,10 @@ def _open_alignment_source(src, regions=None, engine=None, decode="auto"):
                 return aln
             except (ValueError, IOError, OSError, RuntimeError):
                 pass
-        aln = read_bam(src, regions=regions)
+        if named and regions is not None:   # ("build": on the array's own engine)
+            from .bam import _index_path
+            named = dict(index=_index_path(src, index, engine))
+        aln = read_bam(src, regions=regions, **named)
         aln.decoder = "host"
         return aln
     return src
@@ -163,6 +167,8 @@ class BAMGenomeArray(object):
             bamfiles = bamfiles[0]
         # (extension) regions=[(chrom, start, end) | GenomicSegment, ...]: files named by path are staged
         # only where they overlap the regions, via their BAI index -- for a few loci of a large file
+        # (extension) index=None | path | "build": the index file of the region reads (bam.resolve_regions); "build" makes a
+        # missing one on the GPU first (bam.build_index)
         # (the engine exists before the files are opened: large BAM files are inflated and decoded on its GPU)
         self._engine = Engine(kwargs.get("device", 0))
         # (extension) keep_reads=False: files named by path go from their bytes to staged alignments entirely on the GPU
@@ -177,7 +183,8 @@ class BAMGenomeArray(object):
             if any(b.references != self.bamfiles[0].references for b in self.bamfiles):
                 raise ValueError("keep_reads=False needs the same reference list in every file")
         else:
-            self.bamfiles = [_open_alignment_source(x, kwargs.get("regions"), self._engine, kwargs.get("decode", "auto")) for x in bamfiles]
+            self.bamfiles = [_open_alignment_source(x, kwargs.get("regions"), self._engine, kwargs.get("decode", "auto"), kwargs.get("index"))
+                             for x in bamfiles]
         self._strands = ("+", "-", ".")
         self._normalize = False
         self._sum = None
@@ -200,9 +207,10 @@ class BAMGenomeArray(object):
             self._engine.clear_alignments()
             for fi, b in enumerate(self.bamfiles):
                 if kwargs.get("regions") is not None:   # only what overlaps the regions is staged; `mapped` is the index's whole-file count, as pysam's
-                    from .bam import resolve_regions
-                    kept = self._engine.add_bam(b.filename, regions=kwargs["regions"])
-                    whole = resolve_regions(b.filename, [])["mapped"]
+                    from .bam import resolve_regions, _index_path
+                    index = _index_path(b.filename, kwargs.get("index"), self._engine)
+                    kept = self._engine.add_bam(b.filename, regions=kwargs["regions"], index=index)
+                    whole = resolve_regions(b.filename, [], index=index)["mapped"]
                     b.mapped = whole if whole >= 0 else kept
                 else:
                     b.mapped = self._engine.add_bam(b.filename)
