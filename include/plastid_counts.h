@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 8
+#define PC_ABI_VERSION 9
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -137,6 +137,11 @@ int pc_add_alignment_file_wide(pc_engine *e, int64_t n, int32_t ntid, const int3
 int pc_update_flags(pc_engine *e, int file, int64_t n, const uint8_t *flags);
 int pc_num_files(pc_engine *e);
 int64_t pc_num_records(pc_engine *e, int file);
+/* Entries the point rules stream for one staged file: duplicate reads -- same contig, position, aligned length and
+ * strand -- are staged a second time as one entry with a multiplicity (up to 16 reads per entry; excluded reads and
+ * reads binned from the side lists are not carried), and counted once.  Equal to pc_num_records when the file keeps no
+ * such stream (too few duplicates to be worth its memory).  -1: bad file index. */
+int64_t pc_stream_entries(pc_engine *e, int file);
 /* Read objects of a staged file back (the reference hands pysam reads to its callers: get_reads / reads_out,
  * genome_array.py:834-859, and to filter functions, :697-722) -- for files whose records never visited the host
  * (pc_add_alignment_bam[_path | _span]).  pc_read_records: per requested record index its reference id, first aligned

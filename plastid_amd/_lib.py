@@ -46,6 +46,7 @@ SIGNATURES = {
     "pc_set_nh_filter": (_int, [_vp, _int]),
     "pc_num_files": (_int, [_vp]),
     "pc_num_records": (_i64, [_vp, _int]),
+    "pc_stream_entries": (_i64, [_vp, _int]),
     "pc_read_records": (_int, [_vp, _int, _i64] + [_vp] * 8),
     "pc_read_record_runs": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _vp, _vp]),
     "pc_set_mapping": (_int, [_vp, _int, _int, _vp, _vp, _int, _int, _int]),
@@ -112,7 +113,7 @@ _lib = None
 
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 def load():

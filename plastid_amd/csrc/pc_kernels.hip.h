@@ -81,6 +81,11 @@ constexpr int kStreamMaxLen = 255;        // aligned lengths the 4-byte record s
 // The fields sit where the kernel wants them: `word & 0xff4` is the byte offset of the record's
 // (length, strand) entry in the LDS table, `(word + entry) >> 16` its window-relative position.
 constexpr uint32_t kStreamSkip = 1u;
+// The COMPACT stream (stage_kernels.hip.h, k_compact_tiles) carries a group of reads with the same (contig, position,
+// length, strand) as one such word with `reads - 1` in bits 12-15; a word of the per-record stream has 0 there (one
+// read), so the kernel bins both alike.  The field is masked before the add above: it would carry into the position.
+constexpr int kStreamMultShift = 12;
+constexpr uint32_t kStreamMultMask = 0xfu << kStreamMultShift;
 __host__ __device__ inline uint32_t stream_word(uint32_t pos, uint32_t meta) {
     const uint32_t L = meta & 0xffffu, fl = (meta >> 16) & 0xffu, nb = meta >> 24;
     const bool skip = (fl & (kFlagExcluded | kFlagLong)) != 0u || nb >= 2u || L > (uint32_t)kStreamMaxLen;
@@ -98,6 +103,8 @@ constexpr int kModes = 4;
 struct FileView {
     const uint2 *rec;
     const uint32_t *stream;         // 4-byte record stream (see stream_word), padded to a multiple of 4 with skip words
+    const uint32_t *cstream;        // compact stream: duplicate reads as one entry with a multiplicity (nullptr: the file has none)
+    const uint32_t *clin_tab;       // its linear index (first entry at or after every bucket; same shape as lin_tab)
     const uint32_t *blk_off;
     const int2 *blk;
     const int64_t *tid_bounds;      // ntid+1
@@ -156,6 +163,8 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 struct GFile {
     const u32x2 PC_GLOBAL *rec;
     const u32x4 PC_GLOBAL *stream4; // the 4-byte record stream, four records per 16-byte load
+    const u32x4 PC_GLOBAL *cstream4; // the compact stream (nullptr: none)
+    const uint32_t PC_GLOBAL *clin_tab;
     const uint32_t PC_GLOBAL *blk_off;
     const i32x2 PC_GLOBAL *blk;
     const int64_t PC_GLOBAL *tid_bounds;
@@ -195,6 +204,8 @@ __device__ __forceinline__ GFile gfile(const FileView &v) {
     GFile g;
     g.rec = (const u32x2 PC_GLOBAL *)v.rec;
     g.stream4 = (const u32x4 PC_GLOBAL *)v.stream;
+    g.cstream4 = (const u32x4 PC_GLOBAL *)v.cstream;
+    g.clin_tab = (const uint32_t PC_GLOBAL *)v.clin_tab;
     g.blk_off = (const uint32_t PC_GLOBAL *)v.blk_off;
     g.blk = (const i32x2 PC_GLOBAL *)v.blk;
     g.tid_bounds = (const int64_t PC_GLOBAL *)v.tid_bounds;
@@ -275,8 +286,9 @@ struct Piece {
     int32_t pad;
 };
 
+constexpr uint32_t kItemMerge = 1u, kItemCompact = 2u;   // bits of WorkItem::merge
 struct WorkItem {
-    int64_t lo, hi;   // record range of the packed stream
+    int64_t lo, hi;   // range of the packed stream: records -- or, with kItemCompact, entries of the file's compact stream
     int64_t glo, ghi; // range of the gapped-record list (first work item of a tile only)
     int64_t llo, lhi; // candidate range of the long-span list (first work item only)
     uint32_t rlo, rhi; // range of the run stream
@@ -287,7 +299,7 @@ struct WorkItem {
     uint32_t piece_begin, piece_end;
     uint32_t op_begin, op_end;
     int32_t sub_lo, sub_hi; // the part of the window this item owns (window-relative positions)
-    uint32_t merge;         // 1: several items share the window (pile-up / several files) -> merge via hist
+    uint32_t merge;         // kItemMerge: several items share the window (pile-up / several files) -> merge via hist; kItemCompact: lo / hi index the compact stream
     uint16_t span_lo, span_hi; // bins that can ever be read back (see Tile)
 };
 
@@ -505,6 +517,22 @@ __device__ __forceinline__ int64_t lin_exact(const uint32_t PC_GLOBAL *v, const 
     while (lo < hi) {
         const int64_t mid = lo + ((hi - lo) >> 1);
         if ((int64_t)(int32_t)v[mid * STRIDE] < key) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// The exact lookup in a file's COMPACT stream, whose entries carry the low half of a position only: the entries of one
+// bucket lie within 128 positions of its edge, in non-decreasing order, so their distance from the edge (mod 2^16) is
+// monotone and a bisection needs no full positions.
+__device__ __forceinline__ int64_t clin_exact(const uint32_t PC_GLOBAL *cs, const uint32_t PC_GLOBAL *clin, int64_t lin0, int64_t nb, int64_t key) {
+    int64_t b = key <= 0 ? 0 : (key >> kLinShift);
+    if (b > nb) b = nb;
+    const int64_t b1 = b + 1 > nb ? nb : b + 1;
+    int64_t lo = clin[lin0 + b], hi = clin[lin0 + b1];
+    const uint32_t edge = (uint32_t)(b << kLinShift);
+    const int64_t want = key - (b << kLinShift);
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if ((int64_t)(((cs[mid] >> 16) - edge) & 0xffffu) < want) lo = mid + 1; else hi = mid;
     }
     return lo;
 }
@@ -939,7 +967,7 @@ __global__ __launch_bounds__(kRangesWG) void k_tile_ranges(const Tile *__restric
         w.op_begin = tl.op_begin; w.op_end = tl.op_end;
         w.win_start = tl.win_start;
         w.span_lo = tl.span_lo; w.span_hi = tl.span_hi;
-        w.merge = merge ? 1u : 0u;
+        w.merge = merge ? kItemMerge : 0u;
         const int64_t s_lo = ws + tl.span_lo, s_hi = ws + tl.span_hi + (1 << kLinShift) - 1, s_end = ws + tl.span_hi;
         auto head = [&](const FileRange &r) {
             w.lo = r.lo; w.hi = r.hi; w.glo = r.glo; w.ghi = r.ghi; w.llo = r.llo; w.lhi = r.lhi; w.rlo = r.rlo; w.rhi = r.rhi;
@@ -994,6 +1022,19 @@ __global__ __launch_bounds__(kRangesWG) void k_tile_ranges(const Tile *__restric
         }
         return;
     }
+    // One file with a compact stream: an item that is not merged streams ENTRIES -- the same bucket edges and exact
+    // bounds, looked up in the compact stream's index.  Everything that counts reads (the classes, R, the pile-up and
+    // 16-bit guards above) was decided on the record ranges: an item's multiplicities add up to its records.
+    auto compact_range = [&](WorkItem &wi, int64_t lo_key, bool lo_exact, int64_t hi_key, bool hi_exact) {
+        if (fv.cstream4 == nullptr) return;
+        const uint32_t PC_GLOBAL *cs = (const uint32_t PC_GLOBAL *)fv.cstream4;
+        wi.lo = lo_exact ? clin_exact(cs, fv.clin_tab, l0, nb, lo_key) : lin_floor(fv.clin_tab, l0, nb, lo_key);
+        wi.hi = hi_exact ? clin_exact(cs, fv.clin_tab, l0, nb, hi_key) : lin_floor(fv.clin_tab, l0, nb, hi_key);
+        if (wi.hi < wi.lo) wi.hi = wi.lo;
+        wi.merge |= kItemCompact;   // (what tells k_hist_point which stream lo / hi index)
+    };
+    const bool span_exact = (int)tl.span_hi - (int)tl.span_lo <= kExactSpan;
+    const int64_t span_a = ws + tl.span_lo - Ws + 1, span_e = span_exact ? ws + tl.span_hi : ws + tl.span_hi + (1 << kLinShift) - 1;
     WorkItem w;
     w.tile = (uint32_t)t;
     w.file = (uint32_t)f;
@@ -1002,10 +1043,11 @@ __global__ __launch_bounds__(kRangesWG) void k_tile_ranges(const Tile *__restric
     w.op_begin = tl.op_begin; w.op_end = tl.op_end;
     w.win_start = tl.win_start;
     w.span_lo = tl.span_lo; w.span_hi = tl.span_hi;
-    w.merge = merge ? 1u : 0u;
+    w.merge = merge ? kItemMerge : 0u;
     if (n_small) {
         w.lo = wlo; w.hi = whi; w.glo = wglo; w.ghi = wghi; w.llo = llo; w.lhi = lhi;
         w.rlo = (uint32_t)wrlo; w.rhi = (uint32_t)wrhi;
+        compact_range(w, span_a, span_exact, span_e, span_exact);
         w.win_start = tl.win_start + (int32_t)tl.span_lo; // a small window that starts at the first queried position
         w.sub_lo = 0; w.sub_hi = small_g;
         w.span_lo = 0; w.span_hi = (uint16_t)(tl.span_hi - tl.span_lo);
@@ -1043,6 +1085,7 @@ __global__ __launch_bounds__(kRangesWG) void k_tile_ranges(const Tile *__restric
                 w.rlo = fv.nrunrec ? (uint32_t)lin_floor(fv.rlin_tab, l0, nb, a - Wr + 1) : 0u;
                 w.rhi = fv.nrunrec ? (uint32_t)lin_floor(fv.rlin_tab, l0, nb, e) : 0u;
             }
+            compact_range(w, a - Ws + 1, sub <= kExactSpan, e, false);
             w.glo = fv.ngap ? lin_floor(fv.glin_tab, l0, nb, a - W + 1) : 0;
             w.ghi = fv.ngap ? lin_floor(fv.glin_tab, l0, nb, e) : 0;
             w.llo = llo; w.lhi = lhi;
@@ -1079,7 +1122,9 @@ __global__ __launch_bounds__(kRangesWG) void k_tile_ranges(const Tile *__restric
         w.llo = llo; w.lhi = lhi; // every sub-window checks the (few) long-span candidates
         w.sub_lo = S == 1 ? 0 : k * sub;
         w.sub_hi = S == 1 ? G : w.sub_lo + sub;
-        const uint32_t slot = (w.hi - w.lo) > R ? ih++ : work_cap - 1u - (il++);
+        const uint32_t slot = (w.hi - w.lo) > R ? ih++ : work_cap - 1u - (il++);   // (by records)
+        if (S == 1) compact_range(w, span_a, span_exact, span_e, span_exact);
+        else compact_range(w, a - Ws + 1, sub <= kExactSpan, e, false);
         if (slot < work_cap) work[slot] = w; // capacity is an upper bound; the test is defensive
     }
 }
@@ -1217,19 +1262,21 @@ __device__ __forceinline__ void fast_bin(const uint32_t *ftab, uint32_t mode_mas
         uint32_t addr[N];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            const uint32_t d = (w[i] + e[i]) >> 16;
+            const uint32_t d = ((w[i] & ~kStreamMultMask) + e[i]) >> 16;
             // (B16: the entry's low half is the bin's index in 16-bit units -- a byte address with 2-byte granularity)
             addr[i] = (((w[i] << 31) | d) < G) ? ((e[i] & 0xffffu) + d) << (B16 ? 1 : 2) : dump;
         }
-        uint32_t cnt = 1;
+        // (an entry of the compact stream stands for 1 + its multiplicity field reads, a per-record word for one)
+        uint32_t cnt = 0;
 #pragma unroll
         for (int i = 0; i < N; ++i) {
             const bool last = (i == N - 1) || (addr[i + 1 < N ? i + 1 : i] != addr[i]);
+            cnt += ((w[i] >> kStreamMultShift) & 0xfu) + 1u;
             if (last) {
                 if (B16) atomicAdd((uint32_t *)((char *)smem + (addr[i] & ~3u)), cnt << ((addr[i] & 2u) << 3));   // (the dump word is word-aligned: low half)
                 else atomicAdd((uint32_t *)((char *)smem + addr[i]), cnt);
             }
-            cnt = last ? 1u : cnt + 1u;
+            cnt = last ? 0u : cnt;
         }
     }
 }
@@ -1426,7 +1473,11 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MULTI ? 5 : 
     static_assert(U % 2 == 0, "PC_HIST_U must be even");
     const int64_t quad_lo = w.lo >> 2;
     const int nquads = (int)((w.hi >> 2) - quad_lo); // quads wholly below hi (may be 0, never negative)
-    const u32x4 PC_GLOBAL *src = fv.stream4 + quad_lo;
+    // (k_tile_ranges marks the items whose lo / hi it took from the compact stream's index: those of a one-file plan that are not merged)
+    const bool merged = (w.merge & kItemMerge) != 0u;
+    const bool compact = !MULTI && !SINGLE && (w.merge & kItemCompact) != 0u;
+    const u32x4 PC_GLOBAL *const stream4 = compact ? fv.cstream4 : fv.stream4;
+    const u32x4 PC_GLOBAL *src = stream4 + quad_lo;
     const u32x4 none = {kStreamSkip, kStreamSkip, kStreamSkip, kStreamSkip};
     u32x4 cur[U];
     {
@@ -1435,10 +1486,10 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MULTI ? 5 : 
         for (int u = 0; u < U; ++u) cur[u] = (lane_j + u * 64 < nquads) ? src[lane_j + u * 64] : none;
     }
     u32x4 tail = none;
-    if ((w.hi & 3) && threadIdx.x == 0) tail = fv.stream4[w.hi >> 2];
+    if ((w.hi & 3) && threadIdx.x == 0) tail = stream4[w.hi >> 2];
     // the window's output pieces (48 B each) are fetched now and parked in LDS, so that the
     // epilogue does not start with a chain of dependent global loads
-    const int nstage = w.merge ? 0 : (int)min(w.op_end - w.op_begin, (uint32_t)kOpStage);
+    const int nstage = merged ? 0 : (int)min(w.op_end - w.op_begin, (uint32_t)kOpStage);
     u32x4 opq = {0u, 0u, 0u, 0u};
     if ((!SINGLE || work) && (int)threadIdx.x < nstage * 3) opq = ((const u32x4 PC_GLOBAL *)(opieces + w.op_begin))[threadIdx.x];
     const u32x4 gnone = {0u, kFlagExcluded << 16, 0u, 0u};
@@ -1591,7 +1642,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MULTI ? 5 : 
     };
     if (!(PC_HIST_SKIP & 2)) side_lists(fv, w.rlo, w.rhi, w.glo, w.ghi, w.llo, w.lhi, true);
     // ---- joint window (several alignment files): the records of the other files into the same bins
-    if (MULTI && !w.merge) {
+    if (MULTI && !merged) {
         for (int ff = 1; ff < nfiles; ++ff) {
             const FileRange fr = chain[(size_t)slot * (size_t)(nfiles - 1) + (size_t)(ff - 1)];
             const GFile fv2 = ff == 1 ? gfile(file1) : gfile(files[ff]);
@@ -1630,7 +1681,7 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(MULTI ? 5 : 
     __syncthreads();
 
     if (PC_HIST_SKIP & 4) return;
-    if (!w.merge) {
+    if (!merged) {
         // ---- this workgroup owns [sub_lo, sub_hi) of the window and its bins are complete:
         // write every queried segment slice straight into the caller's layout (chain offset,
         // 5'->3' reversal, int64/float64, normalisation) -- SegmentChain.get_counts,

@@ -491,6 +491,12 @@ struct StagedFile {
     int slen_min = 0, slen_max = 0;    // ... among the records the 4-byte stream carries
     int tlen_min = 0, tlen_max = 0;    // ... among those and the reads of the run stream (range of the LDS entry table)
     DevBuf<uint32_t> stream;           // 4-byte record stream (pc::stream_word), padded with skip words
+    // compact stream (build_compact_stream): duplicate reads as one entry with a multiplicity, and its linear index;
+    // rebuilt whenever the stream words are rewritten.  cn = its entries, -1: none (nothing worth merging: the point
+    // rules stream the records)
+    DevBuf<uint32_t> cstream, clin_tab;
+    int64_t cn = -1;
+    size_t nlin = 0;                   // entries of every linear-index table
     // run stream (aligned runs of multi-run reads with L <= kStreamMaxLen, sorted by contig and run start)
     int64_t nrunrec = 0;
     int Wr = 1;                        // longest run it carries
@@ -528,6 +534,7 @@ struct StagedFile {
         FileView v;
         v.rec = rec.p; v.blk_off = blk_off.p; v.blk = blk.p; v.tid_bounds = tid_bounds.p;
         v.stream = stream.p;
+        v.cstream = cn >= 0 ? cstream.p : nullptr; v.clin_tab = cn >= 0 ? clin_tab.p : nullptr;
         v.long_idx = long_idx.p; v.long_tid = long_tid.p; v.long_pmax = long_pmax.p;
         v.long_tid_bounds = long_tid_bounds.p; v.long_rec = long_rec.p; v.n = n; v.nlong = nlong;
         v.gap_rec = gap_rec.p; v.gap_tid_bounds = gap_tid_bounds.p; v.ngap = ngap;
@@ -563,6 +570,8 @@ struct Knobs {
     int hist_memset = 0;       // PC_HIST_MEMSET: the compact histogram of a large plan is cleared as a whole before its first count (round 5) instead of slice by slice
     int64_t hist_lazy_bytes = (int64_t)64 << 20;   // PC_HIST_LAZY_BYTES: size from which it is cleared slice by slice (tests: 1)
     int no_stream_probe = 0;   // PC_NO_STREAM_PROBE: keep the engine's streams as created (see settle_streams)
+    int no_compact = 0;        // PC_NO_COMPACT: no compact stream -- files staged (or re-filtered) from then on are counted record by record (tests compare the two)
+    double compact_keep = 0.9; // PC_COMPACT_KEEP: a file that keeps more than this share of its records as entries gets no compact stream (build_compact_stream)
     int no_single = 0;         // PC_NO_SINGLE: one-window plans go through the work lists like any other (tests compare the two paths)
     int plan_build = 0;        // PC_PLAN_BUILD=host|gpu: where pc_plan_create builds the tables (default: on the GPU from 8 192 segments)
     int small_g = 512;         // PC_SMALL_G: queried span a single-wave window may have
@@ -583,6 +592,8 @@ struct Knobs {
         no_small = getenv("PC_NO_SMALL") ? 1 : 0;
         if (const char *env = getenv("PC_SMALL_ROWS")) small_rows = atoi(env);
         no_single = getenv("PC_NO_SINGLE") ? 1 : 0;
+        no_compact = getenv("PC_NO_COMPACT") ? 1 : 0;
+        if (const char *env = getenv("PC_COMPACT_KEEP")) compact_keep = std::min(1.0, std::max(0.0, atof(env)));
         no_stream_probe = getenv("PC_NO_STREAM_PROBE") ? 1 : 0;
         hist_memset = getenv("PC_HIST_MEMSET") ? 1 : 0;
         hist_lazy_bytes = getenv("PC_HIST_LAZY_BYTES") ? std::max<int64_t>(1, atoll(getenv("PC_HIST_LAZY_BYTES"))) : ((int64_t)64 << 20);
@@ -1462,6 +1473,11 @@ int64_t pc_num_records(pc_engine *e, int file) {
     if (!e || file < 0 || file >= (int)e->files.size()) return -1;
     return e->files[file]->n;
 }
+int64_t pc_stream_entries(pc_engine *e, int file) {
+    if (!e || file < 0 || file >= (int)e->files.size()) return -1;
+    const StagedFile *sf = e->files[file];
+    return sf->cn >= 0 ? sf->cn : sf->n;
+}
 
 namespace {
 // PC_STAGE_TIMING=1: print where pc_add_alignment_file spends its time (stderr)
@@ -1536,6 +1552,7 @@ int pc_add_alignment_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *
 // `dev`: the columns are in HBM already (a BAM file decoded on the GPU, pc_add_alignment_bam): the host pointers of the
 // columns and runs are then NULL and nothing is uploaded or validated (the decoder did that); the wide
 // side arrays come from the host either way.
+static int build_compact_stream(pc_engine *e, StagedFile *sf, int ntid);
 static int stage_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid, const int32_t *pos,
                       const uint16_t *alen, const uint8_t *flags, const uint8_t *nblk, int64_t nrun,
                       const int32_t *blk_start, const int32_t *blk_len, int64_t n_wide, const int64_t *wide_idx,
@@ -2016,6 +2033,10 @@ static int stage_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid,
     }
     if (rc != PC_OK) return rc;
     clk.lap("run stream (GPU sort)");
+    sf->nlin = nlin;
+    rc = build_compact_stream(e, sf, ntid);
+    if (rc != PC_OK) return rc;
+    clk.lap("compact stream (GPU)");
     owner.p = nullptr;
     e->files.push_back(sf);
     e->ntid = ntid;
@@ -2025,6 +2046,56 @@ static int stage_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid,
 }
 
 static int propagate_record_flags(pc_engine *e, StagedFile *sf);
+
+// The compact stream of a staged file and its linear index, from the stream words as they stand (stage_kernels.hip.h):
+// at staging, and again whenever the words are rewritten (pc_update_flags, the FLAG / MAPQ / NH filter).  One pass
+// over 4 bytes per record and an LDS sort per tile; the working arrays are the pool's and go back to it.
+// A file that keeps more than `compact_keep` (PC_COMPACT_KEEP, 0.9) of its records as entries gets none: its block
+// returns to the pool and the point rules stream the records, at no extra HBM.  (Every item pays the multiplicity
+// field's two instructions per word either way, so fewer entries are never slower to bin; what the bound weighs is 4
+// bytes of HBM per entry and a rebuild on every filter change against the stream bytes a count no longer reads, at most
+// a tenth of them at the bound.  The bound is reasoned, not measured: profiles/compact_stream/NOTES.md says how the
+// knob is to settle it.)
+static int build_compact_stream(pc_engine *e, StagedFile *sf, int ntid) {
+    using namespace pcstage;
+    sf->cn = -1;
+    const int64_t n = sf->n;
+    if (n <= 0 || !sf->nlin || e->knobs.no_compact) { sf->cstream.release(); sf->clin_tab.release(); return PC_OK; }
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    const uint32_t ntiles = (uint32_t)((n + kCompactTile - 1) / kCompactTile);
+    DevBuf<uint32_t> d_words, d_cnt, d_off, d_base;
+    DevBuf<uint8_t> d_scan;
+    int rc = d_words.reserve((size_t)n);
+    if (rc == PC_OK) rc = d_cnt.reserve((size_t)ntiles + 1);
+    if (rc == PC_OK) rc = d_off.reserve((size_t)ntiles + 1);
+    if (rc == PC_OK) rc = d_base.reserve((size_t)ntiles);
+    if (rc != PC_OK) return rc;
+    size_t tb = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt.p, d_off.p, (int)ntiles + 1, st));
+    rc = d_scan.reserve(std::max<size_t>(tb, 16));
+    if (rc != PC_OK) return rc;
+    HIP_TRY(hipMemsetAsync(d_cnt.p + ntiles, 0, 4, st));
+    hipLaunchKernelGGL(k_compact_tiles, dim3(ntiles), dim3(256), 0, st, sf->rec.p, sf->stream.p, n, sf->tid_bounds.p, ntid, d_words.p, d_cnt.p, d_base.p);
+    hipError_t he = hipcub::DeviceScan::ExclusiveSum(d_scan.p, tb, d_cnt.p, d_off.p, (int)ntiles + 1, st);
+    uint32_t total = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&total, d_off.p + ntiles, 4, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipGetLastError();
+    if (he == hipSuccess) he = hipStreamSynchronize(st);
+    if (he != hipSuccess) return fail(PC_ERR_HIP, "building the compact stream failed: %s", hipGetErrorString(he));
+    if ((double)total > e->knobs.compact_keep * (double)n) { sf->cstream.release(); sf->clin_tab.release(); return PC_OK; }
+    rc = sf->cstream.reserve((size_t)total + 8);
+    if (rc == PC_OK) rc = sf->clin_tab.reserve(sf->nlin);
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(k_compact_gather, dim3(ntiles), dim3(256), 0, st, d_words.p, d_off.p, ntiles, sf->cstream.p);
+    hipLaunchKernelGGL(k_compact_lin, dim3((unsigned)((sf->nlin + 255) / 256)), dim3(256), 0, st, sf->lin_tab.p, (int64_t)sf->nlin, sf->rec.p, n,
+                       d_off.p, d_base.p, sf->cstream.p, sf->clin_tab.p);
+    he = hipGetLastError();
+    if (he == hipSuccess) he = hipStreamSynchronize(st);   // (the working arrays go out of scope)
+    if (he != hipSuccess) return fail(PC_ERR_HIP, "building the compact stream failed: %s", hipGetErrorString(he));
+    sf->cn = (int64_t)total;
+    return PC_OK;
+}
 
 // The columns the engine's filter reads are there for this file: the ONE test of every setter, of pc_update_flags and
 // of the entry points that read the exclusion bits (check_filter_columns).
@@ -2075,7 +2146,8 @@ int pc_update_flags(pc_engine *e, int file, int64_t n, const uint8_t *flags) {
 }
 
 // The strand / excluded bits of the packed records have changed: copy them into every other staged form of the
-// headers (side lists, run stream), drop what was derived from them (center streams, work lists).  Asynchronous.
+// headers (side lists, run stream), rebuild the compact stream, drop what was derived from them (center streams, work
+// lists).  Waits for the engine's stream (build_compact_stream reads the entry count back).
 static int propagate_record_flags(pc_engine *e, StagedFile *sf) {
     hipStream_t st = e->stream;
     if (sf->nlong)
@@ -2091,6 +2163,7 @@ static int propagate_record_flags(pc_engine *e, StagedFile *sf) {
         hipLaunchKernelGGL(k_update_run_flags, dim3((unsigned)((sf->nrunrec + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->run_rec.p,
                            sf->run_recidx.p, sf->nrunrec, sf->rec.p);
     HIP_TRY(hipGetLastError());
+    { const int crc = build_compact_stream(e, sf, e->ntid); if (crc != PC_OK) return crc; }   // (the stream words have been rewritten)
     for (int k = 0; k < 3; ++k) sf->cs_n[k] = -1;   // the center streams leave excluded reads out: rebuilt at the next center count
     e->files_dirty = true;
     e->work_generation += 1;

@@ -24,6 +24,7 @@
 // and of the first check that fails for that record (an atomic minimum over `record << 8 | check`).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
 #include <stdint.h>
 
 #include "plastid_counts.h"
@@ -310,6 +311,159 @@ __global__ __launch_bounds__(256) void k_side_select(const uint2 *__restrict__ r
             for (int v = 0; v < w; ++v) before += s_w[k][v];
             out[k][at[k] + before + (uint32_t)__popcll(m[k] & below)] = (uint32_t)i;
         }
+}
+
+
+// ---- the compact record stream: duplicate reads counted once.  A point rule sends every read with the same (contig,
+// position, aligned length, strand) to the same bin, so the stream the window kernels read can carry such a group as ONE
+// entry with a multiplicity -- integer adds commute, every count stays what it was.  An entry is a stream word
+// (pc::stream_word) with `reads - 1` in bits 12-15 (pc::kStreamMultShift): up to kCompactCap reads, a larger group is
+// several entries, and a plain stream word is an entry of one read.
+//
+// A coordinate-sorted file orders reads by position only, so the grouping is done here: a tile of kCompactTile
+// consecutive records is sorted in LDS by (tile-relative position, length, strand) and run-length encoded; records with
+// the skip bit (excluded, or binned from a side list) are dropped.  Positions stay non-decreasing across the whole
+// compact stream, a group that straddles two tiles costs one more entry.  A tile that spans a contig change or more than
+// kCompactSpan positions stays as it is, skip words included, one entry per record (`tile_base` = kTileAsIs): two records
+// merge only inside a sorted tile, where equal keys mean equal contig AND equal full position.
+//   k_compact_tiles   per tile: its entries, left-aligned in tmp[tile * kCompactTile ..], their number, its first position
+//   (exclusive sum of the numbers)
+//   k_compact_gather  the entries of all tiles, packed; padded with skip words
+//   k_compact_lin     the linear index of the compact stream from that of the records: the entry that record
+//                     lin_tab[g] became the head of, or would have
+constexpr int kCompactItems = 8, kCompactTile = 256 * kCompactItems;
+constexpr uint32_t kCompactCap = 16u;
+constexpr int64_t kCompactSpan = 0x7ffe;     // (15 bits of relative position; 0x7fff is left to the dropped records' key)
+constexpr uint32_t kTileAsIs = 0xffffffffu;
+constexpr int kCompactKeyBits = 24;          // relative position 15 | aligned length 8 | strand 1
+
+__global__ __launch_bounds__(256) void k_compact_tiles(const uint2 *__restrict__ rec, const uint32_t *__restrict__ stream, int64_t n,
+                                                       const int64_t *__restrict__ tid_bounds, int ntid, uint32_t *__restrict__ tmp,
+                                                       uint32_t *__restrict__ tile_cnt, uint32_t *__restrict__ tile_base) {
+    typedef hipcub::BlockRadixSort<uint32_t, 256, kCompactItems> Sort;
+    typedef hipcub::BlockScan<int, 256> Scan;
+    __shared__ union { typename Sort::TempStorage sort; typename Scan::TempStorage scan; } s_tmp;
+    __shared__ uint32_t s_last[256];
+    __shared__ uint32_t s_epos[kCompactTile + 1];
+    const int64_t i0 = (int64_t)blockIdx.x * kCompactTile, i1 = i0 + kCompactTile < n ? i0 + kCompactTile : n;
+    const uint32_t base = rec[i0].x;
+    bool sortable = (int64_t)rec[i1 - 1].x - (int64_t)base <= kCompactSpan && (int64_t)rec[i1 - 1].x >= (int64_t)base;
+    if (sortable) {   // one contig: the first one that ends behind record i0 holds the whole tile
+        int lo = 0, hi = ntid;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (tid_bounds[mid + 1] <= i0) lo = mid + 1; else hi = mid;
+        }
+        sortable = lo < ntid && tid_bounds[lo + 1] >= i1;
+    }
+    if (!sortable) {
+        for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) tmp[i] = stream[i];
+        if (threadIdx.x == 0) { tile_cnt[blockIdx.x] = (uint32_t)(i1 - i0); tile_base[blockIdx.x] = kTileAsIs; }
+        return;
+    }
+    uint32_t key[kCompactItems];
+    int nvalid_mine = 0;
+#pragma unroll
+    for (int j = 0; j < kCompactItems; ++j) {
+        const int64_t i = i0 + (int64_t)threadIdx.x * kCompactItems + j;
+        key[j] = 0xffffffffu;
+        if (i < i1) {
+            const uint32_t w = stream[i];
+            if (!(w & pc::kStreamSkip)) {
+                key[j] = ((((w >> 16) - base) & 0xffffu) << 9) | (pc::stream_len(w) << 1) | ((w >> 2) & 1u);
+                ++nvalid_mine;
+            }
+        }
+    }
+    int before, nvalid;
+    Scan(s_tmp.scan).ExclusiveSum(nvalid_mine, before, nvalid);
+    __syncthreads();
+    Sort(s_tmp.sort).Sort(key, 0, kCompactKeyBits);   // (the dropped records' keys are all ones: they end up last)
+    s_last[threadIdx.x] = key[kCompactItems - 1];
+    __syncthreads();
+    // the start of the group every sorted record belongs to: a running maximum of the group heads' places
+    uint32_t prev = threadIdx.x ? s_last[threadIdx.x - 1] : 0xffffffffu;
+    const int p0 = (int)threadIdx.x * kCompactItems;
+    int head_mine = -1;
+    {
+        uint32_t pv = prev;
+#pragma unroll
+        for (int j = 0; j < kCompactItems; ++j) {
+            if (p0 + j < nvalid && (key[j] != pv || p0 + j == 0)) head_mine = p0 + j;
+            pv = key[j];
+        }
+    }
+    int gstart;
+    Scan(s_tmp.scan).ExclusiveScan(head_mine, gstart, -1, hipcub::Max());
+    __syncthreads();
+    // an entry starts a group, and every kCompactCap reads inside it
+    uint32_t is_entry = 0;
+    int ne = 0;
+#pragma unroll
+    for (int j = 0; j < kCompactItems; ++j) {
+        const int p = p0 + j;
+        if (p < nvalid) {
+            if (key[j] != prev || p == 0) gstart = p;
+            if ((((uint32_t)(p - gstart)) & (kCompactCap - 1u)) == 0u) { is_entry |= 1u << j; ++ne; }
+        }
+        prev = key[j];
+    }
+    int rank, total;
+    Scan(s_tmp.scan).ExclusiveSum(ne, rank, total);
+    {
+        int r = rank;
+#pragma unroll
+        for (int j = 0; j < kCompactItems; ++j)
+            if ((is_entry >> j) & 1u) s_epos[r++] = (uint32_t)(p0 + j);
+    }
+    if (threadIdx.x == 0) s_epos[total] = (uint32_t)nvalid;
+    __syncthreads();
+    // (an entry's reads: up to the next entry -- the next group, or the next kCompactCap of its own)
+#pragma unroll
+    for (int j = 0; j < kCompactItems; ++j)
+        if ((is_entry >> j) & 1u) {
+            const uint32_t reads = s_epos[rank + 1] - (uint32_t)(p0 + j);
+            const uint32_t k = key[j];
+            tmp[i0 + rank] = (((k >> 9) + base) << 16) | (((k >> 1) & 0xffu) << 4) | ((k & 1u) << 2) | ((reads - 1u) << pc::kStreamMultShift);
+            ++rank;
+        }
+    if (threadIdx.x == 0) { tile_cnt[blockIdx.x] = (uint32_t)total; tile_base[blockIdx.x] = base; }
+}
+
+// `off`: exclusive sum of tile_cnt (ntiles + 1 entries); eight skip words follow the last entry
+__global__ __launch_bounds__(256) void k_compact_gather(const uint32_t *__restrict__ tmp, const uint32_t *__restrict__ off, uint32_t ntiles,
+                                                        uint32_t *__restrict__ cstream) {
+    const uint32_t o0 = off[blockIdx.x], cnt = off[blockIdx.x + 1] - o0;
+    const uint32_t *src = tmp + (size_t)blockIdx.x * kCompactTile;
+    for (uint32_t k = threadIdx.x; k < cnt; k += 256) cstream[o0 + k] = src[k];
+    if (blockIdx.x == 0 && threadIdx.x < 8) cstream[off[ntiles] + threadIdx.x] = pc::kStreamSkip;
+}
+
+// clin[g] = the entries before record lin_tab[g].  A table entry is the first record at or behind a position, and a
+// sorted tile is single-contig and sorted by position, so the records before it are the entries of the earlier tiles and
+// those of its own tile with a smaller position (relative positions are monotone inside a sorted tile).
+__global__ __launch_bounds__(256) void k_compact_lin(const uint32_t *__restrict__ lin_tab, int64_t nlin, const uint2 *__restrict__ rec, int64_t n,
+                                                     const uint32_t *__restrict__ off, const uint32_t *__restrict__ tile_base,
+                                                     const uint32_t *__restrict__ cstream, uint32_t *__restrict__ clin) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= nlin) return;
+    const int64_t r = lin_tab[g];
+    const int64_t tile = r / kCompactTile, t0 = tile * kCompactTile;
+    uint32_t lo = off[tile];
+    if (r > t0) {
+        const uint32_t base = tile_base[tile];
+        if (base == kTileAsIs) lo += (uint32_t)(r - t0);
+        else if (r >= n) lo = off[tile + 1];
+        else {
+            const uint32_t want = rec[r].x - base;
+            uint32_t hi = off[tile + 1];
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if ((((cstream[mid] >> 16) - base) & 0xffffu) < want) lo = mid + 1; else hi = mid;
+            }
+        }
+    }
+    clin[g] = lo;
 }
 
 } // namespace pcstage

@@ -172,6 +172,11 @@ class Engine(object):
         """Records staged for file `file_index`."""
         return int(self._lib.pc_num_records(self._h, int(file_index)))
 
+    def stream_entries(self, file_index):
+        """Entries the point rules stream for file `file_index` (``pc_stream_entries``): duplicate reads are
+        staged as one entry with a multiplicity; equal to ``num_records`` when the file keeps no compact stream."""
+        return int(self._lib.pc_stream_entries(self._h, int(file_index)))
+
     def read_records(self, file_index, indices):
         """Read objects' worth of data for records of a staged file (``pc_read_records`` + ``pc_read_record_runs``):
         dict of arrays ``tid, pos, alen, reverse, nblk, flag16, mapq`` plus ``run_off`` (n + 1), ``run_start``,
