@@ -74,6 +74,12 @@ int fail(int code, const char *fmt, ...) {
                         #expr, hipGetErrorString(err__), __FILE__, __LINE__);                      \
     } while (0)
 
+#define PC_TRY(expr)                                                                               \
+    do {                                                                                           \
+        const int rc__ = (expr);                                                                   \
+        if (rc__ != PC_OK) return rc__;                                                            \
+    } while (0)
+
 // Device blocks that outlive their engine: an engine that goes away hands the idle blocks of its pool to this
 // process-wide reservoir (per device, by size) instead of freeing them, and the pool of a later engine looks here
 // before it allocates.  Engines come and go -- one per BAMGenomeArray, one per config in bench.py -- and on some
@@ -294,8 +300,7 @@ template <typename T> struct DevBuf {
         return PC_OK;
     }
     int upload(const T *src, size_t n, hipStream_t s) {
-        int rc = reserve(n);
-        if (rc != PC_OK) return rc;
+        PC_TRY(reserve(n));
         if (n) HIP_TRY(hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
         return PC_OK;
     }
@@ -581,9 +586,9 @@ struct Knobs {
     int center_t1 = 8;         // PC_CENTER_T1 / PC_CENTER_T2: center chunks with more than T1 x (T1*T2 x) the mean candidate
     int center_t2 = 4;         //   count are cut into 4 (8) sub-chunks
     int64_t center_floor = 32768; // PC_CENTER_FLOOR: stream entries below which a chunk is never cut (a wave alone replays ~50 k per ms)
-    int center_lds = 0;        // PC_CENTER_LDS: bytes of (unused) LDS per k_center workgroup -- an occupancy throttle for experiments
+    int center_lds = 0;        // PC_CENTER_LDS: bytes of (unused) LDS per k_center2 workgroup -- an occupancy throttle for experiments
     int center_per_wave = 0;   // (reserved)
-    int center_debug = 0;      // PC_CENTER_DEBUG: wall-clock span of every dispatched wave of k_center, printed after the launch (synchronises)
+    int center_debug = 0;      // PC_CENTER_DEBUG: wall-clock span of every dispatched wave of k_center2, printed after the launch (synchronises)
     void load() {
         *this = Knobs();
         if (const char *env = getenv("PC_TILE_G")) tile_g = std::max(256, atoi(env) / 256 * 256);
@@ -679,26 +684,15 @@ struct pc_engine {
         mp.table_len = table_len; mp.fw = d_fw.p; mp.rc = d_rc.p;
         return mp;
     }
-    int W() const {
+    int max_over_files(int StagedFile::*field) const {
         int w = 1;
-        for (auto *f : files) w = std::max(w, f->W);
+        for (auto *f : files) w = std::max(w, f->*field);
         return w;
     }
-    int Wg() const {   // halo of the gapped-record list
-        int w = 1;
-        for (auto *f : files) w = std::max(w, f->Wg);
-        return w;
-    }
-    int Wr() const {   // halo of the run stream: its longest run
-        int w = 1;
-        for (auto *f : files) w = std::max(w, f->Wr);
-        return w;
-    }
-    int Ws() const {   // halo of the 4-byte record stream: the longest aligned length it carries
-        int w = 1;
-        for (auto *f : files) w = std::max(w, f->slen_max);
-        return w;
-    }
+    int W() const { return max_over_files(&StagedFile::W); }
+    int Wg() const { return max_over_files(&StagedFile::Wg); }        // halo of the gapped-record list
+    int Wr() const { return max_over_files(&StagedFile::Wr); }        // halo of the run stream: its longest run
+    int Ws() const { return max_over_files(&StagedFile::slen_max); }  // halo of the 4-byte record stream: the longest aligned length it carries
 };
 
 struct pc_plan {
@@ -750,10 +744,9 @@ struct pc_plan {
     DevBuf<CenterSlot> d_cslots; // one descriptor per dispatch entry (plans over one alignment file: k_center2)
     // the center pre-passes (ranges, candidate counts, dispatch order) depend on the plan, the staged files and the
     // knobs only -- not on the mapping rule: kept from count to count while the engine's work generation stands
-    uint64_t center_generation = 0;
+    uint64_t center_generation = 0;        // (0: no dispatch list yet -- the engine's work_generation starts at 1)
     int center_W = -1;
-    bool center_slots = false;             // the dispatch list has been resolved into descriptors (d_cslots)
-    int center_nfiles = 0;                 // ... for this many alignment files (one descriptor per entry and file)
+    int center_nfiles = 0;                 // alignment files the dispatch list was resolved into descriptors for (d_cslots: one per entry and file)
     uint32_t *h_center_counts = nullptr;   // page-locked [2]: heavy, light entries of the list (sizes the grids of later counts)
     hipEvent_t ev_center_counts = nullptr;
     bool center_counts_known = false;
@@ -830,8 +823,7 @@ int refresh_file_views(pc_engine *e) {
     if (!e->files_dirty) return PC_OK;
     std::vector<FileView> v;
     for (auto *f : e->files) v.push_back(f->view());
-    int rc = e->d_files.upload(v, e->stream);
-    if (rc != PC_OK) return rc;
+    PC_TRY(e->d_files.upload(v, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->files_dirty = false;
     return PC_OK;
@@ -942,8 +934,7 @@ int plan_build_gpu(pc_engine *e, pc_plan *p, int64_t nseg, const int32_t *tid, c
         npieces = A.take<uint32_t>(n + 1); piece_at = A.take<uint32_t>(n + 1); nout = A.take<uint32_t>(n + 1); out_at = A.take<uint32_t>(n + 1);
         cub_tmp = A.take<uint8_t>(cub_a + 256);
         if (pass == 0) {
-            rc = e->plan_scratch[0].reserve(A.used + 256);
-            if (rc != PC_OK) return rc;
+            PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
             A.base = e->plan_scratch[0].p;
         }
     }
@@ -1074,8 +1065,7 @@ int plan_build_gpu(pc_engine *e, pc_plan *p, int64_t nseg, const int32_t *tid, c
     const size_t hist_full = (size_t)p->npos * (size_t)p->rows * sizeof(double);
     const bool hist_here = hist_full > 0 && hist_full <= 64 * 1024;
     const size_t at_hist = hist_here ? place(hist_full) : 0;
-    rc = p->d_tables.reserve(bytes);
-    if (rc != PC_OK) return rc;
+    PC_TRY(p->d_tables.reserve(bytes));
     uint8_t *d = p->d_tables.p;
     if (n_tiles) HIP_TRY(hipMemcpyAsync(d + at_tiles, tiles_tmp, n_tiles * sizeof(Tile), hipMemcpyDeviceToDevice, st));
     if (n_pieces) HIP_TRY(hipMemcpyAsync(d + at_pieces, psorted, n_pieces * sizeof(Piece), hipMemcpyDeviceToDevice, st));
@@ -1115,8 +1105,7 @@ int ensure_center_tables(pc_engine *e, pc_plan *p) {
             A.used = 0;
             cnt = A.take<uint32_t>(ntl + 1); at = A.take<uint32_t>(ntl + 1); tmp = A.take<uint8_t>(tb + 256);
             if (pass == 0) {
-                const int rc0 = e->plan_scratch[0].reserve(A.used + 256);
-                if (rc0 != PC_OK) return rc0;
+                PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
                 A.base = e->plan_scratch[0].p;
             }
         }
@@ -1128,13 +1117,11 @@ int ensure_center_tables(pc_engine *e, pc_plan *p) {
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, at, (int)ntl + 1, st));
             HIP_TRY(hipMemcpyAsync(&total, at + ntl, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            const int rc1 = p->d_tables2.reserve(std::max<size_t>((size_t)total * sizeof(CenterChunk), 256));
-            if (rc1 != PC_OK) return rc1;
+            PC_TRY(p->d_tables2.reserve(std::max<size_t>((size_t)total * sizeof(CenterChunk), 256)));
             if (total) hipLaunchKernelGGL(k_cchunk_fill, dim3(g), dim3(256), 0, st, p->d_tiles.p, p->d_pieces.p, (uint32_t)ntl, at, (CenterChunk *)p->d_tables2.p);
             HIP_TRY(hipGetLastError());
         } else {
-            const int rc1 = p->d_tables2.reserve(256);
-            if (rc1 != PC_OK) return rc1;
+            PC_TRY(p->d_tables2.reserve(256));
         }
         p->d_cchunks.p = (CenterChunk *)p->d_tables2.p;
         p->n_cchunks = total;
@@ -1166,8 +1153,7 @@ int ensure_center_tables(pc_engine *e, pc_plan *p) {
             }
         }
     });
-    int rc = p->d_tables2.reserve(std::max<size_t>(p->cchunks.size() * sizeof(CenterChunk), 256));
-    if (rc != PC_OK) return rc;
+    PC_TRY(p->d_tables2.reserve(std::max<size_t>(p->cchunks.size() * sizeof(CenterChunk), 256)));
     if (!p->cchunks.empty()) HIP_TRY(hipMemcpyAsync(p->d_tables2.p, p->cchunks.data(), p->cchunks.size() * sizeof(CenterChunk), hipMemcpyHostToDevice, e->stream));
     p->d_cchunks.p = (CenterChunk *)p->d_tables2.p;
     p->n_cchunks = p->cchunks.size();
@@ -1190,8 +1176,7 @@ int ensure_gather_tables(pc_engine *e, pc_plan *p) {
             A.used = 0;
             cnt = A.take<uint32_t>(n + 1); at = A.take<uint32_t>(n + 1); tmp = A.take<uint8_t>(tb + 256);
             if (pass == 0) {
-                const int rc0 = e->plan_scratch[0].reserve(A.used + 256);
-                if (rc0 != PC_OK) return rc0;
+                PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
                 A.base = e->plan_scratch[0].p;
             }
         }
@@ -1202,8 +1187,7 @@ int ensure_gather_tables(pc_engine *e, pc_plan *p) {
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, at, (int)n + 1, st));
         HIP_TRY(hipMemcpyAsync(&total, at + n, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        const int rc1 = p->d_tables3.reserve(std::max<size_t>((size_t)total * sizeof(GatherChunk), 256));
-        if (rc1 != PC_OK) return rc1;
+        PC_TRY(p->d_tables3.reserve(std::max<size_t>((size_t)total * sizeof(GatherChunk), 256)));
         if (total) hipLaunchKernelGGL(k_gchunk_fill, dim3(g), dim3(256), 0, st, p->nseg, cnt, at, (GatherChunk *)p->d_tables3.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));   // (the scratch block may be reused by the next builder call)
@@ -1224,8 +1208,7 @@ int ensure_gather_tables(pc_engine *e, pc_plan *p) {
     size_t bytes = 0;
     auto place = [&bytes](size_t n) { const size_t a = bytes; bytes += (n + 255) & ~(size_t)255; return a; };
     const size_t at_s = place(p->gsegs.size() * sizeof(GatherSeg)), at_g = place(p->gchunks.size() * sizeof(GatherChunk));
-    int rc = p->d_tables3.reserve(std::max<size_t>(bytes, 256));
-    if (rc != PC_OK) return rc;
+    PC_TRY(p->d_tables3.reserve(std::max<size_t>(bytes, 256)));
     uint8_t *d = p->d_tables3.p;
     if (!p->gsegs.empty()) HIP_TRY(hipMemcpyAsync(d + at_s, p->gsegs.data(), p->gsegs.size() * sizeof(GatherSeg), hipMemcpyHostToDevice, e->stream));
     if (!p->gchunks.empty()) HIP_TRY(hipMemcpyAsync(d + at_g, p->gchunks.data(), p->gchunks.size() * sizeof(GatherChunk), hipMemcpyHostToDevice, e->stream));
@@ -1245,24 +1228,20 @@ int build_center_stream(pc_engine *e, StagedFile *sf, int sel, int nib) {
     if (n + sf->nrun >= (int64_t)0xffffffffu)
         return fail(PC_ERR_ARG, "pc_count: the center rule takes at most 2^32-2 aligned runs per file (%lld records, %lld runs of multi-run reads); split the file",
                     (long long)n, (long long)sf->nrun);
-    int rc = PC_OK;
     if (sf->cs_n[sel] < 0) {   // entries per record and their exclusive sum: independent of the nibble
-        rc = sf->cs_soff[sel].reserve((size_t)n + 1);
-        if (rc != PC_OK) return rc;
+        PC_TRY(sf->cs_soff[sel].reserve((size_t)n + 1));
         hipLaunchKernelGGL(k_cs_count, dim3((unsigned)((n + 1 + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->rec.p, n, sel, sf->cs_soff[sel].p);
         {
             size_t tmp_bytes = 0;
             DevBuf<uint8_t> d_tmp;
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, sf->cs_soff[sel].p, sf->cs_soff[sel].p, (int)(n + 1), st));
-            rc = d_tmp.reserve(tmp_bytes);
-            if (rc != PC_OK) return rc;
+            PC_TRY(d_tmp.reserve(tmp_bytes));
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, sf->cs_soff[sel].p, sf->cs_soff[sel].p, (int)(n + 1), st));
             HIP_TRY(hipStreamSynchronize(st));   // d_tmp goes out of scope
         }
         uint32_t total = 0;
         HIP_TRY(hipMemcpy(&total, sf->cs_soff[sel].p + n, sizeof(total), hipMemcpyDeviceToHost));
-        rc = sf->cs_ent[sel].reserve((size_t)total + 64);
-        if (rc != PC_OK) return rc;
+        PC_TRY(sf->cs_ent[sel].reserve((size_t)total + 64));
         sf->cs_n[sel] = (int64_t)total;
         e->files_dirty = true;
     }
@@ -1319,8 +1298,7 @@ int settle_streams(pc_engine *e) {
     if (e->knobs.no_stream_probe) return PC_OK;
     DevBuf<uint32_t> flag;
     flag.pool = &e->pool;
-    int rc = flag.reserve(2);
-    if (rc != PC_OK) return rc;
+    PC_TRY(flag.reserve(2));
     auto settle = [&](hipStream_t &cand, std::initializer_list<hipStream_t> beside) -> int {
         for (int attempt = 0;; ++attempt) {
             int ok = 1;
@@ -1336,7 +1314,7 @@ int settle_streams(pc_engine *e) {
             cand = fresh;
         }
     };
-    rc = settle(e->side_stream, {e->stream});
+    int rc = settle(e->side_stream, {e->stream});
     if (rc == PC_OK) rc = settle(e->aux_stream[0], {e->stream, e->side_stream});
     return rc;
 }
@@ -1850,8 +1828,7 @@ static int stage_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid,
     }
     // the aligned runs as {start, length} pairs
     if (nrun > 0) {
-        rc = sf->blk.reserve((size_t)nrun);
-        if (rc != PC_OK) return rc;
+        PC_TRY(sf->blk.reserve((size_t)nrun));
         hipLaunchKernelGGL(k_zip_runs, dim3((unsigned)((nrun + kWG - 1) / kWG)), dim3(kWG), 0, e->stream, dev->blk_start, dev->blk_len, nrun, sf->blk.p);
     }
     if (nrun == 0) sf->blk_off.release();   // (all zero: no record keeps runs in the run arrays)
@@ -2034,8 +2011,7 @@ static int stage_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid,
     if (rc != PC_OK) return rc;
     clk.lap("run stream (GPU sort)");
     sf->nlin = nlin;
-    rc = build_compact_stream(e, sf, ntid);
-    if (rc != PC_OK) return rc;
+    PC_TRY(build_compact_stream(e, sf, ntid));
     clk.lap("compact stream (GPU)");
     owner.p = nullptr;
     e->files.push_back(sf);
@@ -2073,8 +2049,7 @@ static int build_compact_stream(pc_engine *e, StagedFile *sf, int ntid) {
     if (rc != PC_OK) return rc;
     size_t tb = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt.p, d_off.p, (int)ntiles + 1, st));
-    rc = d_scan.reserve(std::max<size_t>(tb, 16));
-    if (rc != PC_OK) return rc;
+    PC_TRY(d_scan.reserve(std::max<size_t>(tb, 16)));
     HIP_TRY(hipMemsetAsync(d_cnt.p + ntiles, 0, 4, st));
     hipLaunchKernelGGL(k_compact_tiles, dim3(ntiles), dim3(256), 0, st, sf->rec.p, sf->stream.p, n, sf->tid_bounds.p, ntid, d_words.p, d_cnt.p, d_base.p);
     hipError_t he = hipcub::DeviceScan::ExclusiveSum(d_scan.p, tb, d_cnt.p, d_off.p, (int)ntiles + 1, st);
@@ -2124,8 +2099,7 @@ int pc_update_flags(pc_engine *e, int file, int64_t n, const uint8_t *flags) {
     HIP_TRY(hipSetDevice(e->device));
     if (n == 0) return PC_OK;
     // the flags go up (1 byte per record); every staged copy of the headers is patched in HBM
-    int rc = e->d_flags.reserve((size_t)n);
-    if (rc != PC_OK) return rc;
+    PC_TRY(e->d_flags.reserve((size_t)n));
     hipStream_t st = e->stream;
     HIP_TRY(hipMemcpyAsync(e->d_flags.p, flags, (size_t)n, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_update_flags, dim3((unsigned)((n + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->rec.p, sf->stream.p,
@@ -2163,7 +2137,7 @@ static int propagate_record_flags(pc_engine *e, StagedFile *sf) {
         hipLaunchKernelGGL(k_update_run_flags, dim3((unsigned)((sf->nrunrec + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->run_rec.p,
                            sf->run_recidx.p, sf->nrunrec, sf->rec.p);
     HIP_TRY(hipGetLastError());
-    { const int crc = build_compact_stream(e, sf, e->ntid); if (crc != PC_OK) return crc; }   // (the stream words have been rewritten)
+    PC_TRY(build_compact_stream(e, sf, e->ntid));   // (the stream words have been rewritten)
     for (int k = 0; k < 3; ++k) sf->cs_n[k] = -1;   // the center streams leave excluded reads out: rebuilt at the next center count
     e->files_dirty = true;
     e->work_generation += 1;
@@ -2198,8 +2172,7 @@ static int sync_flag_filter(pc_engine *e) {
     for (StagedFile *sf : e->files) {
         if (sf->n == 0 || !columns_present(e, sf)) continue;
         if (sf->applied_valid && sf->applied == want) continue;
-        const int rc = apply_flag_filter(e, sf);
-        if (rc != PC_OK) return rc;
+        PC_TRY(apply_flag_filter(e, sf));
     }
     return PC_OK;
 }
@@ -2231,8 +2204,7 @@ int pc_set_alignment_nh(pc_engine *e, int file, int64_t n, const uint16_t *nh) {
     HIP_TRY(hipSetDevice(e->device));
     if (n > 0) {
         PoolScope pool_scope(&e->pool);
-        const int rc = sf->sam_nh.reserve((size_t)n);
-        if (rc != PC_OK) return rc;
+        PC_TRY(sf->sam_nh.reserve((size_t)n));
         HIP_TRY(hipMemcpyAsync(sf->sam_nh.p, nh, (size_t)n * 2, hipMemcpyHostToDevice, e->stream));
     }
     sf->have_nh = true;
@@ -2832,488 +2804,568 @@ int pc_plan_table(pc_plan *p, int which, void *buf, int64_t cap_bytes, int64_t *
     return PC_OK;
 }
 
-int pc_count(pc_engine *e, pc_plan *p, int out_dtype) {
+} // extern "C"
+
+namespace {
+
+// ---- run-time values turned into template arguments: `launch` is a generic lambda; it receives the std::integral_constant
+// of the one of Vs that equals v and launches the instantiation it names
+template <int... Vs, class F>
+void dispatch_int(int v, F &&launch) {
+    (void)((v == Vs ? (launch(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// (mapping rule, output mode: 0 int64, 1 float64, 2 normalised float64) -> (KIND, OUTMODE) of k_hist_point.  The one-window
+// callers (a plan of one window, pc_query_segment) never run under the stratified rule: they pass STRAT = false and its
+// kernels are not instantiated.
+template <bool STRAT, class F>
+void dispatch_hist(int kind, int outmode, F &&launch) {
+    const int k = kind == PC_MAP_FIVE ? 0 : kind == PC_MAP_THREE ? 1 : (STRAT && kind == PC_MAP_STRAT5) ? 4 : 3;
+    dispatch_int<0, 1, 2>(outmode, [&](auto O) {
+        if constexpr (STRAT) dispatch_int<0, 1, 3, 4>(k, [&](auto K) { launch(K, O); });
+        else dispatch_int<0, 1, 3>(k, [&](auto K) { launch(K, O); });
+    });
+}
+
+// ---- the dynamic LDS of k_hist_point behind its bins: the offset table of the aligned lengths that occur in the data
+// (the variable rules; longer reads look the tables up in HBM), the output pieces parked in LDS, the entry table of the
+// record stream (the aligned lengths the stream carries) and one dump word per lane.  The caller adds its bin words --
+// max_slots x rows x window, halved for 16-bit bins -- and multiplies by four.
+struct HistLds {
+    int tab_lo = 0, tab_n = 0, fast_lo = 0, fast_hi = 0;
+    size_t table_words = 0;
+};
+
+HistLds hist_lds_shape(const pc_engine *e) {
+    HistLds s;
+    int lmin = 65536, lmax = -1;
+    s.fast_lo = kStreamMaxLen;
+    for (auto *f : e->files) {
+        lmin = std::min(lmin, f->len_min); lmax = std::max(lmax, f->len_max);
+        s.fast_lo = std::min(s.fast_lo, f->tlen_min); s.fast_hi = std::max(s.fast_hi, f->tlen_max);
+    }
+    if ((e->kind == PC_MAP_VAR5 || e->kind == PC_MAP_STRAT5) && lmax >= lmin) {
+        s.tab_lo = lmin;
+        s.tab_n = std::max(0, std::min(std::min(lmax, e->table_len - 1) - lmin + 1, 1024));
+    }
+    s.fast_lo = std::min(s.fast_lo, s.fast_hi);
+    const size_t stage_words = (size_t)kOpStage * sizeof(OutPiece) / sizeof(uint32_t);
+    s.table_words = (size_t)((s.tab_n + 3) & ~3) + stage_words + (size_t)(s.fast_hi + 1) * kModes + 64;
+    return s;
+}
+
+// ---- pc_count, phase by phase.  The phases enqueue on e->stream (the sparse-window class on e->side_stream) in the
+// order they are called and record the events pc_last_timing reads: ev[0] in front of the output memset, ev[1] behind
+// the memsets, ev[2] in front of the first k_hist_point (behind the work lists) or of the center kernels, ev[3] and
+// ev[4] behind the join, ev[5] behind k_gather_split.  A plan without windows records all of them as well.
+struct CountCall {   // what the phases of one call share beside the engine and the plan
+    int out_dtype;
+    int outmode;           // OUTMODE of the kernels that write the output
+    int nfiles, ntiles;
+    int64_t nrec, nextra;  // records and extra runs of all files
+    size_t hist_bytes;     // the compact histogram (uint32 per island position and row): what merged windows of the point rules go through; the center rule does not use it
+    MapParams mp;
+};
+
+int mark(pc_engine *e, int k) {   // ev[1] and ev[4] from profiling level 2, the others from level 1
+    if (e->prof_level >= ((k == 1 || k == 4) ? 2 : 1)) HIP_TRY(hipEventRecord(e->ev[k], e->stream));
+    return PC_OK;
+}
+
+int count_validate(pc_engine *e, pc_plan *p, int out_dtype) {   // (no HIP call)
     if (!e || !p || p->e != e) return fail(PC_ERR_ARG, "pc_count: bad engine/plan");
     if (!e->have_map) return fail(PC_ERR_STATE, "pc_count: no mapping rule set (pc_set_mapping)");
     if (e->files.empty()) return fail(PC_ERR_STATE, "pc_count: no alignments staged (pc_add_alignment_file)");
     if (out_dtype != PC_OUT_INT64 && out_dtype != PC_OUT_FLOAT64) return fail(PC_ERR_ARG, "pc_count: bad out_dtype");
     if (p->rows != e->rows) return fail(PC_ERR_ARG, "pc_count: plan built for %d rows, mapping rule has %d", p->rows, e->rows);
-    { const int frc = check_filter_columns(e, "pc_count"); if (frc != PC_OK) return frc; }
-    const bool center = e->kind == PC_MAP_CENTER;
-    if ((center || e->norm_on) && out_dtype != PC_OUT_FLOAT64)
+    PC_TRY(check_filter_columns(e, "pc_count"));
+    const bool float_only = e->kind == PC_MAP_CENTER || e->norm_on;
+    if (float_only && out_dtype != PC_OUT_FLOAT64)
         return fail(PC_ERR_ARG, "pc_count: center mapping / normalisation produce float64 (map_factories.pyx:230, genome_array.py:826-827)");
-    HIP_TRY(hipSetDevice(e->device));
-    int rc = PC_OK;
+    if (p->has_sums && float_only)
+        return fail(PC_ERR_ARG, "pc_count: summed slices (out_step 0) need an integer mapping rule without normalisation");
+    return PC_OK;
+}
+
+int count_prepare(pc_engine *e, pc_plan *p) {
+    const bool center = e->kind == PC_MAP_CENTER;
     if (center) {   // the center-only tables of a large plan; the center streams of the strand selections it queries
-        rc = ensure_center_tables(e, p);
-        if (rc != PC_OK) return rc;
+        PC_TRY(ensure_center_tables(e, p));
         const bool need[3] = {(p->modes & 1u) != 0, (p->modes & 2u) != 0, (p->modes & 12u) != 0};
         for (auto *f : e->files)
-            for (int k = 0; k < 3 && rc == PC_OK; ++k)
-                if (need[k]) rc = build_center_stream(e, f, k, e->param);   // (no-op when built for this nibble)
-        if (rc != PC_OK) return rc;
+            for (int k = 0; k < 3; ++k)
+                if (need[k]) PC_TRY(build_center_stream(e, f, k, e->param));   // (no-op when built for this nibble)
     }
-    rc = refresh_file_views(e);
-    if (rc != PC_OK) return rc;
-
-    // the compact histogram (uint32 per island position and row): what merged windows of the point rules go through;
-    // the center rule does not use it
-    const size_t hist_bytes = center ? 0 : (size_t)p->npos * p->rows * sizeof(uint32_t);
+    PC_TRY(refresh_file_views(e));
     if (!center && !p->d_hist.p) {
-        rc = p->d_hist_own.reserve(std::max<size_t>((size_t)p->npos * p->rows * sizeof(uint32_t), 8));
+        const int rc = p->d_hist_own.reserve(std::max<size_t>((size_t)p->npos * p->rows * sizeof(uint32_t), 8));
         p->d_hist.p = p->d_hist_own.p;
+        PC_TRY(rc);
     }
-    if (rc == PC_OK) rc = p->d_out.reserve(std::max<size_t>((size_t)p->out_elems * 8, 8));
-    if (rc != PC_OK) return rc;
+    return p->d_out.reserve(std::max<size_t>((size_t)p->out_elems * 8, 8));
+}
 
-    const int nfiles = (int)e->files.size();
-    const int W = e->W();
-    const int G = p->G;
-    const int64_t R = e->knobs.work_r;                             // records per work item
-    const int64_t pile = e->knobs.pile ? e->knobs.pile : 12 * R;   // a 128-nt sub-window with more records than this is merged through the histogram
-    const MapParams mp = e->params();
-    const int ntiles = (int)p->n_tiles;
-    hipStream_t st = e->stream;
-    int64_t nrec = 0, nextra = 0;
-    for (auto *f : e->files) { nrec += f->n; nextra += f->nrun; }
-
-    if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[0], st));
+int count_clear(pc_engine *e, pc_plan *p, const CountCall &c) {
+    const bool center = e->kind == PC_MAP_CENTER;
+    PC_TRY(mark(e, 0));
     // Outputs are written exactly once by the tile kernels.  Only positions that belong to no
     // tile (unknown contig, clipped coordinates) or gaps the caller left between slices need a
     // zero fill; the compact histogram of the point rules is kept all-zero between calls.
-    if (p->has_sums && (center || e->norm_on))
-        return fail(PC_ERR_ARG, "pc_count: summed slices (out_step 0) need an integer mapping rule without normalisation");
     if ((p->has_sums || p->out_needs_zero || p->covered != p->out_elems) && p->out_elems)
-        HIP_TRY(hipMemsetAsync(p->d_out.p, 0, (size_t)p->out_elems * 8, st));
+        HIP_TRY(hipMemsetAsync(p->d_out.p, 0, (size_t)p->out_elems * 8, e->stream));
     // (a large histogram is not cleared as a whole: k_clear_split zeroes the slices of the merged windows behind every
     // k_tile_ranges, which is all that is ever read of it)
     // `hist_clean` says that the WHOLE histogram is zero: true once it has been cleared as a whole, and kept by every
     // count (k_clear_split only zeroes, k_gather_split zeroes what it merged).  Lazy counts never make it true, so the
     // first count after the knobs turn lazy off (pc_reload_knobs) clears what the lazy ones left alone.
-    p->hist_lazy = !center && (int64_t)hist_bytes >= e->knobs.hist_lazy_bytes && !e->knobs.hist_memset;
-    if (!center && hist_bytes && !p->hist_clean && !p->hist_lazy) {
-        HIP_TRY(hipMemsetAsync(p->d_hist.p, 0, hist_bytes, st));
+    p->hist_lazy = !center && (int64_t)c.hist_bytes >= e->knobs.hist_lazy_bytes && !e->knobs.hist_memset;
+    if (!center && c.hist_bytes && !p->hist_clean && !p->hist_lazy) {
+        HIP_TRY(hipMemsetAsync(p->d_hist.p, 0, c.hist_bytes, e->stream));
         p->hist_clean = true;
     }
-    if (e->prof_level >= 2) HIP_TRY(hipEventRecord(e->ev[1], st));
+    return mark(e, 1);
+}
 
-    if (!center) {
-        // (k_gather_split clears what the split tiles merged: a histogram that was all zero stays so)
-        // ---- a plan of ONE window over one file (`ga[segment]`): the whole count is one launch -- the workgroup looks its
-        // record ranges up itself; no work list, no second window class, no merge pass, no events
-        // (not under the stratified rule: its 16-bit bins rely on the work lists, which cut or merge a window that scans
-        // more than 65 535 records)
-        const bool single = ntiles == 1 && nfiles == 1 && !e->knobs.debug_work && !e->knobs.no_single && e->kind != PC_MAP_STRAT5;
-        if (single) {
-            int lmin = 65536, lmax = -1;
-            for (auto *f : e->files) { lmin = std::min(lmin, f->len_min); lmax = std::max(lmax, f->len_max); }
-            int tab_lo = 0, tab_n = 0;
-            if ((e->kind == PC_MAP_VAR5 || e->kind == PC_MAP_STRAT5) && lmax >= lmin) {
-                tab_lo = lmin;
-                tab_n = std::max(0, std::min(std::min(lmax, e->table_len - 1) - lmin + 1, 1024));
-            }
-            int fast_lo = kStreamMaxLen, fast_hi = 0;
-            for (auto *f : e->files) { fast_lo = std::min(fast_lo, f->tlen_min); fast_hi = std::max(fast_hi, f->tlen_max); }
-            fast_lo = std::min(fast_lo, fast_hi);
-            const size_t stage_words = (size_t)kOpStage * sizeof(OutPiece) / sizeof(uint32_t);
-            const size_t lds = ((size_t)p->max_slots * p->rows * G + (size_t)((tab_n + 3) & ~3) + stage_words + (size_t)(fast_hi + 1) * kModes + 64) * sizeof(uint32_t);
-            if (lds > e->max_lds)
-                return fail(PC_ERR_ARG, "pc_count: the window needs %zu bytes of LDS, the device offers %zu per workgroup (too many rows)", lds, e->max_lds);
-            const FileView fv0 = e->files[0]->view();
-            const int outmode = e->norm_on ? 2 : (out_dtype == PC_OUT_FLOAT64 ? 1 : 0);
-            if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[2], st));
-#define PC_LAUNCH_SINGLE(K, O)                                                                                        \
-    hipLaunchKernelGGL((k_hist_point<K, O, kHistWG, false, false, true>), dim3(1), dim3(kHistWG), lds, st, p->d_pieces.p, p->d_opieces.p, \
-                       fv0, fv0, e->d_files.p, (const WorkItem *)p->d_tiles.p, p->d_wcounters.p, p->d_tile_items.p, mp, G, p->max_slots,    \
-                       tab_lo, tab_n, fast_lo, fast_hi, (uint32_t *)p->d_hist.p, (int64_t)e->Ws(), (OutT_<O>::type *)p->d_out.p,           \
-                       e->norm_sum, (uint32_t)e->Wg(), (uint32_t)e->Wr(), (const FileRange *)nullptr, nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u)
-#define PC_LAUNCH_SINGLE_O(K)                                                                                         \
-    do {                                                                                                              \
-        if (outmode == 0) PC_LAUNCH_SINGLE(K, 0);                                                                     \
-        else if (outmode == 1) PC_LAUNCH_SINGLE(K, 1);                                                                \
-        else PC_LAUNCH_SINGLE(K, 2);                                                                                  \
-    } while (0)
-            switch (e->kind) {
-            case PC_MAP_FIVE: PC_LAUNCH_SINGLE_O(0); break;
-            case PC_MAP_THREE: PC_LAUNCH_SINGLE_O(1); break;
-            case PC_MAP_VAR5: PC_LAUNCH_SINGLE_O(3); break;
-            default: PC_LAUNCH_SINGLE_O(4); break;
-            }
-#undef PC_LAUNCH_SINGLE_O
-#undef PC_LAUNCH_SINGLE
-            if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[3], st));
-            if (e->prof_level >= 2) HIP_TRY(hipEventRecord(e->ev[4], st));
-        } else if (ntiles > 0) {
-            // work list capacity: every record lies in at most 1 + ceil(W/G) scan windows
-            // work-list capacity (an upper bound): a window scanning n records yields at most
-            // max(1, 2n/R) items, and every record is scanned by at most 1 + (W+127)/G windows
-            const int halo = std::max(std::max(W, e->Ws()), std::max(e->Wg(), e->Wr()));
-            // (a multi-row plan gives every strand mode of a window a tile of its own -- pc_plan_create, split_modes --
-            // so a record is scanned by up to popcount(modes) tiles per window)
-            const int tiles_per_window = p->rows > 1 ? std::max(1, __builtin_popcount(p->modes)) : 1;
-            const double windows_per_record = (1.0 + (double)(halo + 127) / (double)G) * (double)tiles_per_window;
-            int64_t cap64 = (int64_t)ntiles * nfiles + (int64_t)(2.0 * windows_per_record * (double)nrec / (double)R) + nfiles + 64;
-            if (e->kind == PC_MAP_STRAT5) {
-                // 16-bit bins: a window that scans more than 65 535 records, runs and list entries is merged, in slices of ONE
-                // kind of range each (k_tile_ranges): at most adds / R + 4 items per such window, and fewer than adds / 65 535 of them
-                int64_t nxl = 0, ngp = 0;
-                for (auto *f : e->files) { nxl += f->nxlong; ngp += f->ngap; }
-                cap64 += (int64_t)(6.0 * windows_per_record * (double)(nrec + nextra + ngp) / (double)R) +
-                         (int64_t)ntiles * nfiles * (4 + 2 * (nxl / R));
-            }
-            if (cap64 >= (int64_t)0xffffffffu) return fail(PC_ERR_ARG, "pc_count: work list too large");
-            rc = p->d_work.reserve((size_t)cap64);
-            if (rc != PC_OK) return rc;
-            // sparse windows: single-wave workgroups with a small LDS window (rows == 1 only)
-            // (skipped for dense annotations, where queried positions fill most of every window)
-            const bool sparse_plan = (double)p->npos < 0.25 * (double)ntiles * (double)G;
-            const int small_g = ((p->rows == 1 || e->knobs.small_rows) && sparse_plan && !e->knobs.no_small) ? std::min(e->knobs.small_g, G) : 0;
-            const int64_t small_n = e->knobs.small_n;
-            const int64_t cap_small = small_g ? (int64_t)ntiles * nfiles : 0;
-            rc = p->d_work_small.reserve((size_t)std::max<int64_t>(cap_small, 1));
-            if (rc == PC_OK && nfiles > 1) rc = p->d_chain.reserve((size_t)cap64 * (size_t)(nfiles - 1));
-            if (rc == PC_OK && nfiles > 1) rc = p->d_chain_small.reserve((size_t)std::max<int64_t>(cap_small, 1) * (size_t)(nfiles - 1));
-            if (rc != PC_OK) return rc;
-            pc_plan::WorkKey key;
-            key.generation = e->work_generation; key.nfiles = nfiles; key.G = G; key.Wg = e->Wg(); key.Ws = e->Ws(); key.Wr = e->Wr();
-            key.small_g = small_g; key.R = R; key.pile = pile; key.small_n = small_n; key.cap = cap64;
-            if (!(p->work_valid && p->work_key == key) || e->knobs.debug_work) {
-                // the lists of this plan are (re)built: counters and per-tile item counts start from zero (they arrive
-                // zeroed with the plan's tables, so the first count of a plan needs no memset)
-                if (!p->wcounters_zero) HIP_TRY(hipMemsetAsync(p->d_wcounters.p, 0, 8 * sizeof(uint32_t), st));
-                if (!p->tile_items_zero) HIP_TRY(hipMemsetAsync(p->d_tile_items.p, 0, ((size_t)ntiles + 1) * sizeof(uint32_t), st));
-                p->wcounters_zero = false;
-                p->tile_items_zero = false;
-                const int64_t nwin = nfiles > 1 ? (int64_t)ntiles : (int64_t)ntiles * nfiles; // one thread per window (several files: joint windows)
-                // ... or sixteen lanes per window while that still fits the chip at once: the exact record bounds of a window are
-                // then searched by the group (three rounds of sixteen probes instead of a dozen dependent loads each) -- a plan of
-                // a few thousand windows (C2: 6 144) otherwise runs on two dozen CUs at the pace of one thread's load chain
-                const bool group16 = nwin * 16 <= e->knobs.ranges_cg16_max && !e->knobs.ranges_cg1;
-                const int64_t nthreads = group16 ? nwin * 16 : nwin;
-#define PC_LAUNCH_RANGES(CG)                                                                                           \
-    hipLaunchKernelGGL((k_tile_ranges<CG>), dim3((unsigned)((nthreads + kRangesWG - 1) / kRangesWG)), dim3(kRangesWG), 0, st, p->d_tiles.p, ntiles, \
-                       e->files[0]->view(), e->d_files.p, nfiles, G, e->Wg(), e->Ws(), e->Wr(), R, pile, p->d_work.p, p->d_wcounters.p, p->d_tile_items.p, (uint32_t)cap64, \
-                       p->d_work_small.p, small_g, small_n, e->knobs.debug_work, p->d_chain.p, p->d_chain_small.p, e->kind == PC_MAP_STRAT5 ? 1 : 0)
-                if (group16) PC_LAUNCH_RANGES(16); else PC_LAUNCH_RANGES(1);
-#undef PC_LAUNCH_RANGES
-                if (p->hist_lazy)
-                    hipLaunchKernelGGL(k_clear_split, dim3((unsigned)((ntiles + kClearPerWG - 1) / kClearPerWG)), dim3(kWG), 0, st, p->d_tiles.p, ntiles,
-                                       p->d_pieces.p, p->d_tile_items.p, p->d_wcounters.p, p->rows, (uint32_t *)p->d_hist.p, (int64_t)p->npos);
-                p->work_key = key;
-                p->work_valid = true;
-                p->work_counts_known = false;      // the counts of the lists just replaced size no grid
-                p->guard_pending = true;           // k_gather_split checks the new lists against the capacity: read with the results
-                p->work_counts_generation = 0;
-                // The first count of a plan does not know how many items its lists hold, and used to launch the whole
-                // capacity: for a sparse annotation under a multi-row rule that is 3.6 M workgroups for 0.53 M items (C5:
-                // 3.88 ms against 3.24, and the merge pass on top).  Where the capacity is far above the window count, the
-                // queued counts are read back NOW -- one small copy and a stream synchronisation, ~20 us of idle GPU -- and
-                // this count already launches exact grids.
-                const int64_t spare = cap64 + cap_small - nwin;
-                if (ntiles >= 4096 && spare >= e->knobs.first_sync_spare && !e->knobs.test_stale_counts && !e->knobs.debug_work) {
-                    if (!p->h_work_counts) {
-                        HIP_TRY(hipHostMalloc((void **)&p->h_work_counts, 8 * sizeof(uint32_t), hipHostMallocDefault));
-                        HIP_TRY(hipEventCreateWithFlags(&p->ev_work_counts, hipEventDisableTiming));
-                    }
-                    HIP_TRY(hipMemcpyAsync(p->h_work_counts, p->d_wcounters.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipStreamSynchronize(st));
-                    for (int k = 0; k < 3; ++k) p->work_counts[k] = p->h_work_counts[k];
-                    p->work_merged = p->h_work_counts[4];
-                    p->work_counts_known = true;
-                    p->work_counts_generation = e->work_generation;
-                }
-            }
-            if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[2], st));
-            // offset tables are staged in LDS for the aligned lengths that occur in the data
-            int lmin = 65536, lmax = -1;
-            for (auto *f : e->files) { lmin = std::min(lmin, f->len_min); lmax = std::max(lmax, f->len_max); }
-            int tab_lo = 0, tab_n = 0;
-            if ((e->kind == PC_MAP_VAR5 || e->kind == PC_MAP_STRAT5) && lmax >= lmin) {
-                tab_lo = lmin;
-                tab_n = std::min(lmax, e->table_len - 1) - lmin + 1;
-                tab_n = std::max(0, std::min(tab_n, 1024)); // longer reads look the tables up in HBM
-            }
-            const size_t stage_words = (size_t)kOpStage * sizeof(OutPiece) / sizeof(uint32_t); // output pieces parked in LDS
-            const bool b16 = e->kind == PC_MAP_STRAT5;   // 16-bit bins, two positions per word (k_hist_point)
-            const size_t bins_words = (((size_t)p->max_slots * p->rows * G) >> (b16 ? 1 : 0)) + (size_t)((tab_n + 3) & ~3) + stage_words;
-            // LDS entry table of the record stream: the aligned lengths the stream carries
-            int fast_lo = kStreamMaxLen, fast_hi = 0;
-            for (auto *f : e->files) { fast_lo = std::min(fast_lo, f->tlen_min); fast_hi = std::max(fast_hi, f->tlen_max); }
-            fast_lo = std::min(fast_lo, fast_hi);
-            const size_t fwords = (size_t)(fast_hi + 1) * kModes + 64; // entry table + one dump word per lane (after the staged pieces)
-            const size_t lds = (bins_words + fwords) * sizeof(uint32_t);
-            if (lds > e->max_lds)
-                return fail(PC_ERR_ARG, "pc_count: the window needs %zu bytes of LDS, the device offers %zu per workgroup (too many rows)", lds, e->max_lds);
-            const FileView fv0 = e->files[0]->view();
-            const FileView fv1 = nfiles > 1 ? e->files[1]->view() : fv0;
-            // grids: the whole list capacity, or -- once a count of this plan has shown how many items each
-            // class queues (same alignments, same knobs) -- exactly those: a sparse annotation leaves most
-            // of the capacity empty, and an empty workgroup still costs a dispatch slot
-            unsigned grid = (unsigned)cap64, grid_front = (unsigned)cap64, grid_small = (unsigned)cap_small;
-            uint32_t launched[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};   // exact grids: what k_gather_split checks the queued counts against
-            const bool track_counts = ntiles >= 4096;
-            if (track_counts && p->work_counts_generation == e->work_generation && p->h_work_counts && !p->work_counts_known &&
-                hipEventQuery(p->ev_work_counts) == hipSuccess) {
-                for (int k = 0; k < 3; ++k) p->work_counts[k] = p->h_work_counts[k];
-                p->work_merged = p->h_work_counts[4];
-                p->work_counts_known = true;   // deterministic for this plan while the generation stands: no further read-backs
-            }
-            if (track_counts && p->work_counts_known && p->work_counts_generation == e->work_generation) {
-                const uint32_t nh = p->work_counts[0], nl = p->work_counts[1] - ((e->knobs.test_stale_counts && p->work_counts[1]) ? 1u : 0u), ns = p->work_counts[2];
-                if ((uint64_t)nh + nl <= (uint64_t)cap64 && (int64_t)ns <= cap_small) {
-                    grid_front = nh;
-                    grid = std::max(1u, nh + nl);
-                    grid_small = ns;
-                    launched[0] = nh; launched[1] = nl; launched[2] = ns;
-                    p->exact_grid_used = true;
-                }
-            }
-            const int outmode = e->norm_on ? 2 : (out_dtype == PC_OUT_FLOAT64 ? 1 : 0);
-#define PC_LAUNCH_HIST(K, O)                                                                                          \
-    do {                                                                                                              \
-        if (nfiles > 1) PC_LAUNCH_HIST_M(K, O, true); else PC_LAUNCH_HIST_M(K, O, false);                             \
-    } while (0)
-#define PC_LAUNCH_HIST_M(K, O, M)                                                                                     \
-    do {                                                                                                              \
-        hipLaunchKernelGGL((k_hist_point<K, O, kHistWG, false, M>), dim3(grid), dim3(kHistWG), lds, st, p->d_pieces.p,             \
-                           p->d_opieces.p, fv0, fv1, e->d_files.p, p->d_work.p, p->d_wcounters.p, p->d_tile_items.p, mp, \
-                           G, p->max_slots, tab_lo, tab_n, fast_lo, fast_hi, (uint32_t *)p->d_hist.p, p->npos,                        \
-                           (OutT_<O>::type *)p->d_out.p,                                                                \
-                           e->norm_sum, (uint32_t)cap64, grid_front, p->d_chain.p, nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u); \
-        if (cap_small && grid_small)                                                                                  \
-            hipLaunchKernelGGL((k_hist_point<K, O, 64, true, M>), dim3(grid_small), dim3(64), lds_small, st_small, \
-                               p->d_pieces.p, p->d_opieces.p, fv0, fv1, e->d_files.p, p->d_work_small.p,                \
-                               p->d_wcounters.p, p->d_tile_items.p, mp, small_g, p->max_slots, tab_lo, tab_n, fast_lo, fast_hi, \
-                               (uint32_t *)p->d_hist.p,                                                                 \
-                               p->npos, (OutT_<O>::type *)p->d_out.p, e->norm_sum, (uint32_t)cap_small, grid_small,      \
-                               p->d_chain_small.p, nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u);                  \
-    } while (0)
-#define PC_LAUNCH_HIST_O(K)                                                                                           \
-    do {                                                                                                              \
-        if (outmode == 0) PC_LAUNCH_HIST(K, 0);                                                                       \
-        else if (outmode == 1) PC_LAUNCH_HIST(K, 1);                                                                  \
-        else PC_LAUNCH_HIST(K, 2);                                                                                    \
-    } while (0)
-            const size_t lds_small = ((((size_t)p->max_slots * p->rows * std::max(small_g, 1)) >> (b16 ? 1 : 0)) + (size_t)((tab_n + 3) & ~3) + fwords + stage_words) * sizeof(uint32_t);
-            // sparse windows (single-wave workgroups) and dense ones are two independent launches over
-            // disjoint windows: they run side by side on two streams, forked after the work lists exist
-            // and joined before the last kernel of the call
-            hipStream_t st_small = st;
-            if (cap_small) {
-                st_small = e->side_stream;
-                HIP_TRY(hipEventRecord(e->ev_fork, st));
-                HIP_TRY(hipStreamWaitEvent(st_small, e->ev_fork, 0));
-            }
-            switch (e->kind) {
-            case PC_MAP_FIVE: PC_LAUNCH_HIST_O(0); break;
-            case PC_MAP_THREE: PC_LAUNCH_HIST_O(1); break;
-            case PC_MAP_VAR5: PC_LAUNCH_HIST_O(3); break;
-            default: PC_LAUNCH_HIST_O(4); break;
-            }
-#undef PC_LAUNCH_HIST_O
-#undef PC_LAUNCH_HIST
-#undef PC_LAUNCH_HIST_M
-            if (cap_small) {
-                HIP_TRY(hipEventRecord(e->ev_join, st_small));
-                HIP_TRY(hipStreamWaitEvent(st, e->ev_join, 0));
-            }
-            if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[3], st));
-            if (e->prof_level >= 2) HIP_TRY(hipEventRecord(e->ev[4], st));
-            // tiles that were split into several work items: lay out from the merged histogram
-            const int split_per_wg = kWG; // merged windows are the exception (pile-ups), with several files too (joint windows)
-#define PC_LAUNCH_SPLIT(O)                                                                                            \
-    hipLaunchKernelGGL((k_gather_split<O>), dim3((unsigned)((ntiles + split_per_wg - 1) / split_per_wg)), dim3(kWG), 0, st, \
-                       p->d_tiles.p, ntiles, split_per_wg, p->d_pieces.p,                                               \
-                       p->d_opieces.p, p->d_tile_items.p, p->d_wcounters.p, p->rows, (uint32_t *)p->d_hist.p, p->npos,   \
-                       (OutT_<O>::type *)p->d_out.p, e->norm_sum, launched[0], launched[1], launched[2], (uint32_t)cap64, e->d_counters.p + 12)
-            // (skipped once the plan's lists are known to hold no merged window: the lists are the plan's own and do not
-            // change from count to count, so neither does that -- and the exact grids it would check were read from them)
-            const bool nothing_to_merge = launched[0] != 0xffffffffu && p->work_merged == 0 && !e->knobs.test_stale_counts;
-            if (nothing_to_merge) {}
-            else if (outmode == 0) PC_LAUNCH_SPLIT(0);
-            else if (outmode == 1) PC_LAUNCH_SPLIT(1);
-            else PC_LAUNCH_SPLIT(2);
-#undef PC_LAUNCH_SPLIT
-            if (track_counts) {   // how many items each class queued (k_gather_split keeps a copy): sizes the next launch
-                if (!p->h_work_counts) {
-                    HIP_TRY(hipHostMalloc((void **)&p->h_work_counts, 8 * sizeof(uint32_t), hipHostMallocDefault));
-                    HIP_TRY(hipEventCreateWithFlags(&p->ev_work_counts, hipEventDisableTiming));
-                }
-                if (p->work_counts_generation != e->work_generation) {   // one read-back per (plan, generation)
-                    p->work_counts_known = false;
-                    HIP_TRY(hipMemcpyAsync(p->h_work_counts, p->d_wcounters.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipEventRecord(p->ev_work_counts, st));
-                    p->work_counts_generation = e->work_generation;
-                }
-            }
-            if (e->knobs.debug_work) { // diagnostics: how many work items of each class this call queued
-                uint32_t c4[4] = {0, 0, 0, 0};
-                HIP_TRY(hipMemcpyAsync(c4, p->d_wcounters.p, sizeof(c4), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                fprintf(stderr, "[work] tiles %d: heavy %u light %u small %u, long-span candidates %u (capacity %lld, G %d, R %lld)\n", ntiles,
-                        c4[0], c4[1], c4[2], c4[3], (long long)cap64, G, (long long)R);
-            }
-        } else {
-            if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[2], st));
-            if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[3], st));
-            if (e->prof_level >= 2) HIP_TRY(hipEventRecord(e->ev[4], st));
-        }
-    } else {
-        // (k_center writes every queried position of the tiles straight into the output layout; the compact histogram
-        // is not touched)
-        if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[2], st));
-        const int64_t nchunks = (int64_t)p->n_cchunks;
-        if (nchunks > 0) {
-            if (kCenterCap * nchunks >= (int64_t)1 << kSubShift) return fail(PC_ERR_ARG, "pc_count: too many positions for the center rule");
-            rc = p->d_corder.reserve((size_t)(kCenterCap * nchunks));   // dispatch list: heavy entries front, light back
-            if (rc == PC_OK) rc = p->d_ccand.reserve((size_t)nchunks);
-            if (rc == PC_OK) rc = p->d_cranges.reserve((size_t)nchunks * (size_t)nfiles);
-            if (rc == PC_OK) rc = p->d_crec.reserve((size_t)nchunks * (size_t)nfiles);
-            if (rc == PC_OK) rc = p->d_crows.reserve((size_t)nchunks * (size_t)nfiles * (size_t)(2 * kCenterRows));
-            if (rc == PC_OK) rc = p->d_ccounts.reserve(8);
-            if (rc == PC_OK) rc = e->d_cvalh.reserve(256);
-            // one alignment file (every BASELINE config): descriptors per dispatch entry, several entries per wave (k_center2);
-            // several files keep round 4's kernel, whose waves walk the files of a chunk one after the other
-            const bool slots_on = true;   // (round 6: descriptors for plans over several files too -- one per entry and file)
-            if (rc == PC_OK) rc = p->d_cslots.reserve((size_t)(2 * nchunks) * (size_t)nfiles);   // (heavy entries < chunks, light entries <= chunks)
-            if (rc != PC_OK) return rc;
-            hipLaunchKernelGGL(k_center_vals, dim3(1), dim3(256), 0, st, mp, e->d_invh.p, e->d_cvalh.p);
-            if (p->center_generation != e->work_generation || p->center_W != W || p->center_slots != slots_on || p->center_nfiles != nfiles) {
-                p->center_nfiles = nfiles;
-                HIP_TRY(hipMemsetAsync(p->d_ccounts.p, 0, 8 * sizeof(uint32_t), st));
-                unsigned long long *total = (unsigned long long *)(p->d_ccounts.p + 2);
-                const unsigned wgs = (unsigned)((nchunks + kRangesWG - 1) / kRangesWG);
-                hipLaunchKernelGGL(k_center_weigh, dim3(wgs), dim3(kRangesWG), 0, st, p->d_cchunks.p, nchunks, e->d_files.p, nfiles, W,
-                                   p->d_ccand.p, p->d_cranges.p, p->d_crec.p, p->d_crows.p, total);
-                // cut thresholds, in multiples of the mean candidate count
-                const int ck1 = e->knobs.center_t1, ck2 = e->knobs.center_t2;
-                hipLaunchKernelGGL(k_center_order, dim3(wgs), dim3(kRangesWG), 0, st, p->d_ccand.p, nchunks, total, e->knobs.center_floor,
-                                   (int64_t)2048, ck1, ck2, p->d_corder.p, p->d_ccounts.p);
-                hipLaunchKernelGGL(k_center_slots, dim3((unsigned)((2 * nchunks + kRangesWG - 1) / kRangesWG)), dim3(kRangesWG), 0, st, p->d_cchunks.p, nchunks,
-                                       e->d_files.p, nfiles, W, p->d_corder.p, p->d_ccounts.p, p->d_cranges.p, p->d_crec.p, p->d_crows.p, p->d_opieces.p,
-                                       p->d_cslots.p, (unsigned long long *)(p->d_ccounts.p + 4));
-                p->center_slots = slots_on;
-                p->center_generation = e->work_generation;
-                p->center_W = W;
-                // how many entries the list got: sizes the grid of the later counts of this plan (read back once)
-                if (!p->h_center_counts) {
-                    HIP_TRY(hipHostMalloc((void **)&p->h_center_counts, 2 * sizeof(uint32_t), hipHostMallocDefault));
-                    HIP_TRY(hipEventCreateWithFlags(&p->ev_center_counts, hipEventDisableTiming));
-                }
-                p->center_counts_known = false;
-                HIP_TRY(hipMemcpyAsync(p->h_center_counts, p->d_ccounts.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipEventRecord(p->ev_center_counts, st));
-            } else if (!p->center_counts_known && hipEventQuery(p->ev_center_counts) == hipSuccess) {
-                p->center_counts[0] = p->h_center_counts[0];
-                p->center_counts[1] = p->h_center_counts[1];
-                p->center_counts_known = true;
-            }
-            // PC_CENTER_DEBUG: how long every dispatched wave ran (wall clock ticks), printed after the launch
-            DevBuf<unsigned long long> d_dbg;
-            const bool dbg_on = e->knobs.center_debug != 0 || e->want_center_steps;
-            const size_t dbg_slots = (size_t)(kCenterCap * nchunks);   // heavy entries from the front, light ones from the back
-            if (dbg_on) {
-                rc = d_dbg.reserve(3 * dbg_slots);
-                if (rc != PC_OK) return rc;
-                HIP_TRY(hipMemsetAsync(d_dbg.p, 0, 3 * dbg_slots * 8, st));
-            }
-            unsigned long long *dbg = dbg_on ? d_dbg.p : nullptr;
-            // (files with reads beyond a stream entry's 8-bit fields, or a stream too long for 32-bit byte offsets, take the
-            // instantiation that tests every batch for them)
-            bool general = false;
-            for (auto *f : e->files) general |= f->len_max > 255 || f->n + f->nrun >= ((int64_t)1 << 28);
-            {
-                // descriptors: heavy entries one wave each, PC_CENTER_PER_WAVE light entries per wave (an eighth of the list per XCD)
-                Center2Ctx c2;
-                StagedFile *sf0 = e->files[0];
-                c2.slots = p->d_cslots.p;
-                c2.indirect = 0u;
-                for (int k = 0; k < 3; ++k) {
-                    c2.ent[k] = sf0->cs_n[k] >= 0 ? sf0->cs_ent[k].p : nullptr;
-                    if (sf0->len_max > 255) c2.indirect |= 1u << k;
-                }
-                c2.files = e->d_files.p; c2.nfiles = nfiles; c2.file0 = sf0->view(); c2.mp = mp; c2.W = W; c2.inv = e->d_inv.p; c2.invh = e->d_invh.p; c2.cvalh = e->d_cvalh.p;
-                c2.counters = p->d_ccounts.p;
-                c2.known = p->center_counts_known ? 1u : 0u; c2.n_heavy = p->center_counts[0]; c2.n_light = p->center_counts[1];
-                c2.opieces = p->d_opieces.p; c2.out = (double *)p->d_out.p; c2.norm_sum = e->norm_sum; c2.norm_on = e->norm_on ? 1 : 0;
-                c2.dbg = dbg; c2.dbg_cap = (uint32_t)dbg_slots;
-                uint64_t g2;
-                if (p->center_counts_known) {
-                    const uint64_t n8 = ((uint64_t)p->center_counts[1] + 7) >> 3;
-                    g2 = (uint64_t)p->center_counts[0] + 8 * ((n8 + PC_CENTER_PER_WAVE - 1) / PC_CENTER_PER_WAVE);
-                } else g2 = 2 * (uint64_t)nchunks + 8;
-                const dim3 cg2((unsigned)std::max<uint64_t>(g2, 1));
-                const bool multi = nfiles > 1;   // one descriptor per entry and file, replayed into the same sums in file order
-                {
-#define PC_LAUNCH_CENTER2(D, G, M) hipLaunchKernelGGL((k_center2<D, G, M>), cg2, dim3(64), (size_t)e->knobs.center_lds, st, c2)
-#define PC_LAUNCH_CENTER2_M(D, G) do { if (multi) PC_LAUNCH_CENTER2(D, G, true); else PC_LAUNCH_CENTER2(D, G, false); } while (0)
-                    if (dbg_on) { if (general) PC_LAUNCH_CENTER2_M(true, true); else PC_LAUNCH_CENTER2_M(true, false); }
-                    else { if (general) PC_LAUNCH_CENTER2_M(false, true); else PC_LAUNCH_CENTER2_M(false, false); }
-#undef PC_LAUNCH_CENTER2_M
-#undef PC_LAUNCH_CENTER2
-                }
-            }
-            if (dbg_on) {   // diagnostic launch: replay steps and dispatched waves, summed on the host; PC_CENTER_DEBUG prints them
-                std::vector<unsigned long long> h(2 * dbg_slots), h_slots(dbg_slots);
-                HIP_TRY(hipStreamSynchronize(st));
-                HIP_TRY(hipMemcpy(h.data(), d_dbg.p, h.size() * 8, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(h_slots.data(), d_dbg.p + h.size(), h_slots.size() * 8, hipMemcpyDeviceToHost));
-                e->center_steps = 0; e->center_waves = 0;
-                unsigned long long t0 = ~0ull, t1 = 0, sum = 0, steps_heavy = 0, steps_pers = 0, n_heavy_w = 0, n_pers_w = 0;
-                const size_t n_front = (size_t)nchunks;   // (heavy entries occupy the front of the list: fewer than the chunk count)
-                std::vector<std::pair<unsigned long long, size_t>> byd;
-                for (size_t i = 0; i < dbg_slots; ++i)
-                    if (h[2 * i]) {
-                        e->center_steps += (int64_t)h_slots[i]; e->center_waves += 1;
-                        const bool pers = i >= n_front;
-                        (pers ? steps_pers : steps_heavy) += h_slots[i];
-                        (pers ? n_pers_w : n_heavy_w) += 1;
-                        t0 = std::min(t0, h[2 * i + 1]); t1 = std::max(t1, h[2 * i + 1] + h[2 * i]);
-                        sum += h[2 * i];
-                        byd.emplace_back(h[2 * i], i);
-                    }
-                if (e->knobs.center_debug != 0) {
-                    fprintf(stderr, "[center] replay steps: %llu in %llu waves of the heavy entries, %llu in %llu waves of the light ones\n", steps_heavy, n_heavy_w,
-                            steps_pers, n_pers_w);
-                    fprintf(stderr, "[center] W %d: launch span %llu ticks (100 MHz: %.3f ms), summed wave time %llu ticks = %.1f x the span\n", W, t1 - t0,
-                            (t1 - t0) / 1e5, sum, (double)sum / (double)std::max<unsigned long long>(t1 - t0, 1));
-                    const int nb = 20;
-                    std::vector<double> occ(nb, 0.0);
-                    const double span = (double)std::max<unsigned long long>(t1 - t0, 1);
-                    for (size_t i = 0; i < dbg_slots; ++i)
-                        if (h[2 * i]) {
-                            const double a = (double)(h[2 * i + 1] - t0) / span * nb, b = (double)(h[2 * i + 1] + h[2 * i] - t0) / span * nb;
-                            for (int k = std::max(0, (int)a); k < nb && k < b; ++k) occ[(size_t)k] += std::min(b, k + 1.0) - std::max(a, (double)k);
-                        }
-                    fprintf(stderr, "[center] resident waves per twentieth of the launch:");
-                    for (int k = 0; k < nb; ++k) fprintf(stderr, " %.0f", occ[(size_t)k]);
-                    fprintf(stderr, "\n");
-                    std::sort(byd.rbegin(), byd.rend());
-                    for (size_t k = 0; k < std::min<size_t>(byd.size(), 8); ++k) {
-                        const size_t i = byd[k].second;
-                        fprintf(stderr, "[center]   slot %zu (%s): %.3f ms, started at %.3f ms, %llu steps\n", i,
-                                i >= n_front ? "light" : "heavy", byd[k].first / 1e5, (h[2 * i + 1] - t0) / 1e5, h_slots[i]);
-                    }
-                    if (!byd.empty()) {
-                        const size_t i = byd.back().second;
-                        fprintf(stderr, "[center]   shortest: slot %zu: %.3f ms, %llu steps\n", i, byd.back().first / 1e5, h_slots[i]);
-                    }
-                }
-            }
-        }
-        if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[3], st));
-        if (e->prof_level >= 2) HIP_TRY(hipEventRecord(e->ev[4], st));
+// ---- a plan of ONE window over one file (`ga[segment]`): the whole count is one launch -- the workgroup looks its
+// record ranges up itself; no work list, no second window class, no merge pass, no events
+int count_single(pc_engine *e, pc_plan *p, const CountCall &c) {
+    const HistLds s = hist_lds_shape(e);
+    const size_t lds = ((size_t)p->max_slots * p->rows * p->G + s.table_words) * sizeof(uint32_t);
+    if (lds > e->max_lds)
+        return fail(PC_ERR_ARG, "pc_count: the window needs %zu bytes of LDS, the device offers %zu per workgroup (too many rows)", lds, e->max_lds);
+    const FileView fv0 = e->files[0]->view();
+    PC_TRY(mark(e, 2));
+    dispatch_hist<false>(e->kind, c.outmode, [&](auto K, auto O) {
+        constexpr int k = decltype(K)::value, o = decltype(O)::value;
+        hipLaunchKernelGGL((k_hist_point<k, o, kHistWG, false, false, true>), dim3(1), dim3(kHistWG), lds, e->stream, p->d_pieces.p, p->d_opieces.p,
+                           fv0, fv0, e->d_files.p, (const WorkItem *)p->d_tiles.p, p->d_wcounters.p, p->d_tile_items.p, c.mp, p->G, p->max_slots,
+                           s.tab_lo, s.tab_n, s.fast_lo, s.fast_hi, (uint32_t *)p->d_hist.p, (int64_t)e->Ws(), (typename OutT_<o>::type *)p->d_out.p,
+                           e->norm_sum, (uint32_t)e->Wg(), (uint32_t)e->Wr(), (const FileRange *)nullptr, c.nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u);
+    });
+    PC_TRY(mark(e, 3));
+    return mark(e, 4);
+}
+
+// ---- the work lists of a point-rule count
+struct WorkLists {
+    int64_t cap = 0, cap_small = 0;   // capacity of the list of the dense windows, of the sparse ones
+    int small_g = 0;                  // window of the sparse class (0: no such class)
+    pc_plan::WorkKey key;
+    HistLds shape;                    // dynamic LDS of k_hist_point: what both classes share, and the bytes of either
+    size_t lds = 0, lds_small = 0;
+    // grids: the whole list capacity, or -- once a count of this plan has shown how many items each
+    // class queues (same alignments, same knobs) -- exactly those: a sparse annotation leaves most
+    // of the capacity empty, and an empty workgroup still costs a dispatch slot
+    unsigned grid = 0, grid_front = 0, grid_small = 0;
+    uint32_t launched[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};   // exact grids: what k_gather_split checks the queued counts against
+};
+
+int size_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, WorkLists &w) {
+    const int nfiles = c.nfiles, G = p->G;
+    const int64_t R = e->knobs.work_r;                             // records per work item
+    const int64_t pile = e->knobs.pile ? e->knobs.pile : 12 * R;   // a 128-nt sub-window with more records than this is merged through the histogram
+    // work-list capacity (an upper bound): a window scanning n records yields at most
+    // max(1, 2n/R) items, and every record is scanned by at most 1 + (W+127)/G windows
+    const int halo = std::max(std::max(e->W(), e->Ws()), std::max(e->Wg(), e->Wr()));
+    // (a multi-row plan gives every strand mode of a window a tile of its own -- pc_plan_create, split_modes --
+    // so a record is scanned by up to popcount(modes) tiles per window)
+    const int tiles_per_window = p->rows > 1 ? std::max(1, __builtin_popcount(p->modes)) : 1;
+    const double windows_per_record = (1.0 + (double)(halo + 127) / (double)G) * (double)tiles_per_window;
+    w.cap = (int64_t)c.ntiles * nfiles + (int64_t)(2.0 * windows_per_record * (double)c.nrec / (double)R) + nfiles + 64;
+    const bool b16 = e->kind == PC_MAP_STRAT5;   // 16-bit bins, two positions per word (k_hist_point)
+    if (b16) {
+        // a window that scans more than 65 535 records, runs and list entries is merged, in slices of ONE
+        // kind of range each (k_tile_ranges): at most adds / R + 4 items per such window, and fewer than adds / 65 535 of them
+        int64_t nxl = 0, ngp = 0;
+        for (auto *f : e->files) { nxl += f->nxlong; ngp += f->ngap; }
+        w.cap += (int64_t)(6.0 * windows_per_record * (double)(c.nrec + c.nextra + ngp) / (double)R) +
+                 (int64_t)c.ntiles * nfiles * (4 + 2 * (nxl / R));
     }
-    if (e->prof_level >= 1) HIP_TRY(hipEventRecord(e->ev[5], st));
+    if (w.cap >= (int64_t)0xffffffffu) return fail(PC_ERR_ARG, "pc_count: work list too large");
+    PC_TRY(p->d_work.reserve((size_t)w.cap));
+    // sparse windows: single-wave workgroups with a small LDS window (rows == 1 only)
+    // (skipped for dense annotations, where queried positions fill most of every window)
+    const bool sparse_plan = (double)p->npos < 0.25 * (double)c.ntiles * (double)G;
+    w.small_g = ((p->rows == 1 || e->knobs.small_rows) && sparse_plan && !e->knobs.no_small) ? std::min(e->knobs.small_g, G) : 0;
+    w.cap_small = w.small_g ? (int64_t)c.ntiles * nfiles : 0;
+    PC_TRY(p->d_work_small.reserve((size_t)std::max<int64_t>(w.cap_small, 1)));
+    if (nfiles > 1) {
+        PC_TRY(p->d_chain.reserve((size_t)w.cap * (size_t)(nfiles - 1)));
+        PC_TRY(p->d_chain_small.reserve((size_t)std::max<int64_t>(w.cap_small, 1) * (size_t)(nfiles - 1)));
+    }
+    pc_plan::WorkKey &key = w.key;
+    key.generation = e->work_generation; key.nfiles = nfiles; key.G = G; key.Wg = e->Wg(); key.Ws = e->Ws(); key.Wr = e->Wr();
+    key.small_g = w.small_g; key.R = R; key.pile = pile; key.small_n = e->knobs.small_n; key.cap = w.cap;
+    w.shape = hist_lds_shape(e);
+    const size_t slot_words = (size_t)p->max_slots * p->rows;   // bin words per window position (per two, with 16-bit bins)
+    w.lds = (((slot_words * G) >> (b16 ? 1 : 0)) + w.shape.table_words) * sizeof(uint32_t);
+    w.lds_small = (((slot_words * w.small_g) >> (b16 ? 1 : 0)) + w.shape.table_words) * sizeof(uint32_t);
+    return PC_OK;
+}
+
+// page-locked words that counts queued on the GPU are read back into, and the event behind that copy
+int ensure_readback(uint32_t **host, hipEvent_t *ev, size_t words) {
+    if (*host) return PC_OK;
+    HIP_TRY(hipHostMalloc((void **)host, words * sizeof(uint32_t), hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+    return PC_OK;
+}
+
+int ensure_work_counts(pc_plan *p) { return ensure_readback(&p->h_work_counts, &p->ev_work_counts, 8); }
+
+// a read-back has arrived: deterministic for this plan while the generation stands, no further read-backs
+void take_work_counts(pc_plan *p) {
+    for (int k = 0; k < 3; ++k) p->work_counts[k] = p->h_work_counts[k];
+    p->work_merged = p->h_work_counts[4];
+    p->work_counts_known = true;
+}
+
+int build_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w) {
+    hipStream_t st = e->stream;
+    const int ntiles = c.ntiles;
+    // the lists of this plan are (re)built: counters and per-tile item counts start from zero (they arrive
+    // zeroed with the plan's tables, so the first count of a plan needs no memset)
+    if (!p->wcounters_zero) HIP_TRY(hipMemsetAsync(p->d_wcounters.p, 0, 8 * sizeof(uint32_t), st));
+    if (!p->tile_items_zero) HIP_TRY(hipMemsetAsync(p->d_tile_items.p, 0, ((size_t)ntiles + 1) * sizeof(uint32_t), st));
+    p->wcounters_zero = false;
+    p->tile_items_zero = false;
+    // one thread per window (several files: joint windows), or sixteen lanes per window while that still fits the chip at
+    // once: the exact record bounds of a window are then searched by the group (three rounds of sixteen probes instead of a
+    // dozen dependent loads each) -- a plan of a few thousand windows (C2: 6 144) otherwise runs on two dozen CUs at the
+    // pace of one thread's load chain
+    const int64_t nwin = ntiles;
+    const int lanes = (nwin * 16 <= e->knobs.ranges_cg16_max && !e->knobs.ranges_cg1) ? 16 : 1;
+    dispatch_int<16, 1>(lanes, [&](auto CG) {
+        hipLaunchKernelGGL((k_tile_ranges<decltype(CG)::value>), dim3((unsigned)((nwin * lanes + kRangesWG - 1) / kRangesWG)), dim3(kRangesWG), 0, st, p->d_tiles.p, ntiles,
+                           e->files[0]->view(), e->d_files.p, c.nfiles, p->G, e->Wg(), e->Ws(), e->Wr(), w.key.R, w.key.pile, p->d_work.p, p->d_wcounters.p, p->d_tile_items.p, (uint32_t)w.cap,
+                           p->d_work_small.p, w.small_g, w.key.small_n, e->knobs.debug_work, p->d_chain.p, p->d_chain_small.p, e->kind == PC_MAP_STRAT5 ? 1 : 0);
+    });
+    if (p->hist_lazy)
+        hipLaunchKernelGGL(k_clear_split, dim3((unsigned)((ntiles + kClearPerWG - 1) / kClearPerWG)), dim3(kWG), 0, st, p->d_tiles.p, ntiles,
+                           p->d_pieces.p, p->d_tile_items.p, p->d_wcounters.p, p->rows, (uint32_t *)p->d_hist.p, (int64_t)p->npos);
+    p->work_key = w.key;
+    p->work_valid = true;
+    p->work_counts_known = false;      // the counts of the lists just replaced size no grid
+    p->guard_pending = true;           // k_gather_split checks the new lists against the capacity: read with the results
+    p->work_counts_generation = 0;
+    // The first count of a plan does not know how many items its lists hold, and used to launch the whole
+    // capacity: for a sparse annotation under a multi-row rule that is 3.6 M workgroups for 0.53 M items (C5:
+    // 3.88 ms against 3.24, and the merge pass on top).  Where the capacity is far above the window count, the
+    // queued counts are read back NOW -- one small copy and a stream synchronisation, ~20 us of idle GPU -- and
+    // this count already launches exact grids.
+    const int64_t spare = w.cap + w.cap_small - nwin;
+    if (ntiles >= 4096 && spare >= e->knobs.first_sync_spare && !e->knobs.test_stale_counts && !e->knobs.debug_work) {
+        PC_TRY(ensure_work_counts(p));
+        HIP_TRY(hipMemcpyAsync(p->h_work_counts, p->d_wcounters.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        take_work_counts(p);
+        p->work_counts_generation = e->work_generation;
+    }
+    return PC_OK;
+}
+
+void choose_grids(pc_engine *e, pc_plan *p, const CountCall &c, WorkLists &w) {
+    w.grid = w.grid_front = (unsigned)w.cap;
+    w.grid_small = (unsigned)w.cap_small;
+    if (c.ntiles < 4096 || p->work_counts_generation != e->work_generation) return;   // (small plans do not track their counts)
+    if (p->h_work_counts && !p->work_counts_known && hipEventQuery(p->ev_work_counts) == hipSuccess) take_work_counts(p);
+    if (!p->work_counts_known) return;
+    const uint32_t nh = p->work_counts[0], nl = p->work_counts[1] - ((e->knobs.test_stale_counts && p->work_counts[1]) ? 1u : 0u), ns = p->work_counts[2];
+    if ((uint64_t)nh + nl <= (uint64_t)w.cap && (int64_t)ns <= w.cap_small) {
+        w.grid_front = nh;
+        w.grid = std::max(1u, nh + nl);
+        w.grid_small = ns;
+        w.launched[0] = nh; w.launched[1] = nl; w.launched[2] = ns;
+        p->exact_grid_used = true;
+    }
+}
+
+// sparse windows (single-wave workgroups) and dense ones are two independent launches over
+// disjoint windows: they run side by side on two streams, forked after the work lists exist
+// and joined before the last kernel of the call
+int launch_hist(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w) {
+    const HistLds &s = w.shape;
+    const int nfiles = c.nfiles;
+    const FileView fv0 = e->files[0]->view();
+    const FileView fv1 = nfiles > 1 ? e->files[1]->view() : fv0;
+    hipStream_t st = e->stream, st_small = e->side_stream;
+    if (w.cap_small) {
+        HIP_TRY(hipEventRecord(e->ev_fork, st));
+        HIP_TRY(hipStreamWaitEvent(st_small, e->ev_fork, 0));
+    }
+    dispatch_hist<true>(e->kind, c.outmode, [&](auto K, auto O) {
+        dispatch_int<0, 1>(nfiles > 1, [&](auto M) {
+            constexpr int k = decltype(K)::value, o = decltype(O)::value;
+            constexpr bool m = decltype(M)::value != 0;
+            typename OutT_<o>::type *out = (typename OutT_<o>::type *)p->d_out.p;
+            hipLaunchKernelGGL((k_hist_point<k, o, kHistWG, false, m>), dim3(w.grid), dim3(kHistWG), w.lds, st, p->d_pieces.p,
+                               p->d_opieces.p, fv0, fv1, e->d_files.p, p->d_work.p, p->d_wcounters.p, p->d_tile_items.p, c.mp,
+                               p->G, p->max_slots, s.tab_lo, s.tab_n, s.fast_lo, s.fast_hi, (uint32_t *)p->d_hist.p, p->npos, out,
+                               e->norm_sum, (uint32_t)w.cap, w.grid_front, p->d_chain.p, nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u);
+            if (w.cap_small && w.grid_small)
+                hipLaunchKernelGGL((k_hist_point<k, o, 64, true, m>), dim3(w.grid_small), dim3(64), w.lds_small, st_small,
+                                   p->d_pieces.p, p->d_opieces.p, fv0, fv1, e->d_files.p, p->d_work_small.p,
+                                   p->d_wcounters.p, p->d_tile_items.p, c.mp, w.small_g, p->max_slots, s.tab_lo, s.tab_n, s.fast_lo, s.fast_hi,
+                                   (uint32_t *)p->d_hist.p, p->npos, out, e->norm_sum, (uint32_t)w.cap_small, w.grid_small,
+                                   p->d_chain_small.p, nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u);
+        });
+    });
+    if (w.cap_small) {
+        HIP_TRY(hipEventRecord(e->ev_join, st_small));
+        HIP_TRY(hipStreamWaitEvent(st, e->ev_join, 0));
+    }
+    return PC_OK;
+}
+
+// tiles that were split into several work items: lay out from the merged histogram
+// (k_gather_split clears what the split tiles merged: a histogram that was all zero stays so)
+void merge_windows(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w) {
+    // (skipped once the plan's lists are known to hold no merged window: the lists are the plan's own and do not
+    // change from count to count, so neither does that -- and the exact grids it would check were read from them)
+    if (w.launched[0] != 0xffffffffu && p->work_merged == 0 && !e->knobs.test_stale_counts) return;
+    const int split_per_wg = kWG; // merged windows are the exception (pile-ups), with several files too (joint windows)
+    dispatch_int<0, 1, 2>(c.outmode, [&](auto O) {
+        constexpr int o = decltype(O)::value;
+        hipLaunchKernelGGL((k_gather_split<o>), dim3((unsigned)((c.ntiles + split_per_wg - 1) / split_per_wg)), dim3(kWG), 0, e->stream,
+                           p->d_tiles.p, c.ntiles, split_per_wg, p->d_pieces.p,
+                           p->d_opieces.p, p->d_tile_items.p, p->d_wcounters.p, p->rows, (uint32_t *)p->d_hist.p, p->npos,
+                           (typename OutT_<o>::type *)p->d_out.p, e->norm_sum, w.launched[0], w.launched[1], w.launched[2], (uint32_t)w.cap, e->d_counters.p + 12);
+    });
+}
+
+// how many items each class queued (k_gather_split keeps a copy): sizes the next launch of a large plan
+int read_work_counts(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w) {
+    hipStream_t st = e->stream;
+    if (c.ntiles >= 4096) {
+        PC_TRY(ensure_work_counts(p));
+        if (p->work_counts_generation != e->work_generation) {   // one read-back per (plan, generation)
+            p->work_counts_known = false;
+            HIP_TRY(hipMemcpyAsync(p->h_work_counts, p->d_wcounters.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipEventRecord(p->ev_work_counts, st));
+            p->work_counts_generation = e->work_generation;
+        }
+    }
+    if (e->knobs.debug_work) { // diagnostics: how many work items of each class this call queued
+        uint32_t c4[4] = {0, 0, 0, 0};
+        HIP_TRY(hipMemcpyAsync(c4, p->d_wcounters.p, sizeof(c4), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        fprintf(stderr, "[work] tiles %d: heavy %u light %u small %u, long-span candidates %u (capacity %lld, G %d, R %lld)\n", c.ntiles,
+                c4[0], c4[1], c4[2], c4[3], (long long)w.cap, p->G, (long long)w.key.R);
+    }
+    return PC_OK;
+}
+
+int count_lists(pc_engine *e, pc_plan *p, const CountCall &c) {
+    WorkLists w;
+    PC_TRY(size_work_lists(e, p, c, w));
+    if (!(p->work_valid && p->work_key == w.key) || e->knobs.debug_work) PC_TRY(build_work_lists(e, p, c, w));
+    PC_TRY(mark(e, 2));
+    if (w.lds > e->max_lds)
+        return fail(PC_ERR_ARG, "pc_count: the window needs %zu bytes of LDS, the device offers %zu per workgroup (too many rows)", w.lds, e->max_lds);
+    choose_grids(e, p, c, w);
+    PC_TRY(launch_hist(e, p, c, w));
+    PC_TRY(mark(e, 3));
+    PC_TRY(mark(e, 4));
+    merge_windows(e, p, c, w);
+    return read_work_counts(e, p, c, w);
+}
+
+// ---- the center rule: k_center2 writes every queried position of the tiles straight into the output layout; the
+// compact histogram is not touched
+int reserve_center(pc_engine *e, pc_plan *p) {
+    const size_t nchunks = p->n_cchunks, nfiles = e->files.size();
+    if (kCenterCap * (int64_t)nchunks >= (int64_t)1 << kSubShift) return fail(PC_ERR_ARG, "pc_count: too many positions for the center rule");
+    PC_TRY(p->d_corder.reserve((size_t)kCenterCap * nchunks));   // dispatch list: heavy entries front, light back
+    PC_TRY(p->d_ccand.reserve(nchunks));
+    PC_TRY(p->d_cranges.reserve(nchunks * nfiles));
+    PC_TRY(p->d_crec.reserve(nchunks * nfiles));
+    PC_TRY(p->d_crows.reserve(nchunks * nfiles * (size_t)(2 * kCenterRows)));
+    PC_TRY(p->d_ccounts.reserve(8));
+    PC_TRY(e->d_cvalh.reserve(256));
+    // one descriptor per dispatch entry and file; k_center2 takes several entries per wave
+    return p->d_cslots.reserve(2 * nchunks * nfiles);   // (heavy entries < chunks, light entries <= chunks)
+}
+
+// the dispatch list of the plan's chunks and its descriptors: kept while the work generation, the halo and the file count stand
+int build_center_dispatch(pc_engine *e, pc_plan *p, int W) {
+    hipStream_t st = e->stream;
+    const int nfiles = (int)e->files.size();
+    const int64_t nchunks = (int64_t)p->n_cchunks;
+    p->center_nfiles = nfiles;
+    HIP_TRY(hipMemsetAsync(p->d_ccounts.p, 0, 8 * sizeof(uint32_t), st));
+    unsigned long long *total = (unsigned long long *)(p->d_ccounts.p + 2);
+    const unsigned wgs = (unsigned)((nchunks + kRangesWG - 1) / kRangesWG);
+    hipLaunchKernelGGL(k_center_weigh, dim3(wgs), dim3(kRangesWG), 0, st, p->d_cchunks.p, nchunks, e->d_files.p, nfiles, W,
+                       p->d_ccand.p, p->d_cranges.p, p->d_crec.p, p->d_crows.p, total);
+    // cut thresholds, in multiples of the mean candidate count
+    const int ck1 = e->knobs.center_t1, ck2 = e->knobs.center_t2;
+    hipLaunchKernelGGL(k_center_order, dim3(wgs), dim3(kRangesWG), 0, st, p->d_ccand.p, nchunks, total, e->knobs.center_floor,
+                       (int64_t)2048, ck1, ck2, p->d_corder.p, p->d_ccounts.p);
+    hipLaunchKernelGGL(k_center_slots, dim3((unsigned)((2 * nchunks + kRangesWG - 1) / kRangesWG)), dim3(kRangesWG), 0, st, p->d_cchunks.p, nchunks,
+                       e->d_files.p, nfiles, W, p->d_corder.p, p->d_ccounts.p, p->d_cranges.p, p->d_crec.p, p->d_crows.p, p->d_opieces.p,
+                       p->d_cslots.p, (unsigned long long *)(p->d_ccounts.p + 4));
+    p->center_generation = e->work_generation;
+    p->center_W = W;
+    // how many entries the list got: sizes the grid of the later counts of this plan (read back once)
+    PC_TRY(ensure_readback(&p->h_center_counts, &p->ev_center_counts, 2));
+    p->center_counts_known = false;
+    HIP_TRY(hipMemcpyAsync(p->h_center_counts, p->d_ccounts.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(p->ev_center_counts, st));
+    return PC_OK;
+}
+
+// descriptors: heavy entries one wave each, PC_CENTER_PER_WAVE light entries per wave (an eighth of the list per XCD)
+void launch_center2(pc_engine *e, pc_plan *p, const CountCall &c, int W, unsigned long long *dbg, size_t dbg_slots) {
+    Center2Ctx c2;
+    StagedFile *sf0 = e->files[0];
+    c2.slots = p->d_cslots.p;
+    c2.indirect = 0u;
+    for (int k = 0; k < 3; ++k) {
+        c2.ent[k] = sf0->cs_n[k] >= 0 ? sf0->cs_ent[k].p : nullptr;
+        if (sf0->len_max > 255) c2.indirect |= 1u << k;
+    }
+    c2.files = e->d_files.p; c2.nfiles = c.nfiles; c2.file0 = sf0->view(); c2.mp = c.mp; c2.W = W; c2.inv = e->d_inv.p; c2.invh = e->d_invh.p; c2.cvalh = e->d_cvalh.p;
+    c2.counters = p->d_ccounts.p;
+    c2.known = p->center_counts_known ? 1u : 0u; c2.n_heavy = p->center_counts[0]; c2.n_light = p->center_counts[1];
+    c2.opieces = p->d_opieces.p; c2.out = (double *)p->d_out.p; c2.norm_sum = e->norm_sum; c2.norm_on = e->norm_on ? 1 : 0;
+    c2.dbg = dbg; c2.dbg_cap = (uint32_t)dbg_slots;
+    uint64_t g2;
+    if (p->center_counts_known) {
+        const uint64_t n8 = ((uint64_t)p->center_counts[1] + 7) >> 3;
+        g2 = (uint64_t)p->center_counts[0] + 8 * ((n8 + PC_CENTER_PER_WAVE - 1) / PC_CENTER_PER_WAVE);
+    } else g2 = 2 * (uint64_t)p->n_cchunks + 8;
+    const dim3 cg2((unsigned)std::max<uint64_t>(g2, 1));
+    // (files with reads beyond a stream entry's 8-bit fields, or a stream too long for 32-bit byte offsets, take the
+    // instantiation that tests every batch for them)
+    bool general = false;
+    for (auto *f : e->files) general |= f->len_max > 255 || f->n + f->nrun >= ((int64_t)1 << 28);
+    // (several files: one descriptor per entry and file, replayed into the same sums in file order)
+    dispatch_int<0, 1>(dbg != nullptr, [&](auto D) {
+        dispatch_int<0, 1>(general, [&](auto G) {
+            dispatch_int<0, 1>(c.nfiles > 1, [&](auto M) {
+                hipLaunchKernelGGL((k_center2<decltype(D)::value != 0, decltype(G)::value != 0, decltype(M)::value != 0>), cg2, dim3(64), (size_t)e->knobs.center_lds, e->stream, c2);
+            });
+        });
+    });
+}
+
+// diagnostic launch: replay steps and dispatched waves, summed on the host; PC_CENTER_DEBUG prints them
+int report_center_debug(pc_engine *e, pc_plan *p, int W, const unsigned long long *d_dbg, size_t dbg_slots) {
+    std::vector<unsigned long long> h(2 * dbg_slots), h_slots(dbg_slots);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipMemcpy(h.data(), d_dbg, h.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_slots.data(), d_dbg + h.size(), h_slots.size() * 8, hipMemcpyDeviceToHost));
+    e->center_steps = 0; e->center_waves = 0;
+    unsigned long long t0 = ~0ull, t1 = 0, sum = 0, steps_heavy = 0, steps_pers = 0, n_heavy_w = 0, n_pers_w = 0;
+    const size_t n_front = p->n_cchunks;   // (heavy entries occupy the front of the list: fewer than the chunk count)
+    std::vector<std::pair<unsigned long long, size_t>> byd;
+    for (size_t i = 0; i < dbg_slots; ++i)
+        if (h[2 * i]) {
+            e->center_steps += (int64_t)h_slots[i]; e->center_waves += 1;
+            const bool pers = i >= n_front;
+            (pers ? steps_pers : steps_heavy) += h_slots[i];
+            (pers ? n_pers_w : n_heavy_w) += 1;
+            t0 = std::min(t0, h[2 * i + 1]); t1 = std::max(t1, h[2 * i + 1] + h[2 * i]);
+            sum += h[2 * i];
+            byd.emplace_back(h[2 * i], i);
+        }
+    if (e->knobs.center_debug != 0) {
+        fprintf(stderr, "[center] replay steps: %llu in %llu waves of the heavy entries, %llu in %llu waves of the light ones\n", steps_heavy, n_heavy_w,
+                steps_pers, n_pers_w);
+        fprintf(stderr, "[center] W %d: launch span %llu ticks (100 MHz: %.3f ms), summed wave time %llu ticks = %.1f x the span\n", W, t1 - t0,
+                (t1 - t0) / 1e5, sum, (double)sum / (double)std::max<unsigned long long>(t1 - t0, 1));
+        const int nb = 20;
+        std::vector<double> occ(nb, 0.0);
+        const double span = (double)std::max<unsigned long long>(t1 - t0, 1);
+        for (size_t i = 0; i < dbg_slots; ++i)
+            if (h[2 * i]) {
+                const double a = (double)(h[2 * i + 1] - t0) / span * nb, b = (double)(h[2 * i + 1] + h[2 * i] - t0) / span * nb;
+                for (int k = std::max(0, (int)a); k < nb && k < b; ++k) occ[(size_t)k] += std::min(b, k + 1.0) - std::max(a, (double)k);
+            }
+        fprintf(stderr, "[center] resident waves per twentieth of the launch:");
+        for (int k = 0; k < nb; ++k) fprintf(stderr, " %.0f", occ[(size_t)k]);
+        fprintf(stderr, "\n");
+        std::sort(byd.rbegin(), byd.rend());
+        for (size_t k = 0; k < std::min<size_t>(byd.size(), 8); ++k) {
+            const size_t i = byd[k].second;
+            fprintf(stderr, "[center]   slot %zu (%s): %.3f ms, started at %.3f ms, %llu steps\n", i,
+                    i >= n_front ? "light" : "heavy", byd[k].first / 1e5, (h[2 * i + 1] - t0) / 1e5, h_slots[i]);
+        }
+        if (!byd.empty()) {
+            const size_t i = byd.back().second;
+            fprintf(stderr, "[center]   shortest: slot %zu: %.3f ms, %llu steps\n", i, byd.back().first / 1e5, h_slots[i]);
+        }
+    }
+    return PC_OK;
+}
+
+int count_center(pc_engine *e, pc_plan *p, const CountCall &c) {
+    PC_TRY(mark(e, 2));
+    if (p->n_cchunks > 0) {
+        const int W = e->W();
+        PC_TRY(reserve_center(e, p));
+        hipLaunchKernelGGL(k_center_vals, dim3(1), dim3(256), 0, e->stream, c.mp, e->d_invh.p, e->d_cvalh.p);
+        if (p->center_generation != e->work_generation || p->center_W != W || p->center_nfiles != c.nfiles) {
+            PC_TRY(build_center_dispatch(e, p, W));
+        } else if (!p->center_counts_known && hipEventQuery(p->ev_center_counts) == hipSuccess) {
+            p->center_counts[0] = p->h_center_counts[0];
+            p->center_counts[1] = p->h_center_counts[1];
+            p->center_counts_known = true;
+        }
+        // PC_CENTER_DEBUG: how long every dispatched wave ran (wall clock ticks), printed after the launch
+        DevBuf<unsigned long long> d_dbg;
+        const bool dbg_on = e->knobs.center_debug != 0 || e->want_center_steps;
+        const size_t dbg_slots = (size_t)kCenterCap * p->n_cchunks;   // heavy entries from the front, light ones from the back
+        if (dbg_on) {
+            PC_TRY(d_dbg.reserve(3 * dbg_slots));
+            HIP_TRY(hipMemsetAsync(d_dbg.p, 0, 3 * dbg_slots * 8, e->stream));
+        }
+        launch_center2(e, p, c, W, d_dbg.p, dbg_slots);
+        if (dbg_on) PC_TRY(report_center_debug(e, p, W, d_dbg.p, dbg_slots));
+    }
+    PC_TRY(mark(e, 3));
+    return mark(e, 4);
+}
+
+int count_finish(pc_engine *e, pc_plan *p, const CountCall &c) {
+    PC_TRY(mark(e, 5));
     HIP_TRY(hipGetLastError());
-    p->last_dtype = out_dtype;
+    p->last_dtype = c.out_dtype;
     p->counted = true;
     p->rle_runs = -1;
     e->timing_valid = e->prof_level > 0;
     e->timed_level = e->prof_level;
     // records once (8 B) + extra runs (8 B) + segments (24 B) + outputs once (8 B)
-    e->last_alg_bytes = nrec * 8 + (nextra > 0 ? (nextra - 0) * 8 : 0) + p->nseg * 24 + p->covered * 8;
+    e->last_alg_bytes = c.nrec * 8 + (c.nextra > 0 ? c.nextra * 8 : 0) + p->nseg * 24 + p->covered * 8;
     return PC_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pc_count(pc_engine *e, pc_plan *p, int out_dtype) {
+    PC_TRY(count_validate(e, p, out_dtype));
+    HIP_TRY(hipSetDevice(e->device));
+    PC_TRY(count_prepare(e, p));
+    const bool center = e->kind == PC_MAP_CENTER;
+    CountCall c;
+    c.out_dtype = out_dtype;
+    c.outmode = e->norm_on ? 2 : (out_dtype == PC_OUT_FLOAT64 ? 1 : 0);
+    c.nfiles = (int)e->files.size(); c.ntiles = (int)p->n_tiles;
+    c.nrec = c.nextra = 0;
+    for (auto *f : e->files) { c.nrec += f->n; c.nextra += f->nrun; }
+    c.hist_bytes = center ? 0 : (size_t)p->npos * p->rows * sizeof(uint32_t);
+    c.mp = e->params();
+    PC_TRY(count_clear(e, p, c));
+    // (one window, not under the stratified rule: its 16-bit bins rely on the work lists, which cut or merge a window that
+    // scans more than 65 535 records)
+    const bool single = c.ntiles == 1 && c.nfiles == 1 && !e->knobs.debug_work && !e->knobs.no_single && e->kind != PC_MAP_STRAT5;
+    if (center) PC_TRY(count_center(e, p, c));
+    else if (single) PC_TRY(count_single(e, p, c));
+    else if (c.ntiles > 0) PC_TRY(count_lists(e, p, c));
+    else for (int k = 2; k <= 4; ++k) PC_TRY(mark(e, k));   // a plan without windows
+    return count_finish(e, p, c);
 }
 
 int pc_sync(pc_engine *e) {
@@ -3351,7 +3403,7 @@ int pc_read_counts(pc_engine *e, pc_plan *p, void *host_out, int64_t out_elems) 
     if (!e || !p || p->e != e || !p->counted) return fail(PC_ERR_STATE, "pc_read_counts: nothing counted yet");
     if (out_elems != p->out_elems || (out_elems > 0 && !host_out)) return fail(PC_ERR_ARG, "pc_read_counts: buffer size mismatch");
     HIP_TRY(hipSetDevice(e->device));
-    { const int grc = check_grid_guard(e, p); if (grc != PC_OK) return grc; }
+    PC_TRY(check_grid_guard(e, p));
     const size_t bytes = (size_t)out_elems * 8;
     const char *knob = getenv("PC_STAGE_SLICE");   // (test knob: the ring for every size, in pieces of so many 4 KiB pages)
     if (bytes >= 4 * TransferRing::kPiece || (bytes > 0 && knob)) {
@@ -3405,7 +3457,7 @@ void *pc_total_device_ptr(pc_plan *p) { return p ? (void *)p->d_total.p : nullpt
 int pc_total(pc_engine *e, pc_plan *p, void *host_out8) {
     if (!e || !p || p->e != e || !p->counted) return fail(PC_ERR_STATE, "pc_total: nothing counted yet");
     HIP_TRY(hipSetDevice(e->device));
-    { const int grc = check_grid_guard(e, p); if (grc != PC_OK) return grc; }
+    PC_TRY(check_grid_guard(e, p));
     hipStream_t st = e->stream;
     HIP_TRY(hipMemsetAsync(p->d_total.p, 0, 8, st));
     if (p->out_elems > 0) {
@@ -3413,8 +3465,7 @@ int pc_total(pc_engine *e, pc_plan *p, void *host_out8) {
             hipLaunchKernelGGL(k_total_i64, dim3(1024), dim3(kWG), 0, st, (const int64_t *)p->d_out.p, p->out_elems, (int64_t *)p->d_total.p);
         } else {
             const int nb = 1024;
-            int rc = e->d_partial.reserve(nb);
-            if (rc != PC_OK) return rc;
+            PC_TRY(e->d_partial.reserve(nb));
             hipLaunchKernelGGL(k_total_f64_partial, dim3(nb), dim3(kWG), 0, st, (const double *)p->d_out.p, p->out_elems, e->d_partial.p);
             hipLaunchKernelGGL(k_total_f64_final, dim3(1), dim3(64), 0, st, e->d_partial.p, nb, (double *)p->d_total.p);
         }
@@ -3531,7 +3582,7 @@ int pc_query_segment(pc_engine *e, int32_t tid, int64_t start, int64_t end, uint
     if (len <= 0 || len > kQueryMax || start < 0 || end > 0x7fffffffLL) return fail(PC_ERR_STATE, "pc_query_segment: the segment does not fit one window (1 .. %d positions)", kQueryMax);
     if (tid < 0 || tid >= e->ntid) return fail(PC_ERR_ARG, "pc_query_segment: reference id out of range");
     StagedFile *sf = e->files[0];
-    { const int frc = check_filter_columns(e, "pc_query_segment"); if (frc != PC_OK) return frc; }
+    PC_TRY(check_filter_columns(e, "pc_query_segment"));
     HIP_TRY(hipSetDevice(e->device));
     if (!e->q_host) {
         HIP_TRY(hipHostMalloc((void **)&e->q_host, (size_t)kQueryMax * 8 + 64, hipHostMallocMapped));
@@ -3540,16 +3591,9 @@ int pc_query_segment(pc_engine *e, int32_t tid, int64_t start, int64_t end, uint
     }
     hipStream_t st = e->stream;
     const MapParams mp = e->params();
-    int lmin = sf->len_min, lmax = sf->len_max;
-    int tab_lo = 0, tab_n = 0;
-    if (e->kind == PC_MAP_VAR5 && lmax >= lmin) {
-        tab_lo = lmin;
-        tab_n = std::max(0, std::min(std::min(lmax, e->table_len - 1) - lmin + 1, 1024));
-    }
-    int fast_lo = std::min(sf->tlen_min, sf->tlen_max), fast_hi = sf->tlen_max;
+    const HistLds ls = hist_lds_shape(e);
     const int G = kQueryMax;
-    const size_t stage_words = (size_t)kOpStage * sizeof(OutPiece) / sizeof(uint32_t);
-    const size_t lds = ((size_t)G + (size_t)((tab_n + 3) & ~3) + stage_words + (size_t)(fast_hi + 1) * kModes + 64) * sizeof(uint32_t);
+    const size_t lds = ((size_t)G + ls.table_words) * sizeof(uint32_t);
     if (lds > e->max_lds) return fail(PC_ERR_STATE, "pc_query_segment: the window needs %zu bytes of LDS", lds);
     const int mode = mode_of(strand);
     Tile tl{};
@@ -3563,24 +3607,13 @@ int pc_query_segment(pc_engine *e, int32_t tid, int64_t start, int64_t end, uint
     uint32_t *d_flag = (uint32_t *)((uint8_t *)e->q_dev + (size_t)kQueryMax * 8);
     const FileView fv0 = sf->view();
     const int outmode = e->norm_on ? 2 : (out_dtype == PC_OUT_FLOAT64 ? 1 : 0);
-#define PC_LAUNCH_QUERY(K, O)                                                                                          \
-    hipLaunchKernelGGL((k_hist_point<K, O, kHistWG, false, false, true>), dim3(1), dim3(kHistWG), lds, st, (const Piece *)nullptr, (const OutPiece *)nullptr, \
-                       fv0, fv0, (const FileView *)nullptr, (const WorkItem *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, mp, G, 1,   \
-                       tab_lo, tab_n, fast_lo, fast_hi, (uint32_t *)nullptr, (int64_t)e->Ws(), (OutT_<O>::type *)e->q_dev,                               \
-                       e->norm_sum, (uint32_t)e->Wg(), (uint32_t)e->Wr(), (const FileRange *)nullptr, 1, tl, op, d_flag, seq)
-#define PC_LAUNCH_QUERY_O(K)                                                                                           \
-    do {                                                                                                               \
-        if (outmode == 0) PC_LAUNCH_QUERY(K, 0);                                                                       \
-        else if (outmode == 1) PC_LAUNCH_QUERY(K, 1);                                                                  \
-        else PC_LAUNCH_QUERY(K, 2);                                                                                    \
-    } while (0)
-    switch (e->kind) {
-    case PC_MAP_FIVE: PC_LAUNCH_QUERY_O(0); break;
-    case PC_MAP_THREE: PC_LAUNCH_QUERY_O(1); break;
-    default: PC_LAUNCH_QUERY_O(3); break;
-    }
-#undef PC_LAUNCH_QUERY_O
-#undef PC_LAUNCH_QUERY
+    dispatch_hist<false>(e->kind, outmode, [&](auto K, auto O) {
+        constexpr int k = decltype(K)::value, o = decltype(O)::value;
+        hipLaunchKernelGGL((k_hist_point<k, o, kHistWG, false, false, true>), dim3(1), dim3(kHistWG), lds, st, (const Piece *)nullptr, (const OutPiece *)nullptr,
+                           fv0, fv0, (const FileView *)nullptr, (const WorkItem *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, mp, G, 1,
+                           ls.tab_lo, ls.tab_n, ls.fast_lo, ls.fast_hi, (uint32_t *)nullptr, (int64_t)e->Ws(), (typename OutT_<o>::type *)e->q_dev,
+                           e->norm_sum, (uint32_t)e->Wg(), (uint32_t)e->Wr(), (const FileRange *)nullptr, 1, tl, op, d_flag, seq);
+    });
     HIP_TRY(hipGetLastError());
     // poll the flag the kernel writes behind its counts (a stream synchronisation costs more than the kernel runs);
     // fall back to the synchronisation if it does not show up soon
@@ -3601,7 +3634,7 @@ int pc_query_segment(pc_engine *e, int32_t tid, int64_t start, int64_t end, uint
 
 int pc_center_row_fill(pc_engine *e, pc_plan *p, int64_t *row_entries, int64_t *row_slots) {
     if (!e || !p || p->e != e || !row_entries || !row_slots) return fail(PC_ERR_ARG, "pc_center_row_fill: bad arguments");
-    if (!p->center_slots || p->center_generation != e->work_generation || !p->d_ccounts.p)
+    if (p->center_generation != e->work_generation || !p->d_ccounts.p)
         return fail(PC_ERR_STATE, "pc_center_row_fill: the plan has no center dispatch list of one alignment file (count it under the center rule first)");
     HIP_TRY(hipSetDevice(e->device));
     unsigned long long v[2] = {0, 0};
@@ -3616,8 +3649,7 @@ int pc_stream_probe(pc_engine *e, int64_t bytes, int iters, double *read_gbps, d
     if (!e || bytes < (1 << 20) || iters < 1) return fail(PC_ERR_ARG, "pc_stream_probe: bad arguments");
     HIP_TRY(hipSetDevice(e->device));
     DevBuf<uint8_t> buf;
-    int rc = buf.reserve((size_t)bytes);
-    if (rc != PC_OK) return rc;
+    PC_TRY(buf.reserve((size_t)bytes));
     hipStream_t st = e->stream;
     const int64_t nvec = bytes / 16, n8 = bytes / 8;
     const unsigned grid_r = (unsigned)((nvec + kProbeChunk - 1) / kProbeChunk), grid_w = (unsigned)((n8 + 2 * kProbeChunk - 1) / (2 * kProbeChunk));
@@ -3665,8 +3697,7 @@ int pc_warn_details(pc_engine *e, pc_plan *p, uint8_t *flags, int32_t *last_len)
     }
     if (!any) return PC_OK;
     HIP_TRY(hipSetDevice(e->device));
-    int rc = refresh_file_views(e);
-    if (rc != PC_OK) return rc;
+    PC_TRY(refresh_file_views(e));
     const MapParams mp = e->params();
     std::vector<Unmappable> all;
     std::vector<uint32_t> file_of;   // staged file of every entry of `all` (parallel array, permuted with it)
@@ -3676,8 +3707,7 @@ int pc_warn_details(pc_engine *e, pc_plan *p, uint8_t *flags, int32_t *last_len)
         if (!f->n) continue;
         uint32_t cap = 1u << 16;
         for (;;) {
-            rc = e->d_unmap.reserve(cap);
-            if (rc != PC_OK) return rc;
+            PC_TRY(e->d_unmap.reserve(cap));
             HIP_TRY(hipMemsetAsync(e->d_counters.p + 1, 0, sizeof(uint32_t), e->stream));
             hipLaunchKernelGGL(k_unmappable, dim3((unsigned)((f->n + kWG - 1) / kWG)), dim3(kWG), 0, e->stream, f->view(), mp, e->ntid,
                                e->d_unmap.p, cap, e->d_counters.p + 1);
@@ -3718,7 +3748,7 @@ int pc_warn_details(pc_engine *e, pc_plan *p, uint8_t *flags, int32_t *last_len)
         pmax_f[i] = pf;
         pmax_r[i] = pr;
     }
-    { const int frc = fetch_host_inputs(p); if (frc != PC_OK) return frc; }
+    PC_TRY(fetch_host_inputs(p));
     for (int64_t s = 0; s < p->nseg; ++s) {
         const int32_t t = p->h_tid[(size_t)s];
         if (t < 0 || t >= e->ntid) continue;
@@ -3758,7 +3788,7 @@ int pc_mapped_reads(pc_engine *e, int file, int64_t rec_lo, int64_t rec_hi, int3
                     uint8_t strand, uint8_t *mask) {
     if (!e || file < 0 || file >= (int)e->files.size()) return fail(PC_ERR_ARG, "pc_mapped_reads: bad file index");
     if (!e->have_map) return fail(PC_ERR_STATE, "pc_mapped_reads: no mapping rule set");
-    { const int frc = check_filter_columns(e, "pc_mapped_reads"); if (frc != PC_OK) return frc; }
+    PC_TRY(check_filter_columns(e, "pc_mapped_reads"));
     StagedFile *f = e->files[file];
     if (rec_lo < 0 || rec_hi > f->n || rec_hi < rec_lo || (rec_hi > rec_lo && !mask)) return fail(PC_ERR_ARG, "pc_mapped_reads: bad record range");
     (void)tid;
@@ -3766,8 +3796,7 @@ int pc_mapped_reads(pc_engine *e, int file, int64_t rec_lo, int64_t rec_hi, int3
     HIP_TRY(hipSetDevice(e->device));
     const int64_t n = rec_hi - rec_lo;
     DevBuf<uint8_t> d_mask;
-    int rc = d_mask.reserve((size_t)n);
-    if (rc != PC_OK) return rc;
+    PC_TRY(d_mask.reserve((size_t)n));
     hipLaunchKernelGGL(k_mapped_reads, dim3((unsigned)((n + kWG - 1) / kWG)), dim3(kWG), 0, e->stream, f->view(), e->params(), rec_lo, rec_hi,
                        start, end, mode_of(strand), !(strand & PC_STRAND_NOFILTER), d_mask.p);
     HIP_TRY(hipMemcpyAsync(mask, d_mask.p, (size_t)n, hipMemcpyDeviceToHost, e->stream));
@@ -3779,10 +3808,9 @@ int pc_mapped_reads_batch(pc_engine *e, pc_plan *p, int64_t *offsets, int64_t *t
     if (!e || !p || p->e != e || !offsets || !total) return fail(PC_ERR_ARG, "pc_mapped_reads_batch: bad arguments");
     if (!e->have_map) return fail(PC_ERR_STATE, "pc_mapped_reads_batch: no mapping rule set");
     if (e->files.empty()) return fail(PC_ERR_STATE, "pc_mapped_reads_batch: no alignments staged");
-    { const int frc = check_filter_columns(e, "pc_mapped_reads_batch"); if (frc != PC_OK) return frc; }
+    PC_TRY(check_filter_columns(e, "pc_mapped_reads_batch"));
     HIP_TRY(hipSetDevice(e->device));
-    int rc = refresh_file_views(e);
-    if (rc != PC_OK) return rc;
+    PC_TRY(refresh_file_views(e));
     const int nfiles = (int)e->files.size();
     const int64_t nseg = p->nseg, npair = nseg * nfiles;
     *total = 0;
@@ -3790,7 +3818,7 @@ int pc_mapped_reads_batch(pc_engine *e, pc_plan *p, int64_t *offsets, int64_t *t
     p->mr_total = 0;
     if (npair == 0) return PC_OK;
     if (npair >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_mapped_reads_batch: too many (segment, file) pairs");
-    { const int frc = fetch_host_inputs(p); if (frc != PC_OK) return frc; }
+    PC_TRY(fetch_host_inputs(p));
     std::vector<BatchSeg> segs((size_t)nseg);
     for (int64_t s = 0; s < nseg; ++s) {
         BatchSeg &g = segs[(size_t)s];
@@ -3806,7 +3834,7 @@ int pc_mapped_reads_batch(pc_engine *e, pc_plan *p, int64_t *offsets, int64_t *t
     DevBuf<int64_t> d_spans;
     d_segs.pool = &e->pool; d_spans.pool = &e->pool; p->d_mr_off.pool = &e->pool; p->d_mr_rec.pool = &e->pool;
     hipStream_t st = e->stream;
-    rc = d_segs.upload(segs, st);
+    int rc = d_segs.upload(segs, st);
     if (rc == PC_OK) rc = d_spans.upload(spans, st);
     if (rc == PC_OK) rc = p->d_mr_off.reserve((size_t)npair + 1);
     if (rc != PC_OK) return rc;
@@ -3819,8 +3847,7 @@ int pc_mapped_reads_batch(pc_engine *e, pc_plan *p, int64_t *offsets, int64_t *t
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, p->d_mr_off.p, p->d_mr_off.p, (int)(npair + 1), st));
         DevBuf<uint8_t> d_tmp;
         d_tmp.pool = &e->pool;
-        rc = d_tmp.reserve(std::max<size_t>(tmp_bytes, 16));
-        if (rc != PC_OK) return rc;
+        PC_TRY(d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
         HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, p->d_mr_off.p, p->d_mr_off.p, (int)(npair + 1), st));
         static_assert(sizeof(unsigned long long) == sizeof(int64_t), "offsets are copied as they are");
         HIP_TRY(hipMemcpyAsync(offsets, p->d_mr_off.p, (size_t)(npair + 1) * 8, hipMemcpyDeviceToHost, st));
@@ -3828,8 +3855,7 @@ int pc_mapped_reads_batch(pc_engine *e, pc_plan *p, int64_t *offsets, int64_t *t
     }
     const int64_t tot = offsets[npair];
     if (tot >= (int64_t)0xffffffffu) return fail(PC_ERR_ARG, "pc_mapped_reads_batch: more than 2^32-2 mapped reads in one batch; split the segments");
-    rc = p->d_mr_rec.reserve((size_t)std::max<int64_t>(tot, 1));
-    if (rc != PC_OK) return rc;
+    PC_TRY(p->d_mr_rec.reserve((size_t)std::max<int64_t>(tot, 1)));
     hipLaunchKernelGGL((k_mapped_reads_batch<true>), dim3((unsigned)npair), dim3(kWG), 0, st, d_segs.p, nseg, e->d_files.p, nfiles, d_spans.p, mp,
                        (unsigned long long *)nullptr, p->d_mr_off.p, p->d_mr_rec.p);
     HIP_TRY(hipGetLastError());

@@ -1194,6 +1194,58 @@ def test_exact_grid_guard_and_cache_invalidation(pa, monkeypatch):
     e3.close()
 
 
+def test_first_count_readback_equals_capacity_launch(pa, oracle, monkeypatch):
+    """The first count of a large plan either reads the queued work counts back behind k_tile_ranges and launches exact
+    grids at once (spare capacity >= PC_FIRST_SYNC_SPARE), or launches the whole list capacity.  Both paths, the second
+    count and a third after a sync give the oracle's counts -- under a point rule and under the stratified rule (rows > 1,
+    16-bit bins, a tile per strand mode: the other capacity formula) -- and so does the first count after the alignments
+    changed under the plan."""
+    from plastid_amd import synth
+    from plastid_amd.engine import Engine
+    genome, tx, reads, mapping = synth.make_config("C4", scale=0.004, tx_scale=0.25)
+    half = reads.slice(0, reads.n // 2)
+
+    def engine(spare, files, m):
+        if spare is not None:
+            monkeypatch.setenv("PC_FIRST_SYNC_SPARE", spare)
+        eng = Engine(0)                      # (the knobs are read when the engine is created)
+        monkeypatch.delenv("PC_FIRST_SYNC_SPARE", raising=False)
+        eng.set_alignments(files)
+        synth.mapping_factory(m)._configure(eng)
+        return eng
+
+    # (three length rows: the fewest that are still "several rows" -- the outputs are rows x 23 M positions)
+    for m in (mapping, ("stratified", synth.VARIABLE_OFFSETS, 28, 30)):
+        engines = [engine("0", [reads], m), engine("99999999999", [reads], m)]
+        rows = engines[0].rows
+        assert (rows > 1) == (m[0] == "stratified")
+        p = tx.plan_arrays(rows=rows)
+        exp, _ = oracle_chain_outputs(oracle, [reads], spec_for(oracle, m), tx, p, rows, np.int64)
+        assert exp.sum() > 0
+        plans = []
+        for eng in engines:
+            plan = eng.plan(p["tid"], p["start"], p["end"], p["strand"], p["out_off"], p["out_step"], p["row_stride"],
+                            p["out_elems"], rows)
+            assert plan.tiles >= 4096
+            for k in range(3):               # first: a fresh plan (read-back and exact grids, or the whole capacity)
+                if k == 2:
+                    eng.sync()               # third: the queued read-back has arrived by now
+                got = plan.count(np.int64)
+                assert got.dtype == np.int64 and np.array_equal(got, exp), (m[0], k)
+            plans.append(plan)
+        engines[0].set_alignments([half])    # other records under the same plan: its lists are rebuilt, read back again
+        fresh = engine(None, [half], m)
+        plan_f = fresh.plan(p["tid"], p["start"], p["end"], p["strand"], p["out_off"], p["out_step"], p["row_stride"],
+                            p["out_elems"], rows)
+        part = plan_f.count(np.int64)
+        assert 0 < part.sum() < exp.sum()
+        assert np.array_equal(plans[0].count(np.int64), part), m[0]
+        for pl in plans + [plan_f]:
+            pl.close()
+        for eng in engines + [fresh]:
+            eng.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("group", ["quirks", "random_reads", "wide_reads"])
 def test_golden_reads_out_through_the_batch_call(pa, group):
