@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 9
+#define PC_ABI_VERSION 10
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -408,10 +408,29 @@ int pc_bam_index_finish(int n_ref, int64_t n_runs, const int32_t *run_tid, const
                         const uint64_t *run_end, const int64_t *lin_start, const uint64_t *linear, const uint64_t *ref_beg,
                         const uint64_t *ref_end, const int64_t *ref_mapped, const int64_t *ref_unmapped, int64_t n_no_coor,
                         pc_bam_index **out);
-/* the serialised .bai file: *bytes = its size; copied to buf when cap holds it (call with cap 0 first) */
+/* ---- (ABI 10) the CSI index (SAM specification 5.3; htslib's sam_index_build with min_shift > 0, sam.c:477-485): the
+ * index of a file whose references are longer than 2^29, or of any file with another leaf size.  min_shift: 8 .. 30, the
+ * leaves hold 2^min_shift positions; the depth n_lvls is the smallest with max(reference length) + 256 <=
+ * 2^(min_shift + 3 n_lvls), as htslib takes it from the header (0: one bin).  The same kernels with the shape as a
+ * parameter; the windows of 2^min_shift positions never leave the GPU: they are forward-filled there and every bin takes
+ * the offset of its first window (loff).  Errors: as pc_bam_index_build, and PC_ERR_ARG for a min_shift out of range, for
+ * an alignment that reaches beyond 2^(min_shift + 3 n_lvls) and for a file whose windows, summed over the references,
+ * exceed 2^28 (the message asks for a larger min_shift). */
+int pc_bam_index_build_csi(pc_engine *e, const char *path, int min_shift, pc_bam_index **out);
+/* The host half of a CSI build; no GPU call.  As pc_bam_index_finish, with run_loff -- per run the loff of its bin: the
+ * filled window at the bin's first leaf, 0 beyond the reference's windows; the runs of one bin carry one value -- in place
+ * of the linear arrays.  A bin >= ((1 << (3 n_lvls + 3)) - 1) / 7 is refused; the pseudo-bin is that number + 1. */
+int pc_bam_index_finish_csi(int min_shift, int n_lvls, int n_ref, int64_t n_runs, const int32_t *run_tid, const uint32_t *run_bin,
+                            const uint64_t *run_beg, const uint64_t *run_end, const uint64_t *run_loff, const uint64_t *ref_beg,
+                            const uint64_t *ref_end, const int64_t *ref_mapped, const int64_t *ref_unmapped, int64_t n_no_coor,
+                            pc_bam_index **out);
+/* the serialised .bai file: *bytes = its size; copied to buf when cap holds it (call with cap 0 first).  For a CSI these
+ * are the bytes of the UNCOMPRESSED payload ("CSI\1" ...): a .csi file is that payload in BGZF members, and this library
+ * does not link zlib -- the caller compresses (plastid_amd.bam.build_index does). */
 int pc_bam_index_bytes(pc_bam_index *idx, void *buf, int64_t cap, int64_t *bytes);
-/* [0] records, [1] placed records, [2] runs before the finish, [3] chunks after it, [4] bins (37450 not counted),
- * [5] linear entries, [6] n_no_coor, [7] mapped (what pysam's AlignmentFile.mapped sums from the index) */
+/* [0] records, [1] placed records, [2] runs before the finish, [3] chunks after it, [4] bins (the pseudo-bin not counted),
+ * [5] linear entries (CSI: the windows held on the device), [6] n_no_coor, [7] mapped (what pysam's AlignmentFile.mapped
+ * sums from the index) */
 int pc_bam_index_stats(pc_bam_index *idx, int64_t *out8);
 /* milliseconds: [0] upload, [1] inflate + CRC, [2] record chain (the engine's stream, as pc_bam_timing), [3] fields + order
  * checks, [4] index kernels, [5] read-back, [6] host finish, [7] the whole call (wall clock) */

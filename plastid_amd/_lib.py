@@ -103,6 +103,8 @@ SIGNATURES = {
     "pc_bam_stats": (_int, [_vp, _vp]),
     "pc_bam_index_build": (_int, [_vp, ctypes.c_char_p, _pp]),
     "pc_bam_index_finish": (_int, [_int, _i64] + [_vp] * 10 + [_i64, _pp]),
+    "pc_bam_index_build_csi": (_int, [_vp, ctypes.c_char_p, _int, _pp]),
+    "pc_bam_index_finish_csi": (_int, [_int, _int, _int, _i64] + [_vp] * 9 + [_i64, _pp]),
     "pc_bam_index_bytes": (_int, [_vp, _vp, _i64, ctypes.POINTER(_i64)]),
     "pc_bam_index_stats": (_int, [_vp, _vp]),
     "pc_bam_index_timing": (_int, [_vp, _vp]),
@@ -113,7 +115,7 @@ _lib = None
 
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 def load():

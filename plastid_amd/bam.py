@@ -108,24 +108,85 @@ def _region_tuples(regions):
     return [(r.chrom, r.start, r.end) if hasattr(r, "chrom") else tuple(r) for r in regions]
 
 
+_BGZF_EOF = bytes.fromhex("1f8b08040000000000ff0600424302001b0003000000000000000000")
+_BGZF_PIECE = 0xff00
+
+
+def _bgzf_wrap(payload):
+    """`payload` as a BGZF file: members of at most 0xff00 payload bytes, then the 28-byte EOF block (SAM specification 4.1)."""
+    import struct
+    import zlib
+    out = []
+    for at in range(0, len(payload), _BGZF_PIECE):
+        piece = payload[at:at + _BGZF_PIECE]
+        co = zlib.compressobj(6, zlib.DEFLATED, -15)
+        body = co.compress(piece) + co.flush()
+        out.append(b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0BC\x02\0" + struct.pack("<H", len(body) + 25) + body +
+                   struct.pack("<II", zlib.crc32(piece) & 0xffffffff, len(piece)))
+    out.append(_BGZF_EOF)
+    return b"".join(out)
+
+
+def _bgzf_unwrap(data):
+    """The payload of the BGZF file `data`, member by member; ``ValueError`` for a damaged member or one that is cut off.
+    A file of whole members without the end-of-file block is read as it is, as htslib and the native reader do."""
+    import struct
+    import zlib
+    o, out = 0, []
+    try:
+        while o < len(data):
+            if len(data) - o < 18 or data[o:o + 4] != b"\x1f\x8b\x08\x04":
+                raise ValueError("truncated CSI index (bad BGZF member header)")
+            xlen, = struct.unpack_from("<H", data, o + 10)
+            bsize, x = -1, o + 12
+            while x + 4 <= o + 12 + xlen <= len(data):
+                slen, = struct.unpack_from("<H", data, x + 2)
+                if data[x:x + 2] == b"BC" and slen == 2 and x + 6 <= len(data):
+                    bsize, = struct.unpack_from("<H", data, x + 4)
+                x += 4 + slen
+            if bsize < 0 or bsize + 1 < 12 + xlen + 8 or o + bsize + 1 > len(data):
+                raise ValueError("truncated CSI index (BGZF member)")
+            crc, isize = struct.unpack_from("<II", data, o + bsize + 1 - 8)
+            piece = zlib.decompressobj(-15).decompress(data[o + 12 + xlen:o + bsize + 1 - 8])
+            if len(piece) != isize or zlib.crc32(piece) & 0xffffffff != crc:
+                raise ValueError("damaged CSI index (BGZF member)")
+            out.append(piece)
+            o += bsize + 1
+    except zlib.error:
+        raise ValueError("damaged CSI index (BGZF member)")
+    return b"".join(out)
+
+
 class BamIndex(object):
-    """A BAI index (SAM specification 5.2), parsed: what ``samtools index`` writes and :func:`build_index` builds.
+    """A BAI or CSI index (SAM specification 5.2, 5.3), parsed: what ``samtools index [-c]`` writes and :func:`build_index` builds.
 
     ``bins``: per reference, a dict from bin number to a ``uint64 [k, 2]`` array of chunks ``[begin, end)`` (virtual
-    offsets); ``linear``: per reference, the ``uint64`` offsets of its 16 kb windows; ``meta``: per reference, ``None`` or
-    ``(file begin, file end, mapped, unmapped)`` from samtools' pseudo-bin 37450; ``n_no_coor``: the records without a
-    reference; ``mapped``: the sum of the per-reference mapped counts (pysam's ``AlignmentFile.mapped``), -1 when the
-    index carries none.  Two indexes are equal when their parsed content is: the order of the bins in the file is not part of it
-    (htslib writes them in the order of its hash table; :meth:`to_bytes` writes them ascending, 37450 last)."""
+    offsets); ``linear``: per reference, the ``uint64`` offsets of its 16 kb windows (BAI; empty arrays for a CSI);
+    ``meta``: per reference, ``None`` or ``(file begin, file end, mapped, unmapped)`` from samtools' pseudo-bin
+    (``meta_bin``: 37450 for a BAI); ``n_no_coor``: the records without a reference; ``mapped``: the sum of the per-reference
+    mapped counts (pysam's ``AlignmentFile.mapped``), -1 when the index carries none.
+    ``fmt``: ``"bai"`` or ``"csi"``; ``min_shift``, ``depth``: the shape -- leaves of ``2**min_shift`` positions, ``depth``
+    levels below the root, (14, 5) for a BAI; ``loff``: per reference, a dict from bin number to the offset of the bin's
+    first window (CSI; empty dicts for a BAI).
+    Two indexes are equal when their parsed content is: the order of the bins in the file is not part of it
+    (htslib writes them in the order of its hash table; :meth:`to_bytes` writes them ascending, the pseudo-bin last)."""
 
     META_BIN = 37450
 
-    def __init__(self, bins, linear, meta, n_no_coor=0):
+    def __init__(self, bins, linear, meta, n_no_coor=0, fmt="bai", min_shift=14, depth=5, loff=None):
         self.bins, self.linear, self.meta, self.n_no_coor = bins, linear, meta, int(n_no_coor)
+        if fmt not in ("bai", "csi"):
+            raise ValueError("fmt must be 'bai' or 'csi'")
+        self.fmt, self.min_shift, self.depth = fmt, int(min_shift), int(depth)
+        self.loff = loff if loff is not None else [{} for _ in bins]
 
     @property
     def n_ref(self):
         return len(self.bins)
+
+    @property
+    def meta_bin(self):
+        return ((1 << (3 * self.depth + 3)) - 1) // 7 + 1
 
     @property
     def mapped(self):
@@ -134,62 +195,101 @@ class BamIndex(object):
 
     @classmethod
     def from_bytes(cls, data):
+        """Parse a BAI file, the payload of a CSI file, or a CSI file as it lies on disk (BGZF)."""
         import struct
         data = bytes(data)
-        if len(data) < 8 or data[:4] != b"BAI\x01":
+        if data[:2] == b"\x1f\x8b":
+            data = _bgzf_unwrap(data)
+            if data[:4] != b"CSI\x01":
+                raise ValueError("not a CSI index")
+        csi = data[:4] == b"CSI\x01"
+        if csi:
+            if len(data) < 20:
+                raise ValueError("truncated CSI index")
+            min_shift, depth, l_aux = struct.unpack_from("<iii", data, 4)
+            if not (1 <= min_shift <= 30 and 0 <= depth <= 9 and min_shift + 3 * depth <= 40):
+                raise ValueError("corrupt CSI index (min_shift / depth)")
+            if l_aux < 0 or 16 + l_aux + 4 > len(data):
+                raise ValueError("truncated CSI index")
+            o = 16 + l_aux
+            meta_bin = ((1 << (3 * depth + 3)) - 1) // 7 + 1
+        elif len(data) >= 8 and data[:4] == b"BAI\x01":
+            o, min_shift, depth, meta_bin = 4, 14, 5, cls.META_BIN
+        else:
             raise ValueError("not a BAI index")
-        n_ref, = struct.unpack_from("<i", data, 4)
-        o = 8
-        bins, linear, meta = [], [], []
+        kind = "CSI" if csi else "BAI"
+        head = 16 if csi else 8
+        n_ref, = struct.unpack_from("<i", data, o)
+        o += 4
+        bins, linear, meta, loffs = [], [], [], []
         try:
             for _ in range(n_ref):
                 n_bin, = struct.unpack_from("<i", data, o)
                 o += 4
-                rb, rm = {}, None
+                if n_bin < 0 or o + head * n_bin > len(data):
+                    raise struct.error("bins")
+                rb, rm, rl = {}, None, {}
                 for _ in range(n_bin):
-                    b, nc = struct.unpack_from("<Ii", data, o)
-                    o += 8
+                    if csi:
+                        b, lo, nc = struct.unpack_from("<IQi", data, o)
+                    else:
+                        (b, nc), lo = struct.unpack_from("<Ii", data, o), 0
+                    o += head
                     if nc < 0 or o + 16 * nc > len(data):
                         raise struct.error("chunks")
                     ch = np.frombuffer(data, "<u8", 2 * nc, o).reshape(nc, 2).copy()
                     o += 16 * nc
-                    if b == cls.META_BIN and nc >= 2:
+                    if b == meta_bin and nc >= 2:
                         rm = tuple(int(x) for x in ch[:2].ravel())
-                    elif b != cls.META_BIN:
+                    elif b != meta_bin:
                         rb[int(b)] = ch
-                n_intv, = struct.unpack_from("<i", data, o)
-                o += 4
-                if n_intv < 0 or o + 8 * n_intv > len(data):
-                    raise struct.error("linear")
-                linear.append(np.frombuffer(data, "<u8", n_intv, o).copy())
-                o += 8 * n_intv
+                        if csi:
+                            rl[int(b)] = int(lo)
+                if csi:
+                    linear.append(np.zeros(0, np.uint64))
+                else:
+                    n_intv, = struct.unpack_from("<i", data, o)
+                    o += 4
+                    if n_intv < 0 or o + 8 * n_intv > len(data):
+                        raise struct.error("linear")
+                    linear.append(np.frombuffer(data, "<u8", n_intv, o).copy())
+                    o += 8 * n_intv
                 bins.append(rb)
                 meta.append(rm)
+                loffs.append(rl)
             n_no_coor = struct.unpack_from("<Q", data, o)[0] if o + 8 <= len(data) else 0   # (optional in the format)
         except struct.error:
-            raise ValueError("truncated BAI index")
-        return cls(bins, linear, meta, n_no_coor)
+            raise ValueError("truncated %s index" % kind)
+        return cls(bins, linear, meta, n_no_coor, "csi" if csi else "bai", min_shift, depth, loffs)
 
     @classmethod
     def from_file(cls, path):
         with open(path, "rb") as fh:
             return cls.from_bytes(fh.read())
 
-    def to_bytes(self):
+    def payload(self):
+        """The index serialised without compression: the BAI file, or what the BGZF members of the CSI file hold."""
         import struct
-        out = [b"BAI\x01", struct.pack("<i", self.n_ref)]
-        for rb, lin, rm in zip(self.bins, self.linear, self.meta):
+        csi = self.fmt == "csi"
+        out = [b"CSI\x01" + struct.pack("<iii", self.min_shift, self.depth, 0) if csi else b"BAI\x01", struct.pack("<i", self.n_ref)]
+        for rb, lin, rm, rl in zip(self.bins, self.linear, self.meta, self.loff):
             out.append(struct.pack("<i", len(rb) + (rm is not None)))
             for b in sorted(rb):
                 ch = np.ascontiguousarray(rb[b], "<u8")
-                out.append(struct.pack("<Ii", b, len(ch)))
+                out.append(struct.pack("<IQi", b, rl.get(b, 0), len(ch)) if csi else struct.pack("<Ii", b, len(ch)))
                 out.append(ch.tobytes())
             if rm is not None:
-                out.append(struct.pack("<Ii4Q", self.META_BIN, 2, *rm))
-            out.append(struct.pack("<i", len(lin)))
-            out.append(np.ascontiguousarray(lin, "<u8").tobytes())
+                out.append(struct.pack("<IQi4Q", self.meta_bin, 0, 2, *rm) if csi else struct.pack("<Ii4Q", self.meta_bin, 2, *rm))
+            if not csi:
+                out.append(struct.pack("<i", len(lin)))
+                out.append(np.ascontiguousarray(lin, "<u8").tobytes())
         out.append(struct.pack("<Q", self.n_no_coor))
         return b"".join(out)
+
+    def to_bytes(self):
+        """The bytes of the index FILE: a BAI as it is, a CSI in BGZF members with the end-of-file block."""
+        data = self.payload()
+        return _bgzf_wrap(data) if self.fmt == "csi" else data
 
     def write(self, path):
         with open(path, "wb") as fh:
@@ -199,6 +299,8 @@ class BamIndex(object):
         if not isinstance(other, BamIndex):
             return NotImplemented
         if self.n_ref != other.n_ref or self.n_no_coor != other.n_no_coor or list(self.meta) != list(other.meta):
+            return False
+        if (self.fmt, self.min_shift, self.depth) != (other.fmt, other.min_shift, other.depth) or list(self.loff) != list(other.loff):
             return False
         for a, b, la, lb in zip(self.bins, other.bins, self.linear, other.linear):
             if sorted(a) != sorted(b) or not np.array_equal(la, lb) or any(not np.array_equal(a[k], b[k]) for k in a):
@@ -212,35 +314,48 @@ class BamIndex(object):
     __hash__ = None
 
     def __repr__(self):
-        return "BamIndex(%d references, %d bins, %d chunks, n_no_coor=%d, mapped=%d)" % (
-            self.n_ref, sum(len(b) for b in self.bins), sum(len(c) for b in self.bins for c in b.values()), self.n_no_coor, self.mapped)
+        shape = "" if self.fmt == "bai" else "CSI min_shift=%d depth=%d, " % (self.min_shift, self.depth)
+        return "BamIndex(%s%d references, %d bins, %d chunks, n_no_coor=%d, mapped=%d)" % (
+            shape, self.n_ref, sum(len(b) for b in self.bins), sum(len(c) for b in self.bins for c in b.values()), self.n_no_coor, self.mapped)
 
 
 def find_index(path):
-    """The index file the region reads find beside `path` (``path + ".bai"``, then ``.bai`` in place of the extension), or ``None``."""
+    """The index file the region reads find beside `path`, or ``None``: ``path + ".bai"``, ``.bai`` in place of the
+    extension, then ``path + ".csi"`` and ``.csi`` in place of the extension."""
     path = os.fspath(path)
-    for cand in (path + ".bai", path[:-4] + ".bai" if len(path) > 4 else None):
+    stem = path[:-4] if len(path) > 4 else None
+    for cand in (path + ".bai", stem + ".bai" if stem else None, path + ".csi", stem + ".csi" if stem else None):
         if cand and os.path.isfile(cand):
             return cand
     return None
 
 
-def build_index(path, engine=None, out=None, overwrite=False, timing=None):
-    """Build the BAI index of the coordinate-sorted BAM file `path` ON THE GPU (``pc_bam_index_build``) -- what
-    ``samtools index`` / ``pysam.index`` do -- write it to `out` (default ``path + ".bai"``) and return it as a
-    :class:`BamIndex`.  The file goes through the decoder of :func:`read_bam_gpu` up to the record fields (a file that
-    decoder refuses is refused here with the same message); the bins, runs, linear windows and counts are taken from the
-    records in HBM, and the host finishes the index.  `engine`: a :class:`plastid_amd.engine.Engine` (default: the shared
-    one of device 0).  The file is written under a temporary name and renamed; an existing `out` is only replaced with
-    ``overwrite=True``.  `timing`: optional dict that receives the laps in ms (``upload_ms``, ``inflate_ms``, ``chain_ms``,
-    ``fields_ms``, ``index_ms``, ``readback_ms``, ``finish_ms``, ``total_ms``) and the counts (``records``, ``placed``,
-    ``runs``, ``chunks``, ``bins``, ``linear``, ``n_no_coor``, ``mapped``, ``index_bytes``).
-    ``ValueError``: a reference longer than 2^29 or an alignment that reaches beyond it (BAI cannot hold them)."""
+def build_index(path, engine=None, out=None, overwrite=False, timing=None, fmt="bai", min_shift=14):
+    """Build the index of the coordinate-sorted BAM file `path` ON THE GPU (``pc_bam_index_build`` /
+    ``pc_bam_index_build_csi``) -- what ``samtools index [-c]`` / ``pysam.index`` do -- write it to `out` (default
+    ``path + ".bai"``, or ``path + ".csi"``) and return it as a :class:`BamIndex`.  The file goes through the decoder of
+    :func:`read_bam_gpu` up to the record fields (a file that decoder refuses is refused here with the same message); the
+    bins, runs, linear windows and counts are taken from the records in HBM, and the host finishes the index.
+    `fmt`: ``"bai"``, or ``"csi"`` -- the index for references longer than 2^29: leaves of ``2**min_shift`` positions
+    (8 .. 30) and the depth the longest reference asks for, as htslib's ``sam_index_build(fn, min_shift)``; its windows
+    stay on the GPU (at most 2^28 of them: a larger `min_shift` has fewer), and the file is the payload in BGZF members.
+    `engine`: a :class:`plastid_amd.engine.Engine` (default: the shared one of device 0).  The file is written under a
+    temporary name and renamed; an existing `out` is only replaced with ``overwrite=True``.  `timing`: optional dict that
+    receives the laps in ms (``upload_ms``, ``inflate_ms``, ``chain_ms``, ``fields_ms``, ``index_ms``, ``readback_ms``,
+    ``finish_ms``, ``total_ms``), the counts (``records``, ``placed``, ``runs``, ``chunks``, ``bins``, ``linear``,
+    ``n_no_coor``, ``mapped``, ``index_bytes``) and the shape (``min_shift``, ``depth``).
+    ``ValueError``: for a BAI, a reference longer than 2^29 or an alignment that reaches beyond it (BAI cannot hold them)
+    and a `min_shift` other than 14; for a CSI, a `min_shift` out of range, an alignment beyond the index's reach, too many windows."""
     from . import _lib as clib
+    if fmt not in ("bai", "csi"):
+        raise ValueError("fmt must be 'bai' or 'csi', not %r" % (fmt,))
+    min_shift = int(min_shift)
+    if fmt == "bai" and min_shift != 14:
+        raise ValueError("a BAI index has min_shift 14; pass fmt='csi' for another leaf size")
     path = os.fspath(path)
     if not os.path.isfile(path):
         raise IOError("No such file: %r" % (path,))
-    dest = os.fspath(out) if out is not None else path + ".bai"
+    dest = os.fspath(out) if out is not None else path + "." + fmt
     if os.path.exists(dest) and not overwrite:
         raise FileExistsError("%s exists; pass overwrite=True to replace it" % dest)
     if engine is None:
@@ -248,7 +363,10 @@ def build_index(path, engine=None, out=None, overwrite=False, timing=None):
         engine = default_engine()
     L = clib.load()
     h = ctypes.c_void_p()
-    clib.check(L.pc_bam_index_build(engine._h, os.fsencode(path), ctypes.byref(h)))
+    if fmt == "csi":
+        clib.check(L.pc_bam_index_build_csi(engine._h, os.fsencode(path), min_shift, ctypes.byref(h)))
+    else:
+        clib.check(L.pc_bam_index_build(engine._h, os.fsencode(path), ctypes.byref(h)))
     try:
         data = _index_bytes(L, h)
         if timing is not None:
@@ -257,9 +375,13 @@ def build_index(path, engine=None, out=None, overwrite=False, timing=None):
             clib.check(L.pc_bam_index_stats(h, st.ctypes.data_as(ctypes.c_void_p)))
             timing.update(zip(("upload_ms", "inflate_ms", "chain_ms", "fields_ms", "index_ms", "readback_ms", "finish_ms", "total_ms"), ms.tolist()))
             timing.update(zip(("records", "placed", "runs", "chunks", "bins", "linear", "n_no_coor", "mapped"), st.tolist()))
-            timing["index_bytes"] = len(data)
     finally:
         L.pc_bam_index_close(h)
+    idx = BamIndex.from_bytes(data)
+    if fmt == "csi":
+        data = _bgzf_wrap(data)   # (the library hands the payload over: it does not link zlib)
+    if timing is not None:
+        timing.update(index_bytes=len(data), min_shift=idx.min_shift, depth=idx.depth)
     tmp = "%s.tmp%d" % (dest, os.getpid())
     try:
         with open(tmp, "wb") as fh:
@@ -270,7 +392,7 @@ def build_index(path, engine=None, out=None, overwrite=False, timing=None):
     finally:
         if os.path.exists(tmp):
             os.remove(tmp)
-    return BamIndex.from_bytes(data)
+    return idx
 
 
 def _index_bytes(L, h):
@@ -284,12 +406,13 @@ def _index_bytes(L, h):
 
 def _index_path(path, index, engine=None):
     """The `index` keyword of the region reads: ``None`` -> ``None`` (the lookup beside the file, and its error); a path ->
-    that file; ``"build"`` -> the index beside the file, built first (:func:`build_index`) when there is none."""
+    that file; ``"build"`` / ``"build-csi"`` -> the index beside the file, built first (:func:`build_index`, as a BAI / as
+    a CSI of min_shift 14) when there is none."""
     if index is None:
         return None
-    if isinstance(index, str) and index == "build":
+    if isinstance(index, str) and index in ("build", "build-csi"):
         if find_index(path) is None:
-            build_index(path, engine=engine)
+            build_index(path, engine=engine, fmt="csi" if index == "build-csi" else "bai")
         return None
     return os.fspath(index)
 
@@ -302,16 +425,16 @@ def _pb_open(L, path, index_path):
 
 
 def resolve_regions(path, regions, index=None):
-    """Resolve `regions` (``(chrom, start, end)`` or |GenomicSegments|) through the BAI index of `path` for a decoder
+    """Resolve `regions` (``(chrom, start, end)`` or |GenomicSegments|) through the BAI or CSI index of `path` for a decoder
     that reads the file itself (:func:`read_bam_gpu`, :meth:`Engine.add_bam`): returns a dict with the merged index
     chunks of the regions, ``chunks`` (``uint64 [k, 2]``: ``[voff_beg, voff_end)`` pairs of virtual offsets, ascending and
     disjoint; bins + 16 kb linear index, SAM specification section 5 -- what ``AlignmentFile.fetch`` walks per region,
     genome_array.py:800-809), the span ``voff_begin``, ``voff_end`` that holds them all (0, 0: no chunk), the merged
     regions by reference id (``tid``, ``beg``, ``end`` arrays), the index's whole-file ``mapped`` count (-1: none) and the
     file's ``references`` / ``lengths``.
-    `index`: ``None`` -- the index beside the file (``path + ".bai"`` or ``.bai`` in place of ``.bam``); a path -- that index
-    file (a BAM file in a read-only directory); ``"build"`` -- the index beside the file, built on the GPU first when there
-    is none (:func:`build_index`)."""
+    `index`: ``None`` -- the index beside the file (``path + ".bai"``, ``.bai`` in place of ``.bam``, then the same with ``.csi``); a path -- that index
+    file (a BAM file in a read-only directory), BAI or CSI; ``"build"`` -- the index beside the file, built on the GPU
+    first when there is none (:func:`build_index`); ``"build-csi"`` -- the same, built as a CSI (references beyond 2^29)."""
     L = _load()
     h = _pb_open(L, path, _index_path(path, index))
     try:
@@ -356,7 +479,7 @@ def read_bam_gpu(path, engine, timing=None, regions=None, index=None):
     BGZF members the index chunks of the regions point to (and the leading ones with the header) are uploaded and
     inflated (``pc_bam_open_chunks``; the overlap test then drops the records of those members that no region wants);
     ``mapped`` is then the index's whole-file count, as pysam's.
-    `index` (with `regions`): as for :func:`resolve_regions` -- an index file elsewhere, or ``"build"``."""
+    `index` (with `regions`): as for :func:`resolve_regions` -- an index file elsewhere, ``"build"`` or ``"build-csi"``."""
     import time
     from . import _lib as clib
     L = clib.load()
@@ -426,11 +549,11 @@ def read_bam(path, threads=0, regions=None, index=None):
 
     `regions`: iterable of ``(chrom, start, end)`` (0-based, half-open) or objects with those
     attributes (|GenomicSegments|): only the alignments that overlap one of them are read, through
-    the file's BAI index (``path + ".bai"`` or ``.bai`` in place of ``.bam``) -- what the reference
+    the file's BAI or CSI index (``path + ".bai"``, ``.bai`` in place of ``.bam``, then ``.csi`` likewise) -- what the reference
     does region by region with ``AlignmentFile.fetch`` (genome_array.py:800-809), here for a whole
     query set at once.  Counts over positions inside the regions equal those of the whole file.
-    `index` (with `regions`): ``None`` -- the index beside the file; a path -- that index file; ``"build"`` -- build the
-    index on the GPU first when there is none (:func:`build_index`).
+    `index` (with `regions`): ``None`` -- the index beside the file (BAI or CSI); a path -- that index file; ``"build"`` --
+    build the index on the GPU first when there is none (:func:`build_index`); ``"build-csi"`` -- build it as a CSI.
 
     ``mapped`` is the number of records with flag 0x4 unset (what ``pysam
     AlignmentFile.mapped`` reports from the index); unplaced reads are not staged

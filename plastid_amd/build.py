@@ -32,12 +32,13 @@ def find_hipcc():
 
 
 BAM_SRC = os.path.join(HERE, "csrc", "bam_stager.cpp")
+BAM_HDRS = [os.path.join(HERE, "csrc", "index_shape.h")]   # what bam_stager.cpp includes of csrc/
 BAM_LIB = os.path.join(HERE, "libplastid_bam.so")
 
 
 def build_bam_library(force=False, verbose=False):
     """Compile the native BAM -> packed-array stager (host C++, zlib; no GPU code)."""
-    if not force and os.path.exists(BAM_LIB) and os.path.getmtime(BAM_LIB) >= os.path.getmtime(BAM_SRC):
+    if not force and os.path.exists(BAM_LIB) and os.path.getmtime(BAM_LIB) >= max(os.path.getmtime(f) for f in [BAM_SRC] + BAM_HDRS):
         return BAM_LIB
     cxx = shutil.which("g++") or shutil.which("c++") or find_hipcc()
     cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall", BAM_SRC, "-o", BAM_LIB, "-lz", "-ldl"]

@@ -1,6 +1,6 @@
 // Compressed BAM on the GPU, host side: the entry points of include/plastid_counts.h that decode a BAM file with the
 // kernels of bam_kernels.hip.h.  One open is five phases (bam_open_impl): plan_members, upload_and_inflate, read_header,
-// chain_records, decode_columns.  The BAI index build (bam_index_impl) runs the first four and index_records in place of the fifth.  Part of the one translation unit of plastid_counts.hip.
+// chain_records, decode_columns.  The index build (bam_index_impl: BAI or CSI) runs the first four and index_records in place of the fifth.  Part of the one translation unit of plastid_counts.hip.
 #include "bam_kernels.hip.h"
 #include "index_kernels.hip.h"
 #include "bam_index.h"
@@ -781,20 +781,22 @@ int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const B
     return PC_OK;
 }
 
-// What index_records brings down for pc_bam_index_finish.
+using pcshape::IndexShape;   // the index to build: BAI (min_shift 14, 5 levels), or a CSI of the given shape
+
+// What index_records brings down for pc_bam_index_finish / pc_bam_index_finish_csi.
 struct IndexParts {
     std::vector<int32_t> run_tid;
     std::vector<uint32_t> run_bin;
-    std::vector<uint64_t> run_beg, run_end, linear, ref_beg, ref_end;
+    std::vector<uint64_t> run_beg, run_end, run_loff, linear, ref_beg, ref_end;   // linear: BAI only; run_loff: CSI only
     std::vector<int64_t> lin_start, ref_mapped, ref_unmapped;
-    int64_t n_no_coor = 0;
+    int64_t n_no_coor = 0, n_windows = 0;
     double ms_fields = 0, ms_kernels = 0, ms_readback = 0;   // wall clock between the phase's synchronisations
 };
 
 // The index build's phase 5 (whole-file reads only): k_bam_fields and the order checks as decode_columns runs them -- no
-// column is written or read back -- then the kernels of index_kernels.hip.h; the sorted runs, the linear arrays and the
-// per-reference counts come down.
-int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader &h, const BamRecords &recs, IndexParts &out) {
+// column is written or read back -- then the kernels of index_kernels.hip.h; the sorted runs, the linear arrays (BAI) or
+// the runs' loff (CSI: the windows stay in HBM) and the per-reference counts come down.
+int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader &h, const BamRecords &recs, const IndexShape &shape, IndexParts &out) {
     using namespace pcbam;
     using namespace pcidx;
     hipStream_t st = d.st;
@@ -858,8 +860,9 @@ int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader
     if (recs.truncated) return fail(PC_ERR_ARG, "truncated BAM record");
     const auto t1 = std::chrono::steady_clock::now();
     // ---- keys, runs, per-reference bounds, covered windows
-    hipLaunchKernelGGL(k_idx_keys, dim3(g256p), dim3(256), 0, st, d.d_stream.p, d.d_members.p, d_blk.p, d_rec_base.p, d.d_rec_off.p, nm, nrec, d_rec_member.p,
-                       d_recs.p, d_key.p, d_voff.p, d_win_a.p, d_cov.p, d_mapped.p, (uint32_t *)(d_misc.p + 1));
+    const auto idx_keys = shape.csi ? k_idx_keys<false> : k_idx_keys<true>;
+    hipLaunchKernelGGL(idx_keys, dim3(g256p), dim3(256), 0, st, d.d_stream.p, d.d_members.p, d_blk.p, d_rec_base.p, d.d_rec_off.p, nm, nrec, d_rec_member.p,
+                       d_recs.p, d_key.p, d_voff.p, d_win_a.p, d_cov.p, d_mapped.p, (uint32_t *)(d_misc.p + 1), shape.min_shift, shape.n_lvls);
     HIP_TRY(hipMemsetAsync(d_ref_fl.p, 0xff, 2 * nr * sizeof(int64_t), st));
     hipLaunchKernelGGL(k_idx_heads, dim3(g256p), dim3(256), 0, st, d_key.p, nrec, d_head.p, d_ref_fl.p, d_ref_fl.p + nr);
     HIP_TRY(hipGetLastError());
@@ -897,7 +900,11 @@ int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader
     HIP_TRY(hipMemcpyAsync(&n_runs32, d_slot.p + nrec, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(misc, d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if ((uint32_t)misc[1]) return fail(PC_ERR_ARG, "a BAI index cannot hold %s: an alignment reaches beyond 2^29", d.path.c_str());
+    if ((uint32_t)misc[1]) {
+        if (!shape.csi) return fail(PC_ERR_ARG, "a BAI index cannot hold %s: an alignment reaches beyond 2^29", d.path.c_str());
+        return fail(PC_ERR_ARG, "a CSI index of min_shift %d and depth %d cannot hold %s: an alignment reaches beyond %lld", shape.min_shift, shape.n_lvls,
+                    d.path.c_str(), (long long)shape.reach());
+    }
     int64_t placed = 0;
     for (int t = 0; t < n_ref; ++t) {
         out.lin_start[(size_t)t + 1] = out.lin_start[(size_t)t] + n_intv[(size_t)t];
@@ -905,8 +912,12 @@ int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader
     }
     out.n_no_coor = nrec - placed;
     const int64_t n_runs = (int64_t)n_runs32, n_lin = out.lin_start[(size_t)n_ref];
+    out.n_windows = n_lin;
+    if (shape.csi && n_lin > kMaxWindows)
+        return fail(PC_ERR_ARG, "a CSI index of min_shift %d of %s has %lld windows, more than 2^28: use a larger min_shift", shape.min_shift, d.path.c_str(),
+                    (long long)n_lin);
     // ---- the runs in (tid, bin) order, the linear windows
-    DevBuf<uint64_t> d_run_key, d_run_key2, d_run_beg, d_run_end, d_sbeg, d_send, d_linear;
+    DevBuf<uint64_t> d_run_key, d_run_key2, d_run_beg, d_run_end, d_sbeg, d_send, d_linear, d_filled, d_sloff;
     DevBuf<uint32_t> d_order, d_order2, d_sbin;
     DevBuf<int32_t> d_stid;
     DevBuf<int64_t> d_lin_base;
@@ -914,10 +925,12 @@ int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader
     room(rc, d_run_key, nrun); room(rc, d_run_key2, nrun); room(rc, d_run_beg, nrun); room(rc, d_run_end, nrun); room(rc, d_sbeg, nrun); room(rc, d_send, nrun);
     room(rc, d_order, nrun); room(rc, d_order2, nrun); room(rc, d_sbin, nrun); room(rc, d_stid, nrun);
     room(rc, d_linear, (size_t)std::max<int64_t>(n_lin, 1));
+    if (shape.csi) { room(rc, d_filled, (size_t)std::max<int64_t>(n_lin, 1)); room(rc, d_sloff, nrun); }
     if (rc == PC_OK) rc = d_lin_base.upload(out.lin_start, st);
     if (rc != PC_OK) return rc;
     out.run_tid.resize((size_t)n_runs); out.run_bin.resize((size_t)n_runs); out.run_beg.resize((size_t)n_runs); out.run_end.resize((size_t)n_runs);
-    out.linear.resize((size_t)n_lin);
+    if (shape.csi) out.run_loff.resize((size_t)n_runs);
+    else out.linear.resize((size_t)n_lin);
     if (n_runs) {
         hipLaunchKernelGGL(k_idx_runs, dim3(g256p), dim3(256), 0, st, d_key.p, d_voff.p, d_head.p, d_slot.p, nrec, d_run_key.p, d_run_beg.p, d_run_end.p);
         // (hipcub's iota: the slots 0 .. n_runs - 1 are the values of the sort)
@@ -942,6 +955,21 @@ int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader
         hipLaunchKernelGGL(k_idx_linear, dim3(g256), dim3(256), 0, st, d_cov.p, d_covered.p, d_win_a.p, d_voff.p, nrec, d_lin_base.p, d_linear.p);
         HIP_TRY(hipGetLastError());
     }
+    DevBuf<uint8_t> d_fill_tmp;   // (the scan's scratch: alive up to the synchronisation below)
+    if (shape.csi && n_runs) {   // the forward fill (one running maximum over the windows of all references), then loff per run
+        if (n_lin) {
+            hipLaunchKernelGGL(k_idx_first_window, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), 0, st, n_ref, d_n_intv.p, d_lin_base.p, d_ref_be.p, d_linear.p);
+            HIP_TRY(hipGetLastError());
+            size_t fill_bytes = 0;
+            HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, fill_bytes, d_linear.p, d_filled.p, hipcub::Max(), (int)n_lin, st));
+            rc = d_fill_tmp.reserve(std::max<size_t>(fill_bytes, 16));
+            if (rc != PC_OK) { (void)hipStreamSynchronize(st); return rc; }
+            HIP_TRY(hipcub::DeviceScan::InclusiveScan(d_fill_tmp.p, fill_bytes, d_linear.p, d_filled.p, hipcub::Max(), (int)n_lin, st));
+        }
+        hipLaunchKernelGGL(k_idx_loff, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, d_stid.p, d_sbin.p, n_runs, shape.n_lvls, d_n_intv.p,
+                           d_lin_base.p, d_filled.p, d_sloff.p);
+        HIP_TRY(hipGetLastError());
+    }
     HIP_TRY(hipStreamSynchronize(st));
     out.ms_kernels = ms_since(t1);
     const auto t2 = std::chrono::steady_clock::now();
@@ -951,7 +979,8 @@ int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader
         HIP_TRY(hipMemcpyAsync(out.run_beg.data(), d_sbeg.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(out.run_end.data(), d_send.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
     }
-    if (n_lin) HIP_TRY(hipMemcpyAsync(out.linear.data(), d_linear.p, (size_t)n_lin * 8, hipMemcpyDeviceToHost, st));
+    if (shape.csi) { if (n_runs) HIP_TRY(hipMemcpyAsync(out.run_loff.data(), d_sloff.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st)); }
+    else if (n_lin) HIP_TRY(hipMemcpyAsync(out.linear.data(), d_linear.p, (size_t)n_lin * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     out.ms_readback = ms_since(t2);
     d.clk.lap("fields + index kernels + read-back");
@@ -999,7 +1028,9 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
 }
 
 // The index build: phases 1 - 4 of a whole-file open, index_records, pc_bam_index_finish.
-static int bam_index_impl(pc_engine *e, const void *image_, int64_t size, const char *name, pc_bam_index **out, const UploadedHook *uploaded, const BamKnobs &knobs) {
+// min_shift 0: a BAI; otherwise the CSI with leaves of 2^min_shift positions (its range is the caller's check) and the depth the header asks for.
+static int bam_index_impl(pc_engine *e, const void *image_, int64_t size, const char *name, pc_bam_index **out, const UploadedHook *uploaded, const BamKnobs &knobs,
+                          int min_shift = 0) {
     if (!e || !out || size < 0 || (size > 0 && !image_)) return fail(PC_ERR_ARG, "pc_bam_index_build: bad arguments");
     *out = nullptr;
     const auto t_0 = std::chrono::steady_clock::now();
@@ -1022,18 +1053,32 @@ static int bam_index_impl(pc_engine *e, const void *image_, int64_t size, const 
     rc = chain_records(d, pl, nullptr, h, recs);
     if (rc != PC_OK) return rc;
     if (recs.nrec >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_bam_index_build: more than 2^31-2 records per file are not supported");
+    IndexShape shape;
+    if (min_shift) {   // the depth as htslib takes it from the header (sam.c:478-482)
+        int64_t max_len = 0;
+        for (size_t t = 0; t < h.ref_lengths.size(); ++t) max_len = std::max<int64_t>(max_len, (int64_t)(uint32_t)h.ref_lengths[t]);
+        max_len += 256;
+        shape.csi = true; shape.min_shift = min_shift; shape.n_lvls = 0;
+        while (max_len > shape.reach()) ++shape.n_lvls;
+    }
     IndexParts parts;
-    rc = index_records(d, pl, size, h, recs, parts);
+    rc = index_records(d, pl, size, h, recs, shape, parts);
     if (rc != PC_OK) return rc;
-    for (size_t t = 0; t < h.ref_lengths.size(); ++t)   // (behind the decoder's own refusals)
-        if ((int64_t)h.ref_lengths[t] > pcidx::kBaiReach || h.ref_lengths[t] < 0)
-            return fail(PC_ERR_ARG, "a BAI index cannot hold %s: reference %s is longer than 2^29", d.path.c_str(), h.ref_names[t].c_str());
+    if (!shape.csi)
+        for (size_t t = 0; t < h.ref_lengths.size(); ++t)   // (behind the decoder's own refusals)
+            if ((int64_t)h.ref_lengths[t] > pcidx::kBaiReach || h.ref_lengths[t] < 0)
+                return fail(PC_ERR_ARG, "a BAI index cannot hold %s: reference %s is longer than 2^29", d.path.c_str(), h.ref_names[t].c_str());
     const auto t_f = std::chrono::steady_clock::now();
     pc_bam_index *idx = nullptr;
-    rc = pc_bam_index_finish((int)h.n_ref, (int64_t)parts.run_tid.size(), parts.run_tid.data(), parts.run_bin.data(), parts.run_beg.data(), parts.run_end.data(),
+    if (shape.csi)
+        rc = pc_bam_index_finish_csi(shape.min_shift, shape.n_lvls, (int)h.n_ref, (int64_t)parts.run_tid.size(), parts.run_tid.data(), parts.run_bin.data(),
+                                     parts.run_beg.data(), parts.run_end.data(), parts.run_loff.data(), parts.ref_beg.data(), parts.ref_end.data(),
+                                     parts.ref_mapped.data(), parts.ref_unmapped.data(), parts.n_no_coor, &idx);
+    else rc = pc_bam_index_finish((int)h.n_ref, (int64_t)parts.run_tid.size(), parts.run_tid.data(), parts.run_bin.data(), parts.run_beg.data(), parts.run_end.data(),
                              parts.lin_start.data(), parts.linear.data(), parts.ref_beg.data(), parts.ref_end.data(), parts.ref_mapped.data(),
                              parts.ref_unmapped.data(), parts.n_no_coor, &idx);
     if (rc != PC_OK) return rc;
+    if (shape.csi) idx->stats[5] = parts.n_windows;
     const auto t_e = std::chrono::steady_clock::now();
     for (int k = 0; k < 3; ++k) idx->ms[k] = ms_between(d.ev[k], d.ev[k + 1]);
     idx->ms[3] = parts.ms_fields; idx->ms[4] = parts.ms_kernels; idx->ms[5] = parts.ms_readback;
@@ -1358,6 +1403,35 @@ int pc_bam_index_build(pc_engine *e, const char *path, pc_bam_index **out) {
     const int device = e->device;
     const UploadedHook release = [&mf, device](hipStream_t up) { mf.release_behind(up, device); };
     return bam_index_impl(e, mf.p, (int64_t)mf.size, path, out, &release, knobs);
+}
+
+int pc_bam_index_build_csi(pc_engine *e, const char *path, int min_shift, pc_bam_index **out) {
+    if (!e || !path || !out) return fail(PC_ERR_ARG, "pc_bam_index_build_csi: bad arguments");
+    *out = nullptr;
+    if (min_shift < pcidx::kMinShiftLo || min_shift > pcidx::kMinShiftHi)
+        return fail(PC_ERR_ARG, "pc_bam_index_build_csi: min_shift %d is not in %d .. %d", min_shift, pcidx::kMinShiftLo, pcidx::kMinShiftHi);
+    const BamKnobs knobs;
+    MappedFile mf;
+    const int rc = mf.open(path, -1, knobs.touch);
+    if (rc != PC_OK) return rc;
+    const int device = e->device;
+    const UploadedHook release = [&mf, device](hipStream_t up) { mf.release_behind(up, device); };
+    return bam_index_impl(e, mf.p, (int64_t)mf.size, path, out, &release, knobs, min_shift);
+}
+
+int pc_bam_index_finish_csi(int min_shift, int n_lvls, int n_ref, int64_t n_runs, const int32_t *run_tid, const uint32_t *run_bin, const uint64_t *run_beg,
+                            const uint64_t *run_end, const uint64_t *run_loff, const uint64_t *ref_beg, const uint64_t *ref_end, const int64_t *ref_mapped,
+                            const int64_t *ref_unmapped, int64_t n_no_coor, pc_bam_index **out) {
+    if (!out) return fail(PC_ERR_ARG, "pc_bam_index_finish_csi: bad arguments");
+    *out = nullptr;
+    pc_bam_index *idx = new pc_bam_index();
+    const auto t0 = std::chrono::steady_clock::now();
+    const char *msg = pcidxhost::finish_csi(min_shift, n_lvls, n_ref, n_runs, run_tid, run_bin, run_beg, run_end, run_loff, ref_beg, ref_end, ref_mapped,
+                                            ref_unmapped, n_no_coor, *idx);
+    if (msg) { delete idx; return fail(PC_ERR_ARG, "%s", msg); }
+    idx->ms[6] = idx->ms[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    *out = idx;
+    return PC_OK;
 }
 
 int pc_bam_index_finish(int n_ref, int64_t n_runs, const int32_t *run_tid, const uint32_t *run_bin, const uint64_t *run_beg, const uint64_t *run_end,

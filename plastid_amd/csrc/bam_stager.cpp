@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <numeric>
 #include <string>
 #include <chrono>
 #include <mutex>
@@ -30,6 +31,8 @@
 #include <sys/stat.h>
 #include <unistd.h>
 #include <vector>
+
+#include "index_shape.h"
 
 namespace {
 
@@ -897,7 +900,7 @@ int decode(Bam &bam, int nthreads) {
     return 0;
 }
 
-// ---------------------------------------------------------------- region-limited loading (BAI)
+// ---------------------------------------------------------------- region-limited loading (BAI / CSI)
 // The reference fetches per region through the BAM index (genome_array.py:800-809 via pysam; bin /
 // chunk / linear-index scheme of the SAM specification, section 5).  Here the regions of a whole
 // query set are resolved at once: bins -> chunks of virtual offsets, clipped by the linear index,
@@ -908,59 +911,13 @@ int decode(Bam &bam, int nthreads) {
 struct BaiRef {
     std::vector<uint32_t> bin_id;
     std::vector<std::vector<std::pair<uint64_t, uint64_t>>> chunks;
-    std::vector<uint64_t> linear;
+    std::vector<uint64_t> loff;     // CSI: per bin, the offset of its first window (beside bin_id); BAI: empty
+    std::vector<uint64_t> linear;   // BAI only
     uint64_t n_mapped = 0, n_unmapped = 0;
     bool has_meta = false;
 };
 
-int load_bai(const std::string &bam_path, const std::string &index_path, std::vector<BaiRef> &refs) {
-    std::vector<uint8_t> buf;
-    std::string ipath = index_path.empty() ? bam_path + ".bai" : index_path;
-    if (!index_path.empty()) {
-        if (!read_file(ipath, buf)) return fail("cannot read the index of " + bam_path + " (" + ipath + ")");
-    } else if (!read_file(ipath, buf)) {
-        ipath = bam_path.size() > 4 ? bam_path.substr(0, bam_path.size() - 4) + ".bai" : ipath;
-        if (!read_file(ipath, buf)) return fail("cannot read the index of " + bam_path + " (.bam.bai / .bai)");
-    }
-    const uint8_t *p = buf.data(), *end = p + buf.size();
-    auto need = [&](size_t n) { return (size_t)(end - p) >= n; };
-    if (!need(8) || std::memcmp(p, "BAI\1", 4) != 0) return fail("not a BAI index: " + ipath);
-    const uint32_t n_ref = rd32(p + 4);
-    p += 8;
-    if (n_ref > (1u << 24)) return fail("corrupt BAI index (reference count): " + ipath);
-    refs.assign(n_ref, BaiRef());
-    auto rd64 = [](const uint8_t *q) { return (uint64_t)rd32(q) | ((uint64_t)rd32(q + 4) << 32); };
-    for (uint32_t r = 0; r < n_ref; ++r) {
-        BaiRef &br = refs[r];
-        if (!need(4)) return fail("truncated BAI index: " + ipath);
-        const uint32_t n_bin = rd32(p);
-        p += 4;
-        for (uint32_t b = 0; b < n_bin; ++b) {
-            if (!need(8)) return fail("truncated BAI index: " + ipath);
-            const uint32_t bin = rd32(p), n_chunk = rd32(p + 4);
-            p += 8;
-            if (!need((size_t)n_chunk * 16) || n_chunk > (1u << 28)) return fail("truncated BAI index: " + ipath);
-            if (bin == 37450u) { // samtools' metadata pseudo-bin: (file range), (mapped, unmapped)
-                if (n_chunk >= 2) { br.n_mapped = rd64(p + 16); br.n_unmapped = rd64(p + 24); br.has_meta = true; }
-            } else {
-                br.bin_id.push_back(bin);
-                br.chunks.emplace_back();
-                auto &v = br.chunks.back();
-                v.reserve(n_chunk);
-                for (uint32_t c = 0; c < n_chunk; ++c) v.emplace_back(rd64(p + 16 * (size_t)c), rd64(p + 16 * (size_t)c + 8));
-            }
-            p += (size_t)n_chunk * 16;
-        }
-        if (!need(4)) return fail("truncated BAI index: " + ipath);
-        const uint32_t n_intv = rd32(p);
-        p += 4;
-        if (!need((size_t)n_intv * 8) || n_intv > (1u << 28)) return fail("truncated BAI index: " + ipath);
-        br.linear.resize(n_intv);
-        for (uint32_t i = 0; i < n_intv; ++i) br.linear[i] = rd64(p + 8 * (size_t)i);
-        p += (size_t)n_intv * 8;
-    }
-    return 0;
-}
+using pcshape::IndexShape;   // the shape of a loaded index: BAI is (14, 5); a CSI carries its own (SAM specification 5.3)
 
 // the BGZF member at file offset `coff`, inflated and appended to `out`; returns its compressed
 // length, 0 at end of file, -1 on a damaged member
@@ -995,14 +952,133 @@ long read_member(FILE *f, uint64_t coff, std::vector<uint8_t> &out) {
     return (long)clen;
 }
 
-void reg2bins(int64_t beg, int64_t end, std::vector<uint32_t> &bins) {
-    --end;
-    bins.push_back(0);
-    for (int64_t k = 1 + (beg >> 26); k <= 1 + (end >> 26); ++k) bins.push_back((uint32_t)k);
-    for (int64_t k = 9 + (beg >> 23); k <= 9 + (end >> 23); ++k) bins.push_back((uint32_t)k);
-    for (int64_t k = 73 + (beg >> 20); k <= 73 + (end >> 20); ++k) bins.push_back((uint32_t)k);
-    for (int64_t k = 585 + (beg >> 17); k <= 585 + (end >> 17); ++k) bins.push_back((uint32_t)k);
-    for (int64_t k = 4681 + (beg >> 14); k <= 4681 + (end >> 14); ++k) bins.push_back((uint32_t)k);
+// The index of `bam_path`: the file `index_path`, or the first of x.bam.bai, x.bai, x.bam.csi, x.csi beside it (htslib
+// looks for the .csi first, hts.c:2042-2043; here a file that resolved before this reader knew CSI resolves to the same
+// index).  A BAI as it is; a CSI in its BGZF members (or as the bare payload).  No count is trusted before the bytes
+// behind it are there.
+int load_bai(const std::string &bam_path, const std::string &index_path, std::vector<BaiRef> &refs, IndexShape &shape) {
+    std::vector<uint8_t> buf;
+    std::string ipath = index_path;
+    if (!index_path.empty()) {
+        if (!read_file(ipath, buf)) return fail("cannot read the index of " + bam_path + " (" + ipath + ")");
+    } else {
+        const std::string stem = bam_path.size() > 4 ? bam_path.substr(0, bam_path.size() - 4) : bam_path;
+        const std::string cand[4] = {bam_path + ".bai", stem + ".bai", bam_path + ".csi", stem + ".csi"};
+        bool found = false;
+        for (int k = 0; k < 4 && !found; ++k) { ipath = cand[k]; found = read_file(ipath, buf); }
+        if (!found) return fail("cannot read the index of " + bam_path + " (.bam.bai / .bai / .bam.csi / .csi)");
+    }
+    if (buf.size() >= 2 && buf[0] == 31 && buf[1] == 139) {   // BGZF: member by member, from the bytes read
+        FILE *f = fmemopen(buf.data(), buf.size(), "rb");
+        if (!f) return fail("cannot read the index of " + bam_path + " (" + ipath + ")");
+        std::vector<uint8_t> payload;
+        uint64_t coff = 0;
+        long cl;
+        while ((cl = read_member(f, coff, payload)) > 0) {
+            coff += (uint64_t)cl;
+            if (payload.size() > ((size_t)1 << 32)) { cl = -1; break; }
+        }
+        fclose(f);
+        if (cl < 0) return fail("damaged BGZF member in the index: " + ipath);
+        buf.swap(payload);
+        if (buf.size() < 4 || std::memcmp(buf.data(), "CSI\1", 4) != 0) return fail("not a CSI index: " + ipath);
+    }
+    const uint8_t *p = buf.data(), *end = p + buf.size();
+    auto need = [&](size_t n) { return (size_t)(end - p) >= n; };
+    shape = IndexShape();
+    if (need(4) && std::memcmp(p, "CSI\1", 4) == 0) {
+        if (!need(16)) return fail("truncated CSI index: " + ipath);
+        const int32_t min_shift = (int32_t)rd32(p + 4), depth = (int32_t)rd32(p + 8), l_aux = (int32_t)rd32(p + 12);
+        p += 16;
+        if (min_shift < 1 || min_shift > 30 || depth < 0 || depth > 9 || min_shift + 3 * depth > 40) return fail("corrupt CSI index (min_shift / depth): " + ipath);
+        if (l_aux < 0 || !need((size_t)l_aux)) return fail("truncated CSI index: " + ipath);
+        p += (size_t)l_aux;
+        shape.csi = true; shape.min_shift = min_shift; shape.n_lvls = depth;
+    } else if (need(4) && std::memcmp(p, "BAI\1", 4) == 0) p += 4;
+    else return fail("not a BAI index: " + ipath);
+    const char *kind = shape.csi ? "CSI" : "BAI";
+    const std::string truncated = std::string("truncated ") + kind + " index: " + ipath;
+    if (!need(4)) return fail(truncated);
+    const uint32_t n_ref = rd32(p);
+    p += 4;
+    if (n_ref > (1u << 24)) return fail(std::string("corrupt ") + kind + " index (reference count): " + ipath);
+    refs.assign(n_ref, BaiRef());
+    auto rd64 = [](const uint8_t *q) { return (uint64_t)rd32(q) | ((uint64_t)rd32(q + 4) << 32); };
+    const uint32_t meta_bin = shape.meta_bin();
+    const size_t bin_head = shape.csi ? 16 : 8;
+    for (uint32_t r = 0; r < n_ref; ++r) {
+        BaiRef &br = refs[r];
+        if (!need(4)) return fail(truncated);
+        const uint32_t n_bin = rd32(p);
+        p += 4;
+        if ((size_t)(end - p) / bin_head < (size_t)n_bin) return fail(truncated);   // (every bin takes its head at least)
+        for (uint32_t b = 0; b < n_bin; ++b) {
+            if (!need(bin_head)) return fail(truncated);
+            const uint32_t bin = rd32(p), n_chunk = rd32(p + bin_head - 4);
+            const uint64_t loff = shape.csi ? rd64(p + 4) : 0;
+            p += bin_head;
+            if (n_chunk > (1u << 28) || !need((size_t)n_chunk * 16)) return fail(truncated);
+            if (bin == meta_bin) { // samtools' metadata pseudo-bin: (file range), (mapped, unmapped)
+                if (n_chunk >= 2) { br.n_mapped = rd64(p + 16); br.n_unmapped = rd64(p + 24); br.has_meta = true; }
+            } else {
+                br.bin_id.push_back(bin);
+                if (shape.csi) br.loff.push_back(loff);
+                br.chunks.emplace_back();
+                auto &v = br.chunks.back();
+                v.reserve(n_chunk);
+                for (uint32_t c = 0; c < n_chunk; ++c) v.emplace_back(rd64(p + 16 * (size_t)c), rd64(p + 16 * (size_t)c + 8));
+            }
+            p += (size_t)n_chunk * 16;
+        }
+        if (shape.csi) {   // no linear index; the bins ascending, for csi_min_off's lookups (htslib writes them in hash order)
+            std::vector<size_t> order(br.bin_id.size());
+            std::iota(order.begin(), order.end(), (size_t)0);
+            std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return br.bin_id[a] < br.bin_id[b]; });
+            BaiRef sorted;
+            for (size_t k : order) { sorted.bin_id.push_back(br.bin_id[k]); sorted.loff.push_back(br.loff[k]); sorted.chunks.emplace_back(std::move(br.chunks[k])); }
+            br.bin_id.swap(sorted.bin_id); br.loff.swap(sorted.loff); br.chunks.swap(sorted.chunks);
+            continue;
+        }
+        if (!need(4)) return fail(truncated);
+        const uint32_t n_intv = rd32(p);
+        p += 4;
+        if (n_intv > (1u << 28) || !need((size_t)n_intv * 8)) return fail(truncated);
+        br.linear.resize(n_intv);
+        for (uint32_t i = 0; i < n_intv; ++i) br.linear[i] = rd64(p + 8 * (size_t)i);
+        p += (size_t)n_intv * 8;
+    }
+    return 0;
+}
+
+// whether `bin` is one of the bins a region may have records in (reg2bins, hts.c:1690-1706): at the bin's level, the
+// bins from the one of `beg` to the one of `end - 1`.  Asked per bin the index holds, so a region costs the reference's
+// bins and not the leaves it spans (2^24 of them for a whole reference at min_shift 8).
+bool in_reg2bins(uint32_t bin, int64_t beg, int64_t end, const IndexShape &shape) {
+    if (bin >= shape.n_bins()) return false;
+    int l = 0;
+    while (l < shape.n_lvls && bin >= pcshape::level_first(l + 1)) ++l;
+    const int s = shape.min_shift + 3 * (shape.n_lvls - l);
+    const int64_t k = (int64_t)bin - (int64_t)pcshape::level_first(l);
+    return k >= (beg >> s) && k <= ((end - 1) >> s);
+}
+
+// A CSI has no linear index: the lower bound of a region's chunks is the loff of the nearest bin at or before the leaf of
+// `beg` -- from that leaf, step to the previous sibling, or to the parent at a first sibling, until a bin exists
+// (hts.c:1773-1784); bin 0's loff when the walk ends there, 0 without one.  bin_id is ascending (load_bai).
+uint64_t csi_min_off(const BaiRef &br, const IndexShape &shape, int64_t beg) {
+    auto find = [&](uint32_t bin) -> const uint64_t * {
+        const auto it = std::lower_bound(br.bin_id.begin(), br.bin_id.end(), bin);
+        return it != br.bin_id.end() && *it == bin ? &br.loff[(size_t)(it - br.bin_id.begin())] : nullptr;
+    };
+    uint32_t bin = pcshape::level_first(shape.n_lvls) + (uint32_t)(beg >> shape.min_shift);
+    while (bin > 0) {
+        if (const uint64_t *l = find(bin)) return *l;
+        const uint32_t parent = (bin - 1) >> 3;
+        if (bin > (parent << 3) + 1) --bin;
+        else bin = parent;
+    }
+    const uint64_t *l = find(0);
+    return l ? *l : 0;
 }
 
 // the BAM header from the leading BGZF members of `f`: as many as it takes
@@ -1024,11 +1100,12 @@ int read_header_members(Bam &bam, FILE *f, uint32_t &n_ref) {
 struct RegionSpan { int32_t tid; int64_t s, e; };
 
 // Regions (reference name, 0-based half-open) -> merged regions by reference id and the chunks of virtual offsets
-// that hold every record overlapping one of them: the bins of each region (reg2bins), clipped by the 16 kb linear
-// index, sorted and merged (SAM specification section 5; what hts_itr_query does per region, hts.c:1924-1960).
+// that hold every record overlapping one of them: the bins of each region (in_reg2bins), clipped by the 16 kb linear
+// index (BAI) or the loff of the bin in front of the region (CSI), sorted and merged (SAM specification section 5; what hts_itr_query does per region, hts.c:1924-1960).
 int resolve_regions(const Bam &bam, uint32_t n_ref, int nreg, const char *const *rname, const int64_t *rstart, const int64_t *rend,
                     std::vector<BaiRef> &refs, std::vector<RegionSpan> &merged, std::vector<std::pair<uint64_t, uint64_t>> &chunks) {
-    if (load_bai(bam.path, bam.index_path, refs) != 0) return -1;
+    IndexShape shape;
+    if (load_bai(bam.path, bam.index_path, refs, shape) != 0) return -1;
     if (refs.size() != (size_t)n_ref) return fail("the index does not belong to this BAM file (reference count differs): " + bam.path);
     std::vector<RegionSpan> regs;
     for (int i = 0; i < nreg; ++i) {
@@ -1036,7 +1113,7 @@ int resolve_regions(const Bam &bam, uint32_t n_ref, int nreg, const char *const 
         for (uint32_t r = 0; r < n_ref; ++r)
             if (bam.ref_names[r] == rname[i]) { tid = (int32_t)r; break; }
         if (tid < 0) continue;                           // unknown chromosome: fetch() finds nothing there
-        const int64_t s = std::max<int64_t>(rstart[i], 0), e = std::min<int64_t>(rend[i], (int64_t)1 << 29);
+        const int64_t s = std::max<int64_t>(rstart[i], 0), e = std::min<int64_t>(rend[i], shape.reach());
         if (e > s) regs.push_back({tid, s, e});
     }
     std::sort(regs.begin(), regs.end(), [](const RegionSpan &a, const RegionSpan &b) { return a.tid != b.tid ? a.tid < b.tid : (a.s != b.s ? a.s < b.s : a.e < b.e); });
@@ -1046,17 +1123,17 @@ int resolve_regions(const Bam &bam, uint32_t n_ref, int nreg, const char *const 
         else merged.push_back(r);
     }
     std::vector<std::pair<uint64_t, uint64_t>> ch;
-    std::vector<uint32_t> bins;
     for (const RegionSpan &r : merged) {
         const BaiRef &br = refs[(size_t)r.tid];
-        const size_t w = (size_t)(r.s >> 14);
-        if (br.linear.empty()) continue;
-        const uint64_t min_off = w < br.linear.size() ? br.linear[w] : br.linear.back();
-        bins.clear();
-        reg2bins(r.s, r.e, bins);
-        std::sort(bins.begin(), bins.end());
+        uint64_t min_off;
+        if (shape.csi) min_off = csi_min_off(br, shape, r.s);
+        else {
+            const size_t w = (size_t)(r.s >> 14);
+            if (br.linear.empty()) continue;
+            min_off = w < br.linear.size() ? br.linear[w] : br.linear.back();
+        }
         for (size_t b = 0; b < br.bin_id.size(); ++b) {
-            if (!std::binary_search(bins.begin(), bins.end(), br.bin_id[b])) continue;
+            if (!in_reg2bins(br.bin_id[b], r.s, r.e, shape)) continue;
             for (const auto &c : br.chunks[b])
                 if (c.second > min_off && c.second > c.first) ch.push_back(c);
         }

@@ -1,10 +1,14 @@
-// The BAI index of a BAM file from the records the decoder has in HBM (bam_kernels.hip.h: k_bam_chain's record starts,
+// The BAI or CSI index of a BAM file from the records the decoder has in HBM (bam_kernels.hip.h: k_bam_chain's record starts,
 // k_bam_fields' RecOut): what htslib's sam_index_build pushes record by record (kent/src/htslib/sam.c:470-496,
-// hts_idx_push hts.c:1293-1351), restated as streaming kernels over the records in file order.  BAI: min_shift 14, 5 levels
-// (SAM specification section 5.1.1, 5.2).  The host finishes the index (bam_index.h).  Every kernel: one thread per
-// record (or run, or reference), 256 per workgroup, plain stores -- each output element has exactly one writer.
+// hts_idx_push hts.c:1293-1351), restated as streaming kernels over the records in file order.  The index shape is
+// (min_shift, n_lvls): leaves of 2^min_shift positions, n_lvls levels of 8 children below the root; BAI is (14, 5)
+// (SAM specification section 5.1.1, 5.2), a CSI takes its depth from the longest reference (5.3).  The host finishes the
+// index (bam_index.h); for a CSI the linear windows stay in HBM and end as one offset per bin (k_idx_first_window, a
+// running maximum, k_idx_loff).  Every kernel: one thread per record (or run, or reference), 256 per workgroup, plain
+// stores -- each output element has exactly one writer.
 #pragma once
 #include "bam_kernels.hip.h"
+#include "index_shape.h"
 
 namespace pcidx {
 
@@ -12,14 +16,19 @@ constexpr uint64_t kNoKey = ~0ull;            // the key of a record that belong
 constexpr int64_t kBaiReach = (int64_t)1 << 29;   // the coordinates a 5-level index with 16 kb leaves can hold
 constexpr uint32_t kMetaBin = 37450u;         // samtools' pseudo-bin: ((1 << 18) - 1) / 7 + 1
 
-// the bin of [beg, end) (SAM specification 5.3, reg2bin; hts_reg2bin with min_shift 14, n_lvls 5)
-__host__ __device__ __forceinline__ uint32_t reg2bin(int64_t beg, int64_t end) {
+using pcshape::kBaiShift;
+using pcshape::kBaiLvls;
+using pcshape::level_first;
+constexpr int kMinShiftLo = 8, kMinShiftHi = 30;   // the leaf sizes a CSI build accepts: at most 8 levels for 32-bit coordinates, bins below 2^27
+constexpr int64_t kMaxWindows = (int64_t)1 << 28;  // the windows of all references a CSI build holds in HBM (8 bytes each, twice)
+
+// the bin of [beg, end) (SAM specification 5.3, reg2bin; hts_reg2bin): from the leaves up, the first level at which
+// beg and end - 1 share a bin
+__host__ __device__ __forceinline__ uint32_t reg2bin(int64_t beg, int64_t end, int min_shift, int n_lvls) {
     --end;
-    if (beg >> 14 == end >> 14) return (uint32_t)(((1 << 15) - 1) / 7 + (beg >> 14));
-    if (beg >> 17 == end >> 17) return (uint32_t)(((1 << 12) - 1) / 7 + (beg >> 17));
-    if (beg >> 20 == end >> 20) return (uint32_t)(((1 << 9) - 1) / 7 + (beg >> 20));
-    if (beg >> 23 == end >> 23) return (uint32_t)(((1 << 6) - 1) / 7 + (beg >> 23));
-    if (beg >> 26 == end >> 26) return (uint32_t)(((1 << 3) - 1) / 7 + (beg >> 26));
+    int s = min_shift;
+    for (int l = n_lvls; l > 0; --l, s += 3)
+        if (beg >> s == end >> s) return (uint32_t)(level_first(l) + (uint32_t)(beg >> s));
     return 0u;
 }
 
@@ -29,17 +38,21 @@ __host__ __device__ __forceinline__ uint32_t reg2bin(int64_t beg, int64_t end) {
 //              RecOut.end, which stops at the last ALIGNED base
 //   voff[i]    the virtual offset bgzf_tell gives at the record's first byte (bgzf.c:569-572): blk[2 m] << 16 when the
 //              record starts the member, blk[2 m + 1] << 16 | offset in the payload otherwise; voff[nrec] = blk[2 nm] << 16
-//   win_a[i]   first 16 kb window; cov[i] = tid << 32 | (last window + 1) for a placed record with FLAG 0x4 unset, else 0
+//   win_a[i]   first window (2^min_shift positions); cov[i] = tid << 32 | (last window + 1) for a placed record with FLAG 0x4 unset, else 0
 //   mapped[i]  1 for those records
 // blk: per member {file offset of the first gzip header whose payload begins where this member's does, file offset of the
-// member's own header}; entry nm: where the stream ends.  *beyond is set when a record reaches past 2^29.
+// member's own header}; entry nm: where the stream ends.  *beyond is set when a record reaches past the index's reach,
+// 2^(min_shift + 3 n_lvls).  kBai: the shape is the BAI's constants and the two arguments are not read.
+template <bool kBai>
 __global__ __launch_bounds__(256) void k_idx_keys(const uint8_t *__restrict__ stream, const pcbam::Member *__restrict__ members,
                                                   const uint64_t *__restrict__ blk, const uint64_t *__restrict__ rec_base,
                                                   const uint32_t *__restrict__ rec_off, int nmembers, int64_t nrec,
                                                   const uint32_t *__restrict__ rec_member, const pcbam::RecOut *__restrict__ recs,
                                                   uint64_t *key, uint64_t *voff, int32_t *win_a, uint64_t *cov, uint32_t *mapped,
-                                                  uint32_t *beyond) {
+                                                  uint32_t *beyond, int min_shift_arg, int n_lvls_arg) {
     using namespace pcbam;
+    const int min_shift = kBai ? kBaiShift : min_shift_arg, n_lvls = kBai ? kBaiLvls : n_lvls_arg;
+    const int64_t reach = (int64_t)1 << (min_shift + 3 * n_lvls);
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i > nrec) return;
     if (i == nrec) { voff[i] = blk[2 * (size_t)nmembers] << 16; cov[i] = 0; mapped[i] = 0u; return; }
@@ -65,12 +78,12 @@ __global__ __launch_bounds__(256) void k_idx_keys(const uint8_t *__restrict__ st
             }
             end = (int64_t)o.pos + rlen;
         }
-        if (end > kBaiReach) { *beyond = 1u; end = kBaiReach; }   // (refused by the host; the same value from every writer)
+        if (end > reach) { *beyond = 1u; end = reach; }   // (refused by the host; the same value from every writer)
         // (a CIGAR without reference bases gives end == POS: hts_reg2bin and insert_to_l take it as it is -- the bin of
-        // [POS, POS - 1], no window written, n_intv up to POS >> 14 -- and so do reg2bin and the window range here)
-        k = (uint64_t)(uint32_t)o.tid << 32 | reg2bin(o.pos, end);
-        a = (int32_t)(o.pos >> 14);
-        if (is_mapped) { c = (uint64_t)(uint32_t)o.tid << 32 | (uint64_t)(((end - 1) >> 14) + 1); mp = 1u; }
+        // [POS, POS - 1], no window written, n_intv up to POS >> min_shift -- and so do reg2bin and the window range here)
+        k = (uint64_t)(uint32_t)o.tid << 32 | reg2bin(o.pos, end, min_shift, n_lvls);
+        a = (int32_t)((int64_t)o.pos >> min_shift);
+        if (is_mapped) { c = (uint64_t)(uint32_t)o.tid << 32 | (uint64_t)(((end - 1) >> min_shift) + 1); mp = 1u; }
     }
     key[i] = k; win_a[i] = a; cov[i] = c; mapped[i] = mp;
 }
@@ -155,6 +168,35 @@ __global__ __launch_bounds__(256) void k_idx_linear(const uint64_t *__restrict__
     const uint64_t at = voff[i];
     uint64_t *out = linear + lin_base[tid];
     for (; w < w_end; ++w) out[w] = at;
+}
+
+// ---- CSI only: the windows never leave HBM; every bin takes the offset of its first window (update_loff, hts.c:1193-1221)
+
+// The windows in front of a reference's first covered one take the offset of its first record (offset0: the pseudo-bin's
+// file begin): written into the reference's first window where k_idx_linear left it uncovered.  The file is sorted, so
+// the covered values never decrease along `linear`, from one reference to the next either, and none lies below the
+// first record of its reference: an inclusive running maximum over the whole array then is the forward fill.
+__global__ __launch_bounds__(256) void k_idx_first_window(int n_ref, const int32_t *__restrict__ n_intv, const int64_t *__restrict__ lin_base,
+                                                          const uint64_t *__restrict__ ref_beg, uint64_t *linear) {
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= n_ref || n_intv[t] <= 0) return;
+    uint64_t *w = linear + lin_base[t];
+    if (*w == 0) *w = ref_beg[t];
+}
+
+// Run j of the sorted runs -> loff of its bin: the filled window at the bin's first leaf (hts_bin_bot), 0 when the
+// reference's windows end before it (a reference with placed-unmapped records only has none).
+__global__ __launch_bounds__(256) void k_idx_loff(const int32_t *__restrict__ tid, const uint32_t *__restrict__ bin, int64_t nruns, int n_lvls,
+                                                  const int32_t *__restrict__ n_intv, const int64_t *__restrict__ lin_base,
+                                                  const uint64_t *__restrict__ filled, uint64_t *loff) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nruns) return;
+    const uint32_t b = bin[j];
+    int level = 0;
+    while (level < n_lvls && b >= level_first(level + 1)) ++level;
+    const int64_t bot = (int64_t)(b - level_first(level)) << (3 * (n_lvls - level));
+    const int t = tid[j];
+    loff[j] = bot < (int64_t)n_intv[t] ? filled[lin_base[t] + bot] : 0;
 }
 
 } // namespace pcidx

@@ -147,11 +147,11 @@ class Engine(object):
         counts exactly as after ``add_alignment_file(read_bam(path))``; callers that also want the reads themselves
         (``reads_out`` as objects, host-side filters) use :func:`plastid_amd.bam.read_bam_gpu` instead.
         `regions`: stage only the alignments that overlap one of them (``(chrom, start, end)`` or |GenomicSegments|),
-        through the file's BAI index -- only the BGZF members the index chunks of the regions point to are uploaded and inflated
+        through the file's BAI or CSI index -- only the BGZF members the index chunks of the regions point to are uploaded and inflated
         (``pc_add_alignment_bam_chunks``; what one rank of a multi-GPU job does with its genome range of a shared file);
         the return value is then the number of mapped reads among those staged.
-        `index` (with `regions`): an index file elsewhere, or ``"build"`` to build a missing one on this engine first
-        (:func:`plastid_amd.bam.build_index`)."""
+        `index` (with `regions`): an index file elsewhere, or ``"build"`` / ``"build-csi"`` to build a missing one on this engine
+        first, as a BAI / as a CSI (:func:`plastid_amd.bam.build_index`)."""
         import os
         if not os.path.isfile(path):
             raise IOError("No such file: %r" % (path,))

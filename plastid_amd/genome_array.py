@@ -44,7 +44,7 @@ GPU_DECODE_MIN_BYTES = 32 << 20
 def _open_alignment_source(src, regions=None, engine=None, decode="auto", index=None):
     """Filenames are read with the package's own BAM readers; objects are used as
     given (``multiopen`` passes non-str objects through, util/io/openers.py:90-94).
-    `regions`: stage only the alignments that overlap them (through the BAI index; `index`: as for ``bam.read_bam``).
+    `regions`: stage only the alignments that overlap them (through the BAI or CSI index; `index`: as for ``bam.read_bam``).
     `decode`: ``"host"`` (threads + zlib / libdeflate), ``"gpu"`` (the file image goes to HBM, pc_bam_open) or
     ``"auto"`` (the GPU for whole files of GPU_DECODE_MIN_BYTES and more); both give the same arrays."""
     if isinstance(src, PackedAlignments):
@@ -167,8 +167,8 @@ class BAMGenomeArray(object):
             bamfiles = bamfiles[0]
         # (extension) regions=[(chrom, start, end) | GenomicSegment, ...]: files named by path are staged
         # only where they overlap the regions, via their BAI index -- for a few loci of a large file
-        # (extension) index=None | path | "build": the index file of the region reads (bam.resolve_regions); "build" makes a
-        # missing one on the GPU first (bam.build_index)
+        # (extension) index=None | path | "build" | "build-csi": the index file of the region reads (bam.resolve_regions);
+        # "build" makes a missing one on the GPU first (bam.build_index), "build-csi" makes it a CSI (references beyond 2^29)
         # (the engine exists before the files are opened: large BAM files are inflated and decoded on its GPU)
         self._engine = Engine(kwargs.get("device", 0))
         # (extension) keep_reads=False: files named by path go from their bytes to staged alignments entirely on the GPU
