@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 10
+#define PC_ABI_VERSION 11
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -381,6 +381,35 @@ int pc_add_alignment_bam_chunks(pc_engine *e, const char *path, int nchunk, cons
 /* what an open read: [0] compressed bytes of the file uploaded to HBM, [1] runs they came in (1: a whole file), [2] BGZF
  * members inflated, [3] inflated bytes */
 int pc_bam_stats(pc_bam *b, int64_t *out4);
+/* (ABI 11) COORDINATE SORT AT DECODE: a whole-file read of a BAM file in any record order (an aligner's output, a
+ * name-sorted or collated file) -- what `samtools sort` is run for in front of every reader that needs coordinate order.
+ * The `_flags` twins of the four whole-file entry points take PC_BAM_SORT in `flags` (flags 0: the call without the
+ * suffix, bit for bit; any other bit: PC_ERR_ARG).  With it the staged records come out
+ *   placed records first, ordered by (reference id, POS field, reverse-strand bit of FLAG), ties in file order (a stable
+ *   sort; placed but unmapped records sort by their coordinates like any other); unplaced records last, not staged --
+ * the comparator of a coordinate sort (samtools' bam1_lt as this project knows it: tid, pos, reverse bit; pinned by this
+ * project's own tests, not against samtools).  The key is POS, not the first aligned position.  A file that is in order
+ * already by the test of pc_bam_open ((tid, POS) non-decreasing, no placed record behind an unplaced one) is not touched:
+ * the columns are those of flags 0, whatever the strand order inside its ties.  PC_ERR_UNSORTED cannot occur; a
+ * record's own defects are reported as by pc_bam_open, lowest record number first, then an alignment that starts with a
+ * deletion and so breaks the order of first aligned positions among its SORTED neighbours, a truncated last record last.
+ * (A file that is in order already goes through the checks of pc_bam_open and reports what pc_bam_open reports: of a
+ * deletion-order pair and a record's own defect, the one with the lower record number.  The host reader's pb_load_sorted
+ * gives a record's own defect precedence in that case too; files with both defects are the only ones where the two differ.)
+ * The span and chunk reads take no flag: an index of an unsorted file means nothing. */
+#define PC_BAM_SORT 1u
+int pc_bam_open_flags(pc_engine *e, const void *image, int64_t size, const char *name, uint32_t flags, pc_bam **out);
+int pc_bam_open_path_flags(pc_engine *e, const char *path, uint32_t flags, pc_bam **out);
+int pc_add_alignment_bam_flags(pc_engine *e, const void *image, int64_t size, const char *name, uint32_t flags, int64_t *mapped);
+int pc_add_alignment_bam_path_flags(pc_engine *e, const char *path, uint32_t flags, int64_t *mapped);
+/* out4: [0] 1 if the open asked for PC_BAM_SORT, [1] 1 if the file was in order (nothing was sorted), [2] records whose
+ * staged index differs from their rank among the placed records in file order, [3] key bits the radix sort looked at
+ * (33 + the bits of the largest reference id; 0: no sort ran); *ms (optional): GPU time of the sort phase -- the key
+ * kernel, plus the sort, the ranks and the run offsets when the file was out of order */
+int pc_bam_sort_stats(pc_bam *b, int64_t *out4, double *ms);
+/* the 0-based record number in the file (all records counted, unplaced ones too) of every staged record, counts[0]
+ * elements; PC_ERR_STATE when no record was moved (out4[2] == 0: staged record k is the k-th placed record of the file) */
+int pc_bam_read_file_order(pc_bam *b, int64_t *rec_no);
 
 /* ---- (ABI 8) the BAI index of a coordinate-sorted BAM file, built on the GPU.  Replaces `samtools index` / pysam.index,
  * i.e. htslib's sam_index_build for BAI (kent/src/htslib/sam.c:470-496: every record is pushed with POS, bam_endpos

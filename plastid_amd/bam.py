@@ -44,6 +44,9 @@ def _load():
         L.pb_fill_wide.argtypes = [vp] * 4
         L.pb_fill_sam.argtypes = [vp] * 4
         L.pb_fill_nh.argtypes = [vp] * 2
+        L.pb_load_sorted.argtypes = [vp, ctypes.c_int]
+        L.pb_sort_stats.argtypes = [vp, vp]
+        L.pb_file_order.argtypes = [vp, vp]
         L.pb_resolve_regions.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p)] + [vp] * 9
         L.pb_resolve_chunks.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), vp, vp, ctypes.c_int64] + [vp] * 8
         _lib = L
@@ -467,7 +470,12 @@ def resolve_regions(path, regions, index=None):
                 tid=tid[:k].copy(), beg=beg[:k].copy(), end=end[:k].copy(), mapped=int(mapped.value), references=refs, lengths=lens)
 
 
-def read_bam_gpu(path, engine, timing=None, regions=None, index=None):
+def _no_sort_with_regions(sort, regions):
+    if sort and regions is not None:
+        raise ValueError("sort=True cannot be combined with regions=: a region read goes through the index of a coordinate-sorted file")
+
+
+def read_bam_gpu(path, engine, timing=None, regions=None, index=None, sort=False):
     """The same :class:`PackedAlignments` as :func:`read_bam` gives for a whole file, decoded ON THE GPU: the file image
     goes to HBM as it is, the BGZF members are inflated there (one wave per member) and the BAM records decoded
     (``pc_bam_open``, ``csrc/bam_kernels.hip.h``); only the packed columns -- 13 bytes per record instead of the ~120 of
@@ -479,9 +487,14 @@ def read_bam_gpu(path, engine, timing=None, regions=None, index=None):
     BGZF members the index chunks of the regions point to (and the leading ones with the header) are uploaded and
     inflated (``pc_bam_open_chunks``; the overlap test then drops the records of those members that no region wants);
     ``mapped`` is then the index's whole-file count, as pysam's.
-    `index` (with `regions`): as for :func:`resolve_regions` -- an index file elsewhere, ``"build"`` or ``"build-csi"``."""
+    `index` (with `regions`): as for :func:`resolve_regions` -- an index file elsewhere, ``"build"`` or ``"build-csi"``.
+    `sort`: as for :func:`read_bam` -- a whole file in any record order, coordinate sorted on the GPU at decode
+    (``pc_bam_open_path_flags`` with ``PC_BAM_SORT``: one key kernel, one stable radix sort of the record numbers, and the
+    column kernel scatters by sorted rank); the result equals ``read_bam(path, sort=True)``, ``file_order`` included.
+    `timing` then also has ``sort_ms`` (GPU time of the sort phase), ``sorted_input``, ``records_moved`` and ``sort_key_bits``."""
     import time
     from . import _lib as clib
+    _no_sort_with_regions(sort, regions)
     L = clib.load()
     if not os.path.isfile(path):
         raise IOError("No such file: %r" % (path,))
@@ -496,8 +509,12 @@ def read_bam_gpu(path, engine, timing=None, regions=None, index=None):
                                         pv(span["tid"]), pv(span["beg"]), pv(span["end"]), ctypes.byref(h)))
     else:
         # (the library maps the file itself: pages touched by all host threads at once, unmapped on a thread of its own)
-        clib.check(L.pc_bam_open_path(engine._h, os.fsencode(path), ctypes.byref(h)))
+        if sort:
+            clib.check(L.pc_bam_open_path_flags(engine._h, os.fsencode(path), clib.PC_BAM_SORT, ctypes.byref(h)))
+        else:
+            clib.check(L.pc_bam_open_path(engine._h, os.fsencode(path), ctypes.byref(h)))
     t_open = time.perf_counter()
+    file_order = None
     size = os.path.getsize(path)
     try:
         counts = np.zeros(8, np.int64)
@@ -516,6 +533,14 @@ def read_bam_gpu(path, engine, timing=None, regions=None, index=None):
         clib.check(L.pc_bam_read_sam(h, p(flag16), p(mapq), p(qlen)))
         nh = np.empty(n, np.uint16)
         clib.check(L.pc_bam_read_nh(h, p(nh)))
+        if sort:
+            sst, sms = np.zeros(4, np.int64), ctypes.c_double(0.0)
+            clib.check(L.pc_bam_sort_stats(h, p(sst), ctypes.byref(sms)))
+            if int(sst[2]):
+                file_order = np.empty(n, np.int64)
+                clib.check(L.pc_bam_read_file_order(h, p(file_order)))
+            if timing is not None:
+                timing.update(sort_ms=float(sms.value), sorted_input=bool(sst[1]), records_moved=int(sst[2]), sort_key_bits=int(sst[3]))
         if timing is not None:
             timing.update(open_wall_ms=(t_open - t_0) * 1e3, read_wall_ms=(time.perf_counter() - t_open) * 1e3)
             ms = np.zeros(4, np.float64)
@@ -541,10 +566,11 @@ def read_bam_gpu(path, engine, timing=None, regions=None, index=None):
     out = PackedAlignments(tid, pos, alen, flags, nblk, bs, bl, references=refs, lengths=lens, mapped=mapped,
                            validate=False, flag16=flag16, mapq=mapq, qlen=qlen, nh=nh, **wide)   # the device decoder has checked every invariant validate() checks
     out.filename = path
+    out.file_order = file_order
     return out
 
 
-def read_bam(path, threads=0, regions=None, index=None):
+def read_bam(path, threads=0, regions=None, index=None, sort=False, timing=None):
     """Read a coordinate-sorted BAM file into a :class:`PackedAlignments`.
 
     `regions`: iterable of ``(chrom, start, end)`` (0-based, half-open) or objects with those
@@ -557,12 +583,21 @@ def read_bam(path, threads=0, regions=None, index=None):
 
     ``mapped`` is the number of records with flag 0x4 unset (what ``pysam
     AlignmentFile.mapped`` reports from the index); unplaced reads are not staged
-    (``fetch`` never returns them).  Raises ``ValueError`` for unsorted input, as pysam does."""
+    (``fetch`` never returns them).  Raises ``ValueError`` for unsorted input, as pysam does.
+
+    `sort` (whole files only; with `regions` a ``ValueError``): ``True`` -- the file may be in ANY record order (an
+    aligner's output, a name-sorted or collated file): the placed records are staged in the stable order of (reference,
+    POS, reverse strand), a coordinate sorter's comparator, without a ``samtools sort`` in front.  A file that is in
+    order already is returned exactly as without the keyword.  The result's ``file_order`` is ``None`` unless records
+    were moved, else the 0-based record number in the file (all records counted) of every staged record.
+    `timing`: optional dict; with `sort` it receives ``sort_ms`` (0.0: the host decoder does not time it),
+    ``sorted_input`` and ``records_moved``."""
+    _no_sort_with_regions(sort, regions)
     L = _load()
     h = _pb_open(L, path, _index_path(path, index) if regions is not None else None)
     try:
         if regions is None:
-            rc = L.pb_load(h, int(threads))
+            rc = L.pb_load_sorted(h, int(threads)) if sort else L.pb_load(h, int(threads))
         else:
             regs = _region_tuples(regions)
             names = (ctypes.c_char_p * max(len(regs), 1))(*[os.fsencode(str(c)) for c, _, _ in regs])
@@ -599,6 +634,15 @@ def read_bam(path, threads=0, regions=None, index=None):
         L.pb_fill_sam(h, p(flag16), p(mapq), p(qlen))
         nh = np.empty(n, np.uint16)   # ... and the NH:i tag (0: none): read.get_tag("NH") / has_tag("NH")
         L.pb_fill_nh(h, p(nh))
+        file_order = None
+        if sort:
+            sst = np.zeros(3, np.int64)
+            L.pb_sort_stats(h, p(sst))
+            if int(sst[2]):
+                file_order = np.empty(n, np.int64)
+                L.pb_file_order(h, p(file_order))
+            if timing is not None:
+                timing.update(sort_ms=0.0, sorted_input=bool(sst[1]), records_moved=int(sst[2]))
     finally:
         L.pb_close(h)
     if mapped < 0:   # an index without the per-reference counts samtools writes
@@ -608,4 +652,5 @@ def read_bam(path, threads=0, regions=None, index=None):
     out = PackedAlignments(tid, pos, alen, flags, nblk, bs, bl, references=refs, lengths=lens, mapped=mapped,
                            validate=False, flag16=flag16, mapq=mapq, qlen=qlen, nh=nh, **wide)   # the native reader has checked every invariant validate() checks
     out.filename = path
+    out.file_order = file_order
     return out

@@ -2,6 +2,7 @@
 // kernels of bam_kernels.hip.h.  One open is five phases (bam_open_impl): plan_members, upload_and_inflate, read_header,
 // chain_records, decode_columns.  The index build (bam_index_impl: BAI or CSI) runs the first four and index_records in place of the fifth.  Part of the one translation unit of plastid_counts.hip.
 #include "bam_kernels.hip.h"
+#include "sort_kernels.hip.h"
 #include "index_kernels.hip.h"
 #include "bam_index.h"
 
@@ -24,6 +25,11 @@ struct pc_bam {
     int64_t members = 0, inflated_bytes = 0, compressed_bytes = 0;
     int64_t uploaded_bytes = 0, runs = 0;   // bytes of the file image that went to HBM, contiguous stretches they came from
     int chain_restarts = 0;
+    // PC_BAM_SORT (pc_bam_sort_stats, pc_bam_read_file_order)
+    bool sort_requested = false, sorted_input = true;
+    int64_t moved = 0, key_bits = 0;   // records staged elsewhere than their rank in the file; key bits the radix sort looked at
+    double sort_ms = 0;                // GPU time of the key kernel (+ sort, ranks and run offsets when the file was out of order)
+    DevBuf<uint32_t> file_order;       // moved > 0: the record number in the file of every staged record
 };
 
 namespace {
@@ -660,8 +666,18 @@ std::vector<uint32_t> group_members(const std::vector<uint64_t> &rec_base, int64
     return rec_member;
 }
 
-// Phase 5: fields, order checks, the region filter, the scans that place every kept record, and the columns of `b`.
-int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const BamHeader &h, const BamRecords &recs, pc_bam &b) {
+// the events around the sort phase of an open with PC_BAM_SORT: key kernel [0, 1]; sort, ranks and run offsets [2, 3]
+struct SortEvents {
+    hipEvent_t ev[4] = {};
+    int create() {
+        for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+        return PC_OK;
+    }
+    ~SortEvents() { for (auto x : ev) if (x) (void)hipEventDestroy(x); }
+};
+
+// Phase 5: fields, order checks (or, with `sort`, the coordinate sort), the region filter, the scans that place every kept record, and the columns of `b`.
+int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const BamHeader &h, const BamRecords &recs, pc_bam &b, bool sort) {
     using namespace pcbam;
     hipStream_t st = d.st;
     const int nm = pl.nm();
@@ -671,10 +687,10 @@ int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const B
     DevBuf<uint64_t> d_rec_base;
     DevBuf<uint32_t> d_rec_member, d_placed, d_runs, d_staged_at, d_run_at, d_wide;
     DevBuf<RecOut> d_recs;
-    DevBuf<unsigned long long> d_misc;   // [0] first error (index << 8 | code), [1] mapped, [2] unplaced
-    int rc = d_misc.reserve(4);
+    DevBuf<unsigned long long> d_misc;   // [0] first error (index << 8 | code), [1] mapped, [2] unplaced; with `sort`: [3] out of order, [4] records moved
+    int rc = d_misc.reserve(6);
     if (rc != PC_OK) return rc;
-    const unsigned long long misc0[4] = {~0ull, 0ull, 0ull, 0ull};
+    const unsigned long long misc0[6] = {~0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
     HIP_TRY(hipMemcpyAsync(d_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, st));
     int64_t n_staged = 0, n_runs = 0;
     if (nrec > 0) {
@@ -687,7 +703,27 @@ int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const B
         const unsigned g256 = (unsigned)((nrec + 255) / 256);
         hipLaunchKernelGGL(k_bam_fields, dim3(g256), dim3(256), 0, st, d.d_stream.p, total_u, d.d_members.p, d_rec_base.p, d.d_chain.p, d.d_rec_off.p, nm, nrec,
                            h.n_ref, d_rec_member.p, d_recs.p);
-        hipLaunchKernelGGL(k_bam_order, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, d_placed.p, d_misc.p);
+        // `sort`: the keys first; a file they find in order goes on exactly as without the flag
+        DevBuf<uint64_t> d_key, d_key2;
+        DevBuf<uint32_t> d_idx, d_idx2, d_runs_sorted;
+        SortEvents sev;
+        bool disorder = false;
+        if (sort) {
+            room(rc, d_key, (size_t)nrec); room(rc, d_idx, (size_t)nrec);
+            if (rc == PC_OK) rc = sev.create();
+            if (rc != PC_OK) return rc;
+            unsigned long long dis = 0;
+            HIP_TRY(hipEventRecord(sev.ev[0], st));
+            hipLaunchKernelGGL(k_bam_sort_keys, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, d_key.p, d_idx.p, d_misc.p + 3);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(sev.ev[1], st));
+            HIP_TRY(hipMemcpyAsync(&dis, d_misc.p + 3, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            disorder = dis != 0;
+            b.sorted_input = !disorder;
+            if (!disorder) { d_key.release(); d_idx.release(); }
+        }
+        if (!disorder) hipLaunchKernelGGL(k_bam_order, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, d_placed.p, d_misc.p);
         DevBuf<int32_t> d_rtid;
         DevBuf<int64_t> d_rbe;
         if (span) {   // keep what overlaps a requested region (htslib's overlap rule); everything else is as if it were not in the file
@@ -712,14 +748,46 @@ int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const B
             if (rc != PC_OK) return rc;
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_placed.p, d_staged_at.p, (int)(nrec + 1), st));
             HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_runs.p, d_run_at.p, (int)(nrec + 1), st));
+            // Out of order: one stable radix sort of (key, record number) over the key bits in use, then staged_at and run_at
+            // by rank in the sorted order (the totals stay those of the two scans above).  Placed records sort first.
+            DevBuf<uint8_t> d_sort_tmp;
+            if (disorder) {
+                const int key_bits = sort_key_bits(h.n_ref);
+                room(rc, d_key2, (size_t)nrec); room(rc, d_idx2, (size_t)nrec); room(rc, d_runs_sorted, (size_t)nrec + 1);
+                if (rc != PC_OK) return rc;
+                HIP_TRY(hipEventRecord(sev.ev[2], st));
+                // (double buffers: the passes go back and forth between the two halves, and the sort says which half holds the result)
+                hipcub::DoubleBuffer<uint64_t> keys(d_key.p, d_key2.p);
+                hipcub::DoubleBuffer<uint32_t> vals(d_idx.p, d_idx2.p);
+                size_t sort_bytes = 0;
+                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, vals, (int)nrec, 0, key_bits, st));
+                rc = d_sort_tmp.reserve(std::max<size_t>(sort_bytes, 16));
+                if (rc != PC_OK) { (void)hipStreamSynchronize(st); return rc; }
+                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, sort_bytes, keys, vals, (int)nrec, 0, key_bits, st));
+                const uint32_t *perm = vals.Current();
+                b.file_order.swap(perm == d_idx.p ? d_idx : d_idx2);   // (the permutation is the staged records' numbers in the file)
+                HIP_TRY(hipMemsetAsync(d_runs_sorted.p + nrec, 0, 4, st));
+                hipLaunchKernelGGL(k_bam_sort_rank, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, perm, d_staged_at.p, d_runs_sorted.p, d_misc.p, d_misc.p + 4);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_runs_sorted.p, d_runs_sorted.p, (int)(nrec + 1), st));   // (in place)
+                hipLaunchKernelGGL(k_bam_sort_run_at, dim3(g256), dim3(256), 0, st, perm, d_runs_sorted.p, nrec, d_run_at.p);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipEventRecord(sev.ev[3], st));
+                b.key_bits = key_bits;
+            }
             uint32_t tot[2] = {0, 0};
-            unsigned long long misc[3] = {0, 0, 0};
+            unsigned long long misc[5] = {0, 0, 0, 0, 0};
             HIP_TRY(hipMemcpyAsync(&tot[0], d_staged_at.p + nrec, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(&tot[1], d_run_at.p + nrec, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(misc, d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));   // (d_tmp goes out of scope)
+            HIP_TRY(hipStreamSynchronize(st));   // (d_tmp and the sort's buffers go out of scope)
             n_staged = tot[0]; n_runs = tot[1];
             b.mapped = (int64_t)misc[1]; b.unplaced = (int64_t)misc[2];
+            if (sort) {
+                b.sort_ms = ms_between(sev.ev[0], sev.ev[1]) + (disorder ? ms_between(sev.ev[2], sev.ev[3]) : 0.0);
+                b.moved = (int64_t)misc[4];
+                if (!b.moved) b.file_order.release();
+            }
             if (misc[0] != ~0ull) {
                 rc = record_defect((int)(misc[0] & 0xffu), d.path.c_str());
                 if (rc != PC_OK) return rc;
@@ -771,6 +839,14 @@ int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const B
                         b.wide_alen.push_back((int32_t)ro[(size_t)i].L);
                         b.wide_nblk.push_back((int32_t)ro[(size_t)i].nruns);
                     }
+                if (b.moved) {   // the walk above is in file order: the list is kept ascending by staged index
+                    std::vector<size_t> by((size_t)b.wide_idx.size());
+                    std::iota(by.begin(), by.end(), (size_t)0);
+                    std::sort(by.begin(), by.end(), [&](size_t x, size_t y) { return b.wide_idx[x] < b.wide_idx[y]; });
+                    const std::vector<int64_t> wi = b.wide_idx;
+                    const std::vector<int32_t> wa = b.wide_alen, wn = b.wide_nblk;
+                    for (size_t k = 0; k < by.size(); ++k) { b.wide_idx[k] = wi[by[k]]; b.wide_alen[k] = wa[by[k]]; b.wide_nblk[k] = wn[by[k]]; }
+                }
             }
         }
     } else if (truncated) return fail(PC_ERR_ARG, "truncated BAM record");
@@ -991,9 +1067,11 @@ int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader
 
 // One open: the five phases above, in order.  `span`: a region read (its chunk list and regions); nullptr: the whole file.
 static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const char *name, pc_bam **out, const UploadedHook *uploaded, const BamSpan *span,
-                         const BamKnobs &knobs) {
+                         const BamKnobs &knobs, uint32_t flags = 0) {
     if (!e || !out || size < 0 || (size > 0 && !image_)) return fail(PC_ERR_ARG, "pc_bam_open: bad arguments");
     *out = nullptr;
+    if ((flags & ~(uint32_t)PC_BAM_SORT) || (flags && span)) return fail(PC_ERR_ARG, "pc_bam_open: unknown flags (PC_BAM_SORT is the one there is, for whole-file reads)");
+    const bool sort = (flags & PC_BAM_SORT) != 0;
     const uint8_t *image = (const uint8_t *)image_;
     HIP_TRY(hipSetDevice(e->device));
     PoolScope pool_scope(&e->pool);   // (the decoder's scratch -- image, inflated stream, record table -- is recycled through the engine's pool)
@@ -1019,7 +1097,9 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     b->ref_names = std::move(h.ref_names); b->ref_lengths = std::move(h.ref_lengths);
     b->chain_restarts = recs.chain_restarts; b->total = recs.nrec;
     if (recs.nrec >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_bam_open: more than 2^31-2 records per file are not supported");
-    rc = decode_columns(d, pl, span, h, recs, *b);
+    b->sort_requested = sort;
+    b->key_bits = 0;
+    rc = decode_columns(d, pl, span, h, recs, *b, sort);
     if (rc != PC_OK) return rc;
     for (int k = 0; k < 4; ++k) b->ms[k] = ms_between(d.ev[k], d.ev[k + 1]);
     guard.b = nullptr;
@@ -1090,8 +1170,8 @@ static int bam_index_impl(pc_engine *e, const void *image_, int64_t size, const 
 
 // a region read comes back for a larger slice of the file's head when the header did not fit the first one
 static int bam_open_span_retry(pc_engine *e, const void *image, int64_t size, const char *name, pc_bam **out, const UploadedHook *uploaded, const BamSpan *span,
-                               const BamKnobs &knobs) {
-    if (!span) return bam_open_impl(e, image, size, name, out, uploaded, nullptr, knobs);
+                               const BamKnobs &knobs, uint32_t flags = 0) {
+    if (!span) return bam_open_impl(e, image, size, name, out, uploaded, nullptr, knobs, flags);
     BamSpan sp = *span;
     sp.header_bytes = knobs.header_bytes;
     for (;;) {
@@ -1102,9 +1182,9 @@ static int bam_open_span_retry(pc_engine *e, const void *image, int64_t size, co
 }
 
 static int add_alignment_bam_impl(pc_engine *e, const void *image, int64_t size, const char *name, int64_t *mapped, const UploadedHook *uploaded,
-                                  const BamSpan *span, const BamKnobs &knobs) {
+                                  const BamSpan *span, const BamKnobs &knobs, uint32_t open_flags = 0) {
     pc_bam *b = nullptr;
-    int rc = bam_open_span_retry(e, image, size, name, &b, uploaded, span, knobs);
+    int rc = bam_open_span_retry(e, image, size, name, &b, uploaded, span, knobs, open_flags);
     if (rc != PC_OK) return rc;
     struct Closer { pc_bam *b; ~Closer() { pc_bam_close(b); } } closer{b};
     PoolScope pool_scope(&e->pool);
@@ -1225,7 +1305,7 @@ struct MappedFile {
 // The path-taking entry points: map the file, then open it (`out`) or stage it (`mapped`).  A whole-file read faults the
 // pages as MappedFile::open decides and takes the mapping down as soon as the image has been uploaded; a region read maps
 // only, faults what it uploads, and keeps the mapping to the end (a retry for a longer header reads the file again).
-static int with_mapped_file(pc_engine *e, const char *path, const BamSpan *span, pc_bam **out, int64_t *mapped) {
+static int with_mapped_file(pc_engine *e, const char *path, const BamSpan *span, pc_bam **out, int64_t *mapped, uint32_t flags = 0) {
     const BamKnobs knobs;
     MappedFile mf;
     const int rc = mf.open(path, span ? 0 : -1, knobs.touch);
@@ -1234,8 +1314,8 @@ static int with_mapped_file(pc_engine *e, const char *path, const BamSpan *span,
     const UploadedHook release = [&mf, device](hipStream_t up) { mf.release_behind(up, device); };
     const UploadedHook *hook = span ? nullptr : &release;
     // (the open entry points pass `out`, the staging ones leave it null and may pass `mapped`)
-    return out ? bam_open_span_retry(e, mf.p, (int64_t)mf.size, path, out, hook, span, knobs)
-               : add_alignment_bam_impl(e, mf.p, (int64_t)mf.size, path, mapped, hook, span, knobs);
+    return out ? bam_open_span_retry(e, mf.p, (int64_t)mf.size, path, out, hook, span, knobs, flags)
+               : add_alignment_bam_impl(e, mf.p, (int64_t)mf.size, path, mapped, hook, span, knobs, flags);
 }
 
 static int chunk_args(const char *what, int nchunk, const uint64_t *voff_beg, const uint64_t *voff_end, int nreg, const int32_t *tid, const int64_t *beg,
@@ -1269,22 +1349,54 @@ int pc_bam_close(pc_bam *b) {
     return PC_OK;
 }
 
-int pc_bam_open(pc_engine *e, const void *image, int64_t size, const char *name, pc_bam **out) {
-    return bam_open_impl(e, image, size, name, out, nullptr, nullptr, BamKnobs());
+int pc_bam_open_flags(pc_engine *e, const void *image, int64_t size, const char *name, uint32_t flags, pc_bam **out) {
+    return bam_open_impl(e, image, size, name, out, nullptr, nullptr, BamKnobs(), flags);
+}
+int pc_bam_open(pc_engine *e, const void *image, int64_t size, const char *name, pc_bam **out) { return pc_bam_open_flags(e, image, size, name, 0u, out); }
+
+static int sort_flags_ok(const char *what, uint32_t flags) {
+    return (flags & ~(uint32_t)PC_BAM_SORT) ? fail(PC_ERR_ARG, "%s: unknown flags (PC_BAM_SORT is the one there is)", what) : PC_OK;
 }
 
+int pc_add_alignment_bam_flags(pc_engine *e, const void *image, int64_t size, const char *name, uint32_t flags, int64_t *mapped) {
+    const int rc = sort_flags_ok("pc_add_alignment_bam_flags", flags);
+    return rc != PC_OK ? rc : add_alignment_bam_impl(e, image, size, name, mapped, nullptr, nullptr, BamKnobs(), flags);
+}
 int pc_add_alignment_bam(pc_engine *e, const void *image, int64_t size, const char *name, int64_t *mapped) {
-    return add_alignment_bam_impl(e, image, size, name, mapped, nullptr, nullptr, BamKnobs());
+    return pc_add_alignment_bam_flags(e, image, size, name, 0u, mapped);
 }
 
-int pc_bam_open_path(pc_engine *e, const char *path, pc_bam **out) {
+int pc_bam_open_path_flags(pc_engine *e, const char *path, uint32_t flags, pc_bam **out) {
     if (!e || !path || !out) return fail(PC_ERR_ARG, "pc_bam_open_path: bad arguments");
-    return with_mapped_file(e, path, nullptr, out, nullptr);
+    const int rc = sort_flags_ok("pc_bam_open_path_flags", flags);
+    return rc != PC_OK ? rc : with_mapped_file(e, path, nullptr, out, nullptr, flags);
+}
+int pc_bam_open_path(pc_engine *e, const char *path, pc_bam **out) { return pc_bam_open_path_flags(e, path, 0u, out); }
+
+int pc_add_alignment_bam_path_flags(pc_engine *e, const char *path, uint32_t flags, int64_t *mapped) {
+    if (!e || !path) return fail(PC_ERR_ARG, "pc_add_alignment_bam_path: bad arguments");
+    const int rc = sort_flags_ok("pc_add_alignment_bam_path_flags", flags);
+    return rc != PC_OK ? rc : with_mapped_file(e, path, nullptr, nullptr, mapped, flags);
+}
+int pc_add_alignment_bam_path(pc_engine *e, const char *path, int64_t *mapped) { return pc_add_alignment_bam_path_flags(e, path, 0u, mapped); }
+
+int pc_bam_sort_stats(pc_bam *b, int64_t *out4, double *ms) {
+    if (!b || !out4) return fail(PC_ERR_ARG, "pc_bam_sort_stats: bad arguments");
+    out4[0] = b->sort_requested ? 1 : 0; out4[1] = b->sorted_input ? 1 : 0; out4[2] = b->moved; out4[3] = b->key_bits;
+    if (ms) *ms = b->sort_ms;
+    return PC_OK;
 }
 
-int pc_add_alignment_bam_path(pc_engine *e, const char *path, int64_t *mapped) {
-    if (!e || !path) return fail(PC_ERR_ARG, "pc_add_alignment_bam_path: bad arguments");
-    return with_mapped_file(e, path, nullptr, nullptr, mapped);
+int pc_bam_read_file_order(pc_bam *b, int64_t *rec_no) {
+    if (!b) return fail(PC_ERR_ARG, "pc_bam_read_file_order: NULL handle");
+    if (!b->moved) return fail(PC_ERR_STATE, "pc_bam_read_file_order: no record was moved (the records are in the order of the file)");
+    if (b->n > 0 && !rec_no) return fail(PC_ERR_ARG, "pc_bam_read_file_order: NULL array");
+    HIP_TRY(hipSetDevice(b->e->device));
+    HIP_TRY(hipStreamSynchronize(b->e->stream));
+    std::vector<uint32_t> fo((size_t)b->n);
+    if (b->n) HIP_TRY(hipMemcpy(fo.data(), b->file_order.p, (size_t)b->n * 4, hipMemcpyDeviceToHost));
+    for (int64_t k = 0; k < b->n; ++k) rec_no[k] = (int64_t)fo[(size_t)k];
+    return PC_OK;
 }
 
 int pc_bam_open_span(pc_engine *e, const char *path, uint64_t voff_begin, uint64_t voff_end, int nreg, const int32_t *tid, const int64_t *beg,

@@ -81,6 +81,10 @@ struct Part {
     int32_t first_tid = -1, first_pos = -1, first_spos = -1;
     int32_t last_tid = -1, last_pos = -1, last_spos = -1;
     bool bad_size = false;            // decode_span stopped at a length prefix below the fixed record size
+    // pb_load_sorted only: the POS field of every staged record (the sort key; `pos` holds the first aligned position), its
+    // record number within the piece (all records counted), and the number of the piece's first unplaced record
+    int32_t *rpos = nullptr, *rno = nullptr;
+    int64_t first_unplaced_rec = -1;
 };
 
 // Column storage of one load: 64 MiB anonymous mappings (on huge pages where the host grants them), handed
@@ -165,12 +169,14 @@ struct Cols {
     std::vector<uint16_t> alen, flag16, nh;
     std::vector<uint8_t> flags, nblk, mapq;
     std::vector<int32_t> lseq;
+    std::vector<int32_t> rpos, rno;   // (pb_load_sorted: see Part)
     size_t n = 0;   // records held: the five per-record columns are sized for the piece up front and written by index
     void clear() { n = 0; blk_start.clear(); blk_len.clear(); }
     void room(size_t records) {
         if (tid.size() < records) { tid.resize(records); pos.resize(records); alen.resize(records); flags.resize(records); nblk.resize(records);
                                       flag16.resize(records); mapq.resize(records); lseq.resize(records); nh.resize(records); }
     }
+    void room_sorted(size_t records) { if (rpos.size() < records) { rpos.resize(records); rno.resize(records); } }
 };
 
 struct Bam {
@@ -185,6 +191,12 @@ struct Bam {
     size_t nrec = 0, nrun = 0;
     int threads = 1;
     bool loaded = false;
+    // pb_load_sorted: the decode leaves the checks between records out (`sorting`); perm[k] = the flat (file order) index of
+    // the record staged at k, empty when no record moved; file_order[k] = its record number in the file
+    bool sorting = false, sort_requested = false, sorted_input = true;
+    int64_t moved = 0;
+    std::vector<uint32_t> perm;
+    std::vector<int64_t> file_order;
 };
 
 bool read_file(const std::string &path, std::vector<uint8_t> &buf) {
@@ -406,10 +418,15 @@ static inline uint16_t aux_nh(const uint8_t *after_cigar, int32_t l_seq, const u
     return 0;
 }
 
+// kSort (pb_load_sorted): no check between a record and the one in front (the file may be in any order); POS and the
+// record number of every staged record are kept for the sort.
+template <bool kSort>
 const uint8_t *decode_span_cols(const Bam &bam, Part &pt, Cols &cols, const uint8_t *q, const uint8_t *limit, uint32_t n_ref, int64_t max_rec) {
     std::vector<std::pair<int32_t, int32_t>> runs;
     cols.clear();
     cols.room(limit > q ? (size_t)(limit - q) / 36 + 1 : 1);   // a record takes at least 36 bytes
+    if (kSort) cols.room_sorted(limit > q ? (size_t)(limit - q) / 36 + 1 : 1);
+    int32_t *const c_rpos = cols.rpos.data(), *const c_rno = cols.rno.data();
     // the state every record touches lives in locals (the columns are int32 / uint8 arrays: through `pt` and `cols`
     // the compiler has to assume that every store may change them) and is written back on the way out
     int32_t *const c_tid = cols.tid.data(), *const c_pos = cols.pos.data();
@@ -442,12 +459,16 @@ const uint8_t *decode_span_cols(const Bam &bam, Part &pt, Cols &cols, const uint
         if (!(flag & 0x4)) mapped += 1;
         if (tid < 0) { // unplaced reads sit at the end of a sorted BAM; fetch() never returns them
             unplaced += 1;
+            if (kSort && !saw_unplaced) pt.first_unplaced_rec = i;
             saw_unplaced = true;
             continue;
         }
         if (tid >= (int32_t)n_ref) { ret = bad(i, true, "BAM record with reference id out of range"); break; }
         if (pos < 0) { ret = bad(i, true, "placed BAM record with a negative position"); break; }
-        if (!any_placed) {        // its order against the previous piece is checked when stitching
+        if (kSort) {
+            any_placed = true;
+            c_rpos[n] = pos; c_rno[n] = (int32_t)i;
+        } else if (!any_placed) {        // its order against the previous piece is checked when stitching
             any_placed = true;
             pt.first_placed_rec = i;
             pt.first_tid = tid; pt.first_pos = pos;
@@ -464,7 +485,7 @@ const uint8_t *decode_span_cols(const Bam &bam, Part &pt, Cols &cols, const uint
             const uint32_t v = rd32(cig), op = v & 0xf, len = v >> 4;
             if ((op == 0 || op == 7 || op == 8) && len > 0 && len <= 65535 && (int64_t)pos + len <= 0x7fffffffLL) {
                 if (first) pt.first_spos = pos;
-                else if (last_tid == tid && last_spos > pos) {
+                else if (!kSort && last_tid == tid && last_spos > pos) {
                     ret = bad(i, false, "alignment starting with a deletion breaks coordinate order; not supported");
                     break;
                 }
@@ -514,7 +535,7 @@ const uint8_t *decode_span_cols(const Bam &bam, Part &pt, Cols &cols, const uint
         // D/N (not produced by aligners) is accepted only if that keeps the file order
         const int32_t spos = runs.empty() ? pos : runs[0].first;
         if (first) pt.first_spos = spos;
-        else if (last_tid == tid && last_spos > spos) {
+        else if (!kSort && last_tid == tid && last_spos > spos) {
             ret = bad(i, false, "alignment starting with a deletion breaks coordinate order; not supported");
             break;
         }
@@ -541,11 +562,11 @@ const uint8_t *decode_span_cols(const Bam &bam, Part &pt, Cols &cols, const uint
 
 const uint8_t *decode_span(Bam &bam, Part &pt, const uint8_t *q, const uint8_t *limit, uint32_t n_ref, int64_t max_rec) {
     thread_local Cols cols;
-    const uint8_t *stop = decode_span_cols(bam, pt, cols, q, limit, n_ref, max_rec);
+    const uint8_t *stop = bam.sorting ? decode_span_cols<true>(bam, pt, cols, q, limit, n_ref, max_rec) : decode_span_cols<false>(bam, pt, cols, q, limit, n_ref, max_rec);
     // the finished columns, at their exact size, into the load's arena
     const size_t n = cols.n, m = cols.blk_start.size();
     if (n) {
-        uint8_t *mem = (uint8_t *)bam.arena.alloc(n * 21 + 64 * 9 + m * 8 + 64 * 2);
+        uint8_t *mem = (uint8_t *)bam.arena.alloc(n * 21 + 64 * 9 + m * 8 + 64 * 2 + (bam.sorting ? n * 8 + 64 * 2 : 0));
         if (!mem) {
             if (pt.err_rec == INT64_MAX) { pt.err_rec = 0; pt.err_before_order = true; pt.err = "out of memory reading " + bam.path; }
             return stop;
@@ -559,6 +580,10 @@ const uint8_t *decode_span(Bam &bam, Part &pt, const uint8_t *q, const uint8_t *
         std::memcpy(pt.flag16, cols.flag16.data(), n * 2); std::memcpy(pt.mapq, cols.mapq.data(), n); std::memcpy(pt.lseq, cols.lseq.data(), n * 4);
         pt.nh = (uint16_t *)take(n * 2);
         std::memcpy(pt.nh, cols.nh.data(), n * 2);
+        if (bam.sorting) {
+            pt.rpos = (int32_t *)take(n * 4); pt.rno = (int32_t *)take(n * 4);
+            std::memcpy(pt.rpos, cols.rpos.data(), n * 4); std::memcpy(pt.rno, cols.rno.data(), n * 4);
+        }
         if (m) {
             pt.blk_start = (int32_t *)take(m * 4); pt.blk_len = (int32_t *)take(m * 4);
             std::memcpy(pt.blk_start, cols.blk_start.data(), m * 4); std::memcpy(pt.blk_len, cols.blk_len.data(), m * 4);
@@ -582,7 +607,7 @@ int stitch_parts(Bam &bam, bool truncated, int nthreads) {
         const Part &pt = bam.parts[k];
         int64_t at = INT64_MAX;
         std::string msg;
-        if (pt.any_placed) {
+        if (pt.any_placed && !bam.sorting) {
             const int64_t f = pt.first_placed_rec;
             if (seen_unplaced || (have_prev && (pt.first_tid < prev_tid || (pt.first_tid == prev_tid && pt.first_pos < prev_pos)))) {
                 at = f; msg = "BAM file is not coordinate sorted: " + bam.path;
@@ -898,6 +923,74 @@ int decode(Bam &bam, int nthreads) {
     lap("stitch");
     bam.loaded = true;
     return 0;
+}
+
+// ---------------------------------------------------------------- coordinate sort at load (pb_load_sorted)
+// The wide records of a load as flat (file order) record indices.
+void flat_wide(const Bam &b, std::vector<int64_t> &idx, std::vector<int32_t> &alen, std::vector<int32_t> &nblk) {
+    for (size_t k = 0; k < b.parts.size(); ++k) {
+        const Part &pt = b.parts[k];
+        for (size_t j = 0; j < pt.wide_idx.size(); ++j) {
+            idx.push_back((int64_t)b.rec_off[k] + pt.wide_idx[j]);
+            alen.push_back(pt.wide_alen[j]);
+            nblk.push_back(pt.wide_nblk[j]);
+        }
+    }
+}
+
+// Behind a decode with `sorting`: is the file in order by the test of pb_load ((tid, POS) non-decreasing, no placed
+// record behind an unplaced one)?  Then nothing moves.  Otherwise the staged order is a stable sort of the placed records
+// on (tid, POS, reverse strand) -- the order the device decoder's radix sort gives (sort_kernels.hip.h) -- kept as a
+// permutation that pb_fill* apply.  Either way the first aligned positions of neighbours have to be in order too.
+int sort_loaded(Bam &bam) {
+    const size_t n = bam.nrec;
+    std::vector<int32_t> tid(n), rpos(n), spos(n);
+    std::vector<uint8_t> rev(n);
+    std::vector<int64_t> recno(n);
+    int64_t base = 0, first_unplaced = -1, last_placed = -1;
+    for (size_t k = 0; k < bam.parts.size(); ++k) {
+        const Part &pt = bam.parts[k];
+        const size_t at = bam.rec_off[k];
+        for (size_t j = 0; j < pt.n; ++j) {
+            tid[at + j] = pt.tid[j]; rpos[at + j] = pt.rpos[j]; spos[at + j] = pt.pos[j]; rev[at + j] = pt.flags[j];
+            recno[at + j] = base + pt.rno[j];
+        }
+        if (pt.n) last_placed = base + pt.rno[pt.n - 1];
+        if (first_unplaced < 0 && pt.first_unplaced_rec >= 0) first_unplaced = base + pt.first_unplaced_rec;
+        base += pt.total;
+    }
+    bool disorder = first_unplaced >= 0 && last_placed > first_unplaced;
+    for (size_t i = 1; i < n && !disorder; ++i)
+        disorder = tid[i] < tid[i - 1] || (tid[i] == tid[i - 1] && rpos[i] < rpos[i - 1]);
+    bam.sorted_input = !disorder;
+    std::vector<uint32_t> perm;
+    if (disorder) {
+        perm.resize(n);
+        std::iota(perm.begin(), perm.end(), 0u);
+        std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) {
+            if (tid[a] != tid[b]) return tid[a] < tid[b];
+            if (rpos[a] != rpos[b]) return rpos[a] < rpos[b];
+            return rev[a] < rev[b];
+        });
+    }
+    auto at = [&](size_t k) { return disorder ? (size_t)perm[k] : k; };
+    for (size_t k = 1; k < n; ++k)
+        if (tid[at(k)] == tid[at(k - 1)] && spos[at(k - 1)] > spos[at(k)])
+            return fail("alignment starting with a deletion breaks coordinate order; not supported");
+    bam.moved = 0;
+    for (size_t k = 0; k < perm.size(); ++k) bam.moved += perm[k] != (uint32_t)k ? 1 : 0;
+    if (bam.moved) {
+        bam.file_order.resize(n);
+        for (size_t k = 0; k < n; ++k) bam.file_order[k] = recno[perm[k]];
+        bam.perm.swap(perm);
+    }
+    return 0;
+}
+
+template <typename T> void permute_column(T *col, const std::vector<uint32_t> &perm) {
+    if (!col) return;
+    const std::vector<T> old(col, col + perm.size());
+    for (size_t k = 0; k < perm.size(); ++k) col[k] = old[perm[k]];
 }
 
 // ---------------------------------------------------------------- region-limited loading (BAI / CSI)
@@ -1425,6 +1518,18 @@ int64_t pb_wide_count(void *h) {
 int pb_fill_wide(void *h, int64_t *idx, int32_t *alen, int32_t *nblk) {
     Bam *b = static_cast<Bam *>(h);
     if (!b || !b->loaded) return fail("pb_fill_wide: file not loaded");
+    if (!b->perm.empty()) {   // (pb_load_sorted) by staged index, ascending
+        std::vector<int64_t> fi;
+        std::vector<int32_t> fa, fn;
+        flat_wide(*b, fi, fa, fn);
+        std::vector<uint32_t> inv(b->perm.size());
+        for (size_t k = 0; k < b->perm.size(); ++k) inv[b->perm[k]] = (uint32_t)k;
+        std::vector<size_t> by(fi.size());
+        std::iota(by.begin(), by.end(), (size_t)0);
+        std::sort(by.begin(), by.end(), [&](size_t x, size_t y) { return inv[(size_t)fi[x]] < inv[(size_t)fi[y]]; });
+        for (size_t k = 0; k < by.size(); ++k) { idx[k] = (int64_t)inv[(size_t)fi[by[k]]]; alen[k] = fa[by[k]]; nblk[k] = fn[by[k]]; }
+        return 0;
+    }
     size_t at = 0;
     for (size_t k = 0; k < b->parts.size(); ++k) {
         const Part &pt = b->parts[k];
@@ -1467,6 +1572,21 @@ int pb_fill(void *h, int32_t *tid, int32_t *pos, uint16_t *alen, uint8_t *flags,
     for (int t = 1; t < nt; ++t) pool.emplace_back(worker);
     worker();
     for (auto &t : pool) t.join();
+    if (!b->perm.empty()) {   // (pb_load_sorted) the columns by staged index; every record's runs follow it
+        const std::vector<uint32_t> &perm = b->perm;
+        const size_t n = perm.size();
+        std::vector<int64_t> cnt(nblk, nblk + n), fi;
+        std::vector<int32_t> fa, fn;
+        flat_wide(*b, fi, fa, fn);
+        for (size_t k = 0; k < fi.size(); ++k) cnt[(size_t)fi[k]] = fn[k];   // (a wide record's column holds the marker)
+        std::vector<size_t> roff(n + 1, 0);
+        for (size_t i = 0; i < n; ++i) roff[i + 1] = roff[i] + (cnt[i] >= 2 ? (size_t)cnt[i] : 0);
+        const std::vector<int32_t> os(blk_start, blk_start + roff[n]), ol(blk_len, blk_len + roff[n]);
+        size_t w = 0;
+        for (size_t k = 0; k < n; ++k)
+            for (size_t r = roff[perm[k]]; r < roff[perm[k] + 1]; ++r, ++w) { blk_start[w] = os[r]; blk_len[w] = ol[r]; }
+        permute_column(tid, perm); permute_column(pos, perm); permute_column(alen, perm); permute_column(flags, perm); permute_column(nblk, perm);
+    }
     return 0;
 }
 
@@ -1483,6 +1603,7 @@ int pb_fill_nh(void *h, uint16_t *nh) {
         const Part &pt = b->parts[k];
         if (pt.n && nh) std::memcpy(nh + b->rec_off[k], pt.nh, pt.n * 2);
     }
+    if (!b->perm.empty()) permute_column(nh, b->perm);
     return 0;
 }
 
@@ -1497,6 +1618,39 @@ int pb_fill_sam(void *h, uint16_t *flag16, uint8_t *mapq, int32_t *lseq) {
         if (mapq) std::memcpy(mapq + at, pt.mapq, n);
         if (lseq) std::memcpy(lseq + at, pt.lseq, n * 4);
     }
+    if (!b->perm.empty()) { permute_column(flag16, b->perm); permute_column(mapq, b->perm); permute_column(lseq, b->perm); }
+    return 0;
+}
+
+// pb_load for a file in ANY record order (an aligner's output, a name-sorted file): the records are decoded without the
+// checks between neighbours, and staged placed records first, in the stable order of (reference id, POS, reverse strand)
+// -- a coordinate sorter's comparator; unplaced records are not staged, as ever.  A file that pb_load's own order test
+// accepts is left exactly as pb_load gives it.  pb_fill* then hand the columns over in the staged order.
+int pb_load_sorted(void *h, int nthreads) {
+    Bam *b = static_cast<Bam *>(h);
+    if (!b) return fail("pb_load_sorted: NULL handle");
+    if (b->loaded) return b->sort_requested ? 0 : fail("pb_load_sorted: file already loaded");
+    if (nthreads <= 0) nthreads = default_threads();
+    b->sorting = b->sort_requested = true;
+    if (decode(*b, nthreads) != 0) return -1;
+    if (sort_loaded(*b) != 0) { b->loaded = false; return -1; }
+    return 0;
+}
+
+// out3: [0] 1 after pb_load_sorted, [1] 1 if the file was in order, [2] records staged elsewhere than their rank in the file
+int pb_sort_stats(void *h, int64_t *out3) {
+    Bam *b = static_cast<Bam *>(h);
+    if (!b || !b->loaded || !out3) return fail("pb_sort_stats: file not loaded");
+    out3[0] = b->sort_requested ? 1 : 0; out3[1] = b->sorted_input ? 1 : 0; out3[2] = b->moved;
+    return 0;
+}
+
+// the 0-based record number in the file (all records counted) of every staged record; fails when no record was moved
+int pb_file_order(void *h, int64_t *rec_no) {
+    Bam *b = static_cast<Bam *>(h);
+    if (!b || !b->loaded) return fail("pb_file_order: file not loaded");
+    if (b->perm.empty()) return fail("pb_file_order: no record was moved (the records are in the order of the file)");
+    std::memcpy(rec_no, b->file_order.data(), b->file_order.size() * 8);
     return 0;
 }
 

@@ -140,7 +140,7 @@ class Engine(object):
         for f in files:
             self.add_alignment_file(f, ntid)
 
-    def add_bam(self, path, regions=None, index=None):
+    def add_bam(self, path, regions=None, index=None, sort=False):
         """Stage a coordinate-sorted BAM file WITHOUT its records ever visiting the host (``pc_add_alignment_bam``): the
         file image goes to HBM, the BGZF members are inflated and the records decoded there, and the packed columns are
         staged by kernels.  Returns the number of mapped reads (pysam's ``AlignmentFile.mapped``).  The engine then
@@ -151,8 +151,12 @@ class Engine(object):
         (``pc_add_alignment_bam_chunks``; what one rank of a multi-GPU job does with its genome range of a shared file);
         the return value is then the number of mapped reads among those staged.
         `index` (with `regions`): an index file elsewhere, or ``"build"`` / ``"build-csi"`` to build a missing one on this engine
-        first, as a BAI / as a CSI (:func:`plastid_amd.bam.build_index`)."""
+        first, as a BAI / as a CSI (:func:`plastid_amd.bam.build_index`).
+        `sort` (whole files only): the file may be in any record order; it is coordinate sorted on the GPU at decode
+        (``pc_add_alignment_bam_path_flags`` with ``PC_BAM_SORT``), as :func:`plastid_amd.bam.read_bam_gpu` does."""
         import os
+        from .bam import _no_sort_with_regions
+        _no_sort_with_regions(sort, regions)
         if not os.path.isfile(path):
             raise IOError("No such file: %r" % (path,))
         mapped = ctypes.c_int64(0)
@@ -162,6 +166,9 @@ class Engine(object):
             cb, ce = np.ascontiguousarray(sp["chunks"][:, 0]), np.ascontiguousarray(sp["chunks"][:, 1])
             rc = self._lib.pc_add_alignment_bam_chunks(self._h, os.fsencode(path), len(cb), _ptr(cb), _ptr(ce), len(sp["tid"]),
                                                        _ptr(sp["tid"]), _ptr(sp["beg"]), _ptr(sp["end"]), ctypes.byref(mapped))
+        elif sort:
+            from ._lib import PC_BAM_SORT
+            rc = self._lib.pc_add_alignment_bam_path_flags(self._h, os.fsencode(path), PC_BAM_SORT, ctypes.byref(mapped))
         else:
             rc = self._lib.pc_add_alignment_bam_path(self._h, os.fsencode(path), ctypes.byref(mapped))
         check(rc)

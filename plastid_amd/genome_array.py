@@ -41,7 +41,7 @@ from .roitools import GenomicSegment, SegmentChain
 GPU_DECODE_MIN_BYTES = 32 << 20
 
 
-def _open_alignment_source(src, regions=None, engine=None, decode="auto", index=None):
+def _open_alignment_source(src, regions=None, engine=None, decode="auto", index=None, sort=False):
     """Filenames are read with the package's own BAM readers; objects are used as
     given (``multiopen`` passes non-str objects through, util/io/openers.py:90-94).
     `regions`: stage only the alignments that overlap them (through the BAI or CSI index; `index`: as for ``bam.read_bam``).
@@ -54,6 +54,8 @@ def _open_alignment_source(src, regions=None, engine=None, decode="auto", index=
         if decode not in ("auto", "host", "gpu"):
             raise ValueError("decode must be 'auto', 'host' or 'gpu', got %r" % (decode,))
         named = {} if index is None else dict(index=index)   # (the readers' calls are unchanged without the keyword)
+        if sort:   # (whole files in any record order: bam.read_bam)
+            named["sort"] = True
         on_gpu = decode == "gpu" or (decode == "auto" and regions is None and os.path.exists(src) and os.path.getsize(src) >= GPU_DECODE_MIN_BYTES)
         if on_gpu and engine is not None:
             if decode == "gpu":   # (also with `regions`: the members the index points to are inflated on the GPU)
@@ -63,12 +65,12 @@ def _open_alignment_source(src, regions=None, engine=None, decode="auto", index=
             # "auto": a file the device decoder rejects gets a second opinion from the host decoder (whose verdict -- the
             # arrays or the exception -- is the one the caller sees); ``decoder`` records which of the two read the file
             try:
-                aln = read_bam_gpu(src, engine)
+                aln = read_bam_gpu(src, engine, **({"sort": True} if sort else {}))
                 aln.decoder = "gpu"
                 return aln
             except (ValueError, IOError, OSError, RuntimeError):
                 pass
-        if named and regions is not None:   # ("build": on the array's own engine)
+        if index is not None and regions is not None:   # ("build": on the array's own engine)
             from .bam import _index_path
             named = dict(index=_index_path(src, index, engine))
         aln = read_bam(src, regions=regions, **named)
@@ -170,6 +172,11 @@ class BAMGenomeArray(object):
         # (extension) index=None | path | "build" | "build-csi": the index file of the region reads (bam.resolve_regions);
         # "build" makes a missing one on the GPU first (bam.build_index), "build-csi" makes it a CSI (references beyond 2^29)
         # (the engine exists before the files are opened: large BAM files are inflated and decoded on its GPU)
+        # (extension) sort=True: files named by path may be in any record order; they are coordinate sorted at decode
+        # (bam.read_bam / Engine.add_bam; whole files only)
+        sort = bool(kwargs.get("sort", False))
+        from .bam import _no_sort_with_regions
+        _no_sort_with_regions(sort, kwargs.get("regions"))
         self._engine = Engine(kwargs.get("device", 0))
         # (extension) keep_reads=False: files named by path go from their bytes to staged alignments entirely on the GPU
         # (Engine.add_bam: inflate, record decode and staging as kernels) -- the fastest way to count vectors; the reads
@@ -183,7 +190,7 @@ class BAMGenomeArray(object):
             if any(b.references != self.bamfiles[0].references for b in self.bamfiles):
                 raise ValueError("keep_reads=False needs the same reference list in every file")
         else:
-            self.bamfiles = [_open_alignment_source(x, kwargs.get("regions"), self._engine, kwargs.get("decode", "auto"), kwargs.get("index"))
+            self.bamfiles = [_open_alignment_source(x, kwargs.get("regions"), self._engine, kwargs.get("decode", "auto"), kwargs.get("index"), sort)
                              for x in bamfiles]
         self._strands = ("+", "-", ".")
         self._normalize = False
@@ -213,7 +220,7 @@ class BAMGenomeArray(object):
                     whole = resolve_regions(b.filename, [], index=index)["mapped"]
                     b.mapped = whole if whole >= 0 else kept
                 else:
-                    b.mapped = self._engine.add_bam(b.filename)
+                    b.mapped = self._engine.add_bam(b.filename, **({"sort": True} if sort else {}))
                 b.n = self._engine.num_records(fi)
                 b._engine, b._file_index = self._engine, fi
             self._base_flags = None

@@ -212,6 +212,10 @@ class PackedRead(object):
 class PackedAlignments(object):
     """One coordinate-sorted alignment file as flat arrays (see module doc)."""
 
+    #: set by ``bam.read_bam`` / ``bam.read_bam_gpu`` with ``sort=True`` when records were moved: the 0-based record
+    #: number in the file of every record; ``None`` otherwise (and for arrays made any other way)
+    file_order = None
+
     def __init__(self, tid, pos, alen, flags, nblk, blk_start=None, blk_len=None,
                  references=None, lengths=None, mapped=None, read_objects=None, validate=True,
                  wide_idx=None, wide_alen=None, wide_nblk=None, flag16=None, mapq=None, qlen=None, nh=None):
