@@ -1194,23 +1194,13 @@ static int add_alignment_bam_impl(pc_engine *e, const void *image, int64_t size,
     // the decoder's columns never leave HBM
     // (PC_BAM_STAGE_HOST=1: read them back and hand them over as host arrays, as a caller of pc_bam_read + pc_add_alignment_file does)
     if (!knobs.stage_host) {
-        DevBuf<uint32_t> d_wr;
-        DevBuf<uint2> d_wv;
-        if (nw) {
-            std::vector<uint32_t> wr((size_t)nw);
-            std::vector<uint2> wv((size_t)nw);
-            for (int64_t k = 0; k < nw; ++k) { wr[(size_t)k] = (uint32_t)b->wide_idx[(size_t)k]; wv[(size_t)k] = make_uint2((uint32_t)b->wide_alen[(size_t)k], (uint32_t)b->wide_nblk[(size_t)k]); }
-            rc = d_wr.upload(wr, e->stream);
-            if (rc == PC_OK) rc = d_wv.upload(wv, e->stream);
-            if (rc != PC_OK) return rc;
-            HIP_TRY(hipStreamSynchronize(e->stream));   // (the host vectors go out of scope)
-        }
-        pcstage::DevCols dc;
+        pcstage::DevCols dc = {};   // (the wide records go up in stage_file, from the host arrays)
         dc.tid = b->tid.p; dc.pos = b->pos.p; dc.alen = b->alen.p; dc.flags = b->flags.p; dc.nblk = b->nblk.p;
         dc.blk_start = b->blk_start.p; dc.blk_len = b->blk_len.p;
-        dc.wide_rec = d_wr.p; dc.wide_val = d_wv.p; dc.n_wide = nw;
-        rc = stage_file(e, n, ntid, nullptr, nullptr, nullptr, nullptr, nullptr, m, nullptr, nullptr, nw, b->wide_idx.data(), b->wide_alen.data(),
-                        b->wide_nblk.data(), &dc);
+        StageInput in;
+        in.n = n; in.ntid = ntid; in.nrun = m; in.dev = &dc;
+        in.n_wide = nw; in.wide_idx = b->wide_idx.data(); in.wide_alen = b->wide_alen.data(); in.wide_nblk = b->wide_nblk.data();
+        rc = stage_file(e, in);
         if (rc != PC_OK) return rc;
         // the FLAG / MAPQ columns stay with the staged file (no copy: the decoder's blocks change hands)
         StagedFile *sf = e->files.back();

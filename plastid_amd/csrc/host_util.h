@@ -1,7 +1,7 @@
 // host_util.h -- host-side helpers of the counting engine that do not touch HIP: the worker pool behind
 // parallel_chunks, the galloping lower bound of the plan build, a vector without zero-fill, the host's look at the
-// contig column of caller-owned records (scan_contigs), the window size of a plan (choose_window).  Plain C++17, so that
-// tests/test_host_logic.py can compile tests/host_util_test.cpp against it on a machine without a GPU.
+// contig column of caller-owned records (scan_contigs), the window size of a plan (choose_window), the halo and the
+// linear-index layout of a staged file (choose_halo, lin_layout).  Plain C++17, so that tests/test_host_logic.py can compile tests/host_util_test.cpp against it on a machine without a GPU.
 #pragma once
 #include <algorithm>
 #include <condition_variable>
@@ -202,4 +202,60 @@ static int choose_window(int rows, int nmodes, unsigned long long n_iv, unsigned
     if (knob && knob <= 2 * g) G = knob;
     *budget = g;
     return G;
+}
+
+// What staging derives from the statistics of the WHOLE file, for every later kernel.  The histograms are those of
+// k_cols_pack: records per reference span (`span_hist`, 0 .. 1025, the last bin: anything longer), of those the
+// records of the gapped-record list (`gap_span_hist`) and the wide records (`wide_span_hist`), and the single-run
+// records per aligned length (`len1_hist`, 0 .. 255); `rmin` / `rmax` are the shortest and longest aligned length of a
+// read of the run stream (65536 / -1: none), `n` the record count.
+//   wcap       the window halo: the smallest span bound (>= 64, <= 1024) that covers >= 99.5% of the records; longer
+//              (spliced) reads go through the long-read path
+//   W, Wg      the longest span inside the halo: of any record (a span that only wide records have does not count), of a
+//              record of the gapped-record list
+//   slen, tlen aligned lengths the 4-byte stream carries (single-run records inside the halo, up to `stream_max_len`), and
+//              those together with the run stream's (the range of the LDS entry table); 0 / 0: none
+struct StageHalo { int wcap, W, Wg, slen_min, slen_max, tlen_min, tlen_max; };
+static StageHalo choose_halo(const std::vector<int64_t> &span_hist, const std::vector<int64_t> &gap_span_hist,
+                             const std::vector<int64_t> &wide_span_hist, const std::vector<int64_t> &len1_hist, int rmin, int rmax,
+                             int64_t n, int stream_max_len) {
+    StageHalo h;
+    int64_t cum = 0;
+    const int64_t need = n - n / 200;
+    int s0 = 0;
+    for (; s0 <= 1024; ++s0) {
+        cum += span_hist[(size_t)s0];
+        if (cum >= need) break;
+    }
+    h.wcap = std::max(64, std::min(s0, 1024));
+    h.W = h.Wg = 1;
+    for (int s = 1; s <= h.wcap; ++s) {
+        if (span_hist[(size_t)s] > wide_span_hist[(size_t)s]) h.W = s;
+        if (gap_span_hist[(size_t)s]) h.Wg = s;
+    }
+    int smin = 65536, smax = -1;
+    for (int L = 0; L <= std::min(h.wcap, stream_max_len); ++L)
+        if (len1_hist[(size_t)L]) { smin = std::min(smin, L); smax = std::max(smax, L); }
+    const int tmin = std::min(smin, rmin), tmax = std::max(smax, rmax);
+    h.slen_min = smax >= smin ? smin : 0;
+    h.slen_max = smax >= smin ? smax : 0;
+    h.tlen_min = tmax >= tmin ? tmin : 0;
+    h.tlen_max = tmax >= tmin ? tmax : 0;
+    return h;
+}
+
+// Linear-index layout of a staged file: one table entry per 2^shift-position bucket of each contig, up to the last
+// record start (`last_pos`) -- and up to the furthest end of a read of the contig (`tid_end`, exclusive): a long-span
+// read reaches windows beyond every record start, and the later runs of gapped reads start there -- plus one closing
+// entry per contig.  `lin_off[t]` = first entry of contig t (t = 0 .. ntid); returned: entries of every table.
+static size_t lin_layout(const std::vector<int64_t> &tid_bounds, const std::vector<int32_t> &last_pos, const std::vector<int64_t> &tid_end,
+                         int shift, std::vector<int64_t> &lin_off) {
+    const size_t ntid = last_pos.size();
+    lin_off.assign(ntid + 1, 0);
+    for (size_t t = 0; t < ntid; ++t) {
+        const bool any = tid_bounds[t + 1] > tid_bounds[t];
+        const int64_t last = any ? std::max<int64_t>(last_pos[t], tid_end[t] - 1) : -1;
+        lin_off[t + 1] = lin_off[t] + (last >= 0 ? (last >> shift) + 1 : 0) + 1;
+    }
+    return (size_t)lin_off[ntid];
 }

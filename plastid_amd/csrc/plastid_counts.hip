@@ -143,7 +143,7 @@ struct BigReservoir {
 // hipMalloc / hipFree (the latter synchronises the device): blocks up to 32 MiB are kept by
 // power-of-two size class when a plan lets go of them and handed to the next one.  Every user of
 // one pool enqueues on the same engine stream, so a recycled block is ordered after its last use.  (The one exception,
-// the transfer ring's own stream, synchronises the engine stream before it touches pooled blocks: stage_file.)
+// the transfer ring's own stream, synchronises the engine stream before it touches pooled blocks: stage_upload.)
 struct DevPool {
     static constexpr int kMinShift = 8, kClasses = 18;   // 256 B .. 32 MiB
     static constexpr size_t kMaxCached = (size_t)512 << 20;
@@ -1527,498 +1527,531 @@ int pc_add_alignment_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *
     return pc_add_alignment_file_wide(e, n, ntid, tid, pos, alen, flags, nblk, nrun, blk_start, blk_len, 0, nullptr, nullptr, nullptr);
 }
 
-// `dev`: the columns are in HBM already (a BAM file decoded on the GPU, pc_add_alignment_bam): the host pointers of the
-// columns and runs are then NULL and nothing is uploaded or validated (the decoder did that); the wide
-// side arrays come from the host either way.
 static int build_compact_stream(pc_engine *e, StagedFile *sf, int ntid);
-static int stage_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid, const int32_t *pos,
-                      const uint16_t *alen, const uint8_t *flags, const uint8_t *nblk, int64_t nrun,
-                      const int32_t *blk_start, const int32_t *blk_len, int64_t n_wide, const int64_t *wide_idx,
-                      const int32_t *wide_alen, const int32_t *wide_nblk, const pcstage::DevCols *dev);
+
+} // extern "C"
+
+namespace {
+
+// ---- staging, phase by phase: every alignment file becomes a StagedFile here -- caller-owned columns
+// (pc_add_alignment_file[_wide]), the columns the GPU BAM decoder left in HBM (add_alignment_bam_impl), the same columns
+// read back (PC_BAM_STAGE_HOST=1).  The phases enqueue on e->stream in the order they are called.  A phase owns its
+// temporaries and waits for the stream before they go back to the pool, on the error paths too: PC_TRY / HIP_TRY stand
+// where nothing is in flight, and behind the first launch or copy of a phase its errors are collected and reported behind
+// the wait (finish_phase).
+struct StageInput {   // one file, as its caller has it
+    int64_t n = 0;                // records
+    int32_t ntid = 0;             // contigs of the reference list
+    const int32_t *tid = nullptr, *pos = nullptr;   // host columns (NULL with `dev`)
+    const uint16_t *alen = nullptr;
+    const uint8_t *flags = nullptr, *nblk = nullptr;
+    int64_t nrun = 0;             // aligned runs of the multi-run records
+    const int32_t *blk_start = nullptr, *blk_len = nullptr;
+    int64_t n_wide = 0;           // wide records: always from the host
+    const int64_t *wide_idx = nullptr;
+    const int32_t *wide_alen = nullptr, *wide_nblk = nullptr;
+    // set: the columns are in HBM already (a BAM file decoded on the GPU) -- nothing is uploaded or validated (the decoder
+    // did that); its wide_rec / wide_val / n_wide are filled in here
+    const pcstage::DevCols *dev = nullptr;
+};
+
+struct FileStats {   // the statistics block of k_cols_pack, back on the host
+    std::vector<int64_t> span_hist, gap_span_hist, wide_span_hist, len_hist, len1_hist, tid_end;
+    std::vector<int32_t> last_pos;   // start of the last record of every contig
+    int Wr = 1, rmin = 65536, rmax = -1;
+    int64_t max_span = 1;
+    explicit FileStats(int ntid)
+        : span_hist(pcstage::kSpanBins, 0), gap_span_hist(pcstage::kSpanBins, 0), wide_span_hist(pcstage::kSpanBins, 0), len_hist(pcstage::kLenBins, 0),
+          len1_hist(pcstage::kLen1Bins, 0), tid_end((size_t)ntid, 0), last_pos((size_t)ntid, -1) {}
+};
+
+struct StageCall {   // what the phases of one call share beside the engine and the file under construction
+    const StageInput &in;
+    StageClock clk;
+    // caller-owned columns in HBM as they are (stage_upload); read up to k_zip_runs
+    DevBuf<int32_t> d_pos, d_bs, d_bl;
+    DevBuf<uint16_t> d_alen;
+    DevBuf<uint8_t> d_flags8, d_nblk8;
+    pcstage::DevCols cols;              // the columns every kernel reads: those, or the decoder's
+    std::vector<int64_t> tid_bounds;    // first record of every contig
+    int64_t n_ok;                       // records before the first defect of the contig column
+    DevBuf<uint32_t> d_run_at;          // where the runs of every record go in the run stream (stage_run_layout -> stage_pack)
+    int64_t nrunrec = 0;                // entries of the run stream
+    // run-stream records {run start, len | cum << 8 | L << 16 | flags << 24} and the record of every run, in record order
+    // (stage_pack -> stage_run_stream)
+    DevBuf<uint2> d_val_in;
+    DevBuf<uint32_t> d_idx_in;
+    FileStats stats;
+    int wcap = 64;                      // the window halo
+    uint32_t nwg = 0;                   // workgroups of k_classify
+    DevBuf<uint32_t> d_side_at;         // [3 * nwg + 1]: members of the three side lists per workgroup, then their exclusive sum
+    size_t side_total[3] = {0, 0, 0};   // long, gapped, extra-long
+    std::vector<int64_t> lin_off;       // first linear-index entry of every contig
+    explicit StageCall(const StageInput &i) : in(i), cols(), tid_bounds((size_t)i.ntid + 1, 0), n_ok(i.n), stats(i.ntid) {}
+};
+
+// The end of a phase with work in flight: waits for the stream and reports the first error of the phase (`he`), of a
+// launch, or of the wait.  `what` is a format that takes the error string, or none.
+int finish_phase(hipStream_t st, hipError_t he, const char *what) {
+    if (he == hipSuccess) he = hipGetLastError();
+    const hipError_t waited = hipStreamSynchronize(st);
+    if (he == hipSuccess) he = waited;
+    return he == hipSuccess ? PC_OK : fail(PC_ERR_HIP, what, hipGetErrorString(he));
+}
+
+// `n` elements in each of the buffers; stops at the first that cannot be had
+template <class... Bufs> int reserve_all(size_t n, Bufs &...bufs) {
+    int rc = PC_OK;
+    (void)(((rc = bufs.reserve(n)) == PC_OK) && ...);
+    return rc;
+}
+
+int stage_check(const pc_engine *e, const StageInput &in) {   // (no HIP call)
+    const int64_t n = in.n, nrun = in.nrun, n_wide = in.n_wide;
+    if (!e) return fail(PC_ERR_ARG, "engine is NULL");
+    if (n < 0 || in.ntid <= 0 || nrun < 0) return fail(PC_ERR_ARG, "pc_add_alignment_file: bad sizes");
+    if (!in.dev && n > 0 && (!in.tid || !in.pos || !in.alen || !in.flags || !in.nblk)) return fail(PC_ERR_ARG, "pc_add_alignment_file: NULL array");
+    if (!in.dev && nrun > 0 && (!in.blk_start || !in.blk_len)) return fail(PC_ERR_ARG, "pc_add_alignment_file: NULL run array");
+    if (n_wide < 0 || (n_wide > 0 && (!in.wide_idx || !in.wide_alen || !in.wide_nblk))) return fail(PC_ERR_ARG, "pc_add_alignment_file: bad wide-record arrays");
+    for (int64_t k = 0; k < n_wide && !in.dev; ++k) {
+        const int64_t i = in.wide_idx[k];
+        if (i < 0 || i >= n || (k > 0 && i <= in.wide_idx[k - 1])) return fail(PC_ERR_ARG, "pc_add_alignment_file: wide_idx must be ascending record indices");
+        if (in.alen[i] != 0xffffu || in.nblk[i] != 0xffu) return fail(PC_ERR_ARG, "pc_add_alignment_file: record %lld is listed as wide but its alen / nblk are not 65535 / 255", (long long)i);
+        if (in.wide_alen[k] < 0 || in.wide_nblk[k] < 0 || (in.wide_nblk[k] == 0) != (in.wide_alen[k] == 0) || in.wide_nblk[k] > in.wide_alen[k])
+            return fail(PC_ERR_ARG, "pc_add_alignment_file: record %lld: bad wide alen / nblk", (long long)i);
+    }
+    if (n >= (int64_t)0x7fffffff || nrun >= (int64_t)0xffffffffu)
+        return fail(PC_ERR_ARG, "pc_add_alignment_file: more than 2^31-2 records per file are not supported");
+    if (!e->files.empty() && in.ntid != e->ntid)
+        return fail(PC_ERR_ARG, "pc_add_alignment_file: all files must use the same reference list (ntid %d vs %d)", in.ntid, e->ntid);
+    return PC_OK;
+}
+
+// The wide records by record index, {uint32 record, uint2 {aligned length, run count}}: what the per-record kernels look
+// up, from k_cols_runs on.  They go up once, straight into the arrays the file keeps.
+int upload_wide_records(pc_engine *e, StagedFile *sf, StageCall &c) {
+    const StageInput &in = c.in;
+    if (in.n_wide > 0) {
+        std::vector<uint32_t> wr((size_t)in.n_wide);
+        std::vector<uint2> wv((size_t)in.n_wide);
+        for (int64_t k = 0; k < in.n_wide; ++k) { wr[(size_t)k] = (uint32_t)in.wide_idx[k]; wv[(size_t)k] = make_uint2((uint32_t)in.wide_alen[k], (uint32_t)in.wide_nblk[k]); }
+        int rc = sf->wide_rec.upload(wr, e->stream);
+        if (rc == PC_OK) rc = sf->wide_val.upload(wv, e->stream);
+        if (hipStreamSynchronize(e->stream) != hipSuccess && rc == PC_OK) rc = fail(PC_ERR_HIP, "stage: uploading the wide records failed");   // (the host vectors go out of scope)
+        if (rc != PC_OK) return rc;
+        sf->nwide = in.n_wide;
+    }
+    c.cols.wide_rec = sf->wide_rec.p; c.cols.wide_val = sf->wide_val.p; c.cols.n_wide = in.n_wide;
+    return PC_OK;
+}
+
+// the arrays of the staged file whose sizes follow from the record count alone
+int reserve_record_arrays(StagedFile *sf, StageCall &c) {
+    const size_t n = (size_t)c.in.n;
+    PC_TRY(sf->blk_off.reserve(n + 1));
+    PC_TRY(c.d_run_at.reserve(n + 1));
+    PC_TRY(sf->rec.reserve(n + 2));
+    return sf->stream.reserve(n + 8);
+}
+
+// ---- caller-owned columns: up to HBM as they are.  The host moves bytes and looks at ONE column, the contigs: sorted,
+// that column is ntid + 1 record bounds, so it does not travel -- a streaming comparison finds the bounds (and the first
+// record out of order or out of range) on the worker threads while the other columns cross PCIe through the ring.
+int stage_upload(pc_engine *e, StagedFile *sf, StageCall &c) {
+    const StageInput &in = c.in;
+    const size_t n = (size_t)in.n, nrun = (size_t)in.nrun;
+    PC_TRY(reserve_all(n + 1, c.d_pos, c.d_alen, c.d_flags8, c.d_nblk8));
+    PC_TRY(reserve_all(nrun + 1, c.d_bs, c.d_bl));
+    // (the ring fills these blocks on ITS stream: a block the pool recycled may still be read or written by work
+    // queued on the engine's stream -- a plan buffer that grew inside an asynchronous pc_count -- and every other user of
+    // the pool is ordered on that stream; the ring is the exception, so it starts behind everything queued there)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    size_t piece = TransferRing::kPiece;
+    if (const char *env = getenv("PC_STAGE_SLICE")) piece = (size_t)std::max<int64_t>(1, std::min<int64_t>(atoll(env), (int64_t)(TransferRing::kPiece / 4))) * 4; // test knob: tiny pieces
+    std::vector<TransferJob> jobs;   // (what the first kernel reads goes first)
+    jobs.push_back({c.d_nblk8.p, in.nblk, n});
+    jobs.push_back({c.d_alen.p, in.alen, n * 2});
+    jobs.push_back({c.d_pos.p, in.pos, n * 4});
+    jobs.push_back({c.d_flags8.p, in.flags, n});
+    jobs.push_back({c.d_bs.p, in.blk_start, nrun * 4});
+    jobs.push_back({c.d_bl.p, in.blk_len, nrun * 4});
+    struct Joined { std::future<int> f; ~Joined() { if (f.valid()) f.wait(); } } up;   // (joined on every way out, before the buffers go)
+    c.clk.lap("column buffers");
+    const int devno = e->device;
+    up.f = std::async(std::launch::async, [devno, &jobs, piece]() -> int {
+        StageClock uclk;
+        const int r = TransferRing::of(devno).run(devno, jobs, piece, getenv("PC_STAGE_SLICE") != nullptr);
+        uclk.lap("  (upload thread: ring)");
+        return r;
+    });
+    c.n_ok = scan_contigs(in.tid, in.n, in.ntid, stage_threads(in.n), c.tid_bounds);
+    c.clk.lap("contig bounds");
+    int rc = upload_wide_records(e, sf, c);
+    // while the columns cross PCIe: the arrays of the staged file whose sizes follow from the record count alone (a
+    // billion records: 20 GB of hipMalloc, 0.12 s when the pool has no such blocks -- a third of the call)
+    if (rc == PC_OK) rc = reserve_record_arrays(sf, c);
+    c.clk.lap("arrays of the file (beside the upload)");
+    const int urc = up.f.get();
+    if (rc != PC_OK) return rc;
+    if (urc != PC_OK) return fail(urc, "pc_add_alignment_file: uploading the columns failed");
+    c.cols.tid = nullptr; c.cols.pos = c.d_pos.p; c.cols.alen = c.d_alen.p; c.cols.flags = c.d_flags8.p; c.cols.nblk = c.d_nblk8.p;
+    c.cols.blk_start = c.d_bs.p; c.cols.blk_len = c.d_bl.p;
+    c.clk.lap("columns to HBM");
+    return PC_OK;
+}
+
+// ---- where the runs of every record sit in the run arrays (blk_off, kept with the file) / go in the run stream: two
+// exclusive sums
+int stage_run_layout(pc_engine *e, StagedFile *sf, StageCall &c) {
+    using namespace pcstage;
+    hipStream_t st = e->stream;
+    const int64_t n = c.in.n, nrun = c.in.nrun;
+    DevBuf<uint8_t> d_tmp;
+    DevBuf<unsigned long long> d_tot;
+    PC_TRY(d_tot.reserve(2));
+    size_t tb = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, c.d_run_at.p, c.d_run_at.p, (int)n + 1, st));
+    PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+    unsigned long long tot[2] = {0, 0};
+    hipError_t he = hipMemsetAsync(d_tot.p, 0, 16, st);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(k_cols_runs, dim3((unsigned)std::min<int64_t>((n + 256) / 256, 4096)), dim3(256), 0, st, c.cols, n, sf->blk_off.p, c.d_run_at.p, d_tot.p);
+        size_t b2 = tb;
+        he = hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, sf->blk_off.p, sf->blk_off.p, (int)n + 1, st);
+    }
+    if (he == hipSuccess) {
+        size_t b2 = tb;
+        he = hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, c.d_run_at.p, c.d_run_at.p, (int)n + 1, st);
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(tot, d_tot.p, 16, hipMemcpyDeviceToHost, st);
+    PC_TRY(finish_phase(st, he, "stage: laying out the runs failed: %s"));
+    if ((int64_t)tot[0] != nrun)
+        return fail(PC_ERR_ARG, (int64_t)tot[0] > nrun ? "run arrays shorter than sum of nblk" : "run arrays longer than sum of nblk (%lld vs %lld)",
+                    (long long)tot[0], (long long)nrun);
+    if (tot[1] >= 0x7fffffffull) return fail(PC_ERR_ARG, "pc_add_alignment_file: more than 2^31-2 aligned runs of multi-run reads per file are not supported");
+    c.nrunrec = (int64_t)tot[1];
+    return PC_OK;
+}
+
+// the verdict of k_cols_pack<true>: defect code in the low byte, the record above it
+int column_defect(unsigned long long verdict) {
+    using namespace pcstage;
+    const long long i = (long long)(verdict >> 8);
+    switch ((int)(verdict & 0xffu)) {
+    case kBadNegPos: return fail(PC_ERR_ARG, "record %lld: negative position", i);
+    case kBadOrder: return fail(PC_ERR_UNSORTED, "records are not sorted by (tid, pos) at record %lld; alignment files must be coordinate sorted", i);
+    case kBadRuns: return fail(PC_ERR_ARG, "record %lld: aligned runs must be non-empty, ascending and non-adjacent", i);
+    case kBadFirstRun: return fail(PC_ERR_ARG, "record %lld: first run must start at pos", i);
+    case kBadRunSum: return fail(PC_ERR_ARG, "record %lld: run lengths do not sum to alen", i);
+    case kBadLenRuns: return fail(PC_ERR_ARG, "record %lld: nblk/alen mismatch", i);
+    default: return fail(PC_ERR_ARG, "record %lld: alignment end beyond 2^31-1", i);
+    }
+}
+
+// the first defect of the contig column, as the message the caller sees (unless a record before it has one of its own)
+int contig_defect(const StageInput &in, int64_t i) {
+    if (in.tid[i] < 0 || in.tid[i] >= in.ntid) return fail(PC_ERR_ARG, "record %lld: tid %lld out of range", (long long)i, (long long)in.tid[i]);
+    if (in.pos[i] < 0) return fail(PC_ERR_ARG, "record %lld: negative position", (long long)i);
+    return fail(PC_ERR_UNSORTED, "records are not sorted by (tid, pos) at record %lld; alignment files must be coordinate sorted", (long long)i);
+}
+
+void take_stats(const std::vector<unsigned long long> &hstats, const std::vector<int32_t> &htid_end, StageCall &c) {
+    using namespace pcstage;
+    FileStats &s = c.stats;
+    for (size_t t = 0; t < s.tid_end.size(); ++t) s.tid_end[t] = c.tid_bounds[t + 1] > c.tid_bounds[t] ? (int64_t)htid_end[t] : 0;
+    for (int k = 0; k < kSpanBins; ++k) {
+        s.span_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtSpan + k)];
+        s.gap_span_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtGap + k)];
+        s.wide_span_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtWide + k)];
+    }
+    for (int k = 0; k < kLenBins; ++k) s.len_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtLen + k)];
+    for (int k = 0; k < kLen1Bins; ++k) s.len1_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtLen1 + k)];
+    s.Wr = std::max(1, (int)hstats[(size_t)kAtMisc + 0]);
+    s.rmin = (int)hstats[(size_t)kAtMisc + 1];
+    s.rmax = s.rmin >= 65536 ? -1 : (int)hstats[(size_t)kAtMisc + 2];
+    s.max_span = std::max<int64_t>(1, (int64_t)hstats[(size_t)kAtMisc + 3]);
+}
+
+// ---- one pass over the columns: validation (caller-owned columns), the 8-byte records, the run-stream records, the
+// ends, the statistics of the file (span and length histograms, per-contig bounds) -- stage_kernels.hip.h.  What
+// depends on the statistics of the WHOLE file -- the window halo `wcap` (a span quantile) and with it the long-span
+// class of a record and its stream word -- is derived afterwards (k_classify).
+int stage_pack(pc_engine *e, StagedFile *sf, StageCall &c) {
+    using namespace pcstage;
+    const StageInput &in = c.in;
+    const int64_t n = in.n;
+    const int ntid = in.ntid;
+    const bool host_cols = in.dev == nullptr;
+    if (n == 0) return PC_OK;
+    hipStream_t st = e->stream;
+    DevBuf<unsigned long long> d_stats;   // the statistics block, then the error word of the validation
+    DevBuf<int32_t> d_last_pos, d_tid_end;
+    DevBuf<int64_t> d_bounds;
+    PC_TRY(d_stats.reserve(kStatWords + 1));
+    PC_TRY(reserve_all((size_t)ntid, d_last_pos, d_tid_end));
+    PC_TRY(d_bounds.reserve((size_t)ntid + 1));
+    std::vector<unsigned long long> hstats((size_t)kStatWords + 1, 0ull);
+    hstats[(size_t)kAtMisc + 1] = 65536ull;   // rmin
+    hstats[(size_t)kStatWords] = ~0ull;       // no defect
+    std::vector<int32_t> htid_end((size_t)ntid);
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
+    hipError_t he = hipMemcpyAsync(d_stats.p, hstats.data(), hstats.size() * 8, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemsetAsync(d_tid_end.p, 0, (size_t)ntid * 4, st);
+    if (he == hipSuccess && host_cols) {
+        he = hipMemcpyAsync(d_bounds.p, c.tid_bounds.data(), ((size_t)ntid + 1) * 8, hipMemcpyHostToDevice, st);
+        if (he == hipSuccess)
+            hipLaunchKernelGGL((k_cols_pack<true>), dim3(grid), dim3(256), 0, st, c.cols, c.n_ok, sf->blk_off.p, c.d_run_at.p, sf->rec.p, c.d_val_in.p, c.d_idx_in.p,
+                               d_tid_end.p, d_stats.p, d_bounds.p, ntid, d_stats.p + kStatWords);
+        // the verdict before anything is derived from the records
+        unsigned long long verdict = ~0ull;
+        if (he == hipSuccess) he = hipMemcpyAsync(&verdict, d_stats.p + kStatWords, 8, hipMemcpyDeviceToHost, st);
+        if (he == hipSuccess) he = hipStreamSynchronize(st);
+        if (he == hipSuccess && verdict != ~0ull) return column_defect(verdict);
+        if (he == hipSuccess && c.n_ok < n) return contig_defect(in, c.n_ok);
+        for (int t = 0; t < ntid; ++t)
+            if (c.tid_bounds[(size_t)t + 1] > c.tid_bounds[(size_t)t]) c.stats.last_pos[(size_t)t] = in.pos[c.tid_bounds[(size_t)t + 1] - 1];
+    } else if (he == hipSuccess) {
+        hipLaunchKernelGGL(k_cols_bounds, dim3((unsigned)((ntid + 256) / 256)), dim3(256), 0, st, c.cols.tid, c.cols.pos, n, ntid, d_bounds.p, d_last_pos.p);
+        hipLaunchKernelGGL((k_cols_pack<false>), dim3(grid), dim3(256), 0, st, c.cols, n, sf->blk_off.p, c.d_run_at.p, sf->rec.p, c.d_val_in.p, c.d_idx_in.p,
+                           d_tid_end.p, d_stats.p, d_bounds.p, ntid, (unsigned long long *)nullptr);
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(hstats.data(), d_stats.p, (size_t)kStatWords * 8, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && !host_cols) he = hipMemcpyAsync(c.tid_bounds.data(), d_bounds.p, ((size_t)ntid + 1) * 8, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(htid_end.data(), d_tid_end.p, (size_t)ntid * 4, hipMemcpyDeviceToHost, st);
+    if (he == hipSuccess && !host_cols) he = hipMemcpyAsync(c.stats.last_pos.data(), d_last_pos.p, (size_t)ntid * 4, hipMemcpyDeviceToHost, st);
+    PC_TRY(finish_phase(st, he, "stage: packing the columns failed: %s"));
+    take_stats(hstats, htid_end, c);
+    return PC_OK;
+}
+
+// ---- what every later kernel sees of the file: the window halo and the length ranges of the LDS entry table
+// (choose_halo), the aligned lengths present, the layout of the linear-index tables (lin_layout) -- host arithmetic
+void stage_halo(StagedFile *sf, StageCall &c) {
+    FileStats &s = c.stats;
+    const StageHalo h = choose_halo(s.span_hist, s.gap_span_hist, s.wide_span_hist, s.len1_hist, s.rmin, s.rmax, c.in.n, kStreamMaxLen);
+    c.wcap = h.wcap;
+    sf->slen_min = h.slen_min; sf->slen_max = h.slen_max; sf->tlen_min = h.tlen_min; sf->tlen_max = h.tlen_max;
+    sf->W = h.W; sf->Wg = h.Wg; sf->Wr = s.Wr; sf->max_span = s.max_span;
+    sf->len_hist.swap(s.len_hist);
+    for (int L = 0; L < 65536; ++L)
+        if (sf->len_hist[(size_t)L]) { sf->len_min = std::min(sf->len_min, L); sf->len_max = std::max(sf->len_max, L); }
+    sf->nrunrec = c.nrunrec;
+    sf->nlin = lin_layout(c.tid_bounds, s.last_pos, s.tid_end, kLinShift, c.lin_off);
+}
+
+// ---- sentinels behind the last record, the aligned runs as {start, length} pairs, then the class and the 4-byte stream
+// word of every record; per workgroup, the members of the three side lists
+int stage_classify(pc_engine *e, StagedFile *sf, StageCall &c) {
+    hipStream_t st = e->stream;
+    const int64_t n = c.in.n, nrun = c.in.nrun;
+    c.nwg = (uint32_t)((n + 255) / 256);
+    const int nside = 3 * (int)c.nwg + 1;
+    DevBuf<uint8_t> d_tmp;
+    size_t tb = 0;
+    if (nrun > 0) PC_TRY(sf->blk.reserve((size_t)nrun));
+    if (nrun == 0) sf->blk_off.release();   // (all zero: no record keeps runs in the run arrays)
+    if (n > 0) {
+        PC_TRY(c.d_side_at.reserve((size_t)nside));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, c.d_side_at.p, c.d_side_at.p, nside, st));
+        PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+    }
+    {   // two excluded headers, eight skip words (whole quads can always be loaded)
+        const uint2 tail_rec[2] = {make_uint2(0u, (uint32_t)PC_FLAG_EXCLUDED << 16), make_uint2(0u, (uint32_t)PC_FLAG_EXCLUDED << 16)};
+        uint32_t tail_stream[8];
+        for (int k = 0; k < 8; ++k) tail_stream[k] = kStreamSkip;
+        if (hipMemcpyAsync(sf->rec.p + n, tail_rec, sizeof(tail_rec), hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(sf->stream.p + n, tail_stream, sizeof(tail_stream), hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return fail(PC_ERR_HIP, "pc_add_alignment_file: staging the sentinels failed");
+    }
+    if (nrun > 0)
+        hipLaunchKernelGGL(k_zip_runs, dim3((unsigned)((nrun + kWG - 1) / kWG)), dim3(kWG), 0, st, c.cols.blk_start, c.cols.blk_len, nrun, sf->blk.p);
+    if (n == 0) return PC_OK;
+    uint32_t at[4] = {0, 0, 0, 0};
+    hipError_t he = hipMemsetAsync(c.d_side_at.p + 3 * (size_t)c.nwg, 0, 4, st);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(pcstage::k_classify, dim3(c.nwg), dim3(256), 0, st, sf->rec.p, n, sf->blk_off.p, sf->blk.p, c.wcap, sf->stream.p, c.d_side_at.p);
+        he = hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, c.d_side_at.p, c.d_side_at.p, nside, st);
+    }
+    for (int k = 1; k <= 3 && he == hipSuccess; ++k) he = hipMemcpyAsync(&at[k], c.d_side_at.p + (size_t)k * c.nwg, 4, hipMemcpyDeviceToHost, st);
+    PC_TRY(finish_phase(st, he, "pc_add_alignment_file: deriving the record stream failed: %s"));
+    for (int k = 0; k < 3; ++k) c.side_total[k] = at[k + 1] - at[k];
+    return PC_OK;
+}
+
+// ---- side lists and linear-index tables, on the GPU (pc_kernels.hip.h, "side lists"): the records are there
+// already; from the host come only the two small per-contig tables
+struct SideList {   // one of the three lists: its members in record order, and where its entries go
+    const uint32_t *idx;
+    size_t m;
+    uint4 *rec;
+    int4 *runs;
+    int32_t *tid;       // contig of every entry (the long list only)
+    uint2 *wide;        // true {length, run count} of every entry (files with wide records; not the gapped list)
+    int32_t *pmax;      // running maximum of the ends (NULL: the list has none)
+    int64_t *bounds;    // per-contig ranges
+};
+
+struct SideScratch {   // the working arrays of the running maxima
+    DevBuf<unsigned long long> d_key, d_key_scanned;
+    DevBuf<uint8_t> d_tmp;
+};
+
+dim3 grid_of(size_t m) { return dim3((unsigned)((m + kWG - 1) / kWG)); }
+
+// the entries of one list, and the running maximum of their ends if the list has one
+hipError_t fill_side_list(pc_engine *e, const StagedFile *sf, const StageCall &c, const SideList &l, SideScratch &w) {
+    if (!l.m) return hipSuccess;
+    hipStream_t st = e->stream;
+    hipLaunchKernelGGL(k_side_fill, grid_of(l.m), dim3(kWG), 0, st, l.idx, (int64_t)l.m, sf->rec.p, sf->blk_off.p, sf->blk.p, sf->tid_bounds.p, c.in.ntid,
+                       sf->wide_rec.p, sf->wide_val.p, c.in.n_wide, l.rec, l.runs, l.tid, l.pmax ? w.d_key.p : nullptr, l.wide);
+    if (!l.pmax) return hipSuccess;
+    size_t tb = w.d_tmp.cap;
+    const hipError_t he = hipcub::DeviceScan::InclusiveScan(w.d_tmp.p, tb, w.d_key.p, w.d_key_scanned.p, hipcub::Max(), (int)l.m, st);
+    if (he == hipSuccess) hipLaunchKernelGGL(k_unpack_pmax, grid_of(l.m), dim3(kWG), 0, st, w.d_key_scanned.p, (int64_t)l.m, l.pmax);
+    return he;
+}
+
+int reserve_side_lists(StagedFile *sf, const StageCall &c, size_t nlong, size_t ngap, size_t nxlong) {
+    const size_t ntid1 = (size_t)c.in.ntid + 1, nlin = sf->nlin;
+    const bool wide = c.in.n_wide != 0;
+    PC_TRY(reserve_all(ntid1, sf->tid_bounds, sf->lin_off, sf->long_tid_bounds, sf->gap_tid_bounds));
+    PC_TRY(reserve_all(nlong, sf->long_idx, sf->long_rec, sf->long_runs, sf->long_tid, sf->long_pmax));
+    PC_TRY(reserve_all(ngap, sf->gap_rec, sf->gap_runs));
+    PC_TRY(reserve_all(nxlong, sf->xlong_rec, sf->xlong_runs));
+    if (wide) PC_TRY(sf->long_wide.reserve(nlong));
+    if (wide) PC_TRY(sf->xlong_wide.reserve(nxlong));
+    PC_TRY(reserve_all(nlin, sf->lin_tab, sf->glin_tab, sf->llin_tab, sf->plin_tab));
+    return nxlong ? reserve_all(nlin, sf->xllin_tab, sf->xplin_tab) : PC_OK;
+}
+
+int stage_side_lists(pc_engine *e, StagedFile *sf, StageCall &c) {
+    hipStream_t st = e->stream;
+    const int64_t n = c.in.n;
+    const int ntid = c.in.ntid;
+    const size_t nlong = c.side_total[0], ngap = c.side_total[1], nxlong = c.side_total[2], nlin = sf->nlin;
+    sf->nlong = (int64_t)nlong;
+    sf->ngap = (int64_t)ngap;
+    sf->nxlong = (int64_t)nxlong;
+    DevBuf<uint32_t> d_gap_idx, d_xlong_idx;   // the gapped and the extra-long list keep no member array
+    DevBuf<int64_t> d_xlong_bounds;
+    DevBuf<int32_t> d_xlong_pmax;
+    SideScratch w;
+    PC_TRY(reserve_side_lists(sf, c, nlong, ngap, nxlong));
+    PC_TRY(d_gap_idx.reserve(ngap));
+    PC_TRY(reserve_all(nxlong, d_xlong_idx, d_xlong_pmax));
+    PC_TRY(d_xlong_bounds.reserve((size_t)ntid + 1));
+    PC_TRY(reserve_all(std::max(nlong, nxlong), w.d_key, w.d_key_scanned));
+    size_t need = 0;
+    HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need, w.d_key.p, w.d_key_scanned.p, hipcub::Max(), (int)std::max(nlong, nxlong), st));
+    PC_TRY(w.d_tmp.reserve(std::max<size_t>(need, 16)));
+    const SideList lists[3] = {
+        {sf->long_idx.p, nlong, sf->long_rec.p, sf->long_runs.p, sf->long_tid.p, c.in.n_wide ? sf->long_wide.p : nullptr, sf->long_pmax.p, sf->long_tid_bounds.p},
+        {d_gap_idx.p, ngap, sf->gap_rec.p, sf->gap_runs.p, nullptr, nullptr, nullptr, sf->gap_tid_bounds.p},
+        {d_xlong_idx.p, nxlong, sf->xlong_rec.p, sf->xlong_runs.p, nullptr, c.in.n_wide ? sf->xlong_wide.p : nullptr, d_xlong_pmax.p, d_xlong_bounds.p}};
+    hipError_t he = hipMemcpyAsync(sf->tid_bounds.p, c.tid_bounds.data(), ((size_t)ntid + 1) * 8, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess) he = hipMemcpyAsync(sf->lin_off.p, c.lin_off.data(), ((size_t)ntid + 1) * 8, hipMemcpyHostToDevice, st);
+    if (he == hipSuccess && n > 0 && nlong + ngap + nxlong > 0)   // members of the three lists, in record order
+        hipLaunchKernelGGL(pcstage::k_side_select, dim3(c.nwg), dim3(256), 0, st, sf->rec.p, n, c.d_side_at.p, c.nwg, sf->long_idx.p, d_gap_idx.p, d_xlong_idx.p);
+    // entries and running maxima of the ends, list by list; then the per-contig ranges of every list
+    for (int k = 0; k < 3 && he == hipSuccess; ++k) he = fill_side_list(e, sf, c, lists[k], w);
+    for (int k = 0; k < 3 && he == hipSuccess; ++k)
+        hipLaunchKernelGGL(k_list_bounds, grid_of((size_t)ntid + 1), dim3(kWG), 0, st, lists[k].idx, (int64_t)lists[k].m, sf->tid_bounds.p, ntid, lists[k].bounds);
+    // the linear-index tables: one bisection per table entry
+    if (he == hipSuccess && nlin) {
+        const dim3 gl = grid_of(nlin);
+        hipLaunchKernelGGL((k_lin_table<0>), gl, dim3(kWG), 0, st, (const void *)sf->rec.p, sf->tid_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->lin_tab.p);
+        hipLaunchKernelGGL((k_lin_table<1>), gl, dim3(kWG), 0, st, (const void *)sf->gap_rec.p, sf->gap_tid_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->glin_tab.p);
+        hipLaunchKernelGGL((k_lin_table<1>), gl, dim3(kWG), 0, st, (const void *)sf->long_rec.p, sf->long_tid_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->llin_tab.p);
+        hipLaunchKernelGGL((k_lin_table<2>), gl, dim3(kWG), 0, st, (const void *)sf->long_pmax.p, sf->long_tid_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->plin_tab.p);
+        if (nxlong) {
+            hipLaunchKernelGGL((k_lin_table<1>), gl, dim3(kWG), 0, st, (const void *)sf->xlong_rec.p, d_xlong_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->xllin_tab.p);
+            hipLaunchKernelGGL((k_lin_table<2>), gl, dim3(kWG), 0, st, (const void *)d_xlong_pmax.p, d_xlong_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->xplin_tab.p);
+        }
+    }
+    return finish_phase(st, he, "stage: building the side lists failed: %s");
+}
+
+// ---- run stream: sorted by (contig, run start) on the GPU (radix sort of the 64-bit keys, the 8-byte
+// records and their record indices permuted along), then its linear index by one bisection per bucket
+int stage_run_stream(pc_engine *e, StagedFile *sf, StageCall &c) {
+    const size_t nrunrec = (size_t)c.nrunrec, nlin = sf->nlin;
+    if (!nrunrec) return PC_OK;
+    hipStream_t st = e->stream;
+    const int ntid = c.in.ntid;
+    DevBuf<unsigned long long> d_key, d_key_sorted;
+    DevBuf<uint32_t> d_ord, d_ord_sorted;
+    DevBuf<uint8_t> d_tmp;
+    PC_TRY(reserve_all(nrunrec, d_key, d_ord, d_key_sorted, d_ord_sorted, sf->run_recidx));
+    PC_TRY(sf->run_rec.reserve(nrunrec + 1));
+    PC_TRY(sf->rlin_tab.reserve(nlin));
+    size_t tmp_bytes = 0;
+    const int end_bit = 32 + (ntid > 1 ? 32 - __builtin_clz((unsigned)(ntid - 1)) : 1);
+    hipError_t he = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key.p, d_key_sorted.p, d_ord.p, d_ord_sorted.p, (int)nrunrec, 0, end_bit, st);
+    if (he != hipSuccess) return fail(PC_ERR_HIP, "stage: sorting the run stream failed: %s", hipGetErrorString(he));
+    PC_TRY(d_tmp.reserve(tmp_bytes));
+    const dim3 grid = grid_of(nrunrec);
+    // sort keys (contig << 32 | run start) and the identity permutation, made on the GPU
+    hipLaunchKernelGGL(k_run_keys, grid, dim3(kWG), 0, st, c.d_val_in.p, c.d_idx_in.p, (int64_t)nrunrec, sf->tid_bounds.p, ntid, d_key.p, d_ord.p);
+    he = hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, d_key.p, d_key_sorted.p, d_ord.p, d_ord_sorted.p, (int)nrunrec, 0, end_bit, st);   // stable: equal starts keep record order
+    if (he != hipSuccess) return finish_phase(st, he, "stage: sorting the run stream failed: %s");
+    hipLaunchKernelGGL(k_run_gather, grid, dim3(kWG), 0, st, d_ord_sorted.p, c.d_val_in.p, c.d_idx_in.p, (int64_t)nrunrec, sf->run_rec.p, sf->run_recidx.p);
+    hipLaunchKernelGGL(k_run_lin, grid_of(nlin), dim3(kWG), 0, st, d_key_sorted.p, (int64_t)nrunrec, sf->lin_off.p, ntid, (int64_t)nlin, sf->rlin_tab.p);
+    const uint2 tail_run = make_uint2(0u, (uint32_t)PC_FLAG_EXCLUDED << 24);
+    he = hipMemcpyAsync(sf->run_rec.p + nrunrec, &tail_run, sizeof(tail_run), hipMemcpyHostToDevice, st);
+    return finish_phase(st, he, "stage: building the run stream failed");
+}
+
+int stage_file(pc_engine *e, const StageInput &in) {
+    PC_TRY(stage_check(e, in));
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);   // the file's arrays and the temporaries of staging are recycled through the engine's pool
+    StageCall c(in);
+    StagedFile *sf = new StagedFile();
+    struct Owner { StagedFile *p; ~Owner() { delete p; } } owner{sf};   // (until the file is the engine's)
+    sf->n = in.n;
+    sf->nrun = in.nrun;
+    if (in.dev) {   // the decoder's columns: only the wide records and the per-record arrays are missing
+        c.cols = *in.dev;
+        PC_TRY(upload_wide_records(e, sf, c));
+        PC_TRY(reserve_record_arrays(sf, c));
+    } else PC_TRY(stage_upload(e, sf, c));   // (laps: column buffers, contig bounds, arrays of the file, columns to HBM)
+    PC_TRY(stage_run_layout(e, sf, c));
+    c.clk.lap("run layout (GPU)");
+    PC_TRY(reserve_all((size_t)c.nrunrec, c.d_val_in, c.d_idx_in));
+    c.clk.lap("allocations");
+    PC_TRY(stage_pack(e, sf, c));
+    c.clk.lap("validate + pack (GPU)");
+    stage_halo(sf, c);
+    PC_TRY(stage_classify(e, sf, c));
+    c.clk.lap("record stream (GPU)");
+    PC_TRY(stage_side_lists(e, sf, c));
+    c.clk.lap("side lists + linear index (GPU)");
+    PC_TRY(stage_run_stream(e, sf, c));
+    c.clk.lap("run stream (GPU sort)");
+    PC_TRY(build_compact_stream(e, sf, in.ntid));
+    c.clk.lap("compact stream (GPU)");
+    owner.p = nullptr;
+    e->files.push_back(sf);
+    e->ntid = in.ntid;
+    e->files_dirty = true;
+    e->work_generation += 1;
+    return PC_OK;
+}
+
+} // namespace
+
+extern "C" {
 
 int pc_add_alignment_file_wide(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid, const int32_t *pos,
                                const uint16_t *alen, const uint8_t *flags, const uint8_t *nblk, int64_t nrun,
                                const int32_t *blk_start, const int32_t *blk_len, int64_t n_wide, const int64_t *wide_idx,
                                const int32_t *wide_alen, const int32_t *wide_nblk) {
-    return stage_file(e, n, ntid, tid, pos, alen, flags, nblk, nrun, blk_start, blk_len, n_wide, wide_idx, wide_alen, wide_nblk, nullptr);
-}
-
-static int stage_file(pc_engine *e, int64_t n, int32_t ntid, const int32_t *tid, const int32_t *pos,
-                      const uint16_t *alen, const uint8_t *flags, const uint8_t *nblk, int64_t nrun,
-                      const int32_t *blk_start, const int32_t *blk_len, int64_t n_wide, const int64_t *wide_idx,
-                      const int32_t *wide_alen, const int32_t *wide_nblk, const pcstage::DevCols *dev) {
-    if (!e) return fail(PC_ERR_ARG, "engine is NULL");
-    if (n < 0 || ntid <= 0 || nrun < 0) return fail(PC_ERR_ARG, "pc_add_alignment_file: bad sizes");
-    if (!dev && n > 0 && (!tid || !pos || !alen || !flags || !nblk)) return fail(PC_ERR_ARG, "pc_add_alignment_file: NULL array");
-    if (!dev && nrun > 0 && (!blk_start || !blk_len)) return fail(PC_ERR_ARG, "pc_add_alignment_file: NULL run array");
-    if (n_wide < 0 || (n_wide > 0 && (!wide_idx || !wide_alen || !wide_nblk))) return fail(PC_ERR_ARG, "pc_add_alignment_file: bad wide-record arrays");
-    for (int64_t k = 0; k < n_wide && !dev; ++k) {
-        const int64_t i = wide_idx[k];
-        if (i < 0 || i >= n || (k > 0 && i <= wide_idx[k - 1])) return fail(PC_ERR_ARG, "pc_add_alignment_file: wide_idx must be ascending record indices");
-        if (alen[i] != 0xffffu || nblk[i] != 0xffu) return fail(PC_ERR_ARG, "pc_add_alignment_file: record %lld is listed as wide but its alen / nblk are not 65535 / 255", (long long)i);
-        if (wide_alen[k] < 0 || wide_nblk[k] < 0 || (wide_nblk[k] == 0) != (wide_alen[k] == 0) || wide_nblk[k] > wide_alen[k])
-            return fail(PC_ERR_ARG, "pc_add_alignment_file: record %lld: bad wide alen / nblk", (long long)i);
-    }
-    if (n >= (int64_t)0x7fffffff || nrun >= (int64_t)0xffffffffu)
-        return fail(PC_ERR_ARG, "pc_add_alignment_file: more than 2^31-2 records per file are not supported");
-    if (!e->files.empty() && ntid != e->ntid)
-        return fail(PC_ERR_ARG, "pc_add_alignment_file: all files must use the same reference list (ntid %d vs %d)", ntid, e->ntid);
-    HIP_TRY(hipSetDevice(e->device));
-    PoolScope pool_scope(&e->pool);   // the file's arrays and the temporaries of staging are recycled through the engine's pool
-
-    hipStream_t st = e->stream;
-    StageClock clk;
-
-    // ---- caller-owned columns: up to HBM as they are.  The host moves bytes and looks at ONE column, the contigs: sorted,
-    // that column is ntid + 1 record bounds, so it does not travel -- a streaming comparison finds the bounds (and the first
-    // record out of order or out of range) on the worker threads while the other columns cross PCIe through the ring.
-    const bool host_cols = dev == nullptr;
-    DevBuf<int32_t> d_pos, d_bs, d_bl;
-    DevBuf<uint16_t> d_alen;
-    DevBuf<uint8_t> d_flags8, d_nblk8;
-    DevBuf<uint32_t> d_wr;
-    DevBuf<uint2> d_wv;
-    pcstage::DevCols hc;
-    std::vector<int64_t> tid_bounds((size_t)ntid + 1, 0);
-    int64_t n_ok = n;   // records before the first defect of the contig column
-    StagedFile *sf = new StagedFile();
-    struct Owner { StagedFile *p; ~Owner() { delete p; } } owner{sf};   // (until the file is the engine's)
-    sf->n = n;
-    sf->nrun = nrun;
-    DevBuf<uint32_t> d_run_at;
-    if (host_cols) {
-        int rc = d_pos.reserve((size_t)n + 1);
-        if (rc == PC_OK) rc = d_alen.reserve((size_t)n + 1);
-        if (rc == PC_OK) rc = d_flags8.reserve((size_t)n + 1);
-        if (rc == PC_OK) rc = d_nblk8.reserve((size_t)n + 1);
-        if (rc == PC_OK) rc = d_bs.reserve((size_t)nrun + 1);
-        if (rc == PC_OK) rc = d_bl.reserve((size_t)nrun + 1);
-        if (rc != PC_OK) return rc;
-        // (the ring fills these blocks on ITS stream: a block the pool recycled may still be read or written by work
-        // queued on the engine's stream -- a plan buffer that grew inside an asynchronous pc_count -- and every other user of
-        // the pool is ordered on that stream; the ring is the exception, so it starts behind everything queued there)
-        HIP_TRY(hipStreamSynchronize(st));
-        size_t piece = TransferRing::kPiece;
-        if (const char *env = getenv("PC_STAGE_SLICE")) piece = (size_t)std::max<int64_t>(1, std::min<int64_t>(atoll(env), (int64_t)(TransferRing::kPiece / 4))) * 4; // test knob: tiny pieces
-        std::vector<TransferJob> jobs;   // (what the first kernel reads goes first)
-        jobs.push_back({d_nblk8.p, nblk, (size_t)n});
-        jobs.push_back({d_alen.p, alen, (size_t)n * 2});
-        jobs.push_back({d_pos.p, pos, (size_t)n * 4});
-        jobs.push_back({d_flags8.p, flags, (size_t)n});
-        jobs.push_back({d_bs.p, blk_start, (size_t)nrun * 4});
-        jobs.push_back({d_bl.p, blk_len, (size_t)nrun * 4});
-        struct Joined { std::future<int> f; ~Joined() { if (f.valid()) f.wait(); } } up;   // (joined on every way out, before the buffers go)
-        clk.lap("column buffers");
-        const int devno = e->device;
-        up.f = std::async(std::launch::async, [devno, &jobs, piece]() -> int {
-            StageClock uclk;
-            const int r = TransferRing::of(devno).run(devno, jobs, piece, getenv("PC_STAGE_SLICE") != nullptr);
-            uclk.lap("  (upload thread: ring)");
-            return r;
-        });
-        n_ok = scan_contigs(tid, n, ntid, stage_threads(n), tid_bounds);
-        clk.lap("contig bounds");
-        if (n_wide > 0) {
-            std::vector<uint32_t> wr((size_t)n_wide);
-            std::vector<uint2> wv((size_t)n_wide);
-            for (int64_t k = 0; k < n_wide; ++k) { wr[(size_t)k] = (uint32_t)wide_idx[k]; wv[(size_t)k] = make_uint2((uint32_t)wide_alen[k], (uint32_t)wide_nblk[k]); }
-            rc = d_wr.upload(wr, st);
-            if (rc == PC_OK) rc = d_wv.upload(wv, st);
-            if (rc == PC_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(PC_ERR_HIP, "stage: uploading the wide records failed");
-        }
-        // while the columns cross PCIe: the arrays of the staged file whose sizes follow from the record count alone (a
-        // billion records: 20 GB of hipMalloc, 0.12 s when the pool has no such blocks -- a third of the call)
-        if (rc == PC_OK) rc = sf->blk_off.reserve((size_t)n + 1);
-        if (rc == PC_OK) rc = d_run_at.reserve((size_t)n + 1);
-        if (rc == PC_OK) rc = sf->rec.reserve((size_t)n + 2);
-        if (rc == PC_OK) rc = sf->stream.reserve((size_t)n + 8);
-        clk.lap("arrays of the file (beside the upload)");
-        const int urc = up.f.get();
-        if (rc != PC_OK) return rc;
-        if (urc != PC_OK) return fail(urc, "pc_add_alignment_file: uploading the columns failed");
-        hc.tid = nullptr; hc.pos = d_pos.p; hc.alen = d_alen.p; hc.flags = d_flags8.p; hc.nblk = d_nblk8.p;
-        hc.blk_start = d_bs.p; hc.blk_len = d_bl.p;
-        hc.wide_rec = d_wr.p; hc.wide_val = d_wv.p; hc.n_wide = n_wide;
-        dev = &hc;
-        clk.lap("columns to HBM");
-    }
-    // the first defect of the contig column, as the message the caller sees (unless a record before it has one of its own)
-    auto contig_defect = [&]() -> int {
-        const int64_t i = n_ok;
-        if (tid[i] < 0 || tid[i] >= ntid) return fail(PC_ERR_ARG, "record %lld: tid %lld out of range", (long long)i, (long long)tid[i]);
-        if (pos[i] < 0) return fail(PC_ERR_ARG, "record %lld: negative position", (long long)i);
-        return fail(PC_ERR_UNSORTED, "records are not sorted by (tid, pos) at record %lld; alignment files must be coordinate sorted", (long long)i);
-    };
-
-    // ---- where the runs of every record sit in the run arrays (blk_off, kept with the file) / go in the run stream: two
-    // exclusive sums
-    int64_t nrunrec_total = 0;
-    {
-        using namespace pcstage;
-        DevBuf<uint8_t> d_tmp;
-        DevBuf<unsigned long long> d_tot;
-        int r = sf->blk_off.reserve((size_t)n + 1);
-        if (r == PC_OK) r = d_run_at.reserve((size_t)n + 1);
-        if (r == PC_OK) r = d_tot.reserve(2);
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_run_at.p, d_run_at.p, (int)n + 1, st));
-        if (r == PC_OK) r = d_tmp.reserve(std::max<size_t>(tb, 16));
-        if (r != PC_OK) return r;
-        HIP_TRY(hipMemsetAsync(d_tot.p, 0, 16, st));
-        hipLaunchKernelGGL(k_cols_runs, dim3((unsigned)std::min<int64_t>((n + 256) / 256, 4096)), dim3(256), 0, st, *dev, n, sf->blk_off.p, d_run_at.p, d_tot.p);
-        size_t b2 = tb;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, sf->blk_off.p, sf->blk_off.p, (int)n + 1, st));
-        b2 = tb;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, d_run_at.p, d_run_at.p, (int)n + 1, st));
-        unsigned long long tot[2] = {0, 0};
-        HIP_TRY(hipMemcpyAsync(tot, d_tot.p, 16, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));   // (d_tmp goes out of scope)
-        if ((int64_t)tot[0] != nrun)
-            return fail(PC_ERR_ARG, (int64_t)tot[0] > nrun ? "run arrays shorter than sum of nblk" : "run arrays longer than sum of nblk (%lld vs %lld)",
-                        (long long)tot[0], (long long)nrun);
-        if (tot[1] >= 0x7fffffffull) return fail(PC_ERR_ARG, "pc_add_alignment_file: more than 2^31-2 aligned runs of multi-run reads per file are not supported");
-        nrunrec_total = (int64_t)tot[1];
-    }
-    clk.lap("run layout (GPU)");
-    // run-stream records {run start, len | cum << 8 | L << 16 | flags << 24} and the record of every run, in record order
-    DevBuf<uint2> d_val_in;
-    DevBuf<uint32_t> d_idx_in;
-    int rc = sf->rec.reserve((size_t)n + 2);
-    if (rc == PC_OK && nrunrec_total > 0) rc = d_val_in.reserve((size_t)nrunrec_total);
-    if (rc == PC_OK && nrunrec_total > 0) rc = d_idx_in.reserve((size_t)nrunrec_total);
-    if (rc == PC_OK) rc = sf->stream.reserve((size_t)n + 8);
-    if (rc != PC_OK) return rc;
-    clk.lap("allocations");
-
-    // ---- one pass over the columns: validation (caller-owned columns), the 8-byte records, the run-stream records, the
-    // ends, the statistics of the file (span and length histograms, per-contig bounds) -- stage_kernels.hip.h.  What
-    // depends on the statistics of the WHOLE file -- the window halo `wcap` (a span quantile) and with it the long-span
-    // class of a record and its stream word -- is derived afterwards (k_classify).
-    std::vector<int64_t> span_hist(1026, 0), gap_span_hist(1026, 0), wide_span_hist(1026, 0), len_hist(65536, 0), len1_hist(256, 0), tid_end((size_t)ntid, 0);
-    std::vector<int32_t> last_pos((size_t)ntid, -1);   // start of the last record of every contig
-    int Wr = 1, rmin = 65536, rmax = -1;
-    int64_t max_span = 1;
-    if (n > 0) {
-        using namespace pcstage;
-        DevBuf<unsigned long long> d_stats;   // the statistics block, then the error word of the validation
-        DevBuf<int32_t> d_last_pos, d_tid_end;
-        DevBuf<int64_t> d_bounds;
-        rc = d_stats.reserve(kStatWords + 1);
-        if (rc == PC_OK) rc = d_last_pos.reserve((size_t)ntid);
-        if (rc == PC_OK) rc = d_tid_end.reserve((size_t)ntid);
-        if (rc == PC_OK) rc = d_bounds.reserve((size_t)ntid + 1);
-        if (rc != PC_OK) return rc;
-        std::vector<unsigned long long> hstats((size_t)kStatWords + 1, 0ull);
-        hstats[(size_t)kAtMisc + 1] = 65536ull;   // rmin
-        hstats[(size_t)kStatWords] = ~0ull;       // no defect
-        std::vector<int32_t> htid_end((size_t)ntid);
-        const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 2048);
-        hipError_t he = hipMemcpyAsync(d_stats.p, hstats.data(), hstats.size() * 8, hipMemcpyHostToDevice, st);
-        if (he == hipSuccess) he = hipMemsetAsync(d_tid_end.p, 0, (size_t)ntid * 4, st);
-        if (he == hipSuccess && host_cols) {
-            he = hipMemcpyAsync(d_bounds.p, tid_bounds.data(), ((size_t)ntid + 1) * 8, hipMemcpyHostToDevice, st);
-            if (he == hipSuccess)
-                hipLaunchKernelGGL((k_cols_pack<true>), dim3(grid), dim3(256), 0, st, *dev, n_ok, sf->blk_off.p, d_run_at.p, sf->rec.p, d_val_in.p, d_idx_in.p, d_tid_end.p,
-                                   d_stats.p, d_bounds.p, ntid, d_stats.p + kStatWords);
-            // the verdict before anything is derived from the records
-            unsigned long long verdict = ~0ull;
-            if (he == hipSuccess) he = hipMemcpyAsync(&verdict, d_stats.p + kStatWords, 8, hipMemcpyDeviceToHost, st);
-            if (he == hipSuccess) he = hipStreamSynchronize(st);
-            if (he == hipSuccess && verdict != ~0ull) {
-                const long long i = (long long)(verdict >> 8);
-                switch ((int)(verdict & 0xffu)) {
-                case kBadNegPos: return fail(PC_ERR_ARG, "record %lld: negative position", i);
-                case kBadOrder: return fail(PC_ERR_UNSORTED, "records are not sorted by (tid, pos) at record %lld; alignment files must be coordinate sorted", i);
-                case kBadRuns: return fail(PC_ERR_ARG, "record %lld: aligned runs must be non-empty, ascending and non-adjacent", i);
-                case kBadFirstRun: return fail(PC_ERR_ARG, "record %lld: first run must start at pos", i);
-                case kBadRunSum: return fail(PC_ERR_ARG, "record %lld: run lengths do not sum to alen", i);
-                case kBadLenRuns: return fail(PC_ERR_ARG, "record %lld: nblk/alen mismatch", i);
-                default: return fail(PC_ERR_ARG, "record %lld: alignment end beyond 2^31-1", i);
-                }
-            }
-            if (he == hipSuccess && n_ok < n) return contig_defect();
-            for (int t = 0; t < ntid; ++t)
-                if (tid_bounds[(size_t)t + 1] > tid_bounds[(size_t)t]) last_pos[(size_t)t] = pos[tid_bounds[(size_t)t + 1] - 1];
-        } else if (he == hipSuccess) {
-            hipLaunchKernelGGL(k_cols_bounds, dim3((unsigned)((ntid + 256) / 256)), dim3(256), 0, st, dev->tid, dev->pos, n, ntid, d_bounds.p, d_last_pos.p);
-            hipLaunchKernelGGL((k_cols_pack<false>), dim3(grid), dim3(256), 0, st, *dev, n, sf->blk_off.p, d_run_at.p, sf->rec.p, d_val_in.p, d_idx_in.p, d_tid_end.p,
-                               d_stats.p, d_bounds.p, ntid, (unsigned long long *)nullptr);
-        }
-        if (he == hipSuccess) he = hipMemcpyAsync(hstats.data(), d_stats.p, (size_t)kStatWords * 8, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess && !host_cols) he = hipMemcpyAsync(tid_bounds.data(), d_bounds.p, ((size_t)ntid + 1) * 8, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipMemcpyAsync(htid_end.data(), d_tid_end.p, (size_t)ntid * 4, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess && !host_cols) he = hipMemcpyAsync(last_pos.data(), d_last_pos.p, (size_t)ntid * 4, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipGetLastError();
-        if (he == hipSuccess) he = hipStreamSynchronize(st);
-        if (he != hipSuccess) return fail(PC_ERR_HIP, "stage: packing the columns failed: %s", hipGetErrorString(he));
-        for (int t = 0; t < ntid; ++t)
-            tid_end[(size_t)t] = tid_bounds[(size_t)t + 1] > tid_bounds[(size_t)t] ? (int64_t)htid_end[(size_t)t] : 0;
-        for (int k = 0; k < kSpanBins; ++k) {
-            span_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtSpan + k)];
-            gap_span_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtGap + k)];
-            wide_span_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtWide + k)];
-        }
-        for (int k = 0; k < kLenBins; ++k) len_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtLen + k)];
-        for (int k = 0; k < kLen1Bins; ++k) len1_hist[(size_t)k] = (int64_t)hstats[(size_t)(kAtLen1 + k)];
-        Wr = std::max(1, (int)hstats[(size_t)kAtMisc + 0]);
-        rmin = (int)hstats[(size_t)kAtMisc + 1];
-        rmax = rmin >= 65536 ? -1 : (int)hstats[(size_t)kAtMisc + 2];
-        max_span = std::max<int64_t>(1, (int64_t)hstats[(size_t)kAtMisc + 3]);
-    }
-    clk.lap("validate + pack (GPU)");
-    // the window halo W: the smallest span bound (>= 64, <= 1024) that covers >= 99.5% of the records; longer
-    // (spliced) reads go through the long-read path
-    int wcap = 64;
-    {
-        int64_t cum = 0;
-        const int64_t need = n - n / 200;
-        int s0 = 0;
-        for (; s0 <= 1024; ++s0) {
-            cum += span_hist[(size_t)s0];
-            if (cum >= need) break;
-        }
-        wcap = std::max(64, std::min(s0, 1024));
-    }
-    int W = 1, Wg = 1;   // the longest span inside the halo: of any record, of a record of the gapped-record list
-    for (int s0 = 1; s0 <= wcap; ++s0) {
-        if (span_hist[(size_t)s0] > wide_span_hist[(size_t)s0]) W = s0;
-        if (gap_span_hist[(size_t)s0]) Wg = s0;
-    }
-    {   // aligned lengths the 4-byte stream carries (single-run records inside the halo), and those of the run stream
-        int smin = 65536, smax = -1;
-        for (int L = 0; L <= std::min(wcap, kStreamMaxLen); ++L)
-            if (len1_hist[(size_t)L]) { smin = std::min(smin, L); smax = std::max(smax, L); }
-        const int tmin = std::min(smin, rmin), tmax = std::max(smax, rmax);
-        sf->slen_min = smax >= smin ? smin : 0;
-        sf->slen_max = smax >= smin ? smax : 0;
-        sf->tlen_min = tmax >= tmin ? tmin : 0;
-        sf->tlen_max = tmax >= tmin ? tmax : 0;
-    }
-    sf->W = W;
-    sf->Wg = Wg;
-    sf->Wr = Wr;
-    sf->max_span = max_span;
-    sf->len_hist.swap(len_hist);
-    for (int L = 0; L < 65536; ++L)
-        if (sf->len_hist[(size_t)L]) { sf->len_min = std::min(sf->len_min, L); sf->len_max = std::max(sf->len_max, L); }
-
-    {   // sentinels behind the last record: two excluded headers, eight skip words (whole quads can always be loaded)
-        const uint2 tail_rec[2] = {make_uint2(0u, (uint32_t)PC_FLAG_EXCLUDED << 16), make_uint2(0u, (uint32_t)PC_FLAG_EXCLUDED << 16)};
-        uint32_t tail_stream[8];
-        for (int k = 0; k < 8; ++k) tail_stream[k] = kStreamSkip;
-        if (hipMemcpyAsync(sf->rec.p + n, tail_rec, sizeof(tail_rec), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipMemcpyAsync(sf->stream.p + n, tail_stream, sizeof(tail_stream), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-            hipStreamSynchronize(e->stream) != hipSuccess)
-            return fail(PC_ERR_HIP, "pc_add_alignment_file: staging the sentinels failed");
-    }
-    if (n_wide > 0) {   // the wide records by record index: what the per-record kernels look up
-        if (host_cols) {   // (they went up with the columns)
-            sf->wide_rec.swap(d_wr);
-            sf->wide_val.swap(d_wv);
-        } else {
-            std::vector<uint32_t> wr((size_t)n_wide);
-            std::vector<uint2> wv((size_t)n_wide);
-            for (int64_t k = 0; k < n_wide; ++k) { wr[(size_t)k] = (uint32_t)wide_idx[k]; wv[(size_t)k] = make_uint2((uint32_t)wide_alen[k], (uint32_t)wide_nblk[k]); }
-            rc = sf->wide_rec.upload(wr, e->stream);
-            if (rc == PC_OK) rc = sf->wide_val.upload(wv, e->stream);
-            if (rc == PC_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(PC_ERR_HIP, "stage: sync failed");
-            if (rc != PC_OK) return rc;
-        }
-        sf->nwide = n_wide;
-    }
-    // the aligned runs as {start, length} pairs
-    if (nrun > 0) {
-        PC_TRY(sf->blk.reserve((size_t)nrun));
-        hipLaunchKernelGGL(k_zip_runs, dim3((unsigned)((nrun + kWG - 1) / kWG)), dim3(kWG), 0, e->stream, dev->blk_start, dev->blk_len, nrun, sf->blk.p);
-    }
-    if (nrun == 0) sf->blk_off.release();   // (all zero: no record keeps runs in the run arrays)
-    // the class and the 4-byte stream word of every record; per workgroup, the members of the three side lists
-    const uint32_t nwg = (uint32_t)((n + 255) / 256);
-    DevBuf<uint32_t> d_side_at;   // [3 * nwg + 1]: counts, then their exclusive sum
-    uint32_t side_total[3] = {0, 0, 0};
-    if (n > 0) {
-        using namespace pcstage;
-        DevBuf<uint8_t> d_tmp;
-        const int nside = 3 * (int)nwg + 1;
-        rc = d_side_at.reserve((size_t)nside);
-        size_t tb = 0;
-        hipError_t he = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_side_at.p, d_side_at.p, nside, st);
-        if (rc == PC_OK && he == hipSuccess) rc = d_tmp.reserve(std::max<size_t>(tb, 16));
-        if (rc != PC_OK) return rc;
-        uint32_t at[4] = {0, 0, 0, 0};
-        if (he == hipSuccess) he = hipMemsetAsync(d_side_at.p + 3 * (size_t)nwg, 0, 4, st);
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(pcstage::k_classify, dim3(nwg), dim3(256), 0, st, sf->rec.p, n, sf->blk_off.p, sf->blk.p, wcap, sf->stream.p, d_side_at.p);
-            he = hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_side_at.p, d_side_at.p, nside, st);
-        }
-        for (int k = 1; k <= 3 && he == hipSuccess; ++k) he = hipMemcpyAsync(&at[k], d_side_at.p + (size_t)k * nwg, 4, hipMemcpyDeviceToHost, st);
-        if (he == hipSuccess) he = hipGetLastError();
-        if (he == hipSuccess) he = hipStreamSynchronize(st);   // (d_tmp goes out of scope)
-        if (he != hipSuccess) return fail(PC_ERR_HIP, "pc_add_alignment_file: deriving the record stream failed: %s", hipGetErrorString(he));
-        for (int k = 0; k < 3; ++k) side_total[k] = at[k + 1] - at[k];
-    }
-    clk.lap("record stream (GPU)");
-    const size_t nrunrec = (size_t)nrunrec_total;
-    sf->nrunrec = (int64_t)nrunrec;
-
-    // ---- linear-index layout: one table entry per 2^kLinShift-position bucket of each contig, up to the last
-    // record start -- and up to the furthest end of a read of the contig (tid_end): a long-span read reaches
-    // windows beyond every record start, and the later runs of gapped reads start there
-    std::vector<int64_t> lin_off((size_t)ntid + 1, 0);
-    for (int t = 0; t < ntid; ++t) {
-        const int64_t b = tid_bounds[(size_t)t], en = tid_bounds[(size_t)t + 1];
-        int64_t last = en > b ? (int64_t)last_pos[(size_t)t] : -1;
-        if (en > b) last = std::max<int64_t>(last, tid_end[(size_t)t] - 1);
-        const int64_t nb = last >= 0 ? (last >> kLinShift) + 1 : 0;
-        lin_off[(size_t)t + 1] = lin_off[(size_t)t] + nb + 1;
-    }
-    const size_t nlin = (size_t)lin_off[(size_t)ntid];
-
-    // ---- side lists and linear-index tables, on the GPU (pc_kernels.hip.h, "side lists"): the records are there
-    // already; from the host come only the two small per-contig tables
-    rc = sf->tid_bounds.upload(tid_bounds, st);
-    if (rc == PC_OK) rc = sf->lin_off.upload(lin_off, st);
-    const size_t nlong = side_total[0], ngap = side_total[1], nxlong = side_total[2];
-    DevBuf<uint32_t> d_gap_idx, d_xlong_idx;
-    if (rc == PC_OK && n > 0) {   // members of the three lists, in record order
-        rc = sf->long_idx.reserve(nlong);
-        if (rc == PC_OK) rc = d_gap_idx.reserve(ngap);
-        if (rc == PC_OK) rc = d_xlong_idx.reserve(nxlong);
-        if (rc == PC_OK && nlong + ngap + nxlong > 0)
-            hipLaunchKernelGGL(pcstage::k_side_select, dim3(nwg), dim3(256), 0, st, sf->rec.p, n, d_side_at.p, nwg, sf->long_idx.p, d_gap_idx.p, d_xlong_idx.p);
-    }
-    sf->nlong = (int64_t)nlong;
-    sf->ngap = (int64_t)ngap;
-    sf->nxlong = (int64_t)nxlong;
-    DevBuf<int64_t> d_xlong_bounds;
-    DevBuf<int32_t> d_xlong_pmax;
-    if (rc == PC_OK) {
-        // entries, running maxima of the ends, per-contig ranges
-        DevBuf<unsigned long long> d_key, d_key_scanned;
-        DevBuf<uint8_t> d_tmp;
-        rc = sf->long_rec.reserve(nlong);
-        if (rc == PC_OK) rc = sf->long_runs.reserve(nlong);
-        if (rc == PC_OK) rc = sf->long_tid.reserve(nlong);
-        if (rc == PC_OK) rc = sf->long_pmax.reserve(nlong);
-        if (rc == PC_OK && n_wide) rc = sf->long_wide.reserve(nlong);
-        if (rc == PC_OK) rc = sf->gap_rec.reserve(ngap);
-        if (rc == PC_OK) rc = sf->gap_runs.reserve(ngap);
-        if (rc == PC_OK) rc = sf->xlong_rec.reserve(nxlong);
-        if (rc == PC_OK) rc = sf->xlong_runs.reserve(nxlong);
-        if (rc == PC_OK && n_wide) rc = sf->xlong_wide.reserve(nxlong);
-        if (rc == PC_OK) rc = d_xlong_pmax.reserve(nxlong);
-        if (rc == PC_OK) rc = d_key.reserve(std::max(nlong, nxlong));
-        if (rc == PC_OK) rc = d_key_scanned.reserve(std::max(nlong, nxlong));
-        if (rc == PC_OK) rc = sf->long_tid_bounds.reserve((size_t)ntid + 1);
-        if (rc == PC_OK) rc = sf->gap_tid_bounds.reserve((size_t)ntid + 1);
-        if (rc == PC_OK) rc = d_xlong_bounds.reserve((size_t)ntid + 1);
-        hipError_t he = hipSuccess;
-        if (rc == PC_OK) {
-            size_t need = 0;
-            he = hipcub::DeviceScan::InclusiveScan(nullptr, need, d_key.p, d_key_scanned.p, hipcub::Max(), (int)std::max(nlong, nxlong), st);
-            if (he == hipSuccess && d_tmp.reserve(std::max<size_t>(need, 16)) != PC_OK) he = hipErrorOutOfMemory;
-        }
-        auto grid_of = [](size_t m) { return dim3((unsigned)((m + kWG - 1) / kWG)); };
-        auto running_max = [&](size_t m, int32_t *pmax) {   // d_key -> pmax
-            size_t tb = d_tmp.cap;
-            if (he == hipSuccess) he = hipcub::DeviceScan::InclusiveScan(d_tmp.p, tb, d_key.p, d_key_scanned.p, hipcub::Max(), (int)m, st);
-            if (he == hipSuccess) hipLaunchKernelGGL(k_unpack_pmax, grid_of(m), dim3(kWG), 0, st, d_key_scanned.p, (int64_t)m, pmax);
-        };
-        if (rc == PC_OK && he == hipSuccess) {
-            if (nlong) {
-                hipLaunchKernelGGL(k_side_fill, grid_of(nlong), dim3(kWG), 0, st, sf->long_idx.p, (int64_t)nlong, sf->rec.p, sf->blk_off.p, sf->blk.p,
-                                   sf->tid_bounds.p, ntid, sf->wide_rec.p, sf->wide_val.p, n_wide, sf->long_rec.p, sf->long_runs.p, sf->long_tid.p,
-                                   d_key.p, n_wide ? sf->long_wide.p : nullptr);
-                running_max(nlong, sf->long_pmax.p);
-            }
-            if (ngap)
-                hipLaunchKernelGGL(k_side_fill, grid_of(ngap), dim3(kWG), 0, st, d_gap_idx.p, (int64_t)ngap, sf->rec.p, sf->blk_off.p, sf->blk.p,
-                                   sf->tid_bounds.p, ntid, sf->wide_rec.p, sf->wide_val.p, n_wide, sf->gap_rec.p, sf->gap_runs.p, (int32_t *)nullptr,
-                                   (unsigned long long *)nullptr, (uint2 *)nullptr);
-            if (nxlong) {
-                hipLaunchKernelGGL(k_side_fill, grid_of(nxlong), dim3(kWG), 0, st, d_xlong_idx.p, (int64_t)nxlong, sf->rec.p, sf->blk_off.p, sf->blk.p,
-                                   sf->tid_bounds.p, ntid, sf->wide_rec.p, sf->wide_val.p, n_wide, sf->xlong_rec.p, sf->xlong_runs.p, (int32_t *)nullptr,
-                                   d_key.p, n_wide ? sf->xlong_wide.p : nullptr);
-                running_max(nxlong, d_xlong_pmax.p);
-            }
-            const dim3 gt((unsigned)((ntid + 1 + kWG - 1) / kWG));
-            hipLaunchKernelGGL(k_list_bounds, gt, dim3(kWG), 0, st, sf->long_idx.p, (int64_t)nlong, sf->tid_bounds.p, ntid, sf->long_tid_bounds.p);
-            hipLaunchKernelGGL(k_list_bounds, gt, dim3(kWG), 0, st, d_gap_idx.p, (int64_t)ngap, sf->tid_bounds.p, ntid, sf->gap_tid_bounds.p);
-            hipLaunchKernelGGL(k_list_bounds, gt, dim3(kWG), 0, st, d_xlong_idx.p, (int64_t)nxlong, sf->tid_bounds.p, ntid, d_xlong_bounds.p);
-        }
-        // the linear-index tables: one bisection per table entry
-        if (rc == PC_OK) rc = sf->lin_tab.reserve(nlin);
-        if (rc == PC_OK) rc = sf->glin_tab.reserve(nlin);
-        if (rc == PC_OK) rc = sf->llin_tab.reserve(nlin);
-        if (rc == PC_OK) rc = sf->plin_tab.reserve(nlin);
-        if (rc == PC_OK && nxlong) rc = sf->xllin_tab.reserve(nlin);
-        if (rc == PC_OK && nxlong) rc = sf->xplin_tab.reserve(nlin);
-        if (rc == PC_OK && he == hipSuccess && nlin) {
-            const dim3 gl = grid_of(nlin);
-            hipLaunchKernelGGL((k_lin_table<0>), gl, dim3(kWG), 0, st, (const void *)sf->rec.p, sf->tid_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->lin_tab.p);
-            hipLaunchKernelGGL((k_lin_table<1>), gl, dim3(kWG), 0, st, (const void *)sf->gap_rec.p, sf->gap_tid_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->glin_tab.p);
-            hipLaunchKernelGGL((k_lin_table<1>), gl, dim3(kWG), 0, st, (const void *)sf->long_rec.p, sf->long_tid_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->llin_tab.p);
-            hipLaunchKernelGGL((k_lin_table<2>), gl, dim3(kWG), 0, st, (const void *)sf->long_pmax.p, sf->long_tid_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->plin_tab.p);
-            if (nxlong) {
-                hipLaunchKernelGGL((k_lin_table<1>), gl, dim3(kWG), 0, st, (const void *)sf->xlong_rec.p, d_xlong_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->xllin_tab.p);
-                hipLaunchKernelGGL((k_lin_table<2>), gl, dim3(kWG), 0, st, (const void *)d_xlong_pmax.p, d_xlong_bounds.p, sf->lin_off.p, ntid, (int64_t)nlin, sf->xplin_tab.p);
-            }
-        }
-        if (rc == PC_OK && he == hipSuccess) he = hipGetLastError();
-        if (rc == PC_OK && he == hipSuccess) he = hipStreamSynchronize(st);   // the temporaries go out of scope
-        if (rc == PC_OK && he != hipSuccess) rc = fail(PC_ERR_HIP, "stage: building the side lists failed: %s", hipGetErrorString(he));
-    }
-    clk.lap("side lists + linear index (GPU)");
-    // ---- run stream: sorted by (contig, run start) on the GPU (radix sort of the 64-bit keys, the 8-byte
-    // records and their record indices permuted along), then its linear index by one bisection per bucket
-    if (rc == PC_OK && nrunrec) {
-        DevBuf<unsigned long long> d_key, d_key_sorted;
-        DevBuf<uint32_t> d_ord, d_ord_sorted;
-        DevBuf<uint8_t> d_tmp;
-        rc = d_key.reserve(nrunrec);
-        if (rc == PC_OK) rc = d_ord.reserve(nrunrec);
-        if (rc == PC_OK) rc = d_key_sorted.reserve(nrunrec);
-        if (rc == PC_OK) rc = d_ord_sorted.reserve(nrunrec);
-        if (rc == PC_OK) rc = sf->run_rec.reserve(nrunrec + 1);
-        if (rc == PC_OK) rc = sf->run_recidx.reserve(nrunrec);
-        if (rc == PC_OK) rc = sf->rlin_tab.reserve(nlin);
-        if (rc == PC_OK)   // sort keys (contig << 32 | run start) and the identity permutation, made on the GPU
-            hipLaunchKernelGGL(k_run_keys, dim3((unsigned)((nrunrec + kWG - 1) / kWG)), dim3(kWG), 0, e->stream, d_val_in.p, d_idx_in.p,
-                               (int64_t)nrunrec, sf->tid_bounds.p, ntid, d_key.p, d_ord.p);
-        if (rc == PC_OK) {
-            size_t tmp_bytes = 0;
-            const int end_bit = 32 + (ntid > 1 ? 32 - __builtin_clz((unsigned)(ntid - 1)) : 1);
-            hipError_t he = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key.p, d_key_sorted.p, d_ord.p, d_ord_sorted.p,
-                                                               (int)nrunrec, 0, end_bit, e->stream);
-            if (he == hipSuccess) rc = d_tmp.reserve(tmp_bytes);
-            if (he == hipSuccess && rc == PC_OK)
-                he = hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, d_key.p, d_key_sorted.p, d_ord.p, d_ord_sorted.p, (int)nrunrec,
-                                                        0, end_bit, e->stream);   // stable: equal starts keep record order
-            if (he != hipSuccess) rc = fail(PC_ERR_HIP, "stage: sorting the run stream failed: %s", hipGetErrorString(he));
-        }
-        if (rc == PC_OK) {
-            const unsigned grid = (unsigned)((nrunrec + kWG - 1) / kWG);
-            hipLaunchKernelGGL(k_run_gather, dim3(grid), dim3(kWG), 0, e->stream, d_ord_sorted.p, d_val_in.p, d_idx_in.p, (int64_t)nrunrec,
-                               sf->run_rec.p, sf->run_recidx.p);
-            hipLaunchKernelGGL(k_run_lin, dim3((unsigned)((nlin + kWG - 1) / kWG)), dim3(kWG), 0, e->stream, d_key_sorted.p, (int64_t)nrunrec,
-                               sf->lin_off.p, ntid, (int64_t)nlin, sf->rlin_tab.p);
-            const uint2 tail_run = make_uint2(0u, (uint32_t)PC_FLAG_EXCLUDED << 24);
-            if (hipMemcpyAsync(sf->run_rec.p + nrunrec, &tail_run, sizeof(tail_run), hipMemcpyHostToDevice, e->stream) != hipSuccess ||
-                hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess)
-                rc = fail(PC_ERR_HIP, "stage: building the run stream failed");
-        }
-    }
-    if (rc != PC_OK) return rc;
-    clk.lap("run stream (GPU sort)");
-    sf->nlin = nlin;
-    PC_TRY(build_compact_stream(e, sf, ntid));
-    clk.lap("compact stream (GPU)");
-    owner.p = nullptr;
-    e->files.push_back(sf);
-    e->ntid = ntid;
-    e->files_dirty = true;
-    e->work_generation += 1;
-    return PC_OK;
+    StageInput in;
+    in.n = n; in.ntid = ntid; in.tid = tid; in.pos = pos; in.alen = alen; in.flags = flags; in.nblk = nblk;
+    in.nrun = nrun; in.blk_start = blk_start; in.blk_len = blk_len;
+    in.n_wide = n_wide; in.wide_idx = wide_idx; in.wide_alen = wide_alen; in.wide_nblk = wide_nblk;
+    return stage_file(e, in);
 }
 
 static int propagate_record_flags(pc_engine *e, StagedFile *sf);
@@ -2092,6 +2125,14 @@ static int check_filter_columns(const pc_engine *e, const char *who) {
     return PC_OK;
 }
 
+// the verdicts of the engine's FLAG / MAPQ / NH filter into the exclusion bits of one staged file (`on` 0: taken out again)
+static void launch_flag_filter(pc_engine *e, StagedFile *sf, uint32_t on) {
+    hipLaunchKernelGGL(k_flag_filter, dim3((unsigned)((sf->n + kWG - 1) / kWG)), dim3(kWG), 0, e->stream, sf->rec.p, sf->stream.p,
+                       sf->have_sam ? sf->sam_flag.p : nullptr, sf->have_sam ? sf->sam_mapq.p : nullptr, sf->n, on,
+                       e->ff_on ? e->ff_require : 0u, e->ff_on ? e->ff_exclude : 0u, e->ff_on ? e->ff_min_mapq : 0u,
+                       sf->have_nh ? sf->sam_nh.p : nullptr, e->ff_max_nh);
+}
+
 int pc_update_flags(pc_engine *e, int file, int64_t n, const uint8_t *flags) {
     if (!e || file < 0 || file >= (int)e->files.size()) return fail(PC_ERR_ARG, "pc_update_flags: bad file index");
     StagedFile *sf = e->files[file];
@@ -2108,9 +2149,7 @@ int pc_update_flags(pc_engine *e, int file, int64_t n, const uint8_t *flags) {
     sf->applied = FilterState();
     sf->applied_valid = true;
     if (e->filter_on() && columns_present(e, sf)) {   // the FLAG / MAPQ / NH filter's verdicts on top of the caller's
-        hipLaunchKernelGGL(k_flag_filter, dim3((unsigned)((n + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->rec.p, sf->stream.p, sf->have_sam ? sf->sam_flag.p : nullptr,
-                           sf->have_sam ? sf->sam_mapq.p : nullptr, n, 1u, e->ff_on ? e->ff_require : 0u, e->ff_on ? e->ff_exclude : 0u, e->ff_on ? e->ff_min_mapq : 0u,
-                           sf->have_nh ? sf->sam_nh.p : nullptr, e->ff_max_nh);
+        launch_flag_filter(e, sf, 1u);
         sf->applied = e->filter_state();
     }
     const int prc = propagate_record_flags(e, sf);
@@ -2124,15 +2163,9 @@ int pc_update_flags(pc_engine *e, int file, int64_t n, const uint8_t *flags) {
 // lists).  Waits for the engine's stream (build_compact_stream reads the entry count back).
 static int propagate_record_flags(pc_engine *e, StagedFile *sf) {
     hipStream_t st = e->stream;
-    if (sf->nlong)
-        hipLaunchKernelGGL(k_update_side_flags, dim3((unsigned)((sf->nlong + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->long_rec.p,
-                           sf->nlong, sf->rec.p);
-    if (sf->ngap)
-        hipLaunchKernelGGL(k_update_side_flags, dim3((unsigned)((sf->ngap + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->gap_rec.p,
-                           sf->ngap, sf->rec.p);
-    if (sf->nxlong)
-        hipLaunchKernelGGL(k_update_side_flags, dim3((unsigned)((sf->nxlong + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->xlong_rec.p,
-                           sf->nxlong, sf->rec.p);
+    const struct { uint4 *rec; int64_t m; } side[3] = {{sf->long_rec.p, sf->nlong}, {sf->gap_rec.p, sf->ngap}, {sf->xlong_rec.p, sf->nxlong}};
+    for (const auto &l : side)
+        if (l.m) hipLaunchKernelGGL(k_update_side_flags, dim3((unsigned)((l.m + kWG - 1) / kWG)), dim3(kWG), 0, st, l.rec, l.m, sf->rec.p);
     if (sf->nrunrec)
         hipLaunchKernelGGL(k_update_run_flags, dim3((unsigned)((sf->nrunrec + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->run_rec.p,
                            sf->run_recidx.p, sf->nrunrec, sf->rec.p);
@@ -2155,10 +2188,7 @@ static int apply_flag_filter(pc_engine *e, StagedFile *sf) {
         // nothing to read the verdicts from, and nothing to undo: a file without the columns never had the filter applied
         return PC_OK;
     }
-    hipLaunchKernelGGL(k_flag_filter, dim3((unsigned)((sf->n + kWG - 1) / kWG)), dim3(kWG), 0, e->stream, sf->rec.p, sf->stream.p,
-                       sf->have_sam ? sf->sam_flag.p : nullptr, sf->have_sam ? sf->sam_mapq.p : nullptr, sf->n, e->filter_on() ? 1u : 0u,
-                       e->ff_on ? e->ff_require : 0u, e->ff_on ? e->ff_exclude : 0u, e->ff_on ? e->ff_min_mapq : 0u,
-                       sf->have_nh ? sf->sam_nh.p : nullptr, e->ff_max_nh);
+    launch_flag_filter(e, sf, e->filter_on() ? 1u : 0u);
     sf->applied = e->filter_state();
     sf->applied_valid = true;
     return propagate_record_flags(e, sf);

@@ -621,6 +621,72 @@ def test_staging_rejects_every_defect_of_the_columns(pa, monkeypatch, slice_reco
     assert stage(pos=(3, 0)) is None and stage(pos=(7, 0)) is None
 
 
+@pytest.mark.parametrize("slice_records", [None, "3"])
+def test_a_refused_file_leaves_the_engine_as_it_was(pa, oracle, monkeypatch, slice_records):
+    """Staging is a list of phases, and each of them can refuse a file: the argument checks, the run layout, the GPU's
+    verdict on the columns, the host's on the contig column (and the precedence between those two).  A refusal on an
+    engine that already holds a file, a mapping rule and an open plan gives the half-built file back, leaves one file
+    staged, and the plan counts what it counted, bit for bit; the engine then takes a good file as if nothing had
+    happened.  The file is that of test_staging_rejects_every_defect_of_the_columns plus one read that spans more than
+    1 024 positions (the long list is not empty)."""
+    from plastid_amd.engine import Engine
+    if slice_records:
+        monkeypatch.setenv("PC_STAGE_SLICE", slice_records)
+    refs, lens = ["a", "b", "c"], [5000, 5000, 5000]
+    cols = dict(tid=np.array([0, 0, 0, 1, 1, 1, 1, 2, 2, 2], np.int32),
+                pos=np.array([10, 20, 20, 5, 30, 40, 41, 0, 7, 100], np.int32),
+                alen=np.array([30, 25, 28, 30, 40, 30, 30, 30, 29, 30], np.uint16),
+                flags=np.array([0, 1, 0, 0, 1, 0, 1, 0, 0, 1], np.uint8),
+                nblk=np.array([1, 1, 2, 1, 3, 1, 1, 1, 1, 2], np.uint8),
+                blk_start=np.array([20, 60, 30, 50, 90, 100, 1300], np.int32),
+                blk_len=np.array([10, 18, 10, 20, 10, 15, 15], np.int32))
+
+    def packed(references=refs, lengths=lens, **changed):
+        c = {k: v.copy() for k, v in cols.items()}
+        for k, (i, v) in changed.items():
+            c[k][i] = v
+        return pa.PackedAlignments(c["tid"], c["pos"], c["alen"], c["flags"], c["nblk"], c["blk_start"], c["blk_len"],
+                                   references=references, lengths=lengths, validate=False)
+
+    good = packed()
+    seg_tid = np.array([0, 1, 2, 2, 1], np.int32)
+    seg_start = np.array([0, 0, 0, 1200, 25], np.int64)
+    seg_end = np.array([200, 200, 200, 1400, 60], np.int64)
+    seg_strand = np.array([3, 1, 2, 3, 2], np.uint8)
+    seg_len = seg_end - seg_start
+    mapping = ("fiveprime", 3)
+    spec = spec_for(oracle, mapping)
+
+    def expected(files):
+        arrays, _ = oracle.count_segments(aln_dict(files), spec, seg_tid, seg_start, seg_end, seg_strand)
+        return np.concatenate(arrays)
+
+    eng = engine_for(pa, [good], mapping)
+    plan = eng.plan(seg_tid, seg_start, seg_end, seg_strand, np.concatenate([[0], np.cumsum(seg_len)[:-1]]), np.ones(len(seg_len), np.int8),
+                    seg_len, int(seg_len.sum()), 1)
+    first = plan.count(np.int64).copy()
+    assert np.array_equal(first, expected([good])) and first.sum() > 0
+    refusals = [
+        (packed(references=refs + ["d"], lengths=lens + [5000]), "all files must use the same reference list (ntid 4 vs 3)"),  # argument checks
+        (packed(nblk=(0, 2)), "run arrays shorter than sum of nblk"),                                 # run layout
+        (packed(blk_start=(0, 21)), "record 2: first run must start at pos"),                         # the GPU's verdict
+        (packed(tid=(4, 7)), "record 4: tid 7 out of range"),                                         # the contig column
+        (packed(tid=(5, 9), blk_len=(1, 19)), "record 2: run lengths do not sum to alen"),            # both: the lower record
+    ]
+    for bad, want in refusals:
+        with pytest.raises(ValueError) as ei:
+            eng.add_alignment_file(bad)
+        assert want in str(ei.value), (want, str(ei.value))
+        assert eng._lib.pc_num_files(eng._h) == 1 and eng.nfiles == 1, want
+        assert np.array_equal(plan.count(np.int64), first), want
+    eng.add_alignment_file(packed())
+    assert eng._lib.pc_num_files(eng._h) == 2
+    second = plan.count(np.int64)
+    assert np.array_equal(second, 2 * first) and np.array_equal(second, expected([good, packed()]))
+    plan.close()
+    eng.close()
+
+
 def test_transfer_ring_large_files_pinned_memory_and_two_engines(pa, monkeypatch):
     """Staging and read-back of a file large enough for the ring of page-locked pieces by itself (12 M records: 96 MB of
     columns up, 100 MB of counts down), against the same file sent in 40-byte pieces; page-locked caller memory (a pinned

@@ -424,7 +424,9 @@ def test_host_helpers_of_the_engine(tmp_path):
     the vector without zero-fill, and the host's look at the contig column of caller-owned records (scan_contigs: the
     record bounds of every contig and the first record out of order or out of range, against a record-by-record walk,
     for every thread count) and the window size of a plan (choose_window: the sizes the published numbers were measured
-    with, the knob's limits) -- compiled with the host compiler and run here."""
+    with, the knob's limits), and the host arithmetic of staging (choose_halo: the span quantile, the longest spans inside
+    it and the length ranges of the streams; lin_layout: the entries of the linear-index tables; both against values worked
+    out by hand) -- compiled with the host compiler and run here."""
     import shutil
     import subprocess
     cxx = shutil.which("g++") or shutil.which("c++")
