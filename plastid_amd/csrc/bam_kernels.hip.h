@@ -309,6 +309,8 @@ __device__ __forceinline__ void symbols_at8(const tab_t *lit, const tab_t *dist,
 // batch-wise through the lanes (BATCH, above) or, BATCH = false, one by one through the same uniform reader (round 4's
 // first kernel, kept for comparison: PC_BGZF_SERIAL=1).  (The workgroup IS the wave: __syncthreads() orders the LDS
 // traffic of its lanes and costs no cross-wave barrier.)
+// Pinned by tests/test_gpu_inflate.py on the hand-built streams of tests/inflate_cases.py: the 48-bit symbol at every bit
+// offset of a batch (group D), the window edge (C), the header forms (E); overlaps, block sequencing, geometry: B, F, G.
 // Occupancy (round 6): 7.1 KiB of LDS allow 22 waves per CU; the registers are held to 96 (five waves per SIMD) by looking
 // the batch's symbols up in two groups of four offsets instead of one of eight (PC_BGZF_GROUP).  20 M aligner-like
 // records, 2.39 GB inflated, lap `upload + inflate + crc`: 32-bit entries, four waves per SIMD 25.8 - 26.1 ms; 16-bit
@@ -419,7 +421,10 @@ __global__ __launch_bounds__(kInflWG) __attribute__((amdgpu_waves_per_eu(PC_BGZF
             uint32_t sp = in_pos - (uint32_t)(nb >> 3);
             bb = 0; nb = 0;
             if (sp + len > clen) { err = kInfInputOverrun; break; }
-            // (a stored block can be twice the window: copied and flushed piece by piece)
+            // (a stored block can be twice the window: copied and flushed piece by piece.  The last batch of a Huffman block
+            // may leave up to kWinBytes - 258 bytes unflushed -- a piece on top of that would wrap around the window onto
+            // them, so they go out first.)
+            if (len != 0u && pos - flushed >= (uint32_t)kFlush) flush_to(pos & ~15u);
             for (uint32_t done = 0; done < len;) {
                 const uint32_t piece = len - done < (uint32_t)kFlush ? len - done : (uint32_t)kFlush;
                 for (uint32_t k = lane; k < piece; k += 64) sh.win[(pos + k) & (kWinBytes - 1)] = src[sp + done + k];
@@ -716,6 +721,10 @@ __global__ __launch_bounds__(kInflWG) __attribute__((amdgpu_waves_per_eu(PC_BGZF
         }
     }
     if (err == kInfOk && pos != ulen) err = kInfShort;
+    // Both symbol decoders read zeros behind the end of the data, and the end-of-block code of a fixed block is seven zero
+    // bits: a stream cut inside its last symbol must not pass for a whole one (zlib and libdeflate refuse it).  The
+    // reader's bit position is in_pos * 8 - nb after every kind of block.
+    if (err == kInfOk && in_pos * 8u - (uint32_t)nb > clen * 8u) err = kInfInputOverrun;   // (a member is < 64 KiB: no overflow)
     if (err == kInfOk) flush_to(ulen);
     // CRC-32 of the member is checked by k_bgzf_crc (below) on the inflated bytes in HBM
     if (lane == 0) status[m] = (uint32_t)err;

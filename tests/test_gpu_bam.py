@@ -16,6 +16,7 @@ from plastid_amd import synth  # noqa: E402
 from plastid_amd.bam import read_bam, read_bam_gpu  # noqa: E402
 from plastid_amd.engine import Engine  # noqa: E402
 from tests import bam_writer  # noqa: E402
+from tests.deflate_writer import literal_only_dynamic_member  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -204,90 +205,6 @@ def _member_payloads(path):
         if bsize > 28:
             yield raw[off + 18:off + bsize - 8]
         off += bsize
-
-
-class _Bits(object):
-    def __init__(self):
-        self.acc, self.n, self.out = 0, 0, bytearray()
-
-    def put(self, value, nbits):            # LSB first (header fields, extra bits)
-        self.acc |= value << self.n
-        self.n += nbits
-        while self.n >= 8:
-            self.out.append(self.acc & 255)
-            self.acc >>= 8
-            self.n -= 8
-
-    def code(self, c, nbits):               # Huffman codes go MSB first
-        self.put(int(format(c, "0%db" % nbits)[::-1], 2), nbits)
-
-    def done(self):
-        if self.n:
-            self.out.append(self.acc & 255)
-        return bytes(self.out)
-
-
-def _code_lengths(freq, limit):
-    """Huffman code lengths (<= limit) for the symbols with freq > 0."""
-    import heapq
-    f = {s: c for s, c in enumerate(freq) if c}
-    while True:
-        heap = [(c, s, (s,)) for s, c in f.items()]
-        heapq.heapify(heap)
-        depth = dict.fromkeys(f, 0)
-        if len(heap) == 1:
-            depth[heap[0][1]] = 1
-        while len(heap) > 1:
-            a, b = heapq.heappop(heap), heapq.heappop(heap)
-            for s in a[2] + b[2]:
-                depth[s] += 1
-            heapq.heappush(heap, (a[0] + b[0], min(a[1], b[1]), a[2] + b[2]))
-        if max(depth.values()) <= limit:
-            return depth
-        f = {s: (c + 1) // 2 for s, c in f.items()}
-
-
-def _canonical(lengths):
-    codes, code = {}, 0
-    for ln in range(1, 16):
-        for s in sorted(s for s, l in lengths.items() if l == ln):
-            codes[s] = (code, ln)
-            code += 1
-        code <<= 1
-    return codes
-
-
-def literal_only_dynamic_member(data):
-    """One BGZF member whose payload is ONE dynamic DEFLATE block of literals only, declaring HDIST = 1 distance code
-    of length ZERO (what libdeflate before 1.15 wrote for such blocks; zlib's inflate_table accepts `max == 0`)."""
-    freq = [0] * 257
-    for b in data:
-        freq[b] += 1
-    freq[256] = 1
-    ll = _code_lengths(freq, 15)
-    lens = [ll.get(s, 0) for s in range(257)] + [0]          # 257 literal/length lengths + the one distance length
-    cl_freq = [0] * 19
-    for v in lens:
-        cl_freq[v] += 1
-    cl = _code_lengths(cl_freq, 7)
-    order = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
-    hclen = max(i for i, s in enumerate(order) if cl.get(s, 0)) + 1
-    w = _Bits()
-    w.put(1, 1); w.put(2, 2)                                   # BFINAL, dynamic
-    w.put(0, 5); w.put(0, 5); w.put(max(hclen, 4) - 4, 4)      # HLIT = 257, HDIST = 1
-    for s in order[:max(hclen, 4)]:
-        w.put(cl.get(s, 0), 3)
-    clc = _canonical(cl)
-    for v in lens:
-        w.code(*clc[v])
-    llc = _canonical(ll)
-    for b in data:
-        w.code(*llc[b])
-    w.code(*llc[256])
-    cdata = w.done()
-    assert zlib.decompressobj(-15).decompress(cdata) == data   # zlib itself takes the stream
-    header = struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, ord("B"), ord("C"), 2, len(cdata) + 25)
-    return header + cdata + struct.pack("<II", zlib.crc32(data) & 0xffffffff, len(data))
 
 
 def test_odd_and_damaged_auxiliary_fields_on_the_device(eng, tmp_path):
