@@ -1,11 +1,14 @@
 // host_util.h -- host-side helpers of the counting engine that do not touch HIP: the worker pool behind
 // parallel_chunks, the galloping lower bound of the plan build, a vector without zero-fill, the host's look at the
 // contig column of caller-owned records (scan_contigs), the window size of a plan (choose_window), the halo and the
-// linear-index layout of a staged file (choose_halo, lin_layout).  Plain C++17, so that tests/test_host_logic.py can compile tests/host_util_test.cpp against it on a machine without a GPU.
+// linear-index layout of a staged file (choose_halo, lin_layout), the lap clock of PC_STAGE_TIMING.  Plain C++17, so that tests/test_host_logic.py can compile tests/host_util_test.cpp against it on a machine without a GPU.
 #pragma once
 #include <algorithm>
+#include <chrono>
 #include <condition_variable>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -13,6 +16,18 @@
 #include <utility>
 #include <vector>
 #include <unistd.h>
+
+// PC_STAGE_TIMING: the host time between two laps of a staging call or a plan build, on stderr.
+struct StageClock {
+    bool on = getenv("PC_STAGE_TIMING") != nullptr;
+    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
+    void lap(const char *what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "[stage] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+        t = now;
+    }
+};
 
 // std::vector whose resize() leaves trivially constructible elements uninitialised: the plan's tables are sized
 // once and then filled by all threads, and a serial zero-fill of tens of megabytes (plus the page faults it takes on

@@ -30,6 +30,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "plan_tables.h"   // the tables of a plan: Tile, Piece, OutPiece, CenterChunk, GatherSeg, GatherChunk, mode_of
+
 // The kernels use gfx950 encodings directly (64-bit DPP with row_newbcast in k_center's replay, fixed wave64 layouts):
 // any other offload architecture is rejected here rather than at assembly time.
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
@@ -58,7 +60,6 @@ constexpr int kWG = 256;          // 4 waves of 64
 #define PC_HIST_U(KIND) 4
 #endif
 constexpr int kHistWG = PC_HIST_WG;
-constexpr int kWave = 64;
 constexpr uint32_t kFlagReverse = 0x01;
 constexpr uint32_t kFlagUser = 0x08;      // engine-internal: excluded by the CALLER's own filters (the PC_FLAG_EXCLUDED it staged); kFlagExcluded = this OR the verdict of the FLAG / MAPQ filter (pc_set_flag_filter)
 constexpr uint32_t kFlagWide = 0x10;      // engine-internal: aligned length > 65 535 or > 255 runs -- the 16 / 8-bit fields read 65535 / 255, true values aside
@@ -67,7 +68,6 @@ constexpr uint32_t kFlagLong = 0x40;      // engine-internal: span > W, handled 
 constexpr uint32_t kFlagExcluded = 0x80;
 // the flag byte of a staged record from the caller's PC_FLAG_* bits
 __host__ __device__ inline uint32_t caller_flags(uint32_t f) { return (f & kFlagReverse) | ((f & kFlagExcluded) ? (kFlagExcluded | kFlagUser) : 0u); }
-constexpr int kGatherChunk = 1024;
 constexpr int kLinShift = 7;              // linear-index bucket = 128 genome positions
 constexpr int kStreamMaxLen = 255;        // aligned lengths the 4-byte record stream can carry
 
@@ -92,13 +92,6 @@ __host__ __device__ inline uint32_t stream_word(uint32_t pos, uint32_t meta) {
     return (pos << 16) | (skip ? kStreamSkip : (L << 4)) | ((fl & kFlagReverse) << 2);
 }
 __host__ __device__ inline uint32_t stream_len(uint32_t word) { return (word >> 4) & 0xffu; }
-
-// strand modes of a query interval
-//   0: '+'  keeps forward reads, forward index rule
-//   1: '-'  keeps reverse reads, reverse index rule
-//   2: '.'  keeps all reads,     forward index rule  (map_factories.pyx:345-346: only '-' flips)
-//   3: all reads, reverse index rule (direct map-factory call on a '-' segment, no strand filter)
-constexpr int kModes = 4;
 
 struct FileView {
     const uint2 *rec;
@@ -254,38 +247,6 @@ struct MapParams {
     const int32_t *rc;
 };
 
-struct Tile {
-    int32_t tid;
-    int32_t win_start;
-    uint32_t piece_begin; // island pieces (histogram coordinates)
-    uint32_t piece_end;
-    uint32_t mode_mask;
-    uint32_t op_begin;    // output pieces (segment slices in the caller's layout)
-    uint32_t op_end;
-    uint16_t span_lo;     // queried positions of the window all lie in [span_lo, span_hi) (window-relative)
-    uint16_t span_hi;
-};
-
-// A queried segment cut at the tile grid, with its place in the caller's output buffer:
-// position start+i, row r  ->  out[out_off + step*i + r*row_stride]
-struct OutPiece {
-    int64_t out_off;
-    int64_t row_stride;
-    int64_t hist_off; // same positions in the compact histogram (used when a tile is split)
-    int32_t start;
-    int32_t len;
-    int32_t mode;
-    int32_t step;
-};
-
-struct Piece {
-    int64_t hist_off;
-    int32_t start;
-    int32_t len;
-    int32_t mode;
-    int32_t pad;
-};
-
 constexpr uint32_t kItemMerge = 1u, kItemCompact = 2u;   // bits of WorkItem::merge
 struct WorkItem {
     int64_t lo, hi;   // range of the packed stream: records -- or, with kItemCompact, entries of the file's compact stream
@@ -310,31 +271,6 @@ struct WorkItem {
 struct FileRange {
     int64_t lo, hi, glo, ghi, llo, lhi;
     uint32_t rlo, rhi;
-};
-
-struct CenterChunk {
-    int64_t hist_off;
-    int32_t tid;
-    int32_t start;
-    int32_t len;
-    int32_t mode;
-    uint32_t op_begin, op_end;   // output pieces of the chunk's window (Tile::op_begin / op_end): where its sums go
-};
-
-struct GatherSeg {
-    int64_t out_off;
-    int64_t row_stride;
-    int64_t hist_off; // hist index of position (start + clip_lo); -1: all zero
-    int64_t len;
-    int64_t clip_lo, clip_hi;
-    int64_t start;    // genomic coordinate of the segment's first position
-    int32_t step;
-    int32_t pad;
-};
-
-struct GatherChunk {
-    uint32_t seg;
-    uint32_t chunk;
 };
 
 struct Unmappable {

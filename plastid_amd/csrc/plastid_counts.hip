@@ -49,6 +49,7 @@
 
 #include "plastid_counts.h"
 #include "host_util.h"
+#include "plan_host.h"
 
 using namespace pc;
 
@@ -702,9 +703,7 @@ struct pc_plan {
     uint32_t modes = 0;
     int max_slots = 1;
     int64_t npos = 0; // island positions (hist row length)
-    PodVec<Tile> tiles;
-    PodVec<Piece> pieces;
-    PodVec<OutPiece> opieces;
+    HostPlan host;               // the tables as the host builder made them (empty for a GPU-built plan): the uploads read them, pc_plan_table its gsegs
     size_t n_tiles = 0, n_pieces = 0, n_opieces = 0;   // table sizes (a GPU-built plan keeps its tables in HBM only)
     size_t n_cchunks = 0, n_gchunks = 0;               // ... of the center chunk list and of the gather list, once built
     bool gpu_built = false;      // pc_plan_create built the tables on the GPU (large annotations): they live in HBM only
@@ -715,10 +714,7 @@ struct pc_plan {
     bool out_needs_zero = false; // some queried positions lie outside every tile (unknown contig, clipped)
     bool hist_clean = false;     // the WHOLE compact histogram is known to be zero (a lazy count does not need that: it clears the slices it merges)
     bool hist_lazy = false;      // the histogram is large: never cleared as a whole, k_clear_split runs behind every k_tile_ranges
-    std::vector<CenterChunk> cchunks;
-    std::vector<GatherSeg> gsegs;
-    std::vector<GatherChunk> gchunks;
-    bool lazy_center = false;    // large plans: cchunks / gchunks (and the upload of gsegs) wait for the first center count or coordinate export
+    // GPU-built plans: the center chunks and the gather list wait for the first center count or coordinate export
     bool center_ready = false, gather_ready = false;
     DevBuf<uint8_t> d_tables2, d_tables3;   // ... and live in these blocks (chunks; gather list)
     // host copies for warn evaluation
@@ -811,14 +807,6 @@ struct pc_plan {
 
 namespace {
 
-int mode_of(uint8_t strand) {
-    const bool nofilter = strand & PC_STRAND_NOFILTER;
-    const int s = strand & 3;
-    if (s == PC_STRAND_REV) return nofilter ? 3 : 1;
-    if (s == PC_STRAND_FWD) return nofilter ? 2 : 0;
-    return 2; // '.' and undefined: all reads, forward rule
-}
-
 int refresh_file_views(pc_engine *e) {
     if (!e->files_dirty) return PC_OK;
     std::vector<FileView> v;
@@ -828,17 +816,6 @@ int refresh_file_views(pc_engine *e) {
     e->files_dirty = false;
     return PC_OK;
 }
-
-struct StageClock {
-    bool on = getenv("PC_STAGE_TIMING") != nullptr;
-    std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    void lap(const char *what) {
-        if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[stage] %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-    }
-};
 
 // ---- plans built on the GPU (plan_kernels.hip.h): the host copies of the caller's segment arrays, when a host pass needs them
 struct PlanInputLayout {   // the caller's seven segment arrays in one block
@@ -880,6 +857,36 @@ struct Bump {   // carves the working arrays of one stage out of one block
 };
 
 inline int bits_for(uint64_t v) { int b = 0; while (b < 64 && (v >> b)) ++b; return std::max(b, 1); }
+
+// The plan's block in HBM, as both builders lay it out: tiles, island pieces, output pieces, center chunks, gather
+// records, gather list (the last three empty in a GPU-built plan, which makes them on first use), then what arrives
+// zeroed -- the per-tile item counters, the work counters, the total and, when it is short, the compact histogram (one
+// memset less on the first count).
+struct PlanBlockLayout {
+    size_t at_tiles, at_pieces, at_opieces, at_cchunks, at_gsegs, at_gchunks, at_items, at_wcounters, at_total, at_hist = 0, bytes = 0;
+    bool hist_here;
+    PlanBlockLayout(size_t n_tiles, size_t n_pieces, size_t n_opieces, size_t n_cchunks, size_t n_gsegs, size_t n_gchunks, int64_t npos, int rows) {
+        auto place = [this](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
+        at_tiles = place(n_tiles * sizeof(Tile)); at_pieces = place(n_pieces * sizeof(Piece)); at_opieces = place(n_opieces * sizeof(OutPiece));
+        at_cchunks = place(n_cchunks * sizeof(CenterChunk)); at_gsegs = place(n_gsegs * sizeof(GatherSeg)); at_gchunks = place(n_gchunks * sizeof(GatherChunk));
+        at_items = place((n_tiles + 1) * sizeof(uint32_t)); at_wcounters = place(64); at_total = place(64);
+        const size_t hist_full = (size_t)npos * (size_t)rows * sizeof(double);
+        hist_here = hist_full > 0 && hist_full <= 64 * 1024;
+        if (hist_here) at_hist = place(hist_full);
+    }
+    size_t zeroed_bytes() const { return bytes - at_items; }   // from at_items to the end
+    void bind(pc_plan *p) const {   // the views of `p` into its block (which is, or is about to be, zeroed from at_items on)
+        uint8_t *d = p->d_tables.p;
+        p->d_tiles.p = (Tile *)(d + at_tiles); p->d_pieces.p = (Piece *)(d + at_pieces);
+        p->d_opieces.p = (OutPiece *)(d + at_opieces); p->d_cchunks.p = (CenterChunk *)(d + at_cchunks);
+        p->d_gsegs.p = (GatherSeg *)(d + at_gsegs); p->d_gchunks.p = (GatherChunk *)(d + at_gchunks);
+        p->d_tile_items.p = (uint32_t *)(d + at_items); p->d_total.p = d + at_total;
+        p->d_wcounters.p = (uint32_t *)(d + at_wcounters);
+        p->tile_items_zero = true;
+        p->wcounters_zero = true;
+        if (hist_here) { p->d_hist.p = d + at_hist; p->hist_clean = true; }
+    }
+};
 
 // The tables of a plan, built on the GPU.  `p` arrives with nseg / out_elems / rows set; on PC_OK it has its tables in
 // HBM (d_tables and the views into it), the sizes and flags the host builder sets, and no host copies.
@@ -949,26 +956,15 @@ int plan_build_gpu(pc_engine *e, pc_plan *p, int64_t nseg, const int32_t *tid, c
     HIP_TRY(hipMemcpyAsync(&h, misc, sizeof(h), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (h.first_bad != ~0ull) {   // the defect of the lowest segment index, as a serial pass reports it
-        const long long b = (long long)(h.first_bad >> 8);
-        const int kind = (int)(h.first_bad & 0xffu);
-        if (kind == 1) return fail(PC_ERR_ARG, "segment %lld: end < start", b);
-        if (kind == 2) return fail(PC_ERR_ARG, "segment %lld: out_step must be +1, -1 or 0 (sum)", b);
-        const int64_t len = end[b] - start[b], first = out_off[b], last = out_off[b] + (int64_t)out_step[b] * (len - 1);
-        const int64_t lo = std::min(first, last), hi = std::max(first, last) + (int64_t)(rows - 1) * row_stride[b];
-        return fail(PC_ERR_ARG, "segment %lld: output slice [%lld,%lld] outside buffer of %lld elements", b, (long long)lo, (long long)hi, (long long)out_elems);
+        PlanDefect bad = {(int)(h.first_bad & 0xffu), (int64_t)(h.first_bad >> 8), 0, 0};
+        if (bad.kind == kDefectSlice) plan_slice_bounds({nseg, tid, start, end, strand, out_off, out_step, row_stride}, bad.seg, rows, &bad.lo, &bad.hi);
+        return fail(PC_ERR_ARG, "%s", plan_defect_message(bad, out_elems).c_str());
     }
     p->modes = h.modes;
     p->covered = (int64_t)h.covered;
     p->has_sums = h.has_sums != 0;
-    int nmodes = 0;
-    for (int m = 0; m < kModes; ++m) nmodes += (h.modes >> m) & 1;
-    if (nmodes == 0) nmodes = 1;
-    {   // window size: as the host builder
-        int64_t budget = 0;
-        const int G = choose_window(rows, nmodes, h.n_iv, h.iv_len, e->knobs.tile_g, &budget);
-        if ((rows > 1 ? 2 : 4) * (int64_t)nmodes * rows * G > 150 * 1024) return fail(PC_ERR_ARG, "pc_plan_create: too many rows (%d) for the LDS window", rows);
-        p->G = G;
-    }
+    if (!plan_window(rows, h.modes, h.n_iv, h.iv_len, e->knobs.tile_g, &p->G))
+        return fail(PC_ERR_ARG, "%s", plan_defect_message({kDefectRows, 0, rows, 0}, out_elems).c_str());
     const int G = p->G;
     const int split_modes = rows > 1 ? 1 : 0;
     const size_t n_iv = (size_t)h.n_iv;
@@ -1056,164 +1052,140 @@ int plan_build_gpu(pc_engine *e, pc_plan *p, int64_t nseg, const int32_t *tid, c
     p->max_slots = (int)h.max_slots;
     p->n_tiles = n_tiles; p->n_pieces = n_pieces; p->n_opieces = n_op;
     pclk.lap("plan(gpu): pieces + tiles + output pieces");
-    // ---- the plan's block, laid out as the host builder lays it out
-    size_t bytes = 0;
-    auto place = [&bytes](size_t k) { const size_t at = bytes; bytes += (k + 255) & ~(size_t)255; return at; };
-    const size_t at_tiles = place(n_tiles * sizeof(Tile)), at_pieces = place(n_pieces * sizeof(Piece)), at_opieces = place(n_op * sizeof(OutPiece)),
-                 at_cchunks = place(0), at_gsegs = place(0), at_gchunks = place(0),
-                 at_items = place((n_tiles + 1) * sizeof(uint32_t)), at_wcounters = place(64), at_total = place(64);
-    const size_t hist_full = (size_t)p->npos * (size_t)p->rows * sizeof(double);
-    const bool hist_here = hist_full > 0 && hist_full <= 64 * 1024;
-    const size_t at_hist = hist_here ? place(hist_full) : 0;
-    PC_TRY(p->d_tables.reserve(bytes));
+    // ---- the plan's block
+    const PlanBlockLayout blk(n_tiles, n_pieces, n_op, 0, 0, 0, p->npos, p->rows);
+    PC_TRY(p->d_tables.reserve(blk.bytes));
     uint8_t *d = p->d_tables.p;
-    if (n_tiles) HIP_TRY(hipMemcpyAsync(d + at_tiles, tiles_tmp, n_tiles * sizeof(Tile), hipMemcpyDeviceToDevice, st));
-    if (n_pieces) HIP_TRY(hipMemcpyAsync(d + at_pieces, psorted, n_pieces * sizeof(Piece), hipMemcpyDeviceToDevice, st));
-    if (n_op) hipLaunchKernelGGL(k_out_sorted, dim3((unsigned)((n_op + 255) / 256)), dim3(256), 0, st, misc, otile2, oidx2, oraw, (OutPiece *)(d + at_opieces), (Tile *)(d + at_tiles));
-    HIP_TRY(hipMemsetAsync(d + at_items, 0, bytes - at_items, st));
+    if (n_tiles) HIP_TRY(hipMemcpyAsync(d + blk.at_tiles, tiles_tmp, n_tiles * sizeof(Tile), hipMemcpyDeviceToDevice, st));
+    if (n_pieces) HIP_TRY(hipMemcpyAsync(d + blk.at_pieces, psorted, n_pieces * sizeof(Piece), hipMemcpyDeviceToDevice, st));
+    if (n_op) hipLaunchKernelGGL(k_out_sorted, dim3((unsigned)((n_op + 255) / 256)), dim3(256), 0, st, misc, otile2, oidx2, oraw, (OutPiece *)(d + blk.at_opieces), (Tile *)(d + blk.at_tiles));
+    HIP_TRY(hipMemsetAsync(d + blk.at_items, 0, blk.zeroed_bytes(), st));
     HIP_TRY(hipGetLastError());
-    p->d_tiles.p = (Tile *)(d + at_tiles); p->d_pieces.p = (Piece *)(d + at_pieces);
-    p->d_opieces.p = (OutPiece *)(d + at_opieces); p->d_cchunks.p = (CenterChunk *)(d + at_cchunks);
-    p->d_gsegs.p = (GatherSeg *)(d + at_gsegs); p->d_gchunks.p = (GatherChunk *)(d + at_gchunks);
-    p->d_tile_items.p = (uint32_t *)(d + at_items); p->d_total.p = d + at_total;
-    p->d_wcounters.p = (uint32_t *)(d + at_wcounters);
-    p->tile_items_zero = true;
-    p->wcounters_zero = true;
-    if (hist_here) { p->d_hist.p = d + at_hist; p->hist_clean = true; }
-    p->lazy_center = true;
+    blk.bind(p);
     p->gpu_built = true;
     p->host_inputs = false;
     pclk.lap("plan(gpu): tables");
     return PC_OK;
 }
 
-// The center-only tables of a large plan (see pc_plan_create): built on first use.
-// The tables of a large plan that only the center rule (64-position chunks) or only the coordinate export (the
-// per-segment gather list) reads are built and uploaded when first asked for, each on its own.
+// The tables of a host-built plan (p->host) into one device block with one upload (a plan of one short segment is
+// otherwise dominated by the per-copy cost); the per-tile item counters arrive zeroed with it.  On an error the caller
+// waits for the stream before it deletes the plan: copies out of the plan's vectors may be in flight.
+int plan_upload(pc_engine *e, pc_plan *p) {
+    StageClock pclk;
+    const HostPlan &hp = p->host;
+    const PlanBlockLayout blk(hp.tiles.size(), hp.pieces.size(), hp.opieces.size(), hp.cchunks.size(), hp.gsegs.size(), hp.gchunks.size(), p->npos, p->rows);
+    // (a large annotation's tables -- tens of MB -- go up table by table from where they are: a
+    // page-locked buffer of that size costs more to create than it saves)
+    const bool through_pinned = blk.bytes <= ((size_t)4 << 20);
+    PC_TRY(p->d_tables.reserve(blk.bytes));
+    if (through_pinned && e->pinned_busy && hipEventSynchronize(e->ev_pinned) != hipSuccess) return fail(PC_ERR_HIP, "pc_plan_create: wait failed");
+    if (through_pinned) PC_TRY(e->pinned.reserve(blk.bytes));
+    uint8_t *h = through_pinned ? e->pinned.p : nullptr, *d = p->d_tables.p;
+    bool copy_failed = false;
+    auto put = [&](size_t at, const void *src, size_t n) {
+        if (!n) return;
+        if (through_pinned) memcpy(h + at, src, n);
+        else if (hipMemcpyAsync(d + at, src, n, hipMemcpyHostToDevice, e->stream) != hipSuccess) copy_failed = true;
+    };
+    put(blk.at_tiles, hp.tiles.data(), hp.tiles.size() * sizeof(Tile));
+    put(blk.at_pieces, hp.pieces.data(), hp.pieces.size() * sizeof(Piece));
+    put(blk.at_opieces, hp.opieces.data(), hp.opieces.size() * sizeof(OutPiece));
+    put(blk.at_cchunks, hp.cchunks.data(), hp.cchunks.size() * sizeof(CenterChunk));
+    put(blk.at_gsegs, hp.gsegs.data(), hp.gsegs.size() * sizeof(GatherSeg));
+    put(blk.at_gchunks, hp.gchunks.data(), hp.gchunks.size() * sizeof(GatherChunk));
+    if (through_pinned) memset(h + blk.at_items, 0, blk.zeroed_bytes());
+    else if (hipMemsetAsync(d + blk.at_items, 0, blk.zeroed_bytes(), e->stream) != hipSuccess) copy_failed = true;
+    blk.bind(p);
+    p->n_tiles = hp.tiles.size(); p->n_pieces = hp.pieces.size(); p->n_opieces = hp.opieces.size();
+    p->n_cchunks = hp.cchunks.size(); p->n_gchunks = hp.gchunks.size();
+    if (!through_pinned) {   // the copies read the plan's own vectors, which live as long as the plan
+        if (copy_failed) return fail(PC_ERR_HIP, "pc_plan_create: upload failed");
+    } else {
+        if (hipMemcpyAsync(d, h, blk.bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) return fail(PC_ERR_HIP, "pc_plan_create: upload failed");
+        if (hipEventRecord(e->ev_pinned, e->stream) != hipSuccess) return fail(PC_ERR_HIP, "pc_plan_create: event failed");
+        e->pinned_busy = true;
+    }
+    pclk.lap("plan: upload");
+    return PC_OK;
+}
+
+// The tables of a GPU-built plan that only the center rule (64-position chunks) or only the coordinate export (the
+// per-segment gather list) reads are built when first asked for, each on its own, from the tables in HBM: a point-rule
+// plan of 479 k exons otherwise pays for 1.4 M chunk descriptors it never uses.  (A host-built plan has everything in
+// its one upload.)
 int ensure_center_tables(pc_engine *e, pc_plan *p) {
-    if (!p->lazy_center || p->center_ready) return PC_OK;
-    if (p->gpu_built) {   // from the tables in HBM: chunks per tile, exclusive sum, fill
-        using namespace pcplan;
-        hipStream_t st = e->stream;
-        const size_t ntl = p->n_tiles;
-        size_t tb = 0;
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)ntl + 1, st);
-        Bump A;
-        uint32_t *cnt = nullptr, *at = nullptr;
-        uint8_t *tmp = nullptr;
-        for (int pass = 0; pass < 2; ++pass) {
-            A.used = 0;
-            cnt = A.take<uint32_t>(ntl + 1); at = A.take<uint32_t>(ntl + 1); tmp = A.take<uint8_t>(tb + 256);
-            if (pass == 0) {
-                PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
-                A.base = e->plan_scratch[0].p;
-            }
+    if (!p->gpu_built || p->center_ready) return PC_OK;
+    // chunks per tile, exclusive sum, fill
+    using namespace pcplan;
+    hipStream_t st = e->stream;
+    const size_t ntl = p->n_tiles;
+    size_t tb = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)ntl + 1, st);
+    Bump A;
+    uint32_t *cnt = nullptr, *at = nullptr;
+    uint8_t *tmp = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        A.used = 0;
+        cnt = A.take<uint32_t>(ntl + 1); at = A.take<uint32_t>(ntl + 1); tmp = A.take<uint8_t>(tb + 256);
+        if (pass == 0) {
+            PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
+            A.base = e->plan_scratch[0].p;
         }
-        uint32_t total = 0;
-        if (ntl) {
-            const unsigned g = (unsigned)((ntl + 255) / 256);
-            HIP_TRY(hipMemsetAsync(cnt + ntl, 0, 4, st));
-            hipLaunchKernelGGL(k_cchunk_count, dim3(g), dim3(256), 0, st, p->d_tiles.p, p->d_pieces.p, (uint32_t)ntl, cnt);
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, at, (int)ntl + 1, st));
-            HIP_TRY(hipMemcpyAsync(&total, at + ntl, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            PC_TRY(p->d_tables2.reserve(std::max<size_t>((size_t)total * sizeof(CenterChunk), 256)));
-            if (total) hipLaunchKernelGGL(k_cchunk_fill, dim3(g), dim3(256), 0, st, p->d_tiles.p, p->d_pieces.p, (uint32_t)ntl, at, (CenterChunk *)p->d_tables2.p);
-            HIP_TRY(hipGetLastError());
-        } else {
-            PC_TRY(p->d_tables2.reserve(256));
-        }
-        p->d_cchunks.p = (CenterChunk *)p->d_tables2.p;
-        p->n_cchunks = total;
-        p->center_ready = true;
-        return PC_OK;
     }
-    const int PT = std::min(usable_cpus(), 32);
-    const size_t ntl = p->tiles.size();
-    // chunks per tile, in tile / piece order (what the eager path produces piece by piece)
-    std::vector<size_t> at(ntl + 1, 0);
-    for (size_t t = 0; t < ntl; ++t) {
-        size_t n = 0;
-        for (uint32_t i = p->tiles[t].piece_begin; i < p->tiles[t].piece_end; ++i) n += (size_t)(p->pieces[i].len + kWave - 1) / kWave;
-        at[t + 1] = at[t] + n;
+    uint32_t total = 0;
+    if (ntl) {
+        const unsigned g = (unsigned)((ntl + 255) / 256);
+        HIP_TRY(hipMemsetAsync(cnt + ntl, 0, 4, st));
+        hipLaunchKernelGGL(k_cchunk_count, dim3(g), dim3(256), 0, st, p->d_tiles.p, p->d_pieces.p, (uint32_t)ntl, cnt);
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, at, (int)ntl + 1, st));
+        HIP_TRY(hipMemcpyAsync(&total, at + ntl, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        PC_TRY(p->d_tables2.reserve(std::max<size_t>((size_t)total * sizeof(CenterChunk), 256)));
+        if (total) hipLaunchKernelGGL(k_cchunk_fill, dim3(g), dim3(256), 0, st, p->d_tiles.p, p->d_pieces.p, (uint32_t)ntl, at, (CenterChunk *)p->d_tables2.p);
+        HIP_TRY(hipGetLastError());
+    } else {
+        PC_TRY(p->d_tables2.reserve(256));
     }
-    p->cchunks.resize(at[ntl]);
-    parallel_chunks((int64_t)ntl, PT, [&](int, int64_t tb, int64_t te) {
-        for (int64_t t = tb; t < te; ++t) {
-            size_t k = at[(size_t)t];
-            for (uint32_t i = p->tiles[(size_t)t].piece_begin; i < p->tiles[(size_t)t].piece_end; ++i) {
-                const Piece &pc_ = p->pieces[i];
-                for (int32_t a = 0; a < pc_.len; a += kWave) {
-                    CenterChunk c;
-                    c.hist_off = pc_.hist_off + a; c.tid = p->tiles[(size_t)t].tid; c.start = pc_.start + a;
-                    c.len = std::min<int32_t>(kWave, pc_.len - a); c.mode = pc_.mode;
-                    c.op_begin = p->tiles[(size_t)t].op_begin; c.op_end = p->tiles[(size_t)t].op_end;
-                    p->cchunks[k++] = c;
-                }
-            }
-        }
-    });
-    PC_TRY(p->d_tables2.reserve(std::max<size_t>(p->cchunks.size() * sizeof(CenterChunk), 256)));
-    if (!p->cchunks.empty()) HIP_TRY(hipMemcpyAsync(p->d_tables2.p, p->cchunks.data(), p->cchunks.size() * sizeof(CenterChunk), hipMemcpyHostToDevice, e->stream));
     p->d_cchunks.p = (CenterChunk *)p->d_tables2.p;
-    p->n_cchunks = p->cchunks.size();
+    p->n_cchunks = total;
     p->center_ready = true;
     return PC_OK;
 }
 
 int ensure_gather_tables(pc_engine *e, pc_plan *p) {
-    if (!p->lazy_center || p->gather_ready) return PC_OK;
-    if (p->gpu_built) {   // the per-segment records are in HBM already: (segment, chunk) pairs by count, exclusive sum, fill
-        using namespace pcplan;
-        hipStream_t st = e->stream;
-        const size_t n = (size_t)p->nseg;
-        size_t tb = 0;
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st);
-        Bump A;
-        uint32_t *cnt = nullptr, *at = nullptr;
-        uint8_t *tmp = nullptr;
-        for (int pass = 0; pass < 2; ++pass) {
-            A.used = 0;
-            cnt = A.take<uint32_t>(n + 1); at = A.take<uint32_t>(n + 1); tmp = A.take<uint8_t>(tb + 256);
-            if (pass == 0) {
-                PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
-                A.base = e->plan_scratch[0].p;
-            }
+    if (!p->gpu_built || p->gather_ready) return PC_OK;
+    // the per-segment records are in HBM already: (segment, chunk) pairs by count, exclusive sum, fill
+    using namespace pcplan;
+    hipStream_t st = e->stream;
+    const size_t n = (size_t)p->nseg;
+    size_t tb = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st);
+    Bump A;
+    uint32_t *cnt = nullptr, *at = nullptr;
+    uint8_t *tmp = nullptr;
+    for (int pass = 0; pass < 2; ++pass) {
+        A.used = 0;
+        cnt = A.take<uint32_t>(n + 1); at = A.take<uint32_t>(n + 1); tmp = A.take<uint8_t>(tb + 256);
+        if (pass == 0) {
+            PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
+            A.base = e->plan_scratch[0].p;
         }
-        uint32_t total = 0;
-        const unsigned g = (unsigned)((n + 255) / 256);
-        HIP_TRY(hipMemsetAsync(cnt + n, 0, 4, st));
-        if (n) hipLaunchKernelGGL(k_gchunk_count, dim3(g), dim3(256), 0, st, p->d_gsegs_own.p, p->nseg, cnt);
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, at, (int)n + 1, st));
-        HIP_TRY(hipMemcpyAsync(&total, at + n, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        PC_TRY(p->d_tables3.reserve(std::max<size_t>((size_t)total * sizeof(GatherChunk), 256)));
-        if (total) hipLaunchKernelGGL(k_gchunk_fill, dim3(g), dim3(256), 0, st, p->nseg, cnt, at, (GatherChunk *)p->d_tables3.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));   // (the scratch block may be reused by the next builder call)
-        p->d_gsegs.p = p->d_gsegs_own.p;
-        p->d_gchunks.p = (GatherChunk *)p->d_tables3.p;
-        p->n_gchunks = total;
-        p->gather_ready = true;
-        return PC_OK;
     }
-    const int PT = std::min(usable_cpus(), 32);
-    std::vector<size_t> gat((size_t)p->nseg + 1, 0);
-    for (int64_t s = 0; s < p->nseg; ++s) gat[(size_t)s + 1] = gat[(size_t)s] + (size_t)((p->gsegs[(size_t)s].len + kGatherChunk - 1) / kGatherChunk);
-    p->gchunks.resize(gat[(size_t)p->nseg]);
-    parallel_chunks(p->nseg, PT, [&](int, int64_t sb, int64_t se) {
-        for (int64_t s = sb; s < se; ++s)
-            for (size_t c = 0; c < gat[(size_t)s + 1] - gat[(size_t)s]; ++c) p->gchunks[gat[(size_t)s] + c] = {(uint32_t)s, (uint32_t)c};
-    });
-    size_t bytes = 0;
-    auto place = [&bytes](size_t n) { const size_t a = bytes; bytes += (n + 255) & ~(size_t)255; return a; };
-    const size_t at_s = place(p->gsegs.size() * sizeof(GatherSeg)), at_g = place(p->gchunks.size() * sizeof(GatherChunk));
-    PC_TRY(p->d_tables3.reserve(std::max<size_t>(bytes, 256)));
-    uint8_t *d = p->d_tables3.p;
-    if (!p->gsegs.empty()) HIP_TRY(hipMemcpyAsync(d + at_s, p->gsegs.data(), p->gsegs.size() * sizeof(GatherSeg), hipMemcpyHostToDevice, e->stream));
-    if (!p->gchunks.empty()) HIP_TRY(hipMemcpyAsync(d + at_g, p->gchunks.data(), p->gchunks.size() * sizeof(GatherChunk), hipMemcpyHostToDevice, e->stream));
-    p->d_gsegs.p = (GatherSeg *)(d + at_s); p->d_gchunks.p = (GatherChunk *)(d + at_g);
-    p->n_gchunks = p->gchunks.size();
+    uint32_t total = 0;
+    const unsigned g = (unsigned)((n + 255) / 256);
+    HIP_TRY(hipMemsetAsync(cnt + n, 0, 4, st));
+    if (n) hipLaunchKernelGGL(k_gchunk_count, dim3(g), dim3(256), 0, st, p->d_gsegs_own.p, p->nseg, cnt);
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, at, (int)n + 1, st));
+    HIP_TRY(hipMemcpyAsync(&total, at + n, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    PC_TRY(p->d_tables3.reserve(std::max<size_t>((size_t)total * sizeof(GatherChunk), 256)));
+    if (total) hipLaunchKernelGGL(k_gchunk_fill, dim3(g), dim3(256), 0, st, p->nseg, cnt, at, (GatherChunk *)p->d_tables3.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the scratch block may be reused by the next builder call)
+    p->d_gsegs.p = p->d_gsegs_own.p;
+    p->d_gchunks.p = (GatherChunk *)p->d_tables3.p;
+    p->n_gchunks = total;
     p->gather_ready = true;
     return PC_OK;
 }
@@ -2344,446 +2316,33 @@ int pc_plan_create(pc_engine *e, int64_t nseg, const int32_t *tid, const int64_t
         return fail(PC_ERR_ARG, "pc_plan_create: NULL array");
     if (nseg >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_plan_create: too many segments");
     HIP_TRY(hipSetDevice(e->device));
-    const int ntid = e->ntid;
 
-    // large annotations: every pass of the builder as a kernel, a radix sort or a scan (plan_kernels.hip.h); the host
-    // builder below is what small plans -- and PC_PLAN_BUILD=host -- take, and what the GPU tables are tested against
-    if (nseg > 0 && (int64_t)ntid < ((int64_t)1 << pcplan::kTidBits) && (e->knobs.plan_build == 2 || (e->knobs.plan_build == 0 && nseg >= (1 << 13)))) {
-        pc_plan *gp = new pc_plan(e);
-        gp->nseg = nseg;
-        gp->out_elems = out_elems;
-        gp->rows = rows;
-        const int grc = plan_build_gpu(e, gp, nseg, tid, start, end, strand, out_off, out_step, row_stride, out_elems, rows);
-        if (grc != PC_OK) {
-            (void)hipStreamSynchronize(e->stream);
-            delete gp;
-            return grc;
-        }
-        *out = gp;
-        return PC_OK;
+    // large annotations: every pass of the builder as a kernel, a radix sort or a scan (plan_kernels.hip.h); small plans
+    // -- and PC_PLAN_BUILD=host -- take the serial host builder (plan_host.h), which the GPU tables are tested against
+    const bool on_gpu = nseg > 0 && (int64_t)e->ntid < ((int64_t)1 << pcplan::kTidBits) &&
+                        (e->knobs.plan_build == 2 || (e->knobs.plan_build == 0 && nseg >= (1 << 13)));
+    HostPlan hp;
+    if (!on_gpu) {
+        PlanDefect bad;
+        if (!build_plan_host({nseg, tid, start, end, strand, out_off, out_step, row_stride}, e->ntid, rows, out_elems, e->knobs.tile_g, hp, bad))
+            return fail(PC_ERR_ARG, "%s", plan_defect_message(bad, out_elems).c_str());
     }
-
-    StageClock pclk;
-    struct Iv { int32_t tid; int32_t mode; int64_t s, e; };
-    std::vector<Iv> ivs;
-    ivs.reserve((size_t)nseg);
     pc_plan *p = new pc_plan(e);
     p->nseg = nseg;
     p->out_elems = out_elems;
     p->rows = rows;
-    p->gsegs.resize((size_t)nseg);
-    p->h_tid.assign(tid, tid + nseg);
-    p->h_start.assign(start, start + nseg);
-    p->h_end.assign(end, end + nseg);
-    p->h_strand.assign(strand, strand + nseg);
-    const int64_t kMaxPos = 0x7fffffffLL;
-    uint32_t modes = 0;
-    // (large annotations: the passes over the segments and the per-contig sorts run on a thread pool)
-    const int PT = nseg >= (1 << 16) ? std::min(usable_cpus(), 32) : 1;
-    {
-        struct SegPart { std::vector<Iv> ivs; uint32_t modes = 0; int64_t covered = 0; bool has_sums = false; int64_t bad = -1; int bad_kind = 0; int64_t b_lo = 0, b_hi = 0; };
-        std::vector<SegPart> parts((size_t)PT);
-        parallel_chunks(nseg, PT, [&](int th, int64_t sb, int64_t se) {
-            SegPart &sp = parts[(size_t)th];
-            sp.ivs.reserve((size_t)(se - sb));
-            for (int64_t s = sb; s < se; ++s) {
-                const int64_t len = end[s] - start[s];
-                if (len < 0) { sp.bad = s; sp.bad_kind = 1; return; }
-                if (out_step[s] != 1 && out_step[s] != -1 && out_step[s] != 0) { sp.bad = s; sp.bad_kind = 2; return; }
-                if (out_step[s] == 0) sp.has_sums = true;
-                // output bounds
-                if (len > 0) {
-                    const int64_t first = out_off[s], last = out_off[s] + (int64_t)out_step[s] * (len - 1);
-                    const int64_t lo = std::min(first, last), hi = std::max(first, last) + (int64_t)(rows - 1) * row_stride[s];
-                    if (lo < 0 || hi >= out_elems || row_stride[s] < 0) { sp.bad = s; sp.bad_kind = 3; sp.b_lo = lo; sp.b_hi = hi; return; }
-                }
-                GatherSeg &g = p->gsegs[(size_t)s];
-                g.out_off = out_off[s]; g.row_stride = row_stride[s]; g.len = len; g.step = out_step[s]; g.pad = 0;
-                g.hist_off = -1; g.clip_lo = 0; g.clip_hi = 0; g.start = start[s];
-                sp.covered += (out_step[s] == 0 ? (len > 0 ? 1 : 0) : len) * rows;
-                if (tid[s] < 0 || tid[s] >= ntid || len == 0) continue; // unknown chromosome: zeros (genome_array.py:795-798)
-                const int64_t cs = std::max<int64_t>(start[s], 0), ce = std::min<int64_t>(end[s], kMaxPos);
-                if (ce <= cs) continue;
-                g.clip_lo = cs - start[s];
-                g.clip_hi = ce - start[s];
-                const int m = mode_of(strand[s]);
-                sp.modes |= 1u << m;
-                sp.ivs.push_back({tid[s], m, cs, ce});
-            }
-        });
-        for (const SegPart &sp : parts)   // the defect of the lowest segment index, as a serial pass reports it
-            if (sp.bad >= 0) {
-                const long long b = (long long)sp.bad;
-                delete p;
-                if (sp.bad_kind == 1) return fail(PC_ERR_ARG, "segment %lld: end < start", b);
-                if (sp.bad_kind == 2) return fail(PC_ERR_ARG, "segment %lld: out_step must be +1, -1 or 0 (sum)", b);
-                return fail(PC_ERR_ARG, "segment %lld: output slice [%lld,%lld] outside buffer of %lld elements", b, (long long)sp.b_lo, (long long)sp.b_hi, (long long)out_elems);
-            }
-        for (SegPart &sp : parts) {
-            modes |= sp.modes;
-            p->covered += sp.covered;
-            p->has_sums |= sp.has_sums;
-            ivs.insert(ivs.end(), sp.ivs.begin(), sp.ivs.end());
-        }
+    int rc;
+    if (on_gpu) rc = plan_build_gpu(e, p, nseg, tid, start, end, strand, out_off, out_step, row_stride, out_elems, rows);
+    else {
+        p->G = hp.G; p->modes = hp.modes; p->max_slots = hp.max_slots; p->npos = hp.npos;
+        p->covered = hp.covered; p->has_sums = hp.has_sums; p->out_needs_zero = hp.out_needs_zero;
+        p->host = std::move(hp);
+        p->h_tid.assign(tid, tid + nseg);
+        p->h_start.assign(start, start + nseg);
+        p->h_end.assign(end, end + nseg);
+        p->h_strand.assign(strand, strand + nseg);
+        rc = plan_upload(e, p);
     }
-    p->modes = modes;
-    int nmodes = 0;
-    for (int m = 0; m < kModes; ++m) nmodes += (modes >> m) & 1;
-    if (nmodes == 0) nmodes = 1;
-    {   // window size (the per-call hard limit of LDS is checked in pc_count)
-        unsigned long long iv_len = 0;
-        for (const Iv &iv : ivs) iv_len += (unsigned long long)(iv.e - iv.s);
-        int64_t budget = 0;
-        const int G = choose_window(rows, nmodes, (unsigned long long)ivs.size(), iv_len, e->knobs.tile_g, &budget);
-        if ((rows > 1 ? 2 : 4) * (int64_t)nmodes * rows * G > 150 * 1024) { delete p; return fail(PC_ERR_ARG, "pc_plan_create: too many rows (%d) for the LDS window", rows); }
-        p->G = G;
-    }
-    const int G = p->G;
-
-    pclk.lap("plan: segments");
-    // ---- islands: union of the queried intervals per (tid, mode)
-    // sorted by (contig, mode, start, end): contigs first (a counting pass), then every contig's stretch on its own
-    // thread -- the contigs of an annotation are independent
-    auto by_contig = [ntid, PT](auto &v, auto tid_of, auto less) {
-        typedef typename std::remove_reference<decltype(v)>::type Vec;
-        if (PT <= 1 || v.size() < (size_t)(1 << 16)) { std::sort(v.begin(), v.end(), less); return; }
-        std::vector<size_t> at((size_t)ntid + 1, 0);
-        for (const auto &x : v) at[(size_t)tid_of(x) + 1] += 1;
-        for (int t = 0; t < ntid; ++t) at[(size_t)t + 1] += at[(size_t)t];
-        Vec tmp(v.size());
-        { std::vector<size_t> cur(at.begin(), at.end() - 1); for (const auto &x : v) tmp[cur[(size_t)tid_of(x)]++] = x; }
-        v.swap(tmp);
-        // heaviest contigs first, dealt round-robin
-        std::vector<int> order((size_t)ntid);
-        for (int t = 0; t < ntid; ++t) order[(size_t)t] = t;
-        std::sort(order.begin(), order.end(), [&](int a, int b) { return at[(size_t)a + 1] - at[(size_t)a] > at[(size_t)b + 1] - at[(size_t)b]; });
-        parallel_chunks((int64_t)PT, PT, [&](int th, int64_t, int64_t) {
-            for (size_t k = (size_t)th; k < order.size(); k += (size_t)PT) {
-                const int t = order[k];
-                std::sort(v.begin() + (std::ptrdiff_t)at[(size_t)t], v.begin() + (std::ptrdiff_t)at[(size_t)t + 1], less);
-            }
-        });
-    };
-    by_contig(ivs, [](const Iv &a) { return a.tid; }, [](const Iv &a, const Iv &b) {
-        if (a.tid != b.tid) return a.tid < b.tid;
-        if (a.mode != b.mode) return a.mode < b.mode;
-        if (a.s != b.s) return a.s < b.s;
-        return a.e < b.e;
-    });
-    struct Island { int32_t tid, mode; int64_t s, e, off; };
-    std::vector<Island> islands;
-    for (const Iv &iv : ivs) {
-        if (!islands.empty() && islands.back().tid == iv.tid && islands.back().mode == iv.mode && iv.s <= islands.back().e)
-            islands.back().e = std::max(islands.back().e, iv.e);
-        else
-            islands.push_back({iv.tid, iv.mode, iv.s, iv.e, 0});
-    }
-    int64_t npos = 0;
-    for (Island &is : islands) { is.off = npos; npos += is.e - is.s; }
-    p->npos = npos;
-
-    pclk.lap("plan: islands");
-    // ---- every segment -> its island (binary search)
-    parallel_chunks(nseg, PT, [&](int, int64_t sb, int64_t se) {
-    size_t hint = 0;   // (the exons of a chain follow each other in the caller's arrays: the search starts where the last one ended)
-    for (int64_t s = sb; s < se; ++s) {
-        GatherSeg &g = p->gsegs[(size_t)s];
-        if (g.clip_hi <= g.clip_lo) continue;
-        const int64_t cs = start[s] + g.clip_lo;
-        const int m = mode_of(strand[s]);
-        const int32_t ts = tid[s];
-        // first island after the last one with (tid, mode, s) <= (tid, m, cs)
-        const size_t lo = gallop_lower_bound(islands.size(), hint, [&](size_t k) {
-            const Island &is = islands[k];
-            return is.tid < ts || (is.tid == ts && (is.mode < m || (is.mode == m && is.s <= cs)));
-        });
-        hint = lo;
-        const Island &is = islands[lo - 1];
-        g.hist_off = is.off + (cs - is.s);
-    }
-    });
-
-    pclk.lap("plan: segment->island");
-    // ---- pieces: islands cut at the fixed genome grid of G positions; tiles: grid windows
-    struct RawPiece { int32_t tid; int64_t win; Piece pc_; };
-    PodVec<RawPiece> raw;
-    // The tables only the center rule and the coordinate export read -- the 64-position chunks, the per-segment gather
-    // list -- are built (and uploaded) when first needed for a large annotation: a point-rule plan of 479 k exons
-    // otherwise pays for 1.4 M chunk descriptors it never uses.  Small plans keep everything in their one upload.
-    p->lazy_center = nseg >= (1 << 16);
-    auto cut_island = [G](const Island &is, RawPiece *dst) {   // the island's pieces, in order; returns their number
-        size_t k = 0;
-        for (int64_t a = is.s; a < is.e;) {
-            const int64_t win = (a / G) * G;
-            const int64_t b = std::min<int64_t>(is.e, win + G);
-            if (dst) {
-                Piece pc_;
-                pc_.hist_off = is.off + (a - is.s); pc_.start = (int32_t)a; pc_.len = (int32_t)(b - a); pc_.mode = is.mode; pc_.pad = 0;
-                dst[k] = {is.tid, win, pc_};
-            }
-            ++k;
-            a = b;
-        }
-        return k;
-    };
-    {   // islands -> pieces: counted, placed by prefix sum, filled by all threads
-        std::vector<size_t> at(islands.size() + 1, 0);
-        parallel_chunks((int64_t)islands.size(), PT, [&](int, int64_t ib, int64_t ie) {
-            for (int64_t i = ib; i < ie; ++i) {
-                const Island &is = islands[(size_t)i];
-                at[(size_t)i + 1] = is.e > is.s ? (size_t)((is.e - 1) / G - is.s / G + 1) : 0;
-            }
-        });
-        for (size_t i = 0; i < islands.size(); ++i) at[i + 1] += at[i];
-        raw.resize(at.back());
-        parallel_chunks((int64_t)islands.size(), PT, [&](int, int64_t ib, int64_t ie) {
-            for (int64_t i = ib; i < ie; ++i) cut_island(islands[(size_t)i], raw.data() + at[(size_t)i]);
-        });
-        // sorted by (contig, window, mode, start).  The islands are in contig order, so the pieces of a contig are
-        // already one stretch of `raw`: every stretch is sorted in place on its own thread, heaviest contigs first
-        auto less = [](const RawPiece &a, const RawPiece &b) {
-            if (a.win != b.win) return a.win < b.win;
-            if (a.pc_.mode != b.pc_.mode) return a.pc_.mode < b.pc_.mode;
-            return a.pc_.start < b.pc_.start;
-        };
-        std::vector<std::pair<size_t, size_t>> stretch;   // [begin, end) of every contig that has pieces
-        for (size_t i = 0; i < islands.size();) {
-            size_t j = i + 1;
-            while (j < islands.size() && islands[j].tid == islands[i].tid) ++j;
-            if (at[j] > at[i]) stretch.push_back({at[i], at[j]});
-            i = j;
-        }
-        std::sort(stretch.begin(), stretch.end(), [](const std::pair<size_t, size_t> &a, const std::pair<size_t, size_t> &b) {
-            return a.second - a.first > b.second - b.first;
-        });
-        parallel_chunks((int64_t)PT, PT, [&](int th, int64_t, int64_t) {
-            for (size_t k = (size_t)th; k < stretch.size(); k += (size_t)PT)
-                std::sort(raw.begin() + (std::ptrdiff_t)stretch[k].first, raw.begin() + (std::ptrdiff_t)stretch[k].second, less);
-        });
-    }
-    int max_slots = 1;
-    // A multi-row plan (stratified rule: rows x G bins per strand mode) gives every strand mode of a window a tile of its
-    // own: the LDS window of the launch is then sized for ONE mode -- C5: 14 KB instead of 25, seven workgroups per CU
-    // instead of six -- and the two windows in a hundred that query both strands are scanned twice.  Single-row plans keep
-    // all modes of a window in one tile: one pass over the records serves both strands.
-    const bool split_modes = rows > 1;
-    auto new_tile = [&](size_t i) {
-        return i == 0 || raw[i - 1].tid != raw[i].tid || raw[i - 1].win != raw[i].win || (split_modes && raw[i - 1].pc_.mode != raw[i].pc_.mode);
-    };
-    auto fill_tile = [&](Tile &t, size_t i0, size_t i1) {   // the tile of the sorted pieces [i0, i1)
-        t.tid = raw[i0].tid; t.win_start = (int32_t)raw[i0].win; t.piece_begin = (uint32_t)i0; t.piece_end = (uint32_t)i1;
-        t.mode_mask = 0; t.op_begin = t.op_end = 0; t.span_lo = 0xffff; t.span_hi = 0;
-        for (size_t i = i0; i < i1; ++i) {
-            t.mode_mask |= 1u << raw[i].pc_.mode;
-            t.span_lo = std::min<uint16_t>(t.span_lo, (uint16_t)(raw[i].pc_.start - t.win_start));
-            t.span_hi = std::max<uint16_t>(t.span_hi, (uint16_t)(raw[i].pc_.start - t.win_start + raw[i].pc_.len));
-        }
-    };
-    if (p->lazy_center && PT > 1) {
-        // large plans: every thread takes a stretch of the sorted pieces and owns the tiles that START in it
-        p->pieces.resize(raw.size());
-        std::vector<size_t> tcount((size_t)PT + 1, 0);
-        parallel_chunks((int64_t)raw.size(), PT, [&](int th, int64_t ib, int64_t ie) {
-            size_t n = 0;
-            for (int64_t i = ib; i < ie; ++i) {
-                p->pieces[(size_t)i] = raw[(size_t)i].pc_;
-                n += new_tile((size_t)i) ? 1 : 0;
-            }
-            tcount[(size_t)th + 1] = n;
-        });
-        for (int th = 0; th < PT; ++th) tcount[(size_t)th + 1] += tcount[(size_t)th];
-        p->tiles.resize(tcount[(size_t)PT]);
-        parallel_chunks((int64_t)raw.size(), PT, [&](int th, int64_t ib, int64_t ie) {
-            size_t k = tcount[(size_t)th];
-            for (int64_t i = ib; i < ie; ++i) {
-                if (!new_tile((size_t)i)) continue;
-                size_t j = (size_t)i + 1;
-                while (j < raw.size() && !new_tile(j)) ++j;   // (a tile may end in the next thread's stretch)
-                fill_tile(p->tiles[k++], (size_t)i, j);
-            }
-        });
-    } else {
-        p->pieces.reserve(raw.size());
-        if (!p->lazy_center) p->cchunks.reserve((size_t)(npos / kWave) + raw.size());
-        for (size_t i = 0; i < raw.size();) {
-            size_t j = i + 1;
-            while (j < raw.size() && !new_tile(j)) ++j;
-            Tile t;
-            fill_tile(t, i, j);
-            p->tiles.push_back(t);
-            for (; i < j; ++i) {
-                p->pieces.push_back(raw[i].pc_);
-                // 64-position chunks for the ordered center replay (one wave each)
-                for (int32_t a = 0; !p->lazy_center && a < raw[i].pc_.len; a += kWave) {
-                    CenterChunk c;
-                    c.hist_off = raw[i].pc_.hist_off + a; c.tid = raw[i].tid; c.start = raw[i].pc_.start + a;
-                    c.len = std::min<int32_t>(kWave, raw[i].pc_.len - a); c.mode = raw[i].pc_.mode;
-                    c.op_begin = (uint32_t)(p->tiles.size() - 1); c.op_end = 0;   // the tile, until its output pieces are known (below)
-                    p->cchunks.push_back(c);
-                }
-            }
-        }
-    }
-    for (const Tile &t : p->tiles) max_slots = std::max(max_slots, __builtin_popcount(t.mode_mask));
-    p->max_slots = max_slots;
-
-    pclk.lap("plan: pieces+tiles+chunks");
-    // ---- output pieces: every queried segment cut at the tile grid, in the caller's layout
-    {
-        struct RawOut { uint32_t tile; OutPiece o; };
-        std::vector<std::vector<RawOut>> part((size_t)PT);
-        std::vector<uint8_t> part_zero((size_t)PT, 0);
-        parallel_chunks(nseg, PT, [&](int th, int64_t sb, int64_t se) {
-            std::vector<RawOut> &mine = part[(size_t)th];
-            mine.reserve((size_t)(se - sb) + (size_t)(se - sb) / 2);
-            size_t seg_hint = 0;   // tile of the previous segment's last window: the next exon of the chain is close by
-            for (int64_t s = sb; s < se; ++s) {
-                const GatherSeg &g = p->gsegs[(size_t)s];
-                if (g.len > 0 && (g.hist_off < 0 || g.clip_lo > 0 || g.clip_hi < g.len)) part_zero[(size_t)th] = 1;
-                if (g.hist_off < 0 || g.clip_hi <= g.clip_lo) continue;
-                const int m = mode_of(strand[s]);
-                const int64_t cs = start[s] + g.clip_lo, ce = start[s] + g.clip_hi;
-                size_t prev = (size_t)-1;   // tile of the segment's previous window: the next window's tile follows it
-                for (int64_t a = cs; a < ce;) {
-                    const int64_t win = (a / G) * G;
-                    const int64_t b = std::min<int64_t>(ce, win + G);
-                    // tile of (tid, win)
-                    // (tiles are sorted by contig, window and -- when every mode has its own tile -- mode: a one-mode
-                    // tile's mask, 1 << mode, orders like the mode)
-                    size_t lo = prev + 1;
-                    const uint32_t want_mask = 1u << m;
-                    if (prev == (size_t)-1 || lo >= p->tiles.size() || p->tiles[lo].tid != tid[s] || (int64_t)p->tiles[lo].win_start != win ||
-                        (split_modes && p->tiles[lo].mode_mask != want_mask)) {
-                        const int32_t ts = tid[s];
-                        lo = gallop_lower_bound(p->tiles.size(), seg_hint, [&](size_t k) {
-                            const Tile &t = p->tiles[k];
-                            if (t.tid != ts) return t.tid < ts;
-                            if ((int64_t)t.win_start != win) return (int64_t)t.win_start < win;
-                            return split_modes && t.mode_mask < want_mask;
-                        });
-                    }
-                    prev = lo;
-                    seg_hint = lo;
-                    OutPiece o;
-                    o.out_off = g.out_off + (int64_t)g.step * (a - start[s]);
-                    o.row_stride = g.row_stride;
-                    o.hist_off = g.hist_off + (a - cs);
-                    o.start = (int32_t)a; o.len = (int32_t)(b - a); o.mode = m; o.step = g.step;
-                    mine.push_back({(uint32_t)lo, o});
-                    a = b;
-                }
-            }
-        });
-        for (uint8_t z : part_zero) if (z) p->out_needs_zero = true;
-        // stable counting sort by tile (the thread lists are in segment order, taken in thread order).  The tile
-        // index space is cut into one stretch per thread; every thread walks all the lists' tile indices (4 bytes per
-        // record) and counts, then places, the records of its stretch: no serial pass over the records.
-        const size_t ntl = p->tiles.size();
-        std::vector<size_t> list_off(part.size() + 1, 0);
-        for (size_t k = 0; k < part.size(); ++k) list_off[k + 1] = list_off[k] + part[k].size();
-        PodVec<uint32_t> tile_of(list_off.back());
-        parallel_chunks((int64_t)part.size(), PT, [&](int, int64_t kb, int64_t ke) {
-            for (int64_t k = kb; k < ke; ++k)
-                for (size_t i = 0; i < part[(size_t)k].size(); ++i) tile_of[list_off[(size_t)k] + i] = part[(size_t)k][i].tile;
-        });
-        std::vector<uint32_t> at(ntl + 1, 0);
-        std::vector<size_t> stretch_total((size_t)PT + 1, 0);
-        auto stretch = [&](int th, size_t &t0, size_t &t1) { t0 = ntl * (size_t)th / (size_t)PT; t1 = ntl * ((size_t)th + 1) / (size_t)PT; };
-        parallel_chunks((int64_t)PT, PT, [&](int th, int64_t, int64_t) {   // records per tile of the stretch
-            size_t t0, t1;
-            stretch(th, t0, t1);
-            size_t n = 0;
-            for (const uint32_t t : tile_of)
-                if (t >= t0 && t < t1) { at[(size_t)t + 1] += 1; ++n; }
-            stretch_total[(size_t)th + 1] = n;
-        });
-        for (int th = 0; th < PT; ++th) stretch_total[(size_t)th + 1] += stretch_total[(size_t)th];
-        p->opieces.resize(list_off.back());
-        parallel_chunks((int64_t)PT, PT, [&](int th, int64_t, int64_t) {   // offsets of the stretch's tiles, then placement
-            size_t t0, t1;
-            stretch(th, t0, t1);
-            if (t0 == t1) return;
-            uint32_t run = (uint32_t)stretch_total[(size_t)th];
-            for (size_t t = t0; t < t1; ++t) {
-                const uint32_t c = at[t + 1];
-                p->tiles[t].op_begin = run;
-                at[t + 1] = run;            // cursor of tile t (at[] is indexed t + 1 within the stretch; at[t0] belongs to the stretch below)
-                run += c;
-                p->tiles[t].op_end = run;
-            }
-            for (size_t k = 0; k < part.size(); ++k) {
-                const uint32_t *tl = tile_of.data() + list_off[k];
-                const std::vector<RawOut> &v = part[k];
-                for (size_t i = 0; i < v.size(); ++i)
-                    if (tl[i] >= t0 && tl[i] < t1) p->opieces[at[(size_t)tl[i] + 1]++] = v[i].o;
-            }
-        });
-    }
-
-    for (CenterChunk &c : p->cchunks) {   // (eager tables of a small plan) the chunk's output pieces = those of its tile
-        const Tile &t = p->tiles[c.op_begin];
-        c.op_begin = t.op_begin;
-        c.op_end = t.op_end;
-    }
-    pclk.lap("plan: output pieces");
-    // ---- gather work list (center rule)
-    for (int64_t s = 0; !p->lazy_center && s < nseg; ++s) {
-        const int64_t len = p->gsegs[(size_t)s].len;
-        for (int64_t c = 0; c * kGatherChunk < len; ++c) p->gchunks.push_back({(uint32_t)s, (uint32_t)c});
-    }
-
-    pclk.lap("plan: gather list");
-    // ---- one device block and one upload for all tables (a plan of one short segment is otherwise
-    // dominated by the per-copy cost); the per-tile item counters arrive zeroed with it
-    size_t bytes = 0;
-    auto place = [&bytes](size_t n) { const size_t at = bytes; bytes += (n + 255) & ~(size_t)255; return at; };
-    const size_t at_tiles = place(p->tiles.size() * sizeof(Tile)), at_pieces = place(p->pieces.size() * sizeof(Piece)),
-                 at_opieces = place(p->opieces.size() * sizeof(OutPiece)), at_cchunks = place(p->cchunks.size() * sizeof(CenterChunk)),
-                 at_gsegs = place(p->lazy_center ? 0 : p->gsegs.size() * sizeof(GatherSeg)), at_gchunks = place(p->gchunks.size() * sizeof(GatherChunk)),
-                 at_items = place((p->tiles.size() + 1) * sizeof(uint32_t)), at_wcounters = place(64), at_total = place(64);
-    // a short compact histogram rides along, already zeroed (one memset less on the first count)
-    const size_t hist_full = (size_t)p->npos * (size_t)p->rows * sizeof(double);
-    const bool hist_here = hist_full > 0 && hist_full <= 64 * 1024;
-    const size_t at_hist = hist_here ? place(hist_full) : 0;
-    // (a large annotation's tables -- tens of MB -- go up table by table from where they are: a
-    // page-locked buffer of that size costs more to create than it saves)
-    const bool through_pinned = bytes <= ((size_t)4 << 20);
-    int rc = p->d_tables.reserve(bytes);
-    if (rc == PC_OK && through_pinned && e->pinned_busy && hipEventSynchronize(e->ev_pinned) != hipSuccess) rc = fail(PC_ERR_HIP, "pc_plan_create: wait failed");
-    if (rc == PC_OK && through_pinned) rc = e->pinned.reserve(bytes);
-    if (rc == PC_OK) {
-        uint8_t *h = through_pinned ? e->pinned.p : nullptr, *d = p->d_tables.p;
-        bool copy_failed = false;
-        auto put = [&](size_t at, const void *src, size_t n) {
-            if (!n) return;
-            if (through_pinned) memcpy(h + at, src, n);
-            else if (hipMemcpyAsync(d + at, src, n, hipMemcpyHostToDevice, e->stream) != hipSuccess) copy_failed = true;
-        };
-        put(at_tiles, p->tiles.data(), p->tiles.size() * sizeof(Tile));
-        put(at_pieces, p->pieces.data(), p->pieces.size() * sizeof(Piece));
-        put(at_opieces, p->opieces.data(), p->opieces.size() * sizeof(OutPiece));
-        put(at_cchunks, p->cchunks.data(), p->cchunks.size() * sizeof(CenterChunk));
-        if (!p->lazy_center) put(at_gsegs, p->gsegs.data(), p->gsegs.size() * sizeof(GatherSeg));
-        put(at_gchunks, p->gchunks.data(), p->gchunks.size() * sizeof(GatherChunk));
-        if (through_pinned) memset(h + at_items, 0, bytes - at_items);
-        else if (hipMemsetAsync(d + at_items, 0, bytes - at_items, e->stream) != hipSuccess) copy_failed = true;
-        p->d_tiles.p = (Tile *)(d + at_tiles); p->d_pieces.p = (Piece *)(d + at_pieces);
-        p->d_opieces.p = (OutPiece *)(d + at_opieces); p->d_cchunks.p = (CenterChunk *)(d + at_cchunks);
-        p->d_gsegs.p = (GatherSeg *)(d + at_gsegs); p->d_gchunks.p = (GatherChunk *)(d + at_gchunks);
-        p->d_tile_items.p = (uint32_t *)(d + at_items); p->d_total.p = d + at_total;
-        p->d_wcounters.p = (uint32_t *)(d + at_wcounters);
-        p->tile_items_zero = true;
-        p->wcounters_zero = true;
-        if (hist_here) { p->d_hist.p = d + at_hist; p->hist_clean = true; }
-        if (!through_pinned) {   // the copies read the plan's own vectors, which live as long as the plan
-            if (copy_failed) rc = fail(PC_ERR_HIP, "pc_plan_create: upload failed");
-        } else if (hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, e->stream) != hipSuccess) rc = fail(PC_ERR_HIP, "pc_plan_create: upload failed");
-        else if (hipEventRecord(e->ev_pinned, e->stream) != hipSuccess) rc = fail(PC_ERR_HIP, "pc_plan_create: event failed");
-        else e->pinned_busy = true;
-    }
-    pclk.lap("plan: upload");
-    p->n_tiles = p->tiles.size(); p->n_pieces = p->pieces.size(); p->n_opieces = p->opieces.size();
-    p->n_cchunks = p->cchunks.size(); p->n_gchunks = p->gchunks.size();
     if (rc != PC_OK) {
         (void)hipStreamSynchronize(e->stream);   // copies out of the plan's vectors may be in flight
         delete p;
@@ -2824,7 +2383,7 @@ int pc_plan_table(pc_plan *p, int which, void *buf, int64_t cap_bytes, int64_t *
     else if (which == 1) { src = p->d_pieces.p; n = p->n_pieces * sizeof(Piece); }
     else if (which == 2) { src = p->d_opieces.p; n = p->n_opieces * sizeof(OutPiece); }
     else if (p->gpu_built) { src = p->d_gsegs_own.p; n = (size_t)p->nseg * sizeof(GatherSeg); }
-    else { src = p->gsegs.data(); n = p->gsegs.size() * sizeof(GatherSeg); on_host = true; }
+    else { src = p->host.gsegs.data(); n = p->host.gsegs.size() * sizeof(GatherSeg); on_host = true; }
     *bytes = (int64_t)n;
     const size_t take = (size_t)std::min<int64_t>(cap_bytes, (int64_t)n);
     if (take) {

@@ -1,5 +1,5 @@
-"""Experiment: pc_plan_create of the human-scale annotation (60 k transcripts, 479 k exons) with the host builder and
-with the GPU builder (csrc/plan_kernels.hip.h), for the single-row plan of C4 and the 11-row plan of C5.
+"""Experiment: pc_plan_create of the human-scale annotation (60 k transcripts, 479 k exons) with the host builder (csrc/plan_host.h:
+the serial reference builder) and with the GPU builder (csrc/plan_kernels.hip.h), for the single-row plan of C4 and the 11-row plan of C5.
 PC_STAGE_TIMING=1 prints the laps of either."""
 import os
 import sys
@@ -26,6 +26,7 @@ for rows in (1, 11):
             times.append((time.perf_counter() - t0) * 1e3)
             tiles = plan.tiles
             plan.close()
-        print("rows %2d  %-4s builder: %d segments, %d tiles; plan builds (ms, sync included): %s" % (
-            rows, where, len(p["tid"]), tiles, " ".join("%.2f" % t for t in times)), flush=True)
+        label = "host (serial)" if where == "host" else where
+        print("rows %2d  %-13s builder: %d segments, %d tiles; plan builds (ms, sync included): %s" % (
+            rows, label, len(p["tid"]), tiles, " ".join("%.2f" % t for t in times)), flush=True)
         eng.close()

@@ -88,6 +88,31 @@ def test_human_scale_annotation(monkeypatch, rows, tile_g):
     close(ph, pg, eh, eg)
 
 
+def test_host_builder_above_65536_segments(monkeypatch):
+    """66 000 segments of 30 nt on three contigs: above 65 536 segments the host builder once changed to a threaded
+    build with center tables made on first use.  It is one serial builder at every size: same tables as the GPU
+    builder, and the center rule and the coordinate export -- the readers of the chunk and gather lists -- agree."""
+    rng = np.random.default_rng(11)
+    genome = (["chrA", "chrB", "chrC"], [1000000] * 3)
+    reads = synth.make_reads(genome, None, 20000, seed=3)
+    n = 66000
+    tid = rng.integers(0, 3, n).astype(np.int32)
+    start = rng.integers(0, 1000000 - 30, n).astype(np.int64)
+    end = start + 30
+    strand = rng.choice(np.array([1, 2, 3], np.uint8), n)
+    step = np.ones(n, np.int8)
+    out_off = np.arange(n, dtype=np.int64) * 30
+    row_stride = np.full(n, 30, np.int64)
+    args = (tid, start, end, strand, out_off, step, row_stride, n * 30)
+    eh, ph, eg, pg = both(monkeypatch, reads, args, 1)
+    for eng in (eh, eg):
+        synth.mapping_factory(("center", 0))._configure(eng)
+    a, b = ph.count(np.float64).copy(), pg.count(np.float64).copy()
+    assert a.sum() > 0 and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+    assert np.array_equal(ph.coordinates(), pg.coordinates())
+    close(ph, pg, eh, eg)
+
+
 def test_adversarial_layouts(monkeypatch):
     """Touching, nested, duplicated and overlapping segments on both strands; unknown contigs; empty and clipped
     segments; summed slices; reversed output; segments that span many windows -- and defects, reported as by the host."""

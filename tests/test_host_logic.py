@@ -441,6 +441,27 @@ def test_host_helpers_of_the_engine(tmp_path):
     assert b"host_util: ok" in out.stdout
 
 
+def test_host_plan_builder(tmp_path):
+    """plastid_amd/csrc/plan_host.h is plain C++: the serial host builder of a plan's tables -- the reference the GPU
+    builder is compared with -- against tables written out by hand (two strands and a summed slice over three windows,
+    an unknown contig, a clipped segment; one tile per mode with two rows; a segment that ends on a window border; an
+    empty one; one defect of each kind with a later one that must not win; the row limit of the LDS window) and against
+    a model that expands every queried position of 150 random small plans (islands, pieces, tiles, output pieces, center
+    chunks, gather list, scalars) -- compiled with the host compiler and run here."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "plan_host_test")
+    subprocess.check_call([cxx, "-O2", "-std=c++17", "-I", os.path.join(root, "plastid_amd", "csrc"), "-I", os.path.join(root, "include"),
+                           os.path.join(root, "tests", "plan_host_test.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, timeout=300)
+    assert out.returncode == 0, out.stdout.decode()
+    assert b"plan_host: ok" in out.stdout
+
+
 def test_inflate_and_plan_kernels_are_in_the_code_object(tmp_path):
     """Round 4's device code beside the counting kernels: the BGZF inflate kernel in both forms (batch decoder of the
     block symbols, wave-uniform decoder), without scratch memory and with an LDS footprint that leaves eleven waves per
