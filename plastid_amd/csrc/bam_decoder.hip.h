@@ -1,6 +1,8 @@
 // Compressed BAM on the GPU, host side: the entry points of include/plastid_counts.h that decode a BAM file with the
-// kernels of bam_kernels.hip.h.  One open is five phases (bam_open_impl): plan_members, upload_and_inflate, read_header,
-// chain_records, decode_columns.  The index build (bam_index_impl: BAI or CSI) runs the first four and index_records in place of the fifth.  Part of the one translation unit of plastid_counts.hip.
+// kernels of bam_kernels.hip.h.  One open is five phases (bam_open_impl): plan_members (bam_host.h), upload_and_inflate,
+// read_header, chain_records, decode_columns.  The index build (bam_index_impl: BAI or CSI) runs the first four and
+// index_records in place of the fifth.  Every phase is a list of steps: HIP calls, and the host arithmetic of bam_host.h
+// (plain C++, tested on the CPU by tests/bam_host_test.cpp).  Part of the one translation unit of plastid_counts.hip.
 #include "bam_kernels.hip.h"
 #include "sort_kernels.hip.h"
 #include "index_kernels.hip.h"
@@ -34,8 +36,10 @@ struct pc_bam {
 
 namespace {
 
-uint16_t brd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-uint32_t brd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+namespace bh = pcbamhost;
+using bh::BamHeader;
+using bh::BamPlan;
+using bh::BamSpan;
 
 // CRC-32 tables (RFC 1952): the byte table, and the operator that advances the register over kCrcSlice zero bytes
 // split by register byte (k_bgzf_crc combines 64 slice remainders with it)
@@ -61,6 +65,12 @@ const CrcTables &crc_tables() { static const CrcTables t; return t; }
 double ms_between(hipEvent_t a, hipEvent_t b) { float t = 0.f; return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
 // one more buffer of a phase, unless an earlier one has failed
 template <typename Buf> void room(int &rc, Buf &buf, size_t n) { if (rc == PC_OK) rc = buf.reserve(n); }
+// A step's temporaries are read by what it queued: an early return drains the stream before they go out of scope
+// (disarmed behind the step's own synchronisation).  Declared BEHIND the host and device temporaries it covers.
+struct DrainOnExit {
+    hipStream_t st; bool armed = true;
+    ~DrainOnExit() { if (armed) (void)hipStreamSynchronize(st); }
+};
 
 // The decoder's experiment and test switches, read at the top of every open (the tests flip them between opens on one engine).
 struct BamKnobs {
@@ -96,224 +106,16 @@ struct BamClock {   // PC_BAM_TIMING=1: wall-clock laps of the host side of the 
 // that stream has drained the host copy of the file is not read again (pc_bam_open_path takes its mapping down while the
 // GPU is still inflating).
 typedef std::function<void(hipStream_t)> UploadedHook;
-// A region read (pc_bam_open_chunks; pc_bam_open_span is the same with one chunk): only the members the chunks
-// [cbeg[k], cend[k]) of the BAI index touch go to HBM (plus the leading members that hold the header); chunks that share or
-// touch a member form one run (one contiguous upload, one record chain from the run's first chunk start to its last chunk
-// end), and only the records that overlap one of the regions stay.
-struct BamSpan {
-    int nchunk = 0;                          // 0: header only
-    const uint64_t *cbeg = nullptr, *cend = nullptr;   // (file offset of a member << 16 | offset in its payload), ascending, disjoint
-    int nreg = 0;                            // merged regions, ascending by (reference id, start)
-    const int32_t *tid = nullptr;
-    const int64_t *beg = nullptr, *end = nullptr;
-    int64_t header_bytes = 0;                // compressed bytes from the start of the file searched for the header (BamKnobs, grown on retry)
-};
 constexpr int PC_RETRY_HEADER = -1000;   // (internal) the header did not fit the leading members that were inflated
 
-// ---- member boundaries (host: a walk over the gzip headers; 18 + bytes per 64 KiB of payload)
-// What goes to the GPU and where it lands: the non-empty members, the runs of the file they come from, and where the
-// chunks of a region read start and end.
-struct BamPlan {
-    // [file_lo, file_hi) lands at image offset dev_lo and holds members [m0, m1) (a whole-file read: one run)
-    struct Run { int64_t file_lo, file_hi, dev_lo; int m0, m1; };
-    // where a chunk starts and ends, by member (index in `members` of the member at the offset -- of the next non-empty
-    // one for an empty member, members.size() past the last) and offset in its payload
-    struct ChunkAt { int64_t cb; int s_idx, e_idx; uint32_t ub, ue; };
-    std::vector<pcbam::Member> members;
-    std::vector<Run> runs;
-    std::vector<uint32_t> member_run;   // the run each member belongs to
-    std::vector<ChunkAt> chunk_at;
-    uint64_t total_u = 0;               // bytes of the inflated stream
-    int64_t image_bytes = 0;            // bytes of the file that go to the device
-    int nm() const { return (int)members.size(); }
-    // stream offset at which member index m starts (total_u past the last)
-    uint64_t uoff_of(int m) const { return m < nm() ? members[(size_t)m].uoff : total_u; }
-};
-
-// one member at `off`: 0, or which defect (walk_error's messages)
-int parse_member(const uint8_t *image, int64_t size, int64_t off, pcbam::Member &mb, int64_t &clen_out) {
-    if (off + 18 > size) return 1;
-    const uint8_t *h = image + off;
-    if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return 2;
-    const uint16_t xlen = brd16(h + 10);
-    if (off + 12 + xlen > size) return 3;
-    int bsize = -1;
-    for (size_t x = 0; x + 4 <= xlen;) {
-        const uint8_t *sf = h + 12 + x;
-        const uint16_t slen = brd16(sf + 2);
-        if (sf[0] == 'B' && sf[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = brd16(sf + 4);
-        x += 4 + slen;
-    }
-    if (bsize < 0) return 4;
-    const int64_t clen = (int64_t)bsize + 1;
-    if (off + clen > size) return 5;
-    const uint32_t isize = brd32(image + off + clen - 4);
-    if (isize > (1u << 16)) return 6;
-    const int64_t hdr = 12 + xlen;
-    if (clen < hdr + 8) return 7;
-    mb.coff = (uint64_t)(off + hdr); mb.clen = (uint32_t)(clen - hdr - 8); mb.ulen = isize; mb.uoff = 0;
-    mb.crc = brd32(image + off + clen - 8); mb.hdr = (uint32_t)hdr;
-    clen_out = clen;
-    return 0;
-}
-int walk_error(int code, const char *path) {
-    switch (code) {
-    case 1: return fail(PC_ERR_ARG, "truncated BGZF header");
-    case 2: return fail(PC_ERR_ARG, "not a BGZF file (bad gzip member header)");
-    case 3: return fail(PC_ERR_ARG, "truncated BGZF extra field");
-    case 4: return fail(PC_ERR_ARG, "BGZF member without BC subfield");
-    case 5: return fail(PC_ERR_ARG, "truncated BGZF member");
-    case 6: return fail(PC_ERR_ARG, "corrupt BGZF member (more than 64 KiB of payload)");
-    default: return fail(PC_ERR_ARG, "BGZF inflate failed in %s", path);
-    }
-}
-int belongs_not(const char *why, const char *path) { return fail(PC_ERR_ARG, "the index does not belong to this BAM file (%s): %s", why, path); }
-
-// A region read's members: the header's from the start of the file, then every chunk's.
-int plan_region(const uint8_t *image, int64_t size, const BamSpan &span, const char *path, BamPlan &pl) {
-    std::vector<pcbam::Member> &members = pl.members;
-    std::vector<BamPlan::Run> &runs = pl.runs;
-    // every member walked: its file offset, its index in `members` (see ChunkAt) and its payload length
-    struct Walked { int64_t off; int idx; uint32_t ulen; };
-    std::vector<Walked> walked;
-    // members from `off` on while they start before `hi_excl` (or at `last`, with_last); a new run unless `off` continues the last
-    auto walk = [&](int64_t off, int64_t hi_excl, bool with_last, int64_t last) -> int {
-        if (runs.empty() || runs.back().file_hi != off) runs.push_back(BamPlan::Run{off, off, 0, (int)members.size(), (int)members.size()});
-        const int64_t first = off;
-        while (off < size && (off < hi_excl || (with_last && off <= last))) {
-            pcbam::Member mb;
-            int64_t clen = 0;
-            const int code = parse_member(image, size, off, mb, clen);
-            if (code) return off == first && first > 0 ? belongs_not("a chunk does not start at a BGZF member", path) : walk_error(code, path);
-            walked.push_back(Walked{off, (int)members.size(), mb.ulen});
-            if (mb.ulen) members.push_back(mb);
-            off += clen;
-        }
-        runs.back().file_hi = off; runs.back().m1 = (int)members.size();
-        if (runs.back().file_hi == runs.back().file_lo) runs.pop_back();
-        return PC_OK;
-    };
-    auto find = [&](int64_t off) -> const Walked * {
-        auto it = std::lower_bound(walked.begin(), walked.end(), off, [](const Walked &w, int64_t o) { return w.off < o; });
-        return it != walked.end() && it->off == off ? &*it : nullptr;
-    };
-    const int64_t cb0 = span.nchunk > 0 ? (int64_t)(span.cbeg[0] >> 16) : size;
-    int rc = walk(0, std::min<int64_t>(span.header_bytes, cb0), false, 0);
-    if (rc != PC_OK) return rc;
-    for (int k = 0; k < span.nchunk; ++k) {
-        const uint64_t vb = span.cbeg[k], ve = span.cend[k];
-        const int64_t cb = (int64_t)(vb >> 16), ce = (int64_t)(ve >> 16);
-        const uint32_t ub = (uint32_t)(vb & 0xffffu), ue = (uint32_t)(ve & 0xffffu);
-        if (cb >= size || ce > size || (ue && ce >= size)) return belongs_not("a chunk lies beyond its end", path);
-        const int64_t hi = runs.empty() ? 0 : runs.back().file_hi;
-        if (cb < hi && !find(cb)) return belongs_not("a chunk does not start at a BGZF member", path);
-        rc = walk(std::max(cb, hi), ce, ue != 0, ce);
-        if (rc != PC_OK) return rc;
-        BamPlan::ChunkAt c{cb, 0, 0, ub, ue};
-        const Walked *ws = find(cb);
-        if (!ws || ub > ws->ulen) return belongs_not("a chunk does not start at a BGZF member", path);
-        c.s_idx = ws->idx;
-        if (ue) {
-            const Walked *we = find(ce);
-            if (!we || ue > we->ulen) return belongs_not("a chunk does not end at a BGZF member", path);
-            c.e_idx = we->idx;
-        } else {
-            if (runs.empty() || runs.back().file_hi != ce) return belongs_not("a chunk does not end at a BGZF member", path);
-            c.e_idx = (int)members.size();
-        }
-        pl.chunk_at.push_back(c);
-    }
-    // adjacent runs become one (a run is uploaded as one contiguous copy)
-    for (size_t k = 1; k < runs.size();)
-        if (runs[k].file_lo == runs[k - 1].file_hi) { runs[k - 1].file_hi = runs[k].file_hi; runs[k - 1].m1 = runs[k].m1; runs.erase(runs.begin() + (long)k); }
-        else ++k;
-    int64_t dev = 0;
-    for (BamPlan::Run &r : runs) {   // the members' streams by their place in the image on the device
-        r.dev_lo = dev;
-        for (int m = r.m0; m < r.m1; ++m) members[(size_t)m].coff = (uint64_t)((int64_t)members[(size_t)m].coff - r.file_lo + r.dev_lo);
-        dev += r.file_hi - r.file_lo;
-    }
-    return PC_OK;
+// a defect of bam_host.h (a member header's, or a chunk list that is not this file's) as this library's error
+int host_defect(int code, const char *path) {
+    if (bh::chunk_defect(code)) return fail(PC_ERR_ARG, "the index does not belong to this BAM file (%s): %s", bh::defect_text(code), path);
+    return fail(PC_ERR_ARG, "%s%s", bh::defect_text(code), code == bh::kMemberTiny ? path : "");
 }
 
-// Every member of the file, as one run.
-int plan_whole_file(const uint8_t *image, int64_t size, const char *path, int64_t walk_min, BamPlan &pl) {
-    std::vector<pcbam::Member> &members = pl.members;
-    int64_t walked_to = 0;
-    // Large files: the walk is a chain of dependent cache misses (40 k members: 5.6 ms), so every host thread walks its
-    // own stretch of the file from the first offset in it where three members in a row parse; a stretch counts only if
-    // the walk of the stretch before it LANDS on its first member -- whatever does not chain is walked again, serially.
-    const int WT = size >= walk_min && size >= 64 ? std::max(1, std::min(usable_cpus(), 16)) : 1;
-    if (WT > 1) {
-        struct Stretch { int64_t first = -1, landing = -1; std::vector<pcbam::Member> mem; };
-        std::vector<Stretch> str((size_t)WT);
-        parallel_chunks((int64_t)WT, WT, [&](int, int64_t kb, int64_t ke) {
-            for (int64_t k = kb; k < ke; ++k) {
-                Stretch &sx = str[(size_t)k];
-                const int64_t lo = size * k / WT, hi = size * (k + 1) / WT;
-                int64_t off = lo;
-                if (k > 0) {   // the first offset from which three members parse
-                    off = -1;
-                    for (int64_t c = lo; c < hi && c + 18 <= size; ++c) {
-                        if (image[c] != 31 || image[c + 1] != 139) continue;
-                        int64_t q = c;
-                        bool ok = true;
-                        for (int r = 0; r < 3 && ok && q < size; ++r) {
-                            pcbam::Member mb;
-                            int64_t cl = 0;
-                            ok = parse_member(image, size, q, mb, cl) == 0;
-                            q += cl;
-                        }
-                        if (ok) { off = c; break; }
-                    }
-                    if (off < 0) continue;
-                }
-                sx.first = off;
-                while (off < hi && off < size) {
-                    pcbam::Member mb;
-                    int64_t cl = 0;
-                    if (parse_member(image, size, off, mb, cl) != 0) { sx.first = -1; break; }   // (a defect: the serial walk below reports it)
-                    if (mb.ulen) sx.mem.push_back(mb);
-                    off += cl;
-                }
-                sx.landing = off;
-            }
-        });
-        int64_t expected = 0;
-        for (int k = 0; k < WT; ++k) {
-            const Stretch &sx = str[(size_t)k];
-            if (sx.first < 0 || sx.first != expected) break;
-            members.insert(members.end(), sx.mem.begin(), sx.mem.end());
-            expected = sx.landing;
-        }
-        walked_to = expected;
-    }
-    for (int64_t off = walked_to; off < size;) {
-        pcbam::Member mb;
-        int64_t clen = 0;
-        const int code = parse_member(image, size, off, mb, clen);
-        if (code) return walk_error(code, path);
-        if (mb.ulen) members.push_back(mb);      // (empty members -- the end-of-file marker -- hold nothing)
-        off += clen;
-    }
-    pl.runs.push_back(BamPlan::Run{0, size, 0, 0, (int)members.size()});
-    return PC_OK;
-}
-
-// Phase 1 (host only): which members go to the GPU (`span`: those of a region read; nullptr: the whole file), in which
-// runs, and where they land in the image on the device and in the inflated stream.
-int plan_members(const uint8_t *image, int64_t size, const BamSpan *span, const char *path, int64_t walk_min, BamPlan &pl) {
-    const int rc = span ? plan_region(image, size, *span, path, pl) : plan_whole_file(image, size, path, walk_min, pl);
-    if (rc != PC_OK) return rc;
-    for (pcbam::Member &mb : pl.members) { mb.uoff = pl.total_u; pl.total_u += mb.ulen; }
-    for (const BamPlan::Run &r : pl.runs) pl.image_bytes += r.file_hi - r.file_lo;
-    pl.member_run.assign((size_t)std::max(pl.nm(), 1), 0u);
-    for (size_t r = 0; r < pl.runs.size(); ++r)
-        for (int m = pl.runs[r].m0; m < pl.runs[r].m1; ++m) pl.member_run[(size_t)m] = (uint32_t)r;
-    return PC_OK;
-}
-
-// What the phases of one open share (phases 2 - 5 queue on `st`; each leaves it drained of everything that reads a buffer it owns).
+// What the phases of one open share (phase 1, bh::plan_members, is host only; phases 2 - 5 queue on `st`, and each leaves
+// it drained of everything that reads a buffer it owns).
 struct BamDecode {
     pc_engine *e;
     hipStream_t st;
@@ -327,176 +129,188 @@ struct BamDecode {
     DevBuf<uint32_t> d_rec_off;
 };
 
+// ---- phase 2: upload + inflate, piece by piece (bh::cut_pieces): the file image crosses PCIe on the side stream in
+// pieces of whole members while the members of the pieces before are inflated on the main one (one wave per member).
+// (Every launch ends in a tail of half-empty CUs -- a member takes ~4 ms and ~3 000 are in flight -- so the pieces are
+// large: 20 M aligner-like records, 578 MB: one piece 87 ms, 48 MiB pieces 67 ms, 128 MiB 58 ms, 256 MiB 61 ms.)
+// What its steps share:
+struct Upload {
+    DevBuf<uint8_t> d_image;
+    DevBuf<uint32_t> d_status, d_crc;
+    // (pieces of the image gathered from several runs, for an upload straight from pageable memory: they outlive the drain)
+    std::vector<std::vector<uint8_t>> gathered;
+    hipStream_t up = nullptr;          // the stream the image is uploaded on: the side stream, or the main one
+    int naux = 0;                      // auxiliary streams the inflate launches take turns on, beside the main one
+    bool ring = false, ring_busy[2] = {false, false};
+    int ring_threads = 1;
+    std::vector<hipEvent_t> landed;    // [0]: what the main stream had queued when the side stream started; then one per piece
+    ~Upload() { for (auto x : landed) (void)hipEventDestroy(x); }
+    int mark(hipStream_t on) {         // one more event, recorded on `on`
+        hipEvent_t x;
+        HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
+        landed.push_back(x);
+        HIP_TRY(hipEventRecord(x, on));
+        return PC_OK;
+    }
+};
+// An early return between the first queued copy and the synchronisation behind the inflate launches must not hand the
+// image, the stream buffer or the page-locked ring back (nor let the caller unmap the file) while the side / auxiliary
+// streams still use them: drain every stream the decoder queues on before the buffers of Upload go out of scope.
+struct Drain {
+    pc_engine *e; bool armed;
+    ~Drain() {
+        if (!armed) return;
+        if (e->side_stream) (void)hipStreamSynchronize(e->side_stream);
+        for (int k = 0; k < pc_engine::kAux; ++k) if (e->aux_stream[k]) (void)hipStreamSynchronize(e->aux_stream[k]);
+        (void)hipStreamSynchronize(e->stream);
+    }
+};
+
+// Step 1: the buffers, and the tables of the kernels (members, CRC) on their way.
+int reserve_and_queue_tables(BamDecode &d, const BamPlan &pl, Upload &u) {
+    hipStream_t st = d.st;
+    const int nm = pl.nm();
+    int rc = PC_OK;
+    room(rc, u.d_image, (size_t)std::max<int64_t>(pl.image_bytes, 16) + 16); room(rc, d.d_stream, (size_t)pl.total_u + 64);
+    room(rc, d.d_members, (size_t)std::max(nm, 1)); room(rc, u.d_status, (size_t)std::max(nm, 1)); room(rc, u.d_crc, 5 * 256);
+    if (rc != PC_OK) return rc;
+    d.clk.lap("allocations (image, stream)");
+    HIP_TRY(hipEventRecord(d.ev[0], st));
+    if (nm) HIP_TRY(hipMemcpyAsync(d.d_members.p, pl.members.data(), (size_t)nm * sizeof(pcbam::Member), hipMemcpyHostToDevice, st));
+    const CrcTables &ct = crc_tables();
+    HIP_TRY(hipMemcpyAsync(u.d_crc.p, ct.tab, sizeof(ct.tab), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(u.d_crc.p + 256, ct.shift, sizeof(ct.shift), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(d.d_stream.p + pl.total_u, 0, 64, st));
+    HIP_TRY(hipEventRecord(d.ev[1], st));
+    return PC_OK;
+}
+
+// Step 2: the streams of the upload and of the inflate launches behind the main one, and the page-locked ring.
+int start_streams(BamDecode &d, const BamPlan &pl, Upload &u) {
+    pc_engine *e = d.e;
+    hipStream_t st = d.st;
+    u.up = e->side_stream ? e->side_stream : st;
+    if (u.up != st) {   // the side stream starts behind what the main one has queued so far (the buffers' previous users)
+        PC_TRY(u.mark(st));
+        HIP_TRY(hipStreamWaitEvent(u.up, u.landed[0], 0));
+    }
+    // The inflate launches alternate between the main stream and an auxiliary one: a launch ends in a tail of
+    // half-empty CUs (a member takes ~4 ms, ~3 000 are in flight), which the launch of the next piece fills.
+    // (two streams in turn: measured on two boxes, 64 MiB pieces, 20 M aligner-like records: one stream 56 - 58 ms, two
+    // 46.6 - 53.5, four 48.6; PC_BAM_STREAMS = 1 .. 4 for experiments)
+    u.naux = u.up != st ? std::max(0, std::min(pc_engine::kAux, d.knobs.streams - 1)) : 0;
+    for (int k = 0; k < u.naux; ++k)   // (behind what the main stream has queued: the members table, the previous users of the buffers)
+        HIP_TRY(hipStreamWaitEvent(e->aux_stream[k], u.landed[0], 0));
+    // large files cross PCIe through two page-locked halves of one piece each (made once per engine)
+    const int64_t piece_bytes = d.knobs.piece_bytes;
+    u.ring = u.up != st && pl.image_bytes >= 2 * piece_bytes && !d.knobs.no_ring;
+    u.ring_threads = std::max(1, std::min(usable_cpus(), 16));
+    if (u.ring) {
+        // (a piece ends with a whole member: up to 64 KiB beyond piece_bytes)
+        for (int k = 0; k < 2 && u.ring; ++k) {
+            if (e->bam_ring[k].reserve((size_t)piece_bytes + ((size_t)1 << 17)) != PC_OK) u.ring = false;
+            if (u.ring && !e->ev_ring[k] && hipEventCreateWithFlags(&e->ev_ring[k], hipEventDisableTiming) != hipSuccess) u.ring = false;
+        }
+        (void)hipGetLastError();
+    }
+    return PC_OK;
+}
+
+// Step 3: one piece of the image on its way to the device, by one of three ways.
+int upload_piece(BamDecode &d, const uint8_t *image, const BamPlan &pl, const bh::ImagePiece &pc, int piece_no, Upload &u) {
+    pc_engine *e = d.e;
+    const uint8_t *src = bh::piece_source(image, pl, pc);   // (one_run only)
+    uint8_t *dst = u.d_image.p + pc.byte0;
+    const int64_t len = pc.byte1 - pc.byte0;
+    if (u.ring) {
+        // through a page-locked half: the runtime's own staging of a pageable copy runs on one thread (12 - 20 GB/s);
+        // here every host thread copies its share, and the DMA of one half overlaps the filling of the other
+        const int slot = piece_no & 1;
+        if (u.ring_busy[slot]) HIP_TRY(hipEventSynchronize(e->ev_ring[slot]));
+        uint8_t *half = e->bam_ring[slot].p;
+        const int64_t blk = (int64_t)1 << 20;
+        parallel_chunks((len + blk - 1) / blk, u.ring_threads, [&](int, int64_t b, int64_t en) {
+            const int64_t lo = b * blk, hi = std::min(len, en * blk);
+            if (hi > lo && pc.one_run) std::memcpy(half + lo, src + lo, (size_t)(hi - lo));
+            else if (hi > lo) bh::copy_image(image, pl.runs, half + lo, pc.byte0 + lo, pc.byte0 + hi);
+        });
+        HIP_TRY(hipMemcpyAsync(dst, half, (size_t)len, hipMemcpyHostToDevice, u.up));
+        HIP_TRY(hipEventRecord(e->ev_ring[slot], u.up));
+        u.ring_busy[slot] = true;
+    } else if (pc.one_run)
+        HIP_TRY(hipMemcpyAsync(dst, src, (size_t)len, hipMemcpyHostToDevice, u.up));
+    else {   // several runs in one piece: gathered, one copy
+        u.gathered.emplace_back((size_t)len);
+        bh::copy_image(image, pl.runs, u.gathered.back().data(), pc.byte0, pc.byte1);
+        HIP_TRY(hipMemcpyAsync(dst, u.gathered.back().data(), (size_t)len, hipMemcpyHostToDevice, u.up));
+    }
+    return PC_OK;
+}
+
+// Step 4: the piece's members inflated and their CRCs checked, behind its upload, on the stream whose turn it is.
+int inflate_piece(BamDecode &d, const bh::ImagePiece &pc, int piece_no, Upload &u) {
+    using namespace pcbam;
+    hipStream_t st = d.st;
+    if (u.up != st) PC_TRY(u.mark(u.up));
+    hipStream_t ks = (piece_no % (u.naux + 1)) ? d.e->aux_stream[piece_no % (u.naux + 1) - 1] : st;
+    if (u.up != st) HIP_TRY(hipStreamWaitEvent(ks, u.landed.back(), 0));
+    const dim3 grid((unsigned)(pc.m1 - pc.m0));
+    if (d.knobs.serial_symbols) hipLaunchKernelGGL(k_bgzf_inflate<false>, grid, dim3(kInflWG), 0, ks, u.d_image.p, d.d_members.p, pc.m0, pc.m1, d.d_stream.p, u.d_status.p);
+    else hipLaunchKernelGGL(k_bgzf_inflate<true>, grid, dim3(kInflWG), 0, ks, u.d_image.p, d.d_members.p, pc.m0, pc.m1, d.d_stream.p, u.d_status.p);
+    // (the piece's CRC check right behind it, on the same stream: it runs while other pieces are still inflated)
+    hipLaunchKernelGGL(k_bgzf_crc, grid, dim3(64), 0, ks, d.d_stream.p, d.d_members.p, pc.m0, pc.m1, u.d_crc.p, u.d_crc.p + 256, u.d_status.p);
+    return PC_OK;
+}
+
+// Step 5: every member's status, as the kernels left it.
+int check_status(BamDecode &d, const BamPlan &pl, const std::vector<uint32_t> &status) {
+    const int nm = pl.nm();
+    for (int m = 0; m < nm; ++m)
+        if (status[(size_t)m]) {
+            const pcbam::Member &mb = pl.members[(size_t)m];
+            if (d.knobs.debug) fprintf(stderr, "[bam] member %d of %d (%u compressed -> %u bytes at %llu): inflate status %u\n", m, nm,
+                                       mb.clen, mb.ulen, (unsigned long long)mb.uoff, status[(size_t)m]);
+            return fail(PC_ERR_ARG, "%s%s", status[(size_t)m] == (uint32_t)pcbam::kInfCrc ? bh::kCrcMismatchIn : bh::kInflateFailedIn, d.path.c_str());
+        }
+    return PC_OK;
+}
+
 // Phase 2: the image goes to HBM and is inflated there, piece by piece; returns with every stream drained, every member's
 // status and CRC checked, and the image given back.
 int upload_and_inflate(BamDecode &d, const uint8_t *image, const BamPlan &pl, const UploadedHook *uploaded) {
-    using namespace pcbam;
     pc_engine *e = d.e;
     hipStream_t st = d.st;
-    const std::vector<Member> &members = pl.members;
-    const std::vector<BamPlan::Run> &runs = pl.runs;
     const int nm = pl.nm();
-    DevBuf<uint8_t> d_image;
-    DevBuf<uint32_t> d_status, d_crc;
-    // (pieces of the image gathered from several runs, for an upload straight from pageable memory: they outlive `drain`)
-    std::vector<std::vector<uint8_t>> gathered;
-    int rc = PC_OK;
-    room(rc, d_image, (size_t)std::max<int64_t>(pl.image_bytes, 16) + 16); room(rc, d.d_stream, (size_t)pl.total_u + 64);
-    room(rc, d.d_members, (size_t)std::max(nm, 1)); room(rc, d_status, (size_t)std::max(nm, 1)); room(rc, d_crc, 5 * 256);
-    if (rc != PC_OK) return rc;
-    // An early return between here and the synchronisation behind the inflate launches must not hand the image, the
-    // stream buffer or the page-locked ring back (nor let the caller unmap the file) while the side / auxiliary streams
-    // still use them: drain every stream the decoder queues on before the buffers above go out of scope.
-    struct Drain {
-        pc_engine *e; bool armed;
-        ~Drain() {
-            if (!armed) return;
-            if (e->side_stream) (void)hipStreamSynchronize(e->side_stream);
-            for (int k = 0; k < pc_engine::kAux; ++k) if (e->aux_stream[k]) (void)hipStreamSynchronize(e->aux_stream[k]);
-            (void)hipStreamSynchronize(e->stream);
-        }
-    } drain{e, true};
-    d.clk.lap("allocations (image, stream)");
-    HIP_TRY(hipEventRecord(d.ev[0], st));
-    if (nm) HIP_TRY(hipMemcpyAsync(d.d_members.p, members.data(), (size_t)nm * sizeof(Member), hipMemcpyHostToDevice, st));
-    const CrcTables &ct = crc_tables();
-    HIP_TRY(hipMemcpyAsync(d_crc.p, ct.tab, sizeof(ct.tab), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_crc.p + 256, ct.shift, sizeof(ct.shift), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(d.d_stream.p + pl.total_u, 0, 64, st));
-    HIP_TRY(hipEventRecord(d.ev[1], st));
-    // ---- upload + inflate, piece by piece: the file image crosses PCIe on the side stream in pieces of ~128 MiB of
-    // whole members while the members of the pieces before are inflated on the main one (one wave per member).  (Every
-    // launch ends in a tail of half-empty CUs -- a member takes ~4 ms and ~3 000 are in flight -- so the pieces are
-    // large: 20 M aligner-like records, 578 MB: one piece 87 ms, 48 MiB pieces 67 ms, 128 MiB 58 ms, 256 MiB 61 ms.)
+    Upload u;
+    Drain drain{e, true};
+    PC_TRY(reserve_and_queue_tables(d, pl, u));
     std::vector<uint32_t> status((size_t)nm, 0u);
     if (nm) {
-        const int64_t piece_bytes = d.knobs.piece_bytes;
-        hipStream_t up = e->side_stream ? e->side_stream : st;
-        std::vector<hipEvent_t> landed;
-        struct EvList { std::vector<hipEvent_t> &v; ~EvList() { for (auto x : v) (void)hipEventDestroy(x); } } landed_guard{landed};
-        if (up != st) {   // the side stream starts behind what the main one has queued so far (the buffers' previous users)
-            hipEvent_t x;
-            HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-            landed.push_back(x);
-            HIP_TRY(hipEventRecord(x, st));
-            HIP_TRY(hipStreamWaitEvent(up, x, 0));
-        }
-        // The inflate launches alternate between the main stream and an auxiliary one: a launch ends in a tail of
-        // half-empty CUs (a member takes ~4 ms, ~3 000 are in flight), which the launch of the next piece fills.
-        // (two streams in turn: measured on two boxes, 64 MiB pieces, 20 M aligner-like records: one stream 56 - 58 ms, two
-        // 46.6 - 53.5, four 48.6; PC_BAM_STREAMS = 1 .. 4 for experiments)
-        const int naux = up != st ? std::max(0, std::min(pc_engine::kAux, d.knobs.streams - 1)) : 0;
-        for (int k = 0; k < naux; ++k)   // (behind what the main stream has queued: the members table, the previous users of the buffers)
-            HIP_TRY(hipStreamWaitEvent(e->aux_stream[k], landed[0], 0));
-        // large files cross PCIe through two page-locked halves of one piece each (made once per engine)
-        bool ring = up != st && pl.image_bytes >= 2 * piece_bytes && !d.knobs.no_ring;
-        bool ring_busy[2] = {false, false};
-        const int ring_threads = std::max(1, std::min(usable_cpus(), 16));
-        if (ring) {
-            // (a piece ends with a whole member: up to 64 KiB beyond piece_bytes)
-            for (int k = 0; k < 2 && ring; ++k) {
-                if (e->bam_ring[k].reserve((size_t)piece_bytes + ((size_t)1 << 17)) != PC_OK) ring = false;
-                if (ring && !e->ev_ring[k] && hipEventCreateWithFlags(&e->ev_ring[k], hipEventDisableTiming) != hipSuccess) ring = false;
-            }
-            (void)hipGetLastError();
-        }
-        // bytes [lo, hi) of the image on the device, from the file, to dst: run by run (the file's bytes of run r start at
-        // r.file_lo - r.dev_lo before its offsets in the image on the device)
-        auto copy_image = [&](uint8_t *dst, int64_t lo, int64_t hi) {
-            auto it = std::upper_bound(runs.begin(), runs.end(), lo, [](int64_t x, const BamPlan::Run &r) { return x < r.dev_lo; });
-            for (size_t r = (size_t)(it - runs.begin()) - 1; r < runs.size() && lo < hi; ++r) {
-                const int64_t rhi = std::min(hi, runs[r].dev_lo + (runs[r].file_hi - runs[r].file_lo));
-                if (rhi > lo) std::memcpy(dst, image + (runs[r].file_lo - runs[r].dev_lo) + lo, (size_t)(rhi - lo));
-                dst += std::max<int64_t>(rhi - lo, 0);
-                lo = std::max(lo, rhi);
-            }
-        };
-        const std::vector<uint32_t> &run_of = pl.member_run;   // (pieces end where a run ends; one piece may hold several short runs)
+        PC_TRY(start_streams(d, pl, u));
         int piece_no = 0;
-        int64_t byte0 = 0;                   // the image is uploaded from here on (gzip headers and trailers ride along)
-        for (int m0 = 0; m0 < nm; ++piece_no) {
-            int m1 = m0;
-            int64_t byte1 = byte0;
-            while (m1 < nm && (byte1 - byte0 < piece_bytes || m1 == m0)) {
-                byte1 = (int64_t)(members[(size_t)m1].coff + members[(size_t)m1].clen);
-                ++m1;
-            }
-            if (m1 == nm) byte1 = pl.image_bytes;
-            else if (run_of[(size_t)m1] != run_of[(size_t)m1 - 1]) byte1 = runs[run_of[(size_t)m1]].dev_lo;   // (the rest of the run before)
-            const uint32_t r0 = run_of[(size_t)m0];
-            const bool one_run = byte1 <= runs[r0].dev_lo + (runs[r0].file_hi - runs[r0].file_lo);
-            const uint8_t *run_src = image + (runs[r0].file_lo - runs[r0].dev_lo);   // (one_run: the piece's bytes in the file)
-            if (ring) {
-                // through a page-locked half: the runtime's own staging of a pageable copy runs on one thread (12 - 20 GB/s);
-                // here every host thread copies its share, and the DMA of one half overlaps the filling of the other
-                const int slot = piece_no & 1;
-                if (ring_busy[slot]) HIP_TRY(hipEventSynchronize(e->ev_ring[slot]));
-                uint8_t *dstp = e->bam_ring[slot].p;
-                const uint8_t *srcp = run_src + byte0;
-                const int64_t len = byte1 - byte0, blk = (int64_t)1 << 20;
-                parallel_chunks((len + blk - 1) / blk, ring_threads, [&](int, int64_t b, int64_t en) {
-                    const int64_t lo = b * blk, hi = std::min(len, en * blk);
-                    if (hi > lo && one_run) std::memcpy(dstp + lo, srcp + lo, (size_t)(hi - lo));
-                    else if (hi > lo) copy_image(dstp + lo, byte0 + lo, byte0 + hi);
-                });
-                HIP_TRY(hipMemcpyAsync(d_image.p + byte0, dstp, (size_t)len, hipMemcpyHostToDevice, up));
-                HIP_TRY(hipEventRecord(e->ev_ring[slot], up));
-                ring_busy[slot] = true;
-            } else if (one_run)
-                HIP_TRY(hipMemcpyAsync(d_image.p + byte0, run_src + byte0, (size_t)(byte1 - byte0), hipMemcpyHostToDevice, up));
-            else {   // several runs in one piece: gathered, one copy
-                gathered.emplace_back((size_t)(byte1 - byte0));
-                copy_image(gathered.back().data(), byte0, byte1);
-                HIP_TRY(hipMemcpyAsync(d_image.p + byte0, gathered.back().data(), (size_t)(byte1 - byte0), hipMemcpyHostToDevice, up));
-            }
-            if (up != st) {
-                hipEvent_t x;
-                HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-                landed.push_back(x);
-                HIP_TRY(hipEventRecord(x, up));
-            }
-            hipStream_t ks = (piece_no % (naux + 1)) ? e->aux_stream[piece_no % (naux + 1) - 1] : st;
-            if (up != st) HIP_TRY(hipStreamWaitEvent(ks, landed.back(), 0));
-            if (d.knobs.serial_symbols) hipLaunchKernelGGL(k_bgzf_inflate<false>, dim3((unsigned)(m1 - m0)), dim3(kInflWG), 0, ks, d_image.p, d.d_members.p, m0, m1, d.d_stream.p, d_status.p);
-            else hipLaunchKernelGGL(k_bgzf_inflate<true>, dim3((unsigned)(m1 - m0)), dim3(kInflWG), 0, ks, d_image.p, d.d_members.p, m0, m1, d.d_stream.p, d_status.p);
-            // (the piece's CRC check right behind it, on the same stream: it runs while other pieces are still inflated)
-            hipLaunchKernelGGL(k_bgzf_crc, dim3((unsigned)(m1 - m0)), dim3(64), 0, ks, d.d_stream.p, d.d_members.p, m0, m1, d_crc.p, d_crc.p + 256, d_status.p);
-            byte0 = byte1;
-            m0 = m1;
+        for (const bh::ImagePiece &pc : bh::cut_pieces(pl, d.knobs.piece_bytes)) {
+            PC_TRY(upload_piece(d, image, pl, pc, piece_no, u));
+            PC_TRY(inflate_piece(d, pc, piece_no, u));
+            ++piece_no;
         }
         d.clk.note("every piece copied into the page-locked ring and queued");
-        for (int k = 0; k < naux; ++k) {   // the main stream goes on behind all of them
-            hipEvent_t x;
-            HIP_TRY(hipEventCreateWithFlags(&x, hipEventDisableTiming));
-            landed.push_back(x);
-            HIP_TRY(hipEventRecord(x, e->aux_stream[k]));
-            HIP_TRY(hipStreamWaitEvent(st, x, 0));
+        for (int k = 0; k < u.naux; ++k) {   // the main stream goes on behind all of them
+            PC_TRY(u.mark(e->aux_stream[k]));
+            HIP_TRY(hipStreamWaitEvent(st, u.landed.back(), 0));
         }
-        if (uploaded) (*uploaded)(up);
+        if (uploaded) (*uploaded)(u.up);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(status.data(), d_status.p, (size_t)nm * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(status.data(), u.d_status.p, (size_t)nm * 4, hipMemcpyDeviceToHost, st));
     }
     HIP_TRY(hipEventRecord(d.ev[2], st));
     HIP_TRY(hipStreamSynchronize(st));
     drain.armed = false;   // (the main stream went on behind the side and auxiliary ones: all of them have drained)
     d.clk.lap("upload + inflate + crc (sync)");
-    for (int m = 0; m < nm; ++m)
-        if (status[(size_t)m]) {
-            if (d.knobs.debug) fprintf(stderr, "[bam] member %d of %d (%u compressed -> %u bytes at %llu): inflate status %u\n", m, nm,
-                                       members[(size_t)m].clen, members[(size_t)m].ulen, (unsigned long long)members[(size_t)m].uoff, status[(size_t)m]);
-            return fail(PC_ERR_ARG, "%s%s", status[(size_t)m] == (uint32_t)kInfCrc ? "BGZF CRC mismatch in " : "BGZF inflate failed in ", d.path.c_str());
-        }
-    d_image.release();
+    PC_TRY(check_status(d, pl, status));
+    u.d_image.release();
     d.clk.lap("status check + image release");
     return PC_OK;
 }
-
-struct BamHeader {
-    uint64_t first_record = 0;   // stream offset of the first record
-    uint32_t n_ref = 0;
-    std::vector<std::string> ref_names;
-    std::vector<int32_t> ref_lengths;
-};
 
 // Phase 3: the BAM header (host, from the head of the inflated stream).  A region read looks for it in the leading run
 // only -- what follows is some chunk, from a record in the middle of the file on; PC_RETRY_HEADER: it does not fit that
@@ -508,31 +322,11 @@ int read_header(BamDecode &d, const BamPlan &pl, int64_t size, const BamSpan *sp
     for (;;) {
         head.resize(want);
         if (want) HIP_TRY(hipMemcpy(head.data(), d.d_stream.p, want, hipMemcpyDeviceToHost));
-        const uint8_t *p = head.data(), *end = p + want;
-        bool more = false;
-        auto need = [&](size_t k) { if ((size_t)(end - p) < k) { more = true; return false; } return true; };
-        bool ok = true;
-        if (!need(12)) ok = false;
-        if (ok && std::memcmp(p, "BAM\1", 4) != 0) return fail(PC_ERR_ARG, "not a BAM file (bad magic)");
-        uint32_t l_text = 0;
-        if (ok) { l_text = brd32(p + 4); p += 8; if (!need((size_t)l_text + 4)) ok = false; }
-        if (ok) { p += l_text; h.n_ref = brd32(p); p += 4; }
-        h.ref_names.clear(); h.ref_lengths.clear();
-        for (uint32_t r = 0; ok && r < h.n_ref; ++r) {
-            if (!need(4)) { ok = false; break; }
-            const uint32_t l_name = brd32(p);
-            p += 4;
-            if (!need((size_t)l_name + 4)) { ok = false; break; }
-            h.ref_names.emplace_back((const char *)p, l_name ? l_name - 1 : 0);
-            p += l_name;
-            h.ref_lengths.push_back((int32_t)brd32(p));
-            p += 4;
-        }
-        if (ok) { h.first_record = (uint64_t)(p - head.data()); return PC_OK; }
-        if (more && want >= header_limit && span && header_limit < (size_t)pl.total_u + 1 && span->header_bytes < size) return PC_RETRY_HEADER;
-        if (!more || want >= header_limit)
-            return fail(PC_ERR_ARG, want < 12 ? "not a BAM file (bad magic)" : (h.ref_names.empty() && h.n_ref == 0 ? "truncated BAM header" : "truncated BAM reference list"));
-        want = std::min<size_t>(header_limit, want * 4);
+        const bh::HeaderParse hp = bh::parse_bam_header(head.data(), want, h);
+        if (hp.status == bh::kHeaderOk) return PC_OK;
+        if (hp.status == bh::kHeaderMore && want < header_limit) { want = std::min<size_t>(header_limit, want * 4); continue; }
+        if (hp.status == bh::kHeaderMore && span && header_limit < (size_t)pl.total_u + 1 && span->header_bytes < size) return PC_RETRY_HEADER;
+        return fail(PC_ERR_ARG, "%s", hp.text);
     }
 }
 
@@ -544,104 +338,65 @@ struct BamRecords {
 };
 
 // Phase 4: record starts.  Every member guesses its first record start and walks the chain of length prefixes; the host
-// confirms that the walks chain, and restarts the members whose guess did not.  A whole-file read chains from the header's
-// end to the end of the stream; a region read chains every run from its first chunk's start to its last chunk's end, which
-// the index gives and the chain has to hit exactly (a run without a chunk -- the header's -- has no record).
+// confirms that the walks chain (bh::settle_round), and restarts the members whose guess did not.  A whole-file read chains
+// from the header's end to the end of the stream; a region read chains every run from its first chunk's start to its last
+// chunk's end (bh::run_bounds), which the index gives and the chain has to hit exactly.
 int chain_records(BamDecode &d, const BamPlan &pl, const BamSpan *span, const BamHeader &h, BamRecords &out) {
     using namespace pcbam;
     hipStream_t st = d.st;
-    const std::vector<Member> &members = pl.members;
-    const std::vector<BamPlan::Run> &runs = pl.runs;
-    const std::vector<uint32_t> &member_run = pl.member_run;
     const int nm = pl.nm();
-    const uint64_t total_u = pl.total_u, first_record = h.first_record;
-    auto belongs_not_here = [&](const char *why) { return belongs_not(why, d.path.c_str()); };
-    DevBuf<uint64_t> d_forced;
+    DevBuf<uint64_t> d_forced, d_run_bounds;
+    DevBuf<uint32_t> d_member_run;
     int rc = PC_OK;
     room(rc, d.d_chain, (size_t)std::max(nm, 1)); room(rc, d.d_rec_off, (size_t)std::max(nm, 1) * kMaxRecPerMember); room(rc, d_forced, (size_t)std::max(nm, 1));
     if (rc != PC_OK) return rc;
-    std::vector<uint64_t> run_bounds;   // region read: {start, stop} of every run's record chain
-    DevBuf<uint64_t> d_run_bounds;
-    DevBuf<uint32_t> d_member_run;
+    std::vector<uint64_t> bounds;   // region read: {start, stop} of every run's record chain
     if (span) {
-        run_bounds.assign(2 * std::max<size_t>(runs.size(), 1), ~0ull);
-        for (const BamPlan::ChunkAt &c : pl.chunk_at) {
-            const uint64_t a = pl.uoff_of(c.s_idx) + c.ub, z = pl.uoff_of(c.e_idx) + c.ue;
-            if (a < first_record || z < a || z > total_u) return belongs_not_here("a chunk starts inside the header or ends before it starts");
-            // (the run that holds the chunk's first member; runs ascend by file offset)
-            auto it = std::upper_bound(runs.begin(), runs.end(), c.cb, [](int64_t x, const BamPlan::Run &r) { return x < r.file_lo; });
-            const size_t r = (size_t)(it - runs.begin()) - 1;
-            if (run_bounds[2 * r] == ~0ull) run_bounds[2 * r] = a;
-            run_bounds[2 * r + 1] = z;
-        }
-        for (size_t r = 0; r < runs.size(); ++r)
-            if (run_bounds[2 * r] == ~0ull) run_bounds[2 * r] = run_bounds[2 * r + 1] = pl.uoff_of(runs[r].m1);
-        rc = d_run_bounds.upload(run_bounds, st);
-        if (rc == PC_OK) rc = d_member_run.upload(member_run, st);
+        const int defect = bh::run_bounds(pl, h.first_record, bounds);
+        if (defect) return host_defect(defect, d.path.c_str());
+        rc = d_run_bounds.upload(bounds, st);
+        if (rc == PC_OK) rc = d_member_run.upload(pl.member_run, st);
         if (rc != PC_OK) return rc;
     }
     std::vector<MemberChain> chain((size_t)nm);
     std::vector<uint64_t> forced((size_t)nm, ~0ull);
-    std::vector<uint32_t> nrec_of((size_t)nm, 0u);
-    out.rec_base.assign((size_t)nm + 1, 0);
+    DrainOnExit drained{st};   // (the tables above and the two vectors are read and written by what is queued below)
+    bh::ChainState state(pl, span ? &bounds : nullptr, h.first_record);
     if (nm) {
         HIP_TRY(hipMemsetAsync(d_forced.p, 0xff, (size_t)nm * 8, st));
         int from = 0;
-        uint32_t cur_run = span ? member_run[0] : 0u;   // (region read: the run whose chain `expected` follows)
-        uint64_t expected = span ? run_bounds[2 * (size_t)cur_run] : first_record;
-        uint64_t stop_at = total_u;
         for (int round = 0;; ++round) {
             // (a whole-file read: one chain, no run tables -- both pointers are null)
-            hipLaunchKernelGGL(span ? k_bam_chain<true> : k_bam_chain<false>, dim3((unsigned)(nm - from)), dim3(64), 0, st, d.d_stream.p, total_u, d.d_members.p, nm, from,
-                               h.n_ref, first_record, d_forced.p, d.d_chain.p, d.d_rec_off.p, stop_at, (const uint32_t *)d_member_run.p, (const uint64_t *)d_run_bounds.p);
+            hipLaunchKernelGGL(span ? k_bam_chain<true> : k_bam_chain<false>, dim3((unsigned)(nm - from)), dim3(64), 0, st, d.d_stream.p, pl.total_u, d.d_members.p, nm, from,
+                               h.n_ref, h.first_record, d_forced.p, d.d_chain.p, d.d_rec_off.p, pl.total_u, (const uint32_t *)d_member_run.p, (const uint64_t *)d_run_bounds.p);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(chain.data() + from, d.d_chain.p + from, (size_t)(nm - from) * sizeof(MemberChain), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            int redo = -1;
-            for (int m = from; m < nm; ++m) {
-                if (span && member_run[(size_t)m] != cur_run) {   // each run settles from its forced start and has to end exactly at its stop
-                    if (expected != run_bounds[2 * (size_t)cur_run + 1]) return belongs_not_here("a chunk ends inside a record");
-                    cur_run = member_run[(size_t)m];
-                    expected = run_bounds[2 * (size_t)cur_run];
-                }
-                const uint64_t stop_m = span ? run_bounds[2 * (size_t)cur_run + 1] : stop_at;
-                const uint64_t begin = members[(size_t)m].uoff, end = std::min<uint64_t>(begin + members[(size_t)m].ulen, stop_m);
-                nrec_of[(size_t)m] = 0;
-                if (expected >= end) continue;                      // no record starts in this member (or it lies behind its run's last chunk)
-                const MemberChain &mc = chain[(size_t)m];
-                if (mc.first != expected) {                         // the guess was off (or there was none): walk again from the right place
-                    forced[(size_t)m] = expected;
-                    redo = m;
-                    break;
-                }
-                nrec_of[(size_t)m] = mc.nrec;
-                if (mc.flags & 2u) { out.truncated = true; from = nm; break; }   // a length prefix that cannot be: the walk ends here
-                expected = mc.next;
-            }
-            if (redo < 0) break;
+            const bh::Settle s = bh::settle_round(pl, span ? &bounds : nullptr, chain.data(), from, state);
+            if (s.kind == bh::kInsideRecord) return host_defect(bh::kChunkInRecord, d.path.c_str());
+            if (s.kind == bh::kTruncated) out.truncated = true;
+            if (s.kind != bh::kRedo) break;
             out.chain_restarts += 1;
-            HIP_TRY(hipMemcpyAsync(d_forced.p + redo, &forced[(size_t)redo], 8, hipMemcpyHostToDevice, st));
-            from = redo;
+            forced[(size_t)s.m] = s.forced;
+            HIP_TRY(hipMemcpyAsync(d_forced.p + s.m, &forced[(size_t)s.m], 8, hipMemcpyHostToDevice, st));
+            from = s.m;
             if (round > nm + 8) return fail(PC_ERR_STATE, "pc_bam_open: the record chain of %s did not settle", d.path.c_str());
         }
-        if (span) stop_at = run_bounds[2 * (size_t)cur_run + 1];
-        if (expected != stop_at) {   // the last record runs past (or stops short of) the end of the stream
-            if (span) return belongs_not_here("a chunk ends inside a record");
-            out.truncated = true;
-        }
-        for (int m = 0; m < nm; ++m) out.rec_base[(size_t)m + 1] = out.rec_base[(size_t)m] + nrec_of[(size_t)m];
-        out.nrec = (int64_t)out.rec_base[(size_t)nm];
-    } else if (total_u != first_record && !span) out.truncated = true;
+    } else if (pl.total_u != h.first_record && !span) out.truncated = true;
+    out.rec_base = bh::record_bases(state.nrec_of);
+    out.nrec = (int64_t)out.rec_base[(size_t)nm];
+    drained.armed = false;   // (every round ends in a synchronisation)
     HIP_TRY(hipEventRecord(d.ev[3], st));
     d.clk.lap("header + record chain");
     return PC_OK;
 }
 
-// The first defect the record decode found (k_bam_order's lowest record index), as the error the host reader gives for it;
-// PC_OK for kRecTruncated / kRecBadSize, which the caller reports after every other defect.
-int record_defect(int code, const char *path) {
+// The first defect the record decode found (k_bam_order's lowest record index: `first_err` = index << 8 | code, ~0: none),
+// as the error the host reader gives for it; kRecTruncated / kRecBadSize and a chain that ended short (`truncated`) are
+// reported after every other defect.
+int record_defect(unsigned long long first_err, bool truncated, const char *path) {
     using namespace pcbam;
-    switch (code) {
+    if (first_err != ~0ull) switch ((int)(first_err & 0xffu)) {
     case kRecTidRange: return fail(PC_ERR_ARG, "BAM record with reference id out of range");
     case kRecNegPos: return fail(PC_ERR_ARG, "placed BAM record with a negative position");
     case kRecUnsorted: return fail(PC_ERR_UNSORTED, "BAM file is not coordinate sorted: %s", path);
@@ -650,20 +405,9 @@ int record_defect(int code, const char *path) {
     case kRecEndBeyond: return fail(PC_ERR_ARG, "alignment ends beyond 2^31 - 1");
     case kRecTooLong: return fail(PC_ERR_ARG, "alignment with more than 2^31 - 1 aligned positions");
     case kRecDeletionOrder: return fail(PC_ERR_ARG, "alignment starting with a deletion breaks coordinate order; not supported");
-    default: return PC_OK;
+    default: truncated = true;
     }
-}
-
-// the member of every 256th record (k_bam_fields and its kin walk forward from there)
-std::vector<uint32_t> group_members(const std::vector<uint64_t> &rec_base, int64_t nrec, int nm) {
-    std::vector<uint32_t> rec_member((size_t)((nrec + 255) >> 8));
-    int m = 0;
-    for (size_t g = 0; g < rec_member.size(); ++g) {
-        const uint64_t i = (uint64_t)g << 8;
-        while (m + 1 < nm && rec_base[(size_t)m + 1] <= i) ++m;
-        rec_member[g] = (uint32_t)m;
-    }
-    return rec_member;
+    return truncated ? fail(PC_ERR_ARG, "truncated BAM record") : PC_OK;
 }
 
 // the events around the sort phase of an open with PC_BAM_SORT: key kernel [0, 1]; sort, ranks and run offsets [2, 3]
@@ -676,184 +420,219 @@ struct SortEvents {
     ~SortEvents() { for (auto x : ev) if (x) (void)hipEventDestroy(x); }
 };
 
-// Phase 5: fields, order checks (or, with `sort`, the coordinate sort), the region filter, the scans that place every kept record, and the columns of `b`.
-int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const BamHeader &h, const BamRecords &recs, pc_bam &b, bool sort) {
+// ---- the common head of phase 5 (decode_columns, index_records): the record table on the device and every record's fields
+struct RecordTable {
+    std::vector<uint32_t> rec_member;    // (host copy of d_rec_member: alive while its upload is)
+    DevBuf<uint64_t> d_rec_base;
+    DevBuf<uint32_t> d_rec_member, d_placed;
+    DevBuf<pcbam::RecOut> d_recs;
+    DevBuf<unsigned long long> d_misc;   // [0] first error (index << 8 | code); the rest is the phase's own
+    unsigned g256 = 0;                   // blocks of 256 threads over the records
+    // PC_BAM_SORT: the sort keys, and whether they found the file out of order
+    DevBuf<uint64_t> d_key;
+    DevBuf<uint32_t> d_idx;
+    SortEvents sev;
+    bool disorder = false;
+};
+// k_bam_fields, then the order checks -- or, with `sort`, the keys first: a file they find in order goes on exactly as
+// without the flag.  `n_misc` counters ([0] = ~0, the others 0) and `n_placed` entries of d_placed are the caller's to use.
+int decode_fields(BamDecode &d, const BamPlan &pl, const BamHeader &h, const BamRecords &recs, size_t n_misc, size_t n_placed, bool sort, RecordTable &t) {
     using namespace pcbam;
     hipStream_t st = d.st;
-    const int nm = pl.nm();
-    const uint64_t total_u = pl.total_u;
     const int64_t nrec = recs.nrec;
-    bool truncated = recs.truncated;
-    DevBuf<uint64_t> d_rec_base;
-    DevBuf<uint32_t> d_rec_member, d_placed, d_runs, d_staged_at, d_run_at, d_wide;
-    DevBuf<RecOut> d_recs;
-    DevBuf<unsigned long long> d_misc;   // [0] first error (index << 8 | code), [1] mapped, [2] unplaced; with `sort`: [3] out of order, [4] records moved
-    int rc = d_misc.reserve(6);
+    static const unsigned long long misc0[6] = {~0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    PC_TRY(t.d_misc.reserve(n_misc));
+    HIP_TRY(hipMemcpyAsync(t.d_misc.p, misc0, n_misc * 8, hipMemcpyHostToDevice, st));
+    if (nrec <= 0) return PC_OK;
+    t.rec_member = bh::group_members(recs.rec_base, nrec, pl.nm());
+    int rc = t.d_rec_base.upload(recs.rec_base, st);
+    if (rc == PC_OK) rc = t.d_rec_member.upload(t.rec_member, st);
+    room(rc, t.d_recs, (size_t)nrec); room(rc, t.d_placed, n_placed);
+    if (sort) { room(rc, t.d_key, (size_t)nrec); room(rc, t.d_idx, (size_t)nrec); }
+    if (rc == PC_OK && sort) rc = t.sev.create();
     if (rc != PC_OK) return rc;
-    const unsigned long long misc0[6] = {~0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
-    HIP_TRY(hipMemcpyAsync(d_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, st));
-    int64_t n_staged = 0, n_runs = 0;
-    if (nrec > 0) {
-        const std::vector<uint32_t> rec_member = group_members(recs.rec_base, nrec, nm);
-        rc = d_rec_base.upload(recs.rec_base, st);
-        if (rc == PC_OK) rc = d_rec_member.upload(rec_member, st);
-        room(rc, d_recs, (size_t)nrec);
-        room(rc, d_placed, (size_t)nrec + 1); room(rc, d_runs, (size_t)nrec + 1); room(rc, d_staged_at, (size_t)nrec + 1); room(rc, d_run_at, (size_t)nrec + 1);
-        if (rc != PC_OK) return rc;
-        const unsigned g256 = (unsigned)((nrec + 255) / 256);
-        hipLaunchKernelGGL(k_bam_fields, dim3(g256), dim3(256), 0, st, d.d_stream.p, total_u, d.d_members.p, d_rec_base.p, d.d_chain.p, d.d_rec_off.p, nm, nrec,
-                           h.n_ref, d_rec_member.p, d_recs.p);
-        // `sort`: the keys first; a file they find in order goes on exactly as without the flag
-        DevBuf<uint64_t> d_key, d_key2;
-        DevBuf<uint32_t> d_idx, d_idx2, d_runs_sorted;
-        SortEvents sev;
-        bool disorder = false;
-        if (sort) {
-            room(rc, d_key, (size_t)nrec); room(rc, d_idx, (size_t)nrec);
-            if (rc == PC_OK) rc = sev.create();
-            if (rc != PC_OK) return rc;
-            unsigned long long dis = 0;
-            HIP_TRY(hipEventRecord(sev.ev[0], st));
-            hipLaunchKernelGGL(k_bam_sort_keys, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, d_key.p, d_idx.p, d_misc.p + 3);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(sev.ev[1], st));
-            HIP_TRY(hipMemcpyAsync(&dis, d_misc.p + 3, 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            disorder = dis != 0;
-            b.sorted_input = !disorder;
-            if (!disorder) { d_key.release(); d_idx.release(); }
-        }
-        if (!disorder) hipLaunchKernelGGL(k_bam_order, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, d_placed.p, d_misc.p);
-        DevBuf<int32_t> d_rtid;
-        DevBuf<int64_t> d_rbe;
-        if (span) {   // keep what overlaps a requested region (htslib's overlap rule); everything else is as if it were not in the file
-            const size_t nr = (size_t)std::max(span->nreg, 0);
-            rc = d_rtid.upload(span->tid, nr, st);
-            if (rc == PC_OK) rc = d_rbe.reserve(2 * std::max<size_t>(nr, 1));
-            if (rc != PC_OK) return rc;
-            if (nr) {
-                HIP_TRY(hipMemcpyAsync(d_rbe.p, span->beg, nr * 8, hipMemcpyHostToDevice, st));
-                HIP_TRY(hipMemcpyAsync(d_rbe.p + nr, span->end, nr * 8, hipMemcpyHostToDevice, st));
-            }
-            hipLaunchKernelGGL(k_bam_region_filter, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, (int)nr, d_rtid.p, d_rbe.p, d_rbe.p + nr);
-        }
-        HIP_TRY(hipMemsetAsync(d_placed.p + nrec, 0, 4, st));
-        HIP_TRY(hipMemsetAsync(d_runs.p + nrec, 0, 4, st));
-        hipLaunchKernelGGL(k_bam_scan_inputs, dim3((unsigned)((nrec + 256 * kScanInputsPerThread - 1) / (256 * kScanInputsPerThread))), dim3(256), 0, st, d_recs.p, nrec, d_placed.p, d_runs.p, d_misc.p + 1);
-        {
-            size_t tmp_bytes = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_placed.p, d_staged_at.p, (int)(nrec + 1), st));
-            DevBuf<uint8_t> d_tmp;
-            rc = d_tmp.reserve(std::max<size_t>(tmp_bytes, 16));
-            if (rc != PC_OK) return rc;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_placed.p, d_staged_at.p, (int)(nrec + 1), st));
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_runs.p, d_run_at.p, (int)(nrec + 1), st));
-            // Out of order: one stable radix sort of (key, record number) over the key bits in use, then staged_at and run_at
-            // by rank in the sorted order (the totals stay those of the two scans above).  Placed records sort first.
-            DevBuf<uint8_t> d_sort_tmp;
-            if (disorder) {
-                const int key_bits = sort_key_bits(h.n_ref);
-                room(rc, d_key2, (size_t)nrec); room(rc, d_idx2, (size_t)nrec); room(rc, d_runs_sorted, (size_t)nrec + 1);
-                if (rc != PC_OK) return rc;
-                HIP_TRY(hipEventRecord(sev.ev[2], st));
-                // (double buffers: the passes go back and forth between the two halves, and the sort says which half holds the result)
-                hipcub::DoubleBuffer<uint64_t> keys(d_key.p, d_key2.p);
-                hipcub::DoubleBuffer<uint32_t> vals(d_idx.p, d_idx2.p);
-                size_t sort_bytes = 0;
-                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, vals, (int)nrec, 0, key_bits, st));
-                rc = d_sort_tmp.reserve(std::max<size_t>(sort_bytes, 16));
-                if (rc != PC_OK) { (void)hipStreamSynchronize(st); return rc; }
-                HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, sort_bytes, keys, vals, (int)nrec, 0, key_bits, st));
-                const uint32_t *perm = vals.Current();
-                b.file_order.swap(perm == d_idx.p ? d_idx : d_idx2);   // (the permutation is the staged records' numbers in the file)
-                HIP_TRY(hipMemsetAsync(d_runs_sorted.p + nrec, 0, 4, st));
-                hipLaunchKernelGGL(k_bam_sort_rank, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, perm, d_staged_at.p, d_runs_sorted.p, d_misc.p, d_misc.p + 4);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_runs_sorted.p, d_runs_sorted.p, (int)(nrec + 1), st));   // (in place)
-                hipLaunchKernelGGL(k_bam_sort_run_at, dim3(g256), dim3(256), 0, st, perm, d_runs_sorted.p, nrec, d_run_at.p);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipEventRecord(sev.ev[3], st));
-                b.key_bits = key_bits;
-            }
-            uint32_t tot[2] = {0, 0};
-            unsigned long long misc[5] = {0, 0, 0, 0, 0};
-            HIP_TRY(hipMemcpyAsync(&tot[0], d_staged_at.p + nrec, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(&tot[1], d_run_at.p + nrec, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(misc, d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));   // (d_tmp and the sort's buffers go out of scope)
-            n_staged = tot[0]; n_runs = tot[1];
-            b.mapped = (int64_t)misc[1]; b.unplaced = (int64_t)misc[2];
-            if (sort) {
-                b.sort_ms = ms_between(sev.ev[0], sev.ev[1]) + (disorder ? ms_between(sev.ev[2], sev.ev[3]) : 0.0);
-                b.moved = (int64_t)misc[4];
-                if (!b.moved) b.file_order.release();
-            }
-            if (misc[0] != ~0ull) {
-                rc = record_defect((int)(misc[0] & 0xffu), d.path.c_str());
-                if (rc != PC_OK) return rc;
-                truncated = true;   // kRecTruncated / kRecBadSize: reported below, after every other defect
-            }
-        }
-        if (truncated) return fail(PC_ERR_ARG, "truncated BAM record");
-        const size_t ns = (size_t)std::max<int64_t>(n_staged, 1), nrun = (size_t)std::max<int64_t>(n_runs, 1);   // (no empty column)
-        room(rc, b.tid, ns); room(rc, b.pos, ns); room(rc, b.alen, ns); room(rc, b.flags, ns); room(rc, b.nblk, ns);
-        room(rc, b.flag16, ns); room(rc, b.mapq, ns); room(rc, b.lseq, ns); room(rc, b.nh, ns);
-        room(rc, b.blk_start, nrun); room(rc, b.blk_len, nrun);
-        room(rc, d_wide, ns);
-        if (rc != PC_OK) return rc;
-        HIP_TRY(hipMemsetAsync(d_wide.p, 0, ns * 4, st));
-        hipLaunchKernelGGL(k_bam_columns, dim3(g256), dim3(256), 0, st, d.d_stream.p, d.d_members.p, d_rec_base.p, d.d_rec_off.p, nm, d_rec_member.p, d_recs.p,
-                           nrec, d_staged_at.p, d_run_at.p, b.tid.p, b.pos.p, b.alen.p, b.flags.p, b.nblk.p, b.blk_start.p, b.blk_len.p, d_wide.p,
-                           b.flag16.p, b.mapq.p, b.lseq.p, b.nh.p);
+    t.g256 = (unsigned)((nrec + 255) / 256);
+    hipLaunchKernelGGL(k_bam_fields, dim3(t.g256), dim3(256), 0, st, d.d_stream.p, pl.total_u, d.d_members.p, t.d_rec_base.p, d.d_chain.p, d.d_rec_off.p, pl.nm(), nrec,
+                       h.n_ref, t.d_rec_member.p, t.d_recs.p);
+    if (sort) {
+        unsigned long long dis = 0;
+        HIP_TRY(hipEventRecord(t.sev.ev[0], st));
+        hipLaunchKernelGGL(k_bam_sort_keys, dim3(t.g256), dim3(256), 0, st, t.d_recs.p, nrec, t.d_key.p, t.d_idx.p, t.d_misc.p + 3);
         HIP_TRY(hipGetLastError());
-        // wide records (beyond the 16-bit / 8-bit columns): rare -- their staged indices are found from the markers on
-        // the host side of pc_bam_read; the true values are read back here, record by record
-        {
-            // count the flagged records (a sum reduction through the scan buffers would do; a plain read-back of the
-            // flags is only paid when the file has any: probe with a device-side total first)
-            DevBuf<uint32_t> d_wsum;
-            rc = d_wsum.reserve((size_t)n_staged + 1);
-            if (rc != PC_OK) return rc;
-            size_t tmp_bytes = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_wide.p, d_wsum.p, (int)std::max<int64_t>(n_staged, 1), st));
-            DevBuf<uint8_t> d_tmp;
-            rc = d_tmp.reserve(std::max<size_t>(tmp_bytes, 16));
-            if (rc != PC_OK) return rc;
-            uint32_t last_sum = 0, last_flag = 0;
-            if (n_staged > 0) {
-                HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_wide.p, d_wsum.p, (int)n_staged, st));
-                HIP_TRY(hipMemcpyAsync(&last_sum, d_wsum.p + (n_staged - 1), 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(&last_flag, d_wide.p + (n_staged - 1), 4, hipMemcpyDeviceToHost, st));
-            }
-            HIP_TRY(hipStreamSynchronize(st));
-            const uint32_t nwide = last_sum + last_flag;
-            if (nwide) {
-                std::vector<uint32_t> wf((size_t)n_staged), sa((size_t)nrec);
-                std::vector<RecOut> ro((size_t)nrec);
-                HIP_TRY(hipMemcpy(wf.data(), d_wide.p, (size_t)n_staged * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(sa.data(), d_staged_at.p, (size_t)nrec * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(ro.data(), d_recs.p, (size_t)nrec * sizeof(RecOut), hipMemcpyDeviceToHost));
-                for (int64_t i = 0; i < nrec; ++i)
-                    if (ro[(size_t)i].placed == 1 && wf[sa[(size_t)i]]) {
-                        b.wide_idx.push_back((int64_t)sa[(size_t)i]);
-                        b.wide_alen.push_back((int32_t)ro[(size_t)i].L);
-                        b.wide_nblk.push_back((int32_t)ro[(size_t)i].nruns);
-                    }
-                if (b.moved) {   // the walk above is in file order: the list is kept ascending by staged index
-                    std::vector<size_t> by((size_t)b.wide_idx.size());
-                    std::iota(by.begin(), by.end(), (size_t)0);
-                    std::sort(by.begin(), by.end(), [&](size_t x, size_t y) { return b.wide_idx[x] < b.wide_idx[y]; });
-                    const std::vector<int64_t> wi = b.wide_idx;
-                    const std::vector<int32_t> wa = b.wide_alen, wn = b.wide_nblk;
-                    for (size_t k = 0; k < by.size(); ++k) { b.wide_idx[k] = wi[by[k]]; b.wide_alen[k] = wa[by[k]]; b.wide_nblk[k] = wn[by[k]]; }
-                }
-            }
+        HIP_TRY(hipEventRecord(t.sev.ev[1], st));
+        HIP_TRY(hipMemcpyAsync(&dis, t.d_misc.p + 3, 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        t.disorder = dis != 0;
+        if (!t.disorder) { t.d_key.release(); t.d_idx.release(); }
+    }
+    if (!t.disorder) hipLaunchKernelGGL(k_bam_order, dim3(t.g256), dim3(256), 0, st, t.d_recs.p, nrec, t.d_placed.p, t.d_misc.p);
+    HIP_TRY(hipGetLastError());
+    return PC_OK;
+}
+
+// ---- phase 5 of an open.  What its steps share beside the record table:
+struct ColumnWork {
+    RecordTable t;
+    DevBuf<int32_t> d_rtid;              // region read: the regions' reference ids, starts and ends
+    DevBuf<int64_t> d_rbe;
+    DevBuf<uint32_t> d_runs, d_staged_at, d_run_at, d_wide;   // per record: its runs, where it is staged and where its runs go; per staged record: wide or not
+    int64_t n_staged = 0, n_runs = 0;
+};
+
+// Step 1 (region reads): keep what overlaps a requested region (htslib's overlap rule); everything else is as if it were not in the file.
+int filter_regions(BamDecode &d, const BamSpan &span, int64_t nrec, ColumnWork &w) {
+    hipStream_t st = d.st;
+    const size_t nr = (size_t)std::max(span.nreg, 0);
+    int rc = w.d_rtid.upload(span.tid, nr, st);
+    if (rc == PC_OK) rc = w.d_rbe.reserve(2 * std::max<size_t>(nr, 1));
+    if (rc != PC_OK) return rc;
+    if (nr) {
+        HIP_TRY(hipMemcpyAsync(w.d_rbe.p, span.beg, nr * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(w.d_rbe.p + nr, span.end, nr * 8, hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(pcbam::k_bam_region_filter, dim3(w.t.g256), dim3(256), 0, st, w.t.d_recs.p, nrec, (int)nr, w.d_rtid.p, w.d_rbe.p, w.d_rbe.p + nr);
+    return PC_OK;
+}
+
+// Step 2: where every kept record and its runs go -- two exclusive sums; out of order: one stable radix sort of (key,
+// record number) over the key bits in use, then staged_at and run_at by rank in the sorted order (the totals stay those
+// of the two sums; placed records sort first).  The totals, the counts of `b` and the first defect come down.
+int place_records(BamDecode &d, const BamHeader &h, const BamRecords &recs, bool sort, ColumnWork &w, pc_bam &b) {
+    using namespace pcbam;
+    hipStream_t st = d.st;
+    RecordTable &t = w.t;
+    const int64_t nrec = recs.nrec;
+    uint32_t tot[2] = {0, 0};
+    unsigned long long misc[5] = {0, 0, 0, 0, 0};
+    DevBuf<uint8_t> d_tmp, d_sort_tmp;
+    DevBuf<uint64_t> d_key2;
+    DevBuf<uint32_t> d_idx2, d_runs_sorted;
+    DrainOnExit drained{st};
+    HIP_TRY(hipMemsetAsync(t.d_placed.p + nrec, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(w.d_runs.p + nrec, 0, 4, st));
+    hipLaunchKernelGGL(k_bam_scan_inputs, dim3((unsigned)((nrec + 256 * kScanInputsPerThread - 1) / (256 * kScanInputsPerThread))), dim3(256), 0, st, t.d_recs.p, nrec, t.d_placed.p, w.d_runs.p, t.d_misc.p + 1);
+    size_t tmp_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, t.d_placed.p, w.d_staged_at.p, (int)(nrec + 1), st));
+    PC_TRY(d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, t.d_placed.p, w.d_staged_at.p, (int)(nrec + 1), st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, w.d_runs.p, w.d_run_at.p, (int)(nrec + 1), st));
+    if (t.disorder) {
+        const int key_bits = sort_key_bits(h.n_ref);
+        int rc = PC_OK;
+        room(rc, d_key2, (size_t)nrec); room(rc, d_idx2, (size_t)nrec); room(rc, d_runs_sorted, (size_t)nrec + 1);
+        if (rc != PC_OK) return rc;
+        HIP_TRY(hipEventRecord(t.sev.ev[2], st));
+        // (double buffers: the passes go back and forth between the two halves, and the sort says which half holds the result)
+        hipcub::DoubleBuffer<uint64_t> keys(t.d_key.p, d_key2.p);
+        hipcub::DoubleBuffer<uint32_t> vals(t.d_idx.p, d_idx2.p);
+        size_t sort_bytes = 0;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, vals, (int)nrec, 0, key_bits, st));
+        PC_TRY(d_sort_tmp.reserve(std::max<size_t>(sort_bytes, 16)));
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, sort_bytes, keys, vals, (int)nrec, 0, key_bits, st));
+        const uint32_t *perm = vals.Current();
+        b.file_order.swap(perm == t.d_idx.p ? t.d_idx : d_idx2);   // (the permutation is the staged records' numbers in the file)
+        HIP_TRY(hipMemsetAsync(d_runs_sorted.p + nrec, 0, 4, st));
+        hipLaunchKernelGGL(k_bam_sort_rank, dim3(t.g256), dim3(256), 0, st, t.d_recs.p, nrec, perm, w.d_staged_at.p, d_runs_sorted.p, t.d_misc.p, t.d_misc.p + 4);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_runs_sorted.p, d_runs_sorted.p, (int)(nrec + 1), st));   // (in place)
+        hipLaunchKernelGGL(k_bam_sort_run_at, dim3(t.g256), dim3(256), 0, st, perm, d_runs_sorted.p, nrec, w.d_run_at.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(t.sev.ev[3], st));
+        b.key_bits = key_bits;
+    }
+    HIP_TRY(hipMemcpyAsync(&tot[0], w.d_staged_at.p + nrec, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&tot[1], w.d_run_at.p + nrec, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(misc, t.d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    w.n_staged = tot[0]; w.n_runs = tot[1];
+    b.mapped = (int64_t)misc[1]; b.unplaced = (int64_t)misc[2];
+    if (sort) {
+        b.sort_ms = ms_between(t.sev.ev[0], t.sev.ev[1]) + (t.disorder ? ms_between(t.sev.ev[2], t.sev.ev[3]) : 0.0);
+        b.moved = (int64_t)misc[4];
+        if (!b.moved) b.file_order.release();
+    }
+    return record_defect(misc[0], recs.truncated, d.path.c_str());
+}
+
+// Step 3: the columns of `b`, and the marker of every staged record that is wide.
+int write_columns(BamDecode &d, const BamPlan &pl, int64_t nrec, ColumnWork &w, pc_bam &b) {
+    hipStream_t st = d.st;
+    const RecordTable &t = w.t;
+    const size_t ns = (size_t)std::max<int64_t>(w.n_staged, 1), nrun = (size_t)std::max<int64_t>(w.n_runs, 1);   // (no empty column)
+    int rc = PC_OK;
+    room(rc, b.tid, ns); room(rc, b.pos, ns); room(rc, b.alen, ns); room(rc, b.flags, ns); room(rc, b.nblk, ns);
+    room(rc, b.flag16, ns); room(rc, b.mapq, ns); room(rc, b.lseq, ns); room(rc, b.nh, ns);
+    room(rc, b.blk_start, nrun); room(rc, b.blk_len, nrun);
+    room(rc, w.d_wide, ns);
+    if (rc != PC_OK) return rc;
+    HIP_TRY(hipMemsetAsync(w.d_wide.p, 0, ns * 4, st));
+    hipLaunchKernelGGL(pcbam::k_bam_columns, dim3(t.g256), dim3(256), 0, st, d.d_stream.p, d.d_members.p, t.d_rec_base.p, d.d_rec_off.p, pl.nm(), t.d_rec_member.p, t.d_recs.p,
+                       nrec, w.d_staged_at.p, w.d_run_at.p, b.tid.p, b.pos.p, b.alen.p, b.flags.p, b.nblk.p, b.blk_start.p, b.blk_len.p, w.d_wide.p,
+                       b.flag16.p, b.mapq.p, b.lseq.p, b.nh.p);
+    HIP_TRY(hipGetLastError());
+    return PC_OK;
+}
+
+// Step 4: wide records (beyond the 16-bit / 8-bit columns): rare -- their staged indices are found from the markers on
+// the host side of pc_bam_read; the true values are read back here, record by record.  A plain read-back of the markers is
+// only paid when the file has any: a device-side total first.
+int collect_wide(BamDecode &d, int64_t nrec, ColumnWork &w, pc_bam &b) {
+    hipStream_t st = d.st;
+    const int64_t n_staged = w.n_staged;
+    uint32_t last_sum = 0, last_flag = 0;
+    DevBuf<uint32_t> d_wsum;
+    DevBuf<uint8_t> d_tmp;
+    DrainOnExit drained{st};
+    PC_TRY(d_wsum.reserve((size_t)n_staged + 1));
+    size_t tmp_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, w.d_wide.p, d_wsum.p, (int)std::max<int64_t>(n_staged, 1), st));
+    PC_TRY(d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    if (n_staged > 0) {
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, w.d_wide.p, d_wsum.p, (int)n_staged, st));
+        HIP_TRY(hipMemcpyAsync(&last_sum, d_wsum.p + (n_staged - 1), 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&last_flag, w.d_wide.p + (n_staged - 1), 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    if (last_sum + last_flag == 0) return PC_OK;
+    std::vector<uint32_t> wf((size_t)n_staged), sa((size_t)nrec);
+    std::vector<pcbam::RecOut> ro((size_t)nrec);
+    HIP_TRY(hipMemcpy(wf.data(), w.d_wide.p, (size_t)n_staged * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(sa.data(), w.d_staged_at.p, (size_t)nrec * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(ro.data(), w.t.d_recs.p, (size_t)nrec * sizeof(pcbam::RecOut), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < nrec; ++i)
+        if (ro[(size_t)i].placed == 1 && wf[sa[(size_t)i]]) {
+            b.wide_idx.push_back((int64_t)sa[(size_t)i]);
+            b.wide_alen.push_back((int32_t)ro[(size_t)i].L);
+            b.wide_nblk.push_back((int32_t)ro[(size_t)i].nruns);
         }
-    } else if (truncated) return fail(PC_ERR_ARG, "truncated BAM record");
+    if (b.moved) bh::order_wide_list(b.wide_idx, b.wide_alen, b.wide_nblk);   // (the walk above is in file order)
+    return PC_OK;
+}
+
+// Phase 5: fields, order checks (or, with `sort`, the coordinate sort), the region filter, the scans that place every kept record, and the columns of `b`.
+int decode_columns(BamDecode &d, const BamPlan &pl, const BamSpan *span, const BamHeader &h, const BamRecords &recs, pc_bam &b, bool sort) {
+    hipStream_t st = d.st;
+    const int64_t nrec = recs.nrec;
+    ColumnWork w;
+    DrainOnExit drained{st};   // (misc: [1] mapped, [2] unplaced; with `sort`: [3] out of order, [4] records moved)
+    PC_TRY(decode_fields(d, pl, h, recs, 6, (size_t)nrec + 1, sort, w.t));
+    if (nrec > 0) {
+        int rc = PC_OK;
+        room(rc, w.d_runs, (size_t)nrec + 1); room(rc, w.d_staged_at, (size_t)nrec + 1); room(rc, w.d_run_at, (size_t)nrec + 1);
+        if (rc != PC_OK) return rc;
+        if (sort) b.sorted_input = !w.t.disorder;
+        if (span) PC_TRY(filter_regions(d, *span, nrec, w));
+        PC_TRY(place_records(d, h, recs, sort, w, b));
+        PC_TRY(write_columns(d, pl, nrec, w, b));
+        PC_TRY(collect_wide(d, nrec, w, b));
+    } else if (recs.truncated) return fail(PC_ERR_ARG, "truncated BAM record");
     HIP_TRY(hipEventRecord(d.ev[4], st));
     HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
     d.clk.lap("fields + scans + columns");
-    b.n = n_staged; b.nrun = n_runs;
+    b.n = w.n_staged; b.nrun = w.n_runs;
     return PC_OK;
 }
 
@@ -869,14 +648,194 @@ struct IndexParts {
     double ms_fields = 0, ms_kernels = 0, ms_readback = 0;   // wall clock between the phase's synchronisations
 };
 
-// The index build's phase 5 (whole-file reads only): k_bam_fields and the order checks as decode_columns runs them -- no
-// column is written or read back -- then the kernels of index_kernels.hip.h; the sorted runs, the linear arrays (BAI) or
-// the runs' loff (CSI: the windows stay in HBM) and the per-reference counts come down.
-int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader &h, const BamRecords &recs, const IndexShape &shape, IndexParts &out) {
+// ---- the index build's phase 5.  What its steps share beside the record table:
+struct IndexWork {
+    RecordTable t;
+    std::vector<uint64_t> blk;           // bh::tell_table (host copy: alive while its upload is)
+    DevBuf<uint64_t> d_blk, d_key, d_voff, d_cov, d_covered;
+    DevBuf<uint32_t> d_mapped, d_mapped_before, d_head, d_slot;
+    DevBuf<int32_t> d_win_a;
+    DevBuf<int64_t> d_ref_fl;            // first record of every reference, then the last
+    DevBuf<uint64_t> d_ref_be;           // per reference: offset of its first record, then of the first record behind its last
+    DevBuf<int64_t> d_ref_cnt;           // mapped, then unmapped
+    DevBuf<int32_t> d_n_intv;
+    DevBuf<int64_t> d_lin_base;
+    DevBuf<uint64_t> d_sbeg, d_send, d_linear, d_filled, d_sloff;   // the runs in (tid, bin) order; the windows
+    DevBuf<uint32_t> d_sbin;
+    DevBuf<int32_t> d_stid;
+    size_t nr = 1;                       // references, at least one
+    int64_t n_runs = 0, n_lin = 0;
+    unsigned g256p = 0;                  // blocks of 256 threads over the records and the end entry
+    int reserve(int64_t nrec, int n_ref) {
+        const size_t n1 = (size_t)nrec + 1;
+        nr = (size_t)std::max(n_ref, 1);
+        g256p = (unsigned)((nrec + 1 + 255) / 256);
+        int rc = PC_OK;
+        room(rc, d_key, (size_t)nrec); room(rc, d_voff, n1); room(rc, d_cov, n1); room(rc, d_covered, n1); room(rc, d_win_a, (size_t)nrec);
+        room(rc, d_mapped, n1); room(rc, d_mapped_before, n1); room(rc, d_head, n1); room(rc, d_slot, n1); room(rc, d_ref_fl, 2 * nr);
+        return rc;
+    }
+};
+
+// Step 1: keys, run heads, per-reference bounds and counts, covered windows; what sizes the rest comes down.
+int index_keys_and_stats(BamDecode &d, const BamPlan &pl, const BamHeader &h, const BamRecords &recs, const IndexShape &shape, IndexWork &w, IndexParts &out) {
     using namespace pcbam;
     using namespace pcidx;
     hipStream_t st = d.st;
-    const int nm = pl.nm();
+    const RecordTable &t = w.t;
+    const int64_t nrec = recs.nrec;
+    const int n_ref = (int)h.n_ref, nm = pl.nm();
+    const size_t n1 = (size_t)nrec + 1, nr = w.nr;
+    std::vector<int32_t> n_intv((size_t)n_ref, 0);
+    uint32_t n_runs32 = 0;
+    unsigned long long misc[2] = {0, 0};
+    DevBuf<uint8_t> d_tmp;
+    DrainOnExit drained{st};
+    const auto idx_keys = shape.csi ? k_idx_keys<false> : k_idx_keys<true>;
+    hipLaunchKernelGGL(idx_keys, dim3(w.g256p), dim3(256), 0, st, d.d_stream.p, d.d_members.p, w.d_blk.p, t.d_rec_base.p, d.d_rec_off.p, nm, nrec, t.d_rec_member.p,
+                       t.d_recs.p, w.d_key.p, w.d_voff.p, w.d_win_a.p, w.d_cov.p, w.d_mapped.p, (uint32_t *)(t.d_misc.p + 1), shape.min_shift, shape.n_lvls);
+    HIP_TRY(hipMemsetAsync(w.d_ref_fl.p, 0xff, 2 * nr * sizeof(int64_t), st));
+    hipLaunchKernelGGL(k_idx_heads, dim3(w.g256p), dim3(256), 0, st, w.d_key.p, nrec, w.d_head.p, w.d_ref_fl.p, w.d_ref_fl.p + nr);
+    HIP_TRY(hipGetLastError());
+    {
+        size_t a = 0, b = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, a, w.d_head.p, w.d_slot.p, (int)n1, st));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, b, w.d_cov.p, w.d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st));
+        size_t tmp_bytes = std::max<size_t>(std::max(a, b), 16);
+        PC_TRY(d_tmp.reserve(tmp_bytes));
+        a = b = tmp_bytes;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, a, w.d_head.p, w.d_slot.p, (int)n1, st));
+        a = tmp_bytes;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, a, w.d_mapped.p, w.d_mapped_before.p, (int)n1, st));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(d_tmp.p, b, w.d_cov.p, w.d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st));
+    }
+    int rc = PC_OK;
+    room(rc, w.d_ref_be, 2 * nr); room(rc, w.d_ref_cnt, 2 * nr); room(rc, w.d_n_intv, nr);
+    if (rc != PC_OK) return rc;
+    if (n_ref) {
+        hipLaunchKernelGGL(k_idx_ref_stats, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), 0, st, n_ref, w.d_ref_fl.p, w.d_ref_fl.p + nr, w.d_voff.p, w.d_mapped_before.p,
+                           w.d_covered.p, w.d_ref_be.p, w.d_ref_be.p + nr, w.d_ref_cnt.p, w.d_ref_cnt.p + nr, w.d_n_intv.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(n_intv.data(), w.d_n_intv.p, (size_t)n_ref * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.ref_beg.data(), w.d_ref_be.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.ref_end.data(), w.d_ref_be.p + nr, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.ref_mapped.data(), w.d_ref_cnt.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.ref_unmapped.data(), w.d_ref_cnt.p + nr, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
+    }
+    HIP_TRY(hipMemcpyAsync(&n_runs32, w.d_slot.p + nrec, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(misc, t.d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    if ((uint32_t)misc[1]) {
+        if (!shape.csi) return fail(PC_ERR_ARG, "a BAI index cannot hold %s: an alignment reaches beyond 2^29", d.path.c_str());
+        return fail(PC_ERR_ARG, "a CSI index of min_shift %d and depth %d cannot hold %s: an alignment reaches beyond %lld", shape.min_shift, shape.n_lvls,
+                    d.path.c_str(), (long long)shape.reach());
+    }
+    int64_t placed = 0;
+    for (int r = 0; r < n_ref; ++r) {
+        out.lin_start[(size_t)r + 1] = out.lin_start[(size_t)r] + n_intv[(size_t)r];
+        placed += out.ref_mapped[(size_t)r] + out.ref_unmapped[(size_t)r];
+    }
+    out.n_no_coor = nrec - placed;
+    w.n_runs = (int64_t)n_runs32;
+    w.n_lin = out.n_windows = out.lin_start[(size_t)n_ref];
+    if (shape.csi && w.n_lin > kMaxWindows)
+        return fail(PC_ERR_ARG, "a CSI index of min_shift %d of %s has %lld windows, more than 2^28: use a larger min_shift", shape.min_shift, d.path.c_str(),
+                    (long long)w.n_lin);
+    return PC_OK;
+}
+
+// Step 2: the buffers of the sorted runs and the windows; the runs, sorted by (tid, bin), gathered in that order.
+int index_sort_runs(BamDecode &d, const BamRecords &recs, int n_ref, const IndexShape &shape, IndexWork &w, const IndexParts &out) {
+    using namespace pcidx;
+    hipStream_t st = d.st;
+    const int64_t nrec = recs.nrec, n_runs = w.n_runs, n_lin = w.n_lin;
+    std::vector<uint32_t> iota((size_t)n_runs);   // (hipcub's iota: the slots 0 .. n_runs - 1 are the values of the sort)
+    DevBuf<uint64_t> d_run_key, d_run_key2, d_run_beg, d_run_end;
+    DevBuf<uint32_t> d_order, d_order2;
+    DevBuf<uint8_t> d_sort_tmp;
+    DrainOnExit drained{st};
+    const size_t nrun = (size_t)std::max<int64_t>(n_runs, 1);
+    int rc = PC_OK;
+    room(rc, d_run_key, nrun); room(rc, d_run_key2, nrun); room(rc, d_run_beg, nrun); room(rc, d_run_end, nrun); room(rc, w.d_sbeg, nrun); room(rc, w.d_send, nrun);
+    room(rc, d_order, nrun); room(rc, d_order2, nrun); room(rc, w.d_sbin, nrun); room(rc, w.d_stid, nrun);
+    room(rc, w.d_linear, (size_t)std::max<int64_t>(n_lin, 1));
+    if (shape.csi) { room(rc, w.d_filled, (size_t)std::max<int64_t>(n_lin, 1)); room(rc, w.d_sloff, nrun); }
+    if (rc == PC_OK) rc = w.d_lin_base.upload(out.lin_start, st);
+    if (rc != PC_OK) return rc;
+    if (!n_runs) { drained.armed = false; return PC_OK; }   // (nothing queued but the upload of lin_start, which `out` outlives)
+    hipLaunchKernelGGL(k_idx_runs, dim3(w.g256p), dim3(256), 0, st, w.d_key.p, w.d_voff.p, w.d_head.p, w.d_slot.p, nrec, d_run_key.p, d_run_beg.p, d_run_end.p);
+    std::iota(iota.begin(), iota.end(), 0u);
+    HIP_TRY(hipMemcpyAsync(d_order.p, iota.data(), (size_t)n_runs * 4, hipMemcpyHostToDevice, st));
+    const int key_bits = bh::index_key_bits((uint64_t)n_ref);
+    size_t sort_bytes = 0;
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st));
+    PC_TRY(d_sort_tmp.reserve(std::max<size_t>(sort_bytes, 16)));
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, sort_bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st));
+    hipLaunchKernelGGL(k_idx_gather, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, d_run_key2.p, d_order2.p, d_run_beg.p, d_run_end.p, n_runs,
+                       w.d_stid.p, w.d_sbin.p, w.d_sbeg.p, w.d_send.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (iota and the sort's scratch go out of scope)
+    drained.armed = false;
+    return PC_OK;
+}
+
+// Step 3: the linear windows; CSI: the forward fill (one running maximum over the windows of all references), then loff per run.
+int index_windows(BamDecode &d, int64_t nrec, int n_ref, const IndexShape &shape, IndexWork &w) {
+    using namespace pcidx;
+    hipStream_t st = d.st;
+    const int64_t n_runs = w.n_runs, n_lin = w.n_lin;
+    DevBuf<uint8_t> d_fill_tmp;   // (the scan's scratch: alive up to the synchronisation below)
+    DrainOnExit drained{st};
+    if (n_lin) {
+        HIP_TRY(hipMemsetAsync(w.d_linear.p, 0, (size_t)n_lin * 8, st));
+        hipLaunchKernelGGL(k_idx_linear, dim3(w.t.g256), dim3(256), 0, st, w.d_cov.p, w.d_covered.p, w.d_win_a.p, w.d_voff.p, nrec, w.d_lin_base.p, w.d_linear.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (shape.csi && n_runs) {
+        if (n_lin) {
+            hipLaunchKernelGGL(k_idx_first_window, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), 0, st, n_ref, w.d_n_intv.p, w.d_lin_base.p, w.d_ref_be.p, w.d_linear.p);
+            HIP_TRY(hipGetLastError());
+            size_t fill_bytes = 0;
+            HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, fill_bytes, w.d_linear.p, w.d_filled.p, hipcub::Max(), (int)n_lin, st));
+            PC_TRY(d_fill_tmp.reserve(std::max<size_t>(fill_bytes, 16)));
+            HIP_TRY(hipcub::DeviceScan::InclusiveScan(d_fill_tmp.p, fill_bytes, w.d_linear.p, w.d_filled.p, hipcub::Max(), (int)n_lin, st));
+        }
+        hipLaunchKernelGGL(k_idx_loff, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, w.d_stid.p, w.d_sbin.p, n_runs, shape.n_lvls, w.d_n_intv.p,
+                           w.d_lin_base.p, w.d_filled.p, w.d_sloff.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    return PC_OK;
+}
+
+// Step 4: the sorted runs and the linear arrays (BAI) or the runs' loff (CSI: the windows stay in HBM) come down.
+int index_read_back(BamDecode &d, const IndexShape &shape, IndexWork &w, IndexParts &out) {
+    hipStream_t st = d.st;
+    const size_t n_runs = (size_t)w.n_runs, n_lin = (size_t)w.n_lin;
+    out.run_tid.resize(n_runs); out.run_bin.resize(n_runs); out.run_beg.resize(n_runs); out.run_end.resize(n_runs);
+    if (shape.csi) out.run_loff.resize(n_runs);
+    else out.linear.resize(n_lin);
+    DrainOnExit drained{st};
+    if (n_runs) {
+        HIP_TRY(hipMemcpyAsync(out.run_tid.data(), w.d_stid.p, n_runs * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.run_bin.data(), w.d_sbin.p, n_runs * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.run_beg.data(), w.d_sbeg.p, n_runs * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out.run_end.data(), w.d_send.p, n_runs * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (shape.csi) { if (n_runs) HIP_TRY(hipMemcpyAsync(out.run_loff.data(), w.d_sloff.p, n_runs * 8, hipMemcpyDeviceToHost, st)); }
+    else if (n_lin) HIP_TRY(hipMemcpyAsync(out.linear.data(), w.d_linear.p, n_lin * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    return PC_OK;
+}
+
+// The index build's phase 5 (whole-file reads only): k_bam_fields and the order checks as decode_columns runs them -- no
+// column is written or read back -- then the kernels of index_kernels.hip.h; the sorted runs, the linear arrays (BAI) or
+// the runs' loff (CSI) and the per-reference counts come down.
+int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader &h, const BamRecords &recs, const IndexShape &shape, IndexParts &out) {
+    hipStream_t st = d.st;
     const int64_t nrec = recs.nrec;
     const int n_ref = (int)h.n_ref;
     const auto t0 = std::chrono::steady_clock::now();
@@ -884,180 +843,27 @@ int index_records(BamDecode &d, const BamPlan &pl, int64_t size, const BamHeader
     out.lin_start.assign((size_t)n_ref + 1, 0);
     out.ref_beg.assign((size_t)n_ref, 0); out.ref_end.assign((size_t)n_ref, 0);
     out.ref_mapped.assign((size_t)n_ref, 0); out.ref_unmapped.assign((size_t)n_ref, 0);
-    if (nrec == 0) {
-        if (recs.truncated) return fail(PC_ERR_ARG, "truncated BAM record");
-        return PC_OK;
-    }
-    // where bgzf_tell places a stream position (bgzf.c:569-572): per member, the file offset of the first gzip header whose
-    // payload begins where the member's does -- an empty member in front of it, if there is one -- and of its own header; the
-    // end of the stream lies in the first member behind the last payload (the EOF block), or at the end of the file
-    std::vector<uint64_t> blk(2 * (size_t)nm + 2);
-    {
-        uint64_t prev_end = 0;
-        for (int m = 0; m < nm; ++m) {
-            const Member &mb = pl.members[(size_t)m];
-            const uint64_t own = mb.coff - mb.hdr;
-            blk[2 * (size_t)m] = std::min(prev_end, own); blk[2 * (size_t)m + 1] = own;
-            prev_end = mb.coff + mb.clen + 8;
-        }
-        blk[2 * (size_t)nm] = blk[2 * (size_t)nm + 1] = std::min<uint64_t>(prev_end, (uint64_t)size);
-    }
-    DevBuf<uint64_t> d_rec_base, d_blk, d_key, d_voff, d_cov, d_covered;
-    DevBuf<uint32_t> d_rec_member, d_placed, d_mapped, d_mapped_before, d_head, d_slot;
-    DevBuf<int32_t> d_win_a;
-    DevBuf<RecOut> d_recs;
-    DevBuf<unsigned long long> d_misc;   // [0] first error (index << 8 | code); [1] (as uint32) a record reaches beyond 2^29
-    DevBuf<int64_t> d_ref_fl;            // first record of every reference, then the last
-    const size_t n1 = (size_t)nrec + 1, nr = (size_t)std::max(n_ref, 1);
-    int rc = d_misc.reserve(2);
-    room(rc, d_recs, (size_t)nrec); room(rc, d_placed, 1);
-    room(rc, d_key, (size_t)nrec); room(rc, d_voff, n1); room(rc, d_cov, n1); room(rc, d_covered, n1); room(rc, d_win_a, (size_t)nrec);
-    room(rc, d_mapped, n1); room(rc, d_mapped_before, n1); room(rc, d_head, n1); room(rc, d_slot, n1); room(rc, d_ref_fl, 2 * nr);
-    if (rc == PC_OK) rc = d_rec_base.upload(recs.rec_base, st);
-    const std::vector<uint32_t> rec_member = group_members(recs.rec_base, nrec, nm);
-    if (rc == PC_OK) rc = d_rec_member.upload(rec_member, st);
-    if (rc == PC_OK) rc = d_blk.upload(blk, st);
-    if (rc != PC_OK) return rc;
-    const unsigned long long misc0[2] = {~0ull, 0ull};
-    HIP_TRY(hipMemcpyAsync(d_misc.p, misc0, sizeof(misc0), hipMemcpyHostToDevice, st));
-    const unsigned g256 = (unsigned)((nrec + 255) / 256), g256p = (unsigned)((nrec + 1 + 255) / 256);
-    hipLaunchKernelGGL(k_bam_fields, dim3(g256), dim3(256), 0, st, d.d_stream.p, pl.total_u, d.d_members.p, d_rec_base.p, d.d_chain.p, d.d_rec_off.p, nm, nrec,
-                       h.n_ref, d_rec_member.p, d_recs.p);
-    hipLaunchKernelGGL(k_bam_order, dim3(g256), dim3(256), 0, st, d_recs.p, nrec, d_placed.p, d_misc.p);
-    HIP_TRY(hipGetLastError());
-    unsigned long long misc[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(misc, d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
+    if (nrec == 0) return record_defect(~0ull, recs.truncated, d.path.c_str());
+    IndexWork w;
+    unsigned long long first_err = ~0ull;
+    DrainOnExit drained{st};
+    // (misc: [1] (as uint32) a record reaches beyond the index's range)
+    PC_TRY(decode_fields(d, pl, h, recs, 2, 1, false, w.t));
+    PC_TRY(w.reserve(nrec, n_ref));   // (behind the record table, as ever: the pool hands the blocks out in this order)
+    w.blk = bh::tell_table(pl.members, size);
+    PC_TRY(w.d_blk.upload(w.blk, st));
+    HIP_TRY(hipMemcpyAsync(&first_err, w.t.d_misc.p, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     out.ms_fields = ms_since(t0);
-    if (misc[0] != ~0ull) {   // the decoder's own refusals, in its order
-        rc = record_defect((int)(misc[0] & 0xffu), d.path.c_str());
-        return rc != PC_OK ? rc : fail(PC_ERR_ARG, "truncated BAM record");
-    }
-    if (recs.truncated) return fail(PC_ERR_ARG, "truncated BAM record");
+    PC_TRY(record_defect(first_err, recs.truncated, d.path.c_str()));   // the decoder's own refusals, in its order
     const auto t1 = std::chrono::steady_clock::now();
-    // ---- keys, runs, per-reference bounds, covered windows
-    const auto idx_keys = shape.csi ? k_idx_keys<false> : k_idx_keys<true>;
-    hipLaunchKernelGGL(idx_keys, dim3(g256p), dim3(256), 0, st, d.d_stream.p, d.d_members.p, d_blk.p, d_rec_base.p, d.d_rec_off.p, nm, nrec, d_rec_member.p,
-                       d_recs.p, d_key.p, d_voff.p, d_win_a.p, d_cov.p, d_mapped.p, (uint32_t *)(d_misc.p + 1), shape.min_shift, shape.n_lvls);
-    HIP_TRY(hipMemsetAsync(d_ref_fl.p, 0xff, 2 * nr * sizeof(int64_t), st));
-    hipLaunchKernelGGL(k_idx_heads, dim3(g256p), dim3(256), 0, st, d_key.p, nrec, d_head.p, d_ref_fl.p, d_ref_fl.p + nr);
-    HIP_TRY(hipGetLastError());
-    DevBuf<uint8_t> d_tmp;
-    {
-        size_t a = 0, b = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, a, d_head.p, d_slot.p, (int)n1, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, b, d_cov.p, d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st));
-        size_t tmp_bytes = std::max<size_t>(std::max(a, b), 16);
-        rc = d_tmp.reserve(tmp_bytes);
-        if (rc != PC_OK) return rc;
-        a = b = tmp_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, a, d_head.p, d_slot.p, (int)n1, st));
-        a = tmp_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, a, d_mapped.p, d_mapped_before.p, (int)n1, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(d_tmp.p, b, d_cov.p, d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st));
-    }
-    DevBuf<uint64_t> d_ref_be;     // per reference: offset of its first record, then of the first record behind its last
-    DevBuf<int64_t> d_ref_cnt;     // mapped, then unmapped
-    DevBuf<int32_t> d_n_intv;
-    room(rc, d_ref_be, 2 * nr); room(rc, d_ref_cnt, 2 * nr); room(rc, d_n_intv, nr);
-    if (rc != PC_OK) return rc;
-    std::vector<int32_t> n_intv((size_t)n_ref, 0);
-    uint32_t n_runs32 = 0;
-    if (n_ref) {
-        hipLaunchKernelGGL(k_idx_ref_stats, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), 0, st, n_ref, d_ref_fl.p, d_ref_fl.p + nr, d_voff.p, d_mapped_before.p,
-                           d_covered.p, d_ref_be.p, d_ref_be.p + nr, d_ref_cnt.p, d_ref_cnt.p + nr, d_n_intv.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(n_intv.data(), d_n_intv.p, (size_t)n_ref * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out.ref_beg.data(), d_ref_be.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out.ref_end.data(), d_ref_be.p + nr, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out.ref_mapped.data(), d_ref_cnt.p, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out.ref_unmapped.data(), d_ref_cnt.p + nr, (size_t)n_ref * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIP_TRY(hipMemcpyAsync(&n_runs32, d_slot.p + nrec, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(misc, d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if ((uint32_t)misc[1]) {
-        if (!shape.csi) return fail(PC_ERR_ARG, "a BAI index cannot hold %s: an alignment reaches beyond 2^29", d.path.c_str());
-        return fail(PC_ERR_ARG, "a CSI index of min_shift %d and depth %d cannot hold %s: an alignment reaches beyond %lld", shape.min_shift, shape.n_lvls,
-                    d.path.c_str(), (long long)shape.reach());
-    }
-    int64_t placed = 0;
-    for (int t = 0; t < n_ref; ++t) {
-        out.lin_start[(size_t)t + 1] = out.lin_start[(size_t)t] + n_intv[(size_t)t];
-        placed += out.ref_mapped[(size_t)t] + out.ref_unmapped[(size_t)t];
-    }
-    out.n_no_coor = nrec - placed;
-    const int64_t n_runs = (int64_t)n_runs32, n_lin = out.lin_start[(size_t)n_ref];
-    out.n_windows = n_lin;
-    if (shape.csi && n_lin > kMaxWindows)
-        return fail(PC_ERR_ARG, "a CSI index of min_shift %d of %s has %lld windows, more than 2^28: use a larger min_shift", shape.min_shift, d.path.c_str(),
-                    (long long)n_lin);
-    // ---- the runs in (tid, bin) order, the linear windows
-    DevBuf<uint64_t> d_run_key, d_run_key2, d_run_beg, d_run_end, d_sbeg, d_send, d_linear, d_filled, d_sloff;
-    DevBuf<uint32_t> d_order, d_order2, d_sbin;
-    DevBuf<int32_t> d_stid;
-    DevBuf<int64_t> d_lin_base;
-    const size_t nrun = (size_t)std::max<int64_t>(n_runs, 1);
-    room(rc, d_run_key, nrun); room(rc, d_run_key2, nrun); room(rc, d_run_beg, nrun); room(rc, d_run_end, nrun); room(rc, d_sbeg, nrun); room(rc, d_send, nrun);
-    room(rc, d_order, nrun); room(rc, d_order2, nrun); room(rc, d_sbin, nrun); room(rc, d_stid, nrun);
-    room(rc, d_linear, (size_t)std::max<int64_t>(n_lin, 1));
-    if (shape.csi) { room(rc, d_filled, (size_t)std::max<int64_t>(n_lin, 1)); room(rc, d_sloff, nrun); }
-    if (rc == PC_OK) rc = d_lin_base.upload(out.lin_start, st);
-    if (rc != PC_OK) return rc;
-    out.run_tid.resize((size_t)n_runs); out.run_bin.resize((size_t)n_runs); out.run_beg.resize((size_t)n_runs); out.run_end.resize((size_t)n_runs);
-    if (shape.csi) out.run_loff.resize((size_t)n_runs);
-    else out.linear.resize((size_t)n_lin);
-    if (n_runs) {
-        hipLaunchKernelGGL(k_idx_runs, dim3(g256p), dim3(256), 0, st, d_key.p, d_voff.p, d_head.p, d_slot.p, nrec, d_run_key.p, d_run_beg.p, d_run_end.p);
-        // (hipcub's iota: the slots 0 .. n_runs - 1 are the values of the sort)
-        std::vector<uint32_t> iota((size_t)n_runs);
-        std::iota(iota.begin(), iota.end(), 0u);
-        HIP_TRY(hipMemcpyAsync(d_order.p, iota.data(), (size_t)n_runs * 4, hipMemcpyHostToDevice, st));
-        int key_bits = 32;   // bin below, then as many bits as the reference ids take
-        while (key_bits < 64 && ((uint64_t)n_ref >> (key_bits - 32))) ++key_bits;
-        size_t sort_bytes = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st));
-        DevBuf<uint8_t> d_sort_tmp;
-        rc = d_sort_tmp.reserve(std::max<size_t>(sort_bytes, 16));
-        if (rc != PC_OK) { (void)hipStreamSynchronize(st); return rc; }
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, sort_bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st));
-        hipLaunchKernelGGL(k_idx_gather, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, d_run_key2.p, d_order2.p, d_run_beg.p, d_run_end.p, n_runs,
-                           d_stid.p, d_sbin.p, d_sbeg.p, d_send.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));   // (iota and the sort's scratch go out of scope)
-    }
-    if (n_lin) {
-        HIP_TRY(hipMemsetAsync(d_linear.p, 0, (size_t)n_lin * 8, st));
-        hipLaunchKernelGGL(k_idx_linear, dim3(g256), dim3(256), 0, st, d_cov.p, d_covered.p, d_win_a.p, d_voff.p, nrec, d_lin_base.p, d_linear.p);
-        HIP_TRY(hipGetLastError());
-    }
-    DevBuf<uint8_t> d_fill_tmp;   // (the scan's scratch: alive up to the synchronisation below)
-    if (shape.csi && n_runs) {   // the forward fill (one running maximum over the windows of all references), then loff per run
-        if (n_lin) {
-            hipLaunchKernelGGL(k_idx_first_window, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), 0, st, n_ref, d_n_intv.p, d_lin_base.p, d_ref_be.p, d_linear.p);
-            HIP_TRY(hipGetLastError());
-            size_t fill_bytes = 0;
-            HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, fill_bytes, d_linear.p, d_filled.p, hipcub::Max(), (int)n_lin, st));
-            rc = d_fill_tmp.reserve(std::max<size_t>(fill_bytes, 16));
-            if (rc != PC_OK) { (void)hipStreamSynchronize(st); return rc; }
-            HIP_TRY(hipcub::DeviceScan::InclusiveScan(d_fill_tmp.p, fill_bytes, d_linear.p, d_filled.p, hipcub::Max(), (int)n_lin, st));
-        }
-        hipLaunchKernelGGL(k_idx_loff, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, d_stid.p, d_sbin.p, n_runs, shape.n_lvls, d_n_intv.p,
-                           d_lin_base.p, d_filled.p, d_sloff.p);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    PC_TRY(index_keys_and_stats(d, pl, h, recs, shape, w, out));
+    PC_TRY(index_sort_runs(d, recs, n_ref, shape, w, out));
+    PC_TRY(index_windows(d, nrec, n_ref, shape, w));
     out.ms_kernels = ms_since(t1);
     const auto t2 = std::chrono::steady_clock::now();
-    if (n_runs) {
-        HIP_TRY(hipMemcpyAsync(out.run_tid.data(), d_stid.p, (size_t)n_runs * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out.run_bin.data(), d_sbin.p, (size_t)n_runs * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out.run_beg.data(), d_sbeg.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(out.run_end.data(), d_send.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (shape.csi) { if (n_runs) HIP_TRY(hipMemcpyAsync(out.run_loff.data(), d_sloff.p, (size_t)n_runs * 8, hipMemcpyDeviceToHost, st)); }
-    else if (n_lin) HIP_TRY(hipMemcpyAsync(out.linear.data(), d_linear.p, (size_t)n_lin * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    PC_TRY(index_read_back(d, shape, w, out));
+    drained.armed = false;
     out.ms_readback = ms_since(t2);
     d.clk.lap("fields + index kernels + read-back");
     return PC_OK;
@@ -1077,8 +883,8 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     PoolScope pool_scope(&e->pool);   // (the decoder's scratch -- image, inflated stream, record table -- is recycled through the engine's pool)
     BamDecode d{e, e->stream, name ? name : "<memory>", knobs};
     BamPlan pl;
-    int rc = plan_members(image, size, span, d.path.c_str(), knobs.walk_min, pl);
-    if (rc != PC_OK) return rc;
+    const int defect = bh::plan_members(image, size, span, knobs.walk_min, pl);
+    if (defect) return host_defect(defect, d.path.c_str());
     pc_bam *b = new pc_bam();
     d.clk.lap("member walk");
     b->e = e; b->name = d.path; b->members = (int64_t)pl.nm(); b->inflated_bytes = (int64_t)pl.total_u; b->compressed_bytes = size;
@@ -1086,7 +892,7 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     struct Guard { pc_bam *b; ~Guard() { if (b) pc_bam_close(b); } } guard{b};
     for (auto &x : d.ev) HIP_TRY(hipEventCreate(&x));
     struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]); } } evg{d.ev};
-    rc = upload_and_inflate(d, image, pl, uploaded);
+    int rc = upload_and_inflate(d, image, pl, uploaded);
     if (rc != PC_OK) return rc;
     BamHeader h;
     rc = read_header(d, pl, size, span, h);
@@ -1119,12 +925,12 @@ static int bam_index_impl(pc_engine *e, const void *image_, int64_t size, const 
     PoolScope pool_scope(&e->pool);
     BamDecode d{e, e->stream, name ? name : "<memory>", knobs};
     BamPlan pl;
-    int rc = plan_members(image, size, nullptr, d.path.c_str(), knobs.walk_min, pl);
-    if (rc != PC_OK) return rc;
+    const int defect = bh::plan_members(image, size, nullptr, knobs.walk_min, pl);
+    if (defect) return host_defect(defect, d.path.c_str());
     d.clk.lap("member walk");
     for (auto &x : d.ev) HIP_TRY(hipEventCreate(&x));
     struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]); } } evg{d.ev};
-    rc = upload_and_inflate(d, image, pl, uploaded);
+    int rc = upload_and_inflate(d, image, pl, uploaded);
     if (rc != PC_OK) return rc;
     BamHeader h;
     rc = read_header(d, pl, size, nullptr, h);

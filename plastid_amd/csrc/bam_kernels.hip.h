@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bam_host.h"   // pcbam::Member, pcbam::MemberChain
+
 namespace pcbam {
 
 constexpr int kInflWG = 64;                 // one wave per BGZF member
@@ -48,15 +50,6 @@ constexpr int kLitEntries = 852, kDistEntries = 592;
 constexpr int kInBytes = PC_BGZF_IN;       // compressed input staged in LDS (two halves)
 constexpr uint32_t kInHalf = kInBytes / 2;
 constexpr int kFlush = kWinBytes / 4;       // the window goes to HBM in pieces of this size
-
-struct Member {
-    uint64_t coff;     // offset of the raw DEFLATE stream in the file image (behind the gzip header)
-    uint32_t clen;     // its length (the 8-byte trailer excluded)
-    uint32_t ulen;     // ISIZE: bytes it inflates to
-    uint64_t uoff;     // where they go in the inflated stream
-    uint32_t crc;      // CRC-32 of the payload (gzip trailer)
-    uint32_t hdr;      // bytes of its gzip header (host side: the member starts at coff - hdr in the file)
-};
 
 // error codes of k_bgzf_inflate (per member)
 enum { kInfOk = 0, kInfBadBlockType = 1, kInfBadStored = 2, kInfBadCodeLengths = 3, kInfOverSubscribed = 4, kInfBadSymbol = 5,
@@ -795,13 +788,6 @@ __device__ __forceinline__ bool plausible_record(const uint8_t *q, uint64_t avai
 
 constexpr int kMaxRecPerMember = 1824;   // 65536 / 36 + 3: a record takes at least 36 bytes of the stream
 constexpr int kGuessChain = 3;           // records in a row that have to look like records
-
-struct MemberChain {
-    uint64_t first;      // stream offset of the first record start at or behind the member's begin (guessed or given)
-    uint64_t next;       // where the chain from `first` leaves the member: the first record start at or behind its end
-    uint32_t nrec;       // record starts in [first, member end)
-    uint32_t flags;      // 1: no plausible start found, 2: a length prefix below the fixed fields met on the way
-};
 
 // One wave per member.  forced[m] != ~0: start there instead of guessing (the host found that the preceding member's
 // chain ends there).  rec_off[m * kMaxRecPerMember + k] = offset of record k relative to the member's begin.

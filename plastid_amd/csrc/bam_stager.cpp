@@ -32,6 +32,7 @@
 #include <unistd.h>
 #include <vector>
 
+#include "bam_host.h"
 #include "index_shape.h"
 
 namespace {
@@ -42,11 +43,14 @@ int fail(const std::string &m) {
     return -1;
 }
 
+namespace bh = pcbamhost;   // the member and header parsers both decoders use
+
 struct Block {
     size_t coff;   // offset of the gzip member in the file
     uint32_t clen; // compressed member length
     uint32_t ulen; // uncompressed length (ISIZE)
     size_t uoff;   // offset in the inflated stream
+    uint32_t hdr;  // bytes of its gzip header (0: the member has no room for header and trailer)
 };
 
 // Records decoded from one contiguous piece of the inflated stream (the pieces are decoded in
@@ -240,29 +244,14 @@ struct FileMap {
 };
 
 int scan_blocks(const FileMap &file, std::vector<Block> &blocks, size_t &total_u) {
-    size_t off = 0;
     total_u = 0;
-    while (off < file.size()) {
-        if (off + 18 > file.size()) return fail("truncated BGZF header");
-        const uint8_t *h = file.data() + off;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return fail("not a BGZF file (bad gzip member header)");
-        const uint16_t xlen = rd16(h + 10);
-        if (off + 12 + xlen > file.size()) return fail("truncated BGZF extra field");
-        int bsize = -1;
-        for (size_t x = 0; x + 4 <= xlen;) {
-            const uint8_t *sf = h + 12 + x;
-            const uint16_t slen = rd16(sf + 2);
-            if (sf[0] == 'B' && sf[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = rd16(sf + 4);   // (the two payload bytes lie inside the extra field)
-            x += 4 + slen;
-        }
-        if (bsize < 0) return fail("BGZF member without BC subfield");
-        const size_t clen = (size_t)bsize + 1;
-        if (off + clen > file.size()) return fail("truncated BGZF member");
-        const uint32_t isize = rd32(file.data() + off + clen - 4);
-        if (isize > (1u << 16)) return fail("corrupt BGZF member (more than 64 KiB of payload)");
-        blocks.push_back({off, (uint32_t)clen, isize, total_u});
-        total_u += isize;
-        off += clen;
+    for (int64_t off = 0, clen = 0; off < (int64_t)file.size(); off += clen) {
+        bh::Member mb;
+        mb.hdr = 0;
+        const int code = bh::parse_member(file.data(), (int64_t)file.size(), off, mb, clen);
+        if (code && code != bh::kMemberTiny) return fail(bh::defect_text(code));   // (kMemberTiny: inflate_block refuses it)
+        blocks.push_back({(size_t)off, (uint32_t)clen, mb.ulen, total_u, mb.hdr});
+        total_u += mb.ulen;
     }
     return 0;
 }
@@ -322,9 +311,8 @@ int raw_inflate(const uint8_t *in, size_t in_n, uint8_t *out, size_t out_n, uint
 int inflate_block(const FileMap &file, const Block &b, uint8_t *dst) {
     if (b.ulen == 0) return 0;
     const uint8_t *h = file.data() + b.coff;
-    const size_t hdr = 12 + rd16(h + 10);
-    if (b.clen < hdr + 8) return -1;
-    return raw_inflate(h + hdr, b.clen - hdr - 8, dst, b.ulen, rd32(h + b.clen - 8));
+    if (!b.hdr) return -1;
+    return raw_inflate(h + b.hdr, b.clen - b.hdr - 8, dst, b.ulen, rd32(h + b.clen - 8));
 }
 
 // PB_TIMING=1: print the phases of a load to stderr
@@ -343,28 +331,14 @@ struct Lap {
 // need_more (optional): set when the buffer ends inside the header (a caller that inflates lazily
 // fetches more and retries) instead of reporting truncation.
 int parse_header(Bam &bam, const uint8_t *&p, const uint8_t *end, uint32_t &n_ref_out, bool *need_more = nullptr) {
-    auto trunc = [&](const char *what) { if (need_more) { *need_more = true; return -1; } return fail(what); };
-    if (end - p < 12) return trunc("not a BAM file (bad magic)");
-    if (std::memcmp(p, "BAM\1", 4) != 0) return fail("not a BAM file (bad magic)");
-    const uint32_t l_text = rd32(p + 4);
-    p += 8;
-    if ((size_t)(end - p) < (size_t)l_text + 4) return trunc("truncated BAM header");
-    p += l_text;
-    const uint32_t n_ref = rd32(p);
-    p += 4;
-    bam.ref_names.clear();
-    bam.ref_lengths.clear();
-    for (uint32_t r = 0; r < n_ref; ++r) {
-        if (end - p < 4) return trunc("truncated BAM reference list");
-        const uint32_t l_name = rd32(p);
-        p += 4;
-        if ((size_t)(end - p) < (size_t)l_name + 4) return trunc("truncated BAM reference list");
-        bam.ref_names.emplace_back(reinterpret_cast<const char *>(p), l_name ? l_name - 1 : 0);
-        p += l_name;
-        bam.ref_lengths.push_back((int32_t)rd32(p));
-        p += 4;
-    }
-    n_ref_out = n_ref;
+    bh::BamHeader h;
+    const bh::HeaderParse hp = bh::parse_bam_header(p, (size_t)(end - p), h);
+    if (hp.status == bh::kHeaderMore && need_more) { *need_more = true; return -1; }
+    if (hp.status != bh::kHeaderOk) return fail(hp.text);
+    bam.ref_names = std::move(h.ref_names);
+    bam.ref_lengths = std::move(h.ref_lengths);
+    n_ref_out = h.n_ref;
+    p += h.first_record;
     return 0;
 }
 
@@ -1015,33 +989,24 @@ using pcshape::IndexShape;   // the shape of a loaded index: BAI is (14, 5); a C
 // the BGZF member at file offset `coff`, inflated and appended to `out`; returns its compressed
 // length, 0 at end of file, -1 on a damaged member
 long read_member(FILE *f, uint64_t coff, std::vector<uint8_t> &out) {
-    uint8_t h[18];
+    thread_local std::vector<uint8_t> buf;   // the member as it is in the file: its first 18 bytes say how long it is
     if (fseeko(f, (off_t)coff, SEEK_SET) != 0) return -1;
-    const size_t got = fread(h, 1, 18, f);
+    buf.resize(18);
+    size_t got = fread(buf.data(), 1, 18, f);
     if (got == 0) return 0;
-    if (got < 18 || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return -1;
-    const uint16_t xlen = rd16(h + 10);
-    std::vector<uint8_t> member((size_t)12 + xlen);
-    std::memcpy(member.data(), h, std::min<size_t>(18, member.size()));
-    if (member.size() > 18 && fread(member.data() + 18, 1, member.size() - 18, f) != member.size() - 18) return -1;
-    int bsize = -1;
-    for (size_t x = 0; x + 4 <= xlen;) {
-        const uint8_t *sf = member.data() + 12 + x;
-        const uint16_t slen = rd16(sf + 2);
-        if (sf[0] == 'B' && sf[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = rd16(sf + 4);
-        x += 4 + (size_t)slen;
+    bh::Member mb;
+    int64_t clen = 0;
+    int code = bh::parse_member(buf.data(), (int64_t)got, 0, mb, clen);
+    if (code == bh::kMemberExtraCut) clen = (int64_t)1 << 16;   // (subfields in front of BC: as much as a member can be)
+    if ((code == bh::kMemberCut || code == bh::kMemberExtraCut) && got == 18) {   // the rest of it, and the same parse again
+        buf.resize((size_t)clen);
+        got += fread(buf.data() + 18, 1, (size_t)clen - 18, f);
+        code = bh::parse_member(buf.data(), (int64_t)got, 0, mb, clen);
     }
-    if (bsize < 0) return -1;
-    const size_t clen = (size_t)bsize + 1, hdr = (size_t)12 + xlen;
-    if (clen < hdr + 8) return -1;
-    std::vector<uint8_t> rest(clen - hdr);
-    // (the header bytes beyond 12 + xlen that were read with the first 18 belong to the payload)
-    if (fseeko(f, (off_t)(coff + hdr), SEEK_SET) != 0 || fread(rest.data(), 1, rest.size(), f) != rest.size()) return -1;
-    const uint32_t isize = rd32(rest.data() + rest.size() - 4), crc = rd32(rest.data() + rest.size() - 8);
-    if (isize > (1u << 16)) return -1;
+    if (code != bh::kOk) return -1;
     const size_t at = out.size();
-    out.resize(at + isize);
-    if (isize && raw_inflate(rest.data(), rest.size() - 8, out.data() + at, isize, crc) != 0) return -1;
+    out.resize(at + mb.ulen);
+    if (mb.ulen && raw_inflate(buf.data() + mb.coff, mb.clen, out.data() + at, mb.ulen, mb.crc) != 0) return -1;
     return (long)clen;
 }
 
@@ -1351,26 +1316,6 @@ int decode_regions(Bam &bam, int nthreads, int nreg, const char *const *rname, c
     lap("filter");
     bam.loaded = true;
     return 0;
-}
-
-// CPUs this process may actually use: the smaller of the hardware threads, the affinity mask and the
-// container's CFS quota (cgroup v2 cpu.max / v1 cpu.cfs_quota_us).  Pools sized beyond the quota only
-// burn it in bursts and are then throttled as a whole.
-static int usable_cpus() {
-    unsigned n = std::max(1u, std::thread::hardware_concurrency());
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) n = std::min<unsigned>(n, (unsigned)std::max(1, CPU_COUNT(&set)));
-    long long quota = -1, period = -1;
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-        char q[32] = {0};
-        if (fscanf(f, "%31s %lld", q, &period) == 2 && std::strcmp(q, "max") != 0) quota = atoll(q);
-        fclose(f);
-    } else {
-        if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) { if (fscanf(g, "%lld", &quota) != 1) quota = -1; fclose(g); }
-        if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(g, "%lld", &period) != 1) period = -1; fclose(g); }
-    }
-    if (quota > 0 && period > 0) n = std::min<unsigned>(n, (unsigned)std::max<long long>(1, (quota + period - 1) / period));
-    return (int)n;
 }
 
 // one thread per usable CPU, at most 128 (starting hundreds of threads costs more than they return)

@@ -1,5 +1,5 @@
 // host_util.h -- host-side helpers of the counting engine that do not touch HIP: the worker pool behind
-// parallel_chunks, the galloping lower bound of the plan build, a vector without zero-fill, the host's look at the
+// parallel_chunks, the CPUs a process may use (usable_cpus), the galloping lower bound of the plan build, a vector without zero-fill, the host's look at the
 // contig column of caller-owned records (scan_contigs), the window size of a plan (choose_window), the halo and the
 // linear-index layout of a staged file (choose_halo, lin_layout), the lap clock of PC_STAGE_TIMING.  Plain C++17, so that tests/test_host_logic.py can compile tests/host_util_test.cpp against it on a machine without a GPU.
 #pragma once
@@ -9,12 +9,14 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
 #include <utility>
 #include <vector>
+#include <sched.h>
 #include <unistd.h>
 
 // PC_STAGE_TIMING: the host time between two laps of a staging call or a plan build, on stderr.
@@ -133,7 +135,7 @@ public:
     }
 };
 // (never destroyed: its threads sleep until the process ends -- no joins during static destruction)
-static WorkerPool &worker_pool() { static WorkerPool *p = new WorkerPool; return *p; }
+inline WorkerPool &worker_pool() { static WorkerPool *p = new WorkerPool; return *p; }
 
 // fn(thread index, begin, end) over [0, n) cut into `nthreads` contiguous chunks
 template <typename F> static void parallel_chunks(int64_t n, int nthreads, F fn) {
@@ -150,11 +152,31 @@ template <typename F> static void parallel_chunks(int64_t n, int nthreads, F fn)
     for (auto &x : th) x.join();
 }
 
+// CPUs this process may actually use: the smaller of the hardware threads, the affinity mask and the
+// container's CFS quota (cgroup v2 cpu.max / v1 cpu.cfs_quota_us).  Pools sized beyond the quota only
+// burn it in bursts and are then throttled as a whole.
+inline int usable_cpus() {
+    unsigned n = std::max(1u, std::thread::hardware_concurrency());
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof(set), &set) == 0) n = std::min<unsigned>(n, (unsigned)std::max(1, CPU_COUNT(&set)));
+    long long quota = -1, period = -1;
+    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
+        char q[32] = {0};
+        if (fscanf(f, "%31s %lld", q, &period) == 2 && std::strcmp(q, "max") != 0) quota = atoll(q);
+        fclose(f);
+    } else {
+        if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) { if (fscanf(g, "%lld", &quota) != 1) quota = -1; fclose(g); }
+        if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(g, "%lld", &period) != 1) period = -1; fclose(g); }
+    }
+    if (quota > 0 && period > 0) n = std::min<unsigned>(n, (unsigned)std::max<long long>(1, (quota + period - 1) / period));
+    return (int)n;
+}
+
 // The contig column of caller-owned records, examined where it is: `bounds[t]` = first record of contig t (t = 0 ..
 // ntid) and, returned, the first record whose contig is out of range or lower than its predecessor's (n: none; the
 // bounds then describe the records before it).  Sorted, the column changes value at most ntid times: the pass is a
 // streaming comparison of neighbours, and only a block that holds a change is looked at record by record.
-static int64_t scan_contigs(const int32_t *tid, int64_t n, int32_t ntid, int threads, std::vector<int64_t> &bounds) {
+inline int64_t scan_contigs(const int32_t *tid, int64_t n, int32_t ntid, int threads, std::vector<int64_t> &bounds) {
     bounds.assign((size_t)ntid + 1, 0);
     if (n <= 0) return 0;
     struct Part { std::vector<std::pair<int64_t, int32_t>> changes; int64_t bad = INT64_MAX; };
@@ -205,7 +227,7 @@ static int64_t scan_contigs(const int32_t *tid, int64_t n, int32_t ntid, int thr
 //               (C5: 512 -> 3.38, 640 -> 3.27, 768 -> 3.21, 896 -> 3.21 ms on one box: a third fewer windows outweigh the
 //               fifth workgroup per CU they cost)
 // `knob`: PC_TILE_G, any multiple of 256 up to twice the budget.
-static int choose_window(int rows, int nmodes, unsigned long long n_iv, unsigned long long iv_len, int knob, int64_t *budget) {
+inline int choose_window(int rows, int nmodes, unsigned long long n_iv, unsigned long long iv_len, int knob, int64_t *budget) {
     const int64_t bin_bytes = rows > 1 ? 2 : 4;
     const int64_t g = ((rows > 1 ? 36 : 24) * 1024) / (bin_bytes * nmodes * rows);
     int G = 256;
@@ -231,7 +253,7 @@ static int choose_window(int rows, int nmodes, unsigned long long n_iv, unsigned
 //   slen, tlen aligned lengths the 4-byte stream carries (single-run records inside the halo, up to `stream_max_len`), and
 //              those together with the run stream's (the range of the LDS entry table); 0 / 0: none
 struct StageHalo { int wcap, W, Wg, slen_min, slen_max, tlen_min, tlen_max; };
-static StageHalo choose_halo(const std::vector<int64_t> &span_hist, const std::vector<int64_t> &gap_span_hist,
+inline StageHalo choose_halo(const std::vector<int64_t> &span_hist, const std::vector<int64_t> &gap_span_hist,
                              const std::vector<int64_t> &wide_span_hist, const std::vector<int64_t> &len1_hist, int rmin, int rmax,
                              int64_t n, int stream_max_len) {
     StageHalo h;
@@ -263,7 +285,7 @@ static StageHalo choose_halo(const std::vector<int64_t> &span_hist, const std::v
 // record start (`last_pos`) -- and up to the furthest end of a read of the contig (`tid_end`, exclusive): a long-span
 // read reaches windows beyond every record start, and the later runs of gapped reads start there -- plus one closing
 // entry per contig.  `lin_off[t]` = first entry of contig t (t = 0 .. ntid); returned: entries of every table.
-static size_t lin_layout(const std::vector<int64_t> &tid_bounds, const std::vector<int32_t> &last_pos, const std::vector<int64_t> &tid_end,
+inline size_t lin_layout(const std::vector<int64_t> &tid_bounds, const std::vector<int32_t> &last_pos, const std::vector<int64_t> &tid_end,
                          int shift, std::vector<int64_t> &lin_off) {
     const size_t ntid = last_pos.size();
     lin_off.assign(ntid + 1, 0);

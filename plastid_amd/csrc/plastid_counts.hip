@@ -438,26 +438,6 @@ struct TransferRing {
     }
 };
 
-// CPUs this process may actually use: the smaller of the hardware threads, the affinity mask and the
-// container's CFS quota (cgroup v2 cpu.max / v1 cpu.cfs_quota_us).  Pools sized beyond the quota only
-// burn it in bursts and are then throttled as a whole.
-static int usable_cpus() {
-    unsigned n = std::max(1u, std::thread::hardware_concurrency());
-    cpu_set_t set;
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) n = std::min<unsigned>(n, (unsigned)std::max(1, CPU_COUNT(&set)));
-    long long quota = -1, period = -1;
-    if (FILE *f = fopen("/sys/fs/cgroup/cpu.max", "r")) {
-        char q[32] = {0};
-        if (fscanf(f, "%31s %lld", q, &period) == 2 && std::strcmp(q, "max") != 0) quota = atoll(q);
-        fclose(f);
-    } else {
-        if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r")) { if (fscanf(g, "%lld", &quota) != 1) quota = -1; fclose(g); }
-        if (FILE *g = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r")) { if (fscanf(g, "%lld", &period) != 1) period = -1; fclose(g); }
-    }
-    if (quota > 0 && period > 0) n = std::min<unsigned>(n, (unsigned)std::max<long long>(1, (quota + period - 1) / period));
-    return (int)n;
-}
-
 static int stage_threads(int64_t n) {
     int t = std::min(usable_cpus(), 32);
     if (const char *env = getenv("PC_STAGE_THREADS")) t = std::max(1, atoi(env));

@@ -248,3 +248,41 @@ def test_two_identical_calls_give_identical_arrays(eng, tmp_path):
     chains = tx.chains(limit=60)
     regs = [(c.chrom, c.spanning_segment.start, c.spanning_segment.end) for c in chains[:40]]
     same(read_bam_gpu(path, eng, regions=regs), read_bam_gpu(path, eng, regions=regs))
+
+
+UPLOAD_SETTINGS = {"default": {}, "pieces": {"PC_BAM_PIECE": "7000"}, "pieces.no_ring": {"PC_BAM_PIECE": "7000", "PC_BAM_NO_RING": "1"},
+                   "pieces.one_stream": {"PC_BAM_PIECE": "7000", "PC_BAM_STREAMS": "1"}, "pieces.four_streams": {"PC_BAM_PIECE": "7000", "PC_BAM_STREAMS": "4"}}
+
+
+def test_every_upload_path_of_a_region_read(eng, tmp_path, monkeypatch):
+    """(h) a region read whose image is cut into pieces of a few members: the page-locked ring with pieces that lie in one
+    run and pieces gathered from several short runs, the same pieces straight from the mapping (PC_BAM_NO_RING), and the
+    inflate launches on one, two and four streams -- every setting gives the columns and counts of the default one (one
+    gathered piece) and of the host region reader."""
+    rng = np.random.default_rng(7000)
+    n = 4000
+    tid = np.sort(rng.integers(0, 2, n)).astype(np.int32)
+    pos = rng.integers(0, 190000, n).astype(np.int32)
+    cigars = [("%dM" % L) if k % 7 else ("%dM%dN12M" % (L, 40 + k % 300)) for k, L in enumerate(rng.integers(20, 60, n))]
+    reads = pa.PackedAlignments.from_cigars(tid, pos, cigars, rng.integers(0, 2, n).astype(bool), references=["a", "b"], lengths=[200000, 200000],
+                                            sort=True)
+    path = str(tmp_path / "pieces.bam")
+    indexed_bam(path, reads, 3000)
+    regs = [("a", 60000, 62000), ("a", 150000, 152000), ("b", 100000, 102000)]
+    want = read_bam(path, regions=regs)
+    assert want.n > 20
+    first = None
+    for name, env in UPLOAD_SETTINGS.items():
+        for k in ("PC_BAM_PIECE", "PC_BAM_NO_RING", "PC_BAM_STREAMS"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        timing = {}
+        got = read_bam_gpu(path, eng, regions=regs, timing=timing)
+        same(got, want)
+        assert timing["runs"] >= 3 and timing["uploaded_bytes"] >= 2 * 7000, (name, timing)
+        counts = {k: timing[k] for k in ("runs", "uploaded_bytes", "members", "inflated_bytes")}
+        if first is None:
+            first = (got, counts)
+        same(got, first[0])
+        assert counts == first[1], (name, counts, first[1])

@@ -462,6 +462,34 @@ def test_host_plan_builder(tmp_path):
     assert b"plan_host: ok" in out.stdout
 
 
+def test_bam_decoder_host_logic(tmp_path):
+    """plastid_amd/csrc/bam_host.h is plain C++: the gzip / BGZF member parser and the BAM header parser both decoders
+    use (every defect code from its smallest image, every proper prefix of a header), the GPU decoder's member walk
+    (serial against parallel, false members inside payloads, a defect in the last third) and region plan (runs, chunk
+    positions, rebased offsets and every reason an index does not belong to a file, on a 40-member image with values
+    written out by hand), the piece cutter and the gather of the upload, the bounds and one round of the record chains,
+    and the small tables of the field and index phases -- on BGZF images built by hand, compiled with the host compiler
+    (under the address and undefined-behaviour sanitizers where it has them) and run here."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "bam_host_test")
+    probe = tmp_path / "probe.cpp"
+    probe.write_text("int main() { return 0; }\n")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    if subprocess.call([cxx] + san + [str(probe), "-o", str(tmp_path / "probe")], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL) != 0 \
+            or subprocess.call([str(tmp_path / "probe")]) != 0:
+        san = []
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-pthread"] + san + ["-I", os.path.join(root, "plastid_amd", "csrc"),
+                           os.path.join(root, "tests", "bam_host_test.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+    assert out.returncode == 0, out.stdout.decode()
+    assert b"bam_host: ok" in out.stdout
+
+
 def test_inflate_and_plan_kernels_are_in_the_code_object(tmp_path):
     """Round 4's device code beside the counting kernels: the BGZF inflate kernel in both forms (batch decoder of the
     block symbols, wave-uniform decoder), without scratch memory and with an LDS footprint that leaves eleven waves per
