@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 11
+#define PC_ABI_VERSION 12
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -142,6 +142,13 @@ int64_t pc_num_records(pc_engine *e, int file);
  * reads binned from the side lists are not carried), and counted once.  Equal to pc_num_records when the file keeps no
  * such stream (too few duplicates to be worth its memory).  -1: bad file index. */
 int64_t pc_stream_entries(pc_engine *e, int file);
+/* Entries of the file's CANONICAL stream: one entry per contig, strand and MAPPED position under the current point rule
+ * and size filter (up to 16 reads per entry) -- what a plan over this one file with '+' / '-' segments only streams
+ * under the fiveprime, threeprime and variable rules.  Built at the first count of such a plan, rebuilt when the rule,
+ * the filter or the file's flags change; PC_NO_CANON=1 (read at pc_create / pc_reload_knobs) forbids it.  -1: no such
+ * stream right now (never wanted, forbidden, stale, or not at most 0.9 x the entries of the stream it would replace),
+ * or a bad file index. */
+int64_t pc_canonical_entries(pc_engine *e, int file);
 /* Read objects of a staged file back (the reference hands pysam reads to its callers: get_reads / reads_out,
  * genome_array.py:834-859, and to filter functions, :697-722) -- for files whose records never visited the host
  * (pc_add_alignment_bam[_path | _span]).  pc_read_records: per requested record index its reference id, first aligned

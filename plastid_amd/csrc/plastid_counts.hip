@@ -50,6 +50,7 @@
 #include "plastid_counts.h"
 #include "host_util.h"
 #include "plan_host.h"
+#include "canon_host.h"
 
 using namespace pc;
 
@@ -453,6 +454,18 @@ struct FilterState {
     }
 };
 
+// What a canonical stream was built from (build_canonical_stream): the rule, the size filter, the range of the entry
+// table, the stream words (by their generation) and the stream it was weighed against.
+struct CanonSig {
+    int kind = -1, param = 0, filt_on = 0, filt_min = 0, filt_max = -1, fast_lo = 0, fast_hi = 0, Ws = 0;
+    uint64_t words_gen = 0;
+    std::vector<int32_t> fw, rc;   // the offset tables (variable rule only)
+    bool operator==(const CanonSig &o) const {
+        return kind == o.kind && param == o.param && filt_on == o.filt_on && filt_min == o.filt_min && filt_max == o.filt_max &&
+               fast_lo == o.fast_lo && fast_hi == o.fast_hi && Ws == o.Ws && words_gen == o.words_gen && fw == o.fw && rc == o.rc;
+    }
+};
+
 struct StagedFile {
     int64_t n = 0, nrun = 0, nlong = 0;
     int W = 1;               // max reference span of the records scanned by the window kernels
@@ -482,6 +495,16 @@ struct StagedFile {
     // rules stream the records)
     DevBuf<uint32_t> cstream, clin_tab;
     int64_t cn = -1;
+    uint64_t words_gen = 0;            // counts the rewrites of the stream words (build_compact_stream runs behind every one)
+    // canonical stream (build_canonical_stream): one entry per (strand, mapped position) under ONE rule and size filter,
+    // built at the first count of an eligible plan and kept until `ksig` no longer holds.  kn = its entries, -1: none
+    // (not built, or not worth it under this signature); kid: changes with every build (pc_plan::WorkKey)
+    DevBuf<uint32_t> kstream, klin_tab;
+    DevBuf<int16_t> kshift;
+    int64_t kn = -1;
+    bool ksig_valid = false;
+    CanonSig ksig;
+    uint64_t kid = 0;
     size_t nlin = 0;                   // entries of every linear-index table
     // run stream (aligned runs of multi-run reads with L <= kStreamMaxLen, sorted by contig and run start)
     int64_t nrunrec = 0;
@@ -558,6 +581,7 @@ struct Knobs {
     int no_stream_probe = 0;   // PC_NO_STREAM_PROBE: keep the engine's streams as created (see settle_streams)
     int no_compact = 0;        // PC_NO_COMPACT: no compact stream -- files staged (or re-filtered) from then on are counted record by record (tests compare the two)
     double compact_keep = 0.9; // PC_COMPACT_KEEP: a file that keeps more than this share of its records as entries gets no compact stream (build_compact_stream)
+    int no_canon = 0;          // PC_NO_CANON: no canonical stream -- eligible plans stream what the others do (A/B runs in one build; tests compare the two)
     int no_single = 0;         // PC_NO_SINGLE: one-window plans go through the work lists like any other (tests compare the two paths)
     int plan_build = 0;        // PC_PLAN_BUILD=host|gpu: where pc_plan_create builds the tables (default: on the GPU from 8 192 segments)
     int small_g = 512;         // PC_SMALL_G: queried span a single-wave window may have
@@ -579,6 +603,7 @@ struct Knobs {
         if (const char *env = getenv("PC_SMALL_ROWS")) small_rows = atoi(env);
         no_single = getenv("PC_NO_SINGLE") ? 1 : 0;
         no_compact = getenv("PC_NO_COMPACT") ? 1 : 0;
+        no_canon = getenv("PC_NO_CANON") ? 1 : 0;
         if (const char *env = getenv("PC_COMPACT_KEEP")) compact_keep = std::min(1.0, std::max(0.0, atof(env)));
         no_stream_probe = getenv("PC_NO_STREAM_PROBE") ? 1 : 0;
         hist_memset = getenv("PC_HIST_MEMSET") ? 1 : 0;
@@ -738,8 +763,9 @@ struct pc_plan {
         uint64_t generation = 0;   // engine work_generation (alignments, host-side filters, knobs)
         int nfiles = 0, G = 0, Wg = 0, Ws = 0, Wr = 0, small_g = 0;
         int64_t R = 0, pile = 0, small_n = 0, cap = 0;
+        uint64_t canon = 0;        // StagedFile::kid of the canonical stream the lists index (0: none) -- a rule or filter change rebuilds them
         bool operator==(const WorkKey &o) const {
-            return generation == o.generation && nfiles == o.nfiles && G == o.G && Wg == o.Wg && Ws == o.Ws && Wr == o.Wr &&
+            return canon == o.canon && generation == o.generation && nfiles == o.nfiles && G == o.G && Wg == o.Wg && Ws == o.Ws && Wr == o.Wr &&
                    small_g == o.small_g && R == o.R && pile == o.pile && small_n == o.small_n && cap == o.cap;
         }
     };
@@ -1408,6 +1434,11 @@ int64_t pc_stream_entries(pc_engine *e, int file) {
     const StagedFile *sf = e->files[file];
     return sf->cn >= 0 ? sf->cn : sf->n;
 }
+int64_t pc_canonical_entries(pc_engine *e, int file) {
+    if (!e || file < 0 || file >= (int)e->files.size()) return -1;
+    const StagedFile *sf = e->files[file];
+    return (!e->knobs.no_canon && sf->ksig_valid && sf->ksig.words_gen == sf->words_gen) ? sf->kn : -1;
+}
 
 namespace {
 // PC_STAGE_TIMING=1: print where pc_add_alignment_file spends its time (stderr)
@@ -2020,6 +2051,7 @@ static int propagate_record_flags(pc_engine *e, StagedFile *sf);
 static int build_compact_stream(pc_engine *e, StagedFile *sf, int ntid) {
     using namespace pcstage;
     sf->cn = -1;
+    sf->words_gen += 1;   // (whatever was derived from the words under one rule -- the canonical stream -- is stale)
     const int64_t n = sf->n;
     if (n <= 0 || !sf->nlin || e->knobs.no_compact) { sf->cstream.release(); sf->clin_tab.release(); return PC_OK; }
     PoolScope pool_scope(&e->pool);
@@ -2589,7 +2621,84 @@ void take_work_counts(pc_plan *p) {
     p->work_counts_known = true;
 }
 
-int build_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w) {
+// ---- the canonical stream of the plan's file under the engine's rule and size filter (stage_kernels.hip.h,
+// canon_host.h).  Used by a plan over ONE file, under a point rule without rows (fiveprime, threeprime, variable), whose
+// windows are '+' and '-' only -- a '.' window bins both strands by the forward rule: another grouping -- and only when
+// it has at most `compact_keep` of the entries of the stream it replaces (the compact stream's own rule).  Built at the
+// first count that wants it and kept on the file under its signature: rule, filter, entry-table range, halo and the
+// generation of the stream words.  A steady-state count compares the signature and goes on; a build allocates from the
+// engine's pool and reads the entry total back once.  `canon`: the file's stream when it is to be used, else nullptr.
+int canonical_for_plan(pc_engine *e, pc_plan *p, const CountCall &c, const HistLds &shape, StagedFile **canon) {
+    using namespace pcstage;
+    *canon = nullptr;
+    const bool point = e->kind == PC_MAP_FIVE || e->kind == PC_MAP_THREE || e->kind == PC_MAP_VAR5;
+    if (e->knobs.no_canon || c.nfiles != 1 || !point || p->rows != 1 || (p->modes & ~3u) != 0u || p->modes == 0u) return PC_OK;
+    StagedFile *sf = e->files[0];
+    if (sf->n <= 0 || !sf->nlin) return PC_OK;
+    CanonSig sig;
+    sig.kind = e->kind; sig.param = e->kind == PC_MAP_VAR5 ? 0 : e->param;
+    sig.filt_on = e->filt_on; sig.filt_min = e->filt_on ? e->filt_min : 0; sig.filt_max = e->filt_on ? e->filt_max : -1;
+    sig.fast_lo = shape.fast_lo; sig.fast_hi = shape.fast_hi; sig.Ws = e->Ws(); sig.words_gen = sf->words_gen;
+    if (e->kind == PC_MAP_VAR5) { sig.fw = e->h_fw; sig.rc = e->h_rc; }
+    if (!(sf->ksig_valid && sf->ksig == sig)) {
+        sf->ksig_valid = false;
+        sf->kn = -1;
+        pccanon::RuleIn r;
+        r.kind = e->kind == PC_MAP_FIVE ? 0 : (e->kind == PC_MAP_THREE ? 1 : 3);
+        r.param = e->param; r.table_len = (int)std::min<size_t>((size_t)e->table_len, std::min(e->h_fw.size(), e->h_rc.size()));
+        r.fw = e->h_fw.data(); r.rc = e->h_rc.data();
+        r.filt_on = e->filt_on; r.filt_min = e->filt_min; r.filt_max = e->filt_max;
+        r.fast_lo = shape.fast_lo; r.fast_hi = shape.fast_hi;
+        const pccanon::CanonRule cr = pccanon::canon_rule(r);
+        if (cr.usable && pccanon::canon_fits_halo(cr, sig.Ws)) {
+            PoolScope pool_scope(&e->pool);
+            hipStream_t st = e->stream;
+            const int64_t nlin = (int64_t)sf->nlin;
+            PC_TRY(sf->klin_tab.reserve((size_t)nlin + 1));
+            PC_TRY(sf->kshift.reserve(2 * pccanon::kLenSlots));
+            DevBuf<uint8_t> d_scan;
+            size_t tb = 0;
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, sf->klin_tab.p, sf->klin_tab.p, (int)nlin + 1, st));
+            PC_TRY(d_scan.reserve(std::max<size_t>(tb, 16)));
+            HIP_TRY(hipMemcpyAsync(sf->kshift.p, cr.shift, sizeof(cr.shift), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(sf->klin_tab.p + nlin, 0, 4, st));
+            const int back = pccanon::canon_buckets_back(cr, kLinShift);
+            const uint32_t lc0 = (uint32_t)cr.Lc[0] << 4, lc1 = ((uint32_t)cr.Lc[1] << 4) | 4u;
+            hipLaunchKernelGGL((k_canon_buckets<false>), dim3((unsigned)std::min<int64_t>(nlin, kCanonMaxGrid)), dim3(256), 0, st, sf->stream.p, sf->lin_tab.p, sf->lin_off.p, e->ntid, nlin,
+                               sf->kshift.p, back, lc0, lc1, sf->klin_tab.p, (uint32_t *)nullptr);
+            hipError_t he = hipcub::DeviceScan::ExclusiveSum(d_scan.p, tb, sf->klin_tab.p, sf->klin_tab.p, (int)nlin + 1, st);
+            uint32_t total = 0;
+            if (he == hipSuccess) he = hipMemcpyAsync(&total, sf->klin_tab.p + nlin, 4, hipMemcpyDeviceToHost, st);
+            if (he == hipSuccess) he = hipGetLastError();
+            if (he == hipSuccess) he = hipStreamSynchronize(st);   // (the shift table on the host and the scan's scratch go out of scope)
+            if (he != hipSuccess) return fail(PC_ERR_HIP, "building the canonical stream failed: %s", hipGetErrorString(he));
+            const int64_t replaces = sf->cn >= 0 ? sf->cn : sf->n;
+            if ((double)total <= e->knobs.compact_keep * (double)replaces) {
+                PC_TRY(sf->kstream.reserve((size_t)total + 8));
+                hipLaunchKernelGGL((k_canon_buckets<true>), dim3((unsigned)std::min<int64_t>(nlin, kCanonMaxGrid)), dim3(256), 0, st, sf->stream.p, sf->lin_tab.p, sf->lin_off.p, e->ntid, nlin,
+                                   sf->kshift.p, back, lc0, lc1, sf->klin_tab.p, sf->kstream.p);
+                hipLaunchKernelGGL(k_canon_pad, dim3(1), dim3(64), 0, st, sf->klin_tab.p, nlin, sf->kstream.p);
+                HIP_TRY(hipGetLastError());
+                sf->kn = (int64_t)total;
+            }
+        }
+        if (sf->kn < 0) { sf->kstream.release(); sf->klin_tab.release(); }
+        sf->ksig = sig;
+        sf->ksig_valid = true;
+        sf->kid += 1;
+    }
+    if (sf->kn >= 0) *canon = sf;
+    return PC_OK;
+}
+
+// the view the window kernels get of the plan's first file: its canonical stream in the compact stream's place
+FileView hist_view(pc_engine *e, const StagedFile *canon) {
+    FileView v = e->files[0]->view();
+    if (canon) { v.cstream = canon->kstream.p; v.clin_tab = canon->klin_tab.p; }
+    return v;
+}
+
+int build_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w, const StagedFile *canon) {
     hipStream_t st = e->stream;
     const int ntiles = c.ntiles;
     // the lists of this plan are (re)built: counters and per-tile item counts start from zero (they arrive
@@ -2606,7 +2715,7 @@ int build_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLis
     const int lanes = (nwin * 16 <= e->knobs.ranges_cg16_max && !e->knobs.ranges_cg1) ? 16 : 1;
     dispatch_int<16, 1>(lanes, [&](auto CG) {
         hipLaunchKernelGGL((k_tile_ranges<decltype(CG)::value>), dim3((unsigned)((nwin * lanes + kRangesWG - 1) / kRangesWG)), dim3(kRangesWG), 0, st, p->d_tiles.p, ntiles,
-                           e->files[0]->view(), e->d_files.p, c.nfiles, p->G, e->Wg(), e->Ws(), e->Wr(), w.key.R, w.key.pile, p->d_work.p, p->d_wcounters.p, p->d_tile_items.p, (uint32_t)w.cap,
+                           hist_view(e, canon), e->d_files.p, c.nfiles, p->G, e->Wg(), e->Ws(), e->Wr(), w.key.R, w.key.pile, p->d_work.p, p->d_wcounters.p, p->d_tile_items.p, (uint32_t)w.cap,
                            p->d_work_small.p, w.small_g, w.key.small_n, e->knobs.debug_work, p->d_chain.p, p->d_chain_small.p, e->kind == PC_MAP_STRAT5 ? 1 : 0);
     });
     if (p->hist_lazy)
@@ -2652,10 +2761,10 @@ void choose_grids(pc_engine *e, pc_plan *p, const CountCall &c, WorkLists &w) {
 // sparse windows (single-wave workgroups) and dense ones are two independent launches over
 // disjoint windows: they run side by side on two streams, forked after the work lists exist
 // and joined before the last kernel of the call
-int launch_hist(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w) {
+int launch_hist(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w, const StagedFile *canon) {
     const HistLds &s = w.shape;
     const int nfiles = c.nfiles;
-    const FileView fv0 = e->files[0]->view();
+    const FileView fv0 = hist_view(e, canon);
     const FileView fv1 = nfiles > 1 ? e->files[1]->view() : fv0;
     hipStream_t st = e->stream, st_small = e->side_stream;
     if (w.cap_small) {
@@ -2727,12 +2836,15 @@ int read_work_counts(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLis
 int count_lists(pc_engine *e, pc_plan *p, const CountCall &c) {
     WorkLists w;
     PC_TRY(size_work_lists(e, p, c, w));
-    if (!(p->work_valid && p->work_key == w.key) || e->knobs.debug_work) PC_TRY(build_work_lists(e, p, c, w));
+    StagedFile *canon = nullptr;
+    PC_TRY(canonical_for_plan(e, p, c, w.shape, &canon));
+    w.key.canon = canon ? canon->kid : 0;
+    if (!(p->work_valid && p->work_key == w.key) || e->knobs.debug_work) PC_TRY(build_work_lists(e, p, c, w, canon));
     PC_TRY(mark(e, 2));
     if (w.lds > e->max_lds)
         return fail(PC_ERR_ARG, "pc_count: the window needs %zu bytes of LDS, the device offers %zu per workgroup (too many rows)", w.lds, e->max_lds);
     choose_grids(e, p, c, w);
-    PC_TRY(launch_hist(e, p, c, w));
+    PC_TRY(launch_hist(e, p, c, w, canon));
     PC_TRY(mark(e, 3));
     PC_TRY(mark(e, 4));
     merge_windows(e, p, c, w);

@@ -466,4 +466,84 @@ __global__ __launch_bounds__(256) void k_compact_lin(const uint32_t *__restrict_
     clin[g] = lo;
 }
 
+
+// ---- the canonical stream: one entry per (contig, strand, MAPPED position).  A point rule bins a single-run read at
+// pos + k(L, strand) and needs L for nothing else, so under ONE rule and size filter all reads of a strand that map to
+// the same position can be one entry (canon_host.h: the entry is a stream word with the strand's canonical length Lc and
+// the position pos + k(L, strand) - kc; reads the rule or the filter drops are left out).  Built by 128-nt bucket of the
+// moved positions, without a sort: the reads that land in bucket b of a contig are records of the buckets b - `back` ..
+// b, a range of lin_tab.  A workgroup per entry of the linear index (kCanonMaxGrid of them at most, striding):
+//   k_canon_buckets<false>   the bucket's 256-bin histogram (128 positions x strand) in LDS; its entries -- one per
+//                            kCompactCap reads of a bin -- into cnt[g] (0 for a contig's closing entry)
+//   (exclusive sum in place: cnt becomes the stream's linear index, entry g = the entries before bucket g)
+//   k_canon_buckets<true>    the histogram again; the entries, in (position, strand) order, at clin[g] ...
+// Positions are non-decreasing over a contig, every entry lies inside its bucket, no group is cut anywhere.
+// `shift`: CanonRule::shift; `lc_word`: (Lc << 4 | strand << 2) per strand.
+constexpr int kCanonBins = 256;
+constexpr int64_t kCanonMaxGrid = (int64_t)1 << 22;   // (x 256 threads stays below the 2^32 work-items a launch may have)
+
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_canon_buckets(const uint32_t *__restrict__ stream, const uint32_t *__restrict__ lin_tab,
+                                                       const int64_t *__restrict__ lin_off, int ntid, int64_t nlin,
+                                                       const int16_t *__restrict__ shift, int back, uint32_t lc_word0, uint32_t lc_word1,
+                                                       uint32_t *__restrict__ clin, uint32_t *__restrict__ cstream) {
+    typedef hipcub::BlockScan<uint32_t, 256> Scan;
+    __shared__ typename Scan::TempStorage s_scan;
+    __shared__ uint32_t s_hist[kCanonBins];
+    __shared__ int16_t s_shift[512];
+    s_shift[threadIdx.x] = shift[threadIdx.x];
+    s_shift[threadIdx.x + 256] = shift[threadIdx.x + 256];
+    // (a workgroup takes every gridDim.x-th entry: a human-scale genome has more entries than a grid has workgroups;
+    // every branch around a barrier below is uniform)
+    for (int64_t g = blockIdx.x; g < nlin; g += gridDim.x) {
+        int t;
+        {
+            int lo = 0, hi = ntid;   // first t in [0, ntid] with lin_off[t] > g; the contig is the one before
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (lin_off[mid] <= g) lo = mid + 1; else hi = mid;
+            }
+            t = lo - 1;
+        }
+        const int64_t l0 = lin_off[t], nb = lin_off[t + 1] - l0 - 1, b = g - l0;
+        const int64_t b_lo = b > back ? b - back : 0;
+        const int64_t r_lo = b < nb ? (int64_t)lin_tab[l0 + b_lo] : 0, r_hi = b < nb ? (int64_t)lin_tab[l0 + b + 1] : 0;
+        if (r_lo >= r_hi) {   // the contig's closing entry (no bucket), or no record that could land here
+            if (!FILL && threadIdx.x == 0) clin[g] = 0u;
+            continue;
+        }
+        s_hist[threadIdx.x] = 0u;
+        __syncthreads();
+        const uint32_t base = (uint32_t)(b_lo << pc::kLinShift);   // every record of the range starts in [base, base + 128 (back + 1))
+        for (int64_t i = r_lo + threadIdx.x; i < r_hi; i += 256) {
+            const uint32_t w = stream[i];
+            if (w & pc::kStreamSkip) continue;
+            const uint32_t rev = (w >> 2) & 1u;
+            const int s = s_shift[pc::stream_len(w) * 2u + rev];
+            if (s < 0) continue;
+            const uint32_t sp = base + (((w >> 16) - base) & 0xffffu) + (uint32_t)s;
+            if ((int64_t)(sp >> pc::kLinShift) == b) atomicAdd(&s_hist[((sp & 127u) << 1) | rev], 1u);
+        }
+        __syncthreads();
+        const uint32_t h = s_hist[threadIdx.x], ne = (h + kCompactCap - 1u) / kCompactCap;
+        uint32_t before, total;
+        Scan(s_scan).ExclusiveSum(ne, before, total);
+        if (!FILL) {
+            if (threadIdx.x == 0) clin[g] = total;
+        } else {
+            const uint32_t rev = threadIdx.x & 1u;
+            const uint32_t word = ((((uint32_t)b << pc::kLinShift) + (threadIdx.x >> 1)) << 16) | (rev ? lc_word1 : lc_word0);
+            uint32_t *dst = cstream + clin[g] + before;
+            for (uint32_t j = 0, left = h; j < ne; ++j, left -= kCompactCap)
+                dst[j] = word | (((left < kCompactCap ? left : kCompactCap) - 1u) << pc::kStreamMultShift);
+        }
+        __syncthreads();   // (the histogram and the scan's storage are the next entry's)
+    }
+}
+
+// eight skip words behind the last entry (the window kernels read whole quads)
+__global__ void k_canon_pad(const uint32_t *__restrict__ clin, int64_t nlin, uint32_t *__restrict__ cstream) {
+    if (threadIdx.x < 8) cstream[clin[nlin] + threadIdx.x] = pc::kStreamSkip;
+}
+
 } // namespace pcstage

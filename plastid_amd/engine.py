@@ -184,6 +184,11 @@ class Engine(object):
         staged as one entry with a multiplicity; equal to ``num_records`` when the file keeps no compact stream."""
         return int(self._lib.pc_stream_entries(self._h, int(file_index)))
 
+    def canonical_entries(self, file_index):
+        """Entries of the canonical stream of file `file_index` (``pc_canonical_entries``): one per contig, strand and
+        mapped position under the current point rule and size filter; -1 when the file has no such stream right now."""
+        return int(self._lib.pc_canonical_entries(self._h, int(file_index)))
+
     def read_records(self, file_index, indices):
         """Read objects' worth of data for records of a staged file (``pc_read_records`` + ``pc_read_record_runs``):
         dict of arrays ``tid, pos, alen, reverse, nblk, flag16, mapq`` plus ``run_off`` (n + 1), ``run_start``,
