@@ -146,8 +146,8 @@ int64_t pc_stream_entries(pc_engine *e, int file);
  * and size filter (up to 16 reads per entry) -- what a plan over this one file with '+' / '-' segments only streams
  * under the fiveprime, threeprime and variable rules.  Built at the first count of such a plan, rebuilt when the rule,
  * the filter or the file's flags change; PC_NO_CANON=1 (read at pc_create / pc_reload_knobs) forbids it.  -1: no such
- * stream right now (never wanted, forbidden, stale, or not at most 0.9 x the entries of the stream it would replace),
- * or a bad file index. */
+ * stream right now (never wanted, forbidden, stale, more than one file staged, or not at most 0.9 x the entries of the
+ * stream it would replace), or a bad file index. */
 int64_t pc_canonical_entries(pc_engine *e, int file);
 /* Read objects of a staged file back (the reference hands pysam reads to its callers: get_reads / reads_out,
  * genome_array.py:834-859, and to filter functions, :697-722) -- for files whose records never visited the host

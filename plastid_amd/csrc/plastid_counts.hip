@@ -1437,6 +1437,7 @@ int64_t pc_stream_entries(pc_engine *e, int file) {
 int64_t pc_canonical_entries(pc_engine *e, int file) {
     if (!e || file < 0 || file >= (int)e->files.size()) return -1;
     const StagedFile *sf = e->files[file];
+    if (e->files.size() != 1) return -1;   // (only a plan over ONE file streams it: what an earlier count of file 0 alone built is kept, and not served)
     return (!e->knobs.no_canon && sf->ksig_valid && sf->ksig.words_gen == sf->words_gen) ? sf->kn : -1;
 }
 

@@ -17,7 +17,9 @@ import sys
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stream_models import model_entries  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -167,32 +169,6 @@ def configure(eng, mapping, size_filter=None):
         eng.set_size_filter(*size_filter)
     else:
         eng.set_size_filter(None)
-
-
-def rule_index(mapping, L, rev):
-    """k(L, strand) of a point rule for arrays of lengths and strands; -1: not mapped."""
-    L = L.astype(np.int64)
-    if mapping[0] in ("fiveprime", "threeprime"):
-        p = mapping[1]
-        near_left = (rev == 0) if mapping[0] == "fiveprime" else (rev != 0)
-        return np.where(p >= L, -1, np.where(near_left, p, L - 1 - p))
-    from plastid_amd import synth
-    fac = synth.mapping_factory(mapping)
-    fw, rc = np.asarray(fac.forward_offsets, np.int64), np.asarray(fac.reverse_offsets, np.int64)
-    return np.where(rev != 0, rc[L], fw[L])
-
-
-def model_entries(f, flags, mapping, size_filter=None):
-    """Entries the grouping implies: the single-run reads that are not excluded and that the rule and the filter keep,
-    by (contig, strand, mapped position), one entry per 16 reads of a group."""
-    L, rev = f.alen.astype(np.int64), (flags & 1).astype(np.int64)
-    k = rule_index(mapping, L, rev)
-    keep = (f.nblk == 1) & ((flags & EXCLUDED) == 0) & (k >= 0)
-    if size_filter:
-        keep &= (L >= size_filter[0]) & ((L <= size_filter[1]) | (size_filter[1] == -1))
-    key = (f.tid.astype(np.int64) << 40) | (rev << 39) | (f.pos.astype(np.int64) + k)
-    _, cnt = np.unique(key[keep], return_counts=True)
-    return int(((cnt + CAP - 1) // CAP).sum())
 
 
 def staged(files, flags=None):

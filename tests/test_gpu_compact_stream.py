@@ -14,7 +14,9 @@ import sys
 import numpy as np
 import pytest
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from stream_models import entries_of_sorted_tiles  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -54,20 +56,6 @@ def packed(pa, reads, **kw):
 def with_flags(pa, f, flags):
     """What the oracle is given for `f` under the caller's `flags`: excluded records are simply absent from its input."""
     return f.subset(np.nonzero((flags & EXCLUDED) == 0)[0])
-
-
-def entries_of_sorted_tiles(f, excluded=None):
-    """Entries the format implies for a file whose tiles are all sorted: per tile, ceil(copies / 16) per distinct key."""
-    keep = np.ones(f.n, bool) if excluded is None else ~excluded
-    total = 0
-    for t0 in range(0, f.n, TILE):
-        sl = slice(t0, min(t0 + TILE, f.n))
-        k = keep[sl]
-        key = np.stack([f.pos[sl][k].astype(np.int64), f.alen[sl][k].astype(np.int64), (f.flags[sl][k] & 1).astype(np.int64)], 1)
-        if len(key):
-            _, cnt = np.unique(key, axis=0, return_counts=True)
-            total += int(((cnt + CAP - 1) // CAP).sum())
-    return total
 
 
 def spec_for(oracle, mapping, size_filter=None):

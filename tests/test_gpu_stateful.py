@@ -3,7 +3,8 @@
 Every other randomised GPU test builds a fresh engine per case.  The engine keeps much between counts -- exclusion bits
 folded into the staged records by four setters, cached work lists and exact-grid counts per plan, "the compact histogram
 is zero where it will be read", center streams, the knob block, ``Engine._state`` -- and a stale piece of any of it gives
-wrong counts from correct kernels.  Here the state is exercised on purpose: random sequences (40 seeds), the full table
+wrong counts from correct kernels.  Here the state is exercised on purpose: random sequences (40 seeds, and 24 aimed at the
+compact and the canonical stream of a staged file: tests/test_gpu_stream_state.py has their directed cases), the full table
 of orders in which filters, files and columns can arrive, the lazy histogram across knob reloads, and the
 ``BAMGenomeArray`` layer on top.  The expectation always comes from scratch (oracle on the reads the model keeps).
 docs/stateful_fuzz.md: the step vocabulary, how to replay a trace, what the tests caught."""
@@ -30,7 +31,7 @@ def env():
     return pa, oracle
 
 
-@pytest.mark.parametrize("seed", sc.SEEDS)
+@pytest.mark.parametrize("seed", sc.SEEDS + sc.STREAM_SEEDS)
 def test_operation_sequences_match_the_model(env, seed):
     pa, oracle = env
     sc.run_sequence(pa, oracle, sc.random_sequence(seed, pa))
