@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 12
+#define PC_ABI_VERSION 13
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -149,6 +149,15 @@ int64_t pc_stream_entries(pc_engine *e, int file);
  * stream right now (never wanted, forbidden, stale, more than one file staged, or not at most 0.9 x the entries of the
  * stream it would replace), or a bad file index. */
 int64_t pc_canonical_entries(pc_engine *e, int file);
+/* Cells of the file's DENSE VECTOR: one 16-bit cell per contig, strand ('+', '-') and position of the contig's extent (the
+ * furthest aligned end staged) with the count of that position under the current point rule, size filter and FLAG /
+ * MAPQ / NH filters; counts of 65 535 and more sit in a sorted overflow list.  A plan over this one file with '+' / '-'
+ * segments only and no summed slice is served from it by one gather kernel when the vector takes no more bytes than the
+ * stream it replaces (2 bytes per cell against 4 per entry) and fits the build's cap (2^27 cells).  Built at the first
+ * count of such a plan, rebuilt when the rule, a filter or the file's flags change, dropped with the file; PC_NO_DENSE=1
+ * (read at pc_create / pc_reload_knobs) forbids it.  -1: the engine's last pc_count was not served from it (plan or file
+ * not eligible, forbidden, more than one file staged), the rule or a filter has changed since, or a bad file index. */
+int64_t pc_dense_cells(pc_engine *e, int file);
 /* Read objects of a staged file back (the reference hands pysam reads to its callers: get_reads / reads_out,
  * genome_array.py:834-859, and to filter functions, :697-722) -- for files whose records never visited the host
  * (pc_add_alignment_bam[_path | _span]).  pc_read_records: per requested record index its reference id, first aligned

@@ -16,11 +16,13 @@
 //   pc_plan_create                 segments -> islands -> windows -> output pieces, all tables of a
 //                                  plan in one device block
 //   pc_count                       k_tile_ranges -> k_hist_point (two classes, two streams) ->
-//                                  k_gather_split, or the three center kernels + k_gather
+//                                  k_gather_split, or the three center kernels + k_gather, or -- a '+' / '-' plan
+//                                  under a point rule over a file with a dense vector -- k_dense_gather alone
 //   pc_rle / pc_total / pc_mapped_reads / pc_warn_flags   consumers of a finished count
 #include "pc_kernels.hip.h"
 #include "plan_kernels.hip.h"
 #include "stage_kernels.hip.h"
+#include "dense_kernels.hip.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -51,6 +53,7 @@
 #include "host_util.h"
 #include "plan_host.h"
 #include "canon_host.h"
+#include "dense_host.h"
 
 using namespace pc;
 
@@ -466,6 +469,19 @@ struct CanonSig {
     }
 };
 
+// What a dense vector was built from (build_dense_vector): the rule, the size filter, the stream words (by their
+// generation) and the FLAG / MAPQ / NH filter whose verdicts the records held.
+struct DenseSig {
+    int kind = -1, param = 0, filt_on = 0, filt_min = 0, filt_max = -1;
+    uint64_t words_gen = 0;
+    FilterState applied;
+    std::vector<int32_t> fw, rc;   // the offset tables (variable rule only)
+    bool operator==(const DenseSig &o) const {
+        return kind == o.kind && param == o.param && filt_on == o.filt_on && filt_min == o.filt_min && filt_max == o.filt_max &&
+               words_gen == o.words_gen && applied == o.applied && fw == o.fw && rc == o.rc;
+    }
+};
+
 struct StagedFile {
     int64_t n = 0, nrun = 0, nlong = 0;
     int W = 1;               // max reference span of the records scanned by the window kernels
@@ -505,6 +521,20 @@ struct StagedFile {
     bool ksig_valid = false;
     CanonSig ksig;
     uint64_t kid = 0;
+    // dense vector (build_dense_vector, dense_host.h): one 16-bit cell per (contig, strand, position of the extent) with
+    // the count of that position under ONE rule, size filter and filter state; cells that hold 65 535 or more escape to
+    // the sorted overflow list.  Built at the first count of an eligible plan, kept until `dsig` no longer holds, dropped
+    // with the file.  The layout (extents, cell offsets) depends on the staged reads alone.
+    std::vector<int64_t> tid_end;      // furthest aligned end per contig (0: no read)
+    std::vector<int64_t> dext, dcell_off;   // extents [ntid], first cell of (contig, strand) [2 ntid + 1]; empty: not laid out yet
+    int64_t dcells = -1;               // cells of the layout
+    DevBuf<int64_t> d_dext, d_dcell_off;
+    DevBuf<uint16_t> dense;
+    DevBuf<uint32_t> dovf_key, dovf_val;
+    uint32_t dn_ovf = 0;
+    bool dsig_valid = false;
+    DenseSig dsig;
+    uint64_t did = 0;                  // changes with every build, unique in the process (pc_plan::ditems_id)
     size_t nlin = 0;                   // entries of every linear-index table
     // run stream (aligned runs of multi-run reads with L <= kStreamMaxLen, sorted by contig and run start)
     int64_t nrunrec = 0;
@@ -582,6 +612,8 @@ struct Knobs {
     int no_compact = 0;        // PC_NO_COMPACT: no compact stream -- files staged (or re-filtered) from then on are counted record by record (tests compare the two)
     double compact_keep = 0.9; // PC_COMPACT_KEEP: a file that keeps more than this share of its records as entries gets no compact stream (build_compact_stream)
     int no_canon = 0;          // PC_NO_CANON: no canonical stream -- eligible plans stream what the others do (A/B runs in one build; tests compare the two)
+    int no_dense = 0;          // PC_NO_DENSE: no dense vector -- eligible plans go through the window kernels (A/B runs in one build; tests compare the two)
+    int dense_debug = 0;       // PC_DENSE_DEBUG: print what dense_for_plan decided and from which figures (stderr)
     int no_single = 0;         // PC_NO_SINGLE: one-window plans go through the work lists like any other (tests compare the two paths)
     int plan_build = 0;        // PC_PLAN_BUILD=host|gpu: where pc_plan_create builds the tables (default: on the GPU from 8 192 segments)
     int small_g = 512;         // PC_SMALL_G: queried span a single-wave window may have
@@ -604,6 +636,8 @@ struct Knobs {
         no_single = getenv("PC_NO_SINGLE") ? 1 : 0;
         no_compact = getenv("PC_NO_COMPACT") ? 1 : 0;
         no_canon = getenv("PC_NO_CANON") ? 1 : 0;
+        no_dense = getenv("PC_NO_DENSE") ? 1 : 0;
+        dense_debug = getenv("PC_DENSE_DEBUG") ? 1 : 0;
         if (const char *env = getenv("PC_COMPACT_KEEP")) compact_keep = std::min(1.0, std::max(0.0, atof(env)));
         no_stream_probe = getenv("PC_NO_STREAM_PROBE") ? 1 : 0;
         hist_memset = getenv("PC_HIST_MEMSET") ? 1 : 0;
@@ -680,6 +714,7 @@ struct pc_engine {
     int prof_level = 0;      // pc_set_profiling: 0 no events, 1 whole call + histogram/center kernel, 2 every phase
     int timed_level = 0;     // level the last pc_count was recorded with
     int64_t last_alg_bytes = 0;
+    bool last_count_dense = false;       // the last pc_count was served from the dense vector of file 0 (pc_dense_cells)
     bool want_center_steps = false;      // pc_center_replay_steps: the next center count reports the replay steps it executed
     int64_t center_steps = 0, center_waves = 0;
 
@@ -717,6 +752,13 @@ struct pc_plan {
     DevBuf<GatherSeg> d_gsegs_own;
     bool has_sums = false;       // some slices are summed (out_step 0): the output is an accumulator
     bool out_needs_zero = false; // some queried positions lie outside every tile (unknown contig, clipped)
+    // Gather items of the dense vector (dense_host.h): the plan's segments cut into at most 2 048 positions each, with
+    // the cells they read.  They depend on the plan and the layout of the file's vector only: built by a kernel at the
+    // first count served from a vector, kept while that vector stands (StagedFile::did).
+    bool no_dense = false;       // the plan a dense vector is built with: counted by the window kernels
+    DevBuf<pcdense::Item> d_ditems;
+    uint32_t n_ditems = 0;
+    uint64_t ditems_id = 0;      // (0: none)
     bool hist_clean = false;     // the WHOLE compact histogram is known to be zero (a lazy count does not need that: it clears the slices it merges)
     bool hist_lazy = false;      // the histogram is large: never cleared as a whole, k_clear_split runs behind every k_tile_ranges
     // GPU-built plans: the center chunks and the gather list wait for the first center count or coordinate export
@@ -807,7 +849,7 @@ struct pc_plan {
         d_ccand.pool = pl; d_rle_cnt.pool = pl; d_rle_base.pool = pl; d_rle_starts.pool = pl; d_rle_values.pool = pl;
         d_cranges.pool = pl; d_crec.pool = pl; d_crows.pool = pl; d_ccounts.pool = pl; d_cslots.pool = pl; d_hist_own.pool = pl; d_out.pool = pl; d_tables2.pool = pl; d_tables3.pool = pl;
         d_work.pool = pl; d_work_small.pool = pl; d_chain.pool = pl; d_chain_small.pool = pl;
-        d_inputs.pool = pl; d_gsegs_own.pool = pl;
+        d_inputs.pool = pl; d_gsegs_own.pool = pl; d_ditems.pool = pl;
     }
 };
 
@@ -1820,6 +1862,7 @@ void stage_halo(StagedFile *sf, StageCall &c) {
     for (int L = 0; L < 65536; ++L)
         if (sf->len_hist[(size_t)L]) { sf->len_min = std::min(sf->len_min, L); sf->len_max = std::max(sf->len_max, L); }
     sf->nrunrec = c.nrunrec;
+    sf->tid_end = s.tid_end;
     sf->nlin = lin_layout(c.tid_bounds, s.last_pos, s.tid_end, kLinShift, c.lin_off);
 }
 
@@ -2489,7 +2532,7 @@ int count_validate(pc_engine *e, pc_plan *p, int out_dtype) {   // (no HIP call)
     return PC_OK;
 }
 
-int count_prepare(pc_engine *e, pc_plan *p) {
+int count_prepare(pc_engine *e, pc_plan *p, bool dense) {   // dense: served from a dense vector -- no compact histogram
     const bool center = e->kind == PC_MAP_CENTER;
     if (center) {   // the center-only tables of a large plan; the center streams of the strand selections it queries
         PC_TRY(ensure_center_tables(e, p));
@@ -2499,7 +2542,7 @@ int count_prepare(pc_engine *e, pc_plan *p) {
                 if (need[k]) PC_TRY(build_center_stream(e, f, k, e->param));   // (no-op when built for this nibble)
     }
     PC_TRY(refresh_file_views(e));
-    if (!center && !p->d_hist.p) {
+    if (!center && !dense && !p->d_hist.p) {
         const int rc = p->d_hist_own.reserve(std::max<size_t>((size_t)p->npos * p->rows * sizeof(uint32_t), 8));
         p->d_hist.p = p->d_hist_own.p;
         PC_TRY(rc);
@@ -2507,9 +2550,13 @@ int count_prepare(pc_engine *e, pc_plan *p) {
     return p->d_out.reserve(std::max<size_t>((size_t)p->out_elems * 8, 8));
 }
 
-int count_clear(pc_engine *e, pc_plan *p, const CountCall &c) {
+int count_clear(pc_engine *e, pc_plan *p, const CountCall &c, bool dense) {
     const bool center = e->kind == PC_MAP_CENTER;
     PC_TRY(mark(e, 0));
+    if (dense) {   // k_dense_gather writes every position of every segment, zeros included: only gaps between slices are cleared
+        if (p->covered != p->out_elems && p->out_elems) HIP_TRY(hipMemsetAsync(p->d_out.p, 0, (size_t)p->out_elems * 8, e->stream));
+        return mark(e, 1);
+    }
     // Outputs are written exactly once by the tile kernels.  Only positions that belong to no
     // tile (unknown contig, clipped coordinates) or gaps the caller left between slices need a
     // zero fill; the compact histogram of the point rules is kept all-zero between calls.
@@ -2852,6 +2899,181 @@ int count_lists(pc_engine *e, pc_plan *p, const CountCall &c) {
     return read_work_counts(e, p, c, w);
 }
 
+// ---- the dense vector of the plan's file under the engine's rule and filters (dense_host.h, dense_kernels.hip.h).
+// Under a point rule the count at a position is the same whatever the query, so a file whose genome is small beside its
+// reads keeps one 16-bit cell per (contig, strand, position) and a count of a '+' / '-' plan is a copy with widening:
+// no work lists, no windows, no LDS, no merge pass.
+DenseSig dense_sig(const pc_engine *e, const StagedFile *sf) {
+    DenseSig sig;
+    sig.kind = e->kind; sig.param = e->kind == PC_MAP_VAR5 ? 0 : e->param;
+    sig.filt_on = e->filt_on; sig.filt_min = e->filt_on ? e->filt_min : 0; sig.filt_max = e->filt_on ? e->filt_max : -1;
+    sig.words_gen = sf->words_gen; sig.applied = sf->applied;
+    if (e->kind == PC_MAP_VAR5) { sig.fw = e->h_fw; sig.rc = e->h_rc; }
+    return sig;
+}
+
+std::atomic<uint64_t> g_dense_id{0};
+
+// The build adds no second implementation of the rules and filters: an internal plan of one segment per contig and
+// strand over the whole extent is counted by the window kernels (the dense vector forbidden for that plan) into the
+// int64 block of that plan -- 8 bytes per cell from the engine's pool, at most pcdense::kBuildBlockCap, returned behind
+// the build -- and one kernel narrows it.  Waits for the engine's stream.
+int build_dense_vector(pc_engine *e, StagedFile *sf, const DenseSig &sig) {
+    using namespace pcdense;
+    sf->dsig_valid = false;
+    const int ntid = e->ntid;
+    const int64_t cells = sf->dcells;
+    std::vector<int32_t> tid;
+    std::vector<int64_t> start, end, off, stride;
+    std::vector<uint8_t> strand;
+    std::vector<int8_t> step;
+    for (int t = 0; t < ntid; ++t)
+        for (int s = 0; s < 2 && sf->dext[(size_t)t] > 0; ++s) {
+            tid.push_back(t); start.push_back(0); end.push_back(sf->dext[(size_t)t]); strand.push_back(s ? PC_STRAND_REV : PC_STRAND_FWD);
+            off.push_back(sf->dcell_off[(size_t)(2 * t + s)]); step.push_back(1); stride.push_back(0);
+        }
+    pc_plan *ip = nullptr;
+    PC_TRY(pc_plan_create(e, (int64_t)tid.size(), tid.data(), start.data(), end.data(), strand.data(), off.data(), step.data(), stride.data(), cells, 1, &ip));
+    ip->no_dense = true;
+    // (raw counts, whatever the engine's output mode; the events of the count that asked for the vector stay its own)
+    const int norm_on = e->norm_on, prof_level = e->prof_level;
+    e->norm_on = 0; e->prof_level = 0;
+    int rc = pc_count(e, ip, PC_OUT_INT64);
+    e->norm_on = norm_on; e->prof_level = prof_level;
+    auto narrow = [&]() -> int {
+        PoolScope pool_scope(&e->pool);
+        hipStream_t st = e->stream;
+        DevBuf<uint32_t> d_n, d_key, d_val;
+        DevBuf<uint8_t> d_tmp;
+        PC_TRY(sf->dense.reserve((size_t)cells + 8));
+        PC_TRY(sf->d_dext.upload(sf->dext, st));
+        PC_TRY(sf->d_dcell_off.upload(sf->dcell_off, st));
+        PC_TRY(d_n.reserve(2));
+        HIP_TRY(hipMemsetAsync(d_n.p, 0, 8, st));
+        const unsigned grid = (unsigned)((cells + 255) / 256);
+        const int64_t *src = (const int64_t *)ip->d_out.p;
+        hipLaunchKernelGGL(k_dense_narrow, dim3(grid), dim3(256), 0, st, src, cells, sf->dense.p, d_n.p);
+        uint32_t n_ovf = 0;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&n_ovf, d_n.p, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (n_ovf) {   // the escaped cells, sorted by cell index
+            size_t tb = 0;
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n_ovf, 0, 32, st));
+            PC_TRY(d_key.reserve(n_ovf)); PC_TRY(d_val.reserve(n_ovf)); PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+            PC_TRY(sf->dovf_key.reserve(n_ovf)); PC_TRY(sf->dovf_val.reserve(n_ovf));
+            hipLaunchKernelGGL(k_dense_overflow, dim3(grid), dim3(256), 0, st, src, cells, d_n.p + 1, n_ovf, d_key.p, d_val.p);
+            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tb, d_key.p, sf->dovf_key.p, d_val.p, sf->dovf_val.p, (int)n_ovf, 0, 32, st));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(st));   // (the working arrays go out of scope)
+        }
+        sf->dn_ovf = n_ovf;
+        return PC_OK;
+    };
+    if (rc == PC_OK) rc = narrow();
+    (void)pc_plan_destroy(ip);   // (waits for the stream: the int64 block goes back to the pool)
+    PC_TRY(rc);
+    sf->dsig = sig;
+    sf->dsig_valid = true;
+    sf->did = ++g_dense_id;
+    return PC_OK;
+}
+
+// `dense`: the plan's file when this count is to be served from its vector (built or rebuilt here when its signature
+// no longer holds), else nullptr.  The plan conditions are those of the canonical stream, and no summed slice; the
+// vector must not take more bytes than the stream it replaces -- canonical (weighed, and built, exactly as count_lists
+// would), else compact, else the records -- and its build block must fit (dense_host.h).  A one-window plan keeps its
+// single launch.
+int dense_for_plan(pc_engine *e, pc_plan *p, const CountCall &c, StagedFile **dense) {
+    *dense = nullptr;
+    pcdense::PlanIn in;
+    in.nfiles = c.nfiles;
+    in.point_rule = e->kind == PC_MAP_FIVE || e->kind == PC_MAP_THREE || e->kind == PC_MAP_VAR5;
+    in.rows = p->rows; in.modes = p->modes; in.has_sums = p->has_sums;
+    in.forbidden = e->knobs.no_dense || p->no_dense;
+    if (!pcdense::plan_conditions(in)) return PC_OK;
+    StagedFile *sf = e->files[0];
+    if (sf->n <= 0 || !sf->nlin || sf->tid_end.size() != (size_t)e->ntid) return PC_OK;
+    if (sf->dcells < 0) {   // the layout: once per file
+        sf->dext.resize((size_t)e->ntid);
+        sf->dcell_off.resize(2 * (size_t)e->ntid + 1);
+        for (int t = 0; t < e->ntid; ++t) sf->dext[(size_t)t] = pcdense::extent(0, sf->tid_end[(size_t)t]);   // (the engine is told no declared lengths)
+        sf->dcells = pcdense::layout(e->ntid, sf->dext.data(), sf->dcell_off.data());
+    }
+    in.cells = sf->dcells;
+    if (!pcdense::build_fits(in.cells) || in.cells >= (int64_t)0xffffffffu) return PC_OK;
+    StagedFile *canon = nullptr;
+    PC_TRY(canonical_for_plan(e, p, c, hist_lds_shape(e), &canon));
+    in.stream_entries = canon ? canon->kn : (sf->cn >= 0 ? sf->cn : sf->n);
+    const bool ok = pcdense::eligible(in);
+    if (e->knobs.dense_debug)
+        fprintf(stderr, "[dense] cells %lld (%lld bytes) against %lld entries of the %s stream (%lld bytes): %s\n", (long long)in.cells,
+                (long long)(in.cells * pcdense::kBytesPerCell), (long long)in.stream_entries, canon ? "canonical" : (sf->cn >= 0 ? "compact" : "record"),
+                (long long)(in.stream_entries * 4), ok ? "vector" : "window kernels");
+    if (!ok) return PC_OK;
+    const DenseSig sig = dense_sig(e, sf);
+    if (!(sf->dsig_valid && sf->dsig == sig)) PC_TRY(build_dense_vector(e, sf, sig));
+    *dense = sf;
+    return PC_OK;
+}
+
+// the plan's segments cut into gather items: once per plan and vector
+int ensure_dense_items(pc_engine *e, pc_plan *p, const StagedFile *sf) {
+    using namespace pcdense;
+    if (p->ditems_id == sf->did) return PC_OK;
+    hipStream_t st = e->stream;
+    const size_t n = (size_t)p->nseg;
+    p->ditems_id = 0;
+    p->n_ditems = 0;
+    DevBuf<int32_t> d_tid;
+    DevBuf<uint8_t> d_strand, d_tmp;
+    DevBuf<uint32_t> d_cnt, d_at;
+    d_tid.pool = d_strand.pool = d_tmp.pool = d_cnt.pool = d_at.pool = &e->pool;
+    const GatherSeg *gsegs = p->gpu_built ? p->d_gsegs_own.p : p->d_gsegs.p;
+    const int32_t *tid = nullptr;
+    const uint8_t *strand = nullptr;
+    if (p->gpu_built) {   // the caller's arrays are in HBM
+        const PlanInputLayout L(n);
+        tid = (const int32_t *)(p->d_inputs.p + L.at_tid); strand = p->d_inputs.p + L.at_strand;
+    } else {
+        PC_TRY(d_tid.upload(p->h_tid, st)); PC_TRY(d_strand.upload(p->h_strand, st));
+        tid = d_tid.p; strand = d_strand.p;
+    }
+    uint32_t total = 0;
+    if (n) {
+        size_t tb = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st));
+        PC_TRY(d_cnt.reserve(n + 1)); PC_TRY(d_at.reserve(n + 1)); PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+        const unsigned g = (unsigned)((n + 255) / 256);
+        HIP_TRY(hipMemsetAsync(d_cnt.p + n, 0, 4, st));
+        hipLaunchKernelGGL(k_dense_seg_items, dim3(g), dim3(256), 0, st, gsegs, (int64_t)n, d_cnt.p);
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_cnt.p, d_at.p, (int)n + 1, st));
+        HIP_TRY(hipMemcpyAsync(&total, d_at.p + n, 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        PC_TRY(p->d_ditems.reserve(std::max<size_t>(total, 1)));
+        if (total) hipLaunchKernelGGL(k_dense_items, dim3(g), dim3(256), 0, st, gsegs, tid, strand, (int64_t)n, e->ntid, sf->d_dcell_off.p, sf->d_dext.p, d_at.p, p->d_ditems.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));   // (the working arrays go out of scope)
+    }
+    p->n_ditems = total;
+    p->ditems_id = sf->did;
+    return PC_OK;
+}
+
+// a count served from the dense vector: one launch, between the marks of the histogram kernels
+int count_dense(pc_engine *e, pc_plan *p, const CountCall &c, const StagedFile *sf) {
+    PC_TRY(ensure_dense_items(e, p, sf));
+    PC_TRY(mark(e, 2));
+    if (p->n_ditems)
+        dispatch_int<0, 1, 2>(c.outmode, [&](auto O) {
+            constexpr int o = decltype(O)::value;
+            hipLaunchKernelGGL((pcdense::k_dense_gather<o>), dim3(p->n_ditems), dim3(pcdense::kGatherWG), 0, e->stream, p->d_ditems.p, sf->dense.p,
+                               sf->dovf_key.p, sf->dovf_val.p, sf->dn_ovf, (typename OutT_<o>::type *)p->d_out.p, e->norm_sum);
+        });
+    PC_TRY(mark(e, 3));
+    return mark(e, 4);
+}
+
 // ---- the center rule: k_center2 writes every queried position of the tiles straight into the output layout; the
 // compact histogram is not touched
 int reserve_center(pc_engine *e, pc_plan *p) {
@@ -3029,7 +3251,6 @@ extern "C" {
 int pc_count(pc_engine *e, pc_plan *p, int out_dtype) {
     PC_TRY(count_validate(e, p, out_dtype));
     HIP_TRY(hipSetDevice(e->device));
-    PC_TRY(count_prepare(e, p));
     const bool center = e->kind == PC_MAP_CENTER;
     CountCall c;
     c.out_dtype = out_dtype;
@@ -3039,15 +3260,27 @@ int pc_count(pc_engine *e, pc_plan *p, int out_dtype) {
     for (auto *f : e->files) { c.nrec += f->n; c.nextra += f->nrun; }
     c.hist_bytes = center ? 0 : (size_t)p->npos * p->rows * sizeof(uint32_t);
     c.mp = e->params();
-    PC_TRY(count_clear(e, p, c));
     // (one window, not under the stratified rule: its 16-bit bins rely on the work lists, which cut or merge a window that
     // scans more than 65 535 records)
     const bool single = c.ntiles == 1 && c.nfiles == 1 && !e->knobs.debug_work && !e->knobs.no_single && e->kind != PC_MAP_STRAT5;
+    StagedFile *dense = nullptr;   // (decided first: a build counts a plan of its own on this engine)
+    if (!center && !single && c.ntiles > 0) PC_TRY(dense_for_plan(e, p, c, &dense));
+    e->last_count_dense = dense != nullptr;
+    PC_TRY(count_prepare(e, p, dense != nullptr));
+    PC_TRY(count_clear(e, p, c, dense != nullptr));
     if (center) PC_TRY(count_center(e, p, c));
+    else if (dense) PC_TRY(count_dense(e, p, c, dense));
     else if (single) PC_TRY(count_single(e, p, c));
     else if (c.ntiles > 0) PC_TRY(count_lists(e, p, c));
     else for (int k = 2; k <= 4; ++k) PC_TRY(mark(e, k));   // a plan without windows
     return count_finish(e, p, c);
+}
+
+int64_t pc_dense_cells(pc_engine *e, int file) {
+    if (!e || file < 0 || file >= (int)e->files.size()) return -1;
+    const StagedFile *sf = e->files[file];
+    if (e->files.size() != 1 || e->knobs.no_dense || !e->last_count_dense) return -1;   // (only a plan over ONE file is served from it)
+    return (sf->dsig_valid && sf->dsig == dense_sig(e, sf)) ? sf->dcells : -1;
 }
 
 int pc_sync(pc_engine *e) {

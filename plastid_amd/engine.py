@@ -189,6 +189,11 @@ class Engine(object):
         mapped position under the current point rule and size filter; -1 when the file has no such stream right now."""
         return int(self._lib.pc_canonical_entries(self._h, int(file_index)))
 
+    def dense_cells(self, file_index):
+        """Cells of the dense vector of file `file_index` (``pc_dense_cells``): one per contig, strand and position, holding
+        the count under the current point rule and filters; -1 when the last count was not served from it."""
+        return int(self._lib.pc_dense_cells(self._h, int(file_index)))
+
     def read_records(self, file_index, indices):
         """Read objects' worth of data for records of a staged file (``pc_read_records`` + ``pc_read_record_runs``):
         dict of arrays ``tid, pos, alen, reverse, nblk, flag16, mapq`` plus ``run_off`` (n + 1), ``run_start``,
