@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 13
+#define PC_ABI_VERSION 14
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -426,6 +426,29 @@ int pc_bam_sort_stats(pc_bam *b, int64_t *out4, double *ms);
 /* the 0-based record number in the file (all records counted, unplaced ones too) of every staged record, counts[0]
  * elements; PC_ERR_STATE when no record was moved (out4[2] == 0: staged record k is the k-th placed record of the file) */
 int pc_bam_read_file_order(pc_bam *b, int64_t *rec_no);
+
+/* ---- (ABI 14) SAM TEXT: an aligner's output as it is written (bowtie, bowtie2, bwa, hisat2, minimap2; STAR's default
+ * Aligned.out.sam).  Replaces pysam opening a SAM file with `AlignmentFile(path)` and the `samtools view -b` that every
+ * BGZF reader needs in front of it.  The text crosses PCIe once; line starts, fields and CIGAR strings are parsed by
+ * kernels (csrc/sam_kernels.hip.h) that run the line parser of the host reader (csrc/sam_host.h), and the records go
+ * through the placement of pc_bam_open -- order checks, or the coordinate sort with PC_BAM_SORT in `flags` (any other bit:
+ * PC_ERR_ARG).  The result is an ordinary pc_bam: pc_bam_read, pc_bam_read_sam, pc_bam_read_nh, pc_bam_counts,
+ * pc_bam_sort_stats and pc_bam_read_file_order give, bit for bit, what they give for the same records in a BAM file;
+ * counts[5] (members) and counts[6] (inflated bytes) are 0, pc_bam_stats' out4[0] is the bytes of text uploaded, and
+ * pc_bam_timing's four laps are upload, line starts, fields, placement + columns.
+ * The header is the leading '@' lines; every @SQ gives a reference (SN, LN in 1 .. 2^31-1, any field order; a repeated SN
+ * is refused), every other header line is ignored (@HD SO: too: the records decide).  A line has 11 tab-separated
+ * mandatory fields; FLAG, POS and MAPQ are plain decimal; RNAME is '*' or the SN of an @SQ line; CIGAR is '*' or
+ * <length 0 .. 2^28-1><one of MIDNSHP=X> repeated; l_seq is the length of SEQ (0 for '*'); NH is the value of the first
+ * optional field that begins with "NH:i:", clamped to 0 .. 65 535.  "\r\n" line ends and a last line without '\n' are
+ * read.  A malformed line is PC_ERR_ARG with "<path>: SAM line <n>: <what>" (n 1-based, header lines counted), the lowest
+ * line first; PC_ERR_UNSORTED and the CIGAR defects the formats share are worded as for BAM.  Compressed SAM (gzip or
+ * BGZF magic) is refused.  Limits: 2^31-2 records, and a body that fits HBM.
+ * pc_add_alignment_sam_path_flags stages the file without its columns visiting the host, as pc_add_alignment_bam_path
+ * does; *mapped (optional): the lines with FLAG bit 0x4 unset. */
+int pc_sam_open_path_flags(pc_engine *e, const char *path, uint32_t flags, pc_bam **out);
+int pc_sam_open_flags(pc_engine *e, const void *image, int64_t size, const char *name, uint32_t flags, pc_bam **out);
+int pc_add_alignment_sam_path_flags(pc_engine *e, const char *path, uint32_t flags, int64_t *mapped);
 
 /* ---- (ABI 8) the BAI index of a coordinate-sorted BAM file, built on the GPU.  Replaces `samtools index` / pysam.index,
  * i.e. htslib's sam_index_build for BAI (kent/src/htslib/sam.c:470-496: every record is pushed with POS, bam_endpos

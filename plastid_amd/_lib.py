@@ -109,6 +109,9 @@ SIGNATURES = {
     "pc_add_alignment_bam_path_flags": (_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(_i64)]),
     "pc_bam_sort_stats": (_int, [_vp, _vp, _vp]),
     "pc_bam_read_file_order": (_int, [_vp, _vp]),
+    "pc_sam_open_path_flags": (_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, _pp]),
+    "pc_sam_open_flags": (_int, [_vp, _vp, _i64, ctypes.c_char_p, ctypes.c_uint32, _pp]),
+    "pc_add_alignment_sam_path_flags": (_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.POINTER(_i64)]),
     "pc_bam_index_build": (_int, [_vp, ctypes.c_char_p, _pp]),
     "pc_bam_index_finish": (_int, [_int, _i64] + [_vp] * 10 + [_i64, _pp]),
     "pc_bam_index_build_csi": (_int, [_vp, ctypes.c_char_p, _int, _pp]),
@@ -126,7 +129,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 def load():

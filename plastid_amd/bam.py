@@ -27,6 +27,8 @@ def _load():
         L.pb_last_error.restype = ctypes.c_char_p
         L.pb_open.restype = vp
         L.pb_open.argtypes = [ctypes.c_char_p]
+        L.pb_open_sam.restype = vp
+        L.pb_open_sam.argtypes = [ctypes.c_char_p]
         L.pb_open_indexed.restype = vp
         L.pb_open_indexed.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
         L.pb_close.argtypes = [vp]
@@ -105,6 +107,60 @@ def bam_header(path):
             lens.append(struct.unpack("<i", buf[at + 4 + l_name:at + 8 + l_name])[0])
             at += 8 + l_name
     return refs, lens
+
+
+def is_sam_path(path):
+    """Whether `path` is read as SAM TEXT: its name ends in ``.sam`` (any letter case).  Nothing else makes a path SAM."""
+    return isinstance(path, (str, os.PathLike)) and os.fspath(path).lower().endswith(".sam")
+
+
+def _refuse_compressed_sam(path):
+    with open(path, "rb") as fh:
+        if fh.read(2) == b"\x1f\x8b":
+            raise ValueError("%s: compressed SAM (gzip / BGZF) is not supported: decompress it, or convert it to BAM" % (path,))
+
+
+def _pb_open_sam(L, path):
+    if not os.path.isfile(path):
+        raise IOError("No such file: %r" % (path,))
+    h = L.pb_open_sam(os.fsencode(path))
+    if not h:
+        raise ValueError(L.pb_last_error().decode())   # (compressed, or a malformed header)
+    return h
+
+
+def sam_header(path):
+    """``(references, lengths)`` of a SAM text file from its ``@SQ`` header lines (``SN``, ``LN``; in line order) -- what
+    ``pysam.AlignmentFile(path).references / .lengths`` give.  ``ValueError`` for a header the readers refuse (an ``@SQ``
+    line without ``SN`` or ``LN``, a repeated ``SN``, alignment lines without any ``@SQ``) and for compressed SAM."""
+    L = _load()
+    h = _pb_open_sam(L, os.fspath(path))
+    try:
+        nref = L.pb_nref(h)
+        return [L.pb_ref_name(h, i).decode() for i in range(nref)], [int(L.pb_ref_length(h, i)) for i in range(nref)]
+    finally:
+        L.pb_close(h)
+
+
+def read_sam(path, threads=0, sort=False, timing=None):
+    """Read a SAM TEXT file -- an aligner's output as it is written (bowtie, bowtie2, bwa, hisat2, minimap2; STAR's
+    ``Aligned.out.sam``) -- into the :class:`PackedAlignments` that :func:`read_bam` gives for the same records in a BAM
+    file, ``flag16``, ``mapq``, ``qlen`` and ``nh`` included: no ``samtools view -b`` in front (``pb_open_sam``; the lines
+    are parsed by ``csrc/sam_host.h`` on the worker pool, dealt out by byte ranges cut at line ends).
+    The file must be coordinate sorted unless `sort` is true (as for :func:`read_bam`: any record order, ``file_order``
+    set when records moved).  ``ValueError``: a malformed line (``"<path>: SAM line <n>: <what>"``, the lowest line
+    first), a file out of order without `sort`, compressed SAM.  `timing`: as for :func:`read_bam`."""
+    return read_bam(os.fspath(path), threads=threads, sort=sort, timing=timing, _sam=True)
+
+
+def read_sam_gpu(path, engine, timing=None, sort=False):
+    """:func:`read_sam`, parsed ON THE GPU (``pc_sam_open_path_flags``, ``csrc/sam_kernels.hip.h``): the text crosses PCIe
+    once, line starts, fields and CIGAR strings are parsed by kernels that run the host reader's line parser, and the
+    records go through the placement of :func:`read_bam_gpu` (order checks, or the radix sort with `sort`).  The result
+    equals ``read_sam(path, sort=sort)`` array for array, ``file_order`` included, and a refused file raises the same text.
+    `timing`: optional dict; receives ``upload_ms``, ``lines_ms`` (line starts), ``fields_ms``, ``place_ms`` (placement and
+    columns), ``records``, ``uploaded_bytes`` (the text bytes) and, with `sort`, what :func:`read_bam_gpu` adds."""
+    return read_bam_gpu(os.fspath(path), engine, timing=timing, sort=sort, _sam=True)
 
 
 def _region_tuples(regions):
@@ -356,6 +412,8 @@ def build_index(path, engine=None, out=None, overwrite=False, timing=None, fmt="
     if fmt == "bai" and min_shift != 14:
         raise ValueError("a BAI index has min_shift 14; pass fmt='csi' for another leaf size")
     path = os.fspath(path)
+    if is_sam_path(path):
+        raise ValueError("build_index: %s is SAM text, which has no index; convert it to BAM for region reads" % (path,))
     if not os.path.isfile(path):
         raise IOError("No such file: %r" % (path,))
     dest = os.fspath(out) if out is not None else path + "." + fmt
@@ -475,7 +533,7 @@ def _no_sort_with_regions(sort, regions):
         raise ValueError("sort=True cannot be combined with regions=: a region read goes through the index of a coordinate-sorted file")
 
 
-def read_bam_gpu(path, engine, timing=None, regions=None, index=None, sort=False):
+def read_bam_gpu(path, engine, timing=None, regions=None, index=None, sort=False, _sam=False):
     """The same :class:`PackedAlignments` as :func:`read_bam` gives for a whole file, decoded ON THE GPU: the file image
     goes to HBM as it is, the BGZF members are inflated there (one wave per member) and the BAM records decoded
     (``pc_bam_open``, ``csrc/bam_kernels.hip.h``); only the packed columns -- 13 bytes per record instead of the ~120 of
@@ -507,6 +565,8 @@ def read_bam_gpu(path, engine, timing=None, regions=None, index=None, sort=False
         cb, ce = np.ascontiguousarray(span["chunks"][:, 0]), np.ascontiguousarray(span["chunks"][:, 1])
         clib.check(L.pc_bam_open_chunks(engine._h, os.fsencode(path), len(cb), pv(cb), pv(ce), len(span["tid"]),
                                         pv(span["tid"]), pv(span["beg"]), pv(span["end"]), ctypes.byref(h)))
+    elif _sam:   # (read_sam_gpu: SAM text)
+        clib.check(L.pc_sam_open_path_flags(engine._h, os.fsencode(path), clib.PC_BAM_SORT if sort else 0, ctypes.byref(h)))
     else:
         # (the library maps the file itself: pages touched by all host threads at once, unmapped on a thread of its own)
         if sort:
@@ -547,6 +607,8 @@ def read_bam_gpu(path, engine, timing=None, regions=None, index=None, sort=False
             clib.check(L.pc_bam_timing(h, p(ms)))
             st = np.zeros(4, np.int64)
             clib.check(L.pc_bam_stats(h, p(st)))
+            if _sam:
+                timing.update(lines_ms=float(ms[1]), fields_ms=float(ms[2]), place_ms=float(ms[3]))
             timing.update(upload_ms=float(ms[0]), inflate_ms=float(ms[1]), chain_ms=float(ms[2]), decode_ms=float(ms[3]),
                           members=int(counts[5]), inflated_bytes=int(counts[6]), compressed_bytes=size, chain_restarts=int(counts[7]),
                           records=int(counts[3]), uploaded_bytes=int(st[0]), runs=int(st[1]))
@@ -570,7 +632,7 @@ def read_bam_gpu(path, engine, timing=None, regions=None, index=None, sort=False
     return out
 
 
-def read_bam(path, threads=0, regions=None, index=None, sort=False, timing=None):
+def read_bam(path, threads=0, regions=None, index=None, sort=False, timing=None, _sam=False):
     """Read a coordinate-sorted BAM file into a :class:`PackedAlignments`.
 
     `regions`: iterable of ``(chrom, start, end)`` (0-based, half-open) or objects with those
@@ -594,7 +656,7 @@ def read_bam(path, threads=0, regions=None, index=None, sort=False, timing=None)
     ``sorted_input`` and ``records_moved``."""
     _no_sort_with_regions(sort, regions)
     L = _load()
-    h = _pb_open(L, path, _index_path(path, index) if regions is not None else None)
+    h = _pb_open_sam(L, path) if _sam else _pb_open(L, path, _index_path(path, index) if regions is not None else None)
     try:
         if regions is None:
             rc = L.pb_load_sorted(h, int(threads)) if sort else L.pb_load(h, int(threads))

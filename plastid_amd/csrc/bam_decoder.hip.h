@@ -434,6 +434,7 @@ struct RecordTable {
     SortEvents sev;
     bool disorder = false;
 };
+int check_order(BamDecode &d, int64_t nrec, bool sort, RecordTable &t);
 // k_bam_fields, then the order checks -- or, with `sort`, the keys first: a file they find in order goes on exactly as
 // without the flag.  `n_misc` counters ([0] = ~0, the others 0) and `n_placed` entries of d_placed are the caller's to use.
 int decode_fields(BamDecode &d, const BamPlan &pl, const BamHeader &h, const BamRecords &recs, size_t n_misc, size_t n_placed, bool sort, RecordTable &t) {
@@ -454,6 +455,12 @@ int decode_fields(BamDecode &d, const BamPlan &pl, const BamHeader &h, const Bam
     t.g256 = (unsigned)((nrec + 255) / 256);
     hipLaunchKernelGGL(k_bam_fields, dim3(t.g256), dim3(256), 0, st, d.d_stream.p, pl.total_u, d.d_members.p, t.d_rec_base.p, d.d_chain.p, d.d_rec_off.p, pl.nm(), nrec,
                        h.n_ref, t.d_rec_member.p, t.d_recs.p);
+    return check_order(d, nrec, sort, t);
+}
+// Behind the fields kernel of either format (k_bam_fields, k_sam_fields), on the table it filled:
+int check_order(BamDecode &d, int64_t nrec, bool sort, RecordTable &t) {
+    using namespace pcbam;
+    hipStream_t st = d.st;
     if (sort) {
         unsigned long long dis = 0;
         HIP_TRY(hipEventRecord(t.sev.ev[0], st));
@@ -477,6 +484,7 @@ struct ColumnWork {
     DevBuf<int64_t> d_rbe;
     DevBuf<uint32_t> d_runs, d_staged_at, d_run_at, d_wide;   // per record: its runs, where it is staged and where its runs go; per staged record: wide or not
     int64_t n_staged = 0, n_runs = 0;
+    unsigned long long first_err = ~0ull;   // what place_records brought down (the SAM decoder words its own codes itself)
 };
 
 // Step 1 (region reads): keep what overlaps a requested region (htslib's overlap rule); everything else is as if it were not in the file.
@@ -545,7 +553,7 @@ int place_records(BamDecode &d, const BamHeader &h, const BamRecords &recs, bool
     HIP_TRY(hipMemcpyAsync(misc, t.d_misc.p, sizeof(misc), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     drained.armed = false;
-    w.n_staged = tot[0]; w.n_runs = tot[1];
+    w.n_staged = tot[0]; w.n_runs = tot[1]; w.first_err = misc[0];
     b.mapped = (int64_t)misc[1]; b.unplaced = (int64_t)misc[2];
     if (sort) {
         b.sort_ms = ms_between(t.sev.ev[0], t.sev.ev[1]) + (t.disorder ? ms_between(t.sev.ev[2], t.sev.ev[3]) : 0.0);
@@ -987,11 +995,17 @@ static int bam_open_span_retry(pc_engine *e, const void *image, int64_t size, co
     }
 }
 
+static int stage_opened(pc_engine *e, pc_bam *b, int64_t *mapped, const BamKnobs &knobs);
 static int add_alignment_bam_impl(pc_engine *e, const void *image, int64_t size, const char *name, int64_t *mapped, const UploadedHook *uploaded,
                                   const BamSpan *span, const BamKnobs &knobs, uint32_t open_flags = 0) {
     pc_bam *b = nullptr;
-    int rc = bam_open_span_retry(e, image, size, name, &b, uploaded, span, knobs, open_flags);
-    if (rc != PC_OK) return rc;
+    const int rc = bam_open_span_retry(e, image, size, name, &b, uploaded, span, knobs, open_flags);
+    return rc != PC_OK ? rc : stage_opened(e, b, mapped, knobs);
+}
+// The tail of every staging entry point (BAM and SAM text): the opened file's columns become a staged file of the engine,
+// and the handle is closed.
+static int stage_opened(pc_engine *e, pc_bam *b, int64_t *mapped, const BamKnobs &knobs) {
+    int rc = PC_OK;
     struct Closer { pc_bam *b; ~Closer() { pc_bam_close(b); } } closer{b};
     PoolScope pool_scope(&e->pool);
     const int64_t n = b->n, m = b->nrun, nw = (int64_t)b->wide_idx.size();

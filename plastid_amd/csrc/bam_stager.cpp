@@ -26,6 +26,7 @@
 #include <mutex>
 #include <thread>
 #include <fcntl.h>
+#include <functional>
 #include <sched.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -34,6 +35,7 @@
 
 #include "bam_host.h"
 #include "index_shape.h"
+#include "sam_host.h"
 
 namespace {
 
@@ -201,6 +203,7 @@ struct Bam {
     int64_t moved = 0;
     std::vector<uint32_t> perm;
     std::vector<int64_t> file_order;
+    bool is_sam = false;   // pb_open_sam: the file is SAM text (decode_sam reads it)
 };
 
 bool read_file(const std::string &path, std::vector<uint8_t> &buf) {
@@ -534,16 +537,22 @@ const uint8_t *decode_span_cols(const Bam &bam, Part &pt, Cols &cols, const uint
     return ret ? ret : q;
 }
 
+void keep_columns(Bam &bam, Part &pt, const Cols &cols);
 const uint8_t *decode_span(Bam &bam, Part &pt, const uint8_t *q, const uint8_t *limit, uint32_t n_ref, int64_t max_rec) {
     thread_local Cols cols;
     const uint8_t *stop = bam.sorting ? decode_span_cols<true>(bam, pt, cols, q, limit, n_ref, max_rec) : decode_span_cols<false>(bam, pt, cols, q, limit, n_ref, max_rec);
-    // the finished columns, at their exact size, into the load's arena
+    keep_columns(bam, pt, cols);
+    return stop;
+}
+
+// the finished columns of a piece, at their exact size, into the load's arena
+void keep_columns(Bam &bam, Part &pt, const Cols &cols) {
     const size_t n = cols.n, m = cols.blk_start.size();
     if (n) {
         uint8_t *mem = (uint8_t *)bam.arena.alloc(n * 21 + 64 * 9 + m * 8 + 64 * 2 + (bam.sorting ? n * 8 + 64 * 2 : 0));
         if (!mem) {
             if (pt.err_rec == INT64_MAX) { pt.err_rec = 0; pt.err_before_order = true; pt.err = "out of memory reading " + bam.path; }
-            return stop;
+            return;
         }
         auto take = [&](size_t bytes) { uint8_t *r = mem; mem += (bytes + 63) & ~(size_t)63; return r; };
         pt.tid = (int32_t *)take(n * 4); pt.pos = (int32_t *)take(n * 4); pt.alen = (uint16_t *)take(n * 2);
@@ -565,7 +574,6 @@ const uint8_t *decode_span(Bam &bam, Part &pt, const uint8_t *q, const uint8_t *
     }
     pt.n = n;
     pt.nrun = m;
-    return stop;
 }
 
 // The checks that span two pieces, and the flat offsets of every piece (bam.parts in file order).  The
@@ -895,6 +903,146 @@ int decode(Bam &bam, int nthreads) {
     lap("chain chunks");
     if (stitch_parts(bam, truncated, nthreads) != 0) return -1;
     lap("stitch");
+    bam.loaded = true;
+    return 0;
+}
+
+// ---------------------------------------------------------------- SAM text (pb_open_sam)
+// The lines of [q, limit) -- whole lines, `nlines` of them, the first being line `first_line` of the file -- into `pt`,
+// with the checks of decode_span_cols in its order: a line's own defects (sam_host.h), the order against the record in
+// front, the CIGAR defects the formats share, the order of the first aligned positions.
+template <bool kSort>
+void decode_sam_lines(const Bam &bam, Part &pt, Cols &cols, const uint8_t *q, const uint8_t *limit, int64_t nlines, int64_t first_line,
+                      const pcsam::SamRefs &refs) {
+    cols.clear();
+    cols.room((size_t)nlines + 1);
+    if (kSort) cols.room_sorted((size_t)nlines + 1);
+    size_t n = 0;
+    bool saw_unplaced = false, any_placed = false;
+    int32_t last_tid = -1, last_pos = -1, last_spos = -1;
+    auto bad = [&](int64_t i, bool before_order, const std::string &m) { pt.err_rec = i; pt.err_before_order = before_order; pt.err = m; };
+    for (int64_t i = 0; q < limit; ++i) {
+        const uint8_t *le = (const uint8_t *)std::memchr(q, '\n', (size_t)(limit - q));
+        const uint8_t *const lb = q;
+        if (!le) le = limit;
+        q = le < limit ? le + 1 : limit;
+        pcsam::SamRec r;
+        if (pcsam::sam_parse_line(lb, le, refs, r) >= pcsam::kSamOwnCodes) { bad(i, true, pcsam::sam_defect_message(bam.path.c_str(), first_line + i, r.err)); break; }
+        pt.total += 1;
+        if (!(r.flag & 0x4)) pt.mapped += 1;
+        if (!r.placed) {
+            pt.unplaced += 1;
+            if (kSort && !saw_unplaced) pt.first_unplaced_rec = i;
+            saw_unplaced = true;
+            continue;
+        }
+        if (kSort) {
+            any_placed = true;
+            cols.rpos[n] = r.pos; cols.rno[n] = (int32_t)i;
+        } else if (!any_placed) {        // its order against the previous piece is checked when stitching
+            any_placed = true;
+            pt.first_placed_rec = i;
+            pt.first_tid = r.tid; pt.first_pos = r.pos;
+            if (saw_unplaced) { bad(i, false, "BAM file is not coordinate sorted: " + bam.path); break; }
+        } else if (saw_unplaced || r.tid < last_tid || (r.tid == last_tid && r.pos < last_pos)) {
+            bad(i, false, "BAM file is not coordinate sorted: " + bam.path);
+            break;
+        }
+        if (r.err == pcsam::kSamUnknownOp) { bad(i, false, "unknown CIGAR operation in " + bam.path); break; }
+        if (r.err == pcsam::kSamEndBeyond) { bad(i, false, "alignment ends beyond 2^31 - 1"); break; }
+        if (r.err == pcsam::kSamTooLong) { bad(i, false, "alignment with more than 2^31 - 1 aligned positions"); break; }
+        const bool wide = r.L > 65535u || r.nruns > 255u || (r.L == 65535u && r.nruns == 255u);
+        if (wide) { pt.wide_idx.push_back((int64_t)n); pt.wide_alen.push_back((int32_t)r.L); pt.wide_nblk.push_back((int32_t)r.nruns); }
+        if (n == 0) pt.first_spos = r.spos;
+        else if (!kSort && last_tid == r.tid && last_spos > r.spos) {
+            bad(i, false, "alignment starting with a deletion breaks coordinate order; not supported");
+            break;
+        }
+        last_tid = r.tid; last_pos = r.pos; last_spos = r.spos;
+        cols.tid[n] = r.tid;
+        cols.pos[n] = r.spos;
+        cols.alen[n] = wide ? (uint16_t)65535 : (uint16_t)r.L;
+        cols.flags[n] = (r.flag & 0x10) ? 1 : 0;
+        cols.nblk[n] = wide ? (uint8_t)255 : (uint8_t)r.nruns;
+        cols.flag16[n] = r.flag; cols.mapq[n] = (uint8_t)r.mapq; cols.lseq[n] = r.lseq; cols.nh[n] = (uint16_t)(r.mapq >> 16);
+        ++n;
+        if (r.nruns >= 2) {
+            const uint8_t *cb, *ce, *end = le;
+            if (end > lb && end[-1] == '\r') --end;
+            pcsam::sam_cigar_field(lb, end, cb, ce);
+            (void)pcsam::sam_walk_cigar(cb, ce, (int64_t)r.pos, [&](int64_t ref, uint32_t len, bool new_run) {
+                if (new_run) { cols.blk_start.push_back((int32_t)ref); cols.blk_len.push_back((int32_t)len); }
+                else cols.blk_len.back() += (int32_t)len;
+            });
+        }
+    }
+    cols.n = n;
+    pt.any_placed = any_placed; pt.saw_unplaced = saw_unplaced;
+    pt.last_tid = last_tid; pt.last_pos = last_pos; pt.last_spos = last_spos;
+}
+
+// the header of a SAM file: the references into `bam`; `table`: their names as the line parser looks them up
+int sam_header(Bam &bam, const FileMap &file, pcsam::SamHeader &hd, pcsam::SamRefTable &table) {
+    if (!file.ok) return fail("cannot open " + bam.path);
+    if (pcsam::sam_looks_compressed(file.data(), file.size())) return fail(bam.path + ": " + pcsam::sam_compressed_text());
+    pcsam::parse_sam_header(file.data(), file.size(), hd, table);
+    if (hd.defect != pcsam::kSamOk) return fail(pcsam::sam_defect_message(bam.path.c_str(), hd.defect_line, hd.defect));
+    bam.ref_names = hd.ref_names;
+    bam.ref_lengths = hd.ref_lengths;
+    return 0;
+}
+
+// A whole SAM file -> bam.parts: the body is cut at line ends into pieces of about PB_SAM_PIECE bytes (default 4 MiB);
+// the worker pool counts the lines of every piece (which gives each piece its first line number), then parses them.
+int decode_sam(Bam &bam, int nthreads) {
+    Lap lap;
+    FileMap file(bam.path);
+    pcsam::SamHeader hd;
+    pcsam::SamRefTable table;
+    if (sam_header(bam, file, hd, table) != 0) return -1;
+    const pcsam::SamRefs refs = table.view();
+    const uint8_t *const body = file.data() + hd.body_off, *const end = file.data() + file.size();
+    int64_t piece = (int64_t)4 << 20;
+    if (const char *env = getenv("PB_SAM_PIECE")) piece = std::max(1, atoi(env));   // test knob: tiny pieces exercise the stitching
+    std::vector<const uint8_t *> cuts;
+    for (const uint8_t *q = body; q < end;) {
+        cuts.push_back(q);
+        if (end - q <= piece) break;
+        const uint8_t *nl = (const uint8_t *)std::memchr(q + piece - 1, '\n', (size_t)(end - (q + piece - 1)));
+        if (!nl) break;
+        q = nl + 1;
+    }
+    cuts.push_back(end);
+    const size_t nparts = cuts.size() - 1;
+    bam.parts.assign(nparts, Part());
+    std::vector<int64_t> nlines(nparts, 0), first_line(nparts + 1, hd.header_lines + 1);
+    auto on_pool = [&](const std::function<void(size_t)> &job) {
+        std::atomic<size_t> nextp(0);
+        auto worker = [&]() {
+            for (;;) {
+                const size_t k = nextp.fetch_add(1);
+                if (k >= nparts) return;
+                job(k);
+            }
+        };
+        std::vector<std::thread> pool;
+        const int nt = (int)std::min<size_t>((size_t)nthreads, std::max<size_t>(nparts, 1));
+        for (int t = 1; t < nt; ++t) pool.emplace_back(worker);
+        worker();
+        for (auto &t : pool) t.join();
+    };
+    on_pool([&](size_t k) { nlines[k] = pcsam::sam_count_lines(cuts[k], cuts[k + 1]); });
+    for (size_t k = 0; k < nparts; ++k) first_line[k + 1] = first_line[k] + nlines[k];
+    if (first_line[nparts] - first_line[0] >= (int64_t)0x7fffffff) return fail("more than 2^31-2 records per file are not supported: " + bam.path);
+    lap("sam line count");
+    on_pool([&](size_t k) {
+        thread_local Cols cols;
+        if (bam.sorting) decode_sam_lines<true>(bam, bam.parts[k], cols, cuts[k], cuts[k + 1], nlines[k], first_line[k], refs);
+        else decode_sam_lines<false>(bam, bam.parts[k], cols, cuts[k], cuts[k + 1], nlines[k], first_line[k], refs);
+        keep_columns(bam, bam.parts[k], cols);
+    });
+    lap("sam parse");
+    if (stitch_parts(bam, false, nthreads) != 0) return -1;
     bam.loaded = true;
     return 0;
 }
@@ -1351,6 +1499,21 @@ void *pb_open_indexed(const char *path, const char *index_path) {
     return h;
 }
 
+// A SAM TEXT file (an aligner's output as written; what pysam reads with AlignmentFile(path), and what `samtools view -b`
+// turns into BAM): the header is parsed here (pb_nref / pb_ref_name / pb_ref_length answer at once), pb_load and
+// pb_load_sorted read the lines with the parser of sam_host.h on the worker pool, and every pb_* accessor works as for BAM.
+// NULL (pb_last_error): the file cannot be opened, is compressed, or its header is malformed.
+void *pb_open_sam(const char *path) {
+    Bam *b = static_cast<Bam *>(pb_open(path));
+    if (!b) return nullptr;
+    b->is_sam = true;
+    FileMap file(b->path);
+    pcsam::SamHeader hd;
+    pcsam::SamRefTable table;
+    if (sam_header(*b, file, hd, table) != 0) { delete b; return nullptr; }
+    return b;
+}
+
 void pb_close(void *h) { delete static_cast<Bam *>(h); }
 
 // decode the whole file with `nthreads` inflate threads (<= 0: hardware concurrency)
@@ -1359,7 +1522,7 @@ int pb_load(void *h, int nthreads) {
     if (!b) return fail("pb_load: NULL handle");
     if (b->loaded) return 0;
     if (nthreads <= 0) nthreads = default_threads();
-    return decode(*b, nthreads);
+    return b->is_sam ? decode_sam(*b, nthreads) : decode(*b, nthreads);
 }
 
 // region-limited load through the BAI index: only records that overlap one of the `nreg` regions
@@ -1368,6 +1531,7 @@ int pb_load(void *h, int nthreads) {
 int pb_load_regions(void *h, int nthreads, int nreg, const char *const *names, const int64_t *start, const int64_t *end) {
     Bam *b = static_cast<Bam *>(h);
     if (!b || nreg < 0 || (nreg > 0 && (!names || !start || !end))) return fail("pb_load_regions: bad arguments");
+    if (b->is_sam) return fail("pb_load_regions: SAM text has no index: " + b->path);
     if (b->loaded) return fail("pb_load_regions: file already loaded");
     if (nthreads <= 0) nthreads = default_threads();
     return decode_regions(*b, nthreads, nreg, names, start, end);
@@ -1577,7 +1741,7 @@ int pb_load_sorted(void *h, int nthreads) {
     if (b->loaded) return b->sort_requested ? 0 : fail("pb_load_sorted: file already loaded");
     if (nthreads <= 0) nthreads = default_threads();
     b->sorting = b->sort_requested = true;
-    if (decode(*b, nthreads) != 0) return -1;
+    if ((b->is_sam ? decode_sam(*b, nthreads) : decode(*b, nthreads)) != 0) return -1;
     if (sort_loaded(*b) != 0) { b->loaded = false; return -1; }
     return 0;
 }

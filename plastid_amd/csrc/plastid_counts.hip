@@ -3793,3 +3793,4 @@ int pc_read_mapped_reads(pc_engine *e, pc_plan *p, uint32_t *rec, int64_t total)
 
 // ================================================================== compressed BAM on the GPU (bam_decoder.hip.h, bam_kernels.hip.h)
 #include "bam_decoder.hip.h"
+#include "sam_decoder.hip.h"

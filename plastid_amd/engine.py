@@ -175,6 +175,21 @@ class Engine(object):
         self.nfiles += 1
         return int(mapped.value)
 
+    def add_sam(self, path, sort=False):
+        """Stage a SAM TEXT file -- an aligner's output as written -- WITHOUT its records visiting the host
+        (``pc_add_alignment_sam_path_flags``): the text goes to HBM, its lines are parsed and the packed columns staged by
+        kernels.  Returns the number of mapped reads (lines with FLAG bit 0x4 unset).  The engine then counts exactly as
+        after :meth:`add_bam` of the same records in a BAM file.  `sort`: the file may be in any record order."""
+        import os
+        from ._lib import PC_BAM_SORT
+        path = os.fspath(path)
+        if not os.path.isfile(path):
+            raise IOError("No such file: %r" % (path,))
+        mapped = ctypes.c_int64(0)
+        check(self._lib.pc_add_alignment_sam_path_flags(self._h, os.fsencode(path), PC_BAM_SORT if sort else 0, ctypes.byref(mapped)))
+        self.nfiles += 1
+        return int(mapped.value)
+
     def num_records(self, file_index):
         """Records staged for file `file_index`."""
         return int(self._lib.pc_num_records(self._h, int(file_index)))

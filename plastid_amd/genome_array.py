@@ -40,6 +40,36 @@ from .roitools import GenomicSegment, SegmentChain
 #: HIP kernels, bam.read_bam_gpu): below it the host reader's latency wins
 GPU_DECODE_MIN_BYTES = 32 << 20
 
+#: the same threshold for SAM text (bam.read_sam_gpu against bam.read_sam on 16 threads), from the measured crossover
+#: (profiles/sam_text/NOTES.md): equal at 1 MB, the GPU 1.8x faster at 2 MB and 2.7x at 4 MB on a warm engine
+GPU_DECODE_MIN_BYTES_SAM = 4 << 20
+
+
+def _no_regions_for_sam(path, regions):
+    if regions is not None:
+        raise ValueError("regions= cannot be used with %s: SAM text has no index; convert it to BAM for region reads" % (path,))
+
+
+def _open_sam_source(src, regions, engine, decode, sort):
+    """`_open_alignment_source` for a name that ends in ``.sam``: the SAM readers under the same `decode` rule."""
+    from .bam import read_sam, read_sam_gpu
+    _no_regions_for_sam(src, regions)
+    on_gpu = decode == "gpu" or (decode == "auto" and os.path.exists(src) and os.path.getsize(src) >= GPU_DECODE_MIN_BYTES_SAM)
+    if on_gpu and engine is not None:
+        if decode == "gpu":
+            aln = read_sam_gpu(src, engine, sort=sort)
+            aln.decoder = "gpu"
+            return aln
+        try:   # "auto": the host reader is the second opinion, and its verdict the one the caller sees
+            aln = read_sam_gpu(src, engine, sort=sort)
+            aln.decoder = "gpu"
+            return aln
+        except (ValueError, IOError, OSError, RuntimeError):
+            pass
+    aln = read_sam(src, sort=sort)
+    aln.decoder = "host"
+    return aln
+
 
 def _open_alignment_source(src, regions=None, engine=None, decode="auto", index=None, sort=False):
     """Filenames are read with the package's own BAM readers; objects are used as
@@ -53,6 +83,8 @@ def _open_alignment_source(src, regions=None, engine=None, decode="auto", index=
         from .bam import read_bam, read_bam_gpu
         if decode not in ("auto", "host", "gpu"):
             raise ValueError("decode must be 'auto', 'host' or 'gpu', got %r" % (decode,))
+        if src.lower().endswith(".sam"):   # SAM text: by its name only
+            return _open_sam_source(src, regions, engine, decode, sort)
         named = {} if index is None else dict(index=index)   # (the readers' calls are unchanged without the keyword)
         if sort:   # (whole files in any record order: bam.read_bam)
             named["sort"] = True
@@ -186,7 +218,11 @@ class BAMGenomeArray(object):
             from .bam import bam_header
             if not bamfiles or not all(isinstance(x, str) for x in bamfiles):
                 raise ValueError("keep_reads=False takes BAM files named by path")
-            self.bamfiles = [_DeviceAlignments(x, *bam_header(x)) for x in bamfiles]
+            from .bam import is_sam_path, sam_header
+            for x in bamfiles:
+                if is_sam_path(x):
+                    _no_regions_for_sam(x, kwargs.get("regions"))
+            self.bamfiles = [_DeviceAlignments(x, *(sam_header(x) if is_sam_path(x) else bam_header(x))) for x in bamfiles]
             if any(b.references != self.bamfiles[0].references for b in self.bamfiles):
                 raise ValueError("keep_reads=False needs the same reference list in every file")
         else:
@@ -213,7 +249,9 @@ class BAMGenomeArray(object):
             self._packed = self.bamfiles
             self._engine.clear_alignments()
             for fi, b in enumerate(self.bamfiles):
-                if kwargs.get("regions") is not None:   # only what overlaps the regions is staged; `mapped` is the index's whole-file count, as pysam's
+                if b.filename.lower().endswith(".sam"):   # SAM text (Engine.add_sam)
+                    b.mapped = self._engine.add_sam(b.filename, sort=sort)
+                elif kwargs.get("regions") is not None:   # only what overlaps the regions is staged; `mapped` is the index's whole-file count, as pysam's
                     from .bam import resolve_regions, _index_path
                     index = _index_path(b.filename, kwargs.get("index"), self._engine)
                     kept = self._engine.add_bam(b.filename, regions=kwargs["regions"], index=index)
