@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 14
+#define PC_ABI_VERSION 15
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -504,6 +504,56 @@ int pc_bam_index_stats(pc_bam_index *idx, int64_t *out8);
  * checks, [4] index kernels, [5] read-back, [6] host finish, [7] the whole call (wall clock) */
 int pc_bam_index_timing(pc_bam_index *idx, double *ms8);
 int pc_bam_index_close(pc_bam_index *idx);
+
+/* ---- COUNT TRACKS: a device-resident GenomeArray read from bedGraph / wiggle text (revision 15)
+ * A pc_track is the reference's GenomeArray (plastid/genomics/genome_array.py:1323-1533) as a read-and-count object: one
+ * float64 cell per contig, strand slot and position in HBM, filled from track text and read through a gather kernel.
+ * pc_track_create (GenomeArray.__init__, :1354-1387): nstrands strand slots (1 .. 8; the binding maps '+', '-' ... to
+ * 0, 1 ...); min_chr_size is the length an undeclared contig is born with.  pc_track_declare (the chr_lengths of :1382-1387)
+ * names a contig and its length before any text is added; declared contigs come first in the contig order.  A track
+ * belongs to its engine: pc_destroy takes the engine's remaining tracks with it, and their handles are dead then. */
+typedef struct pc_track pc_track;
+int pc_track_create(pc_engine *e, int nstrands, int64_t min_chr_size, pc_track **out);
+int pc_track_destroy(pc_track *t);
+int pc_track_declare(pc_track *t, const char *name, int64_t length);
+/* add_from_wiggle (genome_array.py:1978-1994) over WiggleReader (plastid/readers/wiggle.py:43-174): the text -- bedGraph,
+ * variableStep and fixedStep wiggle, mixed freely -- is uploaded as it is and parsed by the kernels of
+ * csrc/track_kernels.hip.h; every yielded (contig, start, stop, value) is ADDED to cells [start, stop) of the strand slot,
+ * overlapping lines in file order, a second call on top of the first.  The host reads only the lines that change the
+ * reader's state (data headers, and bedGraph lines that name another contig than the bedGraph line before), the lines with
+ * a token that is not plain (csrc/track_host.h: Python's int / float grammar and strtod) and the lines that reach a
+ * contig's length.  Contigs not declared are born in the order of their first yielded line with min_chr_size; a line
+ * whose end reaches the current length sets it to end + 10 000 (:1593-1602).  Cells are stored up to the furthest end
+ * written per contig and strand slot (the extent), not up to the length.  A malformed line is PC_ERR_ARG with
+ * "<path>: track line <n>: <what>" (n 1-based), the lowest line first, and leaves every cell as it was: a negative start,
+ * a token Python's int / float refuse, a data line under a header without chrom=, a fixedStep data line of several tokens,
+ * coordinates beyond 2^40.  "\r\n" line ends and a last line without '\n' are read.  `name`: what messages call the text. */
+int pc_track_add_text(pc_track *t, const void *image, int64_t size, const char *name, int strand_slot);
+int pc_track_add_path(pc_track *t, const char *path, int strand_slot);
+/* chroms() / lengths() (genome_array.py:1613-1615 and the arrays' sizes): contigs in their order -- declared ones, then the
+ * others by first yielded line; the extent is the number of cells stored for one strand slot (positions beyond it are 0).
+ * -1 / NULL: bad index. */
+int pc_track_num_contigs(pc_track *t);
+const char *pc_track_contig_name(pc_track *t, int i);
+int64_t pc_track_contig_length(pc_track *t, int i);
+int64_t pc_track_contig_extent(pc_track *t, int i, int strand_slot);
+/* get (genome_array.py:1477-1533) for a table of segments in one launch: position i of segment s -- genomic start[s] + i
+ * on contig[s] (index into the contig order, -1: unknown) and strand_slot[s] -- goes to
+ * host_out[out_off[s] + out_step[s] * i], out_step +1 or -1; a chain is its segments at their spliced offsets (reversed
+ * for '-': SegmentChain.get_counts, roitools.pyx:3259-3271).  Positions below 0, beyond the extent or on an unknown contig
+ * are 0.  normalize: 1e6 * v / sum, the reference's order for this class (:1528).  Elements no segment writes are 0. */
+int pc_track_gather(pc_track *t, int64_t nseg, const int32_t *contig, const int32_t *strand_slot, const int64_t *start, const int64_t *end,
+                    const int64_t *out_off, const int8_t *out_step, int64_t out_elems, int normalize, double *host_out);
+/* sum (genome_array.py:1389-1392): a fixed-tree reduction over every cell, the same bits run to run, cached until the
+ * next add.  Equal to the reference's for integer values with a total below 2^53; otherwise a reordering of its sum. */
+int pc_track_sum(pc_track *t, double *sum);
+/* the last add: [0] lines, [1] yielded lines, [2] escaped lines (a token that is not plain: converted on the host),
+ * [3] state records, [4] overlapping lines (members of clusters of several lines, applied in file order), [5] lines that
+ * reached a contig's length */
+int pc_track_stats(pc_track *t, int64_t *out6);
+/* milliseconds of the last add on the engine's stream: [0] upload, [1] line starts, [2] classify + state records,
+ * [3] fields (the host's conversion of escaped lines included), [4] growth, sort and apply */
+int pc_track_timing(pc_track *t, double *ms5);
 
 #ifdef __cplusplus
 }

@@ -12,5 +12,6 @@ from .map_factories import (CenterMapFactory, FivePrimeMapFactory, FlagFilterFac
                             StratifiedVariableFivePrimeMapFactory, ThreePrimeMapFactory,
                             VariableFivePrimeMapFactory)
 from .genome_array import BAMGenomeArray, DenseGenomeArray  # noqa: F401
+from .track import GenomeArray, WiggleTable, read_wiggle  # noqa: F401
 
 __version__ = "0.1.0"

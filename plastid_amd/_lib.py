@@ -120,6 +120,19 @@ SIGNATURES = {
     "pc_bam_index_stats": (_int, [_vp, _vp]),
     "pc_bam_index_timing": (_int, [_vp, _vp]),
     "pc_bam_index_close": (_int, [_vp]),
+    "pc_track_create": (_int, [_vp, _int, _i64, _pp]),
+    "pc_track_destroy": (_int, [_vp]),
+    "pc_track_declare": (_int, [_vp, ctypes.c_char_p, _i64]),
+    "pc_track_add_text": (_int, [_vp, _vp, _i64, ctypes.c_char_p, _int]),
+    "pc_track_add_path": (_int, [_vp, ctypes.c_char_p, _int]),
+    "pc_track_num_contigs": (_int, [_vp]),
+    "pc_track_contig_name": (ctypes.c_char_p, [_vp, _int]),
+    "pc_track_contig_length": (_i64, [_vp, _int]),
+    "pc_track_contig_extent": (_i64, [_vp, _int, _int]),
+    "pc_track_gather": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _vp]),
+    "pc_track_sum": (_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
+    "pc_track_stats": (_int, [_vp, _vp]),
+    "pc_track_timing": (_int, [_vp, _vp]),
 }
 
 _lib = None
@@ -129,7 +142,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def load():

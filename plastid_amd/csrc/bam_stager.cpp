@@ -36,6 +36,7 @@
 #include "bam_host.h"
 #include "index_shape.h"
 #include "sam_host.h"
+#include "track_host.h"
 
 namespace {
 
@@ -1760,6 +1761,43 @@ int pb_file_order(void *h, int64_t *rec_no) {
     if (!b || !b->loaded) return fail("pb_file_order: file not loaded");
     if (b->perm.empty()) return fail("pb_file_order: no record was moved (the records are in the order of the file)");
     std::memcpy(rec_no, b->file_order.data(), b->file_order.size() * 8);
+    return 0;
+}
+
+// ---------------------------------------------------------------- count tracks as text (track_host.h)
+// A bedGraph / wiggle text read on the host by the parser the device import runs: the reference's WiggleReader
+// (plastid/readers/wiggle.py:43-174) as columns.  NULL (pb_last_error): a malformed line, "<name>: track line <n>: <what>".
+void *pb_track_read(const void *image, int64_t size, const char *name) {
+    if (size < 0 || (size > 0 && !image)) { fail("pb_track_read: bad arguments"); return nullptr; }
+    pctrack::TrackTable *t = new pctrack::TrackTable();
+    pctrack::read_track((const uint8_t *)image, (size_t)size, *t);
+    if (t->defect != pctrack::kTrkOk) {
+        fail(pctrack::track_defect_message(name, t->defect_line, t->defect));
+        delete t;
+        return nullptr;
+    }
+    return t;
+}
+void pb_track_close(void *h) { delete static_cast<pctrack::TrackTable *>(h); }
+int64_t pb_track_rows(void *h) { return h ? (int64_t)static_cast<pctrack::TrackTable *>(h)->contig.size() : -1; }
+int pb_track_nchrom(void *h) { return h ? (int)static_cast<pctrack::TrackTable *>(h)->names.size() : -1; }
+const char *pb_track_chrom(void *h, int i) { return static_cast<pctrack::TrackTable *>(h)->names[(size_t)i].c_str(); }
+// the columns, and per row its 0-based line and whether a token of it was not plain
+int pb_track_fill(void *h, int32_t *chrom, int64_t *start, int64_t *stop, double *value, int64_t *line, uint8_t *escaped) {
+    pctrack::TrackTable *t = static_cast<pctrack::TrackTable *>(h);
+    if (!t) return fail("pb_track_fill: NULL handle");
+    const size_t n = t->contig.size();
+    if (n) {
+        std::memcpy(chrom, t->contig.data(), n * 4); std::memcpy(start, t->start.data(), n * 8); std::memcpy(stop, t->stop.data(), n * 8);
+        std::memcpy(value, t->value.data(), n * 8); std::memcpy(line, t->line.data(), n * 8); std::memcpy(escaped, t->escaped.data(), n);
+    }
+    return 0;
+}
+// [0] lines, [1] yielded lines, [2] escaped lines, [3] state records
+int pb_track_stats(void *h, int64_t *out4) {
+    pctrack::TrackTable *t = static_cast<pctrack::TrackTable *>(h);
+    if (!t || !out4) return fail("pb_track_stats: bad arguments");
+    out4[0] = t->lines; out4[1] = (int64_t)t->contig.size(); out4[2] = t->n_escaped; out4[3] = t->states;
     return 0;
 }
 

@@ -658,6 +658,8 @@ struct Knobs {
     }
 };
 
+static void destroy_tracks_of(pc_engine *e);   // (track_decoder.hip.h)
+
 struct pc_engine {
     DevPool pool;   // first member: outlives every buffer of the engine
     DevBuf<uint8_t> plan_scratch[3];   // working arrays of the GPU plan builder (per segment, per piece, per output piece): grown, never shrunk
@@ -672,6 +674,7 @@ struct pc_engine {
     hipEvent_t ev_pinned = nullptr;      // end of the last copy out of `pinned`
     hipEvent_t ev[8] = {};
     std::vector<StagedFile *> files;
+    std::vector<pc_track *> tracks;   // the count tracks made on this engine (track_decoder.hip.h): they go with it
     int ntid = 0;
     DevBuf<FileView> d_files;
     bool files_dirty = true;
@@ -1401,6 +1404,7 @@ int pc_destroy(pc_engine *e) {
     if (!e) return PC_OK;
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
+    destroy_tracks_of(e);
     for (auto *f : e->files) delete f;
     e->files.clear();
     for (auto &ev : e->ev)
@@ -3794,3 +3798,4 @@ int pc_read_mapped_reads(pc_engine *e, pc_plan *p, uint32_t *rec, int64_t total)
 // ================================================================== compressed BAM on the GPU (bam_decoder.hip.h, bam_kernels.hip.h)
 #include "bam_decoder.hip.h"
 #include "sam_decoder.hip.h"
+#include "track_decoder.hip.h"

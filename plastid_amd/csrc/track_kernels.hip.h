@@ -1,0 +1,312 @@
+// track_kernels.hip.h -- count tracks as text on the GPU (track_host.h says what a line means; track_decoder.hip.h drives
+// the kernels).  The text lies in HBM as it is on disk; the line starts are those of sam_kernels.hip.h.
+//   import:  k_track_classify       one lane per line: class and token count; the line is a state line candidate
+//            k_track_states         a bedGraph line starts a state unless the header / bedGraph line before it is a
+//                                   bedGraph line of the same name; the state lines are listed for the host
+//            k_track_fields         one lane per line: governing record by bisection, start / stop / value; escaped lines,
+//                                   the lowest defect
+//            k_track_patch          the host's numbers of the escaped lines
+//            k_track_keys           growth lines, per-contig furthest end and first yielding line; (contig, start) sort
+//                                   keys of the lines that write cells
+//            k_track_clusters       lines that overlap the running maximum end join the cluster of the line before
+//            k_track_fill_short / k_track_fill    singleton clusters, in parallel
+//            k_track_fill_ordered   clusters of several lines, every cell in file order
+//   query:   k_track_gather         k_dense_gather over float64 cells
+//            k_track_sum_partial / k_track_sum_final   fixed-tree sum
+// Every byte access lies in [0, text_len); every cell access inside the strand's extent.
+// Part of the one translation unit of plastid_counts.hip (behind sam_kernels.hip.h and dense_kernels.hip.h).
+#pragma once
+#include "track_host.h"
+
+namespace pctrack {
+
+constexpr uint32_t kNoLine = 0xffffffffu;
+constexpr int kShortLen = 32;                  // lines up to this many positions are filled by one lane
+constexpr unsigned long long kNoDefect = ~0ull;
+
+// line i is [line_start[i], line_start[i + 1] - 1), clamped to the text
+__device__ __forceinline__ void line_bounds(const uint64_t *__restrict__ line_start, uint64_t text_len, int64_t i, uint64_t &b, uint64_t &e) {
+    b = line_start[i]; e = line_start[i + 1] - 1;
+    if (e > text_len) e = text_len;
+    if (b > e) b = e;
+}
+
+// cls[i]: class | token count << 4.  sig[i]: i for a header or bedGraph line, -1 otherwise (max-scanned by the caller);
+// is_data[i]: 1 for a data line (summed by the caller).
+__global__ __launch_bounds__(256) void k_track_classify(const uint8_t *__restrict__ text, uint64_t text_len, const uint64_t *__restrict__ line_start, int64_t nline,
+                                                        uint8_t *__restrict__ cls, int32_t *__restrict__ sig, uint32_t *__restrict__ is_data) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nline) return;
+    uint64_t b, e;
+    line_bounds(line_start, text_len, i, b, e);
+    const LineClass c = classify_line(text + b, text + e);
+    cls[i] = (uint8_t)(c.cls | (c.ntok << 4));
+    sig[i] = (c.cls == kHeader || c.cls == kBed) ? (int32_t)i : -1;
+    is_data[i] = c.cls == kData ? 1u : 0u;
+}
+
+// prev_sig[i]: the last header or bedGraph line in front of line i (-1: none).  State lines are appended to `state_lines`
+// in any order (the host sorts them); *n_state counts them.
+__global__ __launch_bounds__(256) void k_track_states(const uint8_t *__restrict__ text, uint64_t text_len, const uint64_t *__restrict__ line_start, int64_t nline,
+                                                      const uint8_t *__restrict__ cls, const int32_t *__restrict__ prev_sig,
+                                                      uint32_t *__restrict__ state_lines, uint32_t *__restrict__ n_state) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nline) return;
+    const int c = cls[i] & 15;
+    bool state = c == kHeader;
+    if (c == kBed) {
+        const int32_t j = prev_sig[i];
+        state = true;
+        if (j >= 0 && (cls[j] & 15) == kBed) {
+            uint64_t b, e, pb, pe;
+            line_bounds(line_start, text_len, i, b, e);
+            line_bounds(line_start, text_len, j, pb, pe);
+            state = !tok_equal(next_token(text + b, text + e), next_token(text + pb, text + pe));
+        }
+    }
+    if (state) state_lines[atomicAdd(n_state, 1u)] = (uint32_t)i;
+}
+
+// What the import keeps of every line (24 bytes).
+struct LineRec {
+    int64_t start, stop;
+    double value;
+};
+
+// counters of one import, in HBM
+struct TrackCounters {
+    unsigned long long first_err;     // (line << 8 | code) of the lowest defect, kNoDefect: none
+    uint32_t n_state, n_yield, n_escaped, n_growth, n_long, n_multi, n_valid, pad;
+};
+
+// One lane per line.  contig_of[i]: the contig of a yielding line without a defect, -1 otherwise.  A line all of whose
+// tokens are plain is checked here (check_fields); an escaped line is listed, and converted and checked by the host.
+__global__ __launch_bounds__(256) void k_track_fields(const uint8_t *__restrict__ text, uint64_t text_len, const uint64_t *__restrict__ line_start, int64_t nline,
+                                                      const uint8_t *__restrict__ cls, const uint32_t *__restrict__ data_index,
+                                                      const StateRec *__restrict__ recs, int64_t nrec,
+                                                      LineRec *__restrict__ out, int32_t *__restrict__ contig_of, uint32_t *__restrict__ escaped_lines,
+                                                      TrackCounters *__restrict__ cnt) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nline) return;
+    const int c = cls[i] & 15;
+    contig_of[i] = -1;
+    if (c != kBed && c != kData) return;
+    const int64_t g = governing(recs, nrec, i);
+    if (g < 0) return;
+    uint64_t b, e;
+    line_bounds(line_start, text_len, i, b, e);
+    const LineClass lc = classify_line(text + b, text + e);
+    const StateRec r = recs[g];
+    const LineOut o = line_fields<FastOnly>(lc, &r, (int64_t)data_index[i]);
+    if (!o.yields) return;
+    atomicAdd(&cnt->n_yield, 1u);
+    int err = o.err;
+    if (err == kTrkOk && !o.escaped) err = check_fields(o);
+    if (err != kTrkOk) { atomicMin(&cnt->first_err, ((unsigned long long)i << 8) | (unsigned long long)err); return; }
+    if (o.escaped) { escaped_lines[atomicAdd(&cnt->n_escaped, 1u)] = (uint32_t)i; return; }
+    LineRec lr;
+    lr.start = o.start; lr.stop = o.stop; lr.value = o.value;
+    out[i] = lr;
+    contig_of[i] = o.contig;
+}
+
+// the host's numbers of the escaped lines
+__global__ __launch_bounds__(256) void k_track_patch(const uint32_t *__restrict__ lines, const LineRec *__restrict__ vals, const int32_t *__restrict__ contigs,
+                                                     uint32_t n, LineRec *__restrict__ out, int32_t *__restrict__ contig_of) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < n) { out[lines[k]] = vals[k]; contig_of[lines[k]] = contigs[k]; }
+}
+
+// One lane per line, on the final numbers.  len0[c]: the length contig c has before this call; a line whose end reaches it
+// goes to growth_lines.  furthest[c]: max end of the lines that write cells; first_line[c]: min line that yields on c.
+// key: the sort key of a line that writes cells (contig << 41 | start; kNoKey for every other line).
+constexpr uint64_t kNoKey = ~0ull;
+__global__ __launch_bounds__(256) void k_track_keys(const LineRec *__restrict__ recs, const int32_t *__restrict__ contig_of, const uint8_t *__restrict__ cls,
+                                                    int64_t nline, const int64_t *__restrict__ len0, int ncontig,
+                                                    unsigned long long *__restrict__ furthest, uint32_t *__restrict__ first_line,
+                                                    uint32_t *__restrict__ growth_lines, uint64_t *__restrict__ key, uint32_t *__restrict__ idx,
+                                                    TrackCounters *__restrict__ cnt) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    // (every lane of the wave stays to the end: the wave folds its lines before it touches the per-contig words)
+    bool yields = false, writes = false;
+    int32_t t = -1;
+    LineRec r;
+    r.start = 0; r.stop = 0; r.value = 0.0;
+    if (i < nline) {
+        const int c = cls[i] & 15;
+        uint64_t k = kNoKey;
+        if (c == kBed || c == kData) {
+            t = contig_of[i];
+            yields = t >= 0 && t < ncontig;
+            if (yields) {
+                r = recs[i];
+                if (r.stop >= len0[t]) growth_lines[atomicAdd(&cnt->n_growth, 1u)] = (uint32_t)i;
+                writes = r.stop > r.start;                      // an empty interval writes nothing
+                if (writes) { atomicAdd(&cnt->n_valid, 1u); k = ((uint64_t)t << 41) | (uint64_t)r.start; }
+            }
+        }
+        key[i] = k;
+        idx[i] = (uint32_t)i;
+    }
+    // the lines of a wave are neighbours in the file and nearly always on one contig: one atomic pair per wave then
+    const unsigned long long m = __ballot(yields);
+    if (m == 0ull) return;
+    const int leader = __ffsll((long long)m) - 1;
+    const int32_t t_lead = __shfl(t, leader, 64);
+    if (__ballot(yields && t != t_lead) == 0ull) {
+        uint32_t mn = yields ? (uint32_t)i : kNoLine;
+        unsigned long long mx = writes ? (unsigned long long)r.stop : 0ull;
+        for (int o = 32; o > 0; o >>= 1) {
+            const uint32_t a = __shfl_xor(mn, o, 64);
+            const unsigned long long b = __shfl_xor(mx, o, 64);
+            mn = a < mn ? a : mn;
+            mx = b > mx ? b : mx;
+        }
+        if ((int)(threadIdx.x & 63) == leader) {
+            atomicMin(&first_line[t_lead], mn);
+            if (mx) atomicMax(&furthest[t_lead], mx);
+        }
+    } else if (yields) {
+        atomicMin(&first_line[t], (uint32_t)i);
+        if (writes) atomicMax(&furthest[t], (unsigned long long)r.stop);
+    }
+}
+
+// Sorted order (key, idx), nv lines with a key.  end_key[k] = contig << 41 | stop, max-scanned exclusively by the caller.
+__global__ __launch_bounds__(256) void k_track_end_keys(const uint64_t *__restrict__ key, const uint32_t *__restrict__ idx, const LineRec *__restrict__ recs,
+                                                        int64_t nv, uint64_t *__restrict__ end_key) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nv) return;
+    end_key[k] = (key[k] & ~(((uint64_t)1 << 41) - 1)) | (uint64_t)recs[idx[k]].stop;
+}
+
+// head[k] = k when sorted line k starts a cluster -- it does not begin below the furthest end of the lines in front of it
+// on its contig -- and 0 otherwise (max-scanned inclusively by the caller: the cluster's first line)
+__global__ __launch_bounds__(256) void k_track_clusters(const uint64_t *__restrict__ key, const uint64_t *__restrict__ prev_end, int64_t nv,
+                                                        int32_t *__restrict__ head) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nv) return;
+    const uint64_t mask = ((uint64_t)1 << 41) - 1;
+    bool overlaps = false;
+    if (k > 0) {
+        const uint64_t p = prev_end[k];
+        overlaps = (p >> 41) == (key[k] >> 41) && (key[k] & mask) < (p & mask);
+    }
+    head[k] = overlaps ? 0 : (int32_t)k;
+}
+
+// Singleton clusters: short lines are filled here, long ones listed; lines of larger clusters are listed as
+// (cluster << 32 | line) keys for the ordered pass.  cells: the strand's cells of every contig, cell_off[c] its first.
+__global__ __launch_bounds__(256) void k_track_fill_short(const uint32_t *__restrict__ idx, const int32_t *__restrict__ head, int64_t nv,
+                                                          const LineRec *__restrict__ recs, const int32_t *__restrict__ contig_of,
+                                                          const int64_t *__restrict__ cell_off, double *__restrict__ cells,
+                                                          uint32_t *__restrict__ long_lines, uint64_t *__restrict__ multi_keys, TrackCounters *__restrict__ cnt) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nv) return;
+    const uint32_t i = idx[k];
+    const bool single = head[k] == (int32_t)k && (k + 1 == nv || head[k + 1] == (int32_t)(k + 1));
+    if (!single) { multi_keys[atomicAdd(&cnt->n_multi, 1u)] = ((uint64_t)(uint32_t)head[k] << 32) | (uint64_t)i; return; }
+    const LineRec r = recs[i];
+    const int64_t n = r.stop - r.start;
+    if (n > kShortLen) { long_lines[atomicAdd(&cnt->n_long, 1u)] = i; return; }
+    double *dst = cells + cell_off[contig_of[i]] + r.start;
+    for (int64_t p = 0; p < n; ++p) dst[p] = dst[p] + r.value;
+}
+
+// one workgroup per long singleton line, item by item (2 048 positions: 256 lanes x 8)
+__global__ __launch_bounds__(256) void k_track_fill(const uint32_t *__restrict__ long_lines, const LineRec *__restrict__ recs, const int32_t *__restrict__ contig_of,
+                                                    const int64_t *__restrict__ cell_off, double *__restrict__ cells) {
+    const uint32_t i = long_lines[blockIdx.x];
+    const LineRec r = recs[i];
+    double *dst = cells + cell_off[contig_of[i]] + r.start;
+    const int64_t n = r.stop - r.start;
+    for (int64_t a = 0; a < n; a += pcdense::kItemLen)
+#pragma unroll
+        for (int k = 0; k < pcdense::kPerLane; ++k) {
+            const int64_t p = a + threadIdx.x + k * 256;
+            if (p < n) dst[p] = dst[p] + r.value;
+        }
+}
+
+// Clusters of several lines.  multi_keys: (cluster << 32 | line), sorted, so that a cluster's lines stand together in
+// file order.  One workgroup per entry; the one at a cluster's first entry serves the cluster: every lane takes cells of
+// the cluster's extent and adds the lines that cover the cell in file order.  Quadratic in the cluster (cells x lines),
+// exact for any overlap.
+__global__ __launch_bounds__(256) void k_track_fill_ordered(const uint64_t *__restrict__ multi_keys, uint32_t nm, const LineRec *__restrict__ recs,
+                                                            const int32_t *__restrict__ contig_of, const int64_t *__restrict__ cell_off,
+                                                            double *__restrict__ cells) {
+    const uint32_t k0 = blockIdx.x;
+    const uint64_t cluster = multi_keys[k0] >> 32;
+    if (k0 > 0 && (multi_keys[k0 - 1] >> 32) == cluster) return;
+    uint32_t k1 = k0;
+    int64_t lo = INT64_MAX, hi = INT64_MIN;
+    while (k1 < nm && (multi_keys[k1] >> 32) == cluster) {
+        const LineRec r = recs[(uint32_t)multi_keys[k1]];
+        lo = r.start < lo ? r.start : lo;
+        hi = r.stop > hi ? r.stop : hi;
+        ++k1;
+    }
+    double *base = cells + cell_off[contig_of[(uint32_t)multi_keys[k0]]];
+    for (int64_t p = lo + threadIdx.x; p < hi; p += 256) {
+        double v = base[p];
+        for (uint32_t k = k0; k < k1; ++k) {
+            const LineRec r = recs[(uint32_t)multi_keys[k]];
+            if (p >= r.start && p < r.stop) v = v + r.value;
+        }
+        base[p] = v;
+    }
+}
+
+// k_dense_gather over float64 cells: one workgroup per item.  normalize: 1e6 * v / sum (the reference's order for this
+// class, genome_array.py:1528).
+__global__ __launch_bounds__(pcdense::kGatherWG) void k_track_gather(const pcdense::Item *__restrict__ items, const double *__restrict__ cells,
+                                                                      double *__restrict__ out, int normalize, double sum) {
+    const pcdense::Item it = items[blockIdx.x];
+    const int t = (int)threadIdx.x;
+    double v[pcdense::kPerLane];
+#pragma unroll
+    for (int k = 0; k < pcdense::kPerLane; ++k) {
+        const int i = t + k * pcdense::kGatherWG;
+        v[k] = (i >= it.lo && i < it.hi) ? cells[it.cell0 + i] : 0.0;
+    }
+    double *dst = out + it.out_off;
+#pragma unroll
+    for (int k = 0; k < pcdense::kPerLane; ++k) {
+        const int i = t + k * pcdense::kGatherWG;
+        if (i < it.len) dst[(int64_t)it.step * i] = normalize ? 1e6 * v[k] / sum : v[k];
+    }
+}
+
+// Fixed-tree sum: block b adds cells [b * kSumTile, (b + 1) * kSumTile) -- every lane its strided cells in order, then the
+// lanes by halving -- and one workgroup adds the partials the same way.  The order depends on n alone.
+constexpr int kSumTile = 256 * 64;
+__device__ __forceinline__ double block_tree_sum(double v) {
+    __shared__ double s[256];
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] = s[threadIdx.x] + s[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double r = s[0];
+    __syncthreads();
+    return r;
+}
+__global__ __launch_bounds__(256) void k_track_sum_partial(const double *__restrict__ cells, int64_t n, double *__restrict__ partial) {
+    const int64_t base = (int64_t)blockIdx.x * kSumTile;
+    double v = 0.0;
+    for (int k = 0; k < kSumTile / 256; ++k) {
+        const int64_t p = base + (int64_t)k * 256 + threadIdx.x;
+        if (p < n) v = v + cells[p];
+    }
+    const double r = block_tree_sum(v);
+    if (threadIdx.x == 0) partial[blockIdx.x] = r;
+}
+__global__ __launch_bounds__(256) void k_track_sum_final(const double *__restrict__ partial, int64_t n, double *__restrict__ out) {
+    double v = 0.0;
+    for (int64_t p = threadIdx.x; p < n; p += 256) v = v + partial[p];
+    const double r = block_tree_sum(v);
+    if (threadIdx.x == 0) *out = r;
+}
+
+} // namespace pctrack
