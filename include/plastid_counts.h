@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 15
+#define PC_ABI_VERSION 16
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -554,6 +554,51 @@ int pc_track_stats(pc_track *t, int64_t *out6);
 /* milliseconds of the last add on the engine's stream: [0] upload, [1] line starts, [2] classify + state records,
  * [3] fields (the host's conversion of escaped lines included), [4] growth, sort and apply */
 int pc_track_timing(pc_track *t, double *ms5);
+
+/* ---- MUTABLE COUNT TRACKS: set, add, multiply, compare and export (revision 16)
+ * The reference's MutableAbstractGenomeArray / GenomeArray (genome_array.py:1323-2104) without add_from_bowtie and plot.
+ * pc_track_set (__setitem__, :1535-1611): one launch writes every segment of a chain on one contig and strand slot.
+ * Position i of segment s takes values[val_off[s] + val_step[s] * i] (val_step +1 / -1; the binding reverses for '-' as
+ * the reference does), or `scalar` when values is NULL.  An undeclared contig is born at min_chr_size; a segment whose
+ * end reaches the contig's length sets it to max(length, end) + 10000 -- the rule of pc_track_add_text; the cells grow to
+ * the furthest end written; the cached sum is dropped.  Every argument is checked before anything changes. */
+int pc_track_set(pc_track *t, const char *contig, int strand_slot, int64_t nseg, const int64_t *start, const int64_t *end, const int64_t *val_off,
+                 const int8_t *val_step, const double *values, int64_t nvalues, double scalar);
+/* apply_operation (:1697-1835): a NEW track on a's engine, a op b, op 0 add / 1 subtract / 2 multiply; a and b are
+ * unchanged.  b NULL: a op scalar on every cell up to each contig's length (the result stores that many cells).
+ * Otherwise mode_all != 0: the union of the contigs (a's in a's order, then b's remaining ones) at the longer length, zero
+ * for what one side lacks; mode_all == 0 ("truncate"): the common contigs at the shorter length.  length_pad is added to
+ * every length of the result (zeros; the reference's "same" mode grows its result as it writes it).  The result has
+ * nstrands_out strand slots; slot s reads slot_a[s] of a and slot_b[s] of b (-1: the operand has no such strand: zero).
+ * One elementwise kernel over the concatenated cells of the result.  b on another engine: PC_ERR_ARG. */
+int pc_track_combine(pc_track *a, pc_track *b, double scalar, int op, int mode_all, int64_t length_pad, int nstrands_out, const int32_t *slot_a,
+                     const int32_t *slot_b, pc_track **out);
+/* __eq__: over npair (contig, strand) pairs -- public contig index and strand slot in a and in b, -1 where the array lacks
+ * it -- *equal = 1 when every position is non-zero in both arrays or in neither, and |a - b| <= tol where it is non-zero.
+ * A reduction on the device; no cell crosses to the host. */
+int pc_track_equal(pc_track *a, pc_track *b, int64_t npair, const int32_t *contig_a, const int32_t *slot_a, const int32_t *contig_b, const int32_t *slot_b,
+                   double tol, int *equal);
+/* nonzero (:1679-1695): count, exclusive sum and select over the cells; NaN is non-zero, -0.0 is not.
+ * pc_track_nonzero_count fills counts[i * nstrands + s] for public contig i and strand slot s and keeps the indices in HBM;
+ * pc_track_nonzero_read copies them out, slot after slot in that order (`total`: the sum of the counts). */
+int pc_track_nonzero_count(pc_track *t, int64_t *counts);
+int pc_track_nonzero_read(pc_track *t, int64_t *out, int64_t total);
+/* to_bedgraph (kind 0) / to_variable_step (kind 1) of one strand slot (:1996-2084), everything behind the track line, byte
+ * for byte: contigs in the sorted order of their names; bedGraph writes a contig only when its sum is > 0, the leading
+ * "chrom\t0\t<first>\t0" line and the runs of equal value between the first and the last non-zero cell; variableStep
+ * writes every contig's header and a line per non-zero cell.  Values print as Python's repr(float): integers below 10^16,
+ * nan and +-inf by the format kernel, every other value listed for the host (csrc/track_host.h: float_repr) and copied
+ * in.  pc_track_export builds the text in HBM and reports its size; pc_track_export_read copies it out (through the
+ * transfer ring when it is large) and frees it. */
+int pc_track_export(pc_track *t, int kind, int strand_slot, int64_t *bytes);
+int pc_track_export_read(pc_track *t, void *dst, int64_t bytes);
+/* the last export: [0] lines, [1] runs (bedGraph) or non-zero cells (variableStep), [2] values listed for the host, [3] bytes */
+int pc_track_export_stats(pc_track *t, int64_t *out4);
+/* milliseconds of the last export: [0] slot sums, [1] run heads + select, [2] listed values (the host's repr included),
+ * [3] line lengths + offsets, [4] format, [5] read-back (host clock) */
+int pc_track_export_timing(pc_track *t, double *ms6);
+/* [0] cells one workgroup covers in the run-head kernel, [1] lines one workgroup formats */
+int pc_track_export_geometry(int *out2);
 
 #ifdef __cplusplus
 }

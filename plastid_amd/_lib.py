@@ -133,6 +133,16 @@ SIGNATURES = {
     "pc_track_sum": (_int, [_vp, ctypes.POINTER(ctypes.c_double)]),
     "pc_track_stats": (_int, [_vp, _vp]),
     "pc_track_timing": (_int, [_vp, _vp]),
+    "pc_track_set": (_int, [_vp, ctypes.c_char_p, _int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double]),
+    "pc_track_combine": (_int, [_vp, _vp, ctypes.c_double, _int, _int, _i64, _int, _vp, _vp, _pp]),
+    "pc_track_equal": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.POINTER(_int)]),
+    "pc_track_nonzero_count": (_int, [_vp, _vp]),
+    "pc_track_nonzero_read": (_int, [_vp, _vp, _i64]),
+    "pc_track_export": (_int, [_vp, _int, _int, ctypes.POINTER(_i64)]),
+    "pc_track_export_read": (_int, [_vp, _vp, _i64]),
+    "pc_track_export_stats": (_int, [_vp, _vp]),
+    "pc_track_export_timing": (_int, [_vp, _vp]),
+    "pc_track_export_geometry": (_int, [_vp]),
 }
 
 _lib = None
@@ -142,7 +152,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def load():

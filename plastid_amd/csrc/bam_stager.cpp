@@ -1801,4 +1801,32 @@ int pb_track_stats(void *h, int64_t *out4) {
     return 0;
 }
 
+// A track written on the host by the serial writers of track_host.h (the model of the device export).  A writer is a
+// text that grows contig by contig: kind 0 bedGraph, 1 variableStep; the caller passes the contigs in the order of the file.
+struct TrackWriter { std::string text; pctrack::ExportStats stats; };
+void *pb_track_writer_open(void) { return new TrackWriter(); }
+void pb_track_writer_close(void *h) { delete static_cast<TrackWriter *>(h); }
+int pb_track_writer_add(void *h, int kind, const char *name, const double *cells, int64_t n) {
+    TrackWriter *w = static_cast<TrackWriter *>(h);
+    if (!w || !name || n < 0 || (n > 0 && !cells) || (kind != 0 && kind != 1)) return fail("pb_track_writer_add: bad arguments");
+    if (kind == 0) pctrack::write_bedgraph_contig(w->text, name, cells, n, w->stats);
+    else pctrack::write_variable_step_contig(w->text, name, cells, n, w->stats);
+    return 0;
+}
+int64_t pb_track_writer_size(void *h) { return h ? (int64_t)static_cast<TrackWriter *>(h)->text.size() : -1; }
+const char *pb_track_writer_text(void *h) { return static_cast<TrackWriter *>(h)->text.data(); }
+// [0] lines, [1] runs / non-zero cells, [2] values that are not plain, [3] bytes
+int pb_track_writer_stats(void *h, int64_t *out4) {
+    TrackWriter *w = static_cast<TrackWriter *>(h);
+    if (!w || !out4) return fail("pb_track_writer_stats: bad arguments");
+    out4[0] = w->stats.lines; out4[1] = w->stats.runs; out4[2] = w->stats.listed; out4[3] = w->stats.bytes;
+    return 0;
+}
+// repr(float(v[k])) of n values: text k at out + 24 * k, its length in len[k]
+int pb_float_repr(const double *v, int64_t n, char *out, uint8_t *len) {
+    if (n < 0 || (n > 0 && (!v || !out || !len))) return fail("pb_float_repr: bad arguments");
+    for (int64_t k = 0; k < n; ++k) len[k] = (uint8_t)pctrack::float_repr(v[k], out + pctrack::kReprMax * k);
+    return 0;
+}
+
 } // extern "C"

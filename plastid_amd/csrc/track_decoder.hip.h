@@ -4,6 +4,10 @@
 // pc_track_gather.  One import is six phases (track_add_impl): upload, line starts (both shared with SAM text),
 // classify + state records, fields (+ the host's conversion of the escaped lines), growth and storage, sort + apply.
 // The host looks at the state lines, the escaped lines and the growth lines only.
+// Revision 16 makes it the reference's mutable GenomeArray (:1535-2104): pc_track_set (one launch per segment or chain),
+// pc_track_combine (a new track from a op b or a op scalar), pc_track_equal, pc_track_nonzero_count / _read and
+// pc_track_export / _read: the bedGraph / variableStep text of a strand built in HBM in five phases and read back once;
+// of an export the host sees the per-slot sums and the values that are not plain.
 // Part of the one translation unit of plastid_counts.hip (behind sam_decoder.hip.h).
 #include "track_kernels.hip.h"
 
@@ -22,6 +26,15 @@ struct pc_track {
     double sum = 0.0;
     int64_t stats[6] = {0, 0, 0, 0, 0, 0};  // lines, yielded, escaped, state records, overlapping lines, growth lines
     double ms[5] = {0, 0, 0, 0, 0};         // upload | line starts | classify + state records | fields | growth + sort + apply
+    // the last pc_track_export: its text waits in HBM for pc_track_export_read
+    DevBuf<uint8_t> ex_text;
+    int64_t ex_bytes = -1;
+    int64_t ex_stats[4] = {0, 0, 0, 0};     // lines, runs / non-zero cells, values listed for the host, bytes
+    double ex_ms[6] = {0, 0, 0, 0, 0, 0};   // slot sums | run heads + select | listed values | lengths + offsets | format | read-back
+    // the last pc_track_nonzero_count: the indices wait in HBM for pc_track_nonzero_read
+    DevBuf<int64_t> nz;
+    int64_t nz_total = -1;
+    std::vector<int64_t> nz_begin, nz_cnt;  // per slot: its share of nz
 };
 
 // an engine that is destroyed takes its tracks with it (pc_destroy): their cells come from its pool
@@ -45,6 +58,14 @@ int32_t track_contig_id(pc_track *t, const std::string &name) {
     t->ext.resize(t->contigs.size() * (size_t)t->nstrands, 0);
     t->cell_off.resize(t->contigs.size() * (size_t)t->nstrands, 0);
     return id;
+}
+
+// an undeclared contig is born at min_chr_size, behind the contigs the array holds already (import and pc_track_set)
+void track_bear(pc_track *t, int32_t id) {
+    pc_track::Contig &c = t->contigs[(size_t)id];
+    if (c.born) return;
+    c.born = true; c.length = t->min_chr_size;
+    t->order.push_back(id);
 }
 
 // text bounds and data index of listed lines, for the host
@@ -264,7 +285,7 @@ int track_add_impl(pc_track *t, const void *image_, int64_t size, const char *na
         for (int c = 0; c < ncontig; ++c)
             if (!t->contigs[(size_t)c].born && first_line[(size_t)c] != tk::kNoLine) born.emplace_back(first_line[(size_t)c], c);
         std::sort(born.begin(), born.end());
-        for (auto &b : born) { t->contigs[(size_t)b.second].born = true; t->contigs[(size_t)b.second].length = t->min_chr_size; t->order.push_back(b.second); }
+        for (auto &b : born) track_bear(t, b.second);
         // growth: the reference's rule (genome_array.py:1593-1602), folded in file order over the lines that can matter
         t->stats[5] = cnt.n_growth;
         if (cnt.n_growth) {
@@ -277,7 +298,7 @@ int track_add_impl(pc_track *t, const void *image_, int64_t size, const char *na
             std::sort(gr.begin(), gr.end(), [](const TrackGrowth &a, const TrackGrowth &b) { return a.line < b.line; });
             for (const TrackGrowth &x : gr) {
                 int64_t &len = t->contigs[(size_t)x.contig].length;
-                if (x.stop >= len) len = x.stop + 10000;
+                len = tk::grown_length(len, x.stop);
             }
         }
         PC_TRY(track_grow_storage(t, strand, furthest, st));
@@ -337,7 +358,7 @@ int pc_track_create(pc_engine *e, int nstrands, int64_t min_chr_size, pc_track *
     if (!e || !out || nstrands < 1 || nstrands > 8 || min_chr_size < 0) return fail(PC_ERR_ARG, "pc_track_create: bad arguments");
     pc_track *t = new pc_track();
     t->e = e; t->nstrands = nstrands; t->min_chr_size = min_chr_size;
-    t->cells.pool = &e->pool;
+    t->cells.pool = &e->pool; t->ex_text.pool = &e->pool; t->nz.pool = &e->pool;
     e->tracks.push_back(t);
     *out = t;
     return PC_OK;
@@ -477,6 +498,467 @@ int pc_track_stats(pc_track *t, int64_t *out6) {
 int pc_track_timing(pc_track *t, double *ms5) {
     if (!t || !ms5) return fail(PC_ERR_ARG, "pc_track_timing: bad arguments");
     for (int k = 0; k < 5; ++k) ms5[k] = t->ms[k];
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------- writes
+
+int pc_track_set(pc_track *t, const char *contig, int strand_slot, int64_t nseg, const int64_t *start, const int64_t *end, const int64_t *val_off,
+                 const int8_t *val_step, const double *values, int64_t nvalues, double scalar) {
+    if (!t || !contig || nseg < 0 || (nseg > 0 && (!start || !end)) || nvalues < 0 || (values && nseg > 0 && (!val_off || !val_step)))
+        return fail(PC_ERR_ARG, "pc_track_set: bad arguments");
+    if (strand_slot < 0 || strand_slot >= t->nstrands) return fail(PC_ERR_ARG, "pc_track_set: strand slot %d of %d", strand_slot, t->nstrands);
+    // everything is checked before anything changes
+    int64_t furthest = 0;
+    for (int64_t s = 0; s < nseg; ++s) {
+        const int64_t len = end[s] - start[s];
+        if (start[s] < 0 || len < 0 || end[s] > tk::kMaxCoord) return fail(PC_ERR_ARG, "pc_track_set: segment %lld lies outside [0, 2^40]", (long long)s);
+        if (values && len > 0) {
+            if (val_step[s] != 1 && val_step[s] != -1) return fail(PC_ERR_ARG, "pc_track_set: val_step of segment %lld is not +1 / -1", (long long)s);
+            const int64_t a = val_off[s], b = val_off[s] + (int64_t)val_step[s] * (len - 1);
+            if (a < 0 || a >= nvalues || b < 0 || b >= nvalues) return fail(PC_ERR_ARG, "pc_track_set: segment %lld reads outside the vector", (long long)s);
+        }
+        if (len > 0) furthest = std::max(furthest, end[s]);
+    }
+    pc_engine *e = t->e;
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    // birth and growth, segment by segment as the reference's loop meets them (genome_array.py:1593-1608)
+    const int32_t id = track_contig_id(t, contig);
+    track_bear(t, id);
+    for (int64_t s = 0; s < nseg; ++s) t->contigs[(size_t)id].length = tk::grown_length(t->contigs[(size_t)id].length, end[s]);
+    t->sum_valid = false;
+    if (furthest == 0) return PC_OK;
+    std::vector<unsigned long long> far((size_t)id + 1, 0ull);
+    far[(size_t)id] = (unsigned long long)furthest;
+    PC_TRY(track_grow_storage(t, strand_slot, far, st));
+    const size_t slot = (size_t)id * (size_t)t->nstrands + (size_t)strand_slot;
+    std::vector<pcdense::Item> items;
+    for (int64_t s = 0; s < nseg; ++s) {
+        pcdense::SegIn in;
+        in.len = end[s] - start[s];
+        if (in.len <= 0) continue;
+        in.out_off = values ? val_off[s] : 0; in.step = values ? val_step[s] : 1;
+        in.clip_lo = 0; in.clip_hi = in.len; in.start = start[s]; in.known = true;
+        in.cell_base = t->cell_off[slot]; in.ext = t->ext[slot];
+        const int64_t k_end = pcdense::items_of(in.len);
+        for (int64_t k = 0; k < k_end; ++k) items.push_back(pcdense::cut_item(in, k));
+    }
+    if (items.size() >= (size_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_set: too many items");
+    DevBuf<pcdense::Item> d_items;
+    DevBuf<double> d_values;
+    DrainOnExit drained{st};
+    PC_TRY(d_items.upload(items, st));
+    if (values) PC_TRY(d_values.upload(values, (size_t)nvalues, st));
+    hipLaunchKernelGGL(tk::k_track_set, dim3((unsigned)items.size()), dim3(pcdense::kGatherWG), 0, st, d_items.p, t->cells.p, values ? d_values.p : nullptr, scalar);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------- arithmetic, equality
+
+namespace {
+// cells of public contig i (-1: none) on strand slot s (-1: none) of t: first cell and count, -1 / 0 where t has none
+void slot_cells(const pc_track *t, int i, int s, int64_t &c0, int64_t &n) {
+    c0 = -1; n = 0;
+    if (!t || i < 0 || i >= (int)t->order.size() || s < 0 || s >= t->nstrands) return;
+    const size_t slot = (size_t)t->order[(size_t)i] * (size_t)t->nstrands + (size_t)s;
+    c0 = t->cell_off[slot]; n = t->ext[slot];
+}
+int public_index(const pc_track *t, const std::string &name) {
+    auto it = t->ids.find(name);
+    if (it == t->ids.end() || !t->contigs[(size_t)it->second].born) return -1;
+    for (size_t i = 0; i < t->order.size(); ++i) if (t->order[i] == it->second) return (int)i;
+    return -1;
+}
+} // namespace
+
+int pc_track_combine(pc_track *a, pc_track *b, double scalar, int op, int mode_all, int64_t length_pad, int nstrands_out, const int32_t *slot_a,
+                     const int32_t *slot_b, pc_track **out) {
+    if (!a || !out || length_pad < 0 || nstrands_out < 1 || nstrands_out > 8 || !slot_a || (b && !slot_b) || op < tk::kOpAdd || op > tk::kOpMul)
+        return fail(PC_ERR_ARG, "pc_track_combine: bad arguments");
+    if (b && b->e != a->e) return fail(PC_ERR_ARG, "pc_track_combine: the operands live on different engines");
+    pc_engine *e = a->e;
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    // the contigs of the result: a's in a's order, then (mode all) b's remaining ones; truncate: the common ones
+    struct Pick { std::string name; int ia, ib; int64_t length; };
+    std::vector<Pick> picks;
+    for (size_t i = 0; i < a->order.size(); ++i) {
+        const pc_track::Contig &c = a->contigs[(size_t)a->order[i]];
+        const int ib = b ? public_index(b, c.name) : -1;
+        if (b && ib < 0 && !mode_all) continue;
+        int64_t len = c.length;
+        if (ib >= 0) { const int64_t lb = b->contigs[(size_t)b->order[(size_t)ib]].length; len = mode_all ? std::max(len, lb) : std::min(len, lb); }
+        picks.push_back({c.name, (int)i, ib, len});
+    }
+    if (b && mode_all)
+        for (size_t i = 0; i < b->order.size(); ++i) {
+            const pc_track::Contig &c = b->contigs[(size_t)b->order[i]];
+            if (public_index(a, c.name) < 0) picks.push_back({c.name, -1, (int)i, c.length});
+        }
+    pc_track *r = nullptr;
+    PC_TRY(pc_track_create(e, nstrands_out, a->min_chr_size, &r));
+    struct Undo { pc_track *r; ~Undo() { if (r) (void)pc_track_destroy(r); } } undo{r};
+    std::vector<tk::OpSlot> slots;
+    int64_t total = 0;
+    for (const Pick &p : picks) {
+        PC_TRY(pc_track_declare(r, p.name.c_str(), p.length + length_pad));
+        const int32_t id = r->ids[p.name];
+        for (int s = 0; s < nstrands_out; ++s) {
+            tk::OpSlot o;
+            slot_cells(a, p.ia, slot_a[s], o.a0, o.an);
+            slot_cells(b, p.ib, b ? slot_b[s] : -1, o.b0, o.bn);
+            // a scalar acts on every cell up to the length; arrays: up to the furthest cell either side stores
+            o.n = b ? std::min(std::max(o.an, o.bn), p.length) : p.length;
+            o.out0 = total;
+            r->ext[(size_t)id * (size_t)nstrands_out + (size_t)s] = o.n;
+            r->cell_off[(size_t)id * (size_t)nstrands_out + (size_t)s] = total;
+            total += o.n;
+            slots.push_back(o);
+        }
+    }
+    r->ncells = total;
+    if (total > 0) {
+        DevBuf<tk::OpSlot> d_slots;
+        DrainOnExit drained{st};
+        PC_TRY(r->cells.reserve((size_t)total));
+        PC_TRY(d_slots.upload(slots, st));
+        hipLaunchKernelGGL(tk::k_track_op, dim3(grid256(total)), dim3(256), 0, st, d_slots.p, (int)slots.size(), total, a->cells.p, b ? b->cells.p : nullptr,
+                           b ? 1 : 0, scalar, op, r->cells.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        drained.armed = false;
+    }
+    undo.r = nullptr;
+    *out = r;
+    return PC_OK;
+}
+
+// npair slots to compare: public contig and strand slot in a and in b (-1: the array lacks it, all zero)
+int pc_track_equal(pc_track *a, pc_track *b, int64_t npair, const int32_t *contig_a, const int32_t *slot_a, const int32_t *contig_b, const int32_t *slot_b,
+                   double tol, int *equal) {
+    if (!a || !b || !equal || npair < 0 || (npair > 0 && (!contig_a || !slot_a || !contig_b || !slot_b))) return fail(PC_ERR_ARG, "pc_track_equal: bad arguments");
+    if (b->e != a->e) return fail(PC_ERR_ARG, "pc_track_equal: the operands live on different engines");
+    pc_engine *e = a->e;
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    std::vector<tk::OpSlot> slots;
+    int64_t total = 0;
+    for (int64_t k = 0; k < npair; ++k) {
+        tk::OpSlot o;
+        slot_cells(a, contig_a[k], slot_a[k], o.a0, o.an);
+        slot_cells(b, contig_b[k], slot_b[k], o.b0, o.bn);
+        o.n = std::max(o.an, o.bn); o.out0 = total;
+        total += o.n;
+        slots.push_back(o);
+    }
+    *equal = 1;
+    if (total == 0) return PC_OK;
+    DevBuf<tk::OpSlot> d_slots;
+    DevBuf<uint32_t> d_flag;
+    DrainOnExit drained{st};
+    PC_TRY(d_slots.upload(slots, st));
+    PC_TRY(d_flag.reserve(1));
+    HIP_TRY(hipMemsetAsync(d_flag.p, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(tk::k_track_equal, dim3(grid256(total)), dim3(256), 0, st, d_slots.p, (int)slots.size(), total, a->cells.p, b->cells.p, tol, d_flag.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t differs = 0;
+    HIP_TRY(hipMemcpyAsync(&differs, d_flag.p, sizeof(differs), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    *equal = differs ? 0 : 1;
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------- export
+
+// One strand as bedGraph (kind 0) or variableStep (kind 1) text behind the track line (genome_array.py:1996-2084), built
+// in HBM on the engine's stream: slot sums and first / last non-zero; run heads (non-zero cells), count, exclusive sum and
+// select into the run table; the values that are not plain to the host and back as text; a byte length per line; their
+// exclusive sum; the format kernel.  *bytes: the size of the text, which waits for pc_track_export_read.
+int pc_track_export(pc_track *t, int kind, int strand_slot, int64_t *bytes) {
+    if (!t || !bytes || (kind != 0 && kind != 1)) return fail(PC_ERR_ARG, "pc_track_export: bad arguments");
+    if (strand_slot < 0 || strand_slot >= t->nstrands) return fail(PC_ERR_ARG, "pc_track_export: strand slot %d of %d", strand_slot, t->nstrands);
+    pc_engine *e = t->e;
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    for (auto &x : t->ex_stats) x = 0;
+    for (auto &x : t->ex_ms) x = 0.0;
+    t->ex_bytes = 0;
+    *bytes = 0;
+    // the contigs in sorted() order of their names (code points: the bytes of UTF-8 sort alike)
+    std::vector<int32_t> ids(t->order.begin(), t->order.end());
+    std::sort(ids.begin(), ids.end(), [t](int32_t a, int32_t b) { return t->contigs[(size_t)a].name < t->contigs[(size_t)b].name; });
+    const int K0 = (int)ids.size();
+    if (K0 == 0) return PC_OK;
+    if (K0 > 65535) return fail(PC_ERR_ARG, "pc_track_export: more than 65535 contigs");
+    hipEvent_t ev[6] = {};
+    for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+    struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 6; ++i) (void)hipEventDestroy(ev[i]); } } evg{ev};
+    DevBuf<tk::SlotCells> d_slots;
+    DevBuf<tk::SlotStat> d_stat;
+    DevBuf<double> d_partial, d_listed_val;
+    DevBuf<tk::ExRange> d_ranges;
+    DevBuf<uint32_t> d_flags, d_idx, d_run_e, d_listed_slot, d_n_listed;
+    DevBuf<uint8_t> d_tmp, d_names, d_strs, d_lens;
+    DevBuf<int64_t> d_len, d_off;
+    DrainOnExit drained{st};
+
+    // phase 1: per slot the fixed-tree sum, first and last non-zero
+    std::vector<tk::SlotCells> slots((size_t)K0);
+    std::vector<tk::SlotStat> stat((size_t)K0);
+    int64_t max_tiles = 1;
+    for (int k = 0; k < K0; ++k) {
+        const size_t slot = (size_t)ids[(size_t)k] * (size_t)t->nstrands + (size_t)strand_slot;
+        slots[(size_t)k].cell0 = t->cell_off[slot]; slots[(size_t)k].n = t->ext[slot];
+        stat[(size_t)k].sum = 0.0; stat[(size_t)k].first = ~0ull; stat[(size_t)k].last1 = 0ull;
+        max_tiles = std::max(max_tiles, (t->ext[slot] + tk::kSumTile - 1) / tk::kSumTile);
+    }
+    HIP_TRY(hipEventRecord(ev[0], st));
+    PC_TRY(d_slots.upload(slots, st)); PC_TRY(d_stat.upload(stat, st));
+    PC_TRY(d_partial.reserve((size_t)K0 * (size_t)max_tiles));
+    hipLaunchKernelGGL(tk::k_export_slot_partial, dim3((unsigned)max_tiles, (unsigned)K0), dim3(256), 0, st, d_slots.p, t->cells.p, max_tiles, d_partial.p, d_stat.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tk::k_export_slot_final, dim3((unsigned)K0), dim3(256), 0, st, d_slots.p, d_partial.p, max_tiles, d_stat.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(stat.data(), d_stat.p, stat.size() * sizeof(tk::SlotStat), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventRecord(ev[1], st));
+
+    // the contigs that are written and their export cells
+    std::vector<tk::ExRange> ranges;
+    std::vector<uint8_t> names;
+    int64_t E = 0;
+    for (int k = 0; k < K0; ++k) {
+        const tk::SlotStat &s = stat[(size_t)k];
+        const bool nonzero = s.first != ~0ull;
+        if (kind == 0 && !(s.sum > 0.0 && nonzero)) continue;
+        const std::string &nm = t->contigs[(size_t)ids[(size_t)k]].name;
+        tk::ExRange r;
+        r.e0 = E; r.run_base = 0;
+        r.pos0 = kind == 0 ? (int64_t)s.first : 0;
+        r.n = kind == 0 ? (int64_t)(s.last1 - s.first) : slots[(size_t)k].n;
+        r.cell0 = slots[(size_t)k].cell0 + r.pos0;
+        r.name_off = (int32_t)names.size(); r.name_len = (int32_t)nm.size();
+        names.insert(names.end(), nm.begin(), nm.end());
+        E += r.n;
+        ranges.push_back(r);
+    }
+    const int K = (int)ranges.size();
+    if (K == 0) { drained.armed = false; return PC_OK; }
+    if (E >= (int64_t)0x7fffffff || names.size() >= (size_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_export: more than 2^31 cells to export");
+    { tk::ExRange end; end.e0 = E; end.n = 0; end.cell0 = 0; end.pos0 = 0; end.run_base = 0; end.name_off = 0; end.name_len = 0; ranges.push_back(end); }
+    PC_TRY(d_ranges.upload(ranges, st)); PC_TRY(d_names.upload(names, st));
+
+    // phase 2: run heads, count, exclusive sum, select
+    int64_t R = 0;
+    if (E > 0) {
+        int rc = PC_OK;
+        room(rc, d_flags, (size_t)E); room(rc, d_idx, (size_t)E);
+        if (rc != PC_OK) return rc;
+        hipLaunchKernelGGL(tk::k_export_flags, dim3((unsigned)((E + tk::kExportTile - 1) / tk::kExportTile)), dim3(256), 0, st, kind, d_ranges.p, K, E, t->cells.p, d_flags.p);
+        HIP_TRY(hipGetLastError());
+        size_t b0 = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b0, d_flags.p, d_idx.p, (int)E, st));
+        PC_TRY(d_tmp.reserve(std::max<size_t>(b0, 16)));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b0, d_flags.p, d_idx.p, (int)E, st));
+        hipLaunchKernelGGL(tk::k_export_bases, dim3(grid256(K + 1)), dim3(256), 0, st, d_flags.p, d_idx.p, E, d_ranges.p, K);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&R, &d_ranges.p[K].run_base, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (R > 0) {
+            PC_TRY(d_run_e.reserve((size_t)R));
+            hipLaunchKernelGGL(tk::k_export_select, dim3(grid256(E)), dim3(256), 0, st, d_flags.p, d_idx.p, E, d_run_e.p);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipEventRecord(ev[2], st));
+
+    // phase 3: the values that are not plain go to the host and come back as text
+    uint32_t n_listed = 0;
+    {
+        int rc = PC_OK;
+        room(rc, d_listed_slot, (size_t)std::max<int64_t>(R, 1)); room(rc, d_listed_val, (size_t)std::max<int64_t>(R, 1)); room(rc, d_n_listed, 1);
+        if (rc != PC_OK) return rc;
+    }
+    if (R > 0) {
+        HIP_TRY(hipMemsetAsync(d_n_listed.p, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(tk::k_export_classify, dim3(grid256(R)), dim3(256), 0, st, d_ranges.p, K, d_run_e.p, R, t->cells.p, d_listed_slot.p, d_listed_val.p, d_n_listed.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&n_listed, d_n_listed.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    std::vector<uint8_t> strs((size_t)std::max<uint32_t>(n_listed, 1) * tk::kReprMax, 0), lens((size_t)std::max<uint32_t>(n_listed, 1), 0);
+    if (n_listed) {
+        std::vector<double> vals(n_listed);
+        HIP_TRY(hipMemcpyAsync(vals.data(), d_listed_val.p, (size_t)n_listed * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < n_listed; ++k) lens[k] = (uint8_t)tk::float_repr(vals[k], (char *)strs.data() + (size_t)tk::kReprMax * k);
+    }
+    PC_TRY(d_strs.upload(strs, st)); PC_TRY(d_lens.upload(lens, st));
+    HIP_TRY(hipEventRecord(ev[3], st));
+
+    // phases 4, 5: a byte length per line, their exclusive sum, the bytes
+    const int64_t nlines = R + K;
+    if (nlines >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_export: more than 2^31 lines");
+    tk::ExportView view;
+    view.kind = kind; view.ranges = d_ranges.p; view.K = K; view.run_e = d_run_e.p; view.cells = t->cells.p; view.names = d_names.p;
+    view.listed_slot = d_listed_slot.p; view.strs = d_strs.p; view.lens = d_lens.p;
+    {
+        int rc = PC_OK;
+        room(rc, d_len, (size_t)nlines); room(rc, d_off, (size_t)nlines);
+        if (rc != PC_OK) return rc;
+    }
+    const unsigned gl = (unsigned)((nlines + tk::kFormatRuns - 1) / tk::kFormatRuns);
+    hipLaunchKernelGGL(tk::k_export_lengths, dim3(gl), dim3(tk::kFormatRuns), 0, st, view, nlines, d_len.p);
+    HIP_TRY(hipGetLastError());
+    {
+        size_t b0 = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b0, d_len.p, d_off.p, (int)nlines, st));
+        PC_TRY(d_tmp.reserve(std::max<size_t>(b0, 16)));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b0, d_len.p, d_off.p, (int)nlines, st));
+    }
+    int64_t last_off = 0, last_len = 0;
+    HIP_TRY(hipMemcpyAsync(&last_off, d_off.p + (nlines - 1), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&last_len, d_len.p + (nlines - 1), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t total = last_off + last_len;
+    HIP_TRY(hipEventRecord(ev[4], st));
+    PC_TRY(t->ex_text.reserve((size_t)total));
+    hipLaunchKernelGGL(tk::k_export_format, dim3(gl), dim3(tk::kFormatRuns), 0, st, view, nlines, d_off.p, t->ex_text.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[5], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    for (int k = 0; k < 5; ++k) t->ex_ms[k] = ms_between(ev[k], ev[k + 1]);
+    t->ex_stats[0] = nlines; t->ex_stats[1] = R; t->ex_stats[2] = (int64_t)n_listed; t->ex_stats[3] = total;
+    t->ex_bytes = total;
+    *bytes = total;
+    return PC_OK;
+}
+
+// The text of the last pc_track_export (`bytes` as it reported), through the transfer ring when it is large.
+int pc_track_export_read(pc_track *t, void *dst, int64_t bytes) {
+    if (!t || t->ex_bytes < 0 || bytes != t->ex_bytes || (bytes > 0 && !dst)) return fail(PC_ERR_ARG, "pc_track_export_read: no exported text of this size");
+    pc_engine *e = t->e;
+    HIP_TRY(hipSetDevice(e->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bytes > 0) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const std::vector<TransferJob> job{{dst, t->ex_text.p, (size_t)bytes}};
+        PC_TRY(TransferRing::of(e->device).run(e->device, job, TransferRing::kPiece, false, true));
+    }
+    t->ex_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    t->ex_text.release();
+    t->ex_bytes = -1;
+    return PC_OK;
+}
+
+int pc_track_export_stats(pc_track *t, int64_t *out4) {
+    if (!t || !out4) return fail(PC_ERR_ARG, "pc_track_export_stats: bad arguments");
+    for (int k = 0; k < 4; ++k) out4[k] = t->ex_stats[k];
+    return PC_OK;
+}
+
+int pc_track_export_timing(pc_track *t, double *ms6) {
+    if (!t || !ms6) return fail(PC_ERR_ARG, "pc_track_export_timing: bad arguments");
+    for (int k = 0; k < 6; ++k) ms6[k] = t->ex_ms[k];
+    return PC_OK;
+}
+
+int pc_track_export_geometry(int *out2) {
+    if (!out2) return fail(PC_ERR_ARG, "pc_track_export_geometry: bad arguments");
+    out2[0] = tk::kExportTile; out2[1] = tk::kFormatRuns;
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------- nonzero
+
+// counts[i * nstrands + s]: non-zero cells of public contig i on strand slot s; the indices wait for pc_track_nonzero_read
+int pc_track_nonzero_count(pc_track *t, int64_t *counts) {
+    if (!t || (!counts && !t->order.empty())) return fail(PC_ERR_ARG, "pc_track_nonzero_count: bad arguments");
+    const int nslot = (int)t->order.size() * t->nstrands;
+    for (int k = 0; k < nslot; ++k) counts[k] = 0;
+    t->nz_total = 0;
+    if (t->ncells == 0) return PC_OK;
+    if (t->ncells >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_nonzero: more than 2^31 stored cells");
+    pc_engine *e = t->e;
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    // the slots that hold cells, in the order of their cells (that of the internal ids)
+    const int nint = (int)(t->contigs.size() * (size_t)t->nstrands);
+    std::vector<int> live;
+    std::vector<int64_t> at;
+    for (int k = 0; k < nint; ++k)
+        if (t->ext[(size_t)k] > 0) { live.push_back(k); at.push_back(t->cell_off[(size_t)k]); }
+    at.push_back(t->ncells);
+    std::vector<int64_t> picked(at.size());
+    const int64_t n = t->ncells;
+    DevBuf<uint32_t> d_flags, d_idx;
+    DevBuf<uint8_t> d_tmp;
+    DevBuf<int64_t> d_at, d_picked;
+    DrainOnExit drained{st};
+    int rc = PC_OK;
+    room(rc, d_flags, (size_t)n); room(rc, d_idx, (size_t)n); room(rc, d_picked, at.size());
+    if (rc != PC_OK) return rc;
+    PC_TRY(d_at.upload(at, st));
+    hipLaunchKernelGGL(tk::k_track_nz_flags, dim3(grid256(n)), dim3(256), 0, st, t->cells.p, n, d_flags.p);
+    HIP_TRY(hipGetLastError());
+    size_t b0 = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b0, d_flags.p, d_idx.p, (int)n, st));
+    PC_TRY(d_tmp.reserve(std::max<size_t>(b0, 16)));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b0, d_flags.p, d_idx.p, (int)n, st));
+    hipLaunchKernelGGL(tk::k_track_pick, dim3(grid256((int64_t)at.size())), dim3(256), 0, st, d_flags.p, d_idx.p, n, d_at.p, (int)at.size(), d_picked.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(picked.data(), d_picked.p, picked.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t total = picked.back();
+    if (total > 0) {
+        PC_TRY(t->nz.reserve((size_t)total));
+        // (d_at: the live slots' first cells, ascending, in front of its last entry)
+        hipLaunchKernelGGL(tk::k_track_nz_select, dim3(grid256(n)), dim3(256), 0, st, d_flags.p, d_idx.p, n, d_at.p, (int)live.size(), t->nz.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    drained.armed = false;
+    t->nz_begin.assign((size_t)nint, 0); t->nz_cnt.assign((size_t)nint, 0);
+    for (size_t j = 0; j < live.size(); ++j) { t->nz_begin[(size_t)live[j]] = picked[j]; t->nz_cnt[(size_t)live[j]] = picked[j + 1] - picked[j]; }
+    for (size_t i = 0; i < t->order.size(); ++i)
+        for (int s = 0; s < t->nstrands; ++s)
+            counts[i * (size_t)t->nstrands + (size_t)s] = t->nz_cnt[(size_t)t->order[i] * (size_t)t->nstrands + (size_t)s];
+    t->nz_total = total;
+    return PC_OK;
+}
+
+// The indices of the last pc_track_nonzero_count, slot after slot in public order (contig-major), `total` of them.
+int pc_track_nonzero_read(pc_track *t, int64_t *out, int64_t total) {
+    if (!t || t->nz_total < 0 || total != t->nz_total || (total > 0 && !out)) return fail(PC_ERR_ARG, "pc_track_nonzero_read: no counted indices of this size");
+    if (total == 0) { t->nz_total = -1; return PC_OK; }
+    pc_engine *e = t->e;
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    std::vector<int64_t> all((size_t)total);
+    HIP_TRY(hipMemcpyAsync(all.data(), t->nz.p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // the order of the cells (internal ids) -> public order
+    const std::vector<int64_t> &cnt = t->nz_cnt, &begin = t->nz_begin;
+    int64_t w = 0;
+    for (size_t i = 0; i < t->order.size(); ++i)
+        for (int s = 0; s < t->nstrands; ++s) {
+            const size_t k = (size_t)t->order[i] * (size_t)t->nstrands + (size_t)s;
+            if (cnt[k]) memcpy(out + w, all.data() + begin[k], (size_t)cnt[k] * 8);
+            w += cnt[k];
+        }
+    t->nz.release();
+    t->nz_total = -1;
     return PC_OK;
 }
 

@@ -13,17 +13,28 @@
 // its state (line_fields).  int / float are Python's: a PLAIN token -- [+-]?[0-9]{1,18}, and a decimal literal whose
 // significand is at most 2^53 with a net power of ten within +-22 -- is converted by int_fast / value_plain, on the
 // device too; every other token ESCAPES to int_full / value_full (grammar check, then strtod), host only.
+// The way back (revision 16): grown_length, the one growth rule of import and writes; value_class / float_repr, Python's
+// repr(float) -- plain values by a function the format kernel runs too, the others host only; put_bed_line & co, the bytes
+// of an exported line through a sink that counts or stores; write_bedgraph_contig / write_variable_step_contig, the serial
+// writers (genome_array.py:1996-2084), the model of the device export.
 // The per-line functions carry PC_TRK_HD: __host__ __device__ under hipcc, nothing under a host compiler.
-// Plain C++17 (no HIP): tests/track_host_test.cpp compiles it on a machine without a GPU, under the sanitizers.
+// Plain C++17 (no HIP): tests/track_host_test.cpp and tests/track_export_host_test.cpp compile it on a machine without a
+// GPU, under the sanitizers.
 #pragma once
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
 #include <string>
 #include <vector>
+#if !defined(PC_TRK_NO_CHARCONV) && defined(__has_include)
+#if __has_include(<charconv>)
+#include <charconv>   // std::to_chars for doubles, where the library has it (float_repr)
+#endif
+#endif
 
 #if defined(__HIPCC__)
 #define PC_TRK_HD __host__ __device__
@@ -486,6 +497,197 @@ inline void read_track(const uint8_t *text, size_t size, TrackTable &t) {
         p = le < end ? le + 1 : end;
     }
     t.lines = line;
+}
+
+// ---------------------------------------------------------------- growth (genome_array.py:1593-1602)
+
+// The length of a contig after a write (or an imported line) that ends at `end`: reaching the length sets it to
+// max(len, end) + 10000.  The one rule of the import and of pc_track_set.
+PC_TRK_HD inline int64_t grown_length(int64_t len, int64_t end) { return end >= len ? (len > end ? len : end) + 10000 : len; }
+
+// ---------------------------------------------------------------- export: values as text
+
+// A value is PLAIN when it is an integer of magnitude below 10^16: Python's repr is its digits and ".0" (the count-track
+// case; -0.0 is "-0.0").  nan / inf / -inf are kSpecial.  Every other finite value is LISTED: float_repr, host only.
+enum { kValPlain = 0, kValSpecial = 1, kValListed = 2 };
+constexpr int kReprMax = 24;                       // "-1.7976931348623157e+308"
+
+PC_TRK_HD inline int value_class(double v) {
+    if (v != v || v - v != 0.0) return kValSpecial;             // nan, +-inf
+    const double a = v < 0 ? -v : v;
+    if (a < 1e16 && (double)(int64_t)a == a) return kValPlain;
+    return kValListed;
+}
+PC_TRK_HD inline bool sign_bit(double v) {
+    uint64_t u;
+    __builtin_memcpy(&u, &v, 8);
+    return (u >> 63) != 0;
+}
+PC_TRK_HD inline int dec_digits(uint64_t x) {
+    int n = 1;
+    while (x >= 10u) { x /= 10u; ++n; }
+    return n;
+}
+// a sink takes bytes: CountSink counts them, WriteSink stores them
+struct CountSink {
+    int64_t n = 0;
+    PC_TRK_HD void put(uint8_t) { ++n; }
+};
+struct WriteSink {
+    uint8_t *p;
+    PC_TRK_HD void put(uint8_t c) { *p++ = c; }
+};
+template <typename Sink> PC_TRK_HD inline void put_uint(Sink &s, uint64_t x) {
+    uint8_t d[20];
+    int n = 0;
+    do { d[n++] = (uint8_t)('0' + x % 10u); x /= 10u; } while (x);
+    while (n) s.put(d[--n]);
+}
+template <typename Sink> PC_TRK_HD inline void put_bytes(Sink &s, const uint8_t *b, int64_t n) {
+    for (int64_t k = 0; k < n; ++k) s.put(b[k]);
+}
+template <typename Sink> PC_TRK_HD inline void put_word(Sink &s, const char *w) {
+    for (; *w; ++w) s.put((uint8_t)*w);
+}
+// a plain or special value (value_class says which)
+template <typename Sink> PC_TRK_HD inline void put_simple_value(Sink &s, double v) {
+    if (v != v) { put_word(s, "nan"); return; }
+    if (v - v != 0.0) { put_word(s, v < 0 ? "-inf" : "inf"); return; }
+    if (sign_bit(v)) s.put((uint8_t)'-');
+    put_uint(s, (uint64_t)(int64_t)(v < 0 ? -v : v));
+    put_word(s, ".0");
+}
+
+// Host only.  The shortest digits that read back as `v` (v finite, not zero), without sign or point, and the power of
+// ten of the first digit.
+inline void shortest_digits(double v, char *digits, int &ndig, int &exp10) {
+    char buf[48];
+    const double a = v < 0 ? -v : v;
+#if defined(__cpp_lib_to_chars) && !defined(PC_TRK_NO_CHARCONV)
+    const auto r = std::to_chars(buf, buf + sizeof(buf) - 1, a, std::chars_format::scientific);
+    *r.ptr = 0;
+#else
+    for (int prec = 0; prec < 17; ++prec) {
+        snprintf(buf, sizeof(buf), "%.*e", prec, a);
+        if (std::strtod(buf, nullptr) == a) break;
+    }
+#endif
+    ndig = 0;
+    const char *p = buf;
+    for (; *p && *p != 'e'; ++p)
+        if (*p >= '0' && *p <= '9') digits[ndig++] = *p;
+    exp10 = *p == 'e' ? atoi(p + 1) : 0;
+    while (ndig > 1 && digits[ndig - 1] == '0') --ndig;
+}
+
+// repr(float(v)) into out (kReprMax bytes at least); returns the length.  Python's layout: the shortest digits that
+// round-trip, in exponent form ("d.ddde-05", at least two exponent digits) below 1e-4 and from 1e16 on, else with a point.
+inline int float_repr(double v, char *out) {
+    WriteSink s{(uint8_t *)out};
+    if (value_class(v) != kValListed) { put_simple_value(s, v); return (int)((char *)s.p - out); }
+    char dg[24];
+    int nd = 0, e10 = 0;
+    shortest_digits(v, dg, nd, e10);
+    if (v < 0) s.put((uint8_t)'-');
+    if (e10 < -4 || e10 >= 16) {
+        s.put((uint8_t)dg[0]);
+        if (nd > 1) { s.put((uint8_t)'.'); put_bytes(s, (const uint8_t *)dg + 1, nd - 1); }
+        s.put((uint8_t)'e');
+        s.put((uint8_t)(e10 < 0 ? '-' : '+'));
+        const unsigned ae = (unsigned)(e10 < 0 ? -e10 : e10);
+        if (ae < 10u) s.put((uint8_t)'0');
+        put_uint(s, ae);
+    } else if (e10 >= 0) {
+        for (int k = 0; k <= e10; ++k) s.put((uint8_t)(k < nd ? dg[k] : '0'));
+        s.put((uint8_t)'.');
+        if (nd > e10 + 1) put_bytes(s, (const uint8_t *)dg + e10 + 1, nd - e10 - 1); else s.put((uint8_t)'0');
+    } else {
+        put_word(s, "0.");
+        for (int k = 0; k < -e10 - 1; ++k) s.put((uint8_t)'0');
+        put_bytes(s, (const uint8_t *)dg, nd);
+    }
+    return (int)((char *)s.p - out);
+}
+
+// ---------------------------------------------------------------- export: the lines (genome_array.py:1996-2084)
+
+// "chrom\tstart\tend\tvalue\n"; `vtext` (length vlen): the value of a listed run, nullptr: plain or special
+template <typename Sink> PC_TRK_HD inline void put_bed_line(Sink &s, const uint8_t *name, int64_t name_len, int64_t a, int64_t b, double v,
+                                                            const uint8_t *vtext, int vlen) {
+    put_bytes(s, name, name_len); s.put(9); put_uint(s, (uint64_t)a); s.put(9); put_uint(s, (uint64_t)b); s.put(9);
+    if (vtext) put_bytes(s, vtext, vlen); else put_simple_value(s, v);
+    s.put(10);
+}
+// the leading line of a contig: "chrom\t0\t<first>\t0\n" (the integer 0 the reference's loop starts with)
+template <typename Sink> PC_TRK_HD inline void put_bed_lead(Sink &s, const uint8_t *name, int64_t name_len, int64_t first) {
+    put_bytes(s, name, name_len); s.put(9); s.put((uint8_t)'0'); s.put(9); put_uint(s, (uint64_t)first); s.put(9); s.put((uint8_t)'0'); s.put(10);
+}
+template <typename Sink> PC_TRK_HD inline void put_var_header(Sink &s, const uint8_t *name, int64_t name_len) {
+    put_word(s, "variableStep chrom="); put_bytes(s, name, name_len); put_word(s, " span=1"); s.put(10);
+}
+// "<i + 1>\tvalue\n"
+template <typename Sink> PC_TRK_HD inline void put_var_line(Sink &s, int64_t i, double v, const uint8_t *vtext, int vlen) {
+    put_uint(s, (uint64_t)(i + 1)); s.put(9);
+    if (vtext) put_bytes(s, vtext, vlen); else put_simple_value(s, v);
+    s.put(10);
+}
+
+// Host only: the serial writers, the model of the device export.  stats: lines, runs (bedGraph) or non-zero cells
+// (variableStep), values that are not plain (they go through float_repr), bytes.
+struct ExportStats { int64_t lines = 0, runs = 0, listed = 0, bytes = 0; };
+
+struct StringSink {
+    std::string *out;
+    void put(uint8_t c) { out->push_back((char)c); }
+};
+inline void host_value(const double v, char *buf, const uint8_t *&vtext, int &vlen, ExportStats &st) {
+    vtext = nullptr; vlen = 0;
+    if (value_class(v) == kValListed) { vlen = float_repr(v, buf); vtext = (const uint8_t *)buf; st.listed += 1; }
+}
+
+// One contig's strand as bedGraph: nothing unless its sum is > 0; the leading line, then the runs of equal value (by !=)
+// from the first to the last non-zero cell.
+inline void write_bedgraph_contig(std::string &out, const std::string &name, const double *v, int64_t n, ExportStats &st) {
+    double sum = 0.0;
+    int64_t first = -1, last = -1;
+    for (int64_t i = 0; i < n; ++i) {
+        sum = sum + v[i];
+        if (v[i] != 0.0) { if (first < 0) first = i; last = i; }
+    }
+    if (!(sum > 0.0) || first < 0) return;
+    const size_t before = out.size();
+    StringSink s{&out};
+    const uint8_t *nm = (const uint8_t *)name.data();
+    put_bed_lead(s, nm, (int64_t)name.size(), first);
+    st.lines += 1;
+    char buf[kReprMax + 8];
+    int64_t head = first;
+    for (int64_t x = first + 1; x <= last + 1; ++x) {
+        if (x <= last && !(v[x] != v[head])) continue;
+        const uint8_t *vt; int vl;
+        host_value(v[head], buf, vt, vl, st);
+        put_bed_line(s, nm, (int64_t)name.size(), head, x, v[head], vt, vl);
+        st.lines += 1; st.runs += 1;
+        head = x;
+    }
+    st.bytes += (int64_t)(out.size() - before);
+}
+
+// One contig's strand as variableStep: the header whatever the cells hold, then a line per non-zero cell.
+inline void write_variable_step_contig(std::string &out, const std::string &name, const double *v, int64_t n, ExportStats &st) {
+    const size_t before = out.size();
+    StringSink s{&out};
+    put_var_header(s, (const uint8_t *)name.data(), (int64_t)name.size());
+    st.lines += 1;
+    char buf[kReprMax + 8];
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(v[i] != 0.0)) continue;
+        const uint8_t *vt; int vl;
+        host_value(v[i], buf, vt, vl, st);
+        put_var_line(s, i, v[i], vt, vl);
+        st.lines += 1; st.runs += 1;
+    }
+    st.bytes += (int64_t)(out.size() - before);
 }
 
 } // namespace pctrack

@@ -13,6 +13,15 @@
 //            k_track_fill_ordered   clusters of several lines, every cell in file order
 //   query:   k_track_gather         k_dense_gather over float64 cells
 //            k_track_sum_partial / k_track_sum_final   fixed-tree sum
+//   revision 16:
+//   write:   k_track_set            the gather the other way: a fill, or a strided copy from an uploaded vector
+//   combine: k_track_op             one lane per cell of the concatenated result, operands per slot with a length each
+//            k_track_equal          the same walk as a reduction
+//            k_track_nz_flags / k_track_nz_select   nonzero: flags, exclusive sum (caller), select
+//   export:  k_export_slot_partial / k_export_slot_final   per slot: fixed-tree sum, first and last non-zero
+//            k_export_flags / k_export_select / k_export_bases   run heads, the run table, runs in front of a contig
+//            k_export_classify      the values that are not plain, listed for the host's repr
+//            k_export_lengths / k_export_format   a byte length per line; every line's bytes at its offset
 // Every byte access lies in [0, text_len); every cell access inside the strand's extent.
 // Part of the one translation unit of plastid_counts.hip (behind sam_kernels.hip.h and dense_kernels.hip.h).
 #pragma once
@@ -307,6 +316,245 @@ __global__ __launch_bounds__(256) void k_track_sum_final(const double *__restric
     for (int64_t p = threadIdx.x; p < n; p += 256) v = v + partial[p];
     const double r = block_tree_sum(v);
     if (threadIdx.x == 0) *out = r;
+}
+
+// ---------------------------------------------------------------- writes (pc_track_set)
+
+// k_track_gather the other way: position i of the item, lo <= i < hi, takes values[out_off + step * i] (values null: the
+// scalar).  One launch serves every segment of a chain.
+__global__ __launch_bounds__(pcdense::kGatherWG) void k_track_set(const pcdense::Item *__restrict__ items, double *__restrict__ cells,
+                                                                   const double *__restrict__ values, double scalar) {
+    const pcdense::Item it = items[blockIdx.x];
+    const int t = (int)threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < pcdense::kPerLane; ++k) {
+        const int i = t + k * pcdense::kGatherWG;
+        if (i >= it.lo && i < it.hi) cells[it.cell0 + i] = values ? values[it.out_off + (int64_t)it.step * i] : scalar;
+    }
+}
+
+// ---------------------------------------------------------------- arithmetic and equality (pc_track_combine, pc_track_equal)
+
+// One (contig, strand) of the result: cells [out0, out0 + n) of the concatenated output; operand a has cells
+// [a0, a0 + an) for its first an positions and zero behind them (a0 < 0: the operand lacks the slot); b alike.
+struct OpSlot { int64_t out0, n, a0, an, b0, bn; };
+
+// the slot of output cell i: the last one with out0 <= i (empty slots share their out0 with the slot behind them)
+__device__ __forceinline__ int op_slot_of(const OpSlot *__restrict__ slots, int nslot, int64_t i) {
+    int lo = 0, hi = nslot;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (slots[mid].out0 <= i) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+
+enum { kOpAdd = 0, kOpSub = 1, kOpMul = 2 };
+
+// out[i] = a op b over the concatenated output cells; b_cells null: the scalar
+__global__ __launch_bounds__(256) void k_track_op(const OpSlot *__restrict__ slots, int nslot, int64_t total, const double *__restrict__ a_cells,
+                                                  const double *__restrict__ b_cells, int has_b, double scalar, int op, double *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const OpSlot s = slots[op_slot_of(slots, nslot, i)];
+    const int64_t j = i - s.out0;
+    const double va = (s.a0 >= 0 && j < s.an) ? a_cells[s.a0 + j] : 0.0;
+    const double vb = has_b ? ((s.b0 >= 0 && j < s.bn) ? b_cells[s.b0 + j] : 0.0) : scalar;
+    out[i] = op == kOpAdd ? va + vb : op == kOpSub ? va - vb : va * vb;
+}
+
+// *differs |= 1 when some position is non-zero in one operand only, or non-zero in both and not within tol
+__global__ __launch_bounds__(256) void k_track_equal(const OpSlot *__restrict__ slots, int nslot, int64_t total, const double *__restrict__ a_cells,
+                                                     const double *__restrict__ b_cells, double tol, uint32_t *__restrict__ differs) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total) return;
+    const OpSlot s = slots[op_slot_of(slots, nslot, i)];
+    const int64_t j = i - s.out0;
+    const double va = (s.a0 >= 0 && j < s.an) ? a_cells[s.a0 + j] : 0.0;
+    const double vb = (s.b0 >= 0 && j < s.bn) ? b_cells[s.b0 + j] : 0.0;
+    const bool na = va != 0.0, nb = vb != 0.0;
+    if (na != nb || (na && !(fabs(va - vb) <= tol))) atomicOr(differs, 1u);
+}
+
+// ---------------------------------------------------------------- nonzero (pc_track_nonzero)
+
+// NaN is non-zero, -0.0 is not
+__global__ __launch_bounds__(256) void k_track_nz_flags(const double *__restrict__ cells, int64_t n, uint32_t *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) flags[i] = cells[i] != 0.0 ? 1u : 0u;
+}
+// out[idx[i]] = position of cell i on its slot; slot_start: first cell of every slot, ascending
+__global__ __launch_bounds__(256) void k_track_nz_select(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ idx, int64_t n,
+                                                         const int64_t *__restrict__ slot_start, int nslot, int64_t *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n || !flags[i]) return;
+    int lo = 0, hi = nslot;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (slot_start[mid] <= i) lo = mid + 1; else hi = mid;
+    }
+    out[idx[i]] = i - slot_start[lo - 1];
+}
+// out[k] = flags in front of cell at[k] (at[k] == n: all of them), from the exclusive sum idx
+__global__ __launch_bounds__(256) void k_track_pick(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ idx, int64_t n,
+                                                    const int64_t *__restrict__ at, int m, int64_t *__restrict__ out) {
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (k >= m) return;
+    out[k] = at[k] < n ? (int64_t)idx[at[k]] : (int64_t)idx[n - 1] + (int64_t)flags[n - 1];
+}
+
+// ---------------------------------------------------------------- export (pc_track_export)
+
+constexpr int kExportTile = 2048;        // T: cells one workgroup covers in the run-head kernel (256 lanes x 8)
+constexpr int kFormatRuns = 256;         // R: lines one workgroup formats, one per lane
+constexpr uint32_t kNotListed = 0xffffffffu;
+
+// Per exported slot: the fixed-tree sum (k_track_sum_partial's tree over the slot's own cells), first non-zero cell and
+// last non-zero cell + 1 (0: none).
+struct SlotStat { double sum; unsigned long long first, last1; };
+struct SlotCells { int64_t cell0, n; };
+
+// grid (max tiles, slots): block (x, y) adds tile x of slot y
+__global__ __launch_bounds__(256) void k_export_slot_partial(const SlotCells *__restrict__ slots, const double *__restrict__ cells, int64_t max_tiles,
+                                                             double *__restrict__ partial, SlotStat *__restrict__ stat) {
+    const SlotCells s = slots[blockIdx.y];
+    const int64_t base = (int64_t)blockIdx.x * kSumTile;
+    if (base >= s.n) return;                               // (uniform over the workgroup)
+    double v = 0.0;
+    unsigned long long first = ~0ull, last1 = 0ull;
+    for (int k = 0; k < kSumTile / 256; ++k) {
+        const int64_t p = base + (int64_t)k * 256 + threadIdx.x;
+        if (p < s.n) {
+            const double c = cells[s.cell0 + p];
+            v = v + c;
+            if (c != 0.0) { if (first == ~0ull) first = (unsigned long long)p; last1 = (unsigned long long)p + 1ull; }
+        }
+    }
+    const double r = block_tree_sum(v);
+    if (threadIdx.x == 0) partial[(int64_t)blockIdx.y * max_tiles + blockIdx.x] = r;
+    if (first != ~0ull) { atomicMin(&stat[blockIdx.y].first, first); atomicMax(&stat[blockIdx.y].last1, last1); }
+}
+// one workgroup per slot adds the slot's partials
+__global__ __launch_bounds__(256) void k_export_slot_final(const SlotCells *__restrict__ slots, const double *__restrict__ partial, int64_t max_tiles,
+                                                           SlotStat *__restrict__ stat) {
+    const int64_t nt = (slots[blockIdx.x].n + kSumTile - 1) / kSumTile;
+    double v = 0.0;
+    for (int64_t p = threadIdx.x; p < nt; p += 256) v = v + partial[(int64_t)blockIdx.x * max_tiles + p];
+    const double r = block_tree_sum(v);
+    if (threadIdx.x == 0) stat[blockIdx.x].sum = r;
+}
+
+// One written contig.  Its export cells are positions [pos0, pos0 + n) -- bedGraph: first to last non-zero; variableStep:
+// every stored cell -- and stand at [e0, e0 + n) of the concatenated export domain; cell0: the cell of pos0.  run_base:
+// runs (bedGraph) or non-zero cells (variableStep) in front of the contig; its header line is line run_base + k.
+struct ExRange {
+    int64_t e0, n, cell0, pos0, run_base;
+    int32_t name_off, name_len;
+};
+__device__ __forceinline__ int ex_range_of(const ExRange *__restrict__ r, int K, int64_t e) {
+    int lo = 0, hi = K;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (r[mid].e0 <= e) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+// the contig of line L: the last k with run_base[k] + k <= L
+__device__ __forceinline__ int ex_range_of_line(const ExRange *__restrict__ r, int K, int64_t L) {
+    int lo = 0, hi = K;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (r[mid].run_base + mid <= L) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+
+// kind 0 (bedGraph): a cell heads a run when it is the contig's first export cell or differs (!=) from the cell in front
+// of it -- read from HBM, so a run that began in an earlier tile needs nothing more; kind 1: when it is non-zero
+__global__ __launch_bounds__(256) void k_export_flags(int kind, const ExRange *__restrict__ ranges, int K, int64_t E, const double *__restrict__ cells,
+                                                      uint32_t *__restrict__ flags) {
+#pragma unroll
+    for (int k = 0; k < kExportTile / 256; ++k) {
+        const int64_t e = (int64_t)blockIdx.x * kExportTile + k * 256 + threadIdx.x;
+        if (e >= E) continue;
+        const ExRange r = ranges[ex_range_of(ranges, K, e)];
+        const int64_t j = e - r.e0;
+        const double v = cells[r.cell0 + j];
+        bool f;
+        if (kind == 0) f = j == 0 || v != cells[r.cell0 + j - 1];
+        else f = v != 0.0;
+        flags[e] = f ? 1u : 0u;
+    }
+}
+__global__ __launch_bounds__(256) void k_export_select(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ idx, int64_t E, uint32_t *__restrict__ run_e) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e < E && flags[e]) run_e[idx[e]] = (uint32_t)e;
+}
+// ranges[k].run_base for k = 0 .. K (entry K: the sentinel, all runs)
+__global__ __launch_bounds__(256) void k_export_bases(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ idx, int64_t E, ExRange *__restrict__ ranges, int K) {
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (k > K) return;
+    const int64_t e0 = ranges[k].e0;
+    ranges[k].run_base = e0 < E ? (int64_t)idx[e0] : (int64_t)idx[E - 1] + (int64_t)flags[E - 1];
+}
+// The values of the runs that are not plain are listed for the host (any order); listed_slot[r]: the run's place in the
+// list, kNotListed otherwise.
+__global__ __launch_bounds__(256) void k_export_classify(const ExRange *__restrict__ ranges, int K, const uint32_t *__restrict__ run_e, int64_t R,
+                                                         const double *__restrict__ cells, uint32_t *__restrict__ listed_slot, double *__restrict__ listed_val,
+                                                         uint32_t *__restrict__ n_listed) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const int64_t e = (int64_t)run_e[r];
+    const ExRange g = ranges[ex_range_of(ranges, K, e)];
+    const double v = cells[g.cell0 + (e - g.e0)];
+    uint32_t s = kNotListed;
+    if (value_class(v) == kValListed) { s = atomicAdd(n_listed, 1u); listed_val[s] = v; }
+    listed_slot[r] = s;
+}
+
+struct ExportView {
+    int kind;
+    const ExRange *ranges; int K;
+    const uint32_t *run_e;
+    const double *cells;
+    const uint8_t *names;
+    const uint32_t *listed_slot;
+    const uint8_t *strs, *lens;        // text (kReprMax bytes apart) and length of every listed value
+};
+// line L of the text into the sink: the length kernel counts what the format kernel stores
+template <typename Sink> __device__ __forceinline__ void export_line(Sink &s, const ExportView &x, int64_t L) {
+    const int k = ex_range_of_line(x.ranges, x.K, L);
+    const ExRange g = x.ranges[k];
+    const uint8_t *name = x.names + g.name_off;
+    if (L == g.run_base + k) {
+        if (x.kind == 0) put_bed_lead(s, name, (int64_t)g.name_len, g.pos0); else put_var_header(s, name, (int64_t)g.name_len);
+        return;
+    }
+    const int64_t run = L - k - 1;
+    const int64_t j = (int64_t)x.run_e[run] - g.e0;
+    const double v = x.cells[g.cell0 + j];
+    const uint32_t ls = x.listed_slot[run];
+    const uint8_t *vt = ls != kNotListed ? x.strs + (int64_t)kReprMax * ls : nullptr;
+    const int vl = ls != kNotListed ? (int)x.lens[ls] : 0;
+    if (x.kind == 0) {
+        const int64_t end = run + 1 < x.ranges[k + 1].run_base ? (int64_t)x.run_e[run + 1] - g.e0 : g.n;
+        put_bed_line(s, name, (int64_t)g.name_len, g.pos0 + j, g.pos0 + end, v, vt, vl);
+    } else put_var_line(s, g.pos0 + j, v, vt, vl);
+}
+__global__ __launch_bounds__(kFormatRuns) void k_export_lengths(ExportView x, int64_t nlines, int64_t *__restrict__ len) {
+    const int64_t L = (int64_t)blockIdx.x * kFormatRuns + threadIdx.x;
+    if (L >= nlines) return;
+    CountSink s;
+    s.n = 0;
+    export_line(s, x, L);
+    len[L] = s.n;
+}
+// every line's bytes at its offset; text has off[nlines - 1] + len[nlines - 1] bytes
+__global__ __launch_bounds__(kFormatRuns) void k_export_format(ExportView x, int64_t nlines, const int64_t *__restrict__ off, uint8_t *__restrict__ text) {
+    const int64_t L = (int64_t)blockIdx.x * kFormatRuns + threadIdx.x;
+    if (L >= nlines) return;
+    WriteSink s{text + off[L]};
+    export_line(s, x, L);
 }
 
 } // namespace pctrack

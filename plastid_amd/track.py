@@ -1,15 +1,22 @@
-"""Count tracks -- bedGraph, variableStep and fixedStep wiggle text -- read back in.
+"""Count tracks -- bedGraph, variableStep and fixedStep wiggle text -- read in, changed and written out.
 
-:class:`GenomeArray` is the reference's ``GenomeArray`` (plastid/genomics/genome_array.py:1323-1533) as a read-and-count
-class: float64 values per contig, strand and position in HBM, filled by :meth:`GenomeArray.add_from_wiggle` (:1978-1994;
-the text is parsed by the kernels of ``csrc/track_kernels.hip.h``) and read by ``get`` / ``[]``, ``get_counts_batch`` and
-``SegmentChain.get_counts`` / ``get_masked_counts`` through one gather kernel.  :func:`read_wiggle` is the reference's
-``WiggleReader`` (plastid/readers/wiggle.py:43-174) on the host, built from the same ``csrc/track_host.h`` the kernels
-compile: the model of the device import, and the way to read a track without a GPU.
+:class:`GenomeArray` is the reference's ``MutableAbstractGenomeArray`` / ``GenomeArray``
+(plastid/genomics/genome_array.py:1323-2104): float64 values per contig, strand and position in HBM, filled by
+:meth:`GenomeArray.add_from_wiggle` (:1978-1994; the text is parsed by the kernels of ``csrc/track_kernels.hip.h``) and
+by ``ga[seg] = val`` (:1535-1611), read by ``get`` / ``[]``, ``get_counts_batch`` and ``SegmentChain.get_counts`` /
+``get_masked_counts`` through one gather kernel, combined by ``apply_operation`` / ``+`` / ``-`` / ``*`` (:1697-1928),
+compared by ``==``, listed by ``nonzero`` and written by ``to_bedgraph`` / ``to_variable_step`` (:1996-2084), whose text
+is formatted by HIP kernels.  :func:`write_bedgraph` / :func:`write_variable_step` are the same writers on the host over a
+``DenseGenomeArray``: the model of the device export, and the way to write a track without a GPU.  :func:`read_wiggle` is
+the reference's ``WiggleReader`` (plastid/readers/wiggle.py:43-174) on the host, built from the same
+``csrc/track_host.h`` the kernels compile: the model of the device import, and the way to read a track without a GPU.
 
-Not here: ``__setitem__``, arithmetic between arrays, ``add_from_bowtie``, ``nonzero``, export, BigWig.
+Not here: ``add_from_bowtie``, ``plot``, ``SparseGenomeArray``, BigWig.  Deviations from the
+reference (``__eq__``, the ``all`` mode over differing contig sets, operand order) are listed in DESIGN.md section 8.
 """
 import ctypes
+import io
+import operator
 import os
 from collections import OrderedDict
 
@@ -17,6 +24,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
+from .exceptions import DataWarning, warn
 from .roitools import SegmentChain
 
 
@@ -91,6 +99,95 @@ def read_wiggle(fh_or_path):
                        dict(zip(("lines", "yielded", "escaped", "states"), (int(x) for x in stats))))
 
 
+def _track_line(kind, trackname, kwargs):
+    """The track definition line both writers start with (genome_array.py:2018-2022, :2056-2060)."""
+    line = "track type=%s name=%s" % ("bedGraph" if kind == 0 else "wiggle_0", trackname)
+    for k, v in sorted(kwargs.items(), key=lambda x: x[0]):
+        line += " %s=%s" % (k, v)
+    return line + "\n"
+
+
+def _write_text(fh, text):
+    """`text` (bytes or a memoryview of bytes) to a text-mode or binary file."""
+    if isinstance(fh, (io.RawIOBase, io.BufferedIOBase)):
+        fh.write(text)
+        return
+    try:
+        fh.write(str(text, "utf-8"))
+    except TypeError:
+        fh.write(text)
+
+
+def _host_writer():
+    from .bam import _load
+    L = _load()
+    if not hasattr(L.pb_track_writer_open, "_bound"):
+        vp = ctypes.c_void_p
+        L.pb_track_writer_open.restype = vp
+        L.pb_track_writer_open.argtypes = []
+        L.pb_track_writer_close.argtypes = [vp]
+        L.pb_track_writer_add.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, vp, ctypes.c_int64]
+        L.pb_track_writer_size.restype = ctypes.c_int64
+        L.pb_track_writer_size.argtypes = [vp]
+        L.pb_track_writer_text.restype = vp
+        L.pb_track_writer_text.argtypes = [vp]
+        L.pb_track_writer_stats.argtypes = [vp, vp]
+        L.pb_float_repr.argtypes = [vp, ctypes.c_int64, vp, vp]
+        L.pb_track_writer_open._bound = True
+    return L
+
+
+def _write_host(kind, host_array, fh, trackname, strand, kwargs):
+    assert strand in host_array.strands()
+    L = _host_writer()
+    h = L.pb_track_writer_open()
+    try:
+        for chrom in sorted(host_array.chroms()):
+            cells = np.ascontiguousarray(host_array._chroms[chrom][strand], np.float64)
+            if L.pb_track_writer_add(h, kind, chrom.encode("utf-8"), cells.ctypes.data, len(cells)) != 0:
+                raise ValueError(L.pb_last_error().decode())
+        text = ctypes.string_at(L.pb_track_writer_text(h), int(L.pb_track_writer_size(h)))
+        stats = np.zeros(4, np.int64)
+        L.pb_track_writer_stats(h, stats.ctypes.data)
+    finally:
+        L.pb_track_writer_close(h)
+    _write_text(fh, _track_line(kind, trackname, kwargs).encode("utf-8"))
+    _write_text(fh, text)
+    return dict(zip(("lines", "runs", "listed", "bytes"), (int(x) for x in stats)))
+
+
+def write_bedgraph(host_array, fh, trackname, strand, **kwargs):
+    """``GenomeArray.to_bedgraph`` (genome_array.py:2039-2084) of a host ``DenseGenomeArray`` by the serial writer of
+    ``csrc/track_host.h``, byte for byte.  Returns the writer's statistics: lines, runs, values that are not plain, bytes."""
+    return _write_host(0, host_array, fh, trackname, strand, kwargs)
+
+
+def write_variable_step(host_array, fh, trackname, strand, **kwargs):
+    """``GenomeArray.to_variable_step`` (genome_array.py:1996-2037) of a host ``DenseGenomeArray``; see :func:`write_bedgraph`."""
+    return _write_host(1, host_array, fh, trackname, strand, kwargs)
+
+
+def float_repr(values):
+    """``repr(float(x))`` of every value by the formatter of ``csrc/track_host.h`` (the one the export lists values for)."""
+    L = _host_writer()
+    v = np.ascontiguousarray(values, np.float64).ravel()
+    out = np.zeros(max(len(v), 1) * 24, np.uint8)
+    lens = np.zeros(max(len(v), 1), np.uint8)
+    if L.pb_float_repr(v.ctypes.data, len(v), out.ctypes.data, lens.ctypes.data) != 0:
+        raise ValueError(L.pb_last_error().decode())
+    raw = out.tobytes()
+    return [raw[24 * k:24 * k + int(lens[k])].decode("ascii") for k in range(len(v))]
+
+
+def _export_geometry():
+    out = (ctypes.c_int * 2)()
+    check(_lib.load().pc_track_export_geometry(out))
+    return int(out[0]), int(out[1])
+
+
+_OPS = {operator.add: 0, operator.sub: 1, operator.mul: 2}
+
+
 class GenomeArray(object):
     """Device-resident ``GenomeArray``: values live in HBM as float64 cells per (contig, strand).
 
@@ -115,17 +212,38 @@ class GenomeArray(object):
             check(self._lib.pc_track_declare(self._h, os.fsencode(name), int(length)))
         self._names = None
 
+    @classmethod
+    def _wrap(cls, handle, strands, min_chr_size, engine):
+        """A track the library made (``pc_track_combine``) as an array on `engine`."""
+        self = cls.__new__(cls)
+        self._strands, self.min_chr_size = tuple(strands), int(min_chr_size)
+        self._own_engine, self._engine, self._lib = False, engine, _lib.load()
+        self._normalize, self._h, self._names = False, handle, None
+        return self
+
+    @staticmethod
+    def like(other):
+        """An empty array of `other`'s contigs, lengths and strands, on its engine (genome_array.py:2086-2100)."""
+        return GenomeArray(other.lengths(), strands=other.strands(), min_chr_size=getattr(other, "min_chr_size", 10000000),
+                           engine=getattr(other, "_engine", None))
+
     def close(self):
+        """Free the cells; an engine of the array's own is closed with it (and takes the results of arithmetic on this
+        array along: they live on the same engine)."""
+        self._release(True)
+
+    def _release(self, close_engine):
         if self._h is not None:
             if self._engine._finalizer.alive:      # (an engine that is gone took its tracks with it)
                 self._lib.pc_track_destroy(self._h)
             self._h = None
-            if self._own_engine:
+            if self._own_engine and close_engine:
                 self._engine.close()
 
     def __del__(self):
+        # (the engine is left to its own finaliser: the results of arithmetic share it and may outlive this array)
         try:
-            self.close()
+            self._release(False)
         except Exception:
             pass
 
@@ -207,6 +325,185 @@ class GenomeArray(object):
         assert value in (True, False)
         self._normalize = value
 
+    # ---- writes
+    def __setitem__(self, seg, val):
+        """``ga[seg] = val`` over a |GenomicSegment| or a |SegmentChain| (genome_array.py:1535-1611).  `val`: a scalar, or a
+        vector 5'->3' of `seg` (reversed for '-', the chain as a whole).  The contig is born at ``min_chr_size`` if the array
+        does not hold it and grows by the rule of ``add_from_wiggle``; one launch writes every segment of a chain.
+        ``ValueError``: the vector's length is not the region's (nothing is written).  A write while normalisation is on
+        warns ``DataWarning`` and proceeds."""
+        segs = list(seg) if isinstance(seg, SegmentChain) else [seg]
+        strand = seg.strand
+        slot = self._slot(strand)
+        total = sum(max(int(s.end) - int(s.start), 0) for s in segs)
+        scalar = np.ndim(val) == 0
+        if scalar:
+            values, scalar_value = None, float(val)
+        else:
+            values, scalar_value = np.ascontiguousarray(val, np.float64).ravel(), 0.0
+            if len(values) != total:
+                raise ValueError("cannot set %d positions from a vector of %d values" % (total, len(values)))
+        if any(int(s.start) < 0 for s in segs):
+            raise ValueError("cannot set positions below 0")
+        if self._normalize:
+            warn("Temporarily turning off normalization during value set. It will be re-enabled automatically when complete.", DataWarning)
+        if not segs:
+            return
+        start = np.array([s.start for s in segs], np.int64)
+        end = np.maximum(np.array([s.end for s in segs], np.int64), start)
+        # genome order within the chain; a '-' vector runs the other way over the whole chain
+        before = np.concatenate([[0], np.cumsum(end - start)[:-1]]).astype(np.int64)
+        rev = strand == "-"
+        val_off = (total - 1 - before) if rev else before
+        val_step = np.full(len(segs), -1 if rev else 1, np.int8)
+        self._names = None
+        check(self._lib.pc_track_set(self._h, os.fsencode(seg.chrom), slot, len(segs), start.ctypes.data, end.ctypes.data,
+                                     np.ascontiguousarray(val_off, np.int64).ctypes.data, val_step.ctypes.data,
+                                     values.ctypes.data if values is not None else None, 0 if values is None else len(values), scalar_value),
+              "pc_track_set")
+
+    # ---- arithmetic
+    def apply_operation(self, other, func, mode="same"):
+        """A NEW array ``func(self, other)`` elementwise; `self` and `other` are unchanged (genome_array.py:1697-1835).
+        `func`: ``operator.add``, ``operator.sub`` or ``operator.mul`` (``TypeError`` otherwise: the cells are not on the
+        host).  `other`: a scalar -- it acts on every cell up to each contig's length -- or a :class:`GenomeArray` on the
+        same engine (``ValueError`` otherwise), combined under `mode`: ``same`` (equal contigs, strands and lengths are
+        asserted; the result reports the reference's lengths, 10000 more per strand, the operands keep theirs), ``truncate`` (common contigs and strands, the shorter length) or ``all`` (the union, the longer length,
+        zero for what one side lacks; `self`'s contigs and strands first)."""
+        if func not in _OPS:
+            raise TypeError("apply_operation runs operator.add, operator.sub or operator.mul on the device; got %r" % (func,))
+        if self._normalize:
+            warn("Temporarily turning off normalization during value set. It will be re-enabled automatically when complete.", DataWarning)
+        out = ctypes.c_void_p()
+        if isinstance(other, GenomeArray):
+            if other._engine is not self._engine:
+                raise ValueError("the arrays live on different engines")
+            if mode == "same":
+                assert set(self.keys()) == set(other.keys())
+                assert self.strands() == other.strands()
+                assert self.lengths() == other.lengths()
+                strands = list(self._strands)
+            elif mode == "all":
+                strands = list(self._strands) + [s for s in other._strands if s not in self._strands]
+            elif mode == "truncate":
+                strands = [s for s in self._strands if s in other._strands]
+            else:
+                raise ValueError("Mode not understood. Must be 'same', 'all', or 'truncate.'")
+            if not strands:
+                raise ValueError("the arrays have no strand in common")
+            slot_a = np.array([self._strands.index(s) if s in self._strands else -1 for s in strands], np.int32)
+            slot_b = np.array([other._strands.index(s) if s in other._strands else -1 for s in strands], np.int32)
+            # (the reference writes its `same` result through __setitem__ over whole contigs, and a write that ends at the
+            # length grows the contig: its result is 10000 longer per strand, genome_array.py:1771-1775, :1593-1602)
+            pad = 10000 * len(strands) if mode == "same" else 0
+            check(self._lib.pc_track_combine(self._h, other._h, 0.0, _OPS[func], 0 if mode == "truncate" else 1, pad, len(strands),
+                                             slot_a.ctypes.data, slot_b.ctypes.data, ctypes.byref(out)), "pc_track_combine")
+        else:
+            if np.ndim(other) != 0:
+                raise TypeError("the other operand is a scalar or a GenomeArray, not %r" % (type(other),))
+            strands = list(self._strands)
+            slot_a = np.arange(len(strands), dtype=np.int32)
+            check(self._lib.pc_track_combine(self._h, None, float(other), _OPS[func], 1, 0, len(strands), slot_a.ctypes.data, None,
+                                             ctypes.byref(out)), "pc_track_combine")
+        return GenomeArray._wrap(out, strands, self.min_chr_size, self._engine)
+
+    def __add__(self, other, mode="all"):
+        return self.apply_operation(other, operator.add, mode=mode)
+
+    def __mul__(self, other, mode="all"):
+        return self.apply_operation(other, operator.mul, mode=mode)
+
+    def __sub__(self, other, mode="all"):
+        """``self + other * -1`` (genome_array.py:1927)."""
+        return self.__add__(other * -1)
+
+    def __eq__(self, other, tol=1e-10):
+        """The same non-zero positions on every contig and strand, and ``|a - b| <= tol`` at each of them; lengths need
+        not be equal.  Unlike the reference's test (genome_array.py:1445-1448) the difference counts in both directions
+        and at the last non-zero position too.  A reduction on the device."""
+        if not isinstance(other, GenomeArray):
+            return NotImplemented
+        if other._engine is not self._engine:
+            raise ValueError("the arrays live on different engines")
+        mine, theirs = self.chroms(), other.chroms()
+        chroms = mine + [c for c in theirs if c not in mine]
+        strands = list(self._strands) + [s for s in other._strands if s not in self._strands]
+        ia, ib = {c: i for i, c in enumerate(mine)}, {c: i for i, c in enumerate(theirs)}
+        cols = [[], [], [], []]
+        for c in chroms:
+            for s in strands:
+                cols[0].append(ia.get(c, -1))
+                cols[1].append(self._strands.index(s) if s in self._strands else -1)
+                cols[2].append(ib.get(c, -1))
+                cols[3].append(other._strands.index(s) if s in other._strands else -1)
+        arrs = [np.array(x, np.int32) for x in cols]
+        equal = ctypes.c_int(0)
+        check(self._lib.pc_track_equal(self._h, other._h, len(arrs[0]), *[a.ctypes.data for a in arrs], float(tol), ctypes.byref(equal)),
+              "pc_track_equal")
+        return bool(equal.value)
+
+    def __ne__(self, other):
+        r = self.__eq__(other)
+        return r if r is NotImplemented else not r
+
+    __hash__ = object.__hash__
+
+    def nonzero(self):
+        """``{chrom: {strand: int64 indices of the non-zero positions}}`` (genome_array.py:1679-1695); NaN is non-zero,
+        ``-0.0`` is not.  Count, exclusive sum and select on the device; only the indices come back."""
+        chroms = self.chroms()
+        counts = np.zeros(max(len(chroms) * len(self._strands), 1), np.int64)
+        check(self._lib.pc_track_nonzero_count(self._h, counts.ctypes.data), "pc_track_nonzero_count")
+        total = int(counts.sum())
+        flat = np.zeros(max(total, 1), np.int64)
+        check(self._lib.pc_track_nonzero_read(self._h, flat.ctypes.data, total), "pc_track_nonzero_read")
+        out, at = OrderedDict(), 0
+        for i, c in enumerate(chroms):
+            out[c] = {}
+            for s, st in enumerate(self._strands):
+                n = int(counts[i * len(self._strands) + s])
+                out[c][st] = flat[at:at + n].copy()
+                at += n
+        return out
+
+    # ---- export
+    def _export(self, kind, fh, trackname, strand, printer, kwargs):
+        assert strand in self._strands
+        nbytes = ctypes.c_int64(0)
+        check(self._lib.pc_track_export(self._h, kind, self._strands.index(strand), ctypes.byref(nbytes)), "pc_track_export")
+        text = np.empty(max(int(nbytes.value), 1), np.uint8)
+        check(self._lib.pc_track_export_read(self._h, text.ctypes.data, int(nbytes.value)), "pc_track_export_read")
+        if printer is not None:
+            for chrom in sorted(self.chroms()):
+                printer.write("Writing chromosome %s..." % chrom)
+        _write_text(fh, _track_line(kind, trackname, kwargs).encode("utf-8"))
+        _write_text(fh, memoryview(text[:int(nbytes.value)]))
+
+    def to_bedgraph(self, fh, trackname, strand, printer=None, **kwargs):
+        """Write `strand` as bedGraph, the reference's text byte for byte (genome_array.py:2039-2084): contigs in sorted
+        order, only those whose sum is > 0; runs of equal value between the first and the last non-zero position.  The
+        text is built in HBM (``csrc/track_kernels.hip.h``: run heads, select, line lengths, format) and read back once."""
+        self._export(0, fh, trackname, strand, printer, kwargs)
+
+    def to_variable_step(self, fh, trackname, strand, printer=None, **kwargs):
+        """Write `strand` as variableStep wiggle (genome_array.py:1996-2037): every contig's header, a line per non-zero
+        position.  See :meth:`to_bedgraph`."""
+        self._export(1, fh, trackname, strand, printer, kwargs)
+
+    def export_stats(self):
+        """Of the last export: lines, runs (bedGraph) or non-zero positions (variableStep), values listed for the host's
+        ``repr`` formatter (integers below 10^16, nan and inf never are), bytes behind the track line."""
+        out = np.zeros(4, np.int64)
+        check(self._lib.pc_track_export_stats(self._h, out.ctypes.data))
+        return dict(zip(("lines", "runs", "listed", "bytes"), (int(x) for x in out)))
+
+    def export_timing(self):
+        """Milliseconds of the last export: slot sums, run heads + select, listed values, line lengths + offsets, format,
+        read-back."""
+        out = np.zeros(6, np.float64)
+        check(self._lib.pc_track_export_timing(self._h, out.ctypes.data))
+        return dict(zip(("slot_sums", "runs", "listed_values", "lengths", "format", "read_back"), (float(x) for x in out)))
+
     # ---- the query side
     def _gather(self, contig, slot, start, end, out_off, out_step, total):
         out = np.zeros(int(total), np.float64)
@@ -270,3 +567,10 @@ class GenomeArray(object):
         finally:
             self._normalize = norm
         return host
+
+
+def __getattr__(name):
+    # EXPORT_TILE (T): cells one workgroup covers in the run-head kernel; FORMAT_RUNS (R): lines one workgroup formats
+    if name in ("EXPORT_TILE", "FORMAT_RUNS"):
+        return _export_geometry()[0 if name == "EXPORT_TILE" else 1]
+    raise AttributeError(name)
