@@ -63,6 +63,17 @@ struct CrcTables {
 const CrcTables &crc_tables() { static const CrcTables t; return t; }
 
 double ms_between(hipEvent_t a, hipEvent_t b) { float t = 0.f; return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
+// The events that cut a call into laps: N events, destroyed on exit; lap k lies between events k and k + 1.
+template <int N> struct LapEvents {
+    hipEvent_t ev[N] = {};
+    int create() {
+        for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
+        return PC_OK;
+    }
+    ~LapEvents() { for (auto x : ev) if (x) (void)hipEventDestroy(x); }
+    hipEvent_t operator[](int k) const { return ev[k]; }
+    void laps(double *ms, int n) const { for (int k = 0; k < n; ++k) ms[k] = ms_between(ev[k], ev[k + 1]); }
+};
 // one more buffer of a phase, unless an earlier one has failed
 template <typename Buf> void room(int &rc, Buf &buf, size_t n) { if (rc == PC_OK) rc = buf.reserve(n); }
 // A step's temporaries are read by what it queued: an early return drains the stream before they go out of scope
@@ -71,6 +82,26 @@ struct DrainOnExit {
     hipStream_t st; bool armed = true;
     ~DrainOnExit() { if (armed) (void)hipStreamSynchronize(st); }
 };
+// A hipcub call is `call(tmp, bytes)`: with tmp null it says how many temporary bytes it needs, otherwise it runs.
+// cub_run asks, grows `tmp` and runs (a grown block is recycled through the engine's pool in stream order: no
+// synchronise).  Calls that share a temporary sized up front ask through cub_need -- `bytes`: the call's own answer,
+// `most`: the largest so far -- and run through cub_run_sized, which asks nothing more.
+template <typename Call> int cub_need(size_t &most, size_t &bytes, Call call) {
+    bytes = 0;
+    HIP_TRY(call((void *)nullptr, bytes));
+    most = std::max(most, bytes);
+    return PC_OK;
+}
+template <typename Tmp, typename Call> int cub_run_sized(Tmp &tmp, size_t bytes, Call call) {
+    HIP_TRY(call((void *)tmp.p, bytes));
+    return PC_OK;
+}
+template <typename Tmp, typename Call> int cub_run(Tmp &tmp, Call call) {
+    size_t most = 16, bytes = 0;
+    PC_TRY(cub_need(most, bytes, call));
+    PC_TRY(tmp.reserve(most));
+    return cub_run_sized(tmp, bytes, call);
+}
 
 // The decoder's experiment and test switches, read at the top of every open (the tests flip them between opens on one engine).
 struct BamKnobs {
@@ -122,7 +153,7 @@ struct BamDecode {
     std::string path;
     BamKnobs knobs;
     BamClock clk{knobs.timing};
-    hipEvent_t ev[5] = {};             // allocations done | tables queued | inflated | records chained | columns written
+    LapEvents<5> ev;                   // allocations done | tables queued | inflated | records chained | columns written
     DevBuf<uint8_t> d_stream;          // the inflated stream (+ 64 zero bytes)
     DevBuf<pcbam::Member> d_members;
     DevBuf<pcbam::MemberChain> d_chain;   // every member's walk over its records' length prefixes, and the record offsets it found
@@ -411,14 +442,7 @@ int record_defect(unsigned long long first_err, bool truncated, const char *path
 }
 
 // the events around the sort phase of an open with PC_BAM_SORT: key kernel [0, 1]; sort, ranks and run offsets [2, 3]
-struct SortEvents {
-    hipEvent_t ev[4] = {};
-    int create() {
-        for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
-        return PC_OK;
-    }
-    ~SortEvents() { for (auto x : ev) if (x) (void)hipEventDestroy(x); }
-};
+typedef LapEvents<4> SortEvents;
 
 // ---- the common head of phase 5 (decode_columns, index_records): the record table on the device and every record's fields
 struct RecordTable {
@@ -898,8 +922,7 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     b->e = e; b->name = d.path; b->members = (int64_t)pl.nm(); b->inflated_bytes = (int64_t)pl.total_u; b->compressed_bytes = size;
     b->uploaded_bytes = pl.image_bytes; b->runs = (int64_t)pl.runs.size();
     struct Guard { pc_bam *b; ~Guard() { if (b) pc_bam_close(b); } } guard{b};
-    for (auto &x : d.ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]); } } evg{d.ev};
+    PC_TRY(d.ev.create());
     int rc = upload_and_inflate(d, image, pl, uploaded);
     if (rc != PC_OK) return rc;
     BamHeader h;
@@ -915,7 +938,7 @@ static int bam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     b->key_bits = 0;
     rc = decode_columns(d, pl, span, h, recs, *b, sort);
     if (rc != PC_OK) return rc;
-    for (int k = 0; k < 4; ++k) b->ms[k] = ms_between(d.ev[k], d.ev[k + 1]);
+    d.ev.laps(b->ms, 4);
     guard.b = nullptr;
     *out = b;
     return PC_OK;
@@ -936,8 +959,7 @@ static int bam_index_impl(pc_engine *e, const void *image_, int64_t size, const 
     const int defect = bh::plan_members(image, size, nullptr, knobs.walk_min, pl);
     if (defect) return host_defect(defect, d.path.c_str());
     d.clk.lap("member walk");
-    for (auto &x : d.ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]); } } evg{d.ev};
+    PC_TRY(d.ev.create());
     int rc = upload_and_inflate(d, image, pl, uploaded);
     if (rc != PC_OK) return rc;
     BamHeader h;
@@ -974,7 +996,7 @@ static int bam_index_impl(pc_engine *e, const void *image_, int64_t size, const 
     if (rc != PC_OK) return rc;
     if (shape.csi) idx->stats[5] = parts.n_windows;
     const auto t_e = std::chrono::steady_clock::now();
-    for (int k = 0; k < 3; ++k) idx->ms[k] = ms_between(d.ev[k], d.ev[k + 1]);
+    d.ev.laps(idx->ms, 3);
     idx->ms[3] = parts.ms_fields; idx->ms[4] = parts.ms_kernels; idx->ms[5] = parts.ms_readback;
     idx->ms[6] = std::chrono::duration<double, std::milli>(t_e - t_f).count();
     idx->ms[7] = std::chrono::duration<double, std::milli>(t_e - t_0).count();

@@ -145,8 +145,7 @@ static int sam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     b->ref_names = hd.ref_names; b->ref_lengths = hd.ref_lengths;
     b->sort_requested = sort;
     struct Guard { pc_bam *b; ~Guard() { if (b) pc_bam_close(b); } } guard{b};
-    for (auto &x : d.ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]); } } evg{d.ev};
+    PC_TRY(d.ev.create());
     BamHeader h;
     h.n_ref = (uint32_t)hd.ref_names.size();
     BamRecords recs;
@@ -213,7 +212,7 @@ static int sam_open_impl(pc_engine *e, const void *image_, int64_t size, const c
     d.clk.lap("fields + placement + columns");
     b->n = w.n_staged; b->nrun = w.n_runs;
     // upload | line starts | fields | placement + columns
-    for (int k = 0; k < 4; ++k) b->ms[k] = ms_between(d.ev[k], d.ev[k + 1]);
+    d.ev.laps(b->ms, 4);
     guard.b = nullptr;
     *out = b;
     return PC_OK;

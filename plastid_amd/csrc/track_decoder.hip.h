@@ -1,26 +1,21 @@
 // Count tracks on the GPU, host side: the pc_track_* entry points of include/plastid_counts.h.  A pc_track is the
 // reference's GenomeArray (plastid/genomics/genome_array.py:1323-1533) as a read-and-count object: float64 cells per
 // (contig, strand slot) in one block of HBM, filled by pc_track_add_text / _path (add_from_wiggle, :1978-1994) and read by
-// pc_track_gather.  One import is six phases (track_add_impl): upload, line starts (both shared with SAM text),
-// classify + state records, fields (+ the host's conversion of the escaped lines), growth and storage, sort + apply.
-// The host looks at the state lines, the escaped lines and the growth lines only.
+// pc_track_gather.  What decides the contigs, their lengths and every cell address is the track's ContigTable
+// (track_table.h, HIP-free and CPU-tested); the entry points here check their arguments, ask the table for a layout and
+// queue the kernels.  One import is a TrackImport taken through its phases (track_add_impl): upload and line starts
+// (both shared with SAM text), classify + state records, fields (+ the host's conversion of the escaped lines), births,
+// growth and storage, sort + apply.  The host looks at the state lines, the escaped lines and the growth lines only.
 // Revision 16 makes it the reference's mutable GenomeArray (:1535-2104): pc_track_set (one launch per segment or chain),
 // pc_track_combine (a new track from a op b or a op scalar), pc_track_equal, pc_track_nonzero_count / _read and
-// pc_track_export / _read: the bedGraph / variableStep text of a strand built in HBM in five phases and read back once;
-// of an export the host sees the per-slot sums and the values that are not plain.
+// pc_track_export / _read: the bedGraph / variableStep text of a strand built in HBM by the phases of a TrackExport and
+// read back once; of an export the host sees the per-slot sums and the values that are not plain.
 // Part of the one translation unit of plastid_counts.hip (behind sam_decoder.hip.h).
 #include "track_kernels.hip.h"
 
 struct pc_track {
     pc_engine *e = nullptr;
-    int nstrands = 2;
-    int64_t min_chr_size = 10000000;
-    struct Contig { std::string name; int64_t length = 0; bool born = false; };
-    std::vector<Contig> contigs;            // by internal id, in order of first mention
-    std::map<std::string, int32_t> ids;
-    std::vector<int32_t> order;             // the public order: declared contigs, then the others by first yielded line
-    std::vector<int64_t> ext, cell_off;     // per slot (id * nstrands + strand): cells [cell_off, cell_off + ext)
-    int64_t ncells = 0;
+    pctrack::ContigTable tab;               // contigs, public order, lengths, the cells of every slot
     DevBuf<double> cells;
     bool sum_valid = false;
     double sum = 0.0;
@@ -34,7 +29,7 @@ struct pc_track {
     // the last pc_track_nonzero_count: the indices wait in HBM for pc_track_nonzero_read
     DevBuf<int64_t> nz;
     int64_t nz_total = -1;
-    std::vector<int64_t> nz_begin, nz_cnt;  // per slot: its share of nz
+    pctrack::NzShares nz_shares;            // per slot: its share of nz
 };
 
 // an engine that is destroyed takes its tracks with it (pc_destroy): their cells come from its pool
@@ -46,27 +41,6 @@ static void destroy_tracks_of(pc_engine *e) {
 namespace {
 
 namespace tk = pctrack;
-
-int32_t track_contig_id(pc_track *t, const std::string &name) {
-    auto it = t->ids.find(name);
-    if (it != t->ids.end()) return it->second;
-    const int32_t id = (int32_t)t->contigs.size();
-    pc_track::Contig c;
-    c.name = name; c.length = t->min_chr_size; c.born = false;
-    t->contigs.push_back(c);
-    t->ids.emplace(name, id);
-    t->ext.resize(t->contigs.size() * (size_t)t->nstrands, 0);
-    t->cell_off.resize(t->contigs.size() * (size_t)t->nstrands, 0);
-    return id;
-}
-
-// an undeclared contig is born at min_chr_size, behind the contigs the array holds already (import and pc_track_set)
-void track_bear(pc_track *t, int32_t id) {
-    pc_track::Contig &c = t->contigs[(size_t)id];
-    if (c.born) return;
-    c.born = true; c.length = t->min_chr_size;
-    t->order.push_back(id);
-}
 
 // text bounds and data index of listed lines, for the host
 struct TrackLineInfo { uint64_t b, e; uint32_t line, data_index; };
@@ -81,272 +55,434 @@ __global__ __launch_bounds__(256) void k_track_line_info(const uint32_t *__restr
     out[k] = o;
 }
 // contig and end of the growth lines, for the host's fold
-struct TrackGrowth { int64_t stop; uint32_t line; int32_t contig; };
 __global__ __launch_bounds__(256) void k_track_growth_info(const uint32_t *__restrict__ lines, uint32_t n, const tk::LineRec *__restrict__ recs,
-                                                           const int32_t *__restrict__ contig_of, TrackGrowth *__restrict__ out) {
+                                                           const int32_t *__restrict__ contig_of, tk::GrowthLine *__restrict__ out) {
     const uint32_t k = blockIdx.x * 256u + threadIdx.x;
     if (k >= n) return;
-    TrackGrowth o;
+    tk::GrowthLine o;
     o.line = lines[k]; o.stop = recs[o.line].stop; o.contig = contig_of[o.line];
     out[k] = o;
 }
 
 inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-int read_counters(hipStream_t st, const DevBuf<tk::TrackCounters> &d, tk::TrackCounters &h) {
-    HIP_TRY(hipMemcpyAsync(&h, d.p, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return PC_OK;
-}
-
-// listed lines with their text bounds, sorted by line
-int fetch_line_info(hipStream_t st, const DevBuf<uint32_t> &lines, uint32_t n, const SamLines &ln, uint64_t text_len, const DevBuf<uint32_t> &data_index,
-                    std::vector<TrackLineInfo> &out) {
-    out.resize(n);
-    if (!n) return PC_OK;
-    DevBuf<TrackLineInfo> d_info;
-    DrainOnExit drained{st};
-    PC_TRY(d_info.reserve(n));
-    hipLaunchKernelGGL(k_track_line_info, dim3(grid256(n)), dim3(256), 0, st, lines.p, n, ln.d_line_start.p, text_len, data_index.p, d_info.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out.data(), d_info.p, (size_t)n * sizeof(TrackLineInfo), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    drained.armed = false;
-    std::sort(out.begin(), out.end(), [](const TrackLineInfo &a, const TrackLineInfo &b) { return a.line < b.line; });
-    return PC_OK;
-}
-
-// Storage of the strand slots: every slot keeps its cells, slot (c, strand) reaches at least furthest[c].
-int track_grow_storage(pc_track *t, int strand, const std::vector<unsigned long long> &furthest, hipStream_t st) {
-    const size_t nslot = t->contigs.size() * (size_t)t->nstrands;
-    std::vector<int64_t> ext(t->ext.begin(), t->ext.end()), off(nslot, 0);
-    ext.resize(nslot, 0);
-    bool grows = false;
-    for (size_t c = 0; c < furthest.size(); ++c) {
-        int64_t &x = ext[c * (size_t)t->nstrands + (size_t)strand];
-        if ((int64_t)furthest[c] > x) { x = (int64_t)furthest[c]; grows = true; }
-    }
-    if (!grows) return PC_OK;
-    int64_t total = 0;
-    for (size_t s = 0; s < nslot; ++s) { off[s] = total; total += ext[s]; }
-    DevBuf<double> fresh;
-    fresh.pool = &t->e->pool;
-    PC_TRY(fresh.reserve((size_t)total));
-    HIP_TRY(hipMemsetAsync(fresh.p, 0, (size_t)total * sizeof(double), st));
-    for (size_t s = 0; s < nslot && s < t->ext.size(); ++s)
-        if (t->ext[s] > 0)
-            HIP_TRY(hipMemcpyAsync(fresh.p + off[s], t->cells.p + t->cell_off[s], (size_t)t->ext[s] * sizeof(double), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));   // (the old block goes back to the pool)
-    t->cells.swap(fresh);
-    t->ext = ext; t->cell_off = off; t->ncells = total;
-    return PC_OK;
-}
-
-int track_add_impl(pc_track *t, const void *image_, int64_t size, const char *name, int strand) {
-    if (!t || size < 0 || (size > 0 && !image_)) return fail(PC_ERR_ARG, "pc_track_add_text: bad arguments");
-    if (strand < 0 || strand >= t->nstrands) return fail(PC_ERR_ARG, "pc_track_add_text: strand slot %d of %d", strand, t->nstrands);
-    pc_engine *e = t->e;
-    const uint8_t *text = (const uint8_t *)image_;
-    HIP_TRY(hipSetDevice(e->device));
-    PoolScope pool_scope(&e->pool);
-    BamDecode d{e, e->stream, name ? name : "<memory>", BamKnobs()};
-    hipStream_t st = d.st;
-    for (int k = 0; k < 6; ++k) t->stats[k] = 0;
-    for (int k = 0; k < 5; ++k) t->ms[k] = 0.0;
-    if (size == 0) return PC_OK;
-    hipEvent_t ev[6] = {};
-    for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 6; ++i) (void)hipEventDestroy(ev[i]); } } evg{ev};
-    const bool open_end = text[size - 1] != (uint8_t)'\n';
+// What the phases of one import share.  The host vectors that feed an upload live here, behind the stream's last use.
+struct TrackImport {
+    pc_track *t;
+    const uint8_t *text;
+    int64_t size;
+    int strand;
+    BamDecode d;
+    hipStream_t st;
+    LapEvents<6> ev;                   // reserved | uploaded | line starts | states | fields | applied
     SamLines ln;
-    {
-        // phases 1, 2: the text to HBM, the line starts (sam_decoder.hip.h)
-        Upload u;
-        Drain drain{e, true};
-        PC_TRY(d.d_stream.reserve((size_t)size + 64));
-        HIP_TRY(hipEventRecord(ev[0], st));
-        PC_TRY(sam_upload(d, text, size, nullptr, u));
-        HIP_TRY(hipEventRecord(ev[1], st));
-        PC_TRY(sam_line_starts(d, size, open_end, ln));
-        drain.armed = false;
-    }
-    HIP_TRY(hipEventRecord(ev[2], st));
-    const int64_t n = ln.nrec;
-    t->stats[0] = n;
-    if (n == 0) return PC_OK;
-    const uint64_t text_len = (uint64_t)size;
-    const unsigned g = grid256(n);
-
-    // phase 3: classes, the state lines, the data-line prefix count
+    int64_t n = 0;                     // lines
+    unsigned g = 0;
+    int ncontig = 0;
+    tk::TrackCounters cnt;
+    unsigned long long host_err = tk::kNoDefect;
+    std::vector<TrackLineInfo> info;
+    std::vector<tk::StateRec> recs;
+    std::vector<tk::LineRec> patch;
+    std::vector<int32_t> patch_contig;
+    std::vector<uint32_t> lines, first_line;
+    std::vector<int64_t> len0, off;
+    std::vector<unsigned long long> furthest;
     DevBuf<uint8_t> d_cls, d_tmp;
-    DevBuf<int32_t> d_sig, d_prev_sig, d_contig_of, d_head;
+    DevBuf<int32_t> d_sig, d_prev_sig, d_contig_of, d_head, d_patch_contig;
     DevBuf<uint32_t> d_is_data, d_data_index, d_list, d_idx, d_idx2, d_first_line, d_long;
     DevBuf<uint64_t> d_key, d_key2, d_end_key, d_prev_end, d_multi, d_multi2;
     DevBuf<tk::TrackCounters> d_cnt;
     DevBuf<tk::StateRec> d_recs;
     DevBuf<tk::LineRec> d_line, d_patch;
-    DevBuf<int32_t> d_patch_contig;
     DevBuf<int64_t> d_len0, d_off;
     DevBuf<unsigned long long> d_furthest;
-    DevBuf<TrackGrowth> d_growth;
-    DrainOnExit drained{st};
-    int rc = PC_OK;
-    room(rc, d_cls, (size_t)n); room(rc, d_sig, (size_t)n); room(rc, d_prev_sig, (size_t)n); room(rc, d_is_data, (size_t)n);
-    room(rc, d_data_index, (size_t)n); room(rc, d_list, (size_t)n); room(rc, d_cnt, 1);
-    if (rc != PC_OK) return rc;
-    tk::TrackCounters cnt;
-    memset(&cnt, 0, sizeof(cnt));
-    cnt.first_err = tk::kNoDefect;
-    HIP_TRY(hipMemcpyAsync(d_cnt.p, &cnt, sizeof(cnt), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(tk::k_track_classify, dim3(g), dim3(256), 0, st, d.d_stream.p, text_len, ln.d_line_start.p, n, d_cls.p, d_sig.p, d_is_data.p);
-    HIP_TRY(hipGetLastError());
-    {
-        size_t b1 = 0, b2 = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, b1, d_sig.p, d_prev_sig.p, hipcub::Max(), (int32_t)-1, (int)n, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b2, d_is_data.p, d_data_index.p, (int)n, st));
-        PC_TRY(d_tmp.reserve(std::max<size_t>(std::max(b1, b2), 16)));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(d_tmp.p, b1, d_sig.p, d_prev_sig.p, hipcub::Max(), (int32_t)-1, (int)n, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, d_is_data.p, d_data_index.p, (int)n, st));
+    DevBuf<tk::GrowthLine> d_growth;
+    TrackImport(pc_track *t_, const uint8_t *text_, int64_t size_, const char *name, int strand_)
+        : t(t_), text(text_), size(size_), strand(strand_), d{t_->e, t_->e->stream, name ? name : "<memory>", BamKnobs()}, st(d.st) {}
+    uint64_t text_len() const { return (uint64_t)size; }
+    void note_defect(uint32_t line, int err) { if (err != tk::kTrkOk) host_err = std::min(host_err, ((unsigned long long)line << 8) | (unsigned long long)err); }
+    int read_counters() {
+        HIP_TRY(hipMemcpyAsync(&cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return PC_OK;
     }
-    hipLaunchKernelGGL(tk::k_track_states, dim3(g), dim3(256), 0, st, d.d_stream.p, text_len, ln.d_line_start.p, n, d_cls.p, d_prev_sig.p, d_list.p, &d_cnt.p->n_state);
-    HIP_TRY(hipGetLastError());
-    PC_TRY(read_counters(st, d_cnt, cnt));
-    std::vector<TrackLineInfo> info;
-    PC_TRY(fetch_line_info(st, d_list, cnt.n_state, ln, text_len, d_data_index, info));
-    unsigned long long host_err = tk::kNoDefect;
-    std::vector<tk::StateRec> recs(info.size());
-    for (size_t k = 0; k < info.size(); ++k) {
-        const int err = tk::parse_state(text + info[k].b, text + info[k].e, (int64_t)info[k].line, (int64_t)info[k].data_index,
-                                        [t](const std::string &nm) { return track_contig_id(t, nm); }, recs[k]);
-        if (err != tk::kTrkOk) host_err = std::min(host_err, ((unsigned long long)info[k].line << 8) | (unsigned long long)err);
-    }
-    t->stats[3] = (int64_t)recs.size();
-    HIP_TRY(hipEventRecord(ev[3], st));
+};
 
-    // phase 4: the fields of every yielding line; the escaped ones on the host
-    room(rc, d_recs, std::max<size_t>(recs.size(), 1)); room(rc, d_line, (size_t)n); room(rc, d_contig_of, (size_t)n);
-    if (rc != PC_OK) return rc;
-    if (!recs.empty()) HIP_TRY(hipMemcpyAsync(d_recs.p, recs.data(), recs.size() * sizeof(tk::StateRec), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(tk::k_track_fields, dim3(g), dim3(256), 0, st, d.d_stream.p, text_len, ln.d_line_start.p, n, d_cls.p, d_data_index.p, d_recs.p,
-                       (int64_t)recs.size(), d_line.p, d_contig_of.p, d_list.p, d_cnt.p);
+// the first `count` lines of d_list with their text bounds, sorted by line, into c.info
+int fetch_line_info(TrackImport &c, uint32_t count) {
+    c.info.resize(count);
+    if (!count) return PC_OK;
+    DevBuf<TrackLineInfo> d_info;
+    DrainOnExit drained{c.st};
+    PC_TRY(d_info.reserve(count));
+    hipLaunchKernelGGL(k_track_line_info, dim3(grid256(count)), dim3(256), 0, c.st, c.d_list.p, count, c.ln.d_line_start.p, c.text_len(), c.d_data_index.p, d_info.p);
     HIP_TRY(hipGetLastError());
-    PC_TRY(read_counters(st, d_cnt, cnt));
-    t->stats[1] = cnt.n_yield; t->stats[2] = cnt.n_escaped;
-    std::vector<tk::LineRec> patch;
-    std::vector<int32_t> patch_contig;
-    if (cnt.n_escaped) {
-        PC_TRY(fetch_line_info(st, d_list, cnt.n_escaped, ln, text_len, d_data_index, info));
-        patch.resize(info.size()); patch_contig.resize(info.size());
-        for (size_t k = 0; k < info.size(); ++k) {
-            const tk::LineClass lc = tk::classify_line(text + info[k].b, text + info[k].e);
-            const int64_t gv = tk::governing(recs.data(), (int64_t)recs.size(), (int64_t)info[k].line);
-            const tk::LineOut o = tk::line_fields<tk::FastThenFull>(lc, gv >= 0 ? &recs[(size_t)gv] : nullptr, (int64_t)info[k].data_index);
-            int err = o.err;
-            if (err == tk::kTrkOk) err = tk::check_fields(o);
-            if (err != tk::kTrkOk) host_err = std::min(host_err, ((unsigned long long)info[k].line << 8) | (unsigned long long)err);
-            patch[k].start = o.start; patch[k].stop = o.stop; patch[k].value = o.value;
-            patch_contig[k] = err == tk::kTrkOk ? o.contig : -1;
-        }
-    }
-    const unsigned long long first_err = std::min(host_err, cnt.first_err);
-    if (first_err != tk::kNoDefect)
-        return fail(PC_ERR_ARG, "%s", tk::track_defect_message(d.path.c_str(), (int64_t)(first_err >> 8) + 1, (int)(first_err & 0xffu)).c_str());
-    if (cnt.n_escaped) {
-        // (d_list still holds the escaped lines, in the order fetch_line_info saw them: patch by line)
-        std::vector<uint32_t> lines(info.size());
-        for (size_t k = 0; k < info.size(); ++k) lines[k] = info[k].line;
-        PC_TRY(d_patch.upload(patch, st)); PC_TRY(d_patch_contig.upload(patch_contig, st)); PC_TRY(d_list.upload(lines, st));
-        hipLaunchKernelGGL(tk::k_track_patch, dim3(grid256((int64_t)lines.size())), dim3(256), 0, st, d_list.p, d_patch.p, d_patch_contig.p, (uint32_t)lines.size(),
-                           d_line.p, d_contig_of.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));   // (the host vectors above)
-    }
-    HIP_TRY(hipEventRecord(ev[4], st));
-
-    // phase 5: births, growth, storage
-    const int ncontig = (int)t->contigs.size();
-    if (ncontig >= (1 << 22)) return fail(PC_ERR_ARG, "%s: more than 2^22 contigs", d.path.c_str());
-    std::vector<unsigned long long> furthest((size_t)std::max(ncontig, 1), 0ull);
-    std::vector<uint32_t> first_line((size_t)std::max(ncontig, 1), tk::kNoLine);
-    if (ncontig > 0) {
-        std::vector<int64_t> len0((size_t)ncontig);
-        for (int c = 0; c < ncontig; ++c) len0[(size_t)c] = t->contigs[(size_t)c].born ? t->contigs[(size_t)c].length : t->min_chr_size;
-        room(rc, d_key, (size_t)n); room(rc, d_idx, (size_t)n); room(rc, d_key2, (size_t)n); room(rc, d_idx2, (size_t)n);
-        if (rc != PC_OK) return rc;
-        PC_TRY(d_len0.upload(len0, st)); PC_TRY(d_furthest.upload(furthest, st)); PC_TRY(d_first_line.upload(first_line, st));
-        hipLaunchKernelGGL(tk::k_track_keys, dim3(g), dim3(256), 0, st, d_line.p, d_contig_of.p, d_cls.p, n, d_len0.p, ncontig, d_furthest.p, d_first_line.p,
-                           d_list.p, d_key.p, d_idx.p, d_cnt.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(furthest.data(), d_furthest.p, (size_t)ncontig * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(first_line.data(), d_first_line.p, (size_t)ncontig * 4, hipMemcpyDeviceToHost, st));
-        PC_TRY(read_counters(st, d_cnt, cnt));
-        // births, in order of the first yielded line
-        std::vector<std::pair<uint32_t, int32_t>> born;
-        for (int c = 0; c < ncontig; ++c)
-            if (!t->contigs[(size_t)c].born && first_line[(size_t)c] != tk::kNoLine) born.emplace_back(first_line[(size_t)c], c);
-        std::sort(born.begin(), born.end());
-        for (auto &b : born) track_bear(t, b.second);
-        // growth: the reference's rule (genome_array.py:1593-1602), folded in file order over the lines that can matter
-        t->stats[5] = cnt.n_growth;
-        if (cnt.n_growth) {
-            std::vector<TrackGrowth> gr(cnt.n_growth);
-            PC_TRY(d_growth.reserve(cnt.n_growth));
-            hipLaunchKernelGGL(k_track_growth_info, dim3(grid256(cnt.n_growth)), dim3(256), 0, st, d_list.p, cnt.n_growth, d_line.p, d_contig_of.p, d_growth.p);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(gr.data(), d_growth.p, gr.size() * sizeof(TrackGrowth), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            std::sort(gr.begin(), gr.end(), [](const TrackGrowth &a, const TrackGrowth &b) { return a.line < b.line; });
-            for (const TrackGrowth &x : gr) {
-                int64_t &len = t->contigs[(size_t)x.contig].length;
-                len = tk::grown_length(len, x.stop);
-            }
-        }
-        PC_TRY(track_grow_storage(t, strand, furthest, st));
-    }
-
-    // phase 6: sort by (contig, start), clusters, fills
-    const int64_t nv = ncontig > 0 ? (int64_t)cnt.n_valid : 0;
-    if (nv > 0) {
-        std::vector<int64_t> off((size_t)ncontig);
-        for (int c = 0; c < ncontig; ++c) off[(size_t)c] = t->cell_off[(size_t)c * (size_t)t->nstrands + (size_t)strand];
-        PC_TRY(d_off.upload(off, st));
-        room(rc, d_end_key, (size_t)nv); room(rc, d_prev_end, (size_t)nv); room(rc, d_head, (size_t)nv); room(rc, d_long, (size_t)nv);
-        room(rc, d_multi, (size_t)nv); room(rc, d_multi2, (size_t)nv);
-        if (rc != PC_OK) return rc;
-        size_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, b0, d_key.p, d_key2.p, d_idx.p, d_idx2.p, (int)n, 0, 64, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, b1, d_end_key.p, d_prev_end.p, hipcub::Max(), (uint64_t)0, (int)nv, st));
-        HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, b2, d_head.p, d_head.p, hipcub::Max(), (int)nv, st));
-        HIP_TRY(hipcub::DeviceRadixSort::SortKeys(nullptr, b3, d_multi.p, d_multi2.p, (int)nv, 0, 64, st));
-        PC_TRY(d_tmp.reserve(std::max<size_t>(std::max(std::max(b0, b1), std::max(b2, b3)), 16)));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, b0, d_key.p, d_key2.p, d_idx.p, d_idx2.p, (int)n, 0, 64, st));
-        const unsigned gv = grid256(nv);
-        hipLaunchKernelGGL(tk::k_track_end_keys, dim3(gv), dim3(256), 0, st, d_key2.p, d_idx2.p, d_line.p, nv, d_end_key.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(d_tmp.p, b1, d_end_key.p, d_prev_end.p, hipcub::Max(), (uint64_t)0, (int)nv, st));
-        hipLaunchKernelGGL(tk::k_track_clusters, dim3(gv), dim3(256), 0, st, d_key2.p, d_prev_end.p, nv, d_head.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipcub::DeviceScan::InclusiveScan(d_tmp.p, b2, d_head.p, d_head.p, hipcub::Max(), (int)nv, st));
-        hipLaunchKernelGGL(tk::k_track_fill_short, dim3(gv), dim3(256), 0, st, d_idx2.p, d_head.p, nv, d_line.p, d_contig_of.p, d_off.p, t->cells.p, d_long.p,
-                           d_multi.p, d_cnt.p);
-        HIP_TRY(hipGetLastError());
-        PC_TRY(read_counters(st, d_cnt, cnt));
-        t->stats[4] = cnt.n_multi;
-        if (cnt.n_long) {
-            hipLaunchKernelGGL(tk::k_track_fill, dim3(cnt.n_long), dim3(256), 0, st, d_long.p, d_line.p, d_contig_of.p, d_off.p, t->cells.p);
-            HIP_TRY(hipGetLastError());
-        }
-        if (cnt.n_multi) {
-            HIP_TRY(hipcub::DeviceRadixSort::SortKeys(d_tmp.p, b3, d_multi.p, d_multi2.p, (int)cnt.n_multi, 0, 64, st));
-            hipLaunchKernelGGL(tk::k_track_fill_ordered, dim3(cnt.n_multi), dim3(256), 0, st, d_multi2.p, cnt.n_multi, d_line.p, d_contig_of.p, d_off.p, t->cells.p);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    t->sum_valid = false;
-    HIP_TRY(hipEventRecord(ev[5], st));
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(c.info.data(), d_info.p, (size_t)count * sizeof(TrackLineInfo), hipMemcpyDeviceToHost, c.st));
+    HIP_TRY(hipStreamSynchronize(c.st));
     drained.armed = false;
-    for (int k = 0; k < 5; ++k) t->ms[k] = ms_between(ev[k], ev[k + 1]);
+    std::sort(c.info.begin(), c.info.end(), [](const TrackLineInfo &a, const TrackLineInfo &b) { return a.line < b.line; });
+    return PC_OK;
+}
+
+// Phases 1, 2: the text to HBM, the line starts (sam_decoder.hip.h).
+int import_upload_and_lines(TrackImport &c) {
+    {
+        Upload u;
+        Drain drain{c.d.e, true};
+        PC_TRY(c.d.d_stream.reserve((size_t)c.size + 64));
+        HIP_TRY(hipEventRecord(c.ev[0], c.st));
+        PC_TRY(sam_upload(c.d, c.text, c.size, nullptr, u));
+        HIP_TRY(hipEventRecord(c.ev[1], c.st));
+        PC_TRY(sam_line_starts(c.d, c.size, c.text[c.size - 1] != (uint8_t)'\n', c.ln));
+        drain.armed = false;
+    }
+    HIP_TRY(hipEventRecord(c.ev[2], c.st));
+    c.n = c.ln.nrec;
+    c.g = grid256(c.n);
+    c.t->stats[0] = c.n;
+    return PC_OK;
+}
+
+// Phase 3: classes, the state lines (parsed here: they name the contigs), the data-line prefix count.
+int import_classify_and_states(TrackImport &c) {
+    hipStream_t st = c.st;
+    const int64_t n = c.n;
+    int rc = PC_OK;
+    room(rc, c.d_cls, (size_t)n); room(rc, c.d_sig, (size_t)n); room(rc, c.d_prev_sig, (size_t)n); room(rc, c.d_is_data, (size_t)n);
+    room(rc, c.d_data_index, (size_t)n); room(rc, c.d_list, (size_t)n); room(rc, c.d_cnt, 1);
+    if (rc != PC_OK) return rc;
+    memset(&c.cnt, 0, sizeof(c.cnt));
+    c.cnt.first_err = tk::kNoDefect;
+    HIP_TRY(hipMemcpyAsync(c.d_cnt.p, &c.cnt, sizeof(c.cnt), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(tk::k_track_classify, dim3(c.g), dim3(256), 0, st, c.d.d_stream.p, c.text_len(), c.ln.d_line_start.p, n, c.d_cls.p, c.d_sig.p, c.d_is_data.p);
+    HIP_TRY(hipGetLastError());
+    const auto last_sig = [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveScan(tmp, b, c.d_sig.p, c.d_prev_sig.p, hipcub::Max(), (int32_t)-1, (int)n, st); };
+    const auto data_index = [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, c.d_is_data.p, c.d_data_index.p, (int)n, st); };
+    size_t need = 16, b_sig = 0, b_data = 0;
+    PC_TRY(cub_need(need, b_sig, last_sig)); PC_TRY(cub_need(need, b_data, data_index));
+    PC_TRY(c.d_tmp.reserve(need));
+    PC_TRY(cub_run_sized(c.d_tmp, b_sig, last_sig)); PC_TRY(cub_run_sized(c.d_tmp, b_data, data_index));
+    hipLaunchKernelGGL(tk::k_track_states, dim3(c.g), dim3(256), 0, st, c.d.d_stream.p, c.text_len(), c.ln.d_line_start.p, n, c.d_cls.p, c.d_prev_sig.p, c.d_list.p,
+                       &c.d_cnt.p->n_state);
+    HIP_TRY(hipGetLastError());
+    PC_TRY(c.read_counters());
+    PC_TRY(fetch_line_info(c, c.cnt.n_state));
+    c.recs.resize(c.info.size());
+    pc_track *t = c.t;
+    for (size_t k = 0; k < c.info.size(); ++k) {
+        const TrackLineInfo &i = c.info[k];
+        c.note_defect(i.line, tk::parse_state(c.text + i.b, c.text + i.e, (int64_t)i.line, (int64_t)i.data_index,
+                                              [t](const std::string &nm) { return t->tab.id_of(nm); }, c.recs[k]));
+    }
+    t->stats[3] = (int64_t)c.recs.size();
+    HIP_TRY(hipEventRecord(c.ev[3], st));
+    return PC_OK;
+}
+
+// the escaped lines (c.info), converted by the host: c.patch, c.patch_contig
+void convert_escaped(TrackImport &c) {
+    c.patch.resize(c.info.size()); c.patch_contig.resize(c.info.size());
+    for (size_t k = 0; k < c.info.size(); ++k) {
+        const TrackLineInfo &i = c.info[k];
+        const tk::LineClass lc = tk::classify_line(c.text + i.b, c.text + i.e);
+        const int64_t gv = tk::governing(c.recs.data(), (int64_t)c.recs.size(), (int64_t)i.line);
+        const tk::LineOut o = tk::line_fields<tk::FastThenFull>(lc, gv >= 0 ? &c.recs[(size_t)gv] : nullptr, (int64_t)i.data_index);
+        const int err = o.err == tk::kTrkOk ? tk::check_fields(o) : o.err;
+        c.note_defect(i.line, err);
+        c.patch[k].start = o.start; c.patch[k].stop = o.stop; c.patch[k].value = o.value;
+        c.patch_contig[k] = err == tk::kTrkOk ? o.contig : -1;
+    }
+}
+
+// Phase 4: the fields of every yielding line; the escaped ones on the host; the lowest defect of the text ends the import.
+int import_fields(TrackImport &c) {
+    hipStream_t st = c.st;
+    pc_track *t = c.t;
+    int rc = PC_OK;
+    room(rc, c.d_recs, std::max<size_t>(c.recs.size(), 1)); room(rc, c.d_line, (size_t)c.n); room(rc, c.d_contig_of, (size_t)c.n);
+    if (rc != PC_OK) return rc;
+    if (!c.recs.empty()) HIP_TRY(hipMemcpyAsync(c.d_recs.p, c.recs.data(), c.recs.size() * sizeof(tk::StateRec), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(tk::k_track_fields, dim3(c.g), dim3(256), 0, st, c.d.d_stream.p, c.text_len(), c.ln.d_line_start.p, c.n, c.d_cls.p, c.d_data_index.p, c.d_recs.p,
+                       (int64_t)c.recs.size(), c.d_line.p, c.d_contig_of.p, c.d_list.p, c.d_cnt.p);
+    HIP_TRY(hipGetLastError());
+    PC_TRY(c.read_counters());
+    t->stats[1] = c.cnt.n_yield; t->stats[2] = c.cnt.n_escaped;
+    if (c.cnt.n_escaped) {
+        PC_TRY(fetch_line_info(c, c.cnt.n_escaped));
+        convert_escaped(c);
+    }
+    const unsigned long long first_err = std::min(c.host_err, c.cnt.first_err);
+    if (first_err != tk::kNoDefect)
+        return fail(PC_ERR_ARG, "%s", tk::track_defect_message(c.d.path.c_str(), (int64_t)(first_err >> 8) + 1, (int)(first_err & 0xffu)).c_str());
+    if (c.cnt.n_escaped) {
+        // (d_list still holds the escaped lines, in the order fetch_line_info saw them: patch by line)
+        c.lines.resize(c.info.size());
+        for (size_t k = 0; k < c.info.size(); ++k) c.lines[k] = c.info[k].line;
+        PC_TRY(c.d_patch.upload(c.patch, st)); PC_TRY(c.d_patch_contig.upload(c.patch_contig, st)); PC_TRY(c.d_list.upload(c.lines, st));
+        hipLaunchKernelGGL(tk::k_track_patch, dim3(grid256((int64_t)c.lines.size())), dim3(256), 0, st, c.d_list.p, c.d_patch.p, c.d_patch_contig.p,
+                           (uint32_t)c.lines.size(), c.d_line.p, c.d_contig_of.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    HIP_TRY(hipEventRecord(c.ev[4], st));
+    return PC_OK;
+}
+
+// Storage of the strand slots as the plan lays them out: a fresh block, zeroed, every slot's cells copied to their new place.
+int track_grow_storage(pc_track *t, const tk::StoragePlan &plan, hipStream_t st) {
+    if (!plan.grows) return PC_OK;
+    DevBuf<double> fresh;
+    fresh.pool = &t->e->pool;
+    PC_TRY(fresh.reserve((size_t)plan.total));
+    HIP_TRY(hipMemsetAsync(fresh.p, 0, (size_t)plan.total * sizeof(double), st));
+    for (size_t s = 0; s < t->tab.ext.size(); ++s)
+        if (t->tab.ext[s] > 0)
+            HIP_TRY(hipMemcpyAsync(fresh.p + plan.off[s], t->cells.p + t->tab.cell_off[s], (size_t)t->tab.ext[s] * sizeof(double), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the old block goes back to the pool)
+    t->cells.swap(fresh);
+    t->tab.commit(plan);
+    return PC_OK;
+}
+
+// Phase 5: per contig the first yielding line and the furthest end, the sort keys; births, growth, storage.
+int import_births_growth_storage(TrackImport &c) {
+    hipStream_t st = c.st;
+    pc_track *t = c.t;
+    c.ncontig = (int)t->tab.names.size();
+    if (c.ncontig >= (1 << 22)) return fail(PC_ERR_ARG, "%s: more than 2^22 contigs", c.d.path.c_str());
+    if (c.ncontig == 0) return PC_OK;
+    c.furthest.assign((size_t)c.ncontig, 0ull);
+    c.first_line.assign((size_t)c.ncontig, tk::kNoLine);
+    c.len0 = t->tab.lengths_before();
+    int rc = PC_OK;
+    room(rc, c.d_key, (size_t)c.n); room(rc, c.d_idx, (size_t)c.n); room(rc, c.d_key2, (size_t)c.n); room(rc, c.d_idx2, (size_t)c.n);
+    if (rc != PC_OK) return rc;
+    PC_TRY(c.d_len0.upload(c.len0, st)); PC_TRY(c.d_furthest.upload(c.furthest, st)); PC_TRY(c.d_first_line.upload(c.first_line, st));
+    hipLaunchKernelGGL(tk::k_track_keys, dim3(c.g), dim3(256), 0, st, c.d_line.p, c.d_contig_of.p, c.d_cls.p, c.n, c.d_len0.p, c.ncontig, c.d_furthest.p, c.d_first_line.p,
+                       c.d_list.p, c.d_key.p, c.d_idx.p, c.d_cnt.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c.furthest.data(), c.d_furthest.p, (size_t)c.ncontig * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(c.first_line.data(), c.d_first_line.p, (size_t)c.ncontig * 4, hipMemcpyDeviceToHost, st));
+    PC_TRY(c.read_counters());
+    for (int32_t id : t->tab.births(c.first_line)) t->tab.bear(id);
+    t->stats[5] = c.cnt.n_growth;
+    if (c.cnt.n_growth) {
+        std::vector<tk::GrowthLine> gr(c.cnt.n_growth);
+        PC_TRY(c.d_growth.reserve(c.cnt.n_growth));
+        hipLaunchKernelGGL(k_track_growth_info, dim3(grid256(c.cnt.n_growth)), dim3(256), 0, st, c.d_list.p, c.cnt.n_growth, c.d_line.p, c.d_contig_of.p, c.d_growth.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(gr.data(), c.d_growth.p, gr.size() * sizeof(tk::GrowthLine), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        t->tab.fold_growth(gr);
+    }
+    return track_grow_storage(t, t->tab.plan_storage(c.strand, c.furthest), st);
+}
+
+// Phase 6: sort by (contig, start), clusters, fills.
+int import_sort_and_apply(TrackImport &c) {
+    hipStream_t st = c.st;
+    pc_track *t = c.t;
+    const int64_t n = c.n, nv = c.ncontig > 0 ? (int64_t)c.cnt.n_valid : 0;
+    if (nv == 0) return PC_OK;
+    c.off = t->tab.strand_offsets(c.strand);
+    PC_TRY(c.d_off.upload(c.off, st));
+    int rc = PC_OK;
+    room(rc, c.d_end_key, (size_t)nv); room(rc, c.d_prev_end, (size_t)nv); room(rc, c.d_head, (size_t)nv); room(rc, c.d_long, (size_t)nv);
+    room(rc, c.d_multi, (size_t)nv); room(rc, c.d_multi2, (size_t)nv);
+    if (rc != PC_OK) return rc;
+    int64_t nm = nv;   // (the ordered pass sorts the lines of the larger clusters: at most nv, known behind k_track_fill_short)
+    const auto sort_lines = [&](void *tmp, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(tmp, b, c.d_key.p, c.d_key2.p, c.d_idx.p, c.d_idx2.p, (int)n, 0, 64, st); };
+    const auto prev_end = [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveScan(tmp, b, c.d_end_key.p, c.d_prev_end.p, hipcub::Max(), (uint64_t)0, (int)nv, st); };
+    const auto heads = [&](void *tmp, size_t &b) { return hipcub::DeviceScan::InclusiveScan(tmp, b, c.d_head.p, c.d_head.p, hipcub::Max(), (int)nv, st); };
+    const auto sort_multi = [&](void *tmp, size_t &b) { return hipcub::DeviceRadixSort::SortKeys(tmp, b, c.d_multi.p, c.d_multi2.p, (int)nm, 0, 64, st); };
+    size_t need = 16, b_sort = 0, b_prev = 0, b_heads = 0, b_multi = 0;
+    PC_TRY(cub_need(need, b_sort, sort_lines)); PC_TRY(cub_need(need, b_prev, prev_end)); PC_TRY(cub_need(need, b_heads, heads));
+    PC_TRY(cub_need(need, b_multi, sort_multi));
+    PC_TRY(c.d_tmp.reserve(need));
+    PC_TRY(cub_run_sized(c.d_tmp, b_sort, sort_lines));
+    const unsigned gv = grid256(nv);
+    hipLaunchKernelGGL(tk::k_track_end_keys, dim3(gv), dim3(256), 0, st, c.d_key2.p, c.d_idx2.p, c.d_line.p, nv, c.d_end_key.p);
+    HIP_TRY(hipGetLastError());
+    PC_TRY(cub_run_sized(c.d_tmp, b_prev, prev_end));
+    hipLaunchKernelGGL(tk::k_track_clusters, dim3(gv), dim3(256), 0, st, c.d_key2.p, c.d_prev_end.p, nv, c.d_head.p);
+    HIP_TRY(hipGetLastError());
+    PC_TRY(cub_run_sized(c.d_tmp, b_heads, heads));
+    hipLaunchKernelGGL(tk::k_track_fill_short, dim3(gv), dim3(256), 0, st, c.d_idx2.p, c.d_head.p, nv, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p, c.d_long.p,
+                       c.d_multi.p, c.d_cnt.p);
+    HIP_TRY(hipGetLastError());
+    PC_TRY(c.read_counters());
+    t->stats[4] = c.cnt.n_multi;
+    if (c.cnt.n_long) {
+        hipLaunchKernelGGL(tk::k_track_fill, dim3(c.cnt.n_long), dim3(256), 0, st, c.d_long.p, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p);
+        HIP_TRY(hipGetLastError());
+    }
+    if (c.cnt.n_multi) {
+        nm = c.cnt.n_multi;
+        PC_TRY(cub_run_sized(c.d_tmp, b_multi, sort_multi));
+        hipLaunchKernelGGL(tk::k_track_fill_ordered, dim3(c.cnt.n_multi), dim3(256), 0, st, c.d_multi2.p, c.cnt.n_multi, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p);
+        HIP_TRY(hipGetLastError());
+    }
+    return PC_OK;
+}
+
+int track_add_impl(pc_track *t, const void *image, int64_t size, const char *name, int strand) {
+    if (!t || size < 0 || (size > 0 && !image)) return fail(PC_ERR_ARG, "pc_track_add_text: bad arguments");
+    if (strand < 0 || strand >= t->tab.nstrands) return fail(PC_ERR_ARG, "pc_track_add_text: strand slot %d of %d", strand, t->tab.nstrands);
+    HIP_TRY(hipSetDevice(t->e->device));
+    PoolScope pool_scope(&t->e->pool);
+    TrackImport c(t, (const uint8_t *)image, size, name, strand);
+    for (auto &x : t->stats) x = 0;
+    for (auto &x : t->ms) x = 0.0;
+    if (size == 0) return PC_OK;
+    PC_TRY(c.ev.create());
+    PC_TRY(import_upload_and_lines(c));
+    if (c.n == 0) return PC_OK;
+    DrainOnExit drained{c.st};
+    PC_TRY(import_classify_and_states(c));
+    PC_TRY(import_fields(c));
+    PC_TRY(import_births_growth_storage(c));
+    PC_TRY(import_sort_and_apply(c));
+    t->sum_valid = false;
+    HIP_TRY(hipEventRecord(c.ev[5], c.st));
+    HIP_TRY(hipStreamSynchronize(c.st));
+    drained.armed = false;
+    c.ev.laps(t->ms, 5);
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------- export
+
+// What the phases of one export share.
+struct TrackExport {
+    pc_track *t;
+    int kind, strand;
+    hipStream_t st;
+    LapEvents<6> ev;                   // start | slot sums | run table | listed values | lengths + offsets | formatted
+    tk::ExportSlots slots;             // the strand's contigs in the order of the text
+    std::vector<tk::SlotStat> stat;
+    tk::ExportRanges xr;
+    int K = 0;                         // written contigs
+    int64_t R = 0, nlines = 0, total = 0;   // runs, lines, bytes
+    uint32_t n_listed = 0;
+    std::vector<uint8_t> strs, lens;
+    tk::ExportView view;
+    DevBuf<tk::SlotCells> d_slots;
+    DevBuf<tk::SlotStat> d_stat;
+    DevBuf<double> d_partial, d_listed_val;
+    DevBuf<tk::ExRange> d_ranges;
+    DevBuf<uint32_t> d_flags, d_idx, d_run_e, d_listed_slot, d_n_listed;
+    DevBuf<uint8_t> d_tmp, d_names, d_strs, d_lens;
+    DevBuf<int64_t> d_len, d_off;
+};
+
+// Phase 1: per slot the fixed-tree sum, first and last non-zero; from them the contigs that are written.
+int export_slot_sums(TrackExport &c) {
+    hipStream_t st = c.st;
+    const int K0 = (int)c.slots.ids.size();
+    c.stat.assign((size_t)K0, tk::SlotStat{0.0, ~0ull, 0ull});
+    int64_t max_tiles = 1;
+    for (const tk::SlotCells &s : c.slots.cells) max_tiles = std::max(max_tiles, (s.n + tk::kSumTile - 1) / tk::kSumTile);
+    HIP_TRY(hipEventRecord(c.ev[0], st));
+    PC_TRY(c.d_slots.upload(c.slots.cells, st)); PC_TRY(c.d_stat.upload(c.stat, st));
+    PC_TRY(c.d_partial.reserve((size_t)K0 * (size_t)max_tiles));
+    hipLaunchKernelGGL(tk::k_export_slot_partial, dim3((unsigned)max_tiles, (unsigned)K0), dim3(256), 0, st, c.d_slots.p, c.t->cells.p, max_tiles, c.d_partial.p, c.d_stat.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tk::k_export_slot_final, dim3((unsigned)K0), dim3(256), 0, st, c.d_slots.p, c.d_partial.p, max_tiles, c.d_stat.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c.stat.data(), c.d_stat.p, c.stat.size() * sizeof(tk::SlotStat), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipEventRecord(c.ev[1], st));
+    c.xr = c.t->tab.export_ranges(c.kind, c.slots, c.stat);
+    c.K = c.xr.ranges.empty() ? 0 : (int)c.xr.ranges.size() - 1;
+    return PC_OK;
+}
+
+// Phase 2: run heads, count, exclusive sum, select into the run table.
+int export_run_table(TrackExport &c) {
+    hipStream_t st = c.st;
+    const int64_t E = c.xr.cells;
+    if (E >= (int64_t)0x7fffffff || c.xr.names.size() >= (size_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_export: more than 2^31 cells to export");
+    PC_TRY(c.d_ranges.upload(c.xr.ranges, st)); PC_TRY(c.d_names.upload(c.xr.names, st));
+    if (E > 0) {
+        int rc = PC_OK;
+        room(rc, c.d_flags, (size_t)E); room(rc, c.d_idx, (size_t)E);
+        if (rc != PC_OK) return rc;
+        hipLaunchKernelGGL(tk::k_export_flags, dim3((unsigned)((E + tk::kExportTile - 1) / tk::kExportTile)), dim3(256), 0, st, c.kind, c.d_ranges.p, c.K, E, c.t->cells.p,
+                           c.d_flags.p);
+        HIP_TRY(hipGetLastError());
+        PC_TRY(cub_run(c.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, c.d_flags.p, c.d_idx.p, (int)E, st); }));
+        hipLaunchKernelGGL(tk::k_export_bases, dim3(grid256(c.K + 1)), dim3(256), 0, st, c.d_flags.p, c.d_idx.p, E, c.d_ranges.p, c.K);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&c.R, &c.d_ranges.p[c.K].run_base, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c.R > 0) {
+            PC_TRY(c.d_run_e.reserve((size_t)c.R));
+            hipLaunchKernelGGL(tk::k_export_select, dim3(grid256(E)), dim3(256), 0, st, c.d_flags.p, c.d_idx.p, E, c.d_run_e.p);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipEventRecord(c.ev[2], st));
+    return PC_OK;
+}
+
+// Phase 3: the values that are not plain go to the host and come back as text.
+int export_listed_values(TrackExport &c) {
+    hipStream_t st = c.st;
+    const int64_t R = c.R;
+    int rc = PC_OK;
+    room(rc, c.d_listed_slot, (size_t)std::max<int64_t>(R, 1)); room(rc, c.d_listed_val, (size_t)std::max<int64_t>(R, 1)); room(rc, c.d_n_listed, 1);
+    if (rc != PC_OK) return rc;
+    if (R > 0) {
+        HIP_TRY(hipMemsetAsync(c.d_n_listed.p, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(tk::k_export_classify, dim3(grid256(R)), dim3(256), 0, st, c.d_ranges.p, c.K, c.d_run_e.p, R, c.t->cells.p, c.d_listed_slot.p, c.d_listed_val.p,
+                           c.d_n_listed.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&c.n_listed, c.d_n_listed.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    c.strs.assign((size_t)std::max<uint32_t>(c.n_listed, 1) * tk::kReprMax, 0); c.lens.assign((size_t)std::max<uint32_t>(c.n_listed, 1), 0);
+    if (c.n_listed) {
+        std::vector<double> vals(c.n_listed);
+        HIP_TRY(hipMemcpyAsync(vals.data(), c.d_listed_val.p, (size_t)c.n_listed * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < c.n_listed; ++k) c.lens[k] = (uint8_t)tk::float_repr(vals[k], (char *)c.strs.data() + (size_t)tk::kReprMax * k);
+    }
+    PC_TRY(c.d_strs.upload(c.strs, st)); PC_TRY(c.d_lens.upload(c.lens, st));
+    HIP_TRY(hipEventRecord(c.ev[3], st));
+    return PC_OK;
+}
+
+// Phase 4: a byte length per line and their exclusive sum: every line's offset, the size of the text.
+int export_lengths_and_offsets(TrackExport &c) {
+    hipStream_t st = c.st;
+    const int64_t nlines = c.nlines = c.R + c.K;
+    if (nlines >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_export: more than 2^31 lines");
+    tk::ExportView &v = c.view;
+    v.kind = c.kind; v.ranges = c.d_ranges.p; v.K = c.K; v.run_e = c.d_run_e.p; v.cells = c.t->cells.p; v.names = c.d_names.p;
+    v.listed_slot = c.d_listed_slot.p; v.strs = c.d_strs.p; v.lens = c.d_lens.p;
+    int rc = PC_OK;
+    room(rc, c.d_len, (size_t)nlines); room(rc, c.d_off, (size_t)nlines);
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(tk::k_export_lengths, dim3((unsigned)((nlines + tk::kFormatRuns - 1) / tk::kFormatRuns)), dim3(tk::kFormatRuns), 0, st, v, nlines, c.d_len.p);
+    HIP_TRY(hipGetLastError());
+    PC_TRY(cub_run(c.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, c.d_len.p, c.d_off.p, (int)nlines, st); }));
+    int64_t last_off = 0, last_len = 0;
+    HIP_TRY(hipMemcpyAsync(&last_off, c.d_off.p + (nlines - 1), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&last_len, c.d_len.p + (nlines - 1), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c.total = last_off + last_len;
+    HIP_TRY(hipEventRecord(c.ev[4], st));
+    return PC_OK;
+}
+
+// Phase 5: every line's bytes at its offset.
+int export_format(TrackExport &c) {
+    PC_TRY(c.t->ex_text.reserve((size_t)c.total));
+    hipLaunchKernelGGL(tk::k_export_format, dim3((unsigned)((c.nlines + tk::kFormatRuns - 1) / tk::kFormatRuns)), dim3(tk::kFormatRuns), 0, c.st, c.view, c.nlines,
+                       c.d_off.p, c.t->ex_text.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c.ev[5], c.st));
     return PC_OK;
 }
 
@@ -357,7 +493,7 @@ extern "C" {
 int pc_track_create(pc_engine *e, int nstrands, int64_t min_chr_size, pc_track **out) {
     if (!e || !out || nstrands < 1 || nstrands > 8 || min_chr_size < 0) return fail(PC_ERR_ARG, "pc_track_create: bad arguments");
     pc_track *t = new pc_track();
-    t->e = e; t->nstrands = nstrands; t->min_chr_size = min_chr_size;
+    t->e = e; t->tab.nstrands = nstrands; t->tab.min_chr_size = min_chr_size;
     t->cells.pool = &e->pool; t->ex_text.pool = &e->pool; t->nz.pool = &e->pool;
     e->tracks.push_back(t);
     *out = t;
@@ -376,11 +512,7 @@ int pc_track_destroy(pc_track *t) {
 
 int pc_track_declare(pc_track *t, const char *name, int64_t length) {
     if (!t || !name || length < 0) return fail(PC_ERR_ARG, "pc_track_declare: bad arguments");
-    if (t->ids.count(name)) return fail(PC_ERR_ARG, "pc_track_declare: %s is declared already", name);
-    const int32_t id = track_contig_id(t, name);
-    t->contigs[(size_t)id].born = true;
-    t->contigs[(size_t)id].length = length;
-    t->order.push_back(id);
+    if (!t->tab.declare(name, length)) return fail(PC_ERR_ARG, "pc_track_declare: %s is declared already", name);
     return PC_OK;
 }
 
@@ -396,21 +528,21 @@ int pc_track_add_path(pc_track *t, const char *path, int strand_slot) {
     return track_add_impl(t, mf.p, (int64_t)mf.size, path, strand_slot);
 }
 
-int pc_track_num_contigs(pc_track *t) { return t ? (int)t->order.size() : -1; }
+int pc_track_num_contigs(pc_track *t) { return t ? t->tab.num_public() : -1; }
 
 const char *pc_track_contig_name(pc_track *t, int i) {
-    if (!t || i < 0 || i >= (int)t->order.size()) return nullptr;
-    return t->contigs[(size_t)t->order[(size_t)i]].name.c_str();
+    const int32_t id = t ? t->tab.public_id(i) : -1;
+    return id < 0 ? nullptr : t->tab.names[(size_t)id].c_str();
 }
 
 int64_t pc_track_contig_length(pc_track *t, int i) {
-    if (!t || i < 0 || i >= (int)t->order.size()) return -1;
-    return t->contigs[(size_t)t->order[(size_t)i]].length;
+    const int32_t id = t ? t->tab.public_id(i) : -1;
+    return id < 0 ? -1 : t->tab.length[(size_t)id];
 }
 
 int64_t pc_track_contig_extent(pc_track *t, int i, int strand_slot) {
-    if (!t || i < 0 || i >= (int)t->order.size() || strand_slot < 0 || strand_slot >= t->nstrands) return -1;
-    return t->ext[(size_t)t->order[(size_t)i] * (size_t)t->nstrands + (size_t)strand_slot];
+    const int64_t at = t ? t->tab.public_slot(i, strand_slot) : -1;
+    return at < 0 ? -1 : t->tab.ext[(size_t)at];
 }
 
 int pc_track_gather(pc_track *t, int64_t nseg, const int32_t *contig, const int32_t *strand_slot, const int64_t *start, const int64_t *end,
@@ -424,26 +556,10 @@ int pc_track_gather(pc_track *t, int64_t nseg, const int32_t *contig, const int3
     hipStream_t st = e->stream;
     double sum = 1.0;
     if (normalize) PC_TRY(pc_track_sum(t, &sum));
-    // the items, cut on the host by the function the dense vector's item kernel runs (dense_host.h)
+    const std::string bad = tk::check_segments(tk::kGatherWords, nseg, start, end, out_off, out_step, out_elems, false);
+    if (!bad.empty()) return fail(PC_ERR_ARG, "%s", bad.c_str());
     std::vector<pcdense::Item> items;
-    for (int64_t s = 0; s < nseg; ++s) {
-        const int64_t len = end[s] - start[s];
-        if (len <= 0) continue;
-        if (out_step[s] != 1 && out_step[s] != -1) return fail(PC_ERR_ARG, "pc_track_gather: out_step of segment %lld is not +1 / -1", (long long)s);
-        const int64_t first = out_off[s], last = out_off[s] + (int64_t)out_step[s] * (len - 1);
-        if (first < 0 || first >= out_elems || last < 0 || last >= out_elems)
-            return fail(PC_ERR_ARG, "pc_track_gather: segment %lld writes outside the output", (long long)s);
-        pcdense::SegIn in;
-        in.out_off = out_off[s]; in.len = len; in.clip_lo = 0; in.clip_hi = len; in.start = start[s]; in.step = out_step[s];
-        in.known = contig[s] >= 0 && contig[s] < (int32_t)t->order.size() && strand_slot[s] >= 0 && strand_slot[s] < t->nstrands;
-        if (in.known) {
-            const size_t slot = (size_t)t->order[(size_t)contig[s]] * (size_t)t->nstrands + (size_t)strand_slot[s];
-            in.cell_base = t->cell_off[slot];
-            in.ext = t->ext[slot];
-        }
-        const int64_t k_end = pcdense::items_of(len);
-        for (int64_t k = 0; k < k_end; ++k) items.push_back(pcdense::cut_item(in, k));
-    }
+    t->tab.cut_items(nseg, start, end, out_off, out_step, [&](int64_t s) { return t->tab.public_slot(contig[s], strand_slot[s]); }, items);
     DevBuf<pcdense::Item> d_items;
     DevBuf<double> d_out;
     DrainOnExit drained{st};
@@ -465,16 +581,17 @@ int pc_track_sum(pc_track *t, double *sum) {
     if (!t || !sum) return fail(PC_ERR_ARG, "pc_track_sum: bad arguments");
     if (!t->sum_valid) {
         double s = 0.0;
-        if (t->ncells > 0) {
+        const int64_t ncells = t->tab.ncells;
+        if (ncells > 0) {
             pc_engine *e = t->e;
             HIP_TRY(hipSetDevice(e->device));
             PoolScope pool_scope(&e->pool);
             hipStream_t st = e->stream;
-            const int64_t nb = (t->ncells + pctrack::kSumTile - 1) / pctrack::kSumTile;
+            const int64_t nb = (ncells + pctrack::kSumTile - 1) / pctrack::kSumTile;
             DevBuf<double> d_partial;
             DrainOnExit drained{st};
             PC_TRY(d_partial.reserve((size_t)nb + 1));
-            hipLaunchKernelGGL(pctrack::k_track_sum_partial, dim3((unsigned)nb), dim3(256), 0, st, t->cells.p, t->ncells, d_partial.p);
+            hipLaunchKernelGGL(pctrack::k_track_sum_partial, dim3((unsigned)nb), dim3(256), 0, st, t->cells.p, ncells, d_partial.p);
             HIP_TRY(hipGetLastError());
             hipLaunchKernelGGL(pctrack::k_track_sum_final, dim3(1), dim3(256), 0, st, d_partial.p, nb, d_partial.p + nb);
             HIP_TRY(hipGetLastError());
@@ -507,44 +624,22 @@ int pc_track_set(pc_track *t, const char *contig, int strand_slot, int64_t nseg,
                  const int8_t *val_step, const double *values, int64_t nvalues, double scalar) {
     if (!t || !contig || nseg < 0 || (nseg > 0 && (!start || !end)) || nvalues < 0 || (values && nseg > 0 && (!val_off || !val_step)))
         return fail(PC_ERR_ARG, "pc_track_set: bad arguments");
-    if (strand_slot < 0 || strand_slot >= t->nstrands) return fail(PC_ERR_ARG, "pc_track_set: strand slot %d of %d", strand_slot, t->nstrands);
+    if (strand_slot < 0 || strand_slot >= t->tab.nstrands) return fail(PC_ERR_ARG, "pc_track_set: strand slot %d of %d", strand_slot, t->tab.nstrands);
     // everything is checked before anything changes
-    int64_t furthest = 0;
-    for (int64_t s = 0; s < nseg; ++s) {
-        const int64_t len = end[s] - start[s];
-        if (start[s] < 0 || len < 0 || end[s] > tk::kMaxCoord) return fail(PC_ERR_ARG, "pc_track_set: segment %lld lies outside [0, 2^40]", (long long)s);
-        if (values && len > 0) {
-            if (val_step[s] != 1 && val_step[s] != -1) return fail(PC_ERR_ARG, "pc_track_set: val_step of segment %lld is not +1 / -1", (long long)s);
-            const int64_t a = val_off[s], b = val_off[s] + (int64_t)val_step[s] * (len - 1);
-            if (a < 0 || a >= nvalues || b < 0 || b >= nvalues) return fail(PC_ERR_ARG, "pc_track_set: segment %lld reads outside the vector", (long long)s);
-        }
-        if (len > 0) furthest = std::max(furthest, end[s]);
-    }
+    const std::string bad = tk::check_segments(tk::kSetWords, nseg, start, end, values ? val_off : nullptr, val_step, nvalues, true);
+    if (!bad.empty()) return fail(PC_ERR_ARG, "%s", bad.c_str());
     pc_engine *e = t->e;
     HIP_TRY(hipSetDevice(e->device));
     PoolScope pool_scope(&e->pool);
     hipStream_t st = e->stream;
-    // birth and growth, segment by segment as the reference's loop meets them (genome_array.py:1593-1608)
-    const int32_t id = track_contig_id(t, contig);
-    track_bear(t, id);
-    for (int64_t s = 0; s < nseg; ++s) t->contigs[(size_t)id].length = tk::grown_length(t->contigs[(size_t)id].length, end[s]);
+    const int32_t id = t->tab.id_of(contig);
+    const int64_t furthest = t->tab.grow_for_set(id, start, end, nseg);
     t->sum_valid = false;
     if (furthest == 0) return PC_OK;
-    std::vector<unsigned long long> far((size_t)id + 1, 0ull);
-    far[(size_t)id] = (unsigned long long)furthest;
-    PC_TRY(track_grow_storage(t, strand_slot, far, st));
-    const size_t slot = (size_t)id * (size_t)t->nstrands + (size_t)strand_slot;
+    PC_TRY(track_grow_storage(t, t->tab.plan_storage(id, strand_slot, furthest), st));
+    const int64_t slot = (int64_t)t->tab.slot(id, strand_slot);
     std::vector<pcdense::Item> items;
-    for (int64_t s = 0; s < nseg; ++s) {
-        pcdense::SegIn in;
-        in.len = end[s] - start[s];
-        if (in.len <= 0) continue;
-        in.out_off = values ? val_off[s] : 0; in.step = values ? val_step[s] : 1;
-        in.clip_lo = 0; in.clip_hi = in.len; in.start = start[s]; in.known = true;
-        in.cell_base = t->cell_off[slot]; in.ext = t->ext[slot];
-        const int64_t k_end = pcdense::items_of(in.len);
-        for (int64_t k = 0; k < k_end; ++k) items.push_back(pcdense::cut_item(in, k));
-    }
+    t->tab.cut_items(nseg, start, end, values ? val_off : nullptr, val_step, [slot](int64_t) { return slot; }, items);
     if (items.size() >= (size_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_set: too many items");
     DevBuf<pcdense::Item> d_items;
     DevBuf<double> d_values;
@@ -560,22 +655,6 @@ int pc_track_set(pc_track *t, const char *contig, int strand_slot, int64_t nseg,
 
 // ---------------------------------------------------------------- arithmetic, equality
 
-namespace {
-// cells of public contig i (-1: none) on strand slot s (-1: none) of t: first cell and count, -1 / 0 where t has none
-void slot_cells(const pc_track *t, int i, int s, int64_t &c0, int64_t &n) {
-    c0 = -1; n = 0;
-    if (!t || i < 0 || i >= (int)t->order.size() || s < 0 || s >= t->nstrands) return;
-    const size_t slot = (size_t)t->order[(size_t)i] * (size_t)t->nstrands + (size_t)s;
-    c0 = t->cell_off[slot]; n = t->ext[slot];
-}
-int public_index(const pc_track *t, const std::string &name) {
-    auto it = t->ids.find(name);
-    if (it == t->ids.end() || !t->contigs[(size_t)it->second].born) return -1;
-    for (size_t i = 0; i < t->order.size(); ++i) if (t->order[i] == it->second) return (int)i;
-    return -1;
-}
-} // namespace
-
 int pc_track_combine(pc_track *a, pc_track *b, double scalar, int op, int mode_all, int64_t length_pad, int nstrands_out, const int32_t *slot_a,
                      const int32_t *slot_b, pc_track **out) {
     if (!a || !out || length_pad < 0 || nstrands_out < 1 || nstrands_out > 8 || !slot_a || (b && !slot_b) || op < tk::kOpAdd || op > tk::kOpMul)
@@ -585,44 +664,11 @@ int pc_track_combine(pc_track *a, pc_track *b, double scalar, int op, int mode_a
     HIP_TRY(hipSetDevice(e->device));
     PoolScope pool_scope(&e->pool);
     hipStream_t st = e->stream;
-    // the contigs of the result: a's in a's order, then (mode all) b's remaining ones; truncate: the common ones
-    struct Pick { std::string name; int ia, ib; int64_t length; };
-    std::vector<Pick> picks;
-    for (size_t i = 0; i < a->order.size(); ++i) {
-        const pc_track::Contig &c = a->contigs[(size_t)a->order[i]];
-        const int ib = b ? public_index(b, c.name) : -1;
-        if (b && ib < 0 && !mode_all) continue;
-        int64_t len = c.length;
-        if (ib >= 0) { const int64_t lb = b->contigs[(size_t)b->order[(size_t)ib]].length; len = mode_all ? std::max(len, lb) : std::min(len, lb); }
-        picks.push_back({c.name, (int)i, ib, len});
-    }
-    if (b && mode_all)
-        for (size_t i = 0; i < b->order.size(); ++i) {
-            const pc_track::Contig &c = b->contigs[(size_t)b->order[i]];
-            if (public_index(a, c.name) < 0) picks.push_back({c.name, -1, (int)i, c.length});
-        }
     pc_track *r = nullptr;
-    PC_TRY(pc_track_create(e, nstrands_out, a->min_chr_size, &r));
+    PC_TRY(pc_track_create(e, nstrands_out, a->tab.min_chr_size, &r));
     struct Undo { pc_track *r; ~Undo() { if (r) (void)pc_track_destroy(r); } } undo{r};
     std::vector<tk::OpSlot> slots;
-    int64_t total = 0;
-    for (const Pick &p : picks) {
-        PC_TRY(pc_track_declare(r, p.name.c_str(), p.length + length_pad));
-        const int32_t id = r->ids[p.name];
-        for (int s = 0; s < nstrands_out; ++s) {
-            tk::OpSlot o;
-            slot_cells(a, p.ia, slot_a[s], o.a0, o.an);
-            slot_cells(b, p.ib, b ? slot_b[s] : -1, o.b0, o.bn);
-            // a scalar acts on every cell up to the length; arrays: up to the furthest cell either side stores
-            o.n = b ? std::min(std::max(o.an, o.bn), p.length) : p.length;
-            o.out0 = total;
-            r->ext[(size_t)id * (size_t)nstrands_out + (size_t)s] = o.n;
-            r->cell_off[(size_t)id * (size_t)nstrands_out + (size_t)s] = total;
-            total += o.n;
-            slots.push_back(o);
-        }
-    }
-    r->ncells = total;
+    const int64_t total = tk::ContigTable::combine_layout(a->tab, b ? &b->tab : nullptr, mode_all != 0, length_pad, slot_a, slot_b, r->tab, slots);
     if (total > 0) {
         DevBuf<tk::OpSlot> d_slots;
         DrainOnExit drained{st};
@@ -649,15 +695,7 @@ int pc_track_equal(pc_track *a, pc_track *b, int64_t npair, const int32_t *conti
     PoolScope pool_scope(&e->pool);
     hipStream_t st = e->stream;
     std::vector<tk::OpSlot> slots;
-    int64_t total = 0;
-    for (int64_t k = 0; k < npair; ++k) {
-        tk::OpSlot o;
-        slot_cells(a, contig_a[k], slot_a[k], o.a0, o.an);
-        slot_cells(b, contig_b[k], slot_b[k], o.b0, o.bn);
-        o.n = std::max(o.an, o.bn); o.out0 = total;
-        total += o.n;
-        slots.push_back(o);
-    }
+    const int64_t total = tk::ContigTable::equal_layout(a->tab, b->tab, npair, contig_a, slot_a, contig_b, slot_b, slots);
     *equal = 1;
     if (total == 0) return PC_OK;
     DevBuf<tk::OpSlot> d_slots;
@@ -684,163 +722,32 @@ int pc_track_equal(pc_track *a, pc_track *b, int64_t npair, const int32_t *conti
 // exclusive sum; the format kernel.  *bytes: the size of the text, which waits for pc_track_export_read.
 int pc_track_export(pc_track *t, int kind, int strand_slot, int64_t *bytes) {
     if (!t || !bytes || (kind != 0 && kind != 1)) return fail(PC_ERR_ARG, "pc_track_export: bad arguments");
-    if (strand_slot < 0 || strand_slot >= t->nstrands) return fail(PC_ERR_ARG, "pc_track_export: strand slot %d of %d", strand_slot, t->nstrands);
+    if (strand_slot < 0 || strand_slot >= t->tab.nstrands) return fail(PC_ERR_ARG, "pc_track_export: strand slot %d of %d", strand_slot, t->tab.nstrands);
     pc_engine *e = t->e;
     HIP_TRY(hipSetDevice(e->device));
     PoolScope pool_scope(&e->pool);
-    hipStream_t st = e->stream;
     for (auto &x : t->ex_stats) x = 0;
     for (auto &x : t->ex_ms) x = 0.0;
     t->ex_bytes = 0;
     *bytes = 0;
-    // the contigs in sorted() order of their names (code points: the bytes of UTF-8 sort alike)
-    std::vector<int32_t> ids(t->order.begin(), t->order.end());
-    std::sort(ids.begin(), ids.end(), [t](int32_t a, int32_t b) { return t->contigs[(size_t)a].name < t->contigs[(size_t)b].name; });
-    const int K0 = (int)ids.size();
-    if (K0 == 0) return PC_OK;
-    if (K0 > 65535) return fail(PC_ERR_ARG, "pc_track_export: more than 65535 contigs");
-    hipEvent_t ev[6] = {};
-    for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t *ev; ~EvGuard() { for (int i = 0; i < 6; ++i) (void)hipEventDestroy(ev[i]); } } evg{ev};
-    DevBuf<tk::SlotCells> d_slots;
-    DevBuf<tk::SlotStat> d_stat;
-    DevBuf<double> d_partial, d_listed_val;
-    DevBuf<tk::ExRange> d_ranges;
-    DevBuf<uint32_t> d_flags, d_idx, d_run_e, d_listed_slot, d_n_listed;
-    DevBuf<uint8_t> d_tmp, d_names, d_strs, d_lens;
-    DevBuf<int64_t> d_len, d_off;
-    DrainOnExit drained{st};
-
-    // phase 1: per slot the fixed-tree sum, first and last non-zero
-    std::vector<tk::SlotCells> slots((size_t)K0);
-    std::vector<tk::SlotStat> stat((size_t)K0);
-    int64_t max_tiles = 1;
-    for (int k = 0; k < K0; ++k) {
-        const size_t slot = (size_t)ids[(size_t)k] * (size_t)t->nstrands + (size_t)strand_slot;
-        slots[(size_t)k].cell0 = t->cell_off[slot]; slots[(size_t)k].n = t->ext[slot];
-        stat[(size_t)k].sum = 0.0; stat[(size_t)k].first = ~0ull; stat[(size_t)k].last1 = 0ull;
-        max_tiles = std::max(max_tiles, (t->ext[slot] + tk::kSumTile - 1) / tk::kSumTile);
-    }
-    HIP_TRY(hipEventRecord(ev[0], st));
-    PC_TRY(d_slots.upload(slots, st)); PC_TRY(d_stat.upload(stat, st));
-    PC_TRY(d_partial.reserve((size_t)K0 * (size_t)max_tiles));
-    hipLaunchKernelGGL(tk::k_export_slot_partial, dim3((unsigned)max_tiles, (unsigned)K0), dim3(256), 0, st, d_slots.p, t->cells.p, max_tiles, d_partial.p, d_stat.p);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tk::k_export_slot_final, dim3((unsigned)K0), dim3(256), 0, st, d_slots.p, d_partial.p, max_tiles, d_stat.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(stat.data(), d_stat.p, stat.size() * sizeof(tk::SlotStat), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    HIP_TRY(hipEventRecord(ev[1], st));
-
-    // the contigs that are written and their export cells
-    std::vector<tk::ExRange> ranges;
-    std::vector<uint8_t> names;
-    int64_t E = 0;
-    for (int k = 0; k < K0; ++k) {
-        const tk::SlotStat &s = stat[(size_t)k];
-        const bool nonzero = s.first != ~0ull;
-        if (kind == 0 && !(s.sum > 0.0 && nonzero)) continue;
-        const std::string &nm = t->contigs[(size_t)ids[(size_t)k]].name;
-        tk::ExRange r;
-        r.e0 = E; r.run_base = 0;
-        r.pos0 = kind == 0 ? (int64_t)s.first : 0;
-        r.n = kind == 0 ? (int64_t)(s.last1 - s.first) : slots[(size_t)k].n;
-        r.cell0 = slots[(size_t)k].cell0 + r.pos0;
-        r.name_off = (int32_t)names.size(); r.name_len = (int32_t)nm.size();
-        names.insert(names.end(), nm.begin(), nm.end());
-        E += r.n;
-        ranges.push_back(r);
-    }
-    const int K = (int)ranges.size();
-    if (K == 0) { drained.armed = false; return PC_OK; }
-    if (E >= (int64_t)0x7fffffff || names.size() >= (size_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_export: more than 2^31 cells to export");
-    { tk::ExRange end; end.e0 = E; end.n = 0; end.cell0 = 0; end.pos0 = 0; end.run_base = 0; end.name_off = 0; end.name_len = 0; ranges.push_back(end); }
-    PC_TRY(d_ranges.upload(ranges, st)); PC_TRY(d_names.upload(names, st));
-
-    // phase 2: run heads, count, exclusive sum, select
-    int64_t R = 0;
-    if (E > 0) {
-        int rc = PC_OK;
-        room(rc, d_flags, (size_t)E); room(rc, d_idx, (size_t)E);
-        if (rc != PC_OK) return rc;
-        hipLaunchKernelGGL(tk::k_export_flags, dim3((unsigned)((E + tk::kExportTile - 1) / tk::kExportTile)), dim3(256), 0, st, kind, d_ranges.p, K, E, t->cells.p, d_flags.p);
-        HIP_TRY(hipGetLastError());
-        size_t b0 = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b0, d_flags.p, d_idx.p, (int)E, st));
-        PC_TRY(d_tmp.reserve(std::max<size_t>(b0, 16)));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b0, d_flags.p, d_idx.p, (int)E, st));
-        hipLaunchKernelGGL(tk::k_export_bases, dim3(grid256(K + 1)), dim3(256), 0, st, d_flags.p, d_idx.p, E, d_ranges.p, K);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&R, &d_ranges.p[K].run_base, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (R > 0) {
-            PC_TRY(d_run_e.reserve((size_t)R));
-            hipLaunchKernelGGL(tk::k_export_select, dim3(grid256(E)), dim3(256), 0, st, d_flags.p, d_idx.p, E, d_run_e.p);
-            HIP_TRY(hipGetLastError());
-        }
-    }
-    HIP_TRY(hipEventRecord(ev[2], st));
-
-    // phase 3: the values that are not plain go to the host and come back as text
-    uint32_t n_listed = 0;
-    {
-        int rc = PC_OK;
-        room(rc, d_listed_slot, (size_t)std::max<int64_t>(R, 1)); room(rc, d_listed_val, (size_t)std::max<int64_t>(R, 1)); room(rc, d_n_listed, 1);
-        if (rc != PC_OK) return rc;
-    }
-    if (R > 0) {
-        HIP_TRY(hipMemsetAsync(d_n_listed.p, 0, sizeof(uint32_t), st));
-        hipLaunchKernelGGL(tk::k_export_classify, dim3(grid256(R)), dim3(256), 0, st, d_ranges.p, K, d_run_e.p, R, t->cells.p, d_listed_slot.p, d_listed_val.p, d_n_listed.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&n_listed, d_n_listed.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-    }
-    std::vector<uint8_t> strs((size_t)std::max<uint32_t>(n_listed, 1) * tk::kReprMax, 0), lens((size_t)std::max<uint32_t>(n_listed, 1), 0);
-    if (n_listed) {
-        std::vector<double> vals(n_listed);
-        HIP_TRY(hipMemcpyAsync(vals.data(), d_listed_val.p, (size_t)n_listed * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (uint32_t k = 0; k < n_listed; ++k) lens[k] = (uint8_t)tk::float_repr(vals[k], (char *)strs.data() + (size_t)tk::kReprMax * k);
-    }
-    PC_TRY(d_strs.upload(strs, st)); PC_TRY(d_lens.upload(lens, st));
-    HIP_TRY(hipEventRecord(ev[3], st));
-
-    // phases 4, 5: a byte length per line, their exclusive sum, the bytes
-    const int64_t nlines = R + K;
-    if (nlines >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_export: more than 2^31 lines");
-    tk::ExportView view;
-    view.kind = kind; view.ranges = d_ranges.p; view.K = K; view.run_e = d_run_e.p; view.cells = t->cells.p; view.names = d_names.p;
-    view.listed_slot = d_listed_slot.p; view.strs = d_strs.p; view.lens = d_lens.p;
-    {
-        int rc = PC_OK;
-        room(rc, d_len, (size_t)nlines); room(rc, d_off, (size_t)nlines);
-        if (rc != PC_OK) return rc;
-    }
-    const unsigned gl = (unsigned)((nlines + tk::kFormatRuns - 1) / tk::kFormatRuns);
-    hipLaunchKernelGGL(tk::k_export_lengths, dim3(gl), dim3(tk::kFormatRuns), 0, st, view, nlines, d_len.p);
-    HIP_TRY(hipGetLastError());
-    {
-        size_t b0 = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b0, d_len.p, d_off.p, (int)nlines, st));
-        PC_TRY(d_tmp.reserve(std::max<size_t>(b0, 16)));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b0, d_len.p, d_off.p, (int)nlines, st));
-    }
-    int64_t last_off = 0, last_len = 0;
-    HIP_TRY(hipMemcpyAsync(&last_off, d_off.p + (nlines - 1), 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&last_len, d_len.p + (nlines - 1), 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int64_t total = last_off + last_len;
-    HIP_TRY(hipEventRecord(ev[4], st));
-    PC_TRY(t->ex_text.reserve((size_t)total));
-    hipLaunchKernelGGL(tk::k_export_format, dim3(gl), dim3(tk::kFormatRuns), 0, st, view, nlines, d_off.p, t->ex_text.p);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev[5], st));
-    HIP_TRY(hipStreamSynchronize(st));
+    TrackExport c{t, kind, strand_slot, e->stream};
+    c.slots = t->tab.export_slots(strand_slot);
+    if (c.slots.ids.empty()) return PC_OK;
+    if (c.slots.ids.size() > 65535) return fail(PC_ERR_ARG, "pc_track_export: more than 65535 contigs");
+    PC_TRY(c.ev.create());
+    DrainOnExit drained{c.st};
+    PC_TRY(export_slot_sums(c));
+    if (c.K == 0) { drained.armed = false; return PC_OK; }
+    PC_TRY(export_run_table(c));
+    PC_TRY(export_listed_values(c));
+    PC_TRY(export_lengths_and_offsets(c));
+    PC_TRY(export_format(c));
+    HIP_TRY(hipStreamSynchronize(c.st));
     drained.armed = false;
-    for (int k = 0; k < 5; ++k) t->ex_ms[k] = ms_between(ev[k], ev[k + 1]);
-    t->ex_stats[0] = nlines; t->ex_stats[1] = R; t->ex_stats[2] = (int64_t)n_listed; t->ex_stats[3] = total;
-    t->ex_bytes = total;
-    *bytes = total;
+    c.ev.laps(t->ex_ms, 5);
+    t->ex_stats[0] = c.nlines; t->ex_stats[1] = c.R; t->ex_stats[2] = (int64_t)c.n_listed; t->ex_stats[3] = c.total;
+    t->ex_bytes = c.total;
+    *bytes = c.total;
     return PC_OK;
 }
 
@@ -883,40 +790,31 @@ int pc_track_export_geometry(int *out2) {
 
 // counts[i * nstrands + s]: non-zero cells of public contig i on strand slot s; the indices wait for pc_track_nonzero_read
 int pc_track_nonzero_count(pc_track *t, int64_t *counts) {
-    if (!t || (!counts && !t->order.empty())) return fail(PC_ERR_ARG, "pc_track_nonzero_count: bad arguments");
-    const int nslot = (int)t->order.size() * t->nstrands;
-    for (int k = 0; k < nslot; ++k) counts[k] = 0;
+    if (!t || (!counts && t->tab.num_public() > 0)) return fail(PC_ERR_ARG, "pc_track_nonzero_count: bad arguments");
+    for (int k = 0; k < t->tab.num_public() * t->tab.nstrands; ++k) counts[k] = 0;
     t->nz_total = 0;
-    if (t->ncells == 0) return PC_OK;
-    if (t->ncells >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_nonzero: more than 2^31 stored cells");
+    const int64_t n = t->tab.ncells;
+    if (n == 0) return PC_OK;
+    if (n >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_nonzero: more than 2^31 stored cells");
     pc_engine *e = t->e;
     HIP_TRY(hipSetDevice(e->device));
     PoolScope pool_scope(&e->pool);
     hipStream_t st = e->stream;
-    // the slots that hold cells, in the order of their cells (that of the internal ids)
-    const int nint = (int)(t->contigs.size() * (size_t)t->nstrands);
-    std::vector<int> live;
-    std::vector<int64_t> at;
-    for (int k = 0; k < nint; ++k)
-        if (t->ext[(size_t)k] > 0) { live.push_back(k); at.push_back(t->cell_off[(size_t)k]); }
-    at.push_back(t->ncells);
-    std::vector<int64_t> picked(at.size());
-    const int64_t n = t->ncells;
+    tk::NzShares &z = t->nz_shares;
+    z = t->tab.nonzero_slots();
+    std::vector<int64_t> picked(z.at.size());
     DevBuf<uint32_t> d_flags, d_idx;
     DevBuf<uint8_t> d_tmp;
     DevBuf<int64_t> d_at, d_picked;
     DrainOnExit drained{st};
     int rc = PC_OK;
-    room(rc, d_flags, (size_t)n); room(rc, d_idx, (size_t)n); room(rc, d_picked, at.size());
+    room(rc, d_flags, (size_t)n); room(rc, d_idx, (size_t)n); room(rc, d_picked, z.at.size());
     if (rc != PC_OK) return rc;
-    PC_TRY(d_at.upload(at, st));
+    PC_TRY(d_at.upload(z.at, st));
     hipLaunchKernelGGL(tk::k_track_nz_flags, dim3(grid256(n)), dim3(256), 0, st, t->cells.p, n, d_flags.p);
     HIP_TRY(hipGetLastError());
-    size_t b0 = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, b0, d_flags.p, d_idx.p, (int)n, st));
-    PC_TRY(d_tmp.reserve(std::max<size_t>(b0, 16)));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b0, d_flags.p, d_idx.p, (int)n, st));
-    hipLaunchKernelGGL(tk::k_track_pick, dim3(grid256((int64_t)at.size())), dim3(256), 0, st, d_flags.p, d_idx.p, n, d_at.p, (int)at.size(), d_picked.p);
+    PC_TRY(cub_run(d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, d_flags.p, d_idx.p, (int)n, st); }));
+    hipLaunchKernelGGL(tk::k_track_pick, dim3(grid256((int64_t)z.at.size())), dim3(256), 0, st, d_flags.p, d_idx.p, n, d_at.p, (int)z.at.size(), d_picked.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(picked.data(), d_picked.p, picked.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -924,16 +822,12 @@ int pc_track_nonzero_count(pc_track *t, int64_t *counts) {
     if (total > 0) {
         PC_TRY(t->nz.reserve((size_t)total));
         // (d_at: the live slots' first cells, ascending, in front of its last entry)
-        hipLaunchKernelGGL(tk::k_track_nz_select, dim3(grid256(n)), dim3(256), 0, st, d_flags.p, d_idx.p, n, d_at.p, (int)live.size(), t->nz.p);
+        hipLaunchKernelGGL(tk::k_track_nz_select, dim3(grid256(n)), dim3(256), 0, st, d_flags.p, d_idx.p, n, d_at.p, (int)z.live.size(), t->nz.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
     drained.armed = false;
-    t->nz_begin.assign((size_t)nint, 0); t->nz_cnt.assign((size_t)nint, 0);
-    for (size_t j = 0; j < live.size(); ++j) { t->nz_begin[(size_t)live[j]] = picked[j]; t->nz_cnt[(size_t)live[j]] = picked[j + 1] - picked[j]; }
-    for (size_t i = 0; i < t->order.size(); ++i)
-        for (int s = 0; s < t->nstrands; ++s)
-            counts[i * (size_t)t->nstrands + (size_t)s] = t->nz_cnt[(size_t)t->order[i] * (size_t)t->nstrands + (size_t)s];
+    t->tab.nonzero_counts(z, picked, counts);
     t->nz_total = total;
     return PC_OK;
 }
@@ -948,15 +842,7 @@ int pc_track_nonzero_read(pc_track *t, int64_t *out, int64_t total) {
     std::vector<int64_t> all((size_t)total);
     HIP_TRY(hipMemcpyAsync(all.data(), t->nz.p, (size_t)total * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    // the order of the cells (internal ids) -> public order
-    const std::vector<int64_t> &cnt = t->nz_cnt, &begin = t->nz_begin;
-    int64_t w = 0;
-    for (size_t i = 0; i < t->order.size(); ++i)
-        for (int s = 0; s < t->nstrands; ++s) {
-            const size_t k = (size_t)t->order[i] * (size_t)t->nstrands + (size_t)s;
-            if (cnt[k]) memcpy(out + w, all.data() + begin[k], (size_t)cnt[k] * 8);
-            w += cnt[k];
-        }
+    t->tab.nonzero_regroup(t->nz_shares, all.data(), out);
     t->nz.release();
     t->nz_total = -1;
     return PC_OK;

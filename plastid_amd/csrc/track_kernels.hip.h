@@ -25,11 +25,10 @@
 // Every byte access lies in [0, text_len); every cell access inside the strand's extent.
 // Part of the one translation unit of plastid_counts.hip (behind sam_kernels.hip.h and dense_kernels.hip.h).
 #pragma once
-#include "track_host.h"
+#include "track_table.h"
 
 namespace pctrack {
 
-constexpr uint32_t kNoLine = 0xffffffffu;
 constexpr int kShortLen = 32;                  // lines up to this many positions are filled by one lane
 constexpr unsigned long long kNoDefect = ~0ull;
 
@@ -38,6 +37,19 @@ __device__ __forceinline__ void line_bounds(const uint64_t *__restrict__ line_st
     b = line_start[i]; e = line_start[i + 1] - 1;
     if (e > text_len) e = text_len;
     if (b > e) b = e;
+}
+// the last k of [0, n) with key(k) <= x, -1: none (the keys ascend; equal keys: the last of them)
+template <typename Key> __device__ __forceinline__ int last_at_or_below(int n, int64_t x, Key key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key(mid) <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+// flags in front of position p (p == n: all of them), from their exclusive sum idx
+__device__ __forceinline__ int64_t flags_before(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ idx, int64_t n, int64_t p) {
+    return p < n ? (int64_t)idx[p] : (int64_t)idx[n - 1] + (int64_t)flags[n - 1];
 }
 
 // cls[i]: class | token count << 4.  sig[i]: i for a header or bedGraph line, -1 otherwise (max-scanned by the caller);
@@ -335,18 +347,9 @@ __global__ __launch_bounds__(pcdense::kGatherWG) void k_track_set(const pcdense:
 
 // ---------------------------------------------------------------- arithmetic and equality (pc_track_combine, pc_track_equal)
 
-// One (contig, strand) of the result: cells [out0, out0 + n) of the concatenated output; operand a has cells
-// [a0, a0 + an) for its first an positions and zero behind them (a0 < 0: the operand lacks the slot); b alike.
-struct OpSlot { int64_t out0, n, a0, an, b0, bn; };
-
-// the slot of output cell i: the last one with out0 <= i (empty slots share their out0 with the slot behind them)
+// the OpSlot (track_table.h) of output cell i: the last one with out0 <= i (empty slots share their out0 with the slot behind them)
 __device__ __forceinline__ int op_slot_of(const OpSlot *__restrict__ slots, int nslot, int64_t i) {
-    int lo = 0, hi = nslot;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (slots[mid].out0 <= i) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
+    return last_at_or_below(nslot, i, [slots](int k) { return slots[k].out0; });
 }
 
 enum { kOpAdd = 0, kOpSub = 1, kOpMul = 2 };
@@ -388,19 +391,14 @@ __global__ __launch_bounds__(256) void k_track_nz_select(const uint32_t *__restr
                                                          const int64_t *__restrict__ slot_start, int nslot, int64_t *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n || !flags[i]) return;
-    int lo = 0, hi = nslot;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (slot_start[mid] <= i) lo = mid + 1; else hi = mid;
-    }
-    out[idx[i]] = i - slot_start[lo - 1];
+    out[idx[i]] = i - slot_start[last_at_or_below(nslot, i, [slot_start](int k) { return slot_start[k]; })];
 }
 // out[k] = flags in front of cell at[k] (at[k] == n: all of them), from the exclusive sum idx
 __global__ __launch_bounds__(256) void k_track_pick(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ idx, int64_t n,
                                                     const int64_t *__restrict__ at, int m, int64_t *__restrict__ out) {
     const int k = (int)(blockIdx.x * 256u + threadIdx.x);
     if (k >= m) return;
-    out[k] = at[k] < n ? (int64_t)idx[at[k]] : (int64_t)idx[n - 1] + (int64_t)flags[n - 1];
+    out[k] = flags_before(flags, idx, n, at[k]);
 }
 
 // ---------------------------------------------------------------- export (pc_track_export)
@@ -409,11 +407,8 @@ constexpr int kExportTile = 2048;        // T: cells one workgroup covers in the
 constexpr int kFormatRuns = 256;         // R: lines one workgroup formats, one per lane
 constexpr uint32_t kNotListed = 0xffffffffu;
 
-// Per exported slot: the fixed-tree sum (k_track_sum_partial's tree over the slot's own cells), first non-zero cell and
-// last non-zero cell + 1 (0: none).
-struct SlotStat { double sum; unsigned long long first, last1; };
-struct SlotCells { int64_t cell0, n; };
-
+// Per exported slot (SlotCells -> SlotStat, track_table.h): the fixed-tree sum is k_track_sum_partial's tree over the slot's
+// own cells.
 // grid (max tiles, slots): block (x, y) adds tile x of slot y
 __global__ __launch_bounds__(256) void k_export_slot_partial(const SlotCells *__restrict__ slots, const double *__restrict__ cells, int64_t max_tiles,
                                                              double *__restrict__ partial, SlotStat *__restrict__ stat) {
@@ -444,29 +439,13 @@ __global__ __launch_bounds__(256) void k_export_slot_final(const SlotCells *__re
     if (threadIdx.x == 0) stat[blockIdx.x].sum = r;
 }
 
-// One written contig.  Its export cells are positions [pos0, pos0 + n) -- bedGraph: first to last non-zero; variableStep:
-// every stored cell -- and stand at [e0, e0 + n) of the concatenated export domain; cell0: the cell of pos0.  run_base:
-// runs (bedGraph) or non-zero cells (variableStep) in front of the contig; its header line is line run_base + k.
-struct ExRange {
-    int64_t e0, n, cell0, pos0, run_base;
-    int32_t name_off, name_len;
-};
+// the written contig (ExRange, track_table.h) of export cell e
 __device__ __forceinline__ int ex_range_of(const ExRange *__restrict__ r, int K, int64_t e) {
-    int lo = 0, hi = K;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (r[mid].e0 <= e) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
+    return last_at_or_below(K, e, [r](int k) { return r[k].e0; });
 }
 // the contig of line L: the last k with run_base[k] + k <= L
 __device__ __forceinline__ int ex_range_of_line(const ExRange *__restrict__ r, int K, int64_t L) {
-    int lo = 0, hi = K;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (r[mid].run_base + mid <= L) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
+    return last_at_or_below(K, L, [r](int k) { return r[k].run_base + k; });
 }
 
 // kind 0 (bedGraph): a cell heads a run when it is the contig's first export cell or differs (!=) from the cell in front
@@ -494,8 +473,7 @@ __global__ __launch_bounds__(256) void k_export_select(const uint32_t *__restric
 __global__ __launch_bounds__(256) void k_export_bases(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ idx, int64_t E, ExRange *__restrict__ ranges, int K) {
     const int k = (int)(blockIdx.x * 256u + threadIdx.x);
     if (k > K) return;
-    const int64_t e0 = ranges[k].e0;
-    ranges[k].run_base = e0 < E ? (int64_t)idx[e0] : (int64_t)idx[E - 1] + (int64_t)flags[E - 1];
+    ranges[k].run_base = flags_before(flags, idx, E, ranges[k].e0);
 }
 // The values of the runs that are not plain are listed for the host (any order); listed_slot[r]: the run's place in the
 // list, kNotListed otherwise.
