@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 16
+#define PC_ABI_VERSION 17
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -599,6 +599,45 @@ int pc_track_export_stats(pc_track *t, int64_t *out4);
 int pc_track_export_timing(pc_track *t, double *ms6);
 /* [0] cells one workgroup covers in the run-head kernel, [1] lines one workgroup formats */
 int pc_track_export_geometry(int *out2);
+
+/* ---- A COUNTED PLAN AS TEXT, AND INTO A TRACK (revision 17)
+ * BAMGenomeArray.to_bedgraph / to_variable_step (genome_array.py:990-1111) and to_genome_array (:965-988) without the
+ * counts leaving HBM.  The source is a counted plan (pc_count) of ONE row per position without summed slices, at either
+ * output dtype; PC_ERR_STATE before pc_count, PC_ERR_ARG for any other plan or a plan of another engine.
+ *
+ * pc_counts_export_batches: the contigs of one export (lengths in the order of the text) are counted in batches of at
+ * most `budget` output elements (<= 0: 2^27, 1 GiB of counts); a contig longer than the budget gets a batch alone;
+ * batch_of[k]: the batch of contig k.  The layout indexes export elements with 32 bits; the scans of pc_counts_export
+ * count in int, so a contig of 2^31 - 1 positions or more is refused here (PC_ERR_ARG).  The number of contigs in a
+ * batch is bounded by the 2^31 bytes of their names only.
+ *
+ * pc_counts_export: the text of `nrange` ranges, everything behind the track line of this batch.  Range r is len[r]
+ * consecutive output elements from elem_off[r]; element j of it is genomic position j of contig names[r].  kind 0
+ * (bedGraph): a range of length <= 0 writes nothing; the others are cut into windows of `period` positions (>= 1) and
+ * every maximal run of equal value inside a window whose value is > 0 writes "chrom\tstart\tend\tvalue\n" -- no leading
+ * line, a run across a window border is two lines.  kind 1 (variableStep): "variableStep chrom=<name> span=1\n" for every
+ * range, then "<pos + 1>\tvalue\n" for every non-zero element.  An int64 count prints as its decimal digits, a float64
+ * value as Python's repr(float): integers below 10^16 by the format kernel, every other finite value listed for the host
+ * (csrc/track_host.h: float_repr) and copied in.  Phases, all on the engine's stream: run-head flags over the 8-byte
+ * output (typed by the dtype); exclusive sum, select into the run table and the runs in front of every range; bedGraph: a
+ * second flag, sum and select pass keeps the runs whose value is > 0 as the lines; float64: the listed values; a byte
+ * length per line and their exclusive sum; the format kernel.  pc_counts_export_read copies the text out (through the
+ * transfer ring when it is large) and frees it.  One batch holds fewer than 2^31 elements and lines. */
+int pc_counts_export_batches(int64_t n, const int64_t *len, int64_t budget, int32_t *batch_of, int *nbatch);
+int pc_counts_export(pc_engine *e, pc_plan *p, int kind, int64_t period, int nrange, const char *const *names, const int64_t *elem_off,
+                     const int64_t *len, int64_t *bytes);
+int pc_counts_export_read(pc_engine *e, void *dst, int64_t bytes);
+/* the last pc_counts_export: [0] lines, [1] runs of any value (bedGraph) or non-zero elements (variableStep), [2] values
+ * listed for the host, [3] bytes */
+int pc_counts_export_stats(pc_engine *e, int64_t *out4);
+/* milliseconds of the last pc_counts_export: [0] run heads, [1] sums and selects (run table, lines), [2] listed values
+ * (the host's repr included), [3] line lengths + offsets, [4] format, [5] read-back (host clock) */
+int pc_counts_export_timing(pc_engine *e, double *ms6);
+/* Cells [start, start + n) of (contig, strand_slot) = (double) of output elements [elem_off, elem_off + n) of a counted
+ * plan on the track's engine: the birth, growth, extent and cached-sum rules of pc_track_set for one segment; k_track_set
+ * reading HBM instead of an uploaded vector (int64 -> double is exact for every count a file can hold).  Every argument
+ * is checked before anything changes. */
+int pc_track_set_counts(pc_track *t, const char *contig, int strand_slot, int64_t start, pc_plan *p, int64_t elem_off, int64_t n);
 
 #ifdef __cplusplus
 }

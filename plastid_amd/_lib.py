@@ -143,6 +143,12 @@ SIGNATURES = {
     "pc_track_export_stats": (_int, [_vp, _vp]),
     "pc_track_export_timing": (_int, [_vp, _vp]),
     "pc_track_export_geometry": (_int, [_vp]),
+    "pc_counts_export_batches": (_int, [_i64, _vp, _i64, _vp, ctypes.POINTER(_int)]),
+    "pc_counts_export": (_int, [_vp, _vp, _int, _i64, _int, _vp, _vp, _vp, ctypes.POINTER(_i64)]),
+    "pc_counts_export_read": (_int, [_vp, _vp, _i64]),
+    "pc_counts_export_stats": (_int, [_vp, _vp]),
+    "pc_counts_export_timing": (_int, [_vp, _vp]),
+    "pc_track_set_counts": (_int, [_vp, ctypes.c_char_p, _int, _i64, _vp, _i64, _i64]),
 }
 
 _lib = None
@@ -152,7 +158,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 def load():

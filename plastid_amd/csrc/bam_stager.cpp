@@ -1813,6 +1813,17 @@ int pb_track_writer_add(void *h, int kind, const char *name, const double *cells
     else pctrack::write_variable_step_contig(w->text, name, cells, n, w->stats);
     return 0;
 }
+// The text BAMGenomeArray writes of one contig's count vector (genome_array.py:990-1111): `cells` are n int64 counts
+// (is_float 0) or float64 values (1); bedGraph runs are cut at every multiple of `window`.
+int pb_track_writer_add_counts(void *h, int kind, int is_float, const char *name, const void *cells, int64_t n, int64_t window) {
+    TrackWriter *w = static_cast<TrackWriter *>(h);
+    if (!w || !name || n < 0 || (n > 0 && !cells) || (kind != 0 && kind != 1) || (kind == 0 && window < 1)) return fail("pb_track_writer_add_counts: bad arguments");
+    if (kind == 0 && is_float) pctrack::write_count_bedgraph_contig(w->text, name, static_cast<const double *>(cells), n, window, w->stats);
+    else if (kind == 0) pctrack::write_count_bedgraph_contig(w->text, name, static_cast<const int64_t *>(cells), n, window, w->stats);
+    else if (is_float) pctrack::write_count_variable_step_contig(w->text, name, static_cast<const double *>(cells), n, w->stats);
+    else pctrack::write_count_variable_step_contig(w->text, name, static_cast<const int64_t *>(cells), n, w->stats);
+    return 0;
+}
 int64_t pb_track_writer_size(void *h) { return h ? (int64_t)static_cast<TrackWriter *>(h)->text.size() : -1; }
 const char *pb_track_writer_text(void *h) { return static_cast<TrackWriter *>(h)->text.data(); }
 // [0] lines, [1] runs / non-zero cells, [2] values that are not plain, [3] bytes

@@ -19,6 +19,7 @@
 //                                  k_gather_split, or the three center kernels + k_gather, or -- a '+' / '-' plan
 //                                  under a point rule over a file with a dense vector -- k_dense_gather alone
 //   pc_rle / pc_total / pc_mapped_reads / pc_warn_flags   consumers of a finished count
+//                                  (pc_counts_export and pc_track_set_counts, revision 17: track_decoder.hip.h)
 #include "pc_kernels.hip.h"
 #include "plan_kernels.hip.h"
 #include "stage_kernels.hip.h"
@@ -675,6 +676,10 @@ struct pc_engine {
     hipEvent_t ev[8] = {};
     std::vector<StagedFile *> files;
     std::vector<pc_track *> tracks;   // the count tracks made on this engine (track_decoder.hip.h): they go with it
+    DevBuf<uint8_t> cx_text;          // the last pc_counts_export (track_decoder.hip.h): its text waits in HBM for pc_counts_export_read
+    int64_t cx_bytes = -1;
+    int64_t cx_stats[4] = {0, 0, 0, 0};      // lines, runs / non-zero cells, values listed for the host, bytes
+    double cx_ms[6] = {0, 0, 0, 0, 0, 0};    // run heads | sums + selects | listed values | lengths + offsets | format | read-back
     int ntid = 0;
     DevBuf<FileView> d_files;
     bool files_dirty = true;

@@ -10,6 +10,9 @@
 // pc_track_combine (a new track from a op b or a op scalar), pc_track_equal, pc_track_nonzero_count / _read and
 // pc_track_export / _read: the bedGraph / variableStep text of a strand built in HBM by the phases of a TrackExport and
 // read back once; of an export the host sees the per-slot sums and the values that are not plain.
+// Revision 17: a counted plan as the source.  pc_counts_export / _read write the text BAMGenomeArray gives of its count
+// vectors (genome_array.py:990-1111; window borders, runs whose value is > 0, int64 or float64 values) from the plan's
+// output in HBM, by the phases of a CountsExport; pc_track_set_counts is pc_track_set for one segment reading that output.
 // Part of the one translation unit of plastid_counts.hip (behind sam_decoder.hip.h).
 #include "track_kernels.hip.h"
 
@@ -376,6 +379,21 @@ struct TrackExport {
     DevBuf<int64_t> d_len, d_off;
 };
 
+// The listed values of an export come to the host, are formatted by float_repr and go back as text: kReprMax bytes apart
+// in strs, their lengths in lens (both at least one entry long).
+int listed_values_as_text(hipStream_t st, uint32_t n_listed, DevBuf<double> &d_listed_val, std::vector<uint8_t> &strs, std::vector<uint8_t> &lens,
+                          DevBuf<uint8_t> &d_strs, DevBuf<uint8_t> &d_lens) {
+    strs.assign((size_t)std::max<uint32_t>(n_listed, 1) * tk::kReprMax, 0); lens.assign((size_t)std::max<uint32_t>(n_listed, 1), 0);
+    if (n_listed) {
+        std::vector<double> vals(n_listed);
+        HIP_TRY(hipMemcpyAsync(vals.data(), d_listed_val.p, (size_t)n_listed * 8, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t k = 0; k < n_listed; ++k) lens[k] = (uint8_t)tk::float_repr(vals[k], (char *)strs.data() + (size_t)tk::kReprMax * k);
+    }
+    PC_TRY(d_strs.upload(strs, st)); PC_TRY(d_lens.upload(lens, st));
+    return PC_OK;
+}
+
 // Phase 1: per slot the fixed-tree sum, first and last non-zero; from them the contigs that are written.
 int export_slot_sums(TrackExport &c) {
     hipStream_t st = c.st;
@@ -441,14 +459,7 @@ int export_listed_values(TrackExport &c) {
         HIP_TRY(hipMemcpyAsync(&c.n_listed, c.d_n_listed.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    c.strs.assign((size_t)std::max<uint32_t>(c.n_listed, 1) * tk::kReprMax, 0); c.lens.assign((size_t)std::max<uint32_t>(c.n_listed, 1), 0);
-    if (c.n_listed) {
-        std::vector<double> vals(c.n_listed);
-        HIP_TRY(hipMemcpyAsync(vals.data(), c.d_listed_val.p, (size_t)c.n_listed * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (uint32_t k = 0; k < c.n_listed; ++k) c.lens[k] = (uint8_t)tk::float_repr(vals[k], (char *)c.strs.data() + (size_t)tk::kReprMax * k);
-    }
-    PC_TRY(c.d_strs.upload(c.strs, st)); PC_TRY(c.d_lens.upload(c.lens, st));
+    PC_TRY(listed_values_as_text(st, c.n_listed, c.d_listed_val, c.strs, c.lens, c.d_strs, c.d_lens));
     HIP_TRY(hipEventRecord(c.ev[3], st));
     return PC_OK;
 }
@@ -483,6 +494,161 @@ int export_format(TrackExport &c) {
                        c.d_off.p, c.t->ex_text.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.ev[5], c.st));
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------- export of a counted plan (pc_counts_export)
+
+// What the phases of one export of a plan's output share.  The phases that launch typed kernels are templates over the
+// plan's output dtype (int64_t, double).
+struct CountsExport {
+    pc_engine *e;
+    pc_plan *p;
+    int kind;
+    int64_t period;
+    hipStream_t st;
+    LapEvents<6> ev;                   // start | run heads | run table + lines | listed values | lengths + offsets | formatted
+    tk::ExportRanges xr;               // the ranges of the batch and the sentinel behind them
+    int K = 0;                         // ranges
+    int64_t E = 0, R = 0, nvalues = 0, nlines = 0, total = 0;   // elements, runs, classified values, lines, bytes
+    uint32_t n_listed = 0;
+    std::vector<uint8_t> strs, lens;
+    DevBuf<tk::ExRange> d_ranges;
+    DevBuf<uint32_t> d_flags, d_idx, d_run_e, d_line_run, d_listed_slot, d_n_listed;
+    DevBuf<double> d_listed_val;
+    DevBuf<uint8_t> d_tmp, d_names, d_strs, d_lens;
+    DevBuf<int64_t> d_len, d_off;
+    template <typename T> tk::CountView<T> view(bool listed) const {
+        tk::CountView<T> v;
+        v.kind = kind; v.ranges = d_ranges.p; v.K = K; v.run_e = d_run_e.p; v.line_run = d_line_run.p; v.out = (const T *)p->d_out.p; v.names = d_names.p;
+        v.listed_slot = listed ? d_listed_slot.p : nullptr; v.strs = listed ? d_strs.p : nullptr; v.lens = listed ? d_lens.p : nullptr;
+        return v;
+    }
+};
+
+// flags in front of position n of an exclusive sum over n flags
+int flags_total(hipStream_t st, const uint32_t *d_flags, const uint32_t *d_idx, int64_t n, int64_t &total) {
+    uint32_t last[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(&last[0], d_idx + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&last[1], d_flags + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    total = (int64_t)last[0] + (int64_t)last[1];
+    return PC_OK;
+}
+
+// Phase 1: run-head flags over the 8-byte output.
+template <typename T> int counts_run_heads(CountsExport &c) {
+    hipStream_t st = c.st;
+    PC_TRY(c.d_ranges.upload(c.xr.ranges, st));
+    PC_TRY(c.d_names.upload(c.xr.names, st));
+    if (c.E > 0) {
+        int rc = PC_OK;
+        room(rc, c.d_flags, (size_t)c.E); room(rc, c.d_idx, (size_t)c.E);
+        if (rc != PC_OK) return rc;
+        const uint32_t period = tk::count_period32(c.kind, c.period);
+        hipLaunchKernelGGL(tk::k_counts_flags<T>, dim3((unsigned)((c.E + tk::kExportTile - 1) / tk::kExportTile)), dim3(256), 0, st, c.kind, period, c.d_ranges.p, c.K, c.E,
+                           (const T *)c.p->d_out.p, c.d_flags.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c.ev[1], st));
+    return PC_OK;
+}
+
+// Phases 2, 3: exclusive sum and select into the run table, the runs in front of every range; bedGraph: a second flag,
+// sum and select pass keeps the runs whose value is > 0 as the lines.
+template <typename T> int counts_run_table(CountsExport &c) {
+    hipStream_t st = c.st;
+    const int64_t E = c.E;
+    int64_t kept = 0;
+    if (E > 0) {
+        PC_TRY(cub_run(c.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, c.d_flags.p, c.d_idx.p, (int)E, st); }));
+        hipLaunchKernelGGL(tk::k_export_bases, dim3(grid256(c.K + 1)), dim3(256), 0, st, c.d_flags.p, c.d_idx.p, E, c.d_ranges.p, c.K);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&c.R, &c.d_ranges.p[c.K].run_base, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    int rc = PC_OK;
+    room(rc, c.d_run_e, (size_t)std::max<int64_t>(c.R, 1)); room(rc, c.d_line_run, (size_t)std::max<int64_t>(c.R, 1));
+    if (rc != PC_OK) return rc;
+    if (c.R > 0) {
+        hipLaunchKernelGGL(tk::k_export_select, dim3(grid256(E)), dim3(256), 0, st, c.d_flags.p, c.d_idx.p, E, c.d_run_e.p);
+        HIP_TRY(hipGetLastError());
+        if (c.kind == 0) {
+            // (the element flags are spent: the run flags take their place)
+            hipLaunchKernelGGL(tk::k_counts_keep<T>, dim3(grid256(c.R)), dim3(256), 0, st, c.d_ranges.p, c.K, c.d_run_e.p, c.R, (const T *)c.p->d_out.p, c.d_flags.p);
+            HIP_TRY(hipGetLastError());
+            PC_TRY(cub_run(c.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, c.d_flags.p, c.d_idx.p, (int)c.R, st); }));
+            PC_TRY(flags_total(st, c.d_flags.p, c.d_idx.p, c.R, kept));
+            if (kept > 0) {
+                hipLaunchKernelGGL(tk::k_export_select, dim3(grid256(c.R)), dim3(256), 0, st, c.d_flags.p, c.d_idx.p, c.R, c.d_line_run.p);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+    }
+    c.nlines = c.kind == 0 ? kept : c.R + c.K;
+    c.nvalues = c.kind == 0 ? kept : c.R;
+    HIP_TRY(hipEventRecord(c.ev[2], st));
+    return PC_OK;
+}
+
+// Phase 4 (float64): the values of the lines that are not plain go to the host and come back as text.
+int counts_listed_values(CountsExport &c) {
+    hipStream_t st = c.st;
+    int rc = PC_OK;
+    room(rc, c.d_listed_slot, (size_t)std::max<int64_t>(c.nvalues, 1)); room(rc, c.d_listed_val, (size_t)std::max<int64_t>(c.nvalues, 1)); room(rc, c.d_n_listed, 1);
+    if (rc != PC_OK) return rc;
+    if (c.nvalues > 0) {
+        HIP_TRY(hipMemsetAsync(c.d_n_listed.p, 0, sizeof(uint32_t), st));
+        hipLaunchKernelGGL(tk::k_counts_classify, dim3(grid256(c.nvalues)), dim3(256), 0, st, c.view<double>(false), c.nvalues, c.d_listed_slot.p, c.d_listed_val.p, c.d_n_listed.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&c.n_listed, c.d_n_listed.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return listed_values_as_text(st, c.n_listed, c.d_listed_val, c.strs, c.lens, c.d_strs, c.d_lens);
+}
+
+// Phases 5, 6: a byte length per line into a counting sink and their exclusive sum; the format kernel stores every line
+// at its offset.
+template <typename T> int counts_lengths_and_format(CountsExport &c, bool listed) {
+    hipStream_t st = c.st;
+    const int64_t nlines = c.nlines;
+    const tk::CountView<T> v = c.view<T>(listed);
+    const unsigned grid = (unsigned)((nlines + tk::kFormatRuns - 1) / tk::kFormatRuns);
+    int rc = PC_OK;
+    room(rc, c.d_len, (size_t)nlines); room(rc, c.d_off, (size_t)nlines);
+    if (rc != PC_OK) return rc;
+    hipLaunchKernelGGL(tk::k_counts_lengths<T>, dim3(grid), dim3(tk::kFormatRuns), 0, st, v, nlines, c.d_len.p);
+    HIP_TRY(hipGetLastError());
+    PC_TRY(cub_run(c.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, c.d_len.p, c.d_off.p, (int)nlines, st); }));
+    int64_t last_off = 0, last_len = 0;
+    HIP_TRY(hipMemcpyAsync(&last_off, c.d_off.p + (nlines - 1), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&last_len, c.d_len.p + (nlines - 1), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c.total = last_off + last_len;
+    HIP_TRY(hipEventRecord(c.ev[4], st));
+    PC_TRY(c.e->cx_text.reserve((size_t)c.total));
+    hipLaunchKernelGGL(tk::k_counts_format<T>, dim3(grid), dim3(tk::kFormatRuns), 0, st, v, nlines, c.d_off.p, c.e->cx_text.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c.ev[5], st));
+    return PC_OK;
+}
+
+template <typename T> int counts_export_phases(CountsExport &c, bool is_float) {
+    PC_TRY(counts_run_heads<T>(c));
+    PC_TRY(counts_run_table<T>(c));
+    if (c.nlines >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_counts_export: more than 2^31 lines");
+    if (is_float) PC_TRY(counts_listed_values(c));
+    HIP_TRY(hipEventRecord(c.ev[3], c.st));
+    if (c.nlines > 0) PC_TRY(counts_lengths_and_format<T>(c, is_float));
+    else { HIP_TRY(hipEventRecord(c.ev[4], c.st)); HIP_TRY(hipEventRecord(c.ev[5], c.st)); }
+    return PC_OK;
+}
+
+// a counted one-row plan without summed slices on engine e, its results complete
+int counts_source_check(const char *who, pc_engine *e, pc_plan *p) {
+    if (p->e != e) return fail(PC_ERR_ARG, "%s: the plan lives on another engine", who);
+    if (!p->counted) return fail(PC_ERR_STATE, "%s: nothing counted yet", who);
+    if (p->rows != 1 || p->has_sums) return fail(PC_ERR_ARG, "%s: needs a plan of one row per position without summed slices", who);
     return PC_OK;
 }
 
@@ -783,6 +949,128 @@ int pc_track_export_timing(pc_track *t, double *ms6) {
 int pc_track_export_geometry(int *out2) {
     if (!out2) return fail(PC_ERR_ARG, "pc_track_export_geometry: bad arguments");
     out2[0] = tk::kExportTile; out2[1] = tk::kFormatRuns;
+    return PC_OK;
+}
+
+// ---------------------------------------------------------------- a counted plan as text, and into a track (revision 17)
+
+// The contigs of an export in batches of at most `budget` output elements (track_table.h: count_batches).
+int pc_counts_export_batches(int64_t n, const int64_t *len, int64_t budget, int32_t *batch_of, int *nbatch) {
+    if (n < 0 || !nbatch || (n > 0 && (!len || !batch_of))) return fail(PC_ERR_ARG, "pc_counts_export_batches: bad arguments");
+    std::string msg;
+    *nbatch = tk::count_batches(n, len, budget > 0 ? budget : tk::kCountBudget, batch_of, msg);
+    if (!msg.empty()) return fail(PC_ERR_ARG, "pc_counts_export_batches: %s", msg.c_str());
+    // (the scans of pc_counts_export count in int: what the layout admits up to 2^32 - 1 is refused here, where the export is planned)
+    for (int64_t k = 0; k < n; ++k)
+        if (len[k] >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_counts_export_batches: contig %lld has 2^31 - 1 positions or more: a batch of pc_counts_export holds fewer", (long long)k);
+    return PC_OK;
+}
+
+// BAMGenomeArray's to_bedgraph (kind 0; period: the window size) / to_variable_step (kind 1) over the ranges of a counted
+// one-row plan (genome_array.py:990-1111), everything behind the track line, built in HBM on the engine's stream by the
+// phases of a CountsExport: run heads over the 8-byte output, exclusive sum and select into the run table, (bedGraph) the
+// runs whose value is > 0 as lines, (float64) the values that are not plain to the host and back as text, a byte length
+// per line, their exclusive sum, the format kernel.  *bytes: the size of the text, which waits for pc_counts_export_read.
+int pc_counts_export(pc_engine *e, pc_plan *p, int kind, int64_t period, int nrange, const char *const *names, const int64_t *elem_off, const int64_t *len,
+                     int64_t *bytes) {
+    if (!e || !p || !bytes || (kind != 0 && kind != 1) || nrange < 0 || (nrange > 0 && (!names || !elem_off || !len)))
+        return fail(PC_ERR_ARG, "pc_counts_export: bad arguments");
+    PC_TRY(counts_source_check("pc_counts_export", e, p));
+    if (kind == 0 && period < 1) return fail(PC_ERR_ARG, "pc_counts_export: the window of a bedGraph must be at least 1");
+    std::string msg;
+    CountsExport c{e, p, kind, period, e->stream};
+    c.xr = tk::count_ranges(nrange, names, elem_off, len, p->out_elems, msg);
+    if (!msg.empty()) return fail(PC_ERR_ARG, "pc_counts_export: %s", msg.c_str());
+    c.K = nrange; c.E = c.xr.cells;
+    if (c.E >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_counts_export: more than 2^31 elements in one batch");
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    PC_TRY(check_grid_guard(e, p));
+    for (auto &x : e->cx_stats) x = 0;
+    for (auto &x : e->cx_ms) x = 0.0;
+    e->cx_text.pool = &e->pool;
+    e->cx_bytes = 0;
+    *bytes = 0;
+    if (nrange == 0 || (kind == 0 && c.E == 0)) return PC_OK;
+    PC_TRY(c.ev.create());
+    DrainOnExit drained{c.st};
+    HIP_TRY(hipEventRecord(c.ev[0], c.st));
+    const bool is_float = p->last_dtype == PC_OUT_FLOAT64;
+    e->cx_bytes = -1;
+    if (is_float) PC_TRY(counts_export_phases<double>(c, true)); else PC_TRY(counts_export_phases<int64_t>(c, false));
+    HIP_TRY(hipStreamSynchronize(c.st));
+    drained.armed = false;
+    c.ev.laps(e->cx_ms, 5);
+    e->cx_stats[0] = c.nlines; e->cx_stats[1] = c.R; e->cx_stats[2] = (int64_t)c.n_listed; e->cx_stats[3] = c.total;
+    e->cx_bytes = c.total;
+    *bytes = c.total;
+    return PC_OK;
+}
+
+// The text of the last pc_counts_export (`bytes` as it reported), through the transfer ring when it is large.
+int pc_counts_export_read(pc_engine *e, void *dst, int64_t bytes) {
+    if (!e || e->cx_bytes < 0 || bytes != e->cx_bytes || (bytes > 0 && !dst)) return fail(PC_ERR_ARG, "pc_counts_export_read: no exported text of this size");
+    HIP_TRY(hipSetDevice(e->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    if (bytes > 0) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        const std::vector<TransferJob> job{{dst, e->cx_text.p, (size_t)bytes}};
+        PC_TRY(TransferRing::of(e->device).run(e->device, job, TransferRing::kPiece, false, true));
+    }
+    e->cx_ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    e->cx_text.release();
+    e->cx_bytes = -1;
+    return PC_OK;
+}
+
+int pc_counts_export_stats(pc_engine *e, int64_t *out4) {
+    if (!e || !out4) return fail(PC_ERR_ARG, "pc_counts_export_stats: bad arguments");
+    for (int k = 0; k < 4; ++k) out4[k] = e->cx_stats[k];
+    return PC_OK;
+}
+
+int pc_counts_export_timing(pc_engine *e, double *ms6) {
+    if (!e || !ms6) return fail(PC_ERR_ARG, "pc_counts_export_timing: bad arguments");
+    for (int k = 0; k < 6; ++k) ms6[k] = e->cx_ms[k];
+    return PC_OK;
+}
+
+// pc_track_set for one segment [start, start + n) whose values are output elements [elem_off, elem_off + n) of a counted
+// one-row plan on the track's engine, converted to double: no count crosses to the host.
+int pc_track_set_counts(pc_track *t, const char *contig, int strand_slot, int64_t start, pc_plan *p, int64_t elem_off, int64_t n) {
+    if (!t || !contig || !p) return fail(PC_ERR_ARG, "pc_track_set_counts: bad arguments");
+    if (strand_slot < 0 || strand_slot >= t->tab.nstrands) return fail(PC_ERR_ARG, "pc_track_set_counts: strand slot %d of %d", strand_slot, t->tab.nstrands);
+    // everything is checked before anything changes
+    pc_engine *e = t->e;
+    PC_TRY(counts_source_check("pc_track_set_counts", e, p));
+    if (start < 0 || n < 0 || start > tk::kMaxCoord || n > tk::kMaxCoord - start) return fail(PC_ERR_ARG, "pc_track_set_counts: the segment lies outside [0, 2^40]");
+    if (n > 0 && (elem_off < 0 || elem_off > p->out_elems || n > p->out_elems - elem_off)) return fail(PC_ERR_ARG, "pc_track_set_counts: reads outside the plan's output");
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    PC_TRY(check_grid_guard(e, p));
+    const int64_t end = start + n;
+    const int8_t step = 1;
+    const int32_t id = t->tab.id_of(contig);
+    const int64_t furthest = t->tab.grow_for_set(id, &start, &end, 1);
+    t->sum_valid = false;
+    if (furthest == 0) return PC_OK;
+    PC_TRY(track_grow_storage(t, t->tab.plan_storage(id, strand_slot, furthest), st));
+    const int64_t slot = (int64_t)t->tab.slot(id, strand_slot);
+    std::vector<pcdense::Item> items;
+    t->tab.cut_items(1, &start, &end, &elem_off, &step, [slot](int64_t) { return slot; }, items);
+    if (items.empty()) return PC_OK;
+    if (items.size() >= (size_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_set_counts: too many items");
+    DevBuf<pcdense::Item> d_items;
+    DrainOnExit drained{st};
+    PC_TRY(d_items.upload(items, st));
+    if (p->last_dtype == PC_OUT_FLOAT64)
+        hipLaunchKernelGGL(tk::k_track_set_counts<double>, dim3((unsigned)items.size()), dim3(pcdense::kGatherWG), 0, st, d_items.p, t->cells.p, (const double *)p->d_out.p);
+    else
+        hipLaunchKernelGGL(tk::k_track_set_counts<int64_t>, dim3((unsigned)items.size()), dim3(pcdense::kGatherWG), 0, st, d_items.p, t->cells.p, (const int64_t *)p->d_out.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
     return PC_OK;
 }
 

@@ -16,7 +16,9 @@
 // The way back (revision 16): grown_length, the one growth rule of import and writes; value_class / float_repr, Python's
 // repr(float) -- plain values by a function the format kernel runs too, the others host only; put_bed_line & co, the bytes
 // of an exported line through a sink that counts or stores; write_bedgraph_contig / write_variable_step_contig, the serial
-// writers (genome_array.py:1996-2084), the model of the device export.
+// writers (genome_array.py:1996-2084), the model of the device export.  Revision 17: put_count_bed_line / put_count_var_line
+// and write_count_bedgraph_contig / write_count_variable_step_contig, the same for the text BAMGenomeArray writes of a count
+// vector (:990-1111; int64 or float64 cells, windows).
 // The per-line functions carry PC_TRK_HD: __host__ __device__ under hipcc, nothing under a host compiler.
 // Plain C++17 (no HIP): tests/track_host_test.cpp and tests/track_export_host_test.cpp compile it on a machine without a
 // GPU, under the sanitizers.
@@ -685,6 +687,82 @@ inline void write_variable_step_contig(std::string &out, const std::string &name
         const uint8_t *vt; int vl;
         host_value(v[i], buf, vt, vl, st);
         put_var_line(s, i, v[i], vt, vl);
+        st.lines += 1; st.runs += 1;
+    }
+    st.bytes += (int64_t)(out.size() - before);
+}
+
+// ---------------------------------------------------------------- export of a COUNT VECTOR (genome_array.py:990-1111)
+// BAMGenomeArray's text differs from GenomeArray's: the vector is cut into windows of `window` positions, inside a window
+// every maximal run of equal value whose value is > 0 is a bedGraph line (no leading line, no header; a run across a
+// window border is two lines); variableStep writes the header, then every non-zero position.  The cells are int64
+// counts -- "%s" % numpy.int64: the decimal digits -- or float64 values (normalised counts, the center rule):
+// repr(float), plain by put_simple_value, listed by float_repr.  Revision 17.
+
+PC_TRK_HD inline bool count_listed(int64_t) { return false; }
+PC_TRK_HD inline bool count_listed(double v) { return value_class(v) == kValListed; }
+template <typename Sink> PC_TRK_HD inline void put_count(Sink &s, int64_t v, const uint8_t *, int) {
+    if (v < 0) { s.put((uint8_t)'-'); put_uint(s, (uint64_t)0 - (uint64_t)v); } else put_uint(s, (uint64_t)v);
+}
+template <typename Sink> PC_TRK_HD inline void put_count(Sink &s, double v, const uint8_t *vtext, int vlen) {
+    if (vtext) put_bytes(s, vtext, vlen); else put_simple_value(s, v);
+}
+// "chrom\tstart\tend\tvalue\n"
+template <typename Sink, typename T> PC_TRK_HD inline void put_count_bed_line(Sink &s, const uint8_t *name, int64_t name_len, int64_t a, int64_t b, T v,
+                                                                              const uint8_t *vtext, int vlen) {
+    put_bytes(s, name, name_len); s.put(9); put_uint(s, (uint64_t)a); s.put(9); put_uint(s, (uint64_t)b); s.put(9);
+    put_count(s, v, vtext, vlen);
+    s.put(10);
+}
+// "<i + 1>\tvalue\n"
+template <typename Sink, typename T> PC_TRK_HD inline void put_count_var_line(Sink &s, int64_t i, T v, const uint8_t *vtext, int vlen) {
+    put_uint(s, (uint64_t)(i + 1)); s.put(9);
+    put_count(s, v, vtext, vlen);
+    s.put(10);
+}
+
+inline void host_count_value(int64_t, char *, const uint8_t *&vtext, int &vlen, ExportStats &) { vtext = nullptr; vlen = 0; }
+inline void host_count_value(double v, char *buf, const uint8_t *&vtext, int &vlen, ExportStats &st) { host_value(v, buf, vtext, vlen, st); }
+
+// Host only: one contig's vector as bedGraph.  stats: written lines, runs of any value (the run table of the device
+// export), listed values among the written lines, bytes.
+template <typename T> inline void write_count_bedgraph_contig(std::string &out, const std::string &name, const T *v, int64_t n, int64_t window, ExportStats &st) {
+    if (n <= 0 || window < 1) return;
+    const size_t before = out.size();
+    StringSink s{&out};
+    const uint8_t *nm = (const uint8_t *)name.data();
+    char buf[kReprMax + 8];
+    for (int64_t w0 = 0; w0 < n;) {
+        const int64_t w1 = n - w0 > window ? w0 + window : n;
+        int64_t head = w0;
+        for (int64_t x = w0 + 1; x <= w1; ++x) {
+            if (x < w1 && !(v[x] != v[x - 1])) continue;
+            st.runs += 1;
+            if (v[head] > 0) {
+                const uint8_t *vt; int vl;
+                host_count_value(v[head], buf, vt, vl, st);
+                put_count_bed_line(s, nm, (int64_t)name.size(), head, x, v[head], vt, vl);
+                st.lines += 1;
+            }
+            head = x;
+        }
+        w0 = w1;
+    }
+    st.bytes += (int64_t)(out.size() - before);
+}
+
+// Host only: one contig's vector as variableStep: the header whatever the length, then a line per non-zero position.
+template <typename T> inline void write_count_variable_step_contig(std::string &out, const std::string &name, const T *v, int64_t n, ExportStats &st) {
+    const size_t before = out.size();
+    StringSink s{&out};
+    put_var_header(s, (const uint8_t *)name.data(), (int64_t)name.size());
+    st.lines += 1;
+    char buf[kReprMax + 8];
+    for (int64_t i = 0; i < n; ++i) {
+        if (!(v[i] != 0)) continue;
+        const uint8_t *vt; int vl;
+        host_count_value(v[i], buf, vt, vl, st);
+        put_count_var_line(s, i, v[i], vt, vl);
         st.lines += 1; st.runs += 1;
     }
     st.bytes += (int64_t)(out.size() - before);

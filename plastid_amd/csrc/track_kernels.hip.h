@@ -22,6 +22,12 @@
 //            k_export_flags / k_export_select / k_export_bases   run heads, the run table, runs in front of a contig
 //            k_export_classify      the values that are not plain, listed for the host's repr
 //            k_export_lengths / k_export_format   a byte length per line; every line's bytes at its offset
+//   revision 17 (a counted plan's output, int64 or float64, as the source):
+//   write:   k_track_set_counts     k_track_set reading the plan's output in HBM
+//   export:  k_counts_flags         run heads of BAMGenomeArray's text: value changes and window borders; non-zero cells
+//            k_counts_keep          bedGraph: the runs whose value is > 0 are the lines (flags for a second select)
+//            k_counts_classify / k_counts_lengths / k_counts_format   as k_export_*, over the line -> run -> range
+//                                   mapping of track_table.h (count_line_of)
 // Every byte access lies in [0, text_len); every cell access inside the strand's extent.
 // Part of the one translation unit of plastid_counts.hip (behind sam_kernels.hip.h and dense_kernels.hip.h).
 #pragma once
@@ -38,15 +44,7 @@ __device__ __forceinline__ void line_bounds(const uint64_t *__restrict__ line_st
     if (e > text_len) e = text_len;
     if (b > e) b = e;
 }
-// the last k of [0, n) with key(k) <= x, -1: none (the keys ascend; equal keys: the last of them)
-template <typename Key> __device__ __forceinline__ int last_at_or_below(int n, int64_t x, Key key) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (key(mid) <= x) lo = mid + 1; else hi = mid;
-    }
-    return lo - 1;
-}
+// (last_at_or_below, ex_range_of, ex_range_of_line: track_table.h -- the host's tests walk them too)
 // flags in front of position p (p == n: all of them), from their exclusive sum idx
 __device__ __forceinline__ int64_t flags_before(const uint32_t *__restrict__ flags, const uint32_t *__restrict__ idx, int64_t n, int64_t p) {
     return p < n ? (int64_t)idx[p] : (int64_t)idx[n - 1] + (int64_t)flags[n - 1];
@@ -439,15 +437,6 @@ __global__ __launch_bounds__(256) void k_export_slot_final(const SlotCells *__re
     if (threadIdx.x == 0) stat[blockIdx.x].sum = r;
 }
 
-// the written contig (ExRange, track_table.h) of export cell e
-__device__ __forceinline__ int ex_range_of(const ExRange *__restrict__ r, int K, int64_t e) {
-    return last_at_or_below(K, e, [r](int k) { return r[k].e0; });
-}
-// the contig of line L: the last k with run_base[k] + k <= L
-__device__ __forceinline__ int ex_range_of_line(const ExRange *__restrict__ r, int K, int64_t L) {
-    return last_at_or_below(K, L, [r](int k) { return r[k].run_base + k; });
-}
-
 // kind 0 (bedGraph): a cell heads a run when it is the contig's first export cell or differs (!=) from the cell in front
 // of it -- read from HBM, so a run that began in an earlier tile needs nothing more; kind 1: when it is non-zero
 __global__ __launch_bounds__(256) void k_export_flags(int kind, const ExRange *__restrict__ ranges, int K, int64_t E, const double *__restrict__ cells,
@@ -533,6 +522,100 @@ __global__ __launch_bounds__(kFormatRuns) void k_export_format(ExportView x, int
     if (L >= nlines) return;
     WriteSink s{text + off[L]};
     export_line(s, x, L);
+}
+
+// ---------------------------------------------------------------- writes from a counted plan (pc_track_set_counts)
+
+// k_track_set reading HBM: position i of the item takes (double) of output element out_off + step * i of the plan
+template <typename T>
+__global__ __launch_bounds__(pcdense::kGatherWG) void k_track_set_counts(const pcdense::Item *__restrict__ items, double *__restrict__ cells, const T *__restrict__ out) {
+    const pcdense::Item it = items[blockIdx.x];
+    const int t = (int)threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < pcdense::kPerLane; ++k) {
+        const int i = t + k * pcdense::kGatherWG;
+        if (i >= it.lo && i < it.hi) cells[it.cell0 + i] = (double)out[it.out_off + (int64_t)it.step * i];
+    }
+}
+
+// ---------------------------------------------------------------- export of a counted plan (pc_counts_export)
+// The ranges are those of count_ranges (track_table.h): export element e of range r is output element cell0 + (e - e0)
+// of the plan, genomic position e - e0 of the range's contig.  T: the plan's output dtype, int64_t or double.
+
+// run heads by count_is_head (track_table.h); the element in front is read from HBM: no carry across tiles
+template <typename T>
+__global__ __launch_bounds__(256) void k_counts_flags(int kind, uint32_t period, const ExRange *__restrict__ ranges, int K, int64_t E, const T *__restrict__ out,
+                                                      uint32_t *__restrict__ flags) {
+#pragma unroll
+    for (int k = 0; k < kExportTile / 256; ++k) {
+        const int64_t e = (int64_t)blockIdx.x * kExportTile + k * 256 + threadIdx.x;
+        if (e >= E) continue;
+        const ExRange r = ranges[ex_range_of(ranges, K, e)];
+        flags[e] = count_is_head(kind, period, out + r.cell0, e - r.e0) ? 1u : 0u;
+    }
+}
+// bedGraph: run r is a line by count_is_line (its value is > 0)
+template <typename T>
+__global__ __launch_bounds__(256) void k_counts_keep(const ExRange *__restrict__ ranges, int K, const uint32_t *__restrict__ run_e, int64_t R,
+                                                     const T *__restrict__ out, uint32_t *__restrict__ keep) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const int64_t e = (int64_t)run_e[r];
+    const ExRange g = ranges[ex_range_of(ranges, K, e)];
+    keep[r] = count_is_line(out[g.cell0 + (e - g.e0)]) ? 1u : 0u;
+}
+
+template <typename T> struct CountView {
+    int kind;
+    const ExRange *ranges; int K;
+    const uint32_t *run_e, *line_run;
+    const T *out;
+    const uint8_t *names;
+    const uint32_t *listed_slot;       // per classified value (count_line_of: value_at); null: none is listed (int64)
+    const uint8_t *strs, *lens;
+};
+// float64: the values of the lines that are not plain, listed for the host (any order); nvalues: lines (bedGraph) or
+// runs (variableStep) -- count_line_of's value_at
+__global__ __launch_bounds__(256) void k_counts_classify(CountView<double> x, int64_t nvalues, uint32_t *__restrict__ listed_slot, double *__restrict__ listed_val,
+                                                         uint32_t *__restrict__ n_listed) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nvalues) return;
+    int64_t e;
+    if (x.kind == 0) e = (int64_t)x.run_e[x.line_run[i]]; else e = (int64_t)x.run_e[i];
+    const ExRange g = x.ranges[ex_range_of(x.ranges, x.K, e)];
+    const double v = x.out[g.cell0 + (e - g.e0)];
+    uint32_t s = kNotListed;
+    if (count_listed(v)) { s = atomicAdd(n_listed, 1u); listed_val[s] = v; }
+    listed_slot[i] = s;
+}
+// line L of the text into the sink
+template <typename Sink, typename T> __device__ __forceinline__ void count_line(Sink &s, const CountView<T> &x, int64_t L) {
+    const CountLine c = count_line_of(x.kind, x.ranges, x.K, x.run_e, x.line_run, L);
+    const ExRange g = x.ranges[c.k];
+    const uint8_t *name = x.names + g.name_off;
+    if (c.header) { put_var_header(s, name, (int64_t)g.name_len); return; }
+    const T v = x.out[g.cell0 + c.j];
+    const uint32_t ls = x.listed_slot ? x.listed_slot[c.value_at] : kNotListed;
+    const uint8_t *vt = ls != kNotListed ? x.strs + (int64_t)kReprMax * ls : nullptr;
+    const int vl = ls != kNotListed ? (int)x.lens[ls] : 0;
+    if (x.kind == 0) put_count_bed_line(s, name, (int64_t)g.name_len, c.j, c.end, v, vt, vl);
+    else put_count_var_line(s, c.j, v, vt, vl);
+}
+template <typename T>
+__global__ __launch_bounds__(kFormatRuns) void k_counts_lengths(CountView<T> x, int64_t nlines, int64_t *__restrict__ len) {
+    const int64_t L = (int64_t)blockIdx.x * kFormatRuns + threadIdx.x;
+    if (L >= nlines) return;
+    CountSink s;
+    s.n = 0;
+    count_line(s, x, L);
+    len[L] = s.n;
+}
+template <typename T>
+__global__ __launch_bounds__(kFormatRuns) void k_counts_format(CountView<T> x, int64_t nlines, const int64_t *__restrict__ off, uint8_t *__restrict__ text) {
+    const int64_t L = (int64_t)blockIdx.x * kFormatRuns + threadIdx.x;
+    if (L >= nlines) return;
+    WriteSink s{text + off[L]};
+    count_line(s, x, L);
 }
 
 } // namespace pctrack

@@ -63,6 +63,111 @@ inline std::string check_segments(const SegWords &w, int64_t nseg, const int64_t
     return msg;
 }
 
+// the last k of [0, n) with key(k) <= x, -1: none (the keys ascend; equal keys: the last of them)
+template <typename Key> PC_TRK_HD inline int last_at_or_below(int n, int64_t x, Key key) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (key(mid) <= x) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+// the written contig (ExRange) of export cell e
+PC_TRK_HD inline int ex_range_of(const ExRange *r, int K, int64_t e) {
+    return last_at_or_below(K, e, [r](int k) { return r[k].e0; });
+}
+// the contig of line L of a text with one header line per contig: the last k with run_base[k] + k <= L
+PC_TRK_HD inline int ex_range_of_line(const ExRange *r, int K, int64_t L) {
+    return last_at_or_below(K, L, [r](int k) { return r[k].run_base + k; });
+}
+
+// ---------------------------------------------------------------- export of a counted plan (pc_counts_export, revision 17)
+// The contigs of one export, in the sorted order of their names, are counted in BATCHES of at most `budget` output
+// elements; a contig longer than the budget gets a batch alone.  The run table holds export elements in 32 bits.
+constexpr int64_t kCountBudget = (int64_t)1 << 27;            // 1 GiB of 8-byte counts: the cap of one int64 block (dense_host.h)
+constexpr int64_t kCountBatchMax = ((int64_t)1 << 32) - 1;
+
+// batch_of[k]: the batch of contig k (ascending from 0); returns the number of batches.  Empty message: fine.
+inline int count_batches(int64_t n, const int64_t *len, int64_t budget, int32_t *batch_of, std::string &msg) {
+    msg.clear();
+    if (budget < 1) { msg = "the batch budget must be at least one element"; return 0; }
+    int nb = 0;
+    int64_t used = 0;
+    bool open = false;
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t x = len[k] > 0 ? len[k] : 0;
+        if (x > kCountBatchMax) { msg = "contig " + std::to_string((long long)k) + " has more than 2^32 - 1 positions: export elements are indexed with 32 bits"; return 0; }
+        if (open && used + x > budget) { ++nb; used = 0; open = false; }
+        batch_of[k] = nb;
+        used += x; open = true;
+    }
+    return open ? nb + 1 : nb;
+}
+
+// The range table of one batch: range r is len[r] consecutive output elements of the plan from elem_off[r], position j
+// of contig names[r] at element j.  In ExRange terms: cell0 the first output element, pos0 0; the sentinel behind them.
+inline ExportRanges count_ranges(int nrange, const char *const *names, const int64_t *elem_off, const int64_t *len, int64_t out_elems, std::string &msg) {
+    ExportRanges out;
+    msg.clear();
+    for (int r = 0; r < nrange; ++r) {
+        const int64_t n = len[r] > 0 ? len[r] : 0;
+        if (!names[r]) { msg = "range " + std::to_string(r) + " has no name"; return ExportRanges(); }
+        if (n > 0 && (elem_off[r] < 0 || elem_off[r] > out_elems || n > out_elems - elem_off[r])) {
+            msg = "range " + std::to_string(r) + " lies outside the plan's output";
+            return ExportRanges();
+        }
+        const size_t nl = strlen(names[r]);
+        if (out.names.size() + nl >= (size_t)0x7fffffff) { msg = "more than 2^31 bytes of contig names"; return ExportRanges(); }
+        ExRange x;
+        x.e0 = out.cells; x.n = n; x.cell0 = n > 0 ? elem_off[r] : 0; x.pos0 = 0; x.run_base = 0;
+        x.name_off = (int32_t)out.names.size(); x.name_len = (int32_t)nl;
+        out.names.insert(out.names.end(), names[r], names[r] + nl);
+        out.cells += n;
+        if (out.cells > kCountBatchMax) { msg = "a batch of more than 2^32 - 1 elements: export elements are indexed with 32 bits"; return ExportRanges(); }
+        out.ranges.push_back(x);
+    }
+    out.ranges.push_back(ExRange{out.cells, 0, 0, 0, 0, 0, 0});
+    return out;
+}
+
+// The two predicates of the text (k_counts_flags, k_counts_keep and the host's replay run these).  cells: element 0 of
+// the range.  bedGraph (kind 0): element j heads a run when it is the range's first, differs (!=) from the element in
+// front of it, or stands on a window border -- period32: the window, 0: no border below 2^32 (no element index reaches
+// it); variableStep (kind 1): when it is non-zero.  A run is a bedGraph line when its value is > 0.
+template <typename T> PC_TRK_HD inline bool count_is_head(int kind, uint32_t period32, const T *cells, int64_t j) {
+    if (kind != 0) return cells[j] != (T)0;
+    return j == 0 || cells[j] != cells[j - 1] || (period32 != 0u && (uint32_t)j % period32 == 0u);
+}
+PC_TRK_HD inline uint32_t count_period32(int kind, int64_t period) { return kind == 0 && period <= (int64_t)0xffffffff ? (uint32_t)period : 0u; }
+template <typename T> PC_TRK_HD inline bool count_is_line(T v) { return v > (T)0; }
+
+// Line L of the text of a batch -> its run -> its range.  ranges[k].run_base: runs in front of range k (entry K: all).
+// bedGraph (kind 0): run_e holds the head of every run of any value, line_run[L] the run of line L (the runs whose
+// value is > 0); the line ends where the next run of its range begins, or with the range (the windows are run borders).
+// variableStep (kind 1): run_e holds the non-zero elements; range k has its header at line run_base[k] + k.
+// value_at: the place of the line's value among the classified values (bedGraph: the line, variableStep: the run).
+struct CountLine { int k; bool header; int64_t run, j, end, value_at; };
+PC_TRK_HD inline CountLine count_line_of(int kind, const ExRange *ranges, int K, const uint32_t *run_e, const uint32_t *line_run, int64_t L) {
+    CountLine c;
+    c.header = false; c.run = 0; c.j = 0; c.end = 0; c.value_at = 0;
+    if (kind == 0) {
+        c.run = (int64_t)line_run[L];
+        const int64_t e = (int64_t)run_e[c.run];
+        c.k = ex_range_of(ranges, K, e);
+        c.j = e - ranges[c.k].e0;
+        c.end = c.run + 1 < ranges[c.k + 1].run_base ? (int64_t)run_e[c.run + 1] - ranges[c.k].e0 : ranges[c.k].n;
+        c.value_at = L;
+        return c;
+    }
+    c.k = ex_range_of_line(ranges, K, L);
+    if (L == ranges[c.k].run_base + c.k) { c.header = true; return c; }
+    c.run = L - c.k - 1;
+    c.j = (int64_t)run_e[c.run] - ranges[c.k].e0;
+    c.end = c.j + 1;
+    c.value_at = c.run;
+    return c;
+}
+
 struct ContigTable {
     int nstrands = 2;
     int64_t min_chr_size = 10000000;

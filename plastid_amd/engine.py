@@ -6,6 +6,7 @@ vectors.  All counting happens in HIP kernels; this module only moves numpy
 arrays across the ABI.
 """
 import ctypes
+import os
 import weakref
 
 import numpy as np
@@ -289,6 +290,23 @@ class Engine(object):
                                          OUT_FLOAT64 if dtype == np.float64 else OUT_INT64, out.ctypes.data))
         return out
 
+    def export_batches(self, lengths, budget=None):
+        """Lists of indices into `lengths` (the contigs of an export, in the order of the text): batches of at most `budget`
+        output elements (default 2^27), a longer contig alone (``pc_counts_export_batches``)."""
+        lens = _c(lengths, np.int64)
+        batch_of = np.zeros(max(len(lens), 1), np.int32)
+        nb = ctypes.c_int(0)
+        check(self._lib.pc_counts_export_batches(len(lens), _ptr(lens), int(budget or 0), _ptr(batch_of), ctypes.byref(nb)), "pc_counts_export_batches")
+        return [[int(k) for k in np.nonzero(batch_of[:len(lens)] == b)[0]] for b in range(nb.value)]
+
+    def counts_export_stats(self):
+        """``(stats, ms)`` of the last :meth:`Plan.export_text`: int64[4] lines, runs / non-zero elements, listed values,
+        bytes; float64[6] milliseconds of run heads, sums and selects, listed values, lengths + offsets, format, read-back."""
+        stats, ms = np.zeros(4, np.int64), np.zeros(6, np.float64)
+        check(self._lib.pc_counts_export_stats(self._h, _ptr(stats)))
+        check(self._lib.pc_counts_export_timing(self._h, _ptr(ms)))
+        return stats, ms
+
     def sync(self):
         check(self._lib.pc_sync(self._h))
 
@@ -454,6 +472,28 @@ class Plan(object):
         values = np.zeros(n.value, self._dtype)
         check(self._lib.pc_read_rle(self.engine._h, self._h, _ptr(starts), _ptr(values), n.value))
         return starts, values
+
+    def export_text(self, kind, names, elem_off, lens, period=1):
+        """The last count as the text ``BAMGenomeArray`` writes (``pc_counts_export``: kind 0 bedGraph with windows of
+        `period`, kind 1 variableStep), everything behind the track line: range r is ``lens[r]`` output elements from
+        ``elem_off[r]``, position j of contig ``names[r]`` at element j.  The text is built in HBM and read back once;
+        returns it as a ``uint8`` array.  One-row plans without summed slices only."""
+        raw = [os.fsencode(c) for c in names]
+        c_names = (ctypes.c_char_p * max(len(raw), 1))(*raw)
+        elem_off, lens = _c(elem_off, np.int64), _c(lens, np.int64)
+        nbytes = ctypes.c_int64(0)
+        check(self._lib.pc_counts_export(self.engine._h, self._h, int(kind), int(period), len(raw), c_names, _ptr(elem_off), _ptr(lens),
+                                         ctypes.byref(nbytes)), "pc_counts_export")
+        text = np.empty(max(int(nbytes.value), 1), np.uint8)
+        check(self._lib.pc_counts_export_read(self.engine._h, _ptr(text), int(nbytes.value)), "pc_counts_export_read")
+        return text[:int(nbytes.value)]
+
+    def set_track(self, track, contig, strand_slot, start, elem_off, n):
+        """Cells ``[start, start + n)`` of `track` (a :class:`~plastid_amd.track.GenomeArray` on this plan's engine) take
+        output elements ``[elem_off, elem_off + n)`` of the last count, device to device (``pc_track_set_counts``)."""
+        check(self._lib.pc_track_set_counts(track._h, os.fsencode(contig), int(strand_slot), int(start), self._h, int(elem_off), int(n)),
+              "pc_track_set_counts")
+        track._names = None
 
     def total(self):
         buf = np.zeros(1, self._dtype)

@@ -744,7 +744,12 @@ class BAMGenomeArray(object):
     def to_genome_array(self, array_type=None):
         """Dense per-chromosome arrays under the current mapping rule (genome_array.py:965-988): one
         whole-contig launch per chromosome and strand.  As in the reference the query stops one
-        position short of the contig end (``lengths()[chrom] - 1`` as the half-open end)."""
+        position short of the contig end (``lengths()[chrom] - 1`` as the half-open end).
+        ``array_type=plastid_amd.GenomeArray``: a device-resident array on this array's engine, filled device to device
+        (:meth:`_to_device_genome_array`)."""
+        from .track import GenomeArray
+        if array_type is GenomeArray:
+            return self._to_device_genome_array()
         if array_type is None:
             array_type = DenseGenomeArray
         ga = array_type(chr_lengths=self.lengths(), strands=self.strands())
@@ -754,63 +759,113 @@ class BAMGenomeArray(object):
                 ga[seg] = self[seg]
         return ga
 
+    def _to_device_genome_array(self):
+        """``to_genome_array(GenomeArray)``: the array is made on THIS array's engine (it holds the engine, so it outlives
+        this object); the contigs are counted in batches over ``0 .. length - 1`` and every contig and strand is one
+        ``pc_track_set_counts``: no count crosses to the host."""
+        from .track import GenomeArray
+        self._one_row_rule()
+        ga = GenomeArray(chr_lengths=self.lengths(), strands=self.strands(), engine=self._engine)
+        chroms = list(self.chroms())
+        ends = [max(int(self.lengths()[c]) - 1, 0) for c in chroms]
+        batches = self._engine.export_batches(ends)
+        for slot, strand in enumerate(self.strands()):
+            for batch in batches:
+                plan, offs = self._count_contigs([chroms[k] for k in batch], [ends[k] for k in batch], strand)
+                try:
+                    for k, off in zip(batch, offs):
+                        if ends[k] == 0:   # (a segment without positions still meets the growth rule, as ``ga[seg] = self[seg]`` does)
+                            ga[GenomicSegment(chroms[k], 0, 0, strand)] = 0.0
+                        else:
+                            plan.set_track(ga, chroms[k], slot, 0, off, ends[k])
+                finally:
+                    if plan is not None:
+                        plan.close()
+        return ga
+
     # ---------------------------------------------------------------- export
-    def _chromosome_runs(self, chrom, strand, period):
-        """Runs of the whole-chromosome vector (genome order) under the current mapping rule: one
-        count launch + the GPU run-length encoder; only the runs come back.  Returns
-        ``(starts, ends, values)``; runs are also cut at every multiple of `period`."""
-        size = self.lengths()[chrom]
-        self._sync_engine([(chrom, 0, size, strand)])
-        rows = self._engine.rows
-        if rows != 1:
+    def _one_row_rule(self):
+        # (before anything is written)
+        if self._native() and self.map_fn._kind == _lib.MAP_STRAT5:
             raise TypeError("export needs a mapping rule that returns one row per position")
-        plan = self._engine.plan([self._chrom_index[chrom]], [0], [size], [STRAND_CODE[strand]], [0], np.ones(1, np.int8),
-                                 [size], size, 1)
-        plan.launch(self._out_dtype())
-        starts, values = plan.rle(period)
-        self._warn_if_unmappable(plan)
-        plan.close()
-        ends = np.append(starts[1:], size)
-        return starts, ends, values
 
-    def to_bedgraph(self, fh, trackname, strand, window_size=100000, printer=None, **kwargs):
-        """Write a bedGraph under the current mapping rule (:1041-1111).  Same lines as the
-        reference's window loop writes (its runs restart at every window border, windows and runs
-        without counts are skipped), from one launch per chromosome."""
-        assert strand in self.strands()
-        assert window_size > 0
-        fh.write("track type=bedGraph name=%s" % trackname)
-        for k, v in sorted(kwargs.items(), key=lambda x: x[0]):
-            fh.write(" %s=%s" % (k, v))
-        fh.write("\n")
-        for chrom in sorted(self.chroms()):
-            if printer is not None:
-                printer.write("Writing chromosome %s..." % chrom)
-            if self.lengths()[chrom] <= 0:
-                continue
-            starts, ends, values = self._chromosome_runs(chrom, strand, window_size)
-            keep = values > 0
-            for a, b, v in zip(starts[keep], ends[keep], values[keep]):
-                fh.write("%s\t%s\t%s\t%s\n" % (chrom, a, b, v))
+    def _count_contigs(self, chroms, ends, strand):
+        """One plan with one segment ``0 .. end`` per contig (genome order, `strand`, '.' included), counted at
+        ``_out_dtype()``; the counts stay in HBM.  Returns ``(plan, first output element per contig)``; the plan is
+        ``None`` when no contig has a position.  ``TypeError``: the mapping rule gives several rows per position."""
+        ends = [max(int(e), 0) for e in ends]
+        self._sync_engine([(c, 0, e, strand) for c, e in zip(chroms, ends)])
+        if self._engine.rows != 1:
+            raise TypeError("export needs a mapping rule that returns one row per position")
+        offs = np.concatenate([[0], np.cumsum(ends)]).astype(np.int64)
+        live = [k for k, e in enumerate(ends) if e > 0]
+        if not live:
+            return None, offs[:-1]
+        plan = self._engine.plan([self._chrom_index[chroms[k]] for k in live], np.zeros(len(live), np.int64), [ends[k] for k in live],
+                                 [STRAND_CODE[strand]] * len(live), [offs[k] for k in live], np.ones(len(live), np.int8),
+                                 [ends[k] for k in live], int(offs[-1]), 1)
+        try:
+            plan.launch(self._out_dtype())
+            self._warn_if_unmappable(plan)
+        except Exception:
+            plan.close()
+            raise
+        return plan, offs[:-1]
 
-    def to_variable_step(self, fh, trackname, strand, window_size=100000, printer=None, **kwargs):
-        """Write a variableStep wiggle under the current mapping rule (:990-1039): every position
-        with a non-zero count, 1-based."""
+    def _export(self, kind, fh, trackname, strand, window_size, printer, kwargs, batch_elems):
+        from .track import _count_text, _track_line, _write_text
         assert strand in self.strands()
-        fh.write("track type=wiggle_0 name=%s" % trackname)
-        for k, v in sorted(kwargs.items(), key=lambda x: x[0]):
-            fh.write(" %s=%s" % (k, v))
-        fh.write("\n")
-        for chrom in sorted(self.chroms()):
+        if kind == 0:
+            assert window_size > 0
+        self._one_row_rule()
+        chroms = sorted(self.chroms())
+        sizes = [max(int(self.lengths()[c]), 0) for c in chroms]
+        stats, timing = np.zeros(5, np.int64), np.zeros(6, np.float64)
+        self._export_stats, self._export_timing = stats, timing
+        _write_text(fh, _track_line(kind, trackname, kwargs).encode("utf-8"))
+        for batch in self._engine.export_batches(sizes, batch_elems):
+            names, lens = [chroms[k] for k in batch], [sizes[k] for k in batch]
             if printer is not None:
-                printer.write("Writing chromosome %s..." % chrom)
-            fh.write("variableStep chrom=%s span=1\n" % chrom)
-            if self.lengths()[chrom] <= 0:
-                continue
-            starts, ends, values = self._chromosome_runs(chrom, strand, 1)
-            keep = values != 0
-            for a, v in zip(starts[keep], values[keep]):
-                fh.write("%s\t%s\n" % (a + 1, v))
+                for chrom in names:
+                    printer.write("Writing chromosome %s..." % chrom)
+            plan, offs = self._count_contigs(names, lens, strand)
+            stats[4] += 1
+            if plan is None:   # contigs without positions: nothing to count (variableStep still writes their headers)
+                text, st = _count_text(kind, {c: np.zeros(0, np.int64) for c in names}, 1)
+                one = [st[k] for k in ("lines", "runs", "listed", "bytes")]
+            else:
+                try:
+                    text = memoryview(plan.export_text(kind, names, offs, lens, period=int(window_size) if kind == 0 else 1))
+                finally:
+                    plan.close()
+                one, ms = self._engine.counts_export_stats()
+                timing += ms
+            _write_text(fh, text)
+            stats[:4] += one
+
+    def to_bedgraph(self, fh, trackname, strand, window_size=100000, printer=None, _batch_elems=None, **kwargs):
+        """Write a bedGraph under the current mapping rule (:1041-1111), the reference's text byte for byte: contigs in
+        sorted order, every contig cut into windows of `window_size`, a line per run of equal value ``> 0`` inside a window.
+        The contigs are counted in batches -- one plan with one whole-contig segment each, one count -- and the text of a
+        batch is built in HBM from the counts (``pc_counts_export``: run heads, select, line lengths, format) and read back
+        once.  :func:`plastid_amd.track.write_count_bedgraph` writes the same text on the host."""
+        self._export(0, fh, trackname, strand, window_size, printer, kwargs, _batch_elems)
+
+    def to_variable_step(self, fh, trackname, strand, window_size=100000, printer=None, _batch_elems=None, **kwargs):
+        """Write a variableStep wiggle under the current mapping rule (:990-1039): every contig's header, every position
+        with a non-zero count, 1-based (`window_size` does not show in the text).  See :meth:`to_bedgraph`."""
+        self._export(1, fh, trackname, strand, window_size, printer, kwargs, _batch_elems)
+
+    def export_stats(self):
+        """Of the last ``to_bedgraph`` / ``to_variable_step``: lines behind the track line, runs of any value (bedGraph) or
+        non-zero positions (variableStep), values listed for the host's ``repr`` formatter, bytes, batches."""
+        return dict(zip(("lines", "runs", "listed", "bytes", "batches"), (int(x) for x in getattr(self, "_export_stats", np.zeros(5, np.int64)))))
+
+    def export_timing(self):
+        """Milliseconds of the last export's phases, summed over its batches: run heads, sums and selects, listed values,
+        line lengths + offsets, format, read-back."""
+        return dict(zip(("run_heads", "runs", "listed_values", "lengths", "format", "read_back"),
+                        (float(x) for x in getattr(self, "_export_timing", np.zeros(6, np.float64)))))
 
 
 class DenseGenomeArray(object):

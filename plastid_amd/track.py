@@ -127,6 +127,7 @@ def _host_writer():
         L.pb_track_writer_open.argtypes = []
         L.pb_track_writer_close.argtypes = [vp]
         L.pb_track_writer_add.argtypes = [vp, ctypes.c_int, ctypes.c_char_p, vp, ctypes.c_int64]
+        L.pb_track_writer_add_counts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, vp, ctypes.c_int64, ctypes.c_int64]
         L.pb_track_writer_size.restype = ctypes.c_int64
         L.pb_track_writer_size.argtypes = [vp]
         L.pb_track_writer_text.restype = vp
@@ -165,6 +166,57 @@ def write_bedgraph(host_array, fh, trackname, strand, **kwargs):
 def write_variable_step(host_array, fh, trackname, strand, **kwargs):
     """``GenomeArray.to_variable_step`` (genome_array.py:1996-2037) of a host ``DenseGenomeArray``; see :func:`write_bedgraph`."""
     return _write_host(1, host_array, fh, trackname, strand, kwargs)
+
+
+def _count_vectors(vectors):
+    """The vectors of a count export as contiguous 1-D arrays of ONE dtype, int64 or float64."""
+    out = OrderedDict((c, np.asarray(v)) for c, v in vectors.items())
+    is_float = any(v.dtype.kind == "f" and v.size for v in out.values())   # (an empty vector has no say)
+    for c, v in out.items():
+        if v.ndim != 1 or v.dtype.kind not in "iuf" or (v.size and is_float != (v.dtype.kind == "f")):
+            raise TypeError("the vectors of a count export are 1-D arrays, all int64 or all float64 (%r)" % (c,))
+    return OrderedDict((c, np.ascontiguousarray(v, np.float64 if is_float else np.int64)) for c, v in out.items()), is_float
+
+
+def _count_text(kind, vectors, window_size):
+    """``(text, stats)`` of the serial writers over ``{contig: vector}``, contigs in sorted order, without the track line."""
+    vectors, is_float = _count_vectors(vectors)
+    L = _host_writer()
+    h = L.pb_track_writer_open()
+    try:
+        for chrom in sorted(vectors):
+            v = vectors[chrom]
+            if L.pb_track_writer_add_counts(h, kind, 1 if is_float else 0, chrom.encode("utf-8"), v.ctypes.data, len(v), int(window_size)) != 0:
+                raise ValueError(L.pb_last_error().decode())
+        text = ctypes.string_at(L.pb_track_writer_text(h), int(L.pb_track_writer_size(h)))
+        stats = np.zeros(4, np.int64)
+        L.pb_track_writer_stats(h, stats.ctypes.data)
+    finally:
+        L.pb_track_writer_close(h)
+    return text, dict(zip(("lines", "runs", "listed", "bytes"), (int(x) for x in stats)))
+
+
+def _write_counts(kind, vectors, fh, trackname, window_size, kwargs):
+    assert window_size > 0
+    text, stats = _count_text(kind, vectors, window_size)
+    _write_text(fh, _track_line(kind, trackname, kwargs).encode("utf-8"))
+    _write_text(fh, text)
+    return stats
+
+
+def write_count_bedgraph(vectors, fh, trackname, window_size=100000, **kwargs):
+    """``BAMGenomeArray.to_bedgraph`` (genome_array.py:1041-1111) over ``{contig: count vector}`` (genome order; 1-D
+    arrays, all int64 or all float64) by the serial writer of ``csrc/track_host.h``, byte for byte: contigs in sorted
+    order, every vector cut into windows of `window_size`, a line per run of equal value ``> 0`` inside a window.  The
+    model of the device export of a :class:`~plastid_amd.genome_array.BAMGenomeArray`, and the way to write such a track
+    without a GPU.  Returns the statistics of :func:`write_bedgraph` (``runs``: runs of any value)."""
+    return _write_counts(0, vectors, fh, trackname, window_size, kwargs)
+
+
+def write_count_variable_step(vectors, fh, trackname, window_size=100000, **kwargs):
+    """``BAMGenomeArray.to_variable_step`` (genome_array.py:990-1039) over ``{contig: count vector}``: every contig's
+    header, a line per non-zero position (`window_size` does not show in the text); see :func:`write_count_bedgraph`."""
+    return _write_counts(1, vectors, fh, trackname, window_size, kwargs)
 
 
 def float_repr(values):
