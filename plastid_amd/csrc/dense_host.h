@@ -2,10 +2,11 @@
 // plastid_counts.hip): one 16-bit cell per (contig, strand, position) that holds what a count under the engine's point
 // rule, size filter and FLAG / MAPQ / NH filters returns for that position.  Under a point rule that value does not
 // depend on the query, so a steady count of a '+' / '-' plan is a copy with widening: the plan's segments are cut into
-// ITEMS of at most kItemLen positions and one workgroup serves one item.
-// Here: the extent of a contig and the cell offsets, the eligibility decision, the cutting of a segment into items.
-// Plain C++17 (no HIP): tests/dense_host_test.cpp compiles it on a machine without a GPU; cut_item is the very function
-// the item kernel calls.
+// ITEMS of at most kItemLen positions and one workgroup serves one item (a batch of kBatch = 1).
+// Here: the extent of a contig and the cell offsets, the eligibility decision, the cutting of a segment into items, the
+// pairing of an item's output elements and the batches.
+// Plain C++17 (no HIP): tests/dense_host_test.cpp and tests/dense_batches_test.cpp compile it on a machine without a
+// GPU; cut_item, pair_cut, pair_slot and batches_of are the very functions the kernels and their launch call.
 #pragma once
 #include <cstdint>
 
@@ -105,5 +106,41 @@ PCDENSE_HD inline Item cut_item(const SegIn &s, int64_t k) {
     it.cell0 = s.cell_base + s.start + a;    // (may lie below the strand's first cell: only [lo, hi) is read)
     return it;
 }
+
+// ---- how the gather kernel serves an item: PAIRS of output elements that share one 16-byte aligned slot of the
+// output (elements 2j and 2j + 1 of an 8-byte array whose base is 16-byte aligned), one 16-byte store each.  Which
+// positions pair depends on the parity of the item's first output element and on the direction:
+//   head   1: position 0 sits alone in its slot (its partner lies outside the item): one 8-byte store
+//   pairs  pair p (0 <= p < pairs) holds positions i0 = head + 2 p and i0 + 1; the lower element of its slot is
+//          out_off + i0 for step +1 (it takes position i0) and out_off - i0 - 1 for step -1 (it takes position i0 + 1)
+//   tail   1: position len - 1 sits alone
+// Cells are read 4 bytes at a time at even cell indices only: the cell block is 4-byte aligned and holds an even number
+// of cells (two strands per contig), so the 4 bytes around a readable cell lie inside the block.
+struct PairCut {
+    int32_t head, pairs, tail;
+};
+PCDENSE_HD inline PairCut pair_cut(int64_t out_off, int32_t step, int32_t len) {
+    PairCut c;
+    c.head = (int32_t)((step > 0 ? out_off : out_off + 1) & 1);
+    if (c.head > len) c.head = len;
+    c.pairs = (len - c.head) >> 1;
+    c.tail = (len - c.head) & 1;
+    return c;
+}
+// the lower output element of pair p's slot
+PCDENSE_HD inline int64_t pair_slot(int64_t out_off, int32_t step, const PairCut &c, int32_t p) {
+    const int64_t i0 = c.head + 2 * (int64_t)p;
+    return step > 0 ? out_off + i0 : out_off - i0 - 1;
+}
+
+// A workgroup of the gather serves a BATCH of kBatch consecutive items of the plan's item list (plan order; the last
+// batch may be short): every descriptor and every cell of the batch is requested before the first store.  The product
+// serves ONE item per workgroup: batches of 2, 4 and 8 were measured and are slower (profiles/dense_gather/NOTES.md);
+// -DPC_DENSE_BATCH=<B> builds them for scripts/exp_dense_sections.py.
+#ifndef PC_DENSE_BATCH
+#define PC_DENSE_BATCH 1
+#endif
+constexpr int kBatch = PC_DENSE_BATCH;
+PCDENSE_HD inline int64_t batches_of(int64_t n_items) { return (n_items + kBatch - 1) / kBatch; }
 
 } // namespace pcdense

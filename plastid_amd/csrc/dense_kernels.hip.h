@@ -3,7 +3,7 @@
 //   build:  k_dense_narrow     int64 counts of the whole extent -> 16-bit cells, escapes counted
 //           k_dense_overflow   the escaped cells as (cell index, count) pairs, in any order (sorted by the caller)
 //   plan:   k_dense_seg_items  items per segment; k_dense_items: the item descriptors (dense_host.h, cut_item)
-//   count:  k_dense_gather     one 256-thread workgroup per item: descriptor, cells, stores
+//   count:  k_dense_gather     one 256-thread workgroup per item (a batch of kBatch = 1): descriptor, cells, 16-byte stores
 // Included behind pc_kernels.hip.h (out_conv, OutT_, GatherSeg).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -78,30 +78,140 @@ __device__ __forceinline__ uint32_t overflow_count(uint32_t cell, const uint32_t
     return (lo < n && key[lo] == cell) ? val[lo] : kEscape;
 }
 
-// One workgroup per item: the descriptor (one wave-uniform 32-byte load), every cell of the lane, then the stores.  Lane
-// t serves positions t, t + 256, ...: a wave loads 128 consecutive bytes of cells and stores 512 consecutive bytes of
-// output per instruction.  Positions outside [lo, hi) -- clipped, beyond the extent, unknown contig -- are zero.
+// Experiment hooks (scripts/exp_dense_sections.py; never set in the product build): -DPC_DENSE_SKIP=<mask> leaves
+// sections of k_dense_gather out -- results are then wrong, only the time counts.  1: no cell loads (a constant is
+// stored); 2: no stores (the cells are xor-reduced into a value that is never written); 4: no descriptor loads (item j
+// is 2 048 positions at cell and output offset 2 048 j, made from the block index; for plans of such items only).
+// -DPC_DENSE_NT=0 / 1: plain / non-temporal output stores (the product: non-temporal -- the output is streamed once
+// per count and otherwise pushes the cells out of the caches).  -DPC_DENSE_BATCH=<B>: dense_host.h.
+#ifndef PC_DENSE_SKIP
+#define PC_DENSE_SKIP 0
+#endif
+#ifndef PC_DENSE_NT
+#define PC_DENSE_NT 1
+#endif
+
+constexpr int kPairsPerLane = kPerLane / 2;
+
+template <typename T>
+__device__ __forceinline__ void store_out(T *p, T v) {
+    if (PC_DENSE_NT) __builtin_nontemporal_store(v, p); else *p = v;
+}
+
+// One workgroup per batch of kBatch items (dense_host.h: pair_cut, batches_of): the descriptors (wave-uniform 32-byte
+// loads), then every cell of every item of the batch, then the stores.  Lane t serves pairs t, t + 256, ... of each
+// item: where the cells are 4-byte aligned a wave loads 256 consecutive bytes of cells, and it stores 1 KiB of
+// consecutive output per instruction.  The head and the tail of an item (one element each, at most) go through lanes 0
+// and 1.  Positions outside [lo, hi) -- clipped, beyond the extent, unknown contig -- are zero.
 template <int OUTMODE>
-__global__ __launch_bounds__(kGatherWG) void k_dense_gather(const Item *__restrict__ items, const uint16_t *__restrict__ cells, const uint32_t *__restrict__ ovf_key,
-                                                            const uint32_t *__restrict__ ovf_val, uint32_t n_ovf,
+__global__ __launch_bounds__(kGatherWG) void k_dense_gather(const Item *__restrict__ items, uint32_t n_items, const uint16_t *__restrict__ cells,
+                                                            const uint32_t *__restrict__ ovf_key, const uint32_t *__restrict__ ovf_val, uint32_t n_ovf,
                                                             typename pc::OutT_<OUTMODE>::type *__restrict__ out, double norm_sum) {
-    const Item it = items[blockIdx.x];
+    typedef typename pc::OutT_<OUTMODE>::type T;
+    typedef T T2 __attribute__((ext_vector_type(2)));
     const int t = (int)threadIdx.x;
-    uint32_t v[kPerLane];
+    const uint32_t first = blockIdx.x * (uint32_t)kBatch;
+    Item it[kBatch];
+    PairCut pc_[kBatch];
 #pragma unroll
-    for (int k = 0; k < kPerLane; ++k) {
-        const int i = t + k * kGatherWG;
-        v[k] = (i >= it.lo && i < it.hi) ? (uint32_t)cells[it.cell0 + i] : 0u;
-    }
-    typename pc::OutT_<OUTMODE>::type *dst = out + it.out_off;
-#pragma unroll
-    for (int k = 0; k < kPerLane; ++k) {
-        const int i = t + k * kGatherWG;
-        if (i < it.len) {
-            uint32_t c = v[k];
-            if (c == kEscape) c = overflow_count((uint32_t)(it.cell0 + i), ovf_key, ovf_val, n_ovf);
-            dst[(int64_t)it.step * i] = pc::out_conv<OUTMODE>(c, norm_sum);
+    for (int b = 0; b < kBatch; ++b) {
+        const uint32_t j = first + b;
+        if (PC_DENSE_SKIP & 4) {
+            it[b].out_off = (int64_t)j * kItemLen; it[b].cell0 = (int64_t)(j & 8191u) * kItemLen;
+            it[b].len = kItemLen; it[b].step = 1; it[b].lo = 0; it[b].hi = kItemLen;
+        } else {
+            it[b] = items[j < n_items ? j : n_items - 1];
         }
+        if (j >= n_items) { it[b].len = 0; it[b].lo = 0; it[b].hi = 0; }
+        pc_[b] = pair_cut(it[b].out_off, it[b].step, it[b].len);
+    }
+    // ---- every load of the batch: 4-byte loads at even cell indices only (dense_host.h).  c: the first cell of the pair.
+    //   c even: w0 = cells c, c + 1                      where either position is readable
+    //   c odd:  w0 = cells c - 1, c  where the first is, w1 = cells c + 1, c + 2  where the second position is
+    // Every register is the target of one load and nothing is combined here: a use of a loaded value would wait for it
+    uint32_t w0[kBatch][kPairsPerLane], w1[kBatch][kPairsPerLane], edge[kBatch];
+    bool even[kBatch];
+    int ie[kBatch];
+#pragma unroll
+    for (int b = 0; b < kBatch; ++b) {
+        const Item &I = it[b];
+        even[b] = ((I.cell0 + pc_[b].head) & 1) == 0;
+        // lane 0: the head (position 0), lane 1: the tail (position len - 1)
+        ie[b] = t == 0 ? (pc_[b].head ? 0 : -1) : (t == 1 && pc_[b].tail) ? I.len - 1 : -1;
+        edge[b] = 0;
+        if (!(PC_DENSE_SKIP & 1) && ie[b] >= I.lo && ie[b] < I.hi) edge[b] = cells[I.cell0 + ie[b]];
+        const uint32_t *quads = reinterpret_cast<const uint32_t *>(cells + (I.cell0 + pc_[b].head - (even[b] ? 0 : 1)));
+#pragma unroll
+        for (int k = 0; k < kPairsPerLane; ++k) {
+            const int p = t + k * kGatherWG, i0 = pc_[b].head + 2 * p;
+            const bool in0 = i0 >= I.lo && i0 < I.hi, in1 = i0 + 1 >= I.lo && i0 + 1 < I.hi;
+            w0[b][k] = 0; w1[b][k] = 0;
+            if (PC_DENSE_SKIP & 1) { w0[b][k] = 0x00030007u; continue; }
+            if (in0 || (even[b] && in1)) w0[b][k] = quads[p];
+            if (!even[b] && in1) w1[b][k] = quads[p + 1];
+        }
+    }
+    if (PC_DENSE_SKIP & 2) {
+        uint32_t sink = 0;
+#pragma unroll
+        for (int b = 0; b < kBatch; ++b) {
+            sink ^= edge[b];
+#pragma unroll
+            for (int k = 0; k < kPairsPerLane; ++k) sink ^= w0[b][k] ^ w1[b][k];
+        }
+        if (sink == 0x9e3779b9u && norm_sum == -1.0) out[0] = (T)sink;
+        return;
+    }
+    // ---- the counts of the batch, before the first store: a load between two stores would make the second store
+    // wait for the first one's completion (one counter serves both, and it only orders accesses of one kind)
+    uint32_t c0[kBatch][kPairsPerLane], c1[kBatch][kPairsPerLane];
+    bool esc = false;
+#pragma unroll
+    for (int b = 0; b < kBatch; ++b) {
+        const Item &I = it[b];
+#pragma unroll
+        for (int k = 0; k < kPairsPerLane; ++k) {
+            const int i0 = pc_[b].head + 2 * (t + k * kGatherWG);
+            const uint32_t pw = (uint32_t)((((uint64_t)w1[b][k] << 32) | w0[b][k]) >> (even[b] ? 0 : 16));   // the pair's two cells
+            c0[b][k] = pw & 0xffffu;
+            c1[b][k] = pw >> 16;
+            if (!(i0 >= I.lo && i0 < I.hi)) c0[b][k] = 0;            // (a 4-byte load also brings cells that are not this pair's to read)
+            if (!(i0 + 1 >= I.lo && i0 + 1 < I.hi)) c1[b][k] = 0;
+            esc = esc || c0[b][k] == kEscape || c1[b][k] == kEscape;
+        }
+        esc = esc || edge[b] == kEscape;
+    }
+    if (esc) {
+#pragma unroll
+        for (int b = 0; b < kBatch; ++b) {
+            const uint32_t c = (uint32_t)(it[b].cell0 + pc_[b].head);
+#pragma unroll
+            for (int k = 0; k < kPairsPerLane; ++k) {
+                const uint32_t p = (uint32_t)(t + k * kGatherWG);
+                if (c0[b][k] == kEscape) c0[b][k] = overflow_count(c + 2 * p, ovf_key, ovf_val, n_ovf);
+                if (c1[b][k] == kEscape) c1[b][k] = overflow_count(c + 2 * p + 1, ovf_key, ovf_val, n_ovf);
+            }
+            if (edge[b] == kEscape) edge[b] = overflow_count((uint32_t)(it[b].cell0 + ie[b]), ovf_key, ovf_val, n_ovf);
+        }
+        __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0): the looked-up counts have arrived when this branch joins the others
+    }
+    // ---- every store of the batch
+#pragma unroll
+    for (int b = 0; b < kBatch; ++b) {
+        const Item &I = it[b];
+        const bool up = I.step > 0;
+        T *dst = out + I.out_off;
+#pragma unroll
+        for (int k = 0; k < kPairsPerLane; ++k) {
+            const int p = t + k * kGatherWG;
+            if (p < pc_[b].pairs) {
+                const T a = pc::out_conv<OUTMODE>(c0[b][k], norm_sum), z = pc::out_conv<OUTMODE>(c1[b][k], norm_sum);
+                T2 v;
+                v.x = up ? a : z; v.y = up ? z : a;
+                store_out(reinterpret_cast<T2 *>(out + pair_slot(I.out_off, I.step, pc_[b], p)), v);
+            }
+        }
+        if (ie[b] >= 0) store_out(dst + (up ? ie[b] : -ie[b]), pc::out_conv<OUTMODE>(edge[b], norm_sum));
     }
 }
 

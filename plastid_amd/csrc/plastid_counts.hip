@@ -3076,8 +3076,8 @@ int count_dense(pc_engine *e, pc_plan *p, const CountCall &c, const StagedFile *
     if (p->n_ditems)
         dispatch_int<0, 1, 2>(c.outmode, [&](auto O) {
             constexpr int o = decltype(O)::value;
-            hipLaunchKernelGGL((pcdense::k_dense_gather<o>), dim3(p->n_ditems), dim3(pcdense::kGatherWG), 0, e->stream, p->d_ditems.p, sf->dense.p,
-                               sf->dovf_key.p, sf->dovf_val.p, sf->dn_ovf, (typename OutT_<o>::type *)p->d_out.p, e->norm_sum);
+            hipLaunchKernelGGL((pcdense::k_dense_gather<o>), dim3((unsigned)pcdense::batches_of(p->n_ditems)), dim3(pcdense::kGatherWG), 0, e->stream, p->d_ditems.p,
+                               (uint32_t)p->n_ditems, sf->dense.p, sf->dovf_key.p, sf->dovf_val.p, sf->dn_ovf, (typename OutT_<o>::type *)p->d_out.p, e->norm_sum);
         });
     PC_TRY(mark(e, 3));
     return mark(e, 4);
