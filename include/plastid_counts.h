@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 17
+#define PC_ABI_VERSION 18
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -638,6 +638,61 @@ int pc_counts_export_timing(pc_engine *e, double *ms6);
  * reading HBM instead of an uploaded vector (int64 -> double is exact for every count a file can hold).  Every argument
  * is checked before anything changes. */
 int pc_track_set_counts(pc_track *t, const char *contig, int strand_slot, int64_t start, pc_plan *p, int64_t elem_off, int64_t n);
+
+/* ---- bigWig FILES (revision 18)
+ * The reference's BigWigReader / BigWigGenomeArray (plastid/readers/bigwig.pyx:109-412, genome_array.py:1114-1320) over
+ * Kent's readers (kent/src/lib/bbiRead.c, bwgQuery.c:155-285, bwgValsOnChrom.c:36-214).  The container -- the 64-byte
+ * header, the chromosome B+ tree, the unzoomed R-tree -- is walked by the host (csrc/bigwig_host.h); the data blocks,
+ * independent zlib streams of a few KiB each (uncompressBufSize > 0) or stored sections, are inflated, checked and
+ * decoded in HBM (csrc/bigwig_kernels.hip.h).  Zoom levels, the total summary and byte-swapped files are not read.
+ * A file that is refused is PC_ERR_ARG with "<path>: bigWig: <what>" -- the file's structure first, then the lowest
+ * (block, item) -- and changes nothing: a wrong magic (bigBed's named), a byte-swapped file, a version below 3, tree
+ * nodes or blocks outside the file, a zlib header that is not CM = 8 without FDICT, a block above 2^28 bytes or an
+ * uncompressBufSize above 2^30 (the inflate kernel counts bits and bytes in 32 bits), a section of unknown type, a section
+ * whose 24 + itemCount x itemsize is not the block's inflated length, an item with end <= start, a chromId outside the
+ * tree, an end beyond its contig's size, a failed Adler-32, a DEFLATE error.
+ *
+ * pc_bigwig_info (host only, no engine): `path`, or `image` / `size` when image is not NULL (path then only names the file in
+ * messages).  out5: [0] contigs, [1] data blocks, [2] uncompressBufSize, [3] version, [4] bytes of the names with their
+ * NULs.  names / sizes (optional: filled when max_contigs and names_bytes suffice): the contigs in the order of
+ * bbiChromList (a depth-first walk of the tree), names NUL-terminated one behind the other.
+ * pc_bigwig_blocks: the block table in index order -- file offset and bytes of every block; nblocks must be out5[1]. */
+int pc_bigwig_info(const char *path, const void *image, int64_t size, int64_t *out5, int max_contigs, char *names, int64_t names_bytes, int64_t *sizes);
+int pc_bigwig_blocks(const char *path, const void *image, int64_t size, int64_t nblocks, int64_t *off, int64_t *bytes);
+/* n independent zlib streams (RFC 1950), stream k the len[k] bytes at image + off[k], each inflated by one wave of the
+ * zlib instantiation of the BGZF inflate kernel into at most `capacity` bytes and checked against its Adler-32.
+ * out: n x capacity bytes, stream k at out + k x capacity; out_len[k]: the bytes it gave (0 with a status); status[k]: 0,
+ * or 1 - 9 and 11 a DEFLATE error (csrc/bam_kernels.hip.h: 7 more than `capacity` bytes, 11 the stream does not end in the
+ * byte before its trailer), 10 the Adler-32, 12 a header that is not CM = 8 without FDICT.  A refused stream is a status,
+ * not an error of the call.  capacity <= 2^30, len[k] <= 2^28. */
+int pc_inflate_zlib(pc_engine *e, const void *image, int64_t n, const int64_t *off, const int64_t *len, int64_t capacity, void *out, int64_t *out_len,
+                    int32_t *status);
+/* The items of a bigWig file ASSIGNED to cells [start, end) of one strand slot, in file order: where items overlap the
+ * last one wins, as in both Kent readers (Kent's writer refuses such files; the semantic is the contract all the same).
+ * Contigs the track does not hold are declared from the chromosome tree at their sizes, in bbiChromList's order, and do
+ * not grow; cells are stored up to the furthest end written.  Meant for a slot that holds zeros (a BigWigReader's track):
+ * on a slot that holds values the items overwrite them.  The bytes that hold the blocks cross PCIe once (through the
+ * page-locked halves when they are large); the blocks inflate into slots of uncompressBufSize bytes rounded to 16. */
+int pc_track_add_bigwig(pc_track *t, const void *image, int64_t size, const char *name, int strand_slot);
+int pc_track_add_bigwig_path(pc_track *t, const char *path, int strand_slot);
+/* the last pc_track_add_bigwig: [0] blocks, [1] blocks inflated on the GPU, [2] items of bedGraph, [3] variableStep and
+ * [4] fixedStep sections, [5] overlapping items (members of clusters of several items, applied in file order), [6] bytes
+ * uploaded, [7] bytes inflated */
+int pc_track_bigwig_stats(pc_track *t, int64_t *out8);
+/* milliseconds of the last pc_track_add_bigwig on the engine's stream: [0] upload, [1] inflate + Adler-32, [2] sections +
+ * items, [3] contigs, storage, sort and apply */
+int pc_track_bigwig_timing(pc_track *t, double *ms4);
+/* BigWigGenomeArray.get (genome_array.py:1171-1217) over the ntrack readers of one strand, all on one engine: element by
+ * element 0.0 + r1 + r2 + ..., in the order of `tracks`.  The segment table is pc_track_gather's, but contig and
+ * strand_slot hold ntrack rows of nseg entries: row k is the segments' contig index and strand slot IN track k (-1: the
+ * track lacks it: zeros).  One launch per track, each adding onto the output in HBM: every track cuts its own items (its
+ * contigs and extents are its own), and the order of the launches is the order of the sum.  normalize 0: none; 1:
+ * v / sum * 1e6 (BigWigGenomeArray, :1212); 2: 1e6 * v / sum (GenomeArray, :1528); `sum` is the caller's. */
+int pc_track_gather_sum(int ntrack, pc_track *const *tracks, int64_t nseg, const int32_t *contig, const int32_t *strand_slot, const int64_t *start,
+                        const int64_t *end, const int64_t *out_off, const int8_t *out_step, int64_t out_elems, int normalize, double sum, double *host_out);
+/* The fixed-tree sum over nrange ranges of cells: positions [start[r], end[r]) of public contig contig[r] on strand_slot[r]
+ * (beyond the extent: zeros; -1: nothing).  The order of the additions depends on the ranges alone. */
+int pc_track_sum_ranges(pc_track *t, int64_t nrange, const int32_t *contig, const int32_t *strand_slot, const int64_t *start, const int64_t *end, double *sum);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ from .map_factories import (CenterMapFactory, FivePrimeMapFactory, FlagFilterFac
                             StratifiedVariableFivePrimeMapFactory, ThreePrimeMapFactory,
                             VariableFivePrimeMapFactory)
 from .genome_array import BAMGenomeArray, DenseGenomeArray  # noqa: F401
-from .track import GenomeArray, WiggleTable, read_wiggle  # noqa: F401
+from .track import (BigWigGenomeArray, BigWigReader, BigWigTable, GenomeArray, WiggleTable, bigwig_info, read_bigwig,  # noqa: F401
+                    read_wiggle)
 
 __version__ = "0.1.0"

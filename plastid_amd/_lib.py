@@ -149,6 +149,15 @@ SIGNATURES = {
     "pc_counts_export_stats": (_int, [_vp, _vp]),
     "pc_counts_export_timing": (_int, [_vp, _vp]),
     "pc_track_set_counts": (_int, [_vp, ctypes.c_char_p, _int, _i64, _vp, _i64, _i64]),
+    "pc_bigwig_info": (_int, [ctypes.c_char_p, _vp, _i64, _vp, _int, _vp, _i64, _vp]),
+    "pc_bigwig_blocks": (_int, [ctypes.c_char_p, _vp, _i64, _i64, _vp, _vp]),
+    "pc_inflate_zlib": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "pc_track_add_bigwig": (_int, [_vp, _vp, _i64, ctypes.c_char_p, _int]),
+    "pc_track_add_bigwig_path": (_int, [_vp, ctypes.c_char_p, _int]),
+    "pc_track_bigwig_stats": (_int, [_vp, _vp]),
+    "pc_track_bigwig_timing": (_int, [_vp, _vp]),
+    "pc_track_gather_sum": (_int, [_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, ctypes.c_double, _vp]),
+    "pc_track_sum_ranges": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double)]),
 }
 
 _lib = None
@@ -158,7 +167,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 
 def load():

@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "bam_host.h"
+#include "bigwig_host.h"
 #include "index_shape.h"
 #include "sam_host.h"
 #include "track_host.h"
@@ -1837,6 +1838,60 @@ int pb_track_writer_stats(void *h, int64_t *out4) {
 int pb_float_repr(const double *v, int64_t n, char *out, uint8_t *len) {
     if (n < 0 || (n > 0 && (!v || !out || !len))) return fail("pb_float_repr: bad arguments");
     for (int64_t k = 0; k < n; ++k) len[k] = (uint8_t)pctrack::float_repr(v[k], out + pctrack::kReprMax * k);
+    return 0;
+}
+
+// ---------------------------------------------------------------- bigWig (bigwig_host.h)
+// A bigWig file read on the host, block by block with zlib: the items Kent's readers apply (bwgQuery.c:155-285), in file
+// order, as columns.  The model of the device import.  NULL (pb_last_error): "<name>: bigWig: <what>".
+static int zlib_raw_inflate(const uint8_t *src, size_t n, uint8_t *dst, size_t cap, size_t &produced) {
+    z_stream zs;
+    std::memset(&zs, 0, sizeof(zs));
+    if (inflateInit2(&zs, -15) != Z_OK) return 1;
+    zs.next_in = const_cast<Bytef *>(src); zs.avail_in = (uInt)n;
+    zs.next_out = dst; zs.avail_out = (uInt)cap;
+    const int rc = inflate(&zs, Z_FINISH);
+    produced = (size_t)zs.total_out;
+    const bool whole = rc == Z_STREAM_END && zs.avail_in == 0;   // (the stream ends with its last byte: the trailer follows)
+    inflateEnd(&zs);
+    return whole ? 0 : 1;
+}
+void *pb_bigwig_read(const void *image, int64_t size, const char *name) {
+    if (size < 0 || (size > 0 && !image)) { fail("pb_bigwig_read: bad arguments"); return nullptr; }
+    pcbw::ItemTable *t = new pcbw::ItemTable();
+    pcbw::read_items((const uint8_t *)image, (uint64_t)size, zlib_raw_inflate, *t);
+    if (t->defect != pcbw::kNoDefect) {
+        fail(pcbw::defect_message(name, t->defect));
+        delete t;
+        return nullptr;
+    }
+    return t;
+}
+void pb_bigwig_close(void *h) { delete static_cast<pcbw::ItemTable *>(h); }
+int64_t pb_bigwig_rows(void *h) { return h ? (int64_t)static_cast<pcbw::ItemTable *>(h)->chrom.size() : -1; }
+int pb_bigwig_nchrom(void *h) { return h ? (int)static_cast<pcbw::ItemTable *>(h)->file.chroms.size() : -1; }
+const char *pb_bigwig_chrom(void *h, int i) { return static_cast<pcbw::ItemTable *>(h)->file.chroms[(size_t)i].name.c_str(); }
+int64_t pb_bigwig_chrom_size(void *h, int i) { return (int64_t)static_cast<pcbw::ItemTable *>(h)->file.chroms[(size_t)i].size; }
+int64_t pb_bigwig_nblocks(void *h) { return h ? (int64_t)static_cast<pcbw::ItemTable *>(h)->file.blocks.size() : -1; }
+int pb_bigwig_fill(void *h, int32_t *chrom, int64_t *start, int64_t *stop, double *value, int32_t *block, int64_t *block_off, int64_t *block_size) {
+    pcbw::ItemTable *t = static_cast<pcbw::ItemTable *>(h);
+    if (!t) return fail("pb_bigwig_fill: NULL handle");
+    const size_t n = t->chrom.size();
+    if (n) {
+        std::memcpy(chrom, t->chrom.data(), n * 4); std::memcpy(start, t->start.data(), n * 8); std::memcpy(stop, t->stop.data(), n * 8);
+        std::memcpy(value, t->value.data(), n * 8); std::memcpy(block, t->block.data(), n * 4);
+    }
+    for (size_t b = 0; b < t->file.blocks.size(); ++b) { block_off[b] = (int64_t)t->file.blocks[b].off; block_size[b] = (int64_t)t->file.blocks[b].size; }
+    return 0;
+}
+// [0] blocks, [1] compressed blocks, [2-4] items of bedGraph / variableStep / fixedStep sections, [5] bytes inflated,
+// [6] uncompressBufSize, [7] version
+int pb_bigwig_stats(void *h, int64_t *out8) {
+    pcbw::ItemTable *t = static_cast<pcbw::ItemTable *>(h);
+    if (!t || !out8) return fail("pb_bigwig_stats: bad arguments");
+    out8[0] = (int64_t)t->file.blocks.size(); out8[1] = t->file.compressed() ? out8[0] : 0;
+    out8[2] = t->by_type[0]; out8[3] = t->by_type[1]; out8[4] = t->by_type[2]; out8[5] = t->bytes_inflated;
+    out8[6] = t->file.uncompress_buf; out8[7] = t->file.version;
     return 0;
 }
 

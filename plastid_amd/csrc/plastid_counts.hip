@@ -3804,3 +3804,4 @@ int pc_read_mapped_reads(pc_engine *e, pc_plan *p, uint32_t *rec, int64_t total)
 #include "bam_decoder.hip.h"
 #include "sam_decoder.hip.h"
 #include "track_decoder.hip.h"
+#include "bigwig_decoder.hip.h"

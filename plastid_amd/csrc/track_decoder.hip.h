@@ -24,6 +24,9 @@ struct pc_track {
     double sum = 0.0;
     int64_t stats[6] = {0, 0, 0, 0, 0, 0};  // lines, yielded, escaped, state records, overlapping lines, growth lines
     double ms[5] = {0, 0, 0, 0, 0};         // upload | line starts | classify + state records | fields | growth + sort + apply
+    // the last pc_track_add_bigwig (bigwig_decoder.hip.h)
+    int64_t bw_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // blocks, compressed blocks, items by type (3), overlapping items, bytes in, bytes inflated
+    double bw_ms[4] = {0, 0, 0, 0};                   // upload | inflate + adler | sections + items | sort + apply
     // the last pc_track_export: its text waits in HBM for pc_track_export_read
     DevBuf<uint8_t> ex_text;
     int64_t ex_bytes = -1;
@@ -282,8 +285,8 @@ int import_births_growth_storage(TrackImport &c) {
     return track_grow_storage(t, t->tab.plan_storage(c.strand, c.furthest), st);
 }
 
-// Phase 6: sort by (contig, start), clusters, fills.
-int import_sort_and_apply(TrackImport &c) {
+// Phase 6: sort by (contig, start), clusters, fills.  kAssign: the lines write their values (bigwig_decoder.hip.h).
+template <bool kAssign = false> int import_sort_and_apply(TrackImport &c) {
     hipStream_t st = c.st;
     pc_track *t = c.t;
     const int64_t n = c.n, nv = c.ncontig > 0 ? (int64_t)c.cnt.n_valid : 0;
@@ -311,19 +314,19 @@ int import_sort_and_apply(TrackImport &c) {
     hipLaunchKernelGGL(tk::k_track_clusters, dim3(gv), dim3(256), 0, st, c.d_key2.p, c.d_prev_end.p, nv, c.d_head.p);
     HIP_TRY(hipGetLastError());
     PC_TRY(cub_run_sized(c.d_tmp, b_heads, heads));
-    hipLaunchKernelGGL(tk::k_track_fill_short, dim3(gv), dim3(256), 0, st, c.d_idx2.p, c.d_head.p, nv, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p, c.d_long.p,
+    hipLaunchKernelGGL(tk::k_track_fill_short<kAssign>, dim3(gv), dim3(256), 0, st, c.d_idx2.p, c.d_head.p, nv, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p, c.d_long.p,
                        c.d_multi.p, c.d_cnt.p);
     HIP_TRY(hipGetLastError());
     PC_TRY(c.read_counters());
     t->stats[4] = c.cnt.n_multi;
     if (c.cnt.n_long) {
-        hipLaunchKernelGGL(tk::k_track_fill, dim3(c.cnt.n_long), dim3(256), 0, st, c.d_long.p, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p);
+        hipLaunchKernelGGL(tk::k_track_fill<kAssign>, dim3(c.cnt.n_long), dim3(256), 0, st, c.d_long.p, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p);
         HIP_TRY(hipGetLastError());
     }
     if (c.cnt.n_multi) {
         nm = c.cnt.n_multi;
         PC_TRY(cub_run_sized(c.d_tmp, b_multi, sort_multi));
-        hipLaunchKernelGGL(tk::k_track_fill_ordered, dim3(c.cnt.n_multi), dim3(256), 0, st, c.d_multi2.p, c.cnt.n_multi, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p);
+        hipLaunchKernelGGL(tk::k_track_fill_ordered<kAssign>, dim3(c.cnt.n_multi), dim3(256), 0, st, c.d_multi2.p, c.cnt.n_multi, c.d_line.p, c.d_contig_of.p, c.d_off.p, t->cells.p);
         HIP_TRY(hipGetLastError());
     }
     return PC_OK;

@@ -216,6 +216,10 @@ __global__ __launch_bounds__(256) void k_track_clusters(const uint64_t *__restri
 
 // Singleton clusters: short lines are filled here, long ones listed; lines of larger clusters are listed as
 // (cluster << 32 | line) keys for the ordered pass.  cells: the strand's cells of every contig, cell_off[c] its first.
+// kAssign (the three fill kernels; revision 18, the items of a bigWig file): a line WRITES its value instead of adding it --
+// a singleton line as it is, and in a cluster every cell takes the value of the last line in file order that covers it
+// (Kent's readers assign in file order: bwgQuery.c:155-285).  kAssign = false is the add of revisions 15 - 17.
+template <bool kAssign>
 __global__ __launch_bounds__(256) void k_track_fill_short(const uint32_t *__restrict__ idx, const int32_t *__restrict__ head, int64_t nv,
                                                           const LineRec *__restrict__ recs, const int32_t *__restrict__ contig_of,
                                                           const int64_t *__restrict__ cell_off, double *__restrict__ cells,
@@ -229,10 +233,11 @@ __global__ __launch_bounds__(256) void k_track_fill_short(const uint32_t *__rest
     const int64_t n = r.stop - r.start;
     if (n > kShortLen) { long_lines[atomicAdd(&cnt->n_long, 1u)] = i; return; }
     double *dst = cells + cell_off[contig_of[i]] + r.start;
-    for (int64_t p = 0; p < n; ++p) dst[p] = dst[p] + r.value;
+    for (int64_t p = 0; p < n; ++p) dst[p] = kAssign ? r.value : dst[p] + r.value;
 }
 
 // one workgroup per long singleton line, item by item (2 048 positions: 256 lanes x 8)
+template <bool kAssign>
 __global__ __launch_bounds__(256) void k_track_fill(const uint32_t *__restrict__ long_lines, const LineRec *__restrict__ recs, const int32_t *__restrict__ contig_of,
                                                     const int64_t *__restrict__ cell_off, double *__restrict__ cells) {
     const uint32_t i = long_lines[blockIdx.x];
@@ -243,7 +248,7 @@ __global__ __launch_bounds__(256) void k_track_fill(const uint32_t *__restrict__
 #pragma unroll
         for (int k = 0; k < pcdense::kPerLane; ++k) {
             const int64_t p = a + threadIdx.x + k * 256;
-            if (p < n) dst[p] = dst[p] + r.value;
+            if (p < n) dst[p] = kAssign ? r.value : dst[p] + r.value;
         }
 }
 
@@ -251,6 +256,7 @@ __global__ __launch_bounds__(256) void k_track_fill(const uint32_t *__restrict__
 // file order.  One workgroup per entry; the one at a cluster's first entry serves the cluster: every lane takes cells of
 // the cluster's extent and adds the lines that cover the cell in file order.  Quadratic in the cluster (cells x lines),
 // exact for any overlap.
+template <bool kAssign>
 __global__ __launch_bounds__(256) void k_track_fill_ordered(const uint64_t *__restrict__ multi_keys, uint32_t nm, const LineRec *__restrict__ recs,
                                                             const int32_t *__restrict__ contig_of, const int64_t *__restrict__ cell_off,
                                                             double *__restrict__ cells) {
@@ -270,7 +276,7 @@ __global__ __launch_bounds__(256) void k_track_fill_ordered(const uint64_t *__re
         double v = base[p];
         for (uint32_t k = k0; k < k1; ++k) {
             const LineRec r = recs[(uint32_t)multi_keys[k]];
-            if (p >= r.start && p < r.stop) v = v + r.value;
+            if (p >= r.start && p < r.stop) v = kAssign ? r.value : v + r.value;
         }
         base[p] = v;
     }

@@ -11,8 +11,12 @@ is formatted by HIP kernels.  :func:`write_bedgraph` / :func:`write_variable_ste
 the reference's ``WiggleReader`` (plastid/readers/wiggle.py:43-174) on the host, built from the same
 ``csrc/track_host.h`` the kernels compile: the model of the device import, and the way to read a track without a GPU.
 
-Not here: ``add_from_bowtie``, ``plot``, ``SparseGenomeArray``, BigWig.  Deviations from the
-reference (``__eq__``, the ``all`` mode over differing contig sets, operand order) are listed in DESIGN.md section 8.
+:class:`BigWigReader` / :class:`BigWigGenomeArray` are the reference's classes of those names (plastid/readers/bigwig.pyx:109-412,
+genome_array.py:1114-1320) over bigWig files whose blocks are inflated and decoded on the GPU (``csrc/bigwig_kernels.hip.h``);
+:func:`read_bigwig` is the same reader on the host (``csrc/bigwig_host.h``): the model of the device import.
+
+Not here: ``add_from_bowtie``, ``plot``, ``SparseGenomeArray``.  Deviations from the
+reference (``__eq__``, the ``all`` mode over differing contig sets, operand order, the bigWig classes) are listed in DESIGN.md section 8.
 """
 import ctypes
 import io
@@ -619,6 +623,397 @@ class GenomeArray(object):
         finally:
             self._normalize = norm
         return host
+
+
+# ---------------------------------------------------------------- bigWig
+WARN_CHROM_NOT_FOUND = "No data for chromosome '%s' in file '%s'."      # (plastid/readers/bbifile.pyx:25)
+
+
+def _image_of(path_or_bytes):
+    """``(path, buffer, size)`` for the entry points that take a path or an image."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data = bytes(path_or_bytes)
+        return None, ctypes.create_string_buffer(data, len(data)) if data else ctypes.create_string_buffer(1), len(data)
+    path = os.fspath(path_or_bytes)
+    if not os.path.isfile(path):
+        raise IOError("No such file: %r" % (path,))
+    return os.fsencode(path), None, 0
+
+
+def bigwig_info(path_or_bytes):
+    """Header, contigs and block table of a bigWig file (a path, or its bytes) without a GPU (``pc_bigwig_info`` /
+    ``pc_bigwig_blocks``): ``chroms`` -- an ``OrderedDict`` name -> size in the order of Kent's ``bbiChromList`` --
+    ``blocks`` (file offset, bytes) in index order, ``uncompress_buf_size``, ``version``.  ``ValueError("<path>: bigWig:
+    <what>")`` for a file that is refused."""
+    L = _lib.load()
+    path, buf, size = _image_of(path_or_bytes)
+    image = ctypes.cast(buf, ctypes.c_void_p) if buf is not None else None
+    out = np.zeros(5, np.int64)
+    check(L.pc_bigwig_info(path, image, size, out.ctypes.data, 0, None, 0, None), "pc_bigwig_info")
+    nchrom, nblock = int(out[0]), int(out[1])
+    names = ctypes.create_string_buffer(max(int(out[4]), 1))
+    sizes = np.zeros(max(nchrom, 1), np.int64)
+    check(L.pc_bigwig_info(path, image, size, out.ctypes.data, nchrom, names, int(out[4]), sizes.ctypes.data), "pc_bigwig_info")
+    parts = names.raw[:int(out[4])].split(b"\0")[:nchrom]
+    off, nbytes = np.zeros(max(nblock, 1), np.int64), np.zeros(max(nblock, 1), np.int64)
+    check(L.pc_bigwig_blocks(path, image, size, nblock, off.ctypes.data, nbytes.ctypes.data), "pc_bigwig_blocks")
+    return {"chroms": OrderedDict((p.decode("utf-8", "replace"), int(s)) for p, s in zip(parts, sizes)),
+            "blocks": [(int(a), int(b)) for a, b in zip(off[:nblock], nbytes[:nblock])],
+            "uncompress_buf_size": int(out[2]), "version": int(out[3])}
+
+
+class BigWigTable(object):
+    """What :func:`read_bigwig` returns: one row per item in file order -- the order Kent's readers apply them in -- as
+    columns.  ``chrom`` indexes ``names`` (``bbiChromList`` order; ``lengths``: their sizes); ``block``: the data block of
+    the row; ``block_off`` / ``block_size``: the block table; ``stats``: blocks, compressed blocks, items by section
+    type, bytes inflated, ``uncompressBufSize``, version."""
+
+    def __init__(self, names, lengths, chrom, start, stop, value, block, block_off, block_size, stats):
+        self.names, self.lengths, self.chrom, self.start, self.stop, self.value = names, lengths, chrom, start, stop, value
+        self.block, self.block_off, self.block_size, self.stats = block, block_off, block_size, stats
+
+    def __len__(self):
+        return len(self.chrom)
+
+    def tuples(self):
+        return [(self.names[c], int(a), int(b), float(v)) for c, a, b, v in zip(self.chrom, self.start, self.stop, self.value)]
+
+    def chromosome_counts(self, chrom):
+        """Kent's ``bigWigValsOnChromFetchData`` over the table: the contig's size in float64, the items assigned in file order."""
+        i = self.names.index(chrom)
+        out = np.zeros(self.lengths[i], np.float64)
+        for k in np.flatnonzero(self.chrom == i):
+            out[self.start[k]:self.stop[k]] = self.value[k]
+        return out
+
+
+def read_bigwig(path_or_bytes):
+    """Read a bigWig file on the host, one thread, zlib (``pb_bigwig_read``; the container and the section decoders are
+    ``csrc/bigwig_host.h``, which the kernels compile too): the model of the device import, and the way to read a bigWig
+    without a GPU.  ``ValueError("<path>: bigWig: <what>")`` for a file that is refused."""
+    from .bam import _load
+    L = _load()
+    if not hasattr(L.pb_bigwig_read, "_bound"):
+        vp = ctypes.c_void_p
+        L.pb_bigwig_read.restype = vp
+        L.pb_bigwig_read.argtypes = [vp, ctypes.c_int64, ctypes.c_char_p]
+        L.pb_bigwig_close.argtypes = [vp]
+        for f in (L.pb_bigwig_rows, L.pb_bigwig_nblocks):
+            f.restype, f.argtypes = ctypes.c_int64, [vp]
+        L.pb_bigwig_nchrom.argtypes = [vp]
+        L.pb_bigwig_chrom.restype = ctypes.c_char_p
+        L.pb_bigwig_chrom.argtypes = [vp, ctypes.c_int]
+        L.pb_bigwig_chrom_size.restype = ctypes.c_int64
+        L.pb_bigwig_chrom_size.argtypes = [vp, ctypes.c_int]
+        L.pb_bigwig_fill.argtypes = [vp] * 8
+        L.pb_bigwig_stats.argtypes = [vp, vp]
+        L.pb_bigwig_read._bound = True
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data, name = bytes(path_or_bytes), "<memory>"
+    else:
+        data, name = _text_of(path_or_bytes)
+    buf = ctypes.create_string_buffer(data, len(data)) if data else None
+    h = L.pb_bigwig_read(ctypes.cast(buf, ctypes.c_void_p) if buf is not None else None, len(data), os.fsencode(name))
+    if not h:
+        raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    try:
+        n, nb = int(L.pb_bigwig_rows(h)), int(L.pb_bigwig_nblocks(h))
+        nchrom = L.pb_bigwig_nchrom(h)
+        names = [L.pb_bigwig_chrom(h, i).decode("utf-8", "replace") for i in range(nchrom)]
+        lengths = [int(L.pb_bigwig_chrom_size(h, i)) for i in range(nchrom)]
+        chrom, start, stop = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        value, block = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        block_off, block_size = np.zeros(nb, np.int64), np.zeros(nb, np.int64)
+        if L.pb_bigwig_fill(h, *[a.ctypes.data for a in (chrom, start, stop, value, block, block_off, block_size)]) != 0:
+            raise ValueError(L.pb_last_error().decode())
+        stats = np.zeros(8, np.int64)
+        L.pb_bigwig_stats(h, stats.ctypes.data)
+    finally:
+        L.pb_bigwig_close(h)
+    keys = ("blocks", "compressed_blocks", "bedgraph_items", "variable_step_items", "fixed_step_items", "bytes_inflated", "uncompress_buf_size", "version")
+    return BigWigTable(names, lengths, chrom, start, stop, value, block, block_off, block_size, dict(zip(keys, (int(x) for x in stats))))
+
+
+def sum_ranges(lengths):
+    """The positions ``BigWigReader.sum()`` adds, per contig in ``chroms`` order: the reference's position counter is set
+    to 0 once, in front of the loop over the contigs (plastid/readers/bigwig.pyx:273-296), so contig k gives only its
+    positions from the greatest length of the contigs in front of it on.  ``[(start, end)]``, empty ranges included."""
+    out, i = [], 0
+    for n in lengths:
+        out.append((min(i, n), n))
+        i = max(i, n)
+    return out
+
+
+def inflate_zlib(engine, streams, capacity):
+    """``pc_inflate_zlib``: every zlib stream of `streams` (bytes) inflated by one wave on `engine` into at most `capacity`
+    bytes.  Returns ``[(payload bytes, status)]``; status 0, or why the stream was refused (include/plastid_counts.h)."""
+    n = len(streams)
+    image = b"".join(streams)
+    lens = np.array([len(s) for s in streams], np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.int64) if n else np.zeros(0, np.int64)
+    buf = ctypes.create_string_buffer(image, len(image)) if image else ctypes.create_string_buffer(1)
+    out = np.zeros(max(n * int(capacity), 1), np.uint8)
+    out_len, status = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int32)
+    check(_lib.load().pc_inflate_zlib(engine._h, ctypes.cast(buf, ctypes.c_void_p), n, offs.ctypes.data, lens.ctypes.data, int(capacity),
+                                      out.ctypes.data, out_len.ctypes.data, status.ctypes.data), "pc_inflate_zlib")
+    return [(out[k * int(capacity):k * int(capacity) + int(out_len[k])].tobytes(), int(status[k])) for k in range(n)]
+
+
+class BigWigReader(object):
+    """The reference's ``BigWigReader`` (plastid/readers/bigwig.pyx:109-412) with the file's values in HBM: the data blocks
+    are inflated, checked and decoded on the GPU once, at construction, into a one-strand count track (float64 cells per
+    contig up to the furthest end written); every read is a gather.  `maxmem` is accepted and ignored; `engine`: an
+    :class:`~plastid_amd.engine.Engine` to share (default: one of its own on GPU 0).  ``fill`` is fixed at 0.0, as in the
+    reference, whose setter is commented out.  Not here: ``__iter__`` / ``BigWigIterator``, ``summarize``, remote files.
+    ``ValueError("<path>: bigWig: <what>")`` for a file that is refused (README: byte-swapped files are)."""
+
+    def __init__(self, filename, maxmem=0, engine=None, **kwargs):
+        self.filename = os.fspath(filename)
+        if not os.path.isfile(self.filename):
+            raise IOError("No such file: %r" % (self.filename,))
+        self.fill = 0.0
+        self._maxmem = maxmem
+        self._sum = None
+        self._ga = GenomeArray(strands=(".",), engine=engine)
+        try:
+            check(self._ga._lib.pc_track_add_bigwig_path(self._ga._h, os.fsencode(self.filename), 0), "pc_track_add_bigwig_path")
+        except Exception:
+            self._ga.close()
+            raise
+        self._engine = self._ga._engine
+        self._chroms = self._ga.lengths()
+        self._index = {c: i for i, c in enumerate(self._chroms)}
+
+    def close(self):
+        self._ga.close()
+
+    @property
+    def chroms(self):
+        """``{name: size}`` in the order of Kent's ``bbiChromList`` (bbifile.pyx:211-237)."""
+        return OrderedDict(self._chroms)
+
+    def import_stats(self):
+        """Of the import: blocks, blocks inflated on the GPU, items of bedGraph / variableStep / fixedStep sections,
+        overlapping items, bytes uploaded, bytes inflated."""
+        out = np.zeros(8, np.int64)
+        check(self._ga._lib.pc_track_bigwig_stats(self._ga._h, out.ctypes.data))
+        keys = ("blocks", "inflated_blocks", "bedgraph_items", "variable_step_items", "fixed_step_items", "overlapping", "bytes_in", "bytes_inflated")
+        return dict(zip(keys, (int(x) for x in out)))
+
+    def import_timing(self):
+        """Milliseconds of the import: upload, inflate + Adler-32, sections + items, sort + apply."""
+        out = np.zeros(4, np.float64)
+        check(self._ga._lib.pc_track_bigwig_timing(self._ga._h, out.ctypes.data))
+        return dict(zip(("upload", "inflate_adler", "sections_items", "sort_apply"), (float(x) for x in out)))
+
+    def get(self, roi, roi_order=True, fill=np.nan):
+        """Values over a |GenomicSegment| (a |SegmentChain| goes to ``roi.get_counts(self)``), 0.0 where nothing covers;
+        a contig that is not in the file gives zeros and one ``DataWarning``; reversed for ``'-'`` when `roi_order`.
+        `fill` other than NaN or 0.0 raises ``NotImplementedError``: it needs a bitmap of the covered positions, which the
+        import does not build (the reference's own non-zero fill is commented out for ``get_chromosome_counts``)."""
+        if not (np.isnan(fill) or fill == 0.0):
+            raise NotImplementedError("a fill other than 0.0 needs the coverage bitmap, which is not built")
+        if isinstance(roi, SegmentChain):
+            return roi.get_counts(self)
+        n = max(int(roi.end) - int(roi.start), 0)
+        if roi.chrom not in self._index:
+            warn(WARN_CHROM_NOT_FOUND % (roi.chrom, self.filename), DataWarning)
+            return np.zeros(n, np.float64)
+        rev = roi_order is True and roi.strand == "-"
+        return self._ga._gather([self._index[roi.chrom]], [0], [roi.start], [roi.start + n], [n - 1 if rev else 0], [-1 if rev else 1], n)
+
+    def __getitem__(self, roi):
+        return self.get(roi)
+
+    def get_chromosome_counts(self, chrom):
+        """The whole contig at its size in the chromosome tree, zeros where no data; an unknown contig warns and gives
+        ``numpy.array(0, dtype=float)`` (bigwig.pyx:314-412)."""
+        if chrom not in self._index:
+            warn(WARN_CHROM_NOT_FOUND % (chrom, self.filename), DataWarning)
+            warn("Could not retrieve data for chrom '%s' from file '%s'." % (chrom, self.filename), DataWarning)
+            return np.array(0, dtype=float)
+        n = self._chroms[chrom]
+        return self._ga._gather([self._index[chrom]], [0], [0], [n], [0], [1], n)
+
+    def sum(self):
+        """The reference's sum (bigwig.pyx:265-302): over the positions :func:`sum_ranges` lists -- its position counter
+        is never reset between contigs -- by a fixed-tree reduction on the device, cached."""
+        if self._sum is None:
+            warn("Summing over a large BigWig file can take a while.", DataWarning)
+            ranges = sum_ranges(list(self._chroms.values()))
+            n = len(ranges)
+            contig, slot = np.arange(n, dtype=np.int32), np.zeros(n, np.int32)
+            start, end = np.array([a for a, _ in ranges], np.int64), np.array([b for _, b in ranges], np.int64)
+            out = ctypes.c_double()
+            check(self._ga._lib.pc_track_sum_ranges(self._ga._h, n, contig.ctypes.data, slot.ctypes.data, start.ctypes.data, end.ctypes.data,
+                                                    ctypes.byref(out)), "pc_track_sum_ranges")
+            self._sum = float(out.value)
+        return self._sum
+
+
+class BigWigGenomeArray(object):
+    """The reference's ``BigWigGenomeArray`` (genome_array.py:1114-1320) over device-resident :class:`BigWigReader` s on one
+    engine.  ``get`` / ``get_counts_batch`` add the readers of a strand in their order, ``0.0 + r1 + r2 + ...`` per element,
+    one accumulating launch per reader; normalisation is ``v / sum * 1e6`` (:1212; not ``GenomeArray``'s order)."""
+
+    def __init__(self, maxmem=0, engine=None, **kwargs):
+        from .engine import Engine
+        self._strand_dict = OrderedDict()
+        self._normalize = False
+        self._chromset = None
+        self._sum = None
+        self._lengths = None
+        self._strands = []
+        self._maxmem = maxmem
+        self.fill = 0.0
+        self._own_engine = engine is None
+        self._engine = Engine(0) if engine is None else engine
+
+    def close(self):
+        for readers in self._strand_dict.values():
+            for bw in readers:
+                bw.close()
+        self._strand_dict = OrderedDict()
+        if self._own_engine:
+            self._engine.close()
+
+    def add_from_bigwig(self, filename, strand):
+        """Append a reader of `filename` to `strand`'s list; the cached chroms, lengths and sum are dropped (:1271-1292)."""
+        bw = BigWigReader(filename, maxmem=self._maxmem, engine=self._engine)
+        self._chromset = None
+        self._lengths = None
+        self._sum = None
+        self._strand_dict.setdefault(strand, []).append(bw)
+        self._strands = sorted(self._strand_dict.keys())
+
+    def _readers(self):
+        return [bw for readers in self._strand_dict.values() for bw in readers]
+
+    def strands(self):
+        return self._strands
+
+    def chroms(self):
+        if self._chromset is None:
+            self._chromset = set(c for bw in self._readers() for c in bw.chroms)
+        return self._chromset
+
+    def keys(self):
+        return self.chroms()
+
+    def __contains__(self, chrom):
+        return chrom in self.chroms()
+
+    def __len__(self):
+        return len(self._strands) * sum(self.lengths().values())
+
+    def lengths(self):
+        if self._lengths is None:
+            lengths = {}
+            for bw in self._readers():
+                for k, v in bw.chroms.items():
+                    lengths[k] = max(lengths.get(k, 0), v)
+            self._lengths = lengths
+        return self._lengths
+
+    def reset_sum(self):
+        my_sum = 0
+        for bw in self._readers():
+            my_sum += bw.sum()
+        self._sum = my_sum
+        return my_sum
+
+    def set_sum(self, val):
+        self._sum = val
+
+    def sum(self):
+        if self._sum is None:
+            self.reset_sum()
+        return self._sum
+
+    def set_normalize(self, value=True):
+        assert value in (True, False)
+        self._normalize = value
+
+    def _gather(self, strand, chroms, start, end, out_off, out_step, total):
+        """The readers of `strand` over a segment table (``chroms``: the segments' contig names), added in reader order."""
+        out = np.zeros(int(total), np.float64)
+        readers = self._strand_dict.get(strand)
+        if readers is None:
+            warn("Strand '%s' not in BigWigGenomeArray (has %s)." % (strand, ", ".join(self._strand_dict.keys())), DataWarning)
+            readers = []
+        for bw in readers:
+            for c in OrderedDict.fromkeys(chroms):
+                if c not in bw._index:
+                    warn(WARN_CHROM_NOT_FOUND % (c, bw.filename), DataWarning)
+        norm = 1 if self._normalize is True else 0
+        total_sum = float(self.sum()) if norm else 1.0
+        if total == 0:
+            return out
+        nseg, ntrack = len(chroms), len(readers)
+        contig = np.array([[bw._index.get(c, -1) for c in chroms] for bw in readers], np.int32).reshape(ntrack, nseg)
+        slot = np.zeros((ntrack, nseg), np.int32)
+        handles = (ctypes.c_void_p * max(ntrack, 1))(*[bw._ga._h for bw in readers])
+        arrs = (np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64), np.ascontiguousarray(out_off, np.int64),
+                np.ascontiguousarray(out_step, np.int8))
+        check(_lib.load().pc_track_gather_sum(ntrack, handles, nseg, contig.ctypes.data, slot.ctypes.data, *[a.ctypes.data for a in arrs],
+                                              int(total), norm, total_sum, out.ctypes.data), "pc_track_gather_sum")
+        return out
+
+    def get(self, roi, roi_order=True):
+        """Values over a |GenomicSegment| (or a |SegmentChain|): ``zeros(len)`` plus every reader of the strand in order; a
+        strand the array lacks gives zeros and a ``DataWarning`` naming the strands it has; then ``v / sum * 1e6`` when
+        normalising, then the ``'-'`` reversal (:1171-1217)."""
+        if isinstance(roi, SegmentChain):
+            return roi.get_counts(self)
+        n = max(int(roi.end) - int(roi.start), 0)
+        rev = roi_order is True and roi.strand == "-"
+        return self._gather(roi.strand, [roi.chrom], [roi.start], [roi.start + n], [n - 1 if rev else 0], [-1 if rev else 1], n)
+
+    def __getitem__(self, roi):
+        return self.get(roi, roi_order=True)
+
+    def _get_chain_counts(self, chain, stranded=True):
+        return self.get_counts_batch([chain], stranded=stranded)[0]
+
+    def get_counts_batch(self, chains, stranded=True):
+        """Many |SegmentChains|: a list of float64 arrays, each what ``chain.get_counts(self, stranded)`` returns.  The
+        chains of one strand share one call (one launch per reader of that strand)."""
+        from .engine import chain_layout
+        out = [None] * len(chains)
+        by_strand = OrderedDict()
+        for ci, c in enumerate(chains):
+            by_strand.setdefault(c.strand, []).append(ci)
+        for strand, which in by_strand.items():
+            segs = [[(s.start, s.end) for s in chains[ci]] for ci in which]
+            seg_chain, out_off, out_step, _, chain_base, chain_len, total = chain_layout(segs, [strand] * len(which), rows=1, stranded=stranded is True)
+            flat = [se for chain_segs in segs for se in chain_segs]
+            vec = self._gather(strand, [chains[which[k]].chrom for k in seg_chain], [s for s, _ in flat], [e for _, e in flat], out_off, out_step, total)
+            for k, ci in enumerate(which):
+                out[ci] = vec[chain_base[k]:chain_base[k] + chain_len[k]]
+        return out
+
+    def to_genome_array(self):
+        """A device :class:`GenomeArray` on the same engine (:1304-1320): every contig at ``lengths()``, every reader added
+        onto its strand in order by ``pc_track_combine``, device to device -- no cell visits the host.  The reference fills
+        its array through ``__setitem__`` over whole contigs, and the first write that ends at a contig's length grows the
+        contig: every contig of the result reports 10000 more than ``lengths()``.  (Where two readers give one contig
+        different sizes the reference fails on the shapes; here the shorter one is padded with zeros.)"""
+        strands = list(self._strands)
+        acc = GenomeArray(chr_lengths=self.lengths(), strands=strands, engine=self._engine)
+        pad = 10000
+        mine = np.arange(len(strands), dtype=np.int32)
+        for strand in strands:
+            for bw in self._strand_dict.get(strand, []):
+                theirs = np.array([0 if s == strand else -1 for s in strands], np.int32)
+                out = ctypes.c_void_p()
+                check(acc._lib.pc_track_combine(acc._h, bw._ga._h, 0.0, 0, 1, pad, len(strands), mine.ctypes.data, theirs.ctypes.data, ctypes.byref(out)),
+                      "pc_track_combine")
+                pad = 0
+                nxt = GenomeArray._wrap(out, strands, acc.min_chr_size, self._engine)
+                acc._release(False)
+                acc = nxt
+        return acc
 
 
 def __getattr__(name):
