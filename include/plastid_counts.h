@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 18
+#define PC_ABI_VERSION 19
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -693,6 +693,44 @@ int pc_track_gather_sum(int ntrack, pc_track *const *tracks, int64_t nseg, const
 /* The fixed-tree sum over nrange ranges of cells: positions [start[r], end[r]) of public contig contig[r] on strand_slot[r]
  * (beyond the extent: zeros; -1: nothing).  The order of the additions depends on the ranges alone. */
 int pc_track_sum_ranges(pc_track *t, int64_t nrange, const int32_t *contig, const int32_t *strand_slot, const int64_t *start, const int64_t *end, double *sum);
+
+/* The twin of pc_inflate_zlib (revision 19): n independent inputs, input k the len[k] <= 24 600 bytes at image + off[k], each
+ * encoded by one workgroup of k_zlib_deflate (csrc/deflate_kernels.hip.h) into one zlib stream (RFC 1950: 78 01, one
+ * DEFLATE block -- LZ77 matches of 4 .. 258 bytes under the fixed Huffman codes, or a stored block when that is not
+ * smaller -- and the Adler-32).  The bytes are those of the host model (csrc/deflate_host.h, pb_deflate_zlib of the host
+ * library), a pure function of the input.  out: the streams back to back, stream k the out_len[k] <= len[k] + 11 bytes at
+ * out + out_off[k].  PC_ERR_ARG: an input above 24 600 bytes, out_capacity below the sum of len[k] + 11. */
+int pc_deflate_zlib(pc_engine *e, const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off,
+                    int64_t *out_len);
+
+/* One strand slot of a track as a bigWig file (revision 19; csrc/bigwig_writer.hip.h, the container: csrc/bigwig_write_host.h).
+ * A cell is written iff its value != 0.0 (NaN is, -0.0 is not); neighbouring written cells of a contig form one item while
+ * their float64 values compare equal; the value is cast to float32 afterwards.  Contigs stand in the sorted order of their
+ * names, every contig of the track is in the chromosome tree at max(length, cells stored); every items_per_slot items of
+ * a contig make one bedGraph section; block_size is the fan-out of both trees; compress: every section through
+ * k_zlib_deflate (uncompressBufSize: the largest raw section), else stored (0).  Little-endian, version 4, no zoom levels;
+ * the total summary stands at offset 64 when the file has items.  Items, sections, summary and blocks are built in HBM;
+ * the section table comes back, the host lays out offsets and trees, and the blocks cross PCIe once (through the transfer
+ * ring when they are large).  *bytes: the size of the file, which waits on the host for pc_track_export_bigwig_read.
+ * PC_ERR_ARG, before anything is built: items_per_slot outside 1 .. 2048, block_size outside 2 .. 65535, a contig of 2^32
+ * positions or more, a strand of 2^31 - 1 cells or more (it could hold 2^31 items).  The file is what the host writer
+ * (pb_bigwig_write_* of the host library) gives for the same cells, byte for byte, but for the rounding of the
+ * summary's two sums, which are added in a fixed tree here and serially there. */
+int pc_track_export_bigwig(pc_track *t, int strand_slot, int64_t items_per_slot, int64_t block_size, int compress, int64_t *bytes);
+/* The reported length of a contig the track holds becomes `length`: what pc_track_contig_length gives and what a later
+ * write grows from.  The cells stay as they are.  For a track filled through pc_track_set_counts over whole contigs, which
+ * grows a contig written up to its end by the reference's rule: the exporter of a BAMGenomeArray puts the alignment
+ * file's lengths back before it writes the chromosome tree.  PC_ERR_ARG: no such contig. */
+int pc_track_set_length(pc_track *t, const char *name, int64_t length);
+/* copies the file of the last pc_track_export_bigwig out (`bytes` as it reported) and frees it */
+int pc_track_export_bigwig_read(pc_track *t, void *dst, int64_t bytes);
+/* the last pc_track_export_bigwig: [0] contigs, [1] items, [2] sections, [3] raw bytes of the sections, [4] bytes of the
+ * blocks in the file, [5] sections that fell back to a stored DEFLATE block */
+int pc_track_bigwig_export_stats(pc_track *t, int64_t *out6);
+/* milliseconds of the last pc_track_export_bigwig: [0] item heads, their sum and the items per contig, [1] items, section
+ * headers and the summary, [2] deflate and Adler-32, [3] sizes and compaction (on the engine's stream), [4] read-back,
+ * [5] host layout (wall clock) */
+int pc_track_bigwig_export_timing(pc_track *t, double *ms6);
 
 #ifdef __cplusplus
 }

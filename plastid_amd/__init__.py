@@ -13,6 +13,6 @@ from .map_factories import (CenterMapFactory, FivePrimeMapFactory, FlagFilterFac
                             VariableFivePrimeMapFactory)
 from .genome_array import BAMGenomeArray, DenseGenomeArray  # noqa: F401
 from .track import (BigWigGenomeArray, BigWigReader, BigWigTable, GenomeArray, WiggleTable, bigwig_info, read_bigwig,  # noqa: F401
-                    read_wiggle)
+                    read_wiggle, write_bigwig)
 
 __version__ = "0.1.0"

@@ -35,6 +35,8 @@
 
 #include "bam_host.h"
 #include "bigwig_host.h"
+#include "bigwig_write_host.h"
+#include "deflate_host.h"
 #include "index_shape.h"
 #include "sam_host.h"
 #include "track_host.h"
@@ -1892,6 +1894,59 @@ int pb_bigwig_stats(void *h, int64_t *out8) {
     out8[0] = (int64_t)t->file.blocks.size(); out8[1] = t->file.compressed() ? out8[0] : 0;
     out8[2] = t->by_type[0]; out8[3] = t->by_type[1]; out8[4] = t->by_type[2]; out8[5] = t->bytes_inflated;
     out8[6] = t->file.uncompress_buf; out8[7] = t->file.version;
+    return 0;
+}
+
+// ---------------------------------------------------------------- zlib encoder and bigWig writer (deflate_host.h, bigwig_write_host.h)
+// pb_deflate_zlib: pc_deflate_zlib without the engine -- the model encoder over n inputs, the streams back to back.
+int pb_deflate_zlib(const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off, int64_t *out_len) {
+    if (n < 0 || out_capacity < 0 || (n > 0 && (!off || !len || !out || !out_off || !out_len))) return fail("pb_deflate_zlib: bad arguments");
+    int64_t need = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        if (off[k] < 0 || len[k] < 0 || len[k] > (int64_t)pcdeflate::kMaxInput) return fail("pb_deflate_zlib: input " + std::to_string(k) + " lies below 0 or holds more than 24600 bytes");
+        if (len[k] > 0 && !image) return fail("pb_deflate_zlib: bad arguments");
+        need += len[k] + (int64_t)pcdeflate::kStreamOverhead;
+    }
+    if (out_capacity < need) return fail("pb_deflate_zlib: out_capacity below the " + std::to_string(need) + " bytes the streams may take");
+    std::vector<uint8_t> stream;
+    int64_t at = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        stream.clear();
+        pcdeflate::encode((const uint8_t *)image + off[k], (uint32_t)len[k], stream);
+        std::memcpy((uint8_t *)out + at, stream.data(), stream.size());
+        out_off[k] = at; out_len[k] = (int64_t)stream.size();
+        at += (int64_t)stream.size();
+    }
+    return 0;
+}
+
+// The serial bigWig writer: open, one add per contig (any order), finish, then the image and the statistics.
+void *pb_bigwig_write_open(int64_t items_per_slot, int64_t block_size, int compress) {
+    const std::string bad = pcbww::check_params(items_per_slot, block_size);
+    if (!bad.empty()) { fail("pb_bigwig_write: " + bad); return nullptr; }
+    pcbww::HostWriter *w = new pcbww::HostWriter();
+    w->items_per_slot = (uint32_t)items_per_slot; w->block_size = (uint32_t)block_size; w->compress = compress != 0;
+    return w;
+}
+void pb_bigwig_write_close(void *h) { delete static_cast<pcbww::HostWriter *>(h); }
+int pb_bigwig_write_add(void *h, const char *name, int64_t length, const double *cells, int64_t n) {
+    pcbww::HostWriter *w = static_cast<pcbww::HostWriter *>(h);
+    if (!w || !name || length < 0 || n < 0 || (n > 0 && !cells)) return fail("pb_bigwig_write_add: bad arguments");
+    w->in.push_back({name, length, std::vector<double>(cells, cells + n)});
+    return 0;
+}
+int pb_bigwig_write_finish(void *h) {
+    pcbww::HostWriter *w = static_cast<pcbww::HostWriter *>(h);
+    if (!w) return fail("pb_bigwig_write_finish: NULL handle");
+    return w->finish() ? 0 : fail("pb_bigwig_write: " + w->error);
+}
+int64_t pb_bigwig_write_size(void *h) { return h ? (int64_t)static_cast<pcbww::HostWriter *>(h)->image.size() : -1; }
+const void *pb_bigwig_write_image(void *h) { return static_cast<pcbww::HostWriter *>(h)->image.data(); }
+// [0] contigs, [1] items, [2] sections, [3] raw bytes, [4] block bytes, [5] sections that fell back to stored
+int pb_bigwig_write_stats(void *h, int64_t *out6) {
+    pcbww::HostWriter *w = static_cast<pcbww::HostWriter *>(h);
+    if (!w || !out6) return fail("pb_bigwig_write_stats: bad arguments");
+    for (int k = 0; k < 6; ++k) out6[k] = w->stats[k];
     return 0;
 }
 

@@ -1,0 +1,248 @@
+// Writing bigWig files from HBM, host side (revision 19): pc_track_export_bigwig / _read / pc_track_bigwig_export_stats /
+// _timing and pc_track_set_length of include/plastid_counts.h.  One export is a BigWigExport taken through its phases:
+//   1  item heads over the cells of the strand's contigs in sorted order, their exclusive sum, the items in front of
+//      every contig (one read-back of a word per contig: the host cuts the sections from it);
+//   2  the items into their columns and into the raw sections, the section headers, the total summary;
+//   3  k_zlib_deflate over the raw sections (compress), 4 the sizes, their exclusive sum, the compaction;
+//   5  the section table (bounds and sizes) comes back, the host lays out offsets and both trees
+//      (bigwig_write_host.h: the container code of the host writer), and the blocks cross PCIe once, straight into their
+//      place in the image -- through the transfer ring when they are large.
+// What is refused is refused before anything is built, and nothing is left behind.
+// Part of the one translation unit of plastid_counts.hip (behind deflate_encoder.hip.h).
+#include "bigwig_write_kernels.hip.h"
+
+namespace {
+
+namespace ww = pcbww;
+
+struct BigWigExport {
+    pc_track *t;
+    int strand;
+    uint32_t items_per_slot, block_size;
+    bool compress;
+    hipStream_t st;
+    LapEvents<5> ev;                       // start | items known | sections + summary | encoded | compacted
+    tk::ExportSlots slots;                 // the contigs in sorted order and their cells
+    std::vector<ww::WContig> contigs;
+    std::vector<tk::ExRange> ranges;       // one per contig and the sentinel
+    int K = 0;
+    int64_t E = 0, N = 0, nsec = 0, raw_bytes = 0, block_bytes = 0, stored = 0;
+    std::vector<int64_t> sec_first;        // sections in front of every contig
+    std::vector<ww::DevSection> sections;
+    ww::DevSummary total = {0ull, ww::kNoKeyMin, ww::kNoKeyMax, 0.0, 0.0};
+    DevBuf<tk::ExRange> d_ranges;
+    DevBuf<uint32_t> d_flags, d_idx, d_istart, d_iend, d_sec_start, d_sec_end, d_stored;
+    DevBuf<float> d_ival;
+    DevBuf<int64_t> d_sec_first, d_in;     // d_in: the offsets, then the lengths of the raw sections
+    DevBuf<ww::DevSection> d_sections;
+    DevBuf<ww::DevSummary> d_summary;      // the total, then the partials
+    DevBuf<uint8_t> d_raw, d_slots, d_blocks, d_tmp;
+    DevBuf<uint64_t> d_slot_off;
+    DevBuf<unsigned long long> d_res;      // the sizes, then the offsets of the streams
+};
+
+// Phase 1: heads, exclusive sum, items in front of every contig; the host cuts the sections.
+int bwx_items_and_sections(BigWigExport &c) {
+    hipStream_t st = c.st;
+    HIP_TRY(hipEventRecord(c.ev[0], st));
+    if (c.E > 0) {
+        int rc = PC_OK;
+        room(rc, c.d_flags, (size_t)c.E); room(rc, c.d_idx, (size_t)c.E);
+        if (rc != PC_OK) return rc;
+        PC_TRY(c.d_ranges.upload(c.ranges, st));
+        hipLaunchKernelGGL(ww::k_bww_flags, dim3((unsigned)((c.E + tk::kExportTile - 1) / tk::kExportTile)), dim3(256), 0, st, c.d_ranges.p, c.K, c.E, c.t->cells.p, c.d_flags.p);
+        HIP_TRY(hipGetLastError());
+        PC_TRY(cub_run(c.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, c.d_flags.p, c.d_idx.p, (int)c.E, st); }));
+        hipLaunchKernelGGL(tk::k_export_bases, dim3(grid256(c.K + 1)), dim3(256), 0, st, c.d_flags.p, c.d_idx.p, c.E, c.d_ranges.p, c.K);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c.ranges.data(), c.d_ranges.p, c.ranges.size() * sizeof(tk::ExRange), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        c.N = c.ranges[(size_t)c.K].run_base;
+    }
+    c.sec_first.assign((size_t)c.K + 1, 0);
+    for (int k = 0; k < c.K; ++k) {
+        const int64_t first = c.ranges[(size_t)k].run_base, cnt = c.ranges[(size_t)k + 1].run_base - first;
+        c.sec_first[(size_t)k] = (int64_t)c.sections.size();
+        for (int64_t a = 0; a < cnt; a += c.items_per_slot)
+            c.sections.push_back({(uint32_t)k, (uint32_t)std::min<int64_t>(c.items_per_slot, cnt - a), (uint64_t)(first + a)});
+    }
+    c.nsec = (int64_t)c.sections.size();
+    c.sec_first[(size_t)c.K] = c.nsec;
+    c.raw_bytes = 24 * c.nsec + 12 * c.N;
+    HIP_TRY(hipEventRecord(c.ev[1], st));
+    return PC_OK;
+}
+
+// Phase 2: the items, the section headers, the total summary.
+int bwx_fill_sections(BigWigExport &c) {
+    hipStream_t st = c.st;
+    const int64_t ntile = (c.N + ww::kSummaryTile - 1) / ww::kSummaryTile;
+    int rc = PC_OK;
+    room(rc, c.d_istart, (size_t)c.N); room(rc, c.d_iend, (size_t)c.N); room(rc, c.d_ival, (size_t)c.N); room(rc, c.d_raw, (size_t)c.raw_bytes + 64);
+    room(rc, c.d_sec_start, (size_t)c.nsec); room(rc, c.d_sec_end, (size_t)c.nsec); room(rc, c.d_in, 2 * (size_t)c.nsec); room(rc, c.d_summary, 1 + (size_t)ntile);
+    if (rc != PC_OK) return rc;
+    PC_TRY(c.d_sec_first.upload(c.sec_first, st)); PC_TRY(c.d_sections.upload(c.sections, st));
+    HIP_TRY(hipMemcpyAsync(c.d_summary.p, &c.total, sizeof(c.total), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ww::k_bww_items, dim3((unsigned)((c.E + tk::kExportTile - 1) / tk::kExportTile)), dim3(256), 0, st, c.d_ranges.p, c.K, c.E, c.t->cells.p, c.d_flags.p,
+                       c.d_idx.p, c.d_sec_first.p, c.items_per_slot, c.d_istart.p, c.d_iend.p, c.d_ival.p, c.d_raw.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ww::k_bww_headers, dim3(grid256(c.nsec)), dim3(256), 0, st, c.d_sections.p, c.nsec, c.d_istart.p, c.d_iend.p, c.d_raw.p, c.d_sec_start.p, c.d_sec_end.p,
+                       c.d_in.p, c.d_in.p + c.nsec);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ww::k_bww_summary, dim3((unsigned)ntile), dim3(256), 0, st, c.d_istart.p, c.d_iend.p, c.d_ival.p, c.N, c.d_summary.p + 1, c.d_summary.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ww::k_bww_summary_final, dim3(1), dim3(256), 0, st, c.d_summary.p + 1, ntile, c.d_summary.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&c.total, c.d_summary.p, sizeof(c.total), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(c.ev[2], st));
+    return PC_OK;
+}
+
+// Phases 3, 4: every raw section through the encoder, the streams compacted; d_blocks: the blocks of the file back to back.
+int bwx_deflate(BigWigExport &c) {
+    hipStream_t st = c.st;
+    std::vector<uint64_t> slot_off((size_t)c.nsec);
+    uint64_t slots = 0;
+    for (int64_t s = 0; s < c.nsec; ++s) { slot_off[(size_t)s] = slots; slots += 24u + 12u * (uint64_t)c.sections[(size_t)s].count + pcdeflate::kSlotPad; }
+    int rc = PC_OK;
+    room(rc, c.d_slots, (size_t)slots + 64); room(rc, c.d_blocks, (size_t)(c.raw_bytes + (int64_t)pcdeflate::kStreamOverhead * c.nsec) + 64);
+    room(rc, c.d_res, 2 * (size_t)c.nsec); room(rc, c.d_stored, (size_t)c.nsec);
+    if (rc != PC_OK) return rc;
+    PC_TRY(c.d_slot_off.upload(slot_off, st));
+    PC_TRY(queue_zlib_deflate(st, c.d_raw.p, c.d_in.p, c.d_in.p + c.nsec, c.d_slot_off.p, c.nsec, c.d_slots.p, c.d_res.p, c.d_res.p + c.nsec, c.d_stored.p, c.d_tmp,
+                              c.d_blocks.p, c.ev[3]));
+    HIP_TRY(hipStreamSynchronize(st));   // (slot_off goes out of scope)
+    return PC_OK;
+}
+
+// Phase 5: the section table comes back, the host lays the file out, the blocks land in their place.
+int bwx_layout_and_read(BigWigExport &c) {
+    hipStream_t st = c.st;
+    pc_track *t = c.t;
+    std::vector<uint32_t> sec_start((size_t)c.nsec), sec_end((size_t)c.nsec), stored((size_t)c.nsec);
+    std::vector<unsigned long long> sizes((size_t)c.nsec);
+    const auto t0 = std::chrono::steady_clock::now();
+    if (c.nsec > 0) {
+        HIP_TRY(hipMemcpyAsync(sec_start.data(), c.d_sec_start.p, (size_t)c.nsec * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(sec_end.data(), c.d_sec_end.p, (size_t)c.nsec * 4, hipMemcpyDeviceToHost, st));
+        if (c.compress) {
+            HIP_TRY(hipMemcpyAsync(sizes.data(), c.d_res.p, (size_t)c.nsec * 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(stored.data(), c.d_stored.p, (size_t)c.nsec * 4, hipMemcpyDeviceToHost, st));
+        }
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    std::vector<ww::WSection> sections((size_t)c.nsec);
+    uint32_t largest = 0;
+    for (int64_t s = 0; s < c.nsec; ++s) {
+        const uint32_t raw = 24u + 12u * c.sections[(size_t)s].count;
+        sections[(size_t)s] = {c.sections[(size_t)s].chrom, sec_start[(size_t)s], sec_end[(size_t)s], c.compress ? (uint64_t)sizes[(size_t)s] : (uint64_t)raw};
+        largest = std::max(largest, raw);
+        c.stored += c.compress ? (int64_t)stored[(size_t)s] : 0;
+    }
+    ww::Summary sm;
+    sm.valid = c.total.valid; sm.kmin = c.total.kmin; sm.kmax = c.total.kmax; sm.sum = c.total.sum; sm.sumsq = c.total.sumsq;
+    ww::Container box;
+    ww::build_container(c.contigs, sections, c.block_size, c.compress ? largest : 0u, c.N > 0 ? &sm : nullptr, box);
+    c.block_bytes = (int64_t)box.block_bytes;
+    t->bwx_image.resize(box.front.size() + (size_t)c.block_bytes + box.back.size());
+    memcpy(t->bwx_image.data(), box.front.data(), box.front.size());
+    memcpy(t->bwx_image.data() + box.front.size() + (size_t)c.block_bytes, box.back.data(), box.back.size());
+    const auto t2 = std::chrono::steady_clock::now();
+    if (c.block_bytes > 0) {
+        void *dst = t->bwx_image.data() + box.front.size();
+        const void *src = c.compress ? (const void *)c.d_blocks.p : (const void *)c.d_raw.p;
+        const size_t bytes = (size_t)c.block_bytes;
+        const char *knob = getenv("PC_STAGE_SLICE");   // (test knob: the ring for every size, in pieces of so many 4 KiB pages)
+        if (bytes >= 4 * TransferRing::kPiece || knob) {
+            const std::vector<TransferJob> job{{dst, src, bytes}};
+            const size_t piece = knob ? (size_t)std::max<int64_t>(1, std::min<int64_t>(atoll(knob), 4096)) * 4096 : TransferRing::kPiece;
+            PC_TRY(TransferRing::of(t->e->device).run(t->e->device, job, piece, knob != nullptr, true));
+        } else {
+            HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+        }
+    }
+    const auto t3 = std::chrono::steady_clock::now();
+    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    t->bwx_ms[4] = ms(t0, t1) + ms(t2, t3); t->bwx_ms[5] = ms(t1, t2);
+    return PC_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int pc_track_export_bigwig(pc_track *t, int strand_slot, int64_t items_per_slot, int64_t block_size, int compress, int64_t *bytes) {
+    if (!t || !bytes) return fail(PC_ERR_ARG, "pc_track_export_bigwig: bad arguments");
+    if (strand_slot < 0 || strand_slot >= t->tab.nstrands) return fail(PC_ERR_ARG, "pc_track_export_bigwig: strand slot %d of %d", strand_slot, t->tab.nstrands);
+    const std::string bad = ww::check_params(items_per_slot, block_size);
+    if (!bad.empty()) return fail(PC_ERR_ARG, "pc_track_export_bigwig: %s", bad.c_str());
+    pc_engine *e = t->e;
+    BigWigExport c{t, strand_slot, (uint32_t)items_per_slot, (uint32_t)block_size, compress != 0, e->stream};
+    c.slots = t->tab.export_slots(strand_slot);
+    c.K = (int)c.slots.ids.size();
+    for (int k = 0; k < c.K; ++k) {
+        const int32_t id = c.slots.ids[(size_t)k];
+        const int64_t size = std::max(t->tab.length[(size_t)id], c.slots.cells[(size_t)k].n);
+        if (size >= ((int64_t)1 << 32)) return fail(PC_ERR_ARG, "pc_track_export_bigwig: contig %s has 2^32 positions or more", t->tab.names[(size_t)id].c_str());
+        c.contigs.push_back({t->tab.names[(size_t)id], (uint32_t)size});
+        c.ranges.push_back(tk::ExRange{c.E, c.slots.cells[(size_t)k].n, c.slots.cells[(size_t)k].cell0, 0, 0, 0, 0});
+        c.E += c.slots.cells[(size_t)k].n;
+    }
+    c.ranges.push_back(tk::ExRange{c.E, 0, 0, 0, 0, 0, 0});
+    // (the scans count in int: a strand of 2^31 - 1 cells or more could hold 2^31 items, and is refused as a whole)
+    if (c.E >= (int64_t)0x7fffffff) return fail(PC_ERR_ARG, "pc_track_export_bigwig: 2^31 - 1 cells or more on the strand: the items are counted in 31 bits");
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    for (auto &x : t->bwx_stats) x = 0;
+    for (auto &x : t->bwx_ms) x = 0.0;
+    t->bwx_bytes = -1;
+    std::vector<uint8_t>().swap(t->bwx_image);
+    *bytes = 0;
+    PC_TRY(c.ev.create());
+    DrainOnExit drained{c.st};
+    PC_TRY(bwx_items_and_sections(c));
+    if (c.N > 0) PC_TRY(bwx_fill_sections(c)); else HIP_TRY(hipEventRecord(c.ev[2], c.st));
+    if (c.N > 0 && c.compress) PC_TRY(bwx_deflate(c)); else HIP_TRY(hipEventRecord(c.ev[3], c.st));
+    HIP_TRY(hipEventRecord(c.ev[4], c.st));
+    HIP_TRY(hipStreamSynchronize(c.st));
+    const int rc = bwx_layout_and_read(c);
+    if (rc != PC_OK) { std::vector<uint8_t>().swap(t->bwx_image); return rc; }
+    drained.armed = false;
+    c.ev.laps(t->bwx_ms, 4);
+    t->bwx_stats[0] = c.K; t->bwx_stats[1] = c.N; t->bwx_stats[2] = c.nsec; t->bwx_stats[3] = c.raw_bytes; t->bwx_stats[4] = c.block_bytes; t->bwx_stats[5] = c.stored;
+    t->bwx_bytes = (int64_t)t->bwx_image.size();
+    *bytes = t->bwx_bytes;
+    return PC_OK;
+}
+
+int pc_track_set_length(pc_track *t, const char *name, int64_t length) {
+    if (!t || !name || length < 0) return fail(PC_ERR_ARG, "pc_track_set_length: bad arguments");
+    const int i = t->tab.public_index(name);
+    if (i < 0) return fail(PC_ERR_ARG, "pc_track_set_length: the track holds no contig %s", name);
+    t->tab.length[(size_t)t->tab.public_id(i)] = length;
+    return PC_OK;
+}
+
+int pc_track_export_bigwig_read(pc_track *t, void *dst, int64_t bytes) {
+    if (!t || t->bwx_bytes < 0 || bytes != t->bwx_bytes || (bytes > 0 && !dst)) return fail(PC_ERR_ARG, "pc_track_export_bigwig_read: no exported file of this size");
+    if (bytes > 0) memcpy(dst, t->bwx_image.data(), (size_t)bytes);
+    std::vector<uint8_t>().swap(t->bwx_image);
+    t->bwx_bytes = -1;
+    return PC_OK;
+}
+
+int pc_track_bigwig_export_stats(pc_track *t, int64_t *out6) {
+    if (!t || !out6) return fail(PC_ERR_ARG, "pc_track_bigwig_export_stats: bad arguments");
+    for (int k = 0; k < 6; ++k) out6[k] = t->bwx_stats[k];
+    return PC_OK;
+}
+
+int pc_track_bigwig_export_timing(pc_track *t, double *ms6) {
+    if (!t || !ms6) return fail(PC_ERR_ARG, "pc_track_bigwig_export_timing: bad arguments");
+    for (int k = 0; k < 6; ++k) ms6[k] = t->bwx_ms[k];
+    return PC_OK;
+}
+
+}   // extern "C"

@@ -1,0 +1,78 @@
+// The zlib encoder on the GPU, host side (revision 19): pc_deflate_zlib of include/plastid_counts.h, the twin of
+// pc_inflate_zlib.  The inputs cross PCIe once; k_zlib_deflate (deflate_kernels.hip.h) turns each into a stream in its
+// slot of len + 16 bytes; the sizes, their exclusive sum and k_deflate_compact make one contiguous buffer, which is read
+// back with the offsets and sizes.  The bytes are those of pcdeflate::encode (deflate_host.h).
+// Part of the one translation unit of plastid_counts.hip (behind bigwig_decoder.hip.h).
+#include "deflate_kernels.hip.h"
+
+namespace {
+
+// n inputs in HBM -> their streams, compacted into d_out (room for the sum of len + 11), on `st`.  d_slot_off: the
+// exclusive sum of len + 16; d_len / d_off: n sizes and offsets of the streams; d_stored: which fell back to stored;
+// encoded (optional): recorded between the encoder and the compaction.
+int queue_zlib_deflate(hipStream_t st, const uint8_t *d_image, const int64_t *d_in_off, const int64_t *d_in_len, const uint64_t *d_slot_off, int64_t n,
+                       uint8_t *d_slots, unsigned long long *d_len, unsigned long long *d_off, uint32_t *d_stored, DevBuf<uint8_t> &d_tmp, uint8_t *d_out, hipEvent_t encoded = nullptr) {
+    if (n == 0) return PC_OK;
+    hipLaunchKernelGGL(pcdeflate::k_zlib_deflate, dim3((unsigned)n), dim3(pcdeflate::kDefWG), 0, st, d_image, d_in_off, d_in_len, d_slot_off, n, d_slots, d_len, d_stored);
+    HIP_TRY(hipGetLastError());
+    if (encoded) HIP_TRY(hipEventRecord(encoded, st));
+    PC_TRY(cub_run(d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, d_len, d_off, (int)n, st); }));
+    hipLaunchKernelGGL(pcdeflate::k_deflate_compact, dim3((unsigned)n), dim3(256), 0, st, (const uint8_t *)d_slots, d_slot_off, (const unsigned long long *)d_len,
+                       (const unsigned long long *)d_off, n, d_out);
+    HIP_TRY(hipGetLastError());
+    return PC_OK;
+}
+
+}   // namespace
+
+extern "C" {
+
+int pc_deflate_zlib(pc_engine *e, const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off, int64_t *out_len) {
+    if (!e || n < 0 || n >= ((int64_t)1 << 31) || out_capacity < 0 || (n > 0 && (!off || !len || !out || !out_off || !out_len)))
+        return fail(PC_ERR_ARG, "pc_deflate_zlib: bad arguments");
+    if (n == 0) return PC_OK;
+    int64_t image_bytes = 0, need = 0;
+    std::vector<uint64_t> slot_off((size_t)n);
+    uint64_t slots = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        if (off[k] < 0 || len[k] < 0 || len[k] > (int64_t)pcdeflate::kMaxInput)
+            return fail(PC_ERR_ARG, "pc_deflate_zlib: input %lld lies below 0 or holds more than %u bytes", (long long)k, pcdeflate::kMaxInput);
+        if (len[k] > 0) image_bytes = std::max(image_bytes, off[k] + len[k]);
+        need += len[k] + (int64_t)pcdeflate::kStreamOverhead;
+        slot_off[(size_t)k] = slots;
+        slots += (uint64_t)len[k] + pcdeflate::kSlotPad;
+    }
+    if (image_bytes > 0 && !image) return fail(PC_ERR_ARG, "pc_deflate_zlib: bad arguments");
+    if (out_capacity < need) return fail(PC_ERR_ARG, "pc_deflate_zlib: out_capacity %lld below the %lld bytes the streams may take", (long long)out_capacity, (long long)need);
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    DevBuf<uint8_t> d_image, d_slots, d_out, d_tmp;
+    DevBuf<int64_t> d_in;                        // the offsets, then the lengths
+    DevBuf<uint64_t> d_slot_off;
+    DevBuf<unsigned long long> d_res;            // the sizes, then the offsets of the streams
+    DevBuf<uint32_t> d_stored;
+    std::vector<int64_t> h_in(2 * (size_t)n);
+    std::vector<unsigned long long> h_res(2 * (size_t)n);
+    memcpy(h_in.data(), off, (size_t)n * 8); memcpy(h_in.data() + n, len, (size_t)n * 8);
+    DrainOnExit drained{st};
+    int rc = PC_OK;
+    room(rc, d_image, (size_t)image_bytes + 64); room(rc, d_slots, (size_t)slots + 64); room(rc, d_out, (size_t)need + 64); room(rc, d_in, 2 * (size_t)n);
+    room(rc, d_res, 2 * (size_t)n); room(rc, d_stored, (size_t)n);
+    if (rc != PC_OK) return rc;
+    PC_TRY(d_slot_off.upload(slot_off, st));
+    if (image_bytes > 0) HIP_TRY(hipMemcpyAsync(d_image.p, image, (size_t)image_bytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_in.p, h_in.data(), h_in.size() * 8, hipMemcpyHostToDevice, st));
+    PC_TRY(queue_zlib_deflate(st, d_image.p, d_in.p, d_in.p + n, d_slot_off.p, n, d_slots.p, d_res.p, d_res.p + n, d_stored.p, d_tmp, d_out.p));
+    HIP_TRY(hipMemcpyAsync(h_res.data(), d_res.p, h_res.size() * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t total = (int64_t)(h_res[(size_t)(2 * n - 1)] + h_res[(size_t)(n - 1)]);
+    if (total > need) { drained.armed = false; return fail(PC_ERR_STATE, "pc_deflate_zlib: the streams hold %lld bytes, more than %lld", (long long)total, (long long)need); }
+    HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
+    for (int64_t k = 0; k < n; ++k) { out_len[k] = (int64_t)h_res[(size_t)k]; out_off[k] = (int64_t)h_res[(size_t)(n + k)]; }
+    return PC_OK;
+}
+
+}   // extern "C"

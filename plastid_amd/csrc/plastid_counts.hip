@@ -3805,3 +3805,5 @@ int pc_read_mapped_reads(pc_engine *e, pc_plan *p, uint32_t *rec, int64_t total)
 #include "sam_decoder.hip.h"
 #include "track_decoder.hip.h"
 #include "bigwig_decoder.hip.h"
+#include "deflate_encoder.hip.h"
+#include "bigwig_writer.hip.h"

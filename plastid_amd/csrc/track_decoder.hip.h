@@ -36,6 +36,11 @@ struct pc_track {
     DevBuf<int64_t> nz;
     int64_t nz_total = -1;
     pctrack::NzShares nz_shares;            // per slot: its share of nz
+    // the last pc_track_export_bigwig (bigwig_writer.hip.h): the file's image waits for pc_track_export_bigwig_read
+    std::vector<uint8_t> bwx_image;
+    int64_t bwx_bytes = -1;
+    int64_t bwx_stats[6] = {0, 0, 0, 0, 0, 0};   // contigs, items, sections, raw bytes, block bytes, sections stored
+    double bwx_ms[6] = {0, 0, 0, 0, 0, 0};       // runs + items | sections + summary | deflate + adler | sizes + compaction | read-back | host layout
 };
 
 // an engine that is destroyed takes its tracks with it (pc_destroy): their cells come from its pool

@@ -560,6 +560,49 @@ class GenomeArray(object):
         check(self._lib.pc_track_export_timing(self._h, out.ctypes.data))
         return dict(zip(("slot_sums", "runs", "listed_values", "lengths", "format", "read_back"), (float(x) for x in out)))
 
+    def to_bigwig(self, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True):
+        """Write `strand` as a bigWig file (a path, or a file object opened in binary mode; a text-mode file is a
+        ``TypeError``).  No reference counterpart: the reference reads bigWig and does not write it.
+
+        The stored cells are written, as :meth:`to_bedgraph` writes them -- the normalisation ``get`` would show is NOT
+        applied.  A cell is written iff its value ``!= 0.0`` (NaN is, ``-0.0`` is not); neighbouring written cells form
+        one item while their float64 values compare equal; values are cast to float32.  Contigs stand in sorted order,
+        every contig is in the chromosome tree at ``max(lengths()[c], extents()[c][strand])``; every `items_per_slot`
+        items (1 .. 2 048) of a contig make one bedGraph section, `block_size` (2 .. 65 535) is the fan-out of both
+        trees, `compress`: every section through the GPU's zlib encoder (``csrc/deflate_kernels.hip.h``: LZ77 under the
+        fixed Huffman codes, or a stored block), else stored sections.  No zoom levels: readers fall back to the full
+        data.  Items, sections, summary and blocks are built in HBM; the host lays out the header and both trees.  The
+        file is the one :func:`write_bigwig` gives for ``to_host()``."""
+        assert strand in self._strands
+        _check_bigwig_params(items_per_slot, block_size)
+        if isinstance(path_or_file, io.TextIOBase):
+            raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
+        nbytes = ctypes.c_int64(0)
+        check(self._lib.pc_track_export_bigwig(self._h, self._strands.index(strand), int(items_per_slot), int(block_size), 1 if compress else 0,
+                                               ctypes.byref(nbytes)), "pc_track_export_bigwig")
+        image = np.empty(max(int(nbytes.value), 1), np.uint8)
+        check(self._lib.pc_track_export_bigwig_read(self._h, image.ctypes.data, int(nbytes.value)), "pc_track_export_bigwig_read")
+        sink, close = _binary_sink(path_or_file)
+        try:
+            sink.write(memoryview(image[:int(nbytes.value)]))
+        finally:
+            if close:
+                sink.close()
+
+    def bigwig_export_stats(self):
+        """Of the last :meth:`to_bigwig`: contigs, items, sections, raw bytes of the sections, bytes of the blocks in the
+        file, sections that fell back to a stored DEFLATE block."""
+        out = np.zeros(6, np.int64)
+        check(self._lib.pc_track_bigwig_export_stats(self._h, out.ctypes.data))
+        return dict(zip(BIGWIG_WRITE_STATS, (int(x) for x in out)))
+
+    def bigwig_export_timing(self):
+        """Milliseconds of the last :meth:`to_bigwig`: item heads and their sum, items + section headers + summary,
+        deflate + Adler-32, sizes + compaction, read-back, host layout."""
+        out = np.zeros(6, np.float64)
+        check(self._lib.pc_track_bigwig_export_timing(self._h, out.ctypes.data))
+        return dict(zip(("runs_items", "sections_summary", "deflate_adler", "sizes_compaction", "read_back", "host_layout"), (float(x) for x in out)))
+
     # ---- the query side
     def _gather(self, contig, slot, start, end, out_off, out_step, total):
         out = np.zeros(int(total), np.float64)
@@ -758,6 +801,123 @@ def inflate_zlib(engine, streams, capacity):
     check(_lib.load().pc_inflate_zlib(engine._h, ctypes.cast(buf, ctypes.c_void_p), n, offs.ctypes.data, lens.ctypes.data, int(capacity),
                                       out.ctypes.data, out_len.ctypes.data, status.ctypes.data), "pc_inflate_zlib")
     return [(out[k * int(capacity):k * int(capacity) + int(out_len[k])].tobytes(), int(status[k])) for k in range(n)]
+
+
+DEFLATE_MAX_INPUT = 24600     # pcdeflate::kMaxInput: one bedGraph section of 2 048 items
+
+
+def _deflate(call, inputs, capacity):
+    n = len(inputs)
+    image = b"".join(bytes(s) for s in inputs)
+    lens = np.array([len(s) for s in inputs], np.int64)
+    offs = (np.cumsum(lens) - lens).astype(np.int64)
+    need = int(lens.sum()) + 11 * n
+    capacity = need if capacity is None else int(capacity)
+    buf = ctypes.create_string_buffer(image, len(image)) if image else ctypes.create_string_buffer(1)
+    out = np.zeros(max(capacity, 1), np.uint8)
+    out_off, out_len = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1), np.int64)
+    call(ctypes.cast(buf, ctypes.c_void_p), n, offs.ctypes.data, lens.ctypes.data, out.ctypes.data, capacity, out_off.ctypes.data, out_len.ctypes.data)
+    total = int(out_off[n - 1] + out_len[n - 1]) if n else 0
+    return out[:total].tobytes(), out_off[:n].copy(), out_len[:n].copy()
+
+
+def deflate_zlib(engine, inputs, capacity=None):
+    """``pc_deflate_zlib``: every input of `inputs` (bytes, at most 24 600 each) encoded by one workgroup of ``k_zlib_deflate``
+    on `engine` into one zlib stream.  Returns ``(bytes of the streams back to back, offsets, lengths)``; stream k is
+    ``out[off[k]:off[k] + len[k]]``, at most ``len(inputs[k]) + 11`` bytes.  `capacity` (default: the sum of the inputs + 11
+    each): the room offered; less is a ``ValueError``, as an over-long input is.  No reference counterpart."""
+    L = _lib.load()
+
+    def call(*args):
+        check(L.pc_deflate_zlib(engine._h, *args), "pc_deflate_zlib")
+    return _deflate(call, inputs, capacity)
+
+
+def deflate_zlib_host(inputs, capacity=None):
+    """``pb_deflate_zlib``: :func:`deflate_zlib` by the serial model encoder of ``csrc/deflate_host.h`` on the host -- the
+    bytes the kernel must give, and the encoder of :func:`write_bigwig`."""
+    from .bam import _load
+    L = _load()
+    vp = ctypes.c_void_p
+    L.pb_deflate_zlib.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp]
+
+    def call(*args):
+        if L.pb_deflate_zlib(*args) != 0:
+            raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    return _deflate(call, inputs, capacity)
+
+
+BIGWIG_WRITE_STATS = ("contigs", "items", "sections", "raw_bytes", "block_bytes", "stored_sections")
+
+
+def _binary_sink(path_or_file):
+    """``(file object, close it afterwards)`` of a path or a binary file object; a text-mode file is a ``TypeError``."""
+    if isinstance(path_or_file, (str, bytes, os.PathLike)):
+        return open(os.fspath(path_or_file), "wb"), True
+    if isinstance(path_or_file, io.TextIOBase) or not hasattr(path_or_file, "write"):
+        raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
+    return path_or_file, False
+
+
+def _check_bigwig_params(items_per_slot, block_size):
+    if not 1 <= int(items_per_slot) <= 2048:
+        raise ValueError("to_bigwig: items_per_slot outside 1 .. 2048")
+    if not 2 <= int(block_size) <= 65535:
+        raise ValueError("to_bigwig: block_size outside 2 .. 65535")
+
+
+def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True):
+    """Write `strand` of a host ``DenseGenomeArray`` as a bigWig file by the serial writer of ``csrc/bigwig_write_host.h``
+    (``pb_bigwig_write_*``): the item walk, the model encoder of ``csrc/deflate_host.h`` and the container code the device
+    export shares.  The model of :meth:`GenomeArray.to_bigwig`, and the way to write a bigWig without a GPU.
+
+    A cell is written iff its value ``!= 0.0`` (NaN is, ``-0.0`` is not); neighbouring written cells form one item while
+    their float64 values compare equal; values are cast to float32.  Contigs stand in sorted order, every contig is in
+    the chromosome tree at ``max(reported length, cells stored)``; every `items_per_slot` items of a contig make one
+    bedGraph section, `block_size` is the fan-out of both trees.  No zoom levels.  Normalisation is not applied.
+    Returns the writer's statistics (``BIGWIG_WRITE_STATS``).  No reference counterpart."""
+    _check_bigwig_params(items_per_slot, block_size)
+    if isinstance(path_or_file, io.TextIOBase):
+        raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
+    assert strand in host_array.strands()
+    from .bam import _load
+    L = _load()
+    vp = ctypes.c_void_p
+    if not hasattr(L.pb_bigwig_write_open, "_bound"):
+        L.pb_bigwig_write_open.restype = vp
+        L.pb_bigwig_write_open.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int]
+        L.pb_bigwig_write_close.argtypes = [vp]
+        L.pb_bigwig_write_add.argtypes = [vp, ctypes.c_char_p, ctypes.c_int64, vp, ctypes.c_int64]
+        L.pb_bigwig_write_finish.argtypes = [vp]
+        L.pb_bigwig_write_size.restype = ctypes.c_int64
+        L.pb_bigwig_write_size.argtypes = [vp]
+        L.pb_bigwig_write_image.restype = vp
+        L.pb_bigwig_write_image.argtypes = [vp]
+        L.pb_bigwig_write_stats.argtypes = [vp, vp]
+        L.pb_bigwig_write_open._bound = True
+    h = L.pb_bigwig_write_open(int(items_per_slot), int(block_size), 1 if compress else 0)
+    if not h:
+        raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    try:
+        lengths = host_array.lengths()
+        for chrom in host_array.chroms():
+            cells = np.ascontiguousarray(host_array._chroms[chrom][strand], np.float64)
+            if L.pb_bigwig_write_add(h, chrom.encode("utf-8"), int(lengths[chrom]), cells.ctypes.data, len(cells)) != 0:
+                raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+        if L.pb_bigwig_write_finish(h) != 0:
+            raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+        image = ctypes.string_at(L.pb_bigwig_write_image(h), int(L.pb_bigwig_write_size(h)))
+        stats = np.zeros(6, np.int64)
+        L.pb_bigwig_write_stats(h, stats.ctypes.data)
+    finally:
+        L.pb_bigwig_write_close(h)
+    sink, close = _binary_sink(path_or_file)
+    try:
+        sink.write(image)
+    finally:
+        if close:
+            sink.close()
+    return dict(zip(BIGWIG_WRITE_STATS, (int(x) for x in stats)))
 
 
 class BigWigReader(object):
