@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 19
+#define PC_ABI_VERSION 20
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -702,13 +702,29 @@ int pc_track_sum_ranges(pc_track *t, int64_t nrange, const int32_t *contig, cons
  * out + out_off[k].  PC_ERR_ARG: an input above 24 600 bytes, out_capacity below the sum of len[k] + 11. */
 int pc_deflate_zlib(pc_engine *e, const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off,
                     int64_t *out_len);
+/* pc_deflate_zlib with a choice of codes (revision 20).  mode 1: the fixed Huffman codes, pc_deflate_zlib itself.  mode 2:
+ * dynamic codes -- the same matches and the same tokens, under Huffman codes built for the block (lengths within 15, 15
+ * and 7, every code complete, the block header by zlib's run-length rule; csrc/deflate_host.h states every step).  The
+ * body is the dynamic block iff it takes fewer bytes than the fixed block and than the stored block, else what mode 1
+ * gives: a mode-2 stream is never longer than the mode-1 stream.  The bytes are those of pb_deflate_zlib_mode of the
+ * host library.  PC_ERR_ARG as pc_deflate_zlib, and for any other mode. */
+int pc_deflate_zlib_mode(pc_engine *e, const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off,
+                         int64_t *out_len, int mode);
+/* The code lengths the encoder gives n symbols (2 .. 286) of the counts counts[0, n) under a length limit (1 .. 15, 2^limit
+ * >= n), on the device (k_huffman_lengths: the rank sort and the length function k_zlib_deflate compiles): with fewer
+ * than two counts above 0 the lowest-numbered zeros count 1; Huffman's merge over the order (count, symbol), a leaf before
+ * an internal node of equal weight; depths above the limit repaired as csrc/deflate_host.h states; lengths handed out
+ * longest first in that order.  The code is complete (the Kraft sum is 1); unused symbols get 0.  pb_huffman_lengths of
+ * the host library is the model.  PC_ERR_ARG: n or limit out of range, counts that add up to 2^32 or more. */
+int pc_huffman_lengths(pc_engine *e, const uint32_t *counts, int64_t n, int limit, uint8_t *lengths_out);
 
 /* One strand slot of a track as a bigWig file (revision 19; csrc/bigwig_writer.hip.h, the container: csrc/bigwig_write_host.h).
  * A cell is written iff its value != 0.0 (NaN is, -0.0 is not); neighbouring written cells of a contig form one item while
  * their float64 values compare equal; the value is cast to float32 afterwards.  Contigs stand in the sorted order of their
  * names, every contig of the track is in the chromosome tree at max(length, cells stored); every items_per_slot items of
- * a contig make one bedGraph section; block_size is the fan-out of both trees; compress: every section through
- * k_zlib_deflate (uncompressBufSize: the largest raw section), else stored (0).  Little-endian, version 4, no zoom levels;
+ * a contig make one bedGraph section; block_size is the fan-out of both trees; compress: 1 every section through
+ * k_zlib_deflate under the fixed codes, 2 under dynamic codes (pc_deflate_zlib_mode; uncompressBufSize: the largest raw
+ * section), 0 stored sections (uncompressBufSize 0); any other value is PC_ERR_ARG.  Little-endian, version 4, no zoom levels;
  * the total summary stands at offset 64 when the file has items.  Items, sections, summary and blocks are built in HBM;
  * the section table comes back, the host lays out offsets and trees, and the blocks cross PCIe once (through the transfer
  * ring when they are large).  *bytes: the size of the file, which waits on the host for pc_track_export_bigwig_read.
@@ -727,6 +743,9 @@ int pc_track_export_bigwig_read(pc_track *t, void *dst, int64_t bytes);
 /* the last pc_track_export_bigwig: [0] contigs, [1] items, [2] sections, [3] raw bytes of the sections, [4] bytes of the
  * blocks in the file, [5] sections that fell back to a stored DEFLATE block */
 int pc_track_bigwig_export_stats(pc_track *t, int64_t *out6);
+/* the last pc_track_export_bigwig: the sections that went out as [0] stored, [1] fixed, [2] dynamic DEFLATE blocks; they
+ * add up to the sections when compress was 1 or 2 and are 0 when it was 0 */
+int pc_track_bigwig_export_block_types(pc_track *t, int64_t *out3);
 /* milliseconds of the last pc_track_export_bigwig: [0] item heads, their sum and the items per contig, [1] items, section
  * headers and the summary, [2] deflate and Adler-32, [3] sizes and compaction (on the engine's stream), [4] read-back,
  * [5] host layout (wall clock) */

@@ -153,10 +153,13 @@ SIGNATURES = {
     "pc_bigwig_blocks": (_int, [ctypes.c_char_p, _vp, _i64, _i64, _vp, _vp]),
     "pc_inflate_zlib": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "pc_deflate_zlib": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "pc_deflate_zlib_mode": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int]),
+    "pc_huffman_lengths": (_int, [_vp, _vp, _i64, _int, _vp]),
     "pc_track_export_bigwig": (_int, [_vp, _int, _i64, _i64, _int, _vp]),
     "pc_track_export_bigwig_read": (_int, [_vp, _vp, _i64]),
     "pc_track_set_length": (_int, [_vp, ctypes.c_char_p, _i64]),
     "pc_track_bigwig_export_stats": (_int, [_vp, _vp]),
+    "pc_track_bigwig_export_block_types": (_int, [_vp, _vp]),
     "pc_track_bigwig_export_timing": (_int, [_vp, _vp]),
     "pc_track_add_bigwig": (_int, [_vp, _vp, _i64, ctypes.c_char_p, _int]),
     "pc_track_add_bigwig_path": (_int, [_vp, ctypes.c_char_p, _int]),
@@ -173,7 +176,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 def load():

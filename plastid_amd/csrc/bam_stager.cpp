@@ -1898,8 +1898,10 @@ int pb_bigwig_stats(void *h, int64_t *out8) {
 }
 
 // ---------------------------------------------------------------- zlib encoder and bigWig writer (deflate_host.h, bigwig_write_host.h)
-// pb_deflate_zlib: pc_deflate_zlib without the engine -- the model encoder over n inputs, the streams back to back.
-int pb_deflate_zlib(const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off, int64_t *out_len) {
+// pb_deflate_zlib_mode: pc_deflate_zlib_mode without the engine -- the model encoder over n inputs, the streams back to back.
+int pb_deflate_zlib_mode(const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off, int64_t *out_len,
+                         int mode) {
+    if (mode != (int)pcdeflate::kFixed && mode != (int)pcdeflate::kDynamic) return fail("pb_deflate_zlib: mode " + std::to_string(mode) + " is neither 1 (fixed) nor 2 (dynamic)");
     if (n < 0 || out_capacity < 0 || (n > 0 && (!off || !len || !out || !out_off || !out_len))) return fail("pb_deflate_zlib: bad arguments");
     int64_t need = 0;
     for (int64_t k = 0; k < n; ++k) {
@@ -1912,7 +1914,7 @@ int pb_deflate_zlib(const void *image, int64_t n, const int64_t *off, const int6
     int64_t at = 0;
     for (int64_t k = 0; k < n; ++k) {
         stream.clear();
-        pcdeflate::encode((const uint8_t *)image + off[k], (uint32_t)len[k], stream);
+        pcdeflate::encode((const uint8_t *)image + off[k], (uint32_t)len[k], stream, (uint32_t)mode);
         std::memcpy((uint8_t *)out + at, stream.data(), stream.size());
         out_off[k] = at; out_len[k] = (int64_t)stream.size();
         at += (int64_t)stream.size();
@@ -1920,12 +1922,32 @@ int pb_deflate_zlib(const void *image, int64_t n, const int64_t *off, const int6
     return 0;
 }
 
+int pb_deflate_zlib(const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off, int64_t *out_len) {
+    return pb_deflate_zlib_mode(image, n, off, len, out, out_capacity, out_off, out_len, (int)pcdeflate::kFixed);
+}
+
+// pb_huffman_lengths: pc_huffman_lengths without the engine -- pcdeflate::build_code's lengths of n counts under `limit`.
+int pb_huffman_lengths(const uint32_t *counts, int64_t n, int limit, uint8_t *lengths_out) {
+    if (!counts || !lengths_out) return fail("pb_huffman_lengths: bad arguments");
+    if (n < 2 || n > (int64_t)pcdeflate::kLitSyms || limit < 1 || limit > 15 || ((int64_t)1 << limit) < n)
+        return fail("pb_huffman_lengths: " + std::to_string(n) + " symbols under limit " + std::to_string(limit) + " (2 .. 286 symbols, limit 1 .. 15, 2^limit >= symbols)");
+    uint64_t sum = 0;
+    for (int64_t s = 0; s < n; ++s) sum += counts[s];
+    if (sum >= ((uint64_t)1 << 32)) return fail("pb_huffman_lengths: the counts add up to 2^32 or more");
+    std::vector<uint32_t> c(counts, counts + n), weight((size_t)n);
+    std::vector<uint16_t> order((size_t)n), parent(2 * (size_t)n), depth((size_t)n);
+    uint32_t bl_count[16], next_code[16];
+    pcdeflate::build_code(c.data(), (uint32_t)n, (uint32_t)limit, order.data(), weight.data(), parent.data(), depth.data(), bl_count, next_code, lengths_out, nullptr);
+    return 0;
+}
+
 // The serial bigWig writer: open, one add per contig (any order), finish, then the image and the statistics.
 void *pb_bigwig_write_open(int64_t items_per_slot, int64_t block_size, int compress) {
     const std::string bad = pcbww::check_params(items_per_slot, block_size);
     if (!bad.empty()) { fail("pb_bigwig_write: " + bad); return nullptr; }
+    if (compress < 0 || compress > 2) { fail("pb_bigwig_write: compress " + std::to_string(compress) + " is none of 0 (stored sections), 1 (fixed codes), 2 (dynamic codes)"); return nullptr; }
     pcbww::HostWriter *w = new pcbww::HostWriter();
-    w->items_per_slot = (uint32_t)items_per_slot; w->block_size = (uint32_t)block_size; w->compress = compress != 0;
+    w->items_per_slot = (uint32_t)items_per_slot; w->block_size = (uint32_t)block_size; w->compress = compress;
     return w;
 }
 void pb_bigwig_write_close(void *h) { delete static_cast<pcbww::HostWriter *>(h); }
@@ -1947,6 +1969,13 @@ int pb_bigwig_write_stats(void *h, int64_t *out6) {
     pcbww::HostWriter *w = static_cast<pcbww::HostWriter *>(h);
     if (!w || !out6) return fail("pb_bigwig_write_stats: bad arguments");
     for (int k = 0; k < 6; ++k) out6[k] = w->stats[k];
+    return 0;
+}
+// the sections that went out as [0] stored, [1] fixed, [2] dynamic blocks (all 0 for a file of stored sections)
+int pb_bigwig_write_block_types(void *h, int64_t *out3) {
+    pcbww::HostWriter *w = static_cast<pcbww::HostWriter *>(h);
+    if (!w || !out3) return fail("pb_bigwig_write_block_types: bad arguments");
+    for (int k = 0; k < 3; ++k) out3[k] = w->stats[5 + k];
     return 0;
 }
 

@@ -186,10 +186,10 @@ inline void build_container(const std::vector<WContig> &contigs, const std::vect
 struct HostWriter {
     struct In { std::string name; int64_t length; std::vector<double> cells; };
     uint32_t items_per_slot = 1024, block_size = 256;
-    bool compress = true;
+    int compress = 1;                        // 0: stored sections, else the encoder's mode (pcdeflate::kFixed, kDynamic)
     std::vector<In> in;
     std::vector<uint8_t> image;
-    int64_t stats[6] = {0, 0, 0, 0, 0, 0};   // contigs, items, sections, raw bytes, block bytes, sections that fell back to stored
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // contigs, items, sections, raw bytes, block bytes, sections as stored, fixed, dynamic blocks
     std::string error;
 
     bool finish() {
@@ -198,7 +198,7 @@ struct HostWriter {
         std::vector<WSection> sections;
         std::vector<uint8_t> blocks, raw;
         Summary sm;
-        uint64_t nitems = 0, raw_bytes = 0, stored = 0;
+        uint64_t nitems = 0, raw_bytes = 0, by_type[3] = {0, 0, 0};
         uint32_t largest = 0;
         for (size_t c = 0; c < in.size(); ++c) {
             const int64_t size = std::max<int64_t>(in[c].length, (int64_t)in[c].cells.size());
@@ -214,9 +214,9 @@ struct HostWriter {
                 put_section_header(raw.data(), (uint32_t)c, first, last, count);
                 const size_t before = blocks.size();
                 if (compress) {
-                    bool st = false;
-                    pcdeflate::encode(raw.data(), (uint32_t)raw.size(), blocks, &st);
-                    stored += st ? 1u : 0u;
+                    uint32_t type = pcdeflate::kFixed;
+                    pcdeflate::encode(raw.data(), (uint32_t)raw.size(), blocks, (uint32_t)compress, &type);
+                    ++by_type[type];
                 } else blocks.insert(blocks.end(), raw.begin(), raw.end());
                 sections.push_back({(uint32_t)c, first, last, (uint64_t)(blocks.size() - before)});
                 raw_bytes += raw.size(); largest = std::max<uint32_t>(largest, (uint32_t)raw.size());
@@ -244,7 +244,7 @@ struct HostWriter {
         image.insert(image.end(), blocks.begin(), blocks.end());
         image.insert(image.end(), box.back.begin(), box.back.end());
         stats[0] = (int64_t)contigs.size(); stats[1] = (int64_t)nitems; stats[2] = (int64_t)sections.size(); stats[3] = (int64_t)raw_bytes;
-        stats[4] = (int64_t)blocks.size(); stats[5] = (int64_t)stored;
+        stats[4] = (int64_t)blocks.size(); stats[5] = (int64_t)by_type[pcdeflate::kStored]; stats[6] = (int64_t)by_type[pcdeflate::kFixed]; stats[7] = (int64_t)by_type[pcdeflate::kDynamic];
         return true;
     }
 };

@@ -1,5 +1,5 @@
-// Writing bigWig files from HBM, host side (revision 19): pc_track_export_bigwig / _read / pc_track_bigwig_export_stats /
-// _timing and pc_track_set_length of include/plastid_counts.h.  One export is a BigWigExport taken through its phases:
+// Writing bigWig files from HBM, host side (revision 20): pc_track_export_bigwig / _read / pc_track_bigwig_export_stats /
+// _block_types / _timing and pc_track_set_length of include/plastid_counts.h.  One export is a BigWigExport taken through its phases:
 //   1  item heads over the cells of the strand's contigs in sorted order, their exclusive sum, the items in front of
 //      every contig (one read-back of a word per contig: the host cuts the sections from it);
 //   2  the items into their columns and into the raw sections, the section headers, the total summary;
@@ -19,14 +19,14 @@ struct BigWigExport {
     pc_track *t;
     int strand;
     uint32_t items_per_slot, block_size;
-    bool compress;
+    int compress;                          // 0: stored sections, else the encoder's mode (pcdeflate::kFixed, kDynamic)
     hipStream_t st;
     LapEvents<5> ev;                       // start | items known | sections + summary | encoded | compacted
     tk::ExportSlots slots;                 // the contigs in sorted order and their cells
     std::vector<ww::WContig> contigs;
     std::vector<tk::ExRange> ranges;       // one per contig and the sentinel
     int K = 0;
-    int64_t E = 0, N = 0, nsec = 0, raw_bytes = 0, block_bytes = 0, stored = 0;
+    int64_t E = 0, N = 0, nsec = 0, raw_bytes = 0, block_bytes = 0, stored = 0, fixed = 0, dynamic = 0;
     std::vector<int64_t> sec_first;        // sections in front of every contig
     std::vector<ww::DevSection> sections;
     ww::DevSummary total = {0ull, ww::kNoKeyMin, ww::kNoKeyMax, 0.0, 0.0};
@@ -110,7 +110,7 @@ int bwx_deflate(BigWigExport &c) {
     if (rc != PC_OK) return rc;
     PC_TRY(c.d_slot_off.upload(slot_off, st));
     PC_TRY(queue_zlib_deflate(st, c.d_raw.p, c.d_in.p, c.d_in.p + c.nsec, c.d_slot_off.p, c.nsec, c.d_slots.p, c.d_res.p, c.d_res.p + c.nsec, c.d_stored.p, c.d_tmp,
-                              c.d_blocks.p, c.ev[3]));
+                              c.d_blocks.p, (uint32_t)c.compress, c.ev[3]));
     HIP_TRY(hipStreamSynchronize(st));   // (slot_off goes out of scope)
     return PC_OK;
 }
@@ -138,7 +138,10 @@ int bwx_layout_and_read(BigWigExport &c) {
         const uint32_t raw = 24u + 12u * c.sections[(size_t)s].count;
         sections[(size_t)s] = {c.sections[(size_t)s].chrom, sec_start[(size_t)s], sec_end[(size_t)s], c.compress ? (uint64_t)sizes[(size_t)s] : (uint64_t)raw};
         largest = std::max(largest, raw);
-        c.stored += c.compress ? (int64_t)stored[(size_t)s] : 0;
+        if (c.compress) {
+            const uint32_t type = (uint32_t)c.compress - stored[(size_t)s];     // (the encoder reports the steps its block fell back)
+            c.stored += type == pcdeflate::kStored; c.fixed += type == pcdeflate::kFixed; c.dynamic += type == pcdeflate::kDynamic;
+        }
     }
     ww::Summary sm;
     sm.valid = c.total.valid; sm.kmin = c.total.kmin; sm.kmax = c.total.kmax; sm.sum = c.total.sum; sm.sumsq = c.total.sumsq;
@@ -178,8 +181,9 @@ int pc_track_export_bigwig(pc_track *t, int strand_slot, int64_t items_per_slot,
     if (strand_slot < 0 || strand_slot >= t->tab.nstrands) return fail(PC_ERR_ARG, "pc_track_export_bigwig: strand slot %d of %d", strand_slot, t->tab.nstrands);
     const std::string bad = ww::check_params(items_per_slot, block_size);
     if (!bad.empty()) return fail(PC_ERR_ARG, "pc_track_export_bigwig: %s", bad.c_str());
+    if (compress < 0 || compress > 2) return fail(PC_ERR_ARG, "pc_track_export_bigwig: compress %d is none of 0 (stored sections), 1 (fixed codes), 2 (dynamic codes)", compress);
     pc_engine *e = t->e;
-    BigWigExport c{t, strand_slot, (uint32_t)items_per_slot, (uint32_t)block_size, compress != 0, e->stream};
+    BigWigExport c{t, strand_slot, (uint32_t)items_per_slot, (uint32_t)block_size, compress, e->stream};
     c.slots = t->tab.export_slots(strand_slot);
     c.K = (int)c.slots.ids.size();
     for (int k = 0; k < c.K; ++k) {
@@ -211,7 +215,7 @@ int pc_track_export_bigwig(pc_track *t, int strand_slot, int64_t items_per_slot,
     if (rc != PC_OK) { std::vector<uint8_t>().swap(t->bwx_image); return rc; }
     drained.armed = false;
     c.ev.laps(t->bwx_ms, 4);
-    t->bwx_stats[0] = c.K; t->bwx_stats[1] = c.N; t->bwx_stats[2] = c.nsec; t->bwx_stats[3] = c.raw_bytes; t->bwx_stats[4] = c.block_bytes; t->bwx_stats[5] = c.stored;
+    t->bwx_stats[0] = c.K; t->bwx_stats[1] = c.N; t->bwx_stats[2] = c.nsec; t->bwx_stats[3] = c.raw_bytes; t->bwx_stats[4] = c.block_bytes; t->bwx_stats[5] = c.stored; t->bwx_stats[6] = c.fixed; t->bwx_stats[7] = c.dynamic;
     t->bwx_bytes = (int64_t)t->bwx_image.size();
     *bytes = t->bwx_bytes;
     return PC_OK;
@@ -236,6 +240,12 @@ int pc_track_export_bigwig_read(pc_track *t, void *dst, int64_t bytes) {
 int pc_track_bigwig_export_stats(pc_track *t, int64_t *out6) {
     if (!t || !out6) return fail(PC_ERR_ARG, "pc_track_bigwig_export_stats: bad arguments");
     for (int k = 0; k < 6; ++k) out6[k] = t->bwx_stats[k];
+    return PC_OK;
+}
+
+int pc_track_bigwig_export_block_types(pc_track *t, int64_t *out3) {
+    if (!t || !out3) return fail(PC_ERR_ARG, "pc_track_bigwig_export_block_types: bad arguments");
+    out3[0] = t->bwx_stats[5]; out3[1] = t->bwx_stats[6]; out3[2] = t->bwx_stats[7];
     return PC_OK;
 }
 

@@ -1,5 +1,5 @@
-// The zlib encoder on the GPU, host side (revision 19): pc_deflate_zlib of include/plastid_counts.h, the twin of
-// pc_inflate_zlib.  The inputs cross PCIe once; k_zlib_deflate (deflate_kernels.hip.h) turns each into a stream in its
+// The zlib encoder on the GPU, host side (revision 20): pc_deflate_zlib / pc_deflate_zlib_mode and pc_huffman_lengths of
+// include/plastid_counts.h, the twins of pc_inflate_zlib.  The inputs cross PCIe once; k_zlib_deflate (deflate_kernels.hip.h) turns each into a stream in its
 // slot of len + 16 bytes; the sizes, their exclusive sum and k_deflate_compact make one contiguous buffer, which is read
 // back with the offsets and sizes.  The bytes are those of pcdeflate::encode (deflate_host.h).
 // Part of the one translation unit of plastid_counts.hip (behind bigwig_decoder.hip.h).
@@ -8,12 +8,17 @@
 namespace {
 
 // n inputs in HBM -> their streams, compacted into d_out (room for the sum of len + 11), on `st`.  d_slot_off: the
-// exclusive sum of len + 16; d_len / d_off: n sizes and offsets of the streams; d_stored: which fell back to stored;
-// encoded (optional): recorded between the encoder and the compaction.
+// exclusive sum of len + 16; d_len / d_off: n sizes and offsets of the streams; d_fell_back: how far every stream's block fell back from the mode's own codes
+// (its BTYPE is mode - steps); mode: pcdeflate::kFixed or kDynamic; encoded (optional): recorded between the encoder and the compaction.
 int queue_zlib_deflate(hipStream_t st, const uint8_t *d_image, const int64_t *d_in_off, const int64_t *d_in_len, const uint64_t *d_slot_off, int64_t n,
-                       uint8_t *d_slots, unsigned long long *d_len, unsigned long long *d_off, uint32_t *d_stored, DevBuf<uint8_t> &d_tmp, uint8_t *d_out, hipEvent_t encoded = nullptr) {
+                       uint8_t *d_slots, unsigned long long *d_len, unsigned long long *d_off, uint32_t *d_fell_back, DevBuf<uint8_t> &d_tmp, uint8_t *d_out, uint32_t mode, hipEvent_t encoded = nullptr) {
     if (n == 0) return PC_OK;
-    hipLaunchKernelGGL(pcdeflate::k_zlib_deflate, dim3((unsigned)n), dim3(pcdeflate::kDefWG), 0, st, d_image, d_in_off, d_in_len, d_slot_off, n, d_slots, d_len, d_stored);
+    if (mode == pcdeflate::kDynamic)
+        hipLaunchKernelGGL(pcdeflate::k_zlib_deflate<pcdeflate::kDynamic>, dim3((unsigned)n), dim3(pcdeflate::kDefWG), 0, st, d_image, d_in_off, d_in_len, d_slot_off, n, d_slots,
+                           d_len, d_fell_back);
+    else
+        hipLaunchKernelGGL(pcdeflate::k_zlib_deflate<pcdeflate::kFixed>, dim3((unsigned)n), dim3(pcdeflate::kDefWG), 0, st, d_image, d_in_off, d_in_len, d_slot_off, n, d_slots,
+                           d_len, d_fell_back);
     HIP_TRY(hipGetLastError());
     if (encoded) HIP_TRY(hipEventRecord(encoded, st));
     PC_TRY(cub_run(d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, d_len, d_off, (int)n, st); }));
@@ -27,7 +32,9 @@ int queue_zlib_deflate(hipStream_t st, const uint8_t *d_image, const int64_t *d_
 
 extern "C" {
 
-int pc_deflate_zlib(pc_engine *e, const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off, int64_t *out_len) {
+int pc_deflate_zlib_mode(pc_engine *e, const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off,
+                         int64_t *out_len, int mode) {
+    if (mode != (int)pcdeflate::kFixed && mode != (int)pcdeflate::kDynamic) return fail(PC_ERR_ARG, "pc_deflate_zlib: mode %d is neither 1 (fixed) nor 2 (dynamic)", mode);
     if (!e || n < 0 || n >= ((int64_t)1 << 31) || out_capacity < 0 || (n > 0 && (!off || !len || !out || !out_off || !out_len)))
         return fail(PC_ERR_ARG, "pc_deflate_zlib: bad arguments");
     if (n == 0) return PC_OK;
@@ -63,7 +70,7 @@ int pc_deflate_zlib(pc_engine *e, const void *image, int64_t n, const int64_t *o
     PC_TRY(d_slot_off.upload(slot_off, st));
     if (image_bytes > 0) HIP_TRY(hipMemcpyAsync(d_image.p, image, (size_t)image_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_in.p, h_in.data(), h_in.size() * 8, hipMemcpyHostToDevice, st));
-    PC_TRY(queue_zlib_deflate(st, d_image.p, d_in.p, d_in.p + n, d_slot_off.p, n, d_slots.p, d_res.p, d_res.p + n, d_stored.p, d_tmp, d_out.p));
+    PC_TRY(queue_zlib_deflate(st, d_image.p, d_in.p, d_in.p + n, d_slot_off.p, n, d_slots.p, d_res.p, d_res.p + n, d_stored.p, d_tmp, d_out.p, (uint32_t)mode));
     HIP_TRY(hipMemcpyAsync(h_res.data(), d_res.p, h_res.size() * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     const int64_t total = (int64_t)(h_res[(size_t)(2 * n - 1)] + h_res[(size_t)(n - 1)]);
@@ -72,6 +79,35 @@ int pc_deflate_zlib(pc_engine *e, const void *image, int64_t n, const int64_t *o
     HIP_TRY(hipStreamSynchronize(st));
     drained.armed = false;
     for (int64_t k = 0; k < n; ++k) { out_len[k] = (int64_t)h_res[(size_t)k]; out_off[k] = (int64_t)h_res[(size_t)(n + k)]; }
+    return PC_OK;
+}
+
+int pc_deflate_zlib(pc_engine *e, const void *image, int64_t n, const int64_t *off, const int64_t *len, void *out, int64_t out_capacity, int64_t *out_off, int64_t *out_len) {
+    return pc_deflate_zlib_mode(e, image, n, off, len, out, out_capacity, out_off, out_len, (int)pcdeflate::kFixed);
+}
+
+int pc_huffman_lengths(pc_engine *e, const uint32_t *counts, int64_t n, int limit, uint8_t *lengths_out) {
+    if (!e || !counts || !lengths_out) return fail(PC_ERR_ARG, "pc_huffman_lengths: bad arguments");
+    if (n < 2 || n > (int64_t)pcdeflate::kLitSyms || limit < 1 || limit > 15 || ((int64_t)1 << limit) < n)
+        return fail(PC_ERR_ARG, "pc_huffman_lengths: %lld symbols under limit %d (2 .. 286 symbols, limit 1 .. 15, 2^limit >= symbols)", (long long)n, limit);
+    uint64_t sum = 0;
+    for (int64_t s = 0; s < n; ++s) sum += counts[s];
+    if (sum >= ((uint64_t)1 << 32)) return fail(PC_ERR_ARG, "pc_huffman_lengths: the counts add up to 2^32 or more");
+    HIP_TRY(hipSetDevice(e->device));
+    PoolScope pool_scope(&e->pool);
+    hipStream_t st = e->stream;
+    DevBuf<uint32_t> d_counts;
+    DevBuf<uint8_t> d_lengths;
+    DrainOnExit drained{st};
+    int rc = PC_OK;
+    room(rc, d_counts, (size_t)n); room(rc, d_lengths, (size_t)n);
+    if (rc != PC_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(d_counts.p, counts, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(pcdeflate::k_huffman_lengths, dim3(1), dim3(pcdeflate::kDefWG), 0, st, (const uint32_t *)d_counts.p, (uint32_t)n, (uint32_t)limit, d_lengths.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(lengths_out, d_lengths.p, (size_t)n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    drained.armed = false;
     return PC_OK;
 }
 

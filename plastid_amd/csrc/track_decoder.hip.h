@@ -39,7 +39,7 @@ struct pc_track {
     // the last pc_track_export_bigwig (bigwig_writer.hip.h): the file's image waits for pc_track_export_bigwig_read
     std::vector<uint8_t> bwx_image;
     int64_t bwx_bytes = -1;
-    int64_t bwx_stats[6] = {0, 0, 0, 0, 0, 0};   // contigs, items, sections, raw bytes, block bytes, sections stored
+    int64_t bwx_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // contigs, items, sections, raw bytes, block bytes, sections as stored, fixed, dynamic blocks
     double bwx_ms[6] = {0, 0, 0, 0, 0, 0};       // runs + items | sections + summary | deflate + adler | sizes + compaction | read-back | host layout
 };
 

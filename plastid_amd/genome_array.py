@@ -870,9 +870,10 @@ class BAMGenomeArray(object):
         While it runs it takes 8 bytes of HBM per genome position for the temporary array, beside the counts of a
         batch.  :func:`plastid_amd.track.write_bigwig` writes the same file on the host from count vectors."""
         import io
-        from .track import GenomeArray, _check_bigwig_params
+        from .track import GenomeArray, _check_bigwig_params, _compress_mode
         assert strand in self.strands()
         _check_bigwig_params(items_per_slot, block_size)
+        _compress_mode(compress)             # (a bad value is a ValueError before anything is counted)
         if isinstance(path_or_file, io.TextIOBase):
             raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
         self._one_row_rule()
@@ -893,13 +894,17 @@ class BAMGenomeArray(object):
             for c, n in zip(chroms, sizes):   # (a contig written up to its end has grown by the reference's rule: the file takes the BAM's lengths)
                 _lib.check(ga._lib.pc_track_set_length(ga._h, os.fsencode(c), n), "pc_track_set_length")
             ga.to_bigwig(path_or_file, strand, items_per_slot=items_per_slot, block_size=block_size, compress=compress)
-            self._bigwig_export_stats, self._bigwig_export_timing = ga.bigwig_export_stats(), ga.bigwig_export_timing()
+            self._bigwig_export_stats, self._bigwig_export_timing = ga.bigwig_export_stats(block_types=True), ga.bigwig_export_timing()
         finally:
             ga.close()
 
-    def bigwig_export_stats(self):
+    def bigwig_export_stats(self, block_types=False):
         """Of the last :meth:`to_bigwig`: what :meth:`plastid_amd.track.GenomeArray.bigwig_export_stats` reports."""
-        return dict(getattr(self, "_bigwig_export_stats", {}))
+        stats = dict(getattr(self, "_bigwig_export_stats", {}))
+        if not block_types:
+            stats.pop("fixed_sections", None)
+            stats.pop("dynamic_sections", None)
+        return stats
 
     def bigwig_export_timing(self):
         """Of the last :meth:`to_bigwig`: what :meth:`plastid_amd.track.GenomeArray.bigwig_export_timing` reports."""

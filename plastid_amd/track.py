@@ -569,16 +569,19 @@ class GenomeArray(object):
         one item while their float64 values compare equal; values are cast to float32.  Contigs stand in sorted order,
         every contig is in the chromosome tree at ``max(lengths()[c], extents()[c][strand])``; every `items_per_slot`
         items (1 .. 2 048) of a contig make one bedGraph section, `block_size` (2 .. 65 535) is the fan-out of both
-        trees, `compress`: every section through the GPU's zlib encoder (``csrc/deflate_kernels.hip.h``: LZ77 under the
-        fixed Huffman codes, or a stored block), else stored sections.  No zoom levels: readers fall back to the full
+        trees, `compress`: ``True`` or ``"fixed"``: every section through the GPU's zlib encoder
+        (``csrc/deflate_kernels.hip.h``: LZ77 under the fixed Huffman codes, or a stored block); ``"dynamic"``: the same
+        matches under Huffman codes built for every section, never larger and on count data about a third smaller;
+        ``False``: stored sections; anything else is a ``ValueError``.  No zoom levels: readers fall back to the full
         data.  Items, sections, summary and blocks are built in HBM; the host lays out the header and both trees.  The
         file is the one :func:`write_bigwig` gives for ``to_host()``."""
         assert strand in self._strands
         _check_bigwig_params(items_per_slot, block_size)
+        mode = _compress_mode(compress)
         if isinstance(path_or_file, io.TextIOBase):
             raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
         nbytes = ctypes.c_int64(0)
-        check(self._lib.pc_track_export_bigwig(self._h, self._strands.index(strand), int(items_per_slot), int(block_size), 1 if compress else 0,
+        check(self._lib.pc_track_export_bigwig(self._h, self._strands.index(strand), int(items_per_slot), int(block_size), mode,
                                                ctypes.byref(nbytes)), "pc_track_export_bigwig")
         image = np.empty(max(int(nbytes.value), 1), np.uint8)
         check(self._lib.pc_track_export_bigwig_read(self._h, image.ctypes.data, int(nbytes.value)), "pc_track_export_bigwig_read")
@@ -589,12 +592,20 @@ class GenomeArray(object):
             if close:
                 sink.close()
 
-    def bigwig_export_stats(self):
+    def bigwig_export_stats(self, block_types=False):
         """Of the last :meth:`to_bigwig`: contigs, items, sections, raw bytes of the sections, bytes of the blocks in the
-        file, sections that fell back to a stored DEFLATE block."""
+        file, sections that fell back to a stored DEFLATE block.  `block_types`: also ``fixed_sections`` and
+        ``dynamic_sections``, the sections that went out as fixed and as dynamic blocks; with ``stored_sections`` they add
+        up to the sections of a compressed file (all three are 0 for ``compress=False``)."""
         out = np.zeros(6, np.int64)
         check(self._lib.pc_track_bigwig_export_stats(self._h, out.ctypes.data))
-        return dict(zip(BIGWIG_WRITE_STATS, (int(x) for x in out)))
+        stats = dict(zip(BIGWIG_WRITE_STATS, (int(x) for x in out)))
+        if block_types:
+            types = np.zeros(3, np.int64)
+            check(self._lib.pc_track_bigwig_export_block_types(self._h, types.ctypes.data))
+            assert int(types[0]) == stats["stored_sections"]
+            stats["fixed_sections"], stats["dynamic_sections"] = int(types[1]), int(types[2])
+        return stats
 
     def bigwig_export_timing(self):
         """Milliseconds of the last :meth:`to_bigwig`: item heads and their sum, items + section headers + summary,
@@ -821,30 +832,82 @@ def _deflate(call, inputs, capacity):
     return out[:total].tobytes(), out_off[:n].copy(), out_len[:n].copy()
 
 
-def deflate_zlib(engine, inputs, capacity=None):
-    """``pc_deflate_zlib``: every input of `inputs` (bytes, at most 24 600 each) encoded by one workgroup of ``k_zlib_deflate``
+DEFLATE_CODES = {"fixed": 1, "dynamic": 2}      # the modes of pc_deflate_zlib_mode
+
+
+def _codes_mode(codes):
+    if codes not in DEFLATE_CODES:
+        raise ValueError("codes: %r is neither 'fixed' nor 'dynamic'" % (codes,))
+    return DEFLATE_CODES[codes]
+
+
+def _compress_mode(compress):
+    """`compress` of the bigWig writers as the C interface takes it: 0 stored sections, 1 fixed codes, 2 dynamic codes."""
+    if isinstance(compress, str):
+        if compress in DEFLATE_CODES:
+            return DEFLATE_CODES[compress]
+    elif compress is None or isinstance(compress, (bool, np.bool_)) or (isinstance(compress, (int, np.integer)) and compress in (0, 1)):
+        return 1 if compress else 0
+    raise ValueError("compress: %r is none of True, False, 'fixed', 'dynamic'" % (compress,))
+
+
+def deflate_zlib(engine, inputs, capacity=None, codes="fixed"):
+    """``pc_deflate_zlib_mode``: every input of `inputs` (bytes, at most 24 600 each) encoded by one workgroup of ``k_zlib_deflate``
     on `engine` into one zlib stream.  Returns ``(bytes of the streams back to back, offsets, lengths)``; stream k is
     ``out[off[k]:off[k] + len[k]]``, at most ``len(inputs[k]) + 11`` bytes.  `capacity` (default: the sum of the inputs + 11
-    each): the room offered; less is a ``ValueError``, as an over-long input is.  No reference counterpart."""
+    each): the room offered; less is a ``ValueError``, as an over-long input is.  `codes`: ``"fixed"`` (the fixed Huffman
+    codes) or ``"dynamic"`` (the same tokens under codes built for the block; never longer than the fixed stream).  No
+    reference counterpart."""
     L = _lib.load()
+    mode = _codes_mode(codes)
 
     def call(*args):
-        check(L.pc_deflate_zlib(engine._h, *args), "pc_deflate_zlib")
+        check(L.pc_deflate_zlib_mode(engine._h, *(args + (mode,))), "pc_deflate_zlib_mode")
     return _deflate(call, inputs, capacity)
 
 
-def deflate_zlib_host(inputs, capacity=None):
-    """``pb_deflate_zlib``: :func:`deflate_zlib` by the serial model encoder of ``csrc/deflate_host.h`` on the host -- the
-    bytes the kernel must give, and the encoder of :func:`write_bigwig`."""
+def deflate_zlib_host(inputs, capacity=None, codes="fixed"):
+    """``pb_deflate_zlib_mode``: :func:`deflate_zlib` by the serial model encoder of ``csrc/deflate_host.h`` on the host --
+    the bytes the kernel must give, and the encoder of :func:`write_bigwig`."""
     from .bam import _load
     L = _load()
     vp = ctypes.c_void_p
-    L.pb_deflate_zlib.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp]
+    L.pb_deflate_zlib_mode.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int]
+    mode = _codes_mode(codes)
 
     def call(*args):
-        if L.pb_deflate_zlib(*args) != 0:
+        if L.pb_deflate_zlib_mode(*(args + (mode,))) != 0:
             raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
     return _deflate(call, inputs, capacity)
+
+
+def _huffman_counts(counts, limit):
+    counts = np.ascontiguousarray(counts)
+    if counts.ndim != 1 or (len(counts) and (counts.min() < 0 or int(counts.astype(object).sum()) >= 1 << 32)):
+        raise ValueError("huffman_lengths: counts must be one row of numbers >= 0 that add up to less than 2^32")
+    return counts.astype(np.uint32), np.zeros(max(len(counts), 1), np.uint8), int(limit)
+
+
+def huffman_lengths(engine, counts, limit):
+    """``pc_huffman_lengths``: the code lengths (uint8, 0 for an unused symbol) the encoder's dynamic mode gives `counts`
+    (2 .. 286 symbols) under the length `limit` (1 .. 15, ``2 ** limit >= len(counts)``), computed by ``k_huffman_lengths``
+    on `engine`: fewer than two used symbols are padded with the lowest-numbered unused ones, the code is complete, and
+    length never grows with (count, symbol).  ``ValueError`` for what is out of range.  No reference counterpart."""
+    c, out, limit = _huffman_counts(counts, limit)
+    check(_lib.load().pc_huffman_lengths(engine._h, c.ctypes.data, len(c), limit, out.ctypes.data), "pc_huffman_lengths")
+    return out[:len(c)].copy()
+
+
+def huffman_lengths_host(counts, limit):
+    """``pb_huffman_lengths``: :func:`huffman_lengths` by ``pcdeflate::build_code`` of ``csrc/deflate_host.h`` on the host."""
+    from .bam import _load
+    L = _load()
+    vp = ctypes.c_void_p
+    L.pb_huffman_lengths.argtypes = [vp, ctypes.c_int64, ctypes.c_int, vp]
+    c, out, limit = _huffman_counts(counts, limit)
+    if L.pb_huffman_lengths(c.ctypes.data, len(c), limit, out.ctypes.data) != 0:
+        raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    return out[:len(c)].copy()
 
 
 BIGWIG_WRITE_STATS = ("contigs", "items", "sections", "raw_bytes", "block_bytes", "stored_sections")
@@ -866,7 +929,7 @@ def _check_bigwig_params(items_per_slot, block_size):
         raise ValueError("to_bigwig: block_size outside 2 .. 65535")
 
 
-def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True):
+def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True, block_types=False):
     """Write `strand` of a host ``DenseGenomeArray`` as a bigWig file by the serial writer of ``csrc/bigwig_write_host.h``
     (``pb_bigwig_write_*``): the item walk, the model encoder of ``csrc/deflate_host.h`` and the container code the device
     export shares.  The model of :meth:`GenomeArray.to_bigwig`, and the way to write a bigWig without a GPU.
@@ -875,8 +938,11 @@ def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_si
     their float64 values compare equal; values are cast to float32.  Contigs stand in sorted order, every contig is in
     the chromosome tree at ``max(reported length, cells stored)``; every `items_per_slot` items of a contig make one
     bedGraph section, `block_size` is the fan-out of both trees.  No zoom levels.  Normalisation is not applied.
-    Returns the writer's statistics (``BIGWIG_WRITE_STATS``).  No reference counterpart."""
+    `compress` as :meth:`GenomeArray.to_bigwig` takes it: ``True`` / ``"fixed"``, ``"dynamic"``, ``False``.
+    Returns the writer's statistics (``BIGWIG_WRITE_STATS``; with `block_types` also ``fixed_sections`` and
+    ``dynamic_sections``, as :meth:`GenomeArray.bigwig_export_stats` gives them).  No reference counterpart."""
     _check_bigwig_params(items_per_slot, block_size)
+    mode = _compress_mode(compress)
     if isinstance(path_or_file, io.TextIOBase):
         raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
     assert strand in host_array.strands()
@@ -894,8 +960,9 @@ def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_si
         L.pb_bigwig_write_image.restype = vp
         L.pb_bigwig_write_image.argtypes = [vp]
         L.pb_bigwig_write_stats.argtypes = [vp, vp]
+        L.pb_bigwig_write_block_types.argtypes = [vp, vp]
         L.pb_bigwig_write_open._bound = True
-    h = L.pb_bigwig_write_open(int(items_per_slot), int(block_size), 1 if compress else 0)
+    h = L.pb_bigwig_write_open(int(items_per_slot), int(block_size), mode)
     if not h:
         raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
     try:
@@ -909,6 +976,8 @@ def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_si
         image = ctypes.string_at(L.pb_bigwig_write_image(h), int(L.pb_bigwig_write_size(h)))
         stats = np.zeros(6, np.int64)
         L.pb_bigwig_write_stats(h, stats.ctypes.data)
+        types = np.zeros(3, np.int64)
+        L.pb_bigwig_write_block_types(h, types.ctypes.data)
     finally:
         L.pb_bigwig_write_close(h)
     sink, close = _binary_sink(path_or_file)
@@ -917,7 +986,10 @@ def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_si
     finally:
         if close:
             sink.close()
-    return dict(zip(BIGWIG_WRITE_STATS, (int(x) for x in stats)))
+    out = dict(zip(BIGWIG_WRITE_STATS, (int(x) for x in stats)))
+    if block_types:
+        out["fixed_sections"], out["dynamic_sections"] = int(types[1]), int(types[2])
+    return out
 
 
 class BigWigReader(object):

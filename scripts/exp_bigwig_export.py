@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Laps of a bigWig export beside the bedGraph export of the same array (profiles/track_text/NOTES.md).
 
-    python scripts/exp_bigwig_export.py [--lines 10000000] [--repeat 5] [--out result.json]
+    python scripts/exp_bigwig_export.py [--lines 10000000] [--repeat 5] [--codes fixed|dynamic] [--out result.json]
 
 The track of scripts/exp_track_text.py and scripts/exp_bigwig_import.py (`--lines` items of integer counts over runs of
 1 .. 8 positions on 16 contigs) is written as a bigWig by tests/bigwig_writer.py and imported once (``BigWigReader``): its
@@ -10,7 +10,8 @@ one-strand array in HBM is the source.  Timed in ONE process on one engine, `--r
 2. ``GenomeArray.to_bedgraph`` of the same array into memory, the parent's way out: wall clock and ``export_timing()``;
 3. ``write_bigwig`` of ``to_host()`` on one host thread, once (wall clock, without ``to_host``).
 Sizes: the file, its block bytes, the raw bytes of the sections, and the same sections through ``zlib.compress(., 6)``,
-which is what Kent's writer would store.  The device's file is compared with the host writer's once."""
+which is what Kent's writer would store.  The device's file is compared with the host writer's once.  `--codes`: the
+Huffman codes of the encoder (``compress="fixed"``, the default of ``to_bigwig``, or ``"dynamic"``)."""
 import argparse
 import io
 import json
@@ -52,9 +53,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lines", type=int, default=10_000_000)
     ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--codes", choices=("fixed", "dynamic"), default="fixed")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    res = {"lines": a.lines, "repeat": a.repeat}
+    res = {"lines": a.lines, "repeat": a.repeat, "codes": a.codes}
     eng = Engine(0)
     with tempfile.TemporaryDirectory() as tmp:
         chroms, sections = [], []
@@ -74,13 +76,13 @@ def main():
     for k in range(a.repeat + 1):
         fh = io.BytesIO()
         t0 = time.perf_counter()
-        ga.to_bigwig(fh, ".")
+        ga.to_bigwig(fh, ".", compress=a.codes)
         wall = (time.perf_counter() - t0) * 1e3
         if k:
             runs.append(dict(ga.bigwig_export_timing(), wall=wall))
         image = fh.getvalue()
     res["to_bigwig_ms"] = {key: spread(runs, key) for key in runs[0]}
-    res["to_bigwig_stats"] = ga.bigwig_export_stats()
+    res["to_bigwig_stats"] = ga.bigwig_export_stats(block_types=True)
     res["file_bytes"] = len(image)
     # 2. to_bedgraph of the same array
     runs = []
@@ -97,7 +99,7 @@ def main():
     host = ga.to_host()
     fh = io.BytesIO()
     t0 = time.perf_counter()
-    res["write_bigwig_stats"] = pa.write_bigwig(host, fh, ".")
+    res["write_bigwig_stats"] = pa.write_bigwig(host, fh, ".", compress=a.codes)
     res["write_bigwig_ms"] = (time.perf_counter() - t0) * 1e3
     res["same_file"] = fh.getvalue() == image
     # the sections through zlib level 6
