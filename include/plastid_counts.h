@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 20
+#define PC_ABI_VERSION 21
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -724,7 +724,8 @@ int pc_huffman_lengths(pc_engine *e, const uint32_t *counts, int64_t n, int limi
  * names, every contig of the track is in the chromosome tree at max(length, cells stored); every items_per_slot items of
  * a contig make one bedGraph section; block_size is the fan-out of both trees; compress: 1 every section through
  * k_zlib_deflate under the fixed codes, 2 under dynamic codes (pc_deflate_zlib_mode; uncompressBufSize: the largest raw
- * section), 0 stored sections (uncompressBufSize 0); any other value is PC_ERR_ARG.  Little-endian, version 4, no zoom levels;
+ * section), 0 stored sections (uncompressBufSize 0); any other value is PC_ERR_ARG.  Little-endian, version 4, no zoom levels
+ * (pc_track_export_bigwig_zoom, below, writes them);
  * the total summary stands at offset 64 when the file has items.  Items, sections, summary and blocks are built in HBM;
  * the section table comes back, the host lays out offsets and trees, and the blocks cross PCIe once (through the transfer
  * ring when they are large).  *bytes: the size of the file, which waits on the host for pc_track_export_bigwig_read.
@@ -750,6 +751,35 @@ int pc_track_bigwig_export_block_types(pc_track *t, int64_t *out3);
  * headers and the summary, [2] deflate and Adler-32, [3] sizes and compaction (on the engine's stream), [4] read-back,
  * [5] host layout (wall clock) */
 int pc_track_bigwig_export_timing(pc_track *t, double *ms6);
+
+/* ---- ZOOM LEVELS of a written bigWig file (revision 21; csrc/bigwig_zoom_kernels.hip.h; what a level is:
+ * csrc/bigwig_write_host.h, "zoom levels").  pc_track_export_bigwig_zoom is pc_track_export_bigwig with `zoom`: 0 no zoom
+ * levels (pc_track_export_bigwig itself: zoomLevels = 0, the same bytes), -1 the automatic first reduction
+ * r0 = 4 x max(10, validCount / items) capped at 2^20, or r0 itself, 8 .. 2^24; any other value is PC_ERR_ARG.
+ * Reductions are r_k = r0 x 4^k, at most 10 levels, r_k <= 2^30.  Windows lie on a fixed grid -- window w of level k on a
+ * contig covers [w r_k, min((w + 1) r_k, size)) -- and not where Kent's writer, whose windows start where the data does,
+ * would put them; Kent's readers take either.  Level 0 takes every window's overlap with the ITEMS in their order
+ * (validCount, min and max of the float32 values, sum and sum of squares in float64); level k + 1 adds the float64
+ * accumulators of its four children in order, the empty ones skipped.  A window with validCount > 0 gives one 32-byte
+ * record (chromId, start, end, validCount u32; minVal, maxVal, sumData, sumSquares f32, cast there alone, a NaN as
+ * 0x7fc00000).  Level 0 is written whenever the file has items, level k >= 1 iff it has fewer records than level k - 1;
+ * a file without items has no levels and is the zoom = 0 file.  Every min(items_per_slot, 768) records of a contig make
+ * one block, stored or encoded as the sections are; uncompressBufSize is the largest raw section or zoom block.  The
+ * zoom headers (24 bytes each) stand at offset 64, the total summary behind them; behind the unzoomed R-tree every
+ * level has its u32 record count, its blocks and its R-tree.  The accumulators are dense per-window columns in HBM:
+ * 28 bytes per level-0 window and a third of that for the levels above; the record counts per (level, contig) and the
+ * block tables are all that visits the host.  PC_ERR_ARG also: a grid of 2^31 - 2 windows or more over the levels.
+ * The file is what the host writer (pb_bigwig_write_open_zoom of the host library) gives for the same cells, byte for
+ * byte (but for the total summary's two sums, as above). */
+int pc_track_export_bigwig_zoom(pc_track *t, int strand_slot, int64_t items_per_slot, int64_t block_size, int compress, int64_t zoom, int64_t *bytes);
+/* the zoom levels of the last export: *levels (0 .. 10), and per level k at out50 + 5 k: [0] the reduction, [1] records,
+ * [2] blocks, [3] raw bytes of the blocks, [4] their bytes in the file.  out50: room for 50 values. */
+int pc_track_bigwig_export_zoom_stats(pc_track *t, int64_t *levels, int64_t *out50);
+/* milliseconds of the zoom levels of the last export on the engine's stream: [0] level 0 from the items, [1] the levels
+ * above, [2] the flags' sum, the record counts' read-back, records and block table, [3] deflate and compaction of the
+ * zoom blocks.  All 0 when no level was written.  (pc_track_bigwig_export_timing keeps its six laps: the zoom levels
+ * run between its [3] and its [4].) */
+int pc_track_bigwig_export_zoom_timing(pc_track *t, double *ms4);
 
 #ifdef __cplusplus
 }

@@ -156,11 +156,14 @@ SIGNATURES = {
     "pc_deflate_zlib_mode": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int]),
     "pc_huffman_lengths": (_int, [_vp, _vp, _i64, _int, _vp]),
     "pc_track_export_bigwig": (_int, [_vp, _int, _i64, _i64, _int, _vp]),
+    "pc_track_export_bigwig_zoom": (_int, [_vp, _int, _i64, _i64, _int, _i64, _vp]),
     "pc_track_export_bigwig_read": (_int, [_vp, _vp, _i64]),
     "pc_track_set_length": (_int, [_vp, ctypes.c_char_p, _i64]),
     "pc_track_bigwig_export_stats": (_int, [_vp, _vp]),
     "pc_track_bigwig_export_block_types": (_int, [_vp, _vp]),
     "pc_track_bigwig_export_timing": (_int, [_vp, _vp]),
+    "pc_track_bigwig_export_zoom_stats": (_int, [_vp, _vp, _vp]),
+    "pc_track_bigwig_export_zoom_timing": (_int, [_vp, _vp]),
     "pc_track_add_bigwig": (_int, [_vp, _vp, _i64, ctypes.c_char_p, _int]),
     "pc_track_add_bigwig_path": (_int, [_vp, ctypes.c_char_p, _int]),
     "pc_track_bigwig_stats": (_int, [_vp, _vp]),
@@ -176,7 +179,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 
 def load():

@@ -1942,14 +1942,18 @@ int pb_huffman_lengths(const uint32_t *counts, int64_t n, int limit, uint8_t *le
 }
 
 // The serial bigWig writer: open, one add per contig (any order), finish, then the image and the statistics.
-void *pb_bigwig_write_open(int64_t items_per_slot, int64_t block_size, int compress) {
+// zoom: 0 no zoom levels, -1 the automatic first reduction, 8 .. 2^24 the first reduction (bigwig_write_host.h: "zoom levels")
+void *pb_bigwig_write_open_zoom(int64_t items_per_slot, int64_t block_size, int compress, int64_t zoom) {
     const std::string bad = pcbww::check_params(items_per_slot, block_size);
     if (!bad.empty()) { fail("pb_bigwig_write: " + bad); return nullptr; }
     if (compress < 0 || compress > 2) { fail("pb_bigwig_write: compress " + std::to_string(compress) + " is none of 0 (stored sections), 1 (fixed codes), 2 (dynamic codes)"); return nullptr; }
+    const std::string bad_zoom = pcbww::check_zoom(zoom);
+    if (!bad_zoom.empty()) { fail("pb_bigwig_write: " + bad_zoom); return nullptr; }
     pcbww::HostWriter *w = new pcbww::HostWriter();
-    w->items_per_slot = (uint32_t)items_per_slot; w->block_size = (uint32_t)block_size; w->compress = compress;
+    w->items_per_slot = (uint32_t)items_per_slot; w->block_size = (uint32_t)block_size; w->compress = compress; w->zoom = zoom;
     return w;
 }
+void *pb_bigwig_write_open(int64_t items_per_slot, int64_t block_size, int compress) { return pb_bigwig_write_open_zoom(items_per_slot, block_size, compress, 0); }
 void pb_bigwig_write_close(void *h) { delete static_cast<pcbww::HostWriter *>(h); }
 int pb_bigwig_write_add(void *h, const char *name, int64_t length, const double *cells, int64_t n) {
     pcbww::HostWriter *w = static_cast<pcbww::HostWriter *>(h);
@@ -1976,6 +1980,67 @@ int pb_bigwig_write_block_types(void *h, int64_t *out3) {
     pcbww::HostWriter *w = static_cast<pcbww::HostWriter *>(h);
     if (!w || !out3) return fail("pb_bigwig_write_block_types: bad arguments");
     for (int k = 0; k < 3; ++k) out3[k] = w->stats[5 + k];
+    return 0;
+}
+// the zoom levels of the file: *levels, and per level (at most max_levels of them) [0] the reduction, [1] records, [2] blocks,
+// [3] raw bytes of the blocks, [4] their bytes in the file
+int pb_bigwig_write_zoom_stats(void *h, int64_t *levels, int max_levels, int64_t *out5) {
+    pcbww::HostWriter *w = static_cast<pcbww::HostWriter *>(h);
+    if (!w || !levels || max_levels < 0 || (max_levels > 0 && !out5)) return fail("pb_bigwig_write_zoom_stats: bad arguments");
+    *levels = (int64_t)w->zoom_stats.size();
+    for (size_t k = 0; k < w->zoom_stats.size() && k < (size_t)max_levels; ++k) {
+        const pcbww::HostWriter::LevelStats &s = w->zoom_stats[k];
+        out5[5 * k] = s.reduction; out5[5 * k + 1] = s.records; out5[5 * k + 2] = s.blocks; out5[5 * k + 3] = s.raw_bytes; out5[5 * k + 4] = s.file_bytes;
+    }
+    return 0;
+}
+
+// The zoom levels of a bigWig file, read on the host (bigwig_write_host.h: zoom_headers, read_zoom_level).  A file that
+// is refused: "<name>: bigWig: <what>" (pb_last_error).
+namespace {
+struct ZoomRead { std::vector<pcbww::ZoomHeader> levels; pcbww::ZoomTable table; uint32_t uncompress_buf = 0; };
+// the file's structure and its zoom headers; false: refused
+bool zoom_open(const void *image, int64_t size, const char *name, const char *who, ZoomRead &z) {
+    if (size < 0 || (size > 0 && !image)) { fail(std::string(who) + ": bad arguments"); return false; }
+    pcbw::BigWig f;
+    const unsigned long long d = pcbw::parse((const uint8_t *)image, (uint64_t)size, f);
+    if (d != pcbw::kNoDefect) { fail(pcbw::defect_message(name, d)); return false; }
+    const std::string bad = pcbww::zoom_headers((const uint8_t *)image, (uint64_t)size, z.levels);
+    if (!bad.empty()) { fail(std::string(name ? name : "<memory>") + ": bigWig: " + bad); return false; }
+    z.uncompress_buf = f.uncompress_buf;
+    return true;
+}
+}   // namespace
+// *levels, and per level (at most max_levels of them) [0] the reduction, [1] dataOffset, [2] indexOffset, [3] records
+int pb_bigwig_zoom_info(const void *image, int64_t size, const char *name, int64_t *levels, int max_levels, int64_t *out4) {
+    if (!levels || max_levels < 0 || (max_levels > 0 && !out4)) return fail("pb_bigwig_zoom_info: bad arguments");
+    ZoomRead z;
+    if (!zoom_open(image, size, name, "pb_bigwig_zoom_info", z)) return -1;
+    *levels = (int64_t)z.levels.size();
+    for (size_t k = 0; k < z.levels.size() && k < (size_t)max_levels; ++k) {
+        out4[4 * k] = z.levels[k].reduction; out4[4 * k + 1] = (int64_t)z.levels[k].data; out4[4 * k + 2] = (int64_t)z.levels[k].index; out4[4 * k + 3] = z.levels[k].records;
+    }
+    return 0;
+}
+// the records of one level in file order, walked through the level's R-tree; NULL: refused
+void *pb_bigwig_zoom_read(const void *image, int64_t size, const char *name, int64_t level) {
+    ZoomRead *z = new ZoomRead();
+    if (!zoom_open(image, size, name, "pb_bigwig_zoom_read", *z)) { delete z; return nullptr; }
+    const std::string bad = pcbww::read_zoom_level((const uint8_t *)image, (uint64_t)size, z->uncompress_buf, z->levels, level, zlib_raw_inflate, z->table);
+    if (!bad.empty()) { fail(std::string(name ? name : "<memory>") + ": bigWig: " + bad); delete z; return nullptr; }
+    return z;
+}
+void pb_bigwig_zoom_close(void *h) { delete static_cast<ZoomRead *>(h); }
+int64_t pb_bigwig_zoom_rows(void *h) { return h ? (int64_t)static_cast<ZoomRead *>(h)->table.chrom.size() : -1; }
+int pb_bigwig_zoom_fill(void *h, uint32_t *chrom, uint32_t *start, uint32_t *end, uint32_t *valid, float *mn, float *mx, float *sum, float *sumsq) {
+    ZoomRead *z = static_cast<ZoomRead *>(h);
+    if (!z) return fail("pb_bigwig_zoom_fill: NULL handle");
+    const pcbww::ZoomTable &t = z->table;
+    const size_t n = t.chrom.size() * 4;
+    if (n) {
+        std::memcpy(chrom, t.chrom.data(), n); std::memcpy(start, t.start.data(), n); std::memcpy(end, t.end.data(), n); std::memcpy(valid, t.valid.data(), n);
+        std::memcpy(mn, t.mn.data(), n); std::memcpy(mx, t.mx.data(), n); std::memcpy(sum, t.sum.data(), n); std::memcpy(sumsq, t.sumsq.data(), n);
+    }
     return 0;
 }
 

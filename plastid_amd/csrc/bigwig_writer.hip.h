@@ -1,15 +1,21 @@
-// Writing bigWig files from HBM, host side (revision 20): pc_track_export_bigwig / _read / pc_track_bigwig_export_stats /
-// _block_types / _timing and pc_track_set_length of include/plastid_counts.h.  One export is a BigWigExport taken through its phases:
+// Writing bigWig files from HBM, host side (revision 21): pc_track_export_bigwig / _zoom / _read / pc_track_bigwig_export_stats /
+// _block_types / _timing / _zoom_stats / _zoom_timing and pc_track_set_length of include/plastid_counts.h.  One export is a BigWigExport taken through its phases:
 //   1  item heads over the cells of the strand's contigs in sorted order, their exclusive sum, the items in front of
 //      every contig (one read-back of a word per contig: the host cuts the sections from it);
 //   2  the items into their columns and into the raw sections, the section headers, the total summary;
 //   3  k_zlib_deflate over the raw sections (compress), 4 the sizes, their exclusive sum, the compaction;
-//   5  the section table (bounds and sizes) comes back, the host lays out offsets and both trees
-//      (bigwig_write_host.h: the container code of the host writer), and the blocks cross PCIe once, straight into their
-//      place in the image -- through the transfer ring when they are large.
+//   Z  (zoom != 0, the file has items) the zoom levels from the item columns of phase 2 (bigwig_zoom_kernels.hip.h): the
+//      window grid of all candidate levels (bigwig_write_host.h: zoom_plan), level 0, the levels above it, the flags'
+//      exclusive sum; the records in front of every (level, contig) come back (one word each: the host ends the pyramid
+//      and cuts the blocks by them); the records into raw blocks, the block table, k_zlib_deflate and the compaction
+//      over the blocks (compress);
+//   5  the section table (bounds and sizes) and the zoom levels' block tables come back, the host lays out offsets and
+//      all trees (bigwig_write_host.h: the container code of the host writer), and the blocks cross PCIe once, straight
+//      into their place in the image -- through the transfer ring when they are large.
 // What is refused is refused before anything is built, and nothing is left behind.
 // Part of the one translation unit of plastid_counts.hip (behind deflate_encoder.hip.h).
 #include "bigwig_write_kernels.hip.h"
+#include "bigwig_zoom_kernels.hip.h"
 
 namespace {
 
@@ -39,6 +45,22 @@ struct BigWigExport {
     DevBuf<uint8_t> d_raw, d_slots, d_blocks, d_tmp;
     DevBuf<uint64_t> d_slot_off;
     DevBuf<unsigned long long> d_res;      // the sizes, then the offsets of the streams
+    // the zoom levels
+    int64_t zoom = 0;                      // 0: none, -1: the automatic first reduction, else the first reduction
+    LapEvents<5> zev;                      // start | level 0 | levels above | records + block table | encoded + compacted
+    ww::ZoomPlan zplan;
+    int zlevels = 0;                       // the levels written
+    int64_t zrecords = 0, znblk = 0;       // their records and blocks
+    std::vector<int64_t> zrec;             // the records in front of every (level, contig)
+    std::vector<ww::ZoomBlock> zblk;       // the blocks of the written levels, level by level
+    std::vector<int64_t> zblk_first;       // the blocks in front of every written level, and their number
+    DevBuf<int64_t> d_zrows, d_zitem_first, d_zrec, d_zin;
+    DevBuf<uint32_t> d_zsizes, d_zvalid, d_zkmin, d_zkmax, d_zflags, d_zidx, d_zblk_start, d_zblk_end, d_zstored;
+    DevBuf<double> d_zsum, d_zsumsq;
+    DevBuf<ww::ZoomBlock> d_zblk;
+    DevBuf<uint8_t> d_zraw, d_zslots, d_zblocks;
+    DevBuf<uint64_t> d_zslot_off;
+    DevBuf<unsigned long long> d_zres;
 };
 
 // Phase 1: heads, exclusive sum, items in front of every contig; the host cuts the sections.
@@ -115,13 +137,92 @@ int bwx_deflate(BigWigExport &c) {
     return PC_OK;
 }
 
+// Phase Z: the zoom levels.  The item columns of phase 2 are in place; c.total has arrived when the stream has drained.
+int bwx_zoom(BigWigExport &c) {
+    hipStream_t st = c.st;
+    HIP_TRY(hipStreamSynchronize(st));     // (the total summary: the automatic first reduction reads it)
+    const std::string bad = ww::zoom_plan(c.contigs, ww::zoom_first_reduction(c.zoom, (uint64_t)c.N, (uint64_t)c.total.valid), c.zplan);
+    if (!bad.empty()) return fail(PC_ERR_ARG, "pc_track_export_bigwig: %s", bad.c_str());
+    const ww::ZoomGrid &g = c.zplan.g;
+    const int64_t W = c.zplan.windows(), nrow = (int64_t)c.zplan.rows.size();
+    std::vector<uint32_t> sizes((size_t)c.K);
+    std::vector<int64_t> item_first((size_t)c.K + 1);
+    for (int k = 0; k < c.K; ++k) sizes[(size_t)k] = c.contigs[(size_t)k].size;
+    for (int k = 0; k <= c.K; ++k) item_first[(size_t)k] = c.ranges[(size_t)k].run_base;
+    DrainOnExit drained{st};               // (sizes and item_first are read by what is queued below)
+    int rc = PC_OK;
+    room(rc, c.d_zvalid, (size_t)W); room(rc, c.d_zkmin, (size_t)W); room(rc, c.d_zkmax, (size_t)W); room(rc, c.d_zsum, (size_t)W); room(rc, c.d_zsumsq, (size_t)W);
+    room(rc, c.d_zflags, (size_t)W + 1); room(rc, c.d_zidx, (size_t)W + 1); room(rc, c.d_zrec, (size_t)nrow);
+    if (rc != PC_OK) return rc;
+    PC_TRY(c.d_zrows.upload(c.zplan.rows, st)); PC_TRY(c.d_zsizes.upload(sizes, st)); PC_TRY(c.d_zitem_first.upload(item_first, st));
+    const ww::ZoomColumns col{c.d_zvalid.p, c.d_zkmin.p, c.d_zkmax.p, c.d_zsum.p, c.d_zsumsq.p};
+    HIP_TRY(hipEventRecord(c.zev[0], st));
+    hipLaunchKernelGGL(ww::k_bwz_level0, dim3(grid256(g.level_off[1])), dim3(256), 0, st, g, c.d_zrows.p, c.d_zsizes.p, c.d_zitem_first.p, c.d_istart.p, c.d_iend.p, c.d_ival.p,
+                       col, c.d_zflags.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c.zev[1], st));
+    for (int k = 1; k < g.levels; ++k) {
+        hipLaunchKernelGGL(ww::k_bwz_reduce, dim3(grid256(g.level_off[k + 1] - g.level_off[k])), dim3(256), 0, st, g, k, c.d_zrows.p, col, c.d_zflags.p);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(c.zev[2], st));
+    HIP_TRY(hipMemsetAsync(c.d_zflags.p + W, 0, 4, st));
+    PC_TRY(cub_run(c.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, c.d_zflags.p, c.d_zidx.p, (int)(W + 1), st); }));
+    hipLaunchKernelGGL(ww::k_bwz_bases, dim3(grid256(nrow)), dim3(256), 0, st, c.d_zrows.p, nrow, c.d_zidx.p, c.d_zrec.p);
+    HIP_TRY(hipGetLastError());
+    c.zrec.resize((size_t)nrow);
+    HIP_TRY(hipMemcpyAsync(c.zrec.data(), c.d_zrec.p, (size_t)nrow * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    c.zlevels = ww::zoom_levels_written(c.zplan, c.zrec);
+    c.zrecords = c.zrec[(size_t)(c.zlevels - 1) * (size_t)(c.K + 1) + (size_t)c.K];
+    for (int k = 0; k < c.zlevels; ++k) {
+        c.zblk_first.push_back((int64_t)c.zblk.size());
+        ww::zoom_cut_blocks(c.zplan, c.zrec, k, ww::zoom_block_records(c.items_per_slot), c.zblk);
+    }
+    c.znblk = (int64_t)c.zblk.size();
+    c.zblk_first.push_back(c.znblk);
+    room(rc, c.d_zraw, (size_t)c.zrecords * ww::kZoomRecordBytes + 64); room(rc, c.d_zblk_start, (size_t)c.znblk); room(rc, c.d_zblk_end, (size_t)c.znblk);
+    room(rc, c.d_zin, 2 * (size_t)c.znblk);
+    if (rc != PC_OK) return rc;
+    PC_TRY(c.d_zblk.upload(c.zblk, st));
+    hipLaunchKernelGGL(ww::k_bwz_records, dim3(grid256(g.level_off[c.zlevels])), dim3(256), 0, st, g, g.level_off[c.zlevels], c.d_zrows.p, c.d_zsizes.p, col, c.d_zflags.p,
+                       c.d_zidx.p, c.d_zraw.p);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(ww::k_bwz_blocks, dim3(grid256(c.znblk)), dim3(256), 0, st, c.d_zblk.p, c.znblk, c.d_zraw.p, c.d_zblk_start.p, c.d_zblk_end.p, c.d_zin.p,
+                       c.d_zin.p + c.znblk);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(c.zev[3], st));
+    if (c.compress) {
+        std::vector<uint64_t> slot_off((size_t)c.znblk);
+        uint64_t slots = 0;
+        for (int64_t b = 0; b < c.znblk; ++b) { slot_off[(size_t)b] = slots; slots += (uint64_t)ww::kZoomRecordBytes * c.zblk[(size_t)b].count + pcdeflate::kSlotPad; }
+        room(rc, c.d_zslots, (size_t)slots + 64); room(rc, c.d_zblocks, (size_t)(c.zrecords * (int64_t)ww::kZoomRecordBytes + (int64_t)pcdeflate::kStreamOverhead * c.znblk) + 64);
+        room(rc, c.d_zres, 2 * (size_t)c.znblk); room(rc, c.d_zstored, (size_t)c.znblk);
+        if (rc != PC_OK) return rc;
+        PC_TRY(c.d_zslot_off.upload(slot_off, st));
+        PC_TRY(queue_zlib_deflate(st, c.d_zraw.p, c.d_zin.p, c.d_zin.p + c.znblk, c.d_zslot_off.p, c.znblk, c.d_zslots.p, c.d_zres.p, c.d_zres.p + c.znblk, c.d_zstored.p,
+                                  c.d_tmp, c.d_zblocks.p, (uint32_t)c.compress));
+        HIP_TRY(hipEventRecord(c.zev[4], st));
+        HIP_TRY(hipStreamSynchronize(st));   // (slot_off goes out of scope)
+    } else HIP_TRY(hipEventRecord(c.zev[4], st));
+    drained.armed = false;                 // (the stream has drained behind the record counts' read-back)
+    return PC_OK;
+}
+
 // Phase 5: the section table comes back, the host lays the file out, the blocks land in their place.
 int bwx_layout_and_read(BigWigExport &c) {
     hipStream_t st = c.st;
     pc_track *t = c.t;
     std::vector<uint32_t> sec_start((size_t)c.nsec), sec_end((size_t)c.nsec), stored((size_t)c.nsec);
     std::vector<unsigned long long> sizes((size_t)c.nsec);
+    std::vector<uint32_t> zstart((size_t)c.znblk), zend((size_t)c.znblk);
+    std::vector<unsigned long long> zsizes((size_t)c.znblk);
     const auto t0 = std::chrono::steady_clock::now();
+    if (c.znblk > 0) {
+        HIP_TRY(hipMemcpyAsync(zstart.data(), c.d_zblk_start.p, (size_t)c.znblk * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(zend.data(), c.d_zblk_end.p, (size_t)c.znblk * 4, hipMemcpyDeviceToHost, st));
+        if (c.compress) HIP_TRY(hipMemcpyAsync(zsizes.data(), c.d_zres.p, (size_t)c.znblk * 8, hipMemcpyDeviceToHost, st));
+    }
     if (c.nsec > 0) {
         HIP_TRY(hipMemcpyAsync(sec_start.data(), c.d_sec_start.p, (size_t)c.nsec * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(sec_end.data(), c.d_sec_end.p, (size_t)c.nsec * 4, hipMemcpyDeviceToHost, st));
@@ -145,24 +246,52 @@ int bwx_layout_and_read(BigWigExport &c) {
     }
     ww::Summary sm;
     sm.valid = c.total.valid; sm.kmin = c.total.kmin; sm.kmax = c.total.kmax; sm.sum = c.total.sum; sm.sumsq = c.total.sumsq;
+    // the zoom levels: every block's bounds and bytes, level by level
+    std::vector<ww::ZoomLevel> levels((size_t)c.zlevels);
+    for (int k = 0; k < c.zlevels; ++k) {
+        const size_t row = (size_t)k * (size_t)(c.K + 1);
+        levels[(size_t)k].reduction = c.zplan.g.r[k];
+        levels[(size_t)k].records = (uint64_t)(c.zrec[row + (size_t)c.K] - c.zrec[row]);
+        int64_t *zs = t->bwz_stats[k];
+        zs[0] = c.zplan.g.r[k]; zs[1] = (int64_t)levels[(size_t)k].records; zs[2] = c.zblk_first[(size_t)k + 1] - c.zblk_first[(size_t)k]; zs[3] = zs[1] * (int64_t)ww::kZoomRecordBytes; zs[4] = 0;
+        for (int64_t b = c.zblk_first[(size_t)k]; b < c.zblk_first[(size_t)k + 1]; ++b) {
+            const uint32_t raw = ww::kZoomRecordBytes * c.zblk[(size_t)b].count;
+            levels[(size_t)k].blocks.push_back({c.zblk[(size_t)b].chrom, zstart[(size_t)b], zend[(size_t)b], c.compress ? (uint64_t)zsizes[(size_t)b] : (uint64_t)raw});
+            zs[4] += (int64_t)levels[(size_t)k].blocks.back().size;
+            largest = std::max(largest, raw);
+        }
+    }
+    t->bwz_levels = c.zlevels;
     ww::Container box;
-    ww::build_container(c.contigs, sections, c.block_size, c.compress ? largest : 0u, c.N > 0 ? &sm : nullptr, box);
+    ww::build_container(c.contigs, sections, c.block_size, c.compress ? largest : 0u, c.N > 0 ? &sm : nullptr, box, levels);
     c.block_bytes = (int64_t)box.block_bytes;
-    t->bwx_image.resize(box.front.size() + (size_t)c.block_bytes + box.back.size());
-    memcpy(t->bwx_image.data(), box.front.data(), box.front.size());
-    memcpy(t->bwx_image.data() + box.front.size() + (size_t)c.block_bytes, box.back.data(), box.back.size());
+    t->bwx_image.resize((size_t)box.total());
+    // the host's pieces into their places; the blocks' places and where they stand in HBM
+    std::vector<TransferJob> job;
+    size_t at = 0, most = 0;
+    auto host_piece = [&](const std::vector<uint8_t> &v) { memcpy(t->bwx_image.data() + at, v.data(), v.size()); at += v.size(); };
+    auto block_piece = [&](const uint8_t *src, uint64_t bytes) {
+        if (bytes) job.push_back({t->bwx_image.data() + at, src, (size_t)bytes});
+        at += (size_t)bytes; most = std::max(most, (size_t)bytes);
+    };
+    host_piece(box.front);
+    block_piece(c.compress ? c.d_blocks.p : c.d_raw.p, box.block_bytes);
+    host_piece(box.back);
+    uint64_t zat = 0;
+    for (int k = 0; k < c.zlevels; ++k) {
+        host_piece(box.zoom[(size_t)k].front);
+        block_piece((c.compress ? c.d_zblocks.p : c.d_zraw.p) + zat, box.zoom[(size_t)k].block_bytes);
+        zat += box.zoom[(size_t)k].block_bytes;
+        host_piece(box.zoom[(size_t)k].back);
+    }
     const auto t2 = std::chrono::steady_clock::now();
-    if (c.block_bytes > 0) {
-        void *dst = t->bwx_image.data() + box.front.size();
-        const void *src = c.compress ? (const void *)c.d_blocks.p : (const void *)c.d_raw.p;
-        const size_t bytes = (size_t)c.block_bytes;
+    if (!job.empty()) {
         const char *knob = getenv("PC_STAGE_SLICE");   // (test knob: the ring for every size, in pieces of so many 4 KiB pages)
-        if (bytes >= 4 * TransferRing::kPiece || knob) {
-            const std::vector<TransferJob> job{{dst, src, bytes}};
+        if (most >= 4 * TransferRing::kPiece || knob) {
             const size_t piece = knob ? (size_t)std::max<int64_t>(1, std::min<int64_t>(atoll(knob), 4096)) * 4096 : TransferRing::kPiece;
             PC_TRY(TransferRing::of(t->e->device).run(t->e->device, job, piece, knob != nullptr, true));
         } else {
-            HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+            for (const TransferJob &j : job) HIP_TRY(hipMemcpyAsync(j.dst, j.src, j.bytes, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
         }
     }
@@ -177,13 +306,20 @@ int bwx_layout_and_read(BigWigExport &c) {
 extern "C" {
 
 int pc_track_export_bigwig(pc_track *t, int strand_slot, int64_t items_per_slot, int64_t block_size, int compress, int64_t *bytes) {
+    return pc_track_export_bigwig_zoom(t, strand_slot, items_per_slot, block_size, compress, 0, bytes);
+}
+
+int pc_track_export_bigwig_zoom(pc_track *t, int strand_slot, int64_t items_per_slot, int64_t block_size, int compress, int64_t zoom, int64_t *bytes) {
     if (!t || !bytes) return fail(PC_ERR_ARG, "pc_track_export_bigwig: bad arguments");
     if (strand_slot < 0 || strand_slot >= t->tab.nstrands) return fail(PC_ERR_ARG, "pc_track_export_bigwig: strand slot %d of %d", strand_slot, t->tab.nstrands);
     const std::string bad = ww::check_params(items_per_slot, block_size);
     if (!bad.empty()) return fail(PC_ERR_ARG, "pc_track_export_bigwig: %s", bad.c_str());
     if (compress < 0 || compress > 2) return fail(PC_ERR_ARG, "pc_track_export_bigwig: compress %d is none of 0 (stored sections), 1 (fixed codes), 2 (dynamic codes)", compress);
+    const std::string bad_zoom = ww::check_zoom(zoom);
+    if (!bad_zoom.empty()) return fail(PC_ERR_ARG, "pc_track_export_bigwig: %s", bad_zoom.c_str());
     pc_engine *e = t->e;
     BigWigExport c{t, strand_slot, (uint32_t)items_per_slot, (uint32_t)block_size, compress, e->stream};
+    c.zoom = zoom;
     c.slots = t->tab.export_slots(strand_slot);
     c.K = (int)c.slots.ids.size();
     for (int k = 0; k < c.K; ++k) {
@@ -201,20 +337,26 @@ int pc_track_export_bigwig(pc_track *t, int strand_slot, int64_t items_per_slot,
     PoolScope pool_scope(&e->pool);
     for (auto &x : t->bwx_stats) x = 0;
     for (auto &x : t->bwx_ms) x = 0.0;
+    for (auto &x : t->bwz_ms) x = 0.0;
+    t->bwz_levels = 0;
     t->bwx_bytes = -1;
     std::vector<uint8_t>().swap(t->bwx_image);
     *bytes = 0;
     PC_TRY(c.ev.create());
+    if (c.zoom) PC_TRY(c.zev.create());
     DrainOnExit drained{c.st};
     PC_TRY(bwx_items_and_sections(c));
     if (c.N > 0) PC_TRY(bwx_fill_sections(c)); else HIP_TRY(hipEventRecord(c.ev[2], c.st));
     if (c.N > 0 && c.compress) PC_TRY(bwx_deflate(c)); else HIP_TRY(hipEventRecord(c.ev[3], c.st));
     HIP_TRY(hipEventRecord(c.ev[4], c.st));
+    const bool zoomed = c.zoom && c.N > 0;      // (a file without items has no levels)
+    if (zoomed) PC_TRY(bwx_zoom(c));
     HIP_TRY(hipStreamSynchronize(c.st));
     const int rc = bwx_layout_and_read(c);
-    if (rc != PC_OK) { std::vector<uint8_t>().swap(t->bwx_image); return rc; }
+    if (rc != PC_OK) { std::vector<uint8_t>().swap(t->bwx_image); t->bwz_levels = 0; return rc; }
     drained.armed = false;
     c.ev.laps(t->bwx_ms, 4);
+    if (zoomed) c.zev.laps(t->bwz_ms, 4);
     t->bwx_stats[0] = c.K; t->bwx_stats[1] = c.N; t->bwx_stats[2] = c.nsec; t->bwx_stats[3] = c.raw_bytes; t->bwx_stats[4] = c.block_bytes; t->bwx_stats[5] = c.stored; t->bwx_stats[6] = c.fixed; t->bwx_stats[7] = c.dynamic;
     t->bwx_bytes = (int64_t)t->bwx_image.size();
     *bytes = t->bwx_bytes;
@@ -246,6 +388,20 @@ int pc_track_bigwig_export_stats(pc_track *t, int64_t *out6) {
 int pc_track_bigwig_export_block_types(pc_track *t, int64_t *out3) {
     if (!t || !out3) return fail(PC_ERR_ARG, "pc_track_bigwig_export_block_types: bad arguments");
     out3[0] = t->bwx_stats[5]; out3[1] = t->bwx_stats[6]; out3[2] = t->bwx_stats[7];
+    return PC_OK;
+}
+
+int pc_track_bigwig_export_zoom_stats(pc_track *t, int64_t *levels, int64_t *out50) {
+    if (!t || !levels || !out50) return fail(PC_ERR_ARG, "pc_track_bigwig_export_zoom_stats: bad arguments");
+    *levels = t->bwz_levels;
+    for (int k = 0; k < t->bwz_levels; ++k)
+        for (int j = 0; j < 5; ++j) out50[5 * k + j] = t->bwz_stats[k][j];
+    return PC_OK;
+}
+
+int pc_track_bigwig_export_zoom_timing(pc_track *t, double *ms4) {
+    if (!t || !ms4) return fail(PC_ERR_ARG, "pc_track_bigwig_export_zoom_timing: bad arguments");
+    for (int k = 0; k < 4; ++k) ms4[k] = t->bwz_ms[k];
     return PC_OK;
 }
 

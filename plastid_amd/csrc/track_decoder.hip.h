@@ -41,6 +41,9 @@ struct pc_track {
     int64_t bwx_bytes = -1;
     int64_t bwx_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // contigs, items, sections, raw bytes, block bytes, sections as stored, fixed, dynamic blocks
     double bwx_ms[6] = {0, 0, 0, 0, 0, 0};       // runs + items | sections + summary | deflate + adler | sizes + compaction | read-back | host layout
+    int bwz_levels = 0;                          // the zoom levels of that file; per level: reduction, records, blocks, raw bytes, file bytes
+    int64_t bwz_stats[10][5] = {};
+    double bwz_ms[4] = {0, 0, 0, 0};             // level 0 | levels above | flags' sum + records + block table | deflate + compaction
 };
 
 // an engine that is destroyed takes its tracks with it (pc_destroy): their cells come from its pool

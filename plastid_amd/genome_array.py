@@ -856,7 +856,7 @@ class BAMGenomeArray(object):
         with a non-zero count, 1-based (`window_size` does not show in the text).  See :meth:`to_bedgraph`."""
         self._export(1, fh, trackname, strand, window_size, printer, kwargs, _batch_elems)
 
-    def to_bigwig(self, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True, _batch_elems=None):
+    def to_bigwig(self, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True, zoom=False, _batch_elems=None):
         """Write the counts of `strand` under the current mapping rule as a bigWig file (a path, or a file object opened
         in binary mode).  No reference counterpart: the reference writes bedGraph text and leaves the conversion to
         Kent's ``bedGraphToBigWig``.
@@ -864,16 +864,17 @@ class BAMGenomeArray(object):
         The rule must give one row per position (``TypeError`` otherwise, before anything is written).  A temporary
         one-strand :class:`~plastid_amd.track.GenomeArray` on this array's engine is filled device to device, whole
         contigs ``0 .. length``, in the batches of :meth:`to_bedgraph`, and exported by
-        :meth:`~plastid_amd.track.GenomeArray.to_bigwig` (which see for `items_per_slot`, `block_size`, `compress`): no
-        count visits the host.  The items are the maximal runs of equal non-zero count -- no window cuts them -- and
+        :meth:`~plastid_amd.track.GenomeArray.to_bigwig` (which see for `items_per_slot`, `block_size`, `compress` and
+        `zoom`, the zoom levels: ``False``, ``True`` or the first reduction): no count visits the host.  The items are the maximal runs of equal non-zero count -- no window cuts them -- and
         with ``set_normalize(True)`` the values are the normalised ones, as :meth:`to_bedgraph` prints them.
         While it runs it takes 8 bytes of HBM per genome position for the temporary array, beside the counts of a
         batch.  :func:`plastid_amd.track.write_bigwig` writes the same file on the host from count vectors."""
         import io
-        from .track import GenomeArray, _check_bigwig_params, _compress_mode
+        from .track import GenomeArray, _check_bigwig_params, _compress_mode, _zoom_mode
         assert strand in self.strands()
         _check_bigwig_params(items_per_slot, block_size)
         _compress_mode(compress)             # (a bad value is a ValueError before anything is counted)
+        _zoom_mode(zoom)
         if isinstance(path_or_file, io.TextIOBase):
             raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
         self._one_row_rule()
@@ -893,8 +894,9 @@ class BAMGenomeArray(object):
                     plan.close()
             for c, n in zip(chroms, sizes):   # (a contig written up to its end has grown by the reference's rule: the file takes the BAM's lengths)
                 _lib.check(ga._lib.pc_track_set_length(ga._h, os.fsencode(c), n), "pc_track_set_length")
-            ga.to_bigwig(path_or_file, strand, items_per_slot=items_per_slot, block_size=block_size, compress=compress)
+            ga.to_bigwig(path_or_file, strand, items_per_slot=items_per_slot, block_size=block_size, compress=compress, zoom=zoom)
             self._bigwig_export_stats, self._bigwig_export_timing = ga.bigwig_export_stats(block_types=True), ga.bigwig_export_timing()
+            self._bigwig_export_zoom_stats = ga.bigwig_export_zoom_stats()
         finally:
             ga.close()
 
@@ -909,6 +911,10 @@ class BAMGenomeArray(object):
     def bigwig_export_timing(self):
         """Of the last :meth:`to_bigwig`: what :meth:`plastid_amd.track.GenomeArray.bigwig_export_timing` reports."""
         return dict(getattr(self, "_bigwig_export_timing", {}))
+
+    def bigwig_export_zoom_stats(self):
+        """Of the last :meth:`to_bigwig`: what :meth:`plastid_amd.track.GenomeArray.bigwig_export_zoom_stats` reports."""
+        return [dict(x) for x in getattr(self, "_bigwig_export_zoom_stats", [])]
 
     def export_stats(self):
         """Of the last ``to_bedgraph`` / ``to_variable_step``: lines behind the track line, runs of any value (bedGraph) or

@@ -560,7 +560,7 @@ class GenomeArray(object):
         check(self._lib.pc_track_export_timing(self._h, out.ctypes.data))
         return dict(zip(("slot_sums", "runs", "listed_values", "lengths", "format", "read_back"), (float(x) for x in out)))
 
-    def to_bigwig(self, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True):
+    def to_bigwig(self, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True, zoom=False):
         """Write `strand` as a bigWig file (a path, or a file object opened in binary mode; a text-mode file is a
         ``TypeError``).  No reference counterpart: the reference reads bigWig and does not write it.
 
@@ -572,17 +572,31 @@ class GenomeArray(object):
         trees, `compress`: ``True`` or ``"fixed"``: every section through the GPU's zlib encoder
         (``csrc/deflate_kernels.hip.h``: LZ77 under the fixed Huffman codes, or a stored block); ``"dynamic"``: the same
         matches under Huffman codes built for every section, never larger and on count data about a third smaller;
-        ``False``: stored sections; anything else is a ``ValueError``.  No zoom levels: readers fall back to the full
-        data.  Items, sections, summary and blocks are built in HBM; the host lays out the header and both trees.  The
-        file is the one :func:`write_bigwig` gives for ``to_host()``."""
+        ``False``: stored sections; anything else is a ``ValueError``.  Items, sections, summary and blocks are built in
+        HBM; the host lays out the header and the trees.
+
+        `zoom`: ``False`` (the default): no zoom levels, readers fall back to the full data for every summary.  ``True``:
+        a pyramid of summary levels on a fixed grid (``csrc/bigwig_write_host.h``, "zoom levels";
+        ``csrc/bigwig_zoom_kernels.hip.h``): window ``w`` of level ``k`` on a contig covers
+        ``[w * r_k, min((w + 1) * r_k, size))`` with ``r_k = r0 * 4**k``, at most 10 levels, ``r_k <= 2**30``; a window
+        with data gives one 32-byte record (valid, min, max, sum, sum of squares); level 0 is written whenever the file
+        has items and level ``k + 1`` while it has fewer records than level ``k``.  ``r0 = 4 * max(10, valid // items)``
+        capped at ``2**20``; an ``int`` in ``8 .. 2**24`` is ``r0`` itself; anything else is a ``ValueError``.  Every
+        ``min(items_per_slot, 768)`` records of a contig form one block, encoded as the sections are.  Kent's readers
+        (``bigWigSummary``, genome browsers) answer summary queries from these levels; the windows are not where Kent's
+        own writer would put them.  The file is the one :func:`write_bigwig` gives for ``to_host()``."""
         assert strand in self._strands
         _check_bigwig_params(items_per_slot, block_size)
-        mode = _compress_mode(compress)
+        mode, zoom_mode = _compress_mode(compress), _zoom_mode(zoom)
         if isinstance(path_or_file, io.TextIOBase):
             raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
         nbytes = ctypes.c_int64(0)
-        check(self._lib.pc_track_export_bigwig(self._h, self._strands.index(strand), int(items_per_slot), int(block_size), mode,
-                                               ctypes.byref(nbytes)), "pc_track_export_bigwig")
+        if zoom_mode:
+            check(self._lib.pc_track_export_bigwig_zoom(self._h, self._strands.index(strand), int(items_per_slot), int(block_size), mode, zoom_mode,
+                                                        ctypes.byref(nbytes)), "pc_track_export_bigwig_zoom")
+        else:
+            check(self._lib.pc_track_export_bigwig(self._h, self._strands.index(strand), int(items_per_slot), int(block_size), mode,
+                                                   ctypes.byref(nbytes)), "pc_track_export_bigwig")
         image = np.empty(max(int(nbytes.value), 1), np.uint8)
         check(self._lib.pc_track_export_bigwig_read(self._h, image.ctypes.data, int(nbytes.value)), "pc_track_export_bigwig_read")
         sink, close = _binary_sink(path_or_file)
@@ -613,6 +627,21 @@ class GenomeArray(object):
         out = np.zeros(6, np.float64)
         check(self._lib.pc_track_bigwig_export_timing(self._h, out.ctypes.data))
         return dict(zip(("runs_items", "sections_summary", "deflate_adler", "sizes_compaction", "read_back", "host_layout"), (float(x) for x in out)))
+
+    def bigwig_export_zoom_stats(self):
+        """Of the last :meth:`to_bigwig`: one dict per zoom level written -- ``reduction``, ``records``, ``blocks``,
+        ``raw_bytes`` of the blocks and their ``file_bytes`` (an empty list for ``zoom=False``)."""
+        n = ctypes.c_int64(0)
+        out = np.zeros(5 * ZOOM_MAX_LEVELS, np.int64)
+        check(self._lib.pc_track_bigwig_export_zoom_stats(self._h, ctypes.byref(n), out.ctypes.data))
+        return [dict(zip(BIGWIG_ZOOM_STATS, (int(x) for x in out[5 * k:5 * k + 5]))) for k in range(int(n.value))]
+
+    def bigwig_export_zoom_timing(self):
+        """Milliseconds of the zoom levels of the last :meth:`to_bigwig` on the engine's stream: level 0 from the items,
+        the levels above, flags + record numbers + records + block tables, deflate + compaction of the zoom blocks."""
+        out = np.zeros(4, np.float64)
+        check(self._lib.pc_track_bigwig_export_zoom_timing(self._h, out.ctypes.data))
+        return dict(zip(("level0", "upper_levels", "records", "deflate_compaction"), (float(x) for x in out)))
 
     # ---- the query side
     def _gather(self, contig, slot, start, end, out_off, out_step, total):
@@ -788,6 +817,82 @@ def read_bigwig(path_or_bytes):
     return BigWigTable(names, lengths, chrom, start, stop, value, block, block_off, block_size, dict(zip(keys, (int(x) for x in stats))))
 
 
+def _bind_zoom_readers(L):
+    if not hasattr(L.pb_bigwig_zoom_info, "_bound"):
+        vp = ctypes.c_void_p
+        L.pb_bigwig_zoom_info.argtypes = [vp, ctypes.c_int64, ctypes.c_char_p, vp, ctypes.c_int, vp]
+        L.pb_bigwig_zoom_read.restype = vp
+        L.pb_bigwig_zoom_read.argtypes = [vp, ctypes.c_int64, ctypes.c_char_p, ctypes.c_int64]
+        L.pb_bigwig_zoom_close.argtypes = [vp]
+        L.pb_bigwig_zoom_rows.restype = ctypes.c_int64
+        L.pb_bigwig_zoom_rows.argtypes = [vp]
+        L.pb_bigwig_zoom_fill.argtypes = [vp] * 9
+        L.pb_bigwig_zoom_info._bound = True
+
+
+def _bigwig_bytes(path_or_bytes):
+    """``(ctypes pointer or None, size, name, keep-alive)`` of a bigWig file given as a path or as its bytes."""
+    if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+        data, name = bytes(path_or_bytes), "<memory>"
+    else:
+        data, name = _text_of(path_or_bytes)
+    buf = ctypes.create_string_buffer(data, len(data)) if data else None
+    return (ctypes.cast(buf, ctypes.c_void_p) if buf is not None else None), len(data), os.fsencode(name), buf
+
+
+def bigwig_zoom_info(path_or_bytes):
+    """The zoom levels of a bigWig file (a path, or its bytes), without a GPU: a list of ``(reduction, data_offset,
+    index_offset, records)``, one per zoom header in the file's order -- ``data_offset`` points at the level's u32 record
+    count, ``index_offset`` at its R-tree.  Empty for a file without zoom levels.  ``ValueError("<path>: bigWig: <what>")``
+    for a file that is refused."""
+    from .bam import _load
+    L = _load()
+    _bind_zoom_readers(L)
+    ptr, size, name, _keep = _bigwig_bytes(path_or_bytes)
+    n = ctypes.c_int64(0)
+    if L.pb_bigwig_zoom_info(ptr, size, name, ctypes.byref(n), 0, None) != 0:
+        raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    out = np.zeros(4 * max(int(n.value), 1), np.int64)
+    if L.pb_bigwig_zoom_info(ptr, size, name, ctypes.byref(n), int(n.value), out.ctypes.data) != 0:
+        raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    return [tuple(int(x) for x in out[4 * k:4 * k + 4]) for k in range(int(n.value))]
+
+
+class BigWigZoomTable(object):
+    """What :func:`read_bigwig_zoom` returns: the records of one zoom level in file order, as columns: ``chrom_id``,
+    ``start``, ``end``, ``valid`` (uint32) and ``min``, ``max``, ``sum``, ``sumsq`` (float32)."""
+    COLUMNS = ("chrom_id", "start", "end", "valid", "min", "max", "sum", "sumsq")
+
+    def __init__(self, columns):
+        for k, v in zip(self.COLUMNS, columns):
+            setattr(self, k, v)
+
+    def __len__(self):
+        return len(self.chrom_id)
+
+
+def read_bigwig_zoom(path_or_bytes, level):
+    """The records of zoom level `level` of a bigWig file (a path, or its bytes) in file order, walked through that
+    level's R-tree and inflated with zlib on the host (``pb_bigwig_zoom_read``; ``csrc/bigwig_write_host.h``:
+    ``read_zoom_level``): a :class:`BigWigZoomTable`.  ``ValueError("<path>: bigWig: <what>")`` for a level the file does
+    not have and for a file or a level that is refused."""
+    from .bam import _load
+    L = _load()
+    _bind_zoom_readers(L)
+    ptr, size, name, _keep = _bigwig_bytes(path_or_bytes)
+    h = L.pb_bigwig_zoom_read(ptr, size, name, int(level))
+    if not h:
+        raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    try:
+        n = int(L.pb_bigwig_zoom_rows(h))
+        cols = [np.zeros(n, np.uint32) for _ in range(4)] + [np.zeros(n, np.float32) for _ in range(4)]
+        if L.pb_bigwig_zoom_fill(h, *[a.ctypes.data for a in cols]) != 0:
+            raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    finally:
+        L.pb_bigwig_zoom_close(h)
+    return BigWigZoomTable(cols)
+
+
 def sum_ranges(lengths):
     """The positions ``BigWigReader.sum()`` adds, per contig in ``chroms`` order: the reference's position counter is set
     to 0 once, in front of the loop over the contigs (plastid/readers/bigwig.pyx:273-296), so contig k gives only its
@@ -851,6 +956,16 @@ def _compress_mode(compress):
     raise ValueError("compress: %r is none of True, False, 'fixed', 'dynamic'" % (compress,))
 
 
+def _zoom_mode(zoom):
+    """`zoom` of the bigWig writers as the C interface takes it: 0 no zoom levels, -1 the automatic first reduction, or
+    the first reduction itself, 8 .. 2**24.  A bool is not an int here."""
+    if isinstance(zoom, (bool, np.bool_)):
+        return -1 if zoom else 0
+    if isinstance(zoom, (int, np.integer)) and 8 <= int(zoom) <= 2 ** 24:
+        return int(zoom)
+    raise ValueError("zoom: %r is none of False, True, an int in 8 .. 2**24 (the first reduction)" % (zoom,))
+
+
 def deflate_zlib(engine, inputs, capacity=None, codes="fixed"):
     """``pc_deflate_zlib_mode``: every input of `inputs` (bytes, at most 24 600 each) encoded by one workgroup of ``k_zlib_deflate``
     on `engine` into one zlib stream.  Returns ``(bytes of the streams back to back, offsets, lengths)``; stream k is
@@ -911,6 +1026,8 @@ def huffman_lengths_host(counts, limit):
 
 
 BIGWIG_WRITE_STATS = ("contigs", "items", "sections", "raw_bytes", "block_bytes", "stored_sections")
+BIGWIG_ZOOM_STATS = ("reduction", "records", "blocks", "raw_bytes", "file_bytes")
+ZOOM_MAX_LEVELS = 10
 
 
 def _binary_sink(path_or_file):
@@ -929,7 +1046,8 @@ def _check_bigwig_params(items_per_slot, block_size):
         raise ValueError("to_bigwig: block_size outside 2 .. 65535")
 
 
-def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True, block_types=False):
+def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_size=256, compress=True, block_types=False, zoom=False,
+                 zoom_stats=False):
     """Write `strand` of a host ``DenseGenomeArray`` as a bigWig file by the serial writer of ``csrc/bigwig_write_host.h``
     (``pb_bigwig_write_*``): the item walk, the model encoder of ``csrc/deflate_host.h`` and the container code the device
     export shares.  The model of :meth:`GenomeArray.to_bigwig`, and the way to write a bigWig without a GPU.
@@ -937,12 +1055,15 @@ def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_si
     A cell is written iff its value ``!= 0.0`` (NaN is, ``-0.0`` is not); neighbouring written cells form one item while
     their float64 values compare equal; values are cast to float32.  Contigs stand in sorted order, every contig is in
     the chromosome tree at ``max(reported length, cells stored)``; every `items_per_slot` items of a contig make one
-    bedGraph section, `block_size` is the fan-out of both trees.  No zoom levels.  Normalisation is not applied.
-    `compress` as :meth:`GenomeArray.to_bigwig` takes it: ``True`` / ``"fixed"``, ``"dynamic"``, ``False``.
+    bedGraph section, `block_size` is the fan-out of the trees.  Normalisation is not applied.
+    `compress` and `zoom` as :meth:`GenomeArray.to_bigwig` takes them: ``True`` / ``"fixed"``, ``"dynamic"``, ``False``;
+    ``False`` (no zoom levels), ``True`` (the automatic first reduction), or the first reduction, 8 .. 2**24 -- the serial
+    model of the zoom levels, window by window.
     Returns the writer's statistics (``BIGWIG_WRITE_STATS``; with `block_types` also ``fixed_sections`` and
-    ``dynamic_sections``, as :meth:`GenomeArray.bigwig_export_stats` gives them).  No reference counterpart."""
+    ``dynamic_sections``, as :meth:`GenomeArray.bigwig_export_stats` gives them; with `zoom_stats` also ``zoom``, the list
+    :meth:`GenomeArray.bigwig_export_zoom_stats` gives).  No reference counterpart."""
     _check_bigwig_params(items_per_slot, block_size)
-    mode = _compress_mode(compress)
+    mode, zoom_mode = _compress_mode(compress), _zoom_mode(zoom)
     if isinstance(path_or_file, io.TextIOBase):
         raise TypeError("a bigWig file is binary: give a path or a file opened in binary mode")
     assert strand in host_array.strands()
@@ -961,8 +1082,11 @@ def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_si
         L.pb_bigwig_write_image.argtypes = [vp]
         L.pb_bigwig_write_stats.argtypes = [vp, vp]
         L.pb_bigwig_write_block_types.argtypes = [vp, vp]
+        L.pb_bigwig_write_open_zoom.restype = vp
+        L.pb_bigwig_write_open_zoom.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64]
+        L.pb_bigwig_write_zoom_stats.argtypes = [vp, vp, ctypes.c_int, vp]
         L.pb_bigwig_write_open._bound = True
-    h = L.pb_bigwig_write_open(int(items_per_slot), int(block_size), mode)
+    h = L.pb_bigwig_write_open_zoom(int(items_per_slot), int(block_size), mode, zoom_mode)
     if not h:
         raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
     try:
@@ -978,6 +1102,8 @@ def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_si
         L.pb_bigwig_write_stats(h, stats.ctypes.data)
         types = np.zeros(3, np.int64)
         L.pb_bigwig_write_block_types(h, types.ctypes.data)
+        nlevels, levels = ctypes.c_int64(0), np.zeros(5 * ZOOM_MAX_LEVELS, np.int64)
+        L.pb_bigwig_write_zoom_stats(h, ctypes.byref(nlevels), ZOOM_MAX_LEVELS, levels.ctypes.data)
     finally:
         L.pb_bigwig_write_close(h)
     sink, close = _binary_sink(path_or_file)
@@ -989,6 +1115,8 @@ def write_bigwig(host_array, path_or_file, strand, items_per_slot=1024, block_si
     out = dict(zip(BIGWIG_WRITE_STATS, (int(x) for x in stats)))
     if block_types:
         out["fixed_sections"], out["dynamic_sections"] = int(types[1]), int(types[2])
+    if zoom_stats:
+        out["zoom"] = [dict(zip(BIGWIG_ZOOM_STATS, (int(x) for x in levels[5 * k:5 * k + 5]))) for k in range(int(nlevels.value))]
     return out
 
 
