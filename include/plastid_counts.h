@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 21
+#define PC_ABI_VERSION 22
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -158,6 +158,15 @@ int64_t pc_canonical_entries(pc_engine *e, int file);
  * (read at pc_create / pc_reload_knobs) forbids it.  -1: the engine's last pc_count was not served from it (plan or file
  * not eligible, forbidden, more than one file staged), the rule or a filter has changed since, or a bad file index. */
 int64_t pc_dense_cells(pc_engine *e, int file);
+/* Which gather served the engine's last pc_count from the dense vector.  CHUNKS: one workgroup per 1 024 aligned
+ * elements of the output, every element written (no zero fill of the gaps between slices).  ITEMS: one workgroup per
+ * piece of a segment -- plans whose output ranges overlap, an output block that is not 128-byte aligned, or
+ * PC_DENSE_ITEMS=1 (read at pc_create / pc_reload_knobs).  NONE: that count was not served from the vector, or
+ * pc_dense_cells(e, 0) is -1 for any of its reasons (the rule or a filter has changed since, ...). */
+#define PC_DENSE_PATH_NONE 0
+#define PC_DENSE_PATH_ITEMS 1
+#define PC_DENSE_PATH_CHUNKS 2
+int pc_dense_path(pc_engine *e);
 /* Read objects of a staged file back (the reference hands pysam reads to its callers: get_reads / reads_out,
  * genome_array.py:834-859, and to filter functions, :697-722) -- for files whose records never visited the host
  * (pc_add_alignment_bam[_path | _span]).  pc_read_records: per requested record index its reference id, first aligned

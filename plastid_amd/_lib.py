@@ -49,6 +49,7 @@ SIGNATURES = {
     "pc_stream_entries": (_i64, [_vp, _int]),
     "pc_canonical_entries": (_i64, [_vp, _int]),
     "pc_dense_cells": (_i64, [_vp, _int]),
+    "pc_dense_path": (_int, [_vp]),
     "pc_read_records": (_int, [_vp, _int, _i64] + [_vp] * 8),
     "pc_read_record_runs": (_int, [_vp, _int, _i64, _vp, _vp, _i64, _vp, _vp]),
     "pc_set_mapping": (_int, [_vp, _int, _int, _vp, _vp, _int, _int, _int]),
@@ -179,7 +180,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 
 def load():

@@ -143,4 +143,109 @@ PCDENSE_HD inline int64_t pair_slot(int64_t out_off, int32_t step, const PairCut
 constexpr int kBatch = PC_DENSE_BATCH;
 PCDENSE_HD inline int64_t batches_of(int64_t n_items) { return (n_items + kBatch - 1) / kBatch; }
 
+// ---- the CHUNK form of a plan (k_dense_gather_chunks): the output vector is cut into aligned CHUNKS of kChunk
+// elements -- chunk c is out[kChunk c, kChunk c + kChunk) -- and one workgroup writes one chunk, every element of it,
+// zeros included: every lane is busy and every wave store covers whole 128-byte lines, whatever the segments are.  A
+// SPAN is one segment in one chunk; a chunk's DESCRIPTOR names its spans in output order.  The form needs output
+// ranges that do not overlap (the item form writes overlapping ranges in whatever order the workgroups run, which a
+// chunk cannot reproduce); plans with overlaps keep the items.  Chunks of 1 024 elements were measured faster than of
+// 2 048 (profiles/dense_chunks/NOTES.md); -DPC_DENSE_CHUNK=<elements> builds others for scripts/exp_dense_sections.py.
+#ifndef PC_DENSE_CHUNK
+#define PC_DENSE_CHUNK 1024
+#endif
+constexpr int kChunk = PC_DENSE_CHUNK;
+constexpr int kRow = 128;                    // output elements of one wave store: 64 lanes x 16 bytes, eight lines
+constexpr int kInlineSpans = 7;
+static_assert(kChunk % (4 * kRow) == 0 && kChunk / kRow <= 32, "a chunk is whole rows for four waves; its rows are the bits of a word");
+
+// Output elements [a, b) of the chunk (chunk-relative) belong to the span; [ra, rb) of them read a cell -- element e
+// reads cell + dir (e - a) -- and the others are zero (clipped, beyond the extent, unknown contig).  ra == rb: none.
+// Cells are below 2^32 (dense_for_plan); `cell` of a span whose first elements are not readable may have wrapped,
+// and is used modulo 2^32 only.
+// The four bounds are packed two to a word, so that a descriptor is read a word at a time.
+struct Span {
+    uint32_t ab, rr;     // a | b << 16, ra | rb << 16
+    uint32_t cell;
+    int32_t dir;
+    PCDENSE_HD uint32_t a() const { return ab & 0xffffu; }
+    PCDENSE_HD uint32_t b() const { return ab >> 16; }
+    PCDENSE_HD uint32_t ra() const { return rr & 0xffffu; }
+    PCDENSE_HD uint32_t rb() const { return rr >> 16; }
+};
+static_assert(sizeof(Span) == 16, "Span is 16 bytes in HBM");
+// the chunk's first kInlineSpans spans; span s >= kInlineSpans is spans[ovf + s - kInlineSpans] of the plan's span array
+// (which holds every span of every chunk in output order: span 0 of the chunk is spans[ovf - kInlineSpans])
+struct ChunkDesc {
+    uint32_t n, ovf, pad[2];
+    Span s[kInlineSpans];
+};
+static_assert(sizeof(ChunkDesc) == 128, "a descriptor is one line");
+
+PCDENSE_HD inline int64_t chunks_of(int64_t out_elems) { return (out_elems + kChunk - 1) / kChunk; }
+// first output element of a segment (its range is [lo, lo + len))
+PCDENSE_HD inline int64_t seg_out_lo(int64_t out_off, int32_t step, int64_t len) { return step > 0 ? out_off : out_off - len + 1; }
+// spans of a segment: the chunks its output range meets
+PCDENSE_HD inline int64_t spans_of(int64_t out_lo, int64_t len) { return len > 0 ? (out_lo + len - 1) / kChunk - out_lo / kChunk + 1 : 0; }
+// an upper bound of a plan's spans from what the plan records of itself (every segment: its whole chunks and two ends)
+inline bool spans_fit(int64_t nseg, int64_t covered) { return 2 * nseg + covered / kChunk < (int64_t)0xffffffffu; }
+
+// span k (0 <= k < spans_of) of segment s: its part in chunk seg_out_lo / kChunk + k
+PCDENSE_HD inline Span cut_span(const SegIn &s, int64_t k) {
+    const int64_t lo = seg_out_lo(s.out_off, s.step, s.len), base = (lo / kChunk + k) * kChunk;
+    const int64_t a = lo > base ? lo : base, b = lo + s.len < base + kChunk ? lo + s.len : base + kChunk;
+    // readable positions of the segment, as cut_item has them
+    int64_t plo = 0, phi = 0;
+    if (s.known) {
+        plo = s.clip_lo; phi = s.clip_hi;
+        if (s.start + phi > s.ext) phi = s.ext - s.start;
+        if (s.start + plo < 0) plo = -s.start;
+        if (plo < 0) plo = 0;
+        if (phi > s.len) phi = s.len;
+    }
+    // ... as output elements: position i is element out_off + step i
+    int64_t ra = s.step > 0 ? s.out_off + plo : s.out_off - phi + 1, rb = s.step > 0 ? s.out_off + phi : s.out_off - plo + 1;
+    if (ra < a) ra = a;
+    if (rb > b) rb = b;
+    if (phi <= plo || rb <= ra) ra = rb = a;
+    Span sp;
+    sp.ab = (uint32_t)(a - base) | (uint32_t)(b - base) << 16;
+    sp.rr = (uint32_t)(ra - base) | (uint32_t)(rb - base) << 16;
+    sp.dir = s.step > 0 ? 1 : -1;
+    const int64_t pos = s.step > 0 ? a - s.out_off : s.out_off - a;     // the position that element a takes
+    sp.cell = (uint32_t)(s.cell_base + s.start + pos);
+    return sp;
+}
+PCDENSE_HD inline bool span_reads(const Span &s, uint32_t e) { return e >= s.ra() && e < s.rb(); }
+PCDENSE_HD inline uint32_t span_cell(const Span &s, uint32_t e) { return s.cell + (uint32_t)s.dir * (e - s.a()); }
+// How the kernel decides per ROW of kRow elements (kernel and CPU test call these).  span_rows: bit r is set where some
+// element of row r of the chunk reads a cell through the span.  A row in the words of exactly one span of its chunk
+// reads by that span's uniform base: element e reads cell base_cell(span_base(s), s.dir > 0, e) where span_reads says
+// so.  Two cells share one 4-byte load where same_word says so (loads are at even cell indices).
+PCDENSE_HD inline uint32_t span_rows(const Span &s) {
+    const uint32_t ra = s.ra(), rb = s.rb();
+    return ra < rb ? (2u << ((rb - 1u) / kRow)) - (1u << (ra / kRow)) : 0u;
+}
+PCDENSE_HD inline uint32_t span_base(const Span &s) { return s.cell - (uint32_t)s.dir * s.a(); }
+PCDENSE_HD inline uint32_t base_cell(uint32_t base, bool up, uint32_t e) { return up ? base + e : base - e; }
+PCDENSE_HD inline bool same_word(uint32_t x0, uint32_t x1) { return (x0 | 1u) == (x1 | 1u); }
+
+// The table is built from the segments sorted by seg_out_lo (empty ones last).  Of two neighbours in that order:
+// overlap -- any two ranges of a plan overlap only if two neighbours do
+PCDENSE_HD inline bool out_overlap(int64_t prev_lo, int64_t prev_len, int64_t lo) { return prev_lo + prev_len > lo; }
+// span k of a segment is the first span of its chunk: a later chunk of the segment starts inside the segment; the
+// first one unless the segment before ends in that chunk (`prev_end`: where that one ends, -1: there is none)
+PCDENSE_HD inline bool first_of_chunk(int64_t lo, int64_t k, int64_t prev_end) {
+    return k > 0 || lo % kChunk == 0 || prev_end < 0 || (prev_end - 1) / kChunk < lo / kChunk;
+}
+// the descriptor of a chunk whose n spans are spans[first .. first + n), in output order
+PCDENSE_HD inline ChunkDesc make_desc(const Span *spans, uint32_t first, uint32_t n) {
+    ChunkDesc d;
+    d.n = n; d.ovf = first + kInlineSpans; d.pad[0] = d.pad[1] = 0;
+    for (int i = 0; i < kInlineSpans; ++i) {
+        if ((uint32_t)i < n) d.s[i] = spans[first + i];
+        else { d.s[i].ab = d.s[i].rr = 0; d.s[i].cell = 0; d.s[i].dir = 1; }
+    }
+    return d;
+}
+
 } // namespace pcdense

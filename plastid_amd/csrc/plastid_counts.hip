@@ -614,6 +614,7 @@ struct Knobs {
     double compact_keep = 0.9; // PC_COMPACT_KEEP: a file that keeps more than this share of its records as entries gets no compact stream (build_compact_stream)
     int no_canon = 0;          // PC_NO_CANON: no canonical stream -- eligible plans stream what the others do (A/B runs in one build; tests compare the two)
     int no_dense = 0;          // PC_NO_DENSE: no dense vector -- eligible plans go through the window kernels (A/B runs in one build; tests compare the two)
+    int dense_items = 0;       // PC_DENSE_ITEMS: the dense vector serves every plan by items (k_dense_gather), none by chunks (A/B runs in one build; tests compare the two)
     int dense_debug = 0;       // PC_DENSE_DEBUG: print what dense_for_plan decided and from which figures (stderr)
     int no_single = 0;         // PC_NO_SINGLE: one-window plans go through the work lists like any other (tests compare the two paths)
     int plan_build = 0;        // PC_PLAN_BUILD=host|gpu: where pc_plan_create builds the tables (default: on the GPU from 8 192 segments)
@@ -638,6 +639,7 @@ struct Knobs {
         no_compact = getenv("PC_NO_COMPACT") ? 1 : 0;
         no_canon = getenv("PC_NO_CANON") ? 1 : 0;
         no_dense = getenv("PC_NO_DENSE") ? 1 : 0;
+        dense_items = getenv("PC_DENSE_ITEMS") ? 1 : 0;
         dense_debug = getenv("PC_DENSE_DEBUG") ? 1 : 0;
         if (const char *env = getenv("PC_COMPACT_KEEP")) compact_keep = std::min(1.0, std::max(0.0, atof(env)));
         no_stream_probe = getenv("PC_NO_STREAM_PROBE") ? 1 : 0;
@@ -723,6 +725,7 @@ struct pc_engine {
     int timed_level = 0;     // level the last pc_count was recorded with
     int64_t last_alg_bytes = 0;
     bool last_count_dense = false;       // the last pc_count was served from the dense vector of file 0 (pc_dense_cells)
+    int last_dense_path = PC_DENSE_PATH_NONE;   // ... and by which kernel (pc_dense_path)
     bool want_center_steps = false;      // pc_center_replay_steps: the next center count reports the replay steps it executed
     int64_t center_steps = 0, center_waves = 0;
 
@@ -767,6 +770,12 @@ struct pc_plan {
     DevBuf<pcdense::Item> d_ditems;
     uint32_t n_ditems = 0;
     uint64_t ditems_id = 0;      // (0: none)
+    // ... and the chunk table beside them (dense_host.h): one descriptor per 1 024 elements of the output, the spans of
+    // all chunks in output order.  chunks_ok false: the plan's output ranges overlap, or it has too many spans -- items only
+    DevBuf<pcdense::ChunkDesc> d_dchunks;
+    DevBuf<pcdense::Span> d_dspans;
+    bool chunks_ok = false;
+    uint64_t dchunks_id = 0;     // the vector the table was made for (0: none, or not asked for yet: PC_DENSE_ITEMS)
     bool hist_clean = false;     // the WHOLE compact histogram is known to be zero (a lazy count does not need that: it clears the slices it merges)
     bool hist_lazy = false;      // the histogram is large: never cleared as a whole, k_clear_split runs behind every k_tile_ranges
     // GPU-built plans: the center chunks and the gather list wait for the first center count or coordinate export
@@ -857,7 +866,7 @@ struct pc_plan {
         d_ccand.pool = pl; d_rle_cnt.pool = pl; d_rle_base.pool = pl; d_rle_starts.pool = pl; d_rle_values.pool = pl;
         d_cranges.pool = pl; d_crec.pool = pl; d_crows.pool = pl; d_ccounts.pool = pl; d_cslots.pool = pl; d_hist_own.pool = pl; d_out.pool = pl; d_tables2.pool = pl; d_tables3.pool = pl;
         d_work.pool = pl; d_work_small.pool = pl; d_chain.pool = pl; d_chain_small.pool = pl;
-        d_inputs.pool = pl; d_gsegs_own.pool = pl; d_ditems.pool = pl;
+        d_inputs.pool = pl; d_gsegs_own.pool = pl; d_ditems.pool = pl; d_dchunks.pool = pl; d_dspans.pool = pl;
     }
 };
 
@@ -2559,11 +2568,27 @@ int count_prepare(pc_engine *e, pc_plan *p, bool dense) {   // dense: served fro
     return p->d_out.reserve(std::max<size_t>((size_t)p->out_elems * 8, 8));
 }
 
-int count_clear(pc_engine *e, pc_plan *p, const CountCall &c, bool dense) {
+int ensure_dense_tables(pc_engine *e, pc_plan *p, const StagedFile *sf);   // (below, with the dense vector)
+
+// `dense`: the file whose vector serves this count (dense_for_plan), else nullptr; *path: which gather will (pc_dense_path)
+int count_clear(pc_engine *e, pc_plan *p, const CountCall &c, const StagedFile *dense, int *path) {
     const bool center = e->kind == PC_MAP_CENTER;
     PC_TRY(mark(e, 0));
-    if (dense) {   // k_dense_gather writes every position of every segment, zeros included: only gaps between slices are cleared
-        if (p->covered != p->out_elems && p->out_elems) HIP_TRY(hipMemsetAsync(p->d_out.p, 0, (size_t)p->out_elems * 8, e->stream));
+    // A count served from a dense vector: the plan's one-time tables are made here, behind mark 0, so that last_timing()
+    // of a first count holds them.  By chunks where the plan has a chunk table (no overlapping output ranges) and the
+    // output block is line aligned -- the chunk kernel's stores are whole lines -- else by items
+    int dense_path = PC_DENSE_PATH_NONE;
+    if (dense) {
+        PC_TRY(ensure_dense_tables(e, p, dense));
+        const bool chunks = p->chunks_ok && p->dchunks_id == dense->did && !e->knobs.dense_items && ((uintptr_t)p->d_out.p & 127u) == 0;
+        dense_path = chunks ? PC_DENSE_PATH_CHUNKS : PC_DENSE_PATH_ITEMS;
+    }
+    *path = dense_path;
+    if (dense_path != PC_DENSE_PATH_NONE) {
+        // k_dense_gather writes every position of every segment, zeros included: only gaps between slices are cleared.
+        // k_dense_gather_chunks writes every element of the output, the gaps too: nothing is
+        if (dense_path == PC_DENSE_PATH_ITEMS && p->covered != p->out_elems && p->out_elems)
+            HIP_TRY(hipMemsetAsync(p->d_out.p, 0, (size_t)p->out_elems * 8, e->stream));
         return mark(e, 1);
     }
     // Outputs are written exactly once by the tile kernels.  Only positions that belong to no
@@ -3026,14 +3051,61 @@ int dense_for_plan(pc_engine *e, pc_plan *p, const CountCall &c, StagedFile **de
     return PC_OK;
 }
 
-// the plan's segments cut into gather items: once per plan and vector
-int ensure_dense_items(pc_engine *e, pc_plan *p, const StagedFile *sf) {
+// the chunk table of the plan (dense_host.h): the segments sorted by their first output element, their spans counted,
+// placed and written, one descriptor per chunk.  p->chunks_ok says whether the plan can be served by chunks
+int build_dense_chunks(pc_engine *e, pc_plan *p, const StagedFile *sf, const GatherSeg *gsegs, const int32_t *tid, const uint8_t *strand) {
     using namespace pcdense;
-    if (p->ditems_id == sf->did) return PC_OK;
+    p->chunks_ok = false;
+    const size_t n = (size_t)p->nseg, nchunks = (size_t)chunks_of(p->out_elems);
+    if (!n || !nchunks || !spans_fit((int64_t)n, p->covered) || nchunks >= (size_t)0x7fffffffu) return PC_OK;
+    hipStream_t st = e->stream;
+    DevBuf<uint64_t> d_key, d_key2;
+    DevBuf<uint32_t> d_idx, d_idx2, d_cnt, d_at, d_first, d_nof, d_flag;
+    DevBuf<uint8_t> d_tmp;
+    d_key.pool = d_key2.pool = d_idx.pool = d_idx2.pool = d_cnt.pool = d_at.pool = d_first.pool = d_nof.pool = d_flag.pool = d_tmp.pool = &e->pool;
+    size_t sort_b = 0, scan_b = 0;
+    const uint64_t nokey = (uint64_t)p->out_elems;               // the key of an empty segment: behind every start
+    const int key_bits = bits_for(nokey);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, 0, key_bits, st));
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st));
+    PC_TRY(d_key.reserve(n)); PC_TRY(d_key2.reserve(n)); PC_TRY(d_idx.reserve(n)); PC_TRY(d_idx2.reserve(n));
+    PC_TRY(d_cnt.reserve(n + 1)); PC_TRY(d_at.reserve(n + 1)); PC_TRY(d_first.reserve(nchunks)); PC_TRY(d_nof.reserve(nchunks)); PC_TRY(d_flag.reserve(2));
+    PC_TRY(d_tmp.reserve(std::max<size_t>(std::max(sort_b, scan_b), 16)));
+    const unsigned g = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(k_chunk_keys, dim3(g), dim3(256), 0, st, gsegs, (int64_t)n, nokey, d_key.p, d_idx.p);
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, sort_b, d_key.p, d_key2.p, d_idx.p, d_idx2.p, (int)n, 0, key_bits, st));
+    HIP_TRY(hipMemsetAsync(d_cnt.p + n, 0, 4, st));
+    HIP_TRY(hipMemsetAsync(d_flag.p, 0, 8, st));
+    hipLaunchKernelGGL(k_chunk_count, dim3(g), dim3(256), 0, st, gsegs, d_key2.p, d_idx2.p, (int64_t)n, nokey, d_cnt.p, d_flag.p);
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, scan_b, d_cnt.p, d_at.p, (int)n + 1, st));
+    // No wait in between: the span array takes the bound that spans_fit checked (every segment: its whole chunks and two
+    // ends), and k_chunk_descs leaves the descriptors alone where k_chunk_count found an overlap
+    PC_TRY(p->d_dspans.reserve(2 * n + (size_t)(p->covered / kChunk) + 1));
+    PC_TRY(p->d_dchunks.reserve(nchunks));
+    HIP_TRY(hipMemsetAsync(d_nof.p, 0, nchunks * 4, st));
+    HIP_TRY(hipMemsetAsync(d_first.p, 0, nchunks * 4, st));   // (a chunk without spans names none)
+    hipLaunchKernelGGL(k_chunk_spans, dim3(g), dim3(256), 0, st, gsegs, tid, strand, d_key2.p, d_idx2.p, (int64_t)n, nokey, e->ntid, sf->d_dcell_off.p, sf->d_dext.p, d_at.p,
+                       p->d_dspans.p, d_first.p, d_nof.p);
+    hipLaunchKernelGGL(k_chunk_descs, dim3((unsigned)((nchunks + 255) / 256)), dim3(256), 0, st, p->d_dspans.p, d_first.p, d_nof.p, d_flag.p, (int64_t)nchunks, p->d_dchunks.p);
+    HIP_TRY(hipGetLastError());
+    uint32_t overlap = 0;
+    HIP_TRY(hipMemcpyAsync(&overlap, d_flag.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the working arrays go out of scope)
+    if (overlap) return PC_OK;           // overlapping output ranges: the items serve the plan
+    p->chunks_ok = true;
+    return PC_OK;
+}
+
+// the plan's segments cut into gather items, and its chunk table: each once per plan and vector.  The chunk table waits
+// for the first count that may take the chunk path: under PC_DENSE_ITEMS a plan never pays for it
+int ensure_dense_tables(pc_engine *e, pc_plan *p, const StagedFile *sf) {
+    using namespace pcdense;
+    const bool need_items = p->ditems_id != sf->did, need_chunks = !e->knobs.dense_items && p->dchunks_id != sf->did;
+    if (!need_items && !need_chunks) return PC_OK;
     hipStream_t st = e->stream;
     const size_t n = (size_t)p->nseg;
-    p->ditems_id = 0;
-    p->n_ditems = 0;
+    if (need_items) { p->ditems_id = 0; p->n_ditems = 0; }
+    if (need_chunks) { p->dchunks_id = 0; p->chunks_ok = false; }
     DevBuf<int32_t> d_tid;
     DevBuf<uint8_t> d_strand, d_tmp;
     DevBuf<uint32_t> d_cnt, d_at;
@@ -3048,32 +3120,43 @@ int ensure_dense_items(pc_engine *e, pc_plan *p, const StagedFile *sf) {
         PC_TRY(d_tid.upload(p->h_tid, st)); PC_TRY(d_strand.upload(p->h_strand, st));
         tid = d_tid.p; strand = d_strand.p;
     }
-    uint32_t total = 0;
-    if (n) {
-        size_t tb = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st));
-        PC_TRY(d_cnt.reserve(n + 1)); PC_TRY(d_at.reserve(n + 1)); PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
-        const unsigned g = (unsigned)((n + 255) / 256);
-        HIP_TRY(hipMemsetAsync(d_cnt.p + n, 0, 4, st));
-        hipLaunchKernelGGL(k_dense_seg_items, dim3(g), dim3(256), 0, st, gsegs, (int64_t)n, d_cnt.p);
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_cnt.p, d_at.p, (int)n + 1, st));
-        HIP_TRY(hipMemcpyAsync(&total, d_at.p + n, 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        PC_TRY(p->d_ditems.reserve(std::max<size_t>(total, 1)));
-        if (total) hipLaunchKernelGGL(k_dense_items, dim3(g), dim3(256), 0, st, gsegs, tid, strand, (int64_t)n, e->ntid, sf->d_dcell_off.p, sf->d_dext.p, d_at.p, p->d_ditems.p);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));   // (the working arrays go out of scope)
+    if (need_items) {
+        uint32_t total = 0;
+        if (n) {
+            size_t tb = 0;
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st));
+            PC_TRY(d_cnt.reserve(n + 1)); PC_TRY(d_at.reserve(n + 1)); PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+            const unsigned g = (unsigned)((n + 255) / 256);
+            HIP_TRY(hipMemsetAsync(d_cnt.p + n, 0, 4, st));
+            hipLaunchKernelGGL(k_dense_seg_items, dim3(g), dim3(256), 0, st, gsegs, (int64_t)n, d_cnt.p);
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_cnt.p, d_at.p, (int)n + 1, st));
+            HIP_TRY(hipMemcpyAsync(&total, d_at.p + n, 4, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            PC_TRY(p->d_ditems.reserve(std::max<size_t>(total, 1)));
+            if (total) hipLaunchKernelGGL(k_dense_items, dim3(g), dim3(256), 0, st, gsegs, tid, strand, (int64_t)n, e->ntid, sf->d_dcell_off.p, sf->d_dext.p, d_at.p, p->d_ditems.p);
+            HIP_TRY(hipGetLastError());
+        }
+        p->n_ditems = total;
     }
-    p->n_ditems = total;
-    p->ditems_id = sf->did;
+    // (a chunk table that cannot be built -- no memory for it -- is no failure of the count: the items serve the plan)
+    if (need_chunks && n && build_dense_chunks(e, p, sf, gsegs, tid, strand) != PC_OK) { p->chunks_ok = false; (void)hipGetLastError(); }
+    HIP_TRY(hipStreamSynchronize(st));   // (the working arrays go out of scope; behind the chunk table's own wait the stream is idle)
+    if (need_items) p->ditems_id = sf->did;
+    if (need_chunks) p->dchunks_id = sf->did;
     return PC_OK;
 }
 
 // a count served from the dense vector: one launch, between the marks of the histogram kernels
-int count_dense(pc_engine *e, pc_plan *p, const CountCall &c, const StagedFile *sf) {
-    PC_TRY(ensure_dense_items(e, p, sf));
+int count_dense(pc_engine *e, pc_plan *p, const CountCall &c, const StagedFile *sf, int path) {
     PC_TRY(mark(e, 2));
-    if (p->n_ditems)
+    if (path == PC_DENSE_PATH_CHUNKS)
+        dispatch_int<0, 1, 2>(c.outmode, [&](auto O) {
+            constexpr int o = decltype(O)::value;
+            hipLaunchKernelGGL((pcdense::k_dense_gather_chunks<o>), dim3((unsigned)pcdense::chunks_of(p->out_elems)), dim3(pcdense::kGatherWG), 0, e->stream,
+                               p->d_dchunks.p, p->d_dspans.p, sf->dense.p, sf->dovf_key.p, sf->dovf_val.p, sf->dn_ovf, (typename OutT_<o>::type *)p->d_out.p,
+                               (int64_t)p->out_elems, e->norm_sum);
+        });
+    else if (p->n_ditems)
         dispatch_int<0, 1, 2>(c.outmode, [&](auto O) {
             constexpr int o = decltype(O)::value;
             hipLaunchKernelGGL((pcdense::k_dense_gather<o>), dim3((unsigned)pcdense::batches_of(p->n_ditems)), dim3(pcdense::kGatherWG), 0, e->stream, p->d_ditems.p,
@@ -3276,9 +3359,11 @@ int pc_count(pc_engine *e, pc_plan *p, int out_dtype) {
     if (!center && !single && c.ntiles > 0) PC_TRY(dense_for_plan(e, p, c, &dense));
     e->last_count_dense = dense != nullptr;
     PC_TRY(count_prepare(e, p, dense != nullptr));
-    PC_TRY(count_clear(e, p, c, dense != nullptr));
+    int dense_path = PC_DENSE_PATH_NONE;
+    PC_TRY(count_clear(e, p, c, dense, &dense_path));
+    e->last_dense_path = dense_path;
     if (center) PC_TRY(count_center(e, p, c));
-    else if (dense) PC_TRY(count_dense(e, p, c, dense));
+    else if (dense) PC_TRY(count_dense(e, p, c, dense, dense_path));
     else if (single) PC_TRY(count_single(e, p, c));
     else if (c.ntiles > 0) PC_TRY(count_lists(e, p, c));
     else for (int k = 2; k <= 4; ++k) PC_TRY(mark(e, k));   // a plan without windows
@@ -3291,6 +3376,8 @@ int64_t pc_dense_cells(pc_engine *e, int file) {
     if (e->files.size() != 1 || e->knobs.no_dense || !e->last_count_dense) return -1;   // (only a plan over ONE file is served from it)
     return (sf->dsig_valid && sf->dsig == dense_sig(e, sf)) ? sf->dcells : -1;
 }
+
+int pc_dense_path(pc_engine *e) { return e && pc_dense_cells(e, 0) >= 0 ? e->last_dense_path : PC_DENSE_PATH_NONE; }   // (NONE wherever pc_dense_cells says -1)
 
 int pc_sync(pc_engine *e) {
     if (!e) return fail(PC_ERR_ARG, "engine is NULL");

@@ -210,6 +210,11 @@ class Engine(object):
         the count under the current point rule and filters; -1 when the last count was not served from it."""
         return int(self._lib.pc_dense_cells(self._h, int(file_index)))
 
+    def dense_path(self):
+        """Which gather served the last count from the dense vector (``pc_dense_path``): ``"chunks"``, ``"items"`` or
+        ``None`` when that count was not served from it."""
+        return {1: "items", 2: "chunks"}.get(int(self._lib.pc_dense_path(self._h)))
+
     def read_records(self, file_index, indices):
         """Read objects' worth of data for records of a staged file (``pc_read_records`` + ``pc_read_record_runs``):
         dict of arrays ``tid, pos, alen, reverse, nblk, flag16, mapq`` plus ``run_off`` (n + 1), ``run_start``,
