@@ -34,7 +34,7 @@ extern "C" {
 
 /* Bumped whenever entry points are added or the meaning of an argument changes (6: round 6).  A binding checks it
  * BEFORE it resolves any other symbol: a stale library then fails with a version message, not with a missing symbol. */
-#define PC_ABI_VERSION 22
+#define PC_ABI_VERSION 23
 
 typedef struct pc_engine pc_engine;
 typedef struct pc_plan pc_plan;
@@ -789,6 +789,39 @@ int pc_track_bigwig_export_zoom_stats(pc_track *t, int64_t *levels, int64_t *out
  * zoom blocks.  All 0 when no level was written.  (pc_track_bigwig_export_timing keeps its six laps: the zoom levels
  * run between its [3] and its [4].) */
 int pc_track_bigwig_export_zoom_timing(pc_track *t, double *ms4);
+
+/* ---- BINNED SUMMARIES of a bigWig file (revision 23; csrc/bigwig_summary.hip.h, the kernels: csrc/bigwig_summary_kernels.hip.h,
+ * the rules and the model: csrc/bigwig_summary_host.h).  What the summary reader of Kent's library gives
+ * (bigWigSummaryArray: bbiRead.c:18-40 and :405-760, bwgQuery.c:155-287), bit for bit: a query (contig, start, end) is cut
+ * into n_bins equal bins and answered from the zoom level with the greatest reduction <= ((end - start) / n_bins) / 2, from
+ * the items when that is <= 1 or no level is that fine.
+ * pc_bigwig_summary_open / _open_path parse the header, the chromosome tree and the zoom headers on the host and upload
+ * nothing (open copies the image; open_path maps the file for the life of the handle).  A TABLE -- the records of one
+ * level, or the items -- is loaded at the first query that selects it: the host walks its R-tree, the blocks go up as
+ * they are, are inflated and Adler-checked by the kernels of the import, and land in HBM as records in file order (32
+ * bytes per zoom record, 16 per item), where they stay.  One kernel checks that a table's starts and ends do not decrease
+ * within a contig and that a contig's records stand together -- true of every file Kent's writer and ours produce -- and
+ * gives the record range of every contig; a table that fails makes the queries that select it PC_ERR_ARG with "<path>:
+ * bigWig: summarize needs records in coordinate order" (Kent walks a list where this library searches).  A handle goes
+ * with its engine (pc_destroy) unless closed before. */
+typedef struct pc_bigwig_summary pc_bigwig_summary;
+int pc_bigwig_summary_open(pc_engine *e, const void *image, int64_t size, const char *name, pc_bigwig_summary **out);
+int pc_bigwig_summary_open_path(pc_engine *e, const char *path, pc_bigwig_summary **out);
+int pc_bigwig_summary_close(pc_bigwig_summary *s);
+/* nq queries of n_bins bins each: contig[q] the contig's place in the chromosome list (pc_bigwig_info's order; -1: the
+ * file lacks it: no data), 0 <= start[q] < end[q] < 2^31, 1 <= n_bins < 2^31, nq x n_bins < 2^31.  The queries are grouped
+ * by table on the host and k_bbi_summarize runs once per table in use, one lane per (query, bin).  out5: five columns of
+ * nq x n_bins doubles -- validCount, min, max, sum, sum of squares (Kent's bbiSummaryElement), element q x n_bins + bin of
+ * each; a bin without data is all zeros.  The buffer is read back once.  A lane walks its bin serially, because the sums
+ * are exact in their order: bins of millions of items in a file without zoom levels are slow by construction. */
+int pc_bigwig_summary_query(pc_bigwig_summary *s, int64_t nq, const int32_t *contig, const int64_t *start, const int64_t *end, int64_t n_bins, double *out5);
+/* out4: [0] tables the file has (the items and its levels), [1] tables loaded, [2] bytes uploaded, [3] bytes inflated; per
+ * table k (0: the items, 1 + j: level j; at most max_tables of them) out3 + 3 k: [0] the reduction (0: the items), [1]
+ * records (-1: not loaded), [2] queries answered */
+int pc_bigwig_summary_stats(pc_bigwig_summary *s, int64_t *out4, int max_tables, int64_t *out3);
+/* milliseconds of the last pc_bigwig_summary_query on the engine's stream: [0] upload, [1] inflate + Adler-32, [2] records /
+ * items and the order check (0 - 2 are 0 when no table was loaded), [3] k_bbi_summarize, [4] read-back */
+int pc_bigwig_summary_timing(pc_bigwig_summary *s, double *ms5);
 
 #ifdef __cplusplus
 }

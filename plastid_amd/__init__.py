@@ -13,6 +13,7 @@ from .map_factories import (CenterMapFactory, FivePrimeMapFactory, FlagFilterFac
                             VariableFivePrimeMapFactory)
 from .genome_array import BAMGenomeArray, DenseGenomeArray  # noqa: F401
 from .track import (BigWigGenomeArray, BigWigReader, BigWigTable, BigWigZoomTable, GenomeArray, WiggleTable, bigwig_info,  # noqa: F401
-                    bigwig_zoom_info, read_bigwig, read_bigwig_zoom, read_wiggle, write_bigwig)
+                    bigwig_zoom_info, read_bigwig, read_bigwig_zoom, read_wiggle, summarize_bigwig, summary_elements_bigwig,
+                    write_bigwig)
 
 __version__ = "0.1.0"

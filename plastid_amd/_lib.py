@@ -171,6 +171,12 @@ SIGNATURES = {
     "pc_track_bigwig_timing": (_int, [_vp, _vp]),
     "pc_track_gather_sum": (_int, [_int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, ctypes.c_double, _vp]),
     "pc_track_sum_ranges": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double)]),
+    "pc_bigwig_summary_open": (_int, [_vp, _vp, _i64, ctypes.c_char_p, _pp]),
+    "pc_bigwig_summary_open_path": (_int, [_vp, ctypes.c_char_p, _pp]),
+    "pc_bigwig_summary_close": (_int, [_vp]),
+    "pc_bigwig_summary_query": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "pc_bigwig_summary_stats": (_int, [_vp, _vp, _int, _vp]),
+    "pc_bigwig_summary_timing": (_int, [_vp, _vp]),
 }
 
 _lib = None
@@ -180,7 +186,7 @@ _lib = None
 PC_BAM_SORT = 1
 
 #: PC_ABI_VERSION of include/plastid_counts.h this binding was written against
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 
 def load():

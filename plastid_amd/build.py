@@ -32,7 +32,7 @@ def find_hipcc():
 
 
 BAM_SRC = os.path.join(HERE, "csrc", "bam_stager.cpp")
-BAM_HDRS = [os.path.join(HERE, "csrc", f) for f in ("index_shape.h", "bam_host.h", "bigwig_host.h", "bigwig_write_host.h", "deflate_host.h", "host_util.h", "sam_host.h", "track_host.h")]   # what bam_stager.cpp includes of csrc/
+BAM_HDRS = [os.path.join(HERE, "csrc", f) for f in ("index_shape.h", "bam_host.h", "bigwig_host.h", "bigwig_write_host.h", "bigwig_summary_host.h", "deflate_host.h", "host_util.h", "sam_host.h", "track_host.h")]   # what bam_stager.cpp includes of csrc/
 BAM_LIB = os.path.join(HERE, "libplastid_bam.so")
 
 

@@ -36,6 +36,7 @@
 #include "bam_host.h"
 #include "bigwig_host.h"
 #include "bigwig_write_host.h"
+#include "bigwig_summary_host.h"
 #include "deflate_host.h"
 #include "index_shape.h"
 #include "sam_host.h"
@@ -2040,6 +2041,72 @@ int pb_bigwig_zoom_fill(void *h, uint32_t *chrom, uint32_t *start, uint32_t *end
     if (n) {
         std::memcpy(chrom, t.chrom.data(), n); std::memcpy(start, t.start.data(), n); std::memcpy(end, t.end.data(), n); std::memcpy(valid, t.valid.data(), n);
         std::memcpy(mn, t.mn.data(), n); std::memcpy(mx, t.mx.data(), n); std::memcpy(sum, t.sum.data(), n); std::memcpy(sumsq, t.sumsq.data(), n);
+    }
+    return 0;
+}
+
+// Binned summaries of a bigWig file on the host (bigwig_summary_host.h): the model of pc_bigwig_summary_query, one thread.
+// The handle keeps the image's pointer: the caller keeps the image alive.  NULL / -1 (pb_last_error): "<name>: bigWig: <what>".
+namespace {
+struct SummaryRead { pcbws::HostSummary s; std::string name; };
+}   // namespace
+void *pb_bigwig_summary_open(const void *image, int64_t size, const char *name) {
+    if (size < 0 || (size > 0 && !image)) { fail("pb_bigwig_summary_open: bad arguments"); return nullptr; }
+    SummaryRead *h = new SummaryRead();
+    h->name = name ? name : "<memory>";
+    const std::string bad = h->s.open((const uint8_t *)image, (uint64_t)size);
+    if (!bad.empty()) { fail(h->name + ": bigWig: " + bad); delete h; return nullptr; }
+    return h;
+}
+void pb_bigwig_summary_close(void *h) { delete static_cast<SummaryRead *>(h); }
+int pb_bigwig_summary_nchrom(void *h) { return h ? (int)static_cast<SummaryRead *>(h)->s.f.chroms.size() : -1; }
+const char *pb_bigwig_summary_chrom(void *h, int i) { return static_cast<SummaryRead *>(h)->s.f.chroms[(size_t)i].name.c_str(); }
+// nq queries of n_bins bins: contig[q] the place in the chromosome list (-1: the file lacks it).  out5: five columns of
+// nq x n_bins doubles -- validCount, min, max, sum, sum of squares; a bin without data is all zeros.
+int pb_bigwig_summary_query(void *h, int64_t nq, const int32_t *contig, const int64_t *start, const int64_t *end, int64_t n_bins, double *out5) {
+    SummaryRead *r = static_cast<SummaryRead *>(h);
+    if (!r || nq < 0 || (nq > 0 && (!contig || !start || !end || !out5))) return fail("pb_bigwig_summary_query: bad arguments");
+    const std::string bad_args = pcbws::check_queries(nq, start, end, n_bins);
+    if (!bad_args.empty()) return fail("pb_bigwig_summary_query: " + bad_args);
+    std::vector<uint32_t> s32((size_t)nq), e32((size_t)nq);
+    for (int64_t q = 0; q < nq; ++q) { s32[(size_t)q] = (uint32_t)start[q]; e32[(size_t)q] = (uint32_t)end[q]; }
+    const int64_t total = nq * n_bins;
+    std::vector<pcbws::Element> el((size_t)total);
+    const std::string bad = r->s.summarize(nq, contig, s32.data(), e32.data(), (uint32_t)n_bins, zlib_raw_inflate, el.data());
+    if (!bad.empty()) return fail(r->name + ": bigWig: " + bad);
+    for (int64_t k = 0; k < total; ++k) {
+        const pcbws::Element &x = el[(size_t)k];
+        out5[k] = (double)x.valid; out5[total + k] = x.mn; out5[2 * total + k] = x.mx; out5[3 * total + k] = x.sum; out5[4 * total + k] = x.sumsq;
+    }
+    return 0;
+}
+// The five kinds of nq x n_bins elements (five columns, as pb_bigwig_summary_query and pc_bigwig_summary_query give them),
+// by value_of: kinds5 holds five columns -- mean, min, max, coverage, std -- and `fill` where valid is 0.  Only the kinds
+// whose bit is set in kinds_mask (bit k: kind k) are computed; the other columns are left as they are.
+int pb_bigwig_summary_values(int64_t nq, const int64_t *start, const int64_t *end, int64_t n_bins, const double *el5, double fill, int kinds_mask, double *kinds5) {
+    if (nq < 0 || (nq > 0 && (!start || !end || !el5 || !kinds5))) return fail("pb_bigwig_summary_values: bad arguments");
+    const std::string bad_args = pcbws::check_queries(nq, start, end, n_bins);
+    if (!bad_args.empty()) return fail("pb_bigwig_summary_values: " + bad_args);
+    const int64_t total = nq * n_bins;
+    for (int64_t q = 0; q < nq; ++q)
+        for (int64_t i = 0; i < n_bins; ++i) {
+            const int64_t k = q * n_bins + i;
+            pcbws::Element x;
+            x.valid = (uint32_t)el5[k]; x.mn = el5[total + k]; x.mx = el5[2 * total + k]; x.sum = el5[3 * total + k]; x.sumsq = el5[4 * total + k];
+            for (int kind = 0; kind < pcbws::kKinds; ++kind)
+                if (kinds_mask & (1 << kind)) kinds5[(int64_t)kind * total + k] = x.valid ? pcbws::value_of(x, kind, (uint32_t)start[q], (uint32_t)end[q], (uint32_t)n_bins) : fill;
+        }
+    return 0;
+}
+// per table ([0] the items, [1 + k] level k; at most max_tables of them): [0] records (-1: not read), [1] queries; *tables: how many there are
+int pb_bigwig_summary_stats(void *h, int64_t *tables, int max_tables, int64_t *out2) {
+    SummaryRead *r = static_cast<SummaryRead *>(h);
+    if (!r || !tables || max_tables < 0 || (max_tables > 0 && !out2)) return fail("pb_bigwig_summary_stats: bad arguments");
+    *tables = (int64_t)r->s.tables.size();
+    for (size_t k = 0; k < r->s.tables.size() && k < (size_t)max_tables; ++k) {
+        const pcbws::HostTable &t = r->s.tables[k];
+        out2[2 * k] = t.loaded ? (int64_t)(k == 0 ? t.items.size() : t.zoom.size()) : -1;
+        out2[2 * k + 1] = t.queries;
     }
     return 0;
 }

@@ -662,6 +662,7 @@ struct Knobs {
 };
 
 static void destroy_tracks_of(pc_engine *e);   // (track_decoder.hip.h)
+static void destroy_summaries_of(pc_engine *e);   // (bigwig_summary.hip.h)
 
 struct pc_engine {
     DevPool pool;   // first member: outlives every buffer of the engine
@@ -678,6 +679,7 @@ struct pc_engine {
     hipEvent_t ev[8] = {};
     std::vector<StagedFile *> files;
     std::vector<pc_track *> tracks;   // the count tracks made on this engine (track_decoder.hip.h): they go with it
+    std::vector<pc_bigwig_summary *> summaries;   // the summary readers opened on this engine (bigwig_summary.hip.h): their tables come from its pool
     DevBuf<uint8_t> cx_text;          // the last pc_counts_export (track_decoder.hip.h): its text waits in HBM for pc_counts_export_read
     int64_t cx_bytes = -1;
     int64_t cx_stats[4] = {0, 0, 0, 0};      // lines, runs / non-zero cells, values listed for the host, bytes
@@ -1419,6 +1421,7 @@ int pc_destroy(pc_engine *e) {
     (void)hipSetDevice(e->device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     destroy_tracks_of(e);
+    destroy_summaries_of(e);
     for (auto *f : e->files) delete f;
     e->files.clear();
     for (auto &ev : e->ev)
@@ -3894,3 +3897,4 @@ int pc_read_mapped_reads(pc_engine *e, pc_plan *p, uint32_t *rec, int64_t total)
 #include "bigwig_decoder.hip.h"
 #include "deflate_encoder.hip.h"
 #include "bigwig_writer.hip.h"
+#include "bigwig_summary.hip.h"

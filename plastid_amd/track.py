@@ -893,6 +893,115 @@ def read_bigwig_zoom(path_or_bytes, level):
     return BigWigZoomTable(cols)
 
 
+# ---------------------------------------------------------------- binned summaries (csrc/bigwig_summary_host.h)
+SUMMARY_KINDS = ("mean", "min", "max", "coverage", "std")
+SUMMARY_ELEMENTS = ("valid", "min", "max", "sum", "sumsq")
+
+
+def _summary_kinds(kind):
+    """``(the kinds asked for, whether they came as a tuple)``."""
+    kinds = tuple(kind) if isinstance(kind, (tuple, list)) else (kind,)
+    for k in kinds:
+        if k not in SUMMARY_KINDS:
+            raise ValueError("kind %r is none of %r" % (k, SUMMARY_KINDS))
+    return kinds, isinstance(kind, (tuple, list))
+
+
+def _summary_queries(queries, n_bins):
+    """``(chrom names, start, end)`` of queries given as ``(chrom, start, end)`` tuples or as segments; the argument errors."""
+    if int(n_bins) != n_bins or n_bins < 1 or n_bins >= 2 ** 31:
+        raise ValueError("n_bins %r is not in 1 .. 2^31 - 1" % (n_bins,))
+    rows = [(q.chrom, q.start, q.end) if hasattr(q, "chrom") else tuple(q) for q in queries]
+    names = [r[0] for r in rows]
+    start, end = np.array([int(r[1]) for r in rows], np.int64), np.array([int(r[2]) for r in rows], np.int64)
+    for k in np.flatnonzero((start < 0) | (start >= 2 ** 31) | (end >= 2 ** 31))[:1]:
+        raise ValueError("query %d (%s:%d-%d): a coordinate below 0 or at or beyond 2^31" % (k, names[k], start[k], end[k]))
+    for k in np.flatnonzero(start >= end)[:1]:
+        raise ValueError("query %d (%s:%d-%d): start >= end" % (k, names[k], start[k], end[k]))
+    return names, start, end
+
+
+def _summary_contigs(names, index, filename):
+    """The place of every query's contig in the file's chromosome list, -1 (and one ``DataWarning`` per name) where it has none."""
+    contig = np.array([index.get(n, -1) for n in names], np.int32)
+    for c in sorted(set(names[k] for k in np.flatnonzero(contig < 0))):
+        warn(WARN_CHROM_NOT_FOUND % (c, filename), DataWarning)
+    return contig
+
+
+def _bind_summary(L):
+    if not hasattr(L.pb_bigwig_summary_open, "_bound"):
+        vp = ctypes.c_void_p
+        L.pb_bigwig_summary_open.restype = vp
+        L.pb_bigwig_summary_open.argtypes = [vp, ctypes.c_int64, ctypes.c_char_p]
+        L.pb_bigwig_summary_close.argtypes = [vp]
+        L.pb_bigwig_summary_nchrom.argtypes = [vp]
+        L.pb_bigwig_summary_chrom.restype = ctypes.c_char_p
+        L.pb_bigwig_summary_chrom.argtypes = [vp, ctypes.c_int]
+        L.pb_bigwig_summary_query.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp]
+        L.pb_bigwig_summary_values.argtypes = [ctypes.c_int64, vp, vp, ctypes.c_int64, vp, ctypes.c_double, ctypes.c_int, vp]
+        L.pb_bigwig_summary_stats.argtypes = [vp, vp, ctypes.c_int, vp]
+        L.pb_bigwig_summary_open._bound = True
+
+
+def _summary_values(start, end, n_bins, elements, kinds, as_dict, fill):
+    """The kinds of ``float64[5, nq, n_bins]`` elements by the model's formulas (``value_of``), `fill` where valid is 0."""
+    from .bam import _load
+    L = _load()
+    _bind_summary(L)
+    nq = len(start)
+    out = np.empty((5, nq, int(n_bins)), np.float64)          # (only the columns asked for are filled, and returned)
+    mask = sum(1 << SUMMARY_KINDS.index(k) for k in set(kinds))
+    if nq and L.pb_bigwig_summary_values(nq, start.ctypes.data, end.ctypes.data, int(n_bins), elements.ctypes.data, float(fill), mask, out.ctypes.data) != 0:
+        raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    if as_dict:
+        return {k: out[SUMMARY_KINDS.index(k)] for k in kinds}
+    return out[SUMMARY_KINDS.index(kinds[0])]
+
+
+def _summary_elements_host(path_or_bytes, queries, n_bins):
+    from .bam import _load
+    L = _load()
+    _bind_summary(L)
+    names, start, end = _summary_queries(queries, n_bins)
+    ptr, size, name, _keep = _bigwig_bytes(path_or_bytes)
+    h = L.pb_bigwig_summary_open(ptr, size, name)
+    if not h:
+        raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    try:
+        index = {L.pb_bigwig_summary_chrom(h, i).decode("utf-8", "replace"): i for i in range(L.pb_bigwig_summary_nchrom(h))}
+        contig = _summary_contigs(names, index, name.decode("utf-8", "replace"))
+        out = np.empty((5, len(names), int(n_bins)), np.float64)       # (the call fills every element)
+        if len(names) and L.pb_bigwig_summary_query(h, len(names), contig.ctypes.data, start.ctypes.data, end.ctypes.data, int(n_bins), out.ctypes.data) != 0:
+            raise ValueError(L.pb_last_error().decode("utf-8", "replace"))
+    finally:
+        L.pb_bigwig_summary_close(h)
+    return out, start, end
+
+
+def summary_elements_bigwig(path_or_bytes, queries, n_bins):
+    """The summary elements of ``(chrom, start, end)`` queries over `n_bins` equal bins each, on the host, one thread: a
+    dict of ``float64[len(queries), n_bins]`` columns ``valid``, ``min``, ``max``, ``sum``, ``sumsq`` -- Kent's
+    ``bbiSummaryElement`` per bin; a bin without data is all zeros.  See :func:`summarize_bigwig`."""
+    out, _, _ = _summary_elements_host(path_or_bytes, queries, n_bins)
+    return dict(zip(SUMMARY_ELEMENTS, out))
+
+
+def summarize_bigwig(path_or_bytes, queries, n_bins, kind="mean", fill=np.nan):
+    """Binned summaries of a bigWig file (a path, or its bytes) on the host, one thread, without a GPU: what Kent's
+    ``bigWigSummaryArray`` gives, bit for bit (``csrc/bigwig_summary_host.h`` states the rules; the kernels of
+    :meth:`BigWigReader.summarize_batch` run the same functions).  `queries`: ``(chrom, start, end)`` tuples or segments;
+    every query is cut into `n_bins` equal bins and answered from the coarsest zoom level that still gives two records per
+    bin, from the items where no level is coarse enough.  `kind`: one of ``mean``, ``min``, ``max``, ``coverage``, ``std``
+    -- ``float64[len(queries), n_bins]`` -- or a tuple of them -- a dict.  A bin without data, and every bin on a contig
+    the file lacks, is `fill`.  ``ValueError``: ``n_bins < 1``, ``start >= end``, a coordinate at or beyond 2^31, a file
+    that is refused, and ``"<path>: bigWig: summarize needs records in coordinate order"`` for a table whose records are
+    not sorted (Kent's writer and ours sort them)."""
+    kinds, as_dict = _summary_kinds(kind)
+    out, start, end = _summary_elements_host(path_or_bytes, queries, n_bins)
+    return _summary_values(start, end, n_bins, out, kinds, as_dict, fill)
+
+
 def sum_ranges(lengths):
     """The positions ``BigWigReader.sum()`` adds, per contig in ``chroms`` order: the reference's position counter is set
     to 0 once, in front of the loop over the contigs (plastid/readers/bigwig.pyx:273-296), so contig k gives only its
@@ -1125,8 +1234,20 @@ class BigWigReader(object):
     are inflated, checked and decoded on the GPU once, at construction, into a one-strand count track (float64 cells per
     contig up to the furthest end written); every read is a gather.  `maxmem` is accepted and ignored; `engine`: an
     :class:`~plastid_amd.engine.Engine` to share (default: one of its own on GPU 0).  ``fill`` is fixed at 0.0, as in the
-    reference, whose setter is commented out.  Not here: ``__iter__`` / ``BigWigIterator``, ``summarize``, remote files.
-    ``ValueError("<path>: bigWig: <what>")`` for a file that is refused (README: byte-swapped files are)."""
+    reference, whose setter is commented out.  Not here: ``__iter__`` / ``BigWigIterator``, remote files.
+    ``ValueError("<path>: bigWig: <what>")`` for a file that is refused (README: byte-swapped files are).
+
+    :meth:`summarize` / :meth:`summarize_batch` / :meth:`summary_elements_batch` are the batched reader a browser or
+    ``bigWigSummary`` is: mean, min, max, coverage and std over `n_bins` equal bins of each of many regions, Kent's
+    ``bigWigSummaryArray`` bit for bit.  They do not read the cells (the import keeps no coverage: a stored 0.0 and "no
+    data" are the same cell) but the file's ZOOM LEVELS and items: every query is answered from the level with the
+    greatest reduction that still gives two records per bin, from the items where no level is that fine.  A table -- one
+    level's records, or the items -- goes to HBM at the first query that selects it and stays; ``k_bbi_summarize`` then runs
+    one lane per (query, bin), once per table in use, and one buffer of elements comes back.  A lane walks its bin
+    serially, because the sums are exact in their order: a file WITHOUT zoom levels asked for bins of millions of items
+    is slow by construction -- that case is what ``to_bigwig(zoom=True)`` is for.  A table whose records are not in
+    coordinate order (no writer of Kent's or ours makes one) raises ``ValueError("<path>: bigWig: summarize needs records
+    in coordinate order")`` on the queries that would use it; ``get`` and the rest are not affected."""
 
     def __init__(self, filename, maxmem=0, engine=None, **kwargs):
         self.filename = os.fspath(filename)
@@ -1144,9 +1265,23 @@ class BigWigReader(object):
         self._engine = self._ga._engine
         self._chroms = self._ga.lengths()
         self._index = {c: i for i, c in enumerate(self._chroms)}
+        self._summary = None
 
     def close(self):
+        self._close_summary()
         self._ga.close()
+
+    def _close_summary(self):
+        if getattr(self, "_summary", None) is not None:
+            if self._engine._finalizer.alive:      # (an engine that is gone took its summary readers with it)
+                self._ga._lib.pc_bigwig_summary_close(self._summary)
+            self._summary = None
+
+    def __del__(self):
+        try:
+            self._close_summary()
+        except Exception:
+            pass
 
     @property
     def chroms(self):
@@ -1185,6 +1320,74 @@ class BigWigReader(object):
 
     def __getitem__(self, roi):
         return self.get(roi)
+
+    # ---- binned summaries from the zoom levels and the items
+    def _summary_handle(self):
+        if self._summary is None:
+            h = ctypes.c_void_p()
+            check(self._ga._lib.pc_bigwig_summary_open_path(self._engine._h, os.fsencode(self.filename), ctypes.byref(h)), "pc_bigwig_summary_open_path")
+            self._summary = h
+        return self._summary
+
+    def _summary_elements(self, segments, n_bins):
+        """``(float64[5, len, n_bins] elements, start, end)`` of `segments` in genome order."""
+        names, start, end = _summary_queries(segments, n_bins)
+        contig = _summary_contigs(names, self._index, self.filename)
+        out = np.empty((5, len(names), int(n_bins)), np.float64)       # (the call fills every element)
+        if len(names):
+            check(self._ga._lib.pc_bigwig_summary_query(self._summary_handle(), len(names), contig.ctypes.data, start.ctypes.data, end.ctypes.data, int(n_bins),
+                                                        out.ctypes.data), "pc_bigwig_summary_query")
+        return out, start, end
+
+    def summary_elements_batch(self, segments, n_bins):
+        """Kent's ``bbiSummaryElement`` per bin of every segment: a dict of ``float64[len(segments), n_bins]`` columns
+        ``valid``, ``min``, ``max``, ``sum``, ``sumsq``, bins in genome order; a bin without data is all zeros."""
+        out, _, _ = self._summary_elements(segments, n_bins)
+        return dict(zip(SUMMARY_ELEMENTS, out))
+
+    def summarize_batch(self, segments, n_bins, kind="mean", fill=np.nan, roi_order=True):
+        """`kind` -- ``mean``, ``min``, ``max``, ``coverage`` or ``std`` -- over `n_bins` equal bins of every |GenomicSegment|
+        (or ``(chrom, start, end)`` tuple) of `segments`, in one call: ``float64[len(segments), n_bins]``; a tuple of kinds
+        gives a dict of such arrays.  Bin ``i`` of a segment is ``[start + span * i // n_bins, start + span * (i + 1) //
+        n_bins)``; the bins of a ``'-'`` segment come reversed when `roi_order`, as :meth:`get` returns them.  A bin
+        without data is `fill`; so is every bin on a contig the file lacks, with the ``DataWarning`` of :meth:`get`.
+        ``ValueError``: ``n_bins < 1``, ``start >= end``, a coordinate at or beyond 2^31, a table that is not in
+        coordinate order (the class docstring)."""
+        kinds, as_dict = _summary_kinds(kind)
+        segments = list(segments)
+        el, start, end = self._summary_elements(segments, n_bins)
+        out = _summary_values(start, end, n_bins, el, kinds, as_dict, fill)
+        if roi_order is True:
+            rev = np.array([getattr(s, "strand", "+") == "-" for s in segments], bool)
+            for a in (out.values() if as_dict else (out,)):
+                a[rev] = a[rev, ::-1]
+        return out
+
+    def summarize(self, roi, n_bins=1, kind="mean", fill=np.nan, roi_order=True):
+        """:meth:`summarize_batch` of one |GenomicSegment|: ``float64[n_bins]`` (a dict of them for a tuple of kinds)."""
+        out = self.summarize_batch([roi], n_bins, kind=kind, fill=fill, roi_order=roi_order)
+        return {k: v[0] for k, v in out.items()} if isinstance(out, dict) else out[0]
+
+    def summary_stats(self):
+        """Of the summaries so far: ``tables`` the file has (the items and its zoom levels), ``tables_loaded``,
+        ``bytes_uploaded``, ``bytes_inflated``, and per table -- ``"items"`` or the level's reduction -- its ``records``
+        (``None`` until it is loaded) and the ``queries`` it has answered."""
+        L, h = self._ga._lib, self._summary_handle()
+        head = np.zeros(4, np.int64)
+        check(L.pc_bigwig_summary_stats(h, head.ctypes.data, 0, None))
+        per = np.zeros(3 * max(int(head[0]), 1), np.int64)
+        check(L.pc_bigwig_summary_stats(h, head.ctypes.data, int(head[0]), per.ctypes.data))
+        out = dict(zip(("tables", "tables_loaded", "bytes_uploaded", "bytes_inflated"), (int(x) for x in head)))
+        out["per_table"] = OrderedDict(("items" if k == 0 else int(per[3 * k]), {"records": None if per[3 * k + 1] < 0 else int(per[3 * k + 1]), "queries": int(per[3 * k + 2])})
+                                       for k in range(int(head[0])))
+        return out
+
+    def summary_timing(self):
+        """Milliseconds of the last summary call on the engine's stream: upload, inflate + Adler-32, records + order check
+        (all 0 when it loaded no table), the summarize kernels, the read-back."""
+        out = np.zeros(5, np.float64)
+        check(self._ga._lib.pc_bigwig_summary_timing(self._summary_handle(), out.ctypes.data))
+        return dict(zip(("upload", "inflate_adler", "records_order_check", "kernel", "read_back"), (float(x) for x in out)))
 
     def get_chromosome_counts(self, chrom):
         """The whole contig at its size in the chromosome tree, zeros where no data; an unknown contig warns and gives
