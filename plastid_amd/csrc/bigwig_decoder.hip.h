@@ -7,6 +7,9 @@
 // a text import; then the contigs of the chromosome tree are declared at their sizes (no growth: an item cannot pass its
 // contig's size), the storage is made and the records are sorted and applied by the kernels of the text import in their
 // ASSIGN mode.  Every defect is known before the track changes: a refused file leaves it as it was.
+// Upload, inflate and Adler-32 are bigwig_load_blocks over a BigWigBlocks, the section pass is bigwig_sections over a
+// BigWigSections: the summary reader (bigwig_summary.hip.h) loads its tables through the same two, and reads the
+// statuses on the host through bigwig_block_words.  bigwig_parse is the prologue of pc_bigwig_info / _blocks.
 // Part of the one translation unit of plastid_counts.hip (behind track_decoder.hip.h).
 #include "bigwig_kernels.hip.h"
 
@@ -36,107 +39,142 @@ int queue_zlib_inflate(hipStream_t st, const uint8_t *d_image, const pcbam::Memb
     return PC_OK;
 }
 
+// The blocks of a file, or of one zoom level of it, in HBM: inflated and Adler-checked when the file is compressed, as
+// they stand in the file otherwise.  Block b is bytes [off[b], off[b] + len[b]) of data.
+struct BigWigBlocks {
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> sizes;       // stored blocks: what d_len is uploaded from
+    DevBuf<uint8_t> d_inflated;
+    DevBuf<uint32_t> d_status, d_len;  // d_status (compressed): the statuses, then the bytes every block inflated to; d_len (stored): the sizes
+    DevBuf<uint64_t> d_off;
+    const uint8_t *data = nullptr;
+    const uint32_t *len = nullptr, *status = nullptr;   // status: null for stored blocks
+};
+
+// The bytes [data_lo, data_hi) of `f` cross PCIe once into d.d_stream; inflate and Adler-32; the blocks' offsets.  The
+// three events are recorded in front of the upload, behind it, and behind everything queued here.
+int bigwig_load_blocks(BamDecode &d, const uint8_t *image, const bw::BigWig &f, hipEvent_t start, hipEvent_t uploaded, hipEvent_t inflated, BigWigBlocks &k) {
+    hipStream_t st = d.st;
+    const int64_t nb = (int64_t)f.blocks.size(), bytes = (int64_t)(f.data_hi - f.data_lo);
+    {
+        Upload u;
+        Drain drain{d.e, true};
+        PC_TRY(d.d_stream.reserve((size_t)bytes + 64));
+        HIP_TRY(hipEventRecord(start, st));
+        PC_TRY(sam_upload(d, image + f.data_lo, bytes, nullptr, u));
+        HIP_TRY(hipStreamSynchronize(st));   // (the ring's halves and its events are the engine's: the next user finds them idle)
+        drain.armed = false;
+    }
+    HIP_TRY(hipEventRecord(uploaded, st));
+    k.off.resize((size_t)nb);
+    if (f.compressed()) {
+        const std::vector<pcbam::Member> ms = zlib_members(f);
+        for (int64_t b = 0; b < nb; ++b) k.off[(size_t)b] = ms[(size_t)b].uoff;
+        int rc = PC_OK;
+        room(rc, k.d_inflated, (size_t)nb * (size_t)f.slot_bytes() + 64); room(rc, k.d_status, 2 * (size_t)nb);
+        room(rc, d.d_members, (size_t)nb);
+        if (rc != PC_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(d.d_members.p, ms.data(), ms.size() * sizeof(pcbam::Member), hipMemcpyHostToDevice, st));
+        PC_TRY(queue_zlib_inflate(st, d.d_stream.p, d.d_members.p, (int)nb, k.d_inflated.p, k.d_status.p));
+        HIP_TRY(hipStreamSynchronize(st));   // (ms goes out of scope)
+        k.data = k.d_inflated.p; k.len = k.d_status.p + nb; k.status = k.d_status.p;
+    } else {
+        k.sizes.resize((size_t)nb);
+        for (int64_t b = 0; b < nb; ++b) { k.off[(size_t)b] = f.blocks[(size_t)b].off - f.data_lo; k.sizes[(size_t)b] = (uint32_t)f.blocks[(size_t)b].size; }
+        PC_TRY(k.d_len.upload(k.sizes, st));
+        k.data = d.d_stream.p; k.len = k.d_len.p;
+    }
+    PC_TRY(k.d_off.upload(k.off, st));
+    HIP_TRY(hipEventRecord(inflated, st));
+    return PC_OK;
+}
+
+// The statuses of the nb loaded blocks and behind them their lengths, on the host (stored blocks: zeros and the sizes).
+int bigwig_block_words(hipStream_t st, const BigWigBlocks &k, std::vector<uint32_t> &words) {
+    const size_t nb = k.off.size();
+    words.assign(2 * nb, 0u);
+    if (!k.status) {
+        std::copy(k.sizes.begin(), k.sizes.end(), words.begin() + (ptrdiff_t)nb);
+        return PC_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(words.data(), k.status, 2 * nb * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PC_OK;
+}
+
+// What the sections pass leaves: every block's item count and the items in front of it (nb + 1 entries each), the
+// contigs by chromId, the counters in HBM and as they stood behind the pass, the number of items.
+struct BigWigSections {
+    DevBuf<uint32_t> d_count, d_first;
+    DevBuf<bw::ChromOfId> d_ids;
+    DevBuf<bw::BwCounters> d_cnt;
+    bw::BwCounters cnt = {bw::kNoDefect, {0ull, 0ull, 0ull}, 0ull};
+    int64_t nitems = 0;
+};
+
+// Section headers and the exclusive sum of their item counts.  A defective block has no items and leaves its defect in
+// s.cnt.first_err: the caller reports it, behind its items' when it goes on to them.
+int bigwig_sections(hipStream_t st, DevBuf<uint8_t> &d_tmp, const std::string &path, const BigWigBlocks &k, int64_t nb, const std::vector<bw::ChromOfId> &of_id,
+                    BigWigSections &s) {
+    int rc = PC_OK;
+    room(rc, s.d_count, (size_t)nb + 1); room(rc, s.d_first, (size_t)nb + 1); room(rc, s.d_cnt, 1);
+    if (rc != PC_OK) return rc;
+    PC_TRY(s.d_ids.upload(of_id, st));
+    memset(&s.cnt, 0, sizeof(s.cnt));
+    s.cnt.first_err = bw::kNoDefect;
+    HIP_TRY(hipMemcpyAsync(s.d_cnt.p, &s.cnt, sizeof(s.cnt), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(s.d_count.p + nb, 0, 4, st));
+    hipLaunchKernelGGL(bw::k_bw_sections, dim3(grid256(nb)), dim3(256), 0, st, k.data, k.d_off.p, k.len, k.status, nb, s.d_ids.p, (uint32_t)of_id.size(), s.d_count.p, s.d_cnt.p);
+    HIP_TRY(hipGetLastError());
+    // (nb + 1 entries: the last sum is the number of items -- below 2^32 for fewer than 2^16 blocks, checked otherwise)
+    uint64_t total64 = 0;
+    if (nb >= 65536) {
+        std::vector<uint32_t> counts((size_t)nb);
+        HIP_TRY(hipMemcpyAsync(counts.data(), s.d_count.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (uint32_t v : counts) total64 += v;
+        if (total64 >= ((uint64_t)1 << 31)) return fail(PC_ERR_ARG, "%s: bigWig: more than 2^31 - 1 items", path.c_str());
+    }
+    PC_TRY(cub_run(d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, s.d_count.p, s.d_first.p, (int)nb + 1, st); }));
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, s.d_first.p + nb, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&s.cnt, s.d_cnt.p, sizeof(s.cnt), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    s.nitems = (int64_t)total;
+    if (s.nitems >= ((int64_t)1 << 31)) return fail(PC_ERR_ARG, "%s: bigWig: more than 2^31 - 1 items", path.c_str());
+    return PC_OK;
+}
+
 struct BigWigImport {
     TrackImport c;                     // the phases behind the items are the text import's
     bw::BigWig f;
     LapEvents<5> ev;                   // start | uploaded | inflated + checked | sections + items | applied
     std::vector<bw::ChromOfId> of_id;  // by chromId: the TRACK's contig and the size
     std::vector<int32_t> track_id;     // by place in f.chroms
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> len;
-    bw::BwCounters cnt = {bw::kNoDefect, {0ull, 0ull, 0ull}, 0ull};
-    int64_t nitems = 0;
-    DevBuf<uint8_t> d_inflated;
-    DevBuf<uint32_t> d_status, d_len, d_count, d_first;   // d_status: the statuses, then the bytes every block inflated to
-    DevBuf<uint64_t> d_off;
-    DevBuf<bw::ChromOfId> d_ids;
-    DevBuf<bw::BwCounters> d_cnt;
+    BigWigBlocks k;
+    BigWigSections s;
     BigWigImport(pc_track *t, const char *name, int strand) : c(t, nullptr, 0, name, strand) {}
 };
 
-// Phases 2, 3: the blocks to HBM; inflate and Adler-32.  Leaves x.off / d_off, and where the sections and their lengths are.
-int bigwig_upload_and_inflate(BigWigImport &x, const uint8_t *image, const uint8_t *&d_data, const uint32_t *&d_len) {
+// Phase 4: the sections pass, the items as line records; the lowest defect ends the import.
+int bigwig_sections_and_items(BigWigImport &x) {
     TrackImport &c = x.c;
     hipStream_t st = c.st;
-    const bw::BigWig &f = x.f;
-    const int64_t nb = (int64_t)f.blocks.size(), bytes = (int64_t)(f.data_hi - f.data_lo);
-    {
-        Upload u;
-        Drain drain{c.d.e, true};
-        PC_TRY(c.d.d_stream.reserve((size_t)bytes + 64));
-        HIP_TRY(hipEventRecord(x.ev[0], st));
-        PC_TRY(sam_upload(c.d, image + f.data_lo, bytes, nullptr, u));
-        HIP_TRY(hipStreamSynchronize(st));   // (the ring's halves and its events are the engine's: the next user finds them idle)
-        drain.armed = false;
-    }
-    HIP_TRY(hipEventRecord(x.ev[1], st));
-    x.off.resize((size_t)nb); x.len.resize((size_t)nb);
-    int rc = PC_OK;
-    if (f.compressed()) {
-        const std::vector<pcbam::Member> ms = zlib_members(f);
-        for (int64_t b = 0; b < nb; ++b) x.off[(size_t)b] = ms[(size_t)b].uoff;
-        room(rc, x.d_inflated, (size_t)nb * (size_t)f.slot_bytes() + 64); room(rc, x.d_status, 2 * (size_t)nb);
-        room(rc, c.d.d_members, (size_t)nb);
-        if (rc != PC_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(c.d.d_members.p, ms.data(), ms.size() * sizeof(pcbam::Member), hipMemcpyHostToDevice, st));
-        PC_TRY(queue_zlib_inflate(st, c.d.d_stream.p, c.d.d_members.p, (int)nb, x.d_inflated.p, x.d_status.p));
-        HIP_TRY(hipStreamSynchronize(st));   // (ms goes out of scope)
-        d_data = x.d_inflated.p; d_len = x.d_status.p + nb;
-    } else {
-        for (int64_t b = 0; b < nb; ++b) { x.off[(size_t)b] = f.blocks[(size_t)b].off - f.data_lo; x.len[(size_t)b] = (uint32_t)f.blocks[(size_t)b].size; }
-        PC_TRY(x.d_len.upload(x.len, st));
-        d_data = c.d.d_stream.p; d_len = x.d_len.p;
-    }
-    PC_TRY(x.d_off.upload(x.off, st));
-    HIP_TRY(hipEventRecord(x.ev[2], st));
-    return PC_OK;
-}
-
-// Phase 4: section headers, the exclusive sum of their item counts, the items as line records; the lowest defect ends
-// the import.
-int bigwig_sections_and_items(BigWigImport &x, const uint8_t *d_data, const uint32_t *d_len) {
-    TrackImport &c = x.c;
-    hipStream_t st = c.st;
-    const bw::BigWig &f = x.f;
-    const int64_t nb = (int64_t)f.blocks.size();
-    int rc = PC_OK;
-    room(rc, x.d_count, (size_t)nb + 1); room(rc, x.d_first, (size_t)nb + 1); room(rc, x.d_cnt, 1);
-    if (rc != PC_OK) return rc;
-    PC_TRY(x.d_ids.upload(x.of_id, st));
-    memset(&x.cnt, 0, sizeof(x.cnt));
-    x.cnt.first_err = bw::kNoDefect;
-    HIP_TRY(hipMemcpyAsync(x.d_cnt.p, &x.cnt, sizeof(x.cnt), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(x.d_count.p + nb, 0, 4, st));
-    hipLaunchKernelGGL(bw::k_bw_sections, dim3(grid256(nb)), dim3(256), 0, st, d_data, x.d_off.p, d_len, f.compressed() ? x.d_status.p : (uint32_t *)nullptr, nb,
-                       x.d_ids.p, (uint32_t)x.of_id.size(), x.d_count.p, x.d_cnt.p);
-    HIP_TRY(hipGetLastError());
-    // (nb + 1 entries: the last sum is the number of items -- below 2^32 for fewer than 2^16 blocks, checked otherwise)
-    uint64_t total64 = 0;
-    if (nb >= 65536) {
-        std::vector<uint32_t> counts((size_t)nb);
-        HIP_TRY(hipMemcpyAsync(counts.data(), x.d_count.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (uint32_t v : counts) total64 += v;
-        if (total64 >= ((uint64_t)1 << 31)) return fail(PC_ERR_ARG, "%s: bigWig: more than 2^31 - 1 items", c.d.path.c_str());
-    }
-    PC_TRY(cub_run(c.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, x.d_count.p, x.d_first.p, (int)nb + 1, st); }));
-    uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, x.d_first.p + nb, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&x.cnt, x.d_cnt.p, sizeof(x.cnt), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    x.nitems = (int64_t)total;
-    if (x.nitems >= ((int64_t)1 << 31)) return fail(PC_ERR_ARG, "%s: bigWig: more than 2^31 - 1 items", c.d.path.c_str());
+    BigWigSections &s = x.s;
+    const int64_t nb = (int64_t)x.f.blocks.size();
+    PC_TRY(bigwig_sections(st, c.d_tmp, c.d.path, x.k, nb, x.of_id, s));
     // (with a defective block too: an item of a block in front of it may hold the lower defect; such a block has no items here)
-    if (x.nitems > 0) {
-        c.n = x.nitems; c.g = grid256(c.n);
+    if (s.nitems > 0) {
+        c.n = s.nitems; c.g = grid256(c.n);
+        int rc = PC_OK;
         room(rc, c.d_line, (size_t)c.n); room(rc, c.d_contig_of, (size_t)c.n); room(rc, c.d_cls, (size_t)c.n);
         if (rc != PC_OK) return rc;
-        hipLaunchKernelGGL(bw::k_bw_items, dim3(c.g), dim3(256), 0, st, d_data, x.d_off.p, x.d_first.p, nb, c.n, x.d_ids.p, c.d_line.p, c.d_contig_of.p, c.d_cls.p, x.d_cnt.p);
+        hipLaunchKernelGGL(bw::k_bw_items, dim3(c.g), dim3(256), 0, st, x.k.data, x.k.d_off.p, s.d_first.p, nb, c.n, s.d_ids.p, c.d_line.p, c.d_contig_of.p, c.d_cls.p, s.d_cnt.p);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&x.cnt, x.d_cnt.p, sizeof(x.cnt), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&s.cnt, s.d_cnt.p, sizeof(s.cnt), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
-    if (x.cnt.first_err != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(c.d.path.c_str(), x.cnt.first_err).c_str());
+    if (s.cnt.first_err != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(c.d.path.c_str(), s.cnt.first_err).c_str());
     HIP_TRY(hipEventRecord(x.ev[3], st));
     return PC_OK;
 }
@@ -192,11 +230,9 @@ int bigwig_add_impl(pc_track *t, const void *image, int64_t size, const char *na
     if (t->tab.names.size() >= ((size_t)1 << 22)) return fail(PC_ERR_ARG, "%s: more than 2^22 contigs", x.c.d.path.c_str());
     PC_TRY(x.ev.create());
     DrainOnExit drained{x.c.st};
-    const uint8_t *d_data = nullptr;
-    const uint32_t *d_len = nullptr;
     if (!x.f.blocks.empty()) {
-        PC_TRY(bigwig_upload_and_inflate(x, (const uint8_t *)image, d_data, d_len));
-        PC_TRY(bigwig_sections_and_items(x, d_data, d_len));
+        PC_TRY(bigwig_load_blocks(x.c.d, (const uint8_t *)image, x.f, x.ev[0], x.ev[1], x.ev[2], x.k));   // phases 2, 3
+        PC_TRY(bigwig_sections_and_items(x));
     } else {
         for (int k = 0; k < 4; ++k) HIP_TRY(hipEventRecord(x.ev[k], x.c.st));
     }
@@ -208,9 +244,20 @@ int bigwig_add_impl(pc_track *t, const void *image, int64_t size, const char *na
     x.ev.laps(t->bw_ms, 4);
     const int64_t nb = (int64_t)x.f.blocks.size();
     t->bw_stats[0] = nb; t->bw_stats[1] = x.f.compressed() ? nb : 0;
-    for (int k = 0; k < 3; ++k) t->bw_stats[2 + k] = (int64_t)x.cnt.by_type[k];
-    t->bw_stats[5] = x.nitems > 0 ? (int64_t)x.c.cnt.n_multi : 0;
-    t->bw_stats[6] = (int64_t)(x.f.data_hi - x.f.data_lo); t->bw_stats[7] = x.f.compressed() ? (int64_t)x.cnt.bytes : 0;
+    for (int k = 0; k < 3; ++k) t->bw_stats[2 + k] = (int64_t)x.s.cnt.by_type[k];
+    t->bw_stats[5] = x.s.nitems > 0 ? (int64_t)x.c.cnt.n_multi : 0;
+    t->bw_stats[6] = (int64_t)(x.f.data_hi - x.f.data_lo); t->bw_stats[7] = x.f.compressed() ? (int64_t)x.s.cnt.bytes : 0;
+    return PC_OK;
+}
+
+// The container of the image, or of the file at `path` when there is no image (mapped into mf), parsed into f.
+int bigwig_parse(const char *path, const void *image, int64_t size, MappedFile &mf, bw::BigWig &f) {
+    if (!image) {
+        PC_TRY(mf.open(path, 0, 0));
+        image = mf.p; size = (int64_t)mf.size;
+    }
+    const unsigned long long d = bw::parse((const uint8_t *)image, (uint64_t)size, f);
+    if (d != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(path, d).c_str());
     return PC_OK;
 }
 
@@ -221,13 +268,8 @@ extern "C" {
 int pc_bigwig_info(const char *path, const void *image, int64_t size, int64_t *out5, int max_contigs, char *names, int64_t names_bytes, int64_t *sizes) {
     if ((!path && !image) || !out5 || size < 0 || max_contigs < 0 || names_bytes < 0) return fail(PC_ERR_ARG, "pc_bigwig_info: bad arguments");
     MappedFile mf;
-    if (!image) {
-        PC_TRY(mf.open(path, 0, 0));
-        image = mf.p; size = (int64_t)mf.size;
-    }
     bw::BigWig f;
-    const unsigned long long d = bw::parse((const uint8_t *)image, (uint64_t)size, f);
-    if (d != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(path, d).c_str());
+    PC_TRY(bigwig_parse(path, image, size, mf, f));
     int64_t need = 0;
     for (const bw::Chrom &c : f.chroms) need += (int64_t)c.name.size() + 1;
     out5[0] = (int64_t)f.chroms.size(); out5[1] = (int64_t)f.blocks.size(); out5[2] = f.uncompress_buf; out5[3] = f.version; out5[4] = need;
@@ -245,13 +287,8 @@ int pc_bigwig_info(const char *path, const void *image, int64_t size, int64_t *o
 int pc_bigwig_blocks(const char *path, const void *image, int64_t size, int64_t nblocks, int64_t *off, int64_t *bytes) {
     if ((!path && !image) || size < 0 || nblocks < 0 || (nblocks > 0 && (!off || !bytes))) return fail(PC_ERR_ARG, "pc_bigwig_blocks: bad arguments");
     MappedFile mf;
-    if (!image) {
-        PC_TRY(mf.open(path, 0, 0));
-        image = mf.p; size = (int64_t)mf.size;
-    }
     bw::BigWig f;
-    const unsigned long long d = bw::parse((const uint8_t *)image, (uint64_t)size, f);
-    if (d != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(path, d).c_str());
+    PC_TRY(bigwig_parse(path, image, size, mf, f));
     if (nblocks != (int64_t)f.blocks.size()) return fail(PC_ERR_ARG, "pc_bigwig_blocks: the file has %lld blocks", (long long)f.blocks.size());
     for (size_t b = 0; b < f.blocks.size(); ++b) { off[b] = (int64_t)f.blocks[b].off; bytes[b] = (int64_t)f.blocks[b].size; }
     return PC_OK;

@@ -9,9 +9,11 @@
 //                     b(AB) = b(A) + b(B) + |B| (a(A) - 1);
 //   k_bw_sections     one lane per block: the section header against the block's produced length (check_section of
 //                     bigwig_host.h) -> the block's item count (0 with a defect) and the lowest defect;
-//   k_bw_items        one lane per item: its block by bisection over the exclusive sum of the counts, the item decoded
-//                     and checked by the host reader's functions -> the line record (contig, start, stop,
-//                     (double) float32) that k_track_keys and the kernels behind it consume;
+//   item_at           (device function, shared with k_bbi_items of bigwig_summary_kernels.hip.h) an item's block by
+//                     bisection over the exclusive sum of the counts, the item decoded and checked by the host reader's
+//                     functions;
+//   k_bw_items        one lane per item: item_at -> the line record (contig, start, stop, (double) float32) that
+//                     k_track_keys and the kernels behind it consume;
 //   k_track_gather_acc / k_track_scale   BigWigGenomeArray.get: out = out + cells, one launch per reader in reader order
 //                     (every reader cuts its own items: its contigs and extents are its own), then v / sum * 1e6;
 //   k_track_sum_tiles the fixed-tree sum over ranges of cells (BigWigReader.sum()).
@@ -89,27 +91,37 @@ __global__ __launch_bounds__(256) void k_bw_sections(const uint8_t *__restrict__
     atomicAdd(&cnt->bytes, (unsigned long long)len[b]);
 }
 
-// One lane per item.  first[b]: items in front of block b (the exclusive sum of the counts).  The record of item i goes to
-// out[i], the track's contig of it to contig_of[i] (-1 with a defect), its class (a bedGraph line) to cls[i].
+// Item i of a file: its block b (first[b]: items in front of block b, the exclusive sum of the counts; blocks without
+// items share their successor's sum: the last block whose sum is <= i is the one that holds item i), its place k in the
+// block, the section, the item decoded and checked by the host reader's functions, the contig of its chromId.
+struct ItemAt { int b; uint32_t k; Section s; Item it; ChromOfId c; int err; };
+__device__ inline ItemAt item_at(const uint8_t *__restrict__ data, const uint64_t *__restrict__ off, const uint32_t *__restrict__ first, int64_t nblocks, int64_t i,
+                                 const ChromOfId *__restrict__ ids) {
+    ItemAt a;
+    a.b = pctrack::last_at_or_below((int)nblocks, i, [first](int k) { return (int64_t)first[k]; });
+    const uint8_t *p = data + off[a.b];
+    a.s = section_header(p);
+    a.c = ids[a.s.chrom_id];
+    a.k = (uint32_t)(i - (int64_t)first[a.b]);
+    a.it = section_item(a.s, p + kSectionHeader, a.k);
+    a.err = check_item(a.it, a.c.size);
+    return a;
+}
+
+// One lane per item.  The record of item i goes to out[i], the track's contig of it to contig_of[i] (-1 with a defect),
+// its class (a bedGraph line) to cls[i].
 __global__ __launch_bounds__(256) void k_bw_items(const uint8_t *__restrict__ data, const uint64_t *__restrict__ off, const uint32_t *__restrict__ first,
                                                   int64_t nblocks, int64_t nitems, const ChromOfId *__restrict__ ids, pctrack::LineRec *__restrict__ out,
                                                   int32_t *__restrict__ contig_of, uint8_t *__restrict__ cls, BwCounters *__restrict__ cnt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nitems) return;
-    // (blocks without items share their successor's sum: the last block whose sum is <= i is the one that holds item i)
-    const int b = pctrack::last_at_or_below((int)nblocks, i, [first](int k) { return (int64_t)first[k]; });
-    const uint8_t *p = data + off[b];
-    const Section s = section_header(p);
-    const ChromOfId c = ids[s.chrom_id];
-    const uint32_t k = (uint32_t)(i - (int64_t)first[b]);
-    const Item it = section_item(s, p + kSectionHeader, k);
-    const int err = check_item(it, c.size);
+    const ItemAt a = item_at(data, off, first, nblocks, i, ids);
     pctrack::LineRec r;
-    r.start = it.start; r.stop = it.stop; r.value = it.value;
+    r.start = a.it.start; r.stop = a.it.stop; r.value = a.it.value;
     out[i] = r;
     cls[i] = (uint8_t)pctrack::kBed;
-    contig_of[i] = err == kBwOk ? c.contig : -1;
-    if (err != kBwOk) atomicMin(&cnt->first_err, item_defect(b, k, err));
+    contig_of[i] = a.err == kBwOk ? a.c.contig : -1;
+    if (a.err != kBwOk) atomicMin(&cnt->first_err, item_defect(a.b, a.k, a.err));
 }
 
 // k_track_gather that accumulates: out = out + cell for the positions an item covers inside its track's extent (the

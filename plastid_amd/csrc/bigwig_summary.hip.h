@@ -1,8 +1,10 @@
 // Binned summaries of a bigWig file on the GPU, host side (revision 23): pc_bigwig_summary_* of include/plastid_counts.h.
 // A handle holds the file (mapped, or a copy of the image), its header, chromosome tree and zoom headers, and one TABLE
 // per zoom level plus one for the items, loaded into HBM at the first query that selects it (load_zoom / load_items: the
-// host walks the R-tree, the blocks go up as they are through the upload and the zlib inflate of the import, the records
-// are gathered into file order, k_bbi_index checks the order and gives the contigs' ranges).  A query groups its rows by
+// host walks the R-tree, the blocks go up as they are through the import's bigwig_load_blocks, their statuses come to
+// the host and the first failed block is reported here (summary_load_blocks: a zoom level has no section pass that would
+// find it), the items' sections go through the import's bigwig_sections, the records are gathered into file order by
+// this file's kernels, k_bbi_index checks the order and gives the contigs' ranges).  A query groups its rows by
 // table (bigwig_summary_host.h: choose_level) and launches k_bbi_summarize once per table in use.
 // Part of the one translation unit of plastid_counts.hip (behind bigwig_decoder.hip.h, whose helpers it uses).
 #include <memory>
@@ -46,60 +48,34 @@ struct SummaryLoad {
     BamDecode d;
     hipStream_t st;
     LapEvents<4> ev;                   // start | uploaded | inflated + checked | records in order, indexed
-    std::vector<uint64_t> off;
-    std::vector<uint32_t> len, status;
-    DevBuf<uint8_t> d_inflated, d_tmp;
-    DevBuf<uint32_t> d_status, d_len, d_count, d_first, d_flag_runs;
-    DevBuf<uint64_t> d_off;
+    BigWigBlocks k;
+    BigWigSections sec;
+    std::vector<uint32_t> words;       // the blocks' statuses, then their lengths
+    DevBuf<uint8_t> d_tmp;
+    DevBuf<uint32_t> d_first, d_flag_runs;
     DevBuf<int64_t> d_lohi;
-    DevBuf<bw::ChromOfId> d_ids;
-    DevBuf<bw::BwCounters> d_cnt;
     explicit SummaryLoad(pc_bigwig_summary *s_) : s(s_), d{s_->e, s_->e->stream, s_->path, BamKnobs()}, st(d.st) {}
 };
 
-// The blocks of `f` (a file's, or a level's) to HBM, inflated and Adler-checked when the file is compressed.  Leaves
-// x.off / x.d_off (where block b's bytes stand in d_data) and x.len (their lengths, on the host) and the laps 0 and 1.
-int summary_upload_and_inflate(SummaryLoad &x, const bw::BigWig &f, const char *what, const uint8_t *&d_data) {
+// The blocks of `f` (a file's, or a level's) to HBM (bigwig_load_blocks: the laps 0 and 1; no blocks: empty laps), their
+// statuses and lengths to the host (x.words); the first block whose stream failed ends the load.
+int summary_load_blocks(SummaryLoad &x, const bw::BigWig &f, const char *what) {
     pc_bigwig_summary *s = x.s;
-    hipStream_t st = x.st;
-    const int64_t nb = (int64_t)f.blocks.size(), bytes = (int64_t)(f.data_hi - f.data_lo);
-    {
-        Upload u;
-        Drain drain{s->e, true};
-        PC_TRY(x.d.d_stream.reserve((size_t)bytes + 64));
-        HIP_TRY(hipEventRecord(x.ev[0], st));
-        PC_TRY(sam_upload(x.d, s->image + f.data_lo, bytes, nullptr, u));
-        HIP_TRY(hipStreamSynchronize(st));   // (the ring's halves and its events are the engine's: the next user finds them idle)
-        drain.armed = false;
+    const int64_t nb = (int64_t)f.blocks.size();
+    if (nb == 0) {
+        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventRecord(x.ev[k], x.st));
+        return PC_OK;
     }
-    HIP_TRY(hipEventRecord(x.ev[1], st));
-    s->bytes_uploaded += bytes;
-    x.off.resize((size_t)nb); x.len.resize((size_t)nb);
-    if (f.compressed()) {
-        const std::vector<pcbam::Member> ms = zlib_members(f);
-        for (int64_t b = 0; b < nb; ++b) x.off[(size_t)b] = ms[(size_t)b].uoff;
-        int rc = PC_OK;
-        room(rc, x.d_inflated, (size_t)nb * (size_t)f.slot_bytes() + 64); room(rc, x.d_status, 2 * (size_t)nb); room(rc, x.d.d_members, (size_t)nb);
-        if (rc != PC_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(x.d.d_members.p, ms.data(), ms.size() * sizeof(pcbam::Member), hipMemcpyHostToDevice, st));
-        PC_TRY(queue_zlib_inflate(st, x.d.d_stream.p, x.d.d_members.p, (int)nb, x.d_inflated.p, x.d_status.p));
-        x.status.resize(2 * (size_t)nb);
-        HIP_TRY(hipMemcpyAsync(x.status.data(), x.d_status.p, 2 * (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));   // (ms goes out of scope)
-        for (int64_t b = 0; b < nb; ++b) {
-            const uint32_t stt = x.status[(size_t)b];
-            if (stt != 0u)
-                return fail(PC_ERR_ARG, "%s: bigWig: %sblock %lld: %s", s->path.c_str(), what, (long long)b, bw::defect_text(stt == (uint32_t)pcbam::kInfCrc ? bw::kBwAdler : bw::kBwDeflate));
-            x.len[(size_t)b] = x.status[(size_t)(nb + b)];
-            s->bytes_inflated += x.len[(size_t)b];
-        }
-        d_data = x.d_inflated.p;
-    } else {
-        for (int64_t b = 0; b < nb; ++b) { x.off[(size_t)b] = f.blocks[(size_t)b].off - f.data_lo; x.len[(size_t)b] = (uint32_t)f.blocks[(size_t)b].size; }
-        d_data = x.d.d_stream.p;
+    PC_TRY(bigwig_load_blocks(x.d, s->image, f, x.ev[0], x.ev[1], x.ev[2], x.k));
+    s->bytes_uploaded += (int64_t)(f.data_hi - f.data_lo);
+    PC_TRY(bigwig_block_words(x.st, x.k, x.words));
+    if (!f.compressed()) return PC_OK;
+    for (int64_t b = 0; b < nb; ++b) {
+        const uint32_t stt = x.words[(size_t)b];
+        if (stt != 0u)
+            return fail(PC_ERR_ARG, "%s: bigWig: %sblock %lld: %s", s->path.c_str(), what, (long long)b, bw::defect_text(stt == (uint32_t)pcbam::kInfCrc ? bw::kBwAdler : bw::kBwDeflate));
+        s->bytes_inflated += x.words[(size_t)(nb + b)];
     }
-    PC_TRY(x.d_off.upload(x.off, st));
-    HIP_TRY(hipEventRecord(x.ev[2], st));
     return PC_OK;
 }
 
@@ -139,25 +115,21 @@ int summary_load_zoom(SummaryLoad &x, int level, pc_bigwig_summary::Table &t) {
     const std::string lvl = "zoom level " + std::to_string(level) + ": ";
     const int64_t nb = (int64_t)blocks.blocks.size();
     int64_t n = 0;
-    if (nb > 0) {
-        const uint8_t *d_data = nullptr;
-        PC_TRY(summary_upload_and_inflate(x, blocks, lvl.c_str(), d_data));
-        std::vector<uint32_t> first((size_t)nb + 1, 0u);
-        for (int64_t b = 0; b < nb; ++b) {
-            if (x.len[(size_t)b] % pcbww::kZoomRecordBytes != 0u) return fail(PC_ERR_ARG, "%s: bigWig: %sblock %lld: not a whole number of 32-byte records", s->path.c_str(), lvl.c_str(), (long long)b);
-            n += x.len[(size_t)b] / pcbww::kZoomRecordBytes;
-            if (n >= ((int64_t)1 << 31)) return fail(PC_ERR_ARG, "%s: bigWig: %smore than 2^31 - 1 records", s->path.c_str(), lvl.c_str());
-            first[(size_t)b + 1] = (uint32_t)n;
-        }
-        if (n > 0) {
-            PC_TRY(x.d_first.upload(first, st));
-            PC_TRY(t.zoom.reserve((size_t)n));
-            hipLaunchKernelGGL(ws::k_bbi_zoom_records, dim3(grid256(n)), dim3(256), 0, st, d_data, x.d_off.p, x.d_first.p, nb, n, t.zoom.p);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(st));   // (first goes out of scope)
-        }
-    } else {
-        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventRecord(x.ev[k], st));
+    PC_TRY(summary_load_blocks(x, blocks, lvl.c_str()));
+    std::vector<uint32_t> first((size_t)nb + 1, 0u);
+    for (int64_t b = 0; b < nb; ++b) {
+        const uint32_t len = x.words[(size_t)(nb + b)];
+        if (len % pcbww::kZoomRecordBytes != 0u) return fail(PC_ERR_ARG, "%s: bigWig: %sblock %lld: not a whole number of 32-byte records", s->path.c_str(), lvl.c_str(), (long long)b);
+        n += len / pcbww::kZoomRecordBytes;
+        if (n >= ((int64_t)1 << 31)) return fail(PC_ERR_ARG, "%s: bigWig: %smore than 2^31 - 1 records", s->path.c_str(), lvl.c_str());
+        first[(size_t)b + 1] = (uint32_t)n;
+    }
+    if (n > 0) {
+        PC_TRY(x.d_first.upload(first, st));
+        PC_TRY(t.zoom.reserve((size_t)n));
+        hipLaunchKernelGGL(ws::k_bbi_zoom_records, dim3(grid256(n)), dim3(256), 0, st, x.k.data, x.k.d_off.p, x.d_first.p, nb, n, t.zoom.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));   // (first goes out of scope)
     }
     if (n != (int64_t)s->levels[(size_t)level].records)
         return fail(PC_ERR_ARG, "%s: bigWig: %sthe blocks hold %lld records, the level's count says %u", s->path.c_str(), lvl.c_str(), (long long)n, s->levels[(size_t)level].records);
@@ -171,43 +143,22 @@ int summary_load_items(SummaryLoad &x, pc_bigwig_summary::Table &t) {
     hipStream_t st = x.st;
     const bw::BigWig &f = s->f;
     const int64_t nb = (int64_t)f.blocks.size();
-    int64_t n = 0;
+    BigWigSections &sec = x.sec;
+    PC_TRY(summary_load_blocks(x, f, ""));
     if (nb > 0) {
-        const uint8_t *d_data = nullptr;
-        PC_TRY(summary_upload_and_inflate(x, f, "", d_data));
-        int rc = PC_OK;
-        room(rc, x.d_count, (size_t)nb + 1); room(rc, x.d_first, (size_t)nb + 1); room(rc, x.d_cnt, 1);
-        if (rc != PC_OK) return rc;
-        PC_TRY(x.d_len.upload(x.len, st));
-        PC_TRY(x.d_ids.upload(f.of_id, st));
-        bw::BwCounters cnt = {bw::kNoDefect, {0ull, 0ull, 0ull}, 0ull};
-        HIP_TRY(hipMemcpyAsync(x.d_cnt.p, &cnt, sizeof(cnt), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(x.d_count.p + nb, 0, 4, st));
-        // (the statuses were read on the host: every block inflated)
-        hipLaunchKernelGGL(bw::k_bw_sections, dim3(grid256(nb)), dim3(256), 0, st, d_data, x.d_off.p, x.d_len.p, (const uint32_t *)nullptr, nb, x.d_ids.p, (uint32_t)f.of_id.size(),
-                           x.d_count.p, x.d_cnt.p);
-        HIP_TRY(hipGetLastError());
-        std::vector<uint32_t> counts((size_t)nb);
-        HIP_TRY(hipMemcpyAsync(counts.data(), x.d_count.p, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(&cnt, x.d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (cnt.first_err != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(s->path.c_str(), cnt.first_err).c_str());
-        for (uint32_t v : counts) n += v;
-        if (n >= ((int64_t)1 << 31)) return fail(PC_ERR_ARG, "%s: bigWig: more than 2^31 - 1 items", s->path.c_str());
-        if (n > 0) {
-            PC_TRY(cub_run(x.d_tmp, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, x.d_count.p, x.d_first.p, (int)nb + 1, st); }));
-            PC_TRY(t.items.reserve((size_t)n));
-            hipLaunchKernelGGL(ws::k_bbi_items, dim3(grid256(n)), dim3(256), 0, st, d_data, x.d_off.p, x.d_first.p, nb, n, x.d_ids.p, t.items.p, x.d_cnt.p);
+        PC_TRY(bigwig_sections(st, x.d_tmp, s->path, x.k, nb, f.of_id, sec));
+        if (sec.cnt.first_err != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(s->path.c_str(), sec.cnt.first_err).c_str());
+        if (sec.nitems > 0) {
+            PC_TRY(t.items.reserve((size_t)sec.nitems));
+            hipLaunchKernelGGL(ws::k_bbi_items, dim3(grid256(sec.nitems)), dim3(256), 0, st, x.k.data, x.k.d_off.p, sec.d_first.p, nb, sec.nitems, sec.d_ids.p, t.items.p, sec.d_cnt.p);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(&cnt, x.d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(&sec.cnt, sec.d_cnt.p, sizeof(sec.cnt), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
-            if (cnt.first_err != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(s->path.c_str(), cnt.first_err).c_str());
+            if (sec.cnt.first_err != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(s->path.c_str(), sec.cnt.first_err).c_str());
         }
-    } else {
-        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventRecord(x.ev[k], st));
     }
-    PC_TRY(summary_index(x, t.items.p, n, t.ranges));
-    t.n = n;
+    PC_TRY(summary_index(x, t.items.p, sec.nitems, t.ranges));
+    t.n = sec.nitems;
     return PC_OK;
 }
 
@@ -230,7 +181,17 @@ int summary_load(pc_bigwig_summary *s, int table) {
     return PC_OK;
 }
 
-int summary_open_impl(pc_engine *e, pc_bigwig_summary *s, pc_bigwig_summary **out) {
+// The handle over a copy of the image, named `path`, or (size < 0) over the file at `path`, mapped.
+int summary_open_impl(pc_engine *e, const char *path, const void *image, int64_t size, pc_bigwig_summary **out) {
+    std::unique_ptr<pc_bigwig_summary> s(new pc_bigwig_summary());
+    s->path = path;
+    if (size >= 0) {
+        s->own.assign((const uint8_t *)image, (const uint8_t *)image + size);
+        s->image = s->own.data(); s->size = (uint64_t)size;
+    } else {
+        PC_TRY(s->mf.open(path, 0, 0));
+        s->image = (const uint8_t *)s->mf.p; s->size = (uint64_t)s->mf.size;
+    }
     const unsigned long long d = bw::parse(s->image, s->size, s->f);
     if (d != bw::kNoDefect) return fail(PC_ERR_ARG, "%s", bw::defect_message(s->path.c_str(), d).c_str());
     const std::string bad = pcbww::zoom_headers(s->image, s->size, s->levels);
@@ -241,8 +202,8 @@ int summary_open_impl(pc_engine *e, pc_bigwig_summary *s, pc_bigwig_summary **ou
         s->tables.back()->zoom.pool = &e->pool; s->tables.back()->items.pool = &e->pool;
     }
     s->e = e;
-    e->summaries.push_back(s);
-    *out = s;
+    e->summaries.push_back(s.get());
+    *out = s.release();
     return PC_OK;
 }
 
@@ -252,24 +213,12 @@ extern "C" {
 
 int pc_bigwig_summary_open(pc_engine *e, const void *image, int64_t size, const char *name, pc_bigwig_summary **out) {
     if (!e || !out || size < 0 || (size > 0 && !image)) return fail(PC_ERR_ARG, "pc_bigwig_summary_open: bad arguments");
-    std::unique_ptr<pc_bigwig_summary> s(new pc_bigwig_summary());
-    s->path = name ? name : "<memory>";
-    s->own.assign((const uint8_t *)image, (const uint8_t *)image + size);
-    s->image = s->own.data(); s->size = (uint64_t)size;
-    PC_TRY(summary_open_impl(e, s.get(), out));
-    s.release();
-    return PC_OK;
+    return summary_open_impl(e, name ? name : "<memory>", image, size, out);
 }
 
 int pc_bigwig_summary_open_path(pc_engine *e, const char *path, pc_bigwig_summary **out) {
     if (!e || !out || !path) return fail(PC_ERR_ARG, "pc_bigwig_summary_open_path: bad arguments");
-    std::unique_ptr<pc_bigwig_summary> s(new pc_bigwig_summary());
-    s->path = path;
-    PC_TRY(s->mf.open(path, 0, 0));
-    s->image = (const uint8_t *)s->mf.p; s->size = (uint64_t)s->mf.size;
-    PC_TRY(summary_open_impl(e, s.get(), out));
-    s.release();
-    return PC_OK;
+    return summary_open_impl(e, path, nullptr, -1, out);
 }
 
 int pc_bigwig_summary_close(pc_bigwig_summary *s) {

@@ -3,8 +3,8 @@
 // file's 32-byte record as it is) or the items of the file (ItemRec, 16 bytes), in file order, in HBM:
 //   k_bbi_zoom_records  one lane per record: its block by bisection over the exclusive sum of the blocks' record counts,
 //                       the 32 bytes read field by field (a stored block lies at any offset of the file) into one ZoomRec;
-//   k_bbi_items         one lane per item: block by bisection as k_bw_items, the item decoded and checked by the host
-//                       reader's functions (section_item, check_item) -> ItemRec, the lowest defect;
+//   k_bbi_items         one lane per item: located, decoded and checked as k_bw_items' (pcbw::item_at) -> ItemRec, the
+//                       lowest defect;
 //   k_bbi_index         one lane per record: index_record -> the table's order flag, and per chromId the number of runs
 //                       and the bounds of (the last of) them;
 //   k_bbi_summarize     ONE LANE PER (query, bin), a zoom and an items instantiation: the bin's edges, a binary search for
@@ -33,22 +33,17 @@ __global__ __launch_bounds__(256) void k_bbi_zoom_records(const uint8_t *__restr
     out[i] = r;
 }
 
-// As k_bw_items, into ItemRec.  ids: by chromId, contig >= 0 for an id of the tree.
+// As k_bw_items (pcbw::item_at), into ItemRec.  ids: by chromId, contig >= 0 for an id of the tree.
 __global__ __launch_bounds__(256) void k_bbi_items(const uint8_t *__restrict__ data, const uint64_t *__restrict__ off, const uint32_t *__restrict__ first,
                                                    int64_t nblocks, int64_t nitems, const pcbw::ChromOfId *__restrict__ ids, ItemRec *__restrict__ out,
                                                    pcbw::BwCounters *__restrict__ cnt) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= nitems) return;
-    const int b = pctrack::last_at_or_below((int)nblocks, i, [first](int k) { return (int64_t)first[k]; });
-    const uint8_t *p = data + off[b];
-    const pcbw::Section s = pcbw::section_header(p);
-    const uint32_t k = (uint32_t)(i - (int64_t)first[b]);
-    const pcbw::Item it = pcbw::section_item(s, p + pcbw::kSectionHeader, k);
-    const int err = pcbw::check_item(it, ids[s.chrom_id].size);
+    const pcbw::ItemAt a = pcbw::item_at(data, off, first, nblocks, i, ids);
     ItemRec r;
-    r.chrom = s.chrom_id; r.start = (uint32_t)it.start; r.end = (uint32_t)it.stop; r.value = (float)it.value;   // (the float32 of the file, widened and back)
+    r.chrom = a.s.chrom_id; r.start = (uint32_t)a.it.start; r.end = (uint32_t)a.it.stop; r.value = (float)a.it.value;   // (the float32 of the file, widened and back)
     out[i] = r;
-    if (err != pcbw::kBwOk) atomicMin(&cnt->first_err, pcbw::item_defect(b, k, err));
+    if (a.err != pcbw::kBwOk) atomicMin(&cnt->first_err, pcbw::item_defect(a.b, a.k, a.err));
 }
 
 // flag[0]: the table is not in coordinate order.  runs / lo / hi: by chromId (nids of each), zeroed by the caller.

@@ -3,13 +3,15 @@
 //   1  item heads over the cells of the strand's contigs in sorted order, their exclusive sum, the items in front of
 //      every contig (one read-back of a word per contig: the host cuts the sections from it);
 //   2  the items into their columns and into the raw sections, the section headers, the total summary;
-//   3  k_zlib_deflate over the raw sections (compress), 4 the sizes, their exclusive sum, the compaction;
+//   3  k_zlib_deflate over the raw sections (compress), 4 the sizes, their exclusive sum, the compaction: the encode
+//      stage of deflate_encoder.hip.h (zlib_encode_stage), which the zoom levels' blocks go through as well -- a
+//      BwxBlocks each, the raw blocks, their bounds and the stage's buffers;
 //   Z  (zoom != 0, the file has items) the zoom levels from the item columns of phase 2 (bigwig_zoom_kernels.hip.h): the
 //      window grid of all candidate levels (bigwig_write_host.h: zoom_plan), level 0, the levels above it, the flags'
 //      exclusive sum; the records in front of every (level, contig) come back (one word each: the host ends the pyramid
-//      and cuts the blocks by them); the records into raw blocks, the block table, k_zlib_deflate and the compaction
-//      over the blocks (compress);
-//   5  the section table (bounds and sizes) and the zoom levels' block tables come back, the host lays out offsets and
+//      and cuts the blocks by them); the records into raw blocks, the block table, the encode stage over the blocks
+//      (compress);
+//   5  the section table (bounds and sizes) and the zoom levels' block table come back (bwx_read_table), the host lays out offsets and
 //      all trees (bigwig_write_host.h: the container code of the host writer), and the blocks cross PCIe once, straight
 //      into their place in the image -- through the transfer ring when they are large.
 // What is refused is refused before anything is built, and nothing is left behind.
@@ -20,6 +22,18 @@
 namespace {
 
 namespace ww = pcbww;
+
+// One set of blocks of the file -- the data sections, or the blocks of all zoom levels: the raw blocks back to back,
+// every block's bounds, the encode stage over them (compress; its d_in is filled with the raw blocks' places), and the
+// table as bwx_read_table brings it back.
+struct BwxBlocks {
+    DevBuf<uint8_t> d_raw;
+    DevBuf<uint32_t> d_start, d_end;
+    ZlibEncodeStage z;
+    std::vector<uint32_t> start, end, fell_back;
+    std::vector<unsigned long long> sizes;
+    const uint8_t *bytes(bool compress) const { return compress ? z.d_out.p : d_raw.p; }   // the blocks as the file holds them
+};
 
 struct BigWigExport {
     pc_track *t;
@@ -37,14 +51,13 @@ struct BigWigExport {
     std::vector<ww::DevSection> sections;
     ww::DevSummary total = {0ull, ww::kNoKeyMin, ww::kNoKeyMax, 0.0, 0.0};
     DevBuf<tk::ExRange> d_ranges;
-    DevBuf<uint32_t> d_flags, d_idx, d_istart, d_iend, d_sec_start, d_sec_end, d_stored;
+    DevBuf<uint32_t> d_flags, d_idx, d_istart, d_iend;
     DevBuf<float> d_ival;
-    DevBuf<int64_t> d_sec_first, d_in;     // d_in: the offsets, then the lengths of the raw sections
+    DevBuf<int64_t> d_sec_first;
     DevBuf<ww::DevSection> d_sections;
     DevBuf<ww::DevSummary> d_summary;      // the total, then the partials
-    DevBuf<uint8_t> d_raw, d_slots, d_blocks, d_tmp;
-    DevBuf<uint64_t> d_slot_off;
-    DevBuf<unsigned long long> d_res;      // the sizes, then the offsets of the streams
+    DevBuf<uint8_t> d_tmp;
+    BwxBlocks sec;                         // the data sections
     // the zoom levels
     int64_t zoom = 0;                      // 0: none, -1: the automatic first reduction, else the first reduction
     LapEvents<5> zev;                      // start | level 0 | levels above | records + block table | encoded + compacted
@@ -54,13 +67,11 @@ struct BigWigExport {
     std::vector<int64_t> zrec;             // the records in front of every (level, contig)
     std::vector<ww::ZoomBlock> zblk;       // the blocks of the written levels, level by level
     std::vector<int64_t> zblk_first;       // the blocks in front of every written level, and their number
-    DevBuf<int64_t> d_zrows, d_zitem_first, d_zrec, d_zin;
-    DevBuf<uint32_t> d_zsizes, d_zvalid, d_zkmin, d_zkmax, d_zflags, d_zidx, d_zblk_start, d_zblk_end, d_zstored;
+    DevBuf<int64_t> d_zrows, d_zitem_first, d_zrec;
+    DevBuf<uint32_t> d_zsizes, d_zvalid, d_zkmin, d_zkmax, d_zflags, d_zidx;
     DevBuf<double> d_zsum, d_zsumsq;
     DevBuf<ww::ZoomBlock> d_zblk;
-    DevBuf<uint8_t> d_zraw, d_zslots, d_zblocks;
-    DevBuf<uint64_t> d_zslot_off;
-    DevBuf<unsigned long long> d_zres;
+    BwxBlocks zb;                          // the blocks of the written levels
 };
 
 // Phase 1: heads, exclusive sum, items in front of every contig; the host cuts the sections.
@@ -100,16 +111,16 @@ int bwx_fill_sections(BigWigExport &c) {
     hipStream_t st = c.st;
     const int64_t ntile = (c.N + ww::kSummaryTile - 1) / ww::kSummaryTile;
     int rc = PC_OK;
-    room(rc, c.d_istart, (size_t)c.N); room(rc, c.d_iend, (size_t)c.N); room(rc, c.d_ival, (size_t)c.N); room(rc, c.d_raw, (size_t)c.raw_bytes + 64);
-    room(rc, c.d_sec_start, (size_t)c.nsec); room(rc, c.d_sec_end, (size_t)c.nsec); room(rc, c.d_in, 2 * (size_t)c.nsec); room(rc, c.d_summary, 1 + (size_t)ntile);
+    room(rc, c.d_istart, (size_t)c.N); room(rc, c.d_iend, (size_t)c.N); room(rc, c.d_ival, (size_t)c.N); room(rc, c.sec.d_raw, (size_t)c.raw_bytes + 64);
+    room(rc, c.sec.d_start, (size_t)c.nsec); room(rc, c.sec.d_end, (size_t)c.nsec); room(rc, c.sec.z.d_in, 2 * (size_t)c.nsec); room(rc, c.d_summary, 1 + (size_t)ntile);
     if (rc != PC_OK) return rc;
     PC_TRY(c.d_sec_first.upload(c.sec_first, st)); PC_TRY(c.d_sections.upload(c.sections, st));
     HIP_TRY(hipMemcpyAsync(c.d_summary.p, &c.total, sizeof(c.total), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(ww::k_bww_items, dim3((unsigned)((c.E + tk::kExportTile - 1) / tk::kExportTile)), dim3(256), 0, st, c.d_ranges.p, c.K, c.E, c.t->cells.p, c.d_flags.p,
-                       c.d_idx.p, c.d_sec_first.p, c.items_per_slot, c.d_istart.p, c.d_iend.p, c.d_ival.p, c.d_raw.p);
+                       c.d_idx.p, c.d_sec_first.p, c.items_per_slot, c.d_istart.p, c.d_iend.p, c.d_ival.p, c.sec.d_raw.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ww::k_bww_headers, dim3(grid256(c.nsec)), dim3(256), 0, st, c.d_sections.p, c.nsec, c.d_istart.p, c.d_iend.p, c.d_raw.p, c.d_sec_start.p, c.d_sec_end.p,
-                       c.d_in.p, c.d_in.p + c.nsec);
+    hipLaunchKernelGGL(ww::k_bww_headers, dim3(grid256(c.nsec)), dim3(256), 0, st, c.d_sections.p, c.nsec, c.d_istart.p, c.d_iend.p, c.sec.d_raw.p, c.sec.d_start.p, c.sec.d_end.p,
+                       c.sec.z.d_in.p, c.sec.z.d_in.p + c.nsec);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(ww::k_bww_summary, dim3((unsigned)ntile), dim3(256), 0, st, c.d_istart.p, c.d_iend.p, c.d_ival.p, c.N, c.d_summary.p + 1, c.d_summary.p);
     HIP_TRY(hipGetLastError());
@@ -117,23 +128,6 @@ int bwx_fill_sections(BigWigExport &c) {
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(&c.total, c.d_summary.p, sizeof(c.total), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipEventRecord(c.ev[2], st));
-    return PC_OK;
-}
-
-// Phases 3, 4: every raw section through the encoder, the streams compacted; d_blocks: the blocks of the file back to back.
-int bwx_deflate(BigWigExport &c) {
-    hipStream_t st = c.st;
-    std::vector<uint64_t> slot_off((size_t)c.nsec);
-    uint64_t slots = 0;
-    for (int64_t s = 0; s < c.nsec; ++s) { slot_off[(size_t)s] = slots; slots += 24u + 12u * (uint64_t)c.sections[(size_t)s].count + pcdeflate::kSlotPad; }
-    int rc = PC_OK;
-    room(rc, c.d_slots, (size_t)slots + 64); room(rc, c.d_blocks, (size_t)(c.raw_bytes + (int64_t)pcdeflate::kStreamOverhead * c.nsec) + 64);
-    room(rc, c.d_res, 2 * (size_t)c.nsec); room(rc, c.d_stored, (size_t)c.nsec);
-    if (rc != PC_OK) return rc;
-    PC_TRY(c.d_slot_off.upload(slot_off, st));
-    PC_TRY(queue_zlib_deflate(st, c.d_raw.p, c.d_in.p, c.d_in.p + c.nsec, c.d_slot_off.p, c.nsec, c.d_slots.p, c.d_res.p, c.d_res.p + c.nsec, c.d_stored.p, c.d_tmp,
-                              c.d_blocks.p, (uint32_t)c.compress, c.ev[3]));
-    HIP_TRY(hipStreamSynchronize(st));   // (slot_off goes out of scope)
     return PC_OK;
 }
 
@@ -181,66 +175,54 @@ int bwx_zoom(BigWigExport &c) {
     }
     c.znblk = (int64_t)c.zblk.size();
     c.zblk_first.push_back(c.znblk);
-    room(rc, c.d_zraw, (size_t)c.zrecords * ww::kZoomRecordBytes + 64); room(rc, c.d_zblk_start, (size_t)c.znblk); room(rc, c.d_zblk_end, (size_t)c.znblk);
-    room(rc, c.d_zin, 2 * (size_t)c.znblk);
+    room(rc, c.zb.d_raw, (size_t)c.zrecords * ww::kZoomRecordBytes + 64); room(rc, c.zb.d_start, (size_t)c.znblk); room(rc, c.zb.d_end, (size_t)c.znblk);
+    room(rc, c.zb.z.d_in, 2 * (size_t)c.znblk);
     if (rc != PC_OK) return rc;
     PC_TRY(c.d_zblk.upload(c.zblk, st));
     hipLaunchKernelGGL(ww::k_bwz_records, dim3(grid256(g.level_off[c.zlevels])), dim3(256), 0, st, g, g.level_off[c.zlevels], c.d_zrows.p, c.d_zsizes.p, col, c.d_zflags.p,
-                       c.d_zidx.p, c.d_zraw.p);
+                       c.d_zidx.p, c.zb.d_raw.p);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(ww::k_bwz_blocks, dim3(grid256(c.znblk)), dim3(256), 0, st, c.d_zblk.p, c.znblk, c.d_zraw.p, c.d_zblk_start.p, c.d_zblk_end.p, c.d_zin.p,
-                       c.d_zin.p + c.znblk);
+    hipLaunchKernelGGL(ww::k_bwz_blocks, dim3(grid256(c.znblk)), dim3(256), 0, st, c.d_zblk.p, c.znblk, c.zb.d_raw.p, c.zb.d_start.p, c.zb.d_end.p, c.zb.z.d_in.p,
+                       c.zb.z.d_in.p + c.znblk);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(c.zev[3], st));
-    if (c.compress) {
-        std::vector<uint64_t> slot_off((size_t)c.znblk);
-        uint64_t slots = 0;
-        for (int64_t b = 0; b < c.znblk; ++b) { slot_off[(size_t)b] = slots; slots += (uint64_t)ww::kZoomRecordBytes * c.zblk[(size_t)b].count + pcdeflate::kSlotPad; }
-        room(rc, c.d_zslots, (size_t)slots + 64); room(rc, c.d_zblocks, (size_t)(c.zrecords * (int64_t)ww::kZoomRecordBytes + (int64_t)pcdeflate::kStreamOverhead * c.znblk) + 64);
-        room(rc, c.d_zres, 2 * (size_t)c.znblk); room(rc, c.d_zstored, (size_t)c.znblk);
-        if (rc != PC_OK) return rc;
-        PC_TRY(c.d_zslot_off.upload(slot_off, st));
-        PC_TRY(queue_zlib_deflate(st, c.d_zraw.p, c.d_zin.p, c.d_zin.p + c.znblk, c.d_zslot_off.p, c.znblk, c.d_zslots.p, c.d_zres.p, c.d_zres.p + c.znblk, c.d_zstored.p,
-                                  c.d_tmp, c.d_zblocks.p, (uint32_t)c.compress));
-        HIP_TRY(hipEventRecord(c.zev[4], st));
-        HIP_TRY(hipStreamSynchronize(st));   // (slot_off goes out of scope)
-    } else HIP_TRY(hipEventRecord(c.zev[4], st));
+    if (c.compress)
+        PC_TRY(zlib_encode_stage(st, c.zb.d_raw.p, c.znblk, [&c](int64_t b) { return (uint64_t)ww::kZoomRecordBytes * c.zblk[(size_t)b].count; }, (uint32_t)c.compress, c.d_tmp, c.zb.z, nullptr,
+                                 c.zev[4]));
+    else HIP_TRY(hipEventRecord(c.zev[4], st));
     drained.armed = false;                 // (the stream has drained behind the record counts' read-back)
     return PC_OK;
 }
 
-// Phase 5: the section table comes back, the host lays the file out, the blocks land in their place.
+// The table of n blocks comes back: their bounds and (compress) their streams' sizes and, where the caller counts the
+// block types, how far their blocks fell back.  Queued on `st`: the caller waits.
+int bwx_read_table(hipStream_t st, BwxBlocks &b, int64_t n, int compress, bool types) {
+    b.start.resize((size_t)n); b.end.resize((size_t)n); b.sizes.resize((size_t)n); b.fell_back.resize((size_t)n);
+    if (n == 0) return PC_OK;
+    HIP_TRY(hipMemcpyAsync(b.start.data(), b.d_start.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b.end.data(), b.d_end.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    if (compress) HIP_TRY(hipMemcpyAsync(b.sizes.data(), b.z.d_res.p, (size_t)n * 8, hipMemcpyDeviceToHost, st));
+    if (compress && types) HIP_TRY(hipMemcpyAsync(b.fell_back.data(), b.z.d_stored.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    return PC_OK;
+}
+
+// Phase 5: the block tables come back, the host lays the file out, the blocks land in their place.
 int bwx_layout_and_read(BigWigExport &c) {
     hipStream_t st = c.st;
     pc_track *t = c.t;
-    std::vector<uint32_t> sec_start((size_t)c.nsec), sec_end((size_t)c.nsec), stored((size_t)c.nsec);
-    std::vector<unsigned long long> sizes((size_t)c.nsec);
-    std::vector<uint32_t> zstart((size_t)c.znblk), zend((size_t)c.znblk);
-    std::vector<unsigned long long> zsizes((size_t)c.znblk);
     const auto t0 = std::chrono::steady_clock::now();
-    if (c.znblk > 0) {
-        HIP_TRY(hipMemcpyAsync(zstart.data(), c.d_zblk_start.p, (size_t)c.znblk * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(zend.data(), c.d_zblk_end.p, (size_t)c.znblk * 4, hipMemcpyDeviceToHost, st));
-        if (c.compress) HIP_TRY(hipMemcpyAsync(zsizes.data(), c.d_zres.p, (size_t)c.znblk * 8, hipMemcpyDeviceToHost, st));
-    }
-    if (c.nsec > 0) {
-        HIP_TRY(hipMemcpyAsync(sec_start.data(), c.d_sec_start.p, (size_t)c.nsec * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(sec_end.data(), c.d_sec_end.p, (size_t)c.nsec * 4, hipMemcpyDeviceToHost, st));
-        if (c.compress) {
-            HIP_TRY(hipMemcpyAsync(sizes.data(), c.d_res.p, (size_t)c.nsec * 8, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(stored.data(), c.d_stored.p, (size_t)c.nsec * 4, hipMemcpyDeviceToHost, st));
-        }
-        HIP_TRY(hipStreamSynchronize(st));
-    }
+    PC_TRY(bwx_read_table(st, c.zb, c.znblk, c.compress, false));
+    PC_TRY(bwx_read_table(st, c.sec, c.nsec, c.compress, true));
+    if (c.nsec > 0) HIP_TRY(hipStreamSynchronize(st));
     const auto t1 = std::chrono::steady_clock::now();
     std::vector<ww::WSection> sections((size_t)c.nsec);
     uint32_t largest = 0;
     for (int64_t s = 0; s < c.nsec; ++s) {
         const uint32_t raw = 24u + 12u * c.sections[(size_t)s].count;
-        sections[(size_t)s] = {c.sections[(size_t)s].chrom, sec_start[(size_t)s], sec_end[(size_t)s], c.compress ? (uint64_t)sizes[(size_t)s] : (uint64_t)raw};
+        sections[(size_t)s] = {c.sections[(size_t)s].chrom, c.sec.start[(size_t)s], c.sec.end[(size_t)s], c.compress ? (uint64_t)c.sec.sizes[(size_t)s] : (uint64_t)raw};
         largest = std::max(largest, raw);
         if (c.compress) {
-            const uint32_t type = (uint32_t)c.compress - stored[(size_t)s];     // (the encoder reports the steps its block fell back)
+            const uint32_t type = (uint32_t)c.compress - c.sec.fell_back[(size_t)s];     // (the encoder reports the steps its block fell back)
             c.stored += type == pcdeflate::kStored; c.fixed += type == pcdeflate::kFixed; c.dynamic += type == pcdeflate::kDynamic;
         }
     }
@@ -256,7 +238,7 @@ int bwx_layout_and_read(BigWigExport &c) {
         zs[0] = c.zplan.g.r[k]; zs[1] = (int64_t)levels[(size_t)k].records; zs[2] = c.zblk_first[(size_t)k + 1] - c.zblk_first[(size_t)k]; zs[3] = zs[1] * (int64_t)ww::kZoomRecordBytes; zs[4] = 0;
         for (int64_t b = c.zblk_first[(size_t)k]; b < c.zblk_first[(size_t)k + 1]; ++b) {
             const uint32_t raw = ww::kZoomRecordBytes * c.zblk[(size_t)b].count;
-            levels[(size_t)k].blocks.push_back({c.zblk[(size_t)b].chrom, zstart[(size_t)b], zend[(size_t)b], c.compress ? (uint64_t)zsizes[(size_t)b] : (uint64_t)raw});
+            levels[(size_t)k].blocks.push_back({c.zblk[(size_t)b].chrom, c.zb.start[(size_t)b], c.zb.end[(size_t)b], c.compress ? (uint64_t)c.zb.sizes[(size_t)b] : (uint64_t)raw});
             zs[4] += (int64_t)levels[(size_t)k].blocks.back().size;
             largest = std::max(largest, raw);
         }
@@ -275,12 +257,12 @@ int bwx_layout_and_read(BigWigExport &c) {
         at += (size_t)bytes; most = std::max(most, (size_t)bytes);
     };
     host_piece(box.front);
-    block_piece(c.compress ? c.d_blocks.p : c.d_raw.p, box.block_bytes);
+    block_piece(c.sec.bytes(c.compress), box.block_bytes);
     host_piece(box.back);
     uint64_t zat = 0;
     for (int k = 0; k < c.zlevels; ++k) {
         host_piece(box.zoom[(size_t)k].front);
-        block_piece((c.compress ? c.d_zblocks.p : c.d_zraw.p) + zat, box.zoom[(size_t)k].block_bytes);
+        block_piece(c.zb.bytes(c.compress) + zat, box.zoom[(size_t)k].block_bytes);
         zat += box.zoom[(size_t)k].block_bytes;
         host_piece(box.zoom[(size_t)k].back);
     }
@@ -347,7 +329,9 @@ int pc_track_export_bigwig_zoom(pc_track *t, int strand_slot, int64_t items_per_
     DrainOnExit drained{c.st};
     PC_TRY(bwx_items_and_sections(c));
     if (c.N > 0) PC_TRY(bwx_fill_sections(c)); else HIP_TRY(hipEventRecord(c.ev[2], c.st));
-    if (c.N > 0 && c.compress) PC_TRY(bwx_deflate(c)); else HIP_TRY(hipEventRecord(c.ev[3], c.st));
+    if (c.N > 0 && c.compress)             // phases 3, 4: every raw section through the encode stage
+        PC_TRY(zlib_encode_stage(c.st, c.sec.d_raw.p, c.nsec, [&c](int64_t s) { return 24u + 12u * (uint64_t)c.sections[(size_t)s].count; }, (uint32_t)c.compress, c.d_tmp, c.sec.z, c.ev[3]));
+    else HIP_TRY(hipEventRecord(c.ev[3], c.st));
     HIP_TRY(hipEventRecord(c.ev[4], c.st));
     const bool zoomed = c.zoom && c.N > 0;      // (a file without items has no levels)
     if (zoomed) PC_TRY(bwx_zoom(c));

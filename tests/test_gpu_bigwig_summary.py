@@ -5,10 +5,13 @@ CPU by test_bigwig_summary_host.py) bit for bit, and against what Kent's reader 
 (tests/golden/bigwig_summary_fixture.npz), over every fixture file and query: contigs of 1200 to 3000 positions for
 Kent's files, our integer zoom cases compressed and stored.  One batch mixes every table of a file; lanes cross a wave
 and a workgroup; an empty batch; the second call loads nothing; '-' segments; an unknown contig; records out of
-coordinate order; a to_bigwig(zoom=True) file against its cells; compress="dynamic"."""
+coordinate order; damaged zoom levels and data blocks refused with the host readers' words, the table left unloaded;
+a to_bigwig(zoom=True) file against its cells; compress="dynamic"."""
 import collections
+import ctypes
 import io
 import os
+import struct
 import sys
 import warnings
 
@@ -17,9 +20,12 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import plastid_amd as pa  # noqa: E402
+from plastid_amd import _lib  # noqa: E402
 from plastid_amd.engine import Engine  # noqa: E402
 from tests import bigwig_summary_cases as sc  # noqa: E402
+from tests import bigwig_writer as bw  # noqa: E402
 from tests import bigwig_zoom_cases as zc  # noqa: E402
+from tests import test_bigwig_host as host  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ELEMENTS = ("valid", "min", "max", "sum", "sumsq")
@@ -195,6 +201,100 @@ def test_records_out_of_order_raise_and_get_still_answers(readers):
         r.summary_elements_batch([seg], 1)
     assert np.array_equal(r.get(seg), before) and before.shape == (40,)
     assert r.summary_stats()["per_table"]["items"]["queries"] == 0
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# refusals of the device summary: error returns, not faults.  The words are the host readers' for the same file and path.
+
+def zoomed_image(compress):
+    fh = io.BytesIO()
+    pa.write_bigwig(zc.host_array(zc.cases()["grid8_d_plus1"]), fh, "+", compress=compress, zoom=8)
+    return fh.getvalue()
+
+
+def damaged(image, at, fmt, value):
+    b = bytearray(image)
+    b[at:at + struct.calcsize(fmt)] = struct.pack(fmt, value)
+    return bytes(b)
+
+
+def host_words(read, *args):
+    with pytest.raises(ValueError) as e:
+        read(*args)
+    return str(e.value)
+
+
+def test_a_damaged_compressed_zoom_level_is_refused_twice_and_the_items_still_answer(eng, tmp_path):
+    image = zoomed_image(True)
+    headers = zc.zoom_headers(image)
+    reductions = [z[0] for z in pa.bigwig_zoom_info(image)]
+    p = tmp_path / "damaged_zoom.bw"
+    p.write_bytes(damaged(image, headers[0][2] + 4 + 12, "<I", 0x5a5a5a5a))
+    want = host_words(pa.read_bigwig_zoom, str(p), 0)
+    assert want in ("%s: bigWig: zoom level 0: block 0: %s" % (p, w) for w in ("DEFLATE error", "Adler-32 mismatch"))
+    r = pa.BigWigReader(str(p), engine=eng)                     # (the import does not read zoom blocks)
+    try:
+        coarse, fine = pa.GenomicSegment("d_plus1", 0, 25, "+"), pa.GenomicSegment("d_plus1", 0, 24, "+")
+        assert sc.level_of(reductions, 0, 25, 1) == 0 and sc.level_of(reductions, 0, 24, 4) == -1
+        for _ in range(2):                                      # (the table stays unloaded and is tried again)
+            with pytest.raises(ValueError) as e:
+                r.summarize(coarse, 1)
+            assert str(e.value) == want
+        assert r.summary_stats()["per_table"][reductions[0]]["records"] is None
+        assert same_bits(r.summarize(fine, 4), pa.summarize_bigwig(p.read_bytes(), [fine], 4)[0])
+        assert np.array_equal(r.get(coarse), zc.cases()["grid8_d_plus1"].contigs["d_plus1"].cells)
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("what", ["leaf_size_33", "count_5"])
+def test_a_zoom_level_of_a_wrong_shape_is_refused(eng, tmp_path, what):
+    if what == "leaf_size_33":
+        image = zoomed_image(False)
+        h = zc.zoom_headers(image)[0]
+        image = damaged(image, h[3] + 48 + 4 + 24, "<Q", 33)
+        words = "zoom level 0: block 0: not a whole number of 32-byte records"
+    else:
+        image = zoomed_image(True)
+        image = damaged(image, zc.zoom_headers(image)[0][2], "<I", 5)
+        words = "zoom level 0: the blocks hold 4 records, the level's count says 5"
+    p = tmp_path / (what + ".bw")
+    p.write_bytes(image)
+    assert host_words(pa.read_bigwig_zoom, str(p), 0) == "%s: bigWig: %s" % (p, words)
+    r = pa.BigWigReader(str(p), engine=eng)
+    try:
+        with pytest.raises(ValueError) as e:
+            r.summarize(pa.GenomicSegment("d_plus1", 0, 25, "+"), 1)
+        assert str(e.value) == "%s: bigWig: %s" % (p, words)
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("name,words", [("deflate", "block 0: DEFLATE error"), ("adler", "block 1: Adler-32 mismatch")])
+def test_damaged_data_blocks_are_refused_by_the_summary_handle(eng, tmp_path, name, words):
+    L = _lib.load()
+    p = tmp_path / "refused.bw"
+    p.write_bytes(host.refused_image(name))
+    want = host_words(pa.read_bigwig, str(p))
+    assert want == "%s: bigWig: %s" % (p, words)
+    h = ctypes.c_void_p()
+    _lib.check(L.pc_bigwig_summary_open_path(eng._h, os.fsencode(str(p)), ctypes.byref(h)))      # (the container is whole)
+    try:
+        contig, start, end, out = np.zeros(1, np.int32), np.zeros(1, np.int64), np.full(1, 9, np.int64), np.zeros(5, np.float64)
+        with pytest.raises(ValueError) as e:
+            _lib.check(L.pc_bigwig_summary_query(h, 1, contig.ctypes.data, start.ctypes.data, end.ctypes.data, 1, out.ctypes.data))
+        assert str(e.value) == want
+    finally:
+        _lib.check(L.pc_bigwig_summary_close(h))
+    # and the engine goes on working
+    ga = pa.GenomeArray({"chrA": 1000}, strands=("+",), engine=eng)
+    try:
+        good = tmp_path / "good.bw"
+        good.write_bytes(bw.write_bigwig(host.CHROMS, host.GOOD))
+        _lib.check(L.pc_track_add_bigwig_path(ga._h, os.fsencode(str(good)), 0))
+        assert ga.to_host()._chroms["chrB"]["+"][100:108].tolist() == [1.0, 1.0, 0.0, 2.0, 2.0, 0.0, 3.0, 3.0]
+    finally:
+        ga.close()
 
 
 @pytest.mark.parametrize("compress", [True, "dynamic", False])
