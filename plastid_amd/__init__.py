@@ -12,8 +12,10 @@ from .map_factories import (CenterMapFactory, FivePrimeMapFactory, FlagFilterFac
                             StratifiedVariableFivePrimeMapFactory, ThreePrimeMapFactory,
                             VariableFivePrimeMapFactory)
 from .genome_array import BAMGenomeArray, DenseGenomeArray  # noqa: F401
-from .track import (BigWigGenomeArray, BigWigReader, BigWigTable, BigWigZoomTable, GenomeArray, WiggleTable, bigwig_info,  # noqa: F401
-                    bigwig_zoom_info, read_bigwig, read_bigwig_zoom, read_wiggle, summarize_bigwig, summary_elements_bigwig,
-                    write_bigwig)
+from .track import GenomeArray  # noqa: F401
+from .track_text import WiggleTable, read_wiggle  # noqa: F401
+from .bigwig_host import (BigWigTable, BigWigZoomTable, bigwig_info, bigwig_zoom_info, read_bigwig, read_bigwig_zoom,  # noqa: F401
+                          summarize_bigwig, summary_elements_bigwig, write_bigwig)
+from .bigwig import BigWigGenomeArray, BigWigReader  # noqa: F401
 
 __version__ = "0.1.0"

@@ -11,48 +11,9 @@ import os
 
 import numpy as np
 
-from .build import BAM_LIB, build_bam_library
+from ._hostlib import call, load as _load
+from .build import BAM_LIB  # noqa: F401  (the path as built; the library is opened at ``build.BAM_LIB``, read at the first load)
 from .packing import PackedAlignments
-
-_lib = None
-
-
-def _load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(BAM_LIB):
-            build_bam_library()
-        L = ctypes.CDLL(BAM_LIB)
-        vp = ctypes.c_void_p
-        L.pb_last_error.restype = ctypes.c_char_p
-        L.pb_open.restype = vp
-        L.pb_open.argtypes = [ctypes.c_char_p]
-        L.pb_open_sam.restype = vp
-        L.pb_open_sam.argtypes = [ctypes.c_char_p]
-        L.pb_open_indexed.restype = vp
-        L.pb_open_indexed.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
-        L.pb_close.argtypes = [vp]
-        L.pb_load.argtypes = [vp, ctypes.c_int]
-        L.pb_load_regions.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), vp, vp]
-        L.pb_nref.argtypes = [vp]
-        L.pb_ref_name.restype = ctypes.c_char_p
-        L.pb_ref_name.argtypes = [vp, ctypes.c_int]
-        L.pb_ref_length.restype = ctypes.c_int32
-        L.pb_ref_length.argtypes = [vp, ctypes.c_int]
-        L.pb_counts.argtypes = [vp, vp]
-        L.pb_fill.argtypes = [vp] * 8
-        L.pb_wide_count.restype = ctypes.c_int64
-        L.pb_wide_count.argtypes = [vp]
-        L.pb_fill_wide.argtypes = [vp] * 4
-        L.pb_fill_sam.argtypes = [vp] * 4
-        L.pb_fill_nh.argtypes = [vp] * 2
-        L.pb_load_sorted.argtypes = [vp, ctypes.c_int]
-        L.pb_sort_stats.argtypes = [vp, vp]
-        L.pb_file_order.argtypes = [vp, vp]
-        L.pb_resolve_regions.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p)] + [vp] * 9
-        L.pb_resolve_chunks.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), vp, vp, ctypes.c_int64] + [vp] * 8
-        _lib = L
-    return _lib
 
 
 def bam_header(path):
@@ -123,10 +84,7 @@ def _refuse_compressed_sam(path):
 def _pb_open_sam(L, path):
     if not os.path.isfile(path):
         raise IOError("No such file: %r" % (path,))
-    h = L.pb_open_sam(os.fsencode(path))
-    if not h:
-        raise ValueError(L.pb_last_error().decode())   # (compressed, or a malformed header)
-    return h
+    return call(L.pb_open_sam, os.fsencode(path))   # (ValueError: compressed, or a malformed header)
 
 
 def sam_header(path):
@@ -479,10 +437,9 @@ def _index_path(path, index, engine=None):
 
 
 def _pb_open(L, path, index_path):
-    h = L.pb_open(os.fsencode(path)) if index_path is None else L.pb_open_indexed(os.fsencode(path), os.fsencode(index_path))
-    if not h:
-        raise IOError(L.pb_last_error().decode())
-    return h
+    if index_path is None:
+        return call(L.pb_open, os.fsencode(path), exc=IOError)
+    return call(L.pb_open_indexed, os.fsencode(path), os.fsencode(index_path), exc=IOError)
 
 
 def resolve_regions(path, regions, index=None):
@@ -510,10 +467,8 @@ def resolve_regions(path, regions, index=None):
         cap = 8 * n + 64
         while True:
             cb, ce = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
-            rc = L.pb_resolve_chunks(h, n, names, p(starts), p(ends), cap, p(cb), p(ce), ctypes.byref(nch), ctypes.byref(mapped), ctypes.byref(nm),
-                                     p(tid), p(beg), p(end))
-            if rc != 0:
-                raise ValueError(L.pb_last_error().decode())
+            call(L.pb_resolve_chunks, h, n, names, p(starts), p(ends), cap, p(cb), p(ce), ctypes.byref(nch), ctypes.byref(mapped), ctypes.byref(nm),
+                 p(tid), p(beg), p(end))
             if nch.value <= cap:
                 break
             cap = int(nch.value)
@@ -659,17 +614,13 @@ def read_bam(path, threads=0, regions=None, index=None, sort=False, timing=None,
     h = _pb_open_sam(L, path) if _sam else _pb_open(L, path, _index_path(path, index) if regions is not None else None)
     try:
         if regions is None:
-            rc = L.pb_load_sorted(h, int(threads)) if sort else L.pb_load(h, int(threads))
+            call(L.pb_load_sorted if sort else L.pb_load, h, int(threads))
         else:
             regs = _region_tuples(regions)
             names = (ctypes.c_char_p * max(len(regs), 1))(*[os.fsencode(str(c)) for c, _, _ in regs])
             starts = np.array([int(s) for _, s, _ in regs], np.int64)
             ends = np.array([int(e) for _, _, e in regs], np.int64)
-            rc = L.pb_load_regions(h, int(threads), len(regs), names, starts.ctypes.data_as(ctypes.c_void_p),
-                                   ends.ctypes.data_as(ctypes.c_void_p))
-        if rc != 0:
-            msg = L.pb_last_error().decode()
-            raise ValueError(msg)
+            call(L.pb_load_regions, h, int(threads), len(regs), names, starts.ctypes.data_as(ctypes.c_void_p), ends.ctypes.data_as(ctypes.c_void_p))
         counts = np.zeros(4, np.int64)
         L.pb_counts(h, counts.ctypes.data_as(ctypes.c_void_p))
         n, nrun, mapped = int(counts[0]), int(counts[1]), int(counts[2])

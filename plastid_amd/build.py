@@ -32,12 +32,12 @@ def find_hipcc():
 
 
 BAM_SRC = os.path.join(HERE, "csrc", "bam_stager.cpp")
-BAM_HDRS = [os.path.join(HERE, "csrc", f) for f in ("index_shape.h", "bam_host.h", "bigwig_host.h", "bigwig_write_host.h", "bigwig_summary_host.h", "deflate_host.h", "host_util.h", "sam_host.h", "track_host.h")]   # what bam_stager.cpp includes of csrc/
+BAM_HDRS = [f for f in HDRS if os.path.dirname(f) == os.path.dirname(BAM_SRC) and not f.endswith(".hip.h")]   # every host header of csrc/: more than bam_stager.cpp includes, never less
 BAM_LIB = os.path.join(HERE, "libplastid_bam.so")
 
 
 def build_bam_library(force=False, verbose=False):
-    """Compile the native BAM -> packed-array stager (host C++, zlib; no GPU code)."""
+    """Compile the host library: the native BAM -> packed-array stager and the host models (host C++, zlib; no GPU code)."""
     if not force and os.path.exists(BAM_LIB) and os.path.getmtime(BAM_LIB) >= max(os.path.getmtime(f) for f in [BAM_SRC] + BAM_HDRS):
         return BAM_LIB
     cxx = shutil.which("g++") or shutil.which("c++") or find_hipcc()

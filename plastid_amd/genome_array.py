@@ -813,7 +813,7 @@ class BAMGenomeArray(object):
         return plan, offs[:-1]
 
     def _export(self, kind, fh, trackname, strand, window_size, printer, kwargs, batch_elems):
-        from .track import _count_text, _track_line, _write_text
+        from .track_text import _count_text, _track_line, _write_text
         assert strand in self.strands()
         if kind == 0:
             assert window_size > 0
@@ -870,7 +870,8 @@ class BAMGenomeArray(object):
         While it runs it takes 8 bytes of HBM per genome position for the temporary array, beside the counts of a
         batch.  :func:`plastid_amd.track.write_bigwig` writes the same file on the host from count vectors."""
         import io
-        from .track import GenomeArray, _check_bigwig_params, _compress_mode, _zoom_mode
+        from .bigwig_host import _check_bigwig_params, _compress_mode, _zoom_mode
+        from .track import GenomeArray
         assert strand in self.strands()
         _check_bigwig_params(items_per_slot, block_size)
         _compress_mode(compress)             # (a bad value is a ValueError before anything is counted)

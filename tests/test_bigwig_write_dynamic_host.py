@@ -98,7 +98,6 @@ def test_a_bad_compress_value_is_refused():
     # the library's own refusal, under the Python check
     from plastid_amd.bam import _load
     L = _load()
-    write(case, 1024, True)                                   # (binds the argument types)
     for bad in (3, -1):
         assert not L.pb_bigwig_write_open(1024, 256, bad) and b"compress" in L.pb_last_error()
     h = L.pb_bigwig_write_open(1024, 256, 2)

@@ -188,9 +188,6 @@ def raw_call(fn, inputs, *extra):
 def test_mode_1_is_the_old_seam_and_other_modes_are_refused():
     from plastid_amd.bam import _load
     L = _load()
-    vp = ctypes.c_void_p
-    L.pb_deflate_zlib.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp]
-    L.pb_deflate_zlib_mode.argtypes = [vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int]
     inputs = list(INPUTS.values())
     old = raw_call(L.pb_deflate_zlib, inputs)
     assert old[0] == 0 and raw_call(L.pb_deflate_zlib_mode, inputs, 1) == old
