@@ -10,6 +10,8 @@
 #pragma once
 #include <cstdint>
 
+#include "count_host.h"
+
 #if defined(__HIPCC__)
 #define PCDENSE_HD __host__ __device__
 #else
@@ -43,10 +45,11 @@ inline int64_t layout(int ntid, const int64_t *ext, int64_t *cell_off) {
     return at;
 }
 
-// What the decision looks at.  The first block restates the plan conditions of the canonical stream.
+// What the decision looks at.  The first block is what the plan conditions of the canonical stream look at
+// (count_host.h, stream_plan_conditions).
 struct PlanIn {
     int nfiles = 0;
-    bool point_rule = false;     // fiveprime, threeprime or variable
+    int kind = -1;               // the mapping rule (PC_MAP_*): a point rule -- fiveprime, threeprime or variable
     int rows = 1;
     uint32_t modes = 0;          // strand modes of the plan's windows (bit 0 '+', bit 1 '-', bits 2, 3: unstranded)
     bool has_sums = false;       // some slice is summed (out_step 0)
@@ -56,7 +59,7 @@ struct PlanIn {
 };
 
 inline bool plan_conditions(const PlanIn &p) {
-    return !p.forbidden && p.nfiles == 1 && p.point_rule && p.rows == 1 && (p.modes & ~3u) == 0u && p.modes != 0u && !p.has_sums;
+    return !p.forbidden && pccount::stream_plan_conditions(p.nfiles, p.kind, p.rows, p.modes) && !p.has_sums;
 }
 inline bool size_rule(int64_t cells, int64_t stream_entries) { return cells > 0 && cells * kBytesPerCell <= stream_entries * 4; }
 inline bool build_fits(int64_t cells) { return cells * 8 <= kBuildBlockCap; }

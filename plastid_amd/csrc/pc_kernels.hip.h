@@ -69,7 +69,6 @@ constexpr uint32_t kFlagExcluded = 0x80;
 // the flag byte of a staged record from the caller's PC_FLAG_* bits
 __host__ __device__ inline uint32_t caller_flags(uint32_t f) { return (f & kFlagReverse) | ((f & kFlagExcluded) ? (kFlagExcluded | kFlagUser) : 0u); }
 constexpr int kLinShift = 7;              // linear-index bucket = 128 genome positions
-constexpr int kStreamMaxLen = 255;        // aligned lengths the 4-byte record stream can carry
 
 // The record stream the tile kernel reads is 4 bytes per record:
 //   bit  0      skip: excluded by a host-side filter, or binned from a side list instead (gapped,
@@ -1153,8 +1152,6 @@ __device__ __forceinline__ void hist_bin(const HistCfg &c, bool valid, bool rev,
 // Adding the entry to the stream word puts the window-relative position in the high half (the
 // low halves never carry: 0xff5 + 0x3fff < 2^16), so binning a stream record is: one ds_read_b32,
 // add, shift, shift-or (the skip bit poisons the position), compare, and, add-shift, ds_add.
-constexpr int kOpStage = 32;    // output pieces of a window staged in LDS ahead of the epilogue
-
 template <int KIND>
 __device__ __forceinline__ void fast_table_init(const MapParams &mp, const HistCfg &c, uint32_t mode_mask, int lo, int hi,
                                                 uint32_t *ftab, uint32_t bins_word, int tid, int nthreads, int pre_f,

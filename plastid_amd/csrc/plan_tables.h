@@ -4,12 +4,14 @@
 #pragma once
 #include <stdint.h>
 
-#include "plastid_counts.h"
+#include "../../include/plastid_counts.h"   // (by its place in the tree: the host headers that include this file are compiled with this directory alone on the include path)
 
 namespace pc {
 
 constexpr int kWave = 64;
 constexpr int kGatherChunk = 1024;
+constexpr int kStreamMaxLen = 255;        // aligned lengths the 4-byte record stream can carry
+constexpr int kOpStage = 32;              // output pieces of a window that k_hist_point stages in LDS ahead of its epilogue
 
 // strand modes of a query interval
 //   0: '+'  keeps forward reads, forward index rule

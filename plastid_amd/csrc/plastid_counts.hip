@@ -54,6 +54,7 @@
 #include "host_util.h"
 #include "plan_host.h"
 #include "canon_host.h"
+#include "count_host.h"
 #include "dense_host.h"
 
 using namespace pc;
@@ -449,39 +450,10 @@ static int stage_threads(int64_t n) {
     return (int)std::max<int64_t>(1, std::min<int64_t>(t, n / (1 << 20) + 1)); // a thread is not worth < 1 M records
 }
 
-// The FLAG / MAPQ / NH filter as the setters leave it (pc_set_flag_filter, pc_set_nh_filter); all zero: no filter.
-struct FilterState {
-    bool ff_on = false;
-    uint32_t require = 0, exclude = 0, min_mapq = 0, max_nh = 0;
-    bool operator==(const FilterState &o) const {
-        return ff_on == o.ff_on && require == o.require && exclude == o.exclude && min_mapq == o.min_mapq && max_nh == o.max_nh;
-    }
-};
-
-// What a canonical stream was built from (build_canonical_stream): the rule, the size filter, the range of the entry
-// table, the stream words (by their generation) and the stream it was weighed against.
-struct CanonSig {
-    int kind = -1, param = 0, filt_on = 0, filt_min = 0, filt_max = -1, fast_lo = 0, fast_hi = 0, Ws = 0;
-    uint64_t words_gen = 0;
-    std::vector<int32_t> fw, rc;   // the offset tables (variable rule only)
-    bool operator==(const CanonSig &o) const {
-        return kind == o.kind && param == o.param && filt_on == o.filt_on && filt_min == o.filt_min && filt_max == o.filt_max &&
-               fast_lo == o.fast_lo && fast_hi == o.fast_hi && Ws == o.Ws && words_gen == o.words_gen && fw == o.fw && rc == o.rc;
-    }
-};
-
-// What a dense vector was built from (build_dense_vector): the rule, the size filter, the stream words (by their
-// generation) and the FLAG / MAPQ / NH filter whose verdicts the records held.
-struct DenseSig {
-    int kind = -1, param = 0, filt_on = 0, filt_min = 0, filt_max = -1;
-    uint64_t words_gen = 0;
-    FilterState applied;
-    std::vector<int32_t> fw, rc;   // the offset tables (variable rule only)
-    bool operator==(const DenseSig &o) const {
-        return kind == o.kind && param == o.param && filt_on == o.filt_on && filt_min == o.filt_min && filt_max == o.filt_max &&
-               words_gen == o.words_gen && applied == o.applied && fw == o.fw && rc == o.rc;
-    }
-};
+// what a canonical stream / a dense vector of a staged file was built from, and the filter state in the latter (count_host.h)
+using pccount::CanonSig;
+using pccount::DenseSig;
+using pccount::FilterState;
 
 struct StagedFile {
     int64_t n = 0, nrun = 0, nlong = 0;
@@ -593,73 +565,46 @@ struct StagedFile {
     }
 };
 
-} // namespace
-
-// Tuning and diagnostic knobs (environment).  Read ONCE, at pc_create -- the query path is
-// advertised at tens of microseconds per call and does not look at the environment;
-// pc_reload_knobs() re-reads them (tests and experiments drive the scheduling paths with them).
-struct Knobs {
-    int tile_g = 0;            // PC_TILE_G: window size (0: chosen from the LDS budget)
-    int64_t work_r = 49152;    // PC_WORK_R: records per work item (192 KiB of the 4-byte stream)
-    int64_t pile = 0;          // PC_PILE: records of a 128-nt sub-window beyond which it is merged through the histogram (0: 12 R)
-    int no_small = 0;          // PC_NO_SMALL: no single-wave class for sparse windows
-    int small_rows = 0;        // PC_SMALL_ROWS: 1 = multi-row plans (stratified rule) may use the single-wave class too
-    int64_t ranges_cg16_max = (int64_t)1 << 19;   // PC_RANGES_CG16_MAX: k_tile_ranges gives a window sixteen lanes while windows x 16 stays within this many threads
-    int ranges_cg1 = 0;        // PC_RANGES_CG1: one thread per window in k_tile_ranges whatever the plan's size (tests compare the two forms)
-    int64_t first_sync_spare = 65536;   // PC_FIRST_SYNC_SPARE: spare work-list slots from which the first count of a plan reads its item counts back before it launches
-    int hist_memset = 0;       // PC_HIST_MEMSET: the compact histogram of a large plan is cleared as a whole before its first count (round 5) instead of slice by slice
-    int64_t hist_lazy_bytes = (int64_t)64 << 20;   // PC_HIST_LAZY_BYTES: size from which it is cleared slice by slice (tests: 1)
-    int no_stream_probe = 0;   // PC_NO_STREAM_PROBE: keep the engine's streams as created (see settle_streams)
-    int no_compact = 0;        // PC_NO_COMPACT: no compact stream -- files staged (or re-filtered) from then on are counted record by record (tests compare the two)
-    double compact_keep = 0.9; // PC_COMPACT_KEEP: a file that keeps more than this share of its records as entries gets no compact stream (build_compact_stream)
-    int no_canon = 0;          // PC_NO_CANON: no canonical stream -- eligible plans stream what the others do (A/B runs in one build; tests compare the two)
-    int no_dense = 0;          // PC_NO_DENSE: no dense vector -- eligible plans go through the window kernels (A/B runs in one build; tests compare the two)
-    int dense_items = 0;       // PC_DENSE_ITEMS: the dense vector serves every plan by items (k_dense_gather), none by chunks (A/B runs in one build; tests compare the two)
-    int dense_debug = 0;       // PC_DENSE_DEBUG: print what dense_for_plan decided and from which figures (stderr)
-    int no_single = 0;         // PC_NO_SINGLE: one-window plans go through the work lists like any other (tests compare the two paths)
-    int plan_build = 0;        // PC_PLAN_BUILD=host|gpu: where pc_plan_create builds the tables (default: on the GPU from 8 192 segments)
-    int small_g = 512;         // PC_SMALL_G: queried span a single-wave window may have
-    int64_t small_n = 8192;    // PC_SMALL_N: records a single-wave window may scan (C4: 1.25 ms at 2048, 1.22 at 8192, 1.21 at 32768)
-    int debug_work = 0;        // PC_DEBUG_WORK: print the queued work items per class (stderr; synchronises)
-    int test_stale_counts = 0; // PC_TEST_STALE_COUNTS: pretend the cached work counts are one light item short (exercises the exact-grid guard)
-    int center_t1 = 8;         // PC_CENTER_T1 / PC_CENTER_T2: center chunks with more than T1 x (T1*T2 x) the mean candidate
-    int center_t2 = 4;         //   count are cut into 4 (8) sub-chunks
-    int64_t center_floor = 32768; // PC_CENTER_FLOOR: stream entries below which a chunk is never cut (a wave alone replays ~50 k per ms)
-    int center_lds = 0;        // PC_CENTER_LDS: bytes of (unused) LDS per k_center2 workgroup -- an occupancy throttle for experiments
-    int center_per_wave = 0;   // (reserved)
-    int center_debug = 0;      // PC_CENTER_DEBUG: wall-clock span of every dispatched wave of k_center2, printed after the launch (synchronises)
-    void load() {
-        *this = Knobs();
-        if (const char *env = getenv("PC_TILE_G")) tile_g = std::max(256, atoi(env) / 256 * 256);
-        if (const char *env = getenv("PC_WORK_R")) work_r = std::max(1024, atoi(env));
-        if (const char *env = getenv("PC_PILE")) pile = std::max<int64_t>(work_r, atoll(env));
-        no_small = getenv("PC_NO_SMALL") ? 1 : 0;
-        if (const char *env = getenv("PC_SMALL_ROWS")) small_rows = atoi(env);
-        no_single = getenv("PC_NO_SINGLE") ? 1 : 0;
-        no_compact = getenv("PC_NO_COMPACT") ? 1 : 0;
-        no_canon = getenv("PC_NO_CANON") ? 1 : 0;
-        no_dense = getenv("PC_NO_DENSE") ? 1 : 0;
-        dense_items = getenv("PC_DENSE_ITEMS") ? 1 : 0;
-        dense_debug = getenv("PC_DENSE_DEBUG") ? 1 : 0;
-        if (const char *env = getenv("PC_COMPACT_KEEP")) compact_keep = std::min(1.0, std::max(0.0, atof(env)));
-        no_stream_probe = getenv("PC_NO_STREAM_PROBE") ? 1 : 0;
-        hist_memset = getenv("PC_HIST_MEMSET") ? 1 : 0;
-        hist_lazy_bytes = getenv("PC_HIST_LAZY_BYTES") ? std::max<int64_t>(1, atoll(getenv("PC_HIST_LAZY_BYTES"))) : ((int64_t)64 << 20);
-        ranges_cg1 = getenv("PC_RANGES_CG1") ? 1 : 0;
-        ranges_cg16_max = getenv("PC_RANGES_CG16_MAX") ? atoll(getenv("PC_RANGES_CG16_MAX")) : ((int64_t)1 << 19);
-        first_sync_spare = getenv("PC_FIRST_SYNC_SPARE") ? atoll(getenv("PC_FIRST_SYNC_SPARE")) : 65536;
-        if (const char *env = getenv("PC_PLAN_BUILD")) plan_build = std::strcmp(env, "host") == 0 ? 1 : (std::strcmp(env, "gpu") == 0 ? 2 : 0);
-        if (const char *env = getenv("PC_SMALL_G")) small_g = std::max(64, atoi(env) / 64 * 64);
-        if (const char *env = getenv("PC_SMALL_N")) small_n = std::max(64, atoi(env));
-        debug_work = getenv("PC_DEBUG_WORK") ? 1 : 0;
-        test_stale_counts = getenv("PC_TEST_STALE_COUNTS") ? 1 : 0;
-        if (const char *env = getenv("PC_CENTER_T1")) center_t1 = std::max(8, atoi(env));
-        if (const char *env = getenv("PC_CENTER_T2")) center_t2 = std::max(1, atoi(env));
-        if (const char *env = getenv("PC_CENTER_FLOOR")) center_floor = std::max(64, atoi(env));
-        center_debug = getenv("PC_CENTER_DEBUG") ? 1 : 0;
-        if (const char *env = getenv("PC_CENTER_LDS")) center_lds = std::max(0, atoi(env));
+// Counts a kernel queued on the GPU, read back without a wait: page-locked words, the event behind the copy into them,
+// whether that copy has arrived (`known`: host[] holds the counts) and the engine work_generation they belong to
+// (0: none in flight).
+struct QueuedCounts {
+    uint32_t *host = nullptr;
+    size_t words = 0;
+    hipEvent_t ev = nullptr;
+    bool known = false;
+    uint64_t generation = 0;
+    QueuedCounts() = default;
+    QueuedCounts(const QueuedCounts &) = delete;
+    QueuedCounts &operator=(const QueuedCounts &) = delete;
+    ~QueuedCounts() {
+        if (ev) (void)hipEventDestroy(ev);
+        if (host) (void)hipHostFree(host);
+    }
+    int ensure(size_t n) {
+        if (host) return PC_OK;
+        HIP_TRY(hipHostMalloc((void **)&host, n * sizeof(uint32_t), hipHostMallocDefault));
+        words = n;
+        HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        return PC_OK;
+    }
+    int request(hipStream_t st, const uint32_t *src) {   // (behind ensure)
+        known = false;
+        HIP_TRY(hipMemcpyAsync(host, src, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipEventRecord(ev, st));
+        return PC_OK;
+    }
+    // has the read-back arrived?  Deterministic for its plan while the generation stands: no further read-backs
+    bool poll() {
+        if (host && !known && hipEventQuery(ev) == hipSuccess) known = true;
+        return known;
     }
 };
+
+} // namespace
+
+using pccount::Knobs;   // tuning and diagnostic knobs (count_host.h), read from the environment at pc_create and by pc_reload_knobs
+static const char *env_lookup(const char *name) { return getenv(name); }
 
 static void destroy_tracks_of(pc_engine *e);   // (track_decoder.hip.h)
 static void destroy_summaries_of(pc_engine *e);   // (bigwig_summary.hip.h)
@@ -809,10 +754,7 @@ struct pc_plan {
     uint64_t center_generation = 0;        // (0: no dispatch list yet -- the engine's work_generation starts at 1)
     int center_W = -1;
     int center_nfiles = 0;                 // alignment files the dispatch list was resolved into descriptors for (d_cslots: one per entry and file)
-    uint32_t *h_center_counts = nullptr;   // page-locked [2]: heavy, light entries of the list (sizes the grids of later counts)
-    hipEvent_t ev_center_counts = nullptr;
-    bool center_counts_known = false;
-    uint32_t center_counts[2] = {0, 0};
+    QueuedCounts center_counts;            // [2]: heavy, light entries of the list (sizes the grids of later counts)
     DevView<GatherSeg> d_gsegs;
     DevView<GatherChunk> d_gchunks;
     DevView<uint32_t> d_tile_items;
@@ -847,20 +789,9 @@ struct pc_plan {
     bool counted = false;
     // queued work items per class as the last count of this plan left them (a large plan launches exactly
     // that many workgroups next time instead of the whole list capacity)
-    uint32_t *h_work_counts = nullptr;   // page-locked [8]: heavy, light, small, (diagnostics), merged windows
-    hipEvent_t ev_work_counts = nullptr;
-    uint64_t work_counts_generation = 0; // engine work_generation the read-back belongs to (0: none in flight)
-    bool work_counts_known = false;      // the read-back has arrived: work_counts holds it
-    uint32_t work_counts[3] = {0, 0, 0};
-    uint32_t work_merged = 0;            // windows of the lists that are merged through the compact histogram (what k_gather_split lays out)
+    QueuedCounts work_counts;            // [8]: heavy, light, small, (diagnostics), [4] windows of the lists that are merged through the compact histogram (what k_gather_split lays out)
     bool exact_grid_used = false;        // some count of this plan launched exact grids: its results are read back with the guard word
     bool guard_pending = false;          // the work lists were rebuilt since the guard word was last read (capacity check)
-    ~pc_plan() {
-        if (ev_work_counts) (void)hipEventDestroy(ev_work_counts);
-        if (h_work_counts) (void)hipHostFree(h_work_counts);
-        if (ev_center_counts) (void)hipEventDestroy(ev_center_counts);
-        if (h_center_counts) (void)hipHostFree(h_center_counts);
-    }
 
     explicit pc_plan(pc_engine *eng) : e(eng) {
         DevPool *pl = &eng->pool;
@@ -1383,7 +1314,7 @@ int pc_create(int device, pc_engine **out) {
     pc_engine *e = new pc_engine();
     e->device = device;
     e->pool.device = device;
-    e->knobs.load();
+    e->knobs.load(env_lookup);
     BigReservoir::get().engine_created(device);
     HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     HIP_TRY(hipStreamCreateWithFlags(&e->side_stream, hipStreamNonBlocking));
@@ -1470,7 +1401,7 @@ int pc_host_free(pc_engine *e, void *p) {
 
 int pc_reload_knobs(pc_engine *e) {
     if (!e) return fail(PC_ERR_ARG, "engine is NULL");
-    e->knobs.load();
+    e->knobs.load(env_lookup);
     e->work_generation += 1;
     return PC_OK;
 }
@@ -1501,7 +1432,7 @@ int64_t pc_canonical_entries(pc_engine *e, int file) {
     if (!e || file < 0 || file >= (int)e->files.size()) return -1;
     const StagedFile *sf = e->files[file];
     if (e->files.size() != 1) return -1;   // (only a plan over ONE file streams it: what an earlier count of file 0 alone built is kept, and not served)
-    return (!e->knobs.no_canon && sf->ksig_valid && sf->ksig.words_gen == sf->words_gen) ? sf->kn : -1;
+    return (!e->knobs.no_canon && sf->ksig_valid && sf->ksig.rule.words_gen == sf->words_gen) ? sf->kn : -1;
 }
 
 namespace {
@@ -2493,31 +2424,15 @@ void dispatch_hist(int kind, int outmode, F &&launch) {
     });
 }
 
-// ---- the dynamic LDS of k_hist_point behind its bins: the offset table of the aligned lengths that occur in the data
-// (the variable rules; longer reads look the tables up in HBM), the output pieces parked in LDS, the entry table of the
-// record stream (the aligned lengths the stream carries) and one dump word per lane.  The caller adds its bin words --
-// max_slots x rows x window, halved for 16-bit bins -- and multiplies by four.
-struct HistLds {
-    int tab_lo = 0, tab_n = 0, fast_lo = 0, fast_hi = 0;
-    size_t table_words = 0;
-};
+// ---- the dynamic LDS of k_hist_point behind its bins (count_host.h) for the engine's rule and files; hist_lds_bytes
+// puts the bins of a window in front
+using pccount::HistLds;
 
 HistLds hist_lds_shape(const pc_engine *e) {
-    HistLds s;
-    int lmin = 65536, lmax = -1;
-    s.fast_lo = kStreamMaxLen;
-    for (auto *f : e->files) {
-        lmin = std::min(lmin, f->len_min); lmax = std::max(lmax, f->len_max);
-        s.fast_lo = std::min(s.fast_lo, f->tlen_min); s.fast_hi = std::max(s.fast_hi, f->tlen_max);
-    }
-    if ((e->kind == PC_MAP_VAR5 || e->kind == PC_MAP_STRAT5) && lmax >= lmin) {
-        s.tab_lo = lmin;
-        s.tab_n = std::max(0, std::min(std::min(lmax, e->table_len - 1) - lmin + 1, 1024));
-    }
-    s.fast_lo = std::min(s.fast_lo, s.fast_hi);
-    const size_t stage_words = (size_t)kOpStage * sizeof(OutPiece) / sizeof(uint32_t);
-    s.table_words = (size_t)((s.tab_n + 3) & ~3) + stage_words + (size_t)(s.fast_hi + 1) * kModes + 64;
-    return s;
+    std::vector<pccount::LenRange> r;
+    r.reserve(e->files.size());
+    for (auto *f : e->files) r.push_back({f->len_min, f->len_max, f->tlen_min, f->tlen_max});
+    return pccount::hist_lds_shape(e->kind, e->table_len, r.data(), (int)r.size());
 }
 
 // ---- pc_count, phase by phase.  The phases enqueue on e->stream (the sparse-window class on e->side_stream) in the
@@ -2578,33 +2493,24 @@ int count_clear(pc_engine *e, pc_plan *p, const CountCall &c, const StagedFile *
     const bool center = e->kind == PC_MAP_CENTER;
     PC_TRY(mark(e, 0));
     // A count served from a dense vector: the plan's one-time tables are made here, behind mark 0, so that last_timing()
-    // of a first count holds them.  By chunks where the plan has a chunk table (no overlapping output ranges) and the
-    // output block is line aligned -- the chunk kernel's stores are whole lines -- else by items
+    // of a first count holds them.  By chunks or by items: dense_by_chunks (count_host.h)
     int dense_path = PC_DENSE_PATH_NONE;
     if (dense) {
         PC_TRY(ensure_dense_tables(e, p, dense));
-        const bool chunks = p->chunks_ok && p->dchunks_id == dense->did && !e->knobs.dense_items && ((uintptr_t)p->d_out.p & 127u) == 0;
+        const bool chunks = pccount::dense_by_chunks(p->chunks_ok, p->dchunks_id == dense->did, e->knobs.dense_items, (uintptr_t)p->d_out.p);
         dense_path = chunks ? PC_DENSE_PATH_CHUNKS : PC_DENSE_PATH_ITEMS;
     }
     *path = dense_path;
-    if (dense_path != PC_DENSE_PATH_NONE) {
-        // k_dense_gather writes every position of every segment, zeros included: only gaps between slices are cleared.
-        // k_dense_gather_chunks writes every element of the output, the gaps too: nothing is
-        if (dense_path == PC_DENSE_PATH_ITEMS && p->covered != p->out_elems && p->out_elems)
-            HIP_TRY(hipMemsetAsync(p->d_out.p, 0, (size_t)p->out_elems * 8, e->stream));
-        return mark(e, 1);
-    }
-    // Outputs are written exactly once by the tile kernels.  Only positions that belong to no
-    // tile (unknown contig, clipped coordinates) or gaps the caller left between slices need a
-    // zero fill; the compact histogram of the point rules is kept all-zero between calls.
-    if ((p->has_sums || p->out_needs_zero || p->covered != p->out_elems) && p->out_elems)
+    // what the kernels of the path leave unwritten is cleared (out_needs_memset); the compact histogram of the point
+    // rules is kept all-zero between calls
+    const pccount::OutPath out_path = dense_path == PC_DENSE_PATH_CHUNKS ? pccount::kOutChunks : (dense_path == PC_DENSE_PATH_ITEMS ? pccount::kOutItems : pccount::kOutWindows);
+    if (pccount::out_needs_memset(out_path, p->has_sums, p->out_needs_zero, p->covered, p->out_elems))
         HIP_TRY(hipMemsetAsync(p->d_out.p, 0, (size_t)p->out_elems * 8, e->stream));
-    // (a large histogram is not cleared as a whole: k_clear_split zeroes the slices of the merged windows behind every
-    // k_tile_ranges, which is all that is ever read of it)
+    if (dense_path != PC_DENSE_PATH_NONE) return mark(e, 1);
     // `hist_clean` says that the WHOLE histogram is zero: true once it has been cleared as a whole, and kept by every
     // count (k_clear_split only zeroes, k_gather_split zeroes what it merged).  Lazy counts never make it true, so the
     // first count after the knobs turn lazy off (pc_reload_knobs) clears what the lazy ones left alone.
-    p->hist_lazy = !center && (int64_t)c.hist_bytes >= e->knobs.hist_lazy_bytes && !e->knobs.hist_memset;
+    p->hist_lazy = pccount::hist_lazy(center, (int64_t)c.hist_bytes, e->knobs.hist_lazy_bytes, e->knobs.hist_memset);
     if (!center && c.hist_bytes && !p->hist_clean && !p->hist_lazy) {
         HIP_TRY(hipMemsetAsync(p->d_hist.p, 0, c.hist_bytes, e->stream));
         p->hist_clean = true;
@@ -2616,7 +2522,7 @@ int count_clear(pc_engine *e, pc_plan *p, const CountCall &c, const StagedFile *
 // record ranges up itself; no work list, no second window class, no merge pass, no events
 int count_single(pc_engine *e, pc_plan *p, const CountCall &c) {
     const HistLds s = hist_lds_shape(e);
-    const size_t lds = ((size_t)p->max_slots * p->rows * p->G + s.table_words) * sizeof(uint32_t);
+    const size_t lds = pccount::hist_lds_bytes(s, (size_t)p->max_slots * p->rows, p->G, false);
     if (lds > e->max_lds)
         return fail(PC_ERR_ARG, "pc_count: the window needs %zu bytes of LDS, the device offers %zu per workgroup (too many rows)", lds, e->max_lds);
     const FileView fv0 = e->files[0]->view();
@@ -2639,41 +2545,25 @@ struct WorkLists {
     pc_plan::WorkKey key;
     HistLds shape;                    // dynamic LDS of k_hist_point: what both classes share, and the bytes of either
     size_t lds = 0, lds_small = 0;
-    // grids: the whole list capacity, or -- once a count of this plan has shown how many items each
-    // class queues (same alignments, same knobs) -- exactly those: a sparse annotation leaves most
-    // of the capacity empty, and an empty workgroup still costs a dispatch slot
-    unsigned grid = 0, grid_front = 0, grid_small = 0;
-    uint32_t launched[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu};   // exact grids: what k_gather_split checks the queued counts against
+    pccount::Grids grids;             // of both classes: the whole capacity, or exactly the queued items (choose_grids)
 };
 
 int size_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, WorkLists &w) {
     const int nfiles = c.nfiles, G = p->G;
-    const int64_t R = e->knobs.work_r;                             // records per work item
-    const int64_t pile = e->knobs.pile ? e->knobs.pile : 12 * R;   // a 128-nt sub-window with more records than this is merged through the histogram
-    // work-list capacity (an upper bound): a window scanning n records yields at most
-    // max(1, 2n/R) items, and every record is scanned by at most 1 + (W+127)/G windows
-    const int halo = std::max(std::max(e->W(), e->Ws()), std::max(e->Wg(), e->Wr()));
-    // (a multi-row plan gives every strand mode of a window a tile of its own -- pc_plan_create, split_modes --
-    // so a record is scanned by up to popcount(modes) tiles per window)
-    const int tiles_per_window = p->rows > 1 ? std::max(1, __builtin_popcount(p->modes)) : 1;
-    const double windows_per_record = (1.0 + (double)(halo + 127) / (double)G) * (double)tiles_per_window;
-    w.cap = (int64_t)c.ntiles * nfiles + (int64_t)(2.0 * windows_per_record * (double)c.nrec / (double)R) + nfiles + 64;
     const bool b16 = e->kind == PC_MAP_STRAT5;   // 16-bit bins, two positions per word (k_hist_point)
-    if (b16) {
-        // a window that scans more than 65 535 records, runs and list entries is merged, in slices of ONE
-        // kind of range each (k_tile_ranges): at most adds / R + 4 items per such window, and fewer than adds / 65 535 of them
-        int64_t nxl = 0, ngp = 0;
-        for (auto *f : e->files) { nxl += f->nxlong; ngp += f->ngap; }
-        w.cap += (int64_t)(6.0 * windows_per_record * (double)(c.nrec + c.nextra + ngp) / (double)R) +
-                 (int64_t)c.ntiles * nfiles * (4 + 2 * (nxl / R));
-    }
-    if (w.cap >= (int64_t)0xffffffffu) return fail(PC_ERR_ARG, "pc_count: work list too large");
+    pccount::WorkIn in;
+    in.ntiles = c.ntiles; in.nfiles = nfiles; in.G = G; in.rows = p->rows; in.modes = p->modes; in.npos = p->npos;
+    in.nrec = c.nrec; in.nextra = c.nextra;
+    for (auto *f : e->files) { in.nxlong += f->nxlong; in.ngap += f->ngap; }
+    in.W = e->W(); in.Ws = e->Ws(); in.Wg = e->Wg(); in.Wr = e->Wr();
+    in.R = e->knobs.work_r; in.pile = e->knobs.pile;
+    in.no_small = e->knobs.no_small; in.small_rows = e->knobs.small_rows; in.small_g = e->knobs.small_g;
+    in.stratified = b16;
+    const pccount::WorkSizes ws = pccount::work_list_sizes(in);   // the capacities: upper bounds (count_host.h)
+    if (ws.too_large) return fail(PC_ERR_ARG, "pc_count: work list too large");
+    const int64_t R = in.R, pile = ws.pile;
+    w.cap = ws.cap; w.small_g = ws.small_g; w.cap_small = ws.cap_small;
     PC_TRY(p->d_work.reserve((size_t)w.cap));
-    // sparse windows: single-wave workgroups with a small LDS window (rows == 1 only)
-    // (skipped for dense annotations, where queried positions fill most of every window)
-    const bool sparse_plan = (double)p->npos < 0.25 * (double)c.ntiles * (double)G;
-    w.small_g = ((p->rows == 1 || e->knobs.small_rows) && sparse_plan && !e->knobs.no_small) ? std::min(e->knobs.small_g, G) : 0;
-    w.cap_small = w.small_g ? (int64_t)c.ntiles * nfiles : 0;
     PC_TRY(p->d_work_small.reserve((size_t)std::max<int64_t>(w.cap_small, 1)));
     if (nfiles > 1) {
         PC_TRY(p->d_chain.reserve((size_t)w.cap * (size_t)(nfiles - 1)));
@@ -2684,31 +2574,19 @@ int size_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, WorkLists &w) 
     key.small_g = w.small_g; key.R = R; key.pile = pile; key.small_n = e->knobs.small_n; key.cap = w.cap;
     w.shape = hist_lds_shape(e);
     const size_t slot_words = (size_t)p->max_slots * p->rows;   // bin words per window position (per two, with 16-bit bins)
-    w.lds = (((slot_words * G) >> (b16 ? 1 : 0)) + w.shape.table_words) * sizeof(uint32_t);
-    w.lds_small = (((slot_words * w.small_g) >> (b16 ? 1 : 0)) + w.shape.table_words) * sizeof(uint32_t);
+    w.lds = pccount::hist_lds_bytes(w.shape, slot_words, G, b16);
+    w.lds_small = pccount::hist_lds_bytes(w.shape, slot_words, w.small_g, b16);
     return PC_OK;
 }
 
-// page-locked words that counts queued on the GPU are read back into, and the event behind that copy
-int ensure_readback(uint32_t **host, hipEvent_t *ev, size_t words) {
-    if (*host) return PC_OK;
-    HIP_TRY(hipHostMalloc((void **)host, words * sizeof(uint32_t), hipHostMallocDefault));
-    HIP_TRY(hipEventCreateWithFlags(ev, hipEventDisableTiming));
-    return PC_OK;
-}
-
-int ensure_work_counts(pc_plan *p) { return ensure_readback(&p->h_work_counts, &p->ev_work_counts, 8); }
-
-// a read-back has arrived: deterministic for this plan while the generation stands, no further read-backs
-void take_work_counts(pc_plan *p) {
-    for (int k = 0; k < 3; ++k) p->work_counts[k] = p->h_work_counts[k];
-    p->work_merged = p->h_work_counts[4];
-    p->work_counts_known = true;
+// the engine's rule and size filter over the file's stream words: what its canonical stream and its dense vector hang on
+pccount::RuleSig rule_sig(const pc_engine *e, const StagedFile *sf) {
+    return pccount::rule_sig(e->kind, e->param, e->filt_on, e->filt_min, e->filt_max, sf->words_gen, e->h_fw, e->h_rc);
 }
 
 // ---- the canonical stream of the plan's file under the engine's rule and size filter (stage_kernels.hip.h,
-// canon_host.h).  Used by a plan over ONE file, under a point rule without rows (fiveprime, threeprime, variable), whose
-// windows are '+' and '-' only -- a '.' window bins both strands by the forward rule: another grouping -- and only when
+// canon_host.h).  Used by the plans of stream_plan_conditions (count_host.h: ONE file, a point rule without rows,
+// windows '+' and '-' only), and only when
 // it has at most `compact_keep` of the entries of the stream it replaces (the compact stream's own rule).  Built at the
 // first count that wants it and kept on the file under its signature: rule, filter, entry-table range, halo and the
 // generation of the stream words.  A steady-state count compares the signature and goes on; a build allocates from the
@@ -2716,25 +2594,16 @@ void take_work_counts(pc_plan *p) {
 int canonical_for_plan(pc_engine *e, pc_plan *p, const CountCall &c, const HistLds &shape, StagedFile **canon) {
     using namespace pcstage;
     *canon = nullptr;
-    const bool point = e->kind == PC_MAP_FIVE || e->kind == PC_MAP_THREE || e->kind == PC_MAP_VAR5;
-    if (e->knobs.no_canon || c.nfiles != 1 || !point || p->rows != 1 || (p->modes & ~3u) != 0u || p->modes == 0u) return PC_OK;
+    if (e->knobs.no_canon || !pccount::stream_plan_conditions(c.nfiles, e->kind, p->rows, p->modes)) return PC_OK;
     StagedFile *sf = e->files[0];
     if (sf->n <= 0 || !sf->nlin) return PC_OK;
     CanonSig sig;
-    sig.kind = e->kind; sig.param = e->kind == PC_MAP_VAR5 ? 0 : e->param;
-    sig.filt_on = e->filt_on; sig.filt_min = e->filt_on ? e->filt_min : 0; sig.filt_max = e->filt_on ? e->filt_max : -1;
-    sig.fast_lo = shape.fast_lo; sig.fast_hi = shape.fast_hi; sig.Ws = e->Ws(); sig.words_gen = sf->words_gen;
-    if (e->kind == PC_MAP_VAR5) { sig.fw = e->h_fw; sig.rc = e->h_rc; }
+    sig.rule = rule_sig(e, sf);
+    sig.fast_lo = shape.fast_lo; sig.fast_hi = shape.fast_hi; sig.Ws = e->Ws();
     if (!(sf->ksig_valid && sf->ksig == sig)) {
         sf->ksig_valid = false;
         sf->kn = -1;
-        pccanon::RuleIn r;
-        r.kind = e->kind == PC_MAP_FIVE ? 0 : (e->kind == PC_MAP_THREE ? 1 : 3);
-        r.param = e->param; r.table_len = (int)std::min<size_t>((size_t)e->table_len, std::min(e->h_fw.size(), e->h_rc.size()));
-        r.fw = e->h_fw.data(); r.rc = e->h_rc.data();
-        r.filt_on = e->filt_on; r.filt_min = e->filt_min; r.filt_max = e->filt_max;
-        r.fast_lo = shape.fast_lo; r.fast_hi = shape.fast_hi;
-        const pccanon::CanonRule cr = pccanon::canon_rule(r);
+        const pccanon::CanonRule cr = pccanon::canon_rule(pccount::canon_rule_in(sig, e->table_len));
         if (cr.usable && pccanon::canon_fits_halo(cr, sig.Ws)) {
             PoolScope pool_scope(&e->pool);
             hipStream_t st = e->stream;
@@ -2808,9 +2677,9 @@ int build_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLis
                            p->d_pieces.p, p->d_tile_items.p, p->d_wcounters.p, p->rows, (uint32_t *)p->d_hist.p, (int64_t)p->npos);
     p->work_key = w.key;
     p->work_valid = true;
-    p->work_counts_known = false;      // the counts of the lists just replaced size no grid
+    p->work_counts.known = false;      // the counts of the lists just replaced size no grid
     p->guard_pending = true;           // k_gather_split checks the new lists against the capacity: read with the results
-    p->work_counts_generation = 0;
+    p->work_counts.generation = 0;
     // The first count of a plan does not know how many items its lists hold, and used to launch the whole
     // capacity: for a sparse annotation under a multi-row rule that is 3.6 M workgroups for 0.53 M items (C5:
     // 3.88 ms against 3.24, and the merge pass on top).  Where the capacity is far above the window count, the
@@ -2818,29 +2687,23 @@ int build_work_lists(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLis
     // this count already launches exact grids.
     const int64_t spare = w.cap + w.cap_small - nwin;
     if (ntiles >= 4096 && spare >= e->knobs.first_sync_spare && !e->knobs.test_stale_counts && !e->knobs.debug_work) {
-        PC_TRY(ensure_work_counts(p));
-        HIP_TRY(hipMemcpyAsync(p->h_work_counts, p->d_wcounters.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        QueuedCounts &q = p->work_counts;   // (read in place: a copy and a wait, no event)
+        PC_TRY(q.ensure(8));
+        HIP_TRY(hipMemcpyAsync(q.host, p->d_wcounters.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        take_work_counts(p);
-        p->work_counts_generation = e->work_generation;
+        q.known = true;
+        q.generation = e->work_generation;
     }
     return PC_OK;
 }
 
+// the whole list capacity, or what the read-back of an earlier count of these lists says they hold (count_host.h)
 void choose_grids(pc_engine *e, pc_plan *p, const CountCall &c, WorkLists &w) {
-    w.grid = w.grid_front = (unsigned)w.cap;
-    w.grid_small = (unsigned)w.cap_small;
-    if (c.ntiles < 4096 || p->work_counts_generation != e->work_generation) return;   // (small plans do not track their counts)
-    if (p->h_work_counts && !p->work_counts_known && hipEventQuery(p->ev_work_counts) == hipSuccess) take_work_counts(p);
-    if (!p->work_counts_known) return;
-    const uint32_t nh = p->work_counts[0], nl = p->work_counts[1] - ((e->knobs.test_stale_counts && p->work_counts[1]) ? 1u : 0u), ns = p->work_counts[2];
-    if ((uint64_t)nh + nl <= (uint64_t)w.cap && (int64_t)ns <= w.cap_small) {
-        w.grid_front = nh;
-        w.grid = std::max(1u, nh + nl);
-        w.grid_small = ns;
-        w.launched[0] = nh; w.launched[1] = nl; w.launched[2] = ns;
-        p->exact_grid_used = true;
-    }
+    QueuedCounts &q = p->work_counts;
+    const bool tracked = c.ntiles >= 4096 && q.generation == e->work_generation;   // (small plans do not track their counts)
+    const bool known = tracked && q.poll();
+    w.grids = pccount::choose_grids(c.ntiles, tracked, known, q.host, w.cap, w.cap_small, e->knobs.test_stale_counts != 0);
+    if (w.grids.exact) p->exact_grid_used = true;
 }
 
 // sparse windows (single-wave workgroups) and dense ones are two independent launches over
@@ -2861,15 +2724,15 @@ int launch_hist(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w
             constexpr int k = decltype(K)::value, o = decltype(O)::value;
             constexpr bool m = decltype(M)::value != 0;
             typename OutT_<o>::type *out = (typename OutT_<o>::type *)p->d_out.p;
-            hipLaunchKernelGGL((k_hist_point<k, o, kHistWG, false, m>), dim3(w.grid), dim3(kHistWG), w.lds, st, p->d_pieces.p,
+            hipLaunchKernelGGL((k_hist_point<k, o, kHistWG, false, m>), dim3(w.grids.grid), dim3(kHistWG), w.lds, st, p->d_pieces.p,
                                p->d_opieces.p, fv0, fv1, e->d_files.p, p->d_work.p, p->d_wcounters.p, p->d_tile_items.p, c.mp,
                                p->G, p->max_slots, s.tab_lo, s.tab_n, s.fast_lo, s.fast_hi, (uint32_t *)p->d_hist.p, p->npos, out,
-                               e->norm_sum, (uint32_t)w.cap, w.grid_front, p->d_chain.p, nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u);
-            if (w.cap_small && w.grid_small)
-                hipLaunchKernelGGL((k_hist_point<k, o, 64, true, m>), dim3(w.grid_small), dim3(64), w.lds_small, st_small,
+                               e->norm_sum, (uint32_t)w.cap, w.grids.grid_front, p->d_chain.p, nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u);
+            if (w.cap_small && w.grids.grid_small)
+                hipLaunchKernelGGL((k_hist_point<k, o, 64, true, m>), dim3(w.grids.grid_small), dim3(64), w.lds_small, st_small,
                                    p->d_pieces.p, p->d_opieces.p, fv0, fv1, e->d_files.p, p->d_work_small.p,
                                    p->d_wcounters.p, p->d_tile_items.p, c.mp, w.small_g, p->max_slots, s.tab_lo, s.tab_n, s.fast_lo, s.fast_hi,
-                                   (uint32_t *)p->d_hist.p, p->npos, out, e->norm_sum, (uint32_t)w.cap_small, w.grid_small,
+                                   (uint32_t *)p->d_hist.p, p->npos, out, e->norm_sum, (uint32_t)w.cap_small, w.grids.grid_small,
                                    p->d_chain_small.p, nfiles, Tile{}, OutPiece{}, (uint32_t *)nullptr, 0u);
         });
     });
@@ -2885,14 +2748,14 @@ int launch_hist(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w
 void merge_windows(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w) {
     // (skipped once the plan's lists are known to hold no merged window: the lists are the plan's own and do not
     // change from count to count, so neither does that -- and the exact grids it would check were read from them)
-    if (w.launched[0] != 0xffffffffu && p->work_merged == 0 && !e->knobs.test_stale_counts) return;
+    if (w.grids.exact && p->work_counts.host[4] == 0 && !e->knobs.test_stale_counts) return;
     const int split_per_wg = kWG; // merged windows are the exception (pile-ups), with several files too (joint windows)
     dispatch_int<0, 1, 2>(c.outmode, [&](auto O) {
         constexpr int o = decltype(O)::value;
         hipLaunchKernelGGL((k_gather_split<o>), dim3((unsigned)((c.ntiles + split_per_wg - 1) / split_per_wg)), dim3(kWG), 0, e->stream,
                            p->d_tiles.p, c.ntiles, split_per_wg, p->d_pieces.p,
                            p->d_opieces.p, p->d_tile_items.p, p->d_wcounters.p, p->rows, (uint32_t *)p->d_hist.p, p->npos,
-                           (typename OutT_<o>::type *)p->d_out.p, e->norm_sum, w.launched[0], w.launched[1], w.launched[2], (uint32_t)w.cap, e->d_counters.p + 12);
+                           (typename OutT_<o>::type *)p->d_out.p, e->norm_sum, w.grids.launched[0], w.grids.launched[1], w.grids.launched[2], (uint32_t)w.cap, e->d_counters.p + 12);
     });
 }
 
@@ -2900,12 +2763,11 @@ void merge_windows(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists
 int read_work_counts(pc_engine *e, pc_plan *p, const CountCall &c, const WorkLists &w) {
     hipStream_t st = e->stream;
     if (c.ntiles >= 4096) {
-        PC_TRY(ensure_work_counts(p));
-        if (p->work_counts_generation != e->work_generation) {   // one read-back per (plan, generation)
-            p->work_counts_known = false;
-            HIP_TRY(hipMemcpyAsync(p->h_work_counts, p->d_wcounters.p, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipEventRecord(p->ev_work_counts, st));
-            p->work_counts_generation = e->work_generation;
+        QueuedCounts &q = p->work_counts;
+        PC_TRY(q.ensure(8));
+        if (q.generation != e->work_generation) {   // one read-back per (plan, generation)
+            PC_TRY(q.request(st, p->d_wcounters.p));
+            q.generation = e->work_generation;
         }
     }
     if (e->knobs.debug_work) { // diagnostics: how many work items of each class this call queued
@@ -2942,10 +2804,8 @@ int count_lists(pc_engine *e, pc_plan *p, const CountCall &c) {
 // no work lists, no windows, no LDS, no merge pass.
 DenseSig dense_sig(const pc_engine *e, const StagedFile *sf) {
     DenseSig sig;
-    sig.kind = e->kind; sig.param = e->kind == PC_MAP_VAR5 ? 0 : e->param;
-    sig.filt_on = e->filt_on; sig.filt_min = e->filt_on ? e->filt_min : 0; sig.filt_max = e->filt_on ? e->filt_max : -1;
-    sig.words_gen = sf->words_gen; sig.applied = sf->applied;
-    if (e->kind == PC_MAP_VAR5) { sig.fw = e->h_fw; sig.rc = e->h_rc; }
+    sig.rule = rule_sig(e, sf);
+    sig.applied = sf->applied;
     return sig;
 }
 
@@ -3025,7 +2885,7 @@ int dense_for_plan(pc_engine *e, pc_plan *p, const CountCall &c, StagedFile **de
     *dense = nullptr;
     pcdense::PlanIn in;
     in.nfiles = c.nfiles;
-    in.point_rule = e->kind == PC_MAP_FIVE || e->kind == PC_MAP_THREE || e->kind == PC_MAP_VAR5;
+    in.kind = e->kind;
     in.rows = p->rows; in.modes = p->modes; in.has_sums = p->has_sums;
     in.forbidden = e->knobs.no_dense || p->no_dense;
     if (!pcdense::plan_conditions(in)) return PC_OK;
@@ -3206,11 +3066,8 @@ int build_center_dispatch(pc_engine *e, pc_plan *p, int W) {
     p->center_generation = e->work_generation;
     p->center_W = W;
     // how many entries the list got: sizes the grid of the later counts of this plan (read back once)
-    PC_TRY(ensure_readback(&p->h_center_counts, &p->ev_center_counts, 2));
-    p->center_counts_known = false;
-    HIP_TRY(hipMemcpyAsync(p->h_center_counts, p->d_ccounts.p, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipEventRecord(p->ev_center_counts, st));
-    return PC_OK;
+    PC_TRY(p->center_counts.ensure(2));
+    return p->center_counts.request(st, p->d_ccounts.p);
 }
 
 // descriptors: heavy entries one wave each, PC_CENTER_PER_WAVE light entries per wave (an eighth of the list per XCD)
@@ -3225,19 +3082,16 @@ void launch_center2(pc_engine *e, pc_plan *p, const CountCall &c, int W, unsigne
     }
     c2.files = e->d_files.p; c2.nfiles = c.nfiles; c2.file0 = sf0->view(); c2.mp = c.mp; c2.W = W; c2.inv = e->d_inv.p; c2.invh = e->d_invh.p; c2.cvalh = e->d_cvalh.p;
     c2.counters = p->d_ccounts.p;
-    c2.known = p->center_counts_known ? 1u : 0u; c2.n_heavy = p->center_counts[0]; c2.n_light = p->center_counts[1];
+    const QueuedCounts &q = p->center_counts;   // (heavy, light; the kernel reads its own counters while they are not known)
+    const uint32_t n_heavy = q.known ? q.host[0] : 0u, n_light = q.known ? q.host[1] : 0u;
+    c2.known = q.known ? 1u : 0u; c2.n_heavy = n_heavy; c2.n_light = n_light;
     c2.opieces = p->d_opieces.p; c2.out = (double *)p->d_out.p; c2.norm_sum = e->norm_sum; c2.norm_on = e->norm_on ? 1 : 0;
     c2.dbg = dbg; c2.dbg_cap = (uint32_t)dbg_slots;
-    uint64_t g2;
-    if (p->center_counts_known) {
-        const uint64_t n8 = ((uint64_t)p->center_counts[1] + 7) >> 3;
-        g2 = (uint64_t)p->center_counts[0] + 8 * ((n8 + PC_CENTER_PER_WAVE - 1) / PC_CENTER_PER_WAVE);
-    } else g2 = 2 * (uint64_t)p->n_cchunks + 8;
-    const dim3 cg2((unsigned)std::max<uint64_t>(g2, 1));
+    const dim3 cg2((unsigned)pccount::center_grid(q.known, n_heavy, n_light, (uint64_t)p->n_cchunks, PC_CENTER_PER_WAVE));
     // (files with reads beyond a stream entry's 8-bit fields, or a stream too long for 32-bit byte offsets, take the
     // instantiation that tests every batch for them)
     bool general = false;
-    for (auto *f : e->files) general |= f->len_max > 255 || f->n + f->nrun >= ((int64_t)1 << 28);
+    for (auto *f : e->files) general |= pccount::center_general(f->len_max, f->n + f->nrun);
     // (several files: one descriptor per entry and file, replayed into the same sums in file order)
     dispatch_int<0, 1>(dbg != nullptr, [&](auto D) {
         dispatch_int<0, 1>(general, [&](auto G) {
@@ -3306,11 +3160,7 @@ int count_center(pc_engine *e, pc_plan *p, const CountCall &c) {
         hipLaunchKernelGGL(k_center_vals, dim3(1), dim3(256), 0, e->stream, c.mp, e->d_invh.p, e->d_cvalh.p);
         if (p->center_generation != e->work_generation || p->center_W != W || p->center_nfiles != c.nfiles) {
             PC_TRY(build_center_dispatch(e, p, W));
-        } else if (!p->center_counts_known && hipEventQuery(p->ev_center_counts) == hipSuccess) {
-            p->center_counts[0] = p->h_center_counts[0];
-            p->center_counts[1] = p->h_center_counts[1];
-            p->center_counts_known = true;
-        }
+        } else (void)p->center_counts.poll();
         // PC_CENTER_DEBUG: how long every dispatched wave ran (wall clock ticks), printed after the launch
         DevBuf<unsigned long long> d_dbg;
         const bool dbg_on = e->knobs.center_debug != 0 || e->want_center_steps;
@@ -3355,9 +3205,7 @@ int pc_count(pc_engine *e, pc_plan *p, int out_dtype) {
     for (auto *f : e->files) { c.nrec += f->n; c.nextra += f->nrun; }
     c.hist_bytes = center ? 0 : (size_t)p->npos * p->rows * sizeof(uint32_t);
     c.mp = e->params();
-    // (one window, not under the stratified rule: its 16-bit bins rely on the work lists, which cut or merge a window that
-    // scans more than 65 535 records)
-    const bool single = c.ntiles == 1 && c.nfiles == 1 && !e->knobs.debug_work && !e->knobs.no_single && e->kind != PC_MAP_STRAT5;
+    const bool single = pccount::single_window(c.ntiles, c.nfiles, e->kind, e->knobs.debug_work, e->knobs.no_single);
     StagedFile *dense = nullptr;   // (decided first: a build counts a plan of its own on this engine)
     if (!center && !single && c.ntiles > 0) PC_TRY(dense_for_plan(e, p, c, &dense));
     e->last_count_dense = dense != nullptr;
@@ -3400,8 +3248,8 @@ static int check_grid_guard(pc_engine *e, pc_plan *p) {
     p->guard_pending = false;
     if (!err) return PC_OK;
     HIP_TRY(hipMemsetAsync(e->d_counters.p + 12, 0, sizeof(uint32_t), e->stream));
-    p->work_counts_known = false;
-    p->work_counts_generation = 0;
+    p->work_counts.known = false;
+    p->work_counts.generation = 0;
     p->exact_grid_used = false;
     p->work_valid = false;
     if (err & 2u)
@@ -3588,7 +3436,7 @@ int pc_query_segment(pc_engine *e, int32_t tid, int64_t start, int64_t end, uint
     if (!e || !host_out) return fail(PC_ERR_ARG, "pc_query_segment: bad arguments");
     if (!e->have_map) return fail(PC_ERR_STATE, "pc_query_segment: no mapping rule set (pc_set_mapping)");
     if (e->files.size() != 1) return fail(PC_ERR_STATE, "pc_query_segment: needs exactly one staged alignment file (several: pc_plan_create)");
-    if (e->kind != PC_MAP_FIVE && e->kind != PC_MAP_THREE && e->kind != PC_MAP_VAR5)
+    if (!pccount::point_rule(e->kind))
         return fail(PC_ERR_STATE, "pc_query_segment: the center and the stratified rule go through pc_plan_create");
     if (out_dtype != PC_OUT_INT64 && out_dtype != PC_OUT_FLOAT64) return fail(PC_ERR_ARG, "pc_query_segment: bad out_dtype");
     if (e->norm_on && out_dtype != PC_OUT_FLOAT64) return fail(PC_ERR_ARG, "pc_query_segment: normalisation produces float64");
@@ -3607,7 +3455,7 @@ int pc_query_segment(pc_engine *e, int32_t tid, int64_t start, int64_t end, uint
     const MapParams mp = e->params();
     const HistLds ls = hist_lds_shape(e);
     const int G = kQueryMax;
-    const size_t lds = ((size_t)G + ls.table_words) * sizeof(uint32_t);
+    const size_t lds = pccount::hist_lds_bytes(ls, 1, G, false);
     if (lds > e->max_lds) return fail(PC_ERR_STATE, "pc_query_segment: the window needs %zu bytes of LDS", lds);
     const int mode = mode_of(strand);
     Tile tl{};

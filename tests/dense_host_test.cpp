@@ -47,13 +47,13 @@ static int check() {
     CHECK(build_fits(kBuildBlockCap / 8) && !build_fits(kBuildBlockCap / 8 + 1));
     // the plan conditions
     PlanIn p;
-    p.nfiles = 1; p.point_rule = true; p.rows = 1; p.modes = 3u; p.cells = 200; p.stream_entries = 100;
+    p.nfiles = 1; p.kind = PC_MAP_FIVE; p.rows = 1; p.modes = 3u; p.cells = 200; p.stream_entries = 100;
     CHECK(eligible(p));
     { PlanIn q = p; q.modes = 1u; CHECK(eligible(q)); q.modes = 2u; CHECK(eligible(q)); }
     { PlanIn q = p; q.modes = 0u; CHECK(!eligible(q)); }
     { PlanIn q = p; q.modes = 4u; CHECK(!eligible(q)); q.modes = 7u; CHECK(!eligible(q)); q.modes = 8u; CHECK(!eligible(q)); }   // a '.' window
     { PlanIn q = p; q.nfiles = 2; CHECK(!eligible(q)); }
-    { PlanIn q = p; q.point_rule = false; CHECK(!eligible(q)); }
+    { PlanIn q = p; q.kind = PC_MAP_CENTER; CHECK(!eligible(q)); q.kind = PC_MAP_STRAT5; CHECK(!eligible(q)); q.kind = PC_MAP_THREE; CHECK(eligible(q)); q.kind = PC_MAP_VAR5; CHECK(eligible(q)); }
     { PlanIn q = p; q.rows = 11; CHECK(!eligible(q)); }
     { PlanIn q = p; q.has_sums = true; CHECK(!eligible(q)); }
     { PlanIn q = p; q.forbidden = true; CHECK(!eligible(q)); }
