@@ -2,7 +2,8 @@
 // kernels of bam_kernels.hip.h.  One open is five phases (bam_open_impl): plan_members (bam_host.h), upload_and_inflate,
 // read_header, chain_records, decode_columns.  The index build (bam_index_impl: BAI or CSI) runs the first four and
 // index_records in place of the fifth.  Every phase is a list of steps: HIP calls, and the host arithmetic of bam_host.h
-// (plain C++, tested on the CPU by tests/bam_host_test.cpp).  Part of the one translation unit of plastid_counts.hip.
+// (plain C++, tested on the CPU by tests/bam_host_test.cpp).  Part of the one translation unit of plastid_counts.hip;
+// the plumbing -- buffers, room, DrainOnExit, the hipcub seam -- is device_util.hip.h.
 #include "bam_kernels.hip.h"
 #include "sort_kernels.hip.h"
 #include "index_kernels.hip.h"
@@ -61,47 +62,6 @@ struct CrcTables {
     }
 };
 const CrcTables &crc_tables() { static const CrcTables t; return t; }
-
-double ms_between(hipEvent_t a, hipEvent_t b) { float t = 0.f; return hipEventElapsedTime(&t, a, b) == hipSuccess ? (double)t : 0.0; }
-// The events that cut a call into laps: N events, destroyed on exit; lap k lies between events k and k + 1.
-template <int N> struct LapEvents {
-    hipEvent_t ev[N] = {};
-    int create() {
-        for (auto &x : ev) HIP_TRY(hipEventCreate(&x));
-        return PC_OK;
-    }
-    ~LapEvents() { for (auto x : ev) if (x) (void)hipEventDestroy(x); }
-    hipEvent_t operator[](int k) const { return ev[k]; }
-    void laps(double *ms, int n) const { for (int k = 0; k < n; ++k) ms[k] = ms_between(ev[k], ev[k + 1]); }
-};
-// one more buffer of a phase, unless an earlier one has failed
-template <typename Buf> void room(int &rc, Buf &buf, size_t n) { if (rc == PC_OK) rc = buf.reserve(n); }
-// A step's temporaries are read by what it queued: an early return drains the stream before they go out of scope
-// (disarmed behind the step's own synchronisation).  Declared BEHIND the host and device temporaries it covers.
-struct DrainOnExit {
-    hipStream_t st; bool armed = true;
-    ~DrainOnExit() { if (armed) (void)hipStreamSynchronize(st); }
-};
-// A hipcub call is `call(tmp, bytes)`: with tmp null it says how many temporary bytes it needs, otherwise it runs.
-// cub_run asks, grows `tmp` and runs (a grown block is recycled through the engine's pool in stream order: no
-// synchronise).  Calls that share a temporary sized up front ask through cub_need -- `bytes`: the call's own answer,
-// `most`: the largest so far -- and run through cub_run_sized, which asks nothing more.
-template <typename Call> int cub_need(size_t &most, size_t &bytes, Call call) {
-    bytes = 0;
-    HIP_TRY(call((void *)nullptr, bytes));
-    most = std::max(most, bytes);
-    return PC_OK;
-}
-template <typename Tmp, typename Call> int cub_run_sized(Tmp &tmp, size_t bytes, Call call) {
-    HIP_TRY(call((void *)tmp.p, bytes));
-    return PC_OK;
-}
-template <typename Tmp, typename Call> int cub_run(Tmp &tmp, Call call) {
-    size_t most = 16, bytes = 0;
-    PC_TRY(cub_need(most, bytes, call));
-    PC_TRY(tmp.reserve(most));
-    return cub_run_sized(tmp, bytes, call);
-}
 
 // The decoder's experiment and test switches, read at the top of every open (the tests flip them between opens on one engine).
 struct BamKnobs {
@@ -516,7 +476,7 @@ int filter_regions(BamDecode &d, const BamSpan &span, int64_t nrec, ColumnWork &
     hipStream_t st = d.st;
     const size_t nr = (size_t)std::max(span.nreg, 0);
     int rc = w.d_rtid.upload(span.tid, nr, st);
-    if (rc == PC_OK) rc = w.d_rbe.reserve(2 * std::max<size_t>(nr, 1));
+    room(rc, w.d_rbe, 2 * std::max<size_t>(nr, 1));
     if (rc != PC_OK) return rc;
     if (nr) {
         HIP_TRY(hipMemcpyAsync(w.d_rbe.p, span.beg, nr * 8, hipMemcpyHostToDevice, st));
@@ -543,11 +503,12 @@ int place_records(BamDecode &d, const BamHeader &h, const BamRecords &recs, bool
     HIP_TRY(hipMemsetAsync(t.d_placed.p + nrec, 0, 4, st));
     HIP_TRY(hipMemsetAsync(w.d_runs.p + nrec, 0, 4, st));
     hipLaunchKernelGGL(k_bam_scan_inputs, dim3((unsigned)((nrec + 256 * kScanInputsPerThread - 1) / (256 * kScanInputsPerThread))), dim3(256), 0, st, t.d_recs.p, nrec, t.d_placed.p, w.d_runs.p, t.d_misc.p + 1);
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, t.d_placed.p, w.d_staged_at.p, (int)(nrec + 1), st));
-    PC_TRY(d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, t.d_placed.p, w.d_staged_at.p, (int)(nrec + 1), st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, w.d_runs.p, w.d_run_at.p, (int)(nrec + 1), st));
+    auto sum = [=](uint32_t *from, uint32_t *to) { return [=](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, from, to, (int)(nrec + 1), st); }; };
+    size_t most = 16, tmp_bytes = 0;
+    PC_TRY(cub_need(most, tmp_bytes, sum(t.d_placed.p, w.d_staged_at.p)));
+    PC_TRY(d_tmp.reserve(most));
+    PC_TRY(cub_run_sized(d_tmp, tmp_bytes, sum(t.d_placed.p, w.d_staged_at.p)));
+    PC_TRY(cub_run_sized(d_tmp, tmp_bytes, sum(w.d_runs.p, w.d_run_at.p)));
     if (t.disorder) {
         const int key_bits = sort_key_bits(h.n_ref);
         int rc = PC_OK;
@@ -557,16 +518,13 @@ int place_records(BamDecode &d, const BamHeader &h, const BamRecords &recs, bool
         // (double buffers: the passes go back and forth between the two halves, and the sort says which half holds the result)
         hipcub::DoubleBuffer<uint64_t> keys(t.d_key.p, d_key2.p);
         hipcub::DoubleBuffer<uint32_t> vals(t.d_idx.p, d_idx2.p);
-        size_t sort_bytes = 0;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, vals, (int)nrec, 0, key_bits, st));
-        PC_TRY(d_sort_tmp.reserve(std::max<size_t>(sort_bytes, 16)));
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, sort_bytes, keys, vals, (int)nrec, 0, key_bits, st));
+        PC_TRY(cub_run(d_sort_tmp, [&](void *tmp, size_t &bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, vals, (int)nrec, 0, key_bits, st); }));
         const uint32_t *perm = vals.Current();
         b.file_order.swap(perm == t.d_idx.p ? t.d_idx : d_idx2);   // (the permutation is the staged records' numbers in the file)
         HIP_TRY(hipMemsetAsync(d_runs_sorted.p + nrec, 0, 4, st));
         hipLaunchKernelGGL(k_bam_sort_rank, dim3(t.g256), dim3(256), 0, st, t.d_recs.p, nrec, perm, w.d_staged_at.p, d_runs_sorted.p, t.d_misc.p, t.d_misc.p + 4);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_runs_sorted.p, d_runs_sorted.p, (int)(nrec + 1), st));   // (in place)
+        PC_TRY(cub_run_sized(d_tmp, tmp_bytes, sum(d_runs_sorted.p, d_runs_sorted.p)));   // (in place)
         hipLaunchKernelGGL(k_bam_sort_run_at, dim3(t.g256), dim3(256), 0, st, perm, d_runs_sorted.p, nrec, w.d_run_at.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(t.sev.ev[3], st));
@@ -617,11 +575,12 @@ int collect_wide(BamDecode &d, int64_t nrec, ColumnWork &w, pc_bam &b) {
     DevBuf<uint8_t> d_tmp;
     DrainOnExit drained{st};
     PC_TRY(d_wsum.reserve((size_t)n_staged + 1));
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, w.d_wide.p, d_wsum.p, (int)std::max<int64_t>(n_staged, 1), st));
-    PC_TRY(d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
+    auto sum_wide = [&](int64_t cnt) { return [&, cnt](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, w.d_wide.p, d_wsum.p, (int)cnt, st); }; };
+    size_t most = 16, tmp_bytes = 0;
+    PC_TRY(cub_need(most, tmp_bytes, sum_wide(std::max<int64_t>(n_staged, 1))));
+    PC_TRY(d_tmp.reserve(most));
     if (n_staged > 0) {
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, w.d_wide.p, d_wsum.p, (int)n_staged, st));
+        PC_TRY(cub_run_sized(d_tmp, tmp_bytes, sum_wide(n_staged)));
         HIP_TRY(hipMemcpyAsync(&last_sum, d_wsum.p + (n_staged - 1), 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipMemcpyAsync(&last_flag, w.d_wide.p + (n_staged - 1), 4, hipMemcpyDeviceToHost, st));
     }
@@ -730,16 +689,15 @@ int index_keys_and_stats(BamDecode &d, const BamPlan &pl, const BamHeader &h, co
     hipLaunchKernelGGL(k_idx_heads, dim3(w.g256p), dim3(256), 0, st, w.d_key.p, nrec, w.d_head.p, w.d_ref_fl.p, w.d_ref_fl.p + nr);
     HIP_TRY(hipGetLastError());
     {
-        size_t a = 0, b = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, a, w.d_head.p, w.d_slot.p, (int)n1, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, b, w.d_cov.p, w.d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st));
-        size_t tmp_bytes = std::max<size_t>(std::max(a, b), 16);
-        PC_TRY(d_tmp.reserve(tmp_bytes));
-        a = b = tmp_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, a, w.d_head.p, w.d_slot.p, (int)n1, st));
-        a = tmp_bytes;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, a, w.d_mapped.p, w.d_mapped_before.p, (int)n1, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveScan(d_tmp.p, b, w.d_cov.p, w.d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st));
+        auto sum = [=](uint32_t *from, uint32_t *to) { return [=](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, from, to, (int)n1, st); }; };
+        auto max_cov = [&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveScan(tmp, bytes, w.d_cov.p, w.d_covered.p, hipcub::Max(), (uint64_t)0, (int)n1, st); };
+        size_t most = 16, asked = 0;   // (one temporary for the three: each runs with all of it)
+        PC_TRY(cub_need(most, asked, sum(w.d_head.p, w.d_slot.p)));
+        PC_TRY(cub_need(most, asked, max_cov));
+        PC_TRY(d_tmp.reserve(most));
+        PC_TRY(cub_run_sized(d_tmp, most, sum(w.d_head.p, w.d_slot.p)));
+        PC_TRY(cub_run_sized(d_tmp, most, sum(w.d_mapped.p, w.d_mapped_before.p)));
+        PC_TRY(cub_run_sized(d_tmp, most, max_cov));
     }
     int rc = PC_OK;
     room(rc, w.d_ref_be, 2 * nr); room(rc, w.d_ref_cnt, 2 * nr); room(rc, w.d_n_intv, nr);
@@ -800,10 +758,7 @@ int index_sort_runs(BamDecode &d, const BamRecords &recs, int n_ref, const Index
     std::iota(iota.begin(), iota.end(), 0u);
     HIP_TRY(hipMemcpyAsync(d_order.p, iota.data(), (size_t)n_runs * 4, hipMemcpyHostToDevice, st));
     const int key_bits = bh::index_key_bits((uint64_t)n_ref);
-    size_t sort_bytes = 0;
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st));
-    PC_TRY(d_sort_tmp.reserve(std::max<size_t>(sort_bytes, 16)));
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_sort_tmp.p, sort_bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st));
+    PC_TRY(cub_run(d_sort_tmp, [&](void *tmp, size_t &bytes) { return hipcub::DeviceRadixSort::SortPairs(tmp, bytes, d_run_key.p, d_run_key2.p, d_order.p, d_order2.p, (int)n_runs, 0, key_bits, st); }));
     hipLaunchKernelGGL(k_idx_gather, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, d_run_key2.p, d_order2.p, d_run_beg.p, d_run_end.p, n_runs,
                        w.d_stid.p, w.d_sbin.p, w.d_sbeg.p, w.d_send.p);
     HIP_TRY(hipGetLastError());
@@ -828,10 +783,7 @@ int index_windows(BamDecode &d, int64_t nrec, int n_ref, const IndexShape &shape
         if (n_lin) {
             hipLaunchKernelGGL(k_idx_first_window, dim3((unsigned)((n_ref + 255) / 256)), dim3(256), 0, st, n_ref, w.d_n_intv.p, w.d_lin_base.p, w.d_ref_be.p, w.d_linear.p);
             HIP_TRY(hipGetLastError());
-            size_t fill_bytes = 0;
-            HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, fill_bytes, w.d_linear.p, w.d_filled.p, hipcub::Max(), (int)n_lin, st));
-            PC_TRY(d_fill_tmp.reserve(std::max<size_t>(fill_bytes, 16)));
-            HIP_TRY(hipcub::DeviceScan::InclusiveScan(d_fill_tmp.p, fill_bytes, w.d_linear.p, w.d_filled.p, hipcub::Max(), (int)n_lin, st));
+            PC_TRY(cub_run(d_fill_tmp, [&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::InclusiveScan(tmp, bytes, w.d_linear.p, w.d_filled.p, hipcub::Max(), (int)n_lin, st); }));
         }
         hipLaunchKernelGGL(k_idx_loff, dim3((unsigned)((n_runs + 255) / 256)), dim3(256), 0, st, w.d_stid.p, w.d_sbin.p, n_runs, shape.n_lvls, w.d_n_intv.p,
                            w.d_lin_base.p, w.d_filled.p, w.d_sloff.p);

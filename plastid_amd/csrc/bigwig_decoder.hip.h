@@ -10,7 +10,7 @@
 // Upload, inflate and Adler-32 are bigwig_load_blocks over a BigWigBlocks, the section pass is bigwig_sections over a
 // BigWigSections: the summary reader (bigwig_summary.hip.h) loads its tables through the same two, and reads the
 // statuses on the host through bigwig_block_words.  bigwig_parse is the prologue of pc_bigwig_info / _blocks.
-// Part of the one translation unit of plastid_counts.hip (behind track_decoder.hip.h).
+// Part of the one translation unit of plastid_counts.hip (behind track_decoder.hip.h; the plumbing is device_util.hip.h).
 #include "bigwig_kernels.hip.h"
 
 namespace {

@@ -6,7 +6,7 @@
 // find it), the items' sections go through the import's bigwig_sections, the records are gathered into file order by
 // this file's kernels, k_bbi_index checks the order and gives the contigs' ranges).  A query groups its rows by
 // table (bigwig_summary_host.h: choose_level) and launches k_bbi_summarize once per table in use.
-// Part of the one translation unit of plastid_counts.hip (behind bigwig_decoder.hip.h, whose helpers it uses).
+// Part of the one translation unit of plastid_counts.hip (behind bigwig_decoder.hip.h, whose helpers it uses; the plumbing is device_util.hip.h).
 #include <memory>
 
 #include "bigwig_summary_kernels.hip.h"

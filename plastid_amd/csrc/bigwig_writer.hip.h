@@ -15,7 +15,7 @@
 //      all trees (bigwig_write_host.h: the container code of the host writer), and the blocks cross PCIe once, straight
 //      into their place in the image -- through the transfer ring when they are large.
 // What is refused is refused before anything is built, and nothing is left behind.
-// Part of the one translation unit of plastid_counts.hip (behind deflate_encoder.hip.h).
+// Part of the one translation unit of plastid_counts.hip (behind deflate_encoder.hip.h; the plumbing is device_util.hip.h).
 #include "bigwig_write_kernels.hip.h"
 #include "bigwig_zoom_kernels.hip.h"
 

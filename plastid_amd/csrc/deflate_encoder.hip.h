@@ -4,7 +4,7 @@
 // back with the offsets and sizes.  The bytes are those of pcdeflate::encode (deflate_host.h).  From slot offsets to
 // compacted streams the work is zlib_encode_stage over a ZlibEncodeStage, which the bigWig writer uses for its data
 // sections and for its zoom blocks (bigwig_writer.hip.h); nothing else calls queue_zlib_deflate.
-// Part of the one translation unit of plastid_counts.hip (behind bigwig_decoder.hip.h).
+// Part of the one translation unit of plastid_counts.hip (behind bigwig_decoder.hip.h; the plumbing is device_util.hip.h).
 #include "deflate_kernels.hip.h"
 
 namespace {

@@ -6,15 +6,22 @@
 // count comes out of a HIP kernel.
 //
 // Host-side structure, in file order:
-//   DevPool / DevBuf / PinnedBuf   device blocks recycled per engine, one page-locked buffer: a plan of
-//                                  one short segment costs API calls, not bytes
-//   TransferRing / scan_contigs      the caller's columns cross PCIe through a ring of page-locked pieces; the
-//                                  contig column stays on the host and becomes ntid + 1 record bounds
-//   pc_add_alignment_file          staging: columns to HBM, then kernels only (stage_kernels.hip.h: validation,
-//                                  8-byte records, run stream, statistics; pc_kernels.hip.h: record stream,
-//                                  side lists, linear-index tables)
+//   device_util.hip.h (included)   the plumbing of this file and of every driver included at its end: fail / HIP_TRY,
+//                                  DevPool / DevBuf / PinnedBuf (device blocks recycled per engine, one page-locked
+//                                  buffer: a plan of one short segment costs API calls, not bytes; the policy is
+//                                  pool_host.h), TransferRing (the caller's columns cross PCIe through a ring of
+//                                  page-locked pieces), room, DrainOnExit / finish_phase, the hipcub seam
+//   StagedFile / pc_engine / pc_plan   what the entry points keep in HBM
+//   plan_build_gpu                 the tables of a large plan as kernels, sorts and scans (plan_kernels.hip.h), phase
+//                                  by phase: upload, segments, islands, pieces + tiles, output pieces, the block;
+//                                  plan_upload for a host-built plan; the center and gather tables on first use
+//   pc_create / pc_destroy         streams, events, the engine's pool
+//   pc_add_alignment_file          staging, phase by phase (stage_file): columns to HBM while the contig column stays on
+//                                  the host and becomes ntid + 1 record bounds (scan_contigs), then kernels only
+//                                  (stage_kernels.hip.h: validation, 8-byte records, run stream, statistics;
+//                                  pc_kernels.hip.h: record stream, side lists, linear-index tables)
 //   pc_plan_create                 segments -> islands -> windows -> output pieces, all tables of a
-//                                  plan in one device block
+//                                  plan in one device block (host builder: plan_host.h; GPU: plan_build_gpu)
 //   pc_count                       k_tile_ranges -> k_hist_point (two classes, two streams) ->
 //                                  k_gather_split, or the three center kernels + k_gather, or -- a '+' / '-' plan
 //                                  under a point rule over a file with a dense vector -- k_dense_gather alone
@@ -56,393 +63,11 @@
 #include "canon_host.h"
 #include "count_host.h"
 #include "dense_host.h"
+#include "device_util.hip.h"
 
 using namespace pc;
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...) {
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t err__ = (expr);                                                                 \
-        if (err__ != hipSuccess)                                                                   \
-            return fail(err__ == hipErrorOutOfMemory ? PC_ERR_NOMEM : PC_ERR_HIP, "%s failed: %s (%s:%d)", \
-                        #expr, hipGetErrorString(err__), __FILE__, __LINE__);                      \
-    } while (0)
-
-#define PC_TRY(expr)                                                                               \
-    do {                                                                                           \
-        const int rc__ = (expr);                                                                   \
-        if (rc__ != PC_OK) return rc__;                                                            \
-    } while (0)
-
-// Device blocks that outlive their engine: an engine that goes away hands the idle blocks of its pool to this
-// process-wide reservoir (per device, by size) instead of freeing them, and the pool of a later engine looks here
-// before it allocates.  Engines come and go -- one per BAMGenomeArray, one per config in bench.py -- and on some
-// boxes of the pool a hipMalloc that follows the hipFree of tens of GB takes SECONDS (measured round 5: 1.5 s and 2.1 s
-// for the first large buffer of a staging call right after an engine of the same size was destroyed; milliseconds when
-// nothing had been freed).  Only blocks of a destroyed engine get here -- its streams are drained by then, so nothing
-// is in flight on them.
-// What is kept is bounded: PC_POOL_RESERVOIR_GB per device (default 4: the tables of a few plans and a small file; a
-// process that cycles through engines of tens of GB -- bench.py -- opts in to more), and when the LAST engine of a device
-// is destroyed everything above that default is freed, so that another library in the process (torch, cupy) finds the
-// HBM this one no longer uses.  pc_release_cached_memory frees all of it.
-struct BigReservoir {
-    static constexpr size_t kDefaultLimit = (size_t)4 << 30;
-    std::mutex m;
-    struct PerDevice { std::map<size_t, std::vector<void *>> big; size_t cached = 0; int engines = 0; };
-    std::map<int, PerDevice> dev;   // keyed by the device id itself (no folding of ids onto a fixed table)
-    size_t limit = kDefaultLimit;
-    BigReservoir() { if (const char *env = getenv("PC_POOL_RESERVOIR_GB")) limit = (size_t)std::max(0ll, atoll(env)) << 30; }
-    static BigReservoir &get() { static BigReservoir *r = new BigReservoir; return *r; }   // (never destroyed: no hipFree during static destruction)
-    void *take(int device, size_t rounded) {
-        std::lock_guard<std::mutex> g(m);
-        PerDevice &d = dev[device];
-        auto it = d.big.find(rounded);
-        if (it == d.big.end() || it->second.empty()) return nullptr;
-        void *p = it->second.back();
-        it->second.pop_back();
-        d.cached -= rounded;
-        return p;
-    }
-    bool give(int device, void *p, size_t rounded) {
-        std::lock_guard<std::mutex> g(m);
-        PerDevice &d = dev[device];
-        if (d.cached + rounded > limit) return false;
-        d.big[rounded].push_back(p);
-        d.cached += rounded;
-        return true;
-    }
-    // largest blocks first until at most `keep` bytes are left
-    void trim_locked(PerDevice &d, size_t keep) {
-        for (auto it = d.big.rbegin(); it != d.big.rend() && d.cached > keep; ++it)
-            while (!it->second.empty() && d.cached > keep) {
-                (void)hipFree(it->second.back());
-                it->second.pop_back();
-                d.cached -= it->first;
-            }
-    }
-    void free_all(int device) {   // (an allocation failed: what is kept here may be what is missing)
-        std::lock_guard<std::mutex> g(m);
-        trim_locked(dev[device], 0);
-        dev[device].big.clear();
-    }
-    void engine_created(int device) { std::lock_guard<std::mutex> g(m); dev[device].engines += 1; }
-    void engine_destroyed(int device) {   // the last one of the device: only the default amount stays
-        std::lock_guard<std::mutex> g(m);
-        PerDevice &d = dev[device];
-        if (--d.engines <= 0) { d.engines = 0; trim_locked(d, std::min(limit, kDefaultLimit)); }
-    }
-};
-
-// Per-engine cache of small device blocks.  A plan of one short segment is otherwise dominated by
-// hipMalloc / hipFree (the latter synchronises the device): blocks up to 32 MiB are kept by
-// power-of-two size class when a plan lets go of them and handed to the next one.  Every user of
-// one pool enqueues on the same engine stream, so a recycled block is ordered after its last use.  (The one exception,
-// the transfer ring's own stream, synchronises the engine stream before it touches pooled blocks: stage_upload.)
-struct DevPool {
-    static constexpr int kMinShift = 8, kClasses = 18;   // 256 B .. 32 MiB
-    static constexpr size_t kMaxCached = (size_t)512 << 20;
-    // Large blocks (> 32 MiB: the arrays of a staged file, the scratch of the BAM decoder) are kept too, by size rounded
-    // up to a quarter of a power of two, up to kBigLimit in all: on some hosts a hipMalloc / hipFree pair of a few
-    // hundred MB takes tens of milliseconds (measured: 60 ms per call on one box of the pool, < 1 ms on others), which a
-    // caller that stages file after file -- or the same file again -- would pay every time.
-    static constexpr size_t kBigLimit = (size_t)64 << 30;
-    std::mutex m;
-    std::vector<void *> bins[kClasses];
-    size_t cached = 0;
-    std::map<size_t, std::vector<void *>> big;
-    size_t big_cached = 0;
-    int device = 0;
-    static int size_class(size_t bytes) {
-        int c = 0;
-        while (c < kClasses && ((size_t)1 << (kMinShift + c)) < bytes) ++c;
-        return c;   // kClasses: too large to pool
-    }
-    static size_t class_bytes(int c) { return (size_t)1 << (kMinShift + c); }
-    static size_t big_round(size_t bytes) {
-        const int k = 63 - __builtin_clzll((unsigned long long)bytes);
-        const size_t step = (size_t)1 << (k - 2);
-        return (bytes + step - 1) / step * step;
-    }
-    void *take(int c) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            if (!bins[c].empty()) {
-                void *p = bins[c].back();
-                bins[c].pop_back();
-                cached -= class_bytes(c);
-                return p;
-            }
-        }
-        return BigReservoir::get().take(device, class_bytes(c));
-    }
-    bool give(void *p, int c) {
-        std::lock_guard<std::mutex> g(m);
-        if (cached + class_bytes(c) > kMaxCached) return false;
-        bins[c].push_back(p);
-        cached += class_bytes(c);
-        return true;
-    }
-    void *big_take(size_t rounded) {
-        {
-            std::lock_guard<std::mutex> g(m);
-            auto it = big.find(rounded);
-            if (it != big.end() && !it->second.empty()) {
-                void *p = it->second.back();
-                it->second.pop_back();
-                big_cached -= rounded;
-                return p;
-            }
-        }
-        return BigReservoir::get().take(device, rounded);
-    }
-    bool big_give(void *p, size_t rounded) {
-        std::lock_guard<std::mutex> g(m);
-        if (big_cached + rounded > kBigLimit) return false;
-        big[rounded].push_back(p);
-        big_cached += rounded;
-        return true;
-    }
-    // keep_big: the engine is going away with its streams drained -- its blocks go to the process-wide reservoir
-    void drain(bool keep_big) {
-        std::lock_guard<std::mutex> g(m);
-        for (int c = 0; c < kClasses; ++c) {
-            for (void *p : bins[c])
-                if (!keep_big || !BigReservoir::get().give(device, p, class_bytes(c))) (void)hipFree(p);
-            bins[c].clear();
-        }
-        cached = 0;
-        for (auto &kv : big)
-            for (void *p : kv.second)
-                if (!keep_big || !BigReservoir::get().give(device, p, kv.first)) (void)hipFree(p);
-        big.clear();
-        big_cached = 0;
-        if (!keep_big) BigReservoir::get().free_all(device);
-    }
-    ~DevPool() { drain(true); }
-};
-
-// The pool a DevBuf without one of its own takes its blocks from: set for the duration of an entry point that
-// allocates on behalf of an engine (staging, the BAM decoder), so that every buffer made there -- temporaries and the
-// arrays a staged file keeps -- is recycled through that engine's pool.  (All users of one pool enqueue on its engine's
-// streams in an order the entry points fix with events, so a recycled block is ordered after its last use.)
-static thread_local DevPool *tls_pool = nullptr;
-struct PoolScope {
-    DevPool *prev;
-    explicit PoolScope(DevPool *p) : prev(tls_pool) { tls_pool = p; }
-    ~PoolScope() { tls_pool = prev; }
-};
-
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    DevPool *pool = nullptr;   // set: blocks come from / return to this pool
-    int pool_class = -1;       // size class of the current block, -1: plain hipMalloc, -2: a large block of `big_bytes`
-    size_t big_bytes = 0;
-    ~DevBuf() { release(); }
-    void release() {
-        if (p) {
-            bool kept = false;
-            if (pool && pool_class >= 0) kept = pool->give(p, pool_class);
-            else if (pool && pool_class == -2) kept = pool->big_give(p, big_bytes);
-            if (!kept) (void)hipFree(p);
-        }
-        p = nullptr;
-        cap = 0;
-        pool_class = -1;
-        big_bytes = 0;
-    }
-    int reserve(size_t n) {
-        if (n <= cap) return PC_OK;
-        release();
-        if (n == 0) return PC_OK;
-        if (!pool) pool = tls_pool;
-        if (pool) {
-            const int c = DevPool::size_class(n * sizeof(T));
-            if (c < DevPool::kClasses) {
-                void *q = pool->take(c);
-                if (!q && hipMalloc(&q, DevPool::class_bytes(c)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    pool->drain(false);   // (what the pool and the reservoir hold may be what is missing)
-                    HIP_TRY(hipMalloc(&q, DevPool::class_bytes(c)));
-                }
-                p = (T *)q;
-                cap = DevPool::class_bytes(c) / sizeof(T);
-                pool_class = c;
-                return PC_OK;
-            }
-            const size_t rounded = DevPool::big_round(n * sizeof(T));
-            void *q = pool->big_take(rounded);
-            if (!q && hipMalloc(&q, rounded) != hipSuccess) {
-                (void)hipGetLastError();
-                pool->drain(false);   // (what the pool and the reservoir hold may be what is missing)
-                HIP_TRY(hipMalloc(&q, rounded));
-            }
-            p = (T *)q;
-            cap = rounded / sizeof(T);
-            pool_class = -2;
-            big_bytes = rounded;
-            return PC_OK;
-        }
-        if (hipMalloc((void **)&p, n * sizeof(T)) != hipSuccess) {   // (no pool of its own: the reservoir of the current device may hold what is missing)
-            (void)hipGetLastError();
-            p = nullptr;
-            int dev_now = 0;
-            if (hipGetDevice(&dev_now) == hipSuccess) BigReservoir::get().free_all(dev_now);
-            HIP_TRY(hipMalloc((void **)&p, n * sizeof(T)));
-        }
-        cap = n;
-        return PC_OK;
-    }
-    int upload(const T *src, size_t n, hipStream_t s) {
-        PC_TRY(reserve(n));
-        if (n) HIP_TRY(hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, s));
-        return PC_OK;
-    }
-    int upload(const std::vector<T> &v, hipStream_t s) { return upload(v.data(), v.size(), s); }
-    void swap(DevBuf &o) {
-        std::swap(p, o.p); std::swap(cap, o.cap); std::swap(pool, o.pool); std::swap(pool_class, o.pool_class); std::swap(big_bytes, o.big_bytes);
-    }
-};
-
-// Page-locked host buffer that only grows.
-struct PinnedBuf {
-    uint8_t *p = nullptr;
-    size_t cap = 0;
-    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
-    int reserve(size_t n) {
-        if (n <= cap) return PC_OK;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; cap = 0;
-        const size_t want = std::max<size_t>(n + n / 2, 512 * 1024);   // covers every short read-back (kSmallRead) from the start
-        HIP_TRY(hipHostMalloc((void **)&p, want, hipHostMallocDefault));
-        cap = want;
-        return PC_OK;
-    }
-};
-
-// A typed window into a block some DevBuf owns (the tables of a plan share one block and one upload).
-template <typename T> struct DevView {
-    T *p = nullptr;
-};
-
-// Caller-owned (pageable) host arrays <-> HBM at the rate of the PCIe link.  hipMemcpy to or from pageable memory pins
-// the pages on the fly, on one thread inside the driver: 25 GB/s for memory the runtime has not seen before, whatever
-// the number of calling threads or streams (scripts/ubench/upload_probe.hip; 57 GB/s from page-locked memory on the
-// same box).  Here a few host threads move pieces of the arrays through a ring of page-locked slots, each piece with a
-// DMA of its own: 53 - 55 GB/s.  Up: a thread takes the next piece, waits until its slot's previous piece has landed,
-// copies the piece into the slot and queues the DMA.  Down: it queues the DMA into the slot, waits for it and copies the
-// piece out.  Pieces are taken in order and there are more slots than threads, so nobody waits on a piece that has not
-// been taken.
-struct TransferJob { void *dst; const void *src; size_t bytes; };
-struct TransferRing {
-    static constexpr int kSlots = 12, kThreadsUp = 6, kThreadsDown = 10;   // (down: the destination's pages are often touched for the first time)
-    static constexpr size_t kPiece = (size_t)16 << 20;
-    uint8_t *slot[kSlots] = {};
-    hipEvent_t ev[kSlots] = {};
-    hipStream_t stream = nullptr;
-    std::mutex busy;   // one transfer at a time per device
-    // One ring per device for the life of the process: page-locking its 192 MB costs as much as staging ten million
-    // records, and engines come and go (one per BAMGenomeArray).
-    static TransferRing &of(int device) {
-        static std::mutex m;
-        static std::map<int, TransferRing *> *rings = new std::map<int, TransferRing *>;   // (never destroyed: no HIP call during static destruction)
-        std::lock_guard<std::mutex> g(m);
-        TransferRing *&r = (*rings)[device];
-        if (!r) r = new TransferRing;
-        return *r;
-    }
-    // every job has landed when this returns; `down`: dst is host memory, src device memory.
-    // Small transfers take the runtime's own path (`always`: the ring whatever the size)
-    int run(int device, const std::vector<TransferJob> &jobs, size_t piece, bool always, bool down = false) {
-        std::lock_guard<std::mutex> one(busy);
-        HIP_TRY(hipSetDevice(device));
-        if (!stream) HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        size_t total = 0;
-        for (const auto &j : jobs) total += j.bytes;
-        if (total == 0) return PC_OK;
-        const hipMemcpyKind kind = down ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
-        if (total < 4 * kPiece && !always) {
-            for (const auto &j : jobs)
-                if (j.bytes) HIP_TRY(hipMemcpyAsync(j.dst, j.src, j.bytes, kind, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            return PC_OK;
-        }
-        piece = std::max<size_t>(1, std::min(piece, kPiece));
-        std::vector<TransferJob> pieces;
-        for (const auto &j : jobs) {
-            if (j.bytes == 0) continue;
-            // host memory that is page-locked already (hipHostMalloc, hipHostRegister, a pinned torch tensor) needs no ring
-            hipPointerAttribute_t attr;
-            const void *host_side = down ? j.dst : j.src;
-            if (!always && hipPointerGetAttributes(&attr, host_side) == hipSuccess && attr.type == hipMemoryTypeHost) {
-                HIP_TRY(hipMemcpyAsync(j.dst, j.src, j.bytes, kind, stream));
-                continue;
-            }
-            (void)hipGetLastError();   // (an ordinary pointer: some runtimes report it as an error)
-            for (size_t off = 0; off < j.bytes; off += piece)
-                pieces.push_back({(uint8_t *)j.dst + off, (const uint8_t *)j.src + off, std::min(piece, j.bytes - off)});
-        }
-        const size_t np = pieces.size();
-        for (int k = 0; k < kSlots && np > 0; ++k) {
-            if (!slot[k]) HIP_TRY(hipHostMalloc((void **)&slot[k], kPiece, hipHostMallocDefault));
-            if (!ev[k]) HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
-        }
-        std::unique_ptr<std::atomic<uint8_t>[]> done(new std::atomic<uint8_t>[np]);   // up: DMA queued; down: copied out
-        for (size_t k = 0; k < np; ++k) done[k].store(0, std::memory_order_relaxed);
-        std::atomic<size_t> next{0};
-        std::atomic<int> failed{0};
-        std::mutex order;   // DMA and event of a piece are queued together
-        auto work = [&]() {
-            if (hipSetDevice(device) != hipSuccess) failed.store(1);
-            for (;;) {
-                const size_t p = next.fetch_add(1);
-                if (p >= np) return;
-                const int k = (int)(p % kSlots);
-                if (p >= (size_t)kSlots) {   // the slot's previous piece
-                    while (!done[p - kSlots].load(std::memory_order_acquire)) std::this_thread::yield();
-                    if (!down && !failed.load() && hipEventSynchronize(ev[k]) != hipSuccess) failed.store(1);
-                }
-                if (!failed.load()) {
-                    if (!down) std::memcpy(slot[k], pieces[p].src, pieces[p].bytes);
-                    {
-                        std::lock_guard<std::mutex> lk(order);
-                        if (hipMemcpyAsync(down ? (void *)slot[k] : pieces[p].dst, down ? pieces[p].src : (const void *)slot[k], pieces[p].bytes, kind, stream) != hipSuccess ||
-                            hipEventRecord(ev[k], stream) != hipSuccess)
-                            failed.store(1);
-                    }
-                    if (down && !failed.load()) {
-                        if (hipEventSynchronize(ev[k]) != hipSuccess) failed.store(1);
-                        else std::memcpy(pieces[p].dst, slot[k], pieces[p].bytes);
-                    }
-                }
-                done[p].store(1, std::memory_order_release);   // (also after a failure: whoever waits for this slot goes on and ends)
-            }
-        };
-        int T = down ? kThreadsDown : kThreadsUp;
-        if (const char *env = getenv("PC_STAGE_UPLOAD_THREADS")) T = std::max(1, std::min(kSlots - 1, atoi(env)));
-        T = (int)std::min<size_t>((size_t)T, np);
-        std::vector<std::thread> th;
-        for (int t = 1; t < T; ++t) th.emplace_back(work);
-        if (np > 0) work();
-        for (auto &x : th) x.join();
-        const hipError_t he = hipStreamSynchronize(stream);
-        if (failed.load() || he != hipSuccess) { (void)hipGetLastError(); return fail(PC_ERR_HIP, "transfer ring: a copy failed"); }
-        return PC_OK;
-    }
-};
 
 static int stage_threads(int64_t n) {
     int t = std::min(usable_cpus(), 32);
@@ -886,184 +511,249 @@ struct PlanBlockLayout {
     }
 };
 
-// The tables of a plan, built on the GPU.  `p` arrives with nseg / out_elems / rows set; on PC_OK it has its tables in
-// HBM (d_tables and the views into it), the sizes and flags the host builder sets, and no host copies.
-int plan_build_gpu(pc_engine *e, pc_plan *p, int64_t nseg, const int32_t *tid, const int64_t *start, const int64_t *end, const uint8_t *strand,
-                   const int64_t *out_off, const int8_t *out_step, const int64_t *row_stride, int64_t out_elems, int rows) {
-    using namespace pcplan;
-    hipStream_t st = e->stream;
-    const int ntid = e->ntid;
-    const size_t n = (size_t)nseg;
-    StageClock pclk;
-    // ---- the caller's arrays
-    const PlanInputLayout L(n);
-    int rc = p->d_inputs.reserve(std::max<size_t>(L.bytes, 256));
-    if (rc == PC_OK) rc = p->d_gsegs_own.reserve(std::max<size_t>(n, 1));
-    if (rc != PC_OK) return rc;
-    uint8_t *di = p->d_inputs.p;
-    HIP_TRY(hipMemcpyAsync(di + L.at_tid, tid, n * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(di + L.at_start, start, n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(di + L.at_end, end, n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(di + L.at_strand, strand, n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(di + L.at_off, out_off, n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(di + L.at_step, out_step, n, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(di + L.at_stride, row_stride, n * 8, hipMemcpyHostToDevice, st));
-    SegIn in;
-    in.tid = (const int32_t *)(di + L.at_tid); in.start = (const int64_t *)(di + L.at_start); in.end = (const int64_t *)(di + L.at_end);
-    in.strand = di + L.at_strand; in.out_off = (const int64_t *)(di + L.at_off); in.out_step = (const int8_t *)(di + L.at_step);
-    in.row_stride = (const int64_t *)(di + L.at_stride);
-    pclk.lap("plan(gpu): upload");
-    // ---- stage A: per segment
+// ---- the tables of a plan, built on the GPU, phase by phase.  What the phases share beside the engine and the plan:
+// the caller's arrays in HBM, the counters block and its host copy, the working arrays of the three stages -- A per
+// segment, B per piece, C per output piece, each carved from one scratch block of the engine with the temporary of
+// its scans and sorts at the end -- and the counts the read-backs bring.
+struct PlanBuild {
     typedef unsigned long long u64;
-    size_t cub_a = 0;
-    {
-        size_t b = 0;
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const u64 *)nullptr, (u64 *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, 0, 64, st); cub_a = std::max(cub_a, b);
-        (void)hipcub::DeviceScan::InclusiveScan(nullptr, b, (const u64 *)nullptr, (u64 *)nullptr, GroupMax(), (int)n, st); cub_a = std::max(cub_a, b);
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const int64_t *)nullptr, (int64_t *)nullptr, (int)n + 1, st); cub_a = std::max(cub_a, b);
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st); cub_a = std::max(cub_a, b);
-    }
-    Bump A;
+    pc_engine *e;
+    pc_plan *p;
+    const PlanSegments &segs;   // the caller's host arrays
+    int64_t out_elems;
+    int rows;
+    hipStream_t st;
+    int ntid;
+    size_t n;
+    unsigned gseg;              // blocks of a per-segment kernel
+    StageClock pclk;
+    pcplan::SegIn in;
+    pcplan::Misc h, *misc = nullptr;
+    Bump A, B, C;
+    size_t cub_a = 0, cub_b = 0, cub_c = 0;
+    uint8_t *cub_tmp = nullptr, *cub_tmp_b = nullptr, *cub_tmp_c = nullptr;
     u64 *keys = nullptr, *keys2 = nullptr, *ge = nullptr, *pm = nullptr, *island_keys = nullptr;
     uint32_t *ends = nullptr, *ends2 = nullptr, *flags = nullptr, *before = nullptr, *npieces = nullptr, *piece_at = nullptr, *nout = nullptr, *out_at = nullptr;
-    Island *islands = nullptr;
+    pcplan::Island *islands = nullptr;
     int64_t *lens = nullptr, *offs = nullptr;
-    Misc *misc = nullptr;
-    uint8_t *cub_tmp = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {   // (first pass: sizes)
-        A.used = 0;
-        misc = A.take<Misc>(1);
-        keys = A.take<u64>(n); keys2 = A.take<u64>(n); ends = A.take<uint32_t>(n); ends2 = A.take<uint32_t>(n);
-        ge = A.take<u64>(n); pm = A.take<u64>(n); flags = A.take<uint32_t>(n + 1); before = A.take<uint32_t>(n + 1);
-        islands = A.take<Island>(n); island_keys = A.take<u64>(n); lens = A.take<int64_t>(n + 1); offs = A.take<int64_t>(n + 1);
-        npieces = A.take<uint32_t>(n + 1); piece_at = A.take<uint32_t>(n + 1); nout = A.take<uint32_t>(n + 1); out_at = A.take<uint32_t>(n + 1);
-        cub_tmp = A.take<uint8_t>(cub_a + 256);
-        if (pass == 0) {
-            PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
-            A.base = e->plan_scratch[0].p;
-        }
-    }
-    const unsigned gseg = (unsigned)((n + 255) / 256);
-    Misc h;
-    std::memset(&h, 0, sizeof(h));
-    h.first_bad = ~0ull;
-    h.max_slots = 1;
-    HIP_TRY(hipMemcpyAsync(misc, &h, sizeof(h), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_plan_segs, dim3(gseg), dim3(256), 0, st, in, nseg, ntid, rows, out_elems, p->d_gsegs_own.p, keys, ends, misc);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h, misc, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (h.first_bad != ~0ull) {   // the defect of the lowest segment index, as a serial pass reports it
-        PlanDefect bad = {(int)(h.first_bad & 0xffu), (int64_t)(h.first_bad >> 8), 0, 0};
-        if (bad.kind == kDefectSlice) plan_slice_bounds({nseg, tid, start, end, strand, out_off, out_step, row_stride}, bad.seg, rows, &bad.lo, &bad.hi);
-        return fail(PC_ERR_ARG, "%s", plan_defect_message(bad, out_elems).c_str());
-    }
-    p->modes = h.modes;
-    p->covered = (int64_t)h.covered;
-    p->has_sums = h.has_sums != 0;
-    if (!plan_window(rows, h.modes, h.n_iv, h.iv_len, e->knobs.tile_g, &p->G))
-        return fail(PC_ERR_ARG, "%s", plan_defect_message({kDefectRows, 0, rows, 0}, out_elems).c_str());
-    const int G = p->G;
-    const int split_modes = rows > 1 ? 1 : 0;
-    const size_t n_iv = (size_t)h.n_iv;
-    pclk.lap("plan(gpu): segments");
-    if (n_iv) {
-        const unsigned giv = (unsigned)((n_iv + 255) / 256);
-        size_t b = cub_a;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub_tmp, b, keys, keys2, ends, ends2, (int)n, 0, std::min(64, 33 + bits_for((uint64_t)ntid)), st));
-        hipLaunchKernelGGL(k_group_ends, dim3(giv), dim3(256), 0, st, keys2, ends2, misc, ge);
-        b = cub_a;
-        HIP_TRY(hipcub::DeviceScan::InclusiveScan(cub_tmp, b, ge, pm, GroupMax(), (int)n_iv, st));
-        hipLaunchKernelGGL(k_island_flags, dim3(giv), dim3(256), 0, st, keys2, pm, misc, flags, (int64_t)n_iv);
-        b = cub_a;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub_tmp, b, flags, before, (int)n_iv, st));
-        hipLaunchKernelGGL(k_island_fill, dim3(giv), dim3(256), 0, st, keys2, pm, flags, before, misc, islands, island_keys);
-        hipLaunchKernelGGL(k_island_lens, dim3(giv), dim3(256), 0, st, misc, islands, lens, npieces, G, (int64_t)n_iv);
-        b = cub_a;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub_tmp, b, lens, offs, (int)n_iv, st));
-        b = cub_a;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub_tmp, b, npieces, piece_at, (int)n_iv, st));
-        hipLaunchKernelGGL(k_island_offsets, dim3(giv), dim3(256), 0, st, misc, islands, offs, lens, piece_at, npieces);
-    }
-    if (n) {
-        hipLaunchKernelGGL(k_seg_island, dim3(gseg), dim3(256), 0, st, in, nseg, p->d_gsegs_own.p, misc, islands, island_keys, nout, G);
-        size_t b = cub_a;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub_tmp, b, nout, out_at, (int)n, st));
-        hipLaunchKernelGGL(k_out_total, dim3(1), dim3(64), 0, st, misc, out_at, nout, nseg);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h, misc, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    p->npos = (int64_t)h.npos;
-    p->out_needs_zero = h.needs_zero != 0;
-    const size_t n_pieces = h.n_pieces, n_op = h.n_opieces;
-    if (n_pieces >= 0x7fffffffu || n_op >= 0x7fffffffu) return fail(PC_ERR_ARG, "pc_plan_create: too many window pieces");
-    pclk.lap("plan(gpu): islands");
-    // ---- stage B: per piece; stage C: per output piece
-    size_t cub_b = 0, cub_c = 0;
-    {
-        size_t b = 0;
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const u64 *)nullptr, (u64 *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n_pieces, 0, 64, st); cub_b = std::max(cub_b, b);
-        (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n_pieces + 1, st); cub_b = std::max(cub_b, b);
-        (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n_op, 0, 32, st); cub_c = std::max(cub_c, b);
-    }
-    Bump B, C;
     u64 *pkeys = nullptr, *pkeys2 = nullptr, *tile_keys = nullptr;
     uint32_t *pidx = nullptr, *pidx2 = nullptr, *new_tile = nullptr, *tbefore = nullptr, *otile = nullptr, *otile2 = nullptr, *oidx = nullptr, *oidx2 = nullptr;
     Piece *praw = nullptr, *psorted = nullptr;
     Tile *tiles_tmp = nullptr;
     OutPiece *oraw = nullptr;
-    uint8_t *cub_tmp_b = nullptr, *cub_tmp_c = nullptr;
-    for (int pass = 0; pass < 2; ++pass) {
-        B.used = 0; C.used = 0;
-        pkeys = B.take<u64>(n_pieces); pkeys2 = B.take<u64>(n_pieces); pidx = B.take<uint32_t>(n_pieces); pidx2 = B.take<uint32_t>(n_pieces);
-        praw = B.take<Piece>(n_pieces); psorted = B.take<Piece>(n_pieces); new_tile = B.take<uint32_t>(n_pieces + 1); tbefore = B.take<uint32_t>(n_pieces + 1);
-        tiles_tmp = B.take<Tile>(n_pieces); tile_keys = B.take<u64>(n_pieces); cub_tmp_b = B.take<uint8_t>(cub_b + 256);
-        oraw = C.take<OutPiece>(n_op); otile = C.take<uint32_t>(n_op); otile2 = C.take<uint32_t>(n_op); oidx = C.take<uint32_t>(n_op); oidx2 = C.take<uint32_t>(n_op);
-        cub_tmp_c = C.take<uint8_t>(cub_c + 256);
+    int G = 0, split_modes = 0;
+    size_t n_iv = 0, n_pieces = 0, n_op = 0, n_tiles = 0;
+    PlanBuild(pc_engine *eng, pc_plan *plan, const PlanSegments &s, int64_t oe, int r)
+        : e(eng), p(plan), segs(s), out_elems(oe), rows(r), st(eng->stream), ntid(eng->ntid), n((size_t)s.n), gseg((unsigned)(((size_t)s.n + 255) / 256)) {}
+    // The scans and sorts as `call(tmp, bytes)` (cub_need / cub_run_sized).  A stage asks at an upper bound before its
+    // arrays are carved (the pointers are read when the call runs) and runs at the count a read-back brought.
+    auto sort_segs(int end_bit) { return [this, end_bit](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, keys, keys2, ends, ends2, (int)n, 0, end_bit, st); }; }
+    auto max_ends(size_t cnt) { return [this, cnt](void *t, size_t &b) { return hipcub::DeviceScan::InclusiveScan(t, b, ge, pm, pcplan::GroupMax(), (int)cnt, st); }; }
+    template <typename T> auto sum(T *PlanBuild::*from, T *PlanBuild::*to, size_t cnt) {
+        return [this, from, to, cnt](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, this->*from, this->*to, (int)cnt, st); };
+    }
+    auto sort_pieces(int end_bit) { return [this, end_bit](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, pkeys, pkeys2, pidx, pidx2, (int)n_pieces, 0, end_bit, st); }; }
+    auto sort_out(int end_bit) { return [this, end_bit](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, otile, otile2, oidx, oidx2, (int)n_op, 0, end_bit, st); }; }
+    int read_misc() {   // what the phase queued so far, then the counters
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&h, misc, sizeof(h), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return PC_OK;
+    }
+};
+
+int plan_upload_inputs(PlanBuild &x) {
+    pc_plan *p = x.p;
+    hipStream_t st = x.st;
+    const size_t n = x.n;
+    const PlanInputLayout L(n);
+    int rc = p->d_inputs.reserve(std::max<size_t>(L.bytes, 256));
+    room(rc, p->d_gsegs_own, std::max<size_t>(n, 1));
+    if (rc != PC_OK) return rc;
+    uint8_t *di = p->d_inputs.p;
+    HIP_TRY(hipMemcpyAsync(di + L.at_tid, x.segs.tid, n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(di + L.at_start, x.segs.start, n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(di + L.at_end, x.segs.end, n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(di + L.at_strand, x.segs.strand, n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(di + L.at_off, x.segs.out_off, n * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(di + L.at_step, x.segs.out_step, n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(di + L.at_stride, x.segs.row_stride, n * 8, hipMemcpyHostToDevice, st));
+    pcplan::SegIn &in = x.in;
+    in.tid = (const int32_t *)(di + L.at_tid); in.start = (const int64_t *)(di + L.at_start); in.end = (const int64_t *)(di + L.at_end);
+    in.strand = di + L.at_strand; in.out_off = (const int64_t *)(di + L.at_off); in.out_step = (const int8_t *)(di + L.at_step);
+    in.row_stride = (const int64_t *)(di + L.at_stride);
+    x.pclk.lap("plan(gpu): upload");
+    return PC_OK;
+}
+
+// stage A: its arrays, then the per-segment records, the sort keys and the first defect
+int plan_segments(PlanBuild &x) {
+    using namespace pcplan;
+    typedef PlanBuild::u64 u64;
+    pc_engine *e = x.e;
+    pc_plan *p = x.p;
+    const size_t n = x.n;
+    size_t b = 0;   // (the three 32-bit sums are one instantiation: one of them asks for all)
+    PC_TRY(cub_need(x.cub_a, b, x.sort_segs(64)));
+    PC_TRY(cub_need(x.cub_a, b, x.max_ends(n)));
+    PC_TRY(cub_need(x.cub_a, b, x.sum(&PlanBuild::lens, &PlanBuild::offs, n + 1)));
+    PC_TRY(cub_need(x.cub_a, b, x.sum(&PlanBuild::flags, &PlanBuild::before, n + 1)));
+    Bump &A = x.A;
+    for (int pass = 0; pass < 2; ++pass) {   // (first pass: sizes)
+        A.used = 0;
+        x.misc = A.take<Misc>(1);
+        x.keys = A.take<u64>(n); x.keys2 = A.take<u64>(n); x.ends = A.take<uint32_t>(n); x.ends2 = A.take<uint32_t>(n);
+        x.ge = A.take<u64>(n); x.pm = A.take<u64>(n); x.flags = A.take<uint32_t>(n + 1); x.before = A.take<uint32_t>(n + 1);
+        x.islands = A.take<Island>(n); x.island_keys = A.take<u64>(n); x.lens = A.take<int64_t>(n + 1); x.offs = A.take<int64_t>(n + 1);
+        x.npieces = A.take<uint32_t>(n + 1); x.piece_at = A.take<uint32_t>(n + 1); x.nout = A.take<uint32_t>(n + 1); x.out_at = A.take<uint32_t>(n + 1);
+        x.cub_tmp = A.take<uint8_t>(x.cub_a + 256);
         if (pass == 0) {
-            rc = e->plan_scratch[1].reserve(B.used + 256);
-            if (rc == PC_OK) rc = e->plan_scratch[2].reserve(C.used + 256);
+            PC_TRY(e->plan_scratch[0].reserve(A.used + 256));
+            A.base = e->plan_scratch[0].p;
+        }
+    }
+    Misc &h = x.h;
+    std::memset(&h, 0, sizeof(h));
+    h.first_bad = ~0ull;
+    h.max_slots = 1;
+    HIP_TRY(hipMemcpyAsync(x.misc, &h, sizeof(h), hipMemcpyHostToDevice, x.st));
+    hipLaunchKernelGGL(k_plan_segs, dim3(x.gseg), dim3(256), 0, x.st, x.in, x.segs.n, x.ntid, x.rows, x.out_elems, p->d_gsegs_own.p, x.keys, x.ends, x.misc);
+    PC_TRY(x.read_misc());
+    if (h.first_bad != ~0ull) {   // the defect of the lowest segment index, as a serial pass reports it
+        PlanDefect bad = {(int)(h.first_bad & 0xffu), (int64_t)(h.first_bad >> 8), 0, 0};
+        if (bad.kind == kDefectSlice) plan_slice_bounds(x.segs, bad.seg, x.rows, &bad.lo, &bad.hi);
+        return fail(PC_ERR_ARG, "%s", plan_defect_message(bad, x.out_elems).c_str());
+    }
+    p->modes = h.modes;
+    p->covered = (int64_t)h.covered;
+    p->has_sums = h.has_sums != 0;
+    if (!plan_window(x.rows, h.modes, h.n_iv, h.iv_len, e->knobs.tile_g, &p->G))
+        return fail(PC_ERR_ARG, "%s", plan_defect_message({kDefectRows, 0, x.rows, 0}, x.out_elems).c_str());
+    x.G = p->G;
+    x.split_modes = x.rows > 1 ? 1 : 0;
+    x.n_iv = (size_t)h.n_iv;
+    x.pclk.lap("plan(gpu): segments");
+    return PC_OK;
+}
+
+// intervals by (contig, mode, start) -> islands, their lengths and pieces; every segment finds its island
+int plan_islands(PlanBuild &x) {
+    using namespace pcplan;
+    pc_plan *p = x.p;
+    hipStream_t st = x.st;
+    const size_t n = x.n, n_iv = x.n_iv;
+    const int G = x.G;
+    if (n_iv) {
+        const unsigned giv = (unsigned)((n_iv + 255) / 256);
+        PC_TRY(cub_run_sized(x.cub_tmp, x.cub_a, x.sort_segs(std::min(64, 33 + bits_for((uint64_t)x.ntid)))));
+        hipLaunchKernelGGL(k_group_ends, dim3(giv), dim3(256), 0, st, x.keys2, x.ends2, x.misc, x.ge);
+        PC_TRY(cub_run_sized(x.cub_tmp, x.cub_a, x.max_ends(n_iv)));
+        hipLaunchKernelGGL(k_island_flags, dim3(giv), dim3(256), 0, st, x.keys2, x.pm, x.misc, x.flags, (int64_t)n_iv);
+        PC_TRY(cub_run_sized(x.cub_tmp, x.cub_a, x.sum(&PlanBuild::flags, &PlanBuild::before, n_iv)));
+        hipLaunchKernelGGL(k_island_fill, dim3(giv), dim3(256), 0, st, x.keys2, x.pm, x.flags, x.before, x.misc, x.islands, x.island_keys);
+        hipLaunchKernelGGL(k_island_lens, dim3(giv), dim3(256), 0, st, x.misc, x.islands, x.lens, x.npieces, G, (int64_t)n_iv);
+        PC_TRY(cub_run_sized(x.cub_tmp, x.cub_a, x.sum(&PlanBuild::lens, &PlanBuild::offs, n_iv)));
+        PC_TRY(cub_run_sized(x.cub_tmp, x.cub_a, x.sum(&PlanBuild::npieces, &PlanBuild::piece_at, n_iv)));
+        hipLaunchKernelGGL(k_island_offsets, dim3(giv), dim3(256), 0, st, x.misc, x.islands, x.offs, x.lens, x.piece_at, x.npieces);
+    }
+    if (n) {
+        hipLaunchKernelGGL(k_seg_island, dim3(x.gseg), dim3(256), 0, st, x.in, x.segs.n, p->d_gsegs_own.p, x.misc, x.islands, x.island_keys, x.nout, G);
+        PC_TRY(cub_run_sized(x.cub_tmp, x.cub_a, x.sum(&PlanBuild::nout, &PlanBuild::out_at, n)));
+        hipLaunchKernelGGL(k_out_total, dim3(1), dim3(64), 0, st, x.misc, x.out_at, x.nout, x.segs.n);
+    }
+    PC_TRY(x.read_misc());
+    p->npos = (int64_t)x.h.npos;
+    p->out_needs_zero = x.h.needs_zero != 0;
+    x.n_pieces = x.h.n_pieces; x.n_op = x.h.n_opieces;
+    if (x.n_pieces >= 0x7fffffffu || x.n_op >= 0x7fffffffu) return fail(PC_ERR_ARG, "pc_plan_create: too many window pieces");
+    x.pclk.lap("plan(gpu): islands");
+    return PC_OK;
+}
+
+// stage B: the pieces by (contig, window, mode, offset), a tile where the window changes
+int plan_pieces_tiles(PlanBuild &x) {
+    using namespace pcplan;
+    typedef PlanBuild::u64 u64;
+    pc_engine *e = x.e;
+    hipStream_t st = x.st;
+    const size_t n_pieces = x.n_pieces, n_op = x.n_op;
+    size_t b = 0;
+    PC_TRY(cub_need(x.cub_b, b, x.sort_pieces(64)));
+    PC_TRY(cub_need(x.cub_b, b, x.sum(&PlanBuild::new_tile, &PlanBuild::tbefore, n_pieces + 1)));
+    PC_TRY(cub_need(x.cub_c, b, x.sort_out(32)));
+    Bump &B = x.B, &C = x.C;
+    for (int pass = 0; pass < 2; ++pass) {   // (the arrays of stage C beside them: both blocks are had before anything runs)
+        B.used = 0; C.used = 0;
+        x.pkeys = B.take<u64>(n_pieces); x.pkeys2 = B.take<u64>(n_pieces); x.pidx = B.take<uint32_t>(n_pieces); x.pidx2 = B.take<uint32_t>(n_pieces);
+        x.praw = B.take<Piece>(n_pieces); x.psorted = B.take<Piece>(n_pieces); x.new_tile = B.take<uint32_t>(n_pieces + 1); x.tbefore = B.take<uint32_t>(n_pieces + 1);
+        x.tiles_tmp = B.take<Tile>(n_pieces); x.tile_keys = B.take<u64>(n_pieces); x.cub_tmp_b = B.take<uint8_t>(x.cub_b + 256);
+        x.oraw = C.take<OutPiece>(n_op); x.otile = C.take<uint32_t>(n_op); x.otile2 = C.take<uint32_t>(n_op); x.oidx = C.take<uint32_t>(n_op); x.oidx2 = C.take<uint32_t>(n_op);
+        x.cub_tmp_c = C.take<uint8_t>(x.cub_c + 256);
+        if (pass == 0) {
+            int rc = e->plan_scratch[1].reserve(B.used + 256);
+            room(rc, e->plan_scratch[2], C.used + 256);
             if (rc != PC_OK) return rc;
             B.base = e->plan_scratch[1].p; C.base = e->plan_scratch[2].p;
         }
     }
     if (n_pieces) {
         const unsigned gp = (unsigned)((n_pieces + 255) / 256);
-        hipLaunchKernelGGL(k_pieces_raw, dim3(gp), dim3(256), 0, st, misc, islands, piece_at, G, pkeys, pidx, praw);
-        size_t b = cub_b;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub_tmp_b, b, pkeys, pkeys2, pidx, pidx2, (int)n_pieces, 0, std::min(64, 37 + bits_for((uint64_t)ntid)), st));
-        hipLaunchKernelGGL(k_pieces_sorted, dim3(gp), dim3(256), 0, st, misc, pkeys2, pidx2, praw, psorted, new_tile, split_modes, (int64_t)n_pieces);
-        b = cub_b;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(cub_tmp_b, b, new_tile, tbefore, (int)n_pieces, st));
-        hipLaunchKernelGGL(k_tile_fill, dim3(gp), dim3(256), 0, st, misc, pkeys2, psorted, new_tile, tbefore, G, split_modes, tiles_tmp, tile_keys);
+        hipLaunchKernelGGL(k_pieces_raw, dim3(gp), dim3(256), 0, st, x.misc, x.islands, x.piece_at, x.G, x.pkeys, x.pidx, x.praw);
+        PC_TRY(cub_run_sized(x.cub_tmp_b, x.cub_b, x.sort_pieces(std::min(64, 37 + bits_for((uint64_t)x.ntid)))));
+        hipLaunchKernelGGL(k_pieces_sorted, dim3(gp), dim3(256), 0, st, x.misc, x.pkeys2, x.pidx2, x.praw, x.psorted, x.new_tile, x.split_modes, (int64_t)n_pieces);
+        PC_TRY(cub_run_sized(x.cub_tmp_b, x.cub_b, x.sum(&PlanBuild::new_tile, &PlanBuild::tbefore, n_pieces)));
+        hipLaunchKernelGGL(k_tile_fill, dim3(gp), dim3(256), 0, st, x.misc, x.pkeys2, x.psorted, x.new_tile, x.tbefore, x.G, x.split_modes, x.tiles_tmp, x.tile_keys);
     }
-    if (n_op) {
-        hipLaunchKernelGGL(k_out_raw, dim3(gseg), dim3(256), 0, st, in, nseg, p->d_gsegs_own.p, misc, tile_keys, out_at, nout, G, split_modes, oraw, otile, oidx);
-        size_t b = cub_c;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(cub_tmp_c, b, otile, otile2, oidx, oidx2, (int)n_op, 0, std::min(32, bits_for((uint64_t)n_pieces)), st));
+    return PC_OK;
+}
+
+// stage C: the output pieces of every segment, by tile
+int plan_out_pieces(PlanBuild &x) {
+    using namespace pcplan;
+    pc_plan *p = x.p;
+    if (x.n_op) {
+        hipLaunchKernelGGL(k_out_raw, dim3(x.gseg), dim3(256), 0, x.st, x.in, x.segs.n, p->d_gsegs_own.p, x.misc, x.tile_keys, x.out_at, x.nout, x.G, x.split_modes, x.oraw, x.otile, x.oidx);
+        PC_TRY(cub_run_sized(x.cub_tmp_c, x.cub_c, x.sort_out(std::min(32, bits_for((uint64_t)x.n_pieces)))));
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&h, misc, sizeof(h), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const size_t n_tiles = h.n_tiles;
-    p->max_slots = (int)h.max_slots;
-    p->n_tiles = n_tiles; p->n_pieces = n_pieces; p->n_opieces = n_op;
-    pclk.lap("plan(gpu): pieces + tiles + output pieces");
-    // ---- the plan's block
+    PC_TRY(x.read_misc());
+    x.n_tiles = x.h.n_tiles;
+    p->max_slots = (int)x.h.max_slots;
+    p->n_tiles = x.n_tiles; p->n_pieces = x.n_pieces; p->n_opieces = x.n_op;
+    x.pclk.lap("plan(gpu): pieces + tiles + output pieces");
+    return PC_OK;
+}
+
+// the plan's block
+int plan_block(PlanBuild &x) {
+    using namespace pcplan;
+    pc_plan *p = x.p;
+    hipStream_t st = x.st;
+    const size_t n_tiles = x.n_tiles, n_pieces = x.n_pieces, n_op = x.n_op;
     const PlanBlockLayout blk(n_tiles, n_pieces, n_op, 0, 0, 0, p->npos, p->rows);
     PC_TRY(p->d_tables.reserve(blk.bytes));
     uint8_t *d = p->d_tables.p;
-    if (n_tiles) HIP_TRY(hipMemcpyAsync(d + blk.at_tiles, tiles_tmp, n_tiles * sizeof(Tile), hipMemcpyDeviceToDevice, st));
-    if (n_pieces) HIP_TRY(hipMemcpyAsync(d + blk.at_pieces, psorted, n_pieces * sizeof(Piece), hipMemcpyDeviceToDevice, st));
-    if (n_op) hipLaunchKernelGGL(k_out_sorted, dim3((unsigned)((n_op + 255) / 256)), dim3(256), 0, st, misc, otile2, oidx2, oraw, (OutPiece *)(d + blk.at_opieces), (Tile *)(d + blk.at_tiles));
+    if (n_tiles) HIP_TRY(hipMemcpyAsync(d + blk.at_tiles, x.tiles_tmp, n_tiles * sizeof(Tile), hipMemcpyDeviceToDevice, st));
+    if (n_pieces) HIP_TRY(hipMemcpyAsync(d + blk.at_pieces, x.psorted, n_pieces * sizeof(Piece), hipMemcpyDeviceToDevice, st));
+    if (n_op) hipLaunchKernelGGL(k_out_sorted, dim3((unsigned)((n_op + 255) / 256)), dim3(256), 0, st, x.misc, x.otile2, x.oidx2, x.oraw, (OutPiece *)(d + blk.at_opieces), (Tile *)(d + blk.at_tiles));
     HIP_TRY(hipMemsetAsync(d + blk.at_items, 0, blk.zeroed_bytes(), st));
     HIP_TRY(hipGetLastError());
     blk.bind(p);
     p->gpu_built = true;
     p->host_inputs = false;
-    pclk.lap("plan(gpu): tables");
+    x.pclk.lap("plan(gpu): tables");
     return PC_OK;
+}
+
+// The tables of a plan, built on the GPU.  `p` arrives with nseg / out_elems / rows set; on PC_OK it has its tables in
+// HBM (d_tables and the views into it), the sizes and flags the host builder sets, and no host copies.
+int plan_build_gpu(pc_engine *e, pc_plan *p, const PlanSegments &segs, int64_t out_elems, int rows) {
+    PlanBuild x(e, p, segs, out_elems, rows);
+    PC_TRY(plan_upload_inputs(x));
+    PC_TRY(plan_segments(x));
+    PC_TRY(plan_islands(x));
+    PC_TRY(plan_pieces_tiles(x));
+    PC_TRY(plan_out_pieces(x));
+    return plan_block(x);
 }
 
 // The tables of a host-built plan (p->host) into one device block with one upload (a plan of one short segment is
@@ -1118,11 +808,12 @@ int ensure_center_tables(pc_engine *e, pc_plan *p) {
     using namespace pcplan;
     hipStream_t st = e->stream;
     const size_t ntl = p->n_tiles;
-    size_t tb = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)ntl + 1, st);
     Bump A;
     uint32_t *cnt = nullptr, *at = nullptr;
     uint8_t *tmp = nullptr;
+    auto scan = [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, cnt, at, (int)ntl + 1, st); };   // (the pointers as they are when it runs)
+    size_t tb = 0, asked = 0;
+    PC_TRY(cub_need(tb, asked, scan));
     for (int pass = 0; pass < 2; ++pass) {
         A.used = 0;
         cnt = A.take<uint32_t>(ntl + 1); at = A.take<uint32_t>(ntl + 1); tmp = A.take<uint8_t>(tb + 256);
@@ -1136,7 +827,7 @@ int ensure_center_tables(pc_engine *e, pc_plan *p) {
         const unsigned g = (unsigned)((ntl + 255) / 256);
         HIP_TRY(hipMemsetAsync(cnt + ntl, 0, 4, st));
         hipLaunchKernelGGL(k_cchunk_count, dim3(g), dim3(256), 0, st, p->d_tiles.p, p->d_pieces.p, (uint32_t)ntl, cnt);
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, at, (int)ntl + 1, st));
+        PC_TRY(cub_run_sized(tmp, tb, scan));
         HIP_TRY(hipMemcpyAsync(&total, at + ntl, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         PC_TRY(p->d_tables2.reserve(std::max<size_t>((size_t)total * sizeof(CenterChunk), 256)));
@@ -1157,11 +848,12 @@ int ensure_gather_tables(pc_engine *e, pc_plan *p) {
     using namespace pcplan;
     hipStream_t st = e->stream;
     const size_t n = (size_t)p->nseg;
-    size_t tb = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st);
     Bump A;
     uint32_t *cnt = nullptr, *at = nullptr;
     uint8_t *tmp = nullptr;
+    auto scan = [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, cnt, at, (int)n + 1, st); };   // (the pointers as they are when it runs)
+    size_t tb = 0, asked = 0;
+    PC_TRY(cub_need(tb, asked, scan));
     for (int pass = 0; pass < 2; ++pass) {
         A.used = 0;
         cnt = A.take<uint32_t>(n + 1); at = A.take<uint32_t>(n + 1); tmp = A.take<uint8_t>(tb + 256);
@@ -1174,7 +866,7 @@ int ensure_gather_tables(pc_engine *e, pc_plan *p) {
     const unsigned g = (unsigned)((n + 255) / 256);
     HIP_TRY(hipMemsetAsync(cnt + n, 0, 4, st));
     if (n) hipLaunchKernelGGL(k_gchunk_count, dim3(g), dim3(256), 0, st, p->d_gsegs_own.p, p->nseg, cnt);
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, cnt, at, (int)n + 1, st));
+    PC_TRY(cub_run_sized(tmp, tb, scan));
     HIP_TRY(hipMemcpyAsync(&total, at + n, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     PC_TRY(p->d_tables3.reserve(std::max<size_t>((size_t)total * sizeof(GatherChunk), 256)));
@@ -1202,11 +894,9 @@ int build_center_stream(pc_engine *e, StagedFile *sf, int sel, int nib) {
         PC_TRY(sf->cs_soff[sel].reserve((size_t)n + 1));
         hipLaunchKernelGGL(k_cs_count, dim3((unsigned)((n + 1 + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->rec.p, n, sel, sf->cs_soff[sel].p);
         {
-            size_t tmp_bytes = 0;
             DevBuf<uint8_t> d_tmp;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, sf->cs_soff[sel].p, sf->cs_soff[sel].p, (int)(n + 1), st));
-            PC_TRY(d_tmp.reserve(tmp_bytes));
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, sf->cs_soff[sel].p, sf->cs_soff[sel].p, (int)(n + 1), st));
+            uint32_t *soff = sf->cs_soff[sel].p;
+            PC_TRY(cub_run(d_tmp, [=](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, soff, soff, (int)(n + 1), st); }));
             HIP_TRY(hipStreamSynchronize(st));   // d_tmp goes out of scope
         }
         uint32_t total = 0;
@@ -1335,7 +1025,7 @@ int pc_create(int device, pc_engine **out) {
     std::vector<double> invh(65536);
     for (int m = 0; m < 65536; ++m) invh[m] = inv[m] * 0.5;   // exact: a power-of-two scaling of a normal number
     if (rc == PC_OK) rc = e->d_invh.upload(invh, e->stream);
-    if (rc == PC_OK) rc = e->d_counters.reserve(16);
+    room(rc, e->d_counters, 16);
     if (rc == PC_OK && hipMemsetAsync(e->d_counters.p, 0, 16 * sizeof(uint32_t), e->stream) != hipSuccess) rc = fail(PC_ERR_HIP, "pc_create: memset failed");
     if (rc == PC_OK && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(PC_ERR_HIP, "pc_create: sync failed");
     if (rc == PC_OK) rc = settle_streams(e);
@@ -1453,7 +1143,7 @@ int pc_read_records(pc_engine *e, int file, int64_t n, const int64_t *idx, int32
     DevBuf<int64_t> d_idx;
     DevBuf<uint8_t> d_out;   // tid, pos, alen, nblk (int32 each), flag16 (u16), reverse, mapq (u8): 20 bytes per record
     int rc = d_idx.upload(idx, (size_t)n, st);
-    if (rc == PC_OK) rc = d_out.reserve((size_t)n * 20 + 64);
+    room(rc, d_out, (size_t)n * 20 + 64);
     if (rc != PC_OK) return rc;
     int32_t *o_tid = (int32_t *)d_out.p, *o_pos = o_tid + n, *o_alen = o_pos + n, *o_nblk = o_alen + n;
     uint16_t *o_f16 = (uint16_t *)(o_nblk + n);
@@ -1488,7 +1178,7 @@ int pc_read_record_runs(pc_engine *e, int file, int64_t n, const int64_t *idx, c
     DevBuf<int32_t> d_runs;
     int rc = d_idx.upload(idx, (size_t)n, st);
     if (rc == PC_OK) rc = d_at.upload(run_at, (size_t)n, st);
-    if (rc == PC_OK) rc = d_runs.reserve((size_t)nruns * 2);
+    room(rc, d_runs, (size_t)nruns * 2);
     if (rc != PC_OK) return rc;
     // (the caller sized the run arrays from the run counts pc_read_records gave it: a slot beyond them would be a bug there)
     hipLaunchKernelGGL(k_gather_runs, dim3((unsigned)((n + kWG - 1) / kWG)), dim3(kWG), 0, st, sf->view(), d_idx.p, n, d_at.p, d_runs.p, d_runs.p + nruns);
@@ -1568,22 +1258,6 @@ struct StageCall {   // what the phases of one call share beside the engine and 
     explicit StageCall(const StageInput &i) : in(i), cols(), tid_bounds((size_t)i.ntid + 1, 0), n_ok(i.n), stats(i.ntid) {}
 };
 
-// The end of a phase with work in flight: waits for the stream and reports the first error of the phase (`he`), of a
-// launch, or of the wait.  `what` is a format that takes the error string, or none.
-int finish_phase(hipStream_t st, hipError_t he, const char *what) {
-    if (he == hipSuccess) he = hipGetLastError();
-    const hipError_t waited = hipStreamSynchronize(st);
-    if (he == hipSuccess) he = waited;
-    return he == hipSuccess ? PC_OK : fail(PC_ERR_HIP, what, hipGetErrorString(he));
-}
-
-// `n` elements in each of the buffers; stops at the first that cannot be had
-template <class... Bufs> int reserve_all(size_t n, Bufs &...bufs) {
-    int rc = PC_OK;
-    (void)(((rc = bufs.reserve(n)) == PC_OK) && ...);
-    return rc;
-}
-
 int stage_check(const pc_engine *e, const StageInput &in) {   // (no HIP call)
     const int64_t n = in.n, nrun = in.nrun, n_wide = in.n_wide;
     if (!e) return fail(PC_ERR_ARG, "engine is NULL");
@@ -1638,8 +1312,10 @@ int reserve_record_arrays(StagedFile *sf, StageCall &c) {
 int stage_upload(pc_engine *e, StagedFile *sf, StageCall &c) {
     const StageInput &in = c.in;
     const size_t n = (size_t)in.n, nrun = (size_t)in.nrun;
-    PC_TRY(reserve_all(n + 1, c.d_pos, c.d_alen, c.d_flags8, c.d_nblk8));
-    PC_TRY(reserve_all(nrun + 1, c.d_bs, c.d_bl));
+    int rc = PC_OK;
+    room(rc, c.d_pos, n + 1); room(rc, c.d_alen, n + 1); room(rc, c.d_flags8, n + 1); room(rc, c.d_nblk8, n + 1);
+    room(rc, c.d_bs, nrun + 1); room(rc, c.d_bl, nrun + 1);
+    PC_TRY(rc);
     // (the ring fills these blocks on ITS stream: a block the pool recycled may still be read or written by work
     // queued on the engine's stream -- a plan buffer that grew inside an asynchronous pc_count -- and every other user of
     // the pool is ordered on that stream; the ring is the exception, so it starts behind everything queued there)
@@ -1664,7 +1340,7 @@ int stage_upload(pc_engine *e, StagedFile *sf, StageCall &c) {
     });
     c.n_ok = scan_contigs(in.tid, in.n, in.ntid, stage_threads(in.n), c.tid_bounds);
     c.clk.lap("contig bounds");
-    int rc = upload_wide_records(e, sf, c);
+    rc = upload_wide_records(e, sf, c);
     // while the columns cross PCIe: the arrays of the staged file whose sizes follow from the record count alone (a
     // billion records: 20 GB of hipMalloc, 0.12 s when the pool has no such blocks -- a third of the call)
     if (rc == PC_OK) rc = reserve_record_arrays(sf, c);
@@ -1687,20 +1363,17 @@ int stage_run_layout(pc_engine *e, StagedFile *sf, StageCall &c) {
     DevBuf<uint8_t> d_tmp;
     DevBuf<unsigned long long> d_tot;
     PC_TRY(d_tot.reserve(2));
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, c.d_run_at.p, c.d_run_at.p, (int)n + 1, st));
-    PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+    auto sum_in_place = [=](uint32_t *v) { return [=](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, v, v, (int)n + 1, st); }; };
+    size_t most = 16, tb = 0;
+    PC_TRY(cub_need(most, tb, sum_in_place(c.d_run_at.p)));
+    PC_TRY(d_tmp.reserve(most));
     unsigned long long tot[2] = {0, 0};
     hipError_t he = hipMemsetAsync(d_tot.p, 0, 16, st);
     if (he == hipSuccess) {
         hipLaunchKernelGGL(k_cols_runs, dim3((unsigned)std::min<int64_t>((n + 256) / 256, 4096)), dim3(256), 0, st, c.cols, n, sf->blk_off.p, c.d_run_at.p, d_tot.p);
-        size_t b2 = tb;
-        he = hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, sf->blk_off.p, sf->blk_off.p, (int)n + 1, st);
+        he = cub_enqueue(d_tmp.p, tb, sum_in_place(sf->blk_off.p));
     }
-    if (he == hipSuccess) {
-        size_t b2 = tb;
-        he = hipcub::DeviceScan::ExclusiveSum(d_tmp.p, b2, c.d_run_at.p, c.d_run_at.p, (int)n + 1, st);
-    }
+    if (he == hipSuccess) he = cub_enqueue(d_tmp.p, tb, sum_in_place(c.d_run_at.p));
     if (he == hipSuccess) he = hipMemcpyAsync(tot, d_tot.p, 16, hipMemcpyDeviceToHost, st);
     PC_TRY(finish_phase(st, he, "stage: laying out the runs failed: %s"));
     if ((int64_t)tot[0] != nrun)
@@ -1765,9 +1438,9 @@ int stage_pack(pc_engine *e, StagedFile *sf, StageCall &c) {
     DevBuf<unsigned long long> d_stats;   // the statistics block, then the error word of the validation
     DevBuf<int32_t> d_last_pos, d_tid_end;
     DevBuf<int64_t> d_bounds;
-    PC_TRY(d_stats.reserve(kStatWords + 1));
-    PC_TRY(reserve_all((size_t)ntid, d_last_pos, d_tid_end));
-    PC_TRY(d_bounds.reserve((size_t)ntid + 1));
+    int rc = d_stats.reserve(kStatWords + 1);
+    room(rc, d_last_pos, (size_t)ntid); room(rc, d_tid_end, (size_t)ntid); room(rc, d_bounds, (size_t)ntid + 1);
+    PC_TRY(rc);
     std::vector<unsigned long long> hstats((size_t)kStatWords + 1, 0ull);
     hstats[(size_t)kAtMisc + 1] = 65536ull;   // rmin
     hstats[(size_t)kStatWords] = ~0ull;       // no defect
@@ -1826,13 +1499,14 @@ int stage_classify(pc_engine *e, StagedFile *sf, StageCall &c) {
     c.nwg = (uint32_t)((n + 255) / 256);
     const int nside = 3 * (int)c.nwg + 1;
     DevBuf<uint8_t> d_tmp;
-    size_t tb = 0;
+    size_t most = 16, tb = 0;
+    auto sum_sides = [&c, nside, st](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, c.d_side_at.p, c.d_side_at.p, nside, st); };
     if (nrun > 0) PC_TRY(sf->blk.reserve((size_t)nrun));
     if (nrun == 0) sf->blk_off.release();   // (all zero: no record keeps runs in the run arrays)
     if (n > 0) {
         PC_TRY(c.d_side_at.reserve((size_t)nside));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, c.d_side_at.p, c.d_side_at.p, nside, st));
-        PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+        PC_TRY(cub_need(most, tb, sum_sides));
+        PC_TRY(d_tmp.reserve(most));
     }
     {   // two excluded headers, eight skip words (whole quads can always be loaded)
         const uint2 tail_rec[2] = {make_uint2(0u, (uint32_t)PC_FLAG_EXCLUDED << 16), make_uint2(0u, (uint32_t)PC_FLAG_EXCLUDED << 16)};
@@ -1850,7 +1524,7 @@ int stage_classify(pc_engine *e, StagedFile *sf, StageCall &c) {
     hipError_t he = hipMemsetAsync(c.d_side_at.p + 3 * (size_t)c.nwg, 0, 4, st);
     if (he == hipSuccess) {
         hipLaunchKernelGGL(pcstage::k_classify, dim3(c.nwg), dim3(256), 0, st, sf->rec.p, n, sf->blk_off.p, sf->blk.p, c.wcap, sf->stream.p, c.d_side_at.p);
-        he = hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, c.d_side_at.p, c.d_side_at.p, nside, st);
+        he = cub_enqueue(d_tmp.p, tb, sum_sides);
     }
     for (int k = 1; k <= 3 && he == hipSuccess; ++k) he = hipMemcpyAsync(&at[k], c.d_side_at.p + (size_t)k * c.nwg, 4, hipMemcpyDeviceToHost, st);
     PC_TRY(finish_phase(st, he, "pc_add_alignment_file: deriving the record stream failed: %s"));
@@ -1878,6 +1552,11 @@ struct SideScratch {   // the working arrays of the running maxima
 
 dim3 grid_of(size_t m) { return dim3((unsigned)((m + kWG - 1) / kWG)); }
 
+// the running maximum over the first `cnt` packed ends, as `call(tmp, bytes)`: asked at the longer list, run per list
+auto side_max_scan(SideScratch &w, size_t cnt, hipStream_t st) {
+    return [&w, cnt, st](void *t, size_t &b) { return hipcub::DeviceScan::InclusiveScan(t, b, w.d_key.p, w.d_key_scanned.p, hipcub::Max(), (int)cnt, st); };
+}
+
 // the entries of one list, and the running maximum of their ends if the list has one
 hipError_t fill_side_list(pc_engine *e, const StagedFile *sf, const StageCall &c, const SideList &l, SideScratch &w) {
     if (!l.m) return hipSuccess;
@@ -1885,8 +1564,7 @@ hipError_t fill_side_list(pc_engine *e, const StagedFile *sf, const StageCall &c
     hipLaunchKernelGGL(k_side_fill, grid_of(l.m), dim3(kWG), 0, st, l.idx, (int64_t)l.m, sf->rec.p, sf->blk_off.p, sf->blk.p, sf->tid_bounds.p, c.in.ntid,
                        sf->wide_rec.p, sf->wide_val.p, c.in.n_wide, l.rec, l.runs, l.tid, l.pmax ? w.d_key.p : nullptr, l.wide);
     if (!l.pmax) return hipSuccess;
-    size_t tb = w.d_tmp.cap;
-    const hipError_t he = hipcub::DeviceScan::InclusiveScan(w.d_tmp.p, tb, w.d_key.p, w.d_key_scanned.p, hipcub::Max(), (int)l.m, st);
+    const hipError_t he = cub_enqueue(w.d_tmp.p, w.d_tmp.cap, side_max_scan(w, l.m, st));
     if (he == hipSuccess) hipLaunchKernelGGL(k_unpack_pmax, grid_of(l.m), dim3(kWG), 0, st, w.d_key_scanned.p, (int64_t)l.m, l.pmax);
     return he;
 }
@@ -1894,14 +1572,15 @@ hipError_t fill_side_list(pc_engine *e, const StagedFile *sf, const StageCall &c
 int reserve_side_lists(StagedFile *sf, const StageCall &c, size_t nlong, size_t ngap, size_t nxlong) {
     const size_t ntid1 = (size_t)c.in.ntid + 1, nlin = sf->nlin;
     const bool wide = c.in.n_wide != 0;
-    PC_TRY(reserve_all(ntid1, sf->tid_bounds, sf->lin_off, sf->long_tid_bounds, sf->gap_tid_bounds));
-    PC_TRY(reserve_all(nlong, sf->long_idx, sf->long_rec, sf->long_runs, sf->long_tid, sf->long_pmax));
-    PC_TRY(reserve_all(ngap, sf->gap_rec, sf->gap_runs));
-    PC_TRY(reserve_all(nxlong, sf->xlong_rec, sf->xlong_runs));
-    if (wide) PC_TRY(sf->long_wide.reserve(nlong));
-    if (wide) PC_TRY(sf->xlong_wide.reserve(nxlong));
-    PC_TRY(reserve_all(nlin, sf->lin_tab, sf->glin_tab, sf->llin_tab, sf->plin_tab));
-    return nxlong ? reserve_all(nlin, sf->xllin_tab, sf->xplin_tab) : PC_OK;
+    int rc = PC_OK;
+    room(rc, sf->tid_bounds, ntid1); room(rc, sf->lin_off, ntid1); room(rc, sf->long_tid_bounds, ntid1); room(rc, sf->gap_tid_bounds, ntid1);
+    room(rc, sf->long_idx, nlong); room(rc, sf->long_rec, nlong); room(rc, sf->long_runs, nlong); room(rc, sf->long_tid, nlong); room(rc, sf->long_pmax, nlong);
+    room(rc, sf->gap_rec, ngap); room(rc, sf->gap_runs, ngap);
+    room(rc, sf->xlong_rec, nxlong); room(rc, sf->xlong_runs, nxlong);
+    if (wide) { room(rc, sf->long_wide, nlong); room(rc, sf->xlong_wide, nxlong); }
+    room(rc, sf->lin_tab, nlin); room(rc, sf->glin_tab, nlin); room(rc, sf->llin_tab, nlin); room(rc, sf->plin_tab, nlin);
+    if (nxlong) { room(rc, sf->xllin_tab, nlin); room(rc, sf->xplin_tab, nlin); }
+    return rc;
 }
 
 int stage_side_lists(pc_engine *e, StagedFile *sf, StageCall &c) {
@@ -1916,14 +1595,15 @@ int stage_side_lists(pc_engine *e, StagedFile *sf, StageCall &c) {
     DevBuf<int64_t> d_xlong_bounds;
     DevBuf<int32_t> d_xlong_pmax;
     SideScratch w;
-    PC_TRY(reserve_side_lists(sf, c, nlong, ngap, nxlong));
-    PC_TRY(d_gap_idx.reserve(ngap));
-    PC_TRY(reserve_all(nxlong, d_xlong_idx, d_xlong_pmax));
-    PC_TRY(d_xlong_bounds.reserve((size_t)ntid + 1));
-    PC_TRY(reserve_all(std::max(nlong, nxlong), w.d_key, w.d_key_scanned));
-    size_t need = 0;
-    HIP_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need, w.d_key.p, w.d_key_scanned.p, hipcub::Max(), (int)std::max(nlong, nxlong), st));
-    PC_TRY(w.d_tmp.reserve(std::max<size_t>(need, 16)));
+    int rc = reserve_side_lists(sf, c, nlong, ngap, nxlong);
+    room(rc, d_gap_idx, ngap);
+    room(rc, d_xlong_idx, nxlong); room(rc, d_xlong_pmax, nxlong);
+    room(rc, d_xlong_bounds, (size_t)ntid + 1);
+    room(rc, w.d_key, std::max(nlong, nxlong)); room(rc, w.d_key_scanned, std::max(nlong, nxlong));
+    PC_TRY(rc);
+    size_t most = 16, need = 0;
+    PC_TRY(cub_need(most, need, side_max_scan(w, std::max(nlong, nxlong), st)));
+    PC_TRY(w.d_tmp.reserve(most));
     const SideList lists[3] = {
         {sf->long_idx.p, nlong, sf->long_rec.p, sf->long_runs.p, sf->long_tid.p, c.in.n_wide ? sf->long_wide.p : nullptr, sf->long_pmax.p, sf->long_tid_bounds.p},
         {d_gap_idx.p, ngap, sf->gap_rec.p, sf->gap_runs.p, nullptr, nullptr, nullptr, sf->gap_tid_bounds.p},
@@ -1961,18 +1641,22 @@ int stage_run_stream(pc_engine *e, StagedFile *sf, StageCall &c) {
     DevBuf<unsigned long long> d_key, d_key_sorted;
     DevBuf<uint32_t> d_ord, d_ord_sorted;
     DevBuf<uint8_t> d_tmp;
-    PC_TRY(reserve_all(nrunrec, d_key, d_ord, d_key_sorted, d_ord_sorted, sf->run_recidx));
-    PC_TRY(sf->run_rec.reserve(nrunrec + 1));
-    PC_TRY(sf->rlin_tab.reserve(nlin));
-    size_t tmp_bytes = 0;
+    int rc = PC_OK;
+    room(rc, d_key, nrunrec); room(rc, d_ord, nrunrec); room(rc, d_key_sorted, nrunrec); room(rc, d_ord_sorted, nrunrec); room(rc, sf->run_recidx, nrunrec);
+    room(rc, sf->run_rec, nrunrec + 1);
+    room(rc, sf->rlin_tab, nlin);
+    PC_TRY(rc);
     const int end_bit = 32 + (ntid > 1 ? 32 - __builtin_clz((unsigned)(ntid - 1)) : 1);
-    hipError_t he = hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, d_key.p, d_key_sorted.p, d_ord.p, d_ord_sorted.p, (int)nrunrec, 0, end_bit, st);
-    if (he != hipSuccess) return fail(PC_ERR_HIP, "stage: sorting the run stream failed: %s", hipGetErrorString(he));
-    PC_TRY(d_tmp.reserve(tmp_bytes));
+    auto sort_runs = [&, end_bit](void *t, size_t &b) {   // stable: equal starts keep record order
+        return hipcub::DeviceRadixSort::SortPairs(t, b, d_key.p, d_key_sorted.p, d_ord.p, d_ord_sorted.p, (int)nrunrec, 0, end_bit, st);
+    };
+    size_t most = 16, tmp_bytes = 0;
+    PC_TRY(cub_need(most, tmp_bytes, sort_runs));
+    PC_TRY(d_tmp.reserve(most));
     const dim3 grid = grid_of(nrunrec);
     // sort keys (contig << 32 | run start) and the identity permutation, made on the GPU
     hipLaunchKernelGGL(k_run_keys, grid, dim3(kWG), 0, st, c.d_val_in.p, c.d_idx_in.p, (int64_t)nrunrec, sf->tid_bounds.p, ntid, d_key.p, d_ord.p);
-    he = hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tmp_bytes, d_key.p, d_key_sorted.p, d_ord.p, d_ord_sorted.p, (int)nrunrec, 0, end_bit, st);   // stable: equal starts keep record order
+    hipError_t he = cub_enqueue(d_tmp.p, tmp_bytes, sort_runs);
     if (he != hipSuccess) return finish_phase(st, he, "stage: sorting the run stream failed: %s");
     hipLaunchKernelGGL(k_run_gather, grid, dim3(kWG), 0, st, d_ord_sorted.p, c.d_val_in.p, c.d_idx_in.p, (int64_t)nrunrec, sf->run_rec.p, sf->run_recidx.p);
     hipLaunchKernelGGL(k_run_lin, grid_of(nlin), dim3(kWG), 0, st, d_key_sorted.p, (int64_t)nrunrec, sf->lin_off.p, ntid, (int64_t)nlin, sf->rlin_tab.p);
@@ -1997,7 +1681,9 @@ int stage_file(pc_engine *e, const StageInput &in) {
     } else PC_TRY(stage_upload(e, sf, c));   // (laps: column buffers, contig bounds, arrays of the file, columns to HBM)
     PC_TRY(stage_run_layout(e, sf, c));
     c.clk.lap("run layout (GPU)");
-    PC_TRY(reserve_all((size_t)c.nrunrec, c.d_val_in, c.d_idx_in));
+    int rc = PC_OK;
+    room(rc, c.d_val_in, (size_t)c.nrunrec); room(rc, c.d_idx_in, (size_t)c.nrunrec);
+    PC_TRY(rc);
     c.clk.lap("allocations");
     PC_TRY(stage_pack(e, sf, c));
     c.clk.lap("validate + pack (GPU)");
@@ -2056,16 +1742,15 @@ static int build_compact_stream(pc_engine *e, StagedFile *sf, int ntid) {
     DevBuf<uint32_t> d_words, d_cnt, d_off, d_base;
     DevBuf<uint8_t> d_scan;
     int rc = d_words.reserve((size_t)n);
-    if (rc == PC_OK) rc = d_cnt.reserve((size_t)ntiles + 1);
-    if (rc == PC_OK) rc = d_off.reserve((size_t)ntiles + 1);
-    if (rc == PC_OK) rc = d_base.reserve((size_t)ntiles);
+    room(rc, d_cnt, (size_t)ntiles + 1); room(rc, d_off, (size_t)ntiles + 1); room(rc, d_base, (size_t)ntiles);
     if (rc != PC_OK) return rc;
-    size_t tb = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt.p, d_off.p, (int)ntiles + 1, st));
-    PC_TRY(d_scan.reserve(std::max<size_t>(tb, 16)));
+    auto sum_tiles = [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_cnt.p, d_off.p, (int)ntiles + 1, st); };
+    size_t most = 16, tb = 0;
+    PC_TRY(cub_need(most, tb, sum_tiles));
+    PC_TRY(d_scan.reserve(most));
     HIP_TRY(hipMemsetAsync(d_cnt.p + ntiles, 0, 4, st));
     hipLaunchKernelGGL(k_compact_tiles, dim3(ntiles), dim3(256), 0, st, sf->rec.p, sf->stream.p, n, sf->tid_bounds.p, ntid, d_words.p, d_cnt.p, d_base.p);
-    hipError_t he = hipcub::DeviceScan::ExclusiveSum(d_scan.p, tb, d_cnt.p, d_off.p, (int)ntiles + 1, st);
+    hipError_t he = cub_enqueue(d_scan.p, tb, sum_tiles);
     uint32_t total = 0;
     if (he == hipSuccess) he = hipMemcpyAsync(&total, d_off.p + ntiles, 4, hipMemcpyDeviceToHost, st);
     if (he == hipSuccess) he = hipGetLastError();
@@ -2073,7 +1758,7 @@ static int build_compact_stream(pc_engine *e, StagedFile *sf, int ntid) {
     if (he != hipSuccess) return fail(PC_ERR_HIP, "building the compact stream failed: %s", hipGetErrorString(he));
     if ((double)total > e->knobs.compact_keep * (double)n) { sf->cstream.release(); sf->clin_tab.release(); return PC_OK; }
     rc = sf->cstream.reserve((size_t)total + 8);
-    if (rc == PC_OK) rc = sf->clin_tab.reserve(sf->nlin);
+    room(rc, sf->clin_tab, sf->nlin);
     if (rc != PC_OK) return rc;
     hipLaunchKernelGGL(k_compact_gather, dim3(ntiles), dim3(256), 0, st, d_words.p, d_off.p, ntiles, sf->cstream.p);
     hipLaunchKernelGGL(k_compact_lin, dim3((unsigned)((sf->nlin + 255) / 256)), dim3(256), 0, st, sf->lin_tab.p, (int64_t)sf->nlin, sf->rec.p, n,
@@ -2195,7 +1880,7 @@ int pc_set_alignment_sam(pc_engine *e, int file, int64_t n, const uint16_t *flag
     if (n > 0) {
         PoolScope pool_scope(&e->pool);
         int rc = sf->sam_flag.reserve((size_t)n);
-        if (rc == PC_OK) rc = sf->sam_mapq.reserve((size_t)n);
+        room(rc, sf->sam_mapq, (size_t)n);
         if (rc != PC_OK) return rc;
         HIP_TRY(hipMemcpyAsync(sf->sam_flag.p, flag, (size_t)n * 2, hipMemcpyHostToDevice, e->stream));
         HIP_TRY(hipMemcpyAsync(sf->sam_mapq.p, mapq, (size_t)n, hipMemcpyHostToDevice, e->stream));
@@ -2340,7 +2025,7 @@ int pc_plan_create(pc_engine *e, int64_t nseg, const int32_t *tid, const int64_t
     p->out_elems = out_elems;
     p->rows = rows;
     int rc;
-    if (on_gpu) rc = plan_build_gpu(e, p, nseg, tid, start, end, strand, out_off, out_step, row_stride, out_elems, rows);
+    if (on_gpu) rc = plan_build_gpu(e, p, {nseg, tid, start, end, strand, out_off, out_step, row_stride}, out_elems, rows);
     else {
         p->G = hp.G; p->modes = hp.modes; p->max_slots = hp.max_slots; p->npos = hp.npos;
         p->covered = hp.covered; p->has_sums = hp.has_sums; p->out_needs_zero = hp.out_needs_zero;
@@ -2611,16 +2296,17 @@ int canonical_for_plan(pc_engine *e, pc_plan *p, const CountCall &c, const HistL
             PC_TRY(sf->klin_tab.reserve((size_t)nlin + 1));
             PC_TRY(sf->kshift.reserve(2 * pccanon::kLenSlots));
             DevBuf<uint8_t> d_scan;
-            size_t tb = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, sf->klin_tab.p, sf->klin_tab.p, (int)nlin + 1, st));
-            PC_TRY(d_scan.reserve(std::max<size_t>(tb, 16)));
+            auto sum_buckets = [=](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, sf->klin_tab.p, sf->klin_tab.p, (int)nlin + 1, st); };
+            size_t most = 16, tb = 0;
+            PC_TRY(cub_need(most, tb, sum_buckets));
+            PC_TRY(d_scan.reserve(most));
             HIP_TRY(hipMemcpyAsync(sf->kshift.p, cr.shift, sizeof(cr.shift), hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemsetAsync(sf->klin_tab.p + nlin, 0, 4, st));
             const int back = pccanon::canon_buckets_back(cr, kLinShift);
             const uint32_t lc0 = (uint32_t)cr.Lc[0] << 4, lc1 = ((uint32_t)cr.Lc[1] << 4) | 4u;
             hipLaunchKernelGGL((k_canon_buckets<false>), dim3((unsigned)std::min<int64_t>(nlin, kCanonMaxGrid)), dim3(256), 0, st, sf->stream.p, sf->lin_tab.p, sf->lin_off.p, e->ntid, nlin,
                                sf->kshift.p, back, lc0, lc1, sf->klin_tab.p, (uint32_t *)nullptr);
-            hipError_t he = hipcub::DeviceScan::ExclusiveSum(d_scan.p, tb, sf->klin_tab.p, sf->klin_tab.p, (int)nlin + 1, st);
+            hipError_t he = cub_enqueue(d_scan.p, tb, sum_buckets);
             uint32_t total = 0;
             if (he == hipSuccess) he = hipMemcpyAsync(&total, sf->klin_tab.p + nlin, 4, hipMemcpyDeviceToHost, st);
             if (he == hipSuccess) he = hipGetLastError();
@@ -2855,12 +2541,13 @@ int build_dense_vector(pc_engine *e, StagedFile *sf, const DenseSig &sig) {
         HIP_TRY(hipMemcpyAsync(&n_ovf, d_n.p, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         if (n_ovf) {   // the escaped cells, sorted by cell index
-            size_t tb = 0;
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n_ovf, 0, 32, st));
-            PC_TRY(d_key.reserve(n_ovf)); PC_TRY(d_val.reserve(n_ovf)); PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+            auto sort_cells = [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, d_key.p, sf->dovf_key.p, d_val.p, sf->dovf_val.p, (int)n_ovf, 0, 32, st); };
+            size_t most = 16, tb = 0;
+            PC_TRY(cub_need(most, tb, sort_cells));
+            PC_TRY(d_key.reserve(n_ovf)); PC_TRY(d_val.reserve(n_ovf)); PC_TRY(d_tmp.reserve(most));
             PC_TRY(sf->dovf_key.reserve(n_ovf)); PC_TRY(sf->dovf_val.reserve(n_ovf));
             hipLaunchKernelGGL(k_dense_overflow, dim3(grid), dim3(256), 0, st, src, cells, d_n.p + 1, n_ovf, d_key.p, d_val.p);
-            HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, tb, d_key.p, sf->dovf_key.p, d_val.p, sf->dovf_val.p, (int)n_ovf, 0, 32, st));
+            PC_TRY(cub_run_sized(d_tmp, tb, sort_cells));
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipStreamSynchronize(st));   // (the working arrays go out of scope)
         }
@@ -2926,21 +2613,23 @@ int build_dense_chunks(pc_engine *e, pc_plan *p, const StagedFile *sf, const Gat
     DevBuf<uint32_t> d_idx, d_idx2, d_cnt, d_at, d_first, d_nof, d_flag;
     DevBuf<uint8_t> d_tmp;
     d_key.pool = d_key2.pool = d_idx.pool = d_idx2.pool = d_cnt.pool = d_at.pool = d_first.pool = d_nof.pool = d_flag.pool = d_tmp.pool = &e->pool;
-    size_t sort_b = 0, scan_b = 0;
+    size_t most = 16, sort_b = 0, scan_b = 0;
     const uint64_t nokey = (uint64_t)p->out_elems;               // the key of an empty segment: behind every start
     const int key_bits = bits_for(nokey);
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_b, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n, 0, key_bits, st));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st));
+    auto sort_starts = [&](void *t, size_t &b) { return hipcub::DeviceRadixSort::SortPairs(t, b, d_key.p, d_key2.p, d_idx.p, d_idx2.p, (int)n, 0, key_bits, st); };
+    auto sum_spans = [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_cnt.p, d_at.p, (int)n + 1, st); };
+    PC_TRY(cub_need(most, sort_b, sort_starts));
+    PC_TRY(cub_need(most, scan_b, sum_spans));
     PC_TRY(d_key.reserve(n)); PC_TRY(d_key2.reserve(n)); PC_TRY(d_idx.reserve(n)); PC_TRY(d_idx2.reserve(n));
     PC_TRY(d_cnt.reserve(n + 1)); PC_TRY(d_at.reserve(n + 1)); PC_TRY(d_first.reserve(nchunks)); PC_TRY(d_nof.reserve(nchunks)); PC_TRY(d_flag.reserve(2));
-    PC_TRY(d_tmp.reserve(std::max<size_t>(std::max(sort_b, scan_b), 16)));
+    PC_TRY(d_tmp.reserve(most));
     const unsigned g = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_chunk_keys, dim3(g), dim3(256), 0, st, gsegs, (int64_t)n, nokey, d_key.p, d_idx.p);
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(d_tmp.p, sort_b, d_key.p, d_key2.p, d_idx.p, d_idx2.p, (int)n, 0, key_bits, st));
+    PC_TRY(cub_run_sized(d_tmp, sort_b, sort_starts));
     HIP_TRY(hipMemsetAsync(d_cnt.p + n, 0, 4, st));
     HIP_TRY(hipMemsetAsync(d_flag.p, 0, 8, st));
     hipLaunchKernelGGL(k_chunk_count, dim3(g), dim3(256), 0, st, gsegs, d_key2.p, d_idx2.p, (int64_t)n, nokey, d_cnt.p, d_flag.p);
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, scan_b, d_cnt.p, d_at.p, (int)n + 1, st));
+    PC_TRY(cub_run_sized(d_tmp, scan_b, sum_spans));
     // No wait in between: the span array takes the bound that spans_fit checked (every segment: its whole chunks and two
     // ends), and k_chunk_descs leaves the descriptors alone where k_chunk_count found an overlap
     PC_TRY(p->d_dspans.reserve(2 * n + (size_t)(p->covered / kChunk) + 1));
@@ -2986,13 +2675,14 @@ int ensure_dense_tables(pc_engine *e, pc_plan *p, const StagedFile *sf) {
     if (need_items) {
         uint32_t total = 0;
         if (n) {
-            size_t tb = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t *)nullptr, (uint32_t *)nullptr, (int)n + 1, st));
-            PC_TRY(d_cnt.reserve(n + 1)); PC_TRY(d_at.reserve(n + 1)); PC_TRY(d_tmp.reserve(std::max<size_t>(tb, 16)));
+            auto sum_items = [&](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, d_cnt.p, d_at.p, (int)n + 1, st); };
+            size_t most = 16, tb = 0;
+            PC_TRY(cub_need(most, tb, sum_items));
+            PC_TRY(d_cnt.reserve(n + 1)); PC_TRY(d_at.reserve(n + 1)); PC_TRY(d_tmp.reserve(most));
             const unsigned g = (unsigned)((n + 255) / 256);
             HIP_TRY(hipMemsetAsync(d_cnt.p + n, 0, 4, st));
             hipLaunchKernelGGL(k_dense_seg_items, dim3(g), dim3(256), 0, st, gsegs, (int64_t)n, d_cnt.p);
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tb, d_cnt.p, d_at.p, (int)n + 1, st));
+            PC_TRY(cub_run_sized(d_tmp, tb, sum_items));
             HIP_TRY(hipMemcpyAsync(&total, d_at.p + n, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
             PC_TRY(p->d_ditems.reserve(std::max<size_t>(total, 1)));
@@ -3259,8 +2949,6 @@ static int check_grid_guard(pc_engine *e, pc_plan *p) {
                               "the cache has been dropped -- count again");
 }
 
-static constexpr size_t kSmallRead = 256 * 1024;
-
 int pc_read_counts(pc_engine *e, pc_plan *p, void *host_out, int64_t out_elems) {
     if (!e || !p || p->e != e || !p->counted) return fail(PC_ERR_STATE, "pc_read_counts: nothing counted yet");
     if (out_elems != p->out_elems || (out_elems > 0 && !host_out)) return fail(PC_ERR_ARG, "pc_read_counts: buffer size mismatch");
@@ -3268,7 +2956,8 @@ int pc_read_counts(pc_engine *e, pc_plan *p, void *host_out, int64_t out_elems) 
     PC_TRY(check_grid_guard(e, p));
     const size_t bytes = (size_t)out_elems * 8;
     const char *knob = getenv("PC_STAGE_SLICE");   // (test knob: the ring for every size, in pieces of so many 4 KiB pages)
-    if (bytes >= 4 * TransferRing::kPiece || (bytes > 0 && knob)) {
+    const pcmem::Route route = pcmem::read_route(bytes, knob != nullptr);
+    if (route == pcmem::Route::ring) {
         // the counts of a whole annotation: through the ring of page-locked pieces (a pageable destination the runtime has
         // not seen before is filled at 25 GB/s; see TransferRing)
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -3278,7 +2967,7 @@ int pc_read_counts(pc_engine *e, pc_plan *p, void *host_out, int64_t out_elems) 
     }
     // (growing the buffer frees the old one: not while a plan upload may still be reading from it)
     if (bytes > e->pinned.cap && e->pinned_busy) { HIP_TRY(hipEventSynchronize(e->ev_pinned)); e->pinned_busy = false; }
-    if (bytes > 0 && bytes <= kSmallRead && e->pinned.reserve(bytes) == PC_OK) {
+    if (route == pcmem::Route::pinned && e->pinned.reserve(bytes) == PC_OK) {
         // short vectors come back through the page-locked buffer (stream order keeps it behind any
         // plan upload still reading from it): a pageable destination costs an extra staging hop
         HIP_TRY(hipMemcpyAsync(e->pinned.p, p->d_out.p, bytes, hipMemcpyDeviceToHost, e->stream));
@@ -3350,7 +3039,7 @@ int pc_rle(pc_engine *e, pc_plan *p, int64_t period, int64_t *n_runs) {
     if (n == 0) return PC_OK;
     const int64_t nwg = (n + kRleChunk - 1) / kRleChunk;
     int rc = p->d_rle_cnt.reserve((size_t)nwg);
-    if (rc == PC_OK) rc = p->d_rle_base.reserve((size_t)nwg + 1);
+    room(rc, p->d_rle_base, (size_t)nwg + 1);
     if (rc != PC_OK) return rc;
     const unsigned long long *v = (const unsigned long long *)p->d_out.p;
     hipLaunchKernelGGL(k_rle_count, dim3((unsigned)nwg), dim3(kWG), 0, st, v, n, period, p->d_rle_cnt.p);
@@ -3359,7 +3048,7 @@ int pc_rle(pc_engine *e, pc_plan *p, int64_t period, int64_t *n_runs) {
     HIP_TRY(hipMemcpyAsync(&total, p->d_rle_base.p + nwg, sizeof(total), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     rc = p->d_rle_starts.reserve((size_t)std::max<int64_t>(total, 1));
-    if (rc == PC_OK) rc = p->d_rle_values.reserve((size_t)std::max<int64_t>(total, 1));
+    room(rc, p->d_rle_values, (size_t)std::max<int64_t>(total, 1));
     if (rc != PC_OK) return rc;
     hipLaunchKernelGGL(k_rle_write, dim3((unsigned)nwg), dim3(kWG), 0, st, v, n, period, p->d_rle_base.p, p->d_rle_starts.p,
                        p->d_rle_values.p);
@@ -3698,19 +3387,16 @@ int pc_mapped_reads_batch(pc_engine *e, pc_plan *p, int64_t *offsets, int64_t *t
     hipStream_t st = e->stream;
     int rc = d_segs.upload(segs, st);
     if (rc == PC_OK) rc = d_spans.upload(spans, st);
-    if (rc == PC_OK) rc = p->d_mr_off.reserve((size_t)npair + 1);
+    room(rc, p->d_mr_off, (size_t)npair + 1);
     if (rc != PC_OK) return rc;
     const MapParams mp = e->params();
     HIP_TRY(hipMemsetAsync(p->d_mr_off.p + npair, 0, 8, st));
     hipLaunchKernelGGL((k_mapped_reads_batch<false>), dim3((unsigned)npair), dim3(kWG), 0, st, d_segs.p, nseg, e->d_files.p, nfiles, d_spans.p, mp,
                        p->d_mr_off.p, (const unsigned long long *)nullptr, (uint32_t *)nullptr);
     {
-        size_t tmp_bytes = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, p->d_mr_off.p, p->d_mr_off.p, (int)(npair + 1), st));
         DevBuf<uint8_t> d_tmp;
         d_tmp.pool = &e->pool;
-        PC_TRY(d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, p->d_mr_off.p, p->d_mr_off.p, (int)(npair + 1), st));
+        PC_TRY(cub_run(d_tmp, [=](void *t, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(t, b, p->d_mr_off.p, p->d_mr_off.p, (int)(npair + 1), st); }));
         static_assert(sizeof(unsigned long long) == sizeof(int64_t), "offsets are copied as they are");
         HIP_TRY(hipMemcpyAsync(offsets, p->d_mr_off.p, (size_t)(npair + 1) * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));

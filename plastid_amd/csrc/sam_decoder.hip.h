@@ -3,7 +3,7 @@
 // (MappedFile), the header parsed on the host (sam_host.h), the body uploaded (through the page-locked halves when it is
 // large), the line starts found, the fields parsed, the records placed (place_records of bam_decoder.hip.h: order checks,
 // scans, the radix sort of PC_BAM_SORT) and the columns written.  The result is a pc_bam like any other.
-// Part of the one translation unit of plastid_counts.hip (behind bam_decoder.hip.h).
+// Part of the one translation unit of plastid_counts.hip (behind bam_decoder.hip.h; the plumbing is device_util.hip.h).
 #include "sam_kernels.hip.h"
 
 namespace {
@@ -73,10 +73,7 @@ int sam_line_starts(BamDecode &d, int64_t len, bool open_end, SamLines &ln) {
     HIP_TRY(hipMemsetAsync(d_tile.p + ntile, 0, 4, st));
     if (ntile) hipLaunchKernelGGL(sh::k_sam_count_lines, dim3((unsigned)ntile), dim3(sh::kSamTileThreads), 0, st, d.d_stream.p, (uint64_t)len, d_tile.p);
     HIP_TRY(hipGetLastError());
-    size_t tmp_bytes = 0;
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, d_tile.p, d_first.p, (int)(ntile + 1), st));
-    PC_TRY(d_tmp.reserve(std::max<size_t>(tmp_bytes, 16)));
-    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp.p, tmp_bytes, d_tile.p, d_first.p, (int)(ntile + 1), st));
+    PC_TRY(cub_run(d_tmp, [&](void *tmp, size_t &bytes) { return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, d_tile.p, d_first.p, (int)(ntile + 1), st); }));
     HIP_TRY(hipMemcpyAsync(&newlines, d_first.p + ntile, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     ln.nrec = (int64_t)newlines + (open_end ? 1 : 0);

@@ -13,7 +13,7 @@
 // Revision 17: a counted plan as the source.  pc_counts_export / _read write the text BAMGenomeArray gives of its count
 // vectors (genome_array.py:990-1111; window borders, runs whose value is > 0, int64 or float64 values) from the plan's
 // output in HBM, by the phases of a CountsExport; pc_track_set_counts is pc_track_set for one segment reading that output.
-// Part of the one translation unit of plastid_counts.hip (behind sam_decoder.hip.h).
+// Part of the one translation unit of plastid_counts.hip (behind sam_decoder.hip.h; the plumbing is device_util.hip.h).
 #include "track_kernels.hip.h"
 
 struct pc_track {
